@@ -8,14 +8,18 @@ the C boundary (libnntoolkitcore_hip.so, device-pointer entry points).  Default 
       -> LSTM(512, v2) -> TimeDistributedDense(1000)
 with 512 utterances x 1000 frames PER GPU (weak scaling: 8 GPUs = the named batch 4096).
 Other BASELINE configs are selectable with --workload {spectrogram,conv,gru} for the
-per-kernel roofline lines in BASELINE.md / DESIGN.md.
+per-kernel roofline lines in BASELINE.md / DESIGN.md (with --full).
 
 Contract: W untimed warm-up steps, then exactly K timed steps bracketed by barrier +
 torch.cuda.synchronize() on both sides, MAX over ranks, rank 0 prints ONE JSON line.
 Inputs are resident in HBM before the timed region.  `value` = whole-job frames/s.
-`roofline` describes the dominant kernel from HIP-event timings taken inside this run;
-`cpu_baseline` times the CPU oracle (oracle/, a restatement of the reference's
+A plain run prints only what the timed steps measured.  With --full the line also holds
+`roofline`, the dominant kernel from HIP-event timings taken inside this run, and
+`cpu_baseline`, which times the CPU oracle (oracle/, a restatement of the reference's
 single-threaded scalar path) on a bounded sample of the same workload, rank 0, N=1 only.
+--dump-outputs DIR writes what the last timed step computed (rank 0's output tensor, or a
+fixed seeded sample of its frames when it is larger than 32 MiB) as DIR/<workload>_out.npy;
+inputs and weights are seeded, so the same arguments give the same inputs on every run.
 
 Multi-GPU: one process per GPU.  Under a launcher (torch.distributed.run sets RANK / LOCAL_RANK /
 WORLD_SIZE / MASTER_*) this file is a rank.  Run bare as `python bench.py --gpus N` with N > 1 it
@@ -55,7 +59,10 @@ def parse():
     ap.add_argument("--batch-per-gpu", type=int, default=0, help="utterances per GPU (0 = the BASELINE shape)")
     ap.add_argument("--frames", type=int, default=1000)
     ap.add_argument("--conv-stride", type=int, default=1, help="stride of the conv workload's Conv1d (2 = the sub-sampling front end; not a BASELINE config)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU oracle timing")
+    ap.add_argument("--full", action="store_true", help="also the roofline line and the CPU oracle baseline (off by default)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's output (float32; a fixed seeded sample of frames above 32 MiB) as DIR/<workload>_out.npy")
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--dry-run", action="store_true",
                     help="launcher rehearsal on the CPU (gloo): rendezvous + all_gather of the rank ids, no GPU work, "
@@ -279,9 +286,28 @@ class Workload:
                 mark("gru_stack2")
         return ev
 
+    def output(self):
+        """The tensor a caller of the timed path receives (every step overwrites it)."""
+        return getattr(self, {"stack": "tdd_out", "spectrogram": "spec_out", "conv": "conv_out", "gru": "h2"}[self.name])
+
     def destroy(self):
         for l in self.layers:
             l.destroy()
+
+
+DUMP_BYTES = 32 << 20
+
+
+def dump_outputs(wl, path, seed):
+    """Writes wl's output as float32 DIR/<workload>_out.npy: whole when it fits in DUMP_BYTES, otherwise as many of its
+    rows (one row = one frame's channels) as fit, drawn with `seed` and kept in ascending order, shape [rows, channels]."""
+    y = wl.output()
+    if y.numel() * 4 > DUMP_BYTES:
+        y = y.reshape(-1, y.shape[-1])
+        rows = np.sort(np.random.default_rng(seed).choice(y.shape[0], DUMP_BYTES // (4 * y.shape[1]), replace=False))
+        y = y.index_select(0, wl.torch.from_numpy(rows).to(y.device))
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, wl.name + "_out.npy"), y.float().cpu().numpy())
 
 
 def pmc_traffic(kernel_prefix, B):
@@ -636,6 +662,8 @@ def main():
     barrier()
     dt = time.perf_counter() - t0
     check_device_status("after the timed steps")
+    if a.dump_outputs and rank == 0:
+        dump_outputs(wl, a.dump_outputs, a.seed)
     crcs = [weights_crc]
     rank_ms = [dt_own / a.steps * 1e3]
     if dist is not None:
@@ -715,9 +743,10 @@ def main():
         "rank_ms_per_step": {"min": round(min(rank_ms), 4), "max": round(max(rank_ms), 4), "per_rank": [round(v, 4) for v in rank_ms]},
     }
     if rank == 0:
-        out["roofline"] = roofline_for(wl, phase_ms, prof)
-        if world == 1 and not a.no_cpu_baseline:
-            out["cpu_baseline"] = cpu_baseline(a.workload, weights, frames, a.seed)
+        if a.full:
+            out["roofline"] = roofline_for(wl, phase_ms, prof)
+            if world == 1 and not a.no_cpu_baseline:
+                out["cpu_baseline"] = cpu_baseline(a.workload, weights, frames, a.seed)
         print(json.dumps(out), flush=True)
     wl.destroy()
     if dist is not None:

@@ -76,6 +76,33 @@ def test_parent_never_imports_torch_before_forking_ranks():
     assert "import torch" not in head
 
 
+def test_dump_outputs_writes_small_outputs_whole_and_samples_large_ones(tmp_path):
+    import torch
+    import bench
+
+    class Fake:
+        def __init__(self, name, y):
+            self.name, self.y, self.torch = name, y, torch
+
+        def output(self):
+            return self.y
+
+    small = torch.arange(2 * 3 * 5, dtype=torch.float32).reshape(2, 3, 5)
+    bench.dump_outputs(Fake("conv", small), str(tmp_path / "a"), 1)
+    got = np.load(tmp_path / "a" / "conv_out.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, small.numpy())
+    # larger than the budget: a seeded sample of rows (frames), the same on every call, each row intact
+    big = torch.randn(9, 1000, 1000, generator=torch.Generator().manual_seed(0))
+    for d in ("b", "c"):
+        bench.dump_outputs(Fake("stack", big), str(tmp_path / d), 1)
+    b, c = np.load(tmp_path / "b" / "stack_out.npy"), np.load(tmp_path / "c" / "stack_out.npy")
+    assert b.dtype == np.float32 and b.nbytes <= bench.DUMP_BYTES and b.shape == (bench.DUMP_BYTES // 4000, 1000)
+    assert np.array_equal(b, c)
+    flat = big.reshape(-1, 1000).numpy()
+    rows = [int(np.flatnonzero((flat[:, :4] == r[:4]).all(axis=1))[0]) for r in b[:50]]
+    assert rows == sorted(rows) and all(np.array_equal(flat[i], r) for i, r in zip(rows, b))
+
+
 # ------------------------------------------------------------------ GPU ---
 
 def _backend_env():
@@ -86,7 +113,7 @@ def _backend_env():
 @pytest.mark.gpu
 def test_bench_gpus_2_runs_the_device_pipeline_on_two_ranks(gpu):
     args = [sys.executable, BENCH, "--gpus", "2", "--batch-per-gpu", "64", "--frames", "40", "--steps", "2", "--warmup", "1",
-            "--no-cpu-baseline"]
+            "--full", "--no-cpu-baseline"]
     r = _run(args, env=_backend_env())
     assert r.returncode == 0, r.stderr[-3000:]
     lines = _json_lines(r.stdout)
@@ -97,11 +124,31 @@ def test_bench_gpus_2_runs_the_device_pipeline_on_two_ranks(gpu):
     assert out["roofline"]["kernel"].startswith(("rec_", "lstm_rr_kernel", "gru_rr_kernel"))
     assert out["rank_ms_per_step"]["min"] > 0 and len(out["rank_ms_per_step"]["per_rank"]) == 2
     # the N=1 line keeps its shape
-    r1 = _run([sys.executable, BENCH, "--batch-per-gpu", "64", "--frames", "40", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"])
+    r1 = _run([sys.executable, BENCH, "--batch-per-gpu", "64", "--frames", "40", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline"])
     assert r1.returncode == 0, r1.stderr[-3000:]
     one = _json_lines(r1.stdout)[0]
     assert one["n_gpus"] == 1 and one["config"]["ranks_seen"] == [0]
     assert set(one) == set(out)
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_is_lean_and_dumps_the_same_outputs_every_run(gpu, tmp_path):
+    """A plain run times its steps and prints the headline, nothing measured on the side; --dump-outputs writes the last
+    timed step's output, and two runs with the same arguments write the same numbers."""
+    args = [sys.executable, BENCH, "--batch-per-gpu", "64", "--frames", "40", "--steps", "3", "--warmup", "1"]
+    outs = []
+    for d in ("a", "b"):
+        r = _run(args + ["--dump-outputs", str(tmp_path / d)])
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = _json_lines(r.stdout)
+        assert len(lines) == 1, r.stdout
+        outs.append(lines[0])
+    one = outs[0]
+    assert one["steps"] == 3 and one["ms_per_step"] > 0 and one["value"] > 0 and one["unit"] == "frames/s"
+    assert "roofline" not in one and "cpu_baseline" not in one
+    a, b = np.load(tmp_path / "a" / "stack_out.npy"), np.load(tmp_path / "b" / "stack_out.npy")
+    assert a.dtype == np.float32 and a.shape == (64, one["config"]["frames_per_utterance"] - 4, 1000)
+    assert np.isfinite(a).all() and np.array_equal(a, b)
 
 
 _WORKER = r"""

@@ -10,28 +10,28 @@ cd $R
 PART=${2:-all}
 if [ "$PART" != prof ]; then
 for w in stack gru conv spectrogram; do
-  timeout -k 10 300 python bench.py --workload $w > $O/bench_$w.json 2> $O/bench_$w.err; tail -c 300 $O/bench_$w.json; echo
+  timeout -k 10 300 python bench.py --full --workload $w > $O/bench_$w.json 2> $O/bench_$w.err; tail -c 300 $O/bench_$w.json; echo
 done
-NNTK_GEMM_SPLIT_BF16=0 timeout -k 10 300 python bench.py --workload conv --no-cpu-baseline > $O/bench_conv_exact.json 2> $O/bench_conv_exact.err; tail -c 300 $O/bench_conv_exact.json; echo
-NNTK_GEMM_SPLIT_BF16=0 timeout -k 10 300 python bench.py --no-cpu-baseline > $O/bench_stack_exact.json 2> $O/bench_stack_exact.err; tail -c 300 $O/bench_stack_exact.json; echo
+NNTK_GEMM_SPLIT_BF16=0 timeout -k 10 300 python bench.py --full --workload conv --no-cpu-baseline > $O/bench_conv_exact.json 2> $O/bench_conv_exact.err; tail -c 300 $O/bench_conv_exact.json; echo
+NNTK_GEMM_SPLIT_BF16=0 timeout -k 10 300 python bench.py --full --no-cpu-baseline > $O/bench_stack_exact.json 2> $O/bench_stack_exact.err; tail -c 300 $O/bench_stack_exact.json; echo
 timeout -k 10 300 python tools/split_error.py 2>&1 | grep -v amdgpu.ids > $O/split_error.log; timeout -k 10 200 python tools/split_error.py --stress 2>&1 | grep -v amdgpu.ids >> $O/split_error.log; echo split_error $?
 timeout -k 10 300 python tools/conv_probe.py gemm_split_bf16=0,1 2>&1 | grep -v amdgpu.ids > $O/conv_probe_ab.log; cat $O/conv_probe_ab.log
 timeout -k 10 300 python tools/train_bench.py 2>&1 | grep -v amdgpu.ids > $O/train_bench.log; cat $O/train_bench.log
 timeout -k 10 300 python tools/rr_repeat_check.py 40 2>&1 | grep -v amdgpu.ids > $O/rr_repeat_check.log; tail -1 $O/rr_repeat_check.log
 timeout -k 10 300 python tools/rec_ab.py 1024 500 2>&1 | grep -v amdgpu.ids > $O/rec_ab.log; cat $O/rec_ab.log
-NNTK_REC_FUSED2=1 timeout -k 10 300 python bench.py --workload gru --no-cpu-baseline > $O/bench_gru_fused.json 2> /dev/null; tail -c 200 $O/bench_gru_fused.json; echo
+NNTK_REC_FUSED2=1 timeout -k 10 300 python bench.py --full --workload gru --no-cpu-baseline > $O/bench_gru_fused.json 2> /dev/null; tail -c 200 $O/bench_gru_fused.json; echo
 # the two-f16-image kernels: race detector at the full grid, the 256-wide-input instantiation against the exact kernels, the contraction microbenchmark
 timeout -k 10 300 python tools/hf_soak.py 8 2>&1 | grep -v amdgpu.ids > $O/hf_soak.log; tail -1 $O/hf_soak.log
 timeout -k 10 200 python tools/hf_wide_time.py 2>&1 | grep -v amdgpu.ids > $O/hf_wide_time.log; cat $O/hf_wide_time.log
 # north_star's own batch on ONE GPU (4096 utterances = 8 back-to-back launches of the 256-workgroup LSTM kernel), and the round-3 route
-timeout -k 10 300 python bench.py --batch-per-gpu 4096 --steps 3 --warmup 1 --no-cpu-baseline > $O/bench_stack_b4096.json 2> $O/bench_stack_b4096.err; tail -c 300 $O/bench_stack_b4096.json; echo
+timeout -k 10 300 python bench.py --full --batch-per-gpu 4096 --steps 3 --warmup 1 --no-cpu-baseline > $O/bench_stack_b4096.json 2> $O/bench_stack_b4096.err; tail -c 300 $O/bench_stack_b4096.json; echo
 # the LSTM -> dense seam on the frag3 form (six products; bit-identical to the f32 route) instead of the default FRAG2H form (three products)
-NNTK_DENSE_F16X2=0 timeout -k 10 300 python bench.py --no-cpu-baseline > $O/bench_stack_frag3route.json 2> /dev/null; tail -c 200 $O/bench_stack_frag3route.json; echo
-NNTK_BENCH_STACK_F32=1 NNTK_REC_XF=0 timeout -k 10 300 python bench.py --no-cpu-baseline > $O/bench_stack_f32route.json 2> /dev/null; tail -c 200 $O/bench_stack_f32route.json; echo
-NNTK_CONV_FLATK=0 timeout -k 10 300 python bench.py --workload conv --no-cpu-baseline > $O/bench_conv_chunked.json 2> /dev/null; tail -c 200 $O/bench_conv_chunked.json; echo
+NNTK_DENSE_F16X2=0 timeout -k 10 300 python bench.py --full --no-cpu-baseline > $O/bench_stack_frag3route.json 2> /dev/null; tail -c 200 $O/bench_stack_frag3route.json; echo
+NNTK_BENCH_STACK_F32=1 NNTK_REC_XF=0 timeout -k 10 300 python bench.py --full --no-cpu-baseline > $O/bench_stack_f32route.json 2> /dev/null; tail -c 200 $O/bench_stack_f32route.json; echo
+NNTK_CONV_FLATK=0 timeout -k 10 300 python bench.py --full --workload conv --no-cpu-baseline > $O/bench_conv_chunked.json 2> /dev/null; tail -c 200 $O/bench_conv_chunked.json; echo
 # the GRU pair with the full-K family off (both layers split-K: the round-4 default) and on for every shape it takes (layer 1 too)
-NNTK_REC_FK=0 timeout -k 10 300 python bench.py --workload gru --no-cpu-baseline > $O/bench_gru_fk0.json 2> /dev/null; tail -c 200 $O/bench_gru_fk0.json; echo
-NNTK_REC_FK=1 timeout -k 10 300 python bench.py --workload gru --no-cpu-baseline > $O/bench_gru_fk1.json 2> /dev/null; tail -c 200 $O/bench_gru_fk1.json; echo
+NNTK_REC_FK=0 timeout -k 10 300 python bench.py --full --workload gru --no-cpu-baseline > $O/bench_gru_fk0.json 2> /dev/null; tail -c 200 $O/bench_gru_fk0.json; echo
+NNTK_REC_FK=1 timeout -k 10 300 python bench.py --full --workload gru --no-cpu-baseline > $O/bench_gru_fk1.json 2> /dev/null; tail -c 200 $O/bench_gru_fk1.json; echo
 fi
 [ "$PART" = bench ] && { ls $O; exit 0; }
 cd /tmp && export TMPDIR=/tmp
