@@ -523,6 +523,32 @@ int bd_reverse_input_batch_device(const float *d_input, float *d_output, Recurre
 int bd_reverse_backward_batch_device(const float *d_input, float *d_output, RecurrentConfig config, int batch);
 int bd_merge_concat_device(const float *d_forward, const float *d_backward, float *d_output, RecurrentConfig config, int batch);
 int bd_merge_sum_device(const float *d_forward, const float *d_backward, float *d_output, RecurrentConfig config, int batch);
+/* ---- ragged batches and carried state (INTEGRATION.md "Ragged batches and chunked streaming") -----------------------------------
+ * T = the layer's timesteps, also the row stride of the [batch][T][in] input and the [batch][T][H] output.  Row b with L = lengths[b]
+ * (0 <= L <= T) runs its first L steps from h0[b] (c0[b]): return_sequences: out[b][t] = h_t for t < L, zeros for t >= L (as PyTorch's
+ * pad_packed_sequence); otherwise out[b] = h_L.  hT[b] = h_L, cT[b] = c_L (L = 0: h0[b] / c0[b], or zeros without them).  A row's result
+ * equals the stateful single-sequence recurrence (gru.c:189-204, lstm.c:241-268, rnn.c:144-166) on x[b][:L] from that state.
+ * lengths: HOST memory, [batch], or NULL for all T; checked before anything is enqueued (-1 and nntk_last_error() for a length outside
+ * [0, T] or batch < 0) and copied in stream order, so the array may be reused when the call returns.  Every state pointer may be NULL
+ * (zeros in, nothing out).  f32 only; device pointers and asynchrony as the *ApplyDevice calls.  Runs on the kernel family the layer's
+ * *ApplyDevice call takes (*KernelPlan: lstm_rr_kernel / gru_rr_kernel, *_fk_kernel, rec_persistent_kernel or the per-timestep kernels),
+ * with the same bits for every step a row runs.  Each 64-row batch tile runs to its own longest row. */
+int GRUApplyDeviceVarLen(GRU filter, const float *d_input /*[batch,T,in]*/, float *d_output, int batch,
+                         const int *lengths /*host [batch] or NULL*/, const float *d_h0 /*[batch,H] or NULL*/, float *d_hT /*[batch,H] or NULL*/);
+int RNNApplyDeviceVarLen(RNN filter, const float *d_input, float *d_output, int batch, const int *lengths,
+                         const float *d_h0, float *d_hT);
+int LSTMApplyDeviceVarLen(LSTM filter, const float *d_input, float *d_output, int batch, const int *lengths,
+                          const float *d_h0, const float *d_c0, float *d_hT, float *d_cT);
+/* the same on host memory (upload, device call, download) */
+int GRUApplyInferenceBatchVarLen(GRU filter, const float *input, float *output, int batch, const int *lengths,
+                                 const float *h0, float *hT);
+int RNNApplyInferenceBatchVarLen(RNN filter, const float *input, float *output, int batch, const int *lengths,
+                                 const float *h0, float *hT);
+int LSTMApplyInferenceBatchVarLen(LSTM filter, const float *input, float *output, int batch, const int *lengths,
+                                  const float *h0, const float *c0, float *hT, float *cT);
+/* bidirectional helpers for ragged rows: out[b][t] = in[b][lengths[b] - 1 - t] for t < lengths[b], zeros after (lengths: host) */
+int bd_reverse_input_batch_varlen_device(const float *d_input, float *d_output, RecurrentConfig config, int batch, const int *lengths);
+int bd_reverse_backward_batch_varlen_device(const float *d_input, float *d_output, RecurrentConfig config, int batch, const int *lengths);
 /* ---- frag3 tensors: activations already split for the split-bf16 x 3 contraction ---------------------------------------------
  * The default contraction of conv / dense / recurrent layers multiplies every f32 operand as three bf16 terms (x = hi + mid + lo,
  * exactly).  A FRAG3 tensor is a [batch][T][C] f32 tensor stored as those three images in MFMA fragment order:

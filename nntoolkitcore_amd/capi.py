@@ -116,6 +116,7 @@ class MelFilterBankConfig(C.Structure):
                 ("upper_hz", C.c_float)]
 
 
+ip = C.POINTER(C.c_int)
 WINDOW_FN = C.CFUNCTYPE(None, fp, C.c_int)
 ACT_IMPL_FN = C.CFUNCTYPE(None, vp, fp, fp, C.c_int)
 
@@ -354,6 +355,15 @@ SIGNATURES = {
     "TimeDistributedDenseApplyDeviceFrag3": (C.c_int, [vp, vp, vp, C.c_int]),
     "LSTMTimeDistributedDenseApplyDevice": (C.c_int, [vp, vp, vp, vp, C.c_int]),
     "RNNApplyDevice": (C.c_int, [vp, vp, vp, C.c_int]),
+    # ragged batches with carried state: lengths is a host int array (or NULL), the state pointers may be NULL
+    "GRUApplyDeviceVarLen": (C.c_int, [vp, vp, vp, C.c_int, ip, vp, vp]),
+    "RNNApplyDeviceVarLen": (C.c_int, [vp, vp, vp, C.c_int, ip, vp, vp]),
+    "LSTMApplyDeviceVarLen": (C.c_int, [vp, vp, vp, C.c_int, ip, vp, vp, vp, vp]),
+    "GRUApplyInferenceBatchVarLen": (C.c_int, [vp, fp, fp, C.c_int, ip, fp, fp]),
+    "RNNApplyInferenceBatchVarLen": (C.c_int, [vp, fp, fp, C.c_int, ip, fp, fp]),
+    "LSTMApplyInferenceBatchVarLen": (C.c_int, [vp, fp, fp, C.c_int, ip, fp, fp, fp, fp]),
+    "bd_reverse_input_batch_varlen_device": (C.c_int, [vp, vp, RecurrentConfig, C.c_int, ip]),
+    "bd_reverse_backward_batch_varlen_device": (C.c_int, [vp, vp, RecurrentConfig, C.c_int, ip]),
     "bd_reverse_input_batch_device": (C.c_int, [vp, vp, RecurrentConfig, C.c_int]),
     "bd_reverse_backward_batch_device": (C.c_int, [vp, vp, RecurrentConfig, C.c_int]),
     "bd_merge_concat_device": (C.c_int, [vp, vp, vp, RecurrentConfig, C.c_int]),

@@ -111,6 +111,10 @@ int nntk_shim_activation(int kind, float relu_a, int softmax_vector_size,
 /* ---- bidirectional helpers (layers/bidirectional.c): rows of [B, T, F] in reverse time order; row-wise
  *      concatenation [rows, C] | [rows, C] -> [rows, 2C]; elementwise sum */
 int nntk_shim_reverse_time(const float *d_in, float *d_out, long B, int T, int F);
+/* ragged rows: out[b][t] = in[b][len[b] - 1 - t] for t < len[b], zeros for t >= len[b] (d_len [B], device) */
+int nntk_shim_reverse_time_varlen(const float *d_in, float *d_out, const int *d_len, long B, int T, int F);
+/* n ints from host memory to the device, ordered on the stream; the host array may be reused when the call returns */
+int nntk_shim_upload_ints(int *d_dst, const int *h_src, long n);
 /* ---- training, second slice (train.hip): reference operation order throughout ---- */
 int nntk_shim_activation_grad(int kind, int vector_size, int vectors_per_call, const float *d_z, const float *d_a,
                               const float *d_dout, float *d_out, long n);
@@ -177,6 +181,14 @@ int nntk_shim_rnn(const float *d_xw, const float *d_ut, const float *d_bh, const
                   float *d_out, float *d_hT, float *d_work, int B, int T, int H,
                   int return_sequences, int act, float act_scale);
 size_t nntk_shim_recurrent_work_floats(int B, int H);
+/* per-row lengths on the exact-f32 kernels (the *VarLen calls; G = 1 RNN, 3 GRU, 4 LSTM): d_len = [B] lengths then [ceil(B / 64)]
+ * the maxima of the 64-row batch tiles, device memory; T_max = the largest length.  A row follows its first d_len[b] steps and
+ * then keeps its state (d_hT / d_cT, and d_out without sequences, = the state after d_len[b] steps); sequence outputs at
+ * t >= d_len[b] are unspecified until nntk_shim_varlen_zero_pad clears them. */
+int nntk_shim_rec_varlen(int G, const float *d_xw, const float *d_ut, const float *d_bh, const float *d_h0,
+                         const float *d_c0, float *d_out, float *d_hT, float *d_cT, float *d_work, int B, int T, int H,
+                         int return_sequences, const int *acts, const float *act_scales, const int *d_len, int T_max);
+int nntk_shim_varlen_zero_pad(float *d_out, const int *d_len, int B, int T, int H);
 int nntk_shim_gru(const float *d_xw, const float *d_ut, const float *d_bh,
                   const float *d_h0, float *d_out, float *d_hT, float *d_work,
                   int B, int T, int H, int return_sequences, const int acts[3], const float act_scales[3]);
@@ -212,6 +224,13 @@ int nntk_shim_lstm_rr_train_forward(const float *d_x, const float *d_img, const 
 int nntk_shim_lstm_rr(const float *d_x, const void *d_xf3, const float *d_img, const float *d_img4, const float *d_bi, const float *d_bh,
                       const float *d_h0, const float *d_c0, float *d_out, float *d_out_h2 /* frag2h form of the sequence output, or NULL; needs d_out == NULL */,
                       float *d_hseq, float *d_hT, float *d_cT, float *d_work, int B, int T, int in, int H, int return_sequences);
+
+/* per-row lengths on the same kernels (the *VarLen calls; cell 0 LSTM, 1 GRU with d_bi = d_b4 and d_bh NULL): d_len as nntk_shim_rec_varlen's;
+ * row b runs its first d_len[b] steps and keeps its state after them; same family choice and bits as nntk_shim_lstm_rr / _gru_rr for every
+ * step a row runs; 1 = not taken (nothing launched) */
+int nntk_shim_rr_varlen(int cell, const float *d_x, const void *d_xf3, const float *d_img, const float *d_img4, const float *d_bi,
+                        const float *d_bh, const float *d_h0, const float *d_c0, float *d_out, float *d_hseq, float *d_hT, float *d_cT,
+                        float *d_work, const int *d_len, int B, int T, int in, int H, int return_sequences);
 
 /* The HF instantiations of lstm_rr_kernel (H > 256): the h part of Z on two f16 images (three products per k step), the hand-off = the layer's
  * sequence output as a FRAG2H tensor (d_h2: nntk_shim_frag2h_floats(B, T, H) floats).  Zero initial state, x as a frag3 tensor.  Images:

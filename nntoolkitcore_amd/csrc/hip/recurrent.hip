@@ -40,6 +40,8 @@ struct RecParams {
     int B, H, Hj_p, Hk_p;
     int a0, a1, a2, a3, a4;   // activation kinds
     float s0, s1, s2, s3, s4; // ReLU output scales of those activations (activation_default.c:123-129), 1 otherwise
+    const int *len;       // VL: [B] per-row lengths
+    int t;                // VL: this launch's timestep
 };
 
 // NG = number of intra-workgroup split-K groups (256 threads each).  NG = 2 puts two
@@ -47,7 +49,8 @@ struct RecParams {
 // LDS reads / barrier wait / global prefetch are hidden behind them.  The two partial
 // accumulators are summed through LDS in a fixed order (group 0 + group 1), so results
 // do not depend on scheduling or on how the batch is sharded.
-template <int G, bool IS_LSTM, int NG>
+// VL: per-row lengths (the *VarLen calls): a row with t >= len[b] keeps its state -- h_next = h_prev, c untouched.
+template <int G, bool IS_LSTM, int NG, bool VL = false>
 __global__ __launch_bounds__(256 * NG) void rec_step_kernel(RecParams p) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     constexpr int A_SZ = REC_BM * REC_LS;
@@ -216,6 +219,14 @@ __global__ __launch_bounds__(256 * NG) void rec_step_kernel(RecParams p) {
     for (int rr = 0; rr < RPW; ++rr) {
         const int b = b0 + wave * 16 + q * 4 + grp * RPW + rr;
         if (b >= p.B) continue;
+        if constexpr (VL) {
+            if (p.t >= p.len[b]) {                    // past the row's length: the state stays
+                const float hp = p.h_prev[(size_t)b * p.H + j];
+                p.h_next[(size_t)b * p.H + j] = hp;
+                if (p.out) p.out[(size_t)b * p.out_ld + j] = hp;
+                continue;
+            }
+        }
         float hn;
         if constexpr (G == 1) {
             // rnn.c:144-166: gate = (h U [+ b_h]) + (x W + b_i); h' = act(gate)
@@ -295,6 +306,7 @@ struct RecPParams {
 #ifdef NNTK_REC_STAMPS
     unsigned long long *stamp;   // [2 halves][T][8] s_memtime of workgroup 0's leader waves (diagnostics build only)
 #endif
+    const int *len;                 // VL: [B] per-row lengths, followed by [ceil(B / 64)] the batch tiles' maxima
 };
 #ifdef NNTK_REC_STAMPS
 #define REC_STAMP(i) do { if (p.stamp && blockIdx.x == 0 && lane == 0) {                                               \
@@ -370,7 +382,9 @@ __device__ __forceinline__ float4 load4_sc1(__amdgpu_buffer_rsrc_t rsrc, int sof
 // STD = the gate activations are the standard ones (GRU: sigmoid / tanh / sigmoid, LSTM: sigmoid x3 +
 //   tanh x2): the kinds become compile-time constants and the gate phase -- pure VALU work that
 //   cannot overlap the MFMAs -- loses its 10 scalar branch ladders.
-template <int G, bool IS_LSTM, int NCH, int XW, bool PP, bool STD>
+// VL (the *VarLen calls): the batch tile runs its time loop to the longest of its rows (a scalar: every workgroup of the tile
+// and every wave agrees on it), and a row past its own length keeps its state (selected in the gates, no memory operation moves).
+template <int G, bool IS_LSTM, int NCH, int XW, bool PP, bool STD, bool VL = false>
 __global__ __launch_bounds__(512, 2) void rec_persistent_kernel(RecPParams p) {
     const int A0 = STD ? (G == 1 ? NNTK_ACT_TANH : NNTK_ACT_SIGMOID) : p.a0;
     const int A1 = STD ? (IS_LSTM ? NNTK_ACT_SIGMOID : NNTK_ACT_TANH) : p.a1;
@@ -461,7 +475,14 @@ __global__ __launch_bounds__(512, 2) void rec_persistent_kernel(RecPParams p) {
     __syncthreads();
 
     float hn_prev[2] = {0.f, 0.f};
-    for (int t = 0; t < p.T; ++t) {
+    int TL = p.T, len_b = 0;                      // steps this tile runs; VL: this lane's row length
+    if constexpr (VL) {
+        TL = __builtin_amdgcn_readfirstlane(p.len[p.B + (b0 >> 6)]);
+        len_b = row_ok ? p.len[b] : 0;
+        hn_prev[0] = (ok0 && p.h0) ? p.h0[(size_t)b * p.H + j] : 0.0f;
+        hn_prev[1] = (ok1 && p.h0) ? p.h0[(size_t)b * p.H + j + 1] : 0.0f;
+    }
+    for (int t = 0; t < TL; ++t) {
         float xwv[2][G];
 #define REC_XW_ISSUE() do {                                                                          \
             /* one 16-byte load per gate: the 4 hidden units of this lane's quad (both split-K waves  */ \
@@ -593,12 +614,14 @@ __global__ __launch_bounds__(512, 2) void rec_persistent_kernel(RecPParams p) {
         for (int e = 0; e < 2; ++e) {
             if constexpr (G == 1) {
                 hn[e] = nntk_gate_act(A0, xwv[e][0] + (fin[e][0] + bh[e][0]), S0);      // rnn.c:144-166
+                if constexpr (VL) hn[e] = t < len_b ? hn[e] : hn_prev[e];
             } else if constexpr (!IS_LSTM) {
                 const float hz = fin[e][0] + bh[e][0], hr = fin[e][1] + bh[e][1], hh = fin[e][2] + bh[e][2];
                 const float z = nntk_gate_act(A0, xwv[e][0] + hz, S0);
                 const float rg = nntk_gate_act(A2, xwv[e][1] + hr, S2);
                 const float ht = nntk_gate_act(A1, fmaf(rg, hh, xwv[e][2]), S1);
                 hn[e] = fmaf(-z + 1.0f, ht, z * prev[e]);
+                if constexpr (VL) hn[e] = t < len_b ? hn[e] : prev[e];
                 prev[e] = hn[e];
             } else {
                 const float zi = xwv[e][0] + (fin[e][0] + bh[e][0]);
@@ -610,8 +633,14 @@ __global__ __launch_bounds__(512, 2) void rec_persistent_kernel(RecPParams p) {
                 const float gg = nntk_gate_act(A2, zg, S2);
                 const float og = nntk_gate_act(A3, zo, S3);
                 const float cn = fmaf(fg, prev[e], ig * gg);
+                if constexpr (VL) {
+                    const bool live = t < len_b;
+                    hn[e] = live ? og * nntk_gate_act(A4, cn, S4) : hn_prev[e];
+                    prev[e] = live ? cn : prev[e];
+                } else {
                 prev[e] = cn;
                 hn[e] = og * nntk_gate_act(A4, cn, S4);
+                }
             }
         }
         // ---- publish h_t (write-through), then this wave's arrival; the layer output
@@ -645,7 +674,7 @@ __global__ __launch_bounds__(512, 2) void rec_persistent_kernel(RecPParams p) {
         }
         REC_STAMP(7);
         if (XW == 0) {
-            if (p.return_sequences || t == p.T - 1) {
+            if (p.return_sequences || t == TL - 1) {
                 float *o = p.return_sequences ? p.out + ((size_t)b * p.T + t) * p.H + j : p.out + (size_t)b * p.H + j;
                 if (pair8 && ok1) *reinterpret_cast<float2 *>(o) = make_float2(hn[0], hn[1]);
                 else { if (ok0) o[0] = hn[0]; if (ok1) o[1] = hn[1]; }
@@ -653,8 +682,9 @@ __global__ __launch_bounds__(512, 2) void rec_persistent_kernel(RecPParams p) {
         }
         hn_prev[0] = hn[0]; hn_prev[1] = hn[1];
     }
-    if (XW != 0) {   // output of the last step (the only one when !return_sequences)
-        float *o = p.return_sequences ? p.out + ((size_t)b * p.T + (p.T - 1)) * p.H + j : p.out + (size_t)b * p.H + j;
+    // output of the last step (the only one when !return_sequences); VL, a tile of empty rows: h_0 when !return_sequences
+    if (XW != 0 ? (!VL || TL > 0 || !p.return_sequences) : (VL && TL == 0 && !p.return_sequences)) {
+        float *o = p.return_sequences ? p.out + ((size_t)b * p.T + (TL - 1)) * p.H + j : p.out + (size_t)b * p.H + j;
         if (pair8 && ok1) *reinterpret_cast<float2 *>(o) = make_float2(hn_prev[0], hn_prev[1]);
         else { if (ok0) o[0] = hn_prev[0]; if (ok1) o[1] = hn_prev[1]; }
     }
@@ -1242,7 +1272,12 @@ extern "C" size_t nntk_shim_recurrent_work_floats(int B, int H) {
 template <int G, bool IS_LSTM>
 static int run_recurrent(const float *d_xw, const float *d_ut, const float *d_bh, const float *d_h0,
                          const float *d_c0, float *d_out, float *d_hT, float *d_cT, float *d_work,
-                         int B, int T, int H, int return_sequences, const int *acts, const float *scales, int nacts) {
+                         int B, int T, int H, int return_sequences, const int *acts, const float *scales, int nacts,
+                         const int *d_len = nullptr, int T_max = 0) {
+    // d_len (the *VarLen calls): [B] row lengths then [ceil(B / 64)] batch-tile maxima, device memory; T_max = their maximum.
+    // T stays the layout stride of xw / out; the time loop stops at the lengths
+    const bool vl = d_len != nullptr;
+    const int T_run = vl ? T_max : T;
     for (int i = 0; i < nacts; ++i)
         if (!act_ok(acts[i]))
             return nntk_fail_msg("recurrent: gate activation must be one of the built-in identity/sigmoid/tanh/relu");
@@ -1288,14 +1323,25 @@ static int run_recurrent(const float *d_xw, const float *d_ut, const float *d_bh
             // must carry >= 36 groups of 4 MFMAs per wave for the alternation to pay
             const bool pp = std_acts && nch_p >= 12 && G * nch_p >= 36 && opt.rec_pingpong != 0;
             if (xwm < 0) xwm = pp ? 0 : 1;      // measured: ping-pong LSTM-512 11.8 (XW 0) vs 13.1 ms; classic GRU-256 7.82 vs 7.63 (XW 1)
-#define REC_PICK(N) (!std_acts ? rec_persistent_kernel<G, IS_LSTM, N, 0, false, false> \
-                     : xwm == 1 ? rec_persistent_kernel<G, IS_LSTM, N, 1, false, true> : rec_persistent_kernel<G, IS_LSTM, N, 0, false, true>)
-            if (pp && nch_p == 12) kern = xwm == 1 ? rec_persistent_kernel<G, IS_LSTM, 12, 1, true, true> : rec_persistent_kernel<G, IS_LSTM, 12, 0, true, true>;
-            else if (pp)          kern = xwm == 1 ? rec_persistent_kernel<G, IS_LSTM, 16, 1, true, true> : rec_persistent_kernel<G, IS_LSTM, 16, 0, true, true>;
-            else if (nch_p == 4)  kern = REC_PICK(4);
-            else if (nch_p == 8)  kern = REC_PICK(8);
-            else if (nch_p == 12) kern = REC_PICK(12);
-            else                  kern = REC_PICK(16);
+#define REC_PICK(N, V) (!std_acts ? rec_persistent_kernel<G, IS_LSTM, N, 0, false, false, V> \
+                     : xwm == 1 ? rec_persistent_kernel<G, IS_LSTM, N, 1, false, true, V> : rec_persistent_kernel<G, IS_LSTM, N, 0, false, true, V>)
+#define REC_PICK_PP(N, V) (xwm == 1 ? rec_persistent_kernel<G, IS_LSTM, N, 1, true, true, V> : rec_persistent_kernel<G, IS_LSTM, N, 0, true, true, V>)
+            if (vl) {
+                if (pp && nch_p == 12) kern = REC_PICK_PP(12, true);
+                else if (pp)          kern = REC_PICK_PP(16, true);
+                else if (nch_p == 4)  kern = REC_PICK(4, true);
+                else if (nch_p == 8)  kern = REC_PICK(8, true);
+                else if (nch_p == 12) kern = REC_PICK(12, true);
+                else                  kern = REC_PICK(16, true);
+            }
+            else if (pp && nch_p == 12) kern = REC_PICK_PP(12, false);
+            else if (pp)          kern = REC_PICK_PP(16, false);
+            else if (nch_p == 4)  kern = REC_PICK(4, false);
+            else if (nch_p == 8)  kern = REC_PICK(8, false);
+            else if (nch_p == 12) kern = REC_PICK(12, false);
+            else                  kern = REC_PICK(16, false);
+#undef REC_PICK
+#undef REC_PICK_PP
             if (nntk_set_max_dynamic_lds((const void *)kern, lds)) return -1;
             // every workgroup of a launch must be resident: the grid comes from the runtime's occupancy answer for THIS
             // kernel at THIS LDS size (one per CU by design), not from the bare CU count
@@ -1319,6 +1365,7 @@ static int run_recurrent(const float *d_xw, const float *d_ut, const float *d_bh
             q.s0 = p.s0; q.s1 = p.s1; q.s2 = p.s2; q.s3 = p.s3; q.s4 = p.s4;
             q.fault = fault;
             q.spin_ticks = (unsigned long long)(opt.rec_spin_us > 0 ? opt.rec_spin_us : 0) * 100ull;     // s_memrealtime: 100 MHz; 0 = inject a fault
+            q.len = d_len;
             const int ncnt = pp ? 2 : 1;      // arrival counters per batch tile
 #ifdef NNTK_REC_STAMPS
             q.stamp = nullptr;
@@ -1372,21 +1419,31 @@ static int run_recurrent(const float *d_xw, const float *d_ut, const float *d_bh
     if (ng == 2 && lds2 > 64 * 1024) {
         if (nntk_set_max_dynamic_lds((const void *)rec_step_kernel<G, IS_LSTM, 2>, lds2)) return -1;
     }
+    if (vl && ng == 2 && lds2 > 64 * 1024) {
+        if (nntk_set_max_dynamic_lds((const void *)rec_step_kernel<G, IS_LSTM, 2, true>, lds2)) return -1;
+    }
+    p.len = d_len;
     const int span = nntk_prof_span_begin(NNTK_SPAN_REC);
-    for (int t = 0; t < T; ++t) {
+    for (int t = 0; t < T_run; ++t) {
         p.xw = d_xw + (size_t)t * B * G * H;
         p.h_prev = hbuf[t & 1];
         p.h_next = hbuf[(t + 1) & 1];
+        p.t = t;
         if (return_sequences) { p.out = d_out + (size_t)t * H; p.out_ld = (long)T * H; }
-        else if (t == T - 1)  { p.out = d_out; p.out_ld = H; }
+        else if (t == T_run - 1) { p.out = d_out; p.out_ld = H; }
         else                  { p.out = nullptr; p.out_ld = 0; }
-        if (ng == 2) hipLaunchKernelGGL((rec_step_kernel<G, IS_LSTM, 2>), grid, dim3(512), lds2, nntk_stream(), p);
+        if (vl) {
+            if (ng == 2) hipLaunchKernelGGL((rec_step_kernel<G, IS_LSTM, 2, true>), grid, dim3(512), lds2, nntk_stream(), p);
+            else         hipLaunchKernelGGL((rec_step_kernel<G, IS_LSTM, 1, true>), grid, dim3(256), lds1, nntk_stream(), p);
+        } else if (ng == 2) hipLaunchKernelGGL((rec_step_kernel<G, IS_LSTM, 2>), grid, dim3(512), lds2, nntk_stream(), p);
         else         hipLaunchKernelGGL((rec_step_kernel<G, IS_LSTM, 1>), grid, dim3(256), lds1, nntk_stream(), p);
     }
-    nntk_prof_span_end(span, T, T);
+    nntk_prof_span_end(span, T_run, T_run);
     NNTK_LAUNCH_CHECK("rec_step_kernel");
     nntk_set_last_rec_kernel(G == 1 ? "rec_step_kernel<1,RNN>" : IS_LSTM ? "rec_step_kernel<4,LSTM>" : "rec_step_kernel<3,GRU>");
-    if (d_hT) { if (nntk_shim_copy_d2d(d_hT, hbuf[T & 1], BH * 4)) return -1; }
+    // (VL, every row empty: the final state is h_0, and so is the output of a layer without sequences)
+    if (vl && T_run == 0 && !return_sequences) { if (nntk_shim_copy_d2d(d_out, hbuf[0], BH * 4)) return -1; }
+    if (d_hT) { if (nntk_shim_copy_d2d(d_hT, hbuf[T_run & 1], BH * 4)) return -1; }
     if (IS_LSTM && d_cT) { if (nntk_shim_copy_d2d(d_cT, cbuf, BH * 4)) return -1; }
     return 0;
 }
@@ -1407,6 +1464,46 @@ extern "C" int nntk_shim_rnn(const float *d_xw, const float *d_ut, const float *
     const float scales[1] = {act_scale};
     return run_recurrent<1, false>(d_xw, d_ut, d_bh, d_h0, nullptr, d_out, d_hT, nullptr, d_work, B, T, H,
                                    return_sequences, acts, scales, 1);
+}
+
+// per-row lengths (the *VarLen calls): d_len = [B] lengths, then [ceil(B / 64)] the maxima of the 64-row batch tiles (device
+// memory); T_max = the largest length.  Row b follows its first d_len[b] steps and then keeps its state: d_hT / d_cT and the
+// output of a layer without sequences hold the state after d_len[b] steps; sequence outputs at t >= d_len[b] are unspecified
+// (nntk_shim_varlen_zero_pad clears them).  Same kernels and same bits as the calls above for every step a row runs.
+extern "C" int nntk_shim_rec_varlen(int G, const float *d_xw, const float *d_ut, const float *d_bh, const float *d_h0,
+                                    const float *d_c0, float *d_out, float *d_hT, float *d_cT, float *d_work, int B, int T, int H,
+                                    int return_sequences, const int *acts, const float *act_scales, const int *d_len, int T_max) {
+    if (B <= 0 || T <= 0) return 0;
+    if (!d_len || T_max < 0 || T_max > T) return nntk_fail_msg("rec_varlen: bad lengths");
+    if (G == 1) return run_recurrent<1, false>(d_xw, d_ut, d_bh, d_h0, nullptr, d_out, d_hT, nullptr, d_work, B, T, H,
+                                               return_sequences, acts, act_scales, 1, d_len, T_max);
+    if (G == 3) return run_recurrent<3, false>(d_xw, d_ut, d_bh, d_h0, nullptr, d_out, d_hT, nullptr, d_work, B, T, H,
+                                               return_sequences, acts, act_scales, 3, d_len, T_max);
+    return run_recurrent<4, true>(d_xw, d_ut, d_bh, d_h0, d_c0, d_out, d_hT, d_cT, d_work, B, T, H,
+                                  return_sequences, acts, act_scales, 5, d_len, T_max);
+}
+
+// out[b][t][:] = 0 for t >= len[b]: the padding of a *VarLen call's sequence output (pad_packed_sequence's zeros); one wavefront
+// per (b, t) row, only padding rows are written
+__global__ __launch_bounds__(256) void varlen_zero_pad_kernel(float *out, const int *len, long B, int T, int H) {
+    const long rows = B * T;
+    const long wave = (blockIdx.x * (long)blockDim.x + threadIdx.x) >> 6;
+    const long nwaves = ((long)gridDim.x * blockDim.x) >> 6;
+    const int lane = threadIdx.x & 63;
+    for (long r = wave; r < rows; r += nwaves) {
+        const long b = r / T;
+        const int t = (int)(r % T);
+        if (t < len[b]) continue;
+        for (int j = lane; j < H; j += 64) out[r * H + j] = 0.0f;
+    }
+}
+extern "C" int nntk_shim_varlen_zero_pad(float *d_out, const int *d_len, int B, int T, int H) {
+    if (B <= 0 || T <= 0 || H <= 0) return 0;
+    long g = ((long)B * T * 64 + 255) / 256;
+    if (g > 4096) g = 4096;
+    hipLaunchKernelGGL(varlen_zero_pad_kernel, dim3((unsigned)g), dim3(256), 0, nntk_stream(), d_out, d_len, (long)B, T, H);
+    NNTK_LAUNCH_CHECK("varlen_zero_pad_kernel");
+    return 0;
 }
 
 extern "C" int nntk_shim_lstm(const float *d_xw, const float *d_ut, const float *d_bh, const float *d_h0,

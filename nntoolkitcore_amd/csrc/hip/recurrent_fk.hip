@@ -164,7 +164,9 @@ __global__ __launch_bounds__(256) void fk_pack_kernel(const float *__restrict__ 
 // NKH / NKX: k steps (of 16) of the h / x part the kernel is compiled for (multiples of NW; H <= 16 NKH, in <= 16 NKX, zero padded).
 // CELL 0: LSTM (slots i | f | g | o); 1: GRU (slots z | r | h.U_h | x.W_h, recurrent.c gru_rr_build_image).
 // NW: wavefronts sharing an operand (see above); ND: staging sets = groups of k steps requested ahead.
-template <int NKH, int NKX, int CELL, int NW, int ND>
+// VL (the *VarLen calls): per-row lengths, as in recurrent_rr.hip -- the workgroup runs its time loop to the longest row of its 64-row batch
+// tile (a scalar), and a lane past its row's length keeps its state (selected in fin_unit: the published, stored and final values are frozen)
+template <int NKH, int NKX, int CELL, int NW, int ND, bool VL = false>
 __device__ __forceinline__ void fk_body(const RRParams &p) {
     constexpr int NMR = NKH <= 16 ? 3 : 2;            // images of U kept in registers
     constexpr int NMW = NW == 4 && NKX > 8 ? 1 : 0;   // images of W kept in registers
@@ -204,10 +206,13 @@ __device__ __forceinline__ void fk_body(const RRParams &p) {
     const int ct = blockIdx.x / p.NBT;
     const int ht_abs = p.b_base / 32 + bt * NHF + hf;
     const int b0 = p.b_base + bt * 32 * NHF;
-    const int H = p.H, T = p.T;
+    const int H = p.H;
+    // steps the workgroup runs (p.T stays the layout stride; T is a step count everywhere below)
+    const int T = VL ? __builtin_amdgcn_readfirstlane(p.len[p.B + (b0 >> 6)]) : p.T;
     const int NKS = H >> 4;
     const int rows_valid = p.B - b0 < 32 * NHF ? p.B - b0 : 32 * NHF;
     const int gi = NW * ct + ug;                     // this wavefront's group of 8 hidden units
+    if (VL && T == 0) { rr_vl_pass_state(p, b0, 32 * NHF, 8 * NW * ct, 8 * NW, CELL == 0); return; }
     const bool grp_ok = 8 * gi < H;                  // (H % 16 == 0: a group is inside or outside as a whole)
 
     // ---- resident operands ----
@@ -250,6 +255,17 @@ __device__ __forceinline__ void fk_body(const RRParams &p) {
         const int row = b0 + hf * 32 + n;
 #pragma unroll
         for (int e = 0; e < 4; ++e) cst[e] = (p.c0 && row < p.B && jf + e < H) ? p.c0[(size_t)row * H + jf + e] : 0.0f;
+    }
+    // VL: this lane's row length, and (LSTM) the h it keeps past it
+    int vlen = 0;
+    float hkeep[VL && CELL == 0 ? 4 : 1];
+    if constexpr (VL) {
+        const int row = b0 + hf * 32 + n;
+        vlen = row < p.B ? p.len[row] : 0;
+        if constexpr (CELL == 0) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) hkeep[e] = (p.h0 && row < p.B && jf + e < H) ? p.h0[(size_t)row * H + jf + e] : 0.0f;
+        }
     }
     // ---- descriptors and offsets ----
     const int hb_bytes = (int)p.hstep;
@@ -401,7 +417,7 @@ __device__ __forceinline__ void fk_body(const RRParams &p) {
     //      them): FIN_G x groups carry one or more units each, the last of them the stores ----
     float hn[4];
     rr_v4u olast = {0u, 0u, 0u, 0u};
-    auto fin_unit = [&](int e, const f32x16 &acc) __attribute__((always_inline)) {
+    auto fin_unit = [&](int e, const f32x16 &acc, int t) __attribute__((always_inline)) {
         if (RR_DBG(2)) return;
         float zc[4];
 #pragma unroll
@@ -413,6 +429,7 @@ __device__ __forceinline__ void fk_body(const RRParams &p) {
             const float rg = nntk_fast_sigmoid(zc[1]);
             const float ht = nntk_fast_tanh(fmaf(rg, zc[2], zc[3]));
             hn[e] = fmaf(-zg + 1.0f, ht, zg * cst[e]);
+            if constexpr (VL) hn[e] = t < vlen ? hn[e] : cst[e];
             cst[e] = hn[e];
         } else {
             // lstm.c:201-238: Z = xW + b_i + hU (+ b_h); blocks i | f | g | o
@@ -421,8 +438,15 @@ __device__ __forceinline__ void fk_body(const RRParams &p) {
             const float gg = nntk_fast_tanh(zc[2]);
             const float og = nntk_fast_sigmoid(zc[3]);
             const float cn = fmaf(fg, cst[e], ig * gg);
+            if constexpr (VL) {
+                const bool live = t < vlen;
+                hn[e] = live ? og * nntk_fast_tanh(cn) : hkeep[e];
+                cst[e] = live ? cn : cst[e];
+                hkeep[e] = hn[e];
+            } else {
             cst[e] = cn;
             hn[e] = og * nntk_fast_tanh(cn);
+            }
         }
     };
     auto fin_store = [&](int t) __attribute__((always_inline)) {
@@ -618,7 +642,7 @@ __device__ __forceinline__ void fk_body(const RRParams &p) {
             if (fin_here) {
 #pragma unroll
                 for (int e = 0; e < 4; ++e)
-                    if (e * FIN_G / 4 == gx) fin_unit(e, acc);
+                    if (e * FIN_G / 4 == gx) fin_unit(e, acc, t);
                 if (gx == FIN_G - 1) fin_store(t);
 #pragma unroll
                 for (int k = 0; k < 6 * (NW - 1); ++k) {
@@ -641,7 +665,7 @@ __device__ __forceinline__ void fk_body(const RRParams &p) {
                 // the finish as one piece between the h part and the x part.  (Sliced between the x part's MFMAs -- FK_FIN_SLICED -- it was
                 // measured SLOWER: one wavefront per SIMD is bound by its instruction issue, not by the pipe: profiles/r05_fk_*.log)
 #pragma unroll
-                for (int e = 0; e < 4; ++e) fin_unit(e, acc);
+                for (int e = 0; e < 4; ++e) fin_unit(e, acc, t);
                 fin_store(t);
                 FK_STAMP(t, 33);
                 __builtin_amdgcn_sched_barrier(0);
@@ -685,10 +709,10 @@ __device__ __forceinline__ void fk_body(const RRParams &p) {
         }
     }
 }
-template <int NKH, int NKX, int NW, int ND>
-__global__ __launch_bounds__(256) void lstm_fk_kernel(RRParams p) { fk_body<NKH, NKX, 0, NW, ND>(p); }
-template <int NKH, int NKX, int NW, int ND>
-__global__ __launch_bounds__(256) void gru_fk_kernel(RRParams p) { fk_body<NKH, NKX, 1, NW, ND>(p); }
+template <int NKH, int NKX, int NW, int ND, bool VL = false>
+__global__ __launch_bounds__(256) void lstm_fk_kernel(RRParams p) { fk_body<NKH, NKX, 0, NW, ND, VL>(p); }
+template <int NKH, int NKX, int NW, int ND, bool VL = false>
+__global__ __launch_bounds__(256) void gru_fk_kernel(RRParams p) { fk_body<NKH, NKX, 1, NW, ND, VL>(p); }
 
 // ---- host side --------------------------------------------------------------------------------------------------
 // NW = 4 (32 rows x 32 units per workgroup, half the operand traffic) when W's images for 32 units fit LDS (in <= 128); else NW = 2
@@ -740,9 +764,13 @@ int nntk_fk_launch(RRParams q, const float *d_imgfk, int cell, size_t *launches)
     int NKH, NKX, NW;
     if (!d_imgfk || !q.xf3 || q.x_tm || q.out_tm || !fk_shape(q.H, q.in, &NKH, &NKX, &NW)) return 1;
     void (*kern)(RRParams) = nullptr;
-    if (cell == 1) kern = NKX == 8 ? gru_fk_kernel<16, 8, 4, FK_ND_4> : gru_fk_kernel<16, 16, 4, FK_ND_4W>;
+    if (q.len) {
+        if (cell == 1) kern = NKX == 8 ? gru_fk_kernel<16, 8, 4, FK_ND_4, true> : gru_fk_kernel<16, 16, 4, FK_ND_4W, true>;
+        else kern = NKX == 8 ? lstm_fk_kernel<16, 8, 4, FK_ND_4, true> : lstm_fk_kernel<16, 16, 4, FK_ND_4W, true>;
+    } else if (cell == 1) kern = NKX == 8 ? gru_fk_kernel<16, 8, 4, FK_ND_4> : gru_fk_kernel<16, 16, 4, FK_ND_4W>;
     else kern = NKX == 8 ? lstm_fk_kernel<16, 8, 4, FK_ND_4> : lstm_fk_kernel<16, 16, 4, FK_ND_4W>;
 #ifdef FK_NW2_WIDE      // A/B build only: the 256-wide layer on pairs of wavefronts (64 rows x 16 units), measured 8 % behind split-K
+    if (NW == 2 && q.len) return 1;
     if (NW == 2) kern = cell == 1 ? gru_fk_kernel<16, 16, 2, FK_ND_2> : lstm_fk_kernel<16, 16, 2, FK_ND_2>;
 #endif
     const size_t lds = fk_lds_bytes(NKH, NKX, NW);

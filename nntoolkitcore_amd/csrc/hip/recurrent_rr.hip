@@ -195,8 +195,13 @@ __global__ __launch_bounds__(256) void rr_tile_h0_kernel(const float *__restrict
 // instead of three bf16 images and six: U's two f16 images of U 2^q sit in the registers that hold hi / mid (its LDS image is unused), the
 // hand-off carries two blocks per (row block, k step) -- and IS the dense layer's FRAG2H operand -- W's bf16 images are packed
 // pre-multiplied by 2^(15 + q), so both parts accumulate at one scale, taken out (exactly) where the bias is added.
-template <int KH, int KX, bool TRAIN, int CELL, bool XF, bool HF = false>
+// VL (the *VarLen calls; not with TRAIN / HF, never time-major): per-row lengths.  The batch tile runs its time loop to its longest row
+// (a scalar from p.len: every workgroup of the tile and every wave agrees, so the hand-off and the pending marks stay consistent), and a
+// lane whose row is past its length keeps its state: fin_gates selects the old c / h on the VALU, so the published fragments, the output
+// wave's rows and hT / cT all carry the frozen value and no memory operation of the step loop moves.
+template <int KH, int KX, bool TRAIN, int CELL, bool XF, bool HF = false, bool VL = false>
 __device__ __forceinline__ void rr_body(const RRParams &p) {
+    static_assert(!VL || (!TRAIN && !HF), "VL: the inference instantiations");
     constexpr int NH = HF ? 2 : 3;                    // images of the h hand-off
 #ifndef RR_ULR8
 #define RR_ULR8 0
@@ -277,9 +282,13 @@ __device__ __forceinline__ void rr_body(const RRParams &p) {
     const int ct = blockIdx.x / p.NBT;
     const int bt_abs = p.b_base / 64 + bt;
     const int b0 = p.b_base + bt * 64;
-    const int H = p.H, T = p.T;
+    const int H = p.H;
+    // steps the tile runs (p.T stays the layout stride; T is a step count everywhere below, or the extent of a time-major tensor, which VL
+    // calls do not use)
+    const int T = VL ? __builtin_amdgcn_readfirstlane(p.len[p.B + bt_abs]) : p.T;
     const int NKS = H >> 4;                          // k steps the hand-off stores per row block (H % 16 == 0)
     const int rows_valid = p.B - b0 < 64 ? p.B - b0 : 64;
+    if (VL && T == 0) { rr_vl_pass_state(p, b0, 64, 16 * ct, 16, CELL == 0); return; }
 
     // ---- resident operands ----
     const rr_v4u *img = p.img + (size_t)ct * rr_blocks_per_ct(KH, KX) * 64;
@@ -327,6 +336,20 @@ __device__ __forceinline__ void rr_body(const RRParams &p) {
             const int row = b0 + half * 32 + n;
             cst[half][e] = (p.c0 && row < p.B && jf + e < H) ? p.c0[(size_t)row * H + jf + e] : 0.0f;
         }
+    // VL: the lengths of the two rows this lane finishes, and (LSTM) the h it keeps past them
+    int vlen[VL ? 2 : 1];
+    float hkeep[VL && CELL == 0 ? 2 : 1][2];
+    if constexpr (VL) {
+#pragma unroll
+        for (int half = 0; half < 2; ++half) {
+            const int row = b0 + half * 32 + n;
+            vlen[half] = row < p.B ? p.len[row] : 0;
+            if constexpr (CELL == 0) {
+#pragma unroll
+                for (int e = 0; e < 2; ++e) hkeep[half][e] = (p.h0 && row < p.B && jf + e < H) ? p.h0[(size_t)row * H + jf + e] : 0.0f;
+            }
+        }
+    }
     // ---- buffer descriptors and per-lane offsets (everything that must be clipped rides in the range-checked vector offset) ----
     const int hb_bytes = (int)p.hstep;
     // the hand-off of step t: read h_{t-1} (t == 0: the h_0 slot), write h_t -- one descriptor per timestep, 32-bit offsets inside it
@@ -479,6 +502,7 @@ __device__ __forceinline__ void rr_body(const RRParams &p) {
                 const float rg = nntk_fast_sigmoid(zc[1][e]);
                 const float ht = nntk_fast_tanh(fmaf(rg, zc[2][e], zc[3][e]));
                 hn[e] = fmaf(-zg + 1.0f, ht, zg * cst[half][e]);
+                if constexpr (VL) hn[e] = t < vlen[half] ? hn[e] : cst[half][e];
                 cst[half][e] = hn[e];
                 if (TRAIN) {      // the BPTT caches (train.hip gru_train_fwd_step_kernel's): Z_z | Z_r | Z_h | z | r | h~, and h.U_h + b_h
                     zc[2][e] = fmaf(rg, zc[2][e], zc[3][e]);       // Z_h; zc[3] keeps h.U_h + b_h from here on
@@ -492,8 +516,15 @@ __device__ __forceinline__ void rr_body(const RRParams &p) {
             const float gg = nntk_fast_tanh(zc[2][e]);
             const float og = nntk_fast_sigmoid(zc[3][e]);
             const float cn = fmaf(fg, cst[half][e], ig * gg);
+            if constexpr (VL) {
+                const bool live = t < vlen[half];
+                hn[e] = live ? og * nntk_fast_tanh(cn) : hkeep[half][e];
+                cst[half][e] = live ? cn : cst[half][e];
+                hkeep[half][e] = hn[e];
+            } else {
             cst[half][e] = cn;
             hn[e] = og * nntk_fast_tanh(cn);
+            }
             ac[0][e] = ig; ac[1][e] = fg; ac[2][e] = gg; ac[3][e] = og;
         }
         *reinterpret_cast<float2 *>(hx + n * RR_HX_LD + jl) = make_float2(hn[0], hn[1]);
@@ -902,10 +933,10 @@ __device__ __forceinline__ void rr_body(const RRParams &p) {
         }
     }
 }
-template <int KH, int KX, bool TRAIN = false, bool XF = false, bool HF = false>
-__global__ __launch_bounds__(256) void lstm_rr_kernel(RRParams p) { rr_body<KH, KX, TRAIN, 0, XF, HF>(p); }
-template <int KH, int KX, bool TRAIN = false, bool XF = false>
-__global__ __launch_bounds__(256) void gru_rr_kernel(RRParams p) { rr_body<KH, KX, TRAIN, 1, XF>(p); }
+template <int KH, int KX, bool TRAIN = false, bool XF = false, bool HF = false, bool VL = false>
+__global__ __launch_bounds__(256) void lstm_rr_kernel(RRParams p) { rr_body<KH, KX, TRAIN, 0, XF, HF, VL>(p); }
+template <int KH, int KX, bool TRAIN = false, bool XF = false, bool VL = false>
+__global__ __launch_bounds__(256) void gru_rr_kernel(RRParams p) { rr_body<KH, KX, TRAIN, 1, XF, false, VL>(p); }
 
 // ---- host side --------------------------------------------------------------------------------------------------
 #ifdef NNTK_RR_BOUNDS
@@ -1004,6 +1035,7 @@ struct RRIo {
     float *out_h2;            // the sequence output as a FRAG2H tensor (frag3.hip) instead of the f32 rows, or NULL
     int hf;                   // the HF instantiation: `hseq` is a FRAG2H tensor (two images per block), `img` packed by nntk_shim_lstm_rr_pack_hf
     float z_scale;            // ... and the scale its sums carry, inverted
+    const int *len;           // VL: row lengths then the 64-row tiles' maxima (device), or NULL
 };
 static int rr_launch(const RRIo &io, const float *d_img, const float *d_bi, const float *d_bh,
                      int B, int T, int in, int H, int return_sequences, int cell);
@@ -1011,8 +1043,20 @@ static int rr_launch(const RRIo &io, const float *d_img, const float *d_bi, cons
 extern "C" int nntk_shim_lstm_rr(const float *d_x, const void *d_xf3, const float *d_img, const float *d_img4, const float *d_bi, const float *d_bh,
                                  const float *d_h0, const float *d_c0, float *d_out, float *d_out_h2, float *d_hseq, float *d_hT, float *d_cT,
                                  float *d_work, int B, int T, int in, int H, int return_sequences) {
-    RRIo io = {d_img4, d_x, d_xf3, d_out, d_hseq, d_work, d_h0, d_c0, d_hT, d_cT, nullptr, nullptr, 0, 0, d_out_h2, 0, 0.0f};
+    RRIo io = {d_img4, d_x, d_xf3, d_out, d_hseq, d_work, d_h0, d_c0, d_hT, d_cT, nullptr, nullptr, 0, 0, d_out_h2, 0, 0.0f, nullptr};
     return rr_launch(io, d_img, d_bi, d_bh, B, T, in, H, return_sequences, 0);
+}
+// per-row lengths (the *VarLen calls): d_len = [B] lengths then [ceil(B / 64)] the 64-row tiles' maxima, device memory.  Row b runs its first
+// d_len[b] steps and keeps its state after them (hT / cT, and d_out without sequences, = the state after d_len[b] steps); sequence outputs past
+// the length are unspecified (nntk_shim_varlen_zero_pad).  cell 0 LSTM, 1 GRU (d_bi = the four-slot bias, d_bh NULL, d_c0 / d_cT unused).
+// Same kernel family and bits as nntk_shim_lstm_rr / nntk_shim_gru_rr for every step a row runs; 1 = not taken, as those.
+extern "C" int nntk_shim_rr_varlen(int cell, const float *d_x, const void *d_xf3, const float *d_img, const float *d_img4, const float *d_bi,
+                                   const float *d_bh, const float *d_h0, const float *d_c0, float *d_out, float *d_hseq, float *d_hT, float *d_cT,
+                                   float *d_work, const int *d_len, int B, int T, int in, int H, int return_sequences) {
+    if (!d_len) return nntk_fail_msg("rr_varlen: no lengths");
+    RRIo io = {d_img4, d_x, d_xf3, d_out, d_hseq, d_work, d_h0, cell == 1 ? d_h0 : d_c0, d_hT, cell == 1 ? nullptr : d_cT, nullptr, nullptr, 0, 0,
+               nullptr, 0, 0.0f, d_len};
+    return rr_launch(io, d_img, d_bi, d_bh, B, T, in, H, return_sequences, cell);
 }
 // The HF instantiations (H > 256: KH = 8): zero initial state, x as a frag3 tensor, the sequence output ONLY as the FRAG2H tensor the
 // kernel's hand-off is (d_h2: nntk_shim_frag2h_floats(B, T, H) floats).  d_img: nntk_shim_lstm_rr_pack_hf(.., uscale, wscale = 2^15 uscale),
@@ -1043,7 +1087,7 @@ extern "C" int nntk_shim_lstm_rr_pack_hf(const float *d_ut, const float *d_wp, f
 }
 extern "C" int nntk_shim_lstm_rr_hf(const void *d_xf3, const float *d_img, const float *d_bi, const float *d_bh, float *d_h2, float *d_work,
                                     int B, int T, int in, int H, float z_scale) {
-    RRIo io = {nullptr, nullptr, d_xf3, nullptr, d_h2, d_work, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, nullptr, 1, z_scale};
+    RRIo io = {nullptr, nullptr, d_xf3, nullptr, d_h2, d_work, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, nullptr, 1, z_scale, nullptr};
     return rr_launch(io, d_img, d_bi, d_bh, B, T, in, H, 1, 0);
 }
 // GRU on the same kernel frame (gru_rr_kernel): d_img packed from the four-slot matrices [U_z | U_r | U_h | 0] / [W_z | W_r | 0 | W_h],
@@ -1068,7 +1112,11 @@ extern "C" int nntk_shim_lstm_rr_train_forward(const float *d_x, const float *d_
 }
 
 template <int KH, int KX>
-static void (*rr_pick(int cell, bool train, bool xf))(RRParams) {
+static void (*rr_pick(int cell, bool train, bool xf, bool vl = false))(RRParams) {
+    if (vl) {
+        if (cell == 1) return xf ? gru_rr_kernel<KH, KX, false, true, true> : gru_rr_kernel<KH, KX, false, false, true>;
+        return xf ? lstm_rr_kernel<KH, KX, false, true, false, true> : lstm_rr_kernel<KH, KX, false, false, false, true>;
+    }
     if (cell == 1) return train ? gru_rr_kernel<KH, KX, true, false> : xf ? gru_rr_kernel<KH, KX, false, true> : gru_rr_kernel<KH, KX, false, false>;
     return train ? lstm_rr_kernel<KH, KX, true, false> : xf ? lstm_rr_kernel<KH, KX, false, true> : lstm_rr_kernel<KH, KX, false, false>;
 }
@@ -1079,6 +1127,8 @@ static int rr_launch(const RRIo &io, const float *d_img, const float *d_bi, cons
     const bool xf = io.xf3 != nullptr;
     const bool train = io.c_cache != nullptr;
     if (xf && (train || io.x_tm)) return 1;
+    const bool vl = io.len != nullptr;
+    if (vl && (train || io.x_tm || io.out_tm || io.hf || io.out_h2)) return nntk_fail_msg("lstm_rr: lengths with a training / stacked / frag2h call");
     if (!xf && !io.x) return nntk_fail_msg("lstm_rr: no input");
     if (!io.hseq || !io.work) return nntk_fail_msg("lstm_rr: no hand-off buffer");
     // time-major tensors are addressed across the whole batch with 32-bit buffer offsets
@@ -1097,11 +1147,11 @@ static int rr_launch(const RRIo &io, const float *d_img, const float *d_bi, cons
     // the x and out rows of one 64-row batch tile are addressed with 32-bit buffer offsets
     if ((double)64 * T * in * 4 >= 2.0e9 || (double)64 * T * H * 4 >= 2.0e9) return 1;
     void (*kern)(RRParams) = nullptr;
-    if (KH == 8 && KX == 2) kern = rr_pick<8, 2>(cell, train, xf);
-    else if (KH == 8 && KX == 1) kern = rr_pick<8, 1>(cell, train, xf);
-    else if (KH == 4 && KX == 4) kern = rr_pick<4, 4>(cell, train, xf);
-    else if (KH == 4 && KX == 2) kern = rr_pick<4, 2>(cell, train, xf);
-    else if (KH == 4 && KX == 1) kern = rr_pick<4, 1>(cell, train, xf);
+    if (KH == 8 && KX == 2) kern = rr_pick<8, 2>(cell, train, xf, vl);
+    else if (KH == 8 && KX == 1) kern = rr_pick<8, 1>(cell, train, xf, vl);
+    else if (KH == 4 && KX == 4) kern = rr_pick<4, 4>(cell, train, xf, vl);
+    else if (KH == 4 && KX == 2) kern = rr_pick<4, 2>(cell, train, xf, vl);
+    else if (KH == 4 && KX == 1) kern = rr_pick<4, 1>(cell, train, xf, vl);
     if (hf) kern = KX == 4 ? lstm_rr_kernel<8, 4, false, true, true> : KX == 2 ? lstm_rr_kernel<8, 2, false, true, true> : lstm_rr_kernel<8, 1, false, true, true>;
     if (!kern) return 1;
     const size_t lds = rr_lds_bytes(KH, KX, train, hf);
@@ -1142,6 +1192,7 @@ static int rr_launch(const RRIo &io, const float *d_img, const float *d_bi, cons
     q.NHT = nbt_total * 2;
     q.out_h2 = (char *)io.out_h2; q.h2step = rr_step_bytes(B, H) / 3 * 2;
     q.z_scale = io.z_scale;
+    q.len = io.len; q.h0 = io.h0;
 #ifdef NNTK_REC_STAMPS
     q.stamp = nullptr;
     const char *stamp_path = getenv("NNTK_REC_STAMP_FILE");

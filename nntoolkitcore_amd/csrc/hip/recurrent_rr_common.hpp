@@ -117,7 +117,25 @@ struct RRParams {
 #ifdef NNTK_RR_BOUNDS
     unsigned long long *bounds; // [8]: see RR_BOUND below (diagnostics build only)
 #endif
+    // VL instantiations (the *VarLen calls): [B] row lengths followed by [ceil(B / 64)] the 64-row batch tiles' maxima, and h_0 [B][H] in f32
+    // (or NULL: zeros) -- what a row keeps once it is past its length
+    const int *len;
+    const float *h0;
 };
+
+// VL, a tile whose rows are all empty: no step runs, the state passes through -- hT = h_0, cT = c_0 (the GRU's c0 is its h0), and h_0 is
+// the output of a layer without sequences.  Rows [b0, b0 + nrows) x hidden units [j0, j0 + ncols) of this workgroup.
+__device__ inline void rr_vl_pass_state(const RRParams &p, int b0, int nrows, int j0, int ncols, bool lstm) {
+    for (int e = threadIdx.x; e < nrows * ncols; e += blockDim.x) {
+        const int r = b0 + e / ncols, j = j0 + e % ncols;
+        if (r >= p.B || j >= p.H) continue;
+        const size_t i = (size_t)r * p.H + j;
+        const float h = p.h0 ? p.h0[i] : 0.0f;
+        if (p.hT) p.hT[i] = h;
+        if (!p.return_sequences && p.out) p.out[i] = h;
+        if (lstm && p.cT) p.cT[i] = p.c0 ? p.c0[i] : 0.0f;
+    }
+}
 
 // -DNNTK_RR_BOUNDS (tools/rr_bounds_check.py, tests/test_gpu_lstm_rr.py): every request the kernel sends towards a CALLER-visible tensor
 // records the last byte it really touches -- lanes whose vector offset falls outside the descriptor's range touch nothing and are

@@ -536,6 +536,27 @@ __global__ __launch_bounds__(256) void reverse_time_kernel(const float *in, floa
     }
 }
 
+// ragged rows (bd_reverse_*_batch_varlen_device): out[b][t] = in[b][len[b] - 1 - t] for t < len[b], zeros after
+__global__ __launch_bounds__(256) void reverse_time_varlen_kernel(const float *in, float *out, const int *len, long B, int T, int F) {
+    const long total = B * (long)T * F;
+    for (long e = blockIdx.x * (long)blockDim.x + threadIdx.x; e < total; e += (long)gridDim.x * blockDim.x) {
+        const int f = (int)(e % F);
+        const long bt = e / F;
+        const int t = (int)(bt % T);
+        const long b = bt / T;
+        const int L = len[b];
+        out[e] = t < L ? in[(b * T + (L - 1 - t)) * F + f] : 0.0f;
+    }
+}
+
+// a small int array carried in the kernel arguments: copied at launch, so the host array is free when the call returns and the copy
+// is ordered on the stream like every launch (no pinned staging, no synchronisation)
+#define NNTK_INTS_PER_LAUNCH 960
+struct IntChunk { int v[NNTK_INTS_PER_LAUNCH]; };
+__global__ __launch_bounds__(256) void upload_ints_kernel(int *dst, IntChunk c, int n) {
+    for (int i = threadIdx.x; i < n; i += blockDim.x) dst[i] = c.v[i];
+}
+
 // out[r][0:C] = a[r][:], out[r][C:2C] = b[r][:]   (bd_merge_concat, bidirectional.c:40-56, without its transposes)
 __global__ __launch_bounds__(256) void concat2_kernel(const float *a, const float *b, float *out, long rows, int C) {
     const long total = rows * 2L * C;
@@ -624,6 +645,25 @@ int nntk_shim_reverse_time(const float *d_in, float *d_out, long B, int T, int F
     if (d_in == d_out) return nntk_fail_msg("reverse_time: in-place reversal is not supported");
     hipLaunchKernelGGL(reverse_time_kernel, dim3(grid_for(B * T * F, 256)), dim3(256), 0, nntk_stream(), d_in, d_out, B, T, F);
     NNTK_LAUNCH_CHECK("reverse_time_kernel");
+    return 0;
+}
+
+int nntk_shim_reverse_time_varlen(const float *d_in, float *d_out, const int *d_len, long B, int T, int F) {
+    if (B <= 0 || T <= 0 || F <= 0) return 0;
+    if (d_in == d_out) return nntk_fail_msg("reverse_time: in-place reversal is not supported");
+    hipLaunchKernelGGL(reverse_time_varlen_kernel, dim3(grid_for(B * T * F, 256)), dim3(256), 0, nntk_stream(), d_in, d_out, d_len, B, T, F);
+    NNTK_LAUNCH_CHECK("reverse_time_varlen_kernel");
+    return 0;
+}
+
+int nntk_shim_upload_ints(int *d_dst, const int *h_src, long n) {
+    for (long i0 = 0; i0 < n; i0 += NNTK_INTS_PER_LAUNCH) {
+        const int m = n - i0 < NNTK_INTS_PER_LAUNCH ? (int)(n - i0) : NNTK_INTS_PER_LAUNCH;
+        IntChunk c;
+        memcpy(c.v, h_src + i0, (size_t)m * sizeof(int));
+        hipLaunchKernelGGL(upload_ints_kernel, dim3(1), dim3(256), 0, nntk_stream(), d_dst + i0, c, m);
+    }
+    NNTK_LAUNCH_CHECK("upload_ints_kernel");
     return 0;
 }
 

@@ -37,7 +37,7 @@ void   nntk_devbuf_free(nntk_devbuf *b);
  * into another GPU's memory -- released by a thread-exit hook (the former bare _Thread_local buffers leaked
  * device memory with every thread that ever computed a gradient). */
 enum { NNTK_TS_A, NNTK_TS_B, NNTK_TS_C, NNTK_TS_AT, NNTK_TS_BT, NNTK_TS_PACK, NNTK_TS_TMP, NNTK_TS_SCR,
-       NNTK_TS_BD_A, NNTK_TS_BD_B, NNTK_TS_BD_OUT, NNTK_TS_SLOTS };
+       NNTK_TS_BD_A, NNTK_TS_BD_B, NNTK_TS_BD_OUT, NNTK_TS_BD_LEN, NNTK_TS_SLOTS };
 nntk_devbuf *nntk_thread_scratch(int slot);
 
 /* upload a host array into a fresh/reused device buffer */

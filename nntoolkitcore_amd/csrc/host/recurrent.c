@@ -69,6 +69,7 @@ typedef struct {
     nntk_devbuf d_h2;           /* the fused LSTM -> TimeDistributedDense call: the sequence output in FRAG2H form */
     nntk_devbuf d_hseq;         /* register-resident kernels: their T-deep hand-off = the layer output in frag3 form (when the caller supplies no buffer) */
     nntk_devbuf d_xf3;          /* ... and the input packed into frag3 form (when the call packs it) */
+    nntk_devbuf d_len;          /* *VarLen calls: the row lengths, then the 64-row batch tiles' maxima (ints) */
 } rec_core;
 
 /* 1 if the block holds a value the split-bf16 x 3 contraction cannot represent exactly: non-finite, above bf16's largest finite
@@ -120,6 +121,7 @@ static void core_free(rec_core *c) {
     nntk_shim_free(c->d_done);
     nntk_devbuf_free(&c->d_in); nntk_devbuf_free(&c->d_out); nntk_devbuf_free(&c->d_xw); nntk_devbuf_free(&c->d_work); nntk_devbuf_free(&c->d_work_rr); nntk_devbuf_free(&c->d_rr_stage);
     nntk_devbuf_free(&c->d_hseq); nntk_devbuf_free(&c->d_xf3); nntk_devbuf_free(&c->d_h2);
+    nntk_devbuf_free(&c->d_len);
     nntk_wblock_free(&c->wb);
     free(c->weights);
 }
@@ -211,6 +213,10 @@ typedef struct {
     float *d_out;           /* f32 output, or NULL */
     float *d_out_f3;        /* frag3 output [B][T][H] (nntk_frag3_floats), or NULL: handle scratch */
     float *d_out_h2;        /* LSTM only: the sequence output as a FRAG2H tensor (nntk_frag2h_floats) instead of d_out (which must be NULL), or NULL */
+    /* the *VarLen calls: row lengths + tile maxima (device, nntk_shim_rec_varlen's layout) and the caller's state, or d_len NULL */
+    const int *d_len;
+    const float *d_h0, *d_c0;
+    float *d_hT, *d_cT;
 } rr_io;
 
 /* decides the x form and provides it: 0 = f32 rows, 1 = frag3 (*xf3 set; packed here when the caller passed f32), 2 = shape not taken */
@@ -265,6 +271,9 @@ static int core_try_lstm_rr(rec_core *c, int use_bh, const int *acts, const rr_i
     float *d_work = nntk_devbuf_reserve(&c->d_work_rr, nntk_shim_lstm_rr_work_floats(B, c->H));
     float *d_hseq = io->d_out_f3 ? io->d_out_f3 : nntk_devbuf_reserve(&c->d_hseq, nntk_shim_rr_hseq_floats(B, c->T, c->H));
     if (!d_work || !d_hseq) return -1;
+    if (io->d_len)
+        return nntk_shim_rr_varlen(0, xm ? NULL : io->d_in, xm ? xf3 : NULL, c->d_rr, c->d_rr4, c->d_bi, use_bh ? c->d_bh : NULL, io->d_h0, io->d_c0,
+                                   io->d_out, d_hseq, io->d_hT, io->d_cT, d_work, io->d_len, B, c->T, c->in, c->H, c->return_sequences);
     const float *h0 = stateful ? c->d_h[c->cur] : NULL, *c0 = stateful ? c->d_c[c->cur] : NULL;
     float *hT = stateful ? c->d_h[c->cur ^ 1] : NULL, *cT = stateful ? c->d_c[c->cur ^ 1] : NULL;
     return nntk_shim_lstm_rr(xm ? NULL : io->d_in, xm ? xf3 : NULL, c->d_rr, c->d_rr4, c->d_bi, use_bh ? c->d_bh : NULL, h0, c0, io->d_out, io->d_out_h2, d_hseq,
@@ -335,6 +344,9 @@ static int core_try_gru_rr(rec_core *c, const int *acts, const rr_io *io, int B,
     float *d_work = nntk_devbuf_reserve(&c->d_work_rr, nntk_shim_lstm_rr_work_floats(B, H));
     float *d_hseq = io->d_out_f3 ? io->d_out_f3 : nntk_devbuf_reserve(&c->d_hseq, nntk_shim_rr_hseq_floats(B, c->T, H));
     if (!d_work || !d_hseq) return -1;
+    if (io->d_len)
+        return nntk_shim_rr_varlen(1, xm ? NULL : io->d_in, xm ? xf3 : NULL, c->d_rr, c->d_rr4, c->d_b4, NULL, io->d_h0, NULL, io->d_out, d_hseq,
+                                   io->d_hT, NULL, d_work, io->d_len, B, c->T, in, H, c->return_sequences);
     const float *h0 = stateful ? c->d_h[c->cur] : NULL;
     float *hT = stateful ? c->d_h[c->cur ^ 1] : NULL;
     return nntk_shim_gru_rr(xm ? NULL : io->d_in, xm ? xf3 : NULL, c->d_rr, c->d_rr4, c->d_b4, h0, io->d_out, d_hseq, hT, d_work, B, c->T, in, H,
@@ -346,7 +358,7 @@ static int core_apply_device(rec_core *c, int is_lstm, int use_bh, const int *ac
                              const float *d_in, float *d_out, int B, int stateful) {
     int G = c->G, H = c->H, T = c->T;
     if (B <= 0 || T <= 0) return 0;
-    const rr_io io = { d_in, NULL, d_out, NULL, NULL };
+    const rr_io io = { d_in, NULL, d_out, NULL, NULL, NULL, NULL, NULL, NULL, NULL };
     if (is_lstm) {
         int rc = core_try_lstm_rr(c, use_bh, acts, &io, B, stateful);
         if (rc <= 0) return rc;
@@ -372,6 +384,92 @@ static int core_apply_device(rec_core *c, int is_lstm, int use_bh, const int *ac
     return nntk_shim_gru(d_xw, c->d_ut, bh, h0, d_out, hT, d_work, B, T, H, c->return_sequences, acts, scales);
 }
 
+/* Ragged batches with carried state (the *VarLen calls): row b runs its first lengths[b] steps from h0[b] (c0[b]); hT / cT and the
+ * output of a layer without sequences are the state after those steps, sequence outputs past them are zeros.  lengths is host memory
+ * (NULL: every row T), checked before anything is enqueued and copied to the handle in stream order.  The call takes the kernel
+ * family the layer's zero-state batch calls take -- the same router (core_try_lstm_rr / core_try_gru_rr, then the exact-f32 kernels),
+ * so a row's bits for the steps it runs are those of *ApplyDevice. */
+static int core_apply_device_vl(rec_core *c, int is_lstm, int use_bh, const int *acts, const float *scales, const char *who,
+                                const float *d_in, float *d_out, int B, const int *lengths,
+                                const float *d_h0, const float *d_c0, float *d_hT, float *d_cT) {
+    char msg[256];
+    const int G = c->G, H = c->H, T = c->T;
+    if (B < 0) { snprintf(msg, sizeof msg, "%s: batch %d < 0", who, B); NNTK_FAIL(msg); }
+    int T_max = B > 0 ? T : 0, T_min = T;
+    if (lengths) {
+        T_max = 0;
+        for (int b = 0; b < B; ++b) {
+            if (lengths[b] < 0 || lengths[b] > T) {
+                snprintf(msg, sizeof msg, "%s: lengths[%d] = %d is outside [0, %d]", who, b, lengths[b], T);
+                NNTK_FAIL(msg);
+            }
+            if (lengths[b] > T_max) T_max = lengths[b];
+            if (lengths[b] < T_min) T_min = lengths[b];
+        }
+    }
+    if (B == 0 || T <= 0) return 0;
+    const int nbt = (B + 63) / 64;
+    int *hl = (int *)malloc(((size_t)B + nbt) * sizeof(int));
+    if (!hl) NNTK_FAIL("out of host memory");
+    for (int b = 0; b < B; ++b) hl[b] = lengths ? lengths[b] : T;
+    for (int i = 0; i < nbt; ++i) {
+        int m = 0;
+        for (int b = 64 * i; b < B && b < 64 * (i + 1); ++b) m = hl[b] > m ? hl[b] : m;
+        hl[B + i] = m;
+    }
+    int *d_len = (int *)nntk_devbuf_reserve(&c->d_len, (size_t)B + nbt);
+    const int up = d_len ? nntk_shim_upload_ints(d_len, hl, (long)B + nbt) : -1;
+    free(hl);
+    if (up) return -1;
+    const int zero_pad = c->return_sequences && T_min < T;
+    const rr_io io = { d_in, NULL, d_out, NULL, NULL, d_len, d_h0, is_lstm ? d_c0 : NULL, d_hT, is_lstm ? d_cT : NULL };
+    int rc = 1;
+    if (is_lstm) rc = core_try_lstm_rr(c, use_bh, acts, &io, B, 0);
+    else if (G == 3) rc = core_try_gru_rr(c, acts, &io, B, 0);
+    if (rc < 0) return -1;
+    if (rc == 0) return zero_pad ? nntk_shim_varlen_zero_pad(d_out, d_len, B, T, H) : 0;
+    float *d_xw = nntk_devbuf_reserve(&c->d_xw, (size_t)T * B * G * H);
+    float *d_work = nntk_devbuf_reserve(&c->d_work, nntk_shim_recurrent_work_floats(B, H));
+    if (!d_xw || !d_work) return -1;
+    if (T_max > 0 && nntk_shim_conv1d(d_in, c->d_wp, c->d_bi, NULL, 0.f, NNTK_ACT_IDENTITY, 1.f, d_xw, B, T, c->in, G * H, 1, 1, T, 1))
+        return -1;
+    if (nntk_shim_rec_varlen(G, d_xw, c->d_ut, use_bh ? c->d_bh : NULL, d_h0, is_lstm ? d_c0 : NULL, d_out, d_hT, is_lstm ? d_cT : NULL,
+                             d_work, B, T, H, c->return_sequences, acts, scales, d_len, T_max))
+        return -1;
+    return zero_pad ? nntk_shim_varlen_zero_pad(d_out, d_len, B, T, H) : 0;
+}
+
+/* host-pointer form: upload, device call, download (the initial state only when given, the final state only when asked for) */
+static int core_apply_host_vl(rec_core *c, int is_lstm, int use_bh, const int *acts, const float *scales, const char *who,
+                              const float *input, float *output, int B, const int *lengths,
+                              const float *h0, const float *c0, float *hT, float *cT) {
+    if (B <= 0) return core_apply_device_vl(c, is_lstm, use_bh, acts, scales, who, NULL, NULL, B, lengths, NULL, NULL, NULL, NULL);
+    if (core_ensure(c, 1)) return -1;
+    const size_t n_in = (size_t)B * c->T * c->in, n_out = c->return_sequences ? (size_t)B * c->T * c->H : (size_t)B * c->H;
+    const size_t BH = (size_t)B * c->H;
+    const int lstm = is_lstm != 0;
+    float *d_in = nntk_devbuf_reserve(&c->d_in, n_in);
+    /* out | h0 | c0 | hT | cT */
+    float *d_out = nntk_devbuf_reserve(&c->d_out, n_out + (2 + 2 * lstm) * BH);
+    if (!d_in || !d_out) return -1;
+    float *d_h0 = h0 ? d_out + n_out : NULL, *d_c0 = (lstm && c0) ? d_out + n_out + BH : NULL;
+    float *d_hT = hT ? d_out + n_out + (1 + lstm) * BH : NULL, *d_cT = (lstm && cT) ? d_out + n_out + (2 + lstm) * BH : NULL;
+    if (nntk_shim_upload(d_in, input, n_in * sizeof(float))) return -1;
+    if (d_h0 && nntk_shim_upload(d_h0, h0, BH * sizeof(float))) return -1;
+    if (d_c0 && nntk_shim_upload(d_c0, c0, BH * sizeof(float))) return -1;
+    for (int attempt = 0; attempt < 2; ++attempt) {
+        if (core_apply_device_vl(c, is_lstm, use_bh, acts, scales, who, d_in, d_out, B, lengths, d_h0, d_c0, d_hT, d_cT)) return -1;
+        if (nntk_shim_download_nocheck(output, d_out, n_out * sizeof(float))) return -1;
+        /* a persistent launch that gave up (another process held the CUs): the library now keeps to the per-timestep kernels, which
+         * give the same bits -- repeat once on them, as core_apply_host does */
+        if (!nntk_shim_take_fault()) break;
+        if (attempt) NNTK_FAIL("recurrent kernel fault");
+    }
+    if (d_hT && nntk_shim_download(hT, d_hT, BH * sizeof(float))) return -1;
+    if (d_cT && nntk_shim_download(cT, d_cT, BH * sizeof(float))) return -1;
+    return 0;
+}
+
 /* Device call with frag3 tensors on either side (additive API: <Layer>ApplyDeviceFrag3).  Zero state per sequence.  The
  * register-resident kernels take and produce the format natively; every other kernel goes through f32 scratch tensors (frag3 is
  * exact: unpack(pack(x)) == x), so the call works for every shape and the results do not depend on the route. */
@@ -381,7 +479,7 @@ static int core_apply_device_f3(rec_core *c, int is_lstm, int use_bh, const int 
     if (!d_in && !d_in_f3) NNTK_FAIL("ApplyDeviceFrag3: no input tensor");
     if (!d_out && !d_out_f3) NNTK_FAIL("ApplyDeviceFrag3: no output tensor");
     if (d_out_f3 && !c->return_sequences) NNTK_FAIL("ApplyDeviceFrag3: a frag3 output needs return_sequences");
-    const rr_io io = { d_in, d_in_f3, d_out, d_out_f3, NULL };
+    const rr_io io = { d_in, d_in_f3, d_out, d_out_f3, NULL, NULL, NULL, NULL, NULL, NULL };
     int rc = 1;
     if (is_lstm) rc = core_try_lstm_rr(c, use_bh, acts, &io, B, 0);
     else if (c->G == 3) rc = core_try_gru_rr(c, acts, &io, B, 0);
@@ -798,6 +896,25 @@ int GRUApplyDevice(GRU filter, const float *d_input, float *d_output, int batch)
     if (core_ensure(&filter->core, 0)) return -1;
     return core_apply_device(&filter->core, 0, 1, acts, sc, d_input, d_output, batch, 0);
 }
+int GRUApplyDeviceVarLen(GRU filter, const float *d_input, float *d_output, int batch, const int *lengths,
+                         const float *d_h0, float *d_hT) {
+    nntk_shim_clear_error();
+    int acts[3];
+    float sc[3];
+    if (!filter) NNTK_FAIL("GRUApplyDeviceVarLen: NULL handle");
+    if (gru_acts(filter, acts, sc)) return -1;
+    if (core_ensure(&filter->core, 0)) return -1;
+    return core_apply_device_vl(&filter->core, 0, 1, acts, sc, "GRUApplyDeviceVarLen", d_input, d_output, batch, lengths, d_h0, NULL, d_hT, NULL);
+}
+int GRUApplyInferenceBatchVarLen(GRU filter, const float *input, float *output, int batch, const int *lengths,
+                                 const float *h0, float *hT) {
+    nntk_shim_clear_error();
+    int acts[3];
+    float sc[3];
+    if (!filter) NNTK_FAIL("GRUApplyInferenceBatchVarLen: NULL handle");
+    if (gru_acts(filter, acts, sc)) return -1;
+    return core_apply_host_vl(&filter->core, 0, 1, acts, sc, "GRUApplyInferenceBatchVarLen", input, output, batch, lengths, h0, NULL, hT, NULL);
+}
 int GRUApplyDeviceFrag3(GRU filter, const float *d_input, const float *d_input_frag3, float *d_output, float *d_output_frag3, int batch) {
     nntk_shim_clear_error();
     int acts[3];
@@ -1162,6 +1279,27 @@ int LSTMApplyDevice(LSTM filter, const float *d_input, float *d_output, int batc
     if (core_ensure(&filter->core, 0)) return -1;
     return core_apply_device(&filter->core, 1, filter->config.v2, acts, sc, d_input, d_output, batch, 0);
 }
+int LSTMApplyDeviceVarLen(LSTM filter, const float *d_input, float *d_output, int batch, const int *lengths,
+                          const float *d_h0, const float *d_c0, float *d_hT, float *d_cT) {
+    nntk_shim_clear_error();
+    int acts[5];
+    float sc[5];
+    if (!filter) NNTK_FAIL("LSTMApplyDeviceVarLen: NULL handle");
+    if (lstm_acts(filter, acts, sc)) return -1;
+    if (core_ensure(&filter->core, 0)) return -1;
+    return core_apply_device_vl(&filter->core, 1, filter->config.v2, acts, sc, "LSTMApplyDeviceVarLen", d_input, d_output, batch, lengths,
+                                d_h0, d_c0, d_hT, d_cT);
+}
+int LSTMApplyInferenceBatchVarLen(LSTM filter, const float *input, float *output, int batch, const int *lengths,
+                                  const float *h0, const float *c0, float *hT, float *cT) {
+    nntk_shim_clear_error();
+    int acts[5];
+    float sc[5];
+    if (!filter) NNTK_FAIL("LSTMApplyInferenceBatchVarLen: NULL handle");
+    if (lstm_acts(filter, acts, sc)) return -1;
+    return core_apply_host_vl(&filter->core, 1, filter->config.v2, acts, sc, "LSTMApplyInferenceBatchVarLen", input, output, batch, lengths,
+                              h0, c0, hT, cT);
+}
 int LSTMApplyDeviceFrag3(LSTM filter, const float *d_input, const float *d_input_frag3, float *d_output, float *d_output_frag3, int batch) {
     nntk_shim_clear_error();
     int acts[5];
@@ -1429,6 +1567,27 @@ int RNNApplyDevice(RNN filter, const float *d_input, float *d_output, int batch)
     if (core_ensure(&filter->core, 0)) return -1;
     return core_apply_device(&filter->core, 0, filter->config.v2, &act, &sc, d_input, d_output, batch, 0);
 }
+int RNNApplyDeviceVarLen(RNN filter, const float *d_input, float *d_output, int batch, const int *lengths,
+                         const float *d_h0, float *d_hT) {
+    nntk_shim_clear_error();
+    int act;
+    float sc;
+    if (!filter) NNTK_FAIL("RNNApplyDeviceVarLen: NULL handle");
+    if (gate_kind(filter->config.activation, &act, &sc)) return -1;
+    if (core_ensure(&filter->core, 0)) return -1;
+    return core_apply_device_vl(&filter->core, 0, filter->config.v2, &act, &sc, "RNNApplyDeviceVarLen", d_input, d_output, batch, lengths,
+                                d_h0, NULL, d_hT, NULL);
+}
+int RNNApplyInferenceBatchVarLen(RNN filter, const float *input, float *output, int batch, const int *lengths,
+                                 const float *h0, float *hT) {
+    nntk_shim_clear_error();
+    int act;
+    float sc;
+    if (!filter) NNTK_FAIL("RNNApplyInferenceBatchVarLen: NULL handle");
+    if (gate_kind(filter->config.activation, &act, &sc)) return -1;
+    return core_apply_host_vl(&filter->core, 0, filter->config.v2, &act, &sc, "RNNApplyInferenceBatchVarLen", input, output, batch, lengths,
+                              h0, NULL, hT, NULL);
+}
 int RNNResetState(RNN filter) {
     nntk_shim_clear_error();
     if (!filter) NNTK_FAIL("RNNResetState: NULL handle");
@@ -1448,6 +1607,7 @@ int RNNGetState(RNN filter, float *h_host) {
 #define g_bd_a (*nntk_thread_scratch(NNTK_TS_BD_A))
 #define g_bd_b (*nntk_thread_scratch(NNTK_TS_BD_B))
 #define g_bd_out (*nntk_thread_scratch(NNTK_TS_BD_OUT))
+#define g_bd_len (*nntk_thread_scratch(NNTK_TS_BD_LEN))
 
 int bd_reverse_input_batch_device(const float *d_input, float *d_output, RecurrentConfig config, int batch) {
     nntk_shim_clear_error();
@@ -1456,6 +1616,30 @@ int bd_reverse_input_batch_device(const float *d_input, float *d_output, Recurre
 int bd_reverse_backward_batch_device(const float *d_input, float *d_output, RecurrentConfig config, int batch) {
     nntk_shim_clear_error();
     return nntk_shim_reverse_time(d_input, d_output, batch, config.timesteps, config.output_feature_channels);
+}
+/* ragged rows: reverse each row's first lengths[b] steps, zeros after (lengths: host memory, as the *VarLen calls) */
+static int bd_reverse_varlen(const char *who, const float *d_in, float *d_out, int T, int F, int batch, const int *lengths) {
+    nntk_shim_clear_error();
+    char msg[256];
+    if (batch < 0) { snprintf(msg, sizeof msg, "%s: batch %d < 0", who, batch); NNTK_FAIL(msg); }
+    if (!lengths) NNTK_FAIL("bd_reverse_*_varlen_device: NULL lengths");
+    for (int b = 0; b < batch; ++b)
+        if (lengths[b] < 0 || lengths[b] > T) {
+            snprintf(msg, sizeof msg, "%s: lengths[%d] = %d is outside [0, %d]", who, b, lengths[b], T);
+            NNTK_FAIL(msg);
+        }
+    if (batch == 0 || T <= 0 || F <= 0) return 0;
+    int *d_len = (int *)nntk_devbuf_reserve(&g_bd_len, (size_t)batch);
+    if (!d_len || nntk_shim_upload_ints(d_len, lengths, batch)) return -1;
+    return nntk_shim_reverse_time_varlen(d_in, d_out, d_len, batch, T, F);
+}
+int bd_reverse_input_batch_varlen_device(const float *d_input, float *d_output, RecurrentConfig config, int batch, const int *lengths) {
+    return bd_reverse_varlen("bd_reverse_input_batch_varlen_device", d_input, d_output, config.timesteps, config.input_feature_channels,
+                             batch, lengths);
+}
+int bd_reverse_backward_batch_varlen_device(const float *d_input, float *d_output, RecurrentConfig config, int batch, const int *lengths) {
+    return bd_reverse_varlen("bd_reverse_backward_batch_varlen_device", d_input, d_output, config.timesteps, config.output_feature_channels,
+                             batch, lengths);
 }
 int bd_merge_concat_device(const float *d_forward, const float *d_backward, float *d_output, RecurrentConfig config, int batch) {
     nntk_shim_clear_error();

@@ -199,6 +199,30 @@ class _Recurrent:
         check(self._apply_device(self.h, _dp(x), _dp(out), x.shape[0]), type(self).__name__ + "ApplyDevice")
         return out
 
+    def apply_device_varlen(self, x, lengths=None, h0=None, c0=None, return_state=False, out=None):
+        """Ragged batch with carried state (``*ApplyDeviceVarLen``): x [B,T,in] device tensor, row b runs its first
+        lengths[b] steps (None: all T) from h0[b] (c0[b], LSTM); sequence outputs past a row's length are zeros.
+        Returns out, or (out, hT) / (out, hT, cT) with return_state."""
+        B = x.shape[0]
+        H = self.cfg.base.output_feature_channels
+        if out is None:
+            out = self._out((B,), lambda s: x.new_empty(s))
+        lp = None
+        if lengths is not None:
+            lens = np.ascontiguousarray(np.asarray(lengths, dtype=np.int32).reshape(-1))
+            assert lens.shape[0] == B, "lengths: one per row"
+            lp = lens.ctypes.data_as(capi.ip)
+        nul = C.c_void_p(None)
+        hT = x.new_empty((B, H)) if return_state else None
+        state_in = [h0] + ([c0] if self._is_lstm else [])
+        state = [_dp(t) if t is not None else nul for t in state_in]
+        cT = x.new_empty((B, H)) if (return_state and self._is_lstm) else None
+        state += [_dp(hT) if hT is not None else nul] + ([_dp(cT) if cT is not None else nul] if self._is_lstm else [])
+        check(self._apply_device_vl(self.h, _dp(x), _dp(out), B, lp, *state), type(self).__name__ + "ApplyDeviceVarLen")
+        if not return_state:
+            return out
+        return (out, hT, cT) if self._is_lstm else (out, hT)
+
     def sync_weights(self):
         check(self._sync(self.h), "SyncWeights")
 
@@ -220,6 +244,7 @@ class GRU(_Recurrent):
         self.h = L.GRUCreateForInference(self.cfg)
         self._get_weights, self._apply, self._apply_batch = L.GRUGetWeights, L.GRUApplyInference, L.GRUApplyInferenceBatch
         self._apply_device, self._sync, self._reset = L.GRUApplyDevice, L.GRUSyncWeights, L.GRUResetState
+        self._apply_device_vl, self._is_lstm = L.GRUApplyDeviceVarLen, False
         self._destroy, self._acts_destroy = L.GRUDestroy, L.GRUActivationsDestroy
 
     def state(self):
@@ -347,6 +372,7 @@ class RNN(_Recurrent):
         self.h = L.RNNCreateForInference(self.cfg)
         self._get_weights, self._apply, self._apply_batch = L.RNNGetWeights, L.RNNApplyInference, L.RNNApplyInferenceBatch
         self._apply_device, self._sync, self._reset = L.RNNApplyDevice, L.RNNSyncWeights, L.RNNResetState
+        self._apply_device_vl, self._is_lstm = L.RNNApplyDeviceVarLen, False
         self._destroy = L.RNNDestroy
         self.acts = self.act
         self._acts_destroy = L.ActivationFunctionDestroy
@@ -358,13 +384,20 @@ class RNN(_Recurrent):
         return h
 
 
-def bd_reverse_device(x, kind="input"):
-    """[B,T,F] device tensor with every sequence's rows in reverse time order (bidirectional.h)."""
+def bd_reverse_device(x, kind="input", lengths=None):
+    """[B,T,F] device tensor with every sequence's rows in reverse time order (bidirectional.h).  lengths (one per row):
+    reverse each row's first lengths[b] steps and zero the rest (bd_reverse_*_batch_varlen_device)."""
     import torch
     L = capi.load()
     B, T, F = x.shape
     cfg = capi.RecurrentConfig(F, F, True, T)
     out = torch.empty_like(x)
+    if lengths is not None:
+        lens = np.ascontiguousarray(np.asarray(lengths, dtype=np.int32).reshape(-1))
+        assert lens.shape[0] == B, "lengths: one per row"
+        fn = L.bd_reverse_input_batch_varlen_device if kind == "input" else L.bd_reverse_backward_batch_varlen_device
+        check(fn(_dp(x), _dp(out), cfg, B, lens.ctypes.data_as(capi.ip)), "bd_reverse_*_varlen_device")
+        return out
     fn = L.bd_reverse_input_batch_device if kind == "input" else L.bd_reverse_backward_batch_device
     check(fn(_dp(x), _dp(out), cfg, B), "bd_reverse_*_device")
     return out
@@ -395,6 +428,7 @@ class LSTM(_Recurrent):
         self.h = L.LSTMCreateForInference(self.cfg)
         self._get_weights, self._apply, self._apply_batch = L.LSTMGetWeights, L.LSTMApplyInference, L.LSTMApplyInferenceBatch
         self._apply_device, self._sync, self._reset = L.LSTMApplyDevice, L.LSTMSyncWeights, L.LSTMResetState
+        self._apply_device_vl, self._is_lstm = L.LSTMApplyDeviceVarLen, True
         self._destroy, self._acts_destroy = L.LSTMDestroy, L.LSTMActivationsDestroy
 
     def state(self):
