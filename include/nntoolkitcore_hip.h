@@ -549,6 +549,30 @@ int LSTMApplyInferenceBatchVarLen(LSTM filter, const float *input, float *output
 /* bidirectional helpers for ragged rows: out[b][t] = in[b][lengths[b] - 1 - t] for t < lengths[b], zeros after (lengths: host) */
 int bd_reverse_input_batch_varlen_device(const float *d_input, float *d_output, RecurrentConfig config, int batch, const int *lengths);
 int bd_reverse_backward_batch_varlen_device(const float *d_input, float *d_output, RecurrentConfig config, int batch, const int *lengths);
+/* ---- bidirectional layers in one call (INTEGRATION.md "A bidirectional layer") ------------------------------------------------
+ * forward / backward: two layers of one kind with equal input size, hidden size H, timesteps T and return_sequences (the same handle may
+ * be passed twice).  d_input [batch][T][in]; lengths: HOST memory, [batch], or NULL for all T (copied in stream order, as the *VarLen calls).
+ * The result is, bit for bit, that of the composed recipe
+ *     bd_reverse_input_batch[_varlen]_device(x -> xr); *ApplyDevice[VarLen](forward, x -> of); *ApplyDevice[VarLen](backward, xr -> obr);
+ *     return_sequences: bd_reverse_backward_batch[_varlen]_device(obr -> ob), else ob = obr;  bd_merge_{concat,sum}_device(of, ob)
+ * i.e. both directions from zero state; with return_sequences out[b][t] is merge(h_fwd[t], h_bwd[L - 1 - t]) for t < L = lengths[b] and
+ * zeros for t >= L; without, out[b] = merge(forward state after L steps, backward state after its L steps over the reversed prefix).
+ * NNTK_BD_MERGE_CONCAT: output [batch][T][2H] (or [batch][2H]), forward in columns [0, H), backward in [H, 2H); NNTK_BD_MERGE_SUM: [batch][T][H]
+ * (or [batch][H]), forward + backward.  Where both directions take the register-resident / full-K kernels (*KernelPlan) they run in ONE
+ * launch over a virtual batch of both directions (nntk_hip_last_recurrent_kernel() then names the kernel with a ",bd" mark); elsewhere the
+ * call runs the recipe itself.  -1 and nntk_last_error() -- before anything is enqueued, the output untouched -- when the two layers differ
+ * in in / H / T / return_sequences, a length is outside [0, T], merge is not one of the two constants, batch < 0, or (device form) the
+ * output overlaps the input.  Not stateful; f32; device pointers and asynchrony as the *ApplyDevice calls. */
+#define NNTK_BD_MERGE_CONCAT 0
+#define NNTK_BD_MERGE_SUM 1
+int GRUBidirectionalApplyDevice(GRU forward, GRU backward, const float *d_input /*[B,T,in]*/, float *d_output, int batch,
+                                const int *lengths /*host [B] or NULL*/, int merge);
+int LSTMBidirectionalApplyDevice(LSTM forward, LSTM backward, const float *d_input, float *d_output, int batch, const int *lengths, int merge);
+int RNNBidirectionalApplyDevice(RNN forward, RNN backward, const float *d_input, float *d_output, int batch, const int *lengths, int merge);
+/* the same on host memory (upload, device call, download) */
+int GRUBidirectionalApplyInferenceBatch(GRU forward, GRU backward, const float *input, float *output, int batch, const int *lengths, int merge);
+int LSTMBidirectionalApplyInferenceBatch(LSTM forward, LSTM backward, const float *input, float *output, int batch, const int *lengths, int merge);
+int RNNBidirectionalApplyInferenceBatch(RNN forward, RNN backward, const float *input, float *output, int batch, const int *lengths, int merge);
 /* ---- frag3 tensors: activations already split for the split-bf16 x 3 contraction ---------------------------------------------
  * The default contraction of conv / dense / recurrent layers multiplies every f32 operand as three bf16 terms (x = hi + mid + lo,
  * exactly).  A FRAG3 tensor is a [batch][T][C] f32 tensor stored as those three images in MFMA fragment order:

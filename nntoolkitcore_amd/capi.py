@@ -368,6 +368,12 @@ SIGNATURES = {
     "bd_reverse_backward_batch_device": (C.c_int, [vp, vp, RecurrentConfig, C.c_int]),
     "bd_merge_concat_device": (C.c_int, [vp, vp, vp, RecurrentConfig, C.c_int]),
     "bd_merge_sum_device": (C.c_int, [vp, vp, vp, RecurrentConfig, C.c_int]),
+    "GRUBidirectionalApplyDevice": (C.c_int, [vp, vp, vp, vp, C.c_int, ip, C.c_int]),
+    "LSTMBidirectionalApplyDevice": (C.c_int, [vp, vp, vp, vp, C.c_int, ip, C.c_int]),
+    "RNNBidirectionalApplyDevice": (C.c_int, [vp, vp, vp, vp, C.c_int, ip, C.c_int]),
+    "GRUBidirectionalApplyInferenceBatch": (C.c_int, [vp, vp, fp, fp, C.c_int, ip, C.c_int]),
+    "LSTMBidirectionalApplyInferenceBatch": (C.c_int, [vp, vp, fp, fp, C.c_int, ip, C.c_int]),
+    "RNNBidirectionalApplyInferenceBatch": (C.c_int, [vp, vp, fp, fp, C.c_int, ip, C.c_int]),
     "DenseApplyDevice": (C.c_int, [vp, vp, vp, C.c_int]),
     "TimeDistributedDenseApplyDevice": (C.c_int, [vp, vp, vp, C.c_int]),
     "GRUResetState": (C.c_int, [vp]),

@@ -125,6 +125,53 @@ extern "C" int nntk_shim_frag3_pack(const float *d_x, void *d_frag, int B, int T
     return 0;
 }
 
+// ---- the x operand of a bidirectional call (recurrent_rr.hip BD): f32 [B][T][C] -> frag3 of a VIRTUAL batch of 2 Bpad rows,
+// Bpad = 64 ceil(B / 64): row blocks [0, NHT) hold x (rows past B zeros), row blocks [NHT, 2 NHT) the same rows reversed per row,
+// x[b][len[b] - 1 - t] for t < len[b] and zeros after -- frag3_pack of x next to frag3_pack of bd_reverse_*_varlen(x), in one pass
+// over x.  len: [B] device (lengths of the call, T when it has none).  Same blocks and lanes as frag3_pack_kernel.
+__global__ __launch_bounds__(256) void frag3_pack_bd_kernel(const float *__restrict__ x, const int *__restrict__ len, f3_v4u *__restrict__ dst,
+                                                            int B, int T, int C, int NHT, int NKS, int vec_ok) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int n = lane & 31, kh = lane >> 5;
+    const long rb = blockIdx.x;                       // t * 2 NHT + virtual half-tile
+    const int t = (int)(rb / (2 * NHT)), vht = (int)(rb % (2 * NHT));
+    const bool bwd = vht >= NHT;
+    const int b = (bwd ? vht - NHT : vht) * 32 + n;
+    int ts = t;                                       // the source timestep of this row, or -1: zeros
+    if (b >= B) ts = -1;
+    else if (bwd) ts = t < len[b] ? len[b] - 1 - t : -1;
+    const float *row = x + ((size_t)(ts < 0 ? 0 : b) * T + (ts < 0 ? 0 : ts)) * C;
+    for (int ks = w; ks < NKS; ks += 4) {
+        const int c0 = 16 * ks + 8 * kh;
+        float v[8];
+        if (ts >= 0 && vec_ok && c0 + 8 <= C) {
+            const float4 p0 = *reinterpret_cast<const float4 *>(row + c0), p1 = *reinterpret_cast<const float4 *>(row + c0 + 4);
+            v[0] = p0.x; v[1] = p0.y; v[2] = p0.z; v[3] = p0.w; v[4] = p1.x; v[5] = p1.y; v[6] = p1.z; v[7] = p1.w;
+        } else {
+#pragma unroll
+            for (int q = 0; q < 8; ++q) v[q] = (ts >= 0 && c0 + q < C) ? row[c0 + q] : 0.0f;
+        }
+        unsigned h[4], m[4], l[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) f3_split_pair(v[2 * i], v[2 * i + 1], h[i], m[i], l[i]);
+        f3_v4u *d = dst + (((size_t)rb * NKS + ks) * 3) * 64 + lane;
+        d[0] = (f3_v4u){h[0], h[1], h[2], h[3]};
+        d[64] = (f3_v4u){m[0], m[1], m[2], m[3]};
+        d[128] = (f3_v4u){l[0], l[1], l[2], l[3]};
+    }
+}
+// d_frag: nntk_shim_frag3_floats(2 Bpad, T, C) floats
+extern "C" int nntk_shim_frag3_pack_bd(const float *d_x, const int *d_len, void *d_frag, int B, int T, int C) {
+    if (B <= 0 || T <= 0 || C <= 0) return 0;
+    const int NHT = (B + 63) / 64 * 2, NKS = (C + 15) / 16;
+    const long blocks = (long)T * 2 * NHT;
+    if (blocks > 0x7fffffffL) return nntk_fail_msg("frag3_pack_bd: too many row blocks");
+    const int vec_ok = (C % 4) == 0 && (((size_t)d_x) & 15) == 0;
+    hipLaunchKernelGGL(frag3_pack_bd_kernel, dim3((unsigned)blocks), dim3(256), 0, nntk_stream(), d_x, d_len, (f3_v4u *)d_frag, B, T, C, NHT, NKS, vec_ok);
+    NNTK_LAUNCH_CHECK("frag3_pack_bd_kernel");
+    return 0;
+}
+
 // ---- frag3 -> f32 [B][T][C]: x = (hi + mid) + lo, exact (tests; fallback of consumers that do not take the format) ----
 __global__ __launch_bounds__(256) void frag3_unpack_kernel(const f3_v4u *__restrict__ src, float *__restrict__ x, int B, int T, int C,
                                                            int NHT, int NKS) {

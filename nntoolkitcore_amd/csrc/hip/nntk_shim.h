@@ -232,6 +232,16 @@ int nntk_shim_rr_varlen(int cell, const float *d_x, const void *d_xf3, const flo
                         const float *d_bh, const float *d_h0, const float *d_c0, float *d_out, float *d_hseq, float *d_hT, float *d_cT,
                         float *d_work, const int *d_len, int B, int T, int in, int H, int return_sequences);
 
+/* both directions of a bidirectional layer in one launch (the BD instantiations; the *BidirectionalApplyDevice calls): a virtual batch of
+ * 2 Bpad rows, Bpad = 64 ceil(B / 64), forward in [0, Bpad) on d_img / d_img4 / d_bi / d_bh, backward in [Bpad, 2 Bpad) on the _b ones.
+ * d_xf3: nntk_shim_frag3_pack_bd's tensor; d_len: [2 Bpad] virtual-row lengths (padding rows 0) then [2 Bpad / 64] the tiles' maxima;
+ * d_hseq / d_work sized for 2 Bpad rows.  Forward row b writes d_out + b rowpitch + t ldo, backward row b d_out_b + b rowpitch +
+ * (L_b - 1 - t) ldo, rowpitch = T ldo (sequences) or ldo; sequence outputs at t >= L_b are not written.  1 = not taken (nothing launched). */
+int nntk_shim_rr_bd(int cell, const void *d_xf3, const float *d_img, const float *d_img4, const float *d_bi, const float *d_bh,
+                    const float *d_img_b, const float *d_img4_b, const float *d_bi_b, const float *d_bh_b, float *d_out, float *d_out_b,
+                    int ldo, float *d_hseq, float *d_work, const int *d_len, int B, int T, int in, int H, int return_sequences);
+int nntk_shim_rr_bd_fits(int T, int in, int ldo);               /* 0: a 64-row tile of x or of the ldo-wide output rows is past 32-bit offsets (not taken) */
+
 /* The HF instantiations of lstm_rr_kernel (H > 256): the h part of Z on two f16 images (three products per k step), the hand-off = the layer's
  * sequence output as a FRAG2H tensor (d_h2: nntk_shim_frag2h_floats(B, T, H) floats).  Zero initial state, x as a frag3 tensor.  Images:
  * nntk_shim_lstm_rr_pack_hf with uscale = a power of two with max |U| uscale <= 32768 and wscale = 32768 uscale; z_scale = 1 / wscale. */
@@ -246,6 +256,8 @@ int nntk_shim_lstm_rr_hf(const void *d_xf3, const float *d_img, const float *d_b
  * d_wp the packed weights of a Dense layer; returns 1 when the shape is not taken. */
 size_t nntk_shim_frag3_floats(int B, int T, int C);
 int nntk_shim_frag3_pack(const float *d_x, void *d_frag, int B, int T, int C);
+/* a bidirectional call's x operand: frag3 of 2 Bpad virtual rows, x then x reversed per row (d_len: [B] lengths, device), zeros elsewhere */
+int nntk_shim_frag3_pack_bd(const float *d_x, const int *d_len, void *d_frag, int B, int T, int C);
 int nntk_shim_frag3_unpack(const void *d_frag, float *d_x, int B, int T, int C);
 /* FRAG2H (frag3.hip): the same tensor as two f16 images of x * 2^15 (|x| < 2), [T][2 ceil(B / 64)][ceil(C / 16)][2] blocks of 1 KB; the
  * dense GEMM on that form sums three products per k step.  d_wh2: the two f16 images of W * w_scale made by nntk_shim_split_f16x2 from the

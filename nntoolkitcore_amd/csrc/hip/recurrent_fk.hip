@@ -166,8 +166,11 @@ __global__ __launch_bounds__(256) void fk_pack_kernel(const float *__restrict__ 
 // NW: wavefronts sharing an operand (see above); ND: staging sets = groups of k steps requested ahead.
 // VL (the *VarLen calls): per-row lengths, as in recurrent_rr.hip -- the workgroup runs its time loop to the longest row of its 64-row batch
 // tile (a scalar), and a lane past its row's length keeps its state (selected in fin_unit: the published, stored and final values are frozen)
-template <int NKH, int NKX, int CELL, int NW, int ND, bool VL = false>
+// BD (the bidirectional calls; implies VL): both directions in one launch over a virtual batch, as recurrent_rr.hip's BD -- the workgroup's
+// direction (a scalar) selects the weight images, the biases and the output base; a backward lane stores step t at time L - 1 - t of its row
+template <int NKH, int NKX, int CELL, int NW, int ND, bool VL = false, bool BD = false>
 __device__ __forceinline__ void fk_body(const RRParams &p) {
+    static_assert(!BD || VL, "BD: per-row lengths");
     constexpr int NMR = NKH <= 16 ? 3 : 2;            // images of U kept in registers
     constexpr int NMW = NW == 4 && NKX > 8 ? 1 : 0;   // images of W kept in registers
     constexpr int FK_RING = fk_ring(NKX, NW);
@@ -210,13 +213,21 @@ __device__ __forceinline__ void fk_body(const RRParams &p) {
     // steps the workgroup runs (p.T stays the layout stride; T is a step count everywhere below)
     const int T = VL ? __builtin_amdgcn_readfirstlane(p.len[p.B + (b0 >> 6)]) : p.T;
     const int NKS = H >> 4;
-    const int rows_valid = p.B - b0 < 32 * NHF ? p.B - b0 : 32 * NHF;
+    // BD: the workgroup's direction and its first row in the caller's batch (rows_valid: the caller's rows, padding excluded; may be 0)
+    const bool bwd = BD && b0 >= p.bd_pad;
+    const int rb0 = bwd ? b0 - p.bd_pad : b0;
+    const int rows_valid = BD ? (p.bd_rows - rb0 < 32 * NHF ? (p.bd_rows > rb0 ? p.bd_rows - rb0 : 0) : 32 * NHF)
+                              : p.B - b0 < 32 * NHF ? p.B - b0 : 32 * NHF;
     const int gi = NW * ct + ug;                     // this wavefront's group of 8 hidden units
-    if (VL && T == 0) { rr_vl_pass_state(p, b0, 32 * NHF, 8 * NW * ct, 8 * NW, CELL == 0); return; }
+    if (VL && T == 0) {
+        if constexpr (BD) rr_bd_pass_state(p, b0, 32 * NHF, 8 * NW * ct, 8 * NW);
+        else rr_vl_pass_state(p, b0, 32 * NHF, 8 * NW * ct, 8 * NW, CELL == 0);
+        return;
+    }
     const bool grp_ok = 8 * gi < H;                  // (H % 16 == 0: a group is inside or outside as a whole)
 
     // ---- resident operands ----
-    const rr_v4u *img = p.img + (size_t)ct * fk_blocks_per_ct(NKH, NKX, NW) * 64;
+    const rr_v4u *img = (bwd ? p.img_b : p.img) + (size_t)ct * fk_blocks_per_ct(NKH, NKX, NW) * 64;
     rr_bf16x8 uh[NKH][NMR];
 #pragma unroll
     for (int pos = 0; pos < NKH; ++pos)
@@ -245,11 +256,12 @@ __device__ __forceinline__ void fk_body(const RRParams &p) {
     // this lane finishes hidden units jf .. jf + 3 (all four gate slots) of batch row n of its half
     const int jf = 8 * gi + 4 * kh;
     float bsum[4][4];
+    const float *const bi = bwd ? p.bi_b : p.bi, *const bh = bwd ? p.bh_b : p.bh;
 #pragma unroll
     for (int g = 0; g < 4; ++g)
 #pragma unroll
         for (int e = 0; e < 4; ++e)
-            bsum[g][e] = jf + e < H ? p.bi[g * H + jf + e] + (p.bh ? p.bh[g * H + jf + e] : 0.0f) : 0.0f;
+            bsum[g][e] = jf + e < H ? bi[g * H + jf + e] + (bh ? bh[g * H + jf + e] : 0.0f) : 0.0f;
     float cst[4];
     {
         const int row = b0 + hf * 32 + n;
@@ -288,11 +300,12 @@ __device__ __forceinline__ void fk_body(const RRParams &p) {
     const int ugh = (ug ^ (ct / NGH)) & (NW - 1), ugx = (ug ^ (ct / NGX)) & (NW - 1);
     const int hso = ht_abs * NKS * 3 * 1024;
     const int xso = ht_abs * p.NKSx * 3 * 1024;
-    // f32 output rows of this half (rows past the batch masked per lane)
-    const long o_row_bytes = (long)(p.return_sequences ? p.T : 1) * H * 4;
+    // f32 output rows of this half (rows past the batch masked per lane; BD: ldo floats per timestep, the direction's own output base)
+    const int ldo = BD ? p.ldo : H;
+    const long o_row_bytes = (long)(p.return_sequences ? p.T : 1) * ldo * 4;
     const long o_range = rows_valid * o_row_bytes;
     const __amdgpu_buffer_rsrc_t rso = __builtin_amdgcn_make_buffer_rsrc(
-        (void *)(p.out + (size_t)b0 * (o_row_bytes / 4)), 0, (int)(o_range < 0x7fffffffL ? o_range : 0x7fffffffL), 0x00020000);
+        (void *)((bwd ? p.out_b : p.out) + (size_t)rb0 * (o_row_bytes / 4)), 0, (int)(o_range < 0x7fffffffL ? o_range : 0x7fffffffL), 0x00020000);
     const bool row_ok = hf * 32 + n < rows_valid && grp_ok;
     const int out_vo = row_ok ? (int)((hf * 32 + n) * o_row_bytes) + jf * 4 : 0x7fff0000;
     // publication: this lane's 8 bytes of the row's 16-byte fragment slot: block (half-tile, k step = gi / 2, image), k half = gi & 1
@@ -468,7 +481,9 @@ __device__ __forceinline__ void fk_body(const RRParams &p) {
         }
         olast = (rr_v4u){__float_as_uint(hn[0]), __float_as_uint(hn[1]), __float_as_uint(hn[2]), __float_as_uint(hn[3])};
         if (!RR_DBG(1024)) {      // (no branch: a call without a sequence output stores past the descriptor)
-            const int vo = (row_ok && p.return_sequences && p.out) ? out_vo + t * H * 4 : 0x7fff0000;
+            int vo = (row_ok && p.return_sequences && p.out) ? out_vo + t * H * 4 : 0x7fff0000;
+            if constexpr (BD)       // (a row's own steps only; backward: at time L - 1 - t)
+                vo = (row_ok && p.return_sequences && t < vlen) ? out_vo + (bwd ? vlen - 1 - t : t) * ldo * 4 : 0x7fff0000;
             __builtin_amdgcn_raw_buffer_store_b128(olast, rso, vo, 0, 0);
             RR_BOUND(2, (size_t)b0 * o_row_bytes, vo, 0, o_range < 0x7fffffffL ? o_range : 0x7fffffffL, 16);
         }
@@ -697,7 +712,13 @@ __device__ __forceinline__ void fk_body(const RRParams &p) {
         step(I1{}, Tt{}, t + 1, accB, accA);
     }
     // ---- last output / final state: the lanes still hold h_{T-1} and the state ----
-    {
+    if constexpr (BD) {
+        int b0e = rb0;
+        asm volatile("" : "+s"(b0e));
+        const int row = b0e + hf * 32 + n;
+        if (row < p.bd_rows && grp_ok && !p.return_sequences)
+            *reinterpret_cast<rr_v4u *>((bwd ? p.out_b : p.out) + (size_t)row * ldo + jf) = olast;
+    } else {
         int b0e = b0;
         asm volatile("" : "+s"(b0e));
         const int row = b0e + hf * 32 + n;
@@ -709,10 +730,10 @@ __device__ __forceinline__ void fk_body(const RRParams &p) {
         }
     }
 }
-template <int NKH, int NKX, int NW, int ND, bool VL = false>
-__global__ __launch_bounds__(256) void lstm_fk_kernel(RRParams p) { fk_body<NKH, NKX, 0, NW, ND, VL>(p); }
-template <int NKH, int NKX, int NW, int ND, bool VL = false>
-__global__ __launch_bounds__(256) void gru_fk_kernel(RRParams p) { fk_body<NKH, NKX, 1, NW, ND, VL>(p); }
+template <int NKH, int NKX, int NW, int ND, bool VL = false, bool BD = false>
+__global__ __launch_bounds__(256) void lstm_fk_kernel(RRParams p) { fk_body<NKH, NKX, 0, NW, ND, VL, BD>(p); }
+template <int NKH, int NKX, int NW, int ND, bool VL = false, bool BD = false>
+__global__ __launch_bounds__(256) void gru_fk_kernel(RRParams p) { fk_body<NKH, NKX, 1, NW, ND, VL, BD>(p); }
 
 // ---- host side --------------------------------------------------------------------------------------------------
 // NW = 4 (32 rows x 32 units per workgroup, half the operand traffic) when W's images for 32 units fit LDS (in <= 128); else NW = 2
@@ -760,17 +781,23 @@ extern "C" int nntk_shim_fk_pack_raw(const float *d_U, const float *d_W, float *
 
 // 0 = launched; 1 = not taken; -1 = error.  q: the parameters rr_launch (recurrent_rr.hip) has filled (frag3 x, T-deep hand-off with its
 // first two steps preset to the pending pattern, the h_0 slot); d_imgfk: the images of fk_pack.
-int nntk_fk_launch(RRParams q, const float *d_imgfk, int cell, size_t *launches) {
+// d_imgfk_b: the backward direction's images of a bidirectional call (q.out_b set), else unused.
+int nntk_fk_launch(RRParams q, const float *d_imgfk, const float *d_imgfk_b, int cell, size_t *launches) {
     int NKH, NKX, NW;
     if (!d_imgfk || !q.xf3 || q.x_tm || q.out_tm || !fk_shape(q.H, q.in, &NKH, &NKX, &NW)) return 1;
+    const bool bd = q.out_b != nullptr;
+    if (bd && (!d_imgfk_b || !q.len)) return 1;
     void (*kern)(RRParams) = nullptr;
-    if (q.len) {
+    if (bd) {
+        if (cell == 1) kern = NKX == 8 ? gru_fk_kernel<16, 8, 4, FK_ND_4, true, true> : gru_fk_kernel<16, 16, 4, FK_ND_4W, true, true>;
+        else kern = NKX == 8 ? lstm_fk_kernel<16, 8, 4, FK_ND_4, true, true> : lstm_fk_kernel<16, 16, 4, FK_ND_4W, true, true>;
+    } else if (q.len) {
         if (cell == 1) kern = NKX == 8 ? gru_fk_kernel<16, 8, 4, FK_ND_4, true> : gru_fk_kernel<16, 16, 4, FK_ND_4W, true>;
         else kern = NKX == 8 ? lstm_fk_kernel<16, 8, 4, FK_ND_4, true> : lstm_fk_kernel<16, 16, 4, FK_ND_4W, true>;
     } else if (cell == 1) kern = NKX == 8 ? gru_fk_kernel<16, 8, 4, FK_ND_4> : gru_fk_kernel<16, 16, 4, FK_ND_4W>;
     else kern = NKX == 8 ? lstm_fk_kernel<16, 8, 4, FK_ND_4> : lstm_fk_kernel<16, 16, 4, FK_ND_4W>;
 #ifdef FK_NW2_WIDE      // A/B build only: the 256-wide layer on pairs of wavefronts (64 rows x 16 units), measured 8 % behind split-K
-    if (NW == 2 && q.len) return 1;
+    if (NW == 2 && (q.len || bd)) return 1;
     if (NW == 2) kern = cell == 1 ? gru_fk_kernel<16, 16, 2, FK_ND_2> : lstm_fk_kernel<16, 16, 2, FK_ND_2>;
 #endif
     const size_t lds = fk_lds_bytes(NKH, NKX, NW);
@@ -782,6 +809,7 @@ int nntk_fk_launch(RRParams q, const float *d_imgfk, int cell, size_t *launches)
     const int tiles_per_launch = resident / NCT;
     if (tiles_per_launch < 1) return 1;
     q.img = (const rr_v4u *)d_imgfk;
+    if (bd) q.img_b = (const rr_v4u *)d_imgfk_b;
     q.NCT = NCT;
     const int nbt_total = (q.B + rows - 1) / rows;
     for (int bt0 = 0; bt0 < nbt_total; bt0 += tiles_per_launch) {
@@ -791,6 +819,7 @@ int nntk_fk_launch(RRParams q, const float *d_imgfk, int cell, size_t *launches)
     }
     if (launches) *launches = (size_t)((nbt_total + tiles_per_launch - 1) / tiles_per_launch);
     static const char *const names[2][3] = {{"lstm_fk_kernel<16,8,4>", "lstm_fk_kernel<16,16,4>", "lstm_fk_kernel<16,16,2>"}, {"gru_fk_kernel<16,8,4>", "gru_fk_kernel<16,16,4>", "gru_fk_kernel<16,16,2>"}};
-    nntk_set_last_rec_kernel(names[cell == 1][NW == 2 ? 2 : NKX == 16]);
+    static const char *const bd_names[2][2] = {{"lstm_fk_kernel<16,8,4,bd>", "lstm_fk_kernel<16,16,4,bd>"}, {"gru_fk_kernel<16,8,4,bd>", "gru_fk_kernel<16,16,4,bd>"}};
+    nntk_set_last_rec_kernel(bd ? bd_names[cell == 1][NKX == 16] : names[cell == 1][NW == 2 ? 2 : NKX == 16]);
     return 0;
 }

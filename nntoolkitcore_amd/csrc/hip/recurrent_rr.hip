@@ -199,9 +199,14 @@ __global__ __launch_bounds__(256) void rr_tile_h0_kernel(const float *__restrict
 // (a scalar from p.len: every workgroup of the tile and every wave agrees, so the hand-off and the pending marks stay consistent), and a
 // lane whose row is past its length keeps its state: fin_gates selects the old c / h on the VALU, so the published fragments, the output
 // wave's rows and hT / cT all carry the frozen value and no memory operation of the step loop moves.
-template <int KH, int KX, bool TRAIN, int CELL, bool XF, bool HF = false, bool VL = false>
+// BD (the bidirectional calls; implies VL and XF): one launch over a virtual batch of 2 p.bd_pad rows, forward direction first (RRParams).  A
+// 64-row tile belongs to one direction (bd_pad % 64 == 0): the direction is a scalar, and so is everything it selects -- weight images,
+// biases, the output base.  The hand-off, the flags and the x operand keep their layout over the virtual rows.  Output rows are the caller's:
+// a backward lane stores step t at time L - 1 - t of its row, nothing at t >= L; padding rows store nothing.
+template <int KH, int KX, bool TRAIN, int CELL, bool XF, bool HF = false, bool VL = false, bool BD = false>
 __device__ __forceinline__ void rr_body(const RRParams &p) {
     static_assert(!VL || (!TRAIN && !HF), "VL: the inference instantiations");
+    static_assert(!BD || (VL && XF), "BD: per-row lengths and a frag3 x operand");
     constexpr int NH = HF ? 2 : 3;                    // images of the h hand-off
 #ifndef RR_ULR8
 #define RR_ULR8 0
@@ -287,11 +292,18 @@ __device__ __forceinline__ void rr_body(const RRParams &p) {
     // calls do not use)
     const int T = VL ? __builtin_amdgcn_readfirstlane(p.len[p.B + bt_abs]) : p.T;
     const int NKS = H >> 4;                          // k steps the hand-off stores per row block (H % 16 == 0)
-    const int rows_valid = p.B - b0 < 64 ? p.B - b0 : 64;
-    if (VL && T == 0) { rr_vl_pass_state(p, b0, 64, 16 * ct, 16, CELL == 0); return; }
+    // BD: the tile's direction and its first row in the caller's batch (rows_valid: the caller's rows, padding excluded)
+    const bool bwd = BD && b0 >= p.bd_pad;
+    const int rb0 = bwd ? b0 - p.bd_pad : b0;
+    const int rows_valid = BD ? (p.bd_rows - rb0 < 64 ? p.bd_rows - rb0 : 64) : p.B - b0 < 64 ? p.B - b0 : 64;
+    if (VL && T == 0) {
+        if constexpr (BD) rr_bd_pass_state(p, b0, 64, 16 * ct, 16);
+        else rr_vl_pass_state(p, b0, 64, 16 * ct, 16, CELL == 0);
+        return;
+    }
 
     // ---- resident operands ----
-    const rr_v4u *img = p.img + (size_t)ct * rr_blocks_per_ct(KH, KX) * 64;
+    const rr_v4u *img = (bwd ? p.img_b : p.img) + (size_t)ct * rr_blocks_per_ct(KH, KX) * 64;
     rr_bf16x8 uh[KH][2][2];
 #pragma unroll
     for (int i = 0; i < KH; ++i)
@@ -323,11 +335,12 @@ __device__ __forceinline__ void rr_body(const RRParams &p) {
     const int jl = 8 * kh + 4 * (w >> 1) + 2 * (w & 1);
     const int jf = 16 * ct + jl;
     float bsum[4][2];
+    const float *const bi = bwd ? p.bi_b : p.bi, *const bh = bwd ? p.bh_b : p.bh;
 #pragma unroll
     for (int g = 0; g < 4; ++g)
 #pragma unroll
         for (int e = 0; e < 2; ++e)
-            bsum[g][e] = jf + e < H ? p.bi[g * H + jf + e] + (p.bh ? p.bh[g * H + jf + e] : 0.0f) : 0.0f;
+            bsum[g][e] = jf + e < H ? bi[g * H + jf + e] + (bh ? bh[g * H + jf + e] : 0.0f) : 0.0f;
     float cst[2][2];
 #pragma unroll
     for (int half = 0; half < 2; ++half)
@@ -388,11 +401,13 @@ __device__ __forceinline__ void rr_body(const RRParams &p) {
     // consumers; output rows past the batch fall outside the descriptor; hand-off rows past the batch are written too
     // (padding rows compute on zero inputs: finite, read only by themselves)
     // (p.out_tm: the sequence output goes out time-major, [T][B][H], for the next layer of a stack -- rows are then masked per lane)
-    const long o_row_bytes = p.out_tm ? (long)H * 4 : (long)(p.return_sequences ? p.T : 1) * H * 4;
-    const long o_step_bytes = p.out_tm ? (long)p.B * H * 4 : (long)H * 4;
+    // (BD: ldo floats per timestep, the direction's own output base, the caller's rows)
+    const int ldo = BD ? p.ldo : H;
+    const long o_row_bytes = p.out_tm ? (long)H * 4 : (long)(p.return_sequences ? p.T : 1) * ldo * 4;
+    const long o_step_bytes = p.out_tm ? (long)p.B * H * 4 : (long)ldo * 4;
     const long o_range = p.out_tm ? (long)(T - 1) * o_step_bytes + rows_valid * o_row_bytes : rows_valid * o_row_bytes;
     const __amdgpu_buffer_rsrc_t rso = __builtin_amdgcn_make_buffer_rsrc(
-        (void *)(p.out + (size_t)b0 * (o_row_bytes / 4)), 0, (int)(o_range < 0x7fffffffL ? o_range : 0x7fffffffL), 0x00020000);
+        (void *)((bwd ? p.out_b : p.out) + (size_t)rb0 * (o_row_bytes / 4)), 0, (int)(o_range < 0x7fffffffL ? o_range : 0x7fffffffL), 0x00020000);
     const int out_vo = (int)(n * o_row_bytes) + (16 * ct + 8 * kh) * 4;
     const int out_half = (int)(32 * o_row_bytes);
     const int out_step = (int)o_step_bytes;
@@ -598,7 +613,9 @@ __device__ __forceinline__ void rr_body(const RRParams &p) {
             const rr_v4u o0 = *reinterpret_cast<const rr_v4u *>(hx + n * RR_HX_LD + 8 * kh);
             const rr_v4u o1 = *reinterpret_cast<const rr_v4u *>(hx + n * RR_HX_LD + 8 * kh + 4);
             if (p.return_sequences && p.out && !RR_DBG(1024)) {      // (p.out NULL: the caller takes the layer output in frag3 form -- hseq -- only)
-                const int vo = (half ? xok1 : xok0) ? out_vo + half * out_half + t * out_step : 0x7fff0000;   // (past every range, room for + 16); soffset immediate, as above
+                int vo = (half ? xok1 : xok0) ? out_vo + half * out_half + t * out_step : 0x7fff0000;   // (past every range, room for + 16); soffset immediate, as above
+                if constexpr (BD)       // (a row's own steps only; backward: at time L - 1 - t)
+                    vo = (half ? xok1 : xok0) && t < vlen[half] ? out_vo + half * out_half + (bwd ? vlen[half] - 1 - t : t) * out_step : 0x7fff0000;
                 __builtin_amdgcn_raw_buffer_store_b128(o0, rso, vo, 0, 0);
                 __builtin_amdgcn_raw_buffer_store_b128(o1, rso, vo + 16, 0, 0);
                 RR_BOUND(2, (size_t)b0 * o_row_bytes, vo + 16, 0, o_range < 0x7fffffffL ? o_range : 0x7fffffffL, 16);
@@ -616,7 +633,15 @@ __device__ __forceinline__ void rr_body(const RRParams &p) {
                 __builtin_amdgcn_raw_buffer_store_b128(h2lo, rs2, vo + 1024, 0, 0);
                 RR_BOUND(5, (size_t)t * p.h2step, vo + 1024, 0, p.h2step, 16);
             }
-            if (LAST) {
+            if (BD && LAST) {
+                int b0e = rb0;
+                asm volatile("" : "+s"(b0e));
+                const int row = b0e + half * 32 + n;
+                if (row < p.bd_rows && !p.return_sequences) {
+                    float *o = (bwd ? p.out_b : p.out) + (size_t)row * ldo + 16 * ct + 8 * kh;
+                    *reinterpret_cast<rr_v4u *>(o) = o0; *reinterpret_cast<rr_v4u *>(o + 4) = o1;
+                }
+            } else if (LAST) {
                 int b0e = b0;
                 asm volatile("" : "+s"(b0e));             // opaque: keeps these addresses from being computed (and spilled) ahead of the loop
                 const int row = b0e + half * 32 + n;
@@ -933,10 +958,10 @@ __device__ __forceinline__ void rr_body(const RRParams &p) {
         }
     }
 }
-template <int KH, int KX, bool TRAIN = false, bool XF = false, bool HF = false, bool VL = false>
-__global__ __launch_bounds__(256) void lstm_rr_kernel(RRParams p) { rr_body<KH, KX, TRAIN, 0, XF, HF, VL>(p); }
-template <int KH, int KX, bool TRAIN = false, bool XF = false, bool VL = false>
-__global__ __launch_bounds__(256) void gru_rr_kernel(RRParams p) { rr_body<KH, KX, TRAIN, 1, XF, false, VL>(p); }
+template <int KH, int KX, bool TRAIN = false, bool XF = false, bool HF = false, bool VL = false, bool BD = false>
+__global__ __launch_bounds__(256) void lstm_rr_kernel(RRParams p) { rr_body<KH, KX, TRAIN, 0, XF, HF, VL, BD>(p); }
+template <int KH, int KX, bool TRAIN = false, bool XF = false, bool VL = false, bool BD = false>
+__global__ __launch_bounds__(256) void gru_rr_kernel(RRParams p) { rr_body<KH, KX, TRAIN, 1, XF, false, VL, BD>(p); }
 
 // ---- host side --------------------------------------------------------------------------------------------------
 #ifdef NNTK_RR_BOUNDS
@@ -1026,7 +1051,7 @@ extern "C" int nntk_shim_lstm_rr_pack_raw(const float *d_U, const float *d_W, fl
 // 0 = launched; 1 = shape / configuration not taken (the caller runs projection GEMM + rec_persistent_kernel); -1 = error
 // d_x: f32 [B][T][in] (or time-major with x_tm), or NULL with d_xf3 = the same tensor in frag3 form (nntk_shim_frag3_pack);
 // d_out: f32 layer output or NULL (the caller takes it in frag3 form: d_hseq); d_hseq: nntk_shim_rr_hseq_floats(B, T, H) floats
-int nntk_fk_launch(RRParams q, const float *d_imgfk, int cell, size_t *launches);      // recurrent_fk.hip
+int nntk_fk_launch(RRParams q, const float *d_imgfk, const float *d_imgfk_b, int cell, size_t *launches);      // recurrent_fk.hip
 struct RRIo {
     const float *img4;        // images of the full-K kernels (nntk_shim_fk_pack) or NULL
     const float *x; const void *xf3; float *out; float *hseq; float *work;
@@ -1036,6 +1061,11 @@ struct RRIo {
     int hf;                   // the HF instantiation: `hseq` is a FRAG2H tensor (two images per block), `img` packed by nntk_shim_lstm_rr_pack_hf
     float z_scale;            // ... and the scale its sums carry, inverted
     const int *len;           // VL: row lengths then the 64-row tiles' maxima (device), or NULL
+    // BD (nntk_shim_rr_bd): B counts the 2 bd_pad virtual rows; the backward direction's images (split-K, full-K), biases and output base, the
+    // caller's batch, the output's floats per timestep
+    const float *img_b, *img4_b, *bi_b, *bh_b;
+    float *out_b;
+    int bd_rows, ldo;
 };
 static int rr_launch(const RRIo &io, const float *d_img, const float *d_bi, const float *d_bh,
                      int B, int T, int in, int H, int return_sequences, int cell);
@@ -1057,6 +1087,26 @@ extern "C" int nntk_shim_rr_varlen(int cell, const float *d_x, const void *d_xf3
     RRIo io = {d_img4, d_x, d_xf3, d_out, d_hseq, d_work, d_h0, cell == 1 ? d_h0 : d_c0, d_hT, cell == 1 ? nullptr : d_cT, nullptr, nullptr, 0, 0,
                nullptr, 0, 0.0f, d_len};
     return rr_launch(io, d_img, d_bi, d_bh, B, T, in, H, return_sequences, cell);
+}
+// the x and out rows of one 64-row batch tile are addressed with 32-bit buffer offsets: T steps of `in` x floats and of `ow` output floats
+// (ow: H, or a bidirectional call's output row width ldo -- 2H with the concat merge)
+static bool rr_tile_fits(int T, int in, int ow) { return (double)64 * T * in * 4 < 2.0e9 && (double)64 * T * ow * 4 < 2.0e9; }
+extern "C" int nntk_shim_rr_bd_fits(int T, int in, int ldo) { return rr_tile_fits(T, in, ldo); }
+// Both directions of a bidirectional layer in one launch (the *BidirectionalApplyDevice calls): a virtual batch of 2 Bpad rows, Bpad =
+// 64 ceil(B / 64), forward direction in rows [0, Bpad), backward in [Bpad, 2 Bpad).  d_xf3: that batch's x in frag3 form
+// (nntk_shim_frag3_pack_bd); d_len: [2 Bpad] virtual-row lengths (padding rows 0) then [2 Bpad / 64] the tiles' maxima; d_hseq / d_work sized
+// for 2 Bpad rows.  Forward row b writes d_out + b rowpitch + t ldo, backward row b d_out_b + b rowpitch + (L_b - 1 - t) ldo (rowpitch = T ldo
+// with sequences, ldo without; sequence outputs at t >= L_b are not written).  Same kernel family and, per direction, the same bits as
+// nntk_shim_rr_varlen; 1 = not taken.
+extern "C" int nntk_shim_rr_bd(int cell, const void *d_xf3, const float *d_img, const float *d_img4, const float *d_bi, const float *d_bh,
+                               const float *d_img_b, const float *d_img4_b, const float *d_bi_b, const float *d_bh_b, float *d_out, float *d_out_b,
+                               int ldo, float *d_hseq, float *d_work, const int *d_len, int B, int T, int in, int H, int return_sequences) {
+    if (!d_len || !d_xf3 || !d_out || !d_out_b) return nntk_fail_msg("rr_bd: no lengths / input / output");
+    if (B <= 0 || T <= 0) return 0;
+    if (!d_img4 || !d_img4_b) d_img4 = d_img4_b = nullptr;      // (full-K images of one direction only: left over from an earlier rec_fk)
+    RRIo io = {d_img4, nullptr, d_xf3, d_out, d_hseq, d_work, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, nullptr, 0, 0.0f, d_len,
+               d_img_b, d_img4_b, d_bi_b, d_bh_b, d_out_b, B, ldo};
+    return rr_launch(io, d_img, d_bi, d_bh, 2 * ((B + 63) / 64) * 64, T, in, H, return_sequences, cell);
 }
 // The HF instantiations (H > 256: KH = 8): zero initial state, x as a frag3 tensor, the sequence output ONLY as the FRAG2H tensor the
 // kernel's hand-off is (d_h2: nntk_shim_frag2h_floats(B, T, H) floats).  d_img: nntk_shim_lstm_rr_pack_hf(.., uscale, wscale = 2^15 uscale),
@@ -1112,7 +1162,8 @@ extern "C" int nntk_shim_lstm_rr_train_forward(const float *d_x, const float *d_
 }
 
 template <int KH, int KX>
-static void (*rr_pick(int cell, bool train, bool xf, bool vl = false))(RRParams) {
+static void (*rr_pick(int cell, bool train, bool xf, bool vl = false, bool bd = false))(RRParams) {
+    if (bd) return cell == 1 ? gru_rr_kernel<KH, KX, false, true, true, true> : lstm_rr_kernel<KH, KX, false, true, false, true, true>;
     if (vl) {
         if (cell == 1) return xf ? gru_rr_kernel<KH, KX, false, true, true> : gru_rr_kernel<KH, KX, false, false, true>;
         return xf ? lstm_rr_kernel<KH, KX, false, true, false, true> : lstm_rr_kernel<KH, KX, false, false, false, true>;
@@ -1129,6 +1180,8 @@ static int rr_launch(const RRIo &io, const float *d_img, const float *d_bi, cons
     if (xf && (train || io.x_tm)) return 1;
     const bool vl = io.len != nullptr;
     if (vl && (train || io.x_tm || io.out_tm || io.hf || io.out_h2)) return nntk_fail_msg("lstm_rr: lengths with a training / stacked / frag2h call");
+    const bool bd = io.out_b != nullptr;
+    if (bd && (!vl || !xf || io.h0 || io.hT || io.cT)) return nntk_fail_msg("lstm_rr: a bidirectional call needs lengths, a frag3 x and no carried state");
     if (!xf && !io.x) return nntk_fail_msg("lstm_rr: no input");
     if (!io.hseq || !io.work) return nntk_fail_msg("lstm_rr: no hand-off buffer");
     // time-major tensors are addressed across the whole batch with 32-bit buffer offsets
@@ -1144,14 +1197,13 @@ static int rr_launch(const RRIo &io, const float *d_img, const float *d_bi, cons
     if (!xf && ((((size_t)io.x) & 15) != 0 || (in % 4) != 0)) return 1;
     if (hf && (KH != 8 || cell != 0 || !xf || train || io.h0 || io.out || io.out_h2 || io.img4 || !return_sequences || opt.rec_hf == 0)) return 1;
     const int NCT = H / 16;
-    // the x and out rows of one 64-row batch tile are addressed with 32-bit buffer offsets
-    if ((double)64 * T * in * 4 >= 2.0e9 || (double)64 * T * H * 4 >= 2.0e9) return 1;
+    if (!rr_tile_fits(T, in, bd ? io.ldo : H)) return 1;
     void (*kern)(RRParams) = nullptr;
-    if (KH == 8 && KX == 2) kern = rr_pick<8, 2>(cell, train, xf, vl);
-    else if (KH == 8 && KX == 1) kern = rr_pick<8, 1>(cell, train, xf, vl);
-    else if (KH == 4 && KX == 4) kern = rr_pick<4, 4>(cell, train, xf, vl);
-    else if (KH == 4 && KX == 2) kern = rr_pick<4, 2>(cell, train, xf, vl);
-    else if (KH == 4 && KX == 1) kern = rr_pick<4, 1>(cell, train, xf, vl);
+    if (KH == 8 && KX == 2) kern = rr_pick<8, 2>(cell, train, xf, vl, bd);
+    else if (KH == 8 && KX == 1) kern = rr_pick<8, 1>(cell, train, xf, vl, bd);
+    else if (KH == 4 && KX == 4) kern = rr_pick<4, 4>(cell, train, xf, vl, bd);
+    else if (KH == 4 && KX == 2) kern = rr_pick<4, 2>(cell, train, xf, vl, bd);
+    else if (KH == 4 && KX == 1) kern = rr_pick<4, 1>(cell, train, xf, vl, bd);
     if (hf) kern = KX == 4 ? lstm_rr_kernel<8, 4, false, true, true> : KX == 2 ? lstm_rr_kernel<8, 2, false, true, true> : lstm_rr_kernel<8, 1, false, true, true>;
     if (!kern) return 1;
     const size_t lds = rr_lds_bytes(KH, KX, train, hf);
@@ -1193,6 +1245,8 @@ static int rr_launch(const RRIo &io, const float *d_img, const float *d_bi, cons
     q.out_h2 = (char *)io.out_h2; q.h2step = rr_step_bytes(B, H) / 3 * 2;
     q.z_scale = io.z_scale;
     q.len = io.len; q.h0 = io.h0;
+    q.img_b = (const rr_v4u *)io.img_b; q.bi_b = io.bi_b; q.bh_b = io.bh_b; q.out_b = io.out_b;
+    q.bd_pad = bd ? B / 2 : 0; q.bd_rows = io.bd_rows; q.ldo = io.ldo;
 #ifdef NNTK_REC_STAMPS
     q.stamp = nullptr;
     const char *stamp_path = getenv("NNTK_REC_STAMP_FILE");
@@ -1217,7 +1271,7 @@ static int rr_launch(const RRIo &io, const float *d_img, const float *d_bi, cons
     int took4 = 1;
     if (xf && !train && io.img4 && !io.out_tm) {
         q.flags = flags;
-        took4 = nntk_fk_launch(q, io.img4, cell, &launches);
+        took4 = nntk_fk_launch(q, io.img4, io.img4_b, cell, &launches);
         if (took4 < 0) { nntk_persistent_launch_end(); return -1; }
     }
     if (took4 == 1)
@@ -1244,7 +1298,10 @@ static int rr_launch(const RRIo &io, const float *d_img, const float *d_bi, cons
     NNTK_LAUNCH_CHECK("lstm_rr_kernel");
     static const char *const names[2][2][3] = {{{"lstm_rr_kernel<4,1>", "lstm_rr_kernel<4,2>", "lstm_rr_kernel<4,4>"}, {"lstm_rr_kernel<8,1>", "lstm_rr_kernel<8,2>", ""}},
                                                {{"gru_rr_kernel<4,1>", "gru_rr_kernel<4,2>", "gru_rr_kernel<4,4>"}, {"gru_rr_kernel<8,1>", "gru_rr_kernel<8,2>", ""}}};
-    if (hf) nntk_set_last_rec_kernel(KX == 4 ? "lstm_rr_kernel<8,4,hf>" : KX == 2 ? "lstm_rr_kernel<8,2,hf>" : "lstm_rr_kernel<8,1,hf>");
+    static const char *const bd_names[2][2][3] = {{{"lstm_rr_kernel<4,1,bd>", "lstm_rr_kernel<4,2,bd>", "lstm_rr_kernel<4,4,bd>"}, {"lstm_rr_kernel<8,1,bd>", "lstm_rr_kernel<8,2,bd>", ""}},
+                                                  {{"gru_rr_kernel<4,1,bd>", "gru_rr_kernel<4,2,bd>", "gru_rr_kernel<4,4,bd>"}, {"gru_rr_kernel<8,1,bd>", "gru_rr_kernel<8,2,bd>", ""}}};
+    if (bd && took4 == 1) nntk_set_last_rec_kernel(bd_names[cell == 1][KH == 8][KX == 1 ? 0 : KX == 2 ? 1 : 2]);
+    else if (hf) nntk_set_last_rec_kernel(KX == 4 ? "lstm_rr_kernel<8,4,hf>" : KX == 2 ? "lstm_rr_kernel<8,2,hf>" : "lstm_rr_kernel<8,1,hf>");
     else if (took4 == 1) nntk_set_last_rec_kernel(names[cell == 1][KH == 8][KX == 1 ? 0 : KX == 2 ? 1 : 2]);
     return 0;
 }

@@ -121,6 +121,14 @@ struct RRParams {
     // (or NULL: zeros) -- what a row keeps once it is past its length
     const int *len;
     const float *h0;
+    // BD instantiations (the bidirectional calls; always VL and XF): the batch is 2 bd_pad VIRTUAL rows, bd_pad = 64 ceil(bd_rows / 64) --
+    // [0, bd_pad) the forward direction on img / bi / bh writing out, [bd_pad, 2 bd_pad) the backward one (its input reversed per row by the
+    // pack pass) on img_b / bi_b / bh_b writing out_b in forward time.  bd_rows: the caller's batch (rows past it in either direction are
+    // padding and reach no output); ldo: floats per timestep of an output row (2H concat, H sum)
+    const rr_v4u *img_b;
+    const float *bi_b, *bh_b;
+    float *out_b;
+    int bd_pad, bd_rows, ldo;
 };
 
 // VL, a tile whose rows are all empty: no step runs, the state passes through -- hT = h_0, cT = c_0 (the GRU's c0 is its h0), and h_0 is
@@ -134,6 +142,20 @@ __device__ inline void rr_vl_pass_state(const RRParams &p, int b0, int nrows, in
         if (p.hT) p.hT[i] = h;
         if (!p.return_sequences && p.out) p.out[i] = h;
         if (lstm && p.cT) p.cT[i] = p.c0 ? p.c0[i] : 0.0f;
+    }
+}
+
+// BD, a tile whose rows are all empty: the output of a layer without sequences is the zero state (sequence outputs are zeroed by the host's
+// pad pass).  Virtual rows [b0, b0 + nrows) x hidden units [j0, j0 + ncols), mapped as the step loop maps them.
+__device__ inline void rr_bd_pass_state(const RRParams &p, int b0, int nrows, int j0, int ncols) {
+    const bool bwd = b0 >= p.bd_pad;
+    float *o = bwd ? p.out_b : p.out;
+    const int rb0 = bwd ? b0 - p.bd_pad : b0;
+    if (p.return_sequences || !o) return;
+    for (int e = threadIdx.x; e < nrows * ncols; e += blockDim.x) {
+        const int r = rb0 + e / ncols, j = j0 + e % ncols;
+        if (r >= p.bd_rows || j >= p.H) continue;
+        o[(size_t)r * p.ldo + j] = 0.0f;
     }
 }
 

@@ -70,6 +70,7 @@ typedef struct {
     nntk_devbuf d_hseq;         /* register-resident kernels: their T-deep hand-off = the layer output in frag3 form (when the caller supplies no buffer) */
     nntk_devbuf d_xf3;          /* ... and the input packed into frag3 form (when the call packs it) */
     nntk_devbuf d_len;          /* *VarLen calls: the row lengths, then the 64-row batch tiles' maxima (ints) */
+    nntk_devbuf d_bd, d_bd_len; /* bidirectional calls (on the forward handle): the composed route's tensors / the sum merge's backward half; row lengths */
 } rec_core;
 
 /* 1 if the block holds a value the split-bf16 x 3 contraction cannot represent exactly: non-finite, above bf16's largest finite
@@ -122,6 +123,7 @@ static void core_free(rec_core *c) {
     nntk_devbuf_free(&c->d_in); nntk_devbuf_free(&c->d_out); nntk_devbuf_free(&c->d_xw); nntk_devbuf_free(&c->d_work); nntk_devbuf_free(&c->d_work_rr); nntk_devbuf_free(&c->d_rr_stage);
     nntk_devbuf_free(&c->d_hseq); nntk_devbuf_free(&c->d_xf3); nntk_devbuf_free(&c->d_h2);
     nntk_devbuf_free(&c->d_len);
+    nntk_devbuf_free(&c->d_bd); nntk_devbuf_free(&c->d_bd_len);
     nntk_wblock_free(&c->wb);
     free(c->weights);
 }
@@ -245,17 +247,8 @@ static int rr_input(rec_core *c, const rr_io *io, int B, const float **xf3) {
     return 1;
 }
 
-/* 0 = ran; 1 = not taken; -1 = error */
-static int core_try_lstm_rr(rec_core *c, int use_bh, const int *acts, const rr_io *io, int B, int stateful) {
-    int on = -1;
-    (void)nntk_shim_get_option("rec_rr", &on);
-    if (on == 0 || c->G != 4 || !lstm_std_acts(acts) || c->rr_exact_only) return 1;
-    if (on != 1 && stateful) return 1;
-    if (!nntk_shim_rr_image_floats_xf(c->H, c->in)) return 1;
-    const float *xf3 = NULL;
-    const int xm = rr_input(c, io, B, &xf3);
-    if (xm < 0) return -1;
-    if (xm == 2) return 1;
+/* the LSTM's weight images of the register-resident (and, for the shapes that family takes, the full-K) kernels, packed on first use */
+static int lstm_rr_images(rec_core *c) {
     size_t img = nntk_shim_rr_image_floats_xf(c->H, c->in);
     if (nntk_shim_fk_image_floats(c->H, c->in) && !c->d_rr4) c->rr_valid = 0;      /* (option rec_fk switched on after the images were packed) */
     if (!c->rr_valid) {
@@ -268,6 +261,20 @@ static int core_try_lstm_rr(rec_core *c, int use_bh, const int *acts, const rr_i
         }
         c->rr_valid = 1;
     }
+    return 0;
+}
+/* 0 = ran; 1 = not taken; -1 = error */
+static int core_try_lstm_rr(rec_core *c, int use_bh, const int *acts, const rr_io *io, int B, int stateful) {
+    int on = -1;
+    (void)nntk_shim_get_option("rec_rr", &on);
+    if (on == 0 || c->G != 4 || !lstm_std_acts(acts) || c->rr_exact_only) return 1;
+    if (on != 1 && stateful) return 1;
+    if (!nntk_shim_rr_image_floats_xf(c->H, c->in)) return 1;
+    const float *xf3 = NULL;
+    const int xm = rr_input(c, io, B, &xf3);
+    if (xm < 0) return -1;
+    if (xm == 2) return 1;
+    if (lstm_rr_images(c)) return -1;
     float *d_work = nntk_devbuf_reserve(&c->d_work_rr, nntk_shim_lstm_rr_work_floats(B, c->H));
     float *d_hseq = io->d_out_f3 ? io->d_out_f3 : nntk_devbuf_reserve(&c->d_hseq, nntk_shim_rr_hseq_floats(B, c->T, c->H));
     if (!d_work || !d_hseq) return -1;
@@ -321,6 +328,20 @@ static int gru_rr_build_image(int in, int H, const float *W, const float *U, con
     free(tmp);                                              /* (nntk_shim_upload has copied it) */
     return rc ? -1 : 0;
 }
+/* the GRU's images and four-slot bias of those kernels, packed on first use */
+static int gru_rr_images(rec_core *c) {
+    const int H = c->H, in = c->in;
+    const size_t img = nntk_shim_rr_image_floats_xf(H, in);
+    if (nntk_shim_fk_image_floats(H, in) && !c->d_rr4) c->rr_valid = 0;            /* (option rec_fk switched on after the images were packed) */
+    if (!c->rr_valid) {
+        /* from the SHADOW, i.e. the weight version core_upload packed d_wp / d_ut from: the device-pointer calls do not look for
+         * host edits (SyncWeights is their contract), and an un-synced edit must not reach this kernel alone (ADVICE r03) */
+        const float *sW = c->wb.shadow, *sU = sW + (size_t)in * 3 * H, *sbi = sU + (size_t)H * 3 * H, *sbh = sbi + 3 * (size_t)H;
+        if (gru_rr_build_image(in, H, sW, sU, sbi, sbh, &c->d_rr, img, &c->d_b4, &c->d_rr_stage, &c->d_rr4)) return -1;
+        c->rr_valid = 1;
+    }
+    return 0;
+}
 static int core_try_gru_rr(rec_core *c, const int *acts, const rr_io *io, int B, int stateful) {
     int on = -1;
     (void)nntk_shim_get_option("rec_rr", &on);
@@ -333,14 +354,7 @@ static int core_try_gru_rr(rec_core *c, const int *acts, const rr_io *io, int B,
     const int xm = rr_input(c, io, B, &xf3);
     if (xm < 0) return -1;
     if (xm == 2) return 1;
-    if (nntk_shim_fk_image_floats(H, in) && !c->d_rr4) c->rr_valid = 0;            /* (option rec_fk switched on after the images were packed) */
-    if (!c->rr_valid) {
-        /* from the SHADOW, i.e. the weight version core_upload packed d_wp / d_ut from: the device-pointer calls do not look for
-         * host edits (SyncWeights is their contract), and an un-synced edit must not reach this kernel alone (ADVICE r03) */
-        const float *sW = c->wb.shadow, *sU = sW + (size_t)in * 3 * H, *sbi = sU + (size_t)H * 3 * H, *sbh = sbi + 3 * (size_t)H;
-        if (gru_rr_build_image(in, H, sW, sU, sbi, sbh, &c->d_rr, img, &c->d_b4, &c->d_rr_stage, &c->d_rr4)) return -1;
-        c->rr_valid = 1;
-    }
+    if (gru_rr_images(c)) return -1;
     float *d_work = nntk_devbuf_reserve(&c->d_work_rr, nntk_shim_lstm_rr_work_floats(B, H));
     float *d_hseq = io->d_out_f3 ? io->d_out_f3 : nntk_devbuf_reserve(&c->d_hseq, nntk_shim_rr_hseq_floats(B, c->T, H));
     if (!d_work || !d_hseq) return -1;
@@ -1729,4 +1743,211 @@ void bd_accumulate_d_x(const float *forward_dx, const float *backward_dx, float 
 void bd_merge_sum(const float *forward_result, const float *backward_result, float *output,
                   RecurrentConfig config, int batch) {
     bd_merge_host(forward_result, backward_result, output, config, batch, 0);
+}
+
+/* ============================ bidirectional layers in one call ======================== */
+/* *BidirectionalApplyDevice (include/nntoolkitcore_hip.h): the result of the composed recipe -- reverse x per row, run each direction from
+ * zero state, reverse the backward sequence output per row, merge -- bit for bit, on one of two routes:
+ *   fused: both directions would take the register-resident / full-K kernels (the decision core_try_lstm_rr / core_try_gru_rr make) ->
+ *     one pack pass (x and x reversed per row into one frag3 tensor of 2 Bpad virtual rows) and ONE launch of the BD instantiations, which
+ *     write the merged layout themselves (the sum merge: the backward half to scratch, then one add);
+ *   composed: everything else (RNN, non-default activations, shapes those kernels do not take, option rec_rr = 0 or rec_bd = 0, weights the
+ *     bf16 split cannot hold) -> the recipe itself, on the handles' own calls and scratch. */
+
+/* everything that can fail is checked here, before anything is enqueued (dev: in / out are device pointers that must not overlap) */
+static int bd_check(const rec_core *f, const rec_core *b, const char *who, const float *d_in, const float *d_out, int B, const int *lengths,
+                    int merge, int dev, int *T_min) {
+    char msg[256];
+    if (f->in != b->in || f->H != b->H || f->T != b->T || f->return_sequences != b->return_sequences) {
+        snprintf(msg, sizeof msg, "%s: the two directions differ in input size, hidden size, timesteps or return_sequences", who);
+        NNTK_FAIL(msg);
+    }
+    if (merge != NNTK_BD_MERGE_CONCAT && merge != NNTK_BD_MERGE_SUM) {
+        snprintf(msg, sizeof msg, "%s: merge %d is neither NNTK_BD_MERGE_CONCAT nor NNTK_BD_MERGE_SUM", who, merge);
+        NNTK_FAIL(msg);
+    }
+    if (B < 0) { snprintf(msg, sizeof msg, "%s: batch %d < 0", who, B); NNTK_FAIL(msg); }
+    const int T = f->T;
+    *T_min = T;
+    if (lengths)
+        for (int r = 0; r < B; ++r) {
+            if (lengths[r] < 0 || lengths[r] > T) {
+                snprintf(msg, sizeof msg, "%s: lengths[%d] = %d is outside [0, %d]", who, r, lengths[r], T);
+                NNTK_FAIL(msg);
+            }
+            if (lengths[r] < *T_min) *T_min = lengths[r];
+        }
+    if (B == 0 || T <= 0) return 0;
+    if (!d_in || !d_out) { snprintf(msg, sizeof msg, "%s: NULL input or output", who); NNTK_FAIL(msg); }
+    const size_t W = merge == NNTK_BD_MERGE_CONCAT ? 2 * (size_t)f->H : (size_t)f->H;
+    const size_t n_in = (size_t)B * T * f->in, n_out = (size_t)B * (f->return_sequences ? (size_t)T : 1) * W;
+    if (dev && (const char *)d_in < (const char *)(d_out + n_out) && (const char *)d_out < (const char *)(d_in + n_in)) {
+        snprintf(msg, sizeof msg, "%s: the output buffer overlaps the input", who);
+        NNTK_FAIL(msg);
+    }
+    return 0;
+}
+
+/* the fused route: 0 = ran; 1 = not taken (nothing that matters enqueued); -1 = error */
+static int bd_fused(rec_core *f, rec_core *b, int is_lstm, int fbh, int bbh, const int *fa, const int *ba, const float *d_in, float *d_out,
+                    int B, const int *lengths, int merge, int T_min) {
+    int on = -1, bd = -1;
+    (void)nntk_shim_get_option("rec_rr", &on);
+    (void)nntk_shim_get_option("rec_bd", &bd);
+    if (on == 0 || bd == 0 || f->G == 1) return 1;
+    if (is_lstm ? !(lstm_std_acts(fa) && lstm_std_acts(ba)) : !(gru_std_acts(fa) && gru_std_acts(ba))) return 1;
+    if (f->rr_exact_only || b->rr_exact_only) return 1;
+    const int H = f->H, T = f->T, in = f->in;
+    const int rs = f->return_sequences, concat = merge == NNTK_BD_MERGE_CONCAT;
+    if (!nntk_shim_rr_image_floats_xf(H, in)) return 1;
+    /* (the concat merge's rows are 2H wide: a tile of them may pass the kernels' 32-bit offsets where one direction's rows do not) */
+    if (!nntk_shim_rr_bd_fits(T, in, concat ? 2 * H : H)) return 1;
+    if (is_lstm ? (lstm_rr_images(f) || lstm_rr_images(b)) : (gru_rr_images(f) || gru_rr_images(b))) return -1;
+    /* the virtual batch: forward rows [0, Bp), backward rows [Bp, 2 Bp); lengths of its rows (padding 0), then its 64-row tiles' maxima */
+    const int nbt = (B + 63) / 64, Bp = 64 * nbt, Bv = 2 * Bp, nvt = 2 * nbt;
+    int *hl = (int *)malloc(((size_t)Bv + nvt) * sizeof(int));
+    if (!hl) NNTK_FAIL("out of host memory");
+    for (int v = 0; v < Bv; ++v) {
+        const int r = v % Bp;
+        hl[v] = r < B ? (lengths ? lengths[r] : T) : 0;
+    }
+    for (int i = 0; i < nvt; ++i) {
+        int m = 0;
+        for (int v = 64 * i; v < 64 * (i + 1); ++v) m = hl[v] > m ? hl[v] : m;
+        hl[Bv + i] = m;
+    }
+    int *d_len = (int *)nntk_devbuf_reserve(&f->d_len, (size_t)Bv + nvt);
+    const int up = d_len ? nntk_shim_upload_ints(d_len, hl, (long)Bv + nvt) : -1;
+    free(hl);
+    if (up) return -1;
+    const size_t n_dir = (size_t)B * (rs ? (size_t)T : 1) * H;
+    float *xf3 = nntk_devbuf_reserve(&f->d_xf3, nntk_shim_frag3_floats(Bv, T, in));
+    float *d_work = nntk_devbuf_reserve(&f->d_work_rr, nntk_shim_lstm_rr_work_floats(Bv, H));
+    float *d_hseq = nntk_devbuf_reserve(&f->d_hseq, nntk_shim_rr_hseq_floats(Bv, T, H));
+    float *d_bwd = concat ? d_out + H : nntk_devbuf_reserve(&f->d_bd, n_dir);
+    if (!xf3 || !d_work || !d_hseq || !d_bwd) return -1;
+    if (nntk_shim_frag3_pack_bd(d_in, d_len, xf3, B, T, in)) return -1;            /* (d_len's first B entries: the forward rows = the call's lengths) */
+    const float *bi_f = is_lstm ? f->d_bi : f->d_b4, *bi_b = is_lstm ? b->d_bi : b->d_b4;
+    const float *bh_f = is_lstm && fbh ? f->d_bh : NULL, *bh_b = is_lstm && bbh ? b->d_bh : NULL;
+    const int rc = nntk_shim_rr_bd(is_lstm ? 0 : 1, xf3, f->d_rr, f->d_rr4, bi_f, bh_f, b->d_rr, b->d_rr4, bi_b, bh_b, d_out, d_bwd,
+                                   concat ? 2 * H : H, d_hseq, d_work, d_len, B, T, in, H, rs);
+    /* 1: the launcher declined after all (the persistent kernels disabled after a fault, too few resident workgroups) -- the pack pass and
+     * the uploads above were wasted but harmless, and the caller runs the composed route */
+    if (rc) return rc;
+    if (!concat && nntk_shim_add2(d_out, d_bwd, d_out, (long)n_dir)) return -1;
+    return rs && T_min < T ? nntk_shim_varlen_zero_pad(d_out, d_len, B, T, concat ? 2 * H : H) : 0;
+}
+
+/* the composed route: the recipe of bd_reverse_*[_varlen]_device, *ApplyDevice[VarLen] twice and bd_merge_*_device, on the forward handle's scratch */
+static int bd_composed(rec_core *f, rec_core *b, int is_lstm, int fbh, int bbh, const int *fa, const float *fs, const int *ba, const float *bs,
+                       const char *who, const float *d_in, float *d_out, int B, const int *lengths, int merge) {
+    const int H = f->H, T = f->T, in = f->in, rs = f->return_sequences;
+    const size_t n_in = (size_t)B * T * in, n_dir = (size_t)B * (rs ? (size_t)T : 1) * H;
+    float *xr = nntk_devbuf_reserve(&f->d_bd, n_in + 3 * n_dir);
+    if (!xr) return -1;
+    float *of = xr + n_in, *obr = of + n_dir, *ob = obr + n_dir;
+    int *d_len = NULL;
+    if (lengths) {
+        d_len = (int *)nntk_devbuf_reserve(&f->d_bd_len, (size_t)B);
+        if (!d_len || nntk_shim_upload_ints(d_len, lengths, B)) return -1;
+    }
+    if (d_len ? nntk_shim_reverse_time_varlen(d_in, xr, d_len, B, T, in) : nntk_shim_reverse_time(d_in, xr, B, T, in)) return -1;
+    if (lengths) {
+        if (core_apply_device_vl(f, is_lstm, fbh, fa, fs, who, d_in, of, B, lengths, NULL, NULL, NULL, NULL)) return -1;
+        if (core_apply_device_vl(b, is_lstm, bbh, ba, bs, who, xr, obr, B, lengths, NULL, NULL, NULL, NULL)) return -1;
+    } else {
+        if (core_apply_device(f, is_lstm, fbh, fa, fs, d_in, of, B, 0)) return -1;
+        if (core_apply_device(b, is_lstm, bbh, ba, bs, xr, obr, B, 0)) return -1;
+    }
+    if (!rs) ob = obr;          /* the final states: no second reversal */
+    else if (d_len ? nntk_shim_reverse_time_varlen(obr, ob, d_len, B, T, H) : nntk_shim_reverse_time(obr, ob, B, T, H)) return -1;
+    return merge == NNTK_BD_MERGE_CONCAT ? nntk_shim_concat2(of, ob, d_out, (long)B * (rs ? T : 1), H) : nntk_shim_add2(of, ob, d_out, (long)n_dir);
+}
+
+static int core_apply_bd(rec_core *f, rec_core *b, int is_lstm, int fbh, int bbh, const int *fa, const float *fs, const int *ba, const float *bs,
+                         const char *who, const float *d_in, float *d_out, int B, const int *lengths, int merge) {
+    int T_min;
+    if (bd_check(f, b, who, d_in, d_out, B, lengths, merge, 1, &T_min)) return -1;
+    if (B == 0 || f->T <= 0) return 0;
+    if (core_ensure(f, 0) || core_ensure(b, 0)) return -1;
+    const int rc = bd_fused(f, b, is_lstm, fbh, bbh, fa, ba, d_in, d_out, B, lengths, merge, T_min);
+    if (rc <= 0) return rc;
+    return bd_composed(f, b, is_lstm, fbh, bbh, fa, fs, ba, bs, who, d_in, d_out, B, lengths, merge);
+}
+
+/* host-pointer form: upload, device call, download (repeated once on the per-timestep kernels after a persistent-kernel fault, as
+ * core_apply_host) */
+static int core_apply_bd_host(rec_core *f, rec_core *b, int is_lstm, int fbh, int bbh, const int *fa, const float *fs, const int *ba,
+                              const float *bs, const char *who, const float *input, float *output, int B, const int *lengths, int merge) {
+    int T_min;
+    if (bd_check(f, b, who, input, output, B, lengths, merge, 0, &T_min)) return -1;
+    if (B == 0 || f->T <= 0) return 0;
+    if (core_ensure(f, 1) || core_ensure(b, 1)) return -1;
+    const size_t W = merge == NNTK_BD_MERGE_CONCAT ? 2 * (size_t)f->H : (size_t)f->H;
+    const size_t n_in = (size_t)B * f->T * f->in, n_out = (size_t)B * (f->return_sequences ? (size_t)f->T : 1) * W;
+    float *d_in = nntk_devbuf_reserve(&f->d_in, n_in), *d_out = nntk_devbuf_reserve(&f->d_out, n_out);
+    if (!d_in || !d_out) return -1;
+    if (nntk_shim_upload(d_in, input, n_in * sizeof(float))) return -1;
+    for (int attempt = 0; attempt < 2; ++attempt) {
+        if (core_apply_bd(f, b, is_lstm, fbh, bbh, fa, fs, ba, bs, who, d_in, d_out, B, lengths, merge)) return -1;
+        if (nntk_shim_download_nocheck(output, d_out, n_out * sizeof(float))) return -1;
+        if (!nntk_shim_take_fault()) break;
+        if (attempt) NNTK_FAIL("recurrent kernel fault");
+    }
+    return 0;
+}
+
+int GRUBidirectionalApplyDevice(GRU forward, GRU backward, const float *d_input, float *d_output, int batch, const int *lengths, int merge) {
+    nntk_shim_clear_error();
+    int fa[3], ba[3];
+    float fs[3], bs[3];
+    if (!forward || !backward) NNTK_FAIL("GRUBidirectionalApplyDevice: NULL handle");
+    if (gru_acts(forward, fa, fs) || gru_acts(backward, ba, bs)) return -1;
+    return core_apply_bd(&forward->core, &backward->core, 0, 1, 1, fa, fs, ba, bs, "GRUBidirectionalApplyDevice", d_input, d_output, batch,
+                         lengths, merge);
+}
+int LSTMBidirectionalApplyDevice(LSTM forward, LSTM backward, const float *d_input, float *d_output, int batch, const int *lengths, int merge) {
+    nntk_shim_clear_error();
+    int fa[5], ba[5];
+    float fs[5], bs[5];
+    if (!forward || !backward) NNTK_FAIL("LSTMBidirectionalApplyDevice: NULL handle");
+    if (lstm_acts(forward, fa, fs) || lstm_acts(backward, ba, bs)) return -1;
+    return core_apply_bd(&forward->core, &backward->core, 1, forward->config.v2, backward->config.v2, fa, fs, ba, bs,
+                         "LSTMBidirectionalApplyDevice", d_input, d_output, batch, lengths, merge);
+}
+int RNNBidirectionalApplyDevice(RNN forward, RNN backward, const float *d_input, float *d_output, int batch, const int *lengths, int merge) {
+    nntk_shim_clear_error();
+    int fa, ba;
+    float fs, bs;
+    if (!forward || !backward) NNTK_FAIL("RNNBidirectionalApplyDevice: NULL handle");
+    if (gate_kind(forward->config.activation, &fa, &fs) || gate_kind(backward->config.activation, &ba, &bs)) return -1;
+    return core_apply_bd(&forward->core, &backward->core, 0, forward->config.v2, backward->config.v2, &fa, &fs, &ba, &bs,
+                         "RNNBidirectionalApplyDevice", d_input, d_output, batch, lengths, merge);
+}
+int GRUBidirectionalApplyInferenceBatch(GRU forward, GRU backward, const float *input, float *output, int batch, const int *lengths, int merge) {
+    nntk_shim_clear_error();
+    int fa[3], ba[3];
+    float fs[3], bs[3];
+    if (!forward || !backward) NNTK_FAIL("GRUBidirectionalApplyInferenceBatch: NULL handle");
+    if (gru_acts(forward, fa, fs) || gru_acts(backward, ba, bs)) return -1;
+    return core_apply_bd_host(&forward->core, &backward->core, 0, 1, 1, fa, fs, ba, bs, "GRUBidirectionalApplyInferenceBatch", input, output,
+                              batch, lengths, merge);
+}
+int LSTMBidirectionalApplyInferenceBatch(LSTM forward, LSTM backward, const float *input, float *output, int batch, const int *lengths, int merge) {
+    nntk_shim_clear_error();
+    int fa[5], ba[5];
+    float fs[5], bs[5];
+    if (!forward || !backward) NNTK_FAIL("LSTMBidirectionalApplyInferenceBatch: NULL handle");
+    if (lstm_acts(forward, fa, fs) || lstm_acts(backward, ba, bs)) return -1;
+    return core_apply_bd_host(&forward->core, &backward->core, 1, forward->config.v2, backward->config.v2, fa, fs, ba, bs,
+                              "LSTMBidirectionalApplyInferenceBatch", input, output, batch, lengths, merge);
+}
+int RNNBidirectionalApplyInferenceBatch(RNN forward, RNN backward, const float *input, float *output, int batch, const int *lengths, int merge) {
+    nntk_shim_clear_error();
+    int fa, ba;
+    float fs, bs;
+    if (!forward || !backward) NNTK_FAIL("RNNBidirectionalApplyInferenceBatch: NULL handle");
+    if (gate_kind(forward->config.activation, &fa, &fs) || gate_kind(backward->config.activation, &ba, &bs)) return -1;
+    return core_apply_bd_host(&forward->core, &backward->core, 0, forward->config.v2, backward->config.v2, &fa, &fs, &ba, &bs,
+                              "RNNBidirectionalApplyInferenceBatch", input, output, batch, lengths, merge);
 }

@@ -420,6 +420,45 @@ def bd_merge_device(fwd, bwd, mode="concat"):
     return out
 
 
+_BD_MERGE = {"concat": 0, "sum": 1}
+
+
+def _bd_args(fwd, x_shape, lengths, merge):
+    base = fwd.cfg.base
+    B, H, T = x_shape[0], base.output_feature_channels, base.timesteps
+    W = 2 * H if merge == "concat" else H
+    shape = (B, T, W) if base.return_sequences else (B, W)
+    lens, lp = None, None
+    if lengths is not None:
+        lens = np.ascontiguousarray(np.asarray(lengths, dtype=np.int32).reshape(-1))
+        assert lens.shape[0] == B, "lengths: one per row"
+        lp = lens.ctypes.data_as(capi.ip)
+    return B, shape, _BD_MERGE.get(merge, -1), lens, lp
+
+
+def bidirectional_apply_device(fwd, bwd, x, lengths=None, merge="concat", out=None):
+    """``<Layer>BidirectionalApplyDevice``: a bidirectional layer of two GRU / LSTM / RNN layers of one kind (the same object may be
+    passed twice) in one call.  x [B,T,in] device tensor; lengths: one per row, or None for all T; merge "concat" ([...,2H]) or "sum"."""
+    kind = type(fwd).__name__
+    B, shape, m, lens, lp = _bd_args(fwd, x.shape, lengths, merge)
+    if out is None:
+        out = x.new_empty(shape)
+    fn = getattr(capi.load(), kind + "BidirectionalApplyDevice")
+    check(fn(fwd.h, bwd.h, _dp(x), _dp(out), B, lp, m), kind + "BidirectionalApplyDevice")
+    return out
+
+
+def bidirectional_apply(fwd, bwd, x, lengths=None, merge="concat"):
+    """The host-memory form (``<Layer>BidirectionalApplyInferenceBatch``): x [B,T,in] numpy array."""
+    kind = type(fwd).__name__
+    x = _f32(x)
+    B, shape, m, lens, lp = _bd_args(fwd, x.shape, lengths, merge)
+    out = np.empty(shape, np.float32)
+    fn = getattr(capi.load(), kind + "BidirectionalApplyInferenceBatch")
+    check(fn(fwd.h, bwd.h, _p(x), _p(out), B, lp, m), kind + "BidirectionalApplyInferenceBatch")
+    return out
+
+
 class LSTM(_Recurrent):
     def __init__(self, in_features, hidden, return_sequences, timesteps, v2=True, acts=None):
         L = capi.load()
