@@ -549,6 +549,40 @@ int LSTMApplyInferenceBatchVarLen(LSTM filter, const float *input, float *output
 /* bidirectional helpers for ragged rows: out[b][t] = in[b][lengths[b] - 1 - t] for t < lengths[b], zeros after (lengths: host) */
 int bd_reverse_input_batch_varlen_device(const float *d_input, float *d_output, RecurrentConfig config, int batch, const int *lengths);
 int bd_reverse_backward_batch_varlen_device(const float *d_input, float *d_output, RecurrentConfig config, int batch, const int *lengths);
+/* ---- streaming a whole stack (INTEGRATION.md "Streaming a whole stack") ------------------------------------------------------
+ * Audio arrives in chunks, per row (user) and per call; every stage keeps what the next chunk needs in a device STATE buffer the caller
+ * owns, updated in place (the call reads the old state before it writes the new one, in stream order: one buffer per stage).  The
+ * handle's input_size is the most new samples (spectrogram) or new rows (conv) a row may bring per call, and the row stride of the chunk
+ * input.  Counts are HOST arrays [batch], checked before anything is enqueued and copied in stream order; on -1 (nntk_last_error()) nothing
+ * is enqueued and nothing is written, host arrays included.  final[b] != 0 (final may be NULL: none) ends row b's stream: its last frames
+ * are released and its state emptied, so the slot can start a new stream.  n_new[b] = 0 leaves row b's state unchanged (a final still
+ * releases).  out[b][j] is frame / output g_b + j of the one-shot call (SpectrogramApplyDevice, LogMelSpectrogramApplyDevice,
+ * Conv1dBatchNormActivationApplyDevice) on the row's whole stream, g_b = what the row emitted before, BIT FOR BIT; rows j >= frames[b]
+ * (n_out[b]) are zeros.
+ * Spectrogram: row b's virtual sequence is tail ++ new, m = tail_len + n_new samples, F = m >= window_size ? (m - noverlap) / step : 0
+ * complete frames; E = final ? F : F & ~1 are emitted (K1 transforms frames in pairs: an odd frame waits for its partner, one hop of
+ * delay, 10 ms at step 160) and next_tail_len = final ? 0 : m - E * step <= window_size + step - 1.
+ * Conv1d: m = hist_len + n_new rows, O = m >= k ? (m - k) / s + 1 : 0 outputs, next_hist_len = final ? 0 : m - O * s <= k - 1; requires
+ * stride <= kernel_size.  The *_plan / *_sizes functions are that arithmetic (pure host code, no GPU): 0 ok, -1 invalid arguments. */
+int nntk_spectrogram_stream_plan(SpectrogramConfig cfg, int tail_len, int n_new, int final, int *frames, int *next_tail_len);
+int nntk_spectrogram_stream_sizes(SpectrogramConfig cfg, int *tail_floats /* window_size + step - 1 */,
+                                  int *max_frames /* ceil(input_size / step) + 1: the output row stride */);
+int nntk_conv1d_stream_plan(Conv1dConfig cfg, int hist_len, int n_new, int final, int *n_out, int *next_hist_len);
+int nntk_conv1d_stream_sizes(Conv1dConfig cfg, int *hist_rows /* k - 1 */, int *max_outputs /* ceil(input_size / stride) */);
+int SpectrogramApplyDeviceStream(Spectrogram filter, const float *d_input /*[B][input_size]*/, const int *n_new /*host [B]*/,
+                                 const int *final /*host [B] or NULL*/, float *d_tail /*[B][tail_floats], in place*/,
+                                 int *tail_len /*host [B], in/out*/, float *d_output /*[B][max_frames][nfreq]*/, int *frames /*host [B], out*/,
+                                 int batch);
+int LogMelSpectrogramApplyDeviceStream(LogMelSpectrogram filter, const float *d_input, const int *n_new, const int *final, float *d_tail,
+                                       int *tail_len, float *d_output /*[B][max_frames][n_mels]*/, int *frames, int batch);
+int Conv1dBatchNormActivationApplyDeviceStream(Conv1d filter, BatchNorm bn /*or NULL*/, ActivationFunction act /*or NULL*/,
+                                               const float *d_input /*[B][input_size][Cin]*/, const int *n_new, const int *final,
+                                               float *d_hist /*[B][k-1][Cin], in place*/, int *hist_len /*host [B], in/out*/,
+                                               float *d_output /*[B][max_outputs][Cout]*/, int *n_out /*host [B], out*/, int batch);
+/* rows t >= lengths[b] of the [B][ts][out] output are zeros, rows t < lengths[b] the bits of TimeDistributedDenseApplyDevice (lengths:
+ * host [B] or NULL = all ts, checked and copied like the *VarLen calls' lengths) */
+int TimeDistributedDenseApplyDeviceVarLen(TimeDistributedDense filter, const float *d_input, float *d_output, int batch,
+                                          const int *lengths);
 /* ---- bidirectional layers in one call (INTEGRATION.md "A bidirectional layer") ------------------------------------------------
  * forward / backward: two layers of one kind with equal input size, hidden size H, timesteps T and return_sequences (the same handle may
  * be passed twice).  d_input [batch][T][in]; lengths: HOST memory, [batch], or NULL for all T (copied in stream order, as the *VarLen calls).

@@ -376,6 +376,15 @@ SIGNATURES = {
     "RNNBidirectionalApplyInferenceBatch": (C.c_int, [vp, vp, fp, fp, C.c_int, ip, C.c_int]),
     "DenseApplyDevice": (C.c_int, [vp, vp, vp, C.c_int]),
     "TimeDistributedDenseApplyDevice": (C.c_int, [vp, vp, vp, C.c_int]),
+    # streaming a whole stack (INTEGRATION.md "Streaming a whole stack")
+    "nntk_spectrogram_stream_plan": (C.c_int, [SpectrogramConfig, C.c_int, C.c_int, C.c_int, ip, ip]),
+    "nntk_spectrogram_stream_sizes": (C.c_int, [SpectrogramConfig, ip, ip]),
+    "nntk_conv1d_stream_plan": (C.c_int, [Conv1dConfig, C.c_int, C.c_int, C.c_int, ip, ip]),
+    "nntk_conv1d_stream_sizes": (C.c_int, [Conv1dConfig, ip, ip]),
+    "SpectrogramApplyDeviceStream": (C.c_int, [vp, vp, ip, ip, vp, ip, vp, ip, C.c_int]),
+    "LogMelSpectrogramApplyDeviceStream": (C.c_int, [vp, vp, ip, ip, vp, ip, vp, ip, C.c_int]),
+    "Conv1dBatchNormActivationApplyDeviceStream": (C.c_int, [vp, vp, vp, vp, ip, ip, vp, ip, vp, ip, C.c_int]),
+    "TimeDistributedDenseApplyDeviceVarLen": (C.c_int, [vp, vp, vp, C.c_int, ip]),
     "GRUResetState": (C.c_int, [vp]),
     "LSTMResetState": (C.c_int, [vp]),
     "RNNResetState": (C.c_int, [vp]),

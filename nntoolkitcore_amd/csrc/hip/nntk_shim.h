@@ -115,6 +115,16 @@ int nntk_shim_reverse_time(const float *d_in, float *d_out, long B, int T, int F
 int nntk_shim_reverse_time_varlen(const float *d_in, float *d_out, const int *d_len, long B, int T, int F);
 /* n ints from host memory to the device, ordered on the stream; the host array may be reused when the call returns */
 int nntk_shim_upload_ints(int *d_dst, const int *h_src, long n);
+/* ---- streaming calls (INTEGRATION.md "Streaming a whole stack") ----
+ * d_cnt = [4][B] ints on the device: emitted frames / outputs | steps in the assembled row (m) | old state steps | new state steps.
+ * stream_gather: d_seq [B][state_rows + in_rows][C] = state ++ new input ++ zeros per row, then the state rows take the row's last
+ * (new state) steps, in place.  spectrogram_rows: K1 on assembled rows with per-row sample and frame counts (spectrogram.hip ST
+ * instantiations); rows past a row's frames are not written; 1 = the fused mel form does not take this nfft (nothing launched). */
+int nntk_shim_stream_gather(const float *d_in, float *d_state, float *d_seq, const int *d_cnt, int B, int in_rows, int state_rows, int C);
+int nntk_shim_spectrogram_rows(const float *d_in, const float *d_window, const float *d_twiddle, float *d_out,
+                               int B, int row_stride, int nfft, int window_size, int step, int nfreq, int max_frames,
+                               float fft_norm, int mode, float scale, const int *d_cnt,
+                               const int *d_mel_tab, const float *d_mel_w, int n_mels, float eps, int do_log);
 /* ---- training, second slice (train.hip): reference operation order throughout ---- */
 int nntk_shim_activation_grad(int kind, int vector_size, int vectors_per_call, const float *d_z, const float *d_a,
                               const float *d_dout, float *d_out, long n);

@@ -550,6 +550,27 @@ __global__ __launch_bounds__(256) void reverse_time_varlen_kernel(const float *i
     }
 }
 
+// The streaming calls' row assembly (SpectrogramApplyDeviceStream, Conv1dBatchNormActivationApplyDeviceStream): a row is a run of
+// steps of C floats.  seq[b] = state[b][0:sl] ++ in[b][0:m - sl] ++ zeros up to state_rows + in_rows steps, then the new state
+// state[b][0:nsl] = seq[b][m - nsl : m] (m = cnt[B + b], sl = cnt[2B + b], nsl = cnt[3B + b]).  One workgroup per row: it reads the
+// old state before the barrier and writes the new one after it, so the state is updated in place.
+__global__ __launch_bounds__(256) void stream_gather_kernel(const float *in, float *state, float *seq, const int *cnt,
+                                                            int B, int in_rows, int state_rows, int C) {
+    const int b = blockIdx.x;
+    const int m = cnt[B + b], sl = cnt[2 * B + b], nsl = cnt[3 * B + b];
+    const long S = (long)(state_rows + in_rows) * C;
+    float *q = seq + b * S;
+    const float *st = state + (long)b * state_rows * C;
+    const float *x = in + (long)b * in_rows * C;
+    const long e_sl = (long)sl * C, e_m = (long)m * C;
+    for (long e = threadIdx.x; e < S; e += blockDim.x)
+        q[e] = e < e_sl ? st[e] : e < e_m ? x[e - e_sl] : 0.0f;
+    __syncthreads();
+    float *stw = state + (long)b * state_rows * C;
+    const float *src = q + (long)(m - nsl) * C;
+    for (long e = threadIdx.x; e < (long)nsl * C; e += blockDim.x) stw[e] = src[e];
+}
+
 // a small int array carried in the kernel arguments: copied at launch, so the host array is free when the call returns and the copy
 // is ordered on the stream like every launch (no pinned staging, no synchronisation)
 #define NNTK_INTS_PER_LAUNCH 960
@@ -665,6 +686,13 @@ int nntk_shim_upload_ints(int *d_dst, const int *h_src, long n) {
         hipLaunchKernelGGL(upload_ints_kernel, dim3(1), dim3(256), 0, nntk_stream(), d_dst + i0, c, m);
     }
     NNTK_LAUNCH_CHECK("upload_ints_kernel");
+    return 0;
+}
+
+int nntk_shim_stream_gather(const float *d_in, float *d_state, float *d_seq, const int *d_cnt, int B, int in_rows, int state_rows, int C) {
+    if (B <= 0 || state_rows + in_rows <= 0 || C <= 0) return 0;
+    hipLaunchKernelGGL(stream_gather_kernel, dim3((unsigned)B), dim3(256), 0, nntk_stream(), d_in, d_state, d_seq, d_cnt, B, in_rows, state_rows, C);
+    NNTK_LAUNCH_CHECK("stream_gather_kernel");
     return 0;
 }
 

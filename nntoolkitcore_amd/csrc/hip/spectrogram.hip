@@ -19,6 +19,7 @@
 // reference accepts, not tuned.
 #include "nntk_common.hpp"
 #include <stdlib.h>
+#include <type_traits>
 
 struct SpecParams {
     const float *in;      // [B, input_size]
@@ -40,6 +41,21 @@ struct SpecParams {
     int dbg;              // timing experiments only: 1 no stores, 2 no sample loads, 4 no LDS passes (wrong results), 8 no split / shuffles
 #endif
 };
+// ST instantiations (the *ApplyDeviceStream calls) take this extended block: row b holds row_len[b] samples and yields row_frames[b]
+// frames; input_size and nts are then only the row strides of the input and the output.  A row's odd last frame gets the ghost partner
+// the one-shot call gives it: samples past row_len[b] read as zeros (512 kernel), frame A itself (mixed radix).  Every other
+// instantiation keeps the plain SpecParams block, so its arguments and instructions are exactly those it had before ST existed.
+struct SpecRowsParams : SpecParams {
+    const int *row_frames;  // [B]
+    const int *row_len;     // [B]
+};
+template <bool ST> using SpecArgs = typename std::conditional<ST, SpecRowsParams, SpecParams>::type;
+template <bool ST, class P> __device__ __forceinline__ int spec_row_frames(const P &p, int b) {
+    if constexpr (ST) return p.row_frames[b]; else return p.nts;
+}
+template <bool ST, class P> __device__ __forceinline__ int spec_row_len(const P &p, int b) {
+    if constexpr (ST) return p.row_len[b]; else return p.input_size;
+}
 #ifdef NNTK_SPEC_DBG
 #define SPEC_DBG(bit) (p.dbg & (bit))
 #else
@@ -187,8 +203,8 @@ __device__ __forceinline__ float finish_bin(const SpecParams &p, float re, float
 // most expensive LDS instruction of the kernel).  Two image slots per wave (the pair being picked from, the pair in flight);
 // the wave waits for its DMA with a counted vmcnt (an LDS-DMA is ordered for a ds_read only by the issuing wave's vmcnt).
 #define SPEC_IMG_FLOATS 576       // one sample image: step + window <= 576 floats (2304 bytes)
-template <int MODE, bool NORM, bool NZ7, int NLD, bool MEL = false, bool DMA = false>
-__global__ __launch_bounds__(256) void spectrogram512_kernel(SpecParams p) {
+template <int MODE, bool NORM, bool NZ7, int NLD, bool MEL = false, bool DMA = false, bool ST = false>
+__global__ __launch_bounds__(256) void spectrogram512_kernel(SpecArgs<ST> p) {
     __shared__ __attribute__((aligned(16))) float lds_z[4][SPEC_LDS_FLOATS];
     __shared__ __attribute__((aligned(16))) float lds_img[DMA ? 4 : 1][DMA ? 2 * SPEC_IMG_FLOATS : 4];
     __shared__ int mel_tab_s[MEL ? 3 * 257 : 1];      // MEL: the run table and the runs, shared by the workgroup
@@ -265,22 +281,25 @@ __global__ __launch_bounds__(256) void spectrogram512_kernel(SpecParams p) {
     const int vo = lane * 4, vo4 = lane == 0 ? 0 : 0x7ffffff0;     // odd last frame: only lane 0 owns bin 256
 
     for (int b = blockIdx.y; b < p.B; b += gridDim.y) {
+        // ST: this row's frame count bounds its pairs; its sample count is the descriptor's range
+        const int nts_b = spec_row_frames<ST>(p, b);
+        const int ppu_b = ST ? (nts_b + 1) >> 1 : ppu;
         // descriptors of this utterance: every offset that must be clipped at its end rides in the (range-checked)
         // vector offset -- a pair at the very end reads zeros past the signal, never the next utterance
         const __amdgpu_buffer_rsrc_t rin = __builtin_amdgcn_make_buffer_rsrc(
-            (void *)(p.in + (size_t)b * p.input_size), 0, p.input_size * 4, 0x00020000);
+            (void *)(p.in + (size_t)b * p.input_size), 0, spec_row_len<ST>(p, b) * 4, 0x00020000);
         const int orow = MEL ? p.n_mels : p.nfreq;       // floats per output row
         const __amdgpu_buffer_rsrc_t rout = __builtin_amdgcn_make_buffer_rsrc(
             (void *)(p.out + (size_t)b * p.nts * orow), 0, p.nts * orow * 4, 0x00020000);
         // Software prefetch, TWO pairs deep: the sample loads of pair n + 2 are issued while pair n is transformed
         // (two register sets, loop unrolled by two).
         int pr = blockIdx.x * 4 + wave;
-        if (pr >= ppu) continue;
+        if (pr >= ppu_b) continue;
         v4u32x ld0[DMA ? 1 : NLD], ld1[DMA ? 1 : NLD];
         // LDS-DMA: slot `slot` of this wave's two sample images <- the pair's samples (lanes past the image are masked off:
         // a DMA writes base + 16 * lane whatever the source offset says)
 #define SPEC_DMA(slot, pair) do {                                                                       \
-            const int soa_ = 2 * ((pair) < ppu ? (pair) : pr) * p.step * 4;                              \
+            const int soa_ = 2 * ((pair) < ppu_b ? (pair) : pr) * p.step * 4;                              \
             float *img_ = lds_img[wave] + (slot) * SPEC_IMG_FLOATS;                                      \
             _Pragma("unroll") for (int i = 0; i < NLD; ++i)                                              \
                 if (lane * 16 + 1024 * i < need_bytes)                                                   \
@@ -289,7 +308,7 @@ __global__ __launch_bounds__(256) void spectrogram512_kernel(SpecParams p) {
 
         // a pair beyond the wave's last one re-reads the last valid one (cache hit, result unused): no branches around loads
 #define SPEC_ISSUE(ld, pair) do {                                                                       \
-            const int soa_ = 2 * ((pair) < ppu ? (pair) : pr) * p.step * 4;                              \
+            const int soa_ = 2 * ((pair) < ppu_b ? (pair) : pr) * p.step * 4;                              \
             _Pragma("unroll") for (int i = 0; i < NLD; ++i) {                                            \
                 if (SPEC_DBG(2)) { ld[i] = (v4u32x){0x3f000000u + lane, 0x3e000000u + i, 0x3d800000u, 0x3e800000u}; continue; } \
                 ld[i] = __builtin_amdgcn_raw_buffer_load_b128(rin, ld_off[i] + soa_, 0, 0);              \
@@ -297,7 +316,7 @@ __global__ __launch_bounds__(256) void spectrogram512_kernel(SpecParams p) {
 
         auto transform = [&](v4u32x (&ld)[DMA ? 1 : NLD], int slot) __attribute__((always_inline)) {
             const int fa = 2 * pr;
-            const bool has_b = fa + 1 < p.nts;        // wave-uniform
+            const bool has_b = fa + 1 < nts_b;         // wave-uniform
             f2 v[8];
             unsigned xa[NR], xb[NR];
             if (DMA) {
@@ -461,10 +480,10 @@ __global__ __launch_bounds__(256) void spectrogram512_kernel(SpecParams p) {
         for (;;) {
             transform(ld0, 0);
             pr += stride;
-            if (pr >= ppu) break;
+            if (pr >= ppu_b) break;
             transform(ld1, 1);
             pr += stride;
-            if (pr >= ppu) break;
+            if (pr >= ppu_b) break;
         }
         if (DMA) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the two requests past the wave's last pair must land before the slots are reused
 #undef SPEC_ISSUE
@@ -528,7 +547,8 @@ __device__ __forceinline__ void stockham_pass(const f2 *in, f2 *out, const f2 *t
     }
 }
 
-__global__ __launch_bounds__(256) void spectrogram_mixed_kernel(SpecParams p, MixedPlan plan) {
+template <bool ST = false>
+__global__ __launch_bounds__(256) void spectrogram_mixed_kernel(SpecArgs<ST> p, MixedPlan plan) {
     extern __shared__ __attribute__((aligned(16))) float smem_mixed[];
     const int N = p.nfft;
     f2 *za = reinterpret_cast<f2 *>(smem_mixed), *zb = za + N;
@@ -537,7 +557,8 @@ __global__ __launch_bounds__(256) void spectrogram_mixed_kernel(SpecParams p, Mi
     const long total_pairs = (long)p.B * ppu;
     for (long pair = blockIdx.x; pair < total_pairs; pair += gridDim.x) {
         const int b = (int)(pair / ppu), fa = 2 * (int)(pair % ppu);
-        const bool has_b = fa + 1 < p.nts;
+        if constexpr (ST) { if (fa >= p.row_frames[b]) continue; }     // block-uniform: past this row's frames
+        const bool has_b = fa + 1 < spec_row_frames<ST>(p, b);
         const float *xa = p.in + (size_t)b * p.input_size + (size_t)fa * p.step;
         const float *xb = has_b ? xa + p.step : xa;
         for (int n = threadIdx.x; n < N; n += blockDim.x) {
@@ -579,9 +600,11 @@ static bool mixed_plan(int n, MixedPlan *plan) {
 }
 
 // Last resort (nfft with a prime factor above 5, or above 4096): one workgroup per frame, direct DFT over the window support.
-__global__ __launch_bounds__(256) void spectrogram_dft_kernel(SpecParams p) {
+template <bool ST = false>
+__global__ __launch_bounds__(256) void spectrogram_dft_kernel(SpecArgs<ST> p) {
     extern __shared__ __attribute__((aligned(16))) float frame[];   // [window_size]
     for (long f = blockIdx.x; f < p.total_frames; f += gridDim.x) {
+        if (ST && (int)(f % p.nts) >= spec_row_frames<ST>(p, (int)(f / p.nts))) continue;     // block-uniform: past this row's frames
         const float *x = p.in + (f / p.nts) * (long)p.input_size + (f % p.nts) * (long)p.step;
         for (int n = threadIdx.x; n < p.window_size; n += blockDim.x) frame[n] = p.window[n] * x[n];
         __syncthreads();
@@ -604,7 +627,8 @@ __global__ __launch_bounds__(256) void spectrogram_dft_kernel(SpecParams p) {
 static int spectrogram_launch(const float *d_in, const float *d_window, const float *d_twiddle, float *d_out,
                               int B, int input_size, int nfft, int window_size, int step,
                               int nfreq, int nts, float fft_norm, int mode, float scale,
-                              const int *d_mel_tab, const float *d_mel_w, int n_mels, float mel_eps, int mel_log) {
+                              const int *d_mel_tab, const float *d_mel_w, int n_mels, float mel_eps, int mel_log,
+                              const int *d_row_frames = nullptr, const int *d_row_len = nullptr) {
     if (B <= 0 || nts <= 0) return 0;
     if (window_size > nfft) return nntk_fail_msg("spectrogram: window_size must be <= nfft");
     SpecParams p;
@@ -614,6 +638,7 @@ static int spectrogram_launch(const float *d_in, const float *d_window, const fl
     p.input_size = input_size; p.nfft = nfft; p.window_size = window_size; p.step = step;
     p.nfreq = nfreq; p.nts = nts; p.fft_norm = fft_norm; p.scale = scale; p.inv_scale = (float)(1.0 / (double)scale); p.mode = mode;
     p.mel_tab = d_mel_tab; p.mel_w = d_mel_w; p.n_mels = n_mels; p.mel_eps = mel_eps; p.mel_log = mel_log;
+    const bool st = d_row_frames != nullptr;
     const bool mel = d_mel_tab != nullptr;
     if (mel && nfft != 512) return 1;       // the caller runs the two-kernel form (K1, then the k = 1 GEMM)
 #ifdef NNTK_SPEC_DBG
@@ -649,9 +674,22 @@ static int spectrogram_launch(const float *d_in, const float *d_window, const fl
                                  : (ld3 ? spectrogram512_kernel<M, N, Z, 3> : spectrogram512_kernel<M, N, Z, 4>))
 #endif
 #define SPEC_KERN(M, N) (nz7 ? SPEC_KERN2(M, N, true) : SPEC_KERN2(M, N, false))
+#define SPEC_KERN_ST2(M, N, Z) (mel ? (ld3 ? spectrogram512_kernel<M, N, Z, 3, true, false, true> : spectrogram512_kernel<M, N, Z, 4, true, false, true>) \
+                                    : (ld3 ? spectrogram512_kernel<M, N, Z, 3, false, false, true> : spectrogram512_kernel<M, N, Z, 4, false, false, true>))
+#define SPEC_KERN_ST(M, N) (nz7 ? SPEC_KERN_ST2(M, N, true) : SPEC_KERN_ST2(M, N, false))
         auto kern = mode == 0 ? (norm ? SPEC_KERN(0, true) : SPEC_KERN(0, false))
                               : (norm ? SPEC_KERN(1, true) : SPEC_KERN(1, false));
         p.ppw = ppw;
+        if (st) {
+            auto kst = mode == 0 ? (norm ? SPEC_KERN_ST(0, true) : SPEC_KERN_ST(0, false))
+                                 : (norm ? SPEC_KERN_ST(1, true) : SPEC_KERN_ST(1, false));
+            SpecRowsParams ps;
+            static_cast<SpecParams &>(ps) = p;
+            ps.row_frames = d_row_frames; ps.row_len = d_row_len;
+            hipLaunchKernelGGL(kst, dim3(gx, gy), dim3(256), 0, nntk_stream(), ps);
+            NNTK_LAUNCH_CHECK("spectrogram512_kernel<ST>");
+            return 0;
+        }
         hipLaunchKernelGGL(kern, dim3(gx, gy), dim3(256), 0, nntk_stream(), p);
         NNTK_LAUNCH_CHECK("spectrogram512_kernel");
     } else if (MixedPlan plan; nfft <= 4096 && mixed_plan(nfft, &plan)) {
@@ -659,13 +697,27 @@ static int spectrogram_launch(const float *d_in, const float *d_window, const fl
         const long g = pairs < 8192 ? pairs : 8192;
         int bs = (nfft / 4 + 63) & ~63;                     // one radix-4 butterfly per thread where the frame is long enough
         bs = bs < 64 ? 64 : bs > 256 ? 256 : bs;
-        hipLaunchKernelGGL(spectrogram_mixed_kernel, dim3((unsigned)g), dim3(bs), (size_t)nfft * 2 * sizeof(f2), nntk_stream(), p, plan);
+        if (st) {
+            SpecRowsParams ps;
+            static_cast<SpecParams &>(ps) = p;
+            ps.row_frames = d_row_frames; ps.row_len = d_row_len;
+            hipLaunchKernelGGL(spectrogram_mixed_kernel<true>, dim3((unsigned)g), dim3(bs), (size_t)nfft * 2 * sizeof(f2), nntk_stream(), ps, plan);
+        } else {
+            hipLaunchKernelGGL(spectrogram_mixed_kernel<false>, dim3((unsigned)g), dim3(bs), (size_t)nfft * 2 * sizeof(f2), nntk_stream(), p, plan);
+        }
         NNTK_LAUNCH_CHECK("spectrogram_mixed_kernel");
     } else {
         long g = p.total_frames < 4096 ? p.total_frames : 4096;
         size_t lds = (size_t)window_size * sizeof(float);
         if (lds > 64 * 1024) return nntk_fail_msg("spectrogram: window too large for the generic DFT kernel");
-        hipLaunchKernelGGL(spectrogram_dft_kernel, dim3((unsigned)g), dim3(256), lds, nntk_stream(), p);
+        if (st) {
+            SpecRowsParams ps;
+            static_cast<SpecParams &>(ps) = p;
+            ps.row_frames = d_row_frames; ps.row_len = d_row_len;
+            hipLaunchKernelGGL(spectrogram_dft_kernel<true>, dim3((unsigned)g), dim3(256), lds, nntk_stream(), ps);
+        } else {
+            hipLaunchKernelGGL(spectrogram_dft_kernel<false>, dim3((unsigned)g), dim3(256), lds, nntk_stream(), p);
+        }
         NNTK_LAUNCH_CHECK("spectrogram_dft_kernel");
     }
     return 0;
@@ -688,4 +740,17 @@ extern "C" int nntk_shim_spectrogram_mel(const float *d_in, const float *d_windo
     if (!d_mel_tab || !d_mel_w || n_mels <= 0) return nntk_fail_msg("spectrogram_mel: missing filter table");
     return spectrogram_launch(d_in, d_window, d_twiddle, d_out, B, input_size, nfft, window_size, step, nfreq, nts, fft_norm,
                               mode, scale, d_mel_tab, d_mel_w, n_mels, eps, do_log);
+}
+
+// The streaming calls (spectrogram.c SpectrogramApplyDeviceStream / LogMel): d_in = [B][row_stride] assembled rows (tail + new samples),
+// row b holding d_cnt[B + b] samples and yielding d_cnt[b] frames, d_out [B][max_frames][nfreq or n_mels]; rows past a row's frames are
+// not written.  Mel arguments NULL / 0 for the plain spectrogram; 1 (nothing launched) when the fused mel form does not take nfft.
+extern "C" int nntk_shim_spectrogram_rows(const float *d_in, const float *d_window, const float *d_twiddle, float *d_out,
+                                          int B, int row_stride, int nfft, int window_size, int step, int nfreq, int max_frames,
+                                          float fft_norm, int mode, float scale, const int *d_cnt,
+                                          const int *d_mel_tab, const float *d_mel_w, int n_mels, float eps, int do_log) {
+    if (!d_cnt) return nntk_fail_msg("spectrogram_rows: missing row counts");
+    if (d_mel_tab && (!d_mel_w || n_mels <= 0)) return nntk_fail_msg("spectrogram_rows: missing filter table");
+    return spectrogram_launch(d_in, d_window, d_twiddle, d_out, B, row_stride, nfft, window_size, step, nfreq, max_frames, fft_norm,
+                              mode, scale, d_mel_tab, d_mel_w, n_mels, eps, do_log, d_cnt, d_cnt + B);
 }

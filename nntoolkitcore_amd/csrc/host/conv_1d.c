@@ -5,6 +5,7 @@
  * kernel (csrc/hip/conv1d.hip) on first use.
  */
 #include <stdlib.h>
+#include <stdio.h>
 #include <string.h>
 #include "nntk_internal.h"
 
@@ -18,6 +19,7 @@ struct Conv1dStruct {
     float *d_wpf;               /* the same weights packed with a flat K axis (conv1d_flatk.hip), when the shape takes that kernel */
     int flatk_ok;
     nntk_devbuf d_in, d_out;
+    nntk_devbuf d_seq, d_cnt;   /* the streaming call: assembled rows (history ++ new rows), per-row counts (ints) */
     /* training mode (conv_1d.c:104-108): mini-batch size, the last forward pass's input kept on the device for the
      * gradient, and the gradient scratch */
     int training, mini_batch;
@@ -71,6 +73,7 @@ void Conv1dDestroy(Conv1d filter) {
     nntk_shim_free(filter->d_bias);
     nntk_devbuf_free(&filter->d_in);
     nntk_devbuf_free(&filter->d_out);
+    nntk_devbuf_free(&filter->d_seq); nntk_devbuf_free(&filter->d_cnt);
     nntk_devbuf_free(&filter->d_cache); nntk_devbuf_free(&filter->d_dout); nntk_devbuf_free(&filter->d_grad);
     nntk_devbuf_free(&filter->d_wraw); nntk_devbuf_free(&filter->d_scratch);
     nntk_devbuf_free(&filter->d_pad); nntk_devbuf_free(&filter->d_wpk);
@@ -146,17 +149,23 @@ int Conv1dBroadcastWeights(Conv1d filter, int root) {
     return conv_upload(filter);
 }
 
-static int conv_launch(Conv1d f, const float *d_bn, float eps, int act_kind, float relu_a,
-                       const float *d_in, float *d_out, int batch) {
+/* T / Tout: rows per input / output sequence (the config's, except for the streaming call's assembled rows).  The route depends on the
+ * layer only (flatk_ok, the packed shapes), never on T. */
+static int conv_launch_rows(Conv1d f, const float *d_bn, float eps, int act_kind, float relu_a,
+                            const float *d_in, float *d_out, int batch, int T, int Tout) {
     const Conv1dConfig *c = &f->config;
     if (f->flatk_ok) {
-        int rc = nntk_shim_conv1d_flatk(d_in, f->d_wpf, f->d_bias, d_bn, eps, act_kind, relu_a, d_out, batch, c->input_size,
-                                        c->input_feature_channels, c->output_feature_channels, c->kernel_size, c->output_size);
+        int rc = nntk_shim_conv1d_flatk(d_in, f->d_wpf, f->d_bias, d_bn, eps, act_kind, relu_a, d_out, batch, T,
+                                        c->input_feature_channels, c->output_feature_channels, c->kernel_size, Tout);
         if (rc <= 0) return rc;
     }
-    return nntk_shim_conv1d(d_in, f->d_wp, f->d_bias, d_bn, eps, act_kind, relu_a, d_out, batch, c->input_size,
+    return nntk_shim_conv1d(d_in, f->d_wp, f->d_bias, d_bn, eps, act_kind, relu_a, d_out, batch, T,
                             c->input_feature_channels, c->output_feature_channels, c->kernel_size, c->stride,
-                            c->output_size, 0);
+                            Tout, 0);
+}
+static int conv_launch(Conv1d f, const float *d_bn, float eps, int act_kind, float relu_a,
+                       const float *d_in, float *d_out, int batch) {
+    return conv_launch_rows(f, d_bn, eps, act_kind, relu_a, d_in, d_out, batch, f->config.input_size, f->config.output_size);
 }
 
 int Conv1dApplyDevice(Conv1d filter, const float *d_input, float *d_output, int batch) {
@@ -184,6 +193,96 @@ int Conv1dBatchNormActivationApplyDevice(Conv1d filter, BatchNorm bn, Activation
     int kind = act ? act->kind : NNTK_ACT_IDENTITY;
     float a = act ? act->relu_a : 1.0f;
     return conv_launch(filter, d_bn, eps, kind, a, d_input, d_output, batch);
+}
+
+/* ------------------------------ streaming --------------------------------
+ * m = hist_len + n_new rows; O = m >= k ? (m - k) / s + 1 : 0 outputs; the next history is rows O * s .. m - 1 (at most k - 1 of them:
+ * stride <= kernel_size, else the next window would start inside input not yet received).  Pure host arithmetic on configs. */
+static int conv_stream_cfg_ok(Conv1dConfig cfg) {
+    return cfg.kernel_size > 0 && cfg.stride > 0 && cfg.stride <= cfg.kernel_size && cfg.input_size >= 0;
+}
+int nntk_conv1d_stream_sizes(Conv1dConfig cfg, int *hist_rows, int *max_outputs) {
+    nntk_shim_clear_error();
+    if (!conv_stream_cfg_ok(cfg)) NNTK_FAIL("nntk_conv1d_stream_sizes: needs 0 < stride <= kernel_size");
+    if (hist_rows) *hist_rows = cfg.kernel_size - 1;
+    if (max_outputs) *max_outputs = (cfg.input_size + cfg.stride - 1) / cfg.stride;
+    return 0;
+}
+int nntk_conv1d_stream_plan(Conv1dConfig cfg, int hist_len, int n_new, int final, int *n_out, int *next_hist_len) {
+    nntk_shim_clear_error();
+    if (!conv_stream_cfg_ok(cfg)) NNTK_FAIL("nntk_conv1d_stream_plan: needs 0 < stride <= kernel_size");
+    if (hist_len < 0 || hist_len > cfg.kernel_size - 1 || n_new < 0 || n_new > cfg.input_size)
+        NNTK_FAIL("nntk_conv1d_stream_plan: hist_len outside [0, kernel_size - 1] or n_new outside [0, input_size]");
+    const int m = hist_len + n_new;
+    const int O = m >= cfg.kernel_size ? (m - cfg.kernel_size) / cfg.stride + 1 : 0;
+    if (n_out) *n_out = O;
+    if (next_hist_len) *next_hist_len = final ? 0 : m - O * cfg.stride;
+    return 0;
+}
+
+static int ranges_overlap(const void *a, size_t na, const void *b, size_t nb) {
+    const char *x = (const char *)a, *y = (const char *)b;
+    return na > 0 && nb > 0 && x < y + nb && y < x + na;
+}
+
+int Conv1dBatchNormActivationApplyDeviceStream(Conv1d filter, BatchNorm bn, ActivationFunction act, const float *d_input,
+                                               const int *n_new, const int *final, float *d_hist, int *hist_len, float *d_output,
+                                               int *n_out, int batch) {
+    nntk_shim_clear_error();
+    char msg[256];
+    if (!filter) NNTK_FAIL("Conv1dBatchNormActivationApplyDeviceStream: NULL conv handle");
+    const Conv1dConfig *c = &filter->config;
+    if (batch < 0) { snprintf(msg, sizeof msg, "Conv1dBatchNormActivationApplyDeviceStream: batch %d < 0", batch); NNTK_FAIL(msg); }
+    int hr, mo;
+    if (nntk_conv1d_stream_sizes(*c, &hr, &mo)) return -1;
+    if (bn && nntk_batch_norm_channels(bn) != c->output_feature_channels)
+        NNTK_FAIL("fused conv+bn: BatchNorm feature_channels must equal conv output channels");
+    if (!nntk_act_fusable(act)) NNTK_FAIL("fused conv+bn+act: activation must be identity/sigmoid/tanh/relu");
+    if (batch == 0) return 0;
+    if (!d_input || !n_new || !d_hist || !hist_len || !d_output || !n_out)
+        NNTK_FAIL("Conv1dBatchNormActivationApplyDeviceStream: NULL argument");
+    for (int b = 0; b < batch; ++b) {
+        if (n_new[b] < 0 || n_new[b] > c->input_size) {
+            snprintf(msg, sizeof msg, "Conv1dBatchNormActivationApplyDeviceStream: n_new[%d] = %d is outside [0, %d]", b, n_new[b], c->input_size);
+            NNTK_FAIL(msg);
+        }
+        if (hist_len[b] < 0 || hist_len[b] > hr) {
+            snprintf(msg, sizeof msg, "Conv1dBatchNormActivationApplyDeviceStream: hist_len[%d] = %d is outside [0, %d]", b, hist_len[b], hr);
+            NNTK_FAIL(msg);
+        }
+    }
+    const int Cin = c->input_feature_channels, Cout = c->output_feature_channels;
+    const size_t n_in = (size_t)batch * c->input_size * Cin * 4, n_h = (size_t)batch * hr * Cin * 4, n_o = (size_t)batch * mo * Cout * 4;
+    if (ranges_overlap(d_output, n_o, d_input, n_in) || ranges_overlap(d_output, n_o, d_hist, n_h) || ranges_overlap(d_hist, n_h, d_input, n_in))
+        NNTK_FAIL("Conv1dBatchNormActivationApplyDeviceStream: the output, the input and the history buffer must not overlap");
+    if (conv_ensure(filter, 0)) return -1;
+    const float *d_bn = NULL;
+    float eps = 0.f;
+    if (bn) {
+        d_bn = nntk_batch_norm_device_block(bn, 0);
+        if (!d_bn) return -1;
+        eps = nntk_batch_norm_epsilon(bn);
+    }
+    int *h = (int *)malloc((size_t)4 * batch * sizeof(int));
+    if (!h) NNTK_FAIL("out of host memory");
+    /* [4][B]: outputs | rows in the assembled row | old history | new history (nntk_shim.h, streaming calls) */
+    for (int b = 0; b < batch; ++b) {
+        int O, nh;
+        (void)nntk_conv1d_stream_plan(*c, hist_len[b], n_new[b], final ? final[b] : 0, &O, &nh);
+        h[b] = O; h[batch + b] = hist_len[b] + n_new[b]; h[2 * batch + b] = hist_len[b]; h[3 * batch + b] = nh;
+    }
+    const int S = hr + c->input_size;     /* (S - k) / s + 1 = max_outputs */
+    int *d_cnt = (int *)nntk_devbuf_reserve(&filter->d_cnt, (size_t)4 * batch);
+    float *d_seq = nntk_devbuf_reserve(&filter->d_seq, (size_t)batch * S * Cin);
+    int rc = (!d_cnt || !d_seq) ? -1 : nntk_shim_upload_ints(d_cnt, h, 4L * batch);
+    if (!rc) rc = nntk_shim_stream_gather(d_input, d_hist, d_seq, d_cnt, batch, c->input_size, hr, Cin);
+    if (!rc && mo > 0)
+        rc = conv_launch_rows(filter, d_bn, eps, act ? act->kind : NNTK_ACT_IDENTITY, act ? act->relu_a : 1.0f, d_seq, d_output, batch, S, mo);
+    if (!rc) rc = nntk_shim_varlen_zero_pad(d_output, d_cnt, batch, mo, Cout);
+    if (!rc)
+        for (int b = 0; b < batch; ++b) { n_out[b] = h[b]; hist_len[b] = h[3 * batch + b]; }
+    free(h);
+    return rc < 0 ? -1 : 0;
 }
 
 /* additive: the fused layer's output as a frag3 tensor [batch][Tout][Cout] (include/nntoolkitcore_hip.h "frag3 tensors") -- what a

@@ -8,6 +8,7 @@
  */
 #include <math.h>
 #include <stdlib.h>
+#include <stdio.h>
 #include <string.h>
 #include "nntk_internal.h"
 
@@ -355,6 +356,7 @@ int DenseCalculateGradientDevice(Dense filter, float *d_grad_Wb, float *d_dX, co
 struct TimeDistributedDenseStruct {
     TimeDistributedDenseConfig config;
     Dense dense;
+    nntk_devbuf d_len;          /* TimeDistributedDenseApplyDeviceVarLen: the row lengths (ints) */
 };
 
 /* time_distributed_dense.c:18-23 */
@@ -409,7 +411,8 @@ int TimeDistributedDenseCalculateGradientDevice(TimeDistributedDense filter, flo
 DenseWeights *TimeDistributedDenseGetWeights(TimeDistributedDense filter) { return DenseGetWeights(filter->dense); }
 void TimeDistributedDenseDestroy(TimeDistributedDense filter) {
     if (!filter) return;
-    DenseDestroy(filter->dense);
+    DenseDestroy(filter->dense);        /* (synchronises) */
+    nntk_devbuf_free(&filter->d_len);
     free(filter);
 }
 int TimeDistributedDenseSyncWeights(TimeDistributedDense filter) {
@@ -480,6 +483,33 @@ int LSTMTimeDistributedDenseApplyDevice(LSTM lstm, TimeDistributedDense tdd, con
     if (LSTMApplyDeviceFrag3(lstm, d_input, NULL, NULL, d_h3, batch)) return -1;
     if (dense_ensure(tdd->dense, 0)) return -1;
     return dense_frag3_device(tdd->dense, d_h3, d_output, batch, T);
+}
+/* rows t >= lengths[b] are zeros, rows t < lengths[b] are those of TimeDistributedDenseApplyDevice (the same GEMM on every row) */
+int TimeDistributedDenseApplyDeviceVarLen(TimeDistributedDense filter, const float *d_input, float *d_output, int batch, const int *lengths) {
+    nntk_shim_clear_error();
+    char msg[160];
+    if (!filter) NNTK_FAIL("TimeDistributedDenseApplyDeviceVarLen: NULL handle");
+    const int ts = filter->config.ts;
+    if (batch < 0) { snprintf(msg, sizeof msg, "TimeDistributedDenseApplyDeviceVarLen: batch %d < 0", batch); NNTK_FAIL(msg); }
+    int pad = 0;
+    if (lengths)
+        for (int b = 0; b < batch; ++b) {
+            if (lengths[b] < 0 || lengths[b] > ts) {
+                snprintf(msg, sizeof msg, "TimeDistributedDenseApplyDeviceVarLen: lengths[%d] = %d is outside [0, %d]", b, lengths[b], ts);
+                NNTK_FAIL(msg);
+            }
+            pad |= lengths[b] < ts;
+        }
+    if (batch == 0 || ts <= 0) return 0;
+    if (!d_input || !d_output) NNTK_FAIL("TimeDistributedDenseApplyDeviceVarLen: NULL tensor");
+    const size_t n_in = (size_t)batch * ts * filter->dense->config.input_size * 4, n_o = (size_t)batch * ts * filter->dense->config.output_size * 4;
+    const char *o = (const char *)d_output, *i = (const char *)d_input;
+    if (o < i + n_in && i < o + n_o) NNTK_FAIL("TimeDistributedDenseApplyDeviceVarLen: the output must not overlap the input");
+    if (dense_ensure(filter->dense, 0)) return -1;
+    int *d_len = pad ? (int *)nntk_devbuf_reserve(&filter->d_len, (size_t)batch) : NULL;
+    if (pad && (!d_len || nntk_shim_upload_ints(d_len, lengths, batch))) return -1;
+    if (dense_rows_device(filter->dense, d_input, d_output, (long)batch * ts)) return -1;
+    return pad ? nntk_shim_varlen_zero_pad(d_output, d_len, batch, ts, filter->dense->config.output_size) : 0;
 }
 int TimeDistributedDenseApplyDevice(TimeDistributedDense filter, const float *d_input, float *d_output, int batch) {
     nntk_shim_clear_error();

@@ -212,6 +212,65 @@ int LogMelSpectrogramApplyDevice(LogMelSpectrogram filter, const float *d_input,
     return mel_rows_device(filter->bank, d_spec, d_output, rows, 1);
 }
 
+/* streaming form (include/nntoolkitcore_hip.h "Streaming a whole stack"): the fused form and the two-kernel form exactly where
+ * LogMelSpectrogramApplyDevice takes them, so a row's frames have that call's bits.  The two-kernel form zeroes the padding rows after
+ * the mel GEMM (which would turn zero spectra into log(eps)). */
+int LogMelSpectrogramApplyDeviceStream(LogMelSpectrogram filter, const float *d_input, const int *n_new, const int *final, float *d_tail,
+                                       int *tail_len, float *d_output, int *frames, int batch) {
+    nntk_shim_clear_error();
+    static const char who[] = "LogMelSpectrogramApplyDeviceStream";
+    if (!filter) NNTK_FAIL("LogMelSpectrogramApplyDeviceStream: NULL handle");
+    const SpectrogramConfig c = SpectrogramGetConfig(filter->spectrogram);
+    const int n_mels = filter->bank->config.n_mels;
+    int tf, mf;
+    if (nntk_spectrogram_stream_sizes(c, &tf, &mf)) return -1;
+    if (batch > 0) {
+        /* the caller's buffers, for both forms, before anything is reserved, uploaded or enqueued (the two-kernel form's own
+         * spectrogram call only sees the handle's scratch as its output) */
+        if (!d_input || !n_new || !d_tail || !tail_len || !d_output || !frames) NNTK_FAIL("LogMelSpectrogramApplyDeviceStream: NULL argument");
+        const size_t n_out = (size_t)batch * mf * n_mels * 4, n_in = (size_t)batch * c.input_size * 4, n_tail = (size_t)batch * tf * 4;
+        const char *o = (const char *)d_output, *i = (const char *)d_input, *t = (const char *)d_tail;
+        if ((o < i + n_in && i < o + n_out) || (o < t + n_tail && t < o + n_out) || (t < i + n_in && i < t + n_tail))
+            NNTK_FAIL("LogMelSpectrogramApplyDeviceStream: the output, the input and the tail buffer must not overlap");
+    }
+    int fused_off = 0;
+    (void)nntk_shim_get_option("spec_variant", &fused_off);
+    if (fused_off != 1 && batch > 0) {
+        int rs = mel_ensure_sparse(filter->bank);
+        if (rs < 0) return -1;
+        if (rs == 0) {
+            int rc = nntk_spectrogram_stream_device(filter->spectrogram, who, d_input, n_new, final, d_tail, tail_len, d_output, frames,
+                                                    batch, n_mels, filter->bank->d_tab, filter->bank->d_runs, n_mels, NULL);
+            if (rc <= 0) return rc;
+        }
+    }
+    if (batch <= 0)
+        return nntk_spectrogram_stream_device(filter->spectrogram, who, d_input, n_new, final, d_tail, tail_len, NULL, frames, batch,
+                                              c.nfreq, NULL, NULL, 0, NULL);
+    if (mel_ensure(filter->bank)) return -1;           /* the GEMM's weights are in place before the tail is touched */
+    float *d_spec = nntk_devbuf_reserve(&filter->d_spec, (size_t)batch * mf * c.nfreq);
+    if (!d_spec) return -1;
+    const int *d_frames = NULL;
+    int *fr = (int *)malloc((size_t)batch * sizeof(int));
+    int *tl = (int *)malloc((size_t)batch * sizeof(int));
+    if (!fr || !tl) { free(fr); free(tl); NNTK_FAIL("out of host memory"); }
+    memcpy(tl, tail_len, (size_t)batch * sizeof(int));
+    /* counts go to the caller only once every step is enqueued */
+    int rc = nntk_spectrogram_stream_device(filter->spectrogram, who, d_input, n_new, final, d_tail, tl, d_spec, fr, batch, c.nfreq,
+                                            NULL, NULL, 0, &d_frames);
+    /* The spectrogram call leaves d_spec's rows past each row's frames as they were (stale scratch, possibly non-finite).  The GEMM
+     * runs over all batch * max_frames rows in one launch -- every output row is its own dot products, so those rows cannot reach a
+     * valid one -- and the padding pass that follows overwrites their outputs with zeros.  That pass must stay right after the GEMM. */
+    if (rc == 0) rc = mel_rows_device(filter->bank, d_spec, d_output, (long)batch * mf, 1);
+    if (rc == 0) rc = nntk_shim_varlen_zero_pad(d_output, d_frames, batch, mf, n_mels);
+    if (rc == 0) {
+        memcpy(frames, fr, (size_t)batch * sizeof(int));
+        memcpy(tail_len, tl, (size_t)batch * sizeof(int));
+    }
+    free(fr); free(tl);
+    return rc;
+}
+
 int LogMelSpectrogramApplyBatch(LogMelSpectrogram filter, const float *input, float *output, int batch) {
     nntk_shim_clear_error();
     if (!filter) NNTK_FAIL("LogMelSpectrogramApplyBatch: NULL handle");

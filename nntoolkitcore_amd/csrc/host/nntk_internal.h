@@ -79,6 +79,13 @@ const float *nntk_mel_weights(MelFilterBank bank);   /* host [nbins, n_mels] */
 int nntk_spectrogram_apply_mel_device(Spectrogram filter, const float *d_input, float *d_output, int batch,
                                       const int *d_mel_tab, const float *d_mel_w, int n_mels, float eps, int do_log);
 
+/* the streaming spectrogram / log-mel path (spectrogram.c): 0 done, 1 the fused mel form does not take this configuration (nothing
+ * enqueued), -1 error (nothing enqueued, nothing written).  d_frames_out != NULL: the padding rows are left to the caller, which gets the
+ * device copy of the frame counts there. */
+int nntk_spectrogram_stream_device(Spectrogram f, const char *who, const float *d_input, const int *n_new, const int *final,
+                                   float *d_tail, int *tail_len, float *d_output, int *frames, int batch, int orow,
+                                   const int *d_mel_tab, const float *d_mel_w, int n_mels, const int **d_frames_out);
+
 /* recurrent.c, for the fused LSTM -> TimeDistributedDense call in dense.c */
 void nntk_lstm_dims(LSTM f, int *T, int *in, int *H, int *return_sequences);
 float *nntk_lstm_frag3_scratch(LSTM f, int batch);       /* the handle's own frag3 output buffer [batch][T][H] */

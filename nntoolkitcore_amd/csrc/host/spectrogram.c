@@ -7,6 +7,7 @@
  */
 #include <math.h>
 #include <stdlib.h>
+#include <stdio.h>
 #include <string.h>
 #include "nntk_internal.h"
 
@@ -44,6 +45,7 @@ struct SpectrogramStruct {
     int window_dirty;
     float *d_window, *d_twiddle;
     nntk_devbuf d_in, d_out;
+    nntk_devbuf d_seq, d_cnt;   /* the streaming calls: assembled rows (tail ++ new samples), per-row counts (ints) */
 };
 
 /* spectrogram.c:59-70 */
@@ -108,6 +110,8 @@ void SpectrogramDestroy(Spectrogram filter) {
     nntk_shim_free(filter->d_twiddle);
     nntk_devbuf_free(&filter->d_in);
     nntk_devbuf_free(&filter->d_out);
+    nntk_devbuf_free(&filter->d_seq);
+    nntk_devbuf_free(&filter->d_cnt);
     free(filter->window);
     free(filter);
 }
@@ -152,6 +156,104 @@ int nntk_spectrogram_apply_mel_device(Spectrogram filter, const float *d_input, 
     return nntk_shim_spectrogram_mel(d_input, filter->d_window, filter->d_twiddle, d_output, batch, c->input_size, c->nfft,
                                      c->window_size, c->step, c->nfreq, c->ntime_series, c->fft_normalization_factor,
                                      filter->mode, filter->scale_factor, d_mel_tab, d_mel_w, n_mels, eps, do_log);
+}
+
+/* ------------------------------ streaming --------------------------------
+ * Row b's virtual sequence is s = tail ++ new, m = tail_len + n_new samples; F = m >= window_size ? (m - noverlap) / step : 0 complete
+ * frames; emitted E = final ? F : F & ~1 (whole pairs only: K1 transforms frames in pairs, so holding an odd frame back keeps every
+ * pair the one-shot call forms); the next tail is s[E * step : m].  Pure host arithmetic on configs. */
+static int spec_stream_cfg_ok(SpectrogramConfig cfg) {
+    return cfg.window_size > 0 && cfg.step > 0 && cfg.noverlap >= 0 && cfg.input_size >= 0 && cfg.nfft >= cfg.window_size;
+}
+int nntk_spectrogram_stream_sizes(SpectrogramConfig cfg, int *tail_floats, int *max_frames) {
+    nntk_shim_clear_error();
+    if (!spec_stream_cfg_ok(cfg)) NNTK_FAIL("nntk_spectrogram_stream_sizes: invalid spectrogram config");
+    if (tail_floats) *tail_floats = cfg.window_size + cfg.step - 1;
+    if (max_frames) *max_frames = (cfg.input_size + cfg.step - 1) / cfg.step + 1;
+    return 0;
+}
+int nntk_spectrogram_stream_plan(SpectrogramConfig cfg, int tail_len, int n_new, int final, int *frames, int *next_tail_len) {
+    nntk_shim_clear_error();
+    if (!spec_stream_cfg_ok(cfg)) NNTK_FAIL("nntk_spectrogram_stream_plan: invalid spectrogram config");
+    if (tail_len < 0 || tail_len > cfg.window_size + cfg.step - 1 || n_new < 0 || n_new > cfg.input_size)
+        NNTK_FAIL("nntk_spectrogram_stream_plan: tail_len outside [0, window_size + step - 1] or n_new outside [0, input_size]");
+    const int m = tail_len + n_new;
+    const int F = m >= cfg.window_size ? (m - cfg.noverlap) / cfg.step : 0;
+    const int E = final ? F : (F & ~1);
+    if (frames) *frames = E;
+    if (next_tail_len) *next_tail_len = final ? 0 : m - E * cfg.step;
+    return 0;
+}
+
+static int ranges_overlap(const void *a, size_t na, const void *b, size_t nb) {
+    const char *x = (const char *)a, *y = (const char *)b;
+    return na > 0 && nb > 0 && x < y + nb && y < x + na;
+}
+
+/* The one streaming path of SpectrogramApplyDeviceStream and LogMelSpectrogramApplyDeviceStream: validation (nothing enqueued, nothing
+ * written on -1), per-row plans, one count upload, the row assembly (tail update in place), K1's ST instantiation on the assembled rows
+ * and -- unless the caller zeroes its own output (*d_frames_out set: the unfused log-mel form pads after its GEMM) -- the padding rows.
+ * d_mel_tab != NULL: the fused mel form (returns 1, nothing enqueued, when it does not take this nfft).  orow = floats per output row. */
+int nntk_spectrogram_stream_device(Spectrogram f, const char *who, const float *d_input, const int *n_new, const int *final,
+                                   float *d_tail, int *tail_len, float *d_output, int *frames, int batch, int orow,
+                                   const int *d_mel_tab, const float *d_mel_w, int n_mels, const int **d_frames_out) {
+    char msg[256];
+    if (!f) { snprintf(msg, sizeof msg, "%s: NULL handle", who); NNTK_FAIL(msg); }
+    const SpectrogramConfig *c = &f->config;
+    if (batch < 0) { snprintf(msg, sizeof msg, "%s: batch %d < 0", who, batch); NNTK_FAIL(msg); }
+    int tf, mf;
+    if (nntk_spectrogram_stream_sizes(*c, &tf, &mf)) return -1;
+    if (batch == 0) return 0;
+    if (!d_input || !n_new || !d_tail || !tail_len || !d_output || !frames) { snprintf(msg, sizeof msg, "%s: NULL argument", who); NNTK_FAIL(msg); }
+    for (int b = 0; b < batch; ++b) {
+        if (n_new[b] < 0 || n_new[b] > c->input_size) {
+            snprintf(msg, sizeof msg, "%s: n_new[%d] = %d is outside [0, %d]", who, b, n_new[b], c->input_size);
+            NNTK_FAIL(msg);
+        }
+        if (tail_len[b] < 0 || tail_len[b] > tf) {
+            snprintf(msg, sizeof msg, "%s: tail_len[%d] = %d is outside [0, %d]", who, b, tail_len[b], tf);
+            NNTK_FAIL(msg);
+        }
+    }
+    const size_t n_in = (size_t)batch * c->input_size, n_tail = (size_t)batch * tf, n_out = (size_t)batch * mf * orow;
+    if (ranges_overlap(d_output, n_out * 4, d_input, n_in * 4) || ranges_overlap(d_output, n_out * 4, d_tail, n_tail * 4) ||
+        ranges_overlap(d_tail, n_tail * 4, d_input, n_in * 4)) {
+        snprintf(msg, sizeof msg, "%s: the output, the input and the tail buffer must not overlap", who);
+        NNTK_FAIL(msg);
+    }
+    if (d_mel_tab && (c->nfft != 512 || n_mels > 257)) return 1;      /* (spectrogram_launch's own test for the fused form) */
+    int *h = (int *)malloc((size_t)4 * batch * sizeof(int));
+    if (!h) NNTK_FAIL("out of host memory");
+    /* [4][B]: frames | samples in the assembled row | old tail | new tail (nntk_shim.h, streaming calls) */
+    for (int b = 0; b < batch; ++b) {
+        int E, nt;
+        (void)nntk_spectrogram_stream_plan(*c, tail_len[b], n_new[b], final ? final[b] : 0, &E, &nt);
+        h[b] = E; h[batch + b] = tail_len[b] + n_new[b]; h[2 * batch + b] = tail_len[b]; h[3 * batch + b] = nt;
+    }
+    const int S = tf + c->input_size;
+    int *d_cnt = (int *)nntk_devbuf_reserve(&f->d_cnt, (size_t)4 * batch);
+    float *d_seq = nntk_devbuf_reserve(&f->d_seq, (size_t)batch * S);
+    int rc = (!d_cnt || !d_seq || spectrogram_ensure(f)) ? -1 : 0;
+    if (!rc) rc = nntk_shim_upload_ints(d_cnt, h, 4L * batch);
+    if (!rc) rc = nntk_shim_stream_gather(d_input, d_tail, d_seq, d_cnt, batch, c->input_size, tf, 1);
+    if (!rc) rc = nntk_shim_spectrogram_rows(d_seq, f->d_window, f->d_twiddle, d_output, batch, S, c->nfft, c->window_size, c->step,
+                                             c->nfreq, mf, c->fft_normalization_factor, f->mode, f->scale_factor, d_cnt,
+                                             d_mel_tab, d_mel_w, n_mels, 1.5849e-13f, 1);
+    if (!rc && !d_frames_out) rc = nntk_shim_varlen_zero_pad(d_output, d_cnt, batch, mf, orow);
+    if (!rc) {
+        for (int b = 0; b < batch; ++b) { frames[b] = h[b]; tail_len[b] = h[3 * batch + b]; }
+        if (d_frames_out) *d_frames_out = d_cnt;
+    }
+    free(h);
+    return rc < 0 ? -1 : 0;
+}
+
+int SpectrogramApplyDeviceStream(Spectrogram f, const float *d_input, const int *n_new, const int *final, float *d_tail, int *tail_len,
+                                 float *d_output, int *frames, int batch) {
+    nntk_shim_clear_error();
+    if (!f) NNTK_FAIL("SpectrogramApplyDeviceStream: NULL handle");
+    return nntk_spectrogram_stream_device(f, "SpectrogramApplyDeviceStream", d_input, n_new, final, d_tail, tail_len, d_output, frames,
+                                          batch, f->config.nfreq, NULL, NULL, 0, NULL);
 }
 
 int SpectrogramApplyBatch(Spectrogram filter, const float *input, float *output, int batch) {

@@ -37,6 +37,38 @@ def _dp(t):
     return C.c_void_p(t.data_ptr())
 
 
+def _host_ints(a, B, what):
+    """a host int32 array of B entries that the C call may read and write (in place when `a` already is one)"""
+    if isinstance(a, np.ndarray) and a.dtype == np.int32 and a.flags.c_contiguous and a.ndim == 1:
+        assert a.shape[0] == B, what + ": one per row"
+        return a
+    v = np.ascontiguousarray(np.asarray(a, dtype=np.int32).reshape(-1))
+    assert v.shape[0] == B, what + ": one per row"
+    return v
+
+
+def _stream_call(fn, name, pre, x, row_shape, n_new, state, state_row, final, post_out, out):
+    """shared driver of the *ApplyDeviceStream wrappers: state = (device state tensor, host int32 lengths) -- both updated in place.
+    The C call reads [B][row_shape] input and [B][state_row] state and writes post_out: the tensors must be exactly that large."""
+    B = x.shape[0]
+    st, lens = state
+    if tuple(x.shape[1:]) != tuple(row_shape):
+        raise ValueError("%s: input rows must be %s (the handle's input_size), got %s" % (name, tuple(row_shape), tuple(x.shape[1:])))
+    if tuple(st.shape) != (B,) + tuple(state_row) or not st.is_contiguous():
+        raise ValueError("%s: state tensor must be contiguous %s, got %s" % (name, (B,) + tuple(state_row), tuple(st.shape)))
+    if out is not None and (tuple(out.shape) != tuple(post_out) or not out.is_contiguous()):
+        raise ValueError("%s: out must be contiguous %s, got %s" % (name, tuple(post_out), tuple(out.shape)))
+    assert isinstance(lens, np.ndarray) and lens.dtype == np.int32 and lens.shape == (B,), "state: (tensor, int32 [B] lengths)"
+    nn = _host_ints(n_new, B, "n_new")
+    fin = None if final is None else _host_ints(np.asarray(final, dtype=np.int32), B, "final")
+    counts = np.zeros(B, np.int32)
+    if out is None:
+        out = x.new_empty(post_out)
+    check(fn(*pre, _dp(x), nn.ctypes.data_as(capi.ip), fin.ctypes.data_as(capi.ip) if fin is not None else None,
+             _dp(st), lens.ctypes.data_as(capi.ip), _dp(out), counts.ctypes.data_as(capi.ip), B), name)
+    return out, counts
+
+
 def use_torch_stream():
     """Route every launch to torch's current HIP stream so torch events/timing see the kernels."""
     import torch
@@ -120,6 +152,27 @@ class Conv1d:
                                                          _dp(x), _dp(out), B), "Conv1dBatchNormActivationApplyDevice")
         return out
 
+    def stream_sizes(self):
+        """(hist_rows, max_outputs): nntk_conv1d_stream_sizes"""
+        a, b = C.c_int(), C.c_int()
+        check(capi.load().nntk_conv1d_stream_sizes(self.cfg, C.byref(a), C.byref(b)), "nntk_conv1d_stream_sizes")
+        return a.value, b.value
+
+    def new_stream_state(self, batch):
+        """(history [batch, k - 1, Cin] zeros on the current device, host int32 hist_len [batch] zeros)"""
+        import torch
+        hr, _ = self.stream_sizes()
+        return (torch.zeros((batch, hr, self.cfg.input_feature_channels), device="cuda"), np.zeros(batch, np.int32))
+
+    def apply_device_stream(self, x, n_new, state, bn=None, act=None, final=None, out=None):
+        """Conv1dBatchNormActivationApplyDeviceStream: x [B, input_size, Cin] chunk rows, row b brings n_new[b] of them.
+        Returns (out [B, max_outputs, Cout], n_out); the state (history tensor, hist_len) is updated in place."""
+        hr, mo = self.stream_sizes()
+        cin = self.cfg.input_feature_channels
+        return _stream_call(capi.load().Conv1dBatchNormActivationApplyDeviceStream, "Conv1dBatchNormActivationApplyDeviceStream",
+                            (self.h, bn.h if bn else None, act.h if act else None), x, (self.cfg.input_size, cin), n_new, state,
+                            (hr, cin), final, (x.shape[0], mo, self.cfg.output_feature_channels), out)
+
     def apply_device_frag3(self, x, out_f3=None, bn=None, act=None):
         """Conv1dBatchNormActivationApplyDeviceFrag3: the (fused) layer output [B, Tout, Cout] as a frag3 buffer."""
         B = x.shape[0]
@@ -199,10 +252,10 @@ class _Recurrent:
         check(self._apply_device(self.h, _dp(x), _dp(out), x.shape[0]), type(self).__name__ + "ApplyDevice")
         return out
 
-    def apply_device_varlen(self, x, lengths=None, h0=None, c0=None, return_state=False, out=None):
+    def apply_device_varlen(self, x, lengths=None, h0=None, c0=None, return_state=False, out=None, hT=None, cT=None):
         """Ragged batch with carried state (``*ApplyDeviceVarLen``): x [B,T,in] device tensor, row b runs its first
         lengths[b] steps (None: all T) from h0[b] (c0[b], LSTM); sequence outputs past a row's length are zeros.
-        Returns out, or (out, hT) / (out, hT, cT) with return_state."""
+        Returns out, or (out, hT) / (out, hT, cT) with return_state (written into hT / cT when given)."""
         B = x.shape[0]
         H = self.cfg.base.output_feature_channels
         if out is None:
@@ -213,10 +266,12 @@ class _Recurrent:
             assert lens.shape[0] == B, "lengths: one per row"
             lp = lens.ctypes.data_as(capi.ip)
         nul = C.c_void_p(None)
-        hT = x.new_empty((B, H)) if return_state else None
+        if return_state and hT is None:
+            hT = x.new_empty((B, H))
         state_in = [h0] + ([c0] if self._is_lstm else [])
         state = [_dp(t) if t is not None else nul for t in state_in]
-        cT = x.new_empty((B, H)) if (return_state and self._is_lstm) else None
+        if return_state and self._is_lstm and cT is None:
+            cT = x.new_empty((B, H))
         state += [_dp(hT) if hT is not None else nul] + ([_dp(cT) if cT is not None else nul] if self._is_lstm else [])
         check(self._apply_device_vl(self.h, _dp(x), _dp(out), B, lp, *state), type(self).__name__ + "ApplyDeviceVarLen")
         if not return_state:
@@ -510,6 +565,22 @@ class TimeDistributedDense:
               "TimeDistributedDenseApplyDevice")
         return out
 
+    def apply_device_varlen(self, x, lengths=None, out=None):
+        """TimeDistributedDenseApplyDeviceVarLen: rows t >= lengths[b] of the output are zeros"""
+        B = x.shape[0]
+        if tuple(x.shape[1:]) != (self.cfg.ts, self.cfg.dense.input_size):
+            raise ValueError("TimeDistributedDenseApplyDeviceVarLen: input must be [B, %d, %d]" % (self.cfg.ts, self.cfg.dense.input_size))
+        if out is None:
+            out = x.new_empty((B, self.cfg.ts, self.cfg.dense.output_size))
+        elif tuple(out.shape) != (B, self.cfg.ts, self.cfg.dense.output_size):
+            raise ValueError("TimeDistributedDenseApplyDeviceVarLen: out must be [B, %d, %d]" % (self.cfg.ts, self.cfg.dense.output_size))
+        lp = None
+        if lengths is not None:
+            lens = _host_ints(lengths, B, "lengths")
+            lp = lens.ctypes.data_as(capi.ip)
+        check(capi.load().TimeDistributedDenseApplyDeviceVarLen(self.h, _dp(x), _dp(out), B, lp), "TimeDistributedDenseApplyDeviceVarLen")
+        return out
+
     def destroy(self):
         if self.h:
             capi.load().TimeDistributedDenseDestroy(self.h)
@@ -583,7 +654,74 @@ class Spectrogram:
         check(capi.load().SpectrogramApplyDevice(self.h, _dp(x), _dp(out), x.shape[0]), "SpectrogramApplyDevice")
         return out
 
+    def stream_sizes(self):
+        """(tail_floats, max_frames): nntk_spectrogram_stream_sizes"""
+        a, b = C.c_int(), C.c_int()
+        check(capi.load().nntk_spectrogram_stream_sizes(self.cfg, C.byref(a), C.byref(b)), "nntk_spectrogram_stream_sizes")
+        return a.value, b.value
+
+    @property
+    def stream_features(self):
+        return self.cfg.nfreq
+
+    def new_stream_state(self, batch):
+        """(tail [batch, tail_floats] zeros on the current device, host int32 tail_len [batch] zeros)"""
+        import torch
+        tf, _ = self.stream_sizes()
+        return (torch.zeros((batch, tf), device="cuda"), np.zeros(batch, np.int32))
+
+    def apply_device_stream(self, x, n_new, state, final=None, out=None):
+        """SpectrogramApplyDeviceStream: x [B, input_size] chunk samples, row b brings n_new[b] of them.
+        Returns (out [B, max_frames, nfreq], frames); the state (tail tensor, tail_len) is updated in place."""
+        tf, mf = self.stream_sizes()
+        return _stream_call(capi.load().SpectrogramApplyDeviceStream, "SpectrogramApplyDeviceStream", (self.h,), x,
+                            (self.cfg.input_size,), n_new, state, (tf,), final, (x.shape[0], mf, self.cfg.nfreq), out)
+
     def destroy(self):
         if self.h:
             capi.load().SpectrogramDestroy(self.h)
+            self.h = None
+
+
+class LogMelSpectrogram:
+    """LogMelSpectrogramCreate over a Spectrogram (owned by the caller, as in the reference): log(mel + 1.5849e-13)"""
+
+    def __init__(self, spectrogram, n_mels, sample_rate=16000, lower_hz=0.0, upper_hz=8000.0):
+        L = capi.load()
+        self.spec = spectrogram
+        self.mel_cfg = L.MelFilterBankConfigCreate(n_mels, spectrogram.cfg.nfft, sample_rate, C.c_float(lower_hz), C.c_float(upper_hz))
+        self.h = L.LogMelSpectrogramCreate(spectrogram.h, self.mel_cfg)
+        if not self.h:
+            raise capi.NNTKError("LogMelSpectrogramCreate: " + capi.last_error())
+        self.cfg = spectrogram.cfg
+
+    @property
+    def out_shape(self):
+        return (self.cfg.ntime_series, self.mel_cfg.n_mels)
+
+    @property
+    def stream_features(self):
+        return self.mel_cfg.n_mels
+
+    def apply_device(self, x, out=None):
+        if out is None:
+            out = x.new_empty((x.shape[0],) + self.out_shape)
+        check(capi.load().LogMelSpectrogramApplyDevice(self.h, _dp(x), _dp(out), x.shape[0]), "LogMelSpectrogramApplyDevice")
+        return out
+
+    def stream_sizes(self):
+        return self.spec.stream_sizes()
+
+    def new_stream_state(self, batch):
+        return self.spec.new_stream_state(batch)
+
+    def apply_device_stream(self, x, n_new, state, final=None, out=None):
+        """LogMelSpectrogramApplyDeviceStream: as Spectrogram.apply_device_stream, output [B, max_frames, n_mels]"""
+        tf, mf = self.stream_sizes()
+        return _stream_call(capi.load().LogMelSpectrogramApplyDeviceStream, "LogMelSpectrogramApplyDeviceStream", (self.h,), x,
+                            (self.cfg.input_size,), n_new, state, (tf,), final, (x.shape[0], mf, self.mel_cfg.n_mels), out)
+
+    def destroy(self):
+        if self.h:
+            capi.load().LogMelSpectrogramDestroy(self.h)
             self.h = None
