@@ -546,6 +546,49 @@ int RNNApplyInferenceBatchVarLen(RNN filter, const float *input, float *output, 
                                  const float *h0, float *hT);
 int LSTMApplyInferenceBatchVarLen(LSTM filter, const float *input, float *output, int batch, const int *lengths,
                                   const float *h0, const float *c0, float *hT, float *cT);
+/* ---- training on ragged batches with carried state (INTEGRATION.md "Training on ragged batches and long streams") -------------------
+ * The training counterpart of the calls above, on a *CreateForTraining handle: B = its mini_batch_size, T = its timesteps (also the row
+ * stride), H its hidden size.  lengths: HOST memory [B] or NULL (every row T), checked before anything is enqueued (-1 and
+ * nntk_last_error() for a length outside [0, T]; nothing written) and copied in stream order.  Every state pointer may be NULL (zeros in /
+ * nothing out).
+ * Forward: row b runs steps 0 .. L-1 (L = lengths[b]) from h0[b] (c0[b]).  return_sequences: out[b][t] = h_t for t < L, exact zeros for
+ * t >= L; otherwise out[b] = h_L.  hT[b] = h_L, cT[b] = c_L (L = 0: h0[b] / c0[b], zeros without them).  x[b][t >= L] influences nothing
+ * (it may hold NaN).  The handle remembers the lengths and h0 / c0 for the gradient call: the state tensors must stay valid until then,
+ * like d_input.
+ * Gradient: d_dout[b][t >= L] is ignored (it may hold NaN); without return_sequences d_dout[b] enters at step L-1.  d_dhT[b] / d_dcT[b]
+ * is the gradient arriving at h_L / c_L from outside (the next chunk's d_dh0 / d_dc0), added where the recurrence's own carry would be.
+ * d_dh0[b] / d_dc0[b] is the gradient with respect to h0[b] / c0[b] (the zero state when none was given; L = 0: d_dhT[b] / d_dcT[b] passed
+ * through, or zeros -- plus d_dout[b] in d_dh0[b] without return_sequences, where out[b] = h_L is h0[b] itself).  d_dX[b][t >= L] is exact zeros.  d_grad (W | U | b_i | b_h) is ADDED to; only steps t < L contribute, and step 0
+ * contributes its h0 / c0 terms.
+ * With lengths == NULL and every state pointer NULL the calls run the kernels of *ApplyTrainingBatchDevice / *CalculateGradientDevice and
+ * return their bits.  Ragged and carried-state calls take the routes of the fixed-length ones: the forward pass runs the register-resident
+ * kernel (its TRAIN instantiation with per-row lengths: each 64-row batch tile runs to its own longest row) wherever the fixed-length call
+ * does (except a GRU with H <= 256 and in <= 64), the gradient the persistent BPTT kernel wherever the fixed-length call does (a row is idle until its own last step, every 16-row
+ * batch tile starts at its own longest row); otherwise the per-timestep kernels.  nntk_hip_last_recurrent_kernel() names the kernel the last
+ * call ran. */
+int GRUApplyTrainingBatchDeviceVarLen(GRU filter, const float *d_input /*[B,T,in]*/, float *d_output, const int *lengths /*host [B] or NULL*/,
+                                      const float *d_h0 /*[B,H] or NULL*/, float *d_hT /*[B,H] or NULL*/);
+int RNNApplyTrainingBatchDeviceVarLen(RNN filter, const float *d_input, float *d_output, const int *lengths, const float *d_h0, float *d_hT);
+int LSTMApplyTrainingBatchDeviceVarLen(LSTM filter, const float *d_input, float *d_output, const int *lengths,
+                                       const float *d_h0, const float *d_c0, float *d_hT, float *d_cT);
+int GRUCalculateGradientDeviceVarLen(GRU filter, float *d_grad, float *d_dX /*[B,T,in]*/, const float *d_dout,
+                                     const float *d_dhT /*[B,H] or NULL*/, float *d_dh0 /*[B,H] or NULL*/);
+int RNNCalculateGradientDeviceVarLen(RNN filter, float *d_grad, float *d_dX, const float *d_dout, const float *d_dhT, float *d_dh0);
+int LSTMCalculateGradientDeviceVarLen(LSTM filter, float *d_grad, float *d_dX, const float *d_dout,
+                                      const float *d_dhT, const float *d_dcT, float *d_dh0, float *d_dc0);
+/* the same on host memory (upload, device call, download; the gradient block is accumulated as *CalculateGradient does).  int, not void:
+ * -1 and nntk_last_error() on an error */
+int GRUApplyTrainingBatchVarLen(GRU filter, const float *input, float *output, const int *lengths, const float *h0, float *hT);
+int RNNApplyTrainingBatchVarLen(RNN filter, const float *input, float *output, const int *lengths, const float *h0, float *hT);
+int LSTMApplyTrainingBatchVarLen(LSTM filter, const float *input, float *output, const int *lengths,
+                                 const float *h0, const float *c0, float *hT, float *cT);
+int GRUCalculateGradientVarLen(GRU filter, GRUGradient *gradient, const float *d_out, const float *d_hT_grad, float *d_h0_grad);
+int RNNCalculateGradientVarLen(RNN filter, RNNGradient *gradient, const float *d_out, const float *d_hT_grad, float *d_h0_grad);
+int LSTMCalculateGradientVarLen(LSTM filter, LSTMGradient *gradient, const float *d_out, const float *d_hT_grad, const float *d_cT_grad,
+                                float *d_h0_grad, float *d_c0_grad);
+/* the RNN's device-pointer training calls, in the shape of the GRU's (d_grad = W [in][H] | U [H][H] | b_i [H] | b_h [H], ADDED to) */
+int RNNApplyTrainingBatchDevice(RNN filter, const float *d_input, float *d_output);
+int RNNCalculateGradientDevice(RNN filter, float *d_grad, float *d_dX, const float *d_dout);
 /* bidirectional helpers for ragged rows: out[b][t] = in[b][lengths[b] - 1 - t] for t < lengths[b], zeros after (lengths: host) */
 int bd_reverse_input_batch_varlen_device(const float *d_input, float *d_output, RecurrentConfig config, int batch, const int *lengths);
 int bd_reverse_backward_batch_varlen_device(const float *d_input, float *d_output, RecurrentConfig config, int batch, const int *lengths);

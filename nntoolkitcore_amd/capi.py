@@ -362,6 +362,21 @@ SIGNATURES = {
     "GRUApplyInferenceBatchVarLen": (C.c_int, [vp, fp, fp, C.c_int, ip, fp, fp]),
     "RNNApplyInferenceBatchVarLen": (C.c_int, [vp, fp, fp, C.c_int, ip, fp, fp]),
     "LSTMApplyInferenceBatchVarLen": (C.c_int, [vp, fp, fp, C.c_int, ip, fp, fp, fp, fp]),
+    # training on ragged batches with carried state (device forms, then host forms), and the RNN's device-pointer training calls
+    "GRUApplyTrainingBatchDeviceVarLen": (C.c_int, [vp, vp, vp, ip, vp, vp]),
+    "RNNApplyTrainingBatchDeviceVarLen": (C.c_int, [vp, vp, vp, ip, vp, vp]),
+    "LSTMApplyTrainingBatchDeviceVarLen": (C.c_int, [vp, vp, vp, ip, vp, vp, vp, vp]),
+    "GRUCalculateGradientDeviceVarLen": (C.c_int, [vp, vp, vp, vp, vp, vp]),
+    "RNNCalculateGradientDeviceVarLen": (C.c_int, [vp, vp, vp, vp, vp, vp]),
+    "LSTMCalculateGradientDeviceVarLen": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp]),
+    "GRUApplyTrainingBatchVarLen": (C.c_int, [vp, fp, fp, ip, fp, fp]),
+    "RNNApplyTrainingBatchVarLen": (C.c_int, [vp, fp, fp, ip, fp, fp]),
+    "LSTMApplyTrainingBatchVarLen": (C.c_int, [vp, fp, fp, ip, fp, fp, fp, fp]),
+    "GRUCalculateGradientVarLen": (C.c_int, [vp, vp, fp, fp, fp]),
+    "RNNCalculateGradientVarLen": (C.c_int, [vp, vp, fp, fp, fp]),
+    "LSTMCalculateGradientVarLen": (C.c_int, [vp, vp, fp, fp, fp, fp, fp]),
+    "RNNApplyTrainingBatchDevice": (C.c_int, [vp, vp, vp]),
+    "RNNCalculateGradientDevice": (C.c_int, [vp, vp, vp, vp]),
     "bd_reverse_input_batch_varlen_device": (C.c_int, [vp, vp, RecurrentConfig, C.c_int, ip]),
     "bd_reverse_backward_batch_varlen_device": (C.c_int, [vp, vp, RecurrentConfig, C.c_int, ip]),
     "bd_reverse_input_batch_device": (C.c_int, [vp, vp, RecurrentConfig, C.c_int]),

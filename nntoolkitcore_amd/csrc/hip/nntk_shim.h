@@ -151,6 +151,41 @@ int nntk_shim_rnn_train_forward(const float *d_x, const float *d_W, const float 
                                 float *d_h, float *d_gate, int B, int T, int in, int H, int v2, int act, float scale);
 int nntk_shim_rnn_train_backward(const float *d_dout, const float *d_UT /*U transposed [H][H]*/, const float *d_h, const float *d_gate, float *d_dG,
                                  float *d_work /*2*B*H*/, int B, int T, int H, int return_sequences, int act);
+/* Ragged batches and carried state for the training kernels above (the *VarLen training calls; a NULL pointer to it = the fixed-length,
+ * zero-state pass on the same kernels).  All pointers are device memory and may be NULL. */
+typedef struct {
+    const int *d_len;            /* [B] row lengths in [0, T], then the 64-row tiles' maxima (nntk_shim_rr_varlen's layout); NULL: every row T */
+    int max_len;                 /* the longest row (read only with d_len) */
+    const float *d_h0, *d_c0;    /* [B][H] initial state (zeros) */
+    const float *d_dhT, *d_dcT;  /* [B][H] gradient arriving at the final state (zeros) */
+    float *d_dh0, *d_dc0;        /* [B][H] gradient with respect to the initial state (not computed) */
+} nntk_train_vl;
+int nntk_shim_gru_train_forward_vl(const float *d_x, const float *d_W, const float *d_U, const float *d_bi, const float *d_bh,
+                                   float *d_h, float *d_Zg, float *d_hU, int B, int T, int in, int H, const int *acts, const float *scales,
+                                   const nntk_train_vl *vl);
+int nntk_shim_gru_train_backward_vl(const float *d_dout, const float *d_UT, const float *d_h, const float *d_Zg, const float *d_hU,
+                                    float *d_dxW, float *d_dhU, float *d_work /*5*B*H*/, int B, int T, int H, int return_sequences, const int *acts,
+                                    const nntk_train_vl *vl);
+int nntk_shim_lstm_train_forward_vl(const float *d_x, const float *d_W, const float *d_U, const float *d_bi, const float *d_bh,
+                                    float *d_h, float *d_c, float *d_zifgo, int B, int T, int in, int H, int v2, const int *acts, const float *scales,
+                                    const nntk_train_vl *vl);
+int nntk_shim_lstm_train_backward_vl(const float *d_dout, const float *d_UT, const float *d_c, const float *d_zifgo, float *d_dG,
+                                     float *d_work /*6*B*H*/, int B, int T, int H, int return_sequences, const int *acts, const float *scales,
+                                     const nntk_train_vl *vl);
+int nntk_shim_rnn_train_forward_vl(const float *d_x, const float *d_W, const float *d_U, const float *d_bi, const float *d_bh,
+                                   float *d_h, float *d_gate, int B, int T, int in, int H, int v2, int act, float scale, const nntk_train_vl *vl);
+int nntk_shim_rnn_train_backward_vl(const float *d_dout, const float *d_UT, const float *d_h, const float *d_gate, float *d_dG,
+                                    float *d_work /*2*B*H*/, int B, int T, int H, int return_sequences, int act, const nntk_train_vl *vl);
+/* the same forward pass on the register-resident kernels (recurrent_rr.hip, TRAIN + VL): one launch, h0 / c0 in, hT / cT out (may be NULL),
+ * the caches of every step a row runs; d_h rows past a row's length are unspecified until nntk_shim_varlen_zero_pad clears them.  cell 0
+ * LSTM, 1 GRU (d_bi = the four-slot bias, d_bh NULL, d_c = the h.U_h + b_h cache).  0 launched, 1 shape / configuration not taken, -1 error */
+int nntk_shim_rr_train_forward_vl(int cell, const float *d_x, const float *d_img, const float *d_bi, const float *d_bh,
+                                  const float *d_h0, const float *d_c0, float *d_h, float *d_c, float *d_z, float *d_hT, float *d_cT,
+                                  float *d_hseq, float *d_work, const int *d_len, int B, int T, int in, int H);
+/* d_sT [B][H] = d_seq [B][T][H] at each row's last step, or d_s0 (zeros) for an empty row */
+int nntk_shim_train_final_state(const float *d_seq, const int *d_len, const float *d_s0, float *d_sT, int B, int T, int H);
+/* d_xm = d_x [B][T][F] with exact zeros at t >= d_len[b] */
+int nntk_shim_train_mask_rows(const float *d_x, const int *d_len, float *d_xm, int B, int T, int F);
 /* MFMA forms of the large training products: C [M][N] (+)= A [M][K] x Bw [N][K]^T through the inference GEMM kernel (Bw is
  * packed per call into d_pack >= nntk_shim_gemm_nt_scratch_floats(N, K) floats; accumulate uses d_tmp [M][N]) */
 size_t nntk_shim_gemm_nt_scratch_floats(int N, int K);

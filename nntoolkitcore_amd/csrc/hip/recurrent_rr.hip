@@ -195,17 +195,19 @@ __global__ __launch_bounds__(256) void rr_tile_h0_kernel(const float *__restrict
 // instead of three bf16 images and six: U's two f16 images of U 2^q sit in the registers that hold hi / mid (its LDS image is unused), the
 // hand-off carries two blocks per (row block, k step) -- and IS the dense layer's FRAG2H operand -- W's bf16 images are packed
 // pre-multiplied by 2^(15 + q), so both parts accumulate at one scale, taken out (exactly) where the bias is added.
-// VL (the *VarLen calls; not with TRAIN / HF, never time-major): per-row lengths.  The batch tile runs its time loop to its longest row
+// VL (the *VarLen calls; not with HF, never time-major): per-row lengths.  The batch tile runs its time loop to its longest row
 // (a scalar from p.len: every workgroup of the tile and every wave agrees, so the hand-off and the pending marks stay consistent), and a
 // lane whose row is past its length keeps its state: fin_gates selects the old c / h on the VALU, so the published fragments, the output
-// wave's rows and hT / cT all carry the frozen value and no memory operation of the step loop moves.
+// wave's rows and hT / cT all carry the frozen value and no memory operation of the step loop moves.  With TRAIN (the *TrainingBatch*VarLen
+// calls) a lane writes the BPTT caches of its row's own steps only -- rows are p.T apart, the layout stride, not the tile's step count -- and
+// the caches past a row's end are never read; the h rows past it (frozen values up to the tile's longest row) are cleared by the host.
 // BD (the bidirectional calls; implies VL and XF): one launch over a virtual batch of 2 p.bd_pad rows, forward direction first (RRParams).  A
 // 64-row tile belongs to one direction (bd_pad % 64 == 0): the direction is a scalar, and so is everything it selects -- weight images,
 // biases, the output base.  The hand-off, the flags and the x operand keep their layout over the virtual rows.  Output rows are the caller's:
 // a backward lane stores step t at time L - 1 - t of its row, nothing at t >= L; padding rows store nothing.
 template <int KH, int KX, bool TRAIN, int CELL, bool XF, bool HF = false, bool VL = false, bool BD = false>
 __device__ __forceinline__ void rr_body(const RRParams &p) {
-    static_assert(!VL || (!TRAIN && !HF), "VL: the inference instantiations");
+    static_assert(!VL || !HF, "VL: not with the two-f16-image hand-off");
     static_assert(!BD || (VL && XF), "BD: per-row lengths and a frag3 x operand");
     constexpr int NH = HF ? 2 : 3;                    // images of the h hand-off
 #ifndef RR_ULR8
@@ -562,27 +564,29 @@ __device__ __forceinline__ void rr_body(const RRParams &p) {
             unsigned *d = hs + n * RR_HS_LD + (jl >> 1);
             d[0] = sh; d[32 * RR_HS_LD] = sm; d[2 * 32 * RR_HS_LD] = sl;
         }
+        bool own_step = true;                           // TRAIN + VL: the caches of a row's own steps only
+        if constexpr (VL) own_step = t < vlen[half];
         if (TRAIN && CELL == 1) {
             const int row = b0 + half * 32 + n;
-            if (row < p.B && jf + 1 < H + 1) {
-                float *zrow = p.z_cache + ((size_t)row * T + t) * 6 * H + jf;
+            if (row < p.B && jf + 1 < H + 1 && own_step) {
+                float *zrow = p.z_cache + ((size_t)row * p.T + t) * 6 * H + jf;
 #pragma unroll
                 for (int g = 0; g < 3; ++g) {
                     *reinterpret_cast<float2 *>(zrow + g * H) = make_float2(zc[g][0], zc[g][1]);
                     *reinterpret_cast<float2 *>(zrow + (3 + g) * H) = make_float2(ac[g][0], ac[g][1]);
                 }
-                *reinterpret_cast<float2 *>(p.c_cache + ((size_t)row * T + t) * H + jf) = make_float2(zc[3][0], zc[3][1]);
+                *reinterpret_cast<float2 *>(p.c_cache + ((size_t)row * p.T + t) * H + jf) = make_float2(zc[3][0], zc[3][1]);
             }
         } else if (TRAIN) {
             const int row = b0 + half * 32 + n;
-            if (row < p.B && jf + 1 < H + 1) {                 // H % 2 == 0 here (H % 16 == 0): both cells or none
-                float *zrow = p.z_cache + ((size_t)row * T + t) * 8 * H + jf;
+            if (row < p.B && jf + 1 < H + 1 && own_step) {                 // H % 2 == 0 here (H % 16 == 0): both cells or none
+                float *zrow = p.z_cache + ((size_t)row * p.T + t) * 8 * H + jf;
 #pragma unroll
                 for (int g = 0; g < 4; ++g) {
                     *reinterpret_cast<float2 *>(zrow + g * H) = make_float2(zc[g][0], zc[g][1]);
                     *reinterpret_cast<float2 *>(zrow + (4 + g) * H) = make_float2(ac[g][0], ac[g][1]);
                 }
-                *reinterpret_cast<float2 *>(p.c_cache + ((size_t)row * T + t) * H + jf) = make_float2(cst[half][0], cst[half][1]);
+                *reinterpret_cast<float2 *>(p.c_cache + ((size_t)row * p.T + t) * H + jf) = make_float2(cst[half][0], cst[half][1]);
             }
         }
     };
@@ -1161,9 +1165,27 @@ extern "C" int nntk_shim_lstm_rr_train_forward(const float *d_x, const float *d_
     return rr_launch(io, d_img, d_bi, d_bh, B, T, in, H, 1, 0);
 }
 
+// training forward of a ragged batch with carried state (the *TrainingBatch*VarLen calls): d_len as nntk_shim_rr_varlen's, h0 / c0 in, hT / cT
+// out, the caches of every step a row runs; d_h rows past a row's length are unspecified (nntk_shim_varlen_zero_pad).  cell 0 LSTM, 1 GRU
+// (d_bi = the four-slot bias, d_bh NULL, d_c0 / d_cT unused; d_c = the h.U_h + b_h cache).  1 = not taken.
+extern "C" int nntk_shim_rr_train_forward_vl(int cell, const float *d_x, const float *d_img, const float *d_bi, const float *d_bh,
+                                             const float *d_h0, const float *d_c0, float *d_h, float *d_c, float *d_z, float *d_hT, float *d_cT,
+                                             float *d_hseq, float *d_work, const int *d_len, int B, int T, int in, int H) {
+    if (!d_len) return nntk_fail_msg("rr_train_forward_vl: no lengths");
+    RRIo io = {nullptr, d_x, nullptr, d_h, d_hseq, d_work, d_h0, cell == 1 ? d_h0 : d_c0, d_hT, cell == 1 ? nullptr : d_cT, d_c, d_z, 0, 0,
+               nullptr, 0, 0.0f, d_len};
+    return rr_launch(io, d_img, d_bi, d_bh, B, T, in, H, 1, cell);
+}
+
 template <int KH, int KX>
 static void (*rr_pick(int cell, bool train, bool xf, bool vl = false, bool bd = false))(RRParams) {
     if (bd) return cell == 1 ? gru_rr_kernel<KH, KX, false, true, true, true> : lstm_rr_kernel<KH, KX, false, true, false, true, true>;
+    if (vl && train) {
+        // gru_rr_kernel<4, 1, TRAIN, VL> comes out 9 VGPRs over the budget (a 36-byte private segment, which tools/check_rr_waits.py refuses):
+        // not built; a ragged GRU training forward with H <= 256 and in <= 64 runs the per-timestep kernels
+        if constexpr (KH == 4 && KX == 1) return cell == 1 ? nullptr : lstm_rr_kernel<KH, KX, true, false, false, true>;
+        else return cell == 1 ? gru_rr_kernel<KH, KX, true, false, true> : lstm_rr_kernel<KH, KX, true, false, false, true>;
+    }
     if (vl) {
         if (cell == 1) return xf ? gru_rr_kernel<KH, KX, false, true, true> : gru_rr_kernel<KH, KX, false, false, true>;
         return xf ? lstm_rr_kernel<KH, KX, false, true, false, true> : lstm_rr_kernel<KH, KX, false, false, false, true>;
@@ -1179,7 +1201,7 @@ static int rr_launch(const RRIo &io, const float *d_img, const float *d_bi, cons
     const bool train = io.c_cache != nullptr;
     if (xf && (train || io.x_tm)) return 1;
     const bool vl = io.len != nullptr;
-    if (vl && (train || io.x_tm || io.out_tm || io.hf || io.out_h2)) return nntk_fail_msg("lstm_rr: lengths with a training / stacked / frag2h call");
+    if (vl && (io.x_tm || io.out_tm || io.hf || io.out_h2)) return nntk_fail_msg("lstm_rr: lengths with a stacked / frag2h call");
     const bool bd = io.out_b != nullptr;
     if (bd && (!vl || !xf || io.h0 || io.hT || io.cT)) return nntk_fail_msg("lstm_rr: a bidirectional call needs lengths, a frag3 x and no carried state");
     if (!xf && !io.x) return nntk_fail_msg("lstm_rr: no input");

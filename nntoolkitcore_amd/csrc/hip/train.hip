@@ -404,11 +404,14 @@ struct GruTrainParams {
     int B, T, in, H, t;
     int act_z, act_h, act_r;
     float sc_z, sc_h, sc_r;      // ReLU output scales
+    const int *len;              // ragged batches: row b runs steps 0 .. len[b] - 1 (NULL: every row T)
+    const float *h0;             // [B][H] initial state or NULL (zeros)
 };
 __global__ __launch_bounds__(256) void gru_train_fwd_step_kernel(GruTrainParams p) {
     const int b = blockIdx.y, j = blockIdx.x * 32 + (threadIdx.x & 31), H = p.H;
     const size_t row = (size_t)b * p.T + p.t;
-    const float *hp = p.t > 0 ? p.h + (row - 1) * H : nullptr;      // h_0 = 0 for every sequence (gru.c:262)
+    if (p.len && p.t >= p.len[b]) return;                           // past the row's end (uniform: a workgroup is one row); its h row was cleared by the host
+    const float *hp = p.t > 0 ? p.h + (row - 1) * H : p.h0 ? p.h0 + (size_t)b * H : nullptr;      // h_0 = 0 for every sequence (gru.c:262) unless the caller carries one in
     float xw[3], hu[3];
     if (!cell_dots_chunked<3>(p.x + row * p.in, hp, p.W, p.U, p.in, H, j, xw, hu)) return;
 #pragma unroll
@@ -443,22 +446,32 @@ struct GruBwdParams {
     float *dxW, *dhU, *dhU_step, *dhp1_out;
     int B, T, H, t, return_sequences;
     int act_z, act_h, act_r;
+    const int *len;              // ragged batches (NULL: every row T): a row is idle until its own last step
+    const float *h0, *dhT;       // [B][H] initial state / gradient arriving at the final state, or NULL (zeros)
 };
 __global__ __launch_bounds__(256) void gru_train_bwd_step_kernel(GruBwdParams p) {
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= p.B * p.H) return;
     const int b = e / p.H, j = e % p.H, H = p.H;
     const size_t row = (size_t)b * p.T + p.t;
+    const int L = p.len ? p.len[b] : p.T;
+    if (p.t >= L) {              // idle: nothing flows back through this step (d_xW / d_hU rows were cleared by the host)
+        float *ds = p.dhU_step + (size_t)b * 3 * H;
+        ds[j] = 0.0f; ds[H + j] = 0.0f; ds[2 * H + j] = 0.0f;
+        p.dhp1_out[e] = 0.0f;
+        return;
+    }
+    const bool first = p.t == L - 1;      // the row's last step: the first one of its backward pass
     float dout = 0.0f;
     if (p.return_sequences) dout = p.dout[row * H + j];
-    else if (p.t == p.T - 1) dout = p.dout[(size_t)b * H + j];
-    const float carry = p.t == p.T - 1 ? 0.0f : add_rn(p.dhp1[e], p.dhp2[e]);
+    else if (first) dout = p.dout[(size_t)b * H + j];
+    const float carry = first ? (p.dhT ? p.dhT[e] : 0.0f) : add_rn(p.dhp1[e], p.dhp2[e]);
     const float dh = add_rn(carry, dout);
     const float *Zg = p.Zg + row * 6 * H;
     const float z = Zg[3 * H + j], r = Zg[4 * H + j], ht = Zg[5 * H + j];
     const float dhp1 = mul_rn(z, dh);
     const float dht = add_rn(mul_rn(-z, dh), dh);
-    const float dz = mul_rn(p.t > 0 ? sub_rn(p.h[(row - 1) * H + j], ht) : -ht, dh);
+    const float dz = mul_rn(p.t > 0 ? sub_rn(p.h[(row - 1) * H + j], ht) : p.h0 ? sub_rn(p.h0[e], ht) : -ht, dh);
     const float dZh = gate_grad(p.act_h, Zg[2 * H + j], ht, dht);
     const float dr = mul_rn(p.hU[row * H + j], dZh);
     const float dZz = gate_grad(p.act_z, Zg[j], z, dz);
@@ -835,6 +848,11 @@ struct BpttParams {
     int B, T, H, return_sequences;
     int act[5];
     float sc_out;
+    // ragged batches and carried state (all NULL: the fixed-length, zero-state pass)
+    const int *len;              // [B] row lengths
+    const float *s0;             // [B][H] initial state the step-0 terms read: GRU h0, LSTM c0
+    const float *dhT, *dcT;      // [B][H] gradient arriving at the final state (dcT: LSTM)
+    float *carry_out;            // [B][H] the register carry after step 0: GRU d_h_prev_1, LSTM d_c0
 };
 // timing ablations (tools/bptt_ablate.sh): compile-time mask, 0 in the product.  1 no poll, 2 no operand loads, 4 no MFMAs,
 // 8 no wait for the stores, 16 no stores, 32 no cache fetch
@@ -866,48 +884,60 @@ __global__ __launch_bounds__(256) void bptt_persistent_kernel(BpttParams p) {
     const size_t tile_bytes = (size_t)(p.B - bt * 16 < 16 ? p.B - bt * 16 : 16) * T * K * 4;
     const __amdgpu_buffer_rsrc_t rg = __builtin_amdgcn_make_buffer_rsrc((void *)(p.dG + (size_t)bt * 16 * T * K), 0, (unsigned)tile_bytes, 0x00020000);
     if (tid == 0) s_stop = 0;
+    // Ragged batches: row b is idle (carry 0, nothing stored: the host cleared dG / dxW, so the product reads zeros for it) until
+    // t = L - 1, where the gradient arriving at its final state is its incoming carry.  The batch tile starts at its own longest
+    // row: every column tile of the batch tile computes the same TS from the same 16 lengths, so the flag tag -- steps handed off
+    // so far -- only shifts by the tile's start, and a tile whose rows are all empty hands nothing off.
+    const int L = !live ? 0 : p.len ? p.len[b] : T;
+    int TS = T;
+    if (p.len) {
+        TS = 0;
+        for (int r = 0; r < 16 && bt * 16 + r < p.B; ++r) { const int lr = p.len[bt * 16 + r]; TS = lr > TS ? lr : TS; }
+        TS = __builtin_amdgcn_readfirstlane(TS);
+    }
     float carry = 0.0f;          // LSTM: d_c carry; GRU: d_h_prev_1
     float dh2 = 0.0f;            // this thread's element of the product
     // forward caches of one step for this thread's (b, j): fetched one step ahead (the loads fly during the hand-off and the product)
     struct Cached { float z[8]; float c, cprev, dout; };
     auto fetch = [&](int t) {
         Cached f{};
-        if (!live || t < 0 || (BPTT_DBG(32) && t < T - 1)) return f;
+        if (!live || t < 0 || t >= L || (BPTT_DBG(32) && t < T - 1)) return f;
         const size_t row = (size_t)b * T + t;
         if (p.return_sequences) f.dout = p.dout[row * H + j];
-        else if (t == T - 1) f.dout = p.dout[(size_t)b * H + j];
+        else if (t == L - 1) f.dout = p.dout[(size_t)b * H + j];
         if (CELL) {
             const float *zg = p.zifgo + row * 8 * H;
 #pragma unroll
             for (int g = 0; g < 8; ++g) f.z[g] = zg[g * H + j];
             f.c = p.c[row * H + j];
-            f.cprev = t > 0 ? p.c[(row - 1) * H + j] : 0.0f;
+            f.cprev = t > 0 ? p.c[(row - 1) * H + j] : p.s0 ? p.s0[(size_t)b * H + j] : 0.0f;
         } else {
             const float *Zg = p.Zg + row * 6 * H;
 #pragma unroll
             for (int g = 0; g < 6; ++g) f.z[g] = Zg[g * H + j];
             f.c = p.hU[row * H + j];
-            f.cprev = t > 0 ? p.h[(row - 1) * H + j] : 0.0f;
+            f.cprev = t > 0 ? p.h[(row - 1) * H + j] : p.s0 ? p.s0[(size_t)b * H + j] : 0.0f;
         }
         return f;
     };
-    Cached cur = fetch(T - 1);
-    for (int t = T - 1; t >= 0; --t) {
-        const bool last = t == T - 1;
-        if (live) {
+    Cached cur = fetch(TS - 1);
+    for (int t = TS - 1; t >= 0; --t) {
+        const bool last = t == L - 1;                            // the row's own last step: the first of its backward pass
+        if (live && t < L) {
             const size_t row = (size_t)b * T + t;
             const float dout = cur.dout;
             const int vo = ((bl * T + t) * K + j) * 4;
             if (CELL) {
-                const float dh = add_rn(last ? 0.0f : dh2, dout);
+                const float dh = add_rn(last ? (p.dhT ? p.dhT[(size_t)b * H + j] : 0.0f) : dh2, dout);
                 const float it = cur.z[4], ft = cur.z[5], gt = cur.z[6], ot = cur.z[7];
                 const float cv = cur.c;
                 const float tc = nntk_gate_act(p.act[4], cv, p.sc_out);
                 const float d_o = gate_grad(p.act[3], cur.z[3], ot, mul_rn(dh, tc));
                 float dc = gate_grad(p.act[4], cv, nntk_gate_act(p.act[4], cv, 1.0f), mul_rn(dh, ot));
                 if (!last) dc = add_rn(dc, carry);
+                else if (p.dcT) dc = add_rn(dc, p.dcT[(size_t)b * H + j]);
                 const float d_i = gate_grad(p.act[0], cur.z[0], it, mul_rn(dc, gt));
-                const float d_f = t == 0 ? 0.0f : gate_grad(p.act[1], cur.z[1], ft, mul_rn(cur.cprev, dc));
+                const float d_f = t == 0 && !p.s0 ? 0.0f : gate_grad(p.act[1], cur.z[1], ft, mul_rn(cur.cprev, dc));
                 const float d_g = gate_grad(p.act[2], cur.z[2], gt, mul_rn(dc, it));
                 carry = mul_rn(dc, ft);
                 if (BPTT_DBG(16)) { if (d_i + d_f + d_g + d_o == 1.2345f) carry += 1.f; } else {
@@ -917,11 +947,11 @@ __global__ __launch_bounds__(256) void bptt_persistent_kernel(BpttParams p) {
                 __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(d_o), rg, vo + 3 * H * 4, 0, 16);
                 }
             } else {
-                const float dh = add_rn(last ? 0.0f : add_rn(carry, dh2), dout);
+                const float dh = add_rn(last ? (p.dhT ? p.dhT[(size_t)b * H + j] : 0.0f) : add_rn(carry, dh2), dout);
                 const float z = cur.z[3], r = cur.z[4], ht = cur.z[5];
                 carry = mul_rn(z, dh);
                 const float dht = add_rn(mul_rn(-z, dh), dh);
-                const float dz = mul_rn(t > 0 ? sub_rn(cur.cprev, ht) : -ht, dh);
+                const float dz = mul_rn(t > 0 || p.s0 ? sub_rn(cur.cprev, ht) : -ht, dh);
                 const float dZh = gate_grad(p.act[1], cur.z[2], ht, dht);
                 const float dr = mul_rn(cur.c, dZh);
                 const float dZz = gate_grad(p.act[0], cur.z[0], z, dz);
@@ -942,7 +972,7 @@ __global__ __launch_bounds__(256) void bptt_persistent_kernel(BpttParams p) {
         // store, no read-modify-write on a shared counter (32 workgroups adding to one word queue up at L2); wave 0 polls all of
         // the batch tile's flags with one wave-wide load
         if (wv == 0) {
-            const unsigned tag = (unsigned)(T - t);
+            const unsigned tag = (unsigned)(TS - t);
             unsigned *flags = p.count + (size_t)bt * 32;
             if (lane == 0) __hip_atomic_store(flags + ct, tag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             const unsigned long long t_start = __builtin_amdgcn_s_memrealtime();
@@ -992,6 +1022,7 @@ __global__ __launch_bounds__(256) void bptt_persistent_kernel(BpttParams p) {
         dh2 = add_rn(add_rn(add_rn(part[0][sr][sl], part[1][sr][sl]), part[2][sr][sl]), part[3][sr][sl]);
         // part is rewritten only after the next step's two barriers
     }
+    if (p.carry_out && live) p.carry_out[(size_t)b * H + j] = carry;      // (a row that never ran: 0)
 }
 // 0: ran; 1: shape not taken (the caller falls back to the per-step loop); -1: error
 template <int CELL>
@@ -1019,6 +1050,58 @@ static int bptt_persistent(BpttParams &p, float *d_count_words) {
     nntk_persistent_launch_end();
     if (copy_rc) return -1;
     NNTK_LAUNCH_CHECK("bptt_persistent_kernel");
+    nntk_set_last_rec_kernel(CELL ? "bptt_persistent_kernel<LSTM>" : "bptt_persistent_kernel<GRU>");      // the route, for nntk_hip_last_recurrent_kernel()
+    return 0;
+}
+
+// ---- ragged batches and carried state (the *TrainingBatch*VarLen / *CalculateGradient*VarLen calls) ----------------------------
+// nntk_train_vl (nntk_shim.h) rides along every launcher below; NULL = the fixed-length, zero-state calls, kernel for kernel.
+static const nntk_train_vl k_no_vl = {nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+// the state after a row's last step: sT[b] = seq[b][len[b] - 1], or the initial state (zeros without one) of a row that never ran
+__global__ __launch_bounds__(256) void train_final_state_kernel(const float *__restrict__ seq, const int *__restrict__ len,
+                                                                const float *__restrict__ s0, float *__restrict__ sT, int B, int T, int H) {
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= B * H) return;
+    const int b = e / H, j = e % H;
+    const int L = len ? len[b] : T;
+    sT[e] = L > 0 ? seq[((size_t)b * T + L - 1) * H + j] : s0 ? s0[e] : 0.0f;
+}
+extern "C" int nntk_shim_train_final_state(const float *d_seq, const int *d_len, const float *d_s0, float *d_sT, int B, int T, int H) {
+    if (B <= 0 || H <= 0 || T <= 0) return 0;
+    hipLaunchKernelGGL(train_final_state_kernel, dim3((B * H + 255) / 256), dim3(256), 0, nntk_stream(), d_seq, d_len, d_s0, d_sT, B, T, H);
+    NNTK_LAUNCH_CHECK("train_final_state_kernel");
+    return 0;
+}
+// a copy of x [B][T][F] with exact zeros at t >= len[b]: what the weight-gradient product x^T d_xW reads (padding may hold anything,
+// NaN included, and 0 x NaN is not 0)
+__global__ __launch_bounds__(256) void train_mask_rows_kernel(const float *__restrict__ x, const int *__restrict__ len, float *__restrict__ xm,
+                                                              int B, int T, int F) {
+    const long total = (long)B * T * F;
+    for (long e = blockIdx.x * (long)blockDim.x + threadIdx.x; e < total; e += (long)gridDim.x * blockDim.x) {
+        const long row = e / F;
+        xm[e] = (int)(row % T) < len[row / T] ? x[e] : 0.0f;
+    }
+}
+extern "C" int nntk_shim_train_mask_rows(const float *d_x, const int *d_len, float *d_xm, int B, int T, int F) {
+    if (B <= 0 || T <= 0 || F <= 0) return 0;
+    hipLaunchKernelGGL(train_mask_rows_kernel, dim3(grid_for((long)B * T * F, 256)), dim3(256), 0, nntk_stream(), d_x, d_len, d_xm, B, T, F);
+    NNTK_LAUNCH_CHECK("train_mask_rows_kernel");
+    return 0;
+}
+// the gradient with respect to the initial state: a + b (GRU: d_h_prev_1 + d_h_prev_2 of step 0; b NULL: a alone), or -- a row that
+// never ran, whose final state IS its initial state -- what arrived at the final state, passed through: dT, plus (h of a layer without
+// sequences, whose output row is that state: dlast = d_dout [B][H]) the row's output gradient
+__global__ __launch_bounds__(256) void train_state_grad_kernel(const float *__restrict__ a, const float *__restrict__ b2, const int *__restrict__ len,
+                                                               const float *__restrict__ dT, const float *__restrict__ dlast,
+                                                               float *__restrict__ d0, int B, int H) {
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= B * H) return;
+    if (len && len[e / H] == 0) { d0[e] = add_rn(dT ? dT[e] : 0.0f, dlast ? dlast[e] : 0.0f); return; }
+    d0[e] = b2 ? add_rn(a[e], b2[e]) : a[e];
+}
+static int train_state_grad(const float *a, const float *b2, const int *len, const float *dT, const float *dlast, float *d0, int B, int H) {
+    hipLaunchKernelGGL(train_state_grad_kernel, dim3((B * H + 255) / 256), dim3(256), 0, nntk_stream(), a, b2, len, dT, dlast, d0, B, H);
+    NNTK_LAUNCH_CHECK("train_state_grad_kernel");
     return 0;
 }
 
@@ -1026,48 +1109,86 @@ static int bptt_persistent(BpttParams &p, float *d_count_words) {
 extern "C" int nntk_shim_gru_train_forward(const float *d_x, const float *d_W, const float *d_U, const float *d_bi, const float *d_bh,
                                            float *d_h, float *d_Zg, float *d_hU, int B, int T, int in, int H,
                                            const int *acts /*z,h,r*/, const float *scales) {
+    return nntk_shim_gru_train_forward_vl(d_x, d_W, d_U, d_bi, d_bh, d_h, d_Zg, d_hU, B, T, in, H, acts, scales, nullptr);
+}
+// ... of a ragged batch: rows run len[b] steps from h0[b]; d_h rows past a row's end are zeros (cleared here), the other caches' are never read
+extern "C" int nntk_shim_gru_train_forward_vl(const float *d_x, const float *d_W, const float *d_U, const float *d_bi, const float *d_bh,
+                                              float *d_h, float *d_Zg, float *d_hU, int B, int T, int in, int H,
+                                              const int *acts /*z,h,r*/, const float *scales, const nntk_train_vl *vlp) {
     if (B <= 0 || T <= 0) return 0;
+    const nntk_train_vl &vl = vlp ? *vlp : k_no_vl;
+    const int TS = vl.d_len ? vl.max_len : T;
+    if (vl.d_len && nntk_shim_memset(d_h, 0, (size_t)B * T * H * sizeof(float))) return -1;
     if (B > 65535) return nntk_fail_msg("recurrent training: mini-batch above 65535 (one grid row per batch entry)");
     GruTrainParams p{};
     p.x = d_x; p.W = d_W; p.U = d_U; p.bi = d_bi; p.bh = d_bh; p.h = d_h; p.Zg = d_Zg; p.hU = d_hU;
     p.B = B; p.T = T; p.in = in; p.H = H;
     p.act_z = acts[0]; p.act_h = acts[1]; p.act_r = acts[2];
     p.sc_z = scales[0]; p.sc_h = scales[1]; p.sc_r = scales[2];
-    for (int t = 0; t < T; ++t) {
+    p.len = vl.d_len; p.h0 = vl.d_h0;
+    for (int t = 0; t < TS; ++t) {
         p.t = t;
         hipLaunchKernelGGL(gru_train_fwd_step_kernel, dim3((unsigned)((H + 31) / 32), (unsigned)B), dim3(256), 0, nntk_stream(), p);
     }
     NNTK_LAUNCH_CHECK("gru_train_fwd_step_kernel");
+    nntk_set_last_rec_kernel("gru_train_fwd_step_kernel");
     return 0;
 }
 // backward recurrence; d_work: 2 x [B][H] (d_h_prev_1, d_h_prev_2) + [B][3H] (this step's d_hU)
 extern "C" int nntk_shim_gru_train_backward(const float *d_dout, const float *d_UT /*[3H][H]*/, const float *d_h, const float *d_Zg,
                                             const float *d_hU, float *d_dxW, float *d_dhU, float *d_work, int B, int T, int H,
                                             int return_sequences, const int *acts) {
+    return nntk_shim_gru_train_backward_vl(d_dout, d_UT, d_h, d_Zg, d_hU, d_dxW, d_dhU, d_work, B, T, H, return_sequences, acts, nullptr);
+}
+// ... of a ragged batch with carried state.  Rows are idle until their own last step (d_xW / d_hU rows past it: zeros, cleared here, so
+// the weight-gradient products need no mask); vl.d_dh0 = d_h_prev_1 + U d_hU of step 0: one more product than the zero-state pass needs.
+extern "C" int nntk_shim_gru_train_backward_vl(const float *d_dout, const float *d_UT /*[3H][H]*/, const float *d_h, const float *d_Zg,
+                                               const float *d_hU, float *d_dxW, float *d_dhU, float *d_work, int B, int T, int H,
+                                               int return_sequences, const int *acts, const nntk_train_vl *vlp) {
     if (B <= 0 || T <= 0) return 0;
     if (B > 65535) return nntk_fail_msg("recurrent training: mini-batch above 65535 (one grid row per batch entry)");
+    const nntk_train_vl &vl = vlp ? *vlp : k_no_vl;
+    const int TS = vl.d_len ? vl.max_len : T;
     float *dhp1 = d_work, *dhp2 = d_work + (size_t)B * H, *step = d_work + (size_t)2 * B * H;
+    if (vl.d_len) {
+        if (nntk_shim_memset(d_dxW, 0, (size_t)B * T * 3 * H * sizeof(float))) return -1;
+        if (nntk_shim_memset(d_dhU, 0, (size_t)B * T * 3 * H * sizeof(float))) return -1;
+    }
     {
         BpttParams q{};
         q.dout = d_dout; q.UT = d_UT; q.h = d_h; q.Zg = d_Zg; q.hU = d_hU; q.dG = d_dhU; q.dxW = d_dxW;
         q.B = B; q.T = T; q.H = H; q.return_sequences = return_sequences;
         q.act[0] = acts[0]; q.act[1] = acts[1]; q.act[2] = acts[2];
+        q.len = vl.d_len; q.s0 = vl.d_h0; q.dhT = vl.d_dhT; q.carry_out = vl.d_dh0 ? dhp1 : nullptr;
         const int rc = bptt_persistent<0>(q, step);
-        if (rc <= 0) return rc;
+        if (rc < 0) return rc;
+        if (rc == 0) {
+            if (!vl.d_dh0) return 0;
+            // step 0's d_hU rows (the flag words in `step` are done with: stream order), then the product the loop stops short of
+            if (nntk_shim_copy_rows_d2d(step, d_dhU, (size_t)T * 3 * H * sizeof(float), (size_t)3 * H * sizeof(float), (size_t)B)) return -1;
+            launch_rows_times_colmat(step, d_UT, dhp2, (long)B, H, 3 * H);
+            return train_state_grad(dhp1, dhp2, vl.d_len, vl.d_dhT, return_sequences ? nullptr : d_dout, vl.d_dh0, B, H);
+        }
     }
     GruBwdParams p{};
     p.dout = d_dout; p.h = d_h; p.Zg = d_Zg; p.hU = d_hU; p.dxW = d_dxW; p.dhU = d_dhU;
     p.dhp1 = dhp1; p.dhp2 = dhp2; p.dhp1_out = dhp1; p.dhU_step = step;
     p.B = B; p.T = T; p.H = H; p.return_sequences = return_sequences;
     p.act_z = acts[0]; p.act_h = acts[1]; p.act_r = acts[2];
-    for (int t = T - 1; t >= 0; --t) {
+    p.len = vl.d_len; p.h0 = vl.d_h0; p.dhT = vl.d_dhT;
+    if (TS == 0 && vl.d_dh0) {                                   // no row runs: nothing to carry back but what arrived
+        if (nntk_shim_memset(dhp1, 0, (size_t)B * H * sizeof(float))) return -1;
+        return train_state_grad(dhp1, nullptr, vl.d_len, vl.d_dhT, return_sequences ? nullptr : d_dout, vl.d_dh0, B, H);
+    }
+    for (int t = TS - 1; t >= 0; --t) {
         p.t = t;
         hipLaunchKernelGGL(gru_train_bwd_step_kernel, dim3((B * H + 255) / 256), dim3(256), 0, nntk_stream(), p);
-        if (t > 0)
+        if (t > 0 || vl.d_dh0)
             launch_rows_times_colmat(step, d_UT, dhp2, (long)B, H, 3 * H);
     }
     NNTK_LAUNCH_CHECK("gru_train_bwd_step_kernel");
-    return 0;
+    nntk_set_last_rec_kernel("gru_train_bwd_step_kernel");
+    return vl.d_dh0 ? train_state_grad(dhp1, dhp2, vl.d_len, vl.d_dhT, return_sequences ? nullptr : d_dout, vl.d_dh0, B, H) : 0;
 }
 
 // ---- LSTM training (layers/lstm.c:185-239 forward cell, :294-556 BPTT) --------------------------------------------
@@ -1078,11 +1199,14 @@ struct LstmTrainParams {
     int B, T, in, H, t, v2;
     int act[5];                            // i, f, g, o, out
     float sc[5];
+    const int *len;                        // ragged batches (NULL: every row T)
+    const float *h0, *c0;                  // [B][H] initial state or NULL (zeros)
 };
 __global__ __launch_bounds__(256) void lstm_train_fwd_step_kernel(LstmTrainParams p) {
     const int b = blockIdx.y, j = blockIdx.x * 32 + (threadIdx.x & 31), H = p.H;
     const size_t row = (size_t)b * p.T + p.t;
-    const float *hp = p.t > 0 ? p.h + (row - 1) * H : nullptr;      // zero state per sequence (lstm.c:441)
+    if (p.len && p.t >= p.len[b]) return;                           // past the row's end; its h row was cleared by the host
+    const float *hp = p.t > 0 ? p.h + (row - 1) * H : p.h0 ? p.h0 + (size_t)b * H : nullptr;      // zero state per sequence (lstm.c:441) unless carried in
     float Z[4], hu[4];
     if (!cell_dots_chunked<4>(p.x + row * p.in, hp, p.W, p.U, p.in, H, j, Z, hu)) return;
     float a[4];
@@ -1093,7 +1217,7 @@ __global__ __launch_bounds__(256) void lstm_train_fwd_step_kernel(LstmTrainParam
         Z[g] = add_rn(Z[g], hu[g]);
         a[g] = nntk_gate_act(p.act[g], Z[g], p.sc[g]);
     }
-    const float cp = p.t > 0 ? p.c[(row - 1) * H + j] : 0.0f;
+    const float cp = p.t > 0 ? p.c[(row - 1) * H + j] : p.c0 ? p.c0[(size_t)b * H + j] : 0.0f;
     const float c = add_rn(mul_rn(a[1], cp), mul_rn(a[0], a[2]));         // f c_prev + i g
     const float h = mul_rn(a[3], nntk_gate_act(p.act[4], c, p.sc[4]));
     float *zg = p.zifgo + row * 8 * H;
@@ -1112,17 +1236,26 @@ struct LstmBwdParams {
     int B, T, H, t, return_sequences;
     int act[5];
     float sc_out;
+    const int *len;              // ragged batches (NULL: every row T)
+    const float *c0, *dhT, *dcT; // [B][H] initial cell state / gradients arriving at the final state, or NULL (zeros)
 };
 __global__ __launch_bounds__(256) void lstm_train_bwd_step_kernel(LstmBwdParams p) {
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= p.B * p.H) return;
     const int b = e / p.H, j = e % p.H, H = p.H;
     const size_t row = (size_t)b * p.T + p.t;
+    const int L = p.len ? p.len[b] : p.T;
+    if (p.t >= L) {              // idle (the dgates rows were cleared by the host); a row that never runs hands back zeros
+        float *ds = p.dG_step + (size_t)b * 4 * H;
+        ds[j] = 0.0f; ds[H + j] = 0.0f; ds[2 * H + j] = 0.0f; ds[3 * H + j] = 0.0f;
+        p.dc_carry[e] = 0.0f;
+        return;
+    }
+    const bool last = p.t == L - 1;
     float dout = 0.0f;
     if (p.return_sequences) dout = p.dout[row * H + j];
-    else if (p.t == p.T - 1) dout = p.dout[(size_t)b * H + j];
-    const bool last = p.t == p.T - 1;
-    const float dh = add_rn(last ? 0.0f : p.dh_carry[e], dout);
+    else if (last) dout = p.dout[(size_t)b * H + j];
+    const float dh = add_rn(last ? (p.dhT ? p.dhT[e] : 0.0f) : p.dh_carry[e], dout);
     const float *zg = p.zifgo + row * 8 * H;
     const float it = zg[4 * H + j], ft = zg[5 * H + j], gt = zg[6 * H + j], ot = zg[7 * H + j];
     const float ct = p.c[row * H + j];
@@ -1131,8 +1264,10 @@ __global__ __launch_bounds__(256) void lstm_train_bwd_step_kernel(LstmBwdParams 
     // non-cached derivative of the output activation at c_t (activation.c:49-50): forward value recomputed, UNscaled
     float dc = gate_grad(p.act[4], ct, nntk_gate_act(p.act[4], ct, 1.0f), mul_rn(dh, ot));
     if (!last) dc = add_rn(dc, p.dc_carry[e]);
+    else if (p.dcT) dc = add_rn(dc, p.dcT[e]);
+    const float d_f = p.t > 0 ? gate_grad(p.act[1], zg[H + j], ft, mul_rn(p.c[(row - 1) * H + j], dc))
+                    : p.c0 ? gate_grad(p.act[1], zg[H + j], ft, mul_rn(p.c0[e], dc)) : 0.0f;
     const float d_i = gate_grad(p.act[0], zg[j], it, mul_rn(dc, gt));
-    const float d_f = p.t == 0 ? 0.0f : gate_grad(p.act[1], zg[H + j], ft, mul_rn(p.c[(row - 1) * H + j], dc));
     const float d_g = gate_grad(p.act[2], zg[2 * H + j], gt, mul_rn(dc, it));
     p.dc_carry[e] = mul_rn(dc, ft);
     float *dG = p.dG + row * 4 * H, *ds = p.dG_step + (size_t)b * 4 * H;
@@ -1142,48 +1277,88 @@ __global__ __launch_bounds__(256) void lstm_train_bwd_step_kernel(LstmBwdParams 
 extern "C" int nntk_shim_lstm_train_forward(const float *d_x, const float *d_W, const float *d_U, const float *d_bi, const float *d_bh,
                                             float *d_h, float *d_c, float *d_zifgo, int B, int T, int in, int H, int v2,
                                             const int *acts /*i,f,g,o,out*/, const float *scales) {
+    return nntk_shim_lstm_train_forward_vl(d_x, d_W, d_U, d_bi, d_bh, d_h, d_c, d_zifgo, B, T, in, H, v2, acts, scales, nullptr);
+}
+extern "C" int nntk_shim_lstm_train_forward_vl(const float *d_x, const float *d_W, const float *d_U, const float *d_bi, const float *d_bh,
+                                               float *d_h, float *d_c, float *d_zifgo, int B, int T, int in, int H, int v2,
+                                               const int *acts /*i,f,g,o,out*/, const float *scales, const nntk_train_vl *vlp) {
     if (B <= 0 || T <= 0) return 0;
+    const nntk_train_vl &vl = vlp ? *vlp : k_no_vl;
+    const int TS = vl.d_len ? vl.max_len : T;
+    if (vl.d_len && nntk_shim_memset(d_h, 0, (size_t)B * T * H * sizeof(float))) return -1;
     if (B > 65535) return nntk_fail_msg("recurrent training: mini-batch above 65535 (one grid row per batch entry)");
     LstmTrainParams p{};
     p.x = d_x; p.W = d_W; p.U = d_U; p.bi = d_bi; p.bh = d_bh; p.h = d_h; p.c = d_c; p.zifgo = d_zifgo;
     p.B = B; p.T = T; p.in = in; p.H = H; p.v2 = v2;
     for (int g = 0; g < 5; ++g) { p.act[g] = acts[g]; p.sc[g] = scales[g]; }
-    for (int t = 0; t < T; ++t) {
+    p.len = vl.d_len; p.h0 = vl.d_h0; p.c0 = vl.d_c0;
+    for (int t = 0; t < TS; ++t) {
         p.t = t;
         hipLaunchKernelGGL(lstm_train_fwd_step_kernel, dim3((unsigned)((H + 31) / 32), (unsigned)B), dim3(256), 0, nntk_stream(), p);
     }
     NNTK_LAUNCH_CHECK("lstm_train_fwd_step_kernel");
+    nntk_set_last_rec_kernel("lstm_train_fwd_step_kernel");
     return 0;
 }
 // d_work: [B][H] d_h carry + [B][H] d_c carry + [B][4H] this step's dgates
 extern "C" int nntk_shim_lstm_train_backward(const float *d_dout, const float *d_UT /*[4H][H]*/, const float *d_c, const float *d_zifgo,
                                              float *d_dG, float *d_work, int B, int T, int H, int return_sequences,
                                              const int *acts, const float *scales) {
+    return nntk_shim_lstm_train_backward_vl(d_dout, d_UT, d_c, d_zifgo, d_dG, d_work, B, T, H, return_sequences, acts, scales, nullptr);
+}
+// ... of a ragged batch with carried state: vl.d_dh0 = U dgates of step 0, vl.d_dc0 = the d_c carry after step 0
+extern "C" int nntk_shim_lstm_train_backward_vl(const float *d_dout, const float *d_UT /*[4H][H]*/, const float *d_c, const float *d_zifgo,
+                                                float *d_dG, float *d_work, int B, int T, int H, int return_sequences,
+                                                const int *acts, const float *scales, const nntk_train_vl *vlp) {
     if (B <= 0 || T <= 0) return 0;
     if (B > 65535) return nntk_fail_msg("recurrent training: mini-batch above 65535 (one grid row per batch entry)");
+    const nntk_train_vl &vl = vlp ? *vlp : k_no_vl;
+    const int TS = vl.d_len ? vl.max_len : T;
+    const bool want0 = vl.d_dh0 || vl.d_dc0;
     float *dh = d_work, *dc = d_work + (size_t)B * H, *step = d_work + (size_t)2 * B * H;
+    if (vl.d_len && nntk_shim_memset(d_dG, 0, (size_t)B * T * 4 * H * sizeof(float))) return -1;
+    auto finish = [&]() -> int {                                 // dh = U dgates_0, dc = the carry after step 0
+        if (vl.d_dh0 && train_state_grad(dh, nullptr, vl.d_len, vl.d_dhT, return_sequences ? nullptr : d_dout, vl.d_dh0, B, H)) return -1;
+        if (vl.d_dc0 && train_state_grad(dc, nullptr, vl.d_len, vl.d_dcT, nullptr, vl.d_dc0, B, H)) return -1;
+        return 0;
+    };
     {
         BpttParams q{};
         q.dout = d_dout; q.UT = d_UT; q.c = d_c; q.zifgo = d_zifgo; q.dG = d_dG;
         q.B = B; q.T = T; q.H = H; q.return_sequences = return_sequences;
         for (int g = 0; g < 5; ++g) q.act[g] = acts[g];
         q.sc_out = scales[4];
+        q.len = vl.d_len; q.s0 = vl.d_c0; q.dhT = vl.d_dhT; q.dcT = vl.d_dcT; q.carry_out = vl.d_dc0 ? dc : nullptr;
         const int rc = bptt_persistent<1>(q, step);
-        if (rc <= 0) return rc;
+        if (rc < 0) return rc;
+        if (rc == 0) {
+            if (!want0) return 0;
+            if (vl.d_dh0) {
+                if (nntk_shim_copy_rows_d2d(step, d_dG, (size_t)T * 4 * H * sizeof(float), (size_t)4 * H * sizeof(float), (size_t)B)) return -1;
+                launch_rows_times_colmat(step, d_UT, dh, (long)B, H, 4 * H);
+            }
+            return finish();
+        }
     }
     LstmBwdParams p{};
     p.dout = d_dout; p.c = d_c; p.zifgo = d_zifgo; p.dh_carry = dh; p.dc_carry = dc; p.dG = d_dG; p.dG_step = step;
     p.B = B; p.T = T; p.H = H; p.return_sequences = return_sequences;
     for (int g = 0; g < 5; ++g) p.act[g] = acts[g];
     p.sc_out = scales[4];
-    for (int t = T - 1; t >= 0; --t) {
+    p.len = vl.d_len; p.c0 = vl.d_c0; p.dhT = vl.d_dhT; p.dcT = vl.d_dcT;
+    if (TS == 0 && want0) {                                      // no row runs: what arrived goes straight back
+        if (nntk_shim_memset(d_work, 0, (size_t)2 * B * H * sizeof(float))) return -1;
+        return finish();
+    }
+    for (int t = TS - 1; t >= 0; --t) {
         p.t = t;
         hipLaunchKernelGGL(lstm_train_bwd_step_kernel, dim3((B * H + 255) / 256), dim3(256), 0, nntk_stream(), p);
-        if (t > 0)
+        if (t > 0 || vl.d_dh0)
             launch_rows_times_colmat(step, d_UT, dh, (long)B, H, 4 * H);
     }
     NNTK_LAUNCH_CHECK("lstm_train_bwd_step_kernel");
-    return 0;
+    nntk_set_last_rec_kernel("lstm_train_bwd_step_kernel");
+    return want0 ? finish() : 0;
 }
 
 // ---- RNN training (layers/rnn.c:144-166 forward cell, :184-221 backward cell, :249-351) ---------------------------
@@ -1193,11 +1368,14 @@ struct RnnTrainParams {
     float *h, *gate;
     int B, T, in, H, t, v2, act;
     float sc;
+    const int *len;                        // ragged batches (NULL: every row T)
+    const float *h0;                       // [B][H] initial state or NULL (zeros)
 };
 __global__ __launch_bounds__(256) void rnn_train_fwd_step_kernel(RnnTrainParams p) {
     const int b = blockIdx.y, j = blockIdx.x * 32 + (threadIdx.x & 31), H = p.H;
     const size_t row = (size_t)b * p.T + p.t;
-    const float *hp = p.t > 0 ? p.h + (row - 1) * H : nullptr;
+    if (p.len && p.t >= p.len[b]) return;                           // past the row's end; its h row was cleared by the host
+    const float *hp = p.t > 0 ? p.h + (row - 1) * H : p.h0 ? p.h0 + (size_t)b * H : nullptr;
     float xw[1], hu[1];
     if (!cell_dots_chunked<1>(p.x + row * p.in, hp, p.W, p.U, p.in, H, j, xw, hu)) return;
     const float xv = add_rn(xw[0], p.bi[j]);
@@ -1208,47 +1386,75 @@ __global__ __launch_bounds__(256) void rnn_train_fwd_step_kernel(RnnTrainParams 
 }
 __global__ __launch_bounds__(256) void rnn_train_bwd_step_kernel(const float *dout, const float *h, const float *gate,
                                                                  const float *dh_carry, float *dG, float *dG_step,
-                                                                 int B, int T, int H, int t, int return_sequences, int act) {
+                                                                 int B, int T, int H, int t, int return_sequences, int act,
+                                                                 const int *len, const float *dhT) {
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= B * H) return;
     const int b = e / H, j = e % H;
     const size_t row = (size_t)b * T + t;
+    const int L = len ? len[b] : T;
+    if (t >= L) { dG_step[e] = 0.0f; return; }      // idle (the d_gate rows were cleared by the host)
+    const bool last = t == L - 1;
     float d_o = 0.0f;
     if (return_sequences) d_o = dout[row * H + j];
-    else if (t == T - 1) d_o = dout[(size_t)b * H + j];
-    const float dh = add_rn(t == T - 1 ? 0.0f : dh_carry[e], d_o);
+    else if (last) d_o = dout[(size_t)b * H + j];
+    const float dh = add_rn(last ? (dhT ? dhT[e] : 0.0f) : dh_carry[e], d_o);
     const float dg = gate_grad(act, gate[row * H + j], h[row * H + j], dh);
     dG[row * H + j] = dg;
     dG_step[e] = dg;
 }
 extern "C" int nntk_shim_rnn_train_forward(const float *d_x, const float *d_W, const float *d_U, const float *d_bi, const float *d_bh,
                                            float *d_h, float *d_gate, int B, int T, int in, int H, int v2, int act, float scale) {
+    return nntk_shim_rnn_train_forward_vl(d_x, d_W, d_U, d_bi, d_bh, d_h, d_gate, B, T, in, H, v2, act, scale, nullptr);
+}
+extern "C" int nntk_shim_rnn_train_forward_vl(const float *d_x, const float *d_W, const float *d_U, const float *d_bi, const float *d_bh,
+                                              float *d_h, float *d_gate, int B, int T, int in, int H, int v2, int act, float scale,
+                                              const nntk_train_vl *vlp) {
     if (B <= 0 || T <= 0) return 0;
+    const nntk_train_vl &vl = vlp ? *vlp : k_no_vl;
+    const int TS = vl.d_len ? vl.max_len : T;
+    if (vl.d_len && nntk_shim_memset(d_h, 0, (size_t)B * T * H * sizeof(float))) return -1;
     if (B > 65535) return nntk_fail_msg("recurrent training: mini-batch above 65535 (one grid row per batch entry)");
     RnnTrainParams p{};
     p.x = d_x; p.W = d_W; p.U = d_U; p.bi = d_bi; p.bh = d_bh; p.h = d_h; p.gate = d_gate;
     p.B = B; p.T = T; p.in = in; p.H = H; p.v2 = v2; p.act = act; p.sc = scale;
-    for (int t = 0; t < T; ++t) {
+    p.len = vl.d_len; p.h0 = vl.d_h0;
+    for (int t = 0; t < TS; ++t) {
         p.t = t;
         hipLaunchKernelGGL(rnn_train_fwd_step_kernel, dim3((unsigned)((H + 31) / 32), (unsigned)B), dim3(256), 0, nntk_stream(), p);
     }
     NNTK_LAUNCH_CHECK("rnn_train_fwd_step_kernel");
+    nntk_set_last_rec_kernel("rnn_train_fwd_step_kernel");
     return 0;
 }
 // d_work: [B][H] d_h carry + [B][H] this step's d_gate
 extern "C" int nntk_shim_rnn_train_backward(const float *d_dout, const float *d_UT /*[H][H]*/, const float *d_h, const float *d_gate,
                                             float *d_dG, float *d_work, int B, int T, int H, int return_sequences, int act) {
+    return nntk_shim_rnn_train_backward_vl(d_dout, d_UT, d_h, d_gate, d_dG, d_work, B, T, H, return_sequences, act, nullptr);
+}
+// ... of a ragged batch with carried state: vl.d_dh0 = U d_gate of step 0
+extern "C" int nntk_shim_rnn_train_backward_vl(const float *d_dout, const float *d_UT /*[H][H]*/, const float *d_h, const float *d_gate,
+                                               float *d_dG, float *d_work, int B, int T, int H, int return_sequences, int act,
+                                               const nntk_train_vl *vlp) {
     if (B <= 0 || T <= 0) return 0;
     if (B > 65535) return nntk_fail_msg("recurrent training: mini-batch above 65535 (one grid row per batch entry)");
+    const nntk_train_vl &vl = vlp ? *vlp : k_no_vl;
+    const int TS = vl.d_len ? vl.max_len : T;
     float *dh = d_work, *step = d_work + (size_t)B * H;
-    for (int t = T - 1; t >= 0; --t) {
+    if (vl.d_len && nntk_shim_memset(d_dG, 0, (size_t)B * T * H * sizeof(float))) return -1;
+    if (TS == 0 && vl.d_dh0) {
+        if (nntk_shim_memset(dh, 0, (size_t)B * H * sizeof(float))) return -1;
+        return train_state_grad(dh, nullptr, vl.d_len, vl.d_dhT, return_sequences ? nullptr : d_dout, vl.d_dh0, B, H);
+    }
+    for (int t = TS - 1; t >= 0; --t) {
         hipLaunchKernelGGL(rnn_train_bwd_step_kernel, dim3((B * H + 255) / 256), dim3(256), 0, nntk_stream(), d_dout, d_h, d_gate,
-                           (const float *)dh, d_dG, step, B, T, H, t, return_sequences, act);
-        if (t > 0)
+                           (const float *)dh, d_dG, step, B, T, H, t, return_sequences, act, vl.d_len, vl.d_dhT);
+        if (t > 0 || vl.d_dh0)
             launch_rows_times_colmat(step, d_UT, dh, (long)B, H, H);
     }
     NNTK_LAUNCH_CHECK("rnn_train_bwd_step_kernel");
-    return 0;
+    nntk_set_last_rec_kernel("rnn_train_bwd_step_kernel");
+    return vl.d_dh0 ? train_state_grad(dh, nullptr, vl.d_len, vl.d_dhT, return_sequences ? nullptr : d_dout, vl.d_dh0, B, H) : 0;
 }
 
 // ---- MFMA forms of the large training products -------------------------------------------------------------------

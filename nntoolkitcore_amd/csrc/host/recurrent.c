@@ -649,11 +649,45 @@ typedef struct {
     int on, mini_batch, have_batch;
     const float *d_x_cur;        /* the mini-batch input of the last forward: d_x below (host-pointer calls) or the caller's device tensor */
     nntk_devbuf d_x, d_h, d_Zg, d_hU, d_dxW, d_dhU, d_work, d_raw, d_grad, d_scr, d_dout, d_dX;
+    /* the *VarLen training calls: what the last forward ran with (row lengths on the device, the caller's initial state), remembered for
+     * the gradient call; all NULL after a fixed-length, zero-state forward */
+    nntk_train_vl vl;
+    nntk_devbuf d_len, d_xm;     /* the lengths; the input with its padding steps cleared (what d_W's product reads) */
+    nntk_devbuf d_s0;            /* step 0's recurrent gate gradients [B][G H] (+ [G H] unused column sums): d_U's h0 term */
+    nntk_devbuf d_st;            /* host-memory forms: h0 | c0 | hT | cT | d_hT | d_cT | d_h0 | d_c0, [B][H] each */
+    nntk_devbuf d_yo;            /* host-memory forms: the forward output */
+    float *want_hT, *want_cT;    /* the forward call's final-state tensors, for a forward kernel that writes them itself (cleared when it did) */
 } rec_train;
 static void train_free(rec_train *t) {
     nntk_devbuf_free(&t->d_x); nntk_devbuf_free(&t->d_h); nntk_devbuf_free(&t->d_Zg); nntk_devbuf_free(&t->d_hU);
     nntk_devbuf_free(&t->d_dxW); nntk_devbuf_free(&t->d_dhU); nntk_devbuf_free(&t->d_work); nntk_devbuf_free(&t->d_raw);
     nntk_devbuf_free(&t->d_grad); nntk_devbuf_free(&t->d_scr); nntk_devbuf_free(&t->d_dout); nntk_devbuf_free(&t->d_dX);
+    nntk_devbuf_free(&t->d_len); nntk_devbuf_free(&t->d_xm); nntk_devbuf_free(&t->d_s0); nntk_devbuf_free(&t->d_st);
+    nntk_devbuf_free(&t->d_yo);
+}
+/* a ragged or carried-state forward (such a call always brings lengths: the *VarLen entry points fill them in) */
+static int train_vl_active(const nntk_train_vl *vl) { return vl && (vl->d_len || vl->d_h0 || vl->d_c0); }
+/* remembers what the forward ran with and gives the tensor the forward and d_W's product read: x itself, or -- ragged -- its copy with
+ * the padding steps cleared (they may hold NaN) */
+static const float *train_vl_begin(rec_train *t, const nntk_train_vl *vl, const float *d_x, int B, int T, int in) {
+    t->have_batch = 0;           /* until this forward has been enqueued whole: a gradient call must not pair new lengths with old caches */
+    memset(&t->vl, 0, sizeof t->vl);
+    if (!vl) return d_x;
+    t->vl.d_len = vl->d_len; t->vl.max_len = vl->max_len; t->vl.d_h0 = vl->d_h0; t->vl.d_c0 = vl->d_c0;
+    if (!vl->d_len) return d_x;
+    float *d_xm = nntk_devbuf_reserve(&t->d_xm, (size_t)B * T * in);
+    if (!d_xm || nntk_shim_train_mask_rows(d_x, vl->d_len, d_xm, B, T, in)) return NULL;
+    return d_xm;
+}
+/* d_U += h0^T d_hU_0: the step-0 rows of the recurrent gate gradients d_G [B][T][K] against the carried-in state (the time-shifted product
+ * reads zeros there) */
+static int train_vl_dU_h0(rec_train *t, const float *d_G, float *d_dU, int B, int T, int H, int K) {
+    if (!t->vl.d_h0) return 0;
+    float *s0 = nntk_devbuf_reserve(&t->d_s0, (size_t)B * K + K);
+    if (!s0) return -1;
+    if (nntk_shim_copy_rows_d2d(s0, d_G, (size_t)T * K * sizeof(float), (size_t)K * sizeof(float), (size_t)B)) return -1;
+    if (nntk_shim_memset(s0 + (size_t)B * K, 0, (size_t)K * sizeof(float))) return -1;
+    return nntk_train_outer_accumulate(t->vl.d_h0, s0, d_dU, s0 + (size_t)B * K, (long)B, H, K, 0);
 }
 
 struct GRUStruct {
@@ -763,7 +797,7 @@ void RecurrentGradientDestroy(RecurrentGradient *gradient) {
 }
 
 /* forward over the mini-batch with the caches kept for the gradient; d_x is a device tensor that stays valid until the gradient call */
-static int gru_train_forward_dev(GRU filter, const float *d_x) {
+static int gru_train_forward_dev(GRU filter, const float *d_x, const nntk_train_vl *vl) {
     int acts[3];
     float sc[3];
     if (gru_acts(filter, acts, sc)) return -1;
@@ -778,6 +812,7 @@ static int gru_train_forward_dev(GRU filter, const float *d_x) {
     if (!d_h || !d_Zg || !d_hU || !d_raw) return -1;
     if (nntk_shim_upload(d_raw, c->wb.host, nw * sizeof(float))) return -1;          /* W | U | b_i | b_h, caller layout */
     const float *dW = d_raw, *dU = dW + (size_t)in * 3 * H, *dbi = dU + (size_t)H * 3 * H, *dbh = dbi + 3 * (size_t)H;
+    if (!(d_x = train_vl_begin(t, vl, d_x, B, T, in))) return -1;
     /* default activations, any mini-batch: ONE launch of the register-resident kernel with the caches written from
      * its gate phase (recurrent_rr.hip gru_rr_kernel<.., TRAIN>); its image is re-packed from the current weights every call */
     int ran = 0, rr_on = -1;
@@ -789,11 +824,18 @@ static int gru_train_forward_dev(GRU filter, const float *d_x) {
         if (gru_rr_build_image(in, H, c->weights->W, c->weights->U, c->weights->b_i, c->weights->b_h, &c->d_rr_train, img, &c->d_b4_train, &c->d_rr_stage, NULL)) return -1;
         float *d_hs = nntk_devbuf_reserve(&c->d_hseq, nntk_shim_rr_hseq_floats(B, T, H));
         if (!d_hs) return -1;
-        int rc = nntk_shim_gru_rr_train_forward(d_x, c->d_rr_train, c->d_b4_train, d_h, d_hU, d_Zg, d_hs, d_wk, B, T, in, H);
+        int rc;
+        if (train_vl_active(vl)) {       /* the same kernel's TRAIN + VL instantiation: lengths, h0 in, hT out */
+            rc = nntk_shim_rr_train_forward_vl(1, d_x, c->d_rr_train, c->d_b4_train, NULL, vl->d_h0, NULL, d_h, d_hU, d_Zg, t->want_hT, NULL,
+                                               d_hs, d_wk, vl->d_len, B, T, in, H);
+            if (rc == 0 && nntk_shim_varlen_zero_pad(d_h, vl->d_len, B, T, H)) return -1;
+            if (rc == 0) t->want_hT = NULL;
+        } else
+            rc = nntk_shim_gru_rr_train_forward(d_x, c->d_rr_train, c->d_b4_train, d_h, d_hU, d_Zg, d_hs, d_wk, B, T, in, H);
         if (rc < 0) return -1;
         ran = rc == 0;
     }
-    if (!ran && nntk_shim_gru_train_forward(d_x, dW, dU, dbi, dbh, d_h, d_Zg, d_hU, B, T, in, H, acts, sc)) return -1;
+    if (!ran && nntk_shim_gru_train_forward_vl(d_x, dW, dU, dbi, dbh, d_h, d_Zg, d_hU, B, T, in, H, acts, sc, train_vl_active(vl) ? vl : NULL)) return -1;
     t->d_x_cur = d_x;
     t->have_batch = 1;
     return 0;
@@ -809,7 +851,7 @@ int GRUApplyTrainingBatch(GRU filter, const float *input, float *output) {
     float *d_x = nntk_devbuf_reserve(&t->d_x, (size_t)B * T * in);
     if (!d_x) return -1;
     if (nntk_shim_upload(d_x, input, (size_t)B * T * in * sizeof(float))) return -1;
-    if (gru_train_forward_dev(filter, d_x)) return -1;
+    if (gru_train_forward_dev(filter, d_x, NULL)) return -1;
     const float *d_h = t->d_h.p;
     if (c->return_sequences) return nntk_shim_download(output, d_h, (size_t)B * T * H * sizeof(float));
     /* the last step of every sequence (gru.c:286-291, lstm.c:466-471, rnn.c:283-288): one strided copy */
@@ -824,7 +866,7 @@ int GRUApplyTrainingBatchDevice(GRU filter, const float *d_input, float *d_outpu
     rec_train *t = &filter->train;
     const int B = t->mini_batch, T = c->T, H = c->H;
     if (B <= 0 || T <= 0) return 0;
-    if (gru_train_forward_dev(filter, d_input)) return -1;
+    if (gru_train_forward_dev(filter, d_input, NULL)) return -1;
     if (!d_output) return 0;
     if (c->return_sequences) return nntk_shim_copy_d2d(d_output, t->d_h.p, (size_t)B * T * H * sizeof(float));
     return nntk_shim_copy_rows_d2d(d_output, t->d_h.p + (size_t)(T - 1) * H, (size_t)T * H * sizeof(float), (size_t)H * sizeof(float), (size_t)B);
@@ -832,7 +874,7 @@ int GRUApplyTrainingBatchDevice(GRU filter, const float *d_input, float *d_outpu
 
 /* d_W, d_U, d_b_i, d_b_h are ADDED onto the caller's block (recurrent_gradient_sum per (b, t), gru.c:508), d_X is
  * overwritten.  void in the reference; errors through nntk_last_error(). */
-static int gru_train_gradient_dev(GRU filter, const float *d_dout, float *d_grad, float *d_dX) {
+static int gru_train_gradient_dev(GRU filter, const float *d_dout, float *d_grad, float *d_dX, const nntk_train_vl *vl) {
     rec_core *c = &filter->core;
     rec_train *t = &filter->train;
     int acts[3];
@@ -847,11 +889,12 @@ static int gru_train_gradient_dev(GRU filter, const float *d_dout, float *d_grad
     if (!d_dxW || !d_dhU || !d_work || !d_UT) return -1;
     const float *dW = t->d_raw.p, *dU = dW + w;
     if (nntk_shim_transpose(dU, d_UT, H, 3 * H, 0)) return -1;                  /* U^T [3H][H]: coalesced per-step product */
-    if (nntk_shim_gru_train_backward(d_dout, d_UT, t->d_h.p, t->d_Zg.p, t->d_hU.p, d_dxW, d_dhU, d_work, B, T, H,
-                                     c->return_sequences ? 1 : 0, acts)) return -1;
+    if (nntk_shim_gru_train_backward_vl(d_dout, d_UT, t->d_h.p, t->d_Zg.p, t->d_hU.p, d_dxW, d_dhU, d_work, B, T, H,
+                                        c->return_sequences ? 1 : 0, acts, vl)) return -1;
     /* d_W += x^T d_xW, d_b_i += colsum d_xW;  d_U += h_prev^T d_hU, d_b_h += colsum d_hU;  d_X = d_xW W^T */
     if (nntk_train_outer_accumulate(t->d_x_cur, d_dxW, d_grad, d_grad + w + u, (long)rows, in, 3 * H, 0)) return -1;
     if (nntk_train_outer_accumulate(t->d_h.p, d_dhU, d_grad + w, d_grad + w + u + b3, (long)rows, H, 3 * H, T)) return -1;
+    if (vl && train_vl_dU_h0(t, d_dhU, d_grad + w, B, T, H, 3 * H)) return -1;
     return nntk_train_rows_times_rowmat(d_dxW, dW, d_dX, (long)rows, in, 3 * H);
 }
 void GRUCalculateGradient(GRU filter, GRUGradient *gradient, float *d_out) {
@@ -869,7 +912,7 @@ void GRUCalculateGradient(GRU filter, GRUGradient *gradient, float *d_out) {
     if (!d_dout || !d_grad || !d_dX) return;
     if (nntk_shim_upload(d_dout, d_out, n_do * sizeof(float))) return;
     if (nntk_shim_upload(d_grad, gradient->d_W, (w + u + 2 * b3) * sizeof(float))) return;       /* the block is contiguous */
-    if (gru_train_gradient_dev(filter, d_dout, d_grad, d_dX)) return;
+    if (gru_train_gradient_dev(filter, d_dout, d_grad, d_dX, train_vl_active(&t->vl) ? &t->vl : NULL)) return;
     if (nntk_shim_download(gradient->d_W, d_grad, (w + u + 2 * b3) * sizeof(float))) return;
     nntk_shim_download(gradient->d_X, d_dX, rows * in * sizeof(float));
 }
@@ -880,7 +923,7 @@ int GRUCalculateGradientDevice(GRU filter, float *d_grad, float *d_dX, const flo
     nntk_shim_clear_error();
     if (!filter || !d_grad || !d_dX || !d_dout) NNTK_FAIL("GRUCalculateGradientDevice: NULL argument");
     if (!filter->train.on || !filter->train.have_batch) NNTK_FAIL("GRUCalculateGradientDevice: run GRUApplyTrainingBatch[Device] on a training handle first");
-    return gru_train_gradient_dev(filter, d_dout, d_grad, d_dX);
+    return gru_train_gradient_dev(filter, d_dout, d_grad, d_dX, train_vl_active(&filter->train.vl) ? &filter->train.vl : NULL);
 }
 
 int GRUApplyInference(GRU filter, const float *input, float *output) {
@@ -1150,7 +1193,7 @@ LSTMGradient *LSTMGradientCreate(LSTMConfig config, LSTMTrainingConfig training_
     return g;
 }
 
-static int lstm_train_forward_dev(LSTM filter, const float *d_x) {
+static int lstm_train_forward_dev(LSTM filter, const float *d_x, const nntk_train_vl *vl) {
     int acts[5];
     float sc[5];
     if (lstm_acts(filter, acts, sc)) return -1;
@@ -1165,6 +1208,7 @@ static int lstm_train_forward_dev(LSTM filter, const float *d_x) {
     if (!d_h || !d_z || !d_c || !d_raw) return -1;
     if (nntk_shim_upload(d_raw, c->wb.host, nw * sizeof(float))) return -1;          /* W | U | b_i | b_h, caller layout */
     const float *dW = d_raw, *dU = dW + (size_t)in * 4 * H, *dbi = dU + (size_t)H * 4 * H, *dbh = dbi + 4 * (size_t)H;
+    if (!(d_x = train_vl_begin(t, vl, d_x, B, T, in))) return -1;
     /* standard activations, any mini-batch: the register-resident inference kernel with the caches written
      * from its gate phase (recurrent_rr.hip, TRAIN): ONE launch instead of T; its weight images are packed on the device from
      * the block just uploaded (the weights change with every optimiser step).  Otherwise: one launch per timestep. */
@@ -1178,11 +1222,19 @@ static int lstm_train_forward_dev(LSTM filter, const float *d_x) {
         if (nntk_shim_lstm_rr_pack_raw(dU, dW, c->d_rr_train, H, in)) return -1;
         float *d_hs = nntk_devbuf_reserve(&c->d_hseq, nntk_shim_rr_hseq_floats(B, T, H));
         if (!d_hs) return -1;
-        int rc = nntk_shim_lstm_rr_train_forward(d_x, c->d_rr_train, dbi, filter->config.v2 ? dbh : NULL, d_h, d_c, d_z, d_hs, d_wk, B, T, in, H);
+        int rc;
+        if (train_vl_active(vl)) {       /* the same kernel's TRAIN + VL instantiation: lengths, h0 / c0 in, hT / cT out */
+            rc = nntk_shim_rr_train_forward_vl(0, d_x, c->d_rr_train, dbi, filter->config.v2 ? dbh : NULL, vl->d_h0, vl->d_c0, d_h, d_c, d_z,
+                                               t->want_hT, t->want_cT, d_hs, d_wk, vl->d_len, B, T, in, H);
+            if (rc == 0 && nntk_shim_varlen_zero_pad(d_h, vl->d_len, B, T, H)) return -1;
+            if (rc == 0) t->want_hT = t->want_cT = NULL;
+        } else
+            rc = nntk_shim_lstm_rr_train_forward(d_x, c->d_rr_train, dbi, filter->config.v2 ? dbh : NULL, d_h, d_c, d_z, d_hs, d_wk, B, T, in, H);
         if (rc < 0) return -1;
         ran = rc == 0;
     }
-    if (!ran && nntk_shim_lstm_train_forward(d_x, dW, dU, dbi, dbh, d_h, d_c, d_z, B, T, in, H, filter->config.v2 ? 1 : 0, acts, sc)) return -1;
+    if (!ran && nntk_shim_lstm_train_forward_vl(d_x, dW, dU, dbi, dbh, d_h, d_c, d_z, B, T, in, H, filter->config.v2 ? 1 : 0, acts, sc,
+                                                train_vl_active(vl) ? vl : NULL)) return -1;
     t->d_x_cur = d_x;
     t->have_batch = 1;
     return 0;
@@ -1198,7 +1250,7 @@ int LSTMApplyTrainingBatch(LSTM filter, const float *input, float *output) {
     float *d_x = nntk_devbuf_reserve(&t->d_x, (size_t)B * T * in);
     if (!d_x) return -1;
     if (nntk_shim_upload(d_x, input, (size_t)B * T * in * sizeof(float))) return -1;
-    if (lstm_train_forward_dev(filter, d_x)) return -1;
+    if (lstm_train_forward_dev(filter, d_x, NULL)) return -1;
     const float *d_h = t->d_h.p;
     if (c->return_sequences) return nntk_shim_download(output, d_h, (size_t)B * T * H * sizeof(float));
     /* the last step of every sequence (gru.c:286-291, lstm.c:466-471, rnn.c:283-288): one strided copy */
@@ -1213,13 +1265,13 @@ int LSTMApplyTrainingBatchDevice(LSTM filter, const float *d_input, float *d_out
     rec_train *t = &filter->train;
     const int B = t->mini_batch, T = c->T, H = c->H;
     if (B <= 0 || T <= 0) return 0;
-    if (lstm_train_forward_dev(filter, d_input)) return -1;
+    if (lstm_train_forward_dev(filter, d_input, NULL)) return -1;
     if (!d_output) return 0;
     if (c->return_sequences) return nntk_shim_copy_d2d(d_output, t->d_h.p, (size_t)B * T * H * sizeof(float));
     return nntk_shim_copy_rows_d2d(d_output, t->d_h.p + (size_t)(T - 1) * H, (size_t)T * H * sizeof(float), (size_t)H * sizeof(float), (size_t)B);
 }
 
-static int lstm_train_gradient_dev(LSTM filter, const float *d_dout, float *d_grad, float *d_dX) {
+static int lstm_train_gradient_dev(LSTM filter, const float *d_dout, float *d_grad, float *d_dX, const nntk_train_vl *vl) {
     rec_core *c = &filter->core;
     rec_train *t = &filter->train;
     int acts[5];
@@ -1233,10 +1285,11 @@ static int lstm_train_gradient_dev(LSTM filter, const float *d_dout, float *d_gr
     if (!d_dG || !d_work || !d_UT) return -1;
     const float *dW = t->d_raw.p, *dU = dW + w;
     if (nntk_shim_transpose(dU, d_UT, H, 4 * H, 0)) return -1;
-    if (nntk_shim_lstm_train_backward(d_dout, d_UT, t->d_hU.p, t->d_Zg.p, d_dG, d_work, B, T, H, c->return_sequences ? 1 : 0, acts, sc)) return -1;
+    if (nntk_shim_lstm_train_backward_vl(d_dout, d_UT, t->d_hU.p, t->d_Zg.p, d_dG, d_work, B, T, H, c->return_sequences ? 1 : 0, acts, sc, vl)) return -1;
     /* d_W += x^T dgates, d_U += h_prev^T dgates, d_b_i += colsum, d_b_h += colsum (lstm.c:412-415), d_X = dgates W^T */
     if (nntk_train_outer_accumulate(t->d_x_cur, d_dG, d_grad, d_grad + w + u, (long)rows, in, 4 * H, 0)) return -1;
     if (nntk_train_outer_accumulate(t->d_h.p, d_dG, d_grad + w, d_grad + w + u + b4, (long)rows, H, 4 * H, T)) return -1;
+    if (vl && train_vl_dU_h0(t, d_dG, d_grad + w, B, T, H, 4 * H)) return -1;
     return nntk_train_rows_times_rowmat(d_dG, dW, d_dX, (long)rows, in, 4 * H);
 }
 void LSTMCalculateGradient(LSTM filter, LSTMGradient *gradient, float *d_out) {
@@ -1254,7 +1307,7 @@ void LSTMCalculateGradient(LSTM filter, LSTMGradient *gradient, float *d_out) {
     if (!d_dout || !d_grad || !d_dX) return;
     if (nntk_shim_upload(d_dout, d_out, n_do * sizeof(float))) return;
     if (nntk_shim_upload(d_grad, gradient->d_W, (w + u + 2 * b4) * sizeof(float))) return;
-    if (lstm_train_gradient_dev(filter, d_dout, d_grad, d_dX)) return;
+    if (lstm_train_gradient_dev(filter, d_dout, d_grad, d_dX, train_vl_active(&t->vl) ? &t->vl : NULL)) return;
     if (nntk_shim_download(gradient->d_W, d_grad, (w + u + 2 * b4) * sizeof(float))) return;
     nntk_shim_download(gradient->d_X, d_dX, rows * in * sizeof(float));
 }
@@ -1263,7 +1316,7 @@ int LSTMCalculateGradientDevice(LSTM filter, float *d_grad, float *d_dX, const f
     nntk_shim_clear_error();
     if (!filter || !d_grad || !d_dX || !d_dout) NNTK_FAIL("LSTMCalculateGradientDevice: NULL argument");
     if (!filter->train.on || !filter->train.have_batch) NNTK_FAIL("LSTMCalculateGradientDevice: run LSTMApplyTrainingBatch[Device] on a training handle first");
-    return lstm_train_gradient_dev(filter, d_dout, d_grad, d_dX);
+    return lstm_train_gradient_dev(filter, d_dout, d_grad, d_dX, train_vl_active(&filter->train.vl) ? &filter->train.vl : NULL);
 }
 
 int LSTMApplyInference(LSTM filter, const float *input, float *output) {
@@ -1497,31 +1550,86 @@ RNNGradient *RNNGradientCreate(RNNConfig config, RNNTrainingConfig training_conf
     g->d_X = g->d_b_h + H;
     return g;
 }
-int RNNApplyTrainingBatch(RNN filter, const float *input, float *output) {
-    nntk_shim_clear_error();
-    if (!filter) NNTK_FAIL("RNNApplyTrainingBatch: NULL handle");
-    if (!filter->train.on) NNTK_FAIL("RNNApplyTrainingBatch: the handle was created for inference");      /* rnn.c:250-252 */
+/* forward over the mini-batch with the caches kept for the gradient; d_x is a device tensor that stays valid until the gradient call */
+static int rnn_train_forward_dev(RNN filter, const float *d_x, const nntk_train_vl *vl) {
     int act;
     float sc;
     if (gate_kind(filter->config.activation, &act, &sc)) return -1;
     rec_core *c = &filter->core;
     rec_train *t = &filter->train;
     const int B = t->mini_batch, T = c->T, in = c->in, H = c->H;
-    if (B <= 0 || T <= 0) return 0;
     const size_t nw = (size_t)in * H + (size_t)H * H + 2 * (size_t)H;
-    float *d_x = nntk_devbuf_reserve(&t->d_x, (size_t)B * T * in);
     float *d_h = nntk_devbuf_reserve(&t->d_h, (size_t)B * T * H);
     float *d_g = nntk_devbuf_reserve(&t->d_Zg, (size_t)B * T * H);
     float *d_raw = nntk_devbuf_reserve(&t->d_raw, nw);
-    if (!d_x || !d_h || !d_g || !d_raw) return -1;
-    if (nntk_shim_upload(d_x, input, (size_t)B * T * in * sizeof(float))) return -1;
+    if (!d_h || !d_g || !d_raw) return -1;
     if (nntk_shim_upload(d_raw, c->wb.host, nw * sizeof(float))) return -1;
     const float *dW = d_raw, *dU = dW + (size_t)in * H, *dbi = dU + (size_t)H * H, *dbh = dbi + H;
-    if (nntk_shim_rnn_train_forward(d_x, dW, dU, dbi, dbh, d_h, d_g, B, T, in, H, filter->config.v2 ? 1 : 0, act, sc)) return -1;
+    if (!(d_x = train_vl_begin(t, vl, d_x, B, T, in))) return -1;
+    if (nntk_shim_rnn_train_forward_vl(d_x, dW, dU, dbi, dbh, d_h, d_g, B, T, in, H, filter->config.v2 ? 1 : 0, act, sc,
+                                       train_vl_active(vl) ? vl : NULL)) return -1;
+    t->d_x_cur = d_x;
     t->have_batch = 1;
+    return 0;
+}
+int RNNApplyTrainingBatch(RNN filter, const float *input, float *output) {
+    nntk_shim_clear_error();
+    if (!filter) NNTK_FAIL("RNNApplyTrainingBatch: NULL handle");
+    if (!filter->train.on) NNTK_FAIL("RNNApplyTrainingBatch: the handle was created for inference");      /* rnn.c:250-252 */
+    rec_core *c = &filter->core;
+    rec_train *t = &filter->train;
+    const int B = t->mini_batch, T = c->T, in = c->in, H = c->H;
+    if (B <= 0 || T <= 0) return 0;
+    float *d_x = nntk_devbuf_reserve(&t->d_x, (size_t)B * T * in);
+    if (!d_x) return -1;
+    if (nntk_shim_upload(d_x, input, (size_t)B * T * in * sizeof(float))) return -1;
+    if (rnn_train_forward_dev(filter, d_x, NULL)) return -1;
+    const float *d_h = t->d_h.p;
     if (c->return_sequences) return nntk_shim_download(output, d_h, (size_t)B * T * H * sizeof(float));
     /* the last step of every sequence (gru.c:286-291, lstm.c:466-471, rnn.c:283-288): one strided copy */
     return nntk_shim_download_rows(output, d_h + (size_t)(T - 1) * H, (size_t)T * H * sizeof(float), (size_t)H * sizeof(float), (size_t)B);
+}
+/* device-pointer form, in the shape of the GRU's: d_input [B][T][in] must stay valid until RNNCalculateGradientDevice; d_output [B][T][H] or [B][H] */
+int RNNApplyTrainingBatchDevice(RNN filter, const float *d_input, float *d_output) {
+    nntk_shim_clear_error();
+    if (!filter) NNTK_FAIL("RNNApplyTrainingBatchDevice: NULL handle");
+    if (!filter->train.on) NNTK_FAIL("RNNApplyTrainingBatchDevice: the handle was created for inference");
+    rec_core *c = &filter->core;
+    rec_train *t = &filter->train;
+    const int B = t->mini_batch, T = c->T, H = c->H;
+    if (B <= 0 || T <= 0) return 0;
+    if (rnn_train_forward_dev(filter, d_input, NULL)) return -1;
+    if (!d_output) return 0;
+    if (c->return_sequences) return nntk_shim_copy_d2d(d_output, t->d_h.p, (size_t)B * T * H * sizeof(float));
+    return nntk_shim_copy_rows_d2d(d_output, t->d_h.p + (size_t)(T - 1) * H, (size_t)T * H * sizeof(float), (size_t)H * sizeof(float), (size_t)B);
+}
+/* d_W, d_U, d_b_i, d_b_h are ADDED onto the caller's block, d_X is overwritten */
+static int rnn_train_gradient_dev(RNN filter, const float *d_dout, float *d_grad, float *d_dX, const nntk_train_vl *vl) {
+    rec_core *c = &filter->core;
+    rec_train *t = &filter->train;
+    int act;
+    float sc;
+    if (gate_kind(filter->config.activation, &act, &sc)) return -1;
+    const int B = t->mini_batch, T = c->T, in = c->in, H = c->H;
+    const size_t w = (size_t)in * H, u = (size_t)H * H, rows = (size_t)B * T;
+    float *d_dG = nntk_devbuf_reserve(&t->d_dxW, rows * H);
+    float *d_work = nntk_devbuf_reserve(&t->d_work, (size_t)B * 2 * H);
+    float *d_UT = nntk_devbuf_reserve(&t->d_scr, u);
+    if (!d_dG || !d_work || !d_UT) return -1;
+    const float *dW = t->d_raw.p, *dU = dW + w;
+    if (nntk_shim_transpose(dU, d_UT, H, H, 0)) return -1;
+    if (nntk_shim_rnn_train_backward_vl(d_dout, d_UT, t->d_h.p, t->d_Zg.p, d_dG, d_work, B, T, H, c->return_sequences ? 1 : 0, act, vl)) return -1;
+    if (nntk_train_outer_accumulate(t->d_x_cur, d_dG, d_grad, d_grad + w + u, (long)rows, in, H, 0)) return -1;
+    if (nntk_train_outer_accumulate(t->d_h.p, d_dG, d_grad + w, d_grad + w + u + H, (long)rows, H, H, T)) return -1;
+    if (vl && train_vl_dU_h0(t, d_dG, d_grad + w, B, T, H, H)) return -1;
+    return nntk_train_rows_times_rowmat(d_dG, dW, d_dX, (long)rows, in, H);
+}
+/* device-pointer form: d_grad = W [in][H] | U [H][H] | b_i [H] | b_h [H] is ADDED to, d_dX [B][T][in] overwritten; d_dout [B][T][H] or [B][H] */
+int RNNCalculateGradientDevice(RNN filter, float *d_grad, float *d_dX, const float *d_dout) {
+    nntk_shim_clear_error();
+    if (!filter || !d_grad || !d_dX || !d_dout) NNTK_FAIL("RNNCalculateGradientDevice: NULL argument");
+    if (!filter->train.on || !filter->train.have_batch) NNTK_FAIL("RNNCalculateGradientDevice: run RNNApplyTrainingBatch[Device] on a training handle first");
+    return rnn_train_gradient_dev(filter, d_dout, d_grad, d_dX, train_vl_active(&filter->train.vl) ? &filter->train.vl : NULL);
 }
 void RNNCalculateGradient(RNN filter, RNNGradient *gradient, float *d_out) {
     nntk_shim_clear_error();
@@ -1529,29 +1637,220 @@ void RNNCalculateGradient(RNN filter, RNNGradient *gradient, float *d_out) {
     rec_core *c = &filter->core;
     rec_train *t = &filter->train;
     if (!t->on || !t->have_batch) { nntk_set_error("RNNCalculateGradient: run RNNApplyTrainingBatch on a training handle first"); return; }
-    int act;
-    float sc;
-    if (gate_kind(filter->config.activation, &act, &sc)) return;
     const int B = t->mini_batch, T = c->T, in = c->in, H = c->H;
     const size_t w = (size_t)in * H, u = (size_t)H * H, rows = (size_t)B * T;
     const size_t n_do = c->return_sequences ? rows * H : (size_t)B * H;
     float *d_dout = nntk_devbuf_reserve(&t->d_dout, n_do);
-    float *d_dG = nntk_devbuf_reserve(&t->d_dxW, rows * H);
-    float *d_work = nntk_devbuf_reserve(&t->d_work, (size_t)B * 2 * H);
     float *d_grad = nntk_devbuf_reserve(&t->d_grad, w + u + 2 * (size_t)H);
-    float *d_UT = nntk_devbuf_reserve(&t->d_scr, u);
     float *d_dX = nntk_devbuf_reserve(&t->d_dX, rows * in);
-    if (!d_dout || !d_dG || !d_work || !d_grad || !d_UT || !d_dX) return;
-    const float *dW = t->d_raw.p, *dU = dW + w;
+    if (!d_dout || !d_grad || !d_dX) return;
     if (nntk_shim_upload(d_dout, d_out, n_do * sizeof(float))) return;
     if (nntk_shim_upload(d_grad, gradient->d_W, (w + u + 2 * (size_t)H) * sizeof(float))) return;
-    if (nntk_shim_transpose(dU, d_UT, H, H, 0)) return;
-    if (nntk_shim_rnn_train_backward(d_dout, d_UT, t->d_h.p, t->d_Zg.p, d_dG, d_work, B, T, H, c->return_sequences ? 1 : 0, act)) return;
-    if (nntk_train_outer_accumulate(t->d_x.p, d_dG, d_grad, d_grad + w + u, (long)rows, in, H, 0)) return;
-    if (nntk_train_outer_accumulate(t->d_h.p, d_dG, d_grad + w, d_grad + w + u + H, (long)rows, H, H, T)) return;
-    if (nntk_train_rows_times_rowmat(d_dG, dW, d_dX, (long)rows, in, H)) return;
+    if (rnn_train_gradient_dev(filter, d_dout, d_grad, d_dX, train_vl_active(&t->vl) ? &t->vl : NULL)) return;
     if (nntk_shim_download(gradient->d_W, d_grad, (w + u + 2 * (size_t)H) * sizeof(float))) return;
     nntk_shim_download(gradient->d_X, d_dX, rows * in * sizeof(float));
+}
+
+/* ---- training on ragged batches with carried state (INTEGRATION.md "Training on ragged batches and long streams") ----
+ * The *ApplyTrainingBatch*VarLen / *CalculateGradient*VarLen calls of the three cells share everything but the cell's own forward /
+ * gradient routine: the checks, the staging of the lengths, the outputs taken from the h (c) cache and the host-memory wrappers. */
+typedef int (*train_fwd_fn)(void *filter, const float *d_x, const nntk_train_vl *vl);
+typedef int (*train_grad_fn)(void *filter, const float *d_dout, float *d_grad, float *d_dX, const nntk_train_vl *vl);
+static int gru_fwd_v(void *f, const float *x, const nntk_train_vl *vl) { return gru_train_forward_dev((GRU)f, x, vl); }
+static int lstm_fwd_v(void *f, const float *x, const nntk_train_vl *vl) { return lstm_train_forward_dev((LSTM)f, x, vl); }
+static int rnn_fwd_v(void *f, const float *x, const nntk_train_vl *vl) { return rnn_train_forward_dev((RNN)f, x, vl); }
+static int gru_grad_v(void *f, const float *d, float *g, float *dx, const nntk_train_vl *vl) { return gru_train_gradient_dev((GRU)f, d, g, dx, vl); }
+static int lstm_grad_v(void *f, const float *d, float *g, float *dx, const nntk_train_vl *vl) { return lstm_train_gradient_dev((LSTM)f, d, g, dx, vl); }
+static int rnn_grad_v(void *f, const float *d, float *g, float *dx, const nntk_train_vl *vl) { return rnn_train_gradient_dev((RNN)f, d, g, dx, vl); }
+
+/* the lengths: checked before anything is enqueued */
+static int train_vl_check(const char *who, const int *lengths, int B, int T, int *max_len) {
+    char msg[256];
+    *max_len = T;
+    if (!lengths) return 0;
+    int m = 0;
+    for (int b = 0; b < B; ++b) {
+        if (lengths[b] < 0 || lengths[b] > T) {
+            snprintf(msg, sizeof msg, "%s: lengths[%d] = %d is outside [0, %d]", who, b, lengths[b], T);
+            NNTK_FAIL(msg);
+        }
+        if (lengths[b] > m) m = lengths[b];
+    }
+    *max_len = m;
+    return 0;
+}
+static int train_apply_vl_dev(rec_core *c, rec_train *t, void *filter, train_fwd_fn fwd, int is_lstm, const char *who,
+                              const float *d_input, float *d_output, const int *lengths,
+                              const float *d_h0, const float *d_c0, float *d_hT, float *d_cT) {
+    char msg[256];
+    if (!t->on) { snprintf(msg, sizeof msg, "%s: the handle was created for inference", who); NNTK_FAIL(msg); }
+    const int B = t->mini_batch, T = c->T, H = c->H;
+    nntk_train_vl vl;
+    memset(&vl, 0, sizeof vl);
+    if (train_vl_check(who, lengths, B > 0 ? B : 0, T, &vl.max_len)) return -1;
+    if (B <= 0 || T <= 0) return 0;
+    if (!d_input) { snprintf(msg, sizeof msg, "%s: NULL input", who); NNTK_FAIL(msg); }
+    vl.d_h0 = d_h0;
+    vl.d_c0 = is_lstm ? d_c0 : NULL;
+    if (lengths || vl.d_h0 || vl.d_c0) {         /* (a carried-in state alone: every row T) the lengths, then the 64-row tiles' maxima */
+        const int nbt = (B + 63) / 64;
+        int *hl = (int *)malloc(((size_t)B + nbt) * sizeof(int));
+        if (!hl) NNTK_FAIL("out of host memory");
+        for (int i = 0; i < nbt; ++i) hl[B + i] = 0;
+        for (int b = 0; b < B; ++b) {
+            hl[b] = lengths ? lengths[b] : T;
+            if (hl[b] > hl[B + b / 64]) hl[B + b / 64] = hl[b];
+        }
+        int *d_len = (int *)nntk_devbuf_reserve(&t->d_len, (size_t)B + nbt);
+        const int up = d_len ? nntk_shim_upload_ints(d_len, hl, (long)B + nbt) : -1;
+        free(hl);
+        if (up) return -1;
+        vl.d_len = d_len;
+    }
+    t->want_hT = d_hT; t->want_cT = is_lstm ? d_cT : NULL;
+    const int frc = fwd(filter, d_input, &vl);
+    d_hT = t->want_hT; d_cT = t->want_cT;       /* NULL again when the forward kernel wrote them itself */
+    t->want_hT = t->want_cT = NULL;
+    if (frc) return -1;
+    const float *d_h = t->d_h.p;
+    if (d_output) {
+        int rc;
+        if (c->return_sequences) rc = nntk_shim_copy_d2d(d_output, d_h, (size_t)B * T * H * sizeof(float));      /* rows past a length: zeros */
+        else if (vl.d_len) rc = nntk_shim_train_final_state(d_h, vl.d_len, d_h0, d_output, B, T, H);
+        else rc = nntk_shim_copy_rows_d2d(d_output, d_h + (size_t)(T - 1) * H, (size_t)T * H * sizeof(float), (size_t)H * sizeof(float), (size_t)B);
+        if (rc) return -1;
+    }
+    if (d_hT && nntk_shim_train_final_state(d_h, vl.d_len, d_h0, d_hT, B, T, H)) return -1;
+    if (is_lstm && d_cT && nntk_shim_train_final_state(t->d_hU.p, vl.d_len, d_c0, d_cT, B, T, H)) return -1;
+    return 0;
+}
+static int train_gradient_vl_dev(rec_train *t, void *filter, train_grad_fn grad, int is_lstm, const char *who,
+                                 float *d_grad, float *d_dX, const float *d_dout,
+                                 const float *d_dhT, const float *d_dcT, float *d_dh0, float *d_dc0) {
+    char msg[256];
+    if (!d_grad || !d_dX || !d_dout) { snprintf(msg, sizeof msg, "%s: NULL argument", who); NNTK_FAIL(msg); }
+    if (!t->on || !t->have_batch) { snprintf(msg, sizeof msg, "%s: run the forward call on a training handle first", who); NNTK_FAIL(msg); }
+    nntk_train_vl vl = t->vl;
+    vl.d_dhT = d_dhT; vl.d_dh0 = d_dh0;
+    vl.d_dcT = is_lstm ? d_dcT : NULL; vl.d_dc0 = is_lstm ? d_dc0 : NULL;
+    return grad(filter, d_dout, d_grad, d_dX, &vl);
+}
+/* host-memory forms: upload, device call, download; the state tensors live in the handle (h0 / c0 until the gradient call) */
+static int train_apply_vl_host(rec_core *c, rec_train *t, void *filter, train_fwd_fn fwd, int is_lstm, const char *who,
+                               const float *input, float *output, const int *lengths,
+                               const float *h0, const float *c0, float *hT, float *cT) {
+    char msg[256];
+    if (!t->on) { snprintf(msg, sizeof msg, "%s: the handle was created for inference", who); NNTK_FAIL(msg); }
+    const int B = t->mini_batch, T = c->T, in = c->in, H = c->H;
+    int max_len;
+    if (train_vl_check(who, lengths, B > 0 ? B : 0, T, &max_len)) return -1;
+    if (B <= 0 || T <= 0) return 0;
+    if (!input || !output) { snprintf(msg, sizeof msg, "%s: NULL argument", who); NNTK_FAIL(msg); }
+    const size_t BH = (size_t)B * H, n_out = c->return_sequences ? (size_t)B * T * H : BH;
+    float *d_x = nntk_devbuf_reserve(&t->d_x, (size_t)B * T * in);
+    float *d_st = nntk_devbuf_reserve(&t->d_st, 8 * BH);
+    float *d_out = nntk_devbuf_reserve(&t->d_yo, n_out);
+    if (!d_x || !d_st || !d_out) return -1;
+    float *d_h0 = h0 ? d_st : NULL, *d_c0 = (is_lstm && c0) ? d_st + BH : NULL;
+    float *d_hT = hT ? d_st + 2 * BH : NULL, *d_cT = (is_lstm && cT) ? d_st + 3 * BH : NULL;
+    if (nntk_shim_upload(d_x, input, (size_t)B * T * in * sizeof(float))) return -1;
+    if (d_h0 && nntk_shim_upload(d_h0, h0, BH * sizeof(float))) return -1;
+    if (d_c0 && nntk_shim_upload(d_c0, c0, BH * sizeof(float))) return -1;
+    if (train_apply_vl_dev(c, t, filter, fwd, is_lstm, who, d_x, d_out, lengths, d_h0, d_c0, d_hT, d_cT)) return -1;
+    if (d_hT && nntk_shim_download(hT, d_hT, BH * sizeof(float))) return -1;
+    if (d_cT && nntk_shim_download(cT, d_cT, BH * sizeof(float))) return -1;
+    return nntk_shim_download(output, d_out, n_out * sizeof(float));
+}
+static int train_gradient_vl_host(rec_core *c, rec_train *t, void *filter, train_grad_fn grad, int is_lstm, const char *who,
+                                  RecurrentGradient *gradient, const float *d_out, const float *hT_grad, const float *cT_grad,
+                                  float *h0_grad, float *c0_grad) {
+    char msg[256];
+    if (!gradient || !d_out) { snprintf(msg, sizeof msg, "%s: NULL argument", who); NNTK_FAIL(msg); }
+    if (!t->on || !t->have_batch) { snprintf(msg, sizeof msg, "%s: run the forward call on a training handle first", who); NNTK_FAIL(msg); }
+    const int B = t->mini_batch, T = c->T, in = c->in, H = c->H, G = c->G;
+    const size_t nblk = (size_t)in * G * H + (size_t)H * G * H + 2 * (size_t)G * H, rows = (size_t)B * T, BH = (size_t)B * H;
+    const size_t n_do = c->return_sequences ? rows * H : BH;
+    float *d_dout = nntk_devbuf_reserve(&t->d_dout, n_do);
+    float *d_grad = nntk_devbuf_reserve(&t->d_grad, nblk);
+    float *d_dX = nntk_devbuf_reserve(&t->d_dX, rows * in);
+    float *d_st = nntk_devbuf_reserve(&t->d_st, 8 * BH);      /* (already this size when the forward went through the host form: h0 / c0 stay) */
+    if (!d_dout || !d_grad || !d_dX || !d_st) return -1;
+    float *d_dhT = hT_grad ? d_st + 4 * BH : NULL, *d_dcT = (is_lstm && cT_grad) ? d_st + 5 * BH : NULL;
+    float *d_dh0 = h0_grad ? d_st + 6 * BH : NULL, *d_dc0 = (is_lstm && c0_grad) ? d_st + 7 * BH : NULL;
+    if (nntk_shim_upload(d_dout, d_out, n_do * sizeof(float))) return -1;
+    if (nntk_shim_upload(d_grad, gradient->d_W, nblk * sizeof(float))) return -1;       /* the block is contiguous */
+    if (d_dhT && nntk_shim_upload(d_dhT, hT_grad, BH * sizeof(float))) return -1;
+    if (d_dcT && nntk_shim_upload(d_dcT, cT_grad, BH * sizeof(float))) return -1;
+    if (train_gradient_vl_dev(t, filter, grad, is_lstm, who, d_grad, d_dX, d_dout, d_dhT, d_dcT, d_dh0, d_dc0)) return -1;
+    if (nntk_shim_download(gradient->d_W, d_grad, nblk * sizeof(float))) return -1;
+    if (d_dh0 && nntk_shim_download(h0_grad, d_dh0, BH * sizeof(float))) return -1;
+    if (d_dc0 && nntk_shim_download(c0_grad, d_dc0, BH * sizeof(float))) return -1;
+    return nntk_shim_download(gradient->d_X, d_dX, rows * in * sizeof(float));
+}
+
+int GRUApplyTrainingBatchDeviceVarLen(GRU filter, const float *d_input, float *d_output, const int *lengths, const float *d_h0, float *d_hT) {
+    nntk_shim_clear_error();
+    if (!filter) NNTK_FAIL("GRUApplyTrainingBatchDeviceVarLen: NULL handle");
+    return train_apply_vl_dev(&filter->core, &filter->train, filter, gru_fwd_v, 0, "GRUApplyTrainingBatchDeviceVarLen", d_input, d_output, lengths, d_h0, NULL, d_hT, NULL);
+}
+int GRUCalculateGradientDeviceVarLen(GRU filter, float *d_grad, float *d_dX, const float *d_dout, const float *d_dhT, float *d_dh0) {
+    nntk_shim_clear_error();
+    if (!filter) NNTK_FAIL("GRUCalculateGradientDeviceVarLen: NULL handle");
+    return train_gradient_vl_dev(&filter->train, filter, gru_grad_v, 0, "GRUCalculateGradientDeviceVarLen", d_grad, d_dX, d_dout, d_dhT, NULL, d_dh0, NULL);
+}
+int GRUApplyTrainingBatchVarLen(GRU filter, const float *input, float *output, const int *lengths, const float *h0, float *hT) {
+    nntk_shim_clear_error();
+    if (!filter) NNTK_FAIL("GRUApplyTrainingBatchVarLen: NULL handle");
+    return train_apply_vl_host(&filter->core, &filter->train, filter, gru_fwd_v, 0, "GRUApplyTrainingBatchVarLen", input, output, lengths, h0, NULL, hT, NULL);
+}
+int GRUCalculateGradientVarLen(GRU filter, GRUGradient *gradient, const float *d_out, const float *d_hT_grad, float *d_h0_grad) {
+    nntk_shim_clear_error();
+    if (!filter) NNTK_FAIL("GRUCalculateGradientVarLen: NULL handle");
+    return train_gradient_vl_host(&filter->core, &filter->train, filter, gru_grad_v, 0, "GRUCalculateGradientVarLen", gradient, d_out, d_hT_grad, NULL, d_h0_grad, NULL);
+}
+int RNNApplyTrainingBatchDeviceVarLen(RNN filter, const float *d_input, float *d_output, const int *lengths, const float *d_h0, float *d_hT) {
+    nntk_shim_clear_error();
+    if (!filter) NNTK_FAIL("RNNApplyTrainingBatchDeviceVarLen: NULL handle");
+    return train_apply_vl_dev(&filter->core, &filter->train, filter, rnn_fwd_v, 0, "RNNApplyTrainingBatchDeviceVarLen", d_input, d_output, lengths, d_h0, NULL, d_hT, NULL);
+}
+int RNNCalculateGradientDeviceVarLen(RNN filter, float *d_grad, float *d_dX, const float *d_dout, const float *d_dhT, float *d_dh0) {
+    nntk_shim_clear_error();
+    if (!filter) NNTK_FAIL("RNNCalculateGradientDeviceVarLen: NULL handle");
+    return train_gradient_vl_dev(&filter->train, filter, rnn_grad_v, 0, "RNNCalculateGradientDeviceVarLen", d_grad, d_dX, d_dout, d_dhT, NULL, d_dh0, NULL);
+}
+int RNNApplyTrainingBatchVarLen(RNN filter, const float *input, float *output, const int *lengths, const float *h0, float *hT) {
+    nntk_shim_clear_error();
+    if (!filter) NNTK_FAIL("RNNApplyTrainingBatchVarLen: NULL handle");
+    return train_apply_vl_host(&filter->core, &filter->train, filter, rnn_fwd_v, 0, "RNNApplyTrainingBatchVarLen", input, output, lengths, h0, NULL, hT, NULL);
+}
+int RNNCalculateGradientVarLen(RNN filter, RNNGradient *gradient, const float *d_out, const float *d_hT_grad, float *d_h0_grad) {
+    nntk_shim_clear_error();
+    if (!filter) NNTK_FAIL("RNNCalculateGradientVarLen: NULL handle");
+    return train_gradient_vl_host(&filter->core, &filter->train, filter, rnn_grad_v, 0, "RNNCalculateGradientVarLen", gradient, d_out, d_hT_grad, NULL, d_h0_grad, NULL);
+}
+int LSTMApplyTrainingBatchDeviceVarLen(LSTM filter, const float *d_input, float *d_output, const int *lengths,
+                                       const float *d_h0, const float *d_c0, float *d_hT, float *d_cT) {
+    nntk_shim_clear_error();
+    if (!filter) NNTK_FAIL("LSTMApplyTrainingBatchDeviceVarLen: NULL handle");
+    return train_apply_vl_dev(&filter->core, &filter->train, filter, lstm_fwd_v, 1, "LSTMApplyTrainingBatchDeviceVarLen", d_input, d_output, lengths, d_h0, d_c0, d_hT, d_cT);
+}
+int LSTMCalculateGradientDeviceVarLen(LSTM filter, float *d_grad, float *d_dX, const float *d_dout,
+                                      const float *d_dhT, const float *d_dcT, float *d_dh0, float *d_dc0) {
+    nntk_shim_clear_error();
+    if (!filter) NNTK_FAIL("LSTMCalculateGradientDeviceVarLen: NULL handle");
+    return train_gradient_vl_dev(&filter->train, filter, lstm_grad_v, 1, "LSTMCalculateGradientDeviceVarLen", d_grad, d_dX, d_dout, d_dhT, d_dcT, d_dh0, d_dc0);
+}
+int LSTMApplyTrainingBatchVarLen(LSTM filter, const float *input, float *output, const int *lengths,
+                                 const float *h0, const float *c0, float *hT, float *cT) {
+    nntk_shim_clear_error();
+    if (!filter) NNTK_FAIL("LSTMApplyTrainingBatchVarLen: NULL handle");
+    return train_apply_vl_host(&filter->core, &filter->train, filter, lstm_fwd_v, 1, "LSTMApplyTrainingBatchVarLen", input, output, lengths, h0, c0, hT, cT);
+}
+int LSTMCalculateGradientVarLen(LSTM filter, LSTMGradient *gradient, const float *d_out, const float *d_hT_grad, const float *d_cT_grad,
+                                float *d_h0_grad, float *d_c0_grad) {
+    nntk_shim_clear_error();
+    if (!filter) NNTK_FAIL("LSTMCalculateGradientVarLen: NULL handle");
+    return train_gradient_vl_host(&filter->core, &filter->train, filter, lstm_grad_v, 1, "LSTMCalculateGradientVarLen", gradient, d_out, d_hT_grad, d_cT_grad, d_h0_grad, d_c0_grad);
 }
 
 int RNNApplyInference(RNN filter, const float *input, float *output) {
