@@ -491,15 +491,9 @@ int TimeDistributedDenseApplyDeviceVarLen(TimeDistributedDense filter, const flo
     if (!filter) NNTK_FAIL("TimeDistributedDenseApplyDeviceVarLen: NULL handle");
     const int ts = filter->config.ts;
     if (batch < 0) { snprintf(msg, sizeof msg, "TimeDistributedDenseApplyDeviceVarLen: batch %d < 0", batch); NNTK_FAIL(msg); }
-    int pad = 0;
-    if (lengths)
-        for (int b = 0; b < batch; ++b) {
-            if (lengths[b] < 0 || lengths[b] > ts) {
-                snprintf(msg, sizeof msg, "TimeDistributedDenseApplyDeviceVarLen: lengths[%d] = %d is outside [0, %d]", b, lengths[b], ts);
-                NNTK_FAIL(msg);
-            }
-            pad |= lengths[b] < ts;
-        }
+    int shortest;
+    if (nntk_check_lengths("TimeDistributedDenseApplyDeviceVarLen", lengths, batch, ts, &shortest, NULL)) return -1;
+    const int pad = shortest < ts;
     if (batch == 0 || ts <= 0) return 0;
     if (!d_input || !d_output) NNTK_FAIL("TimeDistributedDenseApplyDeviceVarLen: NULL tensor");
     const size_t n_in = (size_t)batch * ts * filter->dense->config.input_size * 4, n_o = (size_t)batch * ts * filter->dense->config.output_size * 4;

@@ -93,6 +93,12 @@ float *nntk_lstm_frag2h_scratch(LSTM f, int batch);      /* ... and its FRAG2H o
 /* the LSTM's sequence output as a FRAG2H tensor: 0 done, 1 not available for this layer (non-standard activations), -1 error */
 int nntk_lstm_apply_device_h2(LSTM f, const float *d_in, const float *d_in_f3, float *d_out_h2, int B);
 
+/* recurrent.c: the row lengths of a *VarLen call (host memory; NULL: every row T), checked before anything is enqueued.  -1 with the error
+ * set when one lies outside [0, T]; else the shortest and the longest row (T and T without lengths); either result pointer may be NULL.
+ * Internal to the library: not an exported symbol. */
+__attribute__((visibility("hidden")))
+int nntk_check_lengths(const char *who, const int *lengths, int B, int T, int *min_len, int *max_len);
+
 void nntk_set_error(const char *msg);
 #define NNTK_FAIL(msg) do { nntk_set_error(msg); return -1; } while (0)
 
