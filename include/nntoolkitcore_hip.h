@@ -740,6 +740,35 @@ int nntk_mean_squared_error_derivative_device(const float *d_y, const float *d_p
 int nntk_categorical_crossentropy_derivative_device(const float *d_y, const float *d_pred, float *d_out, int c, int batch);
 int nntk_sgd_optimize_device(SGD optimizer, const float *d_gradient, float *d_weights, long size);
 
+/* ---- CTC (Graves et al., 2006) on softmax probabilities: loss, gradient, best-path decoding; rows ragged --------
+ * The loss of a frame-wise softmax trained on unsegmented label sequences, and the decoder that goes with it (INTEGRATION.md "CTC").
+ *   d_probs [batch][T][C]: PROBABILITIES (a softmax TimeDistributedDense's output), not log-probabilities; frames t >= input_lengths[b]
+ *     influence nothing and may hold anything, NaN included.
+ *   input_lengths / labels [batch][max_label_len] / label_lengths: HOST memory (input_lengths NULL = every row T), checked before anything
+ *     is enqueued -- -1, nntk_last_error() and nothing written for an input length outside [0, T], a label length outside
+ *     [0, max_label_len], a label outside [0, C) or equal to blank, or blank outside [0, C) -- and copied in stream order.
+ *   d_loss_rows [batch]: -log p(labels_b | probs_b), unreduced; +inf for a row no alignment produces (input_length < label_length + the
+ *     number of adjacent equal labels, or zeros in d_probs on every path).  input_length 0: 0 for an empty label, +inf otherwise.
+ *   d_dprobs [batch][T][C] or NULL: d loss_b / d probs[b][t][k] -- what TimeDistributedDenseCalculateGradientDevice of a softmax layer takes
+ *     as d_dout.  Every element is written; exact zeros for t >= input_lengths[b], for a class no alignment passes through at (b, t)
+ *     (every probs == 0 entry included), and for the whole row when its loss is +inf.
+ *   d_workspace: nntk_ctc_workspace_floats(batch, T, max_label_len) floats, 16-byte aligned.  With d_dprobs == NULL only its first
+ *     nntk_ctc_workspace_floats(batch, 0, max_label_len) floats are touched.  Limits: max_label_len <= 4000; with a gradient C <= 32768.
+ * Deterministic: the same bits on every call, the same loss bits with and without a gradient, a row's bits independent of the other rows.
+ * Greedy decode: per row and t < input_length, argmax over C (ties: the lowest index); frames equal to the previous frame's argmax and
+ * blanks are dropped.  d_labels_out [batch][T]: the row's labels, then -1 up to T; d_out_lengths [batch].
+ * The host-pointer forms upload, run the device form and download.  All run on the calling thread's current stream. */
+size_t nntk_ctc_workspace_floats(int batch, int T, int max_label_len);
+int nntk_ctc_loss_device(const float *d_probs, int batch, int T, int C, const int *input_lengths, const int *labels,
+                         const int *label_lengths, int max_label_len, int blank, float *d_loss_rows, float *d_dprobs,
+                         float *d_workspace);
+int nntk_ctc_greedy_decode_device(const float *d_probs, int batch, int T, int C, const int *input_lengths, int blank,
+                                  int *d_labels_out, int *d_out_lengths);
+int nntk_ctc_loss(const float *probs, int batch, int T, int C, const int *input_lengths, const int *labels, const int *label_lengths,
+                  int max_label_len, int blank, float *loss_rows, float *dprobs);
+int nntk_ctc_greedy_decode(const float *probs, int batch, int T, int C, const int *input_lengths, int blank, int *labels_out,
+                           int *out_lengths);
+
 #ifdef __cplusplus
 }
 #endif

@@ -400,6 +400,12 @@ SIGNATURES = {
     "LogMelSpectrogramApplyDeviceStream": (C.c_int, [vp, vp, ip, ip, vp, ip, vp, ip, C.c_int]),
     "Conv1dBatchNormActivationApplyDeviceStream": (C.c_int, [vp, vp, vp, vp, ip, ip, vp, ip, vp, ip, C.c_int]),
     "TimeDistributedDenseApplyDeviceVarLen": (C.c_int, [vp, vp, vp, C.c_int, ip]),
+    # CTC: loss, gradient with respect to the probabilities, best-path decoding (INTEGRATION.md "CTC")
+    "nntk_ctc_workspace_floats": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "nntk_ctc_loss_device": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, ip, ip, ip, C.c_int, C.c_int, vp, vp, vp]),
+    "nntk_ctc_greedy_decode_device": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, ip, C.c_int, vp, vp]),
+    "nntk_ctc_loss": (C.c_int, [fp, C.c_int, C.c_int, C.c_int, ip, ip, ip, C.c_int, C.c_int, fp, fp]),
+    "nntk_ctc_greedy_decode": (C.c_int, [fp, C.c_int, C.c_int, C.c_int, ip, C.c_int, ip, ip]),
     "GRUResetState": (C.c_int, [vp]),
     "LSTMResetState": (C.c_int, [vp]),
     "RNNResetState": (C.c_int, [vp]),

@@ -133,6 +133,14 @@ int nntk_shim_dense_grad(const float *d_x, const float *d_W /*[in,out] caller la
 int nntk_shim_loss_rows(int kind /*0 mse, 1 categorical ce*/, const float *d_y, const float *d_pred, float *d_per_row, int size, int batch);
 int nntk_shim_loss_grad(int kind, const float *d_y, const float *d_pred, float *d_out, int size, int batch);
 int nntk_shim_sgd(float lr, const float *d_grad, float *d_w, long n);
+/* ---- CTC (ctc.hip): loss rows, gradient with respect to the probabilities, best-path decoding.  The int arrays are HOST memory,
+ *      already checked by the caller (train.c), never NULL, copied in stream order; d_dprobs NULL = loss only; d_ws 16-byte aligned,
+ *      nntk_shim_ctc_workspace_floats words (loss only: the int arrays and 2 words per row at its start are all that is touched) ---- */
+size_t nntk_shim_ctc_workspace_floats(int batch, int T, int max_label_len);
+int nntk_shim_ctc_loss(const float *d_probs, int B, int T, int C, const int *h_input_lengths, const int *h_labels,
+                       const int *h_label_lengths, int max_label_len, int blank, float *d_loss_rows, float *d_dprobs, float *d_ws);
+int nntk_shim_ctc_greedy_decode(const float *d_probs, int B, int T, int C, const int *h_input_lengths, int blank, int *d_labels_out,
+                                int *d_out_lengths);
 /* BatchNorm training (batch_norm.c:191-386): x, d_out [N, F]; d_block = gamma | beta | ...; d_stats [8][F] = mean | variance |
  * var_eps | sqrt_var | d_beta | d_gamma | d_var | d_mu; d_partial [slices][3][F] with slices from nntk_shim_bn_train_slices */
 /* GRU training (gru.c:246-512): caller-layout weights W [in][3H], U [H][3H]; caches h [B][T][H], Zg [B][T][6H], hU [B][T][H];

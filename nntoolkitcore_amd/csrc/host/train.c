@@ -4,6 +4,7 @@
  * and host-pointer signatures, plus device-pointer forms for callers that keep tensors in HBM.  The kernels
  * (csrc/hip/train.hip) follow the reference's operation order.
  */
+#include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 #include "nntk_internal.h"
@@ -154,6 +155,113 @@ void mean_squared_error_derivative(float *y, float *y_pred, float *d_y_pred, int
 }
 void categorical_crossentropy_derivative(float *y, float *y_pred, float *d_y_pred, int c, int batch) {
     loss_grad_host(1, y, y_pred, d_y_pred, c, batch);
+}
+
+/* ---- CTC (csrc/hip/ctc.hip): every host array is checked here, before anything is enqueued or allocated ---- */
+static int ctc_fail(const char *who, const char *fmt, int a, int b, int c) {
+    char msg[200];
+    int n = snprintf(msg, sizeof msg, "%s: ", who);
+    snprintf(msg + n, sizeof msg - (size_t)n, fmt, a, b, c);
+    nntk_set_error(msg);
+    return -1;
+}
+static int ctc_check_shape(const char *who, int batch, int T, int C, int blank) {
+    if (batch < 0 || T < 0 || C <= 0) return ctc_fail(who, "batch %d, T %d, C %d: batch and T must be >= 0, C > 0", batch, T, C);
+    if (blank < 0 || blank >= C) return ctc_fail(who, "blank %d is outside [0, %d)", blank, C, 0);
+    return 0;
+}
+static int ctc_check_labels(const char *who, int batch, int C, const int *labels, const int *label_lengths, int max_label_len, int blank) {
+    if (max_label_len < 0) return ctc_fail(who, "max_label_len %d < 0", max_label_len, 0, 0);
+    if (batch > 0 && (!label_lengths || (max_label_len > 0 && !labels))) NNTK_FAIL("nntk_ctc_loss: NULL labels / label_lengths");
+    for (int b = 0; b < batch; ++b) {
+        const int L = label_lengths[b];
+        if (L < 0 || L > max_label_len) return ctc_fail(who, "label_lengths[%d] = %d is outside [0, %d]", b, L, max_label_len);
+        for (int i = 0; i < L; ++i) {
+            const int k = labels[(size_t)b * max_label_len + i];
+            if (k < 0 || k >= C) return ctc_fail(who, "labels[%d][%d] = %d is not a class", b, i, k);
+            if (k == blank) return ctc_fail(who, "labels[%d][%d] is the blank (%d)", b, i, k);
+        }
+    }
+    return 0;
+}
+/* the input lengths the kernels read: the caller's, or T for every row; NULL = out of host memory */
+static int *ctc_lengths(const int *input_lengths, int batch, int T) {
+    int *len = (int *)malloc((size_t)(batch > 0 ? batch : 1) * sizeof(int));
+    if (!len) { nntk_set_error("out of host memory"); return NULL; }
+    for (int b = 0; b < batch; ++b) len[b] = input_lengths ? input_lengths[b] : T;
+    return len;
+}
+
+size_t nntk_ctc_workspace_floats(int batch, int T, int max_label_len) {
+    return nntk_shim_ctc_workspace_floats(batch, T, max_label_len);
+}
+
+int nntk_ctc_loss_device(const float *d_probs, int batch, int T, int C, const int *input_lengths, const int *labels,
+                         const int *label_lengths, int max_label_len, int blank, float *d_loss_rows, float *d_dprobs,
+                         float *d_workspace) {
+    static const char who[] = "nntk_ctc_loss_device";
+    nntk_shim_clear_error();
+    if (ctc_check_shape(who, batch, T, C, blank) || nntk_check_lengths(who, input_lengths, batch, T, NULL, NULL) ||
+        ctc_check_labels(who, batch, C, labels, label_lengths, max_label_len, blank)) return -1;
+    if (batch == 0) return 0;
+    if (!d_loss_rows || !d_workspace || (!d_probs && T > 0)) NNTK_FAIL("nntk_ctc_loss_device: NULL tensor");
+    int *len = ctc_lengths(input_lengths, batch, T);
+    if (!len) return -1;
+    int rc = nntk_shim_ctc_loss(d_probs, batch, T, C, len, labels, label_lengths, max_label_len, blank, d_loss_rows, d_dprobs, d_workspace);
+    free(len);
+    return rc;
+}
+
+int nntk_ctc_greedy_decode_device(const float *d_probs, int batch, int T, int C, const int *input_lengths, int blank,
+                                  int *d_labels_out, int *d_out_lengths) {
+    static const char who[] = "nntk_ctc_greedy_decode_device";
+    nntk_shim_clear_error();
+    if (ctc_check_shape(who, batch, T, C, blank) || nntk_check_lengths(who, input_lengths, batch, T, NULL, NULL)) return -1;
+    if (batch == 0) return 0;
+    if (!d_out_lengths || ((!d_probs || !d_labels_out) && T > 0)) NNTK_FAIL("nntk_ctc_greedy_decode_device: NULL tensor");
+    int *len = ctc_lengths(input_lengths, batch, T);
+    if (!len) return -1;
+    int rc = nntk_shim_ctc_greedy_decode(d_probs, batch, T, C, len, blank, d_labels_out, d_out_lengths);
+    free(len);
+    return rc;
+}
+
+/* host-pointer forms: upload, device call, download */
+int nntk_ctc_loss(const float *probs, int batch, int T, int C, const int *input_lengths, const int *labels, const int *label_lengths,
+                  int max_label_len, int blank, float *loss_rows, float *dprobs) {
+    static const char who[] = "nntk_ctc_loss";
+    nntk_shim_clear_error();
+    if (ctc_check_shape(who, batch, T, C, blank) || nntk_check_lengths(who, input_lengths, batch, T, NULL, NULL) ||
+        ctc_check_labels(who, batch, C, labels, label_lengths, max_label_len, blank)) return -1;
+    if (batch == 0) return 0;
+    if (!loss_rows || (!probs && T > 0)) NNTK_FAIL("nntk_ctc_loss: NULL array");
+    const size_t n = (size_t)batch * T * C;
+    float *d_p = nntk_devbuf_reserve(&t_a, n + (size_t)batch + 4);
+    float *d_g = dprobs ? nntk_devbuf_reserve(&t_b, n + 4) : NULL;
+    float *d_ws = nntk_devbuf_reserve(&t_c, nntk_shim_ctc_workspace_floats(batch, dprobs ? T : 0, max_label_len));
+    if (!d_p || (dprobs && !d_g) || !d_ws) return -1;
+    float *d_loss = d_p + n;
+    if (n && nntk_shim_upload(d_p, probs, n * sizeof(float))) return -1;
+    if (nntk_ctc_loss_device(d_p, batch, T, C, input_lengths, labels, label_lengths, max_label_len, blank, d_loss, d_g, d_ws)) return -1;
+    if (nntk_shim_download(loss_rows, d_loss, (size_t)batch * sizeof(float))) return -1;
+    return dprobs && n ? nntk_shim_download(dprobs, d_g, n * sizeof(float)) : 0;
+}
+
+int nntk_ctc_greedy_decode(const float *probs, int batch, int T, int C, const int *input_lengths, int blank, int *labels_out,
+                           int *out_lengths) {
+    static const char who[] = "nntk_ctc_greedy_decode";
+    nntk_shim_clear_error();
+    if (ctc_check_shape(who, batch, T, C, blank) || nntk_check_lengths(who, input_lengths, batch, T, NULL, NULL)) return -1;
+    if (batch == 0) return 0;
+    if (!out_lengths || ((!probs || !labels_out) && T > 0)) NNTK_FAIL("nntk_ctc_greedy_decode: NULL array");
+    const size_t n = (size_t)batch * T * C, nl = (size_t)batch * T;
+    float *d_p = nntk_devbuf_reserve(&t_a, n + 4);
+    int *d_o = (int *)nntk_devbuf_reserve(&t_b, nl + (size_t)batch + 4);
+    if (!d_p || !d_o) return -1;
+    if (n && nntk_shim_upload(d_p, probs, n * sizeof(float))) return -1;
+    if (nntk_ctc_greedy_decode_device(d_p, batch, T, C, input_lengths, blank, d_o, d_o + nl)) return -1;
+    if (nl && nntk_shim_download(labels_out, d_o, nl * sizeof(int))) return -1;
+    return nntk_shim_download(out_lengths, d_o + nl, (size_t)batch * sizeof(int));
 }
 
 /* ---- SGD (train/optimizers.c:13-19) ---- */

@@ -514,6 +514,86 @@ def bidirectional_apply(fwd, bwd, x, lengths=None, merge="concat"):
     return out
 
 
+def _ctc_labels(labels, label_lengths, B):
+    """labels as a list of per-row lists, or a padded int array [B, max_label_len] plus label_lengths -> (int32 [B, maxL], int32 [B])"""
+    if label_lengths is None:
+        rows = [np.asarray(r, dtype=np.int32).reshape(-1) for r in labels]
+        assert len(rows) == B, "labels: one list per row"
+        lens = np.array([r.shape[0] for r in rows], dtype=np.int32)
+        lab = np.zeros((B, max(1, int(lens.max()) if B else 1)), np.int32)
+        for b, r in enumerate(rows):
+            lab[b, :r.shape[0]] = r
+        return lab, lens
+    lab = np.ascontiguousarray(np.asarray(labels, dtype=np.int32)).reshape(B, -1)
+    return lab, _host_ints(label_lengths, B, "label_lengths")
+
+
+def _ctc_lengths(input_lengths, B):
+    if input_lengths is None:
+        return None, None
+    lens = _host_ints(input_lengths, B, "input_lengths")
+    return lens, lens.ctypes.data_as(capi.ip)
+
+
+def ctc_loss_device(probs, labels, label_lengths=None, input_lengths=None, blank=0, want_grad=True, loss=None, dprobs=None, workspace=None):
+    """``nntk_ctc_loss_device``: probs [B,T,C] device tensor of softmax PROBABILITIES; labels: a list of per-row lists, or a padded
+    int array [B, max_label_len] with label_lengths.  Returns (loss rows [B], d loss / d probs [B,T,C] or None)."""
+    import torch
+    B, T, Cc = probs.shape
+    lab, ll = _ctc_labels(labels, label_lengths, B)
+    il, ilp = _ctc_lengths(input_lengths, B)
+    L = capi.load()
+    need = L.nntk_ctc_workspace_floats(B, T if want_grad else 0, lab.shape[1])
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.float32, device=probs.device)
+    assert workspace.numel() >= need, "workspace: nntk_ctc_workspace_floats(B, T, max_label_len) floats"
+    if loss is None:
+        loss = torch.empty(B, dtype=torch.float32, device=probs.device)
+    if want_grad and dprobs is None:
+        dprobs = torch.empty_like(probs)
+    check(L.nntk_ctc_loss_device(_dp(probs), B, T, Cc, ilp, lab.ctypes.data_as(capi.ip), ll.ctypes.data_as(capi.ip), lab.shape[1], blank,
+                                 _dp(loss), _dp(dprobs) if want_grad else None, _dp(workspace)), "nntk_ctc_loss_device")
+    return loss, (dprobs if want_grad else None)
+
+
+def ctc_loss(probs, labels, label_lengths=None, input_lengths=None, blank=0, want_grad=True):
+    """The host-memory form (``nntk_ctc_loss``): probs [B,T,C] numpy array."""
+    probs = _f32(probs)
+    B, T, Cc = probs.shape
+    lab, ll = _ctc_labels(labels, label_lengths, B)
+    il, ilp = _ctc_lengths(input_lengths, B)
+    loss = np.empty(B, np.float32)
+    g = np.empty_like(probs) if want_grad else None
+    check(capi.load().nntk_ctc_loss(_p(probs), B, T, Cc, ilp, lab.ctypes.data_as(capi.ip), ll.ctypes.data_as(capi.ip), lab.shape[1], blank,
+                                    _p(loss), _p(g) if want_grad else None), "nntk_ctc_loss")
+    return loss, g
+
+
+def ctc_greedy_decode_device(probs, input_lengths=None, blank=0, labels_out=None, out_lengths=None):
+    """``nntk_ctc_greedy_decode_device``: best path of probs [B,T,C] -> (labels [B,T] int32, -1 behind each row's labels; lengths [B])"""
+    import torch
+    B, T, Cc = probs.shape
+    il, ilp = _ctc_lengths(input_lengths, B)
+    if labels_out is None:
+        labels_out = torch.empty((B, T), dtype=torch.int32, device=probs.device)
+    if out_lengths is None:
+        out_lengths = torch.empty(B, dtype=torch.int32, device=probs.device)
+    check(capi.load().nntk_ctc_greedy_decode_device(_dp(probs), B, T, Cc, ilp, blank, C.c_void_p(labels_out.data_ptr()),
+                                                    C.c_void_p(out_lengths.data_ptr())), "nntk_ctc_greedy_decode_device")
+    return labels_out, out_lengths
+
+
+def ctc_greedy_decode(probs, input_lengths=None, blank=0):
+    """The host-memory form (``nntk_ctc_greedy_decode``): probs [B,T,C] numpy array."""
+    probs = _f32(probs)
+    B, T, Cc = probs.shape
+    il, ilp = _ctc_lengths(input_lengths, B)
+    out, n = np.empty((B, T), np.int32), np.empty(B, np.int32)
+    check(capi.load().nntk_ctc_greedy_decode(_p(probs), B, T, Cc, ilp, blank, out.ctypes.data_as(capi.ip), n.ctypes.data_as(capi.ip)),
+          "nntk_ctc_greedy_decode")
+    return out, n
+
+
 class LSTM(_Recurrent):
     def __init__(self, in_features, hidden, return_sequences, timesteps, v2=True, acts=None):
         L = capi.load()
