@@ -451,6 +451,19 @@ int LSTMSyncWeights(LSTM filter);
 int RNNSyncWeights(RNN filter);
 int DenseSyncWeights(Dense filter);
 int TimeDistributedDenseSyncWeights(TimeDistributedDense filter);
+/* The weight block from DEVICE memory: d_block holds the <Layer>GetWeights() block, same order and size (Conv1d / Dense /
+ * TimeDistributedDense: W | b; BatchNorm: gamma | beta | moving_mean | moving_variance; GRU / LSTM / RNN: W | U | b_i | b_h).  It is
+ * copied into the handle's host block in stream order, the call waits for that copy and then does what <Layer>SyncWeights does: afterwards
+ * <Layer>GetWeights() shows the new values and every call on the handle -- host and device forms, inference and training -- uses them.
+ * The sibling of <Layer>BroadcastWeights (same host block, filled from RCCL); the step after nntk_optimizer_step_device (below).  The copy
+ * goes through the pinned host block on purpose: it is the library's master copy, from which every layer repacks. */
+int Conv1dLoadWeightsDevice(Conv1d filter, const float *d_block);
+int BatchNormLoadWeightsDevice(BatchNorm filter, const float *d_block);
+int GRULoadWeightsDevice(GRU filter, const float *d_block);
+int LSTMLoadWeightsDevice(LSTM filter, const float *d_block);
+int RNNLoadWeightsDevice(RNN filter, const float *d_block);
+int DenseLoadWeightsDevice(Dense filter, const float *d_block);
+int TimeDistributedDenseLoadWeightsDevice(TimeDistributedDense filter, const float *d_block);
 
 /* ---- multi-GPU: one process per GPU, utterances sharded, NO collective on the data path --------------------
  * (every utterance is independent: BatchNorm uses stored statistics, batch_norm.c:178-181; every sequence owns
@@ -739,6 +752,49 @@ int nntk_categorical_crossentropy_device(const float *d_y, const float *d_pred, 
 int nntk_mean_squared_error_derivative_device(const float *d_y, const float *d_pred, float *d_out, int size, int batch);
 int nntk_categorical_crossentropy_derivative_device(const float *d_y, const float *d_pred, float *d_out, int c, int batch);
 int nntk_sgd_optimize_device(SGD optimizer, const float *d_gradient, float *d_weights, long size);
+
+/* ---- a multi-tensor optimizer over caller-owned device blocks: SGD, momentum SGD, Adam / AdamW; gradient scaling, global-norm clipping,
+ *      a non-finite guard and gradient zeroing in the same step (INTEGRATION.md "Optimizers") ------------------------------------------
+ * One handle owns the list of (weights, gradient) blocks of a model -- any device pointers, 4-byte aligned, e.g. the d_grad blocks that
+ * <Layer>CalculateGradientDevice adds into and device copies of the <Layer>GetWeights() blocks -- plus the moments.  A step is TWO kernel
+ * launches whatever n_blocks is, on the calling thread's current stream, and the host reads nothing back: the norm, the clip factor, the
+ * skip decision and the step count are produced and consumed on the device.
+ * Semantics are PyTorch's (torch.optim.SGD / Adam / AdamW, torch.nn.utils.clip_grad_norm_), so hyper-parameters carry over:
+ *   g = gradient * grad_scale;  norm = L2 norm of g over ALL blocks;  g *= min(1, clip_norm / (norm + 1e-6)) when clip_norm > 0
+ *   weight_decay: g += weight_decay * w, or with `decoupled` w *= 1 - lr * weight_decay first (AdamW)
+ *   kind 0: w -= lr * g        kind 1: buf = momentum * buf + g (buf = g on the first step); w -= lr * (nesterov ? g + momentum * buf : buf)
+ *   kind 2: m += (1 - beta1)(g - m); v = beta2 v + (1 - beta2) g^2; w -= lr / (1 - beta1^t) * m / (sqrt(v) / sqrt(1 - beta2^t) + epsilon)
+ * Non-finite guard: when the norm is not finite (a NaN or inf in any gradient, or a sum of squares past the float range) the step is
+ *   SKIPPED: weights, moments and the step count keep their bits, info[2] reads 1; the gradients are still zeroed with zero_gradients.
+ *   The norm is computed whether or not clip_norm is set.
+ * Deterministic: no atomics; the same inputs give the same bits; a block's result does not depend on the order of the list (the
+ *   per-chunk sums of squares are added exactly, as scaled integers); the summation tree inside a block is fixed by the total size.
+ * nntk_optimizer_create checks its arguments before it allocates or enqueues anything and needs no GPU to refuse them: NULL and
+ *   nntk_last_error() for an unknown kind, n_blocks < 0, a negative size, a NULL or misaligned pointer of a non-empty block, beta1 / beta2
+ *   outside [0, 1), a negative epsilon, clip_norm, weight_decay or momentum.  Empty blocks and n_blocks == 0 are valid (the step touches
+ *   no block).  The pointer / size table is uploaded once, here; the blocks must stay allocated while the handle lives.
+ * nntk_optimizer_info_device: 4 floats on the device, valid after a step in stream order: the norm before clipping | the clip factor
+ *   applied (0 on a skipped step) | 1.0 if the step was skipped | steps taken so far.
+ * nntk_optimizer_state_device: the moments of one block for checkpoints (sizes[block] floats each): kind 1 d_m = the momentum buffer,
+ *   kind 2 d_m / d_v = Adam's first / second moment; NULL where the kind has none or the block is empty.
+ * nntk_optimizer_set_learning_rate takes effect at the next step enqueued after it, in stream order. */
+typedef struct {
+    int   kind;               /* 0 SGD, 1 SGD with momentum, 2 Adam */
+    float learning_rate;
+    float momentum; int nesterov;            /* kind 1 */
+    float beta1, beta2, epsilon;             /* kind 2 */
+    float weight_decay; int decoupled;       /* L2 added to the gradient, or (decoupled) w *= 1 - lr * wd first: AdamW */
+    float grad_scale;         /* every gradient is multiplied by this first (1 / batch); 0 means 1 */
+    float clip_norm;          /* global L2 norm over ALL blocks after grad_scale; 0 = no clipping */
+    int   zero_gradients;     /* the step leaves every gradient block zeroed: replaces the caller's memsets */
+} NntkOptimizerConfig;
+typedef struct NntkOptimizerStruct *NntkOptimizer;
+NntkOptimizer nntk_optimizer_create(NntkOptimizerConfig cfg, int n_blocks, float *const *d_weights, float *const *d_grads, const long *sizes);
+int   nntk_optimizer_step_device(NntkOptimizer opt);
+int   nntk_optimizer_set_learning_rate(NntkOptimizer opt, float lr);
+const float *nntk_optimizer_info_device(NntkOptimizer opt);
+int   nntk_optimizer_state_device(NntkOptimizer opt, int block, float **d_m, float **d_v);
+void  nntk_optimizer_destroy(NntkOptimizer opt);
 
 /* ---- CTC (Graves et al., 2006) on softmax probabilities: loss, gradient, best-path decoding; rows ragged --------
  * The loss of a frame-wise softmax trained on unsegmented label sequences, and the decoder that goes with it (INTEGRATION.md "CTC").

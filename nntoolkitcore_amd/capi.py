@@ -55,6 +55,12 @@ class SGD(C.Structure):
     _fields_ = [("learning_rate", C.c_float)]
 
 
+class NntkOptimizerConfig(C.Structure):
+    _fields_ = [("kind", C.c_int), ("learning_rate", C.c_float), ("momentum", C.c_float), ("nesterov", C.c_int),
+                ("beta1", C.c_float), ("beta2", C.c_float), ("epsilon", C.c_float), ("weight_decay", C.c_float),
+                ("decoupled", C.c_int), ("grad_scale", C.c_float), ("clip_norm", C.c_float), ("zero_gradients", C.c_int)]
+
+
 class DefaultWeights(C.Structure):
     _fields_ = [("W", fp), ("b", fp)]
 
@@ -406,6 +412,20 @@ SIGNATURES = {
     "nntk_ctc_greedy_decode_device": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, ip, C.c_int, vp, vp]),
     "nntk_ctc_loss": (C.c_int, [fp, C.c_int, C.c_int, C.c_int, ip, ip, ip, C.c_int, C.c_int, fp, fp]),
     "nntk_ctc_greedy_decode": (C.c_int, [fp, C.c_int, C.c_int, C.c_int, ip, C.c_int, ip, ip]),
+    # weights from device memory into a handle; the multi-tensor optimizer (INTEGRATION.md "Optimizers")
+    "Conv1dLoadWeightsDevice": (C.c_int, [vp, vp]),
+    "BatchNormLoadWeightsDevice": (C.c_int, [vp, vp]),
+    "GRULoadWeightsDevice": (C.c_int, [vp, vp]),
+    "LSTMLoadWeightsDevice": (C.c_int, [vp, vp]),
+    "RNNLoadWeightsDevice": (C.c_int, [vp, vp]),
+    "DenseLoadWeightsDevice": (C.c_int, [vp, vp]),
+    "TimeDistributedDenseLoadWeightsDevice": (C.c_int, [vp, vp]),
+    "nntk_optimizer_create": (vp, [NntkOptimizerConfig, C.c_int, C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_long)]),
+    "nntk_optimizer_step_device": (C.c_int, [vp]),
+    "nntk_optimizer_set_learning_rate": (C.c_int, [vp, C.c_float]),
+    "nntk_optimizer_info_device": (vp, [vp]),
+    "nntk_optimizer_state_device": (C.c_int, [vp, C.c_int, C.POINTER(vp), C.POINTER(vp)]),
+    "nntk_optimizer_destroy": (None, [vp]),
     "GRUResetState": (C.c_int, [vp]),
     "LSTMResetState": (C.c_int, [vp]),
     "RNNResetState": (C.c_int, [vp]),

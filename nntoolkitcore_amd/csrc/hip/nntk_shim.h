@@ -133,6 +133,25 @@ int nntk_shim_dense_grad(const float *d_x, const float *d_W /*[in,out] caller la
 int nntk_shim_loss_rows(int kind /*0 mse, 1 categorical ce*/, const float *d_y, const float *d_pred, float *d_per_row, int size, int batch);
 int nntk_shim_loss_grad(int kind, const float *d_y, const float *d_pred, float *d_out, int size, int batch);
 int nntk_shim_sgd(float lr, const float *d_grad, float *d_w, long n);
+/* ---- the multi-tensor optimizer step (optim.hip): two launches per step for any number of blocks.  The host (train.c) has checked every
+ *      argument and built the tables; all pointers are device memory.
+ *      d_blocks [n_blocks]: w, g the caller's pointers; m, v the moments (NULL where the kind has none), laid out with the 16-byte phase of
+ *      w (phase = (address of w / 4) & 3, so w - phase, m - phase, v - phase are 16-byte aligned); g_vec = g has that phase too; chunk0 =
+ *      the block's first chunk in the flat chunk list, a block taking ceil((phase + n) / chunk_floats) chunks.
+ *      d_partial [n_chunks]; d_ctl [8] = norm | clip factor | skipped | steps taken | learning rate | steps (uint, read) | steps (uint,
+ *      written) | unused ---- */
+typedef struct { float *w, *g, *m, *v; long n; long chunk0; int phase, g_vec; } nntk_optim_block;
+typedef struct {
+    int kind, nesterov, decoupled, zero_gradients;
+    float momentum, beta1, beta2, epsilon, weight_decay, grad_scale, clip_norm;
+    int n_blocks, chunk_floats;
+    long n_chunks;
+    const nntk_optim_block *d_blocks;
+    float *d_partial, *d_ctl;
+} nntk_optim_plan;
+int nntk_shim_optim_chunk_floats(long total_floats);
+int nntk_shim_optim_step(const nntk_optim_plan *plan);
+int nntk_shim_optim_set_lr(float *d_ctl, float lr);        /* in stream order */
 /* ---- CTC (ctc.hip): loss rows, gradient with respect to the probabilities, best-path decoding.  The int arrays are HOST memory,
  *      already checked by the caller (train.c), never NULL, copied in stream order; d_dprobs NULL = loss only; d_ws 16-byte aligned,
  *      nntk_shim_ctc_workspace_floats words (loss only: the int arrays and 2 words per row at its start are all that is touched) ---- */

@@ -149,6 +149,15 @@ int Conv1dBroadcastWeights(Conv1d filter, int root) {
     return conv_upload(filter);
 }
 
+/* the weight block W | b from device memory: staged through the pinned host block (the master copy every repack reads), then Conv1dSyncWeights */
+int Conv1dLoadWeightsDevice(Conv1d filter, const float *d_block) {
+    nntk_shim_clear_error();
+    if (!filter) NNTK_FAIL("Conv1dLoadWeightsDevice: NULL handle");
+    if (!d_block) NNTK_FAIL("Conv1dLoadWeightsDevice: NULL block");
+    if (nntk_shim_download(filter->wb.host, d_block, filter->wb.n * sizeof(float))) return -1;
+    return conv_upload(filter);
+}
+
 /* T / Tout: rows per input / output sequence (the config's, except for the streaming call's assembled rows).  The route depends on the
  * layer only (flatk_ok, the packed shapes), never on T. */
 static int conv_launch_rows(Conv1d f, const float *d_bn, float eps, int act_kind, float relu_a,
@@ -539,6 +548,14 @@ int BatchNormBroadcastWeights(BatchNorm filter, int root) {
     nntk_shim_clear_error();
     if (!filter) NNTK_FAIL("BatchNormBroadcastWeights: NULL handle");
     if (nntk_shim_dist_broadcast_host(filter->wb.host, filter->wb.n, root)) return -1;
+    return bn_upload(filter);
+}
+
+int BatchNormLoadWeightsDevice(BatchNorm filter, const float *d_block) {
+    nntk_shim_clear_error();
+    if (!filter) NNTK_FAIL("BatchNormLoadWeightsDevice: NULL handle");
+    if (!d_block) NNTK_FAIL("BatchNormLoadWeightsDevice: NULL block");
+    if (nntk_shim_download(filter->wb.host, d_block, filter->wb.n * sizeof(float))) return -1;
     return bn_upload(filter);
 }
 

@@ -104,6 +104,15 @@ int DenseBroadcastWeights(Dense filter, int root) {
     return dense_upload(filter);
 }
 
+/* the weight block from device memory: staged through the pinned host block (the master copy every repack reads), then DenseSyncWeights */
+int DenseLoadWeightsDevice(Dense filter, const float *d_block) {
+    nntk_shim_clear_error();
+    if (!filter) NNTK_FAIL("DenseLoadWeightsDevice: NULL handle");
+    if (!d_block) NNTK_FAIL("DenseLoadWeightsDevice: NULL block");
+    if (nntk_shim_download(filter->wb.host, d_block, filter->wb.n * sizeof(float))) return -1;
+    return dense_upload(filter);
+}
+
 static int dense_rows_device(Dense f, const float *d_in, float *d_out, long rows) {
     if (rows <= 0) return 0;
     if (rows > 0x7fffffffL) NNTK_FAIL("dense: too many rows");
@@ -425,6 +434,12 @@ int TimeDistributedDenseBroadcastWeights(TimeDistributedDense filter, int root) 
     nntk_shim_clear_error();
     if (!filter) NNTK_FAIL("TimeDistributedDenseBroadcastWeights: NULL handle");
     return DenseBroadcastWeights(filter->dense, root);
+}
+
+int TimeDistributedDenseLoadWeightsDevice(TimeDistributedDense filter, const float *d_block) {
+    nntk_shim_clear_error();
+    if (!filter) NNTK_FAIL("TimeDistributedDenseLoadWeightsDevice: NULL handle");
+    return DenseLoadWeightsDevice(filter->dense, d_block);
 }
 
 /* time_distributed_dense.c:52-58 (always returns 0 there; here -1 on device errors) */

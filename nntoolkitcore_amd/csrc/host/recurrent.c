@@ -309,6 +309,12 @@ static int core_sync(rec_core *c) {
     nntk_shim_synchronize();
     return core_upload(c);
 }
+/* the weight block W | U | b_i | b_h from device memory: staged through the pinned host block (the master copy every repack reads) */
+static int core_load_device(rec_core *c, const char *who, const float *d_block) {
+    if (!d_block) return rec_fail(who, "NULL block");
+    if (nntk_shim_download(c->wb.host, d_block, c->wb.n * sizeof(float))) return -1;
+    return core_upload(c);
+}
 
 /* kind + ReLU's output scale (activation_default.c:123-129) of one gate activation */
 static int gate_kind(ActivationFunction a, int *kind, float *scale) {
@@ -1396,6 +1402,10 @@ int GRUBroadcastWeights(GRU filter, int root) {
     REC_ENTER("GRUBroadcastWeights", filter);
     return core_broadcast(&filter->l.core, root);
 }
+int GRULoadWeightsDevice(GRU filter, const float *d_block) {
+    REC_ENTER("GRULoadWeightsDevice", filter);
+    return core_load_device(&filter->l.core, "GRULoadWeightsDevice", d_block);
+}
 int GRUSyncWeights(GRU filter) {
     REC_ENTER("GRUSyncWeights", filter);
     return core_sync(&filter->l.core);
@@ -1611,6 +1621,10 @@ int LSTMBroadcastWeights(LSTM filter, int root) {
     REC_ENTER("LSTMBroadcastWeights", filter);
     return core_broadcast(&filter->l.core, root);
 }
+int LSTMLoadWeightsDevice(LSTM filter, const float *d_block) {
+    REC_ENTER("LSTMLoadWeightsDevice", filter);
+    return core_load_device(&filter->l.core, "LSTMLoadWeightsDevice", d_block);
+}
 int LSTMSyncWeights(LSTM filter) {
     REC_ENTER("LSTMSyncWeights", filter);
     return core_sync(&filter->l.core);
@@ -1814,6 +1828,10 @@ void RNNDestroy(RNN filter) { layer_destroy((rec_layer *)filter); }
 int RNNBroadcastWeights(RNN filter, int root) {
     REC_ENTER("RNNBroadcastWeights", filter);
     return core_broadcast(&filter->l.core, root);
+}
+int RNNLoadWeightsDevice(RNN filter, const float *d_block) {
+    REC_ENTER("RNNLoadWeightsDevice", filter);
+    return core_load_device(&filter->l.core, "RNNLoadWeightsDevice", d_block);
 }
 int RNNSyncWeights(RNN filter) {
     REC_ENTER("RNNSyncWeights", filter);

@@ -277,3 +277,130 @@ int sgd_optimize(SGD optimizer, float *gradient, float *weights, int size) {
     if (nntk_shim_sgd(optimizer.learning_rate, dg, dw, size)) return -1;
     return nntk_shim_download(weights, dw, (size_t)size * sizeof(float));
 }
+
+/* ---- the multi-tensor optimizer (csrc/hip/optim.hip): every argument is checked here, before anything is allocated or enqueued ---- */
+struct NntkOptimizerStruct {
+    nntk_optim_plan plan;
+    nntk_optim_block *blocks;       /* host copy of the table: the moment pointers nntk_optimizer_state_device hands out */
+    nntk_optim_block *d_blocks;
+    float *d_state;                 /* the moments of every block */
+    float *d_scalars;               /* the control block [8], then the partial sums [n_chunks] */
+};
+
+static void *opt_fail(const char *fmt, long a) {
+    char msg[200];
+    int n = snprintf(msg, sizeof msg, "nntk_optimizer_create: ");
+    snprintf(msg + n, sizeof msg - (size_t)n, fmt, a);
+    nntk_set_error(msg);
+    return NULL;
+}
+static void *opt_fail_value(const char *name, double v, const char *rule) {
+    char msg[200];
+    snprintf(msg, sizeof msg, "nntk_optimizer_create: %s = %g %s", name, v, rule);
+    nntk_set_error(msg);
+    return NULL;
+}
+
+NntkOptimizer nntk_optimizer_create(NntkOptimizerConfig cfg, int n_blocks, float *const *d_weights, float *const *d_grads, const long *sizes) {
+    nntk_shim_clear_error();
+    if (cfg.kind < 0 || cfg.kind > 2) return opt_fail("unknown kind %ld (0 SGD, 1 momentum SGD, 2 Adam)", cfg.kind);
+    if (n_blocks < 0) return opt_fail("n_blocks %ld < 0", n_blocks);
+    if (!(cfg.beta1 >= 0.0f && cfg.beta1 < 1.0f)) return opt_fail_value("beta1", cfg.beta1, "is outside [0, 1)");
+    if (!(cfg.beta2 >= 0.0f && cfg.beta2 < 1.0f)) return opt_fail_value("beta2", cfg.beta2, "is outside [0, 1)");
+    if (!(cfg.epsilon >= 0.0f)) return opt_fail_value("epsilon", cfg.epsilon, "is negative");
+    if (!(cfg.clip_norm >= 0.0f)) return opt_fail_value("clip_norm", cfg.clip_norm, "is negative");
+    if (!(cfg.weight_decay >= 0.0f)) return opt_fail_value("weight_decay", cfg.weight_decay, "is negative");
+    if (!(cfg.momentum >= 0.0f)) return opt_fail_value("momentum", cfg.momentum, "is negative");
+    if (n_blocks > 0 && (!d_weights || !d_grads || !sizes)) return opt_fail("NULL pointer table for %ld blocks", n_blocks);
+    long total = 0;
+    for (int b = 0; b < n_blocks; ++b) {
+        if (sizes[b] < 0) return opt_fail("block %ld has a negative size", b);
+        if (sizes[b] == 0) continue;
+        if (!d_weights[b] || !d_grads[b]) return opt_fail("block %ld has a NULL weights or gradient pointer", b);
+        if (((size_t)d_weights[b] | (size_t)d_grads[b]) & 3) return opt_fail("block %ld is not 4-byte aligned", b);
+        if (sizes[b] > (1L << 60) - total) return opt_fail("block %ld: the total size overflows", b);
+        total += sizes[b];
+    }
+
+    NntkOptimizer o = (NntkOptimizer)calloc(1, sizeof *o);
+    nntk_optim_block *blk = (nntk_optim_block *)calloc((size_t)n_blocks + 1, sizeof *blk);
+    if (!o || !blk) { free(o); free(blk); nntk_set_error("nntk_optimizer_create: out of host memory"); return NULL; }
+    o->blocks = blk;
+    nntk_optim_plan *p = &o->plan;
+    p->kind = cfg.kind; p->nesterov = cfg.nesterov != 0; p->decoupled = cfg.decoupled != 0; p->zero_gradients = cfg.zero_gradients != 0;
+    p->momentum = cfg.momentum; p->beta1 = cfg.beta1; p->beta2 = cfg.beta2; p->epsilon = cfg.epsilon;
+    p->weight_decay = cfg.weight_decay; p->grad_scale = cfg.grad_scale == 0.0f ? 1.0f : cfg.grad_scale; p->clip_norm = cfg.clip_norm;
+    p->n_blocks = n_blocks;
+    p->chunk_floats = nntk_shim_optim_chunk_floats(total);
+    /* the chunk list and the layout of the moments: block b's moments start `phase` floats into a 16-byte-aligned region of its own */
+    const int n_mom = cfg.kind == 2 ? 2 : cfg.kind == 1 ? 1 : 0;
+    size_t region = 0;
+    for (int b = 0; b < n_blocks; ++b) {
+        blk[b].n = sizes[b];
+        blk[b].chunk0 = p->n_chunks;
+        if (sizes[b] == 0) continue;
+        blk[b].w = d_weights[b]; blk[b].g = d_grads[b];
+        blk[b].phase = (int)(((size_t)d_weights[b] >> 2) & 3);
+        blk[b].g_vec = (int)(((size_t)d_grads[b] >> 2) & 3) == blk[b].phase;
+        p->n_chunks += (blk[b].phase + sizes[b] + p->chunk_floats - 1) / p->chunk_floats;
+        region += ((size_t)blk[b].phase + (size_t)sizes[b] + 3) & ~(size_t)3;
+    }
+    o->d_blocks = (nntk_optim_block *)nntk_shim_malloc(((size_t)n_blocks + 1) * sizeof *blk);
+    o->d_scalars = (float *)nntk_shim_malloc((8 + (size_t)p->n_chunks) * sizeof(float));
+    if (n_mom) o->d_state = (float *)nntk_shim_malloc((size_t)n_mom * region * sizeof(float));
+    if (!o->d_blocks || !o->d_scalars || (n_mom && !o->d_state)) { nntk_optimizer_destroy(o); return NULL; }
+    size_t off = 0;
+    for (int b = 0; b < n_blocks && n_mom; ++b) {
+        if (sizes[b] == 0) continue;
+        blk[b].m = o->d_state + off + blk[b].phase;
+        if (n_mom == 2) blk[b].v = o->d_state + region + off + blk[b].phase;
+        off += ((size_t)blk[b].phase + (size_t)sizes[b] + 3) & ~(size_t)3;
+    }
+    p->d_blocks = o->d_blocks;
+    p->d_ctl = o->d_scalars;
+    p->d_partial = o->d_scalars + 8;
+    const float ctl[8] = { 0.0f, 1.0f, 0.0f, 0.0f, cfg.learning_rate, 0.0f, 0.0f, 0.0f };       /* (the two step counters: integer zero) */
+    if (nntk_shim_upload(o->d_blocks, blk, ((size_t)n_blocks + 1) * sizeof *blk) || nntk_shim_upload(o->d_scalars, ctl, sizeof ctl) ||
+        (n_mom && nntk_shim_memset(o->d_state, 0, (size_t)n_mom * region * sizeof(float))) || nntk_shim_synchronize()) {
+        nntk_optimizer_destroy(o);
+        return NULL;
+    }
+    return o;
+}
+
+void nntk_optimizer_destroy(NntkOptimizer opt) {
+    if (!opt) return;
+    if (opt->d_blocks || opt->d_scalars || opt->d_state) nntk_shim_synchronize();
+    nntk_shim_free(opt->d_blocks);
+    nntk_shim_free(opt->d_scalars);
+    nntk_shim_free(opt->d_state);
+    free(opt->blocks);
+    free(opt);
+}
+
+int nntk_optimizer_step_device(NntkOptimizer opt) {
+    nntk_shim_clear_error();
+    if (!opt) NNTK_FAIL("nntk_optimizer_step_device: NULL handle");
+    return nntk_shim_optim_step(&opt->plan);
+}
+
+int nntk_optimizer_set_learning_rate(NntkOptimizer opt, float lr) {
+    nntk_shim_clear_error();
+    if (!opt) NNTK_FAIL("nntk_optimizer_set_learning_rate: NULL handle");
+    return nntk_shim_optim_set_lr(opt->plan.d_ctl, lr);
+}
+
+const float *nntk_optimizer_info_device(NntkOptimizer opt) {
+    nntk_shim_clear_error();
+    if (!opt) { nntk_set_error("nntk_optimizer_info_device: NULL handle"); return NULL; }
+    return opt->plan.d_ctl;
+}
+
+int nntk_optimizer_state_device(NntkOptimizer opt, int block, float **d_m, float **d_v) {
+    nntk_shim_clear_error();
+    if (!opt) NNTK_FAIL("nntk_optimizer_state_device: NULL handle");
+    if (block < 0 || block >= opt->plan.n_blocks) NNTK_FAIL("nntk_optimizer_state_device: no such block");
+    if (d_m) *d_m = opt->blocks[block].m;
+    if (d_v) *d_v = opt->blocks[block].v;
+    return 0;
+}

@@ -186,6 +186,10 @@ class Conv1d:
     def sync_weights(self):
         check(capi.load().Conv1dSyncWeights(self.h), "Conv1dSyncWeights")
 
+    def load_weights_device(self, block):
+        """Conv1dLoadWeightsDevice: the GetWeights() block from a device tensor (same order and size), then what sync_weights does"""
+        check(capi.load().Conv1dLoadWeightsDevice(self.h, _dp(block)), "Conv1dLoadWeightsDevice")
+
     def destroy(self):
         if self.h:
             capi.load().Conv1dDestroy(self.h)
@@ -216,6 +220,10 @@ class BatchNorm:
         rows = x.numel() // self.cfg.feature_channels
         check(capi.load().BatchNormApplyDevice(self.h, _dp(x), _dp(out), rows), "BatchNormApplyDevice")
         return out
+
+    def load_weights_device(self, block):
+        """BatchNormLoadWeightsDevice: the GetWeights() block from a device tensor (same order and size), then what sync_weights does"""
+        check(capi.load().BatchNormLoadWeightsDevice(self.h, _dp(block)), "BatchNormLoadWeightsDevice")
 
     def destroy(self):
         if self.h:
@@ -280,6 +288,11 @@ class _Recurrent:
 
     def sync_weights(self):
         check(self._sync(self.h), "SyncWeights")
+
+    def load_weights_device(self, block):
+        """<GRU|LSTM|RNN>LoadWeightsDevice: the block W | U | b_i | b_h from a device tensor, then what sync_weights does"""
+        name = type(self).__name__ + "LoadWeightsDevice"
+        check(getattr(capi.load(), name)(self.h, _dp(block)), name)
 
     def reset_state(self):
         check(self._reset(self.h), "ResetState")
@@ -661,6 +674,10 @@ class TimeDistributedDense:
         check(capi.load().TimeDistributedDenseApplyDeviceVarLen(self.h, _dp(x), _dp(out), B, lp), "TimeDistributedDenseApplyDeviceVarLen")
         return out
 
+    def load_weights_device(self, block):
+        """TimeDistributedDenseLoadWeightsDevice: the GetWeights() block from a device tensor (same order and size), then what sync_weights does"""
+        check(capi.load().TimeDistributedDenseLoadWeightsDevice(self.h, _dp(block)), "TimeDistributedDenseLoadWeightsDevice")
+
     def destroy(self):
         if self.h:
             capi.load().TimeDistributedDenseDestroy(self.h)
@@ -685,9 +702,79 @@ class Dense:
         check(capi.load().DenseApplyInference(self.h, _p(x), _p(o)), "DenseApplyInference")
         return o
 
+    def load_weights_device(self, block):
+        """DenseLoadWeightsDevice: the GetWeights() block from a device tensor (same order and size), then what sync_weights does"""
+        check(capi.load().DenseLoadWeightsDevice(self.h, _dp(block)), "DenseLoadWeightsDevice")
+
     def destroy(self):
         if self.h:
             capi.load().DenseDestroy(self.h)
+            self.h = None
+
+
+_OPTIMIZER_KINDS = {"sgd": 0, "momentum": 1, "adam": 2}
+
+
+class Optimizer:
+    """``nntk_optimizer_*``: one device-side step over a list of (weights, gradient) device tensors -- SGD ("sgd"), momentum SGD
+    ("momentum") or Adam / AdamW ("adam", AdamW with weight_decay and decoupled=True) with PyTorch's semantics, gradient scaling,
+    global-norm clipping, the non-finite guard and gradient zeroing in two launches.  Keyword arguments are the fields of
+    NntkOptimizerConfig (learning_rate, momentum, nesterov, beta1, beta2, epsilon, weight_decay, decoupled, grad_scale, clip_norm,
+    zero_gradients); "adam" defaults to PyTorch's beta1 = 0.9, beta2 = 0.999, epsilon = 1e-8.  The tensors are kept alive by the object."""
+
+    def __init__(self, kind, blocks, **cfg):
+        k = _OPTIMIZER_KINDS.get(kind, kind) if isinstance(kind, str) else int(kind)
+        if isinstance(k, str):
+            raise ValueError("Optimizer: kind must be one of %s" % sorted(_OPTIMIZER_KINDS))
+        if k == 2:
+            cfg = dict({"beta1": 0.9, "beta2": 0.999, "epsilon": 1e-8}, **cfg)
+        c = capi.NntkOptimizerConfig(kind=k)
+        names = {f for f, _ in capi.NntkOptimizerConfig._fields_} - {"kind"}
+        for key, value in cfg.items():
+            if key not in names:
+                raise TypeError("Optimizer: unknown option %r" % key)
+            setattr(c, key, value)
+        self.blocks = [(w, g) for w, g in blocks]
+        for w, g in self.blocks:
+            assert w.numel() == g.numel(), "Optimizer: a gradient has the size of its weights"
+            if w.numel():
+                _dp(w), _dp(g)
+        n = len(self.blocks)
+        wp = (C.c_void_p * max(n, 1))(*[w.data_ptr() if w.numel() else None for w, _ in self.blocks])
+        gp = (C.c_void_p * max(n, 1))(*[g.data_ptr() if g.numel() else None for _, g in self.blocks])
+        sz = (C.c_long * max(n, 1))(*[w.numel() for w, _ in self.blocks])
+        self.cfg, self.kind = c, k
+        self.h = capi.load().nntk_optimizer_create(c, n, wp, gp, sz)
+        if not self.h:
+            raise capi.NNTKError("nntk_optimizer_create: " + capi.last_error())
+
+    def step(self):
+        """nntk_optimizer_step_device on the current stream: asynchronous, nothing is read back"""
+        check(capi.load().nntk_optimizer_step_device(self.h), "nntk_optimizer_step_device")
+
+    def set_learning_rate(self, lr):
+        check(capi.load().nntk_optimizer_set_learning_rate(self.h, C.c_float(lr)), "nntk_optimizer_set_learning_rate")
+
+    def _download(self, ptr, n):
+        out = np.empty(n, np.float32)
+        if n:
+            check(capi.load().nntk_device_download(_p(out), C.c_void_p(ptr), n), "nntk_device_download")
+        return out
+
+    def info(self):
+        """a host copy (this waits for the stream) of [norm before clipping, clip factor applied, 1.0 if the step was skipped, steps taken]"""
+        return self._download(capi.load().nntk_optimizer_info_device(self.h), 4)
+
+    def state(self, block):
+        """host copies (m, v) of one block's moments, None where the kind has none: for checkpoints"""
+        m, v = C.c_void_p(), C.c_void_p()
+        check(capi.load().nntk_optimizer_state_device(self.h, block, C.byref(m), C.byref(v)), "nntk_optimizer_state_device")
+        n = self.blocks[block][0].numel()
+        return tuple(self._download(q.value, n).reshape(tuple(self.blocks[block][0].shape)) if q.value else None for q in (m, v))
+
+    def destroy(self):
+        if self.h:
+            capi.load().nntk_optimizer_destroy(self.h)
             self.h = None
 
 
