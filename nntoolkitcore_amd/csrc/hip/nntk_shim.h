@@ -162,24 +162,8 @@ int nntk_shim_ctc_greedy_decode(const float *d_probs, int B, int T, int C, const
                                 int *d_out_lengths);
 /* BatchNorm training (batch_norm.c:191-386): x, d_out [N, F]; d_block = gamma | beta | ...; d_stats [8][F] = mean | variance |
  * var_eps | sqrt_var | d_beta | d_gamma | d_var | d_mu; d_partial [slices][3][F] with slices from nntk_shim_bn_train_slices */
-/* GRU training (gru.c:246-512): caller-layout weights W [in][3H], U [H][3H]; caches h [B][T][H], Zg [B][T][6H], hU [B][T][H];
- * acts / scales in the order z, h, r */
-int nntk_shim_gru_train_forward(const float *d_x, const float *d_W, const float *d_U, const float *d_bi, const float *d_bh,
-                                float *d_h, float *d_Zg, float *d_hU, int B, int T, int in, int H, const int *acts, const float *scales);
-int nntk_shim_gru_train_backward(const float *d_dout, const float *d_UT /*U transposed [3H][H]*/, const float *d_h, const float *d_Zg, const float *d_hU,
-                                 float *d_dxW, float *d_dhU, float *d_work /*5*B*H*/, int B, int T, int H, int return_sequences, const int *acts);
-/* LSTM training (lstm.c:185-239, :294-556): W [in][4H], U [H][4H]; caches h, c [B][T][H], zifgo [B][T][8H]; acts i,f,g,o,out */
-int nntk_shim_lstm_train_forward(const float *d_x, const float *d_W, const float *d_U, const float *d_bi, const float *d_bh,
-                                 float *d_h, float *d_c, float *d_zifgo, int B, int T, int in, int H, int v2, const int *acts, const float *scales);
-int nntk_shim_lstm_train_backward(const float *d_dout, const float *d_UT /*U transposed [4H][H]*/, const float *d_c, const float *d_zifgo, float *d_dG,
-                                  float *d_work /*6*B*H*/, int B, int T, int H, int return_sequences, const int *acts, const float *scales);
-/* RNN training (rnn.c:144-221, :249-351): W [in][H], U [H][H]; caches h, gate [B][T][H] */
-int nntk_shim_rnn_train_forward(const float *d_x, const float *d_W, const float *d_U, const float *d_bi, const float *d_bh,
-                                float *d_h, float *d_gate, int B, int T, int in, int H, int v2, int act, float scale);
-int nntk_shim_rnn_train_backward(const float *d_dout, const float *d_UT /*U transposed [H][H]*/, const float *d_h, const float *d_gate, float *d_dG,
-                                 float *d_work /*2*B*H*/, int B, int T, int H, int return_sequences, int act);
-/* Ragged batches and carried state for the training kernels above (the *VarLen training calls; a NULL pointer to it = the fixed-length,
- * zero-state pass on the same kernels).  All pointers are device memory and may be NULL. */
+/* Ragged batches and carried state for the recurrent training launchers below (the *VarLen training calls; a NULL pointer to it = the
+ * fixed-length, zero-state pass on the same kernels).  All pointers are device memory and may be NULL. */
 typedef struct {
     const int *d_len;            /* [B] row lengths in [0, T], then the 64-row tiles' maxima (nntk_shim_rr_varlen's layout); NULL: every row T */
     int max_len;                 /* the longest row (read only with d_len) */
@@ -187,22 +171,19 @@ typedef struct {
     const float *d_dhT, *d_dcT;  /* [B][H] gradient arriving at the final state (zeros) */
     float *d_dh0, *d_dc0;        /* [B][H] gradient with respect to the initial state (not computed) */
 } nntk_train_vl;
-int nntk_shim_gru_train_forward_vl(const float *d_x, const float *d_W, const float *d_U, const float *d_bi, const float *d_bh,
-                                   float *d_h, float *d_Zg, float *d_hU, int B, int T, int in, int H, const int *acts, const float *scales,
-                                   const nntk_train_vl *vl);
-int nntk_shim_gru_train_backward_vl(const float *d_dout, const float *d_UT, const float *d_h, const float *d_Zg, const float *d_hU,
-                                    float *d_dxW, float *d_dhU, float *d_work /*5*B*H*/, int B, int T, int H, int return_sequences, const int *acts,
-                                    const nntk_train_vl *vl);
-int nntk_shim_lstm_train_forward_vl(const float *d_x, const float *d_W, const float *d_U, const float *d_bi, const float *d_bh,
-                                    float *d_h, float *d_c, float *d_zifgo, int B, int T, int in, int H, int v2, const int *acts, const float *scales,
-                                    const nntk_train_vl *vl);
-int nntk_shim_lstm_train_backward_vl(const float *d_dout, const float *d_UT, const float *d_c, const float *d_zifgo, float *d_dG,
-                                     float *d_work /*6*B*H*/, int B, int T, int H, int return_sequences, const int *acts, const float *scales,
-                                     const nntk_train_vl *vl);
-int nntk_shim_rnn_train_forward_vl(const float *d_x, const float *d_W, const float *d_U, const float *d_bi, const float *d_bh,
-                                   float *d_h, float *d_gate, int B, int T, int in, int H, int v2, int act, float scale, const nntk_train_vl *vl);
-int nntk_shim_rnn_train_backward_vl(const float *d_dout, const float *d_UT, const float *d_h, const float *d_gate, float *d_dG,
-                                    float *d_work /*2*B*H*/, int B, int T, int H, int return_sequences, int act, const nntk_train_vl *vl);
+/* Recurrent training, one pair of calls for the three cells: G = gates per hidden unit, 1 RNN (rnn.c:144-221, :249-351), 3 GRU
+ * (gru.c:246-512), 4 LSTM (lstm.c:185-239, :294-556).  Caller-layout weights W [in][G H], U [H][G H]; acts / scales in the order z, h, r
+ * (GRU) | i, f, g, o, out (LSTM) | the one (RNN); the GRU always adds b_h, the others with use_bh.  Caches per (b, t): d_h [H];
+ * d_Zg: GRU Z_gates [6H], LSTM zifgo [8H], RNN the pre-activation [H]; d_c [H]: GRU h_prev U_h + b_hh, LSTM the cell state, RNN unused.
+ * backward: d_UT = U transposed [G H][H]; d_dG [B][T][G H] the recurrent side's gate gradients, d_dxW the input side's (the GRU's differ,
+ * the other cells pass one buffer twice); d_work: nntk_shim_rec_train_work_floats. */
+int nntk_shim_rec_train_forward(int G, const float *d_x, const float *d_W, const float *d_U, const float *d_bi, const float *d_bh,
+                                float *d_h, float *d_Zg, float *d_c, int B, int T, int in, int H, int use_bh,
+                                const int *acts, const float *scales, const nntk_train_vl *vl);
+size_t nntk_shim_rec_train_work_floats(int G, int B, int H);
+int nntk_shim_rec_train_backward(int G, const float *d_dout, const float *d_UT, const float *d_h, const float *d_Zg, const float *d_c,
+                                 float *d_dxW, float *d_dG, float *d_work, int B, int T, int H, int return_sequences,
+                                 const int *acts, const float *scales, const nntk_train_vl *vl);
 /* the same forward pass on the register-resident kernels (recurrent_rr.hip, TRAIN + VL): one launch, h0 / c0 in, hT / cT out (may be NULL),
  * the caches of every step a row runs; d_h rows past a row's length are unspecified until nntk_shim_varlen_zero_pad clears them.  cell 0
  * LSTM, 1 GRU (d_bi = the four-slot bias, d_bh NULL, d_c = the h.U_h + b_h cache).  0 launched, 1 shape / configuration not taken, -1 error */

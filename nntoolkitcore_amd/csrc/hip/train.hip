@@ -349,13 +349,15 @@ extern "C" int nntk_shim_bn_train_backward(const float *d_x, const float *d_dout
     return 0;
 }
 
-// ---- GRU training (layers/gru.c:246-512) ------------------------------------------------------------------------
+// ---- recurrent training, per-timestep kernels (GRU: layers/gru.c:246-512; LSTM: lstm.c:185-239, :294-556; RNN: rnn.c:144-221, :249-351) ----
 // Correct, deterministic, reference operation order; NOT tuned (one launch per timestep and direction, VALU dots).
-// Forward step t for the whole mini-batch: thread (b, j) computes GRUCellForward's three columns j, H + j, 2H + j
-// (gru.c:128-187; op_mat_mul as sums of separately rounded products, in eight k-ordered chunks -- cell_dots_chunked) and stores what the backward pass
-// reads: Z_gates [B][T][6H] = Z_z | Z_r | Z_h~ | z | r | h~, h_pr_Uh [B][T][H] (= h_prev U_h + b_hh), h [B][T][H].
+// One cell-agnostic core, G = gates per hidden unit: 1 RNN, 3 GRU, 4 LSTM.  The caches the forward keeps for the backward pass, all per (b, t):
+//   h [H] the output;  Zg: GRU Z_gates [6H] = Z_z | Z_r | Z_h~ | z | r | h~, LSTM zifgo [8H] = Z_i | Z_f | Z_g | Z_o | i | f | g | o, RNN the
+//   pre-activation [H];  c [H]: GRU h_pr_Uh (= h_prev U_h + b_hh), LSTM the cell state (the RNN has none).
+// Activations / ReLU scales in the order z, h, r (GRU) | i, f, g, o, out (LSTM) | the one (RNN).
 // The per-timestep forward dots, cut the same way as rows_times_colmat_kernel below: a workgroup is one batch row x 32
-// hidden units x 8 K-chunks of the concatenated [x_t | h_{t-1}] walk; chunk sums are added in chunk order through LDS.
+// hidden units x 8 K-chunks of the concatenated [x_t | h_{t-1}] walk; chunk sums are added in chunk order through LDS
+// (op_mat_mul as sums of separately rounded products, in eight k-ordered chunks).
 // Returns (in the threads with chunk index 0) xw[g] = x_t . W[:, g H + j] and hu[g] = h_{t-1} . U[:, g H + j].
 #define CELL_CHUNKS 8
 template <int G>
@@ -396,92 +398,189 @@ __device__ __forceinline__ bool cell_dots_chunked(const float *__restrict__ x, c
     }
     return true;
 }
+// What step t of row b starts from: the cache row of step t - 1, at t = 0 the state the caller carries in, or nothing -- every sequence
+// starts from zeros (gru.c:262, lstm.c:441).  prev_state is 0 exactly where has_prev_state says there is none.
+__device__ __forceinline__ bool has_prev_state(int t, const float *s0) { return t > 0 || s0; }
+__device__ __forceinline__ float prev_state(const float *seq, const float *s0, int t, size_t row, int b, int H, int j) {
+    return t > 0 ? seq[(row - 1) * H + j] : s0 ? s0[(size_t)b * H + j] : 0.0f;
+}
 
-struct GruTrainParams {
+struct RecFwdParams {
     const float *x;              // [B][T][in]
-    const float *W, *U, *bi, *bh;    // caller layouts: W [in][3H], U [H][3H]
-    float *h, *Zg, *hU;          // caches
+    const float *W, *U, *bi, *bh;    // caller layouts: W [in][G H], U [H][G H]; bh NULL: no recurrent bias (LSTM / RNN without use_bh)
+    float *h, *Zg, *c;           // caches [B][T][...]
     int B, T, in, H, t;
-    int act_z, act_h, act_r;
-    float sc_z, sc_h, sc_r;      // ReLU output scales
+    int act[5];
+    float sc[5];                 // ReLU output scales
     const int *len;              // ragged batches: row b runs steps 0 .. len[b] - 1 (NULL: every row T)
-    const float *h0;             // [B][H] initial state or NULL (zeros)
+    const float *h0, *c0;        // [B][H] initial state or NULL (zeros)
 };
-__global__ __launch_bounds__(256) void gru_train_fwd_step_kernel(GruTrainParams p) {
+// Forward step t for the whole mini-batch: thread (b, j) computes the cell's G columns j, H + j, ... (GRUCellForward gru.c:128-187,
+// lstm.c:185-239, rnn.c:144-166) and stores what the backward pass reads.
+template <int G>
+__global__ __launch_bounds__(256) void rec_train_fwd_step_kernel(RecFwdParams p) {
     const int b = blockIdx.y, j = blockIdx.x * 32 + (threadIdx.x & 31), H = p.H;
     const size_t row = (size_t)b * p.T + p.t;
     if (p.len && p.t >= p.len[b]) return;                           // past the row's end (uniform: a workgroup is one row); its h row was cleared by the host
-    const float *hp = p.t > 0 ? p.h + (row - 1) * H : p.h0 ? p.h0 + (size_t)b * H : nullptr;      // h_0 = 0 for every sequence (gru.c:262) unless the caller carries one in
-    float xw[3], hu[3];
-    if (!cell_dots_chunked<3>(p.x + row * p.in, hp, p.W, p.U, p.in, H, j, xw, hu)) return;
+    const float *hp = !has_prev_state(p.t, p.h0) ? nullptr : p.t > 0 ? p.h + (row - 1) * H : p.h0 + (size_t)b * H;
+    float xw[G], hu[G];
+    if (!cell_dots_chunked<G>(p.x + row * p.in, hp, p.W, p.U, p.in, H, j, xw, hu)) return;
 #pragma unroll
-    for (int g = 0; g < 3; ++g) { xw[g] = add_rn(xw[g], p.bi[g * H + j]); hu[g] = add_rn(hu[g], p.bh[g * H + j]); }
-    const float Zz = add_rn(xw[0], hu[0]), Zr = add_rn(xw[1], hu[1]);
-    const float z = nntk_gate_act(p.act_z, Zz, p.sc_z), r = nntk_gate_act(p.act_r, Zr, p.sc_r);
-    const float Zh = add_rn(mul_rn(r, hu[2]), xw[2]);
-    const float ht = nntk_gate_act(p.act_h, Zh, p.sc_h);
-    const float hprev = hp ? hp[j] : 0.0f;
-    const float hn = add_rn(mul_rn(add_rn(-z, 1.0f), ht), mul_rn(z, hprev));
-    float *Zg = p.Zg + row * 6 * H;
-    Zg[j] = Zz; Zg[H + j] = Zr; Zg[2 * H + j] = Zh; Zg[3 * H + j] = z; Zg[4 * H + j] = r; Zg[5 * H + j] = ht;
-    p.hU[row * H + j] = hu[2];
-    p.h[row * H + j] = hn;
+    for (int g = 0; g < G; ++g) {
+        xw[g] = add_rn(xw[g], p.bi[g * H + j]);
+        if (p.bh) hu[g] = add_rn(hu[g], p.bh[g * H + j]);
+    }
+    if constexpr (G == 3) {
+        const float Zz = add_rn(xw[0], hu[0]), Zr = add_rn(xw[1], hu[1]);
+        const float z = nntk_gate_act(p.act[0], Zz, p.sc[0]), r = nntk_gate_act(p.act[2], Zr, p.sc[2]);
+        const float Zh = add_rn(mul_rn(r, hu[2]), xw[2]);
+        const float ht = nntk_gate_act(p.act[1], Zh, p.sc[1]);
+        const float hprev = hp ? hp[j] : 0.0f;
+        float *Zg = p.Zg + row * 6 * H;
+        Zg[j] = Zz; Zg[H + j] = Zr; Zg[2 * H + j] = Zh; Zg[3 * H + j] = z; Zg[4 * H + j] = r; Zg[5 * H + j] = ht;
+        p.c[row * H + j] = hu[2];
+        p.h[row * H + j] = add_rn(mul_rn(add_rn(-z, 1.0f), ht), mul_rn(z, hprev));
+    } else if constexpr (G == 4) {
+        float Z[4], a[4];
+#pragma unroll
+        for (int g = 0; g < 4; ++g) { Z[g] = add_rn(xw[g], hu[g]); a[g] = nntk_gate_act(p.act[g], Z[g], p.sc[g]); }
+        const float c = add_rn(mul_rn(a[1], prev_state(p.c, p.c0, p.t, row, b, H, j)), mul_rn(a[0], a[2]));         // f c_prev + i g
+        float *zg = p.Zg + row * 8 * H;
+#pragma unroll
+        for (int g = 0; g < 4; ++g) { zg[g * H + j] = Z[g]; zg[(4 + g) * H + j] = a[g]; }
+        p.c[row * H + j] = c;
+        p.h[row * H + j] = mul_rn(a[3], nntk_gate_act(p.act[4], c, p.sc[4]));
+    } else {
+        const float g = add_rn(hu[0], xw[0]);
+        p.Zg[row * H + j] = g;
+        p.h[row * H + j] = nntk_gate_act(p.act[0], g, p.sc[0]);
+    }
 }
 
+// ---- the backward cell, one (b, j) element at one step: shared by the per-step kernel and bptt_persistent_kernel ----
 __device__ __forceinline__ float gate_grad(int kind, float Z, float a, float d) {     // activation_default.c derivatives
     if (kind == NNTK_ACT_SIGMOID) return mul_rn(mul_rn(a, add_rn(-a, 1.0f)), d);
     if (kind == NNTK_ACT_TANH) return mul_rn(add_rn(-mul_rn(a, a), 1.0f), d);
     if (kind == NNTK_ACT_RELU) return mul_rn(fmaxf(fminf(Z, 1.0f), 0.0f), d);
     return d;
 }
-// Backward step t, elementwise part of GRUCellBackward (gru.c:314-430) for thread (b, j):
-//   d_h = (carry or 0) + d_out_t;  d_h_prev_1 = z d_h;  d_h~ = (-z) d_h + d_h;  d_z = (h_prev - h~) d_h;
+// Ragged batches: a row is idle until its own last step t = L - 1 (`last`), the first of its backward pass.  The output gradient of a
+// layer without sequences arrives there; so does, in place of the carry from step t + 1, the gradient at the final state (dhT, NULL: zeros).
+__device__ __forceinline__ float step_dout(const float *dout, int return_sequences, bool last, size_t row, int b, int H, int j) {
+    return return_sequences ? dout[row * H + j] : last ? dout[(size_t)b * H + j] : 0.0f;
+}
+__device__ __forceinline__ float step_dh(bool last, const float *dhT, size_t e, float carry, float dout) {
+    return add_rn(last ? (dhT ? dhT[e] : 0.0f) : carry, dout);
+}
+// GRUCellBackward (gru.c:314-430), elementwise part.  z: the six cached values of Zg; hU: h_pr_Uh; act: z, h, r.
+//   d_h_prev_1 = z d_h;  d_h~ = (-z) d_h + d_h;  d_z = (h_prev - h~) d_h;
 //   d_Zh = act_h'(.) d_h~;  d_r = h_pr_Uh d_Zh;  d_Zz = act_z'(.) d_z;  d_Zr = act_r'(.) d_r
-// writes d_xW [B][T][3H] = d_Zz | d_Zr | d_Zh, d_hU [B][T][3H] = d_Zz | d_Zr | r d_Zh, its copy for this step
-// d_hU_step [B][3H], and d_h_prev_1 [B][H].  carry = d_h_prev_1 + d_h_prev_2 of step t + 1 (gru.c:426).
-struct GruBwdParams {
+// d_xW = d_Zz | d_Zr | d_Zh, d_hU = d_Zz | d_Zr | r d_Zh (dhUh); the next carry is d_h_prev_1 + d_h_prev_2 (= U d_hU) of this step (gru.c:426).
+struct GruCellGrad { float dZz, dZr, dZh, dhUh, dhp1; };
+__device__ __forceinline__ GruCellGrad gru_cell_bwd(const float *z, float hU, float hprev, bool has_prev, float dh, const int *act) {
+    const float zt = z[3], r = z[4], ht = z[5];
+    GruCellGrad g;
+    g.dhp1 = mul_rn(zt, dh);
+    const float dht = add_rn(mul_rn(-zt, dh), dh);
+    const float dz = mul_rn(has_prev ? sub_rn(hprev, ht) : -ht, dh);
+    g.dZh = gate_grad(act[1], z[2], ht, dht);
+    const float dr = mul_rn(hU, g.dZh);
+    g.dZz = gate_grad(act[0], z[0], zt, dz);
+    g.dZr = gate_grad(act[2], z[1], r, dr);
+    g.dhUh = mul_rn(r, g.dZh);
+    return g;
+}
+// LSTMCellBackward (lstm.c:294-416), elementwise part.  z: the eight cached values of zifgo; ct, cprev: c_t, c_{t-1}; act: i, f, g, o, out.
+// d_c takes the carry of step t + 1, or at the row's last step the gradient at the final cell state (dcT, NULL: nothing is added);
+// dc_out is the carry handed to step t - 1.
+struct LstmCellGrad { float d_i, d_f, d_g, d_o, dc_out; };
+__device__ __forceinline__ LstmCellGrad lstm_cell_bwd(const float *z, float ct, float cprev, bool has_prev, float dh, bool last, float dc_carry,
+                                                      const float *dcT, size_t e, const int *act, float sc_out) {
+    const float it = z[4], ft = z[5], gt = z[6], ot = z[7];
+    const float tc = nntk_gate_act(act[4], ct, sc_out);
+    LstmCellGrad g;
+    g.d_o = gate_grad(act[3], z[3], ot, mul_rn(dh, tc));
+    // non-cached derivative of the output activation at c_t (activation.c:49-50): forward value recomputed, UNscaled
+    float dc = gate_grad(act[4], ct, nntk_gate_act(act[4], ct, 1.0f), mul_rn(dh, ot));
+    if (!last) dc = add_rn(dc, dc_carry);
+    else if (dcT) dc = add_rn(dc, dcT[e]);
+    g.d_i = gate_grad(act[0], z[0], it, mul_rn(dc, gt));
+    g.d_f = has_prev ? gate_grad(act[1], z[1], ft, mul_rn(cprev, dc)) : 0.0f;
+    g.d_g = gate_grad(act[2], z[2], gt, mul_rn(dc, it));
+    g.dc_out = mul_rn(dc, ft);
+    return g;
+}
+// the RNN's backward cell (rnn.c:184-221): d_gate = act'(.) d_h
+__device__ __forceinline__ float rnn_cell_bwd(float gate, float h, float dh, int act) { return gate_grad(act, gate, h, dh); }
+
+// Both backward routes read this: the per-step kernel below (fields marked S) and bptt_persistent_kernel (fields marked P).
+struct RecBwdParams {
     const float *dout;           // [B][T][H] or [B][H]
-    const float *h, *Zg, *hU;    // forward caches
-    const float *dhp1, *dhp2;    // [B][H] of step t + 1
-    float *dxW, *dhU, *dhU_step, *dhp1_out;
-    int B, T, H, t, return_sequences;
-    int act_z, act_h, act_r;
-    const int *len;              // ragged batches (NULL: every row T): a row is idle until its own last step
-    const float *h0, *dhT;       // [B][H] initial state / gradient arriving at the final state, or NULL (zeros)
+    const float *h, *Zg, *c;     // forward caches
+    float *dG;                   // gate gradients of the recurrent side [B][T][G H]: GRU d_hU, LSTM / RNN dgates (P: output and exchange)
+    float *dxW;                  // GRU only [B][T][3H]
+    int B, T, H, return_sequences;
+    int act[5];
+    float sc_out;                // LSTM: scale of the output activation
+    // ragged batches and carried state (all NULL: the fixed-length, zero-state pass)
+    const int *len;              // [B] row lengths
+    const float *s0;             // [B][H] initial state the step-0 terms read: GRU h0, LSTM c0
+    const float *dhT, *dcT;      // [B][H] gradient arriving at the final state (dcT: LSTM)
+    // S
+    int t;
+    const float *prod;           // [B][H] d_h_prev of step t + 1 = its gate gradients times U^T
+    float *own;                  // [B][H] the cell's elementwise carry, read and rewritten: GRU d_h_prev_1, LSTM d_c (RNN: none)
+    float *step;                 // [B][G H] this step's dG rows, contiguous for the product
+    // P
+    const float *UT;             // [K][H]
+    unsigned *count;             // [ceil(B / 16)][32] arrival flags (steps handed off per column tile), zeroed by the host
+    unsigned *fault;
+    unsigned long long spin_ticks;
+    float *carry_out;            // [B][H] the register carry after step 0: GRU d_h_prev_1, LSTM d_c0
 };
-__global__ __launch_bounds__(256) void gru_train_bwd_step_kernel(GruBwdParams p) {
+// Backward step t, elementwise, thread (b, j): loads the caches, runs the cell, stores dG (dxW) and this step's copy; the caller then
+// forms d_h_prev = step U^T (launch_rows_times_colmat).  An idle row hands back zeros (its dG / dxW rows were cleared by the host).
+template <int G>
+__global__ __launch_bounds__(256) void rec_train_bwd_step_kernel(RecBwdParams p) {
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= p.B * p.H) return;
-    const int b = e / p.H, j = e % p.H, H = p.H;
-    const size_t row = (size_t)b * p.T + p.t;
+    const int b = e / p.H, j = e % p.H, H = p.H, t = p.t;
+    const size_t row = (size_t)b * p.T + t;
     const int L = p.len ? p.len[b] : p.T;
-    if (p.t >= L) {              // idle: nothing flows back through this step (d_xW / d_hU rows were cleared by the host)
-        float *ds = p.dhU_step + (size_t)b * 3 * H;
-        ds[j] = 0.0f; ds[H + j] = 0.0f; ds[2 * H + j] = 0.0f;
-        p.dhp1_out[e] = 0.0f;
+    float *dG = p.dG + row * G * H, *ds = p.step + (size_t)b * G * H;
+    if (t >= L) {
+#pragma unroll
+        for (int g = 0; g < G; ++g) ds[g * H + j] = 0.0f;
+        if (G != 1) p.own[e] = 0.0f;
         return;
     }
-    const bool first = p.t == L - 1;      // the row's last step: the first one of its backward pass
-    float dout = 0.0f;
-    if (p.return_sequences) dout = p.dout[row * H + j];
-    else if (first) dout = p.dout[(size_t)b * H + j];
-    const float carry = first ? (p.dhT ? p.dhT[e] : 0.0f) : add_rn(p.dhp1[e], p.dhp2[e]);
-    const float dh = add_rn(carry, dout);
-    const float *Zg = p.Zg + row * 6 * H;
-    const float z = Zg[3 * H + j], r = Zg[4 * H + j], ht = Zg[5 * H + j];
-    const float dhp1 = mul_rn(z, dh);
-    const float dht = add_rn(mul_rn(-z, dh), dh);
-    const float dz = mul_rn(p.t > 0 ? sub_rn(p.h[(row - 1) * H + j], ht) : p.h0 ? sub_rn(p.h0[e], ht) : -ht, dh);
-    const float dZh = gate_grad(p.act_h, Zg[2 * H + j], ht, dht);
-    const float dr = mul_rn(p.hU[row * H + j], dZh);
-    const float dZz = gate_grad(p.act_z, Zg[j], z, dz);
-    const float dZr = gate_grad(p.act_r, Zg[H + j], r, dr);
-    const float dhUh = mul_rn(r, dZh);
-    float *dxW = p.dxW + row * 3 * H, *dhU = p.dhU + row * 3 * H, *ds = p.dhU_step + (size_t)b * 3 * H;
-    dxW[j] = dZz; dxW[H + j] = dZr; dxW[2 * H + j] = dZh;
-    dhU[j] = dZz; dhU[H + j] = dZr; dhU[2 * H + j] = dhUh;
-    ds[j] = dZz; ds[H + j] = dZr; ds[2 * H + j] = dhUh;
-    p.dhp1_out[e] = dhp1;
+    const bool last = t == L - 1;
+    const float dout = step_dout(p.dout, p.return_sequences, last, row, b, H, j);
+    float z[2 * G];
+    if constexpr (G != 1) {
+#pragma unroll
+        for (int g = 0; g < 2 * G; ++g) z[g] = p.Zg[(row * 2 * G + g) * H + j];
+    }
+    if constexpr (G == 3) {
+        const float dh = step_dh(last, p.dhT, e, add_rn(p.own[e], p.prod[e]), dout);
+        const GruCellGrad g = gru_cell_bwd(z, p.c[row * H + j], prev_state(p.h, p.s0, t, row, b, H, j), has_prev_state(t, p.s0), dh, p.act);
+        float *dxW = p.dxW + row * 3 * H;
+        dxW[j] = g.dZz; dxW[H + j] = g.dZr; dxW[2 * H + j] = g.dZh;
+        dG[j] = g.dZz; dG[H + j] = g.dZr; dG[2 * H + j] = g.dhUh;
+        ds[j] = g.dZz; ds[H + j] = g.dZr; ds[2 * H + j] = g.dhUh;
+        p.own[e] = g.dhp1;
+    } else if constexpr (G == 4) {
+        const float dh = step_dh(last, p.dhT, e, p.prod[e], dout);
+        const LstmCellGrad g = lstm_cell_bwd(z, p.c[row * H + j], prev_state(p.c, p.s0, t, row, b, H, j), has_prev_state(t, p.s0), dh, last,
+                                             p.own[e], p.dcT, e, p.act, p.sc_out);
+        dG[j] = g.d_i; dG[H + j] = g.d_f; dG[2 * H + j] = g.d_g; dG[3 * H + j] = g.d_o;
+        ds[j] = g.d_i; ds[H + j] = g.d_f; ds[2 * H + j] = g.d_g; ds[3 * H + j] = g.d_o;
+        p.own[e] = g.dc_out;
+    } else {
+        const float dg = rnn_cell_bwd(p.Zg[row * H + j], p.h[row * H + j], step_dh(last, p.dhT, e, p.prod[e], dout), p.act[0]);
+        dG[j] = dg;
+        ds[j] = dg;
+    }
 }
 // out[row][i] = sum_k M[i][k] * d[row][k] in k order (op_mat_mul(M, d, ., I, 1, K)): d_h_prev_2 = U d_hU per step, and
 // d_X = W d_xW for all rows at the end
@@ -832,28 +931,10 @@ extern "C" int nntk_shim_rows_times_rowmat(const float *d_d, const float *d_M, f
 //     wave-wide load, then each workgroup reads the full 16 x K rows back (sc1 loads).  Rows of different t never share an address, so there is no reuse hazard.
 // Hand-off: Guideline 16 R1 (sc1 stores, vmcnt(0) in every storing wave, workgroup barrier, one agent-scope flag store; one
 // polling wave, sc1 loads after a barrier); the spin is bounded and raises the runtime's fault word (runtime.hip).
-// Same arithmetic as the per-step kernels: the elementwise part is their code, the product their chunked k-ordered MFMA chain
-// (4 chunks of K / 4 here instead of 8 of K / 8: a few roundings apart, inside the gradient tests' tolerance).
+// Same arithmetic as the per-step kernels: the elementwise part is the same functions (gru_cell_bwd / lstm_cell_bwd on the prefetched
+// registers), the product their chunked k-ordered MFMA chain (4 chunks of K / 4 here instead of 8 of K / 8: a few roundings apart, inside
+// the gradient tests' tolerance).
 typedef unsigned bp_v4u __attribute__((ext_vector_type(4)));
-struct BpttParams {
-    const float *dout;           // [B][T][H] or [B][H]
-    const float *UT;             // [K][H]
-    const float *c, *zifgo;      // LSTM caches
-    const float *h, *Zg, *hU;    // GRU caches
-    float *dG;                   // LSTM dgates [B][T][4H] / GRU d_hU [B][T][3H]: output and exchange
-    float *dxW;                  // GRU only [B][T][3H]
-    unsigned *count;             // [ceil(B / 16)][32] arrival flags (steps handed off per column tile), zeroed by the host
-    unsigned *fault;
-    unsigned long long spin_ticks;
-    int B, T, H, return_sequences;
-    int act[5];
-    float sc_out;
-    // ragged batches and carried state (all NULL: the fixed-length, zero-state pass)
-    const int *len;              // [B] row lengths
-    const float *s0;             // [B][H] initial state the step-0 terms read: GRU h0, LSTM c0
-    const float *dhT, *dcT;      // [B][H] gradient arriving at the final state (dcT: LSTM)
-    float *carry_out;            // [B][H] the register carry after step 0: GRU d_h_prev_1, LSTM d_c0
-};
 // timing ablations (tools/bptt_ablate.sh): compile-time mask, 0 in the product.  1 no poll, 2 no operand loads, 4 no MFMAs,
 // 8 no wait for the stores, 16 no stores, 32 no cache fetch
 #ifndef NNTK_BPTT_DBG
@@ -861,7 +942,7 @@ struct BpttParams {
 #endif
 #define BPTT_DBG(bit) ((NNTK_BPTT_DBG & (bit)) != 0)
 template <int CELL, int NB>      // CELL 0: GRU, 1: LSTM;  NB: 16-deep K blocks per wave, compile-time (>= K / 64; the excess multiplies zeros)
-__global__ __launch_bounds__(256) void bptt_persistent_kernel(BpttParams p) {
+__global__ __launch_bounds__(256) void bptt_persistent_kernel(RecBwdParams p) {
     constexpr int NG = CELL ? 4 : 3;
     __shared__ float part[4][4][64];
     __shared__ int s_stop;
@@ -898,70 +979,44 @@ __global__ __launch_bounds__(256) void bptt_persistent_kernel(BpttParams p) {
     float carry = 0.0f;          // LSTM: d_c carry; GRU: d_h_prev_1
     float dh2 = 0.0f;            // this thread's element of the product
     // forward caches of one step for this thread's (b, j): fetched one step ahead (the loads fly during the hand-off and the product)
-    struct Cached { float z[8]; float c, cprev, dout; };
+    struct Cached { float z[8]; float c, cprev, dout; };        // c: LSTM c_t / GRU h_pr_Uh; cprev: LSTM c_{t-1} / GRU h_{t-1}
     auto fetch = [&](int t) {
         Cached f{};
         if (!live || t < 0 || t >= L || (BPTT_DBG(32) && t < T - 1)) return f;
         const size_t row = (size_t)b * T + t;
-        if (p.return_sequences) f.dout = p.dout[row * H + j];
-        else if (t == L - 1) f.dout = p.dout[(size_t)b * H + j];
-        if (CELL) {
-            const float *zg = p.zifgo + row * 8 * H;
+        f.dout = step_dout(p.dout, p.return_sequences, t == L - 1, row, b, H, j);
+        const float *zg = p.Zg + row * 2 * NG * H;
 #pragma unroll
-            for (int g = 0; g < 8; ++g) f.z[g] = zg[g * H + j];
-            f.c = p.c[row * H + j];
-            f.cprev = t > 0 ? p.c[(row - 1) * H + j] : p.s0 ? p.s0[(size_t)b * H + j] : 0.0f;
-        } else {
-            const float *Zg = p.Zg + row * 6 * H;
-#pragma unroll
-            for (int g = 0; g < 6; ++g) f.z[g] = Zg[g * H + j];
-            f.c = p.hU[row * H + j];
-            f.cprev = t > 0 ? p.h[(row - 1) * H + j] : p.s0 ? p.s0[(size_t)b * H + j] : 0.0f;
-        }
+        for (int g = 0; g < 2 * NG; ++g) f.z[g] = zg[g * H + j];
+        f.c = p.c[row * H + j];
+        f.cprev = prev_state(CELL ? p.c : p.h, p.s0, t, row, b, H, j);
         return f;
     };
     Cached cur = fetch(TS - 1);
     for (int t = TS - 1; t >= 0; --t) {
         const bool last = t == L - 1;                            // the row's own last step: the first of its backward pass
         if (live && t < L) {
-            const size_t row = (size_t)b * T + t;
-            const float dout = cur.dout;
+            const size_t row = (size_t)b * T + t, e = (size_t)b * H + j;
             const int vo = ((bl * T + t) * K + j) * 4;
             if (CELL) {
-                const float dh = add_rn(last ? (p.dhT ? p.dhT[(size_t)b * H + j] : 0.0f) : dh2, dout);
-                const float it = cur.z[4], ft = cur.z[5], gt = cur.z[6], ot = cur.z[7];
-                const float cv = cur.c;
-                const float tc = nntk_gate_act(p.act[4], cv, p.sc_out);
-                const float d_o = gate_grad(p.act[3], cur.z[3], ot, mul_rn(dh, tc));
-                float dc = gate_grad(p.act[4], cv, nntk_gate_act(p.act[4], cv, 1.0f), mul_rn(dh, ot));
-                if (!last) dc = add_rn(dc, carry);
-                else if (p.dcT) dc = add_rn(dc, p.dcT[(size_t)b * H + j]);
-                const float d_i = gate_grad(p.act[0], cur.z[0], it, mul_rn(dc, gt));
-                const float d_f = t == 0 && !p.s0 ? 0.0f : gate_grad(p.act[1], cur.z[1], ft, mul_rn(cur.cprev, dc));
-                const float d_g = gate_grad(p.act[2], cur.z[2], gt, mul_rn(dc, it));
-                carry = mul_rn(dc, ft);
-                if (BPTT_DBG(16)) { if (d_i + d_f + d_g + d_o == 1.2345f) carry += 1.f; } else {
-                __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(d_i), rg, vo, 0, 16 /* sc1 */);
-                __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(d_f), rg, vo + H * 4, 0, 16);
-                __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(d_g), rg, vo + 2 * H * 4, 0, 16);
-                __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(d_o), rg, vo + 3 * H * 4, 0, 16);
+                const LstmCellGrad g = lstm_cell_bwd(cur.z, cur.c, cur.cprev, has_prev_state(t, p.s0), step_dh(last, p.dhT, e, dh2, cur.dout), last,
+                                                     carry, p.dcT, e, p.act, p.sc_out);
+                carry = g.dc_out;
+                if (BPTT_DBG(16)) { if (g.d_i + g.d_f + g.d_g + g.d_o == 1.2345f) carry += 1.f; } else {
+                __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(g.d_i), rg, vo, 0, 16 /* sc1 */);
+                __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(g.d_f), rg, vo + H * 4, 0, 16);
+                __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(g.d_g), rg, vo + 2 * H * 4, 0, 16);
+                __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(g.d_o), rg, vo + 3 * H * 4, 0, 16);
                 }
             } else {
-                const float dh = add_rn(last ? (p.dhT ? p.dhT[(size_t)b * H + j] : 0.0f) : add_rn(carry, dh2), dout);
-                const float z = cur.z[3], r = cur.z[4], ht = cur.z[5];
-                carry = mul_rn(z, dh);
-                const float dht = add_rn(mul_rn(-z, dh), dh);
-                const float dz = mul_rn(t > 0 || p.s0 ? sub_rn(cur.cprev, ht) : -ht, dh);
-                const float dZh = gate_grad(p.act[1], cur.z[2], ht, dht);
-                const float dr = mul_rn(cur.c, dZh);
-                const float dZz = gate_grad(p.act[0], cur.z[0], z, dz);
-                const float dZr = gate_grad(p.act[2], cur.z[1], r, dr);
-                const float dhUh = mul_rn(r, dZh);
+                const GruCellGrad g = gru_cell_bwd(cur.z, cur.c, cur.cprev, has_prev_state(t, p.s0),
+                                                   step_dh(last, p.dhT, e, add_rn(carry, dh2), cur.dout), p.act);
+                carry = g.dhp1;
                 float *dxW = p.dxW + row * 3 * H;
-                dxW[j] = dZz; dxW[H + j] = dZr; dxW[2 * H + j] = dZh;
-                __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(dZz), rg, vo, 0, 16);
-                __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(dZr), rg, vo + H * 4, 0, 16);
-                __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(dhUh), rg, vo + 2 * H * 4, 0, 16);
+                dxW[j] = g.dZz; dxW[H + j] = g.dZr; dxW[2 * H + j] = g.dZh;
+                __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(g.dZz), rg, vo, 0, 16);
+                __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(g.dZr), rg, vo + H * 4, 0, 16);
+                __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(g.dhUh), rg, vo + 2 * H * 4, 0, 16);
             }
         }
         if (t == 0) break;
@@ -1026,7 +1081,7 @@ __global__ __launch_bounds__(256) void bptt_persistent_kernel(BpttParams p) {
 }
 // 0: ran; 1: shape not taken (the caller falls back to the per-step loop); -1: error
 template <int CELL>
-static int bptt_persistent(BpttParams &p, float *d_count_words) {
+static int bptt_persistent(RecBwdParams &p, float *d_count_words) {
     const int NG = CELL ? 4 : 3;
     const int B = p.B, T = p.T, H = p.H, K = NG * H;
     const NntkOptions &opt = nntk_options();
@@ -1035,7 +1090,7 @@ static int bptt_persistent(BpttParams &p, float *d_count_words) {
     if ((double)16 * T * K * 4 >= 2.0e9) return 1;               // 32-bit buffer offsets inside a batch tile
     const int nbt = (B + 15) / 16, grid = nbt * (H / 16);
     const int nb = K / 64;
-    void (*kern)(BpttParams) = nb <= 8 ? bptt_persistent_kernel<CELL, 8> : nb <= 12 ? bptt_persistent_kernel<CELL, 12> :
+    void (*kern)(RecBwdParams) = nb <= 8 ? bptt_persistent_kernel<CELL, 8> : nb <= 12 ? bptt_persistent_kernel<CELL, 12> :
                                nb <= 16 ? bptt_persistent_kernel<CELL, 16> : nb <= 24 ? bptt_persistent_kernel<CELL, 24> :
                                bptt_persistent_kernel<CELL, 32>;
     if (nntk_resident_blocks((const void *)kern, 256, 0, 8) < grid) return 1;      // every workgroup must be resident
@@ -1055,8 +1110,7 @@ static int bptt_persistent(BpttParams &p, float *d_count_words) {
 }
 
 // ---- ragged batches and carried state (the *TrainingBatch*VarLen / *CalculateGradient*VarLen calls) ----------------------------
-// nntk_train_vl (nntk_shim.h) rides along every launcher below; NULL = the fixed-length, zero-state calls, kernel for kernel.
-static const nntk_train_vl k_no_vl = {nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+// nntk_train_vl (nntk_shim.h) rides along both launchers below; NULL = the fixed-length, zero-state calls, kernel for kernel.
 // the state after a row's last step: sT[b] = seq[b][len[b] - 1], or the initial state (zeros without one) of a row that never ran
 __global__ __launch_bounds__(256) void train_final_state_kernel(const float *__restrict__ seq, const int *__restrict__ len,
                                                                 const float *__restrict__ s0, float *__restrict__ sT, int B, int T, int H) {
@@ -1105,356 +1159,97 @@ static int train_state_grad(const float *a, const float *b2, const int *len, con
     return 0;
 }
 
-// forward over all timesteps; caches: d_h [B][T][H], d_Zg [B][T][6H], d_hU [B][T][H]
-extern "C" int nntk_shim_gru_train_forward(const float *d_x, const float *d_W, const float *d_U, const float *d_bi, const float *d_bh,
-                                           float *d_h, float *d_Zg, float *d_hU, int B, int T, int in, int H,
-                                           const int *acts /*z,h,r*/, const float *scales) {
-    return nntk_shim_gru_train_forward_vl(d_x, d_W, d_U, d_bi, d_bh, d_h, d_Zg, d_hU, B, T, in, H, acts, scales, nullptr);
+// The reported kernel of the per-step routes (nntk_hip_last_recurrent_kernel; the instantiations are rec_train_{fwd,bwd}_step_kernel<G>).
+static const char *step_kernel_name(int G, bool backward) {
+    static const char *const names[2][3] = {{"rnn_train_fwd_step_kernel", "gru_train_fwd_step_kernel", "lstm_train_fwd_step_kernel"},
+                                            {"rnn_train_bwd_step_kernel", "gru_train_bwd_step_kernel", "lstm_train_bwd_step_kernel"}};
+    return names[backward][G == 1 ? 0 : G - 2];
 }
-// ... of a ragged batch: rows run len[b] steps from h0[b]; d_h rows past a row's end are zeros (cleared here), the other caches' are never read
-extern "C" int nntk_shim_gru_train_forward_vl(const float *d_x, const float *d_W, const float *d_U, const float *d_bi, const float *d_bh,
-                                              float *d_h, float *d_Zg, float *d_hU, int B, int T, int in, int H,
-                                              const int *acts /*z,h,r*/, const float *scales, const nntk_train_vl *vlp) {
+// forward over all timesteps of a cell with G gates per unit (1 RNN, 3 GRU, 4 LSTM), caches as RecFwdParams names them (RNN: d_c unused).
+// The GRU always adds b_h, the other cells with use_bh.  Ragged batch: rows run len[b] steps from h0[b] (c0[b]); d_h rows past a row's end
+// are zeros (cleared here), the other caches' are never read.
+extern "C" int nntk_shim_rec_train_forward(int G, const float *d_x, const float *d_W, const float *d_U, const float *d_bi, const float *d_bh,
+                                           float *d_h, float *d_Zg, float *d_c, int B, int T, int in, int H, int use_bh,
+                                           const int *acts, const float *scales, const nntk_train_vl *vlp) {
     if (B <= 0 || T <= 0) return 0;
-    const nntk_train_vl &vl = vlp ? *vlp : k_no_vl;
+    const nntk_train_vl vl = vlp ? *vlp : nntk_train_vl{};
     const int TS = vl.d_len ? vl.max_len : T;
     if (vl.d_len && nntk_shim_memset(d_h, 0, (size_t)B * T * H * sizeof(float))) return -1;
     if (B > 65535) return nntk_fail_msg("recurrent training: mini-batch above 65535 (one grid row per batch entry)");
-    GruTrainParams p{};
-    p.x = d_x; p.W = d_W; p.U = d_U; p.bi = d_bi; p.bh = d_bh; p.h = d_h; p.Zg = d_Zg; p.hU = d_hU;
+    RecFwdParams p{};
+    p.x = d_x; p.W = d_W; p.U = d_U; p.bi = d_bi; p.bh = G == 3 || use_bh ? d_bh : nullptr; p.h = d_h; p.Zg = d_Zg; p.c = d_c;
     p.B = B; p.T = T; p.in = in; p.H = H;
-    p.act_z = acts[0]; p.act_h = acts[1]; p.act_r = acts[2];
-    p.sc_z = scales[0]; p.sc_h = scales[1]; p.sc_r = scales[2];
-    p.len = vl.d_len; p.h0 = vl.d_h0;
-    for (int t = 0; t < TS; ++t) {
-        p.t = t;
-        hipLaunchKernelGGL(gru_train_fwd_step_kernel, dim3((unsigned)((H + 31) / 32), (unsigned)B), dim3(256), 0, nntk_stream(), p);
-    }
-    NNTK_LAUNCH_CHECK("gru_train_fwd_step_kernel");
-    nntk_set_last_rec_kernel("gru_train_fwd_step_kernel");
-    return 0;
-}
-// backward recurrence; d_work: 2 x [B][H] (d_h_prev_1, d_h_prev_2) + [B][3H] (this step's d_hU)
-extern "C" int nntk_shim_gru_train_backward(const float *d_dout, const float *d_UT /*[3H][H]*/, const float *d_h, const float *d_Zg,
-                                            const float *d_hU, float *d_dxW, float *d_dhU, float *d_work, int B, int T, int H,
-                                            int return_sequences, const int *acts) {
-    return nntk_shim_gru_train_backward_vl(d_dout, d_UT, d_h, d_Zg, d_hU, d_dxW, d_dhU, d_work, B, T, H, return_sequences, acts, nullptr);
-}
-// ... of a ragged batch with carried state.  Rows are idle until their own last step (d_xW / d_hU rows past it: zeros, cleared here, so
-// the weight-gradient products need no mask); vl.d_dh0 = d_h_prev_1 + U d_hU of step 0: one more product than the zero-state pass needs.
-extern "C" int nntk_shim_gru_train_backward_vl(const float *d_dout, const float *d_UT /*[3H][H]*/, const float *d_h, const float *d_Zg,
-                                               const float *d_hU, float *d_dxW, float *d_dhU, float *d_work, int B, int T, int H,
-                                               int return_sequences, const int *acts, const nntk_train_vl *vlp) {
-    if (B <= 0 || T <= 0) return 0;
-    if (B > 65535) return nntk_fail_msg("recurrent training: mini-batch above 65535 (one grid row per batch entry)");
-    const nntk_train_vl &vl = vlp ? *vlp : k_no_vl;
-    const int TS = vl.d_len ? vl.max_len : T;
-    float *dhp1 = d_work, *dhp2 = d_work + (size_t)B * H, *step = d_work + (size_t)2 * B * H;
-    if (vl.d_len) {
-        if (nntk_shim_memset(d_dxW, 0, (size_t)B * T * 3 * H * sizeof(float))) return -1;
-        if (nntk_shim_memset(d_dhU, 0, (size_t)B * T * 3 * H * sizeof(float))) return -1;
-    }
-    {
-        BpttParams q{};
-        q.dout = d_dout; q.UT = d_UT; q.h = d_h; q.Zg = d_Zg; q.hU = d_hU; q.dG = d_dhU; q.dxW = d_dxW;
-        q.B = B; q.T = T; q.H = H; q.return_sequences = return_sequences;
-        q.act[0] = acts[0]; q.act[1] = acts[1]; q.act[2] = acts[2];
-        q.len = vl.d_len; q.s0 = vl.d_h0; q.dhT = vl.d_dhT; q.carry_out = vl.d_dh0 ? dhp1 : nullptr;
-        const int rc = bptt_persistent<0>(q, step);
-        if (rc < 0) return rc;
-        if (rc == 0) {
-            if (!vl.d_dh0) return 0;
-            // step 0's d_hU rows (the flag words in `step` are done with: stream order), then the product the loop stops short of
-            if (nntk_shim_copy_rows_d2d(step, d_dhU, (size_t)T * 3 * H * sizeof(float), (size_t)3 * H * sizeof(float), (size_t)B)) return -1;
-            launch_rows_times_colmat(step, d_UT, dhp2, (long)B, H, 3 * H);
-            return train_state_grad(dhp1, dhp2, vl.d_len, vl.d_dhT, return_sequences ? nullptr : d_dout, vl.d_dh0, B, H);
-        }
-    }
-    GruBwdParams p{};
-    p.dout = d_dout; p.h = d_h; p.Zg = d_Zg; p.hU = d_hU; p.dxW = d_dxW; p.dhU = d_dhU;
-    p.dhp1 = dhp1; p.dhp2 = dhp2; p.dhp1_out = dhp1; p.dhU_step = step;
-    p.B = B; p.T = T; p.H = H; p.return_sequences = return_sequences;
-    p.act_z = acts[0]; p.act_h = acts[1]; p.act_r = acts[2];
-    p.len = vl.d_len; p.h0 = vl.d_h0; p.dhT = vl.d_dhT;
-    if (TS == 0 && vl.d_dh0) {                                   // no row runs: nothing to carry back but what arrived
-        if (nntk_shim_memset(dhp1, 0, (size_t)B * H * sizeof(float))) return -1;
-        return train_state_grad(dhp1, nullptr, vl.d_len, vl.d_dhT, return_sequences ? nullptr : d_dout, vl.d_dh0, B, H);
-    }
-    for (int t = TS - 1; t >= 0; --t) {
-        p.t = t;
-        hipLaunchKernelGGL(gru_train_bwd_step_kernel, dim3((B * H + 255) / 256), dim3(256), 0, nntk_stream(), p);
-        if (t > 0 || vl.d_dh0)
-            launch_rows_times_colmat(step, d_UT, dhp2, (long)B, H, 3 * H);
-    }
-    NNTK_LAUNCH_CHECK("gru_train_bwd_step_kernel");
-    nntk_set_last_rec_kernel("gru_train_bwd_step_kernel");
-    return vl.d_dh0 ? train_state_grad(dhp1, dhp2, vl.d_len, vl.d_dhT, return_sequences ? nullptr : d_dout, vl.d_dh0, B, H) : 0;
-}
-
-// ---- LSTM training (layers/lstm.c:185-239 forward cell, :294-556 BPTT) --------------------------------------------
-// Same structure as the GRU path.  Caches: zifgo [B][T][8H] = Z_i | Z_f | Z_g | Z_o | i | f | g | o, c [B][T][H], h [B][T][H].
-struct LstmTrainParams {
-    const float *x, *W, *U, *bi, *bh;      // W [in][4H], U [H][4H]
-    float *h, *c, *zifgo;
-    int B, T, in, H, t, v2;
-    int act[5];                            // i, f, g, o, out
-    float sc[5];
-    const int *len;                        // ragged batches (NULL: every row T)
-    const float *h0, *c0;                  // [B][H] initial state or NULL (zeros)
-};
-__global__ __launch_bounds__(256) void lstm_train_fwd_step_kernel(LstmTrainParams p) {
-    const int b = blockIdx.y, j = blockIdx.x * 32 + (threadIdx.x & 31), H = p.H;
-    const size_t row = (size_t)b * p.T + p.t;
-    if (p.len && p.t >= p.len[b]) return;                           // past the row's end; its h row was cleared by the host
-    const float *hp = p.t > 0 ? p.h + (row - 1) * H : p.h0 ? p.h0 + (size_t)b * H : nullptr;      // zero state per sequence (lstm.c:441) unless carried in
-    float Z[4], hu[4];
-    if (!cell_dots_chunked<4>(p.x + row * p.in, hp, p.W, p.U, p.in, H, j, Z, hu)) return;
-    float a[4];
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-        Z[g] = add_rn(Z[g], p.bi[g * H + j]);
-        if (p.v2) hu[g] = add_rn(hu[g], p.bh[g * H + j]);
-        Z[g] = add_rn(Z[g], hu[g]);
-        a[g] = nntk_gate_act(p.act[g], Z[g], p.sc[g]);
-    }
-    const float cp = p.t > 0 ? p.c[(row - 1) * H + j] : p.c0 ? p.c0[(size_t)b * H + j] : 0.0f;
-    const float c = add_rn(mul_rn(a[1], cp), mul_rn(a[0], a[2]));         // f c_prev + i g
-    const float h = mul_rn(a[3], nntk_gate_act(p.act[4], c, p.sc[4]));
-    float *zg = p.zifgo + row * 8 * H;
-#pragma unroll
-    for (int g = 0; g < 4; ++g) { zg[g * H + j] = Z[g]; zg[(4 + g) * H + j] = a[g]; }
-    p.c[row * H + j] = c;
-    p.h[row * H + j] = h;
-}
-// elementwise part of LSTMCellBackward (lstm.c:294-416) for thread (b, j); d_c carry in place, d_h carry from the
-// previous step's U dgates product
-struct LstmBwdParams {
-    const float *dout, *c, *zifgo;
-    const float *dh_carry;       // [B][H] = U dgates of step t + 1
-    float *dc_carry;             // [B][H], read (t < T-1) and rewritten
-    float *dG, *dG_step;         // [B][T][4H], [B][4H]
-    int B, T, H, t, return_sequences;
-    int act[5];
-    float sc_out;
-    const int *len;              // ragged batches (NULL: every row T)
-    const float *c0, *dhT, *dcT; // [B][H] initial cell state / gradients arriving at the final state, or NULL (zeros)
-};
-__global__ __launch_bounds__(256) void lstm_train_bwd_step_kernel(LstmBwdParams p) {
-    const int e = blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= p.B * p.H) return;
-    const int b = e / p.H, j = e % p.H, H = p.H;
-    const size_t row = (size_t)b * p.T + p.t;
-    const int L = p.len ? p.len[b] : p.T;
-    if (p.t >= L) {              // idle (the dgates rows were cleared by the host); a row that never runs hands back zeros
-        float *ds = p.dG_step + (size_t)b * 4 * H;
-        ds[j] = 0.0f; ds[H + j] = 0.0f; ds[2 * H + j] = 0.0f; ds[3 * H + j] = 0.0f;
-        p.dc_carry[e] = 0.0f;
-        return;
-    }
-    const bool last = p.t == L - 1;
-    float dout = 0.0f;
-    if (p.return_sequences) dout = p.dout[row * H + j];
-    else if (last) dout = p.dout[(size_t)b * H + j];
-    const float dh = add_rn(last ? (p.dhT ? p.dhT[e] : 0.0f) : p.dh_carry[e], dout);
-    const float *zg = p.zifgo + row * 8 * H;
-    const float it = zg[4 * H + j], ft = zg[5 * H + j], gt = zg[6 * H + j], ot = zg[7 * H + j];
-    const float ct = p.c[row * H + j];
-    const float tc = nntk_gate_act(p.act[4], ct, p.sc_out);
-    const float d_o = gate_grad(p.act[3], zg[3 * H + j], ot, mul_rn(dh, tc));
-    // non-cached derivative of the output activation at c_t (activation.c:49-50): forward value recomputed, UNscaled
-    float dc = gate_grad(p.act[4], ct, nntk_gate_act(p.act[4], ct, 1.0f), mul_rn(dh, ot));
-    if (!last) dc = add_rn(dc, p.dc_carry[e]);
-    else if (p.dcT) dc = add_rn(dc, p.dcT[e]);
-    const float d_f = p.t > 0 ? gate_grad(p.act[1], zg[H + j], ft, mul_rn(p.c[(row - 1) * H + j], dc))
-                    : p.c0 ? gate_grad(p.act[1], zg[H + j], ft, mul_rn(p.c0[e], dc)) : 0.0f;
-    const float d_i = gate_grad(p.act[0], zg[j], it, mul_rn(dc, gt));
-    const float d_g = gate_grad(p.act[2], zg[2 * H + j], gt, mul_rn(dc, it));
-    p.dc_carry[e] = mul_rn(dc, ft);
-    float *dG = p.dG + row * 4 * H, *ds = p.dG_step + (size_t)b * 4 * H;
-    dG[j] = d_i; dG[H + j] = d_f; dG[2 * H + j] = d_g; dG[3 * H + j] = d_o;
-    ds[j] = d_i; ds[H + j] = d_f; ds[2 * H + j] = d_g; ds[3 * H + j] = d_o;
-}
-extern "C" int nntk_shim_lstm_train_forward(const float *d_x, const float *d_W, const float *d_U, const float *d_bi, const float *d_bh,
-                                            float *d_h, float *d_c, float *d_zifgo, int B, int T, int in, int H, int v2,
-                                            const int *acts /*i,f,g,o,out*/, const float *scales) {
-    return nntk_shim_lstm_train_forward_vl(d_x, d_W, d_U, d_bi, d_bh, d_h, d_c, d_zifgo, B, T, in, H, v2, acts, scales, nullptr);
-}
-extern "C" int nntk_shim_lstm_train_forward_vl(const float *d_x, const float *d_W, const float *d_U, const float *d_bi, const float *d_bh,
-                                               float *d_h, float *d_c, float *d_zifgo, int B, int T, int in, int H, int v2,
-                                               const int *acts /*i,f,g,o,out*/, const float *scales, const nntk_train_vl *vlp) {
-    if (B <= 0 || T <= 0) return 0;
-    const nntk_train_vl &vl = vlp ? *vlp : k_no_vl;
-    const int TS = vl.d_len ? vl.max_len : T;
-    if (vl.d_len && nntk_shim_memset(d_h, 0, (size_t)B * T * H * sizeof(float))) return -1;
-    if (B > 65535) return nntk_fail_msg("recurrent training: mini-batch above 65535 (one grid row per batch entry)");
-    LstmTrainParams p{};
-    p.x = d_x; p.W = d_W; p.U = d_U; p.bi = d_bi; p.bh = d_bh; p.h = d_h; p.c = d_c; p.zifgo = d_zifgo;
-    p.B = B; p.T = T; p.in = in; p.H = H; p.v2 = v2;
-    for (int g = 0; g < 5; ++g) { p.act[g] = acts[g]; p.sc[g] = scales[g]; }
+    for (int g = 0; g < (G == 4 ? 5 : G); ++g) { p.act[g] = acts[g]; p.sc[g] = scales[g]; }
     p.len = vl.d_len; p.h0 = vl.d_h0; p.c0 = vl.d_c0;
+    void (*kern)(RecFwdParams) = G == 3 ? rec_train_fwd_step_kernel<3> : G == 4 ? rec_train_fwd_step_kernel<4> : rec_train_fwd_step_kernel<1>;
     for (int t = 0; t < TS; ++t) {
         p.t = t;
-        hipLaunchKernelGGL(lstm_train_fwd_step_kernel, dim3((unsigned)((H + 31) / 32), (unsigned)B), dim3(256), 0, nntk_stream(), p);
+        hipLaunchKernelGGL(kern, dim3((unsigned)((H + 31) / 32), (unsigned)B), dim3(256), 0, nntk_stream(), p);
     }
-    NNTK_LAUNCH_CHECK("lstm_train_fwd_step_kernel");
-    nntk_set_last_rec_kernel("lstm_train_fwd_step_kernel");
+    NNTK_LAUNCH_CHECK(step_kernel_name(G, false));
+    nntk_set_last_rec_kernel(step_kernel_name(G, false));
     return 0;
 }
-// d_work: [B][H] d_h carry + [B][H] d_c carry + [B][4H] this step's dgates
-extern "C" int nntk_shim_lstm_train_backward(const float *d_dout, const float *d_UT /*[4H][H]*/, const float *d_c, const float *d_zifgo,
-                                             float *d_dG, float *d_work, int B, int T, int H, int return_sequences,
-                                             const int *acts, const float *scales) {
-    return nntk_shim_lstm_train_backward_vl(d_dout, d_UT, d_c, d_zifgo, d_dG, d_work, B, T, H, return_sequences, acts, scales, nullptr);
-}
-// ... of a ragged batch with carried state: vl.d_dh0 = U dgates of step 0, vl.d_dc0 = the d_c carry after step 0
-extern "C" int nntk_shim_lstm_train_backward_vl(const float *d_dout, const float *d_UT /*[4H][H]*/, const float *d_c, const float *d_zifgo,
-                                                float *d_dG, float *d_work, int B, int T, int H, int return_sequences,
-                                                const int *acts, const float *scales, const nntk_train_vl *vlp) {
+// d_work of the backward recurrence: d_h_prev from the product [B][H], the cell's own carry [B][H] (not the RNN), this step's dG rows [B][G H]
+extern "C" size_t nntk_shim_rec_train_work_floats(int G, int B, int H) { return (size_t)B * H * ((G == 1 ? 1 : 2) + G); }
+// backward recurrence over a ragged batch with carried state, on the persistent kernel where it takes the shape (GRU, LSTM), else step by
+// step.  Rows are idle until their own last step (dG / dxW rows past it: zeros, cleared here, so the weight-gradient products need no mask).
+// d_dG / d_dxW: RecBwdParams (one buffer for the LSTM and the RNN).  vl.d_dh0 = U dG of step 0 (GRU: + d_h_prev_1) -- one more product
+// than the zero-state pass needs; vl.d_dc0 = the d_c carry after step 0.
+extern "C" int nntk_shim_rec_train_backward(int G, const float *d_dout, const float *d_UT /*[G H][H]*/, const float *d_h, const float *d_Zg,
+                                            const float *d_c, float *d_dxW, float *d_dG, float *d_work, int B, int T, int H,
+                                            int return_sequences, const int *acts, const float *scales, const nntk_train_vl *vlp) {
     if (B <= 0 || T <= 0) return 0;
     if (B > 65535) return nntk_fail_msg("recurrent training: mini-batch above 65535 (one grid row per batch entry)");
-    const nntk_train_vl &vl = vlp ? *vlp : k_no_vl;
-    const int TS = vl.d_len ? vl.max_len : T;
-    const bool want0 = vl.d_dh0 || vl.d_dc0;
-    float *dh = d_work, *dc = d_work + (size_t)B * H, *step = d_work + (size_t)2 * B * H;
-    if (vl.d_len && nntk_shim_memset(d_dG, 0, (size_t)B * T * 4 * H * sizeof(float))) return -1;
-    auto finish = [&]() -> int {                                 // dh = U dgates_0, dc = the carry after step 0
-        if (vl.d_dh0 && train_state_grad(dh, nullptr, vl.d_len, vl.d_dhT, return_sequences ? nullptr : d_dout, vl.d_dh0, B, H)) return -1;
-        if (vl.d_dc0 && train_state_grad(dc, nullptr, vl.d_len, vl.d_dcT, nullptr, vl.d_dc0, B, H)) return -1;
+    const nntk_train_vl vl = vlp ? *vlp : nntk_train_vl{};
+    const int TS = vl.d_len ? vl.max_len : T, K = G * H, carries = G == 1 ? 1 : 2;
+    float *d_dc0 = G == 4 ? vl.d_dc0 : nullptr;
+    const bool want0 = vl.d_dh0 || d_dc0;
+    float *prod = d_work, *own = G == 1 ? nullptr : d_work + (size_t)B * H, *step = d_work + (size_t)carries * B * H;
+    if (vl.d_len) {
+        if (G == 3 && nntk_shim_memset(d_dxW, 0, (size_t)B * T * K * sizeof(float))) return -1;
+        if (nntk_shim_memset(d_dG, 0, (size_t)B * T * K * sizeof(float))) return -1;
+    }
+    const float *dlast = return_sequences ? nullptr : d_dout;
+    auto finish = [&]() -> int {                                 // prod = U dG_0, own = the carry after step 0
+        if (vl.d_dh0 && train_state_grad(G == 3 ? own : prod, G == 3 ? prod : nullptr, vl.d_len, vl.d_dhT, dlast, vl.d_dh0, B, H)) return -1;
+        if (d_dc0 && train_state_grad(own, nullptr, vl.d_len, vl.d_dcT, nullptr, d_dc0, B, H)) return -1;
         return 0;
     };
-    {
-        BpttParams q{};
-        q.dout = d_dout; q.UT = d_UT; q.c = d_c; q.zifgo = d_zifgo; q.dG = d_dG;
-        q.B = B; q.T = T; q.H = H; q.return_sequences = return_sequences;
-        for (int g = 0; g < 5; ++g) q.act[g] = acts[g];
-        q.sc_out = scales[4];
-        q.len = vl.d_len; q.s0 = vl.d_c0; q.dhT = vl.d_dhT; q.dcT = vl.d_dcT; q.carry_out = vl.d_dc0 ? dc : nullptr;
-        const int rc = bptt_persistent<1>(q, step);
+    RecBwdParams p{};
+    p.dout = d_dout; p.h = d_h; p.Zg = d_Zg; p.c = d_c; p.dG = d_dG; p.dxW = d_dxW;
+    p.B = B; p.T = T; p.H = H; p.return_sequences = return_sequences;
+    for (int g = 0; g < (G == 4 ? 5 : G); ++g) p.act[g] = acts[g];
+    p.sc_out = G == 4 ? scales[4] : 0.0f;
+    p.len = vl.d_len; p.s0 = G == 4 ? vl.d_c0 : vl.d_h0; p.dhT = vl.d_dhT; p.dcT = G == 4 ? vl.d_dcT : nullptr;
+    p.prod = prod; p.own = own; p.step = step; p.UT = d_UT;
+    if (G != 1) {
+        p.carry_out = (G == 3 ? vl.d_dh0 : d_dc0) ? own : nullptr;
+        const int rc = G == 3 ? bptt_persistent<0>(p, step) : bptt_persistent<1>(p, step);
         if (rc < 0) return rc;
         if (rc == 0) {
             if (!want0) return 0;
-            if (vl.d_dh0) {
-                if (nntk_shim_copy_rows_d2d(step, d_dG, (size_t)T * 4 * H * sizeof(float), (size_t)4 * H * sizeof(float), (size_t)B)) return -1;
-                launch_rows_times_colmat(step, d_UT, dh, (long)B, H, 4 * H);
+            if (vl.d_dh0) {      // step 0's dG rows (the flag words in `step` are done with: stream order), then the product the loop stops short of
+                if (nntk_shim_copy_rows_d2d(step, d_dG, (size_t)T * K * sizeof(float), (size_t)K * sizeof(float), (size_t)B)) return -1;
+                launch_rows_times_colmat(step, d_UT, prod, (long)B, H, K);
             }
             return finish();
         }
     }
-    LstmBwdParams p{};
-    p.dout = d_dout; p.c = d_c; p.zifgo = d_zifgo; p.dh_carry = dh; p.dc_carry = dc; p.dG = d_dG; p.dG_step = step;
-    p.B = B; p.T = T; p.H = H; p.return_sequences = return_sequences;
-    for (int g = 0; g < 5; ++g) p.act[g] = acts[g];
-    p.sc_out = scales[4];
-    p.len = vl.d_len; p.c0 = vl.d_c0; p.dhT = vl.d_dhT; p.dcT = vl.d_dcT;
     if (TS == 0 && want0) {                                      // no row runs: what arrived goes straight back
-        if (nntk_shim_memset(d_work, 0, (size_t)2 * B * H * sizeof(float))) return -1;
+        if (nntk_shim_memset(d_work, 0, (size_t)carries * B * H * sizeof(float))) return -1;
         return finish();
     }
+    void (*kern)(RecBwdParams) = G == 3 ? rec_train_bwd_step_kernel<3> : G == 4 ? rec_train_bwd_step_kernel<4> : rec_train_bwd_step_kernel<1>;
     for (int t = TS - 1; t >= 0; --t) {
         p.t = t;
-        hipLaunchKernelGGL(lstm_train_bwd_step_kernel, dim3((B * H + 255) / 256), dim3(256), 0, nntk_stream(), p);
+        hipLaunchKernelGGL(kern, dim3((B * H + 255) / 256), dim3(256), 0, nntk_stream(), p);
         if (t > 0 || vl.d_dh0)
-            launch_rows_times_colmat(step, d_UT, dh, (long)B, H, 4 * H);
+            launch_rows_times_colmat(step, d_UT, prod, (long)B, H, K);
     }
-    NNTK_LAUNCH_CHECK("lstm_train_bwd_step_kernel");
-    nntk_set_last_rec_kernel("lstm_train_bwd_step_kernel");
+    NNTK_LAUNCH_CHECK(step_kernel_name(G, true));
+    nntk_set_last_rec_kernel(step_kernel_name(G, true));
     return want0 ? finish() : 0;
-}
-
-// ---- RNN training (layers/rnn.c:144-166 forward cell, :184-221 backward cell, :249-351) ---------------------------
-// caches: gate [B][T][H] (pre-activation), h [B][T][H]
-struct RnnTrainParams {
-    const float *x, *W, *U, *bi, *bh;      // W [in][H], U [H][H]
-    float *h, *gate;
-    int B, T, in, H, t, v2, act;
-    float sc;
-    const int *len;                        // ragged batches (NULL: every row T)
-    const float *h0;                       // [B][H] initial state or NULL (zeros)
-};
-__global__ __launch_bounds__(256) void rnn_train_fwd_step_kernel(RnnTrainParams p) {
-    const int b = blockIdx.y, j = blockIdx.x * 32 + (threadIdx.x & 31), H = p.H;
-    const size_t row = (size_t)b * p.T + p.t;
-    if (p.len && p.t >= p.len[b]) return;                           // past the row's end; its h row was cleared by the host
-    const float *hp = p.t > 0 ? p.h + (row - 1) * H : p.h0 ? p.h0 + (size_t)b * H : nullptr;
-    float xw[1], hu[1];
-    if (!cell_dots_chunked<1>(p.x + row * p.in, hp, p.W, p.U, p.in, H, j, xw, hu)) return;
-    const float xv = add_rn(xw[0], p.bi[j]);
-    const float hv = p.v2 ? add_rn(hu[0], p.bh[j]) : hu[0];
-    const float g = add_rn(hv, xv);
-    p.gate[row * H + j] = g;
-    p.h[row * H + j] = nntk_gate_act(p.act, g, p.sc);
-}
-__global__ __launch_bounds__(256) void rnn_train_bwd_step_kernel(const float *dout, const float *h, const float *gate,
-                                                                 const float *dh_carry, float *dG, float *dG_step,
-                                                                 int B, int T, int H, int t, int return_sequences, int act,
-                                                                 const int *len, const float *dhT) {
-    const int e = blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= B * H) return;
-    const int b = e / H, j = e % H;
-    const size_t row = (size_t)b * T + t;
-    const int L = len ? len[b] : T;
-    if (t >= L) { dG_step[e] = 0.0f; return; }      // idle (the d_gate rows were cleared by the host)
-    const bool last = t == L - 1;
-    float d_o = 0.0f;
-    if (return_sequences) d_o = dout[row * H + j];
-    else if (last) d_o = dout[(size_t)b * H + j];
-    const float dh = add_rn(last ? (dhT ? dhT[e] : 0.0f) : dh_carry[e], d_o);
-    const float dg = gate_grad(act, gate[row * H + j], h[row * H + j], dh);
-    dG[row * H + j] = dg;
-    dG_step[e] = dg;
-}
-extern "C" int nntk_shim_rnn_train_forward(const float *d_x, const float *d_W, const float *d_U, const float *d_bi, const float *d_bh,
-                                           float *d_h, float *d_gate, int B, int T, int in, int H, int v2, int act, float scale) {
-    return nntk_shim_rnn_train_forward_vl(d_x, d_W, d_U, d_bi, d_bh, d_h, d_gate, B, T, in, H, v2, act, scale, nullptr);
-}
-extern "C" int nntk_shim_rnn_train_forward_vl(const float *d_x, const float *d_W, const float *d_U, const float *d_bi, const float *d_bh,
-                                              float *d_h, float *d_gate, int B, int T, int in, int H, int v2, int act, float scale,
-                                              const nntk_train_vl *vlp) {
-    if (B <= 0 || T <= 0) return 0;
-    const nntk_train_vl &vl = vlp ? *vlp : k_no_vl;
-    const int TS = vl.d_len ? vl.max_len : T;
-    if (vl.d_len && nntk_shim_memset(d_h, 0, (size_t)B * T * H * sizeof(float))) return -1;
-    if (B > 65535) return nntk_fail_msg("recurrent training: mini-batch above 65535 (one grid row per batch entry)");
-    RnnTrainParams p{};
-    p.x = d_x; p.W = d_W; p.U = d_U; p.bi = d_bi; p.bh = d_bh; p.h = d_h; p.gate = d_gate;
-    p.B = B; p.T = T; p.in = in; p.H = H; p.v2 = v2; p.act = act; p.sc = scale;
-    p.len = vl.d_len; p.h0 = vl.d_h0;
-    for (int t = 0; t < TS; ++t) {
-        p.t = t;
-        hipLaunchKernelGGL(rnn_train_fwd_step_kernel, dim3((unsigned)((H + 31) / 32), (unsigned)B), dim3(256), 0, nntk_stream(), p);
-    }
-    NNTK_LAUNCH_CHECK("rnn_train_fwd_step_kernel");
-    nntk_set_last_rec_kernel("rnn_train_fwd_step_kernel");
-    return 0;
-}
-// d_work: [B][H] d_h carry + [B][H] this step's d_gate
-extern "C" int nntk_shim_rnn_train_backward(const float *d_dout, const float *d_UT /*[H][H]*/, const float *d_h, const float *d_gate,
-                                            float *d_dG, float *d_work, int B, int T, int H, int return_sequences, int act) {
-    return nntk_shim_rnn_train_backward_vl(d_dout, d_UT, d_h, d_gate, d_dG, d_work, B, T, H, return_sequences, act, nullptr);
-}
-// ... of a ragged batch with carried state: vl.d_dh0 = U d_gate of step 0
-extern "C" int nntk_shim_rnn_train_backward_vl(const float *d_dout, const float *d_UT /*[H][H]*/, const float *d_h, const float *d_gate,
-                                               float *d_dG, float *d_work, int B, int T, int H, int return_sequences, int act,
-                                               const nntk_train_vl *vlp) {
-    if (B <= 0 || T <= 0) return 0;
-    if (B > 65535) return nntk_fail_msg("recurrent training: mini-batch above 65535 (one grid row per batch entry)");
-    const nntk_train_vl &vl = vlp ? *vlp : k_no_vl;
-    const int TS = vl.d_len ? vl.max_len : T;
-    float *dh = d_work, *step = d_work + (size_t)B * H;
-    if (vl.d_len && nntk_shim_memset(d_dG, 0, (size_t)B * T * H * sizeof(float))) return -1;
-    if (TS == 0 && vl.d_dh0) {
-        if (nntk_shim_memset(dh, 0, (size_t)B * H * sizeof(float))) return -1;
-        return train_state_grad(dh, nullptr, vl.d_len, vl.d_dhT, return_sequences ? nullptr : d_dout, vl.d_dh0, B, H);
-    }
-    for (int t = TS - 1; t >= 0; --t) {
-        hipLaunchKernelGGL(rnn_train_bwd_step_kernel, dim3((B * H + 255) / 256), dim3(256), 0, nntk_stream(), d_dout, d_h, d_gate,
-                           (const float *)dh, d_dG, step, B, T, H, t, return_sequences, act, vl.d_len, vl.d_dhT);
-        if (t > 0 || vl.d_dh0)
-            launch_rows_times_colmat(step, d_UT, dh, (long)B, H, H);
-    }
-    NNTK_LAUNCH_CHECK("rnn_train_bwd_step_kernel");
-    nntk_set_last_rec_kernel("rnn_train_bwd_step_kernel");
-    return vl.d_dh0 ? train_state_grad(dh, nullptr, vl.d_len, vl.d_dhT, return_sequences ? nullptr : d_dout, vl.d_dh0, B, H) : 0;
 }
 
 // ---- MFMA forms of the large training products -------------------------------------------------------------------

@@ -870,11 +870,9 @@ static int layer_train_forward(rec_layer *l, const float *d_x, const nntk_train_
     int rc = G == 1 ? 1 : train_forward_rr(l, d_x, &raw, vl);
     if (rc < 0) return -1;
     if (rc) {
-        const nntk_train_vl *v = train_vl_active(vl) ? vl : NULL;
-        if (G == 3) rc = nntk_shim_gru_train_forward_vl(d_x, raw.W, raw.U, raw.bi, raw.bh, d_h, d_Zg, d_hU, B, T, in, H, l->acts, l->scales, v);
-        else if (G == 4) rc = nntk_shim_lstm_train_forward_vl(d_x, raw.W, raw.U, raw.bi, raw.bh, d_h, d_hU, d_Zg, B, T, in, H, l->use_bh ? 1 : 0, l->acts, l->scales, v);
-        else rc = nntk_shim_rnn_train_forward_vl(d_x, raw.W, raw.U, raw.bi, raw.bh, d_h, d_Zg, B, T, in, H, l->use_bh ? 1 : 0, l->acts[0], l->scales[0], v);
-        if (rc) return -1;
+        if (nntk_shim_rec_train_forward(G, d_x, raw.W, raw.U, raw.bi, raw.bh, d_h, d_Zg, d_hU, B, T, in, H, l->use_bh ? 1 : 0, l->acts, l->scales,
+                                        train_vl_active(vl) ? vl : NULL))
+            return -1;
     }
     t->d_x_cur = d_x;
     t->have_batch = 1;
@@ -892,16 +890,12 @@ static int layer_train_gradient(rec_layer *l, const float *d_dout, float *d_grad
     /* the gate gradients [B][T][K]: the GRU's differ between the input side (d_xW) and the recurrent side (d_hU), the other cells have one */
     float *d_dxW = nntk_devbuf_reserve(&t->d_dxW, rows * K);
     float *d_dhU = G == 3 ? nntk_devbuf_reserve(&t->d_dhU, rows * K) : d_dxW;
-    float *d_work = nntk_devbuf_reserve(&t->d_work, (size_t)B * (G == 3 ? 5 : G == 4 ? 6 : 2) * H);
+    float *d_work = nntk_devbuf_reserve(&t->d_work, nntk_shim_rec_train_work_floats(G, B, H));
     float *d_UT = nntk_devbuf_reserve(&t->d_scr, u);
     if (!d_dxW || !d_dhU || !d_work || !d_UT) return -1;
     const float *dW = t->d_raw.p, *dU = dW + w;
     if (nntk_shim_transpose(dU, d_UT, H, K, 0)) return -1;                  /* U^T [K][H]: coalesced per-step product */
-    int rc;
-    if (G == 3) rc = nntk_shim_gru_train_backward_vl(d_dout, d_UT, t->d_h.p, t->d_Zg.p, t->d_hU.p, d_dxW, d_dhU, d_work, B, T, H, rs, l->acts, vl);
-    else if (G == 4) rc = nntk_shim_lstm_train_backward_vl(d_dout, d_UT, t->d_hU.p, t->d_Zg.p, d_dxW, d_work, B, T, H, rs, l->acts, l->scales, vl);
-    else rc = nntk_shim_rnn_train_backward_vl(d_dout, d_UT, t->d_h.p, t->d_Zg.p, d_dxW, d_work, B, T, H, rs, l->acts[0], vl);
-    if (rc) return -1;
+    if (nntk_shim_rec_train_backward(G, d_dout, d_UT, t->d_h.p, t->d_Zg.p, t->d_hU.p, d_dxW, d_dhU, d_work, B, T, H, rs, l->acts, l->scales, vl)) return -1;
     /* d_W += x^T d_xW, d_b_i += colsum d_xW;  d_U += h_prev^T d_hU, d_b_h += colsum d_hU;  d_X = d_xW W^T */
     if (nntk_train_outer_accumulate(t->d_x_cur, d_dxW, d_grad, d_grad + w + u, (long)rows, in, K, 0)) return -1;
     if (nntk_train_outer_accumulate(t->d_h.p, d_dhU, d_grad + w, d_grad + w + u + K, (long)rows, H, K, T)) return -1;

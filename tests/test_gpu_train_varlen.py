@@ -428,6 +428,34 @@ def test_persistent_bptt_equals_the_per_step_loop_on_ragged_batches(gpu, bptt_op
         assert err <= 2e-5 * sc, (nm, err)
 
 
+@pytest.mark.parametrize("seq", [True, False], ids=["seq", "last"])
+@pytest.mark.parametrize("kind,B,T,n_in,H", [("gru", 17, 4, 8, 64), ("lstm", 17, 4, 8, 16)])
+def test_a_rows_last_step_has_the_same_bits_on_both_bptt_routes(gpu, bptt_option, kind, B, T, n_in, H, seq):
+    """The persistent kernel and the per-step loop run ONE backward cell (gru_cell_bwd / lstm_cell_bwd, train.hip) and differ only in
+    the product that carries d_h back.  At a row's own last step nothing has been carried yet -- d_h is d_hT plus the output gradient --
+    so the gate gradients there are the cell alone and the two routes agree bit for bit: d_h0 / d_c0 of the rows of length 1 (their
+    last step is step 0), and d_X at every non-empty row's last step (d_xW W^T and d_hU U^T are per-row products at these sizes)."""
+    ln = lengths_for(B, T, 19)
+    assert {0, 1, T} <= set(ln.tolist())
+    res = []
+    for opt in ("auto", 0):
+        bptt_option(opt)
+        net = Net(kind, B, T, n_in, H, seq, 22)
+        x, dout, h0, c0, dhT, dcT = _data(net, 91)
+        net.forward(x, ln, h0, c0)
+        res.append(net.backward(dout, dhT, dcT))
+        # (the persistent kernel steps aside silently when it cannot run: the comparison must not be of the loop with itself)
+        assert net.last_kernel() == ("bptt_persistent_kernel<%s>" % kind.upper() if opt == "auto" else "%s_train_bwd_step_kernel" % kind)
+        net.close()
+    one, rows = ln == 1, np.nonzero(ln > 0)[0]
+    for nm in ("dh0", "dc0"):
+        p_, q_ = (r[PARTS.index(nm)] for r in res)
+        if p_ is not None:
+            assert np.isfinite(p_).all()
+            np.testing.assert_array_equal(p_[one], q_[one], err_msg=nm)
+    np.testing.assert_array_equal(res[0][4][rows, ln[rows] - 1], res[1][4][rows, ln[rows] - 1], err_msg="dX at the last step")
+
+
 @pytest.mark.parametrize("kind,B,T,n_in,H,seq,v2", [("gru", 37, 12, 104, 64, True, True), ("gru", 33, 6, 200, 64, False, True), ("gru", 64, 40, 128, 256, True, True),
                                                     ("gru", 130, 9, 72, 128, True, True), ("lstm", 37, 12, 40, 64, True, False),
                                                     ("lstm", 33, 6, 200, 64, False, True), ("lstm", 64, 40, 128, 512, True, True),
