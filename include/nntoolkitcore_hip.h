@@ -663,6 +663,66 @@ int RNNBidirectionalApplyDevice(RNN forward, RNN backward, const float *d_input,
 int GRUBidirectionalApplyInferenceBatch(GRU forward, GRU backward, const float *input, float *output, int batch, const int *lengths, int merge);
 int LSTMBidirectionalApplyInferenceBatch(LSTM forward, LSTM backward, const float *input, float *output, int batch, const int *lengths, int merge);
 int RNNBidirectionalApplyInferenceBatch(RNN forward, RNN backward, const float *input, float *output, int batch, const int *lengths, int merge);
+/* ---- training a bidirectional layer (INTEGRATION.md "Training a bidirectional layer") -------------------------------------------
+ * Device forms of the reference's gradient helpers (bidirectional.c:58-108), thin wrappers over one-pass kernels.  The three fixed-length
+ * forms return the bits of bd_merge_concat_gradient / bd_merge_sum_gradient / bd_accumulate_d_x; as there, d_backward is NOT reversed
+ * (bd_accumulate_d_x reverses the backward direction's d_X within T).  The varlen forms are what a ragged bidirectional layer needs
+ * (lengths: HOST memory [batch] or NULL = every row T, checked and copied like bd_reverse_*_varlen_device's; L = lengths[b]):
+ *   bd_merge_gradient_varlen_device: d_forward[b][t] = d_dout[b][t][forward part], d_backward_reversed[b][t] = d_dout[b][L-1-t][backward part]
+ *     for t < L, both exact zeros for t >= L whatever d_dout holds there; parts: columns [0, H) / [H, 2H) (NNTK_BD_MERGE_CONCAT) or the whole
+ *     row twice (NNTK_BD_MERGE_SUM); without return_sequences the plain split / copy of [batch][2H] / [batch][H].
+ *   bd_accumulate_d_x_varlen_device: d_output[b][t] = d_forward_dx[b][t] + d_backward_dx[b][L-1-t] for t < L (one f32 add), zeros for t >= L.
+ * -1 and nntk_last_error() for batch < 0, a NULL pointer, a length outside [0, T], an unknown merge, or tensors that overlap (d_output may
+ * be d_forward_dx). */
+int bd_merge_concat_gradient_device(const float *d_dout, float *d_forward, float *d_backward, RecurrentConfig config, int batch);
+int bd_merge_sum_gradient_device(const float *d_dout, float *d_forward, float *d_backward, RecurrentConfig config, int batch);
+int bd_accumulate_d_x_device(const float *d_forward_dx, const float *d_backward_dx, float *d_output, RecurrentConfig config, int batch);
+int bd_merge_gradient_varlen_device(const float *d_dout, float *d_forward, float *d_backward_reversed, RecurrentConfig config, int batch,
+                                    const int *lengths, int merge);
+int bd_accumulate_d_x_varlen_device(const float *d_forward_dx, const float *d_backward_dx, float *d_output, RecurrentConfig config, int batch,
+                                    const int *lengths);
+/* The layer in one call per pass.  forward / backward: two DIFFERENT *CreateForTraining handles of one kind with equal input size, H, T,
+ * return_sequences and mini_batch_size (B; T is also the row stride); one handle holds one set of caches, so the same handle twice is an
+ * error.  Both directions start from zero state (a bidirectional layer cannot be chunked in time: no h0 / hT).  lengths: HOST [B] or NULL.
+ * Forward: bit for bit the recipe
+ *     bd_reverse_input_batch[_varlen]_device(x -> xr); *ApplyTrainingBatchDeviceVarLen(forward, x -> of); *ApplyTrainingBatchDeviceVarLen(backward,
+ *     xr -> obr), both with these lengths and no states; out[b][t] = merge(of[b][t], obr[b][L-1-t])
+ * in the output layout of *BidirectionalApplyDevice: rows t >= L exact zeros, x[b][t >= L] influences nothing (it may hold NaN); without
+ * return_sequences out[b] = merge(of[b], obr[b]).  Each direction takes the kernel its unidirectional call takes;
+ * nntk_hip_last_recurrent_kernel() names the backward direction's (it ran last).  xr lives in the backward handle until its next forward call;
+ * d_input must stay valid until the gradient call.  The forward handle remembers merge and the lengths.
+ * Gradient: bit for bit bd_merge_gradient_varlen_device(d_dout -> d_of, d_obr), *CalculateGradientDeviceVarLen(forward, d_grad_forward, dXf,
+ * d_of) and (backward, d_grad_backward, dXbr, d_obr) without state gradients, bd_accumulate_d_x_varlen_device(dXf, dXbr -> d_dX).
+ * d_grad_* (W | U | b_i | b_h of each direction) are ADDED to, d_dX [B][T][in] is written (exact zeros for t >= L), d_dout[b][t >= L] is
+ * ignored.  The blocks' bits are the recipe's for blocks that enter the call zeroed (what nntk_optimizer_step_device with zero_gradients
+ * leaves).  Onto a block that is not zero the call adds its whole gradient in ONE f32 add per element -- a second call onto the same block
+ * gives exactly twice the first -- where the unidirectional call adds its row slices one by one, so there the last bits may differ from
+ * the recipe's.  All scratch lives in the two handles, reserved on first use.
+ * -1 and nntk_last_error(), before anything is enqueued and with nothing written or remembered: a NULL handle or pointer, an inference
+ * handle, the same handle twice, handles that differ in a size above, a length outside [0, T], an unknown merge, (device form) an output
+ * that overlaps the input; for the gradient call also: (device form) d_grad_forward, d_grad_backward and d_dX overlapping one another; no bidirectional forward call on this pair, in this order, since either handle's
+ * last forward call. */
+int GRUBidirectionalApplyTrainingBatchDevice(GRU forward, GRU backward, const float *d_input /*[B,T,in]*/, float *d_output,
+                                             const int *lengths /*host [B] or NULL*/, int merge);
+int LSTMBidirectionalApplyTrainingBatchDevice(LSTM forward, LSTM backward, const float *d_input, float *d_output, const int *lengths, int merge);
+int RNNBidirectionalApplyTrainingBatchDevice(RNN forward, RNN backward, const float *d_input, float *d_output, const int *lengths, int merge);
+int GRUBidirectionalCalculateGradientDevice(GRU forward, GRU backward, float *d_grad_forward, float *d_grad_backward, float *d_dX /*[B,T,in]*/,
+                                            const float *d_dout);
+int LSTMBidirectionalCalculateGradientDevice(LSTM forward, LSTM backward, float *d_grad_forward, float *d_grad_backward, float *d_dX,
+                                             const float *d_dout);
+int RNNBidirectionalCalculateGradientDevice(RNN forward, RNN backward, float *d_grad_forward, float *d_grad_backward, float *d_dX,
+                                            const float *d_dout);
+/* the same on host memory (upload, device call, download).  The blocks d_W | d_U | d_b_i | d_b_h of the two gradients are accumulated as
+ * *CalculateGradient does; the layer's input gradient goes to d_X [B][T][in] (the d_X fields of the two gradients are not written) */
+int GRUBidirectionalApplyTrainingBatch(GRU forward, GRU backward, const float *input, float *output, const int *lengths, int merge);
+int LSTMBidirectionalApplyTrainingBatch(LSTM forward, LSTM backward, const float *input, float *output, const int *lengths, int merge);
+int RNNBidirectionalApplyTrainingBatch(RNN forward, RNN backward, const float *input, float *output, const int *lengths, int merge);
+int GRUBidirectionalCalculateGradient(GRU forward, GRU backward, GRUGradient *grad_forward, GRUGradient *grad_backward, float *d_X,
+                                      const float *d_out);
+int LSTMBidirectionalCalculateGradient(LSTM forward, LSTM backward, LSTMGradient *grad_forward, LSTMGradient *grad_backward, float *d_X,
+                                       const float *d_out);
+int RNNBidirectionalCalculateGradient(RNN forward, RNN backward, RNNGradient *grad_forward, RNNGradient *grad_backward, float *d_X,
+                                      const float *d_out);
 /* ---- frag3 tensors: activations already split for the split-bf16 x 3 contraction ---------------------------------------------
  * The default contraction of conv / dense / recurrent layers multiplies every f32 operand as three bf16 terms (x = hi + mid + lo,
  * exactly).  A FRAG3 tensor is a [batch][T][C] f32 tensor stored as those three images in MFMA fragment order:

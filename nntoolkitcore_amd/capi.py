@@ -395,6 +395,24 @@ SIGNATURES = {
     "GRUBidirectionalApplyInferenceBatch": (C.c_int, [vp, vp, fp, fp, C.c_int, ip, C.c_int]),
     "LSTMBidirectionalApplyInferenceBatch": (C.c_int, [vp, vp, fp, fp, C.c_int, ip, C.c_int]),
     "RNNBidirectionalApplyInferenceBatch": (C.c_int, [vp, vp, fp, fp, C.c_int, ip, C.c_int]),
+    # training a bidirectional layer: device forms of the gradient helpers, then the layer calls (device forms, host forms)
+    "bd_merge_concat_gradient_device": (C.c_int, [vp, vp, vp, RecurrentConfig, C.c_int]),
+    "bd_merge_sum_gradient_device": (C.c_int, [vp, vp, vp, RecurrentConfig, C.c_int]),
+    "bd_accumulate_d_x_device": (C.c_int, [vp, vp, vp, RecurrentConfig, C.c_int]),
+    "bd_merge_gradient_varlen_device": (C.c_int, [vp, vp, vp, RecurrentConfig, C.c_int, ip, C.c_int]),
+    "bd_accumulate_d_x_varlen_device": (C.c_int, [vp, vp, vp, RecurrentConfig, C.c_int, ip]),
+    "GRUBidirectionalApplyTrainingBatchDevice": (C.c_int, [vp, vp, vp, vp, ip, C.c_int]),
+    "LSTMBidirectionalApplyTrainingBatchDevice": (C.c_int, [vp, vp, vp, vp, ip, C.c_int]),
+    "RNNBidirectionalApplyTrainingBatchDevice": (C.c_int, [vp, vp, vp, vp, ip, C.c_int]),
+    "GRUBidirectionalCalculateGradientDevice": (C.c_int, [vp, vp, vp, vp, vp, vp]),
+    "LSTMBidirectionalCalculateGradientDevice": (C.c_int, [vp, vp, vp, vp, vp, vp]),
+    "RNNBidirectionalCalculateGradientDevice": (C.c_int, [vp, vp, vp, vp, vp, vp]),
+    "GRUBidirectionalApplyTrainingBatch": (C.c_int, [vp, vp, fp, fp, ip, C.c_int]),
+    "LSTMBidirectionalApplyTrainingBatch": (C.c_int, [vp, vp, fp, fp, ip, C.c_int]),
+    "RNNBidirectionalApplyTrainingBatch": (C.c_int, [vp, vp, fp, fp, ip, C.c_int]),
+    "GRUBidirectionalCalculateGradient": (C.c_int, [vp, vp, C.POINTER(RecurrentGradient), C.POINTER(RecurrentGradient), fp, fp]),
+    "LSTMBidirectionalCalculateGradient": (C.c_int, [vp, vp, C.POINTER(RecurrentGradient), C.POINTER(RecurrentGradient), fp, fp]),
+    "RNNBidirectionalCalculateGradient": (C.c_int, [vp, vp, C.POINTER(RecurrentGradient), C.POINTER(RecurrentGradient), fp, fp]),
     "DenseApplyDevice": (C.c_int, [vp, vp, vp, C.c_int]),
     "TimeDistributedDenseApplyDevice": (C.c_int, [vp, vp, vp, C.c_int]),
     # streaming a whole stack (INTEGRATION.md "Streaming a whole stack")

@@ -217,6 +217,17 @@ int nntk_shim_add2(const float *d_a, const float *d_b, float *d_out, long n);
 int nntk_shim_dft_twiddles(float *d_tw, int n);
 int nntk_shim_dft(const float *d_re, const float *d_im, const float *d_tw, float *d_ore, float *d_oim, int n, int inverse);
 int nntk_shim_split2(const float *d_in, float *d_a, float *d_b, long rows, int C);
+/* ---- bidirectional training (bd_train.hip): the merge, the output-gradient scatter and the input-gradient sum, each with the per-row time
+ *      reversal folded in.  d_len [B] on the device or NULL (every row T); L = its entry.  Rows t >= L are written as exact zeros whatever
+ *      the inputs hold there.  Without return_sequences a row is one step and nothing is reversed.  -1 when an output overlaps an input.
+ *      merge:      out[b][t] = merge(of[b][t], obr[b][L-1-t]); concat: [.., 2H], forward in [0, H); else of + obr, [.., H]
+ *      scatter:    d_of[b][t] = dout[b][t][forward part], d_ob[b][t] = dout[b][reverse ? L-1-t : t][backward part] (sum merge: both whole rows)
+ *      accumulate: dx[b][t] = dxf[b][t] + dxbr[b][L-1-t]   (d_dx may be d_dxf) ---- */
+int nntk_shim_bd_merge(const float *d_of, const float *d_obr, float *d_out, const int *d_len, long B, int T, int H,
+                       int return_sequences, int concat);
+int nntk_shim_bd_scatter(const float *d_dout, float *d_of, float *d_ob, const int *d_len, long B, int T, int H,
+                         int return_sequences, int concat, int reverse);
+int nntk_shim_bd_accumulate(const float *d_dxf, const float *d_dxbr, float *d_dx, const int *d_len, long B, int T, int F);
 
 /* ---- K4: recurrent layers -------------------------------------------------
  * d_xw   [T, B, G*H] time-major input projections INCLUDING b_i (from nntk_shim_conv1d out_mode 1)

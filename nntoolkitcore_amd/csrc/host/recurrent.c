@@ -93,6 +93,14 @@ typedef struct {
     nntk_devbuf d_st;            /* host-memory forms: h0 | c0 | hT | cT | d_hT | d_cT | d_h0 | d_c0, [B][H] each */
     nntk_devbuf d_yo;            /* host-memory forms: the forward output */
     float *want_hT, *want_cT;    /* the forward call's final-state tensors, for a forward kernel that writes them itself (cleared when it did) */
+    /* the bidirectional training calls: what this handle was in the last forward (0: none or a unidirectional forward since; 1 the forward,
+     * 2 the backward direction), the other direction's handle and -- on the forward handle -- the merge */
+    int bd_role, bd_merge;
+    const void *bd_peer;
+    nntk_devbuf d_bd_o, d_bd_do, d_bd_dx;      /* this direction's output, its output gradient, its input gradient */
+    nntk_devbuf d_bd_g;          /* this direction's weight gradient of one call (W | U | b_i | b_h), before it is added onto the caller's block */
+    nntk_devbuf d_bd_xr;         /* backward handle: the input reversed per row, kept for the gradient call */
+    nntk_devbuf d_bd_host;       /* forward handle, host-memory forms: the merged output; d_dout | d_dX */
 } rec_train;
 
 /* One recurrent layer of any cell: what every internal routine takes.  The three public handle types are this layout. */
@@ -218,6 +226,8 @@ static void train_free(rec_train *t) {
     nntk_devbuf_free(&t->d_grad); nntk_devbuf_free(&t->d_scr); nntk_devbuf_free(&t->d_dout); nntk_devbuf_free(&t->d_dX);
     nntk_devbuf_free(&t->d_len); nntk_devbuf_free(&t->d_xm); nntk_devbuf_free(&t->d_s0); nntk_devbuf_free(&t->d_st);
     nntk_devbuf_free(&t->d_yo);
+    nntk_devbuf_free(&t->d_bd_o); nntk_devbuf_free(&t->d_bd_do); nntk_devbuf_free(&t->d_bd_dx); nntk_devbuf_free(&t->d_bd_xr);
+    nntk_devbuf_free(&t->d_bd_host); nntk_devbuf_free(&t->d_bd_g);
 }
 
 /* a handle of G gates over the caller's n_act activation handles (which stay the caller's: gru.c:116-126); NULL = error */
@@ -797,6 +807,7 @@ static int train_vl_active(const nntk_train_vl *vl) { return vl && (vl->d_len ||
  * the padding steps cleared (they may hold NaN) */
 static const float *train_vl_begin(rec_train *t, const nntk_train_vl *vl, const float *d_x, int B, int T, int in) {
     t->have_batch = 0;           /* until this forward has been enqueued whole: a gradient call must not pair new lengths with old caches */
+    t->bd_role = 0;              /* (a bidirectional forward sets it again once both directions are enqueued) */
     memset(&t->vl, 0, sizeof t->vl);
     if (!vl) return d_x;
     t->vl.d_len = vl->d_len; t->vl.max_len = vl->max_len; t->vl.d_h0 = vl->d_h0; t->vl.d_c0 = vl->d_c0;
@@ -1188,6 +1199,60 @@ void bd_merge_sum(const float *forward_result, const float *backward_result, flo
     bd_merge_host(forward_result, backward_result, output, config, batch, 0);
 }
 
+/* ---- device forms of the gradient helpers: thin wrappers over bd_train.hip.  The fixed-length ones keep the reference's contract
+ * (d_backward is NOT reversed: bidirectional.c:58-74, :87-97; the reversal happens in bd_accumulate_d_x, :99-108) and return the bits of
+ * the host forms above; the varlen ones serve ragged rows (lengths: host memory, NULL = every row T) and hand the backward direction its
+ * gradient already reversed per row, zeros past a row's length. ---- */
+static int bd_grad_args(const char *who, const void *a, const void *b, const void *c, int batch) {
+    nntk_shim_clear_error();
+    if (batch < 0) return rec_fail(who, "batch %d < 0", batch);
+    if (batch > 0 && (!a || !b || !c)) return rec_fail(who, "NULL argument");
+    return 0;
+}
+/* the row lengths on the device, in the calling thread's scratch: 0 and *d_len (NULL without lengths), or -1 */
+static int bd_stage_lengths(const char *who, const int *lengths, int batch, int T, const int **d_len) {
+    *d_len = NULL;
+    if (nntk_check_lengths(who, lengths, batch, T, NULL, NULL)) return -1;
+    if (!lengths || batch == 0) return 0;
+    int *d = (int *)nntk_devbuf_reserve(&g_bd_len, (size_t)batch);
+    if (!d || nntk_shim_upload_ints(d, lengths, batch)) return -1;
+    *d_len = d;
+    return 0;
+}
+int bd_merge_concat_gradient_device(const float *d_dout, float *d_forward, float *d_backward, RecurrentConfig config, int batch) {
+    if (bd_grad_args("bd_merge_concat_gradient_device", d_dout, d_forward, d_backward, batch)) return -1;
+    return nntk_shim_bd_scatter(d_dout, d_forward, d_backward, NULL, batch, config.timesteps, config.output_feature_channels,
+                                config.return_sequences ? 1 : 0, 1, 0);
+}
+int bd_merge_sum_gradient_device(const float *d_dout, float *d_forward, float *d_backward, RecurrentConfig config, int batch) {
+    if (bd_grad_args("bd_merge_sum_gradient_device", d_dout, d_forward, d_backward, batch)) return -1;
+    return nntk_shim_bd_scatter(d_dout, d_forward, d_backward, NULL, batch, config.timesteps, config.output_feature_channels,
+                                config.return_sequences ? 1 : 0, 0, 0);
+}
+int bd_accumulate_d_x_device(const float *d_forward_dx, const float *d_backward_dx, float *d_output, RecurrentConfig config, int batch) {
+    if (bd_grad_args("bd_accumulate_d_x_device", d_forward_dx, d_backward_dx, d_output, batch)) return -1;
+    return nntk_shim_bd_accumulate(d_forward_dx, d_backward_dx, d_output, NULL, batch, config.timesteps, config.input_feature_channels);
+}
+int bd_merge_gradient_varlen_device(const float *d_dout, float *d_forward, float *d_backward_reversed, RecurrentConfig config, int batch,
+                                    const int *lengths, int merge) {
+    const char *who = "bd_merge_gradient_varlen_device";
+    if (bd_grad_args(who, d_dout, d_forward, d_backward_reversed, batch)) return -1;
+    if (merge != NNTK_BD_MERGE_CONCAT && merge != NNTK_BD_MERGE_SUM)
+        return rec_fail(who, "merge %d is neither NNTK_BD_MERGE_CONCAT nor NNTK_BD_MERGE_SUM", merge);
+    const int *d_len;
+    if (bd_stage_lengths(who, lengths, batch, config.timesteps, &d_len)) return -1;
+    return nntk_shim_bd_scatter(d_dout, d_forward, d_backward_reversed, d_len, batch, config.timesteps, config.output_feature_channels,
+                                config.return_sequences ? 1 : 0, merge == NNTK_BD_MERGE_CONCAT, 1);
+}
+int bd_accumulate_d_x_varlen_device(const float *d_forward_dx, const float *d_backward_dx, float *d_output, RecurrentConfig config, int batch,
+                                    const int *lengths) {
+    const char *who = "bd_accumulate_d_x_varlen_device";
+    if (bd_grad_args(who, d_forward_dx, d_backward_dx, d_output, batch)) return -1;
+    const int *d_len;
+    if (bd_stage_lengths(who, lengths, batch, config.timesteps, &d_len)) return -1;
+    return nntk_shim_bd_accumulate(d_forward_dx, d_backward_dx, d_output, d_len, batch, config.timesteps, config.input_feature_channels);
+}
+
 /* ============================ bidirectional layers in one call ======================== */
 /* *BidirectionalApplyDevice (include/nntoolkitcore_hip.h): the result of the composed recipe -- reverse x per row, run each direction from
  * zero state, reverse the backward sequence output per row, merge -- bit for bit, on one of two routes:
@@ -1301,6 +1366,145 @@ static int core_apply_bd_host(rec_layer *lf, rec_layer *lb, const char *who, con
     const dev_call k = { .run = run_apply_bd, .l = lf, .l2 = lb, .who = who, .B = B, .lengths = lengths, .merge = merge };
     const host_input in = { input, d_in, n_in };
     return host_round_trip(&k, &in, 1, d_out, output, n_out, 1);
+}
+
+/* ============================ bidirectional layers: training ======================== */
+/* *BidirectionalApplyTrainingBatch[Device] / *BidirectionalCalculateGradient[Device] (include/nntoolkitcore_hip.h): the composed recipe on
+ * two *CreateForTraining handles, bit for bit -- each direction IS its unidirectional *VarLen training call from zero state (train_apply_vl_dev
+ * / train_gradient_vl_dev: same router, same kernels, same caches), and what lies around them is one pass each of bd_train.hip: the merge
+ * with the backward output's reversal folded in, the scatter of d_out into both directions' output gradients, the sum of their input
+ * gradients.  Each handle owns its direction's scratch (rec_train d_bd_*); the backward handle keeps x reversed per row, which its
+ * gradient call reads.  Everything that can fail is checked before anything is enqueued or remembered. */
+
+/* the pair itself: two different training handles of one shape */
+static int bd_train_pair(const rec_layer *lf, const rec_layer *lb, const char *who) {
+    const rec_core *f = &lf->core, *b = &lb->core;
+    if (lf == lb) return rec_fail(who, "the same handle was passed for both directions (one handle holds one set of training caches)");
+    if (!lf->train.on || !lb->train.on) return rec_fail(who, "the %s handle was created for inference", lf->train.on ? "backward" : "forward");
+    if (f->G != b->G || f->in != b->in || f->H != b->H || f->T != b->T || f->return_sequences != b->return_sequences ||
+        lf->train.mini_batch != lb->train.mini_batch)
+        return rec_fail(who, "the two directions differ in input size, hidden size, timesteps, return_sequences or mini_batch_size");
+    return 0;
+}
+static int bd_train_forward_check(rec_layer *lf, rec_layer *lb, const char *who, const float *in, const float *out, const int *lengths,
+                                  int merge, int dev) {
+    if (bd_train_pair(lf, lb, who)) return -1;
+    if (merge != NNTK_BD_MERGE_CONCAT && merge != NNTK_BD_MERGE_SUM)
+        return rec_fail(who, "merge %d is neither NNTK_BD_MERGE_CONCAT nor NNTK_BD_MERGE_SUM", merge);
+    const rec_core *f = &lf->core;
+    const int B = lf->train.mini_batch, T = f->T;
+    if (nntk_check_lengths(who, lengths, B, T, NULL, NULL)) return -1;
+    if (B <= 0 || T <= 0) return 0;
+    if (!in || !out) return rec_fail(who, "NULL input or output");
+    const size_t W = merge == NNTK_BD_MERGE_CONCAT ? 2 * (size_t)f->H : (size_t)f->H;
+    const size_t n_in = (size_t)B * T * f->in, n_out = (size_t)B * (f->return_sequences ? (size_t)T : 1) * W;
+    if (dev && (const char *)in < (const char *)(out + n_out) && (const char *)out < (const char *)(in + n_in))
+        return rec_fail(who, "the output buffer overlaps the input");
+    return layer_acts(lf) || layer_acts(lb) ? -1 : 0;
+}
+/* (after bd_train_forward_check) */
+static int bd_train_forward_run(rec_layer *lf, rec_layer *lb, const char *who, const float *d_in, float *d_out, const int *lengths, int merge) {
+    rec_core *f = &lf->core;
+    rec_train *tf = &lf->train, *tb = &lb->train;
+    const int B = tf->mini_batch, T = f->T, in = f->in, H = f->H, rs = f->return_sequences ? 1 : 0;
+    if (B <= 0 || T <= 0) return 0;
+    const size_t n_in = (size_t)B * T * in, n_dir = (size_t)B * (rs ? (size_t)T : 1) * H;
+    float *of = nntk_devbuf_reserve(&tf->d_bd_o, n_dir), *obr = nntk_devbuf_reserve(&tb->d_bd_o, n_dir);
+    float *xr = nntk_devbuf_reserve(&tb->d_bd_xr, n_in);
+    if (!of || !obr || !xr) return -1;
+    /* the forward direction first: it stages the lengths on the device, which the reversal and the merge read as well */
+    if (train_apply_vl_dev(lf, who, d_in, of, lengths, NULL, NULL, NULL, NULL)) return -1;
+    const int *d_len = tf->vl.d_len;
+    if (d_len ? nntk_shim_reverse_time_varlen(d_in, xr, d_len, B, T, in) : nntk_shim_reverse_time(d_in, xr, B, T, in)) return -1;
+    if (train_apply_vl_dev(lb, who, xr, obr, lengths, NULL, NULL, NULL, NULL)) return -1;
+    if (nntk_shim_bd_merge(of, obr, d_out, d_len, B, T, H, rs, merge == NNTK_BD_MERGE_CONCAT)) return -1;
+    tf->bd_role = 1; tf->bd_peer = lb; tf->bd_merge = merge;
+    tb->bd_role = 2; tb->bd_peer = lf;
+    return 0;
+}
+static int bd_train_forward_dev(rec_layer *lf, rec_layer *lb, const char *who, const float *d_in, float *d_out, const int *lengths, int merge) {
+    if (bd_train_forward_check(lf, lb, who, d_in, d_out, lengths, merge, 1)) return -1;
+    return bd_train_forward_run(lf, lb, who, d_in, d_out, lengths, merge);
+}
+static int bd_train_forward_host(rec_layer *lf, rec_layer *lb, const char *who, const float *input, float *output, const int *lengths, int merge) {
+    if (bd_train_forward_check(lf, lb, who, input, output, lengths, merge, 0)) return -1;
+    rec_core *f = &lf->core;
+    const int B = lf->train.mini_batch, T = f->T;
+    if (B <= 0 || T <= 0) return 0;
+    const size_t W = merge == NNTK_BD_MERGE_CONCAT ? 2 * (size_t)f->H : (size_t)f->H;
+    const size_t n_in = (size_t)B * T * f->in, n_out = (size_t)B * (f->return_sequences ? (size_t)T : 1) * W;
+    float *d_x = nntk_devbuf_reserve(&lf->train.d_x, n_in), *d_out = nntk_devbuf_reserve(&lf->train.d_bd_host, n_out);
+    if (!d_x || !d_out) return -1;
+    if (nntk_shim_upload(d_x, input, n_in * sizeof(float))) return -1;
+    if (bd_train_forward_run(lf, lb, who, d_x, d_out, lengths, merge)) return -1;
+    return nntk_shim_download(output, d_out, n_out * sizeof(float));
+}
+
+/* the gradient call's pair: the handles of the last bidirectional forward, in its order, neither used for another forward since */
+static int bd_train_gradient_check(rec_layer *lf, rec_layer *lb, const char *who) {
+    if (bd_train_pair(lf, lb, who)) return -1;
+    const rec_train *tf = &lf->train, *tb = &lb->train;
+    if (!tf->have_batch || !tb->have_batch || tf->bd_role != 1 || tb->bd_role != 2 || tf->bd_peer != lb || tb->bd_peer != lf)
+        return rec_fail(who, "run the bidirectional forward call on this pair of handles (forward, backward) first");
+    return layer_acts(lf) || layer_acts(lb) ? -1 : 0;
+}
+/* d_gf / d_gb: the directions' blocks W | U | b_i | b_h, ADDED to; d_dX [B][T][in] written; d_dout in the forward call's output layout */
+static int bd_train_gradient_run(rec_layer *lf, rec_layer *lb, const char *who, float *d_gf, float *d_gb, float *d_dX, const float *d_dout) {
+    rec_core *f = &lf->core;
+    rec_train *tf = &lf->train, *tb = &lb->train;
+    const int B = tf->mini_batch, T = f->T, in = f->in, H = f->H, rs = f->return_sequences ? 1 : 0;
+    if (B <= 0 || T <= 0) return 0;
+    const size_t n_in = (size_t)B * T * in, n_dir = (size_t)B * (rs ? (size_t)T : 1) * H;
+    float *dof = nntk_devbuf_reserve(&tf->d_bd_do, n_dir), *dob = nntk_devbuf_reserve(&tb->d_bd_do, n_dir);
+    float *dxf = nntk_devbuf_reserve(&tf->d_bd_dx, n_in), *dxb = nntk_devbuf_reserve(&tb->d_bd_dx, n_in);
+    if (!dof || !dob || !dxf || !dxb) return -1;
+    /* Each direction's gradient is summed into a zeroed block of the handle's own and reaches the caller's block in ONE f32 add per element:
+     * onto a zeroed block that is, bit for bit, what *CalculateGradientDeviceVarLen leaves there (it adds its row slices one by one onto
+     * the block: zero + the same slices in the same order), and a second call onto the same block gives exactly twice the first. */
+    const size_t nblk = (size_t)in * f->G * H + (size_t)H * f->G * H + 2 * (size_t)f->G * H;
+    float *gf = nntk_devbuf_reserve(&tf->d_bd_g, nblk), *gb = nntk_devbuf_reserve(&tb->d_bd_g, nblk);
+    if (!gf || !gb) return -1;
+    const int *d_len = tf->vl.d_len;
+    if (nntk_shim_bd_scatter(d_dout, dof, dob, d_len, B, T, H, rs, tf->bd_merge == NNTK_BD_MERGE_CONCAT, 1)) return -1;
+    if (nntk_shim_memset(gf, 0, nblk * sizeof(float)) || nntk_shim_memset(gb, 0, nblk * sizeof(float))) return -1;
+    if (train_gradient_vl_dev(lf, who, gf, dxf, dof, NULL, NULL, NULL, NULL)) return -1;
+    if (train_gradient_vl_dev(lb, who, gb, dxb, dob, NULL, NULL, NULL, NULL)) return -1;
+    if (nntk_shim_add_into(d_gf, gf, (long)nblk) || nntk_shim_add_into(d_gb, gb, (long)nblk)) return -1;
+    return nntk_shim_bd_accumulate(dxf, dxb, d_dX, d_len, B, T, in);
+}
+static int bd_train_gradient_dev(rec_layer *lf, rec_layer *lb, const char *who, float *d_gf, float *d_gb, float *d_dX, const float *d_dout) {
+    if (bd_train_gradient_check(lf, lb, who)) return -1;
+    if (!d_gf || !d_gb || !d_dX || !d_dout) return rec_fail(who, "NULL argument");
+    /* the two blocks and d_dX are written by different kernels of the call: one tensor in two roles would be added to twice or overwritten */
+    const rec_core *f = &lf->core;
+    const size_t nblk = (size_t)f->in * f->G * f->H + (size_t)f->H * f->G * f->H + 2 * (size_t)f->G * f->H;
+    const size_t n_in = (size_t)(lf->train.mini_batch > 0 ? lf->train.mini_batch : 0) * (f->T > 0 ? f->T : 0) * f->in;
+    if ((d_gf < d_gb + nblk && d_gb < d_gf + nblk) || (d_dX < d_gf + nblk && d_gf < d_dX + n_in) || (d_dX < d_gb + nblk && d_gb < d_dX + n_in))
+        return rec_fail(who, "the gradient blocks and d_dX overlap");
+    return bd_train_gradient_run(lf, lb, who, d_gf, d_gb, d_dX, d_dout);
+}
+/* host-memory form: the two gradient blocks go up, are added to and come down as *CalculateGradient's does; the layer's d_X [B][T][in] is
+ * the caller's tensor (the blocks' own d_X fields are not written) */
+static int bd_train_gradient_host(rec_layer *lf, rec_layer *lb, const char *who, RecurrentGradient *gf, RecurrentGradient *gb, float *d_X,
+                                  const float *d_out) {
+    if (bd_train_gradient_check(lf, lb, who)) return -1;
+    if (!gf || !gb || !d_X || !d_out) return rec_fail(who, "NULL argument");
+    rec_core *f = &lf->core;
+    rec_train *tf = &lf->train, *tb = &lb->train;
+    const int B = tf->mini_batch, T = f->T, in = f->in, H = f->H, G = f->G;
+    if (B <= 0 || T <= 0) return 0;
+    const size_t nblk = (size_t)in * G * H + (size_t)H * G * H + 2 * (size_t)G * H, n_in = (size_t)B * T * in;
+    const size_t n_do = (size_t)B * (f->return_sequences ? (size_t)T : 1) * (tf->bd_merge == NNTK_BD_MERGE_CONCAT ? 2 * (size_t)H : (size_t)H);
+    const size_t n_do4 = (n_do + 3) & ~(size_t)3;           /* d_dX behind it stays 16-byte aligned */
+    float *d_dout = nntk_devbuf_reserve(&tf->d_bd_host, n_do4 + n_in);
+    float *d_gf = nntk_devbuf_reserve(&tf->d_grad, nblk), *d_gb = nntk_devbuf_reserve(&tb->d_grad, nblk);
+    if (!d_dout || !d_gf || !d_gb) return -1;
+    float *d_dX = d_dout + n_do4;
+    if (nntk_shim_upload(d_dout, d_out, n_do * sizeof(float))) return -1;
+    if (nntk_shim_upload(d_gf, gf->d_W, nblk * sizeof(float)) || nntk_shim_upload(d_gb, gb->d_W, nblk * sizeof(float))) return -1;   /* contiguous blocks */
+    if (bd_train_gradient_run(lf, lb, who, d_gf, d_gb, d_dX, d_dout)) return -1;
+    if (nntk_shim_download(gf->d_W, d_gf, nblk * sizeof(float)) || nntk_shim_download(gb->d_W, d_gb, nblk * sizeof(float))) return -1;
+    return nntk_shim_download(d_X, d_dX, n_in * sizeof(float));
 }
 
 /* ======================= entry-point bodies of all cells ==================== */
@@ -1485,6 +1689,23 @@ int GRUApplyTrainingBatchVarLen(GRU filter, const float *input, float *output, c
 int GRUCalculateGradientVarLen(GRU filter, GRUGradient *gradient, const float *d_out, const float *d_hT_grad, float *d_h0_grad) {
     REC_ENTER("GRUCalculateGradientVarLen", filter);
     return train_gradient_vl_host(&filter->l, "GRUCalculateGradientVarLen", gradient, d_out, d_hT_grad, NULL, d_h0_grad, NULL);
+}
+/* the bidirectional training calls (bd_train_*): forward / backward are two different GRUCreateForTraining handles of one shape */
+int GRUBidirectionalApplyTrainingBatchDevice(GRU forward, GRU backward, const float *d_input, float *d_output, const int *lengths, int merge) {
+    REC_ENTER("GRUBidirectionalApplyTrainingBatchDevice", forward && backward);
+    return bd_train_forward_dev(&forward->l, &backward->l, "GRUBidirectionalApplyTrainingBatchDevice", d_input, d_output, lengths, merge);
+}
+int GRUBidirectionalCalculateGradientDevice(GRU forward, GRU backward, float *d_grad_forward, float *d_grad_backward, float *d_dX, const float *d_dout) {
+    REC_ENTER("GRUBidirectionalCalculateGradientDevice", forward && backward);
+    return bd_train_gradient_dev(&forward->l, &backward->l, "GRUBidirectionalCalculateGradientDevice", d_grad_forward, d_grad_backward, d_dX, d_dout);
+}
+int GRUBidirectionalApplyTrainingBatch(GRU forward, GRU backward, const float *input, float *output, const int *lengths, int merge) {
+    REC_ENTER("GRUBidirectionalApplyTrainingBatch", forward && backward);
+    return bd_train_forward_host(&forward->l, &backward->l, "GRUBidirectionalApplyTrainingBatch", input, output, lengths, merge);
+}
+int GRUBidirectionalCalculateGradient(GRU forward, GRU backward, GRUGradient *grad_forward, GRUGradient *grad_backward, float *d_X, const float *d_out) {
+    REC_ENTER("GRUBidirectionalCalculateGradient", forward && backward);
+    return bd_train_gradient_host(&forward->l, &backward->l, "GRUBidirectionalCalculateGradient", grad_forward, grad_backward, d_X, d_out);
 }
 
 /* ---- two stacked GRU layers in one persistent launch (BASELINE configs[3]; recurrent.hip gru2_persistent_kernel) ----
@@ -1793,6 +2014,23 @@ int LSTMCalculateGradientVarLen(LSTM filter, LSTMGradient *gradient, const float
     REC_ENTER("LSTMCalculateGradientVarLen", filter);
     return train_gradient_vl_host(&filter->l, "LSTMCalculateGradientVarLen", gradient, d_out, d_hT_grad, d_cT_grad, d_h0_grad, d_c0_grad);
 }
+/* the bidirectional training calls (bd_train_*): forward / backward are two different LSTMCreateForTraining handles of one shape */
+int LSTMBidirectionalApplyTrainingBatchDevice(LSTM forward, LSTM backward, const float *d_input, float *d_output, const int *lengths, int merge) {
+    REC_ENTER("LSTMBidirectionalApplyTrainingBatchDevice", forward && backward);
+    return bd_train_forward_dev(&forward->l, &backward->l, "LSTMBidirectionalApplyTrainingBatchDevice", d_input, d_output, lengths, merge);
+}
+int LSTMBidirectionalCalculateGradientDevice(LSTM forward, LSTM backward, float *d_grad_forward, float *d_grad_backward, float *d_dX, const float *d_dout) {
+    REC_ENTER("LSTMBidirectionalCalculateGradientDevice", forward && backward);
+    return bd_train_gradient_dev(&forward->l, &backward->l, "LSTMBidirectionalCalculateGradientDevice", d_grad_forward, d_grad_backward, d_dX, d_dout);
+}
+int LSTMBidirectionalApplyTrainingBatch(LSTM forward, LSTM backward, const float *input, float *output, const int *lengths, int merge) {
+    REC_ENTER("LSTMBidirectionalApplyTrainingBatch", forward && backward);
+    return bd_train_forward_host(&forward->l, &backward->l, "LSTMBidirectionalApplyTrainingBatch", input, output, lengths, merge);
+}
+int LSTMBidirectionalCalculateGradient(LSTM forward, LSTM backward, LSTMGradient *grad_forward, LSTMGradient *grad_backward, float *d_X, const float *d_out) {
+    REC_ENTER("LSTMBidirectionalCalculateGradient", forward && backward);
+    return bd_train_gradient_host(&forward->l, &backward->l, "LSTMBidirectionalCalculateGradient", grad_forward, grad_backward, d_X, d_out);
+}
 
 /* ================================= RNN ==================================== */
 /* layers/rnn.c.  One gate; the activation is the layer's single ActivationFunction (rnn.h:20-24), which must be
@@ -1904,4 +2142,21 @@ int RNNApplyTrainingBatchVarLen(RNN filter, const float *input, float *output, c
 int RNNCalculateGradientVarLen(RNN filter, RNNGradient *gradient, const float *d_out, const float *d_hT_grad, float *d_h0_grad) {
     REC_ENTER("RNNCalculateGradientVarLen", filter);
     return train_gradient_vl_host(&filter->l, "RNNCalculateGradientVarLen", gradient, d_out, d_hT_grad, NULL, d_h0_grad, NULL);
+}
+/* the bidirectional training calls (bd_train_*): forward / backward are two different RNNCreateForTraining handles of one shape */
+int RNNBidirectionalApplyTrainingBatchDevice(RNN forward, RNN backward, const float *d_input, float *d_output, const int *lengths, int merge) {
+    REC_ENTER("RNNBidirectionalApplyTrainingBatchDevice", forward && backward);
+    return bd_train_forward_dev(&forward->l, &backward->l, "RNNBidirectionalApplyTrainingBatchDevice", d_input, d_output, lengths, merge);
+}
+int RNNBidirectionalCalculateGradientDevice(RNN forward, RNN backward, float *d_grad_forward, float *d_grad_backward, float *d_dX, const float *d_dout) {
+    REC_ENTER("RNNBidirectionalCalculateGradientDevice", forward && backward);
+    return bd_train_gradient_dev(&forward->l, &backward->l, "RNNBidirectionalCalculateGradientDevice", d_grad_forward, d_grad_backward, d_dX, d_dout);
+}
+int RNNBidirectionalApplyTrainingBatch(RNN forward, RNN backward, const float *input, float *output, const int *lengths, int merge) {
+    REC_ENTER("RNNBidirectionalApplyTrainingBatch", forward && backward);
+    return bd_train_forward_host(&forward->l, &backward->l, "RNNBidirectionalApplyTrainingBatch", input, output, lengths, merge);
+}
+int RNNBidirectionalCalculateGradient(RNN forward, RNN backward, RNNGradient *grad_forward, RNNGradient *grad_backward, float *d_X, const float *d_out) {
+    REC_ENTER("RNNBidirectionalCalculateGradient", forward && backward);
+    return bd_train_gradient_host(&forward->l, &backward->l, "RNNBidirectionalCalculateGradient", grad_forward, grad_backward, d_X, d_out);
 }

@@ -305,11 +305,14 @@ class _Recurrent:
 
 
 class GRU(_Recurrent):
-    def __init__(self, in_features, hidden, return_sequences, timesteps, acts=None):
+    def __init__(self, in_features, hidden, return_sequences, timesteps, acts=None, mini_batch=None):
         L = capi.load()
         self.acts = L.GRUActivationsCreateDefault(hidden) if acts is None else acts
         self.cfg = L.GRUConfigCreate(in_features, hidden, return_sequences, timesteps, self.acts)
-        self.h = L.GRUCreateForInference(self.cfg)
+        # mini_batch: a *CreateForTraining handle of that mini-batch size (the training calls), else an inference handle
+        self.mini_batch = mini_batch
+        self.h = (L.GRUCreateForTraining(self.cfg, capi.ConvTrainingConfig(mini_batch)) if mini_batch else
+                  L.GRUCreateForInference(self.cfg))
         self._get_weights, self._apply, self._apply_batch = L.GRUGetWeights, L.GRUApplyInference, L.GRUApplyInferenceBatch
         self._apply_device, self._sync, self._reset = L.GRUApplyDevice, L.GRUSyncWeights, L.GRUResetState
         self._apply_device_vl, self._is_lstm = L.GRUApplyDeviceVarLen, False
@@ -433,11 +436,14 @@ def gru_stack2_apply(g1, g2, x):
 class RNN(_Recurrent):
     """One-gate recurrent layer (rnn.h); `act` is an ActivationFunction handle (default tanh over H)."""
 
-    def __init__(self, in_features, hidden, return_sequences, timesteps, v2=True, act=None):
+    def __init__(self, in_features, hidden, return_sequences, timesteps, v2=True, act=None, mini_batch=None):
         L = capi.load()
         self.act = L.ActivationFunctionCreateTanh(hidden) if act is None else act
         self.cfg = L.RNNConfigCreate(in_features, hidden, return_sequences, timesteps, v2, self.act)
-        self.h = L.RNNCreateForInference(self.cfg)
+        # mini_batch: a *CreateForTraining handle of that mini-batch size (the training calls), else an inference handle
+        self.mini_batch = mini_batch
+        self.h = (L.RNNCreateForTraining(self.cfg, capi.ConvTrainingConfig(mini_batch)) if mini_batch else
+                  L.RNNCreateForInference(self.cfg))
         self._get_weights, self._apply, self._apply_batch = L.RNNGetWeights, L.RNNApplyInference, L.RNNApplyInferenceBatch
         self._apply_device, self._sync, self._reset = L.RNNApplyDevice, L.RNNSyncWeights, L.RNNResetState
         self._apply_device_vl, self._is_lstm = L.RNNApplyDeviceVarLen, False
@@ -527,6 +533,34 @@ def bidirectional_apply(fwd, bwd, x, lengths=None, merge="concat"):
     return out
 
 
+def bidirectional_train_forward_device(fwd, bwd, x, lengths=None, merge="concat", out=None):
+    """``<Layer>BidirectionalApplyTrainingBatchDevice``: the training forward of a bidirectional layer in one call.  fwd, bwd: two
+    different layers of one kind created with ``mini_batch=B``; x [B,T,in] device tensor, which must stay alive until the backward call;
+    lengths: one per row, or None for all T; merge "concat" ([...,2H]) or "sum".  Rows past a length are zeros."""
+    kind = type(fwd).__name__
+    B, shape, m, lens, lp = _bd_args(fwd, x.shape, lengths, merge)
+    if B != fwd.mini_batch:
+        raise ValueError("%sBidirectionalApplyTrainingBatchDevice: x must hold the handles' mini_batch = %s rows" % (kind, fwd.mini_batch))
+    if out is None:
+        out = x.new_empty(shape)
+    name = kind + "BidirectionalApplyTrainingBatchDevice"
+    check(getattr(capi.load(), name)(fwd.h, bwd.h, _dp(x), _dp(out), lp, m), name)
+    return out
+
+
+def bidirectional_train_backward_device(fwd, bwd, dout, grad_fwd, grad_bwd, dX=None):
+    """``<Layer>BidirectionalCalculateGradientDevice`` after bidirectional_train_forward_device on the same pair: dout in the forward
+    call's output layout; grad_fwd / grad_bwd: device tensors of each direction's block W | U | b_i | b_h, ADDED to; returns dX [B,T,in]
+    (written; zeros past a row's length)."""
+    kind = type(fwd).__name__
+    base = fwd.cfg.base
+    if dX is None:
+        dX = dout.new_empty((fwd.mini_batch, base.timesteps, base.input_feature_channels))
+    name = kind + "BidirectionalCalculateGradientDevice"
+    check(getattr(capi.load(), name)(fwd.h, bwd.h, _dp(grad_fwd), _dp(grad_bwd), _dp(dX), _dp(dout)), name)
+    return dX
+
+
 def _ctc_labels(labels, label_lengths, B):
     """labels as a list of per-row lists, or a padded int array [B, max_label_len] plus label_lengths -> (int32 [B, maxL], int32 [B])"""
     if label_lengths is None:
@@ -608,11 +642,14 @@ def ctc_greedy_decode(probs, input_lengths=None, blank=0):
 
 
 class LSTM(_Recurrent):
-    def __init__(self, in_features, hidden, return_sequences, timesteps, v2=True, acts=None):
+    def __init__(self, in_features, hidden, return_sequences, timesteps, v2=True, acts=None, mini_batch=None):
         L = capi.load()
         self.acts = L.LSTMActivationsCreateDefault(hidden) if acts is None else acts
         self.cfg = L.LSTMConfigCreate(in_features, hidden, return_sequences, timesteps, v2, self.acts)
-        self.h = L.LSTMCreateForInference(self.cfg)
+        # mini_batch: a *CreateForTraining handle of that mini-batch size (the training calls), else an inference handle
+        self.mini_batch = mini_batch
+        self.h = (L.LSTMCreateForTraining(self.cfg, capi.ConvTrainingConfig(mini_batch)) if mini_batch else
+                  L.LSTMCreateForInference(self.cfg))
         self._get_weights, self._apply, self._apply_batch = L.LSTMGetWeights, L.LSTMApplyInference, L.LSTMApplyInferenceBatch
         self._apply_device, self._sync, self._reset = L.LSTMApplyDevice, L.LSTMSyncWeights, L.LSTMResetState
         self._apply_device_vl, self._is_lstm = L.LSTMApplyDeviceVarLen, True
