@@ -195,6 +195,22 @@ def _recipe(tw, x, dout, ln):
 def test_equals_the_composed_recipe_bit_for_bit(gpu, kind, merge, seq, B, T, n_in, H):
     """output, d_X and both gradient blocks (accumulated from zeros) equal the recipe on twin handles, ragged and with lengths = NULL; the
     host-memory forms equal the device forms"""
+    _assert_equals_the_recipe(kind, merge, seq, B, T, n_in, H)
+
+
+# bd_train.hip:97-102 (grid_for): at most 2048 workgroups of 256 lanes, one unit (V floats) per lane and trip
+BD_GRID_UNITS = 2048 * 256
+
+
+def test_merge_at_grid_stride_size_equals_the_composed_recipe(gpu):
+    """the forward merge kernel has no helper of its own: one bidirectional RNN layer (the cheapest cell) whose merged output has more
+    four-float units than the grid has lanes"""
+    B, T, n_in, H = 40, 131, 8, 404
+    assert H % 4 == 0 and 2 * B * T * H // 4 == 1_058_480 > BD_GRID_UNITS == 524_288       # bd_train.hip:129-130: V = 4, no / 4 units
+    _assert_equals_the_recipe("rnn", "concat", True, B, T, n_in, H)
+
+
+def _assert_equals_the_recipe(kind, merge, seq, B, T, n_in, H):
     import torch
     L = capi.load()
     p, tw = Pair(kind, B, T, n_in, H, seq, merge), Pair(kind, B, T, n_in, H, seq, merge)
@@ -493,6 +509,20 @@ def test_varlen_helpers_equal_their_formulas(gpu, B, T, n_in, H, merge, seq):
     """against the numpy statement, NaN in the ignored region, exact zeros past L; lengths NULL = every row T"""
     import torch
     L = capi.load()
+    cfg = capi.RecurrentConfig(n_in, H, seq, T)
+    _assert_varlen_helpers(B, T, n_in, H, merge, seq)
+    # refused before anything is written
+    ln = lengths_for(B, T, 5).copy()
+    ln[0] = T + 1
+    do = torch.full((B, T, n_in), SENTINEL, device="cuda")
+    assert L.bd_accumulate_d_x_varlen_device(dp(do), dp(do), dp(do), cfg, B, IP(ln)) == -1 and capi.last_error() != ""
+    assert L.bd_merge_gradient_varlen_device(dp(do), dp(do), dp(do), cfg, B, None, 3) == -1 and capi.last_error() != ""
+    assert bool((do == SENTINEL).all())
+
+
+def _assert_varlen_helpers(B, T, n_in, H, merge, seq, accumulate=True):
+    import torch
+    L = capi.load()
     r = np.random.default_rng(71)
     cfg = capi.RecurrentConfig(n_in, H, seq, T)
     Wd = 2 * H if merge == "concat" else H
@@ -504,27 +534,132 @@ def test_varlen_helpers_equal_their_formulas(gpu, B, T, n_in, H, merge, seq):
             dout[pad] = np.nan
         shape = (B, T, H) if seq else (B, H)
         df, db = torch.full(shape, SENTINEL, device="cuda"), torch.full(shape, SENTINEL, device="cuda")
-        assert L.bd_merge_gradient_varlen_device(dp(dev(dout)), dp(df), dp(db), cfg, B, IP(ln), MERGE[merge]) == 0, capi.last_error()
+        dd = dev(dout)                                   # (named: a temporary's memory would be free again before the call)
+        assert L.bd_merge_gradient_varlen_device(dp(dd), dp(df), dp(db), cfg, B, IP(ln), MERGE[merge]) == 0, capi.last_error()
         wf, wb = np_scatter(dout, ln, H, seq, merge)
         np.testing.assert_array_equal(df.cpu().numpy(), wf)
         np.testing.assert_array_equal(db.cpu().numpy(), wb)
         if seq:
             assert not df.cpu().numpy()[pad].any() and not db.cpu().numpy()[pad].any()
+        if not accumulate:
+            continue
         fx, bx = u(r, B, T, n_in), u(r, B, T, n_in)
         fx[pad] = np.nan
         bx[pad] = np.nan
         do = torch.full((B, T, n_in), SENTINEL, device="cuda")
-        assert L.bd_accumulate_d_x_varlen_device(dp(dev(fx)), dp(dev(bx)), dp(do), cfg, B, IP(ln)) == 0, capi.last_error()
+        dfx, dbx = dev(fx), dev(bx)
+        assert L.bd_accumulate_d_x_varlen_device(dp(dfx), dp(dbx), dp(do), cfg, B, IP(ln)) == 0, capi.last_error()
         got = do.cpu().numpy()
         np.testing.assert_array_equal(got, np_accumulate(fx, bx, ln))
         assert np.isfinite(got).all() and not got[pad].any()
-    # refused before anything is written
-    ln = lengths_for(B, T, 5).copy()
-    ln[0] = T + 1
+
+
+@pytest.mark.parametrize("width", [404, 403], ids=["V4", "V1"])
+@pytest.mark.parametrize("merge", ["concat", "sum"])
+def test_varlen_helpers_past_one_trip_of_the_grid(gpu, width, merge):
+    """more units than the grid has lanes: the second trip of the scatter's and the accumulation's grid-stride loops, in the four-float
+    form (width 404) and the scalar form (403), ragged and with lengths NULL.  The final-state scatter (seq = False) runs at the same
+    widths too; its 16,160 floats stay inside the first trip"""
+    B, T = 40, 131
+    n = B * T * width
+    if width % 4 == 0:
+        assert n == 2_116_960 and n // 4 == 529_240 > BD_GRID_UNITS          # bd_train.hip:145-146 and :160-161: V = 4, n / 4 units
+    else:
+        assert n > BD_GRID_UNITS                                              # bd_train.hip:149 and :163: V = 1, n units
+    _assert_varlen_helpers(B, T, width, width, merge, True)
+    _assert_varlen_helpers(B, T, width, width, merge, False, accumulate=False)
+
+
+def _off16(n, tail=0, fill=SENTINEL):
+    """a tensor of n floats that starts 4 bytes past a 16-byte boundary: (the view, its buffer with one word before and `tail` behind)"""
+    import torch
+    buf = torch.full((n + 1 + tail,), fill, device="cuda")
+    assert buf.data_ptr() % 16 == 0
+    view = buf[1:n + 1]
+    assert view.data_ptr() % 16 == 4
+    return view, buf
+
+
+def test_misaligned_pointers_at_widths_that_are_multiples_of_4(gpu):
+    """H = 12 and F = 8 would take the 16-byte form; at pointers 4 bytes past a 16-byte boundary the shim must fall back to the scalar one
+    (bd_train.hip:104, aligned16).  Same bits as the aligned call, and the words around the views keep their sentinels"""
+    import torch
+    L = capi.load()
+    B, T, n_in, H = 5, 7, 8, 12
+    assert H % 4 == 0 and n_in % 4 == 0
+    r = np.random.default_rng(81)
+    ln = lengths_for(B, T, 5)
+    pad = np.arange(T)[None, :] >= ln[:, None]
+    cfg = capi.RecurrentConfig(n_in, H, True, T)
+    for merge in ("concat", "sum"):
+        dout = u(r, B, T, 2 * H if merge == "concat" else H)
+        dout[pad] = np.nan
+        dd = torch.from_numpy(dout).cuda()
+        df, db = (torch.full((B, T, H), SENTINEL, device="cuda") for _ in range(2))
+        assert L.bd_merge_gradient_varlen_device(dp(dd), dp(df), dp(db), cfg, B, IP(ln), MERGE[merge]) == 0, capi.last_error()
+        (mdd, bdd), (mdf, bdf), (mdb, bdb) = _off16(dout.size), _off16(B * T * H, 1), _off16(B * T * H, 1)
+        mdd.copy_(dd.reshape(-1))
+        assert L.bd_merge_gradient_varlen_device(dp(mdd), dp(mdf), dp(mdb), cfg, B, IP(ln), MERGE[merge]) == 0, capi.last_error()
+        wf, wb = np_scatter(dout, ln, H, True, merge)
+        np.testing.assert_array_equal(df.cpu().numpy(), wf)
+        np.testing.assert_array_equal(db.cpu().numpy(), wb)
+        assert torch.equal(mdf, df.reshape(-1)) and torch.equal(mdb, db.reshape(-1)), merge
+        assert float(bdd[0]) == SENTINEL and all(float(b_[0]) == SENTINEL and float(b_[-1]) == SENTINEL for b_ in (bdf, bdb)), merge
+    fx, bx = u(r, B, T, n_in), u(r, B, T, n_in)
+    fx[pad] = np.nan
+    bx[pad] = np.nan
     do = torch.full((B, T, n_in), SENTINEL, device="cuda")
-    assert L.bd_accumulate_d_x_varlen_device(dp(do), dp(do), dp(do), cfg, B, IP(ln)) == -1 and capi.last_error() != ""
-    assert L.bd_merge_gradient_varlen_device(dp(do), dp(do), dp(do), cfg, B, None, 3) == -1 and capi.last_error() != ""
-    assert bool((do == SENTINEL).all())
+    dfx, dbx = torch.from_numpy(fx).cuda(), torch.from_numpy(bx).cuda()
+    assert L.bd_accumulate_d_x_varlen_device(dp(dfx), dp(dbx), dp(do), cfg, B, IP(ln)) == 0, capi.last_error()
+    (mfx, bfx), (mbx, bbx), (mdo, bdo) = _off16(fx.size), _off16(bx.size), _off16(fx.size, 1)
+    mfx.copy_(torch.from_numpy(fx).reshape(-1)); mbx.copy_(torch.from_numpy(bx).reshape(-1))
+    assert L.bd_accumulate_d_x_varlen_device(dp(mfx), dp(mbx), dp(mdo), cfg, B, IP(ln)) == 0, capi.last_error()
+    np.testing.assert_array_equal(do.cpu().numpy(), np_accumulate(fx, bx, ln))
+    assert torch.equal(mdo, do.reshape(-1))
+    assert float(bfx[0]) == SENTINEL and float(bbx[0]) == SENTINEL and float(bdo[0]) == SENTINEL and float(bdo[-1]) == SENTINEL
+    # the forward merge: its inputs are the handles' own scratch, the output is the caller's
+    for merge in ("concat", "sum"):
+        p = Pair("rnn", B, T, n_in, H, True, merge)
+        xd = torch.from_numpy(u(r, B, T, n_in)).cuda()
+        y = p.forward_dev(xd, ln)
+        my, by = _off16(y.numel(), 1)
+        p.forward_dev(xd, ln, out=my)
+        assert L.nntk_hip_synchronize() == 0
+        assert torch.equal(my, y.reshape(-1)) and float(by[0]) == SENTINEL and float(by[-1]) == SENTINEL, merge
+        p.close()
+
+
+def test_accumulate_with_64_bit_indices(gpu):
+    """2049 x 1024 x 1024 floats reach 2^31: the kernel<V, long> instantiation (bd_train.hip:111).  Small integers, so every sum is
+    exact; filled, run (over d_dxf, which the shim allows) and checked on the device in slices of 64 rows: 16 GiB at the peak"""
+    import torch
+    L = capi.load()
+    B, T, F = 2049, 1024, 1024
+    assert B * T * F == 2_148_532_224 >= 2 ** 31 and F % 4 == 0
+    ln = lengths_for(B, T, 13)
+    ln[-3:] = (T, 0, 1)                                   # (row 2048 is the one whose floats lie past 2^31)
+    assert tuple(ln[:3]) == (T, 0, 1)
+    dev = torch.device("cuda")
+    tt, ff = torch.arange(T, device=dev, dtype=torch.int32)[None, :, None], torch.arange(F, device=dev, dtype=torch.int32)[None, None, :]
+    fval = lambda bb, t_: ((bb * 3 + t_ * 5 + ff) % 17 - 8).float()
+    bval = lambda bb, t_: ((bb * 7 + t_ * 11 + ff * 3) % 19 - 9).float()
+    dxf, dxb = torch.empty((B, T, F), device=dev), torch.empty((B, T, F), device=dev)
+    lens = torch.from_numpy(ln).to(dev)
+    slices = [(b0, min(b0 + 64, B)) for b0 in range(0, B, 64)]
+    nan = torch.tensor(float("nan"), device=dev)
+    for b0, b1 in slices:
+        bb, live = torch.arange(b0, b1, device=dev, dtype=torch.int32)[:, None, None], tt < lens[b0:b1, None, None]
+        dxf[b0:b1] = torch.where(live, fval(bb, tt), nan)             # NaN in the ignored region
+        dxb[b0:b1] = torch.where(live, bval(bb, tt), nan)
+    cfg = capi.RecurrentConfig(F, F, True, T)
+    assert L.bd_accumulate_d_x_varlen_device(dp(dxf), dp(dxb), dp(dxf), cfg, B, IP(ln)) == 0, capi.last_error()
+    assert L.nntk_hip_synchronize() == 0
+    for b0, b1 in slices:
+        bb, Lr = torch.arange(b0, b1, device=dev, dtype=torch.int32)[:, None, None], lens[b0:b1, None, None]
+        want = torch.where(tt < Lr, fval(bb, tt) + bval(bb, (Lr - 1 - tt).clamp(min=0)), torch.zeros((), device=dev))
+        assert torch.equal(dxf[b0:b1], want), "rows %d..%d" % (b0, b1 - 1)
+    del dxf, dxb, want
+    torch.cuda.empty_cache()
 
 
 # ---- 7. a whole step learns ----

@@ -6,10 +6,16 @@ receives and the hyper-parameters rounded to float32 (what the C struct holds).
 Block set: eleven blocks of 1, 0, 3, 4, 5, 255, 256, 257, 4099, 65537 and 2^20 + 3 floats carved from one allocation, the block pointers at
 every 16-byte phase (and the gradient pointers at phases that partly differ from their weights'), every word outside a block a sentinel.
 
+A second set (5, 6 000 003, 0, 4099 and 3 000 001 floats, laid out the same way) has more chunks than either pass has workgroups; a third
+(67 108 864 + 4099 and 5 floats) is past the size at which the chunk doubles, and is checked on the device.
+
 Tolerance (per element): |library - float64| <= FACTOR x (the largest error of torch's own float32 CPU optimizer against float64 on the same
 inputs, over all elements) + one float32 ulp of the weight.  The issue allows FACTOR = 4.
 Measured on an MI355X (12 steps; library error / torch float32 error, both against float64): ratio 1.00 in all twelve cases (errors
-1.1e-6 .. 4.1e-6; DESIGN.md "Optimizer"): the kernel rounds where PyTorch's single-tensor CPU path rounds."""
+1.1e-6 .. 4.1e-6; DESIGN.md "Optimizer"): the kernel rounds where PyTorch's single-tensor CPU path rounds.
+Measured on an MI355X at the large sets: the 2201-chunk set (Adam, scaled and clipped, 3 steps) library error 6.4e-7 against torch float32's
+5.9e-7, ratio 1.09; the 8192-float-chunk set (SGD) norm within 4e-8 relative of the float64 sum in both steps, clip factor 0.499999762
+against 0.499999766, largest weight error 0.500 ulp (the bound is 1)."""
 import ctypes as C
 import functools
 
@@ -28,50 +34,81 @@ SENTINEL = -7.0e-33
 f32 = lambda v: float(np.float32(v))
 
 
-def _layout(phases):
+def _layout(phases, sizes=SIZES):
     """offsets of the blocks in one buffer: at least four sentinel words before each block, block i at 16-byte phase phases[i]"""
     offs, cur = [], 0
-    for n, ph in zip(SIZES, phases):
+    for n, ph in zip(sizes, phases):
         o = ((cur + 3) // 4) * 4 + 4 + ph
         offs.append(o)
         cur = o + n
     return offs, ((cur + 3) // 4) * 4 + 8
 
 
-W_PH = [(3 * i) % 4 for i in range(len(SIZES))]                       # 0 3 2 1 0 ...
-G_PH = [(3 * i + (i % 2)) % 4 for i in range(len(SIZES))]             # equal to the weights' phase for even i, different for odd i
-W_OFF, W_LEN = _layout(W_PH)
-G_OFF, G_LEN = _layout(G_PH)
+_w_phases = lambda n: [(3 * i) % 4 for i in range(n)]                 # 0 3 2 1 0 ...
+_g_phases = lambda n: [(3 * i + (i % 2)) % 4 for i in range(n)]       # equal to the weights' phase for even i, different for odd i
+
+
+# the second block set: more chunks than pass 1 and pass 2 have workgroups, so their grid-stride loops make a second trip
+BIG_SIZES = (5, 6_000_003, 0, 4_099, 3_000_001)
+BIG_STEPS = 3
+OPT_CHUNK, OPT_MAX_CHUNKS, OPT_MAX_GRID = 4096, 16384, 2048       # optim.hip:223, :224 and :29
+
+
+def _chunk_floats(total):
+    ch = OPT_CHUNK                                                # optim.hip:222-226 (nntk_shim_optim_chunk_floats)
+    while total // ch > OPT_MAX_CHUNKS and ch < 2 ** 30:
+        ch *= 2
+    return ch
+
+
+def _n_chunks(sizes, phases):
+    ch = _chunk_floats(sum(sizes))
+    return sum((ph + n + ch - 1) // ch for n, ph in zip(sizes, phases) if n)     # train.c:345 (nntk_optimizer_create)
+
+
+def _make_inputs(sizes, steps):
+    """initial weights and steps + 1 gradient sets (CPU float32)"""
+    gen = torch.Generator().manual_seed(2024)
+    w0 = [torch.randn(n, generator=gen) for n in sizes]
+    grads = [[torch.randn(n, generator=gen) * (1e-3 * (1 + t % 3)) for n in sizes] for t in range(steps + 1)]
+    return w0, grads
 
 
 @functools.lru_cache(None)
 def _inputs():
-    """initial weights and STEPS + 1 gradient sets (CPU float32), shared by every test and never modified"""
-    gen = torch.Generator().manual_seed(2024)
-    w0 = [torch.randn(n, generator=gen) for n in SIZES]
-    grads = [[torch.randn(n, generator=gen) * (1e-3 * (1 + t % 3)) for n in SIZES] for t in range(STEPS + 1)]
-    return w0, grads
+    """the SIZES set: shared by every test and never modified (the large set is made where it is used and not kept)"""
+    return _make_inputs(SIZES, STEPS)
 
 
 class Buffers:
-    """the weights and gradient allocations on the GPU with their sentinels"""
+    """the weights and gradient allocations on the GPU with their sentinels; the weights are w0 (default: the SIZES set's), or with
+    fill = False left to the caller"""
 
-    def __init__(self, gpu):
-        w0, _ = _inputs()
-        self.W = torch.full((W_LEN,), SENTINEL, device=gpu)
-        self.G = torch.full((G_LEN,), SENTINEL, device=gpu)
+    def __init__(self, gpu, sizes=SIZES, w0=None, w_ph=None, g_ph=None, fill=True):
+        if fill and w0 is None:
+            assert sizes == SIZES
+            w0, _ = _inputs()
+        self.w_ph = _w_phases(len(sizes)) if w_ph is None else w_ph
+        self.g_ph = _g_phases(len(sizes)) if g_ph is None else g_ph
+        w_off, w_len = _layout(self.w_ph, sizes)
+        g_off, g_len = _layout(self.g_ph, sizes)
+        self.W = torch.full((w_len,), SENTINEL, device=gpu)
+        self.G = torch.full((g_len,), SENTINEL, device=gpu)
         assert self.W.data_ptr() % 16 == 0 and self.G.data_ptr() % 16 == 0
-        self.w = [self.W[o:o + n] for o, n in zip(W_OFF, SIZES)]
-        self.g = [self.G[o:o + n] for o, n in zip(G_OFF, SIZES)]
-        for dst, src in zip(self.w, w0):
-            dst.copy_(src)
+        self.w = [self.W[o:o + n] for o, n in zip(w_off, sizes)]
+        self.g = [self.G[o:o + n] for o, n in zip(g_off, sizes)]
+        for t, ph in list(zip(self.w, self.w_ph)) + list(zip(self.g, self.g_ph)):
+            assert not t.numel() or (t.data_ptr() // 4) % 4 == ph
+        if fill:
+            for dst, src in zip(self.w, w0):
+                dst.copy_(src)
         for dst in self.g:
             dst.zero_()
-        self.mask_w = torch.ones(W_LEN, dtype=torch.bool)
-        self.mask_g = torch.ones(G_LEN, dtype=torch.bool)
-        for o, n in zip(W_OFF, SIZES):
+        self.mask_w = torch.ones(w_len, dtype=torch.bool)
+        self.mask_g = torch.ones(g_len, dtype=torch.bool)
+        for o, n in zip(w_off, sizes):
             self.mask_w[o:o + n] = False
-        for o, n in zip(G_OFF, SIZES):
+        for o, n in zip(g_off, sizes):
             self.mask_g[o:o + n] = False
 
     def set_grads(self, grads):
@@ -99,6 +136,7 @@ KINDS = {
 GS = f32(0.125)
 # the gradient norm of step t is about 1.06e-3 (1 + t % 3) sqrt(total): clip at 1.5 x the smallest, so steps with t % 3 == 0 pass unclipped
 CLIP = f32(1.5 * 1e-3 * np.sqrt(sum(SIZES)) * GS)
+BIG_CLIP = f32(1.5 * 1e-3 * np.sqrt(sum(BIG_SIZES)) * GS)
 
 
 def _torch_optimizer(params, cfg):
@@ -111,32 +149,37 @@ def _torch_optimizer(params, cfg):
 
 @functools.lru_cache(None)
 def _reference(name, clipped, dtype):
+    return _trajectory(name, clipped, dtype, _inputs(), STEPS, CLIP)
+
+
+def _trajectory(name, clipped, dtype, inputs, steps, clip):
     """the trajectory on the CPU: (final weights, [norm, clip factor] per step)"""
-    w0, grads = _inputs()
+    w0, grads = inputs
     _, cfg = KINDS[name]
     params = [torch.nn.Parameter(w.to(dtype).clone()) for w in w0]            # (a copy: .to() of the same dtype shares storage)
     opt = _torch_optimizer(params, cfg)
     info = []
-    for t in range(STEPS):
+    for t in range(steps):
         for p, g in zip(params, grads[t]):
             p.grad = g.to(dtype) * (GS if clipped else 1.0)
         if clipped:
-            norm = float(torch.nn.utils.clip_grad_norm_(params, CLIP, foreach=False))
-            info.append((norm, min(1.0, CLIP / (norm + 1e-6))))
+            norm = float(torch.nn.utils.clip_grad_norm_(params, clip, foreach=False))
+            info.append((norm, min(1.0, clip / (norm + 1e-6))))
         else:
             info.append((float(torch.sqrt(sum((p.grad.double() ** 2).sum() for p in params))), 1.0))
         opt.step()
     return [p.detach().clone() for p in params], info
 
 
-def _library(gpu, name, clipped, order=None, steps=STEPS, **extra):
-    _, grads = _inputs()
+def _library(gpu, name, clipped, order=None, steps=STEPS, inputs=None, clip=CLIP, **extra):
+    w0, grads = _inputs() if inputs is None else inputs
+    sizes = tuple(w.numel() for w in w0)
     kind, cfg = KINDS[name]
     cfg = dict(cfg, **extra)
     if clipped:
-        cfg.update(grad_scale=GS, clip_norm=CLIP)
-    buf = Buffers(gpu)
-    order = list(range(len(SIZES))) if order is None else order
+        cfg.update(grad_scale=GS, clip_norm=clip)
+    buf = Buffers(gpu, sizes, w0)
+    order = list(range(len(sizes))) if order is None else order
     opt = NL.Optimizer(kind, [(buf.w[i], buf.g[i]) for i in order], **cfg)
     info = []
     for t in range(steps):
@@ -149,12 +192,12 @@ def _library(gpu, name, clipped, order=None, steps=STEPS, **extra):
     return buf, info, state
 
 
-@pytest.mark.parametrize("clipped", [False, True], ids=["plain", "scaled_clipped"])
-@pytest.mark.parametrize("name", list(KINDS))
-def test_trajectory_matches_torch_float64(gpu, name, clipped):
-    r64, info64 = _reference(name, clipped, torch.float64)
-    r32, _ = _reference(name, clipped, torch.float32)
-    buf, info, _ = _library(gpu, name, clipped)
+def _assert_trajectory(gpu, name, clipped, inputs=None, steps=STEPS, clip=CLIP):
+    if inputs is None:
+        (r64, info64), (r32, _) = _reference(name, clipped, torch.float64), _reference(name, clipped, torch.float32)
+    else:
+        (r64, info64), (r32, _) = (_trajectory(name, clipped, dt, inputs, steps, clip) for dt in (torch.float64, torch.float32))
+    buf, info, _ = _library(gpu, name, clipped, steps=steps, inputs=inputs, clip=clip)
     buf.assert_guards()
     if clipped:
         factors = [c for _, c in info64]
@@ -173,6 +216,124 @@ def test_trajectory_matches_torch_float64(gpu, name, clipped):
         worst = max(worst, float(err.max()))
         assert bool((err <= FACTOR * e32 + ulp).all()), (name, i, float(err.max()), e32)
     print("%s %s: library err %.3e, torch float32 err %.3e, ratio %.2f" % (name, "clipped" if clipped else "plain", worst, e32, worst / e32 if e32 else 0.0))
+
+
+@pytest.mark.parametrize("clipped", [False, True], ids=["plain", "scaled_clipped"])
+@pytest.mark.parametrize("name", list(KINDS))
+def test_trajectory_matches_torch_float64(gpu, name, clipped):
+    _assert_trajectory(gpu, name, clipped)
+
+
+# ---- more chunks than workgroups: the grid-stride loops of both passes ----
+
+def _assert_grid_stride_premise():
+    assert _chunk_floats(sum(BIG_SIZES)) == OPT_CHUNK
+    assert _n_chunks(BIG_SIZES, _w_phases(len(BIG_SIZES))) == 2201 > OPT_MAX_GRID          # 153 workgroups of each pass take a second chunk
+
+
+def test_grid_stride_trajectory_matches_torch_float64(gpu):
+    """three Adam steps with grad_scale and a clip_norm that passes step 0 and clips steps 1 and 2, on 2201 chunks"""
+    _assert_grid_stride_premise()
+    _assert_trajectory(gpu, "adam", True, _make_inputs(BIG_SIZES, BIG_STEPS), BIG_STEPS, BIG_CLIP)
+
+
+def test_grid_stride_zero_gradients(gpu):
+    _assert_grid_stride_premise()
+    buf, info, _ = _library(gpu, "adam", True, steps=1, inputs=_make_inputs(BIG_SIZES, 1), clip=BIG_CLIP, zero_gradients=1)
+    assert info[0][2] == 0.0 and info[0][3] == 1.0
+    for g in buf.g:
+        gc = g.cpu()
+        assert torch.equal(gc, torch.zeros_like(gc)) and not bool(torch.signbit(gc).any()), "every gradient element must be +0.0"
+    buf.assert_guards()
+
+
+def test_grid_stride_independent_of_the_block_order(gpu):
+    _assert_grid_stride_premise()
+    inputs = _make_inputs(BIG_SIZES, BIG_STEPS)
+    a, ia, sa = _library(gpu, "adam", True, steps=BIG_STEPS, inputs=inputs, clip=BIG_CLIP)
+    r, ir, sr = _library(gpu, "adam", True, steps=BIG_STEPS, inputs=inputs, clip=BIG_CLIP, order=list(reversed(range(len(BIG_SIZES)))))
+    assert all(np.array_equal(x, y) for x, y in zip(ia, ir))
+    assert all(torch.equal(x, y) for x, y in zip(a.weights(), r.weights()))
+    for k in range(len(BIG_SIZES)):
+        if BIG_SIZES[k]:
+            assert np.array_equal(sa[k][0], sr[k][0]) and np.array_equal(sa[k][1], sr[k][1])
+    r.assert_guards()
+
+
+# ---- a total beyond 4096 x 16384 floats: chunks of 8192 floats.  Everything stays on the device ----
+
+HUGE_SIZES = (OPT_CHUNK * OPT_MAX_CHUNKS + 4_099, 5)
+
+
+def _ulp(a):
+    """one float32 ulp of |a| (a float64 tensor), as float64"""
+    a32 = a.abs().float()
+    return (torch.nextafter(a32, torch.full_like(a32, float("inf"))) - a32).double()
+
+
+def test_chunk_larger_than_4096(gpu):
+    """SGD over 67 M + 4104 floats.  Step one (no scale, no clip) equals nntk_sgd_optimize_device bit for bit; step two (grad_scale and a
+    clip_norm below the norm): norm and clip factor against a float64 sum on the device, every weight within 1 float32 ulp of
+    w - lr * clip * gs * g in float64 -- the update is three float32 roundings of products under one subtraction, and the weights are
+    O(1) (0.5 <= |w| < 1.5) against an update of O(1e-4), so one ulp of the weight covers it"""
+    L = capi.load()
+    total = sum(HUGE_SIZES)
+    assert total == 67_112_968 > OPT_CHUNK * OPT_MAX_CHUNKS and _chunk_floats(total) == 2 * OPT_CHUNK
+    w_ph, g_ph = [3, 2], [3, 0]
+    assert _n_chunks(HUGE_SIZES, w_ph) == 8194 > OPT_MAX_GRID
+    lr = f32(0.05)
+    gen = torch.Generator(device=gpu).manual_seed(67)
+    buf, ref = (Buffers(gpu, HUGE_SIZES, None, w_ph, g_ph, fill=False) for _ in range(2))
+    for w, wr in zip(buf.w, ref.w):
+        w.copy_((torch.rand(w.numel(), generator=gen, device=gpu) + 0.5) * (torch.randint(0, 2, (w.numel(),), generator=gen, device=gpu) * 2 - 1))
+        wr.copy_(w)
+
+    def set_grads(scale):
+        for g, gr in zip(buf.g, ref.g):
+            g.copy_(torch.randn(g.numel(), generator=gen, device=gpu) * scale)
+            gr.copy_(g)
+
+    def guards(b):
+        for full, mask in ((b.W, b.mask_w), (b.G, b.mask_g)):
+            assert bool((full[mask.to(gpu)] == SENTINEL).all()), "a word outside the blocks was written"
+
+    # step one
+    set_grads(1e-3)
+    opt = NL.Optimizer("sgd", list(zip(buf.w, buf.g)), learning_rate=lr)
+    opt.step()
+    info = [float(v) for v in opt.info()]                 # (python floats: the comparisons below are made in float64)
+    opt.destroy()
+    for w, g in zip(ref.w, ref.g):
+        assert L.nntk_sgd_optimize_device(capi.SGD(lr), C.c_void_p(g.data_ptr()), C.c_void_p(w.data_ptr()), w.numel()) == 0, capi.last_error()
+    torch.cuda.synchronize()
+    norm64 = float(torch.sqrt(sum(g.double().square().sum() for g in buf.g)))
+    print("step 1: norm %.9g, float64 %.9g, relative error %.2e" % (info[0], norm64, abs(info[0] - norm64) / norm64))
+    assert abs(info[0] - norm64) <= 1e-6 * norm64 and info[1] == 1.0 and info[2] == 0.0 and info[3] == 1.0, info
+    assert all(torch.equal(x, y) for x, y in zip(buf.w, ref.w)), "kind 0 without scale and clip differs from nntk_sgd_optimize_device"
+    # step two
+    set_grads(2e-3)
+    norm64 = float(torch.sqrt(sum((g.double() * GS).square().sum() for g in buf.g)))
+    clip_norm = f32(0.5 * norm64)
+    clip64 = min(1.0, clip_norm / (norm64 + 1e-6))
+    want = [w.double() - lr * clip64 * GS * g.double() for w, g in zip(buf.w, buf.g)]
+    opt = NL.Optimizer("sgd", list(zip(buf.w, buf.g)), learning_rate=lr, grad_scale=GS, clip_norm=clip_norm)
+    opt.step()
+    info = [float(v) for v in opt.info()]                 # (python floats: the comparisons below are made in float64)
+    opt.destroy()
+    print("step 2: norm %.9g, float64 %.9g, relative error %.2e; clip factor %.9g, float64 %.9g"
+          % (info[0], norm64, abs(info[0] - norm64) / norm64, info[1], clip64))
+    assert abs(info[0] - norm64) <= 1e-6 * norm64, ("norm", info[0], norm64)
+    assert clip64 < 1.0 and abs(info[1] - clip64) <= 2e-6, ("clip factor", info[1], clip64)
+    assert info[2] == 0.0 and info[3] == 1.0
+    for got, w64, before in zip(buf.w, want, ref.w):
+        err = (got.double() - w64).abs() / _ulp(w64)
+        print("step 2: %d weights, largest error %.3f ulp" % (got.numel(), float(err.max())))
+        assert bool((err <= 1.0).all()) and not torch.equal(got, before)
+    for g, gr in zip(buf.g, ref.g):
+        assert torch.equal(g, gr), "without zero_gradients the gradients are untouched"
+    guards(buf); guards(ref)
+    del want, buf, ref
+    torch.cuda.empty_cache()
 
 
 def test_clip_boundary(gpu):
