@@ -885,6 +885,33 @@ int nntk_ctc_loss(const float *probs, int batch, int T, int C, const int *input_
 int nntk_ctc_greedy_decode(const float *probs, int batch, int T, int C, const int *input_lengths, int blank, int *labels_out,
                            int *out_lengths);
 
+/* ---- CTC prefix beam search (csrc/hip/ctc_beam.hip; INTEGRATION.md "CTC prefix beam search") ----
+ * Acoustic scores only: per row the beam_width most probable label prefixes are kept per frame, each with the summed mass of ALL its
+ * alignments (ending in blank, p_b; ending in its last label, p_nb), and the nbest best after the row's last frame are returned.
+ *   d_probs [batch][T][C] probabilities; input_lengths HOST int [batch] or NULL (= all T); frames t >= input_lengths[b] influence
+ *     nothing and may hold NaN.  Host arrays are checked before anything is enqueued: -1, nntk_last_error(), nothing written.
+ *   cutoff_top_n: 0, or >= C - 1, expands every non-blank class per frame; otherwise only the cutoff_top_n non-blank classes of highest
+ *     probability (ties: the lower class).  The blank and the repeat of a prefix's last label are always processed.
+ *   Per frame, beam entry i (rank order) gives the stay cell i * (C + 1) -- the same prefix, p_b' = (p_b + p_nb) p[blank],
+ *     p_nb' = p_nb p[last] -- and for each expanded class c the extend cell i * (C + 1) + 1 + c -- prefix + c, p_b' = 0,
+ *     p_nb' = p_b p[c] if c repeats the last label, else (p_b + p_nb) p[c].  A stay cell whose prefix is also an extend cell's prefix is
+ *     merged into that cell (p_b' of the stay; p_nb' = stay + extension).  Totals p_b' + p_nb' of exactly 0 are dropped; the beam_width
+ *     largest totals form the next beam in descending order, exact ties to the lower cell index.
+ *   d_labels_out [batch][nbest][T]: hypothesis k's labels, then -1; d_out_lengths [batch][nbest]; d_scores [batch][nbest] =
+ *     ln(p_b + p_nb).  A slot without a hypothesis: labels -1, length -1, score -inf.  input_length 0: the empty prefix, score 0, in
+ *     slot 0.  Every element of the three outputs is written.
+ *   d_workspace: nntk_ctc_beam_workspace_floats(batch, T, C, beam_width, cutoff_top_n) floats, 16-byte aligned (24 bytes per row,
+ *     frame and beam entry, plus 8 per row, frame and expanded class when a class cut applies).
+ * Limits: 1 <= nbest <= beam_width <= 128; beam_width * (expanded classes + 1) <= 16384 (the candidate cells of a frame live in one
+ * workgroup's LDS); T < 2^23.  Deterministic: no atomics, the same bits on every call, a row's bits independent of the other rows,
+ * cutoff_top_n >= C - 1 the bits of 0.  The device form runs on the calling thread's stream and reads nothing back. */
+size_t nntk_ctc_beam_workspace_floats(int batch, int T, int C, int beam_width, int cutoff_top_n);
+int nntk_ctc_beam_decode_device(const float *d_probs, int batch, int T, int C, const int *input_lengths, int blank, int beam_width,
+                                int cutoff_top_n, int nbest, int *d_labels_out, int *d_out_lengths, float *d_scores,
+                                float *d_workspace);
+int nntk_ctc_beam_decode(const float *probs, int batch, int T, int C, const int *input_lengths, int blank, int beam_width,
+                         int cutoff_top_n, int nbest, int *labels_out, int *out_lengths, float *scores);
+
 #ifdef __cplusplus
 }
 #endif

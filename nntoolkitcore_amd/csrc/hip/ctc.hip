@@ -19,38 +19,10 @@
 #include <stdint.h>
 #include <limits.h>
 #include "nntk_common.hpp"
+#include "ctc_xf.hpp"
 
-#define CTC_EZERO (-(1 << 28))
-#define CTC_THREADS 256
 #define CTC_GRAD_LDS_FLOATS 8192          // gradient rows staged per workgroup: TT * C <= this (TT >= 1: C <= 32768 at 128 KiB)
 #define CTC_GRAD_MAX_C 32768
-#define CTC_LDS_LIMIT (160 * 1024)
-
-struct xf { float m; int e; };
-
-__device__ __forceinline__ xf xf_zero() { xf r; r.m = 0.0f; r.e = CTC_EZERO; return r; }
-__device__ __forceinline__ xf xf_one() { xf r; r.m = 0.5f; r.e = 1; return r; }
-__device__ __forceinline__ xf xf_norm(float m, int e) {
-    xf r;
-    r.m = __builtin_amdgcn_frexp_mantf(m);
-    r.e = m == 0.0f ? CTC_EZERO : e + __builtin_amdgcn_frexp_expf(m);
-    return r;
-}
-// (a + b) + c in this order, always: the bits of a row never depend on anything but the row
-__device__ __forceinline__ xf xf_add3(xf a, xf b, xf c) {
-    const int em = max(a.e, max(b.e, c.e));
-    const float m = (ldexpf(a.m, a.e - em) + ldexpf(b.m, b.e - em)) + ldexpf(c.m, c.e - em);
-    return xf_norm(m, em);
-}
-__device__ __forceinline__ xf xf_times_prob(xf v, float p) {
-    // the probability as mantissa and exponent too: a denormal p keeps its bits
-    return xf_norm(v.m * __builtin_amdgcn_frexp_mantf(p), v.e + __builtin_amdgcn_frexp_expf(p));
-}
-__device__ __forceinline__ float2 xf_pack(xf v) { return make_float2(v.m, __int_as_float(v.e)); }
-__device__ __forceinline__ xf xf_unpack(float2 w) { xf r; r.m = w.x; r.e = __float_as_int(w.y); return r; }
-
-// LDS traffic only: global loads and stores issued before the barrier stay in flight across it
-#define CTC_LDS_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
 
 // workspace, in 4-byte words: [ints: input lengths B | label lengths B | labels B*maxL | next B*maxL | first B*maxL] [P per row: 2B]
 // [abar: B*T*Smax pairs] [btil: the same]; every part starts on a 16-byte boundary

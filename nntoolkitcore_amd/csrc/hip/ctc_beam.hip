@@ -1,0 +1,542 @@
+// ctc_beam.hip -- CTC prefix beam search (Graves 2012; Hannun et al. 2014) on softmax probabilities [B][T][C], rows ragged, acoustic
+// scores only: per row the W best label prefixes per frame, each with the mass of its alignments ending in blank (p_b) and in its last
+// label (p_nb), and after the last frame an n-best list with log-probabilities.  INTEGRATION.md "CTC prefix beam search" fixes the
+// semantics (candidate cells, merging, the canonical-index tie rule) exactly; this file follows them cell by cell.
+//
+// Range.  Prefix masses fall like C^-T: every mass is an "xf" (ctc_xf.hpp), and the beam is ordered by a 64-bit integer key that is
+// monotone in (exponent, mantissa), zero for a zero mass.
+//
+// Work split.  ctc_beam_cut_kernel (only when a class cut applies): a wavefront per frame finds the cutoff_top_n-th largest non-blank
+// probability by bisection on the float bits and writes the frame's (class, probability) pairs in ascending class order -- parallel
+// over B*T, off the serial chain.  ctc_beam_kernel: one 256-lane workgroup per row, the beam resident in LDS for all frames.  A frame
+// is: stays and merge detection (lanes over beam entries / entry pairs), the W x (n + 1) cell matrix (lanes over cells), the at most
+// W merges, the selection, the new beam.  Selection: one reduction gives the largest and smallest non-zero key; a bisection between
+// them stops as soon as W <= count(key >= theta) <= 256 (or at a single key value, when more than 256 cells tie there); the survivors
+// are compacted in cell order and ranked against each other by counting, which yields the descending order and the lower-index tie
+// rule at once.  No atomics anywhere: every count is a ballot.  The next frame's probabilities are loaded before the frame's first
+// barrier (the barriers wait for LDS only) and land in the other half of a double buffer at its end.  Per entry and frame one
+// (parent rank | prefix length, class or -1) record and the (p_b, p_nb) pair go to the workspace: the only global stores of the loop.
+// ctc_beam_backtrack_kernel: a workgroup per row stages the records of a block of frames in LDS and a lane per hypothesis walks them
+// from the last frame, writing labels in forward order, then the -1 padding, the lengths and the scores.
+//
+// Prefix identity.  No label string is compared in the frame loop.  A prefix is known by a 64-bit hash chained over its labels
+// (splitmix64 finaliser), its length and its last class; an entry also carries its parent prefix's hash.  Entry j merges into the
+// extend cell (i, c) when j's parent hash is i's hash, j is one label longer than i and j's last class is c.  Unlike a parent RANK,
+// this also recognises a prefix that left the beam and came back while its child stayed.  Two different prefixes of one length are
+// taken for one with probability 2^-64 per compared pair.
+#include <stdint.h>
+#include <limits.h>
+#include "nntk_common.hpp"
+#include "ctc_xf.hpp"
+
+#define BEAM_MAX_W 128
+#define BEAM_MAX_CELLS 16384              // W * (n + 1) cells of 8 bytes: 128 KiB of the 160 KiB of LDS
+#define BEAM_LIST 256                     // survivors ranked against each other
+#define BEAM_PF 4                         // staged words a lane carries in registers across the selection
+#define BEAM_BT_RECORDS 8192              // backtrack: records staged per block of frames (64 KiB)
+#define BEAM_MAX_T ((1 << 23) - 1)        // the prefix length shares a signed word with the parent rank: length << 8 < 2^31
+
+typedef unsigned long long u64;
+
+// workspace, in 4-byte words: [ints: input lengths B | final beam size B] [records: B*T*W int2] [masses: B*T*W float4]
+// [class cut: B*T*ncut (class, prob) pairs]; every part starts on a 16-byte boundary
+struct BeamLayout { size_t ints, hist, mass, cut, total; };
+static BeamLayout beam_layout(int B, int T, int W, int ncut) {
+    BeamLayout l;
+    const size_t b = B > 0 ? (size_t)B : 0, t = T > 0 ? (size_t)T : 0, w = W > 0 ? (size_t)W : 0, n = ncut > 0 ? (size_t)ncut : 0;
+    auto up = [](size_t x) { return (x + 3) & ~(size_t)3; };
+    l.ints = 0;
+    l.hist = up(2 * b);
+    l.mass = l.hist + up(2 * b * t * w);
+    l.cut = l.mass + 4 * b * t * w;
+    l.total = l.cut + up(2 * b * t * n) + 4;
+    return l;
+}
+// 0: every non-blank class is expanded
+static int beam_ncut(int C, int cutoff_top_n) { return cutoff_top_n <= 0 || cutoff_top_n >= C - 1 ? 0 : cutoff_top_n; }
+
+// LDS of ctc_beam_kernel, byte offsets; every part 16-byte aligned
+struct BeamLds { unsigned cells, stage, state, frame, sel, lkey, lidx, cnt, red, total; };
+__host__ __device__ static inline BeamLds beam_lds(int W, int n, int C, bool cut, bool stage) {
+    BeamLds l;
+    auto up = [](unsigned x) { return (x + 15u) & ~15u; };
+    l.cells = 0;
+    l.stage = up(8u * (unsigned)W * (unsigned)(n + 1));
+    l.state = l.stage + (stage ? up(cut ? 16u * (unsigned)n : 8u * (unsigned)C) : 0u);
+    l.frame = l.state + up(2u * 44u * (unsigned)W);     // [2] x { p_b, p_nb, hash, parent hash : 8 bytes; last, len, home : 4 bytes } [W]
+    l.sel = l.frame + up(32u * (unsigned)W);            // stay p_b', stay p_nb', p_b + p_nb, record: 8 bytes each [W]
+    l.lkey = l.sel + up(4u * (unsigned)W);
+    l.lidx = l.lkey + 8u * BEAM_LIST;
+    l.cnt = l.lidx + 4u * BEAM_LIST;
+    l.red = l.cnt + 2u * 16u * (BEAM_MAX_CELLS / CTC_THREADS);
+    l.total = l.red + 128u;
+    return l;
+}
+
+__device__ __forceinline__ u64 beam_key(float2 w) {
+    const unsigned mb = __float_as_uint(w.x);
+    return mb == 0u ? 0ull : ((u64)(unsigned)(__float_as_int(w.y) - CTC_EZERO) << 23) | (u64)(mb & 0x7fffffu);
+}
+__device__ __forceinline__ u64 beam_hash(u64 h, int c) {
+    u64 x = h + (u64)(unsigned)(c + 1) * 0x9E3779B97F4A7C15ull;
+    x ^= x >> 30; x *= 0xBF58476D1CE4E5B9ull;
+    x ^= x >> 27; x *= 0x94D049BB133111EBull;
+    return x ^ (x >> 31);
+}
+__device__ __forceinline__ xf xf_add2(xf a, xf b) { return xf_add3(a, b, xf_zero()); }
+
+// ---- class cut: the n non-blank classes of highest probability (ties: the lower class), ascending class order ----
+__global__ __launch_bounds__(CTC_THREADS) void ctc_beam_cut_kernel(const float *__restrict__ probs, int T, int C, int blank, int n,
+                                                                   const int *__restrict__ lens, float2 *__restrict__ pairs, long frames) {
+    const int lane = threadIdx.x & 63;
+    const u64 lt = (1ull << lane) - 1;
+    for (long f = blockIdx.x * 4L + (threadIdx.x >> 6); f < frames; f += gridDim.x * 4L) {
+        const int b = (int)(f / T), t = (int)(f % T);
+        if (t >= lens[b]) continue;
+        const float *row = probs + f * C;
+        float2 *out = pairs + f * n;
+        // the largest lo with count(bits >= lo) >= n: probabilities are non-negative, their bits order like their values
+        unsigned lo = 0u, hi = 0x7f800001u;
+        while (hi - lo > 1u) {
+            const unsigned mid = lo + (hi - lo) / 2u;
+            int cnt = 0;
+            for (int k0 = 0; k0 < C; k0 += 64) {
+                const int k = k0 + lane;
+                const bool in = k < C && k != blank && __float_as_uint(row[k]) >= mid;
+                cnt += __popcll(__ballot(in));
+            }
+            if (cnt >= n) lo = mid; else hi = mid;
+        }
+        int above = 0;
+        for (int k0 = 0; k0 < C; k0 += 64) {
+            const int k = k0 + lane;
+            above += __popcll(__ballot(k < C && k != blank && __float_as_uint(row[k]) > lo));
+        }
+        int need = n - above, pos = 0;                                       // classes equal to the threshold still to take, lowest first
+        for (int k0 = 0; k0 < C; k0 += 64) {
+            const int k = k0 + lane;
+            const bool in = k < C && k != blank;
+            const float v = in ? row[k] : 0.0f;
+            const unsigned vb = __float_as_uint(v);
+            const u64 eqm = __ballot(in && vb == lo);
+            const bool take = in && (vb > lo || (vb == lo && __popcll(eqm & lt) < need));
+            const u64 tm = __ballot(take);
+            if (take) {
+                const int p = pos + __popcll(tm & lt);
+                if (p < n) out[p] = make_float2(__int_as_float(k), v);
+            }
+            pos += __popcll(tm);
+            need -= min(need, (int)__popcll(eqm));
+        }
+    }
+}
+
+// ---- the beam: one workgroup per row ----
+template <bool CUT, bool STAGE>
+__global__ __launch_bounds__(CTC_THREADS) void ctc_beam_kernel(const float *__restrict__ probs, int T, int C, int blank, int W, int n,
+                                                               unsigned magic, const int *__restrict__ lens, int *__restrict__ nfin,
+                                                               int2 *__restrict__ hist, float4 *__restrict__ mass,
+                                                               const float2 *__restrict__ pairs) {
+    extern __shared__ __align__(16) unsigned char beam_smem[];
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const u64 lt = (1ull << lane) - 1;
+    const int Tb = lens[b], n1 = n + 1;
+    const BeamLds L = beam_lds(W, n, C, CUT, STAGE);
+    float2 *cell = (float2 *)(beam_smem + L.cells);
+    float *srow = (float *)(beam_smem + L.stage);                              // !CUT: [2][C] probabilities
+    float2 *spair = (float2 *)(beam_smem + L.stage);                           // CUT: [2][n] (class, probability)
+    unsigned char *st = beam_smem + L.state;
+    float2 *s_pb = (float2 *)st, *s_pnb = s_pb + 2 * W;
+    u64 *s_h = (u64 *)(s_pnb + 2 * W), *s_ph = s_h + 2 * W;
+    int *s_last = (int *)(s_ph + 2 * W), *s_len = s_last + 2 * W, *s_home = s_len + 2 * W;
+    float2 *f_spb = (float2 *)(beam_smem + L.frame), *f_spnb = f_spb + W, *f_sum = f_spnb + W;
+    int2 *f_rec = (int2 *)(f_sum + W);
+    int *sel = (int *)(beam_smem + L.sel);
+    u64 *lkey = (u64 *)(beam_smem + L.lkey);
+    int *lidx = (int *)(beam_smem + L.lidx);
+    int4 *cnt1 = (int4 *)(beam_smem + L.cnt), *cnt2 = cnt1 + BEAM_MAX_CELLS / CTC_THREADS;
+    u64 *r_max = (u64 *)(beam_smem + L.red), *r_min = r_max + 4;
+    int *r_nz = (int *)(r_min + 4), *r_bis = r_nz + 4;                         // r_bis [2][4]
+
+    const float *prow = probs + (long)b * T * C;
+    const float2 *crow = CUT ? pairs + (long)b * T * n : nullptr;
+    int2 *hrow = hist + (long)b * T * W;
+    float4 *mrow = mass + (long)b * T * W;
+    const int M = CUT ? n : C;                                                 // staged elements per frame
+    const bool in_regs = STAGE && M <= BEAM_PF * CTC_THREADS;
+
+    auto div_n1 = [&](int idx) { return n1 == 1 ? idx : (int)__umulhi((unsigned)idx, magic); };
+
+    if (tid == 0) {
+        s_pb[0] = xf_pack(xf_one());
+        s_pnb[0] = xf_pack(xf_zero());
+        s_h[0] = 0x243F6A8885A308D3ull;
+        s_ph[0] = 0ull;
+        s_last[0] = -1;
+        s_len[0] = 0;
+        s_home[0] = -1;
+    }
+    if (STAGE && Tb > 0) {
+        if (CUT) for (int k = tid; k < M; k += CTC_THREADS) spair[k] = crow[k];
+        else for (int k = tid; k < M; k += CTC_THREADS) srow[k] = prow[k];
+    }
+    __syncthreads();
+
+    int nb = 1, cur = 0;
+    for (int t = 0; t < Tb; ++t) {
+        const int o = cur * W, on = (cur ^ 1) * W;                             // this frame's beam, the next one's
+        const float *grow = prow + (long)t * C;
+        const float2 *gpair = CUT ? crow + (long)t * n : nullptr;
+        const float *sr = srow + cur * M;
+        const float2 *sp = spair + cur * M;
+        // the next frame's staged words: in flight across every barrier of this frame
+        float pre[BEAM_PF];
+        float2 pre2[BEAM_PF];
+        if (in_regs && t + 1 < Tb) {
+#pragma unroll
+            for (int q = 0; q < BEAM_PF; ++q) {
+                const int k = tid + CTC_THREADS * q;
+                if (CUT) pre2[q] = k < M ? gpair[n + k] : make_float2(0.0f, 0.0f);
+                else pre[q] = k < M ? grow[C + k] : 0.0f;
+            }
+        }
+        auto prob_of = [&](int c) { return (!CUT && STAGE) ? sr[c] : grow[c]; };
+        auto cell_class = [&](int k, int &c, float &p) {
+            if (CUT) {
+                const float2 v = STAGE ? sp[k] : gpair[k];
+                c = __float_as_int(v.x);
+                p = v.y;
+            } else {
+                c = k + (k >= blank ? 1 : 0);
+                p = prob_of(c);
+            }
+        };
+
+        // ---- stays; which entry's prefix is another entry's prefix plus one expanded class ----
+        if (tid < nb) {
+            const xf pb = xf_unpack(s_pb[o + tid]), pnb = xf_unpack(s_pnb[o + tid]);
+            const xf s = xf_add2(pb, pnb);
+            f_sum[tid] = xf_pack(s);
+            f_spb[tid] = xf_pack(xf_times_prob(s, prob_of(blank)));
+            f_spnb[tid] = xf_pack(s_len[o + tid] > 0 ? xf_times_prob(pnb, prob_of(s_last[o + tid])) : xf_zero());
+        }
+        {
+            int sh = 0;
+            while ((1 << sh) < nb) ++sh;
+            const int pairs_n = nb << sh;
+            for (int p = tid; p < pairs_n; p += CTC_THREADS) {
+                const int j = p & ((1 << sh) - 1), i = p >> sh;                // consecutive lanes: consecutive j
+                if (j >= nb) continue;
+                if (s_len[o + j] != s_len[o + i] + 1 || s_ph[o + j] != s_h[o + i]) continue;
+                const int c = s_last[o + j];
+                int k = -1;
+                if (CUT) {
+                    int a = 0, z = n - 1;
+                    while (a <= z) {
+                        const int mid = (a + z) >> 1;
+                        const int cm = __float_as_int(STAGE ? sp[mid].x : gpair[mid].x);
+                        if (cm == c) { k = mid; break; }
+                        if (cm < c) a = mid + 1; else z = mid - 1;
+                    }
+                } else {
+                    k = c - (c > blank ? 1 : 0);
+                }
+                if (k >= 0) s_home[o + j] = i * n1 + 1 + k;
+            }
+        }
+        CTC_LDS_BARRIER();
+
+        // ---- the cell matrix: cell i * (n + 1) is entry i's stay, cell i * (n + 1) + 1 + k its extension by the k-th expanded class ----
+        const int N = nb * n1;
+        for (int idx = tid; idx < N; idx += CTC_THREADS) {
+            const int i = div_n1(idx), kk = idx - i * n1;
+            xf v;
+            if (kk == 0) {
+                v = s_home[o + i] < 0 ? xf_add2(xf_unpack(f_spb[i]), xf_unpack(f_spnb[i])) : xf_zero();
+            } else {
+                int c;
+                float p;
+                cell_class(kk - 1, c, p);
+                v = xf_times_prob(xf_unpack(c == s_last[o + i] ? s_pb[o + i] : f_sum[i]), p);
+            }
+            cell[idx] = xf_pack(v);
+        }
+        CTC_LDS_BARRIER();
+        // ---- merges: p_nb' = stay + extension, in that order; the cell holds the candidate's total ----
+        if (tid < nb && s_home[o + tid] >= 0) {
+            const int hc = s_home[o + tid];
+            const xf mnb = xf_add2(xf_unpack(f_spnb[tid]), xf_unpack(cell[hc]));
+            f_spnb[tid] = xf_pack(mnb);
+            cell[hc] = xf_pack(xf_add2(xf_unpack(f_spb[tid]), mnb));
+        }
+        CTC_LDS_BARRIER();
+
+        // ---- selection ----
+        const int R = (N + CTC_THREADS - 1) / CTC_THREADS;
+        {
+            u64 mx = 0ull, mn = ~0ull;
+            int nz = 0;
+            for (int r = 0; r < R; ++r) {
+                const int idx = r * CTC_THREADS + tid;
+                const u64 k = idx < N ? beam_key(cell[idx]) : 0ull;
+                if (k) { mx = k > mx ? k : mx; mn = k < mn ? k : mn; ++nz; }
+            }
+            for (int off = 32; off > 0; off >>= 1) {
+                const u64 omx = __shfl_xor(mx, off), omn = __shfl_xor(mn, off);
+                mx = omx > mx ? omx : mx;
+                mn = omn < mn ? omn : mn;
+                nz += __shfl_xor(nz, off);
+            }
+            if (lane == 0) { r_max[wave] = mx; r_min[wave] = mn; r_nz[wave] = nz; }
+        }
+        CTC_LDS_BARRIER();
+        u64 lo = ~0ull, hi = 0ull;
+        int clo = 0;
+        for (int w = 0; w < 4; ++w) {
+            lo = r_min[w] < lo ? r_min[w] : lo;
+            hi = r_max[w] > hi ? r_max[w] : hi;
+            clo += r_nz[w];
+        }
+        const int Wt = min(W, clo);                                           // candidates with total exactly 0 are dropped
+        if (Wt == 0) { nb = 0; break; }                                       // uniform: every lane read the same words
+        hi += 1ull;
+        // count(key >= lo) = clo >= Wt always; count(key >= hi) < Wt always
+        for (int it = 0; clo > BEAM_LIST && hi - lo > 1ull; ++it) {
+            const u64 mid = lo + (hi - lo) / 2ull;
+            int c = 0;
+            for (int r = 0; r < R; ++r) {
+                const int idx = r * CTC_THREADS + tid;
+                c += __popcll(__ballot(idx < N && beam_key(cell[idx]) >= mid));
+            }
+            int *slot = r_bis + (it & 1) * 4;
+            if (lane == 0) slot[wave] = c;
+            CTC_LDS_BARRIER();
+            c = slot[0] + slot[1] + slot[2] + slot[3];
+            if (c >= Wt) { lo = mid; clo = c; } else { hi = mid; }
+        }
+        // survivors in cell order: every key above lo, then the first of those equal to lo, BEAM_LIST in all
+        for (int r = 0; r < R; ++r) {
+            const int idx = r * CTC_THREADS + tid;
+            const u64 k = idx < N ? beam_key(cell[idx]) : 0ull;
+            const int c1 = __popcll(__ballot(k > lo)), c2 = __popcll(__ballot(k == lo));
+            if (lane == 0) { ((int *)(cnt1 + r))[wave] = c1; ((int *)(cnt2 + r))[wave] = c2; }
+        }
+        CTC_LDS_BARRIER();
+        int tot1 = 0, tot2 = 0;
+        for (int r = 0; r < R; ++r) {
+            const int4 a = cnt1[r], e = cnt2[r];
+            tot1 += a.x + a.y + a.z + a.w;
+            tot2 += e.x + e.y + e.z + e.w;
+        }
+        {
+            int run1 = 0, run2 = tot1;
+            for (int r = 0; r < R; ++r) {
+                const int idx = r * CTC_THREADS + tid;
+                const u64 k = idx < N ? beam_key(cell[idx]) : 0ull;
+                const bool g = k > lo, e = k == lo;
+                const u64 m1 = __ballot(g), m2 = __ballot(e);
+                const int4 a = cnt1[r], q = cnt2[r];
+                const int p1 = run1 + (wave > 0 ? a.x : 0) + (wave > 1 ? a.y : 0) + (wave > 2 ? a.z : 0) + __popcll(m1 & lt);
+                const int p2 = run2 + (wave > 0 ? q.x : 0) + (wave > 1 ? q.y : 0) + (wave > 2 ? q.z : 0) + __popcll(m2 & lt);
+                if (g && p1 < BEAM_LIST) { lkey[p1] = k; lidx[p1] = idx; }
+                if (e && p2 < BEAM_LIST) { lkey[p2] = k; lidx[p2] = idx; }
+                run1 += a.x + a.y + a.z + a.w;
+                run2 += q.x + q.y + q.z + q.w;
+            }
+        }
+        const int nl = min(BEAM_LIST, tot1 + tot2);
+        CTC_LDS_BARRIER();
+        if (tid < nl) {
+            const u64 k = lkey[tid];
+            const int idx = lidx[tid];
+            int rank = 0;
+            for (int u = 0; u < nl; ++u) {
+                const u64 ku = lkey[u];
+                rank += (ku > k || (ku == k && lidx[u] < idx)) ? 1 : 0;
+            }
+            if (rank < Wt) sel[rank] = idx;
+        }
+        CTC_LDS_BARRIER();
+
+        // ---- the new beam: rank r as a plain stay or extension first; a merged cell is taken over by the entry whose stay it holds ----
+        if (tid < Wt) {
+            const int idx = sel[tid];
+            const int i = div_n1(idx), kk = idx - i * n1;
+            if (kk == 0) {
+                s_pb[on + tid] = f_spb[i];
+                s_pnb[on + tid] = f_spnb[i];
+                s_h[on + tid] = s_h[o + i];
+                s_ph[on + tid] = s_ph[o + i];
+                s_last[on + tid] = s_last[o + i];
+                s_len[on + tid] = s_len[o + i];
+                f_rec[tid] = make_int2(i | (s_len[o + i] << 8), -1);
+            } else {
+                int c;
+                float p;
+                cell_class(kk - 1, c, p);
+                const u64 h = s_h[o + i];
+                s_pb[on + tid] = xf_pack(xf_zero());
+                s_pnb[on + tid] = cell[idx];
+                s_h[on + tid] = beam_hash(h, c);
+                s_ph[on + tid] = h;
+                s_last[on + tid] = c;
+                s_len[on + tid] = s_len[o + i] + 1;
+                f_rec[tid] = make_int2(i | ((s_len[o + i] + 1) << 8), c);
+                cell[idx].x = __uint_as_float(0x80000000u | (unsigned)tid);    // no mantissa has the sign bit: "selected, rank tid"
+            }
+            s_home[on + tid] = -1;
+        }
+        CTC_LDS_BARRIER();
+        if (tid < nb && s_home[o + tid] >= 0) {
+            const unsigned m = __float_as_uint(cell[s_home[o + tid]].x);
+            if (m & 0x80000000u) {
+                const int r = (int)(m & 0xffffu);
+                s_pb[on + r] = f_spb[tid];
+                s_pnb[on + r] = f_spnb[tid];
+                s_h[on + r] = s_h[o + tid];
+                s_ph[on + r] = s_ph[o + tid];
+                s_last[on + r] = s_last[o + tid];
+                s_len[on + r] = s_len[o + tid];
+                f_rec[r] = make_int2(tid | (s_len[o + tid] << 8), -1);
+            }
+        }
+        if (STAGE && t + 1 < Tb) {
+            if (in_regs) {
+#pragma unroll
+                for (int q = 0; q < BEAM_PF; ++q) {
+                    const int k = tid + CTC_THREADS * q;
+                    if (k < M) {
+                        if (CUT) spair[(cur ^ 1) * M + k] = pre2[q];
+                        else srow[(cur ^ 1) * M + k] = pre[q];
+                    }
+                }
+            } else if (CUT) {
+                for (int k = tid; k < M; k += CTC_THREADS) spair[(cur ^ 1) * M + k] = gpair[n + k];
+            } else {
+                for (int k = tid; k < M; k += CTC_THREADS) srow[(cur ^ 1) * M + k] = grow[C + k];
+            }
+        }
+        CTC_LDS_BARRIER();
+        if (tid < Wt) {
+            const float2 pb = s_pb[on + tid], pnb = s_pnb[on + tid];
+            hrow[(long)t * W + tid] = f_rec[tid];
+            mrow[(long)t * W + tid] = make_float4(pb.x, pb.y, pnb.x, pnb.y);
+        }
+        nb = Wt;
+        cur ^= 1;
+    }
+    if (tid == 0) nfin[b] = nb;
+}
+
+// ---- backtrack: hypothesis k of a row is entry k of its last frame ----
+__global__ __launch_bounds__(CTC_THREADS) void ctc_beam_backtrack_kernel(int T, int W, int nbest, const int *__restrict__ lens,
+                                                                         const int *__restrict__ nfin, const int2 *__restrict__ hist,
+                                                                         const float4 *__restrict__ mass, int *__restrict__ labels,
+                                                                         int *__restrict__ out_len, float *__restrict__ scores) {
+    extern __shared__ __align__(16) unsigned char beam_smem[];
+    __shared__ int s_hlen[BEAM_MAX_W];
+    int2 *rec = (int2 *)beam_smem;
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const int Tb = lens[b];
+    const int nh = Tb == 0 ? 1 : min(nbest, nfin[b]);                         // hypotheses this row has
+    const int2 *hrow = hist + (long)b * T * W;
+    const float4 *mrow = mass + (long)b * T * W;
+    int *lab = labels + (long)b * nbest * T;
+    int rank = tid, len = -1, pos = -1;
+    if (tid < nbest) {
+        float score = -INFINITY;
+        if (tid < nh) {
+            if (Tb == 0) {
+                len = 0;
+                score = 0.0f;
+            } else {
+                len = hrow[(long)(Tb - 1) * W + tid].x >> 8;
+                const float4 m = mrow[(long)(Tb - 1) * W + tid];
+                xf pb, pnb;
+                pb.m = m.x; pb.e = __float_as_int(m.y);
+                pnb.m = m.z; pnb.e = __float_as_int(m.w);
+                const xf s = xf_add2(pb, pnb);
+                // once per hypothesis: double, libm log
+                score = (float)((double)s.e * 0.69314718055994530942 + log((double)s.m));
+            }
+        }
+        pos = len - 1;
+        s_hlen[tid] = len;
+        out_len[(long)b * nbest + tid] = len;
+        scores[(long)b * nbest + tid] = score;
+    }
+    const int TC = max(1, BEAM_BT_RECORDS / W);
+    for (int t1 = Tb; t1 > 0; t1 -= TC) {
+        const int t0 = max(0, t1 - TC);
+        const long base = (long)t0 * W;
+        const int cnt = (t1 - t0) * W;
+        __syncthreads();
+        for (int q = tid; q < cnt; q += CTC_THREADS) rec[q] = hrow[base + q];
+        __syncthreads();
+        if (tid < nh) {
+            for (int t = t1 - 1; t >= t0; --t) {
+                const int2 r = rec[(t - t0) * W + rank];
+                if (r.y >= 0 && pos >= 0) lab[(long)tid * T + pos--] = r.y;
+                rank = r.x & 0xff;
+            }
+        }
+    }
+    __syncthreads();
+    const long cells = (long)nbest * T;
+    for (long q = tid; q < cells; q += CTC_THREADS) {
+        const int k = (int)(q / T), p = (int)(q % T);
+        if (p >= s_hlen[k]) lab[q] = -1;
+    }
+}
+
+extern "C" {
+
+size_t nntk_shim_ctc_beam_workspace_floats(int batch, int T, int C, int beam_width, int cutoff_top_n) {
+    return beam_layout(batch, T, beam_width, beam_ncut(C, cutoff_top_n)).total;
+}
+
+int nntk_shim_ctc_beam_decode(const float *d_probs, int B, int T, int C, const int *h_input_lengths, int blank, int W, int cutoff_top_n,
+                              int nbest, int *d_labels_out, int *d_out_lengths, float *d_scores, float *d_ws) {
+    if (B <= 0) return 0;
+    if (((uintptr_t)d_ws & 15) != 0) return nntk_fail_msg("nntk_ctc_beam_decode_device: the workspace must be 16-byte aligned");
+    const int ncut = beam_ncut(C, cutoff_top_n), n = ncut ? ncut : C - 1;
+    if (W < 1 || W > BEAM_MAX_W || nbest < 1 || nbest > W || (long)W * (n + 1) > BEAM_MAX_CELLS || T > BEAM_MAX_T)
+        return nntk_fail_msg("nntk_ctc_beam_decode_device: beam_width, nbest or beam_width * (classes + 1) beyond the kernel's limits");
+    const BeamLayout lay = beam_layout(B, T, W, ncut);
+    int *d_lens = (int *)d_ws, *d_nfin = d_lens + B;
+    int2 *d_hist = (int2 *)(d_ws + lay.hist);
+    float4 *d_mass = (float4 *)(d_ws + lay.mass);
+    float2 *d_pairs = (float2 *)(d_ws + lay.cut);
+    if (nntk_shim_upload_ints(d_lens, h_input_lengths, B)) return -1;
+    const long frames = (long)B * T;
+    if (ncut && frames > 0) {
+        long g = (frames + 3) / 4;
+        if (g > 16384) g = 16384;
+        hipLaunchKernelGGL(ctc_beam_cut_kernel, dim3((unsigned)g), dim3(CTC_THREADS), 0, nntk_stream(), d_probs, T, C, blank, n, d_lens,
+                           d_pairs, frames);
+        NNTK_LAUNCH_CHECK("ctc_beam_cut_kernel");
+    }
+    // the frame's probabilities (or its cut pairs) double-buffered in LDS where they fit beside the cells
+    const bool stage = beam_lds(W, n, C, ncut != 0, true).total <= CTC_LDS_LIMIT;
+    const size_t lds = beam_lds(W, n, C, ncut != 0, stage).total;
+    if (lds > CTC_LDS_LIMIT) return nntk_fail_msg("nntk_ctc_beam_decode_device: the beam does not fit one workgroup's LDS");
+    const unsigned magic = n + 1 > 1 ? (unsigned)(0x100000000ull / (unsigned)(n + 1)) + 1u : 0u;
+#define BEAM_GO(CUT, STAGE)                                                                                                        \
+    do {                                                                                                                           \
+        if (lds > 48 * 1024 && nntk_set_max_dynamic_lds((const void *)ctc_beam_kernel<CUT, STAGE>, lds)) return -1;                \
+        hipLaunchKernelGGL((ctc_beam_kernel<CUT, STAGE>), dim3((unsigned)B), dim3(CTC_THREADS), lds, nntk_stream(), d_probs, T, C,   \
+                           blank, W, n, magic, d_lens, d_nfin, d_hist, d_mass, d_pairs);                                           \
+    } while (0)
+    if (ncut) { if (stage) BEAM_GO(true, true); else BEAM_GO(true, false); }
+    else { if (stage) BEAM_GO(false, true); else BEAM_GO(false, false); }
+#undef BEAM_GO
+    NNTK_LAUNCH_CHECK("ctc_beam_kernel");
+    const size_t blds = (size_t)BEAM_BT_RECORDS * sizeof(int2);
+    if (nntk_set_max_dynamic_lds((const void *)ctc_beam_backtrack_kernel, blds)) return -1;
+    hipLaunchKernelGGL(ctc_beam_backtrack_kernel, dim3((unsigned)B), dim3(CTC_THREADS), blds, nntk_stream(), T, W, nbest, d_lens, d_nfin,
+                       d_hist, d_mass, d_labels_out, d_out_lengths, d_scores);
+    NNTK_LAUNCH_CHECK("ctc_beam_backtrack_kernel");
+    return 0;
+}
+
+}  // extern "C"

@@ -160,6 +160,11 @@ int nntk_shim_ctc_loss(const float *d_probs, int B, int T, int C, const int *h_i
                        const int *h_label_lengths, int max_label_len, int blank, float *d_loss_rows, float *d_dprobs, float *d_ws);
 int nntk_shim_ctc_greedy_decode(const float *d_probs, int B, int T, int C, const int *h_input_lengths, int blank, int *d_labels_out,
                                 int *d_out_lengths);
+/* ---- CTC prefix beam search (ctc_beam.hip): the n-best prefixes of every row with their log-probabilities.  h_input_lengths is HOST
+ *      memory, checked by the caller (train.c), never NULL; d_ws 16-byte aligned, nntk_shim_ctc_beam_workspace_floats words ---- */
+size_t nntk_shim_ctc_beam_workspace_floats(int batch, int T, int C, int beam_width, int cutoff_top_n);
+int nntk_shim_ctc_beam_decode(const float *d_probs, int B, int T, int C, const int *h_input_lengths, int blank, int beam_width,
+                              int cutoff_top_n, int nbest, int *d_labels_out, int *d_out_lengths, float *d_scores, float *d_ws);
 /* BatchNorm training (batch_norm.c:191-386): x, d_out [N, F]; d_block = gamma | beta | ...; d_stats [8][F] = mean | variance |
  * var_eps | sqrt_var | d_beta | d_gamma | d_var | d_mu; d_partial [slices][3][F] with slices from nntk_shim_bn_train_slices */
 /* Ragged batches and carried state for the recurrent training launchers below (the *VarLen training calls; a NULL pointer to it = the

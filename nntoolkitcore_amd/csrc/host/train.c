@@ -264,6 +264,65 @@ int nntk_ctc_greedy_decode(const float *probs, int batch, int T, int C, const in
     return nntk_shim_download(out_lengths, d_o + nl, (size_t)batch * sizeof(int));
 }
 
+/* ---- CTC prefix beam search (csrc/hip/ctc_beam.hip) ---- */
+#define CTC_BEAM_MAX_W 128
+#define CTC_BEAM_MAX_CELLS 16384
+static int ctc_beam_check(const char *who, int batch, int T, int C, const int *input_lengths, int blank, int beam_width,
+                          int cutoff_top_n, int nbest) {
+    if (ctc_check_shape(who, batch, T, C, blank) || nntk_check_lengths(who, input_lengths, batch, T, NULL, NULL)) return -1;
+    if (beam_width < 1 || beam_width > CTC_BEAM_MAX_W)
+        return ctc_fail(who, "beam_width %d is outside [1, %d]", beam_width, CTC_BEAM_MAX_W, 0);
+    if (nbest < 1 || nbest > beam_width) return ctc_fail(who, "nbest %d is outside [1, beam_width = %d]", nbest, beam_width, 0);
+    if (cutoff_top_n < 0) return ctc_fail(who, "cutoff_top_n %d < 0", cutoff_top_n, 0, 0);
+    const int n = cutoff_top_n == 0 || cutoff_top_n >= C - 1 ? C - 1 : cutoff_top_n;      /* expanded classes per frame */
+    if ((long long)beam_width * (n + 1) > CTC_BEAM_MAX_CELLS)
+        return ctc_fail(who, "beam_width %d x (%d expanded classes + 1) is more than %d candidate cells: lower beam_width or set cutoff_top_n",
+                        beam_width, n, CTC_BEAM_MAX_CELLS);
+    if (T >= (1 << 23)) return ctc_fail(who, "T %d is not below %d frames", T, 1 << 23, 0);
+    return 0;
+}
+
+size_t nntk_ctc_beam_workspace_floats(int batch, int T, int C, int beam_width, int cutoff_top_n) {
+    return nntk_shim_ctc_beam_workspace_floats(batch, T, C, beam_width, cutoff_top_n);
+}
+
+int nntk_ctc_beam_decode_device(const float *d_probs, int batch, int T, int C, const int *input_lengths, int blank, int beam_width,
+                                int cutoff_top_n, int nbest, int *d_labels_out, int *d_out_lengths, float *d_scores,
+                                float *d_workspace) {
+    static const char who[] = "nntk_ctc_beam_decode_device";
+    nntk_shim_clear_error();
+    if (ctc_beam_check(who, batch, T, C, input_lengths, blank, beam_width, cutoff_top_n, nbest)) return -1;
+    if (batch == 0) return 0;
+    if (!d_out_lengths || !d_scores || !d_workspace || ((!d_probs || !d_labels_out) && T > 0))
+        NNTK_FAIL("nntk_ctc_beam_decode_device: NULL tensor");
+    int *len = ctc_lengths(input_lengths, batch, T);
+    if (!len) return -1;
+    int rc = nntk_shim_ctc_beam_decode(d_probs, batch, T, C, len, blank, beam_width, cutoff_top_n, nbest, d_labels_out, d_out_lengths,
+                                       d_scores, d_workspace);
+    free(len);
+    return rc;
+}
+
+int nntk_ctc_beam_decode(const float *probs, int batch, int T, int C, const int *input_lengths, int blank, int beam_width,
+                         int cutoff_top_n, int nbest, int *labels_out, int *out_lengths, float *scores) {
+    static const char who[] = "nntk_ctc_beam_decode";
+    nntk_shim_clear_error();
+    if (ctc_beam_check(who, batch, T, C, input_lengths, blank, beam_width, cutoff_top_n, nbest)) return -1;
+    if (batch == 0) return 0;
+    if (!out_lengths || !scores || ((!probs || !labels_out) && T > 0)) NNTK_FAIL("nntk_ctc_beam_decode: NULL array");
+    const size_t n = (size_t)batch * T * C, nh = (size_t)batch * nbest, nl = nh * T;
+    float *d_p = nntk_devbuf_reserve(&t_a, n + 4);
+    int *d_o = (int *)nntk_devbuf_reserve(&t_b, nl + 2 * nh + 4);             /* labels | lengths | scores */
+    float *d_ws = nntk_devbuf_reserve(&t_c, nntk_shim_ctc_beam_workspace_floats(batch, T, C, beam_width, cutoff_top_n));
+    if (!d_p || !d_o || !d_ws) return -1;
+    if (n && nntk_shim_upload(d_p, probs, n * sizeof(float))) return -1;
+    if (nntk_ctc_beam_decode_device(d_p, batch, T, C, input_lengths, blank, beam_width, cutoff_top_n, nbest, d_o, d_o + nl,
+                                    (float *)(d_o + nl + nh), d_ws)) return -1;
+    if (nl && nntk_shim_download(labels_out, d_o, nl * sizeof(int))) return -1;
+    if (nntk_shim_download(out_lengths, d_o + nl, nh * sizeof(int))) return -1;
+    return nntk_shim_download(scores, d_o + nl + nh, nh * sizeof(float));
+}
+
 /* ---- SGD (train/optimizers.c:13-19) ---- */
 int nntk_sgd_optimize_device(SGD optimizer, const float *d_gradient, float *d_weights, long size) {
     nntk_shim_clear_error();

@@ -641,6 +641,42 @@ def ctc_greedy_decode(probs, input_lengths=None, blank=0):
     return out, n
 
 
+def ctc_beam_decode_device(probs, input_lengths=None, blank=0, beam_width=16, cutoff_top_n=0, nbest=1, labels_out=None, out_lengths=None,
+                           scores=None, workspace=None):
+    """``nntk_ctc_beam_decode_device``: prefix beam search over probs [B,T,C] -> (labels [B,nbest,T] int32, -1 behind each hypothesis'
+    labels; lengths [B,nbest] int32, -1 for a slot without a hypothesis; scores [B,nbest] float32 = ln of the prefix probability)"""
+    import torch
+    B, T, Cc = probs.shape
+    il, ilp = _ctc_lengths(input_lengths, B)
+    L = capi.load()
+    need = L.nntk_ctc_beam_workspace_floats(B, T, Cc, beam_width, cutoff_top_n)
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.float32, device=probs.device)
+    assert workspace.numel() >= need, "workspace: nntk_ctc_beam_workspace_floats(B, T, C, beam_width, cutoff_top_n) floats"
+    if labels_out is None:
+        labels_out = torch.empty((B, max(nbest, 0), T), dtype=torch.int32, device=probs.device)
+    if out_lengths is None:
+        out_lengths = torch.empty((B, max(nbest, 0)), dtype=torch.int32, device=probs.device)
+    if scores is None:
+        scores = torch.empty((B, max(nbest, 0)), dtype=torch.float32, device=probs.device)
+    check(L.nntk_ctc_beam_decode_device(_dp(probs), B, T, Cc, ilp, blank, beam_width, cutoff_top_n, nbest,
+                                        C.c_void_p(labels_out.data_ptr()), C.c_void_p(out_lengths.data_ptr()), _dp(scores),
+                                        _dp(workspace)), "nntk_ctc_beam_decode_device")
+    return labels_out, out_lengths, scores
+
+
+def ctc_beam_decode(probs, input_lengths=None, blank=0, beam_width=16, cutoff_top_n=0, nbest=1):
+    """The host-memory form (``nntk_ctc_beam_decode``): probs [B,T,C] numpy array."""
+    probs = _f32(probs)
+    B, T, Cc = probs.shape
+    il, ilp = _ctc_lengths(input_lengths, B)
+    nb = max(nbest, 0)
+    out, n, sc = np.empty((B, nb, T), np.int32), np.empty((B, nb), np.int32), np.empty((B, nb), np.float32)
+    check(capi.load().nntk_ctc_beam_decode(_p(probs), B, T, Cc, ilp, blank, beam_width, cutoff_top_n, nbest, out.ctypes.data_as(capi.ip),
+                                           n.ctypes.data_as(capi.ip), _p(sc)), "nntk_ctc_beam_decode")
+    return out, n, sc
+
+
 class LSTM(_Recurrent):
     def __init__(self, in_features, hidden, return_sequences, timesteps, v2=True, acts=None, mini_batch=None):
         L = capi.load()
