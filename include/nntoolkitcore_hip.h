@@ -912,6 +912,34 @@ int nntk_ctc_beam_decode_device(const float *d_probs, int batch, int T, int C, c
 int nntk_ctc_beam_decode(const float *probs, int batch, int T, int C, const int *input_lengths, int blank, int beam_width,
                          int cutoff_top_n, int nbest, int *labels_out, int *out_lengths, float *scores);
 
+/* ---- CTC forced alignment (csrc/hip/ctc_align.hip; INTEGRATION.md "CTC forced alignment") ----
+ * Given a row's labels, its single most probable alignment (Viterbi): which frames belong to which label.
+ *   d_probs, input_lengths, labels [batch][max_label_len], label_lengths: as for nntk_ctc_loss_device -- probabilities, HOST int arrays
+ *     (input_lengths NULL = every row T) with the same checks, made before anything is enqueued: -1, nntk_last_error(), nothing
+ *     written.  Frames t >= input_lengths[b] influence nothing and may hold NaN.
+ *   Row b has L labels and the extended states s in [0, 2L]; cls(s) is the blank for even s, labels[(s - 1) / 2] for odd s.
+ *     v_0(0) = p[0][blank], v_0(1) = p[0][cls(1)], every other v_0 is 0; v_t(s) = max(v_{t-1}(s), v_{t-1}(s-1), v_{t-1}(s-2)) p[t][cls(s)],
+ *     the s - 2 term only for odd s >= 3 with cls(s) != cls(s - 2).  Values carry an int32 exponent of their own: no underflow.
+ *   Ties: the candidates are taken in the order s, s - 1, s - 2 and a later one replaces the current one only if it is strictly
+ *     greater.  The path ends in state 2L unless v(2L - 1) is strictly greater (L = 0: state 0).
+ *   d_states [batch][T] or NULL: the best path's state for t < input_length, then -1.  Odd s: frame t emits label (s - 1) / 2; even: blank.
+ *   d_spans [batch][max_label_len][2] or NULL: for label i < L the first frame in state 2i + 1 and one past the last such frame (they
+ *     are contiguous); -1, -1 for i >= L.
+ *   d_scores [batch]: ln of the best path's probability.  A row no alignment produces (input_length < label_length + the number of
+ *     adjacent equal labels, or zeros in d_probs on every path): -inf, every state -1, every span -1.  input_length 0: 0 for an empty
+ *     label, -inf otherwise.  Every element of every non-NULL output is written.
+ *   d_workspace: nntk_ctc_align_workspace_floats(batch, T, max_label_len) floats, 16-byte aligned: 1 byte per row, frame and extended
+ *     state (batch * T * (2 max_label_len + 1) bytes of backpointers), plus 4 (3 + max_label_len) bytes per row and 16.
+ * Limit: max_label_len <= 4000.  Deterministic: no atomics, the same bits on every call, a row's bits independent of the other rows
+ * and of max_label_len.  The host-pointer form uploads, runs the device form and downloads.  The device form runs on the calling
+ * thread's stream and reads nothing back. */
+size_t nntk_ctc_align_workspace_floats(int batch, int T, int max_label_len);
+int nntk_ctc_align_device(const float *d_probs, int batch, int T, int C, const int *input_lengths, const int *labels,
+                          const int *label_lengths, int max_label_len, int blank, int *d_states, int *d_spans, float *d_scores,
+                          float *d_workspace);
+int nntk_ctc_align(const float *probs, int batch, int T, int C, const int *input_lengths, const int *labels, const int *label_lengths,
+                   int max_label_len, int blank, int *states, int *spans, float *scores);
+
 #ifdef __cplusplus
 }
 #endif

@@ -433,6 +433,9 @@ SIGNATURES = {
     "nntk_ctc_beam_workspace_floats": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "nntk_ctc_beam_decode_device": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, ip, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]),
     "nntk_ctc_beam_decode": (C.c_int, [fp, C.c_int, C.c_int, C.c_int, ip, C.c_int, C.c_int, C.c_int, C.c_int, ip, ip, fp]),
+    "nntk_ctc_align_workspace_floats": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "nntk_ctc_align_device": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, ip, ip, ip, C.c_int, C.c_int, vp, vp, vp, vp]),
+    "nntk_ctc_align": (C.c_int, [fp, C.c_int, C.c_int, C.c_int, ip, ip, ip, C.c_int, C.c_int, ip, ip, fp]),
     # weights from device memory into a handle; the multi-tensor optimizer (INTEGRATION.md "Optimizers")
     "Conv1dLoadWeightsDevice": (C.c_int, [vp, vp]),
     "BatchNormLoadWeightsDevice": (C.c_int, [vp, vp]),

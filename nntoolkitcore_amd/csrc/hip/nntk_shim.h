@@ -165,6 +165,13 @@ int nntk_shim_ctc_greedy_decode(const float *d_probs, int B, int T, int C, const
 size_t nntk_shim_ctc_beam_workspace_floats(int batch, int T, int C, int beam_width, int cutoff_top_n);
 int nntk_shim_ctc_beam_decode(const float *d_probs, int B, int T, int C, const int *h_input_lengths, int blank, int beam_width,
                               int cutoff_top_n, int nbest, int *d_labels_out, int *d_out_lengths, float *d_scores, float *d_ws);
+/* ---- CTC forced alignment (ctc_align.hip): the best single alignment of every row to its labels -- the state of every frame, the
+ *      frame span of every label, ln of the path's probability.  The int arrays are HOST memory, already checked by the caller
+ *      (train.c), never NULL; d_states / d_spans may be NULL; d_ws 16-byte aligned, nntk_shim_ctc_align_workspace_floats words ---- */
+size_t nntk_shim_ctc_align_workspace_floats(int batch, int T, int max_label_len);
+int nntk_shim_ctc_align(const float *d_probs, int B, int T, int C, const int *h_input_lengths, const int *h_labels,
+                        const int *h_label_lengths, int max_label_len, int blank, int *d_states, int *d_spans, float *d_scores,
+                        float *d_ws);
 /* BatchNorm training (batch_norm.c:191-386): x, d_out [N, F]; d_block = gamma | beta | ...; d_stats [8][F] = mean | variance |
  * var_eps | sqrt_var | d_beta | d_gamma | d_var | d_mu; d_partial [slices][3][F] with slices from nntk_shim_bn_train_slices */
 /* Ragged batches and carried state for the recurrent training launchers below (the *VarLen training calls; a NULL pointer to it = the

@@ -323,6 +323,57 @@ int nntk_ctc_beam_decode(const float *probs, int batch, int T, int C, const int 
     return nntk_shim_download(scores, d_o + nl + nh, nh * sizeof(float));
 }
 
+/* ---- CTC forced alignment (csrc/hip/ctc_align.hip) ---- */
+#define CTC_ALIGN_MAX_LABELS 4000
+static int ctc_align_check(const char *who, int batch, int T, int C, const int *input_lengths, const int *labels, const int *label_lengths,
+                           int max_label_len, int blank) {
+    if (ctc_check_shape(who, batch, T, C, blank) || nntk_check_lengths(who, input_lengths, batch, T, NULL, NULL)) return -1;
+    if (max_label_len > CTC_ALIGN_MAX_LABELS)
+        return ctc_fail(who, "max_label_len %d is more than %d (the extended states of a row live in one workgroup's LDS)", max_label_len,
+                        CTC_ALIGN_MAX_LABELS, 0);
+    return ctc_check_labels(who, batch, C, labels, label_lengths, max_label_len, blank);
+}
+
+size_t nntk_ctc_align_workspace_floats(int batch, int T, int max_label_len) {
+    return nntk_shim_ctc_align_workspace_floats(batch, T, max_label_len);
+}
+
+int nntk_ctc_align_device(const float *d_probs, int batch, int T, int C, const int *input_lengths, const int *labels,
+                          const int *label_lengths, int max_label_len, int blank, int *d_states, int *d_spans, float *d_scores,
+                          float *d_workspace) {
+    static const char who[] = "nntk_ctc_align_device";
+    nntk_shim_clear_error();
+    if (ctc_align_check(who, batch, T, C, input_lengths, labels, label_lengths, max_label_len, blank)) return -1;
+    if (batch == 0) return 0;
+    if (!d_scores || !d_workspace || (!d_probs && T > 0)) NNTK_FAIL("nntk_ctc_align_device: NULL tensor");
+    int *len = ctc_lengths(input_lengths, batch, T);
+    if (!len) return -1;
+    int rc = nntk_shim_ctc_align(d_probs, batch, T, C, len, labels, label_lengths, max_label_len, blank, d_states, d_spans, d_scores,
+                                 d_workspace);
+    free(len);
+    return rc;
+}
+
+int nntk_ctc_align(const float *probs, int batch, int T, int C, const int *input_lengths, const int *labels, const int *label_lengths,
+                   int max_label_len, int blank, int *states, int *spans, float *scores) {
+    static const char who[] = "nntk_ctc_align";
+    nntk_shim_clear_error();
+    if (ctc_align_check(who, batch, T, C, input_lengths, labels, label_lengths, max_label_len, blank)) return -1;
+    if (batch == 0) return 0;
+    if (!scores || (!probs && T > 0)) NNTK_FAIL("nntk_ctc_align: NULL array");
+    const size_t n = (size_t)batch * T * C, ns = states ? (size_t)batch * T : 0, np = spans ? 2 * (size_t)batch * max_label_len : 0;
+    float *d_p = nntk_devbuf_reserve(&t_a, n + 4);
+    int *d_o = (int *)nntk_devbuf_reserve(&t_b, ns + np + (size_t)batch + 4);           /* states | spans | scores */
+    float *d_ws = nntk_devbuf_reserve(&t_c, nntk_shim_ctc_align_workspace_floats(batch, T, max_label_len));
+    if (!d_p || !d_o || !d_ws) return -1;
+    if (n && nntk_shim_upload(d_p, probs, n * sizeof(float))) return -1;
+    if (nntk_ctc_align_device(d_p, batch, T, C, input_lengths, labels, label_lengths, max_label_len, blank, ns ? d_o : NULL,
+                              np ? d_o + ns : NULL, (float *)(d_o + ns + np), d_ws)) return -1;
+    if (ns && nntk_shim_download(states, d_o, ns * sizeof(int))) return -1;
+    if (np && nntk_shim_download(spans, d_o + ns, np * sizeof(int))) return -1;
+    return nntk_shim_download(scores, d_o + ns + np, (size_t)batch * sizeof(float));
+}
+
 /* ---- SGD (train/optimizers.c:13-19) ---- */
 int nntk_sgd_optimize_device(SGD optimizer, const float *d_gradient, float *d_weights, long size) {
     nntk_shim_clear_error();

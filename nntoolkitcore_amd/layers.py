@@ -677,6 +677,43 @@ def ctc_beam_decode(probs, input_lengths=None, blank=0, beam_width=16, cutoff_to
     return out, n, sc
 
 
+def ctc_align_device(probs, labels, label_lengths=None, input_lengths=None, blank=0, states=None, spans=None, scores=None, workspace=None):
+    """``nntk_ctc_align_device``: the best alignment of probs [B,T,C] to the labels (as for ``ctc_loss_device``) -> (states [B,T] int32,
+    the extended state of every frame, -1 behind each row; spans [B,max_label_len,2] int32, each label's first frame and one past
+    its last, -1 for a label the row does not have; scores [B] float32 = ln of the path's probability, -inf where there is no path)"""
+    import torch
+    B, T, Cc = probs.shape
+    lab, ll = _ctc_labels(labels, label_lengths, B)
+    il, ilp = _ctc_lengths(input_lengths, B)
+    L = capi.load()
+    need = L.nntk_ctc_align_workspace_floats(B, T, lab.shape[1])
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.float32, device=probs.device)
+    assert workspace.numel() >= need, "workspace: nntk_ctc_align_workspace_floats(B, T, max_label_len) floats"
+    if states is None:
+        states = torch.empty((B, T), dtype=torch.int32, device=probs.device)
+    if spans is None:
+        spans = torch.empty((B, lab.shape[1], 2), dtype=torch.int32, device=probs.device)
+    if scores is None:
+        scores = torch.empty(B, dtype=torch.float32, device=probs.device)
+    check(L.nntk_ctc_align_device(_dp(probs), B, T, Cc, ilp, lab.ctypes.data_as(capi.ip), ll.ctypes.data_as(capi.ip), lab.shape[1], blank,
+                                  C.c_void_p(states.data_ptr()), C.c_void_p(spans.data_ptr()), _dp(scores), _dp(workspace)),
+          "nntk_ctc_align_device")
+    return states, spans, scores
+
+
+def ctc_align(probs, labels, label_lengths=None, input_lengths=None, blank=0):
+    """The host-memory form (``nntk_ctc_align``): probs [B,T,C] numpy array."""
+    probs = _f32(probs)
+    B, T, Cc = probs.shape
+    lab, ll = _ctc_labels(labels, label_lengths, B)
+    il, ilp = _ctc_lengths(input_lengths, B)
+    st, sp, sc = np.empty((B, T), np.int32), np.empty((B, lab.shape[1], 2), np.int32), np.empty(B, np.float32)
+    check(capi.load().nntk_ctc_align(_p(probs), B, T, Cc, ilp, lab.ctypes.data_as(capi.ip), ll.ctypes.data_as(capi.ip), lab.shape[1], blank,
+                                     st.ctypes.data_as(capi.ip), sp.ctypes.data_as(capi.ip), _p(sc)), "nntk_ctc_align")
+    return st, sp, sc
+
+
 class LSTM(_Recurrent):
     def __init__(self, in_features, hidden, return_sequences, timesteps, v2=True, acts=None, mini_batch=None):
         L = capi.load()
