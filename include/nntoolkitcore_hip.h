@@ -912,6 +912,51 @@ int nntk_ctc_beam_decode_device(const float *d_probs, int batch, int T, int C, c
 int nntk_ctc_beam_decode(const float *probs, int batch, int T, int C, const int *input_lengths, int blank, int beam_width,
                          int cutoff_top_n, int nbest, int *labels_out, int *out_lengths, float *scores);
 
+/* ---- streaming CTC decoding (INTEGRATION.md "CTC prefix beam search", Streaming) ----
+ * A handle is pushed chunk by chunk -- d_probs [batch][max_frames][C] and n_frames are what a streaming stack's push returns -- and
+ * after every push row b's outputs are the nbest hypotheses nntk_ctc_beam_decode_device gives on the concatenation of the row's valid
+ * frames since its last reset, with the same blank, beam_width, cutoff_top_n, nbest: labels, lengths and the score BITS, for every
+ * way of cutting the stream into pushes (one frame per push and pushes with n_frames[b] == 0 included).  All semantics of that call
+ * carry over: candidate cells, merging, the canonical-index tie rule, dropping exact-zero totals, -1 / -inf for empty slots.
+ *   A row that has seen no frame reports the empty prefix in slot 0 (length 0, score 0.0).  n_frames[b] == 0 leaves the row's state
+ *     as it is and rewrites its current n-best.  A row whose beam has died (a frame with zero mass on every candidate) holds no
+ *     hypothesis -- every slot -1 / -1 / -inf -- until it is reset.  Frames t >= n_frames[b] influence nothing and may hold NaN.
+ *   final (HOST int [batch] or NULL): final[b] != 0 makes this push's outputs the row's final result; after they are written the
+ *     row is reset and starts a new stream on the next push.  nntk_ctc_beam_stream_reset does the same for the listed rows at any time.
+ *   max_labels: the capacity of the stored and returned label strings.  A longer hypothesis keeps its first max_labels labels and
+ *     d_out_lengths still reports its true length; scores, lengths and ranking are unaffected (no string is ever compared).
+ *     d_labels_out [batch][nbest][max_labels]: labels at index >= min(length, max_labels) are -1.  Every output element is written
+ *     on every push.
+ *   Host checks: n_frames (0..max_frames each) and the pointers are checked before anything is enqueued; on a refusal -1,
+ *     nntk_last_error(), nothing written, the state untouched.  The host arrays are copied in stream order and are free for reuse on
+ *     return.  The handle counts each row's frames since its reset on the host and refuses a push that would take a row past
+ *     2^23 - 1 frames (the prefix length shares a word with the parent rank).
+ *   create checks every argument before touching a device (NULL + nntk_last_error() on refusal): the one-shot call's limits
+ *     (1 <= nbest <= beam_width <= 128, the 16384-cell limit, LDS fit), max_frames >= 1, max_labels >= 1, batch >= 0.  batch == 0:
+ *     every call returns 0 without a device.  The device memory (nntk_ctc_beam_stream_state_bytes: 40 bytes per row and beam entry,
+ *     two label strings of max_labels ints per row and beam entry, and the scratch of one push -- 8 bytes per row, frame of a push
+ *     and beam entry, 8 more per expanded class under a class cut) is allocated by the first push.
+ *   Deterministic: no atomics, the same bits on every run, a row's bits independent of the other rows and of how THEY are chunked.
+ *   The device push runs on the calling thread's stream and reads nothing back; pushes of one handle belong on one stream.  The
+ *   host-pointer push uploads, runs the device push and downloads. */
+typedef struct NntkCtcBeamStreamStruct *NntkCtcBeamStream;
+NntkCtcBeamStream nntk_ctc_beam_stream_create(int batch, int max_frames, int C, int blank, int beam_width, int cutoff_top_n, int nbest,
+                                              int max_labels);
+size_t nntk_ctc_beam_stream_state_bytes(int batch, int max_frames, int C, int beam_width, int cutoff_top_n, int max_labels);
+int nntk_ctc_beam_stream_push_device(NntkCtcBeamStream s, const float *d_probs, const int *n_frames, const int *final,
+                                     int *d_labels_out, int *d_out_lengths, float *d_scores);
+int nntk_ctc_beam_stream_reset(NntkCtcBeamStream s, const int *rows, int n_rows);
+void nntk_ctc_beam_stream_destroy(NntkCtcBeamStream s);
+int nntk_ctc_beam_stream_push(NntkCtcBeamStream s, const float *probs, const int *n_frames, const int *final, int *labels_out,
+                              int *out_lengths, float *scores);
+/* Streaming best path: the labels THIS chunk adds.  d_probs [batch][T][C]; n_frames HOST int [batch], 0..T; d_prev [batch] device
+ * int, in/out: the argmax of the row's last frame seen, -1 = a new stream (the caller resets a row by writing -1); unchanged where
+ * n_frames[b] == 0.  A frame whose argmax equals the previous frame's (d_prev[b] for the chunk's first) is dropped, then blanks are.
+ * d_labels_out [batch][T], -1 behind the labels; d_out_lengths [batch].  The concatenation of a row's chunk outputs equals
+ * nntk_ctc_greedy_decode_device on the concatenated frames; argument checks and ties (lowest index) are that call's. */
+int nntk_ctc_greedy_decode_stream_device(const float *d_probs, int batch, int T, int C, const int *n_frames, int blank, int *d_prev,
+                                         int *d_labels_out, int *d_out_lengths);
+
 /* ---- CTC forced alignment (csrc/hip/ctc_align.hip; INTEGRATION.md "CTC forced alignment") ----
  * Given a row's labels, its single most probable alignment (Viterbi): which frames belong to which label.
  *   d_probs, input_lengths, labels [batch][max_label_len], label_lengths: as for nntk_ctc_loss_device -- probabilities, HOST int arrays

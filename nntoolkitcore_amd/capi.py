@@ -433,6 +433,14 @@ SIGNATURES = {
     "nntk_ctc_beam_workspace_floats": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "nntk_ctc_beam_decode_device": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, ip, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]),
     "nntk_ctc_beam_decode": (C.c_int, [fp, C.c_int, C.c_int, C.c_int, ip, C.c_int, C.c_int, C.c_int, C.c_int, ip, ip, fp]),
+    # streaming CTC decoding (INTEGRATION.md "CTC prefix beam search", Streaming)
+    "nntk_ctc_beam_stream_create": (vp, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "nntk_ctc_beam_stream_state_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "nntk_ctc_beam_stream_push_device": (C.c_int, [vp, vp, ip, ip, vp, vp, vp]),
+    "nntk_ctc_beam_stream_reset": (C.c_int, [vp, ip, C.c_int]),
+    "nntk_ctc_beam_stream_destroy": (None, [vp]),
+    "nntk_ctc_beam_stream_push": (C.c_int, [vp, fp, ip, ip, ip, ip, fp]),
+    "nntk_ctc_greedy_decode_stream_device": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, ip, C.c_int, vp, vp, vp]),
     "nntk_ctc_align_workspace_floats": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "nntk_ctc_align_device": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, ip, ip, ip, C.c_int, C.c_int, vp, vp, vp, vp]),
     "nntk_ctc_align": (C.c_int, [fp, C.c_int, C.c_int, C.c_int, ip, ip, ip, C.c_int, C.c_int, ip, ip, fp]),

@@ -224,21 +224,23 @@ __global__ __launch_bounds__(CTC_THREADS) void ctc_argmax_kernel(const float *__
     }
 }
 
-// lens_io[b]: the row's input length on entry, the decoded length on exit
-__global__ __launch_bounds__(CTC_THREADS) void ctc_compact_kernel(int *__restrict__ out, int *__restrict__ lens_io, int T, int blank) {
+// lens_io[b]: the row's input length on entry, the decoded length on exit.  prev_io (streaming, else NULL): [B], the argmax of the frame
+// before the row's first (-1: none), replaced by the argmax of the row's last frame when the row has one
+__global__ __launch_bounds__(CTC_THREADS) void ctc_compact_kernel(int *__restrict__ out, int *__restrict__ lens_io, int T, int blank,
+                                                                  int *__restrict__ prev_io) {
     __shared__ int sh[CTC_THREADS];
     __shared__ int wtot[CTC_THREADS / 64];
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     int *row = out + (long)b * T;
     const int len = lens_io[b];
-    int base = 0, prev_last = -1;
+    int base = 0, prev_last = prev_io ? prev_io[b] : -1;
     for (int t0 = 0; t0 < len; t0 += CTC_THREADS) {
         const int t = t0 + tid;
         const int a = t < len ? row[t] : -1;
         sh[tid] = a;
         __syncthreads();
         const int prev = tid > 0 ? sh[tid - 1] : prev_last;
-        const bool keep = t < len && a != blank && (t == 0 || a != prev);
+        const bool keep = t < len && a != blank && a != prev;                 // frame 0: prev is -1, or the carried argmax
         const unsigned long long mask = __ballot(keep);
         if (lane == 0) wtot[wave] = __popcll(mask);
         const int last = sh[CTC_THREADS - 1];
@@ -250,6 +252,7 @@ __global__ __launch_bounds__(CTC_THREADS) void ctc_compact_kernel(int *__restric
             tot += wtot[w];
         }
         if (keep) row[pos] = a;                                               // pos <= t: never a frame of a later chunk
+        if (prev_io && t == len - 1) prev_io[b] = a;                          // every lane read it two barriers ago
         base += tot;
         prev_last = last;
         __syncthreads();
@@ -306,8 +309,9 @@ int nntk_shim_ctc_loss(const float *d_probs, int B, int T, int C, const int *h_i
     return 0;
 }
 
-int nntk_shim_ctc_greedy_decode(const float *d_probs, int B, int T, int C, const int *h_input_lengths, int blank, int *d_labels_out,
-                                int *d_out_lengths) {
+// d_prev NULL: the one-shot call; else the chunk's labels, with the repeat rule reaching back to the row's previous frame
+int nntk_shim_ctc_greedy_decode_stream(const float *d_probs, int B, int T, int C, const int *h_input_lengths, int blank, int *d_prev,
+                                       int *d_labels_out, int *d_out_lengths) {
     if (B <= 0) return 0;
     if (nntk_shim_upload_ints(d_out_lengths, h_input_lengths, B)) return -1;   // the lengths ride in the output until the compaction
     const long frames = (long)B * T;
@@ -318,9 +322,15 @@ int nntk_shim_ctc_greedy_decode(const float *d_probs, int B, int T, int C, const
                            d_labels_out, frames);
         NNTK_LAUNCH_CHECK("ctc_argmax_kernel");
     }
-    hipLaunchKernelGGL(ctc_compact_kernel, dim3((unsigned)B), dim3(CTC_THREADS), 0, nntk_stream(), d_labels_out, d_out_lengths, T, blank);
+    hipLaunchKernelGGL(ctc_compact_kernel, dim3((unsigned)B), dim3(CTC_THREADS), 0, nntk_stream(), d_labels_out, d_out_lengths, T, blank,
+                       d_prev);
     NNTK_LAUNCH_CHECK("ctc_compact_kernel");
     return 0;
+}
+
+int nntk_shim_ctc_greedy_decode(const float *d_probs, int B, int T, int C, const int *h_input_lengths, int blank, int *d_labels_out,
+                                int *d_out_lengths) {
+    return nntk_shim_ctc_greedy_decode_stream(d_probs, B, T, C, h_input_lengths, blank, nullptr, d_labels_out, d_out_lengths);
 }
 
 }  // extern "C"

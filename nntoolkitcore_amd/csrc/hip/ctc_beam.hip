@@ -84,6 +84,45 @@ __device__ __forceinline__ u64 beam_hash(u64 h, int c) {
     return x ^ (x >> 31);
 }
 __device__ __forceinline__ xf xf_add2(xf a, xf b) { return xf_add3(a, b, xf_zero()); }
+// ln(p_b + p_nb) of a final entry, once per hypothesis: double, libm log.  One expression for the one-shot and the streaming form.
+__device__ __forceinline__ float beam_score(float4 m) {
+    xf pb, pnb;
+    pb.m = m.x; pb.e = __float_as_int(m.y);
+    pnb.m = m.z; pnb.e = __float_as_int(m.w);
+    const xf s = xf_add2(pb, pnb);
+    return (float)((double)s.e * 0.69314718055994530942 + log((double)s.m));
+}
+
+// ---- streaming: the beam a row carries from one push to the next (INTEGRATION.md "CTC prefix beam search", Streaming).  Plain global
+// memory, a slot per row: written once per push with ordinary stores by the row's workgroup, read back by the same row's workgroup of
+// the next launch on the stream.  ctl = [4][B] ints the host uploads per push: frames in this push | frames the row had seen before it
+// (0: the row starts from the empty prefix and its slot is not read) | which half of the label strings is current | unused.
+struct BeamCarry {
+    float4 *mass;                         // [B][W] p_b, p_nb (mantissa, exponent each)
+    u64 *h, *ph;                          // [B][W] prefix hash, parent prefix hash
+    int2 *tail;                           // [B][W] last class, length
+    int *nb;                              // [B] entries; 0: the beam has died
+    const int *seen;                      // ctl + B
+};
+// buffer of a streaming handle, in 4-byte words; every part starts on a 16-byte boundary
+struct BeamStreamLayout { size_t ctl, nb, mass, h, ph, tail, str, hist, cut, total; };
+static BeamStreamLayout beam_stream_layout(int B, int T, int W, int ncut, int L) {
+    BeamStreamLayout l;
+    const size_t b = B > 0 ? (size_t)B : 0, t = T > 0 ? (size_t)T : 0, w = W > 0 ? (size_t)W : 0, n = ncut > 0 ? (size_t)ncut : 0;
+    const size_t ml = L > 0 ? (size_t)L : 0;
+    auto up = [](size_t x) { return (x + 3) & ~(size_t)3; };
+    l.ctl = 0;
+    l.nb = up(4 * b);
+    l.mass = l.nb + up(b);
+    l.h = l.mass + 4 * b * w;
+    l.ph = l.h + up(2 * b * w);
+    l.tail = l.ph + up(2 * b * w);
+    l.str = l.tail + up(2 * b * w);
+    l.hist = l.str + up(2 * b * w * ml);
+    l.cut = l.hist + up(2 * b * t * w);
+    l.total = l.cut + up(2 * b * t * n) + 4;
+    return l;
+}
 
 // ---- class cut: the n non-blank classes of highest probability (ties: the lower class), ascending class order ----
 __global__ __launch_bounds__(CTC_THREADS) void ctc_beam_cut_kernel(const float *__restrict__ probs, int T, int C, int blank, int n,
@@ -132,11 +171,13 @@ __global__ __launch_bounds__(CTC_THREADS) void ctc_beam_cut_kernel(const float *
 }
 
 // ---- the beam: one workgroup per row ----
-template <bool CUT, bool STAGE>
+// STREAM: T is the capacity of a push and lens its frame counts; the beam starts from the row's slot of `cs` (or the empty prefix, for
+// a row that has seen no frame) and ends there; the masses of the frames in between are not kept.
+template <bool CUT, bool STAGE, bool STREAM>
 __global__ __launch_bounds__(CTC_THREADS) void ctc_beam_kernel(const float *__restrict__ probs, int T, int C, int blank, int W, int n,
                                                                unsigned magic, const int *__restrict__ lens, int *__restrict__ nfin,
                                                                int2 *__restrict__ hist, float4 *__restrict__ mass,
-                                                               const float2 *__restrict__ pairs) {
+                                                               const float2 *__restrict__ pairs, BeamCarry cs) {
     extern __shared__ __align__(16) unsigned char beam_smem[];
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const u64 lt = (1ull << lane) - 1;
@@ -167,7 +208,28 @@ __global__ __launch_bounds__(CTC_THREADS) void ctc_beam_kernel(const float *__re
 
     auto div_n1 = [&](int idx) { return n1 == 1 ? idx : (int)__umulhi((unsigned)idx, magic); };
 
-    if (tid == 0) {
+    // the row's beam: the carried one, or the empty prefix
+    const bool carried = STREAM && cs.seen[b] > 0;
+    int nb = 1, cur = 0;
+    if (STREAM) {
+        if (Tb == 0) return;                                                   // uniform: nothing to do, the slot stays as it is
+        if (carried) nb = min(max(cs.nb[b], 0), W);
+        if (nb == 0) return;                                                   // a dead beam stays dead
+    }
+    if (carried) {
+        if (tid < nb) {
+            const long q = (long)b * W + tid;
+            const float4 m = cs.mass[q];
+            const int2 tl = cs.tail[q];
+            s_pb[tid] = make_float2(m.x, m.y);
+            s_pnb[tid] = make_float2(m.z, m.w);
+            s_h[tid] = cs.h[q];
+            s_ph[tid] = cs.ph[q];
+            s_last[tid] = tl.x;
+            s_len[tid] = tl.y;
+            s_home[tid] = -1;
+        }
+    } else if (tid == 0) {
         s_pb[0] = xf_pack(xf_one());
         s_pnb[0] = xf_pack(xf_zero());
         s_h[0] = 0x243F6A8885A308D3ull;
@@ -180,9 +242,8 @@ __global__ __launch_bounds__(CTC_THREADS) void ctc_beam_kernel(const float *__re
         if (CUT) for (int k = tid; k < M; k += CTC_THREADS) spair[k] = crow[k];
         else for (int k = tid; k < M; k += CTC_THREADS) srow[k] = prow[k];
     }
-    __syncthreads();
+    __syncthreads();                                                           // the slot's words are in LDS: the stores needed them
 
-    int nb = 1, cur = 0;
     for (int t = 0; t < Tb; ++t) {
         const int o = cur * W, on = (cur ^ 1) * W;                             // this frame's beam, the next one's
         const float *grow = prow + (long)t * C;
@@ -420,12 +481,26 @@ __global__ __launch_bounds__(CTC_THREADS) void ctc_beam_kernel(const float *__re
         if (tid < Wt) {
             const float2 pb = s_pb[on + tid], pnb = s_pnb[on + tid];
             hrow[(long)t * W + tid] = f_rec[tid];
-            mrow[(long)t * W + tid] = make_float4(pb.x, pb.y, pnb.x, pnb.y);
+            if (!STREAM) mrow[(long)t * W + tid] = make_float4(pb.x, pb.y, pnb.x, pnb.y);
         }
         nb = Wt;
         cur ^= 1;
     }
-    if (tid == 0) nfin[b] = nb;
+    if (STREAM) {
+        // the beam this push leaves (written in LDS before the loop's last barrier)
+        if (tid < nb) {
+            const int o = cur * W + tid;
+            const long q = (long)b * W + tid;
+            const float2 pb = s_pb[o], pnb = s_pnb[o];
+            cs.mass[q] = make_float4(pb.x, pb.y, pnb.x, pnb.y);
+            cs.h[q] = s_h[o];
+            cs.ph[q] = s_ph[o];
+            cs.tail[q] = make_int2(s_last[o], s_len[o]);
+        }
+        if (tid == 0) cs.nb[b] = nb;
+    } else if (tid == 0) {
+        nfin[b] = nb;
+    }
 }
 
 // ---- backtrack: hypothesis k of a row is entry k of its last frame ----
@@ -451,13 +526,7 @@ __global__ __launch_bounds__(CTC_THREADS) void ctc_beam_backtrack_kernel(int T, 
                 score = 0.0f;
             } else {
                 len = hrow[(long)(Tb - 1) * W + tid].x >> 8;
-                const float4 m = mrow[(long)(Tb - 1) * W + tid];
-                xf pb, pnb;
-                pb.m = m.x; pb.e = __float_as_int(m.y);
-                pnb.m = m.z; pnb.e = __float_as_int(m.w);
-                const xf s = xf_add2(pb, pnb);
-                // once per hypothesis: double, libm log
-                score = (float)((double)s.e * 0.69314718055994530942 + log((double)s.m));
+                score = beam_score(mrow[(long)(Tb - 1) * W + tid]);
             }
         }
         pos = len - 1;
@@ -486,6 +555,85 @@ __global__ __launch_bounds__(CTC_THREADS) void ctc_beam_backtrack_kernel(int T, 
     for (long q = tid; q < cells; q += CTC_THREADS) {
         const int k = (int)(q / T), p = (int)(q % T);
         if (p >= s_hlen[k]) lab[q] = -1;
+    }
+}
+
+// ---- streaming commit: a workgroup per row, a lane per surviving entry.  The lane walks the push's records from its last frame to its
+// first, which gives the labels the entry gained inside the push (a record carries the length after it, so each label knows its
+// place) and the rank it descends from at the push's start; the entry's string = that ancestor's stored string + those labels goes
+// to the other half of the double-buffered store, cut at L labels, and the first nbest entries go to the outputs as well.  A row
+// without frames in this push only rewrites its outputs from what it holds.
+__global__ __launch_bounds__(CTC_THREADS) void ctc_beam_commit_kernel(int B, int T, int W, int nbest, int L, const int *__restrict__ ctl,
+                                                                      BeamCarry cs, const int2 *__restrict__ hist, int *__restrict__ strs,
+                                                                      int *__restrict__ labels, int *__restrict__ out_len,
+                                                                      float *__restrict__ scores) {
+    extern __shared__ __align__(16) unsigned char beam_smem[];
+    __shared__ int s_hlen[BEAM_MAX_W], s_anc[BEAM_MAX_W], s_alen[BEAM_MAX_W];
+    int2 *rec = (int2 *)beam_smem;
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const int Tb = ctl[b], seen = ctl[B + b], par = ctl[2 * B + b] & 1;
+    const bool fresh = seen == 0 && Tb == 0;                                   // no frame since the reset: the empty prefix alone
+    const int nb = fresh ? 1 : min(max(cs.nb[b], 0), W);
+    const int nh = min(nbest, nb);
+    const int *src = strs + ((long)par * B + b) * W * L;
+    int *dst = strs + ((long)(par ^ 1) * B + b) * W * L;
+    const int2 *hrow = hist + (long)b * T * W;
+    int *lab = labels + (long)b * nbest * L;
+    int len = -1;
+    if (tid < nb) len = fresh ? 0 : cs.tail[(long)b * W + tid].y;
+    if (tid < nbest) {
+        float score = -INFINITY;
+        if (tid < nh) score = fresh ? 0.0f : beam_score(cs.mass[(long)b * W + tid]);
+        out_len[(long)b * nbest + tid] = tid < nh ? len : -1;
+        scores[(long)b * nbest + tid] = score;
+    }
+    if (tid < W) s_hlen[tid] = len;
+    const long cells_out = (long)nbest * L;
+    if (Tb == 0 || nb == 0) {
+        __syncthreads();
+        for (long q = tid; q < cells_out; q += CTC_THREADS) {
+            const int k = (int)(q / L), p = (int)(q % L);
+            lab[q] = (k < nh && p < min(s_hlen[k], L)) ? src[(long)k * L + p] : -1;
+        }
+        return;
+    }
+    int rank = tid, gained = 0;
+    const int TC = max(1, BEAM_BT_RECORDS / W);
+    for (int t1 = Tb; t1 > 0; t1 -= TC) {
+        const int t0 = max(0, t1 - TC);
+        const long base = (long)t0 * W;
+        const int cnt = (t1 - t0) * W;
+        __syncthreads();
+        for (int q = tid; q < cnt; q += CTC_THREADS) rec[q] = hrow[base + q];
+        __syncthreads();
+        if (tid < nb) {
+            for (int t = t1 - 1; t >= t0; --t) {
+                const int2 r = rec[(t - t0) * W + rank];
+                if (r.y >= 0) {
+                    const int pos = (r.x >> 8) - 1;
+                    if (pos < L) {
+                        dst[(long)tid * L + pos] = r.y;
+                        if (tid < nbest) lab[(long)tid * L + pos] = r.y;
+                    }
+                    ++gained;
+                }
+                rank = r.x & 0xff;
+            }
+        }
+    }
+    if (tid < nb) { s_anc[tid] = rank; s_alen[tid] = len - gained; }
+    __syncthreads();
+    // the ancestors' strings, and the -1 behind every reported hypothesis; the places in between were written above
+    const long cells = (long)max(nb, nbest) * L;
+    for (long q = tid; q < cells; q += CTC_THREADS) {
+        const int k = (int)(q / L), p = (int)(q % L);
+        if (k < nb && p < min(s_alen[k], L)) {
+            const int v = src[(long)s_anc[k] * L + p];
+            dst[(long)k * L + p] = v;
+            if (k < nbest) lab[(long)k * L + p] = v;
+        } else if (k < nbest && (k >= nh || p >= min(s_hlen[k], L))) {
+            lab[(long)k * L + p] = -1;
+        }
     }
 }
 
@@ -523,9 +671,9 @@ int nntk_shim_ctc_beam_decode(const float *d_probs, int B, int T, int C, const i
     const unsigned magic = n + 1 > 1 ? (unsigned)(0x100000000ull / (unsigned)(n + 1)) + 1u : 0u;
 #define BEAM_GO(CUT, STAGE)                                                                                                        \
     do {                                                                                                                           \
-        if (lds > 48 * 1024 && nntk_set_max_dynamic_lds((const void *)ctc_beam_kernel<CUT, STAGE>, lds)) return -1;                \
-        hipLaunchKernelGGL((ctc_beam_kernel<CUT, STAGE>), dim3((unsigned)B), dim3(CTC_THREADS), lds, nntk_stream(), d_probs, T, C,   \
-                           blank, W, n, magic, d_lens, d_nfin, d_hist, d_mass, d_pairs);                                           \
+        if (lds > 48 * 1024 && nntk_set_max_dynamic_lds((const void *)ctc_beam_kernel<CUT, STAGE, false>, lds)) return -1;         \
+        hipLaunchKernelGGL((ctc_beam_kernel<CUT, STAGE, false>), dim3((unsigned)B), dim3(CTC_THREADS), lds, nntk_stream(), d_probs,  \
+                           T, C, blank, W, n, magic, d_lens, d_nfin, d_hist, d_mass, d_pairs, BeamCarry());                        \
     } while (0)
     if (ncut) { if (stage) BEAM_GO(true, true); else BEAM_GO(true, false); }
     else { if (stage) BEAM_GO(false, true); else BEAM_GO(false, false); }
@@ -536,6 +684,72 @@ int nntk_shim_ctc_beam_decode(const float *d_probs, int B, int T, int C, const i
     hipLaunchKernelGGL(ctc_beam_backtrack_kernel, dim3((unsigned)B), dim3(CTC_THREADS), blds, nntk_stream(), T, W, nbest, d_lens, d_nfin,
                        d_hist, d_mass, d_labels_out, d_out_lengths, d_scores);
     NNTK_LAUNCH_CHECK("ctc_beam_backtrack_kernel");
+    return 0;
+}
+
+// ---- streaming form: the handle's buffer (beam_stream_layout), one push ----
+size_t nntk_shim_ctc_beam_stream_floats(int batch, int max_frames, int C, int beam_width, int cutoff_top_n, int max_labels) {
+    return beam_stream_layout(batch, max_frames, beam_width, beam_ncut(C, cutoff_top_n), max_labels).total;
+}
+
+// the limits of the kernel that only the launch knows in the one-shot call; no device is touched
+int nntk_shim_ctc_beam_stream_check(int C, int W, int cutoff_top_n) {
+    const int ncut = beam_ncut(C, cutoff_top_n), n = ncut ? ncut : C - 1;
+    if (W < 1 || W > BEAM_MAX_W || (long)W * (n + 1) > BEAM_MAX_CELLS)
+        return nntk_fail_msg("nntk_ctc_beam_stream_create: beam_width or beam_width * (classes + 1) beyond the kernel's limits");
+    if (beam_lds(W, n, C, ncut != 0, false).total > CTC_LDS_LIMIT)
+        return nntk_fail_msg("nntk_ctc_beam_stream_create: the beam does not fit one workgroup's LDS");
+    return 0;
+}
+
+int nntk_shim_ctc_beam_stream_push(const float *d_probs, int B, int T, int C, const int *h_ctl, int any_frames, int blank, int W,
+                                   int cutoff_top_n, int nbest, int L, int *d_labels_out, int *d_out_lengths, float *d_scores,
+                                   float *d_buf) {
+    if (B <= 0) return 0;
+    if (((uintptr_t)d_buf & 15) != 0) return nntk_fail_msg("nntk_ctc_beam_stream_push_device: the handle's buffer is not 16-byte aligned");
+    const int ncut = beam_ncut(C, cutoff_top_n), n = ncut ? ncut : C - 1;
+    const BeamStreamLayout lay = beam_stream_layout(B, T, W, ncut, L);
+    int *d_ctl = (int *)d_buf;
+    BeamCarry cs;
+    cs.nb = (int *)(d_buf + lay.nb);
+    cs.mass = (float4 *)(d_buf + lay.mass);
+    cs.h = (u64 *)(d_buf + lay.h);
+    cs.ph = (u64 *)(d_buf + lay.ph);
+    cs.tail = (int2 *)(d_buf + lay.tail);
+    cs.seen = d_ctl + B;
+    int *d_strs = (int *)(d_buf + lay.str);
+    int2 *d_hist = (int2 *)(d_buf + lay.hist);
+    float2 *d_pairs = (float2 *)(d_buf + lay.cut);
+    if (nntk_shim_upload_ints(d_ctl, h_ctl, 4L * B)) return -1;
+    if (any_frames) {
+        const long frames = (long)B * T;
+        if (ncut) {
+            long g = (frames + 3) / 4;
+            if (g > 16384) g = 16384;
+            hipLaunchKernelGGL(ctc_beam_cut_kernel, dim3((unsigned)g), dim3(CTC_THREADS), 0, nntk_stream(), d_probs, T, C, blank, n, d_ctl,
+                               d_pairs, frames);
+            NNTK_LAUNCH_CHECK("ctc_beam_cut_kernel");
+        }
+        const bool stage = beam_lds(W, n, C, ncut != 0, true).total <= CTC_LDS_LIMIT;
+        const size_t lds = beam_lds(W, n, C, ncut != 0, stage).total;
+        if (lds > CTC_LDS_LIMIT) return nntk_fail_msg("nntk_ctc_beam_stream_push_device: the beam does not fit one workgroup's LDS");
+        const unsigned magic = n + 1 > 1 ? (unsigned)(0x100000000ull / (unsigned)(n + 1)) + 1u : 0u;
+#define BEAM_GO(CUT, STAGE)                                                                                                        \
+    do {                                                                                                                           \
+        if (lds > 48 * 1024 && nntk_set_max_dynamic_lds((const void *)ctc_beam_kernel<CUT, STAGE, true>, lds)) return -1;          \
+        hipLaunchKernelGGL((ctc_beam_kernel<CUT, STAGE, true>), dim3((unsigned)B), dim3(CTC_THREADS), lds, nntk_stream(), d_probs,   \
+                           T, C, blank, W, n, magic, d_ctl, (int *)nullptr, d_hist, (float4 *)nullptr, d_pairs, cs);               \
+    } while (0)
+        if (ncut) { if (stage) BEAM_GO(true, true); else BEAM_GO(true, false); }
+        else { if (stage) BEAM_GO(false, true); else BEAM_GO(false, false); }
+#undef BEAM_GO
+        NNTK_LAUNCH_CHECK("ctc_beam_kernel");
+    }
+    const size_t blds = (size_t)BEAM_BT_RECORDS * sizeof(int2);
+    if (nntk_set_max_dynamic_lds((const void *)ctc_beam_commit_kernel, blds)) return -1;
+    hipLaunchKernelGGL(ctc_beam_commit_kernel, dim3((unsigned)B), dim3(CTC_THREADS), blds, nntk_stream(), B, T, W, nbest, L, d_ctl, cs,
+                       d_hist, d_strs, d_labels_out, d_out_lengths, d_scores);
+    NNTK_LAUNCH_CHECK("ctc_beam_commit_kernel");
     return 0;
 }
 

@@ -160,11 +160,23 @@ int nntk_shim_ctc_loss(const float *d_probs, int B, int T, int C, const int *h_i
                        const int *h_label_lengths, int max_label_len, int blank, float *d_loss_rows, float *d_dprobs, float *d_ws);
 int nntk_shim_ctc_greedy_decode(const float *d_probs, int B, int T, int C, const int *h_input_lengths, int blank, int *d_labels_out,
                                 int *d_out_lengths);
+/* the chunk's labels only: d_prev [B] device, in/out, the argmax of each row's last frame seen (-1: none) */
+int nntk_shim_ctc_greedy_decode_stream(const float *d_probs, int B, int T, int C, const int *h_input_lengths, int blank, int *d_prev,
+                                       int *d_labels_out, int *d_out_lengths);
 /* ---- CTC prefix beam search (ctc_beam.hip): the n-best prefixes of every row with their log-probabilities.  h_input_lengths is HOST
  *      memory, checked by the caller (train.c), never NULL; d_ws 16-byte aligned, nntk_shim_ctc_beam_workspace_floats words ---- */
 size_t nntk_shim_ctc_beam_workspace_floats(int batch, int T, int C, int beam_width, int cutoff_top_n);
 int nntk_shim_ctc_beam_decode(const float *d_probs, int B, int T, int C, const int *h_input_lengths, int blank, int beam_width,
                               int cutoff_top_n, int nbest, int *d_labels_out, int *d_out_lengths, float *d_scores, float *d_ws);
+/* streaming form: d_buf = the handle's buffer, nntk_shim_ctc_beam_stream_floats words, 16-byte aligned, kept from push to push (the
+ * carried beam, both halves of the label strings, the records and cut pairs of one push).  h_ctl HOST [4][B], built by train.c:
+ * frames in this push | frames the row had seen before it | the current half of its label strings | 0.  any_frames 0: no row brings
+ * a frame, only the outputs are rewritten.  _check: the launch-time limits, without a device. */
+size_t nntk_shim_ctc_beam_stream_floats(int batch, int max_frames, int C, int beam_width, int cutoff_top_n, int max_labels);
+int nntk_shim_ctc_beam_stream_check(int C, int beam_width, int cutoff_top_n);
+int nntk_shim_ctc_beam_stream_push(const float *d_probs, int B, int max_frames, int C, const int *h_ctl, int any_frames, int blank,
+                                   int beam_width, int cutoff_top_n, int nbest, int max_labels, int *d_labels_out, int *d_out_lengths,
+                                   float *d_scores, float *d_buf);
 /* ---- CTC forced alignment (ctc_align.hip): the best single alignment of every row to its labels -- the state of every frame, the
  *      frame span of every label, ln of the path's probability.  The int arrays are HOST memory, already checked by the caller
  *      (train.c), never NULL; d_states / d_spans may be NULL; d_ws 16-byte aligned, nntk_shim_ctc_align_workspace_floats words ---- */

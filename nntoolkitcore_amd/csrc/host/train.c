@@ -323,6 +323,141 @@ int nntk_ctc_beam_decode(const float *probs, int batch, int T, int C, const int 
     return nntk_shim_download(scores, d_o + nl + nh, nh * sizeof(float));
 }
 
+/* ---- streaming CTC decoding (INTEGRATION.md "CTC prefix beam search", Streaming).  The beam lives in the handle's device buffer; which
+ *      rows are new, how many frames each has seen and which half of its label strings is current is host bookkeeping, uploaded with
+ *      every push: a reset touches no device memory ---- */
+#define CTC_BEAM_MAX_T ((1 << 23) - 1)
+struct NntkCtcBeamStreamStruct {
+    int batch, max_frames, C, blank, beam_width, cutoff_top_n, nbest, max_labels;
+    int *frames;                    /* [batch] frames since the row's reset */
+    int *half;                      /* [batch] the current half of the row's label strings */
+    int *ctl;                       /* [4][batch] staging of one push */
+    nntk_devbuf d_buf;              /* nntk_shim_ctc_beam_stream_floats words, reserved by the first push */
+    nntk_devbuf d_io;               /* the host-pointer push: probabilities | labels | lengths | scores */
+};
+
+size_t nntk_ctc_beam_stream_state_bytes(int batch, int max_frames, int C, int beam_width, int cutoff_top_n, int max_labels) {
+    return sizeof(float) * nntk_shim_ctc_beam_stream_floats(batch, max_frames, C, beam_width, cutoff_top_n, max_labels);
+}
+
+NntkCtcBeamStream nntk_ctc_beam_stream_create(int batch, int max_frames, int C, int blank, int beam_width, int cutoff_top_n, int nbest,
+                                              int max_labels) {
+    static const char who[] = "nntk_ctc_beam_stream_create";
+    nntk_shim_clear_error();
+    if (ctc_beam_check(who, batch, 0, C, NULL, blank, beam_width, cutoff_top_n, nbest)) return NULL;
+    if (max_frames < 1) { ctc_fail(who, "max_frames %d < 1", max_frames, 0, 0); return NULL; }
+    if (max_labels < 1) { ctc_fail(who, "max_labels %d < 1", max_labels, 0, 0); return NULL; }
+    if (nntk_shim_ctc_beam_stream_check(C, beam_width, cutoff_top_n)) return NULL;
+    NntkCtcBeamStream s = (NntkCtcBeamStream)calloc(1, sizeof *s);
+    const size_t rows = (size_t)(batch > 0 ? batch : 1);
+    if (s) {
+        s->frames = (int *)calloc(rows, sizeof(int));
+        s->half = (int *)calloc(rows, sizeof(int));
+        s->ctl = (int *)calloc(4 * rows, sizeof(int));
+    }
+    if (!s || !s->frames || !s->half || !s->ctl) {
+        nntk_ctc_beam_stream_destroy(s);
+        nntk_set_error("out of host memory");
+        return NULL;
+    }
+    s->batch = batch; s->max_frames = max_frames; s->C = C; s->blank = blank;
+    s->beam_width = beam_width; s->cutoff_top_n = cutoff_top_n; s->nbest = nbest; s->max_labels = max_labels;
+    return s;
+}
+
+void nntk_ctc_beam_stream_destroy(NntkCtcBeamStream s) {
+    if (!s) return;
+    nntk_devbuf_free(&s->d_buf);
+    nntk_devbuf_free(&s->d_io);
+    free(s->frames);
+    free(s->half);
+    free(s->ctl);
+    free(s);
+}
+
+int nntk_ctc_beam_stream_reset(NntkCtcBeamStream s, const int *rows, int n_rows) {
+    static const char who[] = "nntk_ctc_beam_stream_reset";
+    nntk_shim_clear_error();
+    if (!s) NNTK_FAIL("nntk_ctc_beam_stream_reset: NULL handle");
+    if (n_rows < 0) return ctc_fail(who, "n_rows %d < 0", n_rows, 0, 0);
+    if (n_rows > 0 && !rows) NNTK_FAIL("nntk_ctc_beam_stream_reset: NULL rows");
+    for (int i = 0; i < n_rows; ++i)
+        if (rows[i] < 0 || rows[i] >= s->batch) return ctc_fail(who, "rows[%d] = %d is outside [0, %d)", i, rows[i], s->batch);
+    for (int i = 0; i < n_rows; ++i) s->frames[rows[i]] = 0;        /* the next push starts the row from the empty prefix */
+    return 0;
+}
+
+/* every check of a push; nothing is enqueued and nothing in the handle changes */
+static int beam_stream_check_push(const char *who, NntkCtcBeamStream s, const void *probs, const int *n_frames, const void *labels,
+                                  const void *lengths, const void *scores) {
+    if (!n_frames || !probs || !labels || !lengths || !scores) return ctc_fail(who, "NULL argument", 0, 0, 0);
+    for (int b = 0; b < s->batch; ++b) {
+        if (n_frames[b] < 0 || n_frames[b] > s->max_frames)
+            return ctc_fail(who, "n_frames[%d] = %d is outside [0, max_frames = %d]", b, n_frames[b], s->max_frames);
+        if (n_frames[b] > CTC_BEAM_MAX_T - s->frames[b])
+            return ctc_fail(who, "row %d would pass %d frames since its reset", b, CTC_BEAM_MAX_T, 0);
+    }
+    return 0;
+}
+
+int nntk_ctc_beam_stream_push_device(NntkCtcBeamStream s, const float *d_probs, const int *n_frames, const int *final,
+                                     int *d_labels_out, int *d_out_lengths, float *d_scores) {
+    static const char who[] = "nntk_ctc_beam_stream_push_device";
+    nntk_shim_clear_error();
+    if (!s) NNTK_FAIL("nntk_ctc_beam_stream_push_device: NULL handle");
+    if (s->batch == 0) return 0;
+    if (beam_stream_check_push(who, s, d_probs, n_frames, d_labels_out, d_out_lengths, d_scores)) return -1;
+    const int B = s->batch;
+    float *d_buf = nntk_devbuf_reserve(&s->d_buf, nntk_shim_ctc_beam_stream_floats(B, s->max_frames, s->C, s->beam_width, s->cutoff_top_n,
+                                                                                   s->max_labels));
+    if (!d_buf) return -1;
+    int any = 0;
+    for (int b = 0; b < B; ++b) {
+        s->ctl[b] = n_frames[b];
+        s->ctl[B + b] = s->frames[b];
+        s->ctl[2 * B + b] = s->half[b];
+        s->ctl[3 * B + b] = 0;
+        any |= n_frames[b] > 0;
+    }
+    if (nntk_shim_ctc_beam_stream_push(d_probs, B, s->max_frames, s->C, s->ctl, any, s->blank, s->beam_width, s->cutoff_top_n, s->nbest,
+                                       s->max_labels, d_labels_out, d_out_lengths, d_scores, d_buf)) return -1;
+    for (int b = 0; b < B; ++b) {
+        if (n_frames[b] > 0) { s->frames[b] += n_frames[b]; s->half[b] ^= 1; }
+        if (final && final[b]) s->frames[b] = 0;
+    }
+    return 0;
+}
+
+int nntk_ctc_beam_stream_push(NntkCtcBeamStream s, const float *probs, const int *n_frames, const int *final, int *labels_out,
+                              int *out_lengths, float *scores) {
+    static const char who[] = "nntk_ctc_beam_stream_push";
+    nntk_shim_clear_error();
+    if (!s) NNTK_FAIL("nntk_ctc_beam_stream_push: NULL handle");
+    if (s->batch == 0) return 0;
+    if (beam_stream_check_push(who, s, probs, n_frames, labels_out, out_lengths, scores)) return -1;
+    const size_t n = (size_t)s->batch * s->max_frames * s->C, nh = (size_t)s->batch * s->nbest, nl = nh * s->max_labels;
+    float *d_p = nntk_devbuf_reserve(&s->d_io, n + nl + 2 * nh + 4);
+    if (!d_p) return -1;
+    int *d_o = (int *)(d_p + n);
+    if (nntk_shim_upload(d_p, probs, n * sizeof(float))) return -1;
+    if (nntk_ctc_beam_stream_push_device(s, d_p, n_frames, final, d_o, d_o + nl, (float *)(d_o + nl + nh))) return -1;
+    if (nntk_shim_download(labels_out, d_o, nl * sizeof(int))) return -1;
+    if (nntk_shim_download(out_lengths, d_o + nl, nh * sizeof(int))) return -1;
+    return nntk_shim_download(scores, d_o + nl + nh, nh * sizeof(float));
+}
+
+int nntk_ctc_greedy_decode_stream_device(const float *d_probs, int batch, int T, int C, const int *n_frames, int blank, int *d_prev,
+                                         int *d_labels_out, int *d_out_lengths) {
+    static const char who[] = "nntk_ctc_greedy_decode_stream_device";
+    nntk_shim_clear_error();
+    if (ctc_check_shape(who, batch, T, C, blank)) return -1;
+    if (batch > 0 && !n_frames) NNTK_FAIL("nntk_ctc_greedy_decode_stream_device: NULL n_frames");
+    if (nntk_check_lengths(who, n_frames, batch, T, NULL, NULL)) return -1;
+    if (batch == 0) return 0;
+    if (!d_prev || !d_out_lengths || ((!d_probs || !d_labels_out) && T > 0)) NNTK_FAIL("nntk_ctc_greedy_decode_stream_device: NULL tensor");
+    return nntk_shim_ctc_greedy_decode_stream(d_probs, batch, T, C, n_frames, blank, d_prev, d_labels_out, d_out_lengths);
+}
+
 /* ---- CTC forced alignment (csrc/hip/ctc_align.hip) ---- */
 #define CTC_ALIGN_MAX_LABELS 4000
 static int ctc_align_check(const char *who, int batch, int T, int C, const int *input_lengths, const int *labels, const int *label_lengths,

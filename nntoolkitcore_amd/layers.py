@@ -677,6 +677,88 @@ def ctc_beam_decode(probs, input_lengths=None, blank=0, beam_width=16, cutoff_to
     return out, n, sc
 
 
+class CtcBeamStream:
+    """``nntk_ctc_beam_stream_*``: prefix beam search pushed chunk by chunk for ``batch`` independent streams.  After every push row
+    b holds what ``ctc_beam_decode_device`` gives on the row's frames since its last reset, bit for bit (INTEGRATION.md "CTC prefix
+    beam search", Streaming).  ``max_labels``: the capacity of the returned label strings (default: max_frames)."""
+
+    def __init__(self, batch, max_frames, C, blank=0, beam_width=16, cutoff_top_n=0, nbest=1, max_labels=None):
+        self.B, self.T, self.C, self.nbest = int(batch), int(max_frames), int(C), int(nbest)
+        self.max_labels = int(max_frames if max_labels is None else max_labels)
+        self.h = capi.load().nntk_ctc_beam_stream_create(self.B, self.T, self.C, blank, beam_width, cutoff_top_n, nbest, self.max_labels)
+        if not self.h:
+            raise capi.NNTKError("nntk_ctc_beam_stream_create: " + capi.last_error())
+
+    def _final(self, final):
+        if final is None:
+            return None, None
+        f = _host_ints(np.asarray(final).astype(np.int32), self.B, "final")
+        return f, f.ctypes.data_as(capi.ip)
+
+    def push(self, probs, n_frames, final=None, labels_out=None, out_lengths=None, scores=None):
+        """probs [B, max_frames, C] device tensor, n_frames / final host ints per row (a streaming stack's out, cnt, final) ->
+        (labels [B, nbest, max_labels] int32, lengths [B, nbest] int32, scores [B, nbest] float32), the rows' current n-best"""
+        import torch
+        assert tuple(probs.shape) == (self.B, self.T, self.C), "probs: [batch, max_frames, C]"
+        nf = _host_ints(n_frames, self.B, "n_frames")
+        f, fptr = self._final(final)
+        if labels_out is None:
+            labels_out = torch.empty((self.B, self.nbest, self.max_labels), dtype=torch.int32, device=probs.device)
+        if out_lengths is None:
+            out_lengths = torch.empty((self.B, self.nbest), dtype=torch.int32, device=probs.device)
+        if scores is None:
+            scores = torch.empty((self.B, self.nbest), dtype=torch.float32, device=probs.device)
+        check(capi.load().nntk_ctc_beam_stream_push_device(self.h, _dp(probs), nf.ctypes.data_as(capi.ip), fptr,
+                                                           C.c_void_p(labels_out.data_ptr()), C.c_void_p(out_lengths.data_ptr()),
+                                                           _dp(scores)), "nntk_ctc_beam_stream_push_device")
+        return labels_out, out_lengths, scores
+
+    def push_host(self, probs, n_frames, final=None):
+        """The host-memory form (``nntk_ctc_beam_stream_push``): probs [B, max_frames, C] numpy array."""
+        probs = _f32(probs)
+        assert probs.shape == (self.B, self.T, self.C), "probs: [batch, max_frames, C]"
+        nf = _host_ints(n_frames, self.B, "n_frames")
+        f, fptr = self._final(final)
+        out = np.empty((self.B, self.nbest, self.max_labels), np.int32)
+        n, sc = np.empty((self.B, self.nbest), np.int32), np.empty((self.B, self.nbest), np.float32)
+        check(capi.load().nntk_ctc_beam_stream_push(self.h, _p(probs), nf.ctypes.data_as(capi.ip), fptr, out.ctypes.data_as(capi.ip),
+                                                    n.ctypes.data_as(capi.ip), _p(sc)), "nntk_ctc_beam_stream_push")
+        return out, n, sc
+
+    def reset(self, rows):
+        """these rows start new streams"""
+        rows = np.ascontiguousarray(np.asarray(rows, dtype=np.int32).reshape(-1))
+        check(capi.load().nntk_ctc_beam_stream_reset(self.h, rows.ctypes.data_as(capi.ip), rows.shape[0]), "nntk_ctc_beam_stream_reset")
+
+    def close(self):
+        if self.h:
+            capi.load().nntk_ctc_beam_stream_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def ctc_greedy_decode_stream_device(probs, n_frames, prev, blank=0, labels_out=None, out_lengths=None):
+    """``nntk_ctc_greedy_decode_stream_device``: the labels this chunk adds.  probs [B,T,C]; n_frames host ints per row; prev [B] int32
+    device tensor, updated in place (-1 = a new stream) -> (labels [B,T] int32, -1 behind each row's labels; lengths [B])"""
+    import torch
+    B, T, Cc = probs.shape
+    nf = _host_ints(n_frames, B, "n_frames")
+    assert prev.is_cuda and prev.dtype == torch.int32 and prev.is_contiguous() and prev.numel() == B, "prev: [B] int32 device tensor"
+    if labels_out is None:
+        labels_out = torch.empty((B, T), dtype=torch.int32, device=probs.device)
+    if out_lengths is None:
+        out_lengths = torch.empty(B, dtype=torch.int32, device=probs.device)
+    check(capi.load().nntk_ctc_greedy_decode_stream_device(_dp(probs), B, T, Cc, nf.ctypes.data_as(capi.ip), blank,
+                                                           C.c_void_p(prev.data_ptr()), C.c_void_p(labels_out.data_ptr()),
+                                                           C.c_void_p(out_lengths.data_ptr())), "nntk_ctc_greedy_decode_stream_device")
+    return labels_out, out_lengths
+
+
 def ctc_align_device(probs, labels, label_lengths=None, input_lengths=None, blank=0, states=None, spans=None, scores=None, workspace=None):
     """``nntk_ctc_align_device``: the best alignment of probs [B,T,C] to the labels (as for ``ctc_loss_device``) -> (states [B,T] int32,
     the extended state of every frame, -1 behind each row; spans [B,max_label_len,2] int32, each label's first frame and one past
