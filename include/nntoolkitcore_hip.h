@@ -886,7 +886,7 @@ int nntk_ctc_greedy_decode(const float *probs, int batch, int T, int C, const in
                            int *out_lengths);
 
 /* ---- CTC prefix beam search (csrc/hip/ctc_beam.hip; INTEGRATION.md "CTC prefix beam search") ----
- * Acoustic scores only: per row the beam_width most probable label prefixes are kept per frame, each with the summed mass of ALL its
+ * Acoustic scores only (nntk_ctc_beam_decode_lm_device below fuses an n-gram language model): per row the beam_width most probable label prefixes are kept per frame, each with the summed mass of ALL its
  * alignments (ending in blank, p_b; ending in its last label, p_nb), and the nbest best after the row's last frame are returned.
  *   d_probs [batch][T][C] probabilities; input_lengths HOST int [batch] or NULL (= all T); frames t >= input_lengths[b] influence
  *     nothing and may hold NaN.  Host arrays are checked before anything is enqueued: -1, nntk_last_error(), nothing written.
@@ -949,6 +949,50 @@ int nntk_ctc_beam_stream_reset(NntkCtcBeamStream s, const int *rows, int n_rows)
 void nntk_ctc_beam_stream_destroy(NntkCtcBeamStream s);
 int nntk_ctc_beam_stream_push(NntkCtcBeamStream s, const float *probs, const int *n_frames, const int *final, int *labels_out,
                               int *out_lengths, float *scores);
+/* ---- language-model fusion (INTEGRATION.md "CTC prefix beam search", Language-model fusion) ----
+ * A token-level n-gram model as a deterministic backoff automaton (the usual ARPA-to-automaton form).  State 0 is the empty context;
+ * state s owns the arcs [arc_begin[s], arc_begin[s+1]), labels strictly ascending, in [0, n_classes), never blank; an arc carries a
+ * natural-log conditional probability and the next state.  backoff_state[0] == -1 and 0 <= backoff_state[s] < s for s > 0 (shorter
+ * contexts first); backoff_logw finite; final_logp [n_states] (may hold -inf) or NULL: the end-of-sentence log-probability from each
+ * state, already backed off.  The walk from state s on label c takes backoffs until a state has an arc labelled c, or state 0 has none:
+ *   F(s, c) = B(s_0) B(s_1) ... G(arc), next = arc_next;   or   F = B(s_0) ... U, next = 0      with
+ *   G = exp(alpha arc_logp + beta), B(s) = exp(alpha backoff_logw[s]), U = exp(alpha unk_logp + beta), E(s) = exp(alpha final_logp[s])
+ *   (E = 1 without final_logp).  Each factor is computed in double and rounded once to an f32 mantissa with an int exponent; the
+ *   product runs from left to right.  alpha == 0 switches the model off (every G and U is exp(beta), every B and E is 1); alpha == 0
+ *   and beta == 0 make every factor exactly 1.
+ * create checks all of it before it allocates anything and never touches a device: NULL + nntk_last_error() for an arc_begin that does
+ * not start at 0, is not monotone or reaches 2^31; labels out of range, unsorted or blank; arc_next / start_state / backoff_state out of
+ * range; NaN or +inf anywhere, a non-finite backoff_logw; alpha < 0 or not finite, beta not finite; blank outside [0, n_classes); a
+ * factor whose natural log lies outside [-65536, 65536].  The arrays are copied.  The device tables (nntk_ngram_lm_device_bytes: 16
+ * bytes per arc, 32 per state) are uploaded by the first decode that uses the handle; one handle belongs to one device.
+ * nntk_ngram_lm_score (host only): the sum of ln F along labels from start_state, plus ln E of the last state when with_final, in
+ * double from the unrounded values: fused score - nntk_ngram_lm_score = the acoustic score.  NaN + nntk_last_error() for a bad label.
+ *
+ * nntk_ctc_beam_decode_lm_device: nntk_ctc_beam_decode_device with the model fused in.  Every beam entry carries an LM state (the
+ * empty prefix: start_state); a stay keeps it; the extend cell (i, c) holds F(state_i, c) times the acoustic value above (one more
+ * multiply) and its entry takes next(state_i, c).  After the row's last frame every total is multiplied by E(state), exact zeros are
+ * dropped, the rest are ordered descending (ties: the lower rank of the last beam) and the first nbest are reported with
+ * score = ln(product).  A row without frames reports the empty prefix with score ln E(start_state).  lm == NULL: the acoustic call's
+ * bits.  -1, nothing written, when lm was built for another class count or blank.  Workspace: nntk_ctc_beam_lm_workspace_floats.
+ * nntk_ctc_beam_stream_create_lm: the streaming handle with a model, which must outlive the stream (NULL: nntk_ctc_beam_stream_create);
+ * after every push a row's outputs are the bits of nntk_ctc_beam_decode_lm_device on its frames since the reset -- the E step applies
+ * to what is reported, never to the carried beam.  nntk_ctc_beam_stream_state_bytes_lm: 4 more bytes per row and beam entry. */
+typedef struct NntkNgramLmStruct *NntkNgramLm;
+NntkNgramLm nntk_ngram_lm_create(int n_classes, int blank, int n_states, const long *arc_begin, const int *arc_label, const float *arc_logp,
+                                 const int *arc_next, const int *backoff_state, const float *backoff_logw, const float *final_logp,
+                                 int start_state, float unk_logp, float alpha, float beta);
+double nntk_ngram_lm_score(NntkNgramLm lm, const int *labels, int n, int with_final);
+size_t nntk_ngram_lm_device_bytes(NntkNgramLm lm);
+void nntk_ngram_lm_destroy(NntkNgramLm lm);
+size_t nntk_ctc_beam_lm_workspace_floats(int batch, int T, int C, int beam_width, int cutoff_top_n);
+int nntk_ctc_beam_decode_lm_device(const float *d_probs, int batch, int T, int C, const int *input_lengths, int blank, int beam_width,
+                                   int cutoff_top_n, int nbest, NntkNgramLm lm, int *d_labels_out, int *d_out_lengths, float *d_scores,
+                                   float *d_workspace);
+int nntk_ctc_beam_decode_lm(const float *probs, int batch, int T, int C, const int *input_lengths, int blank, int beam_width,
+                            int cutoff_top_n, int nbest, NntkNgramLm lm, int *labels_out, int *out_lengths, float *scores);
+NntkCtcBeamStream nntk_ctc_beam_stream_create_lm(int batch, int max_frames, int C, int blank, int beam_width, int cutoff_top_n, int nbest,
+                                                 int max_labels, NntkNgramLm lm);
+size_t nntk_ctc_beam_stream_state_bytes_lm(int batch, int max_frames, int C, int beam_width, int cutoff_top_n, int max_labels);
 /* Streaming best path: the labels THIS chunk adds.  d_probs [batch][T][C]; n_frames HOST int [batch], 0..T; d_prev [batch] device
  * int, in/out: the argmax of the row's last frame seen, -1 = a new stream (the caller resets a row by writing -1); unchanged where
  * n_frames[b] == 0.  A frame whose argmax equals the previous frame's (d_prev[b] for the chunk's first) is dropped, then blanks are.

@@ -441,6 +441,17 @@ SIGNATURES = {
     "nntk_ctc_beam_stream_destroy": (None, [vp]),
     "nntk_ctc_beam_stream_push": (C.c_int, [vp, fp, ip, ip, ip, ip, fp]),
     "nntk_ctc_greedy_decode_stream_device": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, ip, C.c_int, vp, vp, vp]),
+    # language-model fusion (INTEGRATION.md "CTC prefix beam search", Language-model fusion)
+    "nntk_ngram_lm_create": (vp, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_long), ip, fp, ip, ip, fp, fp, C.c_int, C.c_float, C.c_float,
+                                  C.c_float]),
+    "nntk_ngram_lm_score": (C.c_double, [vp, ip, C.c_int, C.c_int]),
+    "nntk_ngram_lm_device_bytes": (C.c_size_t, [vp]),
+    "nntk_ngram_lm_destroy": (None, [vp]),
+    "nntk_ctc_beam_lm_workspace_floats": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "nntk_ctc_beam_decode_lm_device": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, ip, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp]),
+    "nntk_ctc_beam_decode_lm": (C.c_int, [fp, C.c_int, C.c_int, C.c_int, ip, C.c_int, C.c_int, C.c_int, C.c_int, vp, ip, ip, fp]),
+    "nntk_ctc_beam_stream_create_lm": (vp, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
+    "nntk_ctc_beam_stream_state_bytes_lm": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "nntk_ctc_align_workspace_floats": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "nntk_ctc_align_device": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, ip, ip, ip, C.c_int, C.c_int, vp, vp, vp, vp]),
     "nntk_ctc_align": (C.c_int, [fp, C.c_int, C.c_int, C.c_int, ip, ip, ip, C.c_int, C.c_int, ip, ip, fp]),

@@ -1,5 +1,5 @@
-// ctc_beam.hip -- CTC prefix beam search (Graves 2012; Hannun et al. 2014) on softmax probabilities [B][T][C], rows ragged, acoustic
-// scores only: per row the W best label prefixes per frame, each with the mass of its alignments ending in blank (p_b) and in its last
+// ctc_beam.hip -- CTC prefix beam search (Graves 2012; Hannun et al. 2014) on softmax probabilities [B][T][C], rows ragged, on acoustic
+// scores alone or fused with a token-level n-gram language model (the LM instantiations; "Language model" below): per row the W best label prefixes per frame, each with the mass of its alignments ending in blank (p_b) and in its last
 // label (p_nb), and after the last frame an n-best list with log-probabilities.  INTEGRATION.md "CTC prefix beam search" fixes the
 // semantics (candidate cells, merging, the canonical-index tie rule) exactly; this file follows them cell by cell.
 //
@@ -24,6 +24,15 @@
 // extend cell (i, c) when j's parent hash is i's hash, j is one label longer than i and j's last class is c.  Unlike a parent RANK,
 // this also recognises a prefix that left the beam and came back while its child stayed.  Two different prefixes of one length are
 // taken for one with probability 2^-64 per compared pair.
+//
+// Language model (LM instantiations only; the others are compiled without any of it).  Every beam entry carries the state of a
+// deterministic backoff automaton (one more int in the LDS state block, and in the carry of a stream).  The extend cell (i, c) is
+// multiplied by F(state_i, c): beam_lm_walk takes the state's backoffs until a state has an arc labelled c -- a binary search over the
+// state's sorted 16-byte arc records per step -- multiplying the backoff factors and the arc's factor from left to right, or the
+// unknown-label factor when state 0 has no such arc.  The walk is bounded by the table's longest backoff chain as a loop count as well
+// as by reaching state 0.  Cells stay 8 bytes: the next state is looked up again for the at most W surviving extend cells.  After the
+// row's last frame every total is multiplied by the end-of-sentence factor of its state and the entries are ranked again; the
+// backtrack (or the commit of a stream) reports in that order, and a stream carries the beam as it was before it.
 #include <stdint.h>
 #include <limits.h>
 #include "nntk_common.hpp"
@@ -39,9 +48,10 @@
 typedef unsigned long long u64;
 
 // workspace, in 4-byte words: [ints: input lengths B | final beam size B] [records: B*T*W int2] [masses: B*T*W float4]
-// [class cut: B*T*ncut (class, prob) pairs]; every part starts on a 16-byte boundary
-struct BeamLayout { size_t ints, hist, mass, cut, total; };
-static BeamLayout beam_layout(int B, int T, int W, int ncut) {
+// [class cut: B*T*ncut (class, prob) pairs] [LM only: final order B*W ints | final masses B*W float4]; every part starts on a 16-byte
+// boundary
+struct BeamLayout { size_t ints, hist, mass, cut, forder, fmass, total; };
+static BeamLayout beam_layout(int B, int T, int W, int ncut, bool lm = false) {
     BeamLayout l;
     const size_t b = B > 0 ? (size_t)B : 0, t = T > 0 ? (size_t)T : 0, w = W > 0 ? (size_t)W : 0, n = ncut > 0 ? (size_t)ncut : 0;
     auto up = [](size_t x) { return (x + 3) & ~(size_t)3; };
@@ -49,7 +59,9 @@ static BeamLayout beam_layout(int B, int T, int W, int ncut) {
     l.hist = up(2 * b);
     l.mass = l.hist + up(2 * b * t * w);
     l.cut = l.mass + 4 * b * t * w;
-    l.total = l.cut + up(2 * b * t * n) + 4;
+    l.forder = l.cut + up(2 * b * t * n);
+    l.fmass = l.forder + (lm ? up(b * w) : 0);
+    l.total = l.fmass + (lm ? 4 * b * w : 0) + 4;
     return l;
 }
 // 0: every non-blank class is expanded
@@ -57,13 +69,14 @@ static int beam_ncut(int C, int cutoff_top_n) { return cutoff_top_n <= 0 || cuto
 
 // LDS of ctc_beam_kernel, byte offsets; every part 16-byte aligned
 struct BeamLds { unsigned cells, stage, state, frame, sel, lkey, lidx, cnt, red, total; };
-__host__ __device__ static inline BeamLds beam_lds(int W, int n, int C, bool cut, bool stage) {
+__host__ __device__ static inline BeamLds beam_lds(int W, int n, int C, bool cut, bool stage, bool lm = false) {
     BeamLds l;
     auto up = [](unsigned x) { return (x + 15u) & ~15u; };
     l.cells = 0;
     l.stage = up(8u * (unsigned)W * (unsigned)(n + 1));
     l.state = l.stage + (stage ? up(cut ? 16u * (unsigned)n : 8u * (unsigned)C) : 0u);
-    l.frame = l.state + up(2u * 44u * (unsigned)W);     // [2] x { p_b, p_nb, hash, parent hash : 8 bytes; last, len, home : 4 bytes } [W]
+    // [2] x { p_b, p_nb, hash, parent hash : 8 bytes; last, len, home : 4 bytes; LM: the LM state, 4 bytes } [W]
+    l.frame = l.state + up(2u * (lm ? 48u : 44u) * (unsigned)W);
     l.sel = l.frame + up(32u * (unsigned)W);            // stay p_b', stay p_nb', p_b + p_nb, record: 8 bytes each [W]
     l.lkey = l.sel + up(4u * (unsigned)W);
     l.lidx = l.lkey + 8u * BEAM_LIST;
@@ -93,6 +106,35 @@ __device__ __forceinline__ float beam_score(float4 m) {
     return (float)((double)s.e * 0.69314718055994530942 + log((double)s.m));
 }
 
+// ---- language model: F(state, c) and next(state, c) of INTEGRATION.md "Language-model fusion" ----
+__device__ __forceinline__ xf xf_mul(xf a, xf b) { return xf_norm(a.m * b.m, a.e + b.e); }
+__device__ __forceinline__ xf beam_lm_xf(int m, int e) { xf r; r.m = __int_as_float(m); r.e = e; return r; }
+__device__ static xf beam_lm_walk(const nntk_shim_lm &lm, int s, int c, int &next) {
+    const int4 *arcs = (const int4 *)lm.d_arcs, *states = (const int4 *)lm.d_states, *fac = (const int4 *)lm.d_factors;
+    xf f = xf_one();
+    s = min(max(s, 0), lm.n_states - 1);
+    for (int d = 0; d <= lm.depth; ++d) {                                      // at most depth backoffs: depth + 1 states
+        const int4 st = states[s];
+        int a = st.x, z = st.x + st.y - 1;
+        while (a <= z) {
+            const int mid = a + ((z - a) >> 1);
+            const int4 arc = arcs[mid];
+            if (arc.x == c) { next = arc.y; return xf_mul(f, beam_lm_xf(arc.z, arc.w)); }
+            if (arc.x < c) a = mid + 1; else z = mid - 1;
+        }
+        if (s == 0) break;
+        const int4 bf = fac[s];
+        f = xf_mul(f, beam_lm_xf(bf.x, bf.y));
+        s = min(max(st.z, 0), s - 1);                                          // shorter contexts first: a walk only descends
+    }
+    next = 0;
+    return xf_mul(f, beam_lm_xf(lm.unk_m, lm.unk_e));
+}
+__device__ __forceinline__ xf beam_lm_final(const nntk_shim_lm &lm, int s) {
+    const int4 f = ((const int4 *)lm.d_factors)[s];
+    return beam_lm_xf(f.z, f.w);
+}
+
 // ---- streaming: the beam a row carries from one push to the next (INTEGRATION.md "CTC prefix beam search", Streaming).  Plain global
 // memory, a slot per row: written once per push with ordinary stores by the row's workgroup, read back by the same row's workgroup of
 // the next launch on the stream.  ctl = [4][B] ints the host uploads per push: frames in this push | frames the row had seen before it
@@ -102,11 +144,12 @@ struct BeamCarry {
     u64 *h, *ph;                          // [B][W] prefix hash, parent prefix hash
     int2 *tail;                           // [B][W] last class, length
     int *nb;                              // [B] entries; 0: the beam has died
+    int *lm;                              // [B][W] LM state (LM instantiations; else NULL)
     const int *seen;                      // ctl + B
 };
 // buffer of a streaming handle, in 4-byte words; every part starts on a 16-byte boundary
-struct BeamStreamLayout { size_t ctl, nb, mass, h, ph, tail, str, hist, cut, total; };
-static BeamStreamLayout beam_stream_layout(int B, int T, int W, int ncut, int L) {
+struct BeamStreamLayout { size_t ctl, nb, mass, h, ph, tail, str, hist, cut, lm, total; };
+static BeamStreamLayout beam_stream_layout(int B, int T, int W, int ncut, int L, bool lm = false) {
     BeamStreamLayout l;
     const size_t b = B > 0 ? (size_t)B : 0, t = T > 0 ? (size_t)T : 0, w = W > 0 ? (size_t)W : 0, n = ncut > 0 ? (size_t)ncut : 0;
     const size_t ml = L > 0 ? (size_t)L : 0;
@@ -120,7 +163,8 @@ static BeamStreamLayout beam_stream_layout(int B, int T, int W, int ncut, int L)
     l.str = l.tail + up(2 * b * w);
     l.hist = l.str + up(2 * b * w * ml);
     l.cut = l.hist + up(2 * b * t * w);
-    l.total = l.cut + up(2 * b * t * n) + 4;
+    l.lm = l.cut + up(2 * b * t * n);                                          // the carried LM states, behind everything else
+    l.total = l.lm + (lm ? up(b * w) : 0) + 4;
     return l;
 }
 
@@ -173,16 +217,19 @@ __global__ __launch_bounds__(CTC_THREADS) void ctc_beam_cut_kernel(const float *
 // ---- the beam: one workgroup per row ----
 // STREAM: T is the capacity of a push and lens its frame counts; the beam starts from the row's slot of `cs` (or the empty prefix, for
 // a row that has seen no frame) and ends there; the masses of the frames in between are not kept.
-template <bool CUT, bool STAGE, bool STREAM>
+// LM: every extension is weighted by the language model `lm`; !STREAM: the final ranking goes to forder / fmass ([B][W] each: the entry
+// of the last beam that hypothesis k is, and its finalised total as (m, e, 0, zero's exponent)) and its size to nfin.
+template <bool CUT, bool STAGE, bool STREAM, bool LM>
 __global__ __launch_bounds__(CTC_THREADS) void ctc_beam_kernel(const float *__restrict__ probs, int T, int C, int blank, int W, int n,
                                                                unsigned magic, const int *__restrict__ lens, int *__restrict__ nfin,
                                                                int2 *__restrict__ hist, float4 *__restrict__ mass,
-                                                               const float2 *__restrict__ pairs, BeamCarry cs) {
+                                                               const float2 *__restrict__ pairs, BeamCarry cs, nntk_shim_lm lm,
+                                                               int *__restrict__ forder, float4 *__restrict__ fmass) {
     extern __shared__ __align__(16) unsigned char beam_smem[];
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const u64 lt = (1ull << lane) - 1;
     const int Tb = lens[b], n1 = n + 1;
-    const BeamLds L = beam_lds(W, n, C, CUT, STAGE);
+    const BeamLds L = beam_lds(W, n, C, CUT, STAGE, LM);
     float2 *cell = (float2 *)(beam_smem + L.cells);
     float *srow = (float *)(beam_smem + L.stage);                              // !CUT: [2][C] probabilities
     float2 *spair = (float2 *)(beam_smem + L.stage);                           // CUT: [2][n] (class, probability)
@@ -190,6 +237,7 @@ __global__ __launch_bounds__(CTC_THREADS) void ctc_beam_kernel(const float *__re
     float2 *s_pb = (float2 *)st, *s_pnb = s_pb + 2 * W;
     u64 *s_h = (u64 *)(s_pnb + 2 * W), *s_ph = s_h + 2 * W;
     int *s_last = (int *)(s_ph + 2 * W), *s_len = s_last + 2 * W, *s_home = s_len + 2 * W;
+    int *s_lm = s_home + 2 * W;                                                // LM only
     float2 *f_spb = (float2 *)(beam_smem + L.frame), *f_spnb = f_spb + W, *f_sum = f_spnb + W;
     int2 *f_rec = (int2 *)(f_sum + W);
     int *sel = (int *)(beam_smem + L.sel);
@@ -228,6 +276,7 @@ __global__ __launch_bounds__(CTC_THREADS) void ctc_beam_kernel(const float *__re
             s_last[tid] = tl.x;
             s_len[tid] = tl.y;
             s_home[tid] = -1;
+            if (LM) s_lm[tid] = cs.lm[q];
         }
     } else if (tid == 0) {
         s_pb[0] = xf_pack(xf_one());
@@ -237,6 +286,7 @@ __global__ __launch_bounds__(CTC_THREADS) void ctc_beam_kernel(const float *__re
         s_last[0] = -1;
         s_len[0] = 0;
         s_home[0] = -1;
+        if (LM) s_lm[0] = lm.start_state;
     }
     if (STAGE && Tb > 0) {
         if (CUT) for (int k = tid; k < M; k += CTC_THREADS) spair[k] = crow[k];
@@ -319,6 +369,10 @@ __global__ __launch_bounds__(CTC_THREADS) void ctc_beam_kernel(const float *__re
                 float p;
                 cell_class(kk - 1, c, p);
                 v = xf_times_prob(xf_unpack(c == s_last[o + i] ? s_pb[o + i] : f_sum[i]), p);
+                if (LM) {
+                    int nx;
+                    v = xf_mul(v, beam_lm_walk(lm, s_lm[o + i], c, nx));
+                }
             }
             cell[idx] = xf_pack(v);
         }
@@ -430,6 +484,7 @@ __global__ __launch_bounds__(CTC_THREADS) void ctc_beam_kernel(const float *__re
                 s_ph[on + tid] = s_ph[o + i];
                 s_last[on + tid] = s_last[o + i];
                 s_len[on + tid] = s_len[o + i];
+                if (LM) s_lm[on + tid] = s_lm[o + i];
                 f_rec[tid] = make_int2(i | (s_len[o + i] << 8), -1);
             } else {
                 int c;
@@ -442,6 +497,11 @@ __global__ __launch_bounds__(CTC_THREADS) void ctc_beam_kernel(const float *__re
                 s_ph[on + tid] = h;
                 s_last[on + tid] = c;
                 s_len[on + tid] = s_len[o + i] + 1;
+                if (LM) {
+                    int nx;
+                    beam_lm_walk(lm, s_lm[o + i], c, nx);
+                    s_lm[on + tid] = nx;
+                }
                 f_rec[tid] = make_int2(i | ((s_len[o + i] + 1) << 8), c);
                 cell[idx].x = __uint_as_float(0x80000000u | (unsigned)tid);    // no mantissa has the sign bit: "selected, rank tid"
             }
@@ -458,6 +518,7 @@ __global__ __launch_bounds__(CTC_THREADS) void ctc_beam_kernel(const float *__re
                 s_ph[on + r] = s_ph[o + tid];
                 s_last[on + r] = s_last[o + tid];
                 s_len[on + r] = s_len[o + tid];
+                if (LM) s_lm[on + r] = s_lm[o + tid];
                 f_rec[r] = make_int2(tid | (s_len[o + tid] << 8), -1);
             }
         }
@@ -496,24 +557,53 @@ __global__ __launch_bounds__(CTC_THREADS) void ctc_beam_kernel(const float *__re
             cs.h[q] = s_h[o];
             cs.ph[q] = s_ph[o];
             cs.tail[q] = make_int2(s_last[o], s_len[o]);
+            if (LM) cs.lm[q] = s_lm[o];
         }
         if (tid == 0) cs.nb[b] = nb;
+    } else if (LM) {
+        // the end of the row: every total times the end-of-sentence factor of its state, exact zeros dropped, the rest in descending
+        // order, ties to the lower rank in the last beam (the beam's words were written before the loop's last barrier)
+        __syncthreads();
+        xf v = xf_zero();
+        if (tid < nb) {
+            const int o = cur * W + tid;
+            v = xf_mul(xf_add2(xf_unpack(s_pb[o]), xf_unpack(s_pnb[o])), beam_lm_final(lm, s_lm[o]));
+            lkey[tid] = beam_key(xf_pack(v));
+        }
+        __syncthreads();
+        if (tid < nb) {
+            const u64 k = lkey[tid];
+            int rank = 0, alive = 0;
+            for (int u = 0; u < nb; ++u) {
+                const u64 ku = lkey[u];
+                rank += (ku > k || (ku == k && u < tid)) ? 1 : 0;
+                alive += ku != 0ull ? 1 : 0;
+            }
+            if (k != 0ull) {
+                forder[(long)b * W + rank] = tid;
+                fmass[(long)b * W + rank] = make_float4(v.m, __int_as_float(v.e), 0.0f, __int_as_float(CTC_EZERO));
+            }
+            if (tid == 0) nfin[b] = alive;
+        }
+        if (nb == 0 && tid == 0) nfin[b] = 0;
     } else if (tid == 0) {
         nfin[b] = nb;
     }
 }
 
-// ---- backtrack: hypothesis k of a row is entry k of its last frame ----
+// ---- backtrack: hypothesis k of a row is entry k of its last frame; FIN (the LM calls): entry forder[k], with the total fmass[k] ----
+template <bool FIN>
 __global__ __launch_bounds__(CTC_THREADS) void ctc_beam_backtrack_kernel(int T, int W, int nbest, const int *__restrict__ lens,
                                                                          const int *__restrict__ nfin, const int2 *__restrict__ hist,
-                                                                         const float4 *__restrict__ mass, int *__restrict__ labels,
+                                                                         const float4 *__restrict__ mass, const int *__restrict__ forder,
+                                                                         const float4 *__restrict__ fmass, int *__restrict__ labels,
                                                                          int *__restrict__ out_len, float *__restrict__ scores) {
     extern __shared__ __align__(16) unsigned char beam_smem[];
     __shared__ int s_hlen[BEAM_MAX_W];
     int2 *rec = (int2 *)beam_smem;
     const int b = blockIdx.x, tid = threadIdx.x;
     const int Tb = lens[b];
-    const int nh = Tb == 0 ? 1 : min(nbest, nfin[b]);                         // hypotheses this row has
+    const int nh = (!FIN && Tb == 0) ? 1 : min(nbest, nfin[b]);               // hypotheses this row has
     const int2 *hrow = hist + (long)b * T * W;
     const float4 *mrow = mass + (long)b * T * W;
     int *lab = labels + (long)b * nbest * T;
@@ -521,12 +611,13 @@ __global__ __launch_bounds__(CTC_THREADS) void ctc_beam_backtrack_kernel(int T, 
     if (tid < nbest) {
         float score = -INFINITY;
         if (tid < nh) {
+            if (FIN) rank = forder[(long)b * W + tid];
             if (Tb == 0) {
                 len = 0;
-                score = 0.0f;
+                score = FIN ? beam_score(fmass[(long)b * W + tid]) : 0.0f;
             } else {
-                len = hrow[(long)(Tb - 1) * W + tid].x >> 8;
-                score = beam_score(mrow[(long)(Tb - 1) * W + tid]);
+                len = hrow[(long)(Tb - 1) * W + rank].x >> 8;
+                score = FIN ? beam_score(fmass[(long)b * W + tid]) : beam_score(mrow[(long)(Tb - 1) * W + tid]);
             }
         }
         pos = len - 1;
@@ -562,26 +653,65 @@ __global__ __launch_bounds__(CTC_THREADS) void ctc_beam_backtrack_kernel(int T, 
 // first, which gives the labels the entry gained inside the push (a record carries the length after it, so each label knows its
 // place) and the rank it descends from at the push's start; the entry's string = that ancestor's stored string + those labels goes
 // to the other half of the double-buffered store, cut at L labels, and the first nbest entries go to the outputs as well.  A row
-// without frames in this push only rewrites its outputs from what it holds.
+// without frames in this push only rewrites its outputs from what it holds.  FIN (a stream with a language model): what is REPORTED is
+// the beam after the end-of-sentence factors -- entry tid goes to output slot `slot` (its rank among the finalised totals, or none) --
+// while the carried beam and its strings stay in entry order, unfinalised.
+template <bool FIN>
 __global__ __launch_bounds__(CTC_THREADS) void ctc_beam_commit_kernel(int B, int T, int W, int nbest, int L, const int *__restrict__ ctl,
                                                                       BeamCarry cs, const int2 *__restrict__ hist, int *__restrict__ strs,
                                                                       int *__restrict__ labels, int *__restrict__ out_len,
-                                                                      float *__restrict__ scores) {
+                                                                      float *__restrict__ scores, nntk_shim_lm lm) {
     extern __shared__ __align__(16) unsigned char beam_smem[];
     __shared__ int s_hlen[BEAM_MAX_W], s_anc[BEAM_MAX_W], s_alen[BEAM_MAX_W];
+    __shared__ int s_slot[FIN ? BEAM_MAX_W : 1], s_ord[FIN ? BEAM_MAX_W : 1];
+    __shared__ u64 s_key[FIN ? BEAM_MAX_W : 1];
     int2 *rec = (int2 *)beam_smem;
     const int b = blockIdx.x, tid = threadIdx.x;
     const int Tb = ctl[b], seen = ctl[B + b], par = ctl[2 * B + b] & 1;
     const bool fresh = seen == 0 && Tb == 0;                                   // no frame since the reset: the empty prefix alone
     const int nb = fresh ? 1 : min(max(cs.nb[b], 0), W);
-    const int nh = min(nbest, nb);
+    int nh = min(nbest, nb);
     const int *src = strs + ((long)par * B + b) * W * L;
     int *dst = strs + ((long)(par ^ 1) * B + b) * W * L;
     const int2 *hrow = hist + (long)b * T * W;
     int *lab = labels + (long)b * nbest * L;
     int len = -1;
     if (tid < nb) len = fresh ? 0 : cs.tail[(long)b * W + tid].y;
-    if (tid < nbest) {
+    int slot = tid < nh ? tid : -1;                                            // the output slot that reports entry tid
+    if (FIN) {
+        xf v = xf_zero();
+        if (tid < nb) {
+            xf tot = xf_one();
+            int st = lm.start_state;
+            if (!fresh) {
+                const float4 m = cs.mass[(long)b * W + tid];
+                tot = xf_add2(xf_unpack(make_float2(m.x, m.y)), xf_unpack(make_float2(m.z, m.w)));
+                st = min(max(cs.lm[(long)b * W + tid], 0), lm.n_states - 1);
+            }
+            v = xf_mul(tot, beam_lm_final(lm, st));
+            s_key[tid] = beam_key(xf_pack(v));
+        }
+        __syncthreads();
+        const u64 k = tid < nb ? s_key[tid] : 0ull;
+        int rank = 0, alive = 0;
+        for (int u = 0; u < nb; ++u) {
+            const u64 ku = s_key[u];
+            rank += (ku > k || (ku == k && u < tid)) ? 1 : 0;
+            alive += ku != 0ull ? 1 : 0;
+        }
+        nh = min(nbest, alive);
+        slot = (k != 0ull && rank < nbest) ? rank : -1;
+        if (tid < W) s_slot[tid] = slot;
+        if (slot >= 0) {
+            s_ord[slot] = tid;
+            out_len[(long)b * nbest + slot] = len;
+            scores[(long)b * nbest + slot] = beam_score(make_float4(v.m, __int_as_float(v.e), 0.0f, __int_as_float(CTC_EZERO)));
+        }
+        if (tid < nbest && tid >= nh) {
+            out_len[(long)b * nbest + tid] = -1;
+            scores[(long)b * nbest + tid] = -INFINITY;
+        }
+    } else if (tid < nbest) {
         float score = -INFINITY;
         if (tid < nh) score = fresh ? 0.0f : beam_score(cs.mass[(long)b * W + tid]);
         out_len[(long)b * nbest + tid] = tid < nh ? len : -1;
@@ -593,7 +723,8 @@ __global__ __launch_bounds__(CTC_THREADS) void ctc_beam_commit_kernel(int B, int
         __syncthreads();
         for (long q = tid; q < cells_out; q += CTC_THREADS) {
             const int k = (int)(q / L), p = (int)(q % L);
-            lab[q] = (k < nh && p < min(s_hlen[k], L)) ? src[(long)k * L + p] : -1;
+            const int e = FIN ? (k < nh ? s_ord[k] : 0) : k;
+            lab[q] = (k < nh && p < min(s_hlen[e], L)) ? src[(long)e * L + p] : -1;
         }
         return;
     }
@@ -613,7 +744,7 @@ __global__ __launch_bounds__(CTC_THREADS) void ctc_beam_commit_kernel(int B, int
                     const int pos = (r.x >> 8) - 1;
                     if (pos < L) {
                         dst[(long)tid * L + pos] = r.y;
-                        if (tid < nbest) lab[(long)tid * L + pos] = r.y;
+                        if (FIN ? slot >= 0 : tid < nbest) lab[(long)(FIN ? slot : tid) * L + pos] = r.y;
                     }
                     ++gained;
                 }
@@ -627,7 +758,15 @@ __global__ __launch_bounds__(CTC_THREADS) void ctc_beam_commit_kernel(int B, int
     const long cells = (long)max(nb, nbest) * L;
     for (long q = tid; q < cells; q += CTC_THREADS) {
         const int k = (int)(q / L), p = (int)(q % L);
-        if (k < nb && p < min(s_alen[k], L)) {
+        if (FIN) {
+            // k as an entry: its ancestor's string; k as an output slot: the -1 behind the hypothesis it reports (disjoint places)
+            if (k < nb && p < min(s_alen[k], L)) {
+                const int v = src[(long)s_anc[k] * L + p];
+                dst[(long)k * L + p] = v;
+                if (s_slot[k] >= 0) lab[(long)s_slot[k] * L + p] = v;
+            }
+            if (k < nbest && (k >= nh || p >= min(s_hlen[s_ord[k < nh ? k : 0]], L))) lab[(long)k * L + p] = -1;
+        } else if (k < nb && p < min(s_alen[k], L)) {
             const int v = src[(long)s_anc[k] * L + p];
             dst[(long)k * L + p] = v;
             if (k < nbest) lab[(long)k * L + p] = v;
@@ -637,21 +776,18 @@ __global__ __launch_bounds__(CTC_THREADS) void ctc_beam_commit_kernel(int B, int
     }
 }
 
-extern "C" {
-
-size_t nntk_shim_ctc_beam_workspace_floats(int batch, int T, int C, int beam_width, int cutoff_top_n) {
-    return beam_layout(batch, T, beam_width, beam_ncut(C, cutoff_top_n)).total;
-}
-
-int nntk_shim_ctc_beam_decode(const float *d_probs, int B, int T, int C, const int *h_input_lengths, int blank, int W, int cutoff_top_n,
-                              int nbest, int *d_labels_out, int *d_out_lengths, float *d_scores, float *d_ws) {
+// lm NULL: the acoustic-only kernels, exactly
+static int beam_decode(const float *d_probs, int B, int T, int C, const int *h_input_lengths, int blank, int W, int cutoff_top_n,
+                       int nbest, const nntk_shim_lm *lm, int *d_labels_out, int *d_out_lengths, float *d_scores, float *d_ws) {
     if (B <= 0) return 0;
     if (((uintptr_t)d_ws & 15) != 0) return nntk_fail_msg("nntk_ctc_beam_decode_device: the workspace must be 16-byte aligned");
     const int ncut = beam_ncut(C, cutoff_top_n), n = ncut ? ncut : C - 1;
     if (W < 1 || W > BEAM_MAX_W || nbest < 1 || nbest > W || (long)W * (n + 1) > BEAM_MAX_CELLS || T > BEAM_MAX_T)
         return nntk_fail_msg("nntk_ctc_beam_decode_device: beam_width, nbest or beam_width * (classes + 1) beyond the kernel's limits");
-    const BeamLayout lay = beam_layout(B, T, W, ncut);
+    const BeamLayout lay = beam_layout(B, T, W, ncut, lm != nullptr);
     int *d_lens = (int *)d_ws, *d_nfin = d_lens + B;
+    int *d_forder = (int *)(d_ws + lay.forder);
+    float4 *d_fmass = (float4 *)(d_ws + lay.fmass);
     int2 *d_hist = (int2 *)(d_ws + lay.hist);
     float4 *d_mass = (float4 *)(d_ws + lay.mass);
     float2 *d_pairs = (float2 *)(d_ws + lay.cut);
@@ -665,50 +801,57 @@ int nntk_shim_ctc_beam_decode(const float *d_probs, int B, int T, int C, const i
         NNTK_LAUNCH_CHECK("ctc_beam_cut_kernel");
     }
     // the frame's probabilities (or its cut pairs) double-buffered in LDS where they fit beside the cells
-    const bool stage = beam_lds(W, n, C, ncut != 0, true).total <= CTC_LDS_LIMIT;
-    const size_t lds = beam_lds(W, n, C, ncut != 0, stage).total;
+    const bool stage = beam_lds(W, n, C, ncut != 0, true, lm != nullptr).total <= CTC_LDS_LIMIT;
+    const size_t lds = beam_lds(W, n, C, ncut != 0, stage, lm != nullptr).total;
     if (lds > CTC_LDS_LIMIT) return nntk_fail_msg("nntk_ctc_beam_decode_device: the beam does not fit one workgroup's LDS");
     const unsigned magic = n + 1 > 1 ? (unsigned)(0x100000000ull / (unsigned)(n + 1)) + 1u : 0u;
-#define BEAM_GO(CUT, STAGE)                                                                                                        \
+    const nntk_shim_lm lmv = lm ? *lm : nntk_shim_lm();
+#define BEAM_GO(CUT, STAGE, LM)                                                                                                    \
     do {                                                                                                                           \
-        if (lds > 48 * 1024 && nntk_set_max_dynamic_lds((const void *)ctc_beam_kernel<CUT, STAGE, false>, lds)) return -1;         \
-        hipLaunchKernelGGL((ctc_beam_kernel<CUT, STAGE, false>), dim3((unsigned)B), dim3(CTC_THREADS), lds, nntk_stream(), d_probs,  \
-                           T, C, blank, W, n, magic, d_lens, d_nfin, d_hist, d_mass, d_pairs, BeamCarry());                        \
+        if (lds > 48 * 1024 && nntk_set_max_dynamic_lds((const void *)ctc_beam_kernel<CUT, STAGE, false, LM>, lds)) return -1;     \
+        hipLaunchKernelGGL((ctc_beam_kernel<CUT, STAGE, false, LM>), dim3((unsigned)B), dim3(CTC_THREADS), lds, nntk_stream(),     \
+                           d_probs, T, C, blank, W, n, magic, d_lens, d_nfin, d_hist, d_mass, d_pairs, BeamCarry(), lmv, d_forder,   \
+                           d_fmass);                                                                                               \
     } while (0)
-    if (ncut) { if (stage) BEAM_GO(true, true); else BEAM_GO(true, false); }
-    else { if (stage) BEAM_GO(false, true); else BEAM_GO(false, false); }
-#undef BEAM_GO
+#define BEAM_GO2(LM)                                                                                                               \
+    do {                                                                                                                           \
+        if (ncut) { if (stage) BEAM_GO(true, true, LM); else BEAM_GO(true, false, LM); }                                           \
+        else { if (stage) BEAM_GO(false, true, LM); else BEAM_GO(false, false, LM); }                                              \
+    } while (0)
+    if (lm) BEAM_GO2(true); else BEAM_GO2(false);
     NNTK_LAUNCH_CHECK("ctc_beam_kernel");
     const size_t blds = (size_t)BEAM_BT_RECORDS * sizeof(int2);
-    if (nntk_set_max_dynamic_lds((const void *)ctc_beam_backtrack_kernel, blds)) return -1;
-    hipLaunchKernelGGL(ctc_beam_backtrack_kernel, dim3((unsigned)B), dim3(CTC_THREADS), blds, nntk_stream(), T, W, nbest, d_lens, d_nfin,
-                       d_hist, d_mass, d_labels_out, d_out_lengths, d_scores);
+#define BEAM_BT(FIN)                                                                                                               \
+    do {                                                                                                                           \
+        if (nntk_set_max_dynamic_lds((const void *)ctc_beam_backtrack_kernel<FIN>, blds)) return -1;                               \
+        hipLaunchKernelGGL(ctc_beam_backtrack_kernel<FIN>, dim3((unsigned)B), dim3(CTC_THREADS), blds, nntk_stream(), T, W, nbest,   \
+                           d_lens, d_nfin, d_hist, d_mass, d_forder, d_fmass, d_labels_out, d_out_lengths, d_scores);              \
+    } while (0)
+    if (lm) BEAM_BT(true); else BEAM_BT(false);
+#undef BEAM_BT
+#undef BEAM_GO2
+#undef BEAM_GO
     NNTK_LAUNCH_CHECK("ctc_beam_backtrack_kernel");
     return 0;
 }
 
-// ---- streaming form: the handle's buffer (beam_stream_layout), one push ----
-size_t nntk_shim_ctc_beam_stream_floats(int batch, int max_frames, int C, int beam_width, int cutoff_top_n, int max_labels) {
-    return beam_stream_layout(batch, max_frames, beam_width, beam_ncut(C, cutoff_top_n), max_labels).total;
-}
-
-// the limits of the kernel that only the launch knows in the one-shot call; no device is touched
-int nntk_shim_ctc_beam_stream_check(int C, int W, int cutoff_top_n) {
+// the cell and LDS limits of the launch, without a device; lm: with the per-entry LM state in the LDS state block
+static int beam_stream_check(int C, int W, int cutoff_top_n, bool lm) {
     const int ncut = beam_ncut(C, cutoff_top_n), n = ncut ? ncut : C - 1;
     if (W < 1 || W > BEAM_MAX_W || (long)W * (n + 1) > BEAM_MAX_CELLS)
         return nntk_fail_msg("nntk_ctc_beam_stream_create: beam_width or beam_width * (classes + 1) beyond the kernel's limits");
-    if (beam_lds(W, n, C, ncut != 0, false).total > CTC_LDS_LIMIT)
+    if (beam_lds(W, n, C, ncut != 0, false, lm).total > CTC_LDS_LIMIT)
         return nntk_fail_msg("nntk_ctc_beam_stream_create: the beam does not fit one workgroup's LDS");
     return 0;
 }
 
-int nntk_shim_ctc_beam_stream_push(const float *d_probs, int B, int T, int C, const int *h_ctl, int any_frames, int blank, int W,
-                                   int cutoff_top_n, int nbest, int L, int *d_labels_out, int *d_out_lengths, float *d_scores,
-                                   float *d_buf) {
+static int beam_stream_push(const float *d_probs, int B, int T, int C, const int *h_ctl, int any_frames, int blank, int W,
+                            int cutoff_top_n, int nbest, int L, const nntk_shim_lm *lm, int *d_labels_out, int *d_out_lengths,
+                            float *d_scores, float *d_buf) {
     if (B <= 0) return 0;
     if (((uintptr_t)d_buf & 15) != 0) return nntk_fail_msg("nntk_ctc_beam_stream_push_device: the handle's buffer is not 16-byte aligned");
     const int ncut = beam_ncut(C, cutoff_top_n), n = ncut ? ncut : C - 1;
-    const BeamStreamLayout lay = beam_stream_layout(B, T, W, ncut, L);
+    const BeamStreamLayout lay = beam_stream_layout(B, T, W, ncut, L, lm != nullptr);
     int *d_ctl = (int *)d_buf;
     BeamCarry cs;
     cs.nb = (int *)(d_buf + lay.nb);
@@ -716,10 +859,12 @@ int nntk_shim_ctc_beam_stream_push(const float *d_probs, int B, int T, int C, co
     cs.h = (u64 *)(d_buf + lay.h);
     cs.ph = (u64 *)(d_buf + lay.ph);
     cs.tail = (int2 *)(d_buf + lay.tail);
+    cs.lm = lm ? (int *)(d_buf + lay.lm) : nullptr;
     cs.seen = d_ctl + B;
     int *d_strs = (int *)(d_buf + lay.str);
     int2 *d_hist = (int2 *)(d_buf + lay.hist);
     float2 *d_pairs = (float2 *)(d_buf + lay.cut);
+    const nntk_shim_lm lmv = lm ? *lm : nntk_shim_lm();
     if (nntk_shim_upload_ints(d_ctl, h_ctl, 4L * B)) return -1;
     if (any_frames) {
         const long frames = (long)B * T;
@@ -730,27 +875,82 @@ int nntk_shim_ctc_beam_stream_push(const float *d_probs, int B, int T, int C, co
                                d_pairs, frames);
             NNTK_LAUNCH_CHECK("ctc_beam_cut_kernel");
         }
-        const bool stage = beam_lds(W, n, C, ncut != 0, true).total <= CTC_LDS_LIMIT;
-        const size_t lds = beam_lds(W, n, C, ncut != 0, stage).total;
+        const bool stage = beam_lds(W, n, C, ncut != 0, true, lm != nullptr).total <= CTC_LDS_LIMIT;
+        const size_t lds = beam_lds(W, n, C, ncut != 0, stage, lm != nullptr).total;
         if (lds > CTC_LDS_LIMIT) return nntk_fail_msg("nntk_ctc_beam_stream_push_device: the beam does not fit one workgroup's LDS");
         const unsigned magic = n + 1 > 1 ? (unsigned)(0x100000000ull / (unsigned)(n + 1)) + 1u : 0u;
-#define BEAM_GO(CUT, STAGE)                                                                                                        \
+#define BEAM_GO(CUT, STAGE, LM)                                                                                                    \
     do {                                                                                                                           \
-        if (lds > 48 * 1024 && nntk_set_max_dynamic_lds((const void *)ctc_beam_kernel<CUT, STAGE, true>, lds)) return -1;          \
-        hipLaunchKernelGGL((ctc_beam_kernel<CUT, STAGE, true>), dim3((unsigned)B), dim3(CTC_THREADS), lds, nntk_stream(), d_probs,   \
-                           T, C, blank, W, n, magic, d_ctl, (int *)nullptr, d_hist, (float4 *)nullptr, d_pairs, cs);               \
+        if (lds > 48 * 1024 && nntk_set_max_dynamic_lds((const void *)ctc_beam_kernel<CUT, STAGE, true, LM>, lds)) return -1;      \
+        hipLaunchKernelGGL((ctc_beam_kernel<CUT, STAGE, true, LM>), dim3((unsigned)B), dim3(CTC_THREADS), lds, nntk_stream(),      \
+                           d_probs, T, C, blank, W, n, magic, d_ctl, (int *)nullptr, d_hist, (float4 *)nullptr, d_pairs, cs, lmv,  \
+                           (int *)nullptr, (float4 *)nullptr);                                                                     \
     } while (0)
-        if (ncut) { if (stage) BEAM_GO(true, true); else BEAM_GO(true, false); }
-        else { if (stage) BEAM_GO(false, true); else BEAM_GO(false, false); }
+#define BEAM_GO2(LM)                                                                                                               \
+    do {                                                                                                                           \
+        if (ncut) { if (stage) BEAM_GO(true, true, LM); else BEAM_GO(true, false, LM); }                                           \
+        else { if (stage) BEAM_GO(false, true, LM); else BEAM_GO(false, false, LM); }                                              \
+    } while (0)
+        if (lm) BEAM_GO2(true); else BEAM_GO2(false);
+#undef BEAM_GO2
 #undef BEAM_GO
         NNTK_LAUNCH_CHECK("ctc_beam_kernel");
     }
     const size_t blds = (size_t)BEAM_BT_RECORDS * sizeof(int2);
-    if (nntk_set_max_dynamic_lds((const void *)ctc_beam_commit_kernel, blds)) return -1;
-    hipLaunchKernelGGL(ctc_beam_commit_kernel, dim3((unsigned)B), dim3(CTC_THREADS), blds, nntk_stream(), B, T, W, nbest, L, d_ctl, cs,
-                       d_hist, d_strs, d_labels_out, d_out_lengths, d_scores);
+#define BEAM_COMMIT(FIN)                                                                                                           \
+    do {                                                                                                                           \
+        if (nntk_set_max_dynamic_lds((const void *)ctc_beam_commit_kernel<FIN>, blds)) return -1;                                  \
+        hipLaunchKernelGGL(ctc_beam_commit_kernel<FIN>, dim3((unsigned)B), dim3(CTC_THREADS), blds, nntk_stream(), B, T, W, nbest, L, \
+                           d_ctl, cs, d_hist, d_strs, d_labels_out, d_out_lengths, d_scores, lmv);                                 \
+    } while (0)
+    if (lm) BEAM_COMMIT(true); else BEAM_COMMIT(false);
+#undef BEAM_COMMIT
     NNTK_LAUNCH_CHECK("ctc_beam_commit_kernel");
     return 0;
+}
+
+extern "C" {
+
+size_t nntk_shim_ctc_beam_workspace_floats(int batch, int T, int C, int beam_width, int cutoff_top_n) {
+    return beam_layout(batch, T, beam_width, beam_ncut(C, cutoff_top_n)).total;
+}
+size_t nntk_shim_ctc_beam_lm_workspace_floats(int batch, int T, int C, int beam_width, int cutoff_top_n) {
+    return beam_layout(batch, T, beam_width, beam_ncut(C, cutoff_top_n), true).total;
+}
+
+int nntk_shim_ctc_beam_decode(const float *d_probs, int B, int T, int C, const int *h_input_lengths, int blank, int W, int cutoff_top_n,
+                              int nbest, int *d_labels_out, int *d_out_lengths, float *d_scores, float *d_ws) {
+    return beam_decode(d_probs, B, T, C, h_input_lengths, blank, W, cutoff_top_n, nbest, nullptr, d_labels_out, d_out_lengths, d_scores,
+                       d_ws);
+}
+int nntk_shim_ctc_beam_decode_lm(const float *d_probs, int B, int T, int C, const int *h_input_lengths, int blank, int W, int cutoff_top_n,
+                                 int nbest, const nntk_shim_lm *lm, int *d_labels_out, int *d_out_lengths, float *d_scores, float *d_ws) {
+    return beam_decode(d_probs, B, T, C, h_input_lengths, blank, W, cutoff_top_n, nbest, lm, d_labels_out, d_out_lengths, d_scores, d_ws);
+}
+
+// ---- streaming form: the handle's buffer (beam_stream_layout), one push ----
+size_t nntk_shim_ctc_beam_stream_floats(int batch, int max_frames, int C, int beam_width, int cutoff_top_n, int max_labels) {
+    return beam_stream_layout(batch, max_frames, beam_width, beam_ncut(C, cutoff_top_n), max_labels).total;
+}
+size_t nntk_shim_ctc_beam_stream_lm_floats(int batch, int max_frames, int C, int beam_width, int cutoff_top_n, int max_labels) {
+    return beam_stream_layout(batch, max_frames, beam_width, beam_ncut(C, cutoff_top_n), max_labels, true).total;
+}
+
+// the limits of the kernel that only the launch knows in the one-shot call; no device is touched
+int nntk_shim_ctc_beam_stream_check(int C, int W, int cutoff_top_n) { return beam_stream_check(C, W, cutoff_top_n, false); }
+int nntk_shim_ctc_beam_stream_check_lm(int C, int W, int cutoff_top_n) { return beam_stream_check(C, W, cutoff_top_n, true); }
+
+int nntk_shim_ctc_beam_stream_push(const float *d_probs, int B, int T, int C, const int *h_ctl, int any_frames, int blank, int W,
+                                   int cutoff_top_n, int nbest, int L, int *d_labels_out, int *d_out_lengths, float *d_scores,
+                                   float *d_buf) {
+    return beam_stream_push(d_probs, B, T, C, h_ctl, any_frames, blank, W, cutoff_top_n, nbest, L, nullptr, d_labels_out, d_out_lengths,
+                            d_scores, d_buf);
+}
+int nntk_shim_ctc_beam_stream_push_lm(const float *d_probs, int B, int T, int C, const int *h_ctl, int any_frames, int blank, int W,
+                                      int cutoff_top_n, int nbest, int L, const nntk_shim_lm *lm, int *d_labels_out, int *d_out_lengths,
+                                      float *d_scores, float *d_buf) {
+    return beam_stream_push(d_probs, B, T, C, h_ctl, any_frames, blank, W, cutoff_top_n, nbest, L, lm, d_labels_out, d_out_lengths,
+                            d_scores, d_buf);
 }
 
 }  // extern "C"

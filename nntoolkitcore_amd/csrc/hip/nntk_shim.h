@@ -177,6 +177,22 @@ int nntk_shim_ctc_beam_stream_check(int C, int beam_width, int cutoff_top_n);
 int nntk_shim_ctc_beam_stream_push(const float *d_probs, int B, int max_frames, int C, const int *h_ctl, int any_frames, int blank,
                                    int beam_width, int cutoff_top_n, int nbest, int max_labels, int *d_labels_out, int *d_out_lengths,
                                    float *d_scores, float *d_buf);
+/* Language-model fusion (INTEGRATION.md "CTC prefix beam search", Language-model fusion): the device tables of an n-gram handle, 16-byte
+ * records -- arcs {label, next state, factor mantissa, factor exponent}, states {first arc, arcs, backoff state, 0} and per-state factors
+ * {backoff m, e, final m, e}.  depth = the longest backoff chain: the walk's loop count.  lm == NULL in the _lm calls: the calls above. */
+typedef struct {
+    const int *d_arcs, *d_states, *d_factors;
+    int n_states, start_state, depth, unk_m, unk_e;
+} nntk_shim_lm;
+size_t nntk_shim_ctc_beam_lm_workspace_floats(int batch, int T, int C, int beam_width, int cutoff_top_n);
+int nntk_shim_ctc_beam_decode_lm(const float *d_probs, int B, int T, int C, const int *h_input_lengths, int blank, int beam_width,
+                                 int cutoff_top_n, int nbest, const nntk_shim_lm *lm, int *d_labels_out, int *d_out_lengths,
+                                 float *d_scores, float *d_ws);
+size_t nntk_shim_ctc_beam_stream_lm_floats(int batch, int max_frames, int C, int beam_width, int cutoff_top_n, int max_labels);
+int nntk_shim_ctc_beam_stream_check_lm(int C, int beam_width, int cutoff_top_n);
+int nntk_shim_ctc_beam_stream_push_lm(const float *d_probs, int B, int max_frames, int C, const int *h_ctl, int any_frames, int blank,
+                                      int beam_width, int cutoff_top_n, int nbest, int max_labels, const nntk_shim_lm *lm,
+                                      int *d_labels_out, int *d_out_lengths, float *d_scores, float *d_buf);
 /* ---- CTC forced alignment (ctc_align.hip): the best single alignment of every row to its labels -- the state of every frame, the
  *      frame span of every label, ln of the path's probability.  The int arrays are HOST memory, already checked by the caller
  *      (train.c), never NULL; d_states / d_spans may be NULL; d_ws 16-byte aligned, nntk_shim_ctc_align_workspace_floats words ---- */

@@ -323,6 +323,62 @@ int nntk_ctc_beam_decode(const float *probs, int batch, int T, int C, const int 
     return nntk_shim_download(scores, d_o + nl + nh, nh * sizeof(float));
 }
 
+/* ---- language-model fusion (INTEGRATION.md "CTC prefix beam search", Language-model fusion): the calls above with an n-gram handle
+ *      (ngram_lm.c); lm NULL: the calls above themselves ---- */
+size_t nntk_ctc_beam_lm_workspace_floats(int batch, int T, int C, int beam_width, int cutoff_top_n) {
+    return nntk_shim_ctc_beam_lm_workspace_floats(batch, T, C, beam_width, cutoff_top_n);
+}
+
+static int ctc_beam_lm_check(const char *who, NntkNgramLm lm, int C, int blank) {
+    if (lm && !nntk_ngram_lm_matches(lm, C, blank))
+        return ctc_fail(who, "the language model was built for another class count or blank than C = %d, blank = %d", C, blank, 0);
+    return 0;
+}
+
+int nntk_ctc_beam_decode_lm_device(const float *d_probs, int batch, int T, int C, const int *input_lengths, int blank, int beam_width,
+                                   int cutoff_top_n, int nbest, NntkNgramLm lm, int *d_labels_out, int *d_out_lengths, float *d_scores,
+                                   float *d_workspace) {
+    static const char who[] = "nntk_ctc_beam_decode_lm_device";
+    if (!lm)
+        return nntk_ctc_beam_decode_device(d_probs, batch, T, C, input_lengths, blank, beam_width, cutoff_top_n, nbest, d_labels_out,
+                                           d_out_lengths, d_scores, d_workspace);
+    nntk_shim_clear_error();
+    if (ctc_beam_check(who, batch, T, C, input_lengths, blank, beam_width, cutoff_top_n, nbest) || ctc_beam_lm_check(who, lm, C, blank))
+        return -1;
+    if (batch == 0) return 0;
+    if (!d_out_lengths || !d_scores || !d_workspace || ((!d_probs || !d_labels_out) && T > 0))
+        NNTK_FAIL("nntk_ctc_beam_decode_lm_device: NULL tensor");
+    nntk_shim_lm tab;
+    if (nntk_ngram_lm_device(lm, &tab)) return -1;
+    int *len = ctc_lengths(input_lengths, batch, T);
+    if (!len) return -1;
+    int rc = nntk_shim_ctc_beam_decode_lm(d_probs, batch, T, C, len, blank, beam_width, cutoff_top_n, nbest, &tab, d_labels_out,
+                                          d_out_lengths, d_scores, d_workspace);
+    free(len);
+    return rc;
+}
+
+int nntk_ctc_beam_decode_lm(const float *probs, int batch, int T, int C, const int *input_lengths, int blank, int beam_width,
+                            int cutoff_top_n, int nbest, NntkNgramLm lm, int *labels_out, int *out_lengths, float *scores) {
+    static const char who[] = "nntk_ctc_beam_decode_lm";
+    nntk_shim_clear_error();
+    if (ctc_beam_check(who, batch, T, C, input_lengths, blank, beam_width, cutoff_top_n, nbest) || ctc_beam_lm_check(who, lm, C, blank))
+        return -1;
+    if (batch == 0) return 0;
+    if (!out_lengths || !scores || ((!probs || !labels_out) && T > 0)) NNTK_FAIL("nntk_ctc_beam_decode_lm: NULL array");
+    const size_t n = (size_t)batch * T * C, nh = (size_t)batch * nbest, nl = nh * T;
+    float *d_p = nntk_devbuf_reserve(&t_a, n + 4);
+    int *d_o = (int *)nntk_devbuf_reserve(&t_b, nl + 2 * nh + 4);             /* labels | lengths | scores */
+    float *d_ws = nntk_devbuf_reserve(&t_c, nntk_shim_ctc_beam_lm_workspace_floats(batch, T, C, beam_width, cutoff_top_n));
+    if (!d_p || !d_o || !d_ws) return -1;
+    if (n && nntk_shim_upload(d_p, probs, n * sizeof(float))) return -1;
+    if (nntk_ctc_beam_decode_lm_device(d_p, batch, T, C, input_lengths, blank, beam_width, cutoff_top_n, nbest, lm, d_o, d_o + nl,
+                                       (float *)(d_o + nl + nh), d_ws)) return -1;
+    if (nl && nntk_shim_download(labels_out, d_o, nl * sizeof(int))) return -1;
+    if (nntk_shim_download(out_lengths, d_o + nl, nh * sizeof(int))) return -1;
+    return nntk_shim_download(scores, d_o + nl + nh, nh * sizeof(float));
+}
+
 /* ---- streaming CTC decoding (INTEGRATION.md "CTC prefix beam search", Streaming).  The beam lives in the handle's device buffer; which
  *      rows are new, how many frames each has seen and which half of its label strings is current is host bookkeeping, uploaded with
  *      every push: a reset touches no device memory ---- */
@@ -332,6 +388,7 @@ struct NntkCtcBeamStreamStruct {
     int *frames;                    /* [batch] frames since the row's reset */
     int *half;                      /* [batch] the current half of the row's label strings */
     int *ctl;                       /* [4][batch] staging of one push */
+    NntkNgramLm lm;                 /* NULL: acoustic scores only.  Not owned: it outlives the stream */
     nntk_devbuf d_buf;              /* nntk_shim_ctc_beam_stream_floats words, reserved by the first push */
     nntk_devbuf d_io;               /* the host-pointer push: probabilities | labels | lengths | scores */
 };
@@ -340,14 +397,25 @@ size_t nntk_ctc_beam_stream_state_bytes(int batch, int max_frames, int C, int be
     return sizeof(float) * nntk_shim_ctc_beam_stream_floats(batch, max_frames, C, beam_width, cutoff_top_n, max_labels);
 }
 
+size_t nntk_ctc_beam_stream_state_bytes_lm(int batch, int max_frames, int C, int beam_width, int cutoff_top_n, int max_labels) {
+    return sizeof(float) * nntk_shim_ctc_beam_stream_lm_floats(batch, max_frames, C, beam_width, cutoff_top_n, max_labels);
+}
+
 NntkCtcBeamStream nntk_ctc_beam_stream_create(int batch, int max_frames, int C, int blank, int beam_width, int cutoff_top_n, int nbest,
                                               int max_labels) {
+    return nntk_ctc_beam_stream_create_lm(batch, max_frames, C, blank, beam_width, cutoff_top_n, nbest, max_labels, NULL);
+}
+
+NntkCtcBeamStream nntk_ctc_beam_stream_create_lm(int batch, int max_frames, int C, int blank, int beam_width, int cutoff_top_n, int nbest,
+                                                 int max_labels, NntkNgramLm lm) {
     static const char who[] = "nntk_ctc_beam_stream_create";
     nntk_shim_clear_error();
     if (ctc_beam_check(who, batch, 0, C, NULL, blank, beam_width, cutoff_top_n, nbest)) return NULL;
     if (max_frames < 1) { ctc_fail(who, "max_frames %d < 1", max_frames, 0, 0); return NULL; }
     if (max_labels < 1) { ctc_fail(who, "max_labels %d < 1", max_labels, 0, 0); return NULL; }
-    if (nntk_shim_ctc_beam_stream_check(C, beam_width, cutoff_top_n)) return NULL;
+    if (ctc_beam_lm_check(who, lm, C, blank)) return NULL;
+    if (lm ? nntk_shim_ctc_beam_stream_check_lm(C, beam_width, cutoff_top_n) : nntk_shim_ctc_beam_stream_check(C, beam_width, cutoff_top_n))
+        return NULL;
     NntkCtcBeamStream s = (NntkCtcBeamStream)calloc(1, sizeof *s);
     const size_t rows = (size_t)(batch > 0 ? batch : 1);
     if (s) {
@@ -362,6 +430,7 @@ NntkCtcBeamStream nntk_ctc_beam_stream_create(int batch, int max_frames, int C, 
     }
     s->batch = batch; s->max_frames = max_frames; s->C = C; s->blank = blank;
     s->beam_width = beam_width; s->cutoff_top_n = cutoff_top_n; s->nbest = nbest; s->max_labels = max_labels;
+    s->lm = lm;
     return s;
 }
 
@@ -408,8 +477,10 @@ int nntk_ctc_beam_stream_push_device(NntkCtcBeamStream s, const float *d_probs, 
     if (s->batch == 0) return 0;
     if (beam_stream_check_push(who, s, d_probs, n_frames, d_labels_out, d_out_lengths, d_scores)) return -1;
     const int B = s->batch;
-    float *d_buf = nntk_devbuf_reserve(&s->d_buf, nntk_shim_ctc_beam_stream_floats(B, s->max_frames, s->C, s->beam_width, s->cutoff_top_n,
-                                                                                   s->max_labels));
+    nntk_shim_lm tab;
+    if (s->lm && nntk_ngram_lm_device(s->lm, &tab)) return -1;
+    float *d_buf = nntk_devbuf_reserve(&s->d_buf, (s->lm ? nntk_shim_ctc_beam_stream_lm_floats : nntk_shim_ctc_beam_stream_floats)(
+                                                      B, s->max_frames, s->C, s->beam_width, s->cutoff_top_n, s->max_labels));
     if (!d_buf) return -1;
     int any = 0;
     for (int b = 0; b < B; ++b) {
@@ -419,8 +490,10 @@ int nntk_ctc_beam_stream_push_device(NntkCtcBeamStream s, const float *d_probs, 
         s->ctl[3 * B + b] = 0;
         any |= n_frames[b] > 0;
     }
-    if (nntk_shim_ctc_beam_stream_push(d_probs, B, s->max_frames, s->C, s->ctl, any, s->blank, s->beam_width, s->cutoff_top_n, s->nbest,
-                                       s->max_labels, d_labels_out, d_out_lengths, d_scores, d_buf)) return -1;
+    if (s->lm ? nntk_shim_ctc_beam_stream_push_lm(d_probs, B, s->max_frames, s->C, s->ctl, any, s->blank, s->beam_width, s->cutoff_top_n,
+                                                  s->nbest, s->max_labels, &tab, d_labels_out, d_out_lengths, d_scores, d_buf)
+              : nntk_shim_ctc_beam_stream_push(d_probs, B, s->max_frames, s->C, s->ctl, any, s->blank, s->beam_width, s->cutoff_top_n,
+                                               s->nbest, s->max_labels, d_labels_out, d_out_lengths, d_scores, d_buf)) return -1;
     for (int b = 0; b < B; ++b) {
         if (n_frames[b] > 0) { s->frames[b] += n_frames[b]; s->half[b] ^= 1; }
         if (final && final[b]) s->frames[b] = 0;

@@ -677,15 +677,170 @@ def ctc_beam_decode(probs, input_lengths=None, blank=0, beam_width=16, cutoff_to
     return out, n, sc
 
 
+class NgramLm:
+    """``nntk_ngram_lm_*``: a token-level n-gram language model as a deterministic backoff automaton, for ``ctc_beam_decode_lm_device``
+    and ``CtcBeamStream(lm=...)`` (INTEGRATION.md "CTC prefix beam search", Language-model fusion).  Log-probabilities are natural."""
+
+    def __init__(self, h, n_states):
+        self.h, self.n_states = h, n_states
+
+    @classmethod
+    def from_arrays(cls, n_classes, blank, arc_begin, arc_label, arc_logp, arc_next, backoff_state, backoff_logw, final_logp=None,
+                    start_state=0, unk_logp=-np.inf, alpha=1.0, beta=0.0):
+        ab = np.ascontiguousarray(np.asarray(arc_begin, dtype=np.int64).reshape(-1))
+        assert C.sizeof(C.c_long) == 8 and ab.shape[0] >= 2, "arc_begin: n_states + 1 entries"
+        ns = ab.shape[0] - 1
+        ints = lambda a: np.ascontiguousarray(np.asarray(a, dtype=np.int32).reshape(-1))
+        al, an, bs = ints(arc_label), ints(arc_next), ints(backoff_state)
+        ap, bw = _f32(arc_logp).reshape(-1), _f32(backoff_logw).reshape(-1)
+        fl = None if final_logp is None else _f32(final_logp).reshape(-1)
+        assert al.shape[0] == an.shape[0] == ap.shape[0], "arc_label, arc_logp, arc_next: one entry per arc"
+        assert bs.shape[0] == bw.shape[0] == ns and (fl is None or fl.shape[0] == ns), "backoff_state, backoff_logw, final_logp: one entry per state"
+        na = al.shape[0]
+        assert ab.size == 0 or int(ab.max()) <= na, "arc_begin points past the arc arrays"
+        h = capi.load().nntk_ngram_lm_create(int(n_classes), int(blank), ns, ab.ctypes.data_as(C.POINTER(C.c_long)),
+                                             al.ctypes.data_as(capi.ip), _p(ap), an.ctypes.data_as(capi.ip), bs.ctypes.data_as(capi.ip),
+                                             _p(bw), None if fl is None else _p(fl), int(start_state), float(unk_logp), float(alpha),
+                                             float(beta))
+        if not h:
+            raise capi.NNTKError("nntk_ngram_lm_create: " + capi.last_error())
+        return cls(h, ns)
+
+    @staticmethod
+    def arpa_arrays(text, classes, unk_logp=-np.inf):
+        """The automaton of an ARPA file's text.  ``classes``: token -> class index.  log10 becomes ln; the states are the contexts
+        that occur (as a history of some n-gram, or as the n-1 last tokens of a non-final one), shortest first; ``<s>`` is dropped
+        as a label and the start state is the context (<s>) when there is one; ``</s>`` becomes final_logp, backed off.
+        -> dict of from_arrays' array arguments"""
+        ln10 = float(np.log(10.0))
+        grams, order = {}, 0
+        for line in text.splitlines():
+            line = line.strip()
+            if line.startswith("\\") and line.endswith("-grams:"):
+                order = int(line[1:line.index("-")])
+            elif line.startswith("\\") or not line or line.startswith("ngram "):
+                order = 0 if line.startswith("\\") else order
+            elif order:
+                f = line.split()
+                toks = tuple(f[1:1 + order])
+                grams[toks] = (float(f[0]) * ln10, float(f[1 + order]) * ln10 if len(f) > 1 + order else 0.0)
+        nmax = max((len(g) for g in grams), default=1)
+        ctxs = {()}
+        for g in grams:
+            if "</s>" not in g[:-1]:
+                ctxs.add(g[:-1])
+                if len(g) < nmax and g[-1] != "</s>":
+                    ctxs.add(g)
+        ctxs = {c for c in ctxs if "<s>" not in c[1:]}
+        closed = set()
+        for c in ctxs:                                   # every suffix of a context is a context: the backoff chain
+            while c not in closed:
+                closed.add(c)
+                c = c[1:]
+        order_ctx = sorted(closed, key=lambda c: (len(c), c))
+        sid = {c: i for i, c in enumerate(order_ctx)}
+
+        def longest(c):
+            while c not in sid:
+                c = c[1:]
+            return sid[c]
+        arc_begin, arc_label, arc_logp, arc_next, bo_state, bo_logw, final = [0], [], [], [], [], [], []
+        for c in order_ctx:
+            arcs = sorted((classes[g[-1]], lp, g) for g, (lp, _) in grams.items()
+                          if g[:-1] == c and g[-1] in classes and g[-1] not in ("<s>", "</s>"))
+            for k, lp, g in arcs:
+                arc_label.append(k); arc_logp.append(lp); arc_next.append(longest(g[-(nmax - 1):] if nmax > 1 else ()))
+            arc_begin.append(len(arc_label))
+            bo_state.append(-1 if not c else longest(c[1:]))
+            bo_logw.append(grams.get(c, (0.0, 0.0))[1] if c else 0.0)
+            f, cc = 0.0, c                               # </s> from this context, backed off
+            while cc + ("</s>",) not in grams and cc:
+                f += grams.get(cc, (0.0, 0.0))[1]
+                cc = cc[1:]
+            final.append(f + grams[cc + ("</s>",)][0] if cc + ("</s>",) in grams else -np.inf)
+        return dict(arc_begin=arc_begin, arc_label=arc_label, arc_logp=arc_logp, arc_next=arc_next, backoff_state=bo_state,
+                    backoff_logw=bo_logw, final_logp=final, start_state=sid.get(("<s>",), 0), unk_logp=unk_logp)
+
+    @classmethod
+    def from_arpa(cls, text, classes, blank, alpha=1.0, beta=0.0, unk_logp=-np.inf):
+        """``classes``: token -> class index (the blank has no token).  Not a hot path: pure Python."""
+        n_classes = max(list(classes.values()) + [blank]) + 1
+        return cls.from_arrays(n_classes, blank, alpha=alpha, beta=beta, **cls.arpa_arrays(text, classes, unk_logp))
+
+    def score(self, labels, with_final=False):
+        """sum of ln F along labels (+ ln E of the last state): what the fused score holds beyond the acoustic one.  Host only."""
+        lab = np.ascontiguousarray(np.asarray(labels, dtype=np.int32).reshape(-1))
+        v = capi.load().nntk_ngram_lm_score(self.h, lab.ctypes.data_as(capi.ip), lab.shape[0], int(bool(with_final)))
+        if v != v:
+            raise capi.NNTKError("nntk_ngram_lm_score: " + capi.last_error())
+        return v
+
+    def device_bytes(self):
+        return capi.load().nntk_ngram_lm_device_bytes(self.h)
+
+    def close(self):
+        if self.h:
+            capi.load().nntk_ngram_lm_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def ctc_beam_decode_lm_device(probs, lm, input_lengths=None, blank=0, beam_width=16, cutoff_top_n=0, nbest=1, labels_out=None,
+                              out_lengths=None, scores=None, workspace=None):
+    """``nntk_ctc_beam_decode_lm_device``: ``ctc_beam_decode_device`` with the n-gram model ``lm`` (an NgramLm, or None) fused in;
+    scores = ln(acoustic prefix probability x LM factors x end-of-sentence factor)"""
+    import torch
+    B, T, Cc = probs.shape
+    il, ilp = _ctc_lengths(input_lengths, B)
+    L = capi.load()
+    need = L.nntk_ctc_beam_lm_workspace_floats(B, T, Cc, beam_width, cutoff_top_n)
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.float32, device=probs.device)
+    assert workspace.numel() >= need, "workspace: nntk_ctc_beam_lm_workspace_floats(B, T, C, beam_width, cutoff_top_n) floats"
+    if labels_out is None:
+        labels_out = torch.empty((B, max(nbest, 0), T), dtype=torch.int32, device=probs.device)
+    if out_lengths is None:
+        out_lengths = torch.empty((B, max(nbest, 0)), dtype=torch.int32, device=probs.device)
+    if scores is None:
+        scores = torch.empty((B, max(nbest, 0)), dtype=torch.float32, device=probs.device)
+    check(L.nntk_ctc_beam_decode_lm_device(_dp(probs), B, T, Cc, ilp, blank, beam_width, cutoff_top_n, nbest, lm.h if lm else None,
+                                           C.c_void_p(labels_out.data_ptr()), C.c_void_p(out_lengths.data_ptr()), _dp(scores),
+                                           _dp(workspace)), "nntk_ctc_beam_decode_lm_device")
+    return labels_out, out_lengths, scores
+
+
+def ctc_beam_decode_lm(probs, lm, input_lengths=None, blank=0, beam_width=16, cutoff_top_n=0, nbest=1):
+    """The host-memory form (``nntk_ctc_beam_decode_lm``): probs [B,T,C] numpy array."""
+    probs = _f32(probs)
+    B, T, Cc = probs.shape
+    il, ilp = _ctc_lengths(input_lengths, B)
+    nb = max(nbest, 0)
+    out, n, sc = np.empty((B, nb, T), np.int32), np.empty((B, nb), np.int32), np.empty((B, nb), np.float32)
+    check(capi.load().nntk_ctc_beam_decode_lm(_p(probs), B, T, Cc, ilp, blank, beam_width, cutoff_top_n, nbest, lm.h if lm else None,
+                                              out.ctypes.data_as(capi.ip), n.ctypes.data_as(capi.ip), _p(sc)), "nntk_ctc_beam_decode_lm")
+    return out, n, sc
+
+
 class CtcBeamStream:
     """``nntk_ctc_beam_stream_*``: prefix beam search pushed chunk by chunk for ``batch`` independent streams.  After every push row
     b holds what ``ctc_beam_decode_device`` gives on the row's frames since its last reset, bit for bit (INTEGRATION.md "CTC prefix
-    beam search", Streaming).  ``max_labels``: the capacity of the returned label strings (default: max_frames)."""
+    beam search", Streaming).  ``max_labels``: the capacity of the returned label strings (default: max_frames).  ``lm``: an NgramLm
+    fused in as by ``ctc_beam_decode_lm_device``; it must outlive the stream."""
 
-    def __init__(self, batch, max_frames, C, blank=0, beam_width=16, cutoff_top_n=0, nbest=1, max_labels=None):
+    def __init__(self, batch, max_frames, C, blank=0, beam_width=16, cutoff_top_n=0, nbest=1, max_labels=None, lm=None):
         self.B, self.T, self.C, self.nbest = int(batch), int(max_frames), int(C), int(nbest)
         self.max_labels = int(max_frames if max_labels is None else max_labels)
-        self.h = capi.load().nntk_ctc_beam_stream_create(self.B, self.T, self.C, blank, beam_width, cutoff_top_n, nbest, self.max_labels)
+        self.lm = lm
+        if lm is None:
+            self.h = capi.load().nntk_ctc_beam_stream_create(self.B, self.T, self.C, blank, beam_width, cutoff_top_n, nbest, self.max_labels)
+        else:
+            self.h = capi.load().nntk_ctc_beam_stream_create_lm(self.B, self.T, self.C, blank, beam_width, cutoff_top_n, nbest,
+                                                                self.max_labels, lm.h)
         if not self.h:
             raise capi.NNTKError("nntk_ctc_beam_stream_create: " + capi.last_error())
 
