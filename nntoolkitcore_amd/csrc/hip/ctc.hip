@@ -272,7 +272,8 @@ int nntk_shim_ctc_loss(const float *d_probs, int B, int T, int C, const int *h_i
     const CtcLayout lay = ctc_layout(B, T, maxL);
     const int Smax = 2 * maxL + 1;
     const size_t lds = (((size_t)Smax * 4 + 15) & ~(size_t)15) + 2 * (size_t)(Smax + 4) * sizeof(float2);
-    if (lds > CTC_LDS_LIMIT) return nntk_fail_msg("nntk_ctc_loss_device: max_label_len is beyond what one workgroup's LDS holds (4000)");
+    if (lds > CTC_LDS_LIMIT)
+        return nntk_fail_msg("nntk_ctc_loss_device: max_label_len is beyond what one workgroup's LDS holds (" NNTK_STR(NNTK_CTC_ALIGN_MAX_LABELS) ")");
     if (d_dprobs && C > CTC_GRAD_MAX_C) return nntk_fail_msg("nntk_ctc_loss_device: the gradient takes at most 32768 classes");
     int *d_ints = (int *)d_ws;
     if (nntk_shim_upload_ints(d_ints, h_input_lengths, B)) return -1;

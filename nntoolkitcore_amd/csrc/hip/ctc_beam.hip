@@ -38,12 +38,12 @@
 #include "nntk_common.hpp"
 #include "ctc_xf.hpp"
 
-#define BEAM_MAX_W 128
-#define BEAM_MAX_CELLS 16384              // W * (n + 1) cells of 8 bytes: 128 KiB of the 160 KiB of LDS
+#define BEAM_MAX_W NNTK_CTC_BEAM_MAX_W    // (the three limits the host layer checks too: nntk_shim.h)
+#define BEAM_MAX_CELLS NNTK_CTC_BEAM_MAX_CELLS  // W * (n + 1) cells of 8 bytes: 128 KiB of the 160 KiB of LDS
 #define BEAM_LIST 256                     // survivors ranked against each other
 #define BEAM_PF 4                         // staged words a lane carries in registers across the selection
 #define BEAM_BT_RECORDS 8192              // backtrack: records staged per block of frames (64 KiB)
-#define BEAM_MAX_T ((1 << 23) - 1)        // the prefix length shares a signed word with the parent rank: length << 8 < 2^31
+#define BEAM_MAX_T NNTK_CTC_BEAM_MAX_T    // the prefix length shares a signed word with the parent rank: length << 8 < 2^31
 
 typedef unsigned long long u64;
 
@@ -776,22 +776,14 @@ __global__ __launch_bounds__(CTC_THREADS) void ctc_beam_commit_kernel(int B, int
     }
 }
 
-// lm NULL: the acoustic-only kernels, exactly
-static int beam_decode(const float *d_probs, int B, int T, int C, const int *h_input_lengths, int blank, int W, int cutoff_top_n,
-                       int nbest, const nntk_shim_lm *lm, int *d_labels_out, int *d_out_lengths, float *d_scores, float *d_ws) {
-    if (B <= 0) return 0;
-    if (((uintptr_t)d_ws & 15) != 0) return nntk_fail_msg("nntk_ctc_beam_decode_device: the workspace must be 16-byte aligned");
-    const int ncut = beam_ncut(C, cutoff_top_n), n = ncut ? ncut : C - 1;
-    if (W < 1 || W > BEAM_MAX_W || nbest < 1 || nbest > W || (long)W * (n + 1) > BEAM_MAX_CELLS || T > BEAM_MAX_T)
-        return nntk_fail_msg("nntk_ctc_beam_decode_device: beam_width, nbest or beam_width * (classes + 1) beyond the kernel's limits");
-    const BeamLayout lay = beam_layout(B, T, W, ncut, lm != nullptr);
-    int *d_lens = (int *)d_ws, *d_nfin = d_lens + B;
-    int *d_forder = (int *)(d_ws + lay.forder);
-    float4 *d_fmass = (float4 *)(d_ws + lay.fmass);
-    int2 *d_hist = (int2 *)(d_ws + lay.hist);
-    float4 *d_mass = (float4 *)(d_ws + lay.mass);
-    float2 *d_pairs = (float2 *)(d_ws + lay.cut);
-    if (nntk_shim_upload_ints(d_lens, h_input_lengths, B)) return -1;
+// ---- host section.  lm NULL: the acoustic-only kernels, exactly ----
+
+// The class cut (when one applies) and the beam kernel.  One-shot call (STREAM false): lens = the rows' lengths, nfin / mass / forder /
+// fmass the workspace's, an empty carry.  Push (STREAM true): lens = the control block, cs = the handle's beam, those four null.
+template <bool STREAM>
+static int beam_launch(const float *d_probs, int B, int T, int C, int blank, int W, int ncut, const nntk_shim_lm *lm, const int *d_lens,
+                       int *d_nfin, int2 *d_hist, float4 *d_mass, float2 *d_pairs, const BeamCarry &cs, int *d_forder, float4 *d_fmass) {
+    const int n = ncut ? ncut : C - 1;
     const long frames = (long)B * T;
     if (ncut && frames > 0) {
         long g = (frames + 3) / 4;
@@ -803,15 +795,16 @@ static int beam_decode(const float *d_probs, int B, int T, int C, const int *h_i
     // the frame's probabilities (or its cut pairs) double-buffered in LDS where they fit beside the cells
     const bool stage = beam_lds(W, n, C, ncut != 0, true, lm != nullptr).total <= CTC_LDS_LIMIT;
     const size_t lds = beam_lds(W, n, C, ncut != 0, stage, lm != nullptr).total;
-    if (lds > CTC_LDS_LIMIT) return nntk_fail_msg("nntk_ctc_beam_decode_device: the beam does not fit one workgroup's LDS");
+    if (lds > CTC_LDS_LIMIT)
+        return nntk_fail_msg(STREAM ? "nntk_ctc_beam_stream_push_device: the beam does not fit one workgroup's LDS"
+                                    : "nntk_ctc_beam_decode_device: the beam does not fit one workgroup's LDS");
     const unsigned magic = n + 1 > 1 ? (unsigned)(0x100000000ull / (unsigned)(n + 1)) + 1u : 0u;
     const nntk_shim_lm lmv = lm ? *lm : nntk_shim_lm();
 #define BEAM_GO(CUT, STAGE, LM)                                                                                                    \
     do {                                                                                                                           \
-        if (lds > 48 * 1024 && nntk_set_max_dynamic_lds((const void *)ctc_beam_kernel<CUT, STAGE, false, LM>, lds)) return -1;     \
-        hipLaunchKernelGGL((ctc_beam_kernel<CUT, STAGE, false, LM>), dim3((unsigned)B), dim3(CTC_THREADS), lds, nntk_stream(),     \
-                           d_probs, T, C, blank, W, n, magic, d_lens, d_nfin, d_hist, d_mass, d_pairs, BeamCarry(), lmv, d_forder,   \
-                           d_fmass);                                                                                               \
+        if (lds > 48 * 1024 && nntk_set_max_dynamic_lds((const void *)ctc_beam_kernel<CUT, STAGE, STREAM, LM>, lds)) return -1;    \
+        hipLaunchKernelGGL((ctc_beam_kernel<CUT, STAGE, STREAM, LM>), dim3((unsigned)B), dim3(CTC_THREADS), lds, nntk_stream(),    \
+                           d_probs, T, C, blank, W, n, magic, d_lens, d_nfin, d_hist, d_mass, d_pairs, cs, lmv, d_forder, d_fmass); \
     } while (0)
 #define BEAM_GO2(LM)                                                                                                               \
     do {                                                                                                                           \
@@ -819,7 +812,34 @@ static int beam_decode(const float *d_probs, int B, int T, int C, const int *h_i
         else { if (stage) BEAM_GO(false, true, LM); else BEAM_GO(false, false, LM); }                                              \
     } while (0)
     if (lm) BEAM_GO2(true); else BEAM_GO2(false);
+#undef BEAM_GO2
+#undef BEAM_GO
     NNTK_LAUNCH_CHECK("ctc_beam_kernel");
+    return 0;
+}
+
+extern "C" {
+
+size_t nntk_shim_ctc_beam_workspace_floats(int batch, int T, int C, int beam_width, int cutoff_top_n, int lm) {
+    return beam_layout(batch, T, beam_width, beam_ncut(C, cutoff_top_n), lm != 0).total;
+}
+
+int nntk_shim_ctc_beam_decode(const float *d_probs, int B, int T, int C, const int *h_input_lengths, int blank, int W, int cutoff_top_n,
+                              int nbest, const nntk_shim_lm *lm, int *d_labels_out, int *d_out_lengths, float *d_scores, float *d_ws) {
+    if (B <= 0) return 0;
+    if (((uintptr_t)d_ws & 15) != 0) return nntk_fail_msg("nntk_ctc_beam_decode_device: the workspace must be 16-byte aligned");
+    const int ncut = beam_ncut(C, cutoff_top_n), n = ncut ? ncut : C - 1;
+    if (W < 1 || W > BEAM_MAX_W || nbest < 1 || nbest > W || (long)W * (n + 1) > BEAM_MAX_CELLS || T > BEAM_MAX_T)
+        return nntk_fail_msg("nntk_ctc_beam_decode_device: beam_width, nbest or beam_width * (classes + 1) beyond the kernel's limits");
+    const BeamLayout lay = beam_layout(B, T, W, ncut, lm != nullptr);
+    int *d_lens = (int *)d_ws, *d_nfin = d_lens + B;
+    int *d_forder = (int *)(d_ws + lay.forder);
+    float4 *d_fmass = (float4 *)(d_ws + lay.fmass);
+    int2 *d_hist = (int2 *)(d_ws + lay.hist);
+    float4 *d_mass = (float4 *)(d_ws + lay.mass);
+    if (nntk_shim_upload_ints(d_lens, h_input_lengths, B)) return -1;
+    if (beam_launch<false>(d_probs, B, T, C, blank, W, ncut, lm, d_lens, d_nfin, d_hist, d_mass, (float2 *)(d_ws + lay.cut), BeamCarry(),
+                           d_forder, d_fmass)) return -1;
     const size_t blds = (size_t)BEAM_BT_RECORDS * sizeof(int2);
 #define BEAM_BT(FIN)                                                                                                               \
     do {                                                                                                                           \
@@ -829,28 +849,32 @@ static int beam_decode(const float *d_probs, int B, int T, int C, const int *h_i
     } while (0)
     if (lm) BEAM_BT(true); else BEAM_BT(false);
 #undef BEAM_BT
-#undef BEAM_GO2
-#undef BEAM_GO
     NNTK_LAUNCH_CHECK("ctc_beam_backtrack_kernel");
     return 0;
 }
 
-// the cell and LDS limits of the launch, without a device; lm: with the per-entry LM state in the LDS state block
-static int beam_stream_check(int C, int W, int cutoff_top_n, bool lm) {
+// ---- streaming form: the handle's buffer (beam_stream_layout), one push ----
+size_t nntk_shim_ctc_beam_stream_floats(int batch, int max_frames, int C, int beam_width, int cutoff_top_n, int max_labels, int lm) {
+    return beam_stream_layout(batch, max_frames, beam_width, beam_ncut(C, cutoff_top_n), max_labels, lm != 0).total;
+}
+
+// the limits of the kernel that only the launch knows in the one-shot call; no device is touched.  lm: with the per-entry LM state in the
+// LDS state block
+int nntk_shim_ctc_beam_stream_check(int C, int W, int cutoff_top_n, int lm) {
     const int ncut = beam_ncut(C, cutoff_top_n), n = ncut ? ncut : C - 1;
     if (W < 1 || W > BEAM_MAX_W || (long)W * (n + 1) > BEAM_MAX_CELLS)
         return nntk_fail_msg("nntk_ctc_beam_stream_create: beam_width or beam_width * (classes + 1) beyond the kernel's limits");
-    if (beam_lds(W, n, C, ncut != 0, false, lm).total > CTC_LDS_LIMIT)
+    if (beam_lds(W, n, C, ncut != 0, false, lm != 0).total > CTC_LDS_LIMIT)
         return nntk_fail_msg("nntk_ctc_beam_stream_create: the beam does not fit one workgroup's LDS");
     return 0;
 }
 
-static int beam_stream_push(const float *d_probs, int B, int T, int C, const int *h_ctl, int any_frames, int blank, int W,
-                            int cutoff_top_n, int nbest, int L, const nntk_shim_lm *lm, int *d_labels_out, int *d_out_lengths,
-                            float *d_scores, float *d_buf) {
+int nntk_shim_ctc_beam_stream_push(const float *d_probs, int B, int T, int C, const int *h_ctl, int any_frames, int blank, int W,
+                                   int cutoff_top_n, int nbest, int L, const nntk_shim_lm *lm, int *d_labels_out, int *d_out_lengths,
+                                   float *d_scores, float *d_buf) {
     if (B <= 0) return 0;
     if (((uintptr_t)d_buf & 15) != 0) return nntk_fail_msg("nntk_ctc_beam_stream_push_device: the handle's buffer is not 16-byte aligned");
-    const int ncut = beam_ncut(C, cutoff_top_n), n = ncut ? ncut : C - 1;
+    const int ncut = beam_ncut(C, cutoff_top_n);
     const BeamStreamLayout lay = beam_stream_layout(B, T, W, ncut, L, lm != nullptr);
     int *d_ctl = (int *)d_buf;
     BeamCarry cs;
@@ -863,39 +887,10 @@ static int beam_stream_push(const float *d_probs, int B, int T, int C, const int
     cs.seen = d_ctl + B;
     int *d_strs = (int *)(d_buf + lay.str);
     int2 *d_hist = (int2 *)(d_buf + lay.hist);
-    float2 *d_pairs = (float2 *)(d_buf + lay.cut);
     const nntk_shim_lm lmv = lm ? *lm : nntk_shim_lm();
     if (nntk_shim_upload_ints(d_ctl, h_ctl, 4L * B)) return -1;
-    if (any_frames) {
-        const long frames = (long)B * T;
-        if (ncut) {
-            long g = (frames + 3) / 4;
-            if (g > 16384) g = 16384;
-            hipLaunchKernelGGL(ctc_beam_cut_kernel, dim3((unsigned)g), dim3(CTC_THREADS), 0, nntk_stream(), d_probs, T, C, blank, n, d_ctl,
-                               d_pairs, frames);
-            NNTK_LAUNCH_CHECK("ctc_beam_cut_kernel");
-        }
-        const bool stage = beam_lds(W, n, C, ncut != 0, true, lm != nullptr).total <= CTC_LDS_LIMIT;
-        const size_t lds = beam_lds(W, n, C, ncut != 0, stage, lm != nullptr).total;
-        if (lds > CTC_LDS_LIMIT) return nntk_fail_msg("nntk_ctc_beam_stream_push_device: the beam does not fit one workgroup's LDS");
-        const unsigned magic = n + 1 > 1 ? (unsigned)(0x100000000ull / (unsigned)(n + 1)) + 1u : 0u;
-#define BEAM_GO(CUT, STAGE, LM)                                                                                                    \
-    do {                                                                                                                           \
-        if (lds > 48 * 1024 && nntk_set_max_dynamic_lds((const void *)ctc_beam_kernel<CUT, STAGE, true, LM>, lds)) return -1;      \
-        hipLaunchKernelGGL((ctc_beam_kernel<CUT, STAGE, true, LM>), dim3((unsigned)B), dim3(CTC_THREADS), lds, nntk_stream(),      \
-                           d_probs, T, C, blank, W, n, magic, d_ctl, (int *)nullptr, d_hist, (float4 *)nullptr, d_pairs, cs, lmv,  \
-                           (int *)nullptr, (float4 *)nullptr);                                                                     \
-    } while (0)
-#define BEAM_GO2(LM)                                                                                                               \
-    do {                                                                                                                           \
-        if (ncut) { if (stage) BEAM_GO(true, true, LM); else BEAM_GO(true, false, LM); }                                           \
-        else { if (stage) BEAM_GO(false, true, LM); else BEAM_GO(false, false, LM); }                                              \
-    } while (0)
-        if (lm) BEAM_GO2(true); else BEAM_GO2(false);
-#undef BEAM_GO2
-#undef BEAM_GO
-        NNTK_LAUNCH_CHECK("ctc_beam_kernel");
-    }
+    if (any_frames && beam_launch<true>(d_probs, B, T, C, blank, W, ncut, lm, d_ctl, nullptr, d_hist, nullptr, (float2 *)(d_buf + lay.cut),
+                                        cs, nullptr, nullptr)) return -1;
     const size_t blds = (size_t)BEAM_BT_RECORDS * sizeof(int2);
 #define BEAM_COMMIT(FIN)                                                                                                           \
     do {                                                                                                                           \
@@ -907,50 +902,6 @@ static int beam_stream_push(const float *d_probs, int B, int T, int C, const int
 #undef BEAM_COMMIT
     NNTK_LAUNCH_CHECK("ctc_beam_commit_kernel");
     return 0;
-}
-
-extern "C" {
-
-size_t nntk_shim_ctc_beam_workspace_floats(int batch, int T, int C, int beam_width, int cutoff_top_n) {
-    return beam_layout(batch, T, beam_width, beam_ncut(C, cutoff_top_n)).total;
-}
-size_t nntk_shim_ctc_beam_lm_workspace_floats(int batch, int T, int C, int beam_width, int cutoff_top_n) {
-    return beam_layout(batch, T, beam_width, beam_ncut(C, cutoff_top_n), true).total;
-}
-
-int nntk_shim_ctc_beam_decode(const float *d_probs, int B, int T, int C, const int *h_input_lengths, int blank, int W, int cutoff_top_n,
-                              int nbest, int *d_labels_out, int *d_out_lengths, float *d_scores, float *d_ws) {
-    return beam_decode(d_probs, B, T, C, h_input_lengths, blank, W, cutoff_top_n, nbest, nullptr, d_labels_out, d_out_lengths, d_scores,
-                       d_ws);
-}
-int nntk_shim_ctc_beam_decode_lm(const float *d_probs, int B, int T, int C, const int *h_input_lengths, int blank, int W, int cutoff_top_n,
-                                 int nbest, const nntk_shim_lm *lm, int *d_labels_out, int *d_out_lengths, float *d_scores, float *d_ws) {
-    return beam_decode(d_probs, B, T, C, h_input_lengths, blank, W, cutoff_top_n, nbest, lm, d_labels_out, d_out_lengths, d_scores, d_ws);
-}
-
-// ---- streaming form: the handle's buffer (beam_stream_layout), one push ----
-size_t nntk_shim_ctc_beam_stream_floats(int batch, int max_frames, int C, int beam_width, int cutoff_top_n, int max_labels) {
-    return beam_stream_layout(batch, max_frames, beam_width, beam_ncut(C, cutoff_top_n), max_labels).total;
-}
-size_t nntk_shim_ctc_beam_stream_lm_floats(int batch, int max_frames, int C, int beam_width, int cutoff_top_n, int max_labels) {
-    return beam_stream_layout(batch, max_frames, beam_width, beam_ncut(C, cutoff_top_n), max_labels, true).total;
-}
-
-// the limits of the kernel that only the launch knows in the one-shot call; no device is touched
-int nntk_shim_ctc_beam_stream_check(int C, int W, int cutoff_top_n) { return beam_stream_check(C, W, cutoff_top_n, false); }
-int nntk_shim_ctc_beam_stream_check_lm(int C, int W, int cutoff_top_n) { return beam_stream_check(C, W, cutoff_top_n, true); }
-
-int nntk_shim_ctc_beam_stream_push(const float *d_probs, int B, int T, int C, const int *h_ctl, int any_frames, int blank, int W,
-                                   int cutoff_top_n, int nbest, int L, int *d_labels_out, int *d_out_lengths, float *d_scores,
-                                   float *d_buf) {
-    return beam_stream_push(d_probs, B, T, C, h_ctl, any_frames, blank, W, cutoff_top_n, nbest, L, nullptr, d_labels_out, d_out_lengths,
-                            d_scores, d_buf);
-}
-int nntk_shim_ctc_beam_stream_push_lm(const float *d_probs, int B, int T, int C, const int *h_ctl, int any_frames, int blank, int W,
-                                      int cutoff_top_n, int nbest, int L, const nntk_shim_lm *lm, int *d_labels_out, int *d_out_lengths,
-                                      float *d_scores, float *d_buf) {
-    return beam_stream_push(d_probs, B, T, C, h_ctl, any_frames, blank, W, cutoff_top_n, nbest, L, lm, d_labels_out, d_out_lengths,
-                            d_scores, d_buf);
 }
 
 }  // extern "C"

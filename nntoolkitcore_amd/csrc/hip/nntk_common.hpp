@@ -64,6 +64,10 @@ int nntk_outer_mfma_launch(const float *d_A, const float *d_B, float *d_partial,
                            long rps, long seq_pitch, long row_pitch);
 int nntk_resident_blocks(const void *kernel, int threads, size_t lds, int max_per_cu);   // occupancy x CUs (0: does not fit)
 
+// a limit of nntk_shim.h inside a message: NNTK_STR(NNTK_CTC_ALIGN_MAX_LABELS) is "4000"
+#define NNTK_STR_(x) #x
+#define NNTK_STR(x) NNTK_STR_(x)
+
 #define NNTK_HIP_TRY(expr)                                             \
     do {                                                               \
         hipError_t _e = (expr);                                        \

@@ -152,8 +152,13 @@ typedef struct {
 int nntk_shim_optim_chunk_floats(long total_floats);
 int nntk_shim_optim_step(const nntk_optim_plan *plan);
 int nntk_shim_optim_set_lr(float *d_ctl, float lr);        /* in stream order */
+/* the CTC kernels' limits, stated here once for the host's checks (ctc.c) and the launchers */
+#define NNTK_CTC_BEAM_MAX_W 128
+#define NNTK_CTC_BEAM_MAX_CELLS 16384           /* beam_width x (expanded classes + 1) cells of 8 bytes: 128 KiB of the 160 KiB of LDS */
+#define NNTK_CTC_BEAM_MAX_T ((1 << 23) - 1)     /* frames of a row, or of a stream's row since its reset: length << 8 < 2^31 in the records */
+#define NNTK_CTC_ALIGN_MAX_LABELS 4000          /* max_label_len of the alignment and the loss: a row's extended states live in LDS */
 /* ---- CTC (ctc.hip): loss rows, gradient with respect to the probabilities, best-path decoding.  The int arrays are HOST memory,
- *      already checked by the caller (train.c), never NULL, copied in stream order; d_dprobs NULL = loss only; d_ws 16-byte aligned,
+ *      already checked by the caller (ctc.c), never NULL, copied in stream order; d_dprobs NULL = loss only; d_ws 16-byte aligned,
  *      nntk_shim_ctc_workspace_floats words (loss only: the int arrays and 2 words per row at its start are all that is touched) ---- */
 size_t nntk_shim_ctc_workspace_floats(int batch, int T, int max_label_len);
 int nntk_shim_ctc_loss(const float *d_probs, int B, int T, int C, const int *h_input_lengths, const int *h_labels,
@@ -163,39 +168,32 @@ int nntk_shim_ctc_greedy_decode(const float *d_probs, int B, int T, int C, const
 /* the chunk's labels only: d_prev [B] device, in/out, the argmax of each row's last frame seen (-1: none) */
 int nntk_shim_ctc_greedy_decode_stream(const float *d_probs, int B, int T, int C, const int *h_input_lengths, int blank, int *d_prev,
                                        int *d_labels_out, int *d_out_lengths);
-/* ---- CTC prefix beam search (ctc_beam.hip): the n-best prefixes of every row with their log-probabilities.  h_input_lengths is HOST
- *      memory, checked by the caller (train.c), never NULL; d_ws 16-byte aligned, nntk_shim_ctc_beam_workspace_floats words ---- */
-size_t nntk_shim_ctc_beam_workspace_floats(int batch, int T, int C, int beam_width, int cutoff_top_n);
-int nntk_shim_ctc_beam_decode(const float *d_probs, int B, int T, int C, const int *h_input_lengths, int blank, int beam_width,
-                              int cutoff_top_n, int nbest, int *d_labels_out, int *d_out_lengths, float *d_scores, float *d_ws);
-/* streaming form: d_buf = the handle's buffer, nntk_shim_ctc_beam_stream_floats words, 16-byte aligned, kept from push to push (the
- * carried beam, both halves of the label strings, the records and cut pairs of one push).  h_ctl HOST [4][B], built by train.c:
- * frames in this push | frames the row had seen before it | the current half of its label strings | 0.  any_frames 0: no row brings
- * a frame, only the outputs are rewritten.  _check: the launch-time limits, without a device. */
-size_t nntk_shim_ctc_beam_stream_floats(int batch, int max_frames, int C, int beam_width, int cutoff_top_n, int max_labels);
-int nntk_shim_ctc_beam_stream_check(int C, int beam_width, int cutoff_top_n);
-int nntk_shim_ctc_beam_stream_push(const float *d_probs, int B, int max_frames, int C, const int *h_ctl, int any_frames, int blank,
-                                   int beam_width, int cutoff_top_n, int nbest, int max_labels, int *d_labels_out, int *d_out_lengths,
-                                   float *d_scores, float *d_buf);
 /* Language-model fusion (INTEGRATION.md "CTC prefix beam search", Language-model fusion): the device tables of an n-gram handle, 16-byte
  * records -- arcs {label, next state, factor mantissa, factor exponent}, states {first arc, arcs, backoff state, 0} and per-state factors
- * {backoff m, e, final m, e}.  depth = the longest backoff chain: the walk's loop count.  lm == NULL in the _lm calls: the calls above. */
+ * {backoff m, e, final m, e}.  depth = the longest backoff chain: the walk's loop count. */
 typedef struct {
     const int *d_arcs, *d_states, *d_factors;
     int n_states, start_state, depth, unk_m, unk_e;
 } nntk_shim_lm;
-size_t nntk_shim_ctc_beam_lm_workspace_floats(int batch, int T, int C, int beam_width, int cutoff_top_n);
-int nntk_shim_ctc_beam_decode_lm(const float *d_probs, int B, int T, int C, const int *h_input_lengths, int blank, int beam_width,
-                                 int cutoff_top_n, int nbest, const nntk_shim_lm *lm, int *d_labels_out, int *d_out_lengths,
-                                 float *d_scores, float *d_ws);
-size_t nntk_shim_ctc_beam_stream_lm_floats(int batch, int max_frames, int C, int beam_width, int cutoff_top_n, int max_labels);
-int nntk_shim_ctc_beam_stream_check_lm(int C, int beam_width, int cutoff_top_n);
-int nntk_shim_ctc_beam_stream_push_lm(const float *d_probs, int B, int max_frames, int C, const int *h_ctl, int any_frames, int blank,
-                                      int beam_width, int cutoff_top_n, int nbest, int max_labels, const nntk_shim_lm *lm,
-                                      int *d_labels_out, int *d_out_lengths, float *d_scores, float *d_buf);
+/* ---- CTC prefix beam search (ctc_beam.hip): the n-best prefixes of every row with their log-probabilities.  lm NULL (the sizes and the
+ *      check: lm 0): acoustic scores only, on kernels compiled without the model.  h_input_lengths is HOST memory, checked by the caller
+ *      (ctc.c), never NULL; d_ws 16-byte aligned, nntk_shim_ctc_beam_workspace_floats words ---- */
+size_t nntk_shim_ctc_beam_workspace_floats(int batch, int T, int C, int beam_width, int cutoff_top_n, int lm);
+int nntk_shim_ctc_beam_decode(const float *d_probs, int B, int T, int C, const int *h_input_lengths, int blank, int beam_width,
+                              int cutoff_top_n, int nbest, const nntk_shim_lm *lm, int *d_labels_out, int *d_out_lengths,
+                              float *d_scores, float *d_ws);
+/* streaming form: d_buf = the handle's buffer, nntk_shim_ctc_beam_stream_floats words, 16-byte aligned, kept from push to push (the
+ * carried beam, both halves of the label strings, the records and cut pairs of one push).  h_ctl HOST [4][B], built by ctc.c:
+ * frames in this push | frames the row had seen before it | the current half of its label strings | 0.  any_frames 0: no row brings
+ * a frame, only the outputs are rewritten.  _check: the launch-time limits, without a device. */
+size_t nntk_shim_ctc_beam_stream_floats(int batch, int max_frames, int C, int beam_width, int cutoff_top_n, int max_labels, int lm);
+int nntk_shim_ctc_beam_stream_check(int C, int beam_width, int cutoff_top_n, int lm);
+int nntk_shim_ctc_beam_stream_push(const float *d_probs, int B, int max_frames, int C, const int *h_ctl, int any_frames, int blank,
+                                   int beam_width, int cutoff_top_n, int nbest, int max_labels, const nntk_shim_lm *lm,
+                                   int *d_labels_out, int *d_out_lengths, float *d_scores, float *d_buf);
 /* ---- CTC forced alignment (ctc_align.hip): the best single alignment of every row to its labels -- the state of every frame, the
  *      frame span of every label, ln of the path's probability.  The int arrays are HOST memory, already checked by the caller
- *      (train.c), never NULL; d_states / d_spans may be NULL; d_ws 16-byte aligned, nntk_shim_ctc_align_workspace_floats words ---- */
+ *      (ctc.c), never NULL; d_states / d_spans may be NULL; d_ws 16-byte aligned, nntk_shim_ctc_align_workspace_floats words ---- */
 size_t nntk_shim_ctc_align_workspace_floats(int batch, int T, int max_label_len);
 int nntk_shim_ctc_align(const float *d_probs, int B, int T, int C, const int *h_input_lengths, const int *h_labels,
                         const int *h_label_lengths, int max_label_len, int blank, int *d_states, int *d_spans, float *d_scores,

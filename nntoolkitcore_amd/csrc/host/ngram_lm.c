@@ -184,7 +184,7 @@ double nntk_ngram_lm_score(NntkNgramLm lm, const int *labels, int n, int with_fi
     return sum;
 }
 
-/* ---- for the decoders (train.c) ---- */
+/* ---- for the decoders (ctc.c) ---- */
 int nntk_ngram_lm_matches(NntkNgramLm lm, int C, int blank) { return lm->n_classes == C && lm->blank == blank; }
 
 int nntk_ngram_lm_device(NntkNgramLm lm, nntk_shim_lm *out) {

@@ -99,7 +99,7 @@ int nntk_lstm_apply_device_h2(LSTM f, const float *d_in, const float *d_in_f3, f
 __attribute__((visibility("hidden")))
 int nntk_check_lengths(const char *who, const int *lengths, int B, int T, int *min_len, int *max_len);
 
-/* ngram_lm.c, for the fused decoders of train.c: whether the model was built for these classes and this blank; the device form of its
+/* ngram_lm.c, for the fused decoders of ctc.c: whether the model was built for these classes and this blank; the device form of its
  * tables, uploaded by the first call (-1 with the error set when that fails).  Internal to the library. */
 __attribute__((visibility("hidden"))) int nntk_ngram_lm_matches(NntkNgramLm lm, int C, int blank);
 __attribute__((visibility("hidden"))) int nntk_ngram_lm_device(NntkNgramLm lm, nntk_shim_lm *out);

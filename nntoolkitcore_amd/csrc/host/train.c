@@ -157,431 +157,6 @@ void categorical_crossentropy_derivative(float *y, float *y_pred, float *d_y_pre
     loss_grad_host(1, y, y_pred, d_y_pred, c, batch);
 }
 
-/* ---- CTC (csrc/hip/ctc.hip): every host array is checked here, before anything is enqueued or allocated ---- */
-static int ctc_fail(const char *who, const char *fmt, int a, int b, int c) {
-    char msg[200];
-    int n = snprintf(msg, sizeof msg, "%s: ", who);
-    snprintf(msg + n, sizeof msg - (size_t)n, fmt, a, b, c);
-    nntk_set_error(msg);
-    return -1;
-}
-static int ctc_check_shape(const char *who, int batch, int T, int C, int blank) {
-    if (batch < 0 || T < 0 || C <= 0) return ctc_fail(who, "batch %d, T %d, C %d: batch and T must be >= 0, C > 0", batch, T, C);
-    if (blank < 0 || blank >= C) return ctc_fail(who, "blank %d is outside [0, %d)", blank, C, 0);
-    return 0;
-}
-static int ctc_check_labels(const char *who, int batch, int C, const int *labels, const int *label_lengths, int max_label_len, int blank) {
-    if (max_label_len < 0) return ctc_fail(who, "max_label_len %d < 0", max_label_len, 0, 0);
-    if (batch > 0 && (!label_lengths || (max_label_len > 0 && !labels))) NNTK_FAIL("nntk_ctc_loss: NULL labels / label_lengths");
-    for (int b = 0; b < batch; ++b) {
-        const int L = label_lengths[b];
-        if (L < 0 || L > max_label_len) return ctc_fail(who, "label_lengths[%d] = %d is outside [0, %d]", b, L, max_label_len);
-        for (int i = 0; i < L; ++i) {
-            const int k = labels[(size_t)b * max_label_len + i];
-            if (k < 0 || k >= C) return ctc_fail(who, "labels[%d][%d] = %d is not a class", b, i, k);
-            if (k == blank) return ctc_fail(who, "labels[%d][%d] is the blank (%d)", b, i, k);
-        }
-    }
-    return 0;
-}
-/* the input lengths the kernels read: the caller's, or T for every row; NULL = out of host memory */
-static int *ctc_lengths(const int *input_lengths, int batch, int T) {
-    int *len = (int *)malloc((size_t)(batch > 0 ? batch : 1) * sizeof(int));
-    if (!len) { nntk_set_error("out of host memory"); return NULL; }
-    for (int b = 0; b < batch; ++b) len[b] = input_lengths ? input_lengths[b] : T;
-    return len;
-}
-
-size_t nntk_ctc_workspace_floats(int batch, int T, int max_label_len) {
-    return nntk_shim_ctc_workspace_floats(batch, T, max_label_len);
-}
-
-int nntk_ctc_loss_device(const float *d_probs, int batch, int T, int C, const int *input_lengths, const int *labels,
-                         const int *label_lengths, int max_label_len, int blank, float *d_loss_rows, float *d_dprobs,
-                         float *d_workspace) {
-    static const char who[] = "nntk_ctc_loss_device";
-    nntk_shim_clear_error();
-    if (ctc_check_shape(who, batch, T, C, blank) || nntk_check_lengths(who, input_lengths, batch, T, NULL, NULL) ||
-        ctc_check_labels(who, batch, C, labels, label_lengths, max_label_len, blank)) return -1;
-    if (batch == 0) return 0;
-    if (!d_loss_rows || !d_workspace || (!d_probs && T > 0)) NNTK_FAIL("nntk_ctc_loss_device: NULL tensor");
-    int *len = ctc_lengths(input_lengths, batch, T);
-    if (!len) return -1;
-    int rc = nntk_shim_ctc_loss(d_probs, batch, T, C, len, labels, label_lengths, max_label_len, blank, d_loss_rows, d_dprobs, d_workspace);
-    free(len);
-    return rc;
-}
-
-int nntk_ctc_greedy_decode_device(const float *d_probs, int batch, int T, int C, const int *input_lengths, int blank,
-                                  int *d_labels_out, int *d_out_lengths) {
-    static const char who[] = "nntk_ctc_greedy_decode_device";
-    nntk_shim_clear_error();
-    if (ctc_check_shape(who, batch, T, C, blank) || nntk_check_lengths(who, input_lengths, batch, T, NULL, NULL)) return -1;
-    if (batch == 0) return 0;
-    if (!d_out_lengths || ((!d_probs || !d_labels_out) && T > 0)) NNTK_FAIL("nntk_ctc_greedy_decode_device: NULL tensor");
-    int *len = ctc_lengths(input_lengths, batch, T);
-    if (!len) return -1;
-    int rc = nntk_shim_ctc_greedy_decode(d_probs, batch, T, C, len, blank, d_labels_out, d_out_lengths);
-    free(len);
-    return rc;
-}
-
-/* host-pointer forms: upload, device call, download */
-int nntk_ctc_loss(const float *probs, int batch, int T, int C, const int *input_lengths, const int *labels, const int *label_lengths,
-                  int max_label_len, int blank, float *loss_rows, float *dprobs) {
-    static const char who[] = "nntk_ctc_loss";
-    nntk_shim_clear_error();
-    if (ctc_check_shape(who, batch, T, C, blank) || nntk_check_lengths(who, input_lengths, batch, T, NULL, NULL) ||
-        ctc_check_labels(who, batch, C, labels, label_lengths, max_label_len, blank)) return -1;
-    if (batch == 0) return 0;
-    if (!loss_rows || (!probs && T > 0)) NNTK_FAIL("nntk_ctc_loss: NULL array");
-    const size_t n = (size_t)batch * T * C;
-    float *d_p = nntk_devbuf_reserve(&t_a, n + (size_t)batch + 4);
-    float *d_g = dprobs ? nntk_devbuf_reserve(&t_b, n + 4) : NULL;
-    float *d_ws = nntk_devbuf_reserve(&t_c, nntk_shim_ctc_workspace_floats(batch, dprobs ? T : 0, max_label_len));
-    if (!d_p || (dprobs && !d_g) || !d_ws) return -1;
-    float *d_loss = d_p + n;
-    if (n && nntk_shim_upload(d_p, probs, n * sizeof(float))) return -1;
-    if (nntk_ctc_loss_device(d_p, batch, T, C, input_lengths, labels, label_lengths, max_label_len, blank, d_loss, d_g, d_ws)) return -1;
-    if (nntk_shim_download(loss_rows, d_loss, (size_t)batch * sizeof(float))) return -1;
-    return dprobs && n ? nntk_shim_download(dprobs, d_g, n * sizeof(float)) : 0;
-}
-
-int nntk_ctc_greedy_decode(const float *probs, int batch, int T, int C, const int *input_lengths, int blank, int *labels_out,
-                           int *out_lengths) {
-    static const char who[] = "nntk_ctc_greedy_decode";
-    nntk_shim_clear_error();
-    if (ctc_check_shape(who, batch, T, C, blank) || nntk_check_lengths(who, input_lengths, batch, T, NULL, NULL)) return -1;
-    if (batch == 0) return 0;
-    if (!out_lengths || ((!probs || !labels_out) && T > 0)) NNTK_FAIL("nntk_ctc_greedy_decode: NULL array");
-    const size_t n = (size_t)batch * T * C, nl = (size_t)batch * T;
-    float *d_p = nntk_devbuf_reserve(&t_a, n + 4);
-    int *d_o = (int *)nntk_devbuf_reserve(&t_b, nl + (size_t)batch + 4);
-    if (!d_p || !d_o) return -1;
-    if (n && nntk_shim_upload(d_p, probs, n * sizeof(float))) return -1;
-    if (nntk_ctc_greedy_decode_device(d_p, batch, T, C, input_lengths, blank, d_o, d_o + nl)) return -1;
-    if (nl && nntk_shim_download(labels_out, d_o, nl * sizeof(int))) return -1;
-    return nntk_shim_download(out_lengths, d_o + nl, (size_t)batch * sizeof(int));
-}
-
-/* ---- CTC prefix beam search (csrc/hip/ctc_beam.hip) ---- */
-#define CTC_BEAM_MAX_W 128
-#define CTC_BEAM_MAX_CELLS 16384
-static int ctc_beam_check(const char *who, int batch, int T, int C, const int *input_lengths, int blank, int beam_width,
-                          int cutoff_top_n, int nbest) {
-    if (ctc_check_shape(who, batch, T, C, blank) || nntk_check_lengths(who, input_lengths, batch, T, NULL, NULL)) return -1;
-    if (beam_width < 1 || beam_width > CTC_BEAM_MAX_W)
-        return ctc_fail(who, "beam_width %d is outside [1, %d]", beam_width, CTC_BEAM_MAX_W, 0);
-    if (nbest < 1 || nbest > beam_width) return ctc_fail(who, "nbest %d is outside [1, beam_width = %d]", nbest, beam_width, 0);
-    if (cutoff_top_n < 0) return ctc_fail(who, "cutoff_top_n %d < 0", cutoff_top_n, 0, 0);
-    const int n = cutoff_top_n == 0 || cutoff_top_n >= C - 1 ? C - 1 : cutoff_top_n;      /* expanded classes per frame */
-    if ((long long)beam_width * (n + 1) > CTC_BEAM_MAX_CELLS)
-        return ctc_fail(who, "beam_width %d x (%d expanded classes + 1) is more than %d candidate cells: lower beam_width or set cutoff_top_n",
-                        beam_width, n, CTC_BEAM_MAX_CELLS);
-    if (T >= (1 << 23)) return ctc_fail(who, "T %d is not below %d frames", T, 1 << 23, 0);
-    return 0;
-}
-
-size_t nntk_ctc_beam_workspace_floats(int batch, int T, int C, int beam_width, int cutoff_top_n) {
-    return nntk_shim_ctc_beam_workspace_floats(batch, T, C, beam_width, cutoff_top_n);
-}
-
-int nntk_ctc_beam_decode_device(const float *d_probs, int batch, int T, int C, const int *input_lengths, int blank, int beam_width,
-                                int cutoff_top_n, int nbest, int *d_labels_out, int *d_out_lengths, float *d_scores,
-                                float *d_workspace) {
-    static const char who[] = "nntk_ctc_beam_decode_device";
-    nntk_shim_clear_error();
-    if (ctc_beam_check(who, batch, T, C, input_lengths, blank, beam_width, cutoff_top_n, nbest)) return -1;
-    if (batch == 0) return 0;
-    if (!d_out_lengths || !d_scores || !d_workspace || ((!d_probs || !d_labels_out) && T > 0))
-        NNTK_FAIL("nntk_ctc_beam_decode_device: NULL tensor");
-    int *len = ctc_lengths(input_lengths, batch, T);
-    if (!len) return -1;
-    int rc = nntk_shim_ctc_beam_decode(d_probs, batch, T, C, len, blank, beam_width, cutoff_top_n, nbest, d_labels_out, d_out_lengths,
-                                       d_scores, d_workspace);
-    free(len);
-    return rc;
-}
-
-int nntk_ctc_beam_decode(const float *probs, int batch, int T, int C, const int *input_lengths, int blank, int beam_width,
-                         int cutoff_top_n, int nbest, int *labels_out, int *out_lengths, float *scores) {
-    static const char who[] = "nntk_ctc_beam_decode";
-    nntk_shim_clear_error();
-    if (ctc_beam_check(who, batch, T, C, input_lengths, blank, beam_width, cutoff_top_n, nbest)) return -1;
-    if (batch == 0) return 0;
-    if (!out_lengths || !scores || ((!probs || !labels_out) && T > 0)) NNTK_FAIL("nntk_ctc_beam_decode: NULL array");
-    const size_t n = (size_t)batch * T * C, nh = (size_t)batch * nbest, nl = nh * T;
-    float *d_p = nntk_devbuf_reserve(&t_a, n + 4);
-    int *d_o = (int *)nntk_devbuf_reserve(&t_b, nl + 2 * nh + 4);             /* labels | lengths | scores */
-    float *d_ws = nntk_devbuf_reserve(&t_c, nntk_shim_ctc_beam_workspace_floats(batch, T, C, beam_width, cutoff_top_n));
-    if (!d_p || !d_o || !d_ws) return -1;
-    if (n && nntk_shim_upload(d_p, probs, n * sizeof(float))) return -1;
-    if (nntk_ctc_beam_decode_device(d_p, batch, T, C, input_lengths, blank, beam_width, cutoff_top_n, nbest, d_o, d_o + nl,
-                                    (float *)(d_o + nl + nh), d_ws)) return -1;
-    if (nl && nntk_shim_download(labels_out, d_o, nl * sizeof(int))) return -1;
-    if (nntk_shim_download(out_lengths, d_o + nl, nh * sizeof(int))) return -1;
-    return nntk_shim_download(scores, d_o + nl + nh, nh * sizeof(float));
-}
-
-/* ---- language-model fusion (INTEGRATION.md "CTC prefix beam search", Language-model fusion): the calls above with an n-gram handle
- *      (ngram_lm.c); lm NULL: the calls above themselves ---- */
-size_t nntk_ctc_beam_lm_workspace_floats(int batch, int T, int C, int beam_width, int cutoff_top_n) {
-    return nntk_shim_ctc_beam_lm_workspace_floats(batch, T, C, beam_width, cutoff_top_n);
-}
-
-static int ctc_beam_lm_check(const char *who, NntkNgramLm lm, int C, int blank) {
-    if (lm && !nntk_ngram_lm_matches(lm, C, blank))
-        return ctc_fail(who, "the language model was built for another class count or blank than C = %d, blank = %d", C, blank, 0);
-    return 0;
-}
-
-int nntk_ctc_beam_decode_lm_device(const float *d_probs, int batch, int T, int C, const int *input_lengths, int blank, int beam_width,
-                                   int cutoff_top_n, int nbest, NntkNgramLm lm, int *d_labels_out, int *d_out_lengths, float *d_scores,
-                                   float *d_workspace) {
-    static const char who[] = "nntk_ctc_beam_decode_lm_device";
-    if (!lm)
-        return nntk_ctc_beam_decode_device(d_probs, batch, T, C, input_lengths, blank, beam_width, cutoff_top_n, nbest, d_labels_out,
-                                           d_out_lengths, d_scores, d_workspace);
-    nntk_shim_clear_error();
-    if (ctc_beam_check(who, batch, T, C, input_lengths, blank, beam_width, cutoff_top_n, nbest) || ctc_beam_lm_check(who, lm, C, blank))
-        return -1;
-    if (batch == 0) return 0;
-    if (!d_out_lengths || !d_scores || !d_workspace || ((!d_probs || !d_labels_out) && T > 0))
-        NNTK_FAIL("nntk_ctc_beam_decode_lm_device: NULL tensor");
-    nntk_shim_lm tab;
-    if (nntk_ngram_lm_device(lm, &tab)) return -1;
-    int *len = ctc_lengths(input_lengths, batch, T);
-    if (!len) return -1;
-    int rc = nntk_shim_ctc_beam_decode_lm(d_probs, batch, T, C, len, blank, beam_width, cutoff_top_n, nbest, &tab, d_labels_out,
-                                          d_out_lengths, d_scores, d_workspace);
-    free(len);
-    return rc;
-}
-
-int nntk_ctc_beam_decode_lm(const float *probs, int batch, int T, int C, const int *input_lengths, int blank, int beam_width,
-                            int cutoff_top_n, int nbest, NntkNgramLm lm, int *labels_out, int *out_lengths, float *scores) {
-    static const char who[] = "nntk_ctc_beam_decode_lm";
-    nntk_shim_clear_error();
-    if (ctc_beam_check(who, batch, T, C, input_lengths, blank, beam_width, cutoff_top_n, nbest) || ctc_beam_lm_check(who, lm, C, blank))
-        return -1;
-    if (batch == 0) return 0;
-    if (!out_lengths || !scores || ((!probs || !labels_out) && T > 0)) NNTK_FAIL("nntk_ctc_beam_decode_lm: NULL array");
-    const size_t n = (size_t)batch * T * C, nh = (size_t)batch * nbest, nl = nh * T;
-    float *d_p = nntk_devbuf_reserve(&t_a, n + 4);
-    int *d_o = (int *)nntk_devbuf_reserve(&t_b, nl + 2 * nh + 4);             /* labels | lengths | scores */
-    float *d_ws = nntk_devbuf_reserve(&t_c, nntk_shim_ctc_beam_lm_workspace_floats(batch, T, C, beam_width, cutoff_top_n));
-    if (!d_p || !d_o || !d_ws) return -1;
-    if (n && nntk_shim_upload(d_p, probs, n * sizeof(float))) return -1;
-    if (nntk_ctc_beam_decode_lm_device(d_p, batch, T, C, input_lengths, blank, beam_width, cutoff_top_n, nbest, lm, d_o, d_o + nl,
-                                       (float *)(d_o + nl + nh), d_ws)) return -1;
-    if (nl && nntk_shim_download(labels_out, d_o, nl * sizeof(int))) return -1;
-    if (nntk_shim_download(out_lengths, d_o + nl, nh * sizeof(int))) return -1;
-    return nntk_shim_download(scores, d_o + nl + nh, nh * sizeof(float));
-}
-
-/* ---- streaming CTC decoding (INTEGRATION.md "CTC prefix beam search", Streaming).  The beam lives in the handle's device buffer; which
- *      rows are new, how many frames each has seen and which half of its label strings is current is host bookkeeping, uploaded with
- *      every push: a reset touches no device memory ---- */
-#define CTC_BEAM_MAX_T ((1 << 23) - 1)
-struct NntkCtcBeamStreamStruct {
-    int batch, max_frames, C, blank, beam_width, cutoff_top_n, nbest, max_labels;
-    int *frames;                    /* [batch] frames since the row's reset */
-    int *half;                      /* [batch] the current half of the row's label strings */
-    int *ctl;                       /* [4][batch] staging of one push */
-    NntkNgramLm lm;                 /* NULL: acoustic scores only.  Not owned: it outlives the stream */
-    nntk_devbuf d_buf;              /* nntk_shim_ctc_beam_stream_floats words, reserved by the first push */
-    nntk_devbuf d_io;               /* the host-pointer push: probabilities | labels | lengths | scores */
-};
-
-size_t nntk_ctc_beam_stream_state_bytes(int batch, int max_frames, int C, int beam_width, int cutoff_top_n, int max_labels) {
-    return sizeof(float) * nntk_shim_ctc_beam_stream_floats(batch, max_frames, C, beam_width, cutoff_top_n, max_labels);
-}
-
-size_t nntk_ctc_beam_stream_state_bytes_lm(int batch, int max_frames, int C, int beam_width, int cutoff_top_n, int max_labels) {
-    return sizeof(float) * nntk_shim_ctc_beam_stream_lm_floats(batch, max_frames, C, beam_width, cutoff_top_n, max_labels);
-}
-
-NntkCtcBeamStream nntk_ctc_beam_stream_create(int batch, int max_frames, int C, int blank, int beam_width, int cutoff_top_n, int nbest,
-                                              int max_labels) {
-    return nntk_ctc_beam_stream_create_lm(batch, max_frames, C, blank, beam_width, cutoff_top_n, nbest, max_labels, NULL);
-}
-
-NntkCtcBeamStream nntk_ctc_beam_stream_create_lm(int batch, int max_frames, int C, int blank, int beam_width, int cutoff_top_n, int nbest,
-                                                 int max_labels, NntkNgramLm lm) {
-    static const char who[] = "nntk_ctc_beam_stream_create";
-    nntk_shim_clear_error();
-    if (ctc_beam_check(who, batch, 0, C, NULL, blank, beam_width, cutoff_top_n, nbest)) return NULL;
-    if (max_frames < 1) { ctc_fail(who, "max_frames %d < 1", max_frames, 0, 0); return NULL; }
-    if (max_labels < 1) { ctc_fail(who, "max_labels %d < 1", max_labels, 0, 0); return NULL; }
-    if (ctc_beam_lm_check(who, lm, C, blank)) return NULL;
-    if (lm ? nntk_shim_ctc_beam_stream_check_lm(C, beam_width, cutoff_top_n) : nntk_shim_ctc_beam_stream_check(C, beam_width, cutoff_top_n))
-        return NULL;
-    NntkCtcBeamStream s = (NntkCtcBeamStream)calloc(1, sizeof *s);
-    const size_t rows = (size_t)(batch > 0 ? batch : 1);
-    if (s) {
-        s->frames = (int *)calloc(rows, sizeof(int));
-        s->half = (int *)calloc(rows, sizeof(int));
-        s->ctl = (int *)calloc(4 * rows, sizeof(int));
-    }
-    if (!s || !s->frames || !s->half || !s->ctl) {
-        nntk_ctc_beam_stream_destroy(s);
-        nntk_set_error("out of host memory");
-        return NULL;
-    }
-    s->batch = batch; s->max_frames = max_frames; s->C = C; s->blank = blank;
-    s->beam_width = beam_width; s->cutoff_top_n = cutoff_top_n; s->nbest = nbest; s->max_labels = max_labels;
-    s->lm = lm;
-    return s;
-}
-
-void nntk_ctc_beam_stream_destroy(NntkCtcBeamStream s) {
-    if (!s) return;
-    nntk_devbuf_free(&s->d_buf);
-    nntk_devbuf_free(&s->d_io);
-    free(s->frames);
-    free(s->half);
-    free(s->ctl);
-    free(s);
-}
-
-int nntk_ctc_beam_stream_reset(NntkCtcBeamStream s, const int *rows, int n_rows) {
-    static const char who[] = "nntk_ctc_beam_stream_reset";
-    nntk_shim_clear_error();
-    if (!s) NNTK_FAIL("nntk_ctc_beam_stream_reset: NULL handle");
-    if (n_rows < 0) return ctc_fail(who, "n_rows %d < 0", n_rows, 0, 0);
-    if (n_rows > 0 && !rows) NNTK_FAIL("nntk_ctc_beam_stream_reset: NULL rows");
-    for (int i = 0; i < n_rows; ++i)
-        if (rows[i] < 0 || rows[i] >= s->batch) return ctc_fail(who, "rows[%d] = %d is outside [0, %d)", i, rows[i], s->batch);
-    for (int i = 0; i < n_rows; ++i) s->frames[rows[i]] = 0;        /* the next push starts the row from the empty prefix */
-    return 0;
-}
-
-/* every check of a push; nothing is enqueued and nothing in the handle changes */
-static int beam_stream_check_push(const char *who, NntkCtcBeamStream s, const void *probs, const int *n_frames, const void *labels,
-                                  const void *lengths, const void *scores) {
-    if (!n_frames || !probs || !labels || !lengths || !scores) return ctc_fail(who, "NULL argument", 0, 0, 0);
-    for (int b = 0; b < s->batch; ++b) {
-        if (n_frames[b] < 0 || n_frames[b] > s->max_frames)
-            return ctc_fail(who, "n_frames[%d] = %d is outside [0, max_frames = %d]", b, n_frames[b], s->max_frames);
-        if (n_frames[b] > CTC_BEAM_MAX_T - s->frames[b])
-            return ctc_fail(who, "row %d would pass %d frames since its reset", b, CTC_BEAM_MAX_T, 0);
-    }
-    return 0;
-}
-
-int nntk_ctc_beam_stream_push_device(NntkCtcBeamStream s, const float *d_probs, const int *n_frames, const int *final,
-                                     int *d_labels_out, int *d_out_lengths, float *d_scores) {
-    static const char who[] = "nntk_ctc_beam_stream_push_device";
-    nntk_shim_clear_error();
-    if (!s) NNTK_FAIL("nntk_ctc_beam_stream_push_device: NULL handle");
-    if (s->batch == 0) return 0;
-    if (beam_stream_check_push(who, s, d_probs, n_frames, d_labels_out, d_out_lengths, d_scores)) return -1;
-    const int B = s->batch;
-    nntk_shim_lm tab;
-    if (s->lm && nntk_ngram_lm_device(s->lm, &tab)) return -1;
-    float *d_buf = nntk_devbuf_reserve(&s->d_buf, (s->lm ? nntk_shim_ctc_beam_stream_lm_floats : nntk_shim_ctc_beam_stream_floats)(
-                                                      B, s->max_frames, s->C, s->beam_width, s->cutoff_top_n, s->max_labels));
-    if (!d_buf) return -1;
-    int any = 0;
-    for (int b = 0; b < B; ++b) {
-        s->ctl[b] = n_frames[b];
-        s->ctl[B + b] = s->frames[b];
-        s->ctl[2 * B + b] = s->half[b];
-        s->ctl[3 * B + b] = 0;
-        any |= n_frames[b] > 0;
-    }
-    if (s->lm ? nntk_shim_ctc_beam_stream_push_lm(d_probs, B, s->max_frames, s->C, s->ctl, any, s->blank, s->beam_width, s->cutoff_top_n,
-                                                  s->nbest, s->max_labels, &tab, d_labels_out, d_out_lengths, d_scores, d_buf)
-              : nntk_shim_ctc_beam_stream_push(d_probs, B, s->max_frames, s->C, s->ctl, any, s->blank, s->beam_width, s->cutoff_top_n,
-                                               s->nbest, s->max_labels, d_labels_out, d_out_lengths, d_scores, d_buf)) return -1;
-    for (int b = 0; b < B; ++b) {
-        if (n_frames[b] > 0) { s->frames[b] += n_frames[b]; s->half[b] ^= 1; }
-        if (final && final[b]) s->frames[b] = 0;
-    }
-    return 0;
-}
-
-int nntk_ctc_beam_stream_push(NntkCtcBeamStream s, const float *probs, const int *n_frames, const int *final, int *labels_out,
-                              int *out_lengths, float *scores) {
-    static const char who[] = "nntk_ctc_beam_stream_push";
-    nntk_shim_clear_error();
-    if (!s) NNTK_FAIL("nntk_ctc_beam_stream_push: NULL handle");
-    if (s->batch == 0) return 0;
-    if (beam_stream_check_push(who, s, probs, n_frames, labels_out, out_lengths, scores)) return -1;
-    const size_t n = (size_t)s->batch * s->max_frames * s->C, nh = (size_t)s->batch * s->nbest, nl = nh * s->max_labels;
-    float *d_p = nntk_devbuf_reserve(&s->d_io, n + nl + 2 * nh + 4);
-    if (!d_p) return -1;
-    int *d_o = (int *)(d_p + n);
-    if (nntk_shim_upload(d_p, probs, n * sizeof(float))) return -1;
-    if (nntk_ctc_beam_stream_push_device(s, d_p, n_frames, final, d_o, d_o + nl, (float *)(d_o + nl + nh))) return -1;
-    if (nntk_shim_download(labels_out, d_o, nl * sizeof(int))) return -1;
-    if (nntk_shim_download(out_lengths, d_o + nl, nh * sizeof(int))) return -1;
-    return nntk_shim_download(scores, d_o + nl + nh, nh * sizeof(float));
-}
-
-int nntk_ctc_greedy_decode_stream_device(const float *d_probs, int batch, int T, int C, const int *n_frames, int blank, int *d_prev,
-                                         int *d_labels_out, int *d_out_lengths) {
-    static const char who[] = "nntk_ctc_greedy_decode_stream_device";
-    nntk_shim_clear_error();
-    if (ctc_check_shape(who, batch, T, C, blank)) return -1;
-    if (batch > 0 && !n_frames) NNTK_FAIL("nntk_ctc_greedy_decode_stream_device: NULL n_frames");
-    if (nntk_check_lengths(who, n_frames, batch, T, NULL, NULL)) return -1;
-    if (batch == 0) return 0;
-    if (!d_prev || !d_out_lengths || ((!d_probs || !d_labels_out) && T > 0)) NNTK_FAIL("nntk_ctc_greedy_decode_stream_device: NULL tensor");
-    return nntk_shim_ctc_greedy_decode_stream(d_probs, batch, T, C, n_frames, blank, d_prev, d_labels_out, d_out_lengths);
-}
-
-/* ---- CTC forced alignment (csrc/hip/ctc_align.hip) ---- */
-#define CTC_ALIGN_MAX_LABELS 4000
-static int ctc_align_check(const char *who, int batch, int T, int C, const int *input_lengths, const int *labels, const int *label_lengths,
-                           int max_label_len, int blank) {
-    if (ctc_check_shape(who, batch, T, C, blank) || nntk_check_lengths(who, input_lengths, batch, T, NULL, NULL)) return -1;
-    if (max_label_len > CTC_ALIGN_MAX_LABELS)
-        return ctc_fail(who, "max_label_len %d is more than %d (the extended states of a row live in one workgroup's LDS)", max_label_len,
-                        CTC_ALIGN_MAX_LABELS, 0);
-    return ctc_check_labels(who, batch, C, labels, label_lengths, max_label_len, blank);
-}
-
-size_t nntk_ctc_align_workspace_floats(int batch, int T, int max_label_len) {
-    return nntk_shim_ctc_align_workspace_floats(batch, T, max_label_len);
-}
-
-int nntk_ctc_align_device(const float *d_probs, int batch, int T, int C, const int *input_lengths, const int *labels,
-                          const int *label_lengths, int max_label_len, int blank, int *d_states, int *d_spans, float *d_scores,
-                          float *d_workspace) {
-    static const char who[] = "nntk_ctc_align_device";
-    nntk_shim_clear_error();
-    if (ctc_align_check(who, batch, T, C, input_lengths, labels, label_lengths, max_label_len, blank)) return -1;
-    if (batch == 0) return 0;
-    if (!d_scores || !d_workspace || (!d_probs && T > 0)) NNTK_FAIL("nntk_ctc_align_device: NULL tensor");
-    int *len = ctc_lengths(input_lengths, batch, T);
-    if (!len) return -1;
-    int rc = nntk_shim_ctc_align(d_probs, batch, T, C, len, labels, label_lengths, max_label_len, blank, d_states, d_spans, d_scores,
-                                 d_workspace);
-    free(len);
-    return rc;
-}
-
-int nntk_ctc_align(const float *probs, int batch, int T, int C, const int *input_lengths, const int *labels, const int *label_lengths,
-                   int max_label_len, int blank, int *states, int *spans, float *scores) {
-    static const char who[] = "nntk_ctc_align";
-    nntk_shim_clear_error();
-    if (ctc_align_check(who, batch, T, C, input_lengths, labels, label_lengths, max_label_len, blank)) return -1;
-    if (batch == 0) return 0;
-    if (!scores || (!probs && T > 0)) NNTK_FAIL("nntk_ctc_align: NULL array");
-    const size_t n = (size_t)batch * T * C, ns = states ? (size_t)batch * T : 0, np = spans ? 2 * (size_t)batch * max_label_len : 0;
-    float *d_p = nntk_devbuf_reserve(&t_a, n + 4);
-    int *d_o = (int *)nntk_devbuf_reserve(&t_b, ns + np + (size_t)batch + 4);           /* states | spans | scores */
-    float *d_ws = nntk_devbuf_reserve(&t_c, nntk_shim_ctc_align_workspace_floats(batch, T, max_label_len));
-    if (!d_p || !d_o || !d_ws) return -1;
-    if (n && nntk_shim_upload(d_p, probs, n * sizeof(float))) return -1;
-    if (nntk_ctc_align_device(d_p, batch, T, C, input_lengths, labels, label_lengths, max_label_len, blank, ns ? d_o : NULL,
-                              np ? d_o + ns : NULL, (float *)(d_o + ns + np), d_ws)) return -1;
-    if (ns && nntk_shim_download(states, d_o, ns * sizeof(int))) return -1;
-    if (np && nntk_shim_download(spans, d_o + ns, np * sizeof(int))) return -1;
-    return nntk_shim_download(scores, d_o + ns + np, (size_t)batch * sizeof(float));
-}
-
 /* ---- SGD (train/optimizers.c:13-19) ---- */
 int nntk_sgd_optimize_device(SGD optimizer, const float *d_gradient, float *d_weights, long size) {
     nntk_shim_clear_error();

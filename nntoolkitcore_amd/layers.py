@@ -641,40 +641,58 @@ def ctc_greedy_decode(probs, input_lengths=None, blank=0):
     return out, n
 
 
-def ctc_beam_decode_device(probs, input_lengths=None, blank=0, beam_width=16, cutoff_top_n=0, nbest=1, labels_out=None, out_lengths=None,
-                           scores=None, workspace=None):
-    """``nntk_ctc_beam_decode_device``: prefix beam search over probs [B,T,C] -> (labels [B,nbest,T] int32, -1 behind each hypothesis'
-    labels; lengths [B,nbest] int32, -1 for a slot without a hypothesis; scores [B,nbest] float32 = ln of the prefix probability)"""
+def _beam_outputs(device, B, nbest, L, labels_out, out_lengths, scores):
+    """the caller's output tensors of a beam search, or new ones: labels [B, nbest, L] int32, lengths [B, nbest] int32, scores float32"""
+    import torch
+    if labels_out is None:
+        labels_out = torch.empty((B, nbest, L), dtype=torch.int32, device=device)
+    if out_lengths is None:
+        out_lengths = torch.empty((B, nbest), dtype=torch.int32, device=device)
+    if scores is None:
+        scores = torch.empty((B, nbest), dtype=torch.float32, device=device)
+    return labels_out, out_lengths, scores
+
+
+def _beam_decode_device(entry, ws_name, lm_arg, probs, input_lengths, blank, beam_width, cutoff_top_n, nbest, labels_out, out_lengths, scores,
+                        workspace):
+    """the one-shot search on device tensors through the C entry ``entry``; lm_arg: () for the acoustic entries, else (model handle or None,)"""
     import torch
     B, T, Cc = probs.shape
     il, ilp = _ctc_lengths(input_lengths, B)
     L = capi.load()
-    need = L.nntk_ctc_beam_workspace_floats(B, T, Cc, beam_width, cutoff_top_n)
+    need = getattr(L, ws_name)(B, T, Cc, beam_width, cutoff_top_n)
     if workspace is None:
         workspace = torch.empty(need, dtype=torch.float32, device=probs.device)
-    assert workspace.numel() >= need, "workspace: nntk_ctc_beam_workspace_floats(B, T, C, beam_width, cutoff_top_n) floats"
-    if labels_out is None:
-        labels_out = torch.empty((B, max(nbest, 0), T), dtype=torch.int32, device=probs.device)
-    if out_lengths is None:
-        out_lengths = torch.empty((B, max(nbest, 0)), dtype=torch.int32, device=probs.device)
-    if scores is None:
-        scores = torch.empty((B, max(nbest, 0)), dtype=torch.float32, device=probs.device)
-    check(L.nntk_ctc_beam_decode_device(_dp(probs), B, T, Cc, ilp, blank, beam_width, cutoff_top_n, nbest,
-                                        C.c_void_p(labels_out.data_ptr()), C.c_void_p(out_lengths.data_ptr()), _dp(scores),
-                                        _dp(workspace)), "nntk_ctc_beam_decode_device")
+    assert workspace.numel() >= need, "workspace: %s(B, T, C, beam_width, cutoff_top_n) floats" % ws_name
+    labels_out, out_lengths, scores = _beam_outputs(probs.device, B, max(nbest, 0), T, labels_out, out_lengths, scores)
+    check(getattr(L, entry)(_dp(probs), B, T, Cc, ilp, blank, beam_width, cutoff_top_n, nbest, *lm_arg, C.c_void_p(labels_out.data_ptr()),
+                            C.c_void_p(out_lengths.data_ptr()), _dp(scores), _dp(workspace)), entry)
     return labels_out, out_lengths, scores
 
 
-def ctc_beam_decode(probs, input_lengths=None, blank=0, beam_width=16, cutoff_top_n=0, nbest=1):
-    """The host-memory form (``nntk_ctc_beam_decode``): probs [B,T,C] numpy array."""
+def _beam_decode_host(entry, lm_arg, probs, input_lengths, blank, beam_width, cutoff_top_n, nbest):
+    """the host-memory form of the same; lm_arg as above"""
     probs = _f32(probs)
     B, T, Cc = probs.shape
     il, ilp = _ctc_lengths(input_lengths, B)
     nb = max(nbest, 0)
     out, n, sc = np.empty((B, nb, T), np.int32), np.empty((B, nb), np.int32), np.empty((B, nb), np.float32)
-    check(capi.load().nntk_ctc_beam_decode(_p(probs), B, T, Cc, ilp, blank, beam_width, cutoff_top_n, nbest, out.ctypes.data_as(capi.ip),
-                                           n.ctypes.data_as(capi.ip), _p(sc)), "nntk_ctc_beam_decode")
+    check(getattr(capi.load(), entry)(_p(probs), B, T, Cc, ilp, blank, beam_width, cutoff_top_n, nbest, *lm_arg, out.ctypes.data_as(capi.ip),
+                                      n.ctypes.data_as(capi.ip), _p(sc)), entry)
     return out, n, sc
+
+
+def ctc_beam_decode_device(probs, input_lengths=None, blank=0, beam_width=16, cutoff_top_n=0, nbest=1, labels_out=None, out_lengths=None,
+                           scores=None, workspace=None):
+    """``nntk_ctc_beam_decode_device``: prefix beam search over probs [B,T,C] -> (labels [B,nbest,T] int32, -1 behind each hypothesis'
+    labels; lengths [B,nbest] int32, -1 for a slot without a hypothesis; scores [B,nbest] float32 = ln of the prefix probability)"""
+    return _beam_decode_device("nntk_ctc_beam_decode_device", "nntk_ctc_beam_workspace_floats", (), probs, input_lengths, blank, beam_width,
+                               cutoff_top_n, nbest, labels_out, out_lengths, scores, workspace)
+
+
+def ctc_beam_decode(probs, input_lengths=None, blank=0, beam_width=16, cutoff_top_n=0, nbest=1):
+    """The host-memory form (``nntk_ctc_beam_decode``): probs [B,T,C] numpy array."""
+    return _beam_decode_host("nntk_ctc_beam_decode", (), probs, input_lengths, blank, beam_width, cutoff_top_n, nbest)
 
 
 class NgramLm:
@@ -794,36 +812,13 @@ def ctc_beam_decode_lm_device(probs, lm, input_lengths=None, blank=0, beam_width
                               out_lengths=None, scores=None, workspace=None):
     """``nntk_ctc_beam_decode_lm_device``: ``ctc_beam_decode_device`` with the n-gram model ``lm`` (an NgramLm, or None) fused in;
     scores = ln(acoustic prefix probability x LM factors x end-of-sentence factor)"""
-    import torch
-    B, T, Cc = probs.shape
-    il, ilp = _ctc_lengths(input_lengths, B)
-    L = capi.load()
-    need = L.nntk_ctc_beam_lm_workspace_floats(B, T, Cc, beam_width, cutoff_top_n)
-    if workspace is None:
-        workspace = torch.empty(need, dtype=torch.float32, device=probs.device)
-    assert workspace.numel() >= need, "workspace: nntk_ctc_beam_lm_workspace_floats(B, T, C, beam_width, cutoff_top_n) floats"
-    if labels_out is None:
-        labels_out = torch.empty((B, max(nbest, 0), T), dtype=torch.int32, device=probs.device)
-    if out_lengths is None:
-        out_lengths = torch.empty((B, max(nbest, 0)), dtype=torch.int32, device=probs.device)
-    if scores is None:
-        scores = torch.empty((B, max(nbest, 0)), dtype=torch.float32, device=probs.device)
-    check(L.nntk_ctc_beam_decode_lm_device(_dp(probs), B, T, Cc, ilp, blank, beam_width, cutoff_top_n, nbest, lm.h if lm else None,
-                                           C.c_void_p(labels_out.data_ptr()), C.c_void_p(out_lengths.data_ptr()), _dp(scores),
-                                           _dp(workspace)), "nntk_ctc_beam_decode_lm_device")
-    return labels_out, out_lengths, scores
+    return _beam_decode_device("nntk_ctc_beam_decode_lm_device", "nntk_ctc_beam_lm_workspace_floats", (lm.h if lm else None,), probs,
+                               input_lengths, blank, beam_width, cutoff_top_n, nbest, labels_out, out_lengths, scores, workspace)
 
 
 def ctc_beam_decode_lm(probs, lm, input_lengths=None, blank=0, beam_width=16, cutoff_top_n=0, nbest=1):
     """The host-memory form (``nntk_ctc_beam_decode_lm``): probs [B,T,C] numpy array."""
-    probs = _f32(probs)
-    B, T, Cc = probs.shape
-    il, ilp = _ctc_lengths(input_lengths, B)
-    nb = max(nbest, 0)
-    out, n, sc = np.empty((B, nb, T), np.int32), np.empty((B, nb), np.int32), np.empty((B, nb), np.float32)
-    check(capi.load().nntk_ctc_beam_decode_lm(_p(probs), B, T, Cc, ilp, blank, beam_width, cutoff_top_n, nbest, lm.h if lm else None,
-                                              out.ctypes.data_as(capi.ip), n.ctypes.data_as(capi.ip), _p(sc)), "nntk_ctc_beam_decode_lm")
-    return out, n, sc
+    return _beam_decode_host("nntk_ctc_beam_decode_lm", (lm.h if lm else None,), probs, input_lengths, blank, beam_width, cutoff_top_n, nbest)
 
 
 class CtcBeamStream:
@@ -853,16 +848,10 @@ class CtcBeamStream:
     def push(self, probs, n_frames, final=None, labels_out=None, out_lengths=None, scores=None):
         """probs [B, max_frames, C] device tensor, n_frames / final host ints per row (a streaming stack's out, cnt, final) ->
         (labels [B, nbest, max_labels] int32, lengths [B, nbest] int32, scores [B, nbest] float32), the rows' current n-best"""
-        import torch
         assert tuple(probs.shape) == (self.B, self.T, self.C), "probs: [batch, max_frames, C]"
         nf = _host_ints(n_frames, self.B, "n_frames")
         f, fptr = self._final(final)
-        if labels_out is None:
-            labels_out = torch.empty((self.B, self.nbest, self.max_labels), dtype=torch.int32, device=probs.device)
-        if out_lengths is None:
-            out_lengths = torch.empty((self.B, self.nbest), dtype=torch.int32, device=probs.device)
-        if scores is None:
-            scores = torch.empty((self.B, self.nbest), dtype=torch.float32, device=probs.device)
+        labels_out, out_lengths, scores = _beam_outputs(probs.device, self.B, self.nbest, self.max_labels, labels_out, out_lengths, scores)
         check(capi.load().nntk_ctc_beam_stream_push_device(self.h, _dp(probs), nf.ctypes.data_as(capi.ip), fptr,
                                                            C.c_void_p(labels_out.data_ptr()), C.c_void_p(out_lengths.data_ptr()),
                                                            _dp(scores)), "nntk_ctc_beam_stream_push_device")

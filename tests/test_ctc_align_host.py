@@ -1,4 +1,4 @@
-"""CTC forced alignment: what the host layer decides before any device is touched (csrc/host/train.c) -- the workspace size and the
+"""CTC forced alignment: what the host layer decides before any device is touched (csrc/host/ctc.c) -- the workspace size and the
 argument checks of the host-pointer form.  No GPU."""
 import numpy as np
 import pytest

@@ -1,4 +1,4 @@
-"""CTC prefix beam search: what the host layer decides before any device is touched (csrc/host/train.c) -- the workspace size and
+"""CTC prefix beam search: what the host layer decides before any device is touched (csrc/host/ctc.c) -- the workspace size and
 the argument checks of the host-pointer form.  No GPU."""
 import numpy as np
 import pytest

@@ -1,4 +1,4 @@
-"""The host side of the CTC calls (csrc/host/train.c): the workspace size and the argument checks of the host-pointer forms, which
+"""The host side of the CTC calls (csrc/host/ctc.c): the workspace size and the argument checks of the host-pointer forms, which
 run before anything is allocated, uploaded or enqueued.  No GPU."""
 import numpy as np
 

@@ -1,4 +1,4 @@
-"""Streaming CTC decoding: what the host layer decides before any device is touched (csrc/host/train.c) -- the checks of
+"""Streaming CTC decoding: what the host layer decides before any device is touched (csrc/host/ctc.c) -- the checks of
 nntk_ctc_beam_stream_create, the size of a handle's device memory, the empty batch, the exported symbols.  No GPU."""
 import ctypes as C
 

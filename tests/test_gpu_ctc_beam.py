@@ -1,7 +1,7 @@
 """CTC prefix beam search (csrc/hip/ctc_beam.hip) against a float64 restatement of its semantics, and against the CTC loss.
 
-Reference: ``_ref_row`` below -- dicts of label tuples, linear space, float64 (which holds these sizes without scaling), the same
-candidate cells, merge order and canonical-index tie rule as INTEGRATION.md "CTC prefix beam search".
+Reference: ``ref_row`` of ctc_reference.py -- dicts of label tuples, linear space, float64 (which holds these sizes without scaling),
+the same candidate cells, merge order and canonical-index tie rule as INTEGRATION.md "CTC prefix beam search".
 
 Premise of every parity case, asserted in float64 on the reference: at every frame the relative gap between the W-th and the (W+1)-th
 candidate total, and after the last frame between adjacent hypotheses up to the one behind the last reported, is at least
@@ -16,79 +16,15 @@ import numpy as np
 import pytest
 import torch
 
+from ctc_reference import decode as _run, ref_row as _ref_row, reference, softmax as _softmax, tol as _tol
 from nntoolkitcore_amd import capi, layers as NL
 
 pytestmark = pytest.mark.gpu
 
 
-def _softmax(seed, B, T, Cc):
-    rng = np.random.default_rng(seed)
-    z = 2.0 * rng.standard_normal((B, T, Cc))
-    e = np.exp(z - z.max(-1, keepdims=True))
-    return (e / e.sum(-1, keepdims=True)).astype(np.float32)
-
-
-def _ref_row(p, blank, W, cutoff):
-    """p [T][C] float64, the row's valid frames -> (beam in rank order as (labels, p_b, p_nb), smallest relative W / W+1 gap)"""
-    T, Cc = p.shape
-    beam = [((), 1.0, 0.0)]
-    gap = np.inf
-    nonblank = [c for c in range(Cc) if c != blank]
-    for t in range(T):
-        pt = p[t]
-        if cutoff == 0 or cutoff >= Cc - 1:
-            E = nonblank
-        else:
-            E = sorted(sorted(nonblank, key=lambda c: (-pt[c], c))[:cutoff])
-        stays, cand = {}, {}
-        for i, (l, pb, pnb) in enumerate(beam):
-            stays[l] = (i * (Cc + 1), (pb + pnb) * pt[blank], pnb * pt[l[-1]] if l else 0.0)
-        for i, (l, pb, pnb) in enumerate(beam):
-            for c in E:
-                v = pb * pt[c] if (l and c == l[-1]) else (pb + pnb) * pt[c]
-                lc = l + (c,)
-                if lc in stays:
-                    _, sb, snb = stays.pop(lc)
-                    cand[lc] = (i * (Cc + 1) + 1 + c, sb, snb + v)
-                else:
-                    cand[lc] = (i * (Cc + 1) + 1 + c, 0.0, v)
-        for l, v in stays.items():
-            cand[l] = v
-        items = sorted(((-(sb + snb), idx, l, sb, snb) for l, (idx, sb, snb) in cand.items() if sb + snb != 0.0))
-        if len(items) > W:
-            a, b = -items[W - 1][0], -items[W][0]
-            gap = min(gap, (a - b) / a)
-        beam = [(l, sb, snb) for _, _, l, sb, snb in items[:W]]
-    return beam, gap
-
-
 def _reference(p, lens, blank, W, cutoff, nbest):
-    """-> labels [B][nbest][T], lengths, float64 scores, the smallest gap of the premise"""
-    B, T, _ = p.shape
-    lab, n, sc = np.full((B, nbest, T), -1, np.int32), np.full((B, nbest), -1, np.int32), np.full((B, nbest), -np.inf)
-    gap = np.inf
-    for b in range(B):
-        beam, g = _ref_row(p[b, :lens[b]].astype(np.float64), blank, W, cutoff)
-        gap = min(gap, g)
-        tot = [pb + pnb for _, pb, pnb in beam]
-        for k in range(min(nbest, len(beam))):
-            l = beam[k][0]
-            lab[b, k, :len(l)] = l
-            n[b, k] = len(l)
-            sc[b, k] = np.log(tot[k])
-            if k + 1 < len(beam):
-                gap = min(gap, (tot[k] - tot[k + 1]) / tot[k])
-    return lab, n, sc, gap
-
-
-def _tol(T, ref):
-    return 8 * T * 2.0 ** -24 + 4 * np.spacing(np.abs(ref).astype(np.float32)).astype(np.float64)
-
-
-def _run(gpu, p, lens, blank, W, cutoff, nbest):
-    out = NL.ctc_beam_decode_device(torch.from_numpy(p).to(gpu), lens, blank, W, cutoff, nbest)
-    torch.cuda.synchronize()
-    return tuple(t.cpu().numpy() for t in out)
+    """the acoustic search: without the flag of the fused search's end-of-sentence step"""
+    return reference(p, lens, blank, W, cutoff, nbest)[:4]
 
 
 def _assert_scores(tag, T, got, ref):

@@ -2,8 +2,8 @@
 against a float64 restatement of its semantics, against the acoustic-only call, the CTC loss and the host scorer, and the streaming
 form against the one-shot call.
 
-Reference: ``_ref_row`` -- test_gpu_ctc_beam.py's float64 prefix beam search (dicts of label tuples, linear space, the same candidate
-cells, merge order and canonical-index tie rule) restated here with the model: every entry carries an LM state, an extension is
+Reference: ``ref_row`` of ctc_reference.py -- the float64 prefix beam search (dicts of label tuples, linear space, the same candidate
+cells, merge order and canonical-index tie rule) given the model (``Walk`` below): every entry carries an LM state, an extension is
 multiplied by F(state, c) = exp(sum of alpha * backoff_logw along the walk + alpha * arc_logp + beta) (or the unknown-label factor),
 and after the last frame every total is multiplied by E(state), zeros are dropped and the rest are ordered again, ties to the lower
 rank.  The table's float32 inputs are taken as they are; everything else is float64.
@@ -25,17 +25,12 @@ import numpy as np
 import pytest
 import torch
 
+from ctc_reference import (decode as _run_acoustic, drive as _drive, eq as _eq, ref_row as _ref_row, reference as _reference,
+                           softmax as _softmax, tol_lm as _tol)
 from nntoolkitcore_amd import capi, layers as NL
 
 pytestmark = pytest.mark.gpu
 INF = float("inf")
-
-
-def _softmax(seed, B, T, Cc, scale=2.0):
-    rng = np.random.default_rng(seed)
-    z = scale * rng.standard_normal((B, T, Cc))
-    e = np.exp(z - z.max(-1, keepdims=True))
-    return (e / e.sum(-1, keepdims=True)).astype(np.float32)
 
 
 # ---- tables ----
@@ -124,86 +119,12 @@ class Walk:
         return 1.0 if self.fin is None else float(np.exp(self._ln(self.fin[s], 0.0)))
 
 
-def _ref_row(p, blank, W, cutoff, walk):
-    """p [T][C] float64, the row's valid frames; walk None: acoustic only -> (the last beam in rank order as (labels, p_b, p_nb, state),
-    the smallest relative W / W+1 gap)"""
-    T, Cc = p.shape
-    beam = [((), 1.0, 0.0, walk.t["start_state"] if walk else 0)]
-    gap = np.inf
-    nonblank = [c for c in range(Cc) if c != blank]
-    for t in range(T):
-        pt = p[t]
-        if cutoff == 0 or cutoff >= Cc - 1:
-            E = nonblank
-        else:
-            E = sorted(sorted(nonblank, key=lambda c: (-pt[c], c))[:cutoff])
-        stays, cand = {}, {}
-        for i, (l, pb, pnb, s) in enumerate(beam):
-            stays[l] = (i * (Cc + 1), (pb + pnb) * pt[blank], pnb * pt[l[-1]] if l else 0.0, s)
-        for i, (l, pb, pnb, s) in enumerate(beam):
-            for c in E:
-                v = pb * pt[c] if (l and c == l[-1]) else (pb + pnb) * pt[c]
-                nx = s
-                if walk:
-                    f, nx = walk(s, c)
-                    v = f * v
-                lc = l + (c,)
-                if lc in stays:
-                    _, sb, snb, ss = stays.pop(lc)
-                    assert ss == nx
-                    cand[lc] = (i * (Cc + 1) + 1 + c, sb, snb + v, nx)
-                else:
-                    cand[lc] = (i * (Cc + 1) + 1 + c, 0.0, v, nx)
-        for l, v in stays.items():
-            cand[l] = v
-        items = sorted(((-(sb + snb), idx, l, sb, snb, s) for l, (idx, sb, snb, s) in cand.items() if sb + snb != 0.0))
-        if len(items) > W:
-            a, b = -items[W - 1][0], -items[W][0]
-            gap = min(gap, (a - b) / a)
-        beam = [(l, sb, snb, s) for _, _, l, sb, snb, s in items[:W]]
-    return beam, gap
-
-
-def _reference(p, lens, blank, W, cutoff, nbest, walk):
-    """-> labels [B][nbest][T], lengths, float64 scores, the smallest gap of the premise, whether the end-of-sentence step reordered
-    the reported part of some row's beam"""
-    B, T, _ = p.shape
-    lab, n, sc = np.full((B, nbest, T), -1, np.int32), np.full((B, nbest), -1, np.int32), np.full((B, nbest), -np.inf)
-    gap, reordered = np.inf, False
-    for b in range(B):
-        beam, g = _ref_row(p[b, :lens[b]].astype(np.float64), blank, W, cutoff, walk)
-        gap = min(gap, g)
-        fin = [(-(pb + pnb) * (walk.final(s) if walk else 1.0), k, l) for k, (l, pb, pnb, s) in enumerate(beam)]
-        fin = sorted(x for x in fin if x[0] != 0.0)
-        reordered |= [k for _, k, _ in fin[:nbest]] != list(range(min(nbest, len(fin))))
-        for k in range(min(nbest, len(fin))):
-            l = fin[k][2]
-            lab[b, k, :len(l)] = l
-            n[b, k] = len(l)
-            sc[b, k] = np.log(-fin[k][0])
-            if k + 1 < len(fin):
-                gap = min(gap, (fin[k + 1][0] - fin[k][0]) / -fin[k][0])
-    return lab, n, sc, gap, reordered
-
-
 def _rounds(T, D):
     return (4 + 2 * D + 2) * T + 2
 
 
-def _tol(rounds, ref):
-    return 2 * rounds * 2.0 ** -24 + 4 * np.spacing(np.abs(ref).astype(np.float32)).astype(np.float64)
-
-
 def _run(gpu, p, lm, lens, blank, W, cutoff, nbest):
-    out = NL.ctc_beam_decode_lm_device(torch.from_numpy(p).to(gpu), lm, lens, blank, W, cutoff, nbest)
-    torch.cuda.synchronize()
-    return tuple(t.cpu().numpy() for t in out)
-
-
-def _run_acoustic(gpu, p, lens, blank, W, cutoff, nbest):
-    out = NL.ctc_beam_decode_device(torch.from_numpy(p).to(gpu), lens, blank, W, cutoff, nbest)
-    torch.cuda.synchronize()
-    return tuple(t.cpu().numpy() for t in out)
+    return _run_acoustic(gpu, p, lens, blank, W, cutoff, nbest, lm)
 
 
 def _assert_scores(tag, rounds, got, ref):
@@ -212,12 +133,6 @@ def _assert_scores(tag, rounds, got, ref):
     err = np.abs(got[fin].astype(np.float64) - ref[fin])
     print("%s: largest score error %.3g of %.3g allowed" % (tag, err.max(initial=0.0), _tol(rounds, ref[fin]).min(initial=np.inf)))
     assert (err <= _tol(rounds, ref[fin])).all(), tag
-
-
-def _eq(got, want, msg=""):
-    np.testing.assert_array_equal(got[1], want[1], err_msg=msg)
-    np.testing.assert_array_equal(got[0], want[0], err_msg=msg)
-    np.testing.assert_array_equal(got[2].view(np.int32), want[2].view(np.int32), err_msg=msg)
 
 
 # name: (posterior seed, B, T, C, W, cutoff, nbest, blank, lengths, table, alpha, beta, D)
@@ -340,28 +255,6 @@ IRREGULAR = [[5, 0, 1], [0, 3, 0], [8, 0, 0], [0, 0, 0], [2, 8, 0], [7, 1, 0], [
 
 def _ch_lm():
     return NL.NgramLm.from_arrays(alpha=0.75, beta=0.25, **sparse_trigram(3, CH["C"], CH["blank"], n_bi=4, n_tri=8, arcs0=6, final=True))
-
-
-def _chunk(p, pos, n, max_frames):
-    B, _, Cc = p.shape
-    x = np.full((B, max_frames, Cc), np.nan, np.float32)
-    for b in range(B):
-        x[b, :n[b]] = p[b, pos[b]:pos[b] + n[b]]
-    return x
-
-
-def _drive(gpu, dec, p, pushes, max_frames, finals=None, after=None):
-    B = p.shape[0]
-    pos, got = [0] * B, None
-    for i, n in enumerate(pushes):
-        out = dec.push(torch.from_numpy(_chunk(p, pos, n, max_frames)).to(gpu), n, None if finals is None else finals[i])
-        torch.cuda.synchronize()
-        got = tuple(t.cpu().numpy() for t in out)
-        for b in range(B):
-            pos[b] += n[b]
-        if after is not None:
-            after(i, list(pos), got)
-    return got
 
 
 @pytest.mark.parametrize("schedule", ["frame_by_frame", "irregular"])

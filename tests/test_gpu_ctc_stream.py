@@ -5,8 +5,8 @@ streaming best path against the one-shot best path.
 "Equal" below is assert_array_equal on labels and lengths and on the scores viewed as int32.  The frames a push does not bring
 (t >= n_frames[b]) are filled with NaN by the driver, so every case also checks that they influence nothing.
 
-One case is anchored outside the kernels: a float64 prefix beam search (``_ref_row``, restated from test_gpu_ctc_beam.py: dicts of label
-tuples, linear space, the same candidate cells, merge order and canonical-index tie rule) under that file's premise -- at every frame
+One case is anchored outside the kernels: the float64 prefix beam search of ctc_reference.py (dicts of label tuples, linear space, the
+same candidate cells, merge order and canonical-index tie rule) under test_gpu_ctc_beam.py's premise -- at every frame
 the relative gap between the W-th and the (W+1)-th candidate total, and between adjacent reported hypotheses, is at least
 16 * T * 2^-24 -- and its score tolerance 8 * T * 2^-24 + 4 * ulp_f32(|ref|)."""
 import ctypes as C
@@ -16,54 +16,10 @@ import numpy as np
 import pytest
 import torch
 
+from ctc_reference import chunk as _chunk, decode as _oneshot, drive as _drive, eq as _eq, reference, softmax as _softmax, tol as _tol
 from nntoolkitcore_amd import capi, layers as NL
 
 pytestmark = pytest.mark.gpu
-
-
-def _softmax(seed, B, T, Cc):
-    rng = np.random.default_rng(seed)
-    z = 2.0 * rng.standard_normal((B, T, Cc))
-    e = np.exp(z - z.max(-1, keepdims=True))
-    return (e / e.sum(-1, keepdims=True)).astype(np.float32)
-
-
-def _oneshot(gpu, p, lens, blank, W, cutoff, nbest):
-    out = NL.ctc_beam_decode_device(torch.from_numpy(p).to(gpu), lens, blank, W, cutoff, nbest)
-    torch.cuda.synchronize()
-    return tuple(t.cpu().numpy() for t in out)
-
-
-def _eq(got, want, msg=""):
-    np.testing.assert_array_equal(got[1], want[1], err_msg=msg)
-    np.testing.assert_array_equal(got[0], want[0], err_msg=msg)
-    np.testing.assert_array_equal(got[2].view(np.int32), want[2].view(np.int32), err_msg=msg)
-
-
-def _chunk(p, pos, n, max_frames):
-    """the block of one push: row b's next n[b] frames, NaN behind them"""
-    B, _, Cc = p.shape
-    x = np.full((B, max_frames, Cc), np.nan, np.float32)
-    for b in range(B):
-        x[b, :n[b]] = p[b, pos[b]:pos[b] + n[b]]
-    return x
-
-
-def _drive(gpu, dec, p, pushes, max_frames, pos=None, finals=None, after=None):
-    """push the rows of p through dec: pushes = one [B] list of frame counts per push.  Returns the last push's outputs as numpy."""
-    B = p.shape[0]
-    pos = [0] * B if pos is None else pos
-    got = None
-    for i, n in enumerate(pushes):
-        x = torch.from_numpy(_chunk(p, pos, n, max_frames)).to(gpu)
-        out = dec.push(x, n, None if finals is None else finals[i])
-        torch.cuda.synchronize()
-        got = tuple(t.cpu().numpy() for t in out)
-        for b in range(B):
-            pos[b] += n[b]
-        if after is not None:
-            after(i, list(pos), got)
-    return got
 
 
 def _frame_by_frame(lens):
@@ -134,68 +90,11 @@ def test_every_kernel_path_split_in_three(gpu, name):
     dec.close()
 
 
-def _ref_row(p, blank, W, cutoff):
-    """p [T][C] float64, the row's valid frames -> (beam in rank order as (labels, p_b, p_nb), smallest relative W / W+1 gap)"""
-    T, Cc = p.shape
-    beam = [((), 1.0, 0.0)]
-    gap = np.inf
-    nonblank = [c for c in range(Cc) if c != blank]
-    for t in range(T):
-        pt = p[t]
-        if cutoff == 0 or cutoff >= Cc - 1:
-            E = nonblank
-        else:
-            E = sorted(sorted(nonblank, key=lambda c: (-pt[c], c))[:cutoff])
-        stays, cand = {}, {}
-        for i, (l, pb, pnb) in enumerate(beam):
-            stays[l] = (i * (Cc + 1), (pb + pnb) * pt[blank], pnb * pt[l[-1]] if l else 0.0)
-        for i, (l, pb, pnb) in enumerate(beam):
-            for c in E:
-                v = pb * pt[c] if (l and c == l[-1]) else (pb + pnb) * pt[c]
-                lc = l + (c,)
-                if lc in stays:
-                    _, sb, snb = stays.pop(lc)
-                    cand[lc] = (i * (Cc + 1) + 1 + c, sb, snb + v)
-                else:
-                    cand[lc] = (i * (Cc + 1) + 1 + c, 0.0, v)
-        for l, v in stays.items():
-            cand[l] = v
-        items = sorted(((-(sb + snb), idx, l, sb, snb) for l, (idx, sb, snb) in cand.items() if sb + snb != 0.0))
-        if len(items) > W:
-            a, b = -items[W - 1][0], -items[W][0]
-            gap = min(gap, (a - b) / a)
-        beam = [(l, sb, snb) for _, _, l, sb, snb in items[:W]]
-    return beam, gap
-
-
-def _reference(p, lens, blank, W, cutoff, nbest):
-    """-> labels [B][nbest][T], lengths, float64 scores, the smallest gap of the premise"""
-    B, T, _ = p.shape
-    lab, n, sc = np.full((B, nbest, T), -1, np.int32), np.full((B, nbest), -1, np.int32), np.full((B, nbest), -np.inf)
-    gap = np.inf
-    for b in range(B):
-        beam, g = _ref_row(p[b, :lens[b]].astype(np.float64), blank, W, cutoff)
-        gap = min(gap, g)
-        tot = [pb + pnb for _, pb, pnb in beam]
-        for k in range(min(nbest, len(beam))):
-            l = beam[k][0]
-            lab[b, k, :len(l)] = l
-            n[b, k] = len(l)
-            sc[b, k] = np.log(tot[k])
-            if k + 1 < len(beam):
-                gap = min(gap, (tot[k] - tot[k + 1]) / tot[k])
-    return lab, n, sc, gap
-
-
-def _tol(T, ref):
-    return 8 * T * 2.0 ** -24 + 4 * np.spacing(np.abs(ref).astype(np.float32)).astype(np.float64)
-
-
 def test_frame_by_frame_against_the_float64_search(gpu):
     """case 4: the `small` shape, one frame per push in a block of three, against a reference that shares no code with the kernels"""
     seed, B, T, Cc, W, cutoff, nbest, blank = 0, 2, 12, 5, 4, 0, 4, 4
     p = _softmax(seed, B, T, Cc)
-    lab, n, sc, gap = _reference(p, [T] * B, blank, W, cutoff, nbest)
+    lab, n, sc, gap, _ = reference(p, [T] * B, blank, W, cutoff, nbest)
     print("smallest relative gap %.3g, premise %.3g" % (gap, 16 * T * 2.0 ** -24))
     assert gap >= 16 * T * 2.0 ** -24, "the premise does not hold for this seed"
     dec = NL.CtcBeamStream(B, 3, Cc, blank, W, cutoff, nbest, max_labels=T)

@@ -63,7 +63,7 @@ def _chunk_floats(total):
 
 def _n_chunks(sizes, phases):
     ch = _chunk_floats(sum(sizes))
-    return sum((ph + n + ch - 1) // ch for n, ph in zip(sizes, phases) if n)     # train.c:345 (nntk_optimizer_create)
+    return sum((ph + n + ch - 1) // ch for n, ph in zip(sizes, phases) if n)     # train.c:238 (nntk_optimizer_create)
 
 
 def _make_inputs(sizes, steps):

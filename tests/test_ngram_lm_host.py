@@ -1,5 +1,5 @@
 """The n-gram language model of the fused CTC beam search: what the host layer decides without a device (csrc/host/ngram_lm.c,
-train.c) -- every refusal of nntk_ngram_lm_create, nntk_ngram_lm_score against a float64 walk, the ARPA parser, the size functions,
+ctc.c) -- every refusal of nntk_ngram_lm_create, nntk_ngram_lm_score against a float64 walk, the ARPA parser, the size functions,
 the empty batch.  No GPU."""
 import ctypes as C
 
