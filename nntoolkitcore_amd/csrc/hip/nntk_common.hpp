@@ -25,6 +25,7 @@ struct NntkOptions {
     int rec_xf = -1;             // register-resident kernels: f32 input packed into frag3 form first (1 always, 0 only when the f32 path cannot take the shape; auto: see recurrent.c)
     int rec_fk = -1;             // full-K register-resident kernels (recurrent_fk.hip): 1 every shape they take, 0 none; auto: 256-wide inputs (where they beat the split-K family)
     int rec_hf = -1;             // LSTM (H > 256) -> FRAG2H output: the HF instantiation of lstm_rr_kernel (h.U on two f16 images, three products); 0 off
+    int rec_hf_pend = 1;         // the HF instantiation's hand-off: 1 pending pattern (lstm_rr_hfp_kernel), 0 flag words (the control; same bits)
     int rec_bd = -1;             // bidirectional calls: both directions in one launch of the BD instantiations where both take those kernels; 0: always the composed recipe (A/B)
     int dense_frag3 = -1;        // dense GEMM with a frag3 A operand (0: consumers unpack to f32 and run the LDS-staged GEMM)
     int dense_f16x2 = -1;        // LSTM -> TimeDistributedDense: the tensor in between as two f16 images, three products (frag3.hip FRAG2H); 0: the frag3 route

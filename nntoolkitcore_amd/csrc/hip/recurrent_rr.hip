@@ -32,7 +32,7 @@
 //     t + 1 into its column tile's flag word; a consumer wave reads the batch tile's flags with one wave-wide sc1 load before it
 //     requests the operand.  Cheapest in instructions; the chain publication -> drain -> flag -> poll -> operand request -> operand
 //     is ~5 k cycles, which a 10-k-step half-step covers.
-//   * PENDING PATTERN (KH = 4, H <= 256): that chain is LONGER than a 6..8-k-step half-step (stamps, DESIGN K4b round 4: the
+//   * PENDING PATTERN (KH = 4, H <= 256; and the HF instantiations, whose 6-MFMA k steps no longer cover the flag chain: HP below): that chain is LONGER than a 6..8-k-step half-step (stamps, DESIGN K4b round 4: the
 //     half-step took as long as the chain, 5.15 k cycles against 2.3 k of MFMA time), so these shapes drop the flag: a block that
 //     has not been written yet holds the word 0xffffffff in every position, a published block never does (the publisher maps the
 //     one bf16 pair that would -- two NaNs with all payload bits set -- to another NaN), and the consumer simply requests the
@@ -205,8 +205,12 @@ __global__ __launch_bounds__(256) void rr_tile_h0_kernel(const float *__restrict
 // 64-row tile belongs to one direction (bd_pad % 64 == 0): the direction is a scalar, and so is everything it selects -- weight images,
 // biases, the output base.  The hand-off, the flags and the x operand keep their layout over the virtual rows.  Output rows are the caller's:
 // a backward lane stores step t at time L - 1 - t of its row, nothing at t >= L; padding rows store nothing.
-template <int KH, int KX, bool TRAIN, int CELL, bool XF, bool HF = false, bool VL = false, bool BD = false>
+// HP (HF only: lstm_rr_hfp_kernel): the HF hand-off by PENDING PATTERN instead of flags.  A FRAG2H word is two f16 values of one image; "not
+// written" is the same 0xffffffff (a pair of all-ones NaNs), which the publisher's clamp keeps out of every published word.  Marks, looks,
+// bounded spin, fault word and fault injection are the KH = 4 protocol's, on two blocks per (row block, k step) instead of three.
+template <int KH, int KX, bool TRAIN, int CELL, bool XF, bool HF = false, bool VL = false, bool BD = false, bool HP = false>
 __device__ __forceinline__ void rr_body(const RRParams &p) {
+    static_assert(!HP || HF, "HP: the pending-pattern form of the HF instantiations");
     static_assert(!VL || !HF, "VL: not with the two-f16-image hand-off");
     static_assert(!BD || (VL && XF), "BD: per-row lengths and a frag3 x operand");
     constexpr int NH = HF ? 2 : 3;                    // images of the h hand-off
@@ -226,7 +230,7 @@ __device__ __forceinline__ void rr_body(const RRParams &p) {
 #ifndef RR_PEND
 #define RR_PEND (KH == 4)
 #endif
-    constexpr bool PEND = RR_PEND;
+    constexpr bool PEND = (RR_PEND) || HP;
 #ifndef RR_S_E1_XLATE
 #define RR_S_E1_XLATE 2           // the KX = 4 shapes (x requests behind the poll) may arrive from k step 2 on: 6.82 -> 6.66 us per step; 4: 8.3 -- the chain is that tight
 #endif
@@ -248,20 +252,29 @@ __device__ __forceinline__ void rr_body(const RRParams &p) {
 #ifndef RR_HEAD_LEAD
 #define RR_HEAD_LEAD 1            // PEND: the head of the other half's next operand goes out this many k steps before the half-step's last one
 #endif                            // (GRU-256 pair: 0: 10.6, 1: 10.2, 2: 11.2, 3: 12.0 ms -- earlier than that the fragments are still pending and the second look costs a round trip)
-    constexpr int S_HEAD = !PEND ? S_E2 : S_E2 - RR_HEAD_LEAD > S_PUB ? S_E2 - RR_HEAD_LEAD : S_PUB + 1;
+    // HP: the same two constants for the HF kernel without its flag chain (RR_HF_PEND_HEAD_LEAD, RR_HF_PEND_NPRE: the table is in DESIGN K4e)
+#ifndef RR_HF_PEND_HEAD_LEAD
+#define RR_HF_PEND_HEAD_LEAD 1
+#endif
+#ifndef RR_HF_PEND_NPRE
+#define RR_HF_PEND_NPRE 5
+#endif
+    constexpr int HEAD_LEAD = HP ? RR_HF_PEND_HEAD_LEAD : RR_HEAD_LEAD;
+    constexpr int S_HEAD = !PEND ? S_E2 : S_E2 - HEAD_LEAD > S_PUB ? S_E2 - HEAD_LEAD : S_PUB + 1;
     // Operand schedule: the fragments of h k step i are requested NPRE k steps ... see issue_h below: i < NPRE at S_HEAD of the
     // OTHER half's sequence (flag protocol: after the poll), i >= NPRE at k step i - NPRE of the half's own sequence (needed at KX + i).
 #ifndef RR_HF_NPRE
 #define RR_HF_NPRE 5
 #endif
-    constexpr int NPRE = (HF ? RR_HF_NPRE : RR_NPRE) < KH ? (HF ? RR_HF_NPRE : RR_NPRE) : KH;
+    constexpr int NPRE_ = HP ? RR_HF_PEND_NPRE : HF ? RR_HF_NPRE : RR_NPRE;
+    constexpr int NPRE = NPRE_ < KH ? NPRE_ : KH;
     // flag protocol: vector-memory operations a wave issues between a publication (S_PUB) and its arrival (S_E1): the own-sequence
     // operand requests of k steps S_PUB .. S_E1 - 1 and the x request at S_XSPL -- what the arrival's counted wait leaves in flight
     constexpr int own_lo = S_PUB + NPRE < KH ? S_PUB + NPRE : KH, own_hi = S_E1 + NPRE < KH ? S_E1 + NPRE : KH;
     constexpr int NXR = XF ? 3 * KX : 2 * KX;         // vector-memory requests of one x fetch
     constexpr int N_X_AFTER_PUB = (X_LATE || S_XSPL >= S_E1) ? 0 : NXR;      // (S_XSPL == S_E1: the arrival precedes the x requests in its k step)
     constexpr int N_AFTER_PUB = NH * (own_hi - own_lo) + N_X_AFTER_PUB;
-    static_assert(!HF || (!PEND && !TRAIN && XF && CELL == 0 && !ULR), "HF: the flag-protocol LSTM instantiations with a frag3 x operand");
+    static_assert(!HF || (PEND == HP && !TRAIN && XF && CELL == 0 && !ULR), "HF: the LSTM instantiations with a frag3 x operand (flags, or HP: pending pattern)");
     static_assert(NST >= 5 && S_XSPL >= KX && S_XSPL > S_PUB && KH - NPRE <= S_E2 && S_HEAD > S_PUB && S_HEAD <= S_E2, "slice schedule");
     // flag protocol: the flags are requested POLL_LEAD k steps before they are looked at.  Two k steps (~1 k cycles) cover the load's round
     // trip; with one the check waited for it: LSTM-512 5.94-5.98 -> 5.78-5.85 ms in four alternating rounds, three k steps 5.82-5.85
@@ -553,6 +566,8 @@ __device__ __forceinline__ void rr_body(const RRParams &p) {
         if (HF && !RR_DBG(128)) {                       // the hand-off's two f16 words (images 0, 1 of `hs`)
             unsigned sh, sl;
             rr_split_pair_h2(hn[0], hn[1], sh, sl);
+            // HP: as below -- a pair of all-ones f16 NaNs becomes another NaN pair; no finite value changes
+            if (PEND) { sh = min(sh, 0xfffffffeu); sl = min(sl, 0xfffffffeu); }
             unsigned *d = hs + n * RR_HS_LD + (jl >> 1);
             d[0] = sh; d[32 * RR_HS_LD] = sl;
         } else if (!RR_DBG(128)) {
@@ -664,14 +679,14 @@ __device__ __forceinline__ void rr_body(const RRParams &p) {
             // the OTHER half's publishing wave (idle in this slice) marks this column tile's blocks of step t + 2 pending (see "Hand-off
             // protocol" above); past the last step the offset is out of range and the stores are dropped
             if (!RR_DBG(128)) {
-                const int vo = lane16 + (((bt_abs * 2 + half) * NKS + ct) * 3) * 1024;
+                const int vo = lane16 + (((bt_abs * 2 + half) * NKS + ct) * NH) * 1024;
                 const __amdgpu_buffer_rsrc_t rs2 = rs_wr(t + 2 < T ? t + 2 : t);
                 const int vo2 = t + 2 < T ? vo : RR_OOB_F;
                 const rr_v4u pend = {RR_PENDING, RR_PENDING, RR_PENDING, RR_PENDING};
                 __builtin_amdgcn_raw_buffer_store_b128(pend, rs2, vo2, 0, RR_ST_AUX);
                 __builtin_amdgcn_raw_buffer_store_b128(pend, rs2, vo2 + 1024, 0, RR_ST_AUX);
-                __builtin_amdgcn_raw_buffer_store_b128(pend, rs2, vo2 + 2048, 0, RR_ST_AUX);
-                RR_BOUND(3, (size_t)(t + 2 < T ? t + 2 : t) * p.hstep, vo2 + 2048, 0, hb_bytes, 16);
+                if (NH == 3) __builtin_amdgcn_raw_buffer_store_b128(pend, rs2, vo2 + 2048, 0, RR_ST_AUX);
+                RR_BOUND(3, (size_t)(t + 2 < T ? t + 2 : t) * p.hstep, vo2 + (NH - 1) * 1024, 0, hb_bytes, 16);
             }
         }
     };
@@ -719,7 +734,7 @@ __device__ __forceinline__ void rr_body(const RRParams &p) {
     };
 
     // ---- pending-pattern protocol (PEND) ----
-    // validity of a fetched k step: no word of its three fragments is the pending pattern.  The fast path is 7 vector-ALU
+    // validity of a fetched k step: no word of its NH fragments (three; HP: two) is the pending pattern.  The fast path is 7 vector-ALU
     // instructions and an untaken branch per k step; a fragment that is still pending is requested again (bounded; a peer that gave up
     // has raised the fault word and ends every other spin at once).  spin_ticks == 0 is fault injection (tests): behave as if the
     // first look had found nothing and the budget had run out.
@@ -729,7 +744,7 @@ __device__ __forceinline__ void rr_body(const RRParams &p) {
         constexpr int half = decltype(half_tag)::value;
         unsigned mx = 0;
 #pragma unroll
-        for (int m = 0; m < 3; ++m) {
+        for (int m = 0; m < NH; ++m) {
             const rr_v4u v = hf[half][i][m];
             mx = max(mx, max(max(v.x, v.y), max(v.z, v.w)));
         }
@@ -741,7 +756,7 @@ __device__ __forceinline__ void rr_body(const RRParams &p) {
             const unsigned long long t_start = __builtin_amdgcn_s_memrealtime();
             bool expired = p.spin_ticks == 0;
             while (!expired) {
-                issue_h(half_tag, t, 3 * i, 3 * i + 3);
+                issue_h(half_tag, t, NH * i, NH * i + NH);
                 if (probe_h(half_tag, i) == 0) break;
                 if (__hip_atomic_load(p.fault, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) { expired = true; break; }
                 __builtin_amdgcn_s_sleep(1);
@@ -964,6 +979,9 @@ __device__ __forceinline__ void rr_body(const RRParams &p) {
 }
 template <int KH, int KX, bool TRAIN = false, bool XF = false, bool HF = false, bool VL = false, bool BD = false>
 __global__ __launch_bounds__(256) void lstm_rr_kernel(RRParams p) { rr_body<KH, KX, TRAIN, 0, XF, HF, VL, BD>(p); }
+// the HF instantiations with the pending-pattern hand-off (option rec_hf_pend; lstm_rr_kernel<KH, KX, false, true, true> keeps the flags)
+template <int KH, int KX>
+__global__ __launch_bounds__(256) void lstm_rr_hfp_kernel(RRParams p) { rr_body<KH, KX, false, 0, true, true, false, false, true>(p); }
 template <int KH, int KX, bool TRAIN = false, bool XF = false, bool VL = false, bool BD = false>
 __global__ __launch_bounds__(256) void gru_rr_kernel(RRParams p) { rr_body<KH, KX, TRAIN, 1, XF, false, VL, BD>(p); }
 
@@ -1226,7 +1244,12 @@ static int rr_launch(const RRIo &io, const float *d_img, const float *d_bi, cons
     else if (KH == 4 && KX == 4) kern = rr_pick<4, 4>(cell, train, xf, vl, bd);
     else if (KH == 4 && KX == 2) kern = rr_pick<4, 2>(cell, train, xf, vl, bd);
     else if (KH == 4 && KX == 1) kern = rr_pick<4, 1>(cell, train, xf, vl, bd);
+    // HF: hand-off by pending pattern (lstm_rr_hfp_kernel), or, with option rec_hf_pend = 0, by flags (control and fallback)
+    // (KX = 4: flags only -- with four x k steps' operand sets next to both halves' h operand the looks do not fit the register file: the
+    // instantiation came out with a private segment, which tools/check_rr_waits.py refuses)
+    const bool hfp = hf && opt.rec_hf_pend != 0 && KX != 4;
     if (hf) kern = KX == 4 ? lstm_rr_kernel<8, 4, false, true, true> : KX == 2 ? lstm_rr_kernel<8, 2, false, true, true> : lstm_rr_kernel<8, 1, false, true, true>;
+    if (hfp) kern = KX == 2 ? lstm_rr_hfp_kernel<8, 2> : lstm_rr_hfp_kernel<8, 1>;
     if (!kern) return 1;
     const size_t lds = rr_lds_bytes(KH, KX, train, hf);
     if (lds > 160 * 1024) return 1;
@@ -1323,6 +1346,8 @@ static int rr_launch(const RRIo &io, const float *d_img, const float *d_bi, cons
     static const char *const bd_names[2][2][3] = {{{"lstm_rr_kernel<4,1,bd>", "lstm_rr_kernel<4,2,bd>", "lstm_rr_kernel<4,4,bd>"}, {"lstm_rr_kernel<8,1,bd>", "lstm_rr_kernel<8,2,bd>", ""}},
                                                   {{"gru_rr_kernel<4,1,bd>", "gru_rr_kernel<4,2,bd>", "gru_rr_kernel<4,4,bd>"}, {"gru_rr_kernel<8,1,bd>", "gru_rr_kernel<8,2,bd>", ""}}};
     if (bd && took4 == 1) nntk_set_last_rec_kernel(bd_names[cell == 1][KH == 8][KX == 1 ? 0 : KX == 2 ? 1 : 2]);
+    // (the HF family reports one name per shape; its flag-protocol control says so ahead of the suffix)
+    else if (hf && !hfp && KX != 4) nntk_set_last_rec_kernel(KX == 2 ? "lstm_rr_kernel<8,2,flags,hf>" : "lstm_rr_kernel<8,1,flags,hf>");
     else if (hf) nntk_set_last_rec_kernel(KX == 4 ? "lstm_rr_kernel<8,4,hf>" : KX == 2 ? "lstm_rr_kernel<8,2,hf>" : "lstm_rr_kernel<8,1,hf>");
     else if (took4 == 1) nntk_set_last_rec_kernel(names[cell == 1][KH == 8][KX == 1 ? 0 : KX == 2 ? 1 : 2]);
     return 0;

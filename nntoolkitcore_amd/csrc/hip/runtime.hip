@@ -47,6 +47,7 @@ static const OptDesc g_opt_table[] = {
     {"rec_xf", "NNTK_REC_XF", &NntkOptions::rec_xf},
     {"rec_fk", "NNTK_REC_FK", &NntkOptions::rec_fk},
     {"rec_hf", "NNTK_REC_HF", &NntkOptions::rec_hf},
+    {"rec_hf_pend", "NNTK_REC_HF_PEND", &NntkOptions::rec_hf_pend},
     {"rec_bd", "NNTK_REC_BD", &NntkOptions::rec_bd},
     {"dense_frag3", "NNTK_DENSE_FRAG3", &NntkOptions::dense_frag3},
     {"dense_f16x2", "NNTK_DENSE_F16X2", &NntkOptions::dense_f16x2},

@@ -35,13 +35,15 @@ def main():
     print("lstm_rr_kernel / gru_rr_kernel: %d flag polls checked, %d violations" % (ptotal, pbad))
     qbad, qtotal = check_pending(txt)
     print("lstm_rr_kernel / gru_rr_kernel: %d pending-pattern looks checked, %d defects" % (qtotal, qbad))
+    hbad, htotal = check_pending(txt, HFP, 8, 32)
+    print("lstm_rr_hfp_kernel (HF, pending pattern): %d looks checked, %d defects" % (htotal, hbad))
     mbad, mtotal = check_marks(txt)
-    print("pending-pattern kernels (rr KH = 4, fk): %d mark groups checked, %d not covered by a vmcnt wait before the second barrier / the next publication" % (mtotal, mbad))
+    print("pending-pattern kernels (rr KH = 4, rr HF, fk): %d mark groups checked, %d not covered by a vmcnt wait before the second barrier / the next publication" % (mtotal, mbad))
     fbad, ftotal = check_split_fma(txt)
     print("bf16 x 3 splits (rr, fk, frag3, conv): %d conversions checked, %d fed by a fused multiply-add of an image" % (ftotal, fbad))
     sbad, stotal = check_scratch(txt)
     print("register-resident / MFMA kernels (rr, fk, dense_frag3, conv1d): %d kernels checked, %d with a private segment (spills)" % (stotal, sbad))
-    return 1 if (bad or total == 0 or pbad or ptotal == 0 or qbad or qtotal == 0 or mbad or mtotal == 0 or fbad or ftotal == 0
+    return 1 if (bad or total == 0 or pbad or ptotal == 0 or qbad or qtotal == 0 or hbad or htotal == 0 or mbad or mtotal == 0 or fbad or ftotal == 0
                  or sbad or stotal == 0) else 0
 
 
@@ -189,16 +191,21 @@ def check_polls(txt):
     return bad, total
 
 
-def check_pending(txt):
+HFP = r'^(_Z18lstm_rr_hfp_kernel\w+):'
+
+
+def check_pending(txt, pattern=r'^(_Z1[34](?:lstm|gru)_rr_kernelILi4E\w+):', leaves=12, min_looks=32):
     """The KH = 4 instantiations hand h over WITHOUT flags: a consumer looks at the fragments it fetched and takes a word of 0xffffffff
     for "not written yet" (recurrent_rr.hip, probe_h / settle_h).  That is only sound if every WORD of the three fragments of a k step
     is looked at (nothing is assumed about how a 16-byte store becomes visible).  For each such kernel: every `v_cmp_eq_u32 -1, vN`
     sits on top of a v_max_u32 / v_max3_u32 tree with exactly twelve leaf registers; there are at least 2 x 4 k steps x 2 halves of
     them (the steady-state loop and the peeled last half-steps, fast path + the second look of the slow path); the kernel contains no
-    asm vmcnt wait (the flag protocol's drain) and uses no scratch.  (Which registers hold a fragment changes from one peeled copy to
+    asm vmcnt wait (the flag protocol's drain) and uses no scratch.  The HF instantiations with the pending pattern (lstm_rr_hfp_kernel:
+    `pattern`) are checked the same way: two fragments per k step, so eight leaf registers per look, and at least 2 x 8 k steps x 2 halves
+    of looks.  (Which registers hold a fragment changes from one peeled copy to
     the next, so the leaves are not traced back to the loads; the bit-for-bit shard / whole-batch tests do that at run time.)"""
     bad = total = 0
-    for kname in re.findall(r'^(_Z1[34](?:lstm|gru)_rr_kernelILi4E\w+):', txt, re.M):
+    for kname in re.findall(pattern, txt, re.M):
         a = txt.index("\n" + kname + ":")
         s = [l.strip() for l in txt[a:txt.index(".Lfunc_end", a)].split("\n")]
         m = re.search(r'\.amdhsa_kernel %s\b.*?\.end_amdhsa_kernel' % re.escape(kname), txt, re.S)
@@ -223,10 +230,10 @@ def check_pending(txt):
                     r = regs_of(o.strip())
                     if len(r) == 1:
                         want |= r                  # (a source that no earlier max in the window defines stays in `want`: a leaf)
-            if len(want) != 12:
+            if len(want) != leaves:
                 bad += 1
-                print("%s: the look at +%d covers %d registers %s, not the twelve words of three fragments" % (kname, i, len(want), sorted(want)))
-        if looks < 32:
+                print("%s: the look at +%d covers %d registers %s, not the %d words of %d fragments" % (kname, i, len(want), sorted(want), leaves, leaves // 4))
+        if looks < min_looks:
             bad += 1
             print("%s: only %d looks" % (kname, looks))
         if any("ASMSTART" in s[k - 1] and re.match(r's_waitcnt vmcnt', t) for k, t in enumerate(s)):
@@ -251,7 +258,7 @@ def check_marks(txt):
     `s_waitcnt vmcnt(N)` with N <= the vector-memory instructions issued on that path since the marks (so none of the <= N operations
     still in flight is a mark)."""
     bad = total = 0
-    for kname, ins in list(kernels(txt, r'^(_Z1[34](?:lstm|gru)_rr_kernelILi4E\w+):')) + list(kernels(txt, r'^(_Z1[34](?:lstm|gru)_fk_kernel\w+):')):
+    for kname, ins in list(kernels(txt, r'^(_Z1[34](?:lstm|gru)_rr_kernelILi4E\w+):')) + list(kernels(txt, HFP)) + list(kernels(txt, r'^(_Z1[34](?:lstm|gru)_fk_kernel\w+):')):
         fk = "_fk_kernel" in kname
         labels = {m.group(1): i for i, t in enumerate(ins) for m in [re.match(r'(\.LBB\w+):', t)] if m}
         # registers that are ever set to -1 (flow-insensitive: the marks' data registers are constants, set once ahead of the loop or
