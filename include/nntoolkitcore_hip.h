@@ -1029,6 +1029,43 @@ int nntk_ctc_align_device(const float *d_probs, int batch, int T, int C, const i
 int nntk_ctc_align(const float *probs, int batch, int T, int C, const int *input_lengths, const int *labels, const int *label_lengths,
                    int max_label_len, int blank, int *states, int *spans, float *scores);
 
+/* ---- RNN-Transducer (Graves, 2012): loss, gradient and joiner (csrc/hip/rnnt.hip; INTEGRATION.md "RNN-Transducer: loss and joiner") ----
+ *   d_logits [batch][T][max_label_len + 1][V]: UNNORMALISED scores (the vocabulary Dense on top of the joiner, identity activation); the
+ *     log-softmax over V is fused into the call.  Write U_b = label_lengths[b], T_b = input_lengths[b], p = softmax over V, y_u the row's
+ *     u-th label (1-based).  alpha(0, 0) = 1, alpha(t, u) = alpha(t-1, u) p_blank(t-1, u) + alpha(t, u-1) p_{y_u}(t, u-1);
+ *     P_b = alpha(T_b-1, U_b) p_blank(T_b-1, U_b); beta symmetrically, beta(T_b-1, U_b) = p_blank(T_b-1, U_b).  Cells with t >= T_b or
+ *     u > U_b influence nothing and may hold anything, NaN included.
+ *   input_lengths / labels [batch][max_label_len] / label_lengths: HOST memory (input_lengths NULL = every row T), checked before anything
+ *     is enqueued, as are the shape and the pointers -- -1, nntk_last_error() and nothing written for an input length outside [1, T], a
+ *     label length outside [0, max_label_len], a label outside [0, V) or equal to blank, blank outside [0, V), V < 2, a NULL tensor, a
+ *     d_logits / d_dlogits / d_workspace that is not 16-byte aligned, d_dlogits overlapping d_logits -- and copied in stream order.  A
+ *     refusal needs no device.  Repeated labels need no special rule.
+ *   d_loss_rows [batch]: -log P_b, unreduced.  Finite whenever the row's live scores are (the variables and the emissions carry an
+ *     int32 exponent of their own; an emission below 2^-4000 of its cell's total counts as 2^-4000); +inf only through -inf scores.
+ *   d_dlogits or NULL: d loss_b / d logits; per live cell
+ *       alpha(t,u) / P ( p_v beta(t,u) - [v = blank] p_blank beta(t+1,u) - [v = y_{u+1}] p_y beta(t,u+1) ),
+ *     beta(T_b, U_b) standing for 1 in the blank term of the last cell.  Every element is written: exact zeros for t >= T_b or u > U_b
+ *     and for a row with P = 0.
+ *   d_workspace: nntk_rnnt_workspace_floats(batch, T, max_label_len, want_grad) floats, 16-byte aligned: 16 bytes per cell of
+ *     [batch][T][max_label_len + 1], 24 more with a gradient, plus 4 (4 + max_label_len) bytes per row and 16.
+ * Limits: max_label_len <= 4000, T + max_label_len <= 65536.  Deterministic: no atomics, the same bits on every call, the same loss
+ * bits with and without a gradient, a row's bits independent of the other rows and of the T / max_label_len padding.
+ * The host-pointer form uploads, runs the device form and downloads.  All run on the calling thread's current stream.
+ *
+ * Joiner: d_out [batch][T][U1][J] = act(d_enc [batch][T][J] + d_pred [batch][U1][J]); activation 0 identity, 1 tanh (tanhf), 2 relu
+ * (max(x, 0)), the formulas of activation_default.  Backward, from the forward OUTPUT (not read for the identity) and d_dout of the same
+ * shape, overwriting both results: d_denc[b][t][:] = sum over u, ascending, of d_dout act'; d_dpred[b][u][:] = the sum over t, ascending;
+ * one accumulator per element, no atomics.  The vocabulary projection on top is Dense / TimeDistributedDense with batch T U1 rows. */
+size_t nntk_rnnt_workspace_floats(int batch, int T, int max_label_len, int want_grad);
+int nntk_rnnt_loss_device(const float *d_logits, int batch, int T, int V, const int *input_lengths, const int *labels,
+                          const int *label_lengths, int max_label_len, int blank, float *d_loss_rows, float *d_dlogits,
+                          float *d_workspace);
+int nntk_rnnt_loss(const float *logits, int batch, int T, int V, const int *input_lengths, const int *labels, const int *label_lengths,
+                   int max_label_len, int blank, float *loss_rows, float *dlogits);
+int nntk_rnnt_joint_device(const float *d_enc, const float *d_pred, int batch, int T, int U1, int J, int activation, float *d_out);
+int nntk_rnnt_joint_backward_device(const float *d_out_fwd, const float *d_dout, int batch, int T, int U1, int J, int activation,
+                                    float *d_denc, float *d_dpred);
+
 #ifdef __cplusplus
 }
 #endif

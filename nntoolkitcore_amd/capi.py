@@ -455,6 +455,12 @@ SIGNATURES = {
     "nntk_ctc_align_workspace_floats": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "nntk_ctc_align_device": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, ip, ip, ip, C.c_int, C.c_int, vp, vp, vp, vp]),
     "nntk_ctc_align": (C.c_int, [fp, C.c_int, C.c_int, C.c_int, ip, ip, ip, C.c_int, C.c_int, ip, ip, fp]),
+    # RNN-Transducer: loss, gradient with respect to the scores, the joiner (INTEGRATION.md "RNN-Transducer: loss and joiner")
+    "nntk_rnnt_workspace_floats": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "nntk_rnnt_loss_device": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, ip, ip, ip, C.c_int, C.c_int, vp, vp, vp]),
+    "nntk_rnnt_loss": (C.c_int, [fp, C.c_int, C.c_int, C.c_int, ip, ip, ip, C.c_int, C.c_int, fp, fp]),
+    "nntk_rnnt_joint_device": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
+    "nntk_rnnt_joint_backward_device": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),
     # weights from device memory into a handle; the multi-tensor optimizer (INTEGRATION.md "Optimizers")
     "Conv1dLoadWeightsDevice": (C.c_int, [vp, vp]),
     "BatchNormLoadWeightsDevice": (C.c_int, [vp, vp]),

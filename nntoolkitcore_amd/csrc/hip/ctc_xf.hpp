@@ -1,4 +1,4 @@
-// ctc_xf.hpp -- what the CTC units (ctc.hip, ctc_beam.hip, ctc_align.hip) share: the extended-range "xf" arithmetic (an f32 mantissa in [0.5, 1)
+// ctc_xf.hpp -- what the CTC units (ctc.hip, ctc_beam.hip, ctc_align.hip) and the transducer unit (rnnt.hip) share: the extended-range "xf" arithmetic (an f32 mantissa in [0.5, 1)
 // with its own int32 exponent; ctc.hip's header says why), the LDS-only barrier and the LDS ceiling of one workgroup.
 #pragma once
 #include "nntk_common.hpp"
@@ -27,6 +27,10 @@ __device__ __forceinline__ xf xf_times_prob(xf v, float p) {
     // the probability as mantissa and exponent too: a denormal p keeps its bits
     return xf_norm(v.m * __builtin_amdgcn_frexp_mantf(p), v.e + __builtin_amdgcn_frexp_expf(p));
 }
+// v times a factor that is itself mantissa and exponent (rnnt.hip: an emission far below what an f32 holds)
+__device__ __forceinline__ xf xf_times(xf v, xf p) { return xf_norm(v.m * p.m, v.e + p.e); }
+// the value as a plain f32 scaled by 2^-e0 (0 below the f32 range)
+__device__ __forceinline__ float xf_to_float(xf v, int e0) { return ldexpf(v.m, max(v.e - e0, -1000)); }
 // a > b: exponent first, then mantissa (both normalised, neither negative); zero, with the lowest exponent, is below everything
 __device__ __forceinline__ bool xf_greater(xf a, xf b) { return a.e > b.e || (a.e == b.e && a.m > b.m); }
 __device__ __forceinline__ float2 xf_pack(xf v) { return make_float2(v.m, __int_as_float(v.e)); }

@@ -198,6 +198,18 @@ size_t nntk_shim_ctc_align_workspace_floats(int batch, int T, int max_label_len)
 int nntk_shim_ctc_align(const float *d_probs, int B, int T, int C, const int *h_input_lengths, const int *h_labels,
                         const int *h_label_lengths, int max_label_len, int blank, int *d_states, int *d_spans, float *d_scores,
                         float *d_ws);
+/* the transducer kernels' limits, stated here once for the host's checks (rnnt.c) and the launcher */
+#define NNTK_RNNT_MAX_LABELS 4000               /* max_label_len: two diagonals of max_label_len + 1 cells, 16 bytes each, live in LDS */
+#define NNTK_RNNT_MAX_DIAGONALS 65536           /* T + max_label_len: the exponents of that many emissions (each >= -4000) sum inside 2^28 */
+/* ---- RNN-Transducer (rnnt.hip): loss rows and the gradient with respect to the unnormalised scores [B][T][max_label_len + 1][V]; the
+ *      joiner and its backward.  The int arrays are HOST memory, already checked by the caller (rnnt.c), never NULL, copied in stream
+ *      order; d_dlogits NULL = loss only; the tensors and d_ws 16-byte aligned, nntk_shim_rnnt_workspace_floats words ---- */
+size_t nntk_shim_rnnt_workspace_floats(int batch, int T, int max_label_len, int want_grad);
+int nntk_shim_rnnt_loss(const float *d_logits, int B, int T, int V, const int *h_input_lengths, const int *h_labels,
+                        const int *h_label_lengths, int max_label_len, int blank, float *d_loss_rows, float *d_dlogits, float *d_ws);
+int nntk_shim_rnnt_joint(const float *d_enc, const float *d_pred, int B, int T, int U1, int J, int kind, float *d_out);
+int nntk_shim_rnnt_joint_backward(const float *d_out_fwd, const float *d_dout, int B, int T, int U1, int J, int kind, float *d_denc,
+                                  float *d_dpred);
 /* BatchNorm training (batch_norm.c:191-386): x, d_out [N, F]; d_block = gamma | beta | ...; d_stats [8][F] = mean | variance |
  * var_eps | sqrt_var | d_beta | d_gamma | d_var | d_mu; d_partial [slices][3][F] with slices from nntk_shim_bn_train_slices */
 /* Ragged batches and carried state for the recurrent training launchers below (the *VarLen training calls; a NULL pointer to it = the

@@ -1,0 +1,412 @@
+// rnnt.hip -- the RNN-Transducer (Graves, 2012): the per-row negative log-likelihood over the lattice of unnormalised scores
+// [B][T][U1 = max_label_len + 1][V], its gradient with respect to those scores, and the joiner that makes the tensor the scores are
+// projected from (out = act(enc[b][t] + pred[b][u])) with its backward.
+//
+// Range.  alpha(t, u) sums binomial(t + u, u) paths of t + u emissions each: like the CTC variables it is an f32 mantissa with an int32
+// exponent of its own (ctc_xf.hpp).  The emissions exp(x - lse) are carried the same way, straight from the base-2 logarithm -- mantissa
+// exp2(frac), exponent floor -- so a label 170 bits below its cell's maximum still has all its mantissa bits; the exponent is floored at
+// RNNT_EMIN, which keeps every sum of T + U exponents inside an int32 and above CTC_EZERO (a finite score never becomes a zero).
+//
+// Work split, three launches; the score tensor is read twice and the gradient written once.
+//  rnnt_emit_kernel: a wavefront per live cell: maximum, then the sum of exp(x - max) accumulated in double (the second read of the row
+//    comes from the cache).  Kept per cell: the blank's and the next label's emission (16 bytes) and, for the gradient, lse as a double.
+//  rnnt_lattice_kernel: one 256-lane workgroup per (row, direction) -- blockIdx.y = 0 runs alpha over the anti-diagonals t + u = n
+//    upwards, 1 runs beta downwards, concurrently -- lanes over u (a lane owns u = tid, tid + 256, ...).  The previous diagonal sits in
+//    double-buffered LDS, one LDS-only barrier per diagonal; the emissions of the NEXT diagonal's cells are loaded before the barrier.
+//    P = alpha(T-1, U) p_blank(T-1, U) comes out of the forward direction alone: the loss bits do not depend on whether a gradient is asked.
+//  rnnt_grad_kernel: a wavefront per cell: three scalars from alpha, beta, the emissions and P (the occupancy A = alpha beta / P, and
+//    the two outgoing flows), then V scores in and g[v] = A exp(x[v] - lse) - [v = blank] flow_blank - [v = label] flow_label out.
+//    Padding cells (t >= T_b or u > U_b) are zero-filled with 16-byte stores.
+// No atomics anywhere; every reduction is a fixed butterfly or a fixed-order loop.
+#include <stdint.h>
+#include "nntk_common.hpp"
+#include "ctc_xf.hpp"
+
+#define RNNT_EMIN (-4000)                 // floor of an emission's base-2 exponent: NNTK_RNNT_MAX_DIAGONALS * 4000 < 2^28 = -CTC_EZERO
+#define RNNT_MAX_GRID (1 << 20)
+#define RNNT_JOINT_UNROLL 4               // terms of a joiner-backward sum loaded together (added in ascending order all the same)
+
+// workspace, in 4-byte words: [ints: input lengths B | label lengths B | labels B*maxL] [P per row: 2B] [emissions: 4 per cell]
+// with a gradient: [lse: 2 per cell] [alpha: 2 per cell] [beta: 2 per cell]; every part starts on a 16-byte boundary
+struct RnntLayout { size_t hdr, em, lse, alpha, beta, total; };
+static RnntLayout rnnt_layout(int B, int T, int maxL, int want_grad) {
+    RnntLayout l;
+    const size_t b = B > 0 ? (size_t)B : 0, t = T > 0 ? (size_t)T : 0, ml = maxL > 0 ? (size_t)maxL : 0;
+    auto up = [](size_t x) { return (x + 3) & ~(size_t)3; };
+    const size_t cells = b * t * (ml + 1);
+    l.hdr = up(b * (2 + ml));
+    l.em = l.hdr + up(2 * b);
+    l.lse = l.em + 4 * cells;
+    l.alpha = l.lse + (want_grad ? up(2 * cells) : 0);
+    l.beta = l.alpha + (want_grad ? up(2 * cells) : 0);
+    l.total = l.beta + (want_grad ? up(2 * cells) : 0) + 4;
+    return l;
+}
+
+__device__ __forceinline__ float rnnt_wave_max(float v) {
+    for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off));
+    return v;
+}
+__device__ __forceinline__ double rnnt_wave_sum(double v) {
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+    return v;
+}
+
+// exp(x - lse) as mantissa and exponent; -inf (and NaN) scores: zero
+__device__ __forceinline__ xf rnnt_emission(float x, double lse) {
+    if (!(x > -INFINITY)) return xf_zero();
+    double l2 = ((double)x - lse) * 1.44269504088896340736;
+    l2 = l2 < (double)RNNT_EMIN ? (double)RNNT_EMIN : l2;
+    const double fl = floor(l2);
+    return xf_norm(exp2f((float)(l2 - fl)), (int)fl);
+}
+
+// cell c = (b * T + t) * U1 + u
+struct RnntCell { int b, t, u; };
+__device__ __forceinline__ RnntCell rnnt_cell(long c, int T, int U1) {
+    RnntCell r;
+    const long bt = c / U1;
+    r.u = (int)(c - bt * U1);
+    r.b = (int)(bt / T);
+    r.t = (int)(bt - (long)r.b * T);
+    return r;
+}
+
+// VEC: V % 4 == 0 and the tensor 16-byte aligned, so every row is: 16-byte loads
+template <bool VEC>
+__global__ __launch_bounds__(CTC_THREADS) void rnnt_emit_kernel(const float *__restrict__ logits, int B, int T, int U1, int V, int blank,
+                                                                const int *__restrict__ ints, float4 *__restrict__ em,
+                                                                double *__restrict__ lse_out, long cells) {
+    const int lane = threadIdx.x & 63;
+    for (long c = blockIdx.x * 4L + (threadIdx.x >> 6); c < cells; c += gridDim.x * 4L) {
+        const RnntCell q = rnnt_cell(c, T, U1);
+        const int Ub = ints[B + q.b];
+        if (q.t >= ints[q.b] || q.u > Ub) continue;
+        const float *row = logits + c * V;
+        const f32x4 *row4 = (const f32x4 *)row;
+        float mx = -INFINITY;
+        if (VEC) {
+            for (int i = lane; i < (V >> 2); i += 64) {
+                const f32x4 x = row4[i];
+                mx = fmaxf(mx, fmaxf(fmaxf(x[0], x[1]), fmaxf(x[2], x[3])));
+            }
+        } else {
+            for (int k = lane; k < V; k += 64) mx = fmaxf(mx, row[k]);
+        }
+        mx = rnnt_wave_max(mx);
+        double s = 0.0;
+        if (VEC) {
+            for (int i = lane; i < (V >> 2); i += 64) {
+                const f32x4 x = row4[i];
+                s += (double)expf(x[0] - mx);
+                s += (double)expf(x[1] - mx);
+                s += (double)expf(x[2] - mx);
+                s += (double)expf(x[3] - mx);
+            }
+        } else {
+            for (int k = lane; k < V; k += 64) s += (double)expf(row[k] - mx);
+        }
+        s = rnnt_wave_sum(s);
+        if (lane == 0) {
+            const double lse = (double)mx + log(s);
+            const xf pb = rnnt_emission(row[blank], lse);
+            const xf py = q.u < Ub ? rnnt_emission(row[ints[2L * B + (long)q.b * (U1 - 1) + q.u]], lse) : xf_zero();
+            em[c] = make_float4(pb.m, __int_as_float(pb.e), py.m, __int_as_float(py.e));
+            if (lse_out) lse_out[c] = lse;
+        }
+    }
+}
+
+// NJ > 0: a lane's cells of a diagonal (at most NJ) take their emissions from registers, loaded one diagonal ahead; NJ = 0: any U1
+// that fits the LDS, emissions fetched inside the step.  LDS per u: forward, alpha p_blank | alpha p_label of the lane's cell -- what
+// flows on to (t + 1, u) and to (t, u + 1); backward, beta itself.
+template <int NJ>
+__global__ __launch_bounds__(CTC_THREADS) void rnnt_lattice_kernel(int B, int T, int U1, const int *__restrict__ ints,
+                                                                   const float4 *__restrict__ em, float2 *ws_alpha, float2 *ws_beta,
+                                                                   float *hdr, float *loss_rows) {
+    extern __shared__ __align__(16) unsigned char rnnt_smem[];
+    float4 *st = (float4 *)rnnt_smem;                                       // [2][U1]
+    const int b = blockIdx.x, dir = blockIdx.y, tid = threadIdx.x;
+    const int Tb = ints[b], Ub = ints[B + b];
+    const long base = (long)b * T * U1;
+    const float4 *e = em + base;
+    float2 *ws = dir ? ws_beta : ws_alpha;
+    if (ws) ws += base;
+    const int ND = Tb + Ub;                                                 // diagonals n = t + u = 0 .. ND - 1
+    constexpr int NR = NJ > 0 ? NJ : 1;
+    const float4 none = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    auto live = [&](int n, int u) { return u <= Ub && n - u >= 0 && n - u < Tb; };
+    float4 en[NR];
+    if (NJ > 0) {
+        const int n0 = dir ? ND - 1 : 0;
+#pragma unroll
+        for (int j = 0; j < NR; ++j) {
+            const int u = tid + CTC_THREADS * j;
+            en[j] = none;
+            if (live(n0, u)) en[j] = e[(long)(n0 - u) * U1 + u];
+        }
+    }
+    int cur = 0;
+    for (int i = 0; i < ND; ++i) {
+        const int n = dir ? ND - 1 - i : i;
+        float4 ec[NR];
+        if (NJ > 0) {
+#pragma unroll
+            for (int j = 0; j < NR; ++j) ec[j] = en[j];
+            if (i + 1 < ND) {                                               // the next diagonal's emissions: not on the dependent chain
+                const int nn = dir ? n - 1 : n + 1;
+#pragma unroll
+                for (int j = 0; j < NR; ++j) {
+                    const int u = tid + CTC_THREADS * j;
+                    en[j] = none;
+                    if (live(nn, u)) en[j] = e[(long)(nn - u) * U1 + u];
+                }
+            }
+        }
+        const float4 *src = st + cur * U1;
+        float4 *dst = st + (cur ^ 1) * U1;
+        auto cell = [&](int u, float4 e4) {
+            const int t = n - u;
+            xf pb, py;
+            pb.m = e4.x; pb.e = __float_as_int(e4.y);
+            py.m = e4.z; py.e = __float_as_int(e4.w);
+            if (dir == 0) {
+                xf a;
+                if (n == 0) {
+                    a = xf_one();
+                } else {                                                    // from (t - 1, u) by a blank, then from (t, u - 1) by label u
+                    const xf ft = t >= 1 ? xf_unpack(make_float2(src[u].x, src[u].y)) : xf_zero();
+                    const xf fu = u >= 1 ? xf_unpack(make_float2(src[u - 1].z, src[u - 1].w)) : xf_zero();
+                    a = xf_add3(ft, fu, xf_zero());
+                }
+                if (ws) ws[(long)t * U1 + u] = xf_pack(a);
+                const xf ab = xf_times(a, pb), ay = xf_times(a, py);
+                dst[u] = make_float4(ab.m, __int_as_float(ab.e), ay.m, __int_as_float(ay.e));
+                if (i == ND - 1) {                                          // the one cell of the last diagonal: (Tb - 1, Ub)
+                    hdr[2 * b] = ab.m;
+                    hdr[2 * b + 1] = __int_as_float(ab.e);
+                    // once per row: double, libm log
+                    loss_rows[b] = ab.m == 0.0f ? INFINITY : (float)-((double)ab.e * 0.69314718055994530942 + log((double)ab.m));
+                }
+            } else {                                                        // beta(Tb, Ub) stands for 1; beta(Tb, u < Ub) and beta(t, Ub + 1) are 0
+                const xf bt = t + 1 < Tb ? xf_unpack(make_float2(src[u].x, src[u].y)) : u == Ub ? xf_one() : xf_zero();
+                const xf bu = u < Ub ? xf_unpack(make_float2(src[u + 1].x, src[u + 1].y)) : xf_zero();
+                const xf v = xf_add3(xf_times(bt, pb), xf_times(bu, py), xf_zero());
+                ws[(long)t * U1 + u] = xf_pack(v);
+                dst[u] = make_float4(v.m, __int_as_float(v.e), 0.0f, 0.0f);
+            }
+        };
+        if (NJ > 0) {
+#pragma unroll
+            for (int j = 0; j < NR; ++j)
+                if (live(n, tid + CTC_THREADS * j)) cell(tid + CTC_THREADS * j, ec[j]);
+        } else {
+            for (int u = tid; u <= Ub; u += CTC_THREADS)
+                if (live(n, u)) cell(u, e[(long)(n - u) * U1 + u]);
+        }
+        CTC_LDS_BARRIER();
+        cur ^= 1;
+    }
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(CTC_THREADS) void rnnt_grad_kernel(const float *__restrict__ logits, int B, int T, int U1, int V, int blank,
+                                                                const int *__restrict__ ints, const float4 *__restrict__ em,
+                                                                const double *__restrict__ lse_in, const float2 *__restrict__ wa,
+                                                                const float2 *__restrict__ wb, const float *__restrict__ hdr,
+                                                                float *__restrict__ dlogits, long cells) {
+    const int lane = threadIdx.x & 63;
+    for (long c = blockIdx.x * 4L + (threadIdx.x >> 6); c < cells; c += gridDim.x * 4L) {
+        const RnntCell q = rnnt_cell(c, T, U1);
+        const int Tb = ints[q.b], Ub = ints[B + q.b];
+        float *g = dlogits + c * V;
+        const float mP = hdr[2 * q.b];
+        if (q.t >= Tb || q.u > Ub || !(mP > 0.0f)) {                        // padding, or a row no path reaches (P = 0): zeros
+            const int head = min(V, (int)((4 - (((uintptr_t)g >> 2) & 3)) & 3));
+            const int quads = (V - head) >> 2;
+            if (lane < head) g[lane] = 0.0f;
+            f32x4 *g4 = (f32x4 *)(g + head);
+            const f32x4 z = {0.0f, 0.0f, 0.0f, 0.0f};
+            for (int i = lane; i < quads; i += 64) g4[i] = z;
+            const int done = head + 4 * quads;
+            if (lane < V - done) g[done + lane] = 0.0f;
+            continue;
+        }
+        const int eP = __float_as_int(hdr[2 * q.b + 1]);
+        const xf a = xf_unpack(wa[c]);
+        const float4 e4 = em[c];
+        xf pb, py;
+        pb.m = e4.x; pb.e = __float_as_int(e4.y);
+        py.m = e4.z; py.e = __float_as_int(e4.w);
+        const float occ = xf_to_float(xf_times(a, xf_unpack(wb[c])), eP) / mP;                    // alpha beta / P
+        const xf bt = q.t + 1 < Tb ? xf_unpack(wb[c + U1]) : q.u == Ub ? xf_one() : xf_zero();
+        const float fb = xf_to_float(xf_times(xf_times(a, pb), bt), eP) / mP;                    // alpha p_blank beta(t + 1, u) / P
+        float fy = 0.0f;
+        int y = -1;
+        if (q.u < Ub) {
+            y = ints[2L * B + (long)q.b * (U1 - 1) + q.u];
+            fy = xf_to_float(xf_times(xf_times(a, py), xf_unpack(wb[c + 1])), eP) / mP;           // alpha p_label beta(t, u + 1) / P
+        }
+        const double lse = lse_in[c];
+        const float *row = logits + c * V;
+        auto grad = [&](float x, int v) {
+            float r = occ * expf((float)((double)x - lse));
+            if (v == blank) r -= fb;
+            if (v == y) r -= fy;
+            return r;
+        };
+        if (VEC) {
+            const f32x4 *row4 = (const f32x4 *)row;
+            f32x4 *g4 = (f32x4 *)g;
+            for (int i = lane; i < (V >> 2); i += 64) {
+                const f32x4 x = row4[i];
+                f32x4 r;
+                r[0] = grad(x[0], 4 * i);
+                r[1] = grad(x[1], 4 * i + 1);
+                r[2] = grad(x[2], 4 * i + 2);
+                r[3] = grad(x[3], 4 * i + 3);
+                g4[i] = r;
+            }
+        } else {
+            for (int k = lane; k < V; k += 64) g[k] = grad(row[k], k);
+        }
+    }
+}
+
+// ---- the joiner: out[b][t][u][:] = act(enc[b][t][:] + pred[b][u][:]); activation 0 identity, 1 tanh (tanhf), 2 relu (max(x, 0)) ----
+__device__ __forceinline__ float rnnt_act(int kind, float x) { return kind == 1 ? tanhf(x) : kind == 2 ? fmaxf(x, 0.0f) : x; }
+// d act / d x from the activation's OUTPUT
+__device__ __forceinline__ float rnnt_dact(int kind, float o) { return kind == 1 ? 1.0f - o * o : kind == 2 ? (o > 0.0f ? 1.0f : 0.0f) : 1.0f; }
+
+// W = 4: J % 4 == 0 and the three tensors 16-byte aligned; n = elements / W
+template <int W>
+__global__ __launch_bounds__(256) void rnnt_joint_kernel(const float *__restrict__ enc, const float *__restrict__ pred, int T, int U1, int JW,
+                                                         int kind, float *__restrict__ out, long n) {
+    for (long i = blockIdx.x * 256L + threadIdx.x; i < n; i += gridDim.x * 256L) {
+        const long cell = i / JW;
+        const int j = (int)(i - cell * JW);
+        const long bt = cell / U1;
+        const int u = (int)(cell - bt * U1);
+        const long bu = bt / T * U1 + u;
+        if (W == 4) {
+            const f32x4 a = ((const f32x4 *)enc)[bt * JW + j], p = ((const f32x4 *)pred)[bu * JW + j];
+            f32x4 r;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) r[k] = rnnt_act(kind, a[k] + p[k]);
+            ((f32x4 *)out)[i] = r;
+        } else {
+            out[i] = rnnt_act(kind, enc[bt * JW + j] + pred[bu * JW + j]);
+        }
+    }
+}
+
+// dst[o][r] = sum over k < R, ascending, of dout[o * ostride + k * rstride + r] * act'(out[the same]); one accumulator per element.
+// d_enc: o = (b, t), r = j, k = u; d_pred: o = b, r = (u, j), k = t
+__global__ __launch_bounds__(256) void rnnt_joint_reduce_kernel(const float *__restrict__ out, const float *__restrict__ dout, long n, long M,
+                                                                long ostride, int R, long rstride, int kind, float *__restrict__ dst) {
+    for (long i = blockIdx.x * 256L + threadIdx.x; i < n; i += gridDim.x * 256L) {
+        const long o = i / M;
+        const long at = o * ostride + (i - o * M);
+        float acc = 0.0f;
+        int k = 0;
+        for (; k + RNNT_JOINT_UNROLL <= R; k += RNNT_JOINT_UNROLL) {
+            float d[RNNT_JOINT_UNROLL], f[RNNT_JOINT_UNROLL];
+#pragma unroll
+            for (int w = 0; w < RNNT_JOINT_UNROLL; ++w) {
+                d[w] = dout[at + (k + w) * rstride];
+                f[w] = kind ? out[at + (k + w) * rstride] : 0.0f;
+            }
+#pragma unroll
+            for (int w = 0; w < RNNT_JOINT_UNROLL; ++w) acc += d[w] * rnnt_dact(kind, f[w]);
+        }
+        for (; k < R; ++k) acc += dout[at + k * rstride] * rnnt_dact(kind, kind ? out[at + k * rstride] : 0.0f);
+        dst[i] = acc;
+    }
+}
+
+static unsigned rnnt_grid(long items, long per_block) {
+    long g = (items + per_block - 1) / per_block;
+    return (unsigned)(g < 1 ? 1 : g > RNNT_MAX_GRID ? RNNT_MAX_GRID : g);
+}
+
+extern "C" {
+
+size_t nntk_shim_rnnt_workspace_floats(int batch, int T, int max_label_len, int want_grad) {
+    return rnnt_layout(batch, T, max_label_len, want_grad).total;
+}
+
+int nntk_shim_rnnt_loss(const float *d_logits, int B, int T, int V, const int *h_input_lengths, const int *h_labels,
+                        const int *h_label_lengths, int maxL, int blank, float *d_loss_rows, float *d_dlogits, float *d_ws) {
+    if (B <= 0) return 0;
+    if (maxL > NNTK_RNNT_MAX_LABELS || (long)T + maxL > NNTK_RNNT_MAX_DIAGONALS)
+        return nntk_fail_msg("nntk_rnnt_loss_device: max_label_len or T + max_label_len is beyond the lattice kernel's limits");
+    if ((((uintptr_t)d_ws | (uintptr_t)d_logits | (uintptr_t)d_dlogits) & 15) != 0)
+        return nntk_fail_msg("nntk_rnnt_loss_device: the tensors and the workspace must be 16-byte aligned");
+    const int U1 = maxL + 1;
+    const RnntLayout lay = rnnt_layout(B, T, maxL, d_dlogits != nullptr);
+    const long cells = (long)B * T * U1;
+    int *d_ints = (int *)d_ws;
+    if (nntk_shim_upload_ints(d_ints, h_input_lengths, B)) return -1;
+    if (nntk_shim_upload_ints(d_ints + B, h_label_lengths, B)) return -1;
+    if (maxL > 0 && nntk_shim_upload_ints(d_ints + 2L * B, h_labels, (long)B * maxL)) return -1;
+    float *hdr = d_ws + lay.hdr;
+    float4 *em = (float4 *)(d_ws + lay.em);
+    double *lse = d_dlogits ? (double *)(d_ws + lay.lse) : nullptr;
+    float2 *wa = d_dlogits ? (float2 *)(d_ws + lay.alpha) : nullptr, *wb = d_dlogits ? (float2 *)(d_ws + lay.beta) : nullptr;
+    const bool vec = (V & 3) == 0;
+    const dim3 cgrid(rnnt_grid(cells, 4));
+    if (vec)
+        hipLaunchKernelGGL(rnnt_emit_kernel<true>, cgrid, dim3(CTC_THREADS), 0, nntk_stream(), d_logits, B, T, U1, V, blank, d_ints, em, lse, cells);
+    else
+        hipLaunchKernelGGL(rnnt_emit_kernel<false>, cgrid, dim3(CTC_THREADS), 0, nntk_stream(), d_logits, B, T, U1, V, blank, d_ints, em, lse, cells);
+    NNTK_LAUNCH_CHECK("rnnt_emit_kernel");
+    const size_t lds = 2 * (size_t)U1 * sizeof(float4);
+    const dim3 grid((unsigned)B, d_dlogits ? 2 : 1);
+#define RNNT_AB(NJ)                                                                                                          \
+    do {                                                                                                                     \
+        if (lds > 48 * 1024 && nntk_set_max_dynamic_lds((const void *)rnnt_lattice_kernel<NJ>, lds)) return -1;               \
+        hipLaunchKernelGGL(rnnt_lattice_kernel<NJ>, grid, dim3(CTC_THREADS), lds, nntk_stream(), B, T, U1, d_ints, em, wa, wb, \
+                           hdr, d_loss_rows);                                                                                \
+    } while (0)
+    if (U1 <= CTC_THREADS) RNNT_AB(1);
+    else if (U1 <= 2 * CTC_THREADS) RNNT_AB(2);
+    else RNNT_AB(0);
+#undef RNNT_AB
+    NNTK_LAUNCH_CHECK("rnnt_lattice_kernel");
+    if (d_dlogits) {
+        if (vec)
+            hipLaunchKernelGGL(rnnt_grad_kernel<true>, cgrid, dim3(CTC_THREADS), 0, nntk_stream(), d_logits, B, T, U1, V, blank, d_ints, em, lse,
+                               wa, wb, hdr, d_dlogits, cells);
+        else
+            hipLaunchKernelGGL(rnnt_grad_kernel<false>, cgrid, dim3(CTC_THREADS), 0, nntk_stream(), d_logits, B, T, U1, V, blank, d_ints, em, lse,
+                               wa, wb, hdr, d_dlogits, cells);
+        NNTK_LAUNCH_CHECK("rnnt_grad_kernel");
+    }
+    return 0;
+}
+
+int nntk_shim_rnnt_joint(const float *d_enc, const float *d_pred, int B, int T, int U1, int J, int kind, float *d_out) {
+    const long n = (long)B * T * U1 * J;
+    if (n <= 0) return 0;
+    if ((J & 3) == 0 && (((uintptr_t)d_enc | (uintptr_t)d_pred | (uintptr_t)d_out) & 15) == 0)
+        hipLaunchKernelGGL(rnnt_joint_kernel<4>, dim3(rnnt_grid(n / 4, 256)), dim3(256), 0, nntk_stream(), d_enc, d_pred, T, U1, J / 4, kind,
+                           d_out, n / 4);
+    else
+        hipLaunchKernelGGL(rnnt_joint_kernel<1>, dim3(rnnt_grid(n, 256)), dim3(256), 0, nntk_stream(), d_enc, d_pred, T, U1, J, kind, d_out, n);
+    NNTK_LAUNCH_CHECK("rnnt_joint_kernel");
+    return 0;
+}
+
+int nntk_shim_rnnt_joint_backward(const float *d_out_fwd, const float *d_dout, int B, int T, int U1, int J, int kind, float *d_denc,
+                                  float *d_dpred) {
+    if ((long)B * T * U1 * J <= 0) return 0;
+    const long ne = (long)B * T * J, np = (long)B * U1 * J;
+    hipLaunchKernelGGL(rnnt_joint_reduce_kernel, dim3(rnnt_grid(ne, 256)), dim3(256), 0, nntk_stream(), d_out_fwd, d_dout, ne, (long)J,
+                       (long)U1 * J, U1, (long)J, kind, d_denc);
+    hipLaunchKernelGGL(rnnt_joint_reduce_kernel, dim3(rnnt_grid(np, 256)), dim3(256), 0, nntk_stream(), d_out_fwd, d_dout, np, (long)U1 * J,
+                       (long)T * U1 * J, T, (long)U1 * J, kind, d_dpred);
+    NNTK_LAUNCH_CHECK("rnnt_joint_reduce_kernel");
+    return 0;
+}
+
+}  // extern "C"

@@ -1,0 +1,131 @@
+/*
+ * rnnt.c -- host layer of the RNN-Transducer calls (csrc/hip/rnnt.hip): the loss over the [batch][T][max_label_len + 1][V] lattice of
+ * unnormalised scores with its gradient, and the joiner with its backward.  Every host array, shape, limit and pointer is checked
+ * here, before anything is enqueued or allocated: a refusal needs no device.  The loss has a device-pointer form and a host-pointer
+ * form (upload, device call, download).
+ */
+#include <stdint.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include "nntk_internal.h"
+
+#define t_a (*nntk_thread_scratch(NNTK_TS_A))
+#define t_b (*nntk_thread_scratch(NNTK_TS_B))
+#define t_c (*nntk_thread_scratch(NNTK_TS_C))
+
+static int rnnt_fail(const char *who, const char *fmt, int a, int b, int c) {
+    char msg[200];
+    int n = snprintf(msg, sizeof msg, "%s: ", who);
+    snprintf(msg + n, sizeof msg - (size_t)n, fmt, a, b, c);
+    nntk_set_error(msg);
+    return -1;
+}
+
+/* everything that lives in host memory, and the limits of the kernels */
+static int rnnt_check(const char *who, int batch, int T, int V, const int *input_lengths, const int *labels, const int *label_lengths,
+                      int max_label_len, int blank) {
+    if (batch < 0 || T < 0 || max_label_len < 0)
+        return rnnt_fail(who, "batch %d, T %d, max_label_len %d: none may be negative", batch, T, max_label_len);
+    if (V < 2) return rnnt_fail(who, "V %d < 2: a transducer has the blank and at least one label", V, 0, 0);
+    if (blank < 0 || blank >= V) return rnnt_fail(who, "blank %d is outside [0, %d)", blank, V, 0);
+    if (max_label_len > NNTK_RNNT_MAX_LABELS)
+        return rnnt_fail(who, "max_label_len %d is beyond what one workgroup's LDS holds (%d)", max_label_len, NNTK_RNNT_MAX_LABELS, 0);
+    if ((long long)T + max_label_len > NNTK_RNNT_MAX_DIAGONALS)
+        return rnnt_fail(who, "T + max_label_len = %d is more than %d lattice diagonals", T + max_label_len, NNTK_RNNT_MAX_DIAGONALS, 0);
+    if (batch > 0 && (!label_lengths || (max_label_len > 0 && !labels))) return rnnt_fail(who, "NULL labels / label_lengths", 0, 0, 0);
+    if (batch > 0 && T < 1) return rnnt_fail(who, "T %d < 1", T, 0, 0);
+    for (int b = 0; b < batch; ++b) {
+        if (input_lengths && (input_lengths[b] < 1 || input_lengths[b] > T))
+            return rnnt_fail(who, "input_lengths[%d] = %d is outside [1, %d]", b, input_lengths[b], T);
+        const int L = label_lengths[b];
+        if (L < 0 || L > max_label_len) return rnnt_fail(who, "label_lengths[%d] = %d is outside [0, %d]", b, L, max_label_len);
+        for (int i = 0; i < L; ++i) {
+            const int k = labels[(size_t)b * max_label_len + i];
+            if (k < 0 || k >= V) return rnnt_fail(who, "labels[%d][%d] = %d is not a class", b, i, k);
+            if (k == blank) return rnnt_fail(who, "labels[%d][%d] is the blank (%d)", b, i, k);
+        }
+    }
+    return 0;
+}
+
+static int rnnt_check_ptr(const char *who, const char *name, const void *p, unsigned align) {
+    char msg[200];
+    if (p && ((uintptr_t)p & (align - 1)) == 0) return 0;
+    if (p) snprintf(msg, sizeof msg, "%s: %s is not %u-byte aligned", who, name, align);
+    else snprintf(msg, sizeof msg, "%s: %s is NULL", who, name);
+    nntk_set_error(msg);
+    return -1;
+}
+
+size_t nntk_rnnt_workspace_floats(int batch, int T, int max_label_len, int want_grad) {
+    return nntk_shim_rnnt_workspace_floats(batch, T, max_label_len, want_grad != 0);
+}
+
+int nntk_rnnt_loss_device(const float *d_logits, int batch, int T, int V, const int *input_lengths, const int *labels,
+                          const int *label_lengths, int max_label_len, int blank, float *d_loss_rows, float *d_dlogits,
+                          float *d_workspace) {
+    static const char who[] = "nntk_rnnt_loss_device";
+    nntk_shim_clear_error();
+    if (rnnt_check(who, batch, T, V, input_lengths, labels, label_lengths, max_label_len, blank)) return -1;
+    if (batch == 0) return 0;
+    if (rnnt_check_ptr(who, "d_logits", d_logits, 16) || rnnt_check_ptr(who, "d_loss_rows", d_loss_rows, 4) ||
+        rnnt_check_ptr(who, "d_workspace", d_workspace, 16) || (d_dlogits && rnnt_check_ptr(who, "d_dlogits", d_dlogits, 16))) return -1;
+    const size_t bytes = (size_t)batch * T * (max_label_len + 1) * V * sizeof(float);
+    if (d_dlogits && (uintptr_t)d_dlogits < (uintptr_t)d_logits + bytes && (uintptr_t)d_logits < (uintptr_t)d_dlogits + bytes)
+        return rnnt_fail(who, "d_dlogits overlaps d_logits", 0, 0, 0);
+    int *len = (int *)malloc((size_t)batch * sizeof(int));
+    if (!len) NNTK_FAIL("out of host memory");
+    for (int b = 0; b < batch; ++b) len[b] = input_lengths ? input_lengths[b] : T;
+    int rc = nntk_shim_rnnt_loss(d_logits, batch, T, V, len, labels, label_lengths, max_label_len, blank, d_loss_rows, d_dlogits,
+                                 d_workspace);
+    free(len);
+    return rc;
+}
+
+int nntk_rnnt_loss(const float *logits, int batch, int T, int V, const int *input_lengths, const int *labels, const int *label_lengths,
+                   int max_label_len, int blank, float *loss_rows, float *dlogits) {
+    static const char who[] = "nntk_rnnt_loss";
+    nntk_shim_clear_error();
+    if (rnnt_check(who, batch, T, V, input_lengths, labels, label_lengths, max_label_len, blank)) return -1;
+    if (batch == 0) return 0;
+    if (rnnt_check_ptr(who, "logits", logits, 4) || rnnt_check_ptr(who, "loss_rows", loss_rows, 4) ||
+        (dlogits && rnnt_check_ptr(who, "dlogits", dlogits, 4))) return -1;
+    const size_t n = (size_t)batch * T * (max_label_len + 1) * V;
+    float *d_x = nntk_devbuf_reserve(&t_a, n + (size_t)batch + 4);
+    float *d_g = dlogits ? nntk_devbuf_reserve(&t_b, n + 4) : NULL;
+    float *d_ws = nntk_devbuf_reserve(&t_c, nntk_shim_rnnt_workspace_floats(batch, T, max_label_len, dlogits != NULL));
+    if (!d_x || (dlogits && !d_g) || !d_ws) return -1;
+    float *d_loss = d_x + n;
+    if (nntk_shim_upload(d_x, logits, n * sizeof(float))) return -1;
+    if (nntk_rnnt_loss_device(d_x, batch, T, V, input_lengths, labels, label_lengths, max_label_len, blank, d_loss, d_g, d_ws)) return -1;
+    if (nntk_shim_download(loss_rows, d_loss, (size_t)batch * sizeof(float))) return -1;
+    return dlogits ? nntk_shim_download(dlogits, d_g, n * sizeof(float)) : 0;
+}
+
+/* ---- the joiner ---- */
+static int joint_check(const char *who, int batch, int T, int U1, int J, int activation) {
+    if (batch < 0 || T < 0 || U1 < 0) return rnnt_fail(who, "batch %d, T %d, U1 %d: none may be negative", batch, T, U1);
+    if (J < 0) return rnnt_fail(who, "J %d < 0", J, 0, 0);
+    if (activation < 0 || activation > 2) return rnnt_fail(who, "activation %d is none of 0 (identity), 1 (tanh), 2 (relu)", activation, 0, 0);
+    return 0;
+}
+
+int nntk_rnnt_joint_device(const float *d_enc, const float *d_pred, int batch, int T, int U1, int J, int activation, float *d_out) {
+    static const char who[] = "nntk_rnnt_joint_device";
+    nntk_shim_clear_error();
+    if (joint_check(who, batch, T, U1, J, activation)) return -1;
+    if ((size_t)batch * T * U1 * J == 0) return 0;
+    if (rnnt_check_ptr(who, "d_enc", d_enc, 4) || rnnt_check_ptr(who, "d_pred", d_pred, 4) || rnnt_check_ptr(who, "d_out", d_out, 4)) return -1;
+    return nntk_shim_rnnt_joint(d_enc, d_pred, batch, T, U1, J, activation, d_out);
+}
+
+int nntk_rnnt_joint_backward_device(const float *d_out_fwd, const float *d_dout, int batch, int T, int U1, int J, int activation,
+                                    float *d_denc, float *d_dpred) {
+    static const char who[] = "nntk_rnnt_joint_backward_device";
+    nntk_shim_clear_error();
+    if (joint_check(who, batch, T, U1, J, activation)) return -1;
+    if ((size_t)batch * T * U1 * J == 0) return 0;
+    if ((activation != 0 && rnnt_check_ptr(who, "d_out_fwd", d_out_fwd, 4)) || rnnt_check_ptr(who, "d_dout", d_dout, 4) ||
+        rnnt_check_ptr(who, "d_denc", d_denc, 4) || rnnt_check_ptr(who, "d_dpred", d_dpred, 4)) return -1;
+    return nntk_shim_rnnt_joint_backward(d_out_fwd, d_dout, batch, T, U1, J, activation, d_denc, d_dpred);
+}

@@ -940,6 +940,85 @@ def ctc_align(probs, labels, label_lengths=None, input_lengths=None, blank=0):
     return st, sp, sc
 
 
+RNNT_ACTIVATIONS = {ACT_IDENTITY: 0, ACT_TANH: 1, ACT_RELU: 2}
+
+
+def _rnnt_labels(labels, label_lengths, B, maxL):
+    """labels as for ``ctc_loss_device``, padded to the lattice's max_label_len = U1 - 1 -> (int32 [B, maxL], int32 [B])"""
+    if label_lengths is None:
+        rows = [np.asarray(r, dtype=np.int32).reshape(-1) for r in labels]
+        assert len(rows) == B, "labels: one list per row"
+        assert all(r.shape[0] <= maxL for r in rows), "labels: at most logits.shape[2] - 1 per row"
+        lab = np.zeros((B, maxL), np.int32)
+        for b, r in enumerate(rows):
+            lab[b, :r.shape[0]] = r
+        return lab, np.array([r.shape[0] for r in rows], dtype=np.int32)
+    lab = np.ascontiguousarray(np.asarray(labels, dtype=np.int32)).reshape(B, maxL)
+    return lab, _host_ints(label_lengths, B, "label_lengths")
+
+
+def rnnt_loss_device(logits, labels, label_lengths=None, input_lengths=None, blank=0, want_grad=True, loss=None, dlogits=None, workspace=None):
+    """``nntk_rnnt_loss_device``: logits [B,T,U1,V] device tensor of UNNORMALISED scores (U1 = max_label_len + 1); labels: a list of
+    per-row lists, or a padded int array [B, U1 - 1] with label_lengths.  Returns (loss rows [B], d loss / d logits [B,T,U1,V] or None)."""
+    import torch
+    B, T, U1, V = logits.shape
+    lab, ll = _rnnt_labels(labels, label_lengths, B, U1 - 1)
+    il, ilp = _ctc_lengths(input_lengths, B)
+    L = capi.load()
+    need = L.nntk_rnnt_workspace_floats(B, T, U1 - 1, int(want_grad))
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.float32, device=logits.device)
+    assert workspace.numel() >= need, "workspace: nntk_rnnt_workspace_floats(B, T, max_label_len, want_grad) floats"
+    if loss is None:
+        loss = torch.empty(B, dtype=torch.float32, device=logits.device)
+    if want_grad and dlogits is None:
+        dlogits = torch.empty_like(logits)
+    check(L.nntk_rnnt_loss_device(_dp(logits), B, T, V, ilp, lab.ctypes.data_as(capi.ip), ll.ctypes.data_as(capi.ip), U1 - 1, blank,
+                                  _dp(loss), _dp(dlogits) if want_grad else None, _dp(workspace)), "nntk_rnnt_loss_device")
+    return loss, (dlogits if want_grad else None)
+
+
+def rnnt_loss(logits, labels, label_lengths=None, input_lengths=None, blank=0, want_grad=True):
+    """The host-memory form (``nntk_rnnt_loss``): logits [B,T,U1,V] numpy array."""
+    logits = _f32(logits)
+    B, T, U1, V = logits.shape
+    lab, ll = _rnnt_labels(labels, label_lengths, B, U1 - 1)
+    il, ilp = _ctc_lengths(input_lengths, B)
+    loss = np.empty(B, np.float32)
+    g = np.empty_like(logits) if want_grad else None
+    check(capi.load().nntk_rnnt_loss(_p(logits), B, T, V, ilp, lab.ctypes.data_as(capi.ip), ll.ctypes.data_as(capi.ip), U1 - 1, blank,
+                                     _p(loss), _p(g) if want_grad else None), "nntk_rnnt_loss")
+    return loss, g
+
+
+def rnnt_joint_device(enc, pred, activation=ACT_TANH, out=None):
+    """``nntk_rnnt_joint_device``: enc [B,T,J], pred [B,U1,J] device tensors -> out [B,T,U1,J] = act(enc[b,t] + pred[b,u])"""
+    B, T, J = enc.shape
+    U1 = pred.shape[1]
+    assert tuple(pred.shape) == (B, U1, J), "pred: [B, U1, J] with enc's B and J"
+    if out is None:
+        out = enc.new_empty((B, T, U1, J))
+    assert tuple(out.shape) == (B, T, U1, J)
+    check(capi.load().nntk_rnnt_joint_device(_dp(enc), _dp(pred), B, T, U1, J, RNNT_ACTIVATIONS[activation], _dp(out)),
+          "nntk_rnnt_joint_device")
+    return out
+
+
+def rnnt_joint_backward_device(out, dout, activation=ACT_TANH, denc=None, dpred=None):
+    """``nntk_rnnt_joint_backward_device``: the joiner's forward output and the gradient arriving at it, both [B,T,U1,J] ->
+    (d enc [B,T,J], d pred [B,U1,J]), both overwritten"""
+    B, T, U1, J = dout.shape
+    assert tuple(out.shape) == (B, T, U1, J)
+    if denc is None:
+        denc = dout.new_empty((B, T, J))
+    if dpred is None:
+        dpred = dout.new_empty((B, U1, J))
+    assert tuple(denc.shape) == (B, T, J) and tuple(dpred.shape) == (B, U1, J)
+    check(capi.load().nntk_rnnt_joint_backward_device(_dp(out), _dp(dout), B, T, U1, J, RNNT_ACTIVATIONS[activation], _dp(denc), _dp(dpred)),
+          "nntk_rnnt_joint_backward_device")
+    return denc, dpred
+
+
 class LSTM(_Recurrent):
     def __init__(self, in_features, hidden, return_sequences, timesteps, v2=True, acts=None, mini_batch=None):
         L = capi.load()
