@@ -1066,6 +1066,51 @@ int nntk_rnnt_joint_device(const float *d_enc, const float *d_pred, int batch, i
 int nntk_rnnt_joint_backward_device(const float *d_out_fwd, const float *d_dout, int batch, int T, int U1, int J, int activation,
                                     float *d_denc, float *d_dpred);
 
+/* ---- RNN-Transducer: greedy decoding (csrc/hip/rnnt_decode.hip; INTEGRATION.md "RNN-Transducer: greedy decoding") ----
+ * The model: a one-layer LSTM prediction network over a label embedding, a linear projection to the joiner width, the joiner of
+ * nntk_rnnt_joint_device and a vocabulary Dense.  V classes, embedding width E, hidden width H, joiner width J; caller-owned device blocks:
+ *   d_embed [V][E] row-major; row `blank` is the start-of-sequence input
+ *   d_lstm  the LSTMGetWeights block W [E,4H] | U [H,4H] | b_i [4H] | b_h [4H], gates i, f, g, o, the default activations
+ *   d_pred_proj  Dense layout W [H,J] | b [J], or NULL: identity, which requires H == J
+ *   d_out   Dense layout W [J,V] | b [V]
+ * create / load_weights_device copy what the kernel reads into the decoder's own device memory -- U, the projection, the vocabulary
+ * Dense, and the table embed W + b_i + b_h [V][4H] (one product, so an emission costs h U alone) -- and return after the copies are
+ * done: the four blocks may be freed or rewritten at once.  load takes d_pred_proj exactly when create did.
+ * Per row b, with n = n_frames[b] live frames of d_enc [batch][T][J]: (h, c) = 0, one LSTM step on embed[blank], g = proj(h); t = 0,
+ * s = 0; while t < n: z = act(enc[b][t] + g), logits = z W_out + b_out, k = argmax (ties: the lowest index), lp = logits[k] -
+ * logsumexp(logits), score += lp; k == blank: t += 1, s = 0; else label k is appended with frame t, an LSTM step on embed[k], g = proj(h),
+ * s += 1, and when s == max_symbols_per_frame: t += 1, s = 0 (no blank is scored for that move).  A row that holds max_labels labels
+ * stops for good.  Frames t >= n_frames[b] influence nothing and may hold NaN.
+ *   d_labels_out [batch][max_labels]: the labels, then -1; d_label_frames (same shape, or NULL): the frame of each label, then -1;
+ *   d_out_lengths [batch]; d_scores [batch] or NULL: the sum of lp over the row's decisions.  n_frames 0: length 0, score 0.
+ * With a state (nntk_rnnt_decode_state_create: batch rows of h, c, g, s, the label count, the frames consumed and the score, 8 H + 4 J +
+ * 28 bytes per row whatever the stream's length) the call continues every row where the last call left it: the caller passes the
+ * same output buffers on every push, labels are appended, frames count from the start of the row's stream, lengths and scores are
+ * rewritten, and any split of a row's frames into pushes gives the one-shot call's labels, frames, lengths and score bits.  reset
+ * (rows NULL, 0: every row) puts rows back to the start, in stream order.  A state belongs to its decoder and must not outlive it.
+ * Checks, all on the host before anything is enqueued (-1 / NULL, nntk_last_error(), nothing written): a NULL handle or required
+ * pointer; V < 2 or > 8192; blank outside [0, V); E, H, J < 1 or > 1024; d_pred_proj NULL with H != J; joint_activation not 0 / 1 / 2;
+ * max_symbols_per_frame < 1; max_labels < 1; n_frames[b] outside [0, T] (host array; NULL = every row T); batch different from the
+ * state's; a tensor that is not 4-byte aligned; output arrays overlapping one another or d_enc.
+ * Deterministic: no atomics, the same bits on every call; a row's labels, frames and score bits do not depend on the other rows, its
+ * position in the batch, the T padding, or how many rows share a workgroup.  One launch on the calling thread's stream, nothing read
+ * back.  The host-pointer form uploads, runs the device form and downloads (with a state it first uploads the label buffers). */
+typedef struct { int V, blank, E, H, J, joint_activation, max_symbols_per_frame; } NntkRnntDecoderConfig;
+typedef struct NntkRnntDecoderStruct *NntkRnntDecoder;
+typedef struct NntkRnntDecodeStateStruct *NntkRnntDecodeState;
+NntkRnntDecoder nntk_rnnt_decoder_create(NntkRnntDecoderConfig cfg, const float *d_embed, const float *d_lstm, const float *d_pred_proj,
+                                         const float *d_out);
+int nntk_rnnt_decoder_load_weights_device(NntkRnntDecoder d, const float *d_embed, const float *d_lstm, const float *d_pred_proj,
+                                          const float *d_out);
+void nntk_rnnt_decoder_destroy(NntkRnntDecoder d);
+NntkRnntDecodeState nntk_rnnt_decode_state_create(NntkRnntDecoder d, int batch);
+int nntk_rnnt_decode_state_reset(NntkRnntDecodeState s, const int *rows, int n_rows);
+void nntk_rnnt_decode_state_destroy(NntkRnntDecodeState s);
+int nntk_rnnt_greedy_decode_device(NntkRnntDecoder d, NntkRnntDecodeState state, const float *d_enc, int batch, int T, const int *n_frames,
+                                   int max_labels, int *d_labels_out, int *d_label_frames, int *d_out_lengths, float *d_scores);
+int nntk_rnnt_greedy_decode(NntkRnntDecoder d, NntkRnntDecodeState state, const float *enc, int batch, int T, const int *n_frames,
+                            int max_labels, int *labels_out, int *label_frames, int *out_lengths, float *scores);
+
 #ifdef __cplusplus
 }
 #endif

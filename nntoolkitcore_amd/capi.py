@@ -61,6 +61,11 @@ class NntkOptimizerConfig(C.Structure):
                 ("decoupled", C.c_int), ("grad_scale", C.c_float), ("clip_norm", C.c_float), ("zero_gradients", C.c_int)]
 
 
+class NntkRnntDecoderConfig(C.Structure):
+    _fields_ = [("V", C.c_int), ("blank", C.c_int), ("E", C.c_int), ("H", C.c_int), ("J", C.c_int), ("joint_activation", C.c_int),
+                ("max_symbols_per_frame", C.c_int)]
+
+
 class DefaultWeights(C.Structure):
     _fields_ = [("W", fp), ("b", fp)]
 
@@ -461,6 +466,15 @@ SIGNATURES = {
     "nntk_rnnt_loss": (C.c_int, [fp, C.c_int, C.c_int, C.c_int, ip, ip, ip, C.c_int, C.c_int, fp, fp]),
     "nntk_rnnt_joint_device": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
     "nntk_rnnt_joint_backward_device": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),
+    # RNN-Transducer: greedy decoding, one-shot and streamed (INTEGRATION.md "RNN-Transducer: greedy decoding")
+    "nntk_rnnt_decoder_create": (vp, [NntkRnntDecoderConfig, vp, vp, vp, vp]),
+    "nntk_rnnt_decoder_load_weights_device": (C.c_int, [vp, vp, vp, vp, vp]),
+    "nntk_rnnt_decoder_destroy": (None, [vp]),
+    "nntk_rnnt_decode_state_create": (vp, [vp, C.c_int]),
+    "nntk_rnnt_decode_state_reset": (C.c_int, [vp, ip, C.c_int]),
+    "nntk_rnnt_decode_state_destroy": (None, [vp]),
+    "nntk_rnnt_greedy_decode_device": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, ip, C.c_int, vp, vp, vp, vp]),
+    "nntk_rnnt_greedy_decode": (C.c_int, [vp, vp, fp, C.c_int, C.c_int, ip, C.c_int, ip, ip, ip, fp]),
     # weights from device memory into a handle; the multi-tensor optimizer (INTEGRATION.md "Optimizers")
     "Conv1dLoadWeightsDevice": (C.c_int, [vp, vp]),
     "BatchNormLoadWeightsDevice": (C.c_int, [vp, vp]),

@@ -210,6 +210,27 @@ int nntk_shim_rnnt_loss(const float *d_logits, int B, int T, int V, const int *h
 int nntk_shim_rnnt_joint(const float *d_enc, const float *d_pred, int B, int T, int U1, int J, int kind, float *d_out);
 int nntk_shim_rnnt_joint_backward(const float *d_out_fwd, const float *d_dout, int B, int T, int U1, int J, int kind, float *d_denc,
                                   float *d_dpred);
+/* ---- greedy transducer decoding (rnnt_decode.hip).  The limits, stated once for the host's checks (rnnt_decode.c) and the launcher: a
+ *      row's h, c, g, joiner output and max(4H, V) logits / gate pre-activations live in one workgroup's LDS (48 KiB at the limits), and
+ *      the folded input table is V x 4H floats (128 MiB at the limits).  Batches above NNTK_RNNT_DEC_GROUP_BATCH rows put
+ *      NNTK_RNNT_DEC_GROUP rows into a workgroup where their LDS fits (nntk_shim_rnnt_dec_rows_per_group); the bits do not depend on it. ---- */
+#define NNTK_RNNT_DEC_MAX_WIDTH 1024            /* E, H, J */
+#define NNTK_RNNT_DEC_MAX_V 8192
+#define NNTK_RNNT_DEC_GROUP 4
+#define NNTK_RNNT_DEC_GROUP_BATCH 512
+/* the decoder's own device blocks: d_table [V][4H] = embed W + b_i + b_h, d_U [H][4H], d_proj [H][J] | b [J] or NULL, d_out [J][V] | b [V] */
+typedef struct {
+    const float *d_table, *d_U, *d_proj, *d_out;
+    int V, blank, E, H, J, activation, max_symbols_per_frame;
+} nntk_shim_rnnt_dec;
+int nntk_shim_rnnt_dec_rows_per_group(int batch, int H, int J, int V);
+int nntk_shim_rnnt_dec_table(const float *d_embed, const float *d_lstm, int V, int E, int H, float *d_table);
+int nntk_shim_rnnt_dec_reset(int *d_st_i, const int *d_rows, int n_rows);      /* the listed rows start anew; in stream order */
+/* h_n_frames HOST [batch], checked by the caller, copied in stream order (it rides in d_lengths).  State: d_st_f [batch][2H + J] (h | c |
+ * g), d_st_score [batch] doubles, d_st_i [batch][4] (started | symbols in the frame | labels | frames consumed), or three NULLs: every
+ * row from the start.  d_frames, d_scores may be NULL. */
+int nntk_shim_rnnt_greedy(const nntk_shim_rnnt_dec *m, const float *d_enc, int batch, int T, const int *h_n_frames, int max_labels,
+                          float *d_st_f, double *d_st_score, int *d_st_i, int *d_labels, int *d_frames, int *d_lengths, float *d_scores);
 /* BatchNorm training (batch_norm.c:191-386): x, d_out [N, F]; d_block = gamma | beta | ...; d_stats [8][F] = mean | variance |
  * var_eps | sqrt_var | d_beta | d_gamma | d_var | d_mu; d_partial [slices][3][F] with slices from nntk_shim_bn_train_slices */
 /* Ragged batches and carried state for the recurrent training launchers below (the *VarLen training calls; a NULL pointer to it = the

@@ -1,0 +1,237 @@
+/*
+ * rnnt_decode.c -- host layer of greedy RNN-Transducer decoding (csrc/hip/rnnt_decode.hip): the decoder handle with its own device
+ * copy of the weights, the per-row state of a stream, and the decode call in its device-pointer and host-pointer forms.  Every
+ * argument is checked here, before anything is allocated, uploaded or enqueued: a refusal needs no device and writes nothing.
+ */
+#include <stdint.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include "nntk_internal.h"
+
+#define t_a (*nntk_thread_scratch(NNTK_TS_A))
+#define t_b (*nntk_thread_scratch(NNTK_TS_B))
+#define DEC_STR_(x) #x
+#define DEC_STR(x) DEC_STR_(x)
+
+struct NntkRnntDecoderStruct {
+    NntkRnntDecoderConfig cfg;
+    float *d_table, *d_U, *d_proj, *d_out;      /* the decoder's own blocks (d_proj NULL: identity) */
+};
+
+struct NntkRnntDecodeStateStruct {
+    NntkRnntDecoder dec;
+    int batch;
+    float *d_f;                                 /* [batch][2H + J] */
+    double *d_score;                            /* [batch] */
+    int *d_i;                                   /* [batch][4], then [batch]: the rows of a reset */
+};
+
+static int dec_fail(const char *who, const char *fmt, long a, long b, long c) {
+    char msg[240];
+    int n = snprintf(msg, sizeof msg, "%s: ", who);
+    snprintf(msg + n, sizeof msg - (size_t)n, fmt, a, b, c);
+    nntk_set_error(msg);
+    return -1;
+}
+
+static int dec_named_ptr(const char *who, const char *name, const void *p) {
+    char msg[240];
+    if (p && ((uintptr_t)p & 3) == 0) return 0;
+    snprintf(msg, sizeof msg, p ? "%s: %s is not 4-byte aligned" : "%s: %s is NULL", who, name);
+    nntk_set_error(msg);
+    return -1;
+}
+
+static int dec_check_blocks(const char *who, const NntkRnntDecoderConfig *c, const float *d_embed, const float *d_lstm,
+                            const float *d_pred_proj, const float *d_out) {
+    if (dec_named_ptr(who, "d_embed", d_embed) || dec_named_ptr(who, "d_lstm", d_lstm) || dec_named_ptr(who, "d_out", d_out)) return -1;
+    if (d_pred_proj && dec_named_ptr(who, "d_pred_proj", d_pred_proj)) return -1;
+    if (!d_pred_proj && c->H != c->J)
+        return dec_fail(who, "d_pred_proj is NULL (identity) but H %ld != J %ld", c->H, c->J, 0);
+    return 0;
+}
+
+static int dec_check_config(const char *who, const NntkRnntDecoderConfig *c) {
+    if (c->V < 2) return dec_fail(who, "V %ld < 2: a transducer has the blank and at least one label", c->V, 0, 0);
+    if (c->V > NNTK_RNNT_DEC_MAX_V) return dec_fail(who, "V %ld is above the limit %ld", c->V, NNTK_RNNT_DEC_MAX_V, 0);
+    if (c->blank < 0 || c->blank >= c->V) return dec_fail(who, "blank %ld is outside [0, %ld)", c->blank, c->V, 0);
+    if (c->E < 1 || c->H < 1 || c->J < 1) return dec_fail(who, "E %ld, H %ld, J %ld: each must be at least 1", c->E, c->H, c->J);
+    if (c->E > NNTK_RNNT_DEC_MAX_WIDTH || c->H > NNTK_RNNT_DEC_MAX_WIDTH || c->J > NNTK_RNNT_DEC_MAX_WIDTH)
+        return dec_fail(who, "E %ld, H %ld, J %ld: one is above the limit " DEC_STR(NNTK_RNNT_DEC_MAX_WIDTH), c->E, c->H, c->J);
+    if (c->joint_activation < 0 || c->joint_activation > 2)
+        return dec_fail(who, "joint_activation %ld is none of 0 (identity), 1 (tanh), 2 (relu)", c->joint_activation, 0, 0);
+    if (c->max_symbols_per_frame < 1) return dec_fail(who, "max_symbols_per_frame %ld < 1", c->max_symbols_per_frame, 0, 0);
+    return 0;
+}
+
+/* the device work of create and load: copies of U, the projection and the vocabulary Dense, and the folded table embed W + b_i + b_h */
+static int dec_load(NntkRnntDecoder d, const float *d_embed, const float *d_lstm, const float *d_pred_proj, const float *d_out) {
+    const NntkRnntDecoderConfig *c = &d->cfg;
+    const size_t G = 4 * (size_t)c->H;
+    if (nntk_shim_rnnt_dec_table(d_embed, d_lstm, c->V, c->E, c->H, d->d_table)) return -1;
+    if (nntk_shim_copy_d2d(d->d_U, d_lstm + (size_t)c->E * G, (size_t)c->H * G * sizeof(float))) return -1;
+    if (d_pred_proj && nntk_shim_copy_d2d(d->d_proj, d_pred_proj, ((size_t)c->H + 1) * c->J * sizeof(float))) return -1;
+    if (nntk_shim_copy_d2d(d->d_out, d_out, ((size_t)c->J + 1) * c->V * sizeof(float))) return -1;
+    return nntk_shim_synchronize();             /* the caller's blocks are free for reuse on return */
+}
+
+NntkRnntDecoder nntk_rnnt_decoder_create(NntkRnntDecoderConfig cfg, const float *d_embed, const float *d_lstm, const float *d_pred_proj,
+                                         const float *d_out) {
+    static const char who[] = "nntk_rnnt_decoder_create";
+    nntk_shim_clear_error();
+    if (dec_check_config(who, &cfg) || dec_check_blocks(who, &cfg, d_embed, d_lstm, d_pred_proj, d_out)) return NULL;
+    NntkRnntDecoder d = (NntkRnntDecoder)calloc(1, sizeof *d);
+    if (!d) { nntk_set_error("nntk_rnnt_decoder_create: out of host memory"); return NULL; }
+    d->cfg = cfg;
+    const size_t G = 4 * (size_t)cfg.H;
+    d->d_table = (float *)nntk_shim_malloc((size_t)cfg.V * G * sizeof(float));
+    d->d_U = d->d_table ? (float *)nntk_shim_malloc((size_t)cfg.H * G * sizeof(float)) : NULL;
+    d->d_out = d->d_U ? (float *)nntk_shim_malloc(((size_t)cfg.J + 1) * cfg.V * sizeof(float)) : NULL;
+    if (d->d_out && d_pred_proj) d->d_proj = (float *)nntk_shim_malloc(((size_t)cfg.H + 1) * cfg.J * sizeof(float));
+    if (!d->d_table || !d->d_U || !d->d_out || (d_pred_proj && !d->d_proj) || dec_load(d, d_embed, d_lstm, d_pred_proj, d_out)) {
+        nntk_rnnt_decoder_destroy(d);
+        return NULL;
+    }
+    return d;
+}
+
+int nntk_rnnt_decoder_load_weights_device(NntkRnntDecoder d, const float *d_embed, const float *d_lstm, const float *d_pred_proj,
+                                          const float *d_out) {
+    static const char who[] = "nntk_rnnt_decoder_load_weights_device";
+    nntk_shim_clear_error();
+    if (!d) return dec_fail(who, "NULL handle", 0, 0, 0);
+    if (dec_check_blocks(who, &d->cfg, d_embed, d_lstm, d_pred_proj, d_out)) return -1;
+    if ((d_pred_proj != NULL) != (d->d_proj != NULL))
+        return dec_fail(who, "d_pred_proj must be given exactly when the decoder was created with one", 0, 0, 0);
+    return dec_load(d, d_embed, d_lstm, d_pred_proj, d_out);
+}
+
+void nntk_rnnt_decoder_destroy(NntkRnntDecoder d) {
+    if (!d) return;
+    if (d->d_table) nntk_shim_synchronize();
+    nntk_shim_free(d->d_table);
+    nntk_shim_free(d->d_U);
+    nntk_shim_free(d->d_proj);
+    nntk_shim_free(d->d_out);
+    free(d);
+}
+
+NntkRnntDecodeState nntk_rnnt_decode_state_create(NntkRnntDecoder d, int batch) {
+    nntk_shim_clear_error();
+    if (!d) { nntk_set_error("nntk_rnnt_decode_state_create: NULL decoder"); return NULL; }
+    if (batch < 1) { dec_fail("nntk_rnnt_decode_state_create", "batch %ld < 1", batch, 0, 0); return NULL; }
+    NntkRnntDecodeState s = (NntkRnntDecodeState)calloc(1, sizeof *s);
+    if (!s) { nntk_set_error("nntk_rnnt_decode_state_create: out of host memory"); return NULL; }
+    s->dec = d;
+    s->batch = batch;
+    s->d_f = (float *)nntk_shim_malloc((size_t)batch * (2 * (size_t)d->cfg.H + d->cfg.J) * sizeof(float));
+    s->d_score = s->d_f ? (double *)nntk_shim_malloc((size_t)batch * sizeof(double)) : NULL;
+    s->d_i = s->d_score ? (int *)nntk_shim_malloc((size_t)batch * 5 * sizeof(int)) : NULL;
+    if (!s->d_i || nntk_shim_memset(s->d_i, 0, (size_t)batch * 5 * sizeof(int))) {
+        nntk_rnnt_decode_state_destroy(s);
+        return NULL;
+    }
+    return s;
+}
+
+int nntk_rnnt_decode_state_reset(NntkRnntDecodeState s, const int *rows, int n_rows) {
+    static const char who[] = "nntk_rnnt_decode_state_reset";
+    nntk_shim_clear_error();
+    if (!s) return dec_fail(who, "NULL state", 0, 0, 0);
+    if (n_rows < 0 || n_rows > s->batch) return dec_fail(who, "n_rows %ld is outside [0, %ld]", n_rows, s->batch, 0);
+    if (!rows && n_rows > 0) return dec_fail(who, "rows is NULL with n_rows %ld", n_rows, 0, 0);
+    if (!rows) return nntk_shim_memset(s->d_i, 0, (size_t)s->batch * 4 * sizeof(int));
+    for (int i = 0; i < n_rows; ++i)
+        if (rows[i] < 0 || rows[i] >= s->batch) return dec_fail(who, "rows[%ld] = %ld is outside [0, %ld)", i, rows[i], s->batch);
+    if (n_rows == 0) return 0;
+    int *d_rows = s->d_i + 4 * (size_t)s->batch;
+    if (nntk_shim_upload_ints(d_rows, rows, n_rows)) return -1;
+    return nntk_shim_rnnt_dec_reset(s->d_i, d_rows, n_rows);
+}
+
+void nntk_rnnt_decode_state_destroy(NntkRnntDecodeState s) {
+    if (!s) return;
+    if (s->d_f) nntk_shim_synchronize();
+    nntk_shim_free(s->d_f);
+    nntk_shim_free(s->d_score);
+    nntk_shim_free(s->d_i);
+    free(s);
+}
+
+static int dec_overlap(const void *a, size_t na, const void *b, size_t nb) {
+    return a && b && na && nb && (uintptr_t)a < (uintptr_t)b + nb && (uintptr_t)b < (uintptr_t)a + na;
+}
+
+/* everything a decode call can be refused for; tensors = 1: the device form's pointers (alignment, overlap) */
+static int dec_check_call(const char *who, NntkRnntDecoder d, NntkRnntDecodeState state, const float *enc, int batch, int T,
+                          const int *n_frames, int max_labels, const int *labels_out, const int *label_frames, const int *out_lengths,
+                          const float *scores) {
+    if (!d) return dec_fail(who, "NULL decoder", 0, 0, 0);
+    if (batch < 0 || T < 0) return dec_fail(who, "batch %ld, T %ld: neither may be negative", batch, T, 0);
+    if (max_labels < 1) return dec_fail(who, "max_labels %ld < 1", max_labels, 0, 0);
+    if (state && state->dec != d) return dec_fail(who, "the state belongs to another decoder", 0, 0, 0);
+    if (state && state->batch != batch) return dec_fail(who, "batch %ld differs from the state's %ld", batch, state->batch, 0);
+    if (batch == 0) return 0;
+    for (int b = 0; n_frames && b < batch; ++b)
+        if (n_frames[b] < 0 || n_frames[b] > T) return dec_fail(who, "n_frames[%ld] = %ld is outside [0, %ld]", b, n_frames[b], T);
+    if (T > 0 && dec_named_ptr(who, "enc", enc)) return -1;
+    if (dec_named_ptr(who, "labels_out", labels_out) || dec_named_ptr(who, "out_lengths", out_lengths)) return -1;
+    if (label_frames && dec_named_ptr(who, "label_frames", label_frames)) return -1;
+    if (scores && dec_named_ptr(who, "scores", scores)) return -1;
+    const size_t nl = (size_t)batch * max_labels * sizeof(int), nb = (size_t)batch * sizeof(int);
+    const size_t ne = (size_t)batch * T * d->cfg.J * sizeof(float);
+    const void *p[5] = { labels_out, label_frames, out_lengths, scores, enc };
+    const size_t n[5] = { nl, nl, nb, nb, ne };
+    static const char *const name[5] = { "labels_out", "label_frames", "out_lengths", "scores", "enc" };
+    for (int i = 0; i < 5; ++i)
+        for (int j = i + 1; j < 5; ++j)
+            if (dec_overlap(p[i], n[i], p[j], n[j])) {
+                char msg[240];
+                snprintf(msg, sizeof msg, "%s: %s overlaps %s", who, name[i], name[j]);
+                nntk_set_error(msg);
+                return -1;
+            }
+    return 0;
+}
+
+int nntk_rnnt_greedy_decode_device(NntkRnntDecoder d, NntkRnntDecodeState state, const float *d_enc, int batch, int T, const int *n_frames,
+                                   int max_labels, int *d_labels_out, int *d_label_frames, int *d_out_lengths, float *d_scores) {
+    static const char who[] = "nntk_rnnt_greedy_decode_device";
+    nntk_shim_clear_error();
+    if (dec_check_call(who, d, state, d_enc, batch, T, n_frames, max_labels, d_labels_out, d_label_frames, d_out_lengths, d_scores)) return -1;
+    if (batch == 0) return 0;
+    int *len = (int *)malloc((size_t)batch * sizeof(int));
+    if (!len) NNTK_FAIL("nntk_rnnt_greedy_decode_device: out of host memory");
+    for (int b = 0; b < batch; ++b) len[b] = n_frames ? n_frames[b] : T;
+    const nntk_shim_rnnt_dec m = { d->d_table, d->d_U, d->d_proj, d->d_out, d->cfg.V, d->cfg.blank, d->cfg.E, d->cfg.H, d->cfg.J,
+                                   d->cfg.joint_activation, d->cfg.max_symbols_per_frame };
+    int rc = nntk_shim_rnnt_greedy(&m, d_enc, batch, T, len, max_labels, state ? state->d_f : NULL, state ? state->d_score : NULL,
+                                   state ? state->d_i : NULL, d_labels_out, d_label_frames, d_out_lengths, d_scores);
+    free(len);
+    return rc;
+}
+
+int nntk_rnnt_greedy_decode(NntkRnntDecoder d, NntkRnntDecodeState state, const float *enc, int batch, int T, const int *n_frames,
+                            int max_labels, int *labels_out, int *label_frames, int *out_lengths, float *scores) {
+    static const char who[] = "nntk_rnnt_greedy_decode";
+    nntk_shim_clear_error();
+    if (dec_check_call(who, d, state, enc, batch, T, n_frames, max_labels, labels_out, label_frames, out_lengths, scores)) return -1;
+    if (batch == 0) return 0;
+    const size_t ne = (size_t)batch * T * d->cfg.J, nl = (size_t)batch * max_labels;
+    float *d_enc = nntk_devbuf_reserve(&t_a, ne + 4);
+    int *d_lab = (int *)nntk_devbuf_reserve(&t_b, 2 * nl + 2 * (size_t)batch + 4);
+    if (!d_enc || !d_lab) return -1;
+    int *d_fr = d_lab + nl, *d_len = d_fr + nl;
+    float *d_sc = (float *)(d_len + batch);
+    if (ne && nntk_shim_upload(d_enc, enc, ne * sizeof(float))) return -1;
+    if (state) {                                /* a push appends to what the caller's buffers hold */
+        if (nntk_shim_upload(d_lab, labels_out, nl * sizeof(int))) return -1;
+        if (label_frames && nntk_shim_upload(d_fr, label_frames, nl * sizeof(int))) return -1;
+    }
+    if (nntk_rnnt_greedy_decode_device(d, state, d_enc, batch, T, n_frames, max_labels, d_lab, label_frames ? d_fr : NULL, d_len,
+                                       scores ? d_sc : NULL)) return -1;
+    if (nntk_shim_download(labels_out, d_lab, nl * sizeof(int))) return -1;
+    if (label_frames && nntk_shim_download(label_frames, d_fr, nl * sizeof(int))) return -1;
+    if (nntk_shim_download(out_lengths, d_len, (size_t)batch * sizeof(int))) return -1;
+    return scores ? nntk_shim_download(scores, d_sc, (size_t)batch * sizeof(float)) : 0;
+}

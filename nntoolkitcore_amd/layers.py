@@ -1019,6 +1019,143 @@ def rnnt_joint_backward_device(out, dout, activation=ACT_TANH, denc=None, dpred=
     return denc, dpred
 
 
+def _ipv(t):
+    """device pointer of a contiguous int32 torch tensor"""
+    import torch
+    assert t.is_cuda and t.is_contiguous() and t.dtype == torch.int32
+    return C.c_void_p(t.data_ptr())
+
+
+class RnntDecoder:
+    """``nntk_rnnt_decoder_*``: greedy transducer decoding with the prediction network inside the search (INTEGRATION.md
+    "RNN-Transducer: greedy decoding").  Device tensors in the library's layouts: embed [V, E]; lstm_block, the flat ``LSTMGetWeights``
+    block W [E,4H] | U [H,4H] | b_i | b_h; pred_proj, the flat Dense block W [H,J] | b [J], or None (identity, H == J); out, the flat
+    Dense block W [J,V] | b [V].  The decoder keeps its own copy: the tensors may be freed or updated afterwards (``load_weights``)."""
+
+    def __init__(self, embed, lstm_block, pred_proj, out, blank=0, joint_activation=ACT_TANH, max_symbols_per_frame=10):
+        V, E = embed.shape
+        H = self._hidden(lstm_block.numel(), E)
+        J = H if pred_proj is None else pred_proj.numel() // (H + 1)
+        assert pred_proj is None or pred_proj.numel() == (H + 1) * J, "pred_proj: the flat block W [H,J] | b [J]"
+        assert out.numel() == (J + 1) * V, "out: the flat block W [J,V] | b [V]"
+        self.V, self.E, self.H, self.J, self.max_symbols = int(V), int(E), int(H), int(J), int(max_symbols_per_frame)
+        cfg = capi.NntkRnntDecoderConfig(self.V, int(blank), self.E, self.H, self.J, RNNT_ACTIVATIONS[joint_activation], self.max_symbols)
+        self.h = capi.load().nntk_rnnt_decoder_create(cfg, _dp(embed), _dp(lstm_block), _dp(pred_proj) if pred_proj is not None else None,
+                                                      _dp(out))
+        if not self.h:
+            raise capi.NNTKError("nntk_rnnt_decoder_create: " + capi.last_error())
+
+    @staticmethod
+    def _hidden(n, E):
+        """H from the block's size n = 4H (E + H + 2)"""
+        H = int(round((-(E + 2) + ((E + 2) ** 2 + n) ** 0.5) / 2))
+        assert H >= 1 and 4 * H * (E + H + 2) == n, "lstm_block: the flat block W [E,4H] | U [H,4H] | b_i [4H] | b_h [4H]"
+        return H
+
+    def load_weights(self, embed, lstm_block, pred_proj, out):
+        """``nntk_rnnt_decoder_load_weights_device``: the same four blocks, e.g. after an optimizer step"""
+        check(capi.load().nntk_rnnt_decoder_load_weights_device(self.h, _dp(embed), _dp(lstm_block),
+                                                                _dp(pred_proj) if pred_proj is not None else None, _dp(out)),
+              "nntk_rnnt_decoder_load_weights_device")
+
+    def _outputs(self, device, B, max_labels):
+        import torch
+        return (torch.empty((B, max_labels), dtype=torch.int32, device=device), torch.empty((B, max_labels), dtype=torch.int32, device=device),
+                torch.empty(B, dtype=torch.int32, device=device), torch.empty(B, dtype=torch.float32, device=device))
+
+    def _decode(self, state, enc, n_frames, max_labels, outs):
+        B, T, J = enc.shape
+        assert J == self.J, "enc: [B, T, J]"
+        nf = None if n_frames is None else _host_ints(n_frames, B, "n_frames")
+        labels, frames, lengths, scores = outs
+        check(capi.load().nntk_rnnt_greedy_decode_device(self.h, state, _dp(enc), B, T, nf.ctypes.data_as(capi.ip) if nf is not None else None,
+                                                         int(max_labels), _ipv(labels), _ipv(frames), _ipv(lengths), _dp(scores)),
+              "nntk_rnnt_greedy_decode_device")
+        return outs
+
+    def decode(self, enc, n_frames=None, max_labels=None):
+        """enc [B, T, J] device tensor, n_frames host ints per row (None: T) -> (labels [B, max_labels] int32, -1 behind each row's
+        labels; label_frames, the same shape; lengths [B] int32; scores [B] float32).  max_labels defaults to
+        max_symbols_per_frame * T, which never truncates."""
+        B, T, _ = enc.shape
+        if max_labels is None:
+            max_labels = max(1, self.max_symbols * T)
+        return self._decode(None, enc, n_frames, max_labels, self._outputs(enc.device, B, max_labels))
+
+    def destroy(self):
+        if self.h:
+            capi.load().nntk_rnnt_decoder_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.destroy()
+        except Exception:
+            pass
+
+
+class RnntGreedyStream:
+    """``nntk_rnnt_decode_state_*``: greedy transducer decoding pushed chunk by chunk for ``batch`` independent streams.  After every
+    push row b holds what ``decoder.decode`` gives on the row's frames since its last reset, bit for bit.  The stream owns the output
+    buffers (labels, label_frames [batch, max_labels]; lengths, scores [batch]) and returns them from every push."""
+
+    def __init__(self, decoder, batch, max_labels):
+        self.dec, self.B, self.max_labels = decoder, int(batch), int(max_labels)
+        self.outs = None
+        self.h = capi.load().nntk_rnnt_decode_state_create(decoder.h, self.B)
+        if not self.h:
+            raise capi.NNTKError("nntk_rnnt_decode_state_create: " + capi.last_error())
+
+    def push(self, enc_chunk, n_frames):
+        """enc_chunk [batch, T, J] device tensor, n_frames host ints per row (0 allowed) -> (labels, label_frames, lengths, scores)"""
+        assert enc_chunk.shape[0] == self.B, "enc_chunk: [batch, T, J]"
+        if self.outs is None:
+            self.outs = self.dec._outputs(enc_chunk.device, self.B, self.max_labels)
+        return self.dec._decode(self.h, enc_chunk, n_frames, self.max_labels, self.outs)
+
+    def reset(self, rows=None):
+        """these rows (None: every row) start new streams"""
+        if rows is None:
+            check(capi.load().nntk_rnnt_decode_state_reset(self.h, None, 0), "nntk_rnnt_decode_state_reset")
+            return
+        rows = np.ascontiguousarray(np.asarray(rows, dtype=np.int32).reshape(-1))
+        check(capi.load().nntk_rnnt_decode_state_reset(self.h, rows.ctypes.data_as(capi.ip), rows.shape[0]), "nntk_rnnt_decode_state_reset")
+
+    def close(self):
+        if self.h:
+            capi.load().nntk_rnnt_decode_state_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def rnnt_greedy_decode(embed, lstm_block, pred_proj, out, enc, n_frames=None, max_labels=None, blank=0, joint_activation=ACT_TANH,
+                       max_symbols_per_frame=10):
+    """Greedy transducer decoding on numpy arrays (the weights go to the device, ``nntk_rnnt_greedy_decode`` takes enc and the results
+    as host memory): enc [B, T, J] -> (labels [B, max_labels], label_frames, lengths [B], scores [B])"""
+    import torch
+    dev = lambda a: None if a is None else torch.from_numpy(_f32(a).reshape(-1) if a is not embed else _f32(a)).cuda()
+    dec = RnntDecoder(dev(embed), dev(lstm_block), dev(pred_proj), dev(out), blank, joint_activation, max_symbols_per_frame)
+    enc = _f32(enc)
+    B, T, _ = enc.shape
+    if max_labels is None:
+        max_labels = max(1, dec.max_symbols * T)
+    nf = None if n_frames is None else _host_ints(n_frames, B, "n_frames")
+    labels, frames = np.empty((B, max_labels), np.int32), np.empty((B, max_labels), np.int32)
+    lengths, scores = np.empty(B, np.int32), np.empty(B, np.float32)
+    try:
+        check(capi.load().nntk_rnnt_greedy_decode(dec.h, None, _p(enc), B, T, nf.ctypes.data_as(capi.ip) if nf is not None else None,
+                                                  int(max_labels), labels.ctypes.data_as(capi.ip), frames.ctypes.data_as(capi.ip),
+                                                  lengths.ctypes.data_as(capi.ip), _p(scores)), "nntk_rnnt_greedy_decode")
+    finally:
+        dec.destroy()
+    return labels, frames, lengths, scores
+
+
 class LSTM(_Recurrent):
     def __init__(self, in_features, hidden, return_sequences, timesteps, v2=True, acts=None, mini_batch=None):
         L = capi.load()
