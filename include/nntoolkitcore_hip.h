@@ -1111,6 +1111,62 @@ int nntk_rnnt_greedy_decode_device(NntkRnntDecoder d, NntkRnntDecodeState state,
 int nntk_rnnt_greedy_decode(NntkRnntDecoder d, NntkRnntDecodeState state, const float *enc, int batch, int T, const int *n_frames,
                             int max_labels, int *labels_out, int *label_frames, int *out_lengths, float *scores);
 
+/* ---- RNN-Transducer: beam search (csrc/hip/rnnt_beam.hip; INTEGRATION.md "RNN-Transducer: beam search") ----
+ * The model, the weight blocks, the decoder handle and max_symbols_per_frame (S below) are those of greedy decoding; W = beam_width.
+ * A hypothesis is a label sequence y, a score (natural log of probability mass, carried in double) and the prediction-network state
+ * (h, c, g) after blank, y_1 .. y_|y|.  logp(t, hyp)[v] = (logits[v] - max) - log(sum exp(logits - max)), the logits from
+ * act(enc[b][t] + g) W_out + b_out with the greedy kernel's arithmetic (four interleaved fmaf chains, expf per element, the sum in
+ * double in a fixed order); the difference is taken in float, the rest in double.  Per row b with n = n_frames[b] live frames:
+ *   A = [ (y = (), score = 0, state = LSTM step on embed[blank] from zero) ]
+ *   for t in 0 .. n-1:
+ *       B = empty list                       hypotheses that have left frame t
+ *       C = A                                rank order
+ *       for depth in 0 .. S:                 depth = labels emitted inside frame t
+ *           for i, hyp in enumerate(C):      position order
+ *               cand = (hyp.y, hyp.score + logp(t, hyp)[blank])
+ *               if cand.score == -inf: drop
+ *               elif an entry of B has the same label sequence:
+ *                   entry.score = logaddexp(entry.score, cand.score)      double; the entry keeps its insertion index and state
+ *               else: append to B            insertion index = running count
+ *           if depth == S: break
+ *           cells = { (i, v) : C[i].score + logp(t, C[i])[v]  for v != blank, for C[i] with fewer than max_labels labels, score > -inf }
+ *           C = the W best cells, score descending, exact ties to the lower i*V + v;
+ *               each becomes (C[i].y + v, that score, LSTM step on embed[v] from C[i]'s state)
+ *           if C is empty: break
+ *       A = the W best of B, score descending, exact ties to the lower insertion index
+ *   result: A[0 .. nbest-1]
+ * Sequences that meet at different depths are merged only in B; p_blank depends only on (t, y), so this is the lattice sum: with no
+ * pruning and S at least the label count, a hypothesis's final score is exactly ln P(y | x), minus the transducer loss.  "Same label
+ * sequence" is decided exactly on the labels (a hash only pre-filters).  B holds at most W (S + 1) entries a frame.
+ *   d_labels_out [batch][nbest][max_labels]: hypothesis k's labels, then -1; d_out_lengths [batch][nbest]; d_scores [batch][nbest]: the
+ *   double score rounded to f32.  A slot without a hypothesis holds labels -1, length -1, score -inf.  n_frames[b] == 0: the empty
+ *   hypothesis with score 0 in slot 0.  Every element of the three outputs is written.  Frames t >= n_frames[b] influence nothing and
+ *   may hold NaN.  d_workspace: nntk_rnnt_beam_workspace_floats(d, batch, beam_width, max_labels) floats, 16-byte aligned.
+ * state NULL: every row starts from the beginning and nothing is kept.  With a state (nntk_rnnt_beam_state_create: per row W label
+ * sequences, double scores and (h, c, g); nntk_rnnt_beam_state_bytes bytes whatever the stream's length) the call continues every
+ * row from the A the last push left, and the three outputs are rewritten with the n-best over all frames pushed so far: any split of
+ * a row's frames into pushes gives the one-shot call's labels, lengths and score bits.  beam_width and max_labels must equal the
+ * state's; a state belongs to its decoder and must not outlive it.  reset (rows NULL, 0: every row) puts rows back to the start.
+ * Checks, all on the host before anything is enqueued (-1 / NULL, nntk_last_error(), nothing written): a NULL handle or required
+ * pointer; beam_width outside [1, 32]; nbest outside [1, beam_width]; max_labels < 1; n_frames[b] outside [0, T] (host array; NULL =
+ * every row T); batch, beam_width or max_labels different from the state's; an output that is not 4-byte aligned, a workspace that is
+ * not 16-byte aligned; outputs overlapping one another, d_enc or the workspace; a model beyond the kernel's LDS.
+ * Deterministic: no atomics, the same bits on every call; a row's bits do not depend on the other rows, its position in the batch,
+ * the T padding, or how many hypotheses share a pass over a matrix.  One launch on the calling thread's stream.  The host-pointer
+ * form uploads, runs the device form on a workspace of its own and downloads.  Not part of the call: label timestamps,
+ * language-model fusion, length normalisation. */
+typedef struct NntkRnntBeamStateStruct *NntkRnntBeamState;
+size_t nntk_rnnt_beam_workspace_floats(NntkRnntDecoder d, int batch, int beam_width, int max_labels);
+int nntk_rnnt_beam_decode_device(NntkRnntDecoder d, NntkRnntBeamState state, const float *d_enc, int batch, int T, const int *n_frames,
+                                 int beam_width, int nbest, int max_labels, int *d_labels_out, int *d_out_lengths, float *d_scores,
+                                 float *d_workspace);
+int nntk_rnnt_beam_decode(NntkRnntDecoder d, NntkRnntBeamState state, const float *enc, int batch, int T, const int *n_frames,
+                          int beam_width, int nbest, int max_labels, int *labels_out, int *out_lengths, float *scores);
+NntkRnntBeamState nntk_rnnt_beam_state_create(NntkRnntDecoder d, int batch, int beam_width, int max_labels);
+size_t nntk_rnnt_beam_state_bytes(NntkRnntDecoder d, int batch, int beam_width, int max_labels);
+int nntk_rnnt_beam_state_reset(NntkRnntBeamState s, const int *rows, int n_rows);
+void nntk_rnnt_beam_state_destroy(NntkRnntBeamState s);
+
 #ifdef __cplusplus
 }
 #endif

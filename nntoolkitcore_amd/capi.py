@@ -475,6 +475,14 @@ SIGNATURES = {
     "nntk_rnnt_decode_state_destroy": (None, [vp]),
     "nntk_rnnt_greedy_decode_device": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, ip, C.c_int, vp, vp, vp, vp]),
     "nntk_rnnt_greedy_decode": (C.c_int, [vp, vp, fp, C.c_int, C.c_int, ip, C.c_int, ip, ip, ip, fp]),
+    # RNN-Transducer: beam search with n-best, one-shot and streamed (INTEGRATION.md "RNN-Transducer: beam search")
+    "nntk_rnnt_beam_workspace_floats": (C.c_size_t, [vp, C.c_int, C.c_int, C.c_int]),
+    "nntk_rnnt_beam_decode_device": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, ip, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]),
+    "nntk_rnnt_beam_decode": (C.c_int, [vp, vp, fp, C.c_int, C.c_int, ip, C.c_int, C.c_int, C.c_int, ip, ip, fp]),
+    "nntk_rnnt_beam_state_create": (vp, [vp, C.c_int, C.c_int, C.c_int]),
+    "nntk_rnnt_beam_state_bytes": (C.c_size_t, [vp, C.c_int, C.c_int, C.c_int]),
+    "nntk_rnnt_beam_state_reset": (C.c_int, [vp, ip, C.c_int]),
+    "nntk_rnnt_beam_state_destroy": (None, [vp]),
     # weights from device memory into a handle; the multi-tensor optimizer (INTEGRATION.md "Optimizers")
     "Conv1dLoadWeightsDevice": (C.c_int, [vp, vp]),
     "BatchNormLoadWeightsDevice": (C.c_int, [vp, vp]),

@@ -231,6 +231,27 @@ int nntk_shim_rnnt_dec_reset(int *d_st_i, const int *d_rows, int n_rows);      /
  * row from the start.  d_frames, d_scores may be NULL. */
 int nntk_shim_rnnt_greedy(const nntk_shim_rnnt_dec *m, const float *d_enc, int batch, int T, const int *h_n_frames, int max_labels,
                           float *d_st_f, double *d_st_score, int *d_st_i, int *d_labels, int *d_frames, int *d_lengths, float *d_scores);
+/* ---- transducer beam search (rnnt_beam.hip) on the greedy decoder's blocks.  One workgroup runs a row's whole search; the hypotheses
+ *      of a depth share passes over the matrices in groups of NNTK_RNNT_DEC_GROUP where the group's LDS fits, else one by one
+ *      (nntk_shim_rnnt_beam_group; nntk_shim_rnnt_beam_set_group(1 or NNTK_RNNT_DEC_GROUP) pins it for tests and timing, 0 = automatic;
+ *      the bits do not depend on it).  The workspace holds, after the rows' frame counts, per row (S' + 2) beam_width hypothesis slots
+ *      (h | c | g, the labels, length and hash), beam_width V logits and the frame's list of beam_width (S' + 1) finished hypotheses,
+ *      S' = min(max_symbols_per_frame, max_labels). ---- */
+#define NNTK_RNNT_BEAM_MAX_W 32
+/* a stream's rows: score [batch][W] doubles, f [batch][W][2H + J], lab [batch][W][max_labels], meta [batch][W][2] (length | hash),
+ * i [batch][4] (started | hypotheses | - | -); all NULL: every row from the start, nothing kept */
+typedef struct {
+    double *score;
+    float *f;
+    int *lab, *meta, *i;
+} nntk_shim_rnnt_beam_state;
+size_t nntk_shim_rnnt_beam_workspace_floats(int batch, int H, int J, int V, int max_sym, int beam_width, int max_labels);
+int nntk_shim_rnnt_beam_fits(int H, int J, int V);                             /* the kernel's LDS at one hypothesis a pass */
+int nntk_shim_rnnt_beam_group(int beam_width, int H, int J, int V);
+void nntk_shim_rnnt_beam_set_group(int group);
+/* h_n_frames HOST [batch], checked by the caller, copied in stream order into the workspace; d_ws 16-byte aligned */
+int nntk_shim_rnnt_beam(const nntk_shim_rnnt_dec *m, const float *d_enc, int batch, int T, const int *h_n_frames, int beam_width, int nbest,
+                        int max_labels, const nntk_shim_rnnt_beam_state *st, int *d_labels, int *d_lengths, float *d_scores, float *d_ws);
 /* BatchNorm training (batch_norm.c:191-386): x, d_out [N, F]; d_block = gamma | beta | ...; d_stats [8][F] = mean | variance |
  * var_eps | sqrt_var | d_beta | d_gamma | d_var | d_mu; d_partial [slices][3][F] with slices from nntk_shim_bn_train_slices */
 /* Ragged batches and carried state for the recurrent training launchers below (the *VarLen training calls; a NULL pointer to it = the

@@ -14,12 +14,7 @@
 // only in the output, so a stream's chunks add up exactly as the one-shot call does.
 //
 // Precomputed at create / load time (rnnt_dec_table_kernel): table[v][:] = embed[v] W + b_i + b_h, so an emission costs h U alone.
-#include <stdint.h>
-#include "nntk_common.hpp"
-
-#define RD_THREADS 1024
-#define RD_WAVES (RD_THREADS / 64)
-#define RD_LDS_MAX (152 * 1024)            // of the 160 KiB of a CU
+#include "rnnt_dec_common.hpp"                // rd_matvec, rd_act, rd_sigmoid, the reduction butterflies: shared with rnnt_beam.hip
 
 struct RnntDecArgs {
     const float *enc;                      // [batch][T][J]
@@ -46,43 +41,6 @@ static size_t rd_lds_bytes(int R, int H, int J, int V) {
     const size_t W = 4 * (size_t)H > (size_t)V ? 4 * (size_t)H : (size_t)V, Wp = (W + 3) & ~(size_t)3;
     const size_t fixed = R == 1 ? sizeof(RdShared<1>) : sizeof(RdShared<NNTK_RNNT_DEC_GROUP>);
     return ((fixed + 15) & ~(size_t)15) + (size_t)R * (2 * Hp + 2 * Jp + Wp) * sizeof(float);
-}
-
-__device__ __forceinline__ float rd_act(int kind, float x) { return kind == 1 ? tanhf(x) : kind == 2 ? fmaxf(x, 0.0f) : x; }
-__device__ __forceinline__ float rd_sigmoid(float x) { return 1.0f / (1.0f + expf(-x)); }
-
-// column n of x [R][Kp] (LDS, rows 16-byte aligned) times Wm [K][N]: four interleaved fmaf chains per row, combined pairwise
-template <int R>
-__device__ __forceinline__ void rd_matvec(const float *__restrict__ Wm, int K, int N, int n, const float *x, int Kp, float (&res)[R]) {
-    float p[R][4];
-#pragma unroll
-    for (int r = 0; r < R; ++r) p[r][0] = p[r][1] = p[r][2] = p[r][3] = 0.0f;
-    const float *w = Wm + n;
-    int k = 0;
-#pragma unroll 2
-    for (; k + 4 <= K; k += 4) {
-        const float w0 = w[(size_t)k * N], w1 = w[(size_t)(k + 1) * N], w2 = w[(size_t)(k + 2) * N], w3 = w[(size_t)(k + 3) * N];
-#pragma unroll
-        for (int r = 0; r < R; ++r) {
-            const f32x4 v = *(const f32x4 *)(x + r * Kp + k);
-            p[r][0] = fmaf(v[0], w0, p[r][0]);
-            p[r][1] = fmaf(v[1], w1, p[r][1]);
-            p[r][2] = fmaf(v[2], w2, p[r][2]);
-            p[r][3] = fmaf(v[3], w3, p[r][3]);
-        }
-    }
-    for (int i = 0; k < K; ++k, ++i) {                                       // at most three left: chains 0, 1, 2
-        const float wk = w[(size_t)k * N];
-#pragma unroll
-        for (int r = 0; r < R; ++r) {
-            const float v = x[r * Kp + k];
-            if (i == 0) p[r][0] = fmaf(v, wk, p[r][0]);
-            else if (i == 1) p[r][1] = fmaf(v, wk, p[r][1]);
-            else p[r][2] = fmaf(v, wk, p[r][2]);
-        }
-    }
-#pragma unroll
-    for (int r = 0; r < R; ++r) res[r] = (p[r][0] + p[r][1]) + (p[r][2] + p[r][3]);
 }
 
 template <int R>
@@ -199,11 +157,7 @@ __global__ __launch_bounds__(RD_THREADS) void rnnt_greedy_kernel(const RnntDecAr
         }
 #pragma unroll
         for (int r = 0; r < R; ++r) {
-            for (int off = 32; off > 0; off >>= 1) {
-                const float om = __shfl_xor(m[r], off);
-                const int oi = __shfl_xor(mi[r], off);
-                if (om > m[r] || (om == m[r] && oi < mi[r])) { m[r] = om; mi[r] = oi; }
-            }
+            rd_wave_argmax(m[r], mi[r]);
             if (lane == 0) { sh.red_max[r][wave] = m[r]; sh.red_idx[r][wave] = mi[r]; }
         }
         __syncthreads();
@@ -215,9 +169,7 @@ __global__ __launch_bounds__(RD_THREADS) void rnnt_greedy_kernel(const RnntDecAr
                 const int oi = sh.red_idx[r][w];
                 if (om > m[r] || (om == m[r] && oi < mi[r])) { m[r] = om; mi[r] = oi; }
             }
-            double sum = 0.0;
-            for (int n = tid; n < V; n += RD_THREADS) sum += (double)expf(sh_buf[r * Wp + n] - m[r]);
-            for (int off = 32; off > 0; off >>= 1) sum += __shfl_xor(sum, off);
+            const double sum = rd_wave_sum_exp(sh_buf + r * Wp, V, tid, m[r]);
             if (lane == 0) sh.red_sum[r][wave] = sum;
             if (tid == 0) { sh.best[r] = mi[r]; sh.live[r] = act[r]; }
         }

@@ -1,7 +1,8 @@
 /*
- * rnnt_decode.c -- host layer of greedy RNN-Transducer decoding (csrc/hip/rnnt_decode.hip): the decoder handle with its own device
- * copy of the weights, the per-row state of a stream, and the decode call in its device-pointer and host-pointer forms.  Every
- * argument is checked here, before anything is allocated, uploaded or enqueued: a refusal needs no device and writes nothing.
+ * rnnt_decode.c -- host layer of RNN-Transducer decoding: the decoder handle with its own device copy of the weights; greedy search
+ * (csrc/hip/rnnt_decode.hip) and, below it, beam search (csrc/hip/rnnt_beam.hip), each with the per-row state of a stream and the
+ * decode call in its device-pointer and host-pointer forms.  Every argument is checked here, before anything is allocated, uploaded
+ * or enqueued: a refusal needs no device and writes nothing.
  */
 #include <stdint.h>
 #include <stdio.h>
@@ -234,4 +235,166 @@ int nntk_rnnt_greedy_decode(NntkRnntDecoder d, NntkRnntDecodeState state, const 
     if (label_frames && nntk_shim_download(label_frames, d_fr, nl * sizeof(int))) return -1;
     if (nntk_shim_download(out_lengths, d_len, (size_t)batch * sizeof(int))) return -1;
     return scores ? nntk_shim_download(scores, d_sc, (size_t)batch * sizeof(float)) : 0;
+}
+
+/* ---- beam search (csrc/hip/rnnt_beam.hip) on the same decoder handle ---- */
+
+struct NntkRnntBeamStateStruct {
+    NntkRnntDecoder dec;
+    int batch, width, max_labels;
+    nntk_shim_rnnt_beam_state d;                /* d.i: [batch][4], then [batch]: the rows of a reset */
+};
+
+static int beam_check_sizes(const char *who, NntkRnntDecoder d, int beam_width, int max_labels) {
+    if (!d) return dec_fail(who, "NULL decoder", 0, 0, 0);
+    if (beam_width < 1 || beam_width > NNTK_RNNT_BEAM_MAX_W)
+        return dec_fail(who, "beam_width %ld is outside [1, %ld]", beam_width, NNTK_RNNT_BEAM_MAX_W, 0);
+    if (max_labels < 1) return dec_fail(who, "max_labels %ld < 1", max_labels, 0, 0);
+    return 0;
+}
+
+size_t nntk_rnnt_beam_workspace_floats(NntkRnntDecoder d, int batch, int beam_width, int max_labels) {
+    if (!d || batch <= 0 || beam_width < 1 || beam_width > NNTK_RNNT_BEAM_MAX_W || max_labels < 1) return 0;
+    return nntk_shim_rnnt_beam_workspace_floats(batch, d->cfg.H, d->cfg.J, d->cfg.V, d->cfg.max_symbols_per_frame, beam_width, max_labels);
+}
+
+size_t nntk_rnnt_beam_state_bytes(NntkRnntDecoder d, int batch, int beam_width, int max_labels) {
+    if (!d || batch <= 0 || beam_width < 1 || beam_width > NNTK_RNNT_BEAM_MAX_W || max_labels < 1) return 0;
+    const size_t per_hyp = sizeof(double) + (2 * (size_t)d->cfg.H + d->cfg.J) * sizeof(float) + ((size_t)max_labels + 2) * sizeof(int);
+    return (size_t)batch * (beam_width * per_hyp + 5 * sizeof(int));
+}
+
+NntkRnntBeamState nntk_rnnt_beam_state_create(NntkRnntDecoder d, int batch, int beam_width, int max_labels) {
+    static const char who[] = "nntk_rnnt_beam_state_create";
+    nntk_shim_clear_error();
+    if (beam_check_sizes(who, d, beam_width, max_labels)) return NULL;
+    if (batch < 1) { dec_fail(who, "batch %ld < 1", batch, 0, 0); return NULL; }
+    NntkRnntBeamState s = (NntkRnntBeamState)calloc(1, sizeof *s);
+    if (!s) { nntk_set_error("nntk_rnnt_beam_state_create: out of host memory"); return NULL; }
+    s->dec = d; s->batch = batch; s->width = beam_width; s->max_labels = max_labels;
+    const size_t hyps = (size_t)batch * beam_width;
+    s->d.score = (double *)nntk_shim_malloc(hyps * sizeof(double));
+    s->d.f = s->d.score ? (float *)nntk_shim_malloc(hyps * (2 * (size_t)d->cfg.H + d->cfg.J) * sizeof(float)) : NULL;
+    s->d.lab = s->d.f ? (int *)nntk_shim_malloc(hyps * max_labels * sizeof(int)) : NULL;
+    s->d.meta = s->d.lab ? (int *)nntk_shim_malloc(hyps * 2 * sizeof(int)) : NULL;
+    s->d.i = s->d.meta ? (int *)nntk_shim_malloc((size_t)batch * 5 * sizeof(int)) : NULL;
+    if (!s->d.i || nntk_shim_memset(s->d.i, 0, (size_t)batch * 5 * sizeof(int))) {
+        nntk_rnnt_beam_state_destroy(s);
+        return NULL;
+    }
+    return s;
+}
+
+int nntk_rnnt_beam_state_reset(NntkRnntBeamState s, const int *rows, int n_rows) {
+    static const char who[] = "nntk_rnnt_beam_state_reset";
+    nntk_shim_clear_error();
+    if (!s) return dec_fail(who, "NULL state", 0, 0, 0);
+    if (n_rows < 0 || n_rows > s->batch) return dec_fail(who, "n_rows %ld is outside [0, %ld]", n_rows, s->batch, 0);
+    if (!rows && n_rows > 0) return dec_fail(who, "rows is NULL with n_rows %ld", n_rows, 0, 0);
+    if (!rows) return nntk_shim_memset(s->d.i, 0, (size_t)s->batch * 4 * sizeof(int));
+    for (int i = 0; i < n_rows; ++i)
+        if (rows[i] < 0 || rows[i] >= s->batch) return dec_fail(who, "rows[%ld] = %ld is outside [0, %ld)", i, rows[i], s->batch);
+    if (n_rows == 0) return 0;
+    int *d_rows = s->d.i + 4 * (size_t)s->batch;
+    if (nntk_shim_upload_ints(d_rows, rows, n_rows)) return -1;
+    return nntk_shim_rnnt_dec_reset(s->d.i, d_rows, n_rows);      /* the started word of a row, as in the greedy state */
+}
+
+void nntk_rnnt_beam_state_destroy(NntkRnntBeamState s) {
+    if (!s) return;
+    if (s->d.score) nntk_shim_synchronize();
+    nntk_shim_free(s->d.score);
+    nntk_shim_free(s->d.f);
+    nntk_shim_free(s->d.lab);
+    nntk_shim_free(s->d.meta);
+    nntk_shim_free(s->d.i);
+    free(s);
+}
+
+/* everything a beam call can be refused for; ws NULL: the host-pointer form, which owns its workspace */
+static int beam_check_call(const char *who, NntkRnntDecoder d, NntkRnntBeamState state, const float *enc, int batch, int T,
+                           const int *n_frames, int beam_width, int nbest, int max_labels, const int *labels_out, const int *out_lengths,
+                           const float *scores, const float *ws, int device_form) {
+    if (!d) return dec_fail(who, "NULL decoder", 0, 0, 0);
+    if (batch < 0 || T < 0) return dec_fail(who, "batch %ld, T %ld: neither may be negative", batch, T, 0);
+    if (beam_width < 1 || beam_width > NNTK_RNNT_BEAM_MAX_W)
+        return dec_fail(who, "beam_width %ld is outside [1, %ld]", beam_width, NNTK_RNNT_BEAM_MAX_W, 0);
+    if (nbest < 1 || nbest > beam_width) return dec_fail(who, "nbest %ld is outside [1, beam_width %ld]", nbest, beam_width, 0);
+    if (max_labels < 1) return dec_fail(who, "max_labels %ld < 1", max_labels, 0, 0);
+    if (state && state->dec != d) return dec_fail(who, "the state belongs to another decoder", 0, 0, 0);
+    if (state && state->batch != batch) return dec_fail(who, "batch %ld differs from the state's %ld", batch, state->batch, 0);
+    if (state && state->width != beam_width)
+        return dec_fail(who, "beam_width %ld differs from the state's %ld", beam_width, state->width, 0);
+    if (state && state->max_labels != max_labels)
+        return dec_fail(who, "max_labels %ld differs from the state's %ld", max_labels, state->max_labels, 0);
+    if (batch == 0) return 0;
+    for (int b = 0; n_frames && b < batch; ++b)
+        if (n_frames[b] < 0 || n_frames[b] > T) return dec_fail(who, "n_frames[%ld] = %ld is outside [0, %ld]", b, n_frames[b], T);
+    if (T > 0 && dec_named_ptr(who, "enc", enc)) return -1;
+    if (dec_named_ptr(who, "labels_out", labels_out) || dec_named_ptr(who, "out_lengths", out_lengths) ||
+        dec_named_ptr(who, "scores", scores)) return -1;
+    if (device_form) {
+        char msg[240];
+        if (!ws || ((uintptr_t)ws & 15)) {
+            snprintf(msg, sizeof msg, ws ? "%s: workspace is not 16-byte aligned" : "%s: workspace is NULL", who);
+            nntk_set_error(msg);
+            return -1;
+        }
+    }
+    const size_t nh = (size_t)batch * nbest;
+    const void *p[5] = { labels_out, out_lengths, scores, enc, ws };
+    const size_t n[5] = { nh * max_labels * sizeof(int), nh * sizeof(int), nh * sizeof(float), (size_t)batch * T * d->cfg.J * sizeof(float),
+                          device_form ? nntk_rnnt_beam_workspace_floats(d, batch, beam_width, max_labels) * sizeof(float) : 0 };
+    static const char *const name[5] = { "labels_out", "out_lengths", "scores", "enc", "workspace" };
+    for (int i = 0; i < 3; ++i)
+        for (int j = i + 1; j < 5; ++j)
+            if (dec_overlap(p[i], n[i], p[j], n[j])) {
+                char msg[240];
+                snprintf(msg, sizeof msg, "%s: %s overlaps %s", who, name[i], name[j]);
+                nntk_set_error(msg);
+                return -1;
+            }
+    if (!nntk_shim_rnnt_beam_fits(d->cfg.H, d->cfg.J, d->cfg.V))
+        return dec_fail(who, "the model (H %ld, J %ld, V %ld) is beyond the beam kernel's LDS", d->cfg.H, d->cfg.J, d->cfg.V);
+    return 0;
+}
+
+int nntk_rnnt_beam_decode_device(NntkRnntDecoder d, NntkRnntBeamState state, const float *d_enc, int batch, int T, const int *n_frames,
+                                 int beam_width, int nbest, int max_labels, int *d_labels_out, int *d_out_lengths, float *d_scores,
+                                 float *d_workspace) {
+    static const char who[] = "nntk_rnnt_beam_decode_device";
+    nntk_shim_clear_error();
+    if (beam_check_call(who, d, state, d_enc, batch, T, n_frames, beam_width, nbest, max_labels, d_labels_out, d_out_lengths, d_scores,
+                        d_workspace, 1)) return -1;
+    if (batch == 0) return 0;
+    int *len = (int *)malloc((size_t)batch * sizeof(int));
+    if (!len) NNTK_FAIL("nntk_rnnt_beam_decode_device: out of host memory");
+    for (int b = 0; b < batch; ++b) len[b] = n_frames ? n_frames[b] : T;
+    const nntk_shim_rnnt_dec m = { d->d_table, d->d_U, d->d_proj, d->d_out, d->cfg.V, d->cfg.blank, d->cfg.E, d->cfg.H, d->cfg.J,
+                                   d->cfg.joint_activation, d->cfg.max_symbols_per_frame };
+    int rc = nntk_shim_rnnt_beam(&m, d_enc, batch, T, len, beam_width, nbest, max_labels, state ? &state->d : NULL, d_labels_out,
+                                 d_out_lengths, d_scores, d_workspace);
+    free(len);
+    return rc;
+}
+
+int nntk_rnnt_beam_decode(NntkRnntDecoder d, NntkRnntBeamState state, const float *enc, int batch, int T, const int *n_frames,
+                          int beam_width, int nbest, int max_labels, int *labels_out, int *out_lengths, float *scores) {
+    static const char who[] = "nntk_rnnt_beam_decode";
+    nntk_shim_clear_error();
+    if (beam_check_call(who, d, state, enc, batch, T, n_frames, beam_width, nbest, max_labels, labels_out, out_lengths, scores, NULL, 0))
+        return -1;
+    if (batch == 0) return 0;
+    const size_t ne = (size_t)batch * T * d->cfg.J, nh = (size_t)batch * nbest, nl = nh * max_labels;
+    float *d_enc = nntk_devbuf_reserve(&t_a, ne + 4);
+    int *d_lab = (int *)nntk_devbuf_reserve(&t_b, nl + 2 * nh + 4);
+    float *d_ws = nntk_devbuf_reserve(nntk_thread_scratch(NNTK_TS_C), nntk_rnnt_beam_workspace_floats(d, batch, beam_width, max_labels));
+    if (!d_enc || !d_lab || !d_ws) return -1;
+    int *d_len = d_lab + nl;
+    float *d_sc = (float *)(d_len + nh);
+    if (ne && nntk_shim_upload(d_enc, enc, ne * sizeof(float))) return -1;
+    if (nntk_rnnt_beam_decode_device(d, state, d_enc, batch, T, n_frames, beam_width, nbest, max_labels, d_lab, d_len, d_sc, d_ws)) return -1;
+    if (nntk_shim_download(labels_out, d_lab, nl * sizeof(int))) return -1;
+    if (nntk_shim_download(out_lengths, d_len, nh * sizeof(int))) return -1;
+    return nntk_shim_download(scores, d_sc, nh * sizeof(float));
 }

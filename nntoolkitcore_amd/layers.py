@@ -1082,6 +1082,37 @@ class RnntDecoder:
             max_labels = max(1, self.max_symbols * T)
         return self._decode(None, enc, n_frames, max_labels, self._outputs(enc.device, B, max_labels))
 
+    def _beam_outputs(self, device, B, nbest, max_labels):
+        import torch
+        return (torch.empty((B, nbest, max_labels), dtype=torch.int32, device=device),
+                torch.empty((B, nbest), dtype=torch.int32, device=device), torch.empty((B, nbest), dtype=torch.float32, device=device))
+
+    def _beam_workspace(self, device, B, beam_width, max_labels):
+        import torch
+        need = capi.load().nntk_rnnt_beam_workspace_floats(self.h, B, int(beam_width), int(max_labels))
+        return torch.empty(max(int(need), 4), dtype=torch.float32, device=device)
+
+    def _beam(self, state, enc, n_frames, beam_width, nbest, max_labels, outs, workspace):
+        B, T, J = enc.shape
+        assert J == self.J, "enc: [B, T, J]"
+        nf = None if n_frames is None else _host_ints(n_frames, B, "n_frames")
+        labels, lengths, scores = outs
+        check(capi.load().nntk_rnnt_beam_decode_device(self.h, state, _dp(enc), B, T, nf.ctypes.data_as(capi.ip) if nf is not None else None,
+                                                       int(beam_width), int(nbest), int(max_labels), _ipv(labels), _ipv(lengths),
+                                                       _dp(scores), _dp(workspace)), "nntk_rnnt_beam_decode_device")
+        return outs
+
+    def beam_decode(self, enc, n_frames=None, beam_width=8, nbest=1, max_labels=None):
+        """``nntk_rnnt_beam_decode_device`` (INTEGRATION.md "RNN-Transducer: beam search"): enc [B, T, J] device tensor, n_frames host
+        ints per row (None: T) -> (labels [B, nbest, max_labels] int32, -1 behind each hypothesis's labels; lengths [B, nbest] int32,
+        -1 for a slot without a hypothesis; scores [B, nbest] float32, -inf there).  max_labels defaults to
+        max_symbols_per_frame * T, which never truncates."""
+        B, T, _ = enc.shape
+        if max_labels is None:
+            max_labels = max(1, self.max_symbols * T)
+        return self._beam(None, enc, n_frames, beam_width, nbest, max_labels, self._beam_outputs(enc.device, B, nbest, max_labels),
+                          self._beam_workspace(enc.device, B, beam_width, max_labels))
+
     def destroy(self):
         if self.h:
             capi.load().nntk_rnnt_decoder_destroy(self.h)
@@ -1131,6 +1162,70 @@ class RnntGreedyStream:
             self.close()
         except Exception:
             pass
+
+
+class RnntBeamStream:
+    """``nntk_rnnt_beam_state_*``: transducer beam search pushed chunk by chunk for ``batch`` independent streams.  After every push
+    row b holds what ``decoder.beam_decode`` gives on the row's frames since its last reset, bit for bit.  The stream owns the output
+    buffers (labels [batch, nbest, max_labels]; lengths, scores [batch, nbest]) and the workspace, and returns the outputs from every
+    push."""
+
+    def __init__(self, decoder, batch, beam_width, nbest, max_labels):
+        self.dec, self.B, self.W, self.nbest, self.max_labels = decoder, int(batch), int(beam_width), int(nbest), int(max_labels)
+        self.outs = self.ws = None
+        self.h = capi.load().nntk_rnnt_beam_state_create(decoder.h, self.B, self.W, self.max_labels)
+        if not self.h:
+            raise capi.NNTKError("nntk_rnnt_beam_state_create: " + capi.last_error())
+
+    def push(self, enc_chunk, n_frames):
+        """enc_chunk [batch, T, J] device tensor, n_frames host ints per row (0 allowed) -> (labels, lengths, scores)"""
+        assert enc_chunk.shape[0] == self.B, "enc_chunk: [batch, T, J]"
+        if self.outs is None:
+            self.outs = self.dec._beam_outputs(enc_chunk.device, self.B, self.nbest, self.max_labels)
+            self.ws = self.dec._beam_workspace(enc_chunk.device, self.B, self.W, self.max_labels)
+        return self.dec._beam(self.h, enc_chunk, n_frames, self.W, self.nbest, self.max_labels, self.outs, self.ws)
+
+    def reset(self, rows=None):
+        """these rows (None: every row) start new streams"""
+        if rows is None:
+            check(capi.load().nntk_rnnt_beam_state_reset(self.h, None, 0), "nntk_rnnt_beam_state_reset")
+            return
+        rows = np.ascontiguousarray(np.asarray(rows, dtype=np.int32).reshape(-1))
+        check(capi.load().nntk_rnnt_beam_state_reset(self.h, rows.ctypes.data_as(capi.ip), rows.shape[0]), "nntk_rnnt_beam_state_reset")
+
+    def close(self):
+        if self.h:
+            capi.load().nntk_rnnt_beam_state_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def rnnt_beam_decode(embed, lstm_block, pred_proj, out, enc, n_frames=None, beam_width=8, nbest=1, max_labels=None, blank=0,
+                     joint_activation=ACT_TANH, max_symbols_per_frame=10):
+    """Transducer beam search on numpy arrays (the weights go to the device, ``nntk_rnnt_beam_decode`` takes enc and the results as
+    host memory): enc [B, T, J] -> (labels [B, nbest, max_labels], lengths [B, nbest], scores [B, nbest])"""
+    import torch
+    dev = lambda a: None if a is None else torch.from_numpy(_f32(a).reshape(-1) if a is not embed else _f32(a)).cuda()
+    dec = RnntDecoder(dev(embed), dev(lstm_block), dev(pred_proj), dev(out), blank, joint_activation, max_symbols_per_frame)
+    enc = _f32(enc)
+    B, T, _ = enc.shape
+    if max_labels is None:
+        max_labels = max(1, dec.max_symbols * T)
+    nf = None if n_frames is None else _host_ints(n_frames, B, "n_frames")
+    labels = np.empty((B, nbest, max_labels), np.int32)
+    lengths, scores = np.empty((B, nbest), np.int32), np.empty((B, nbest), np.float32)
+    try:
+        check(capi.load().nntk_rnnt_beam_decode(dec.h, None, _p(enc), B, T, nf.ctypes.data_as(capi.ip) if nf is not None else None,
+                                                int(beam_width), int(nbest), int(max_labels), labels.ctypes.data_as(capi.ip),
+                                                lengths.ctypes.data_as(capi.ip), _p(scores)), "nntk_rnnt_beam_decode")
+    finally:
+        dec.destroy()
+    return labels, lengths, scores
 
 
 def rnnt_greedy_decode(embed, lstm_block, pred_proj, out, enc, n_frames=None, max_labels=None, blank=0, joint_activation=ACT_TANH,
