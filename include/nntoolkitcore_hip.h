@@ -1066,6 +1066,37 @@ int nntk_rnnt_joint_device(const float *d_enc, const float *d_pred, int batch, i
 int nntk_rnnt_joint_backward_device(const float *d_out_fwd, const float *d_dout, int batch, int T, int U1, int J, int activation,
                                     float *d_denc, float *d_dpred);
 
+/* ---- RNN-Transducer: fused training loss (csrc/hip/rnnt_fused.hip; INTEGRATION.md "RNN-Transducer: fused training loss") ----
+ * Joiner, vocabulary projection and loss in one call: with logits[b][t][u] = act(d_enc[b][t] + d_pred[b][u]) W + b, d_loss_rows[b] is
+ * what nntk_rnnt_loss_device defines on those logits -- which are never stored, and neither is their gradient.
+ *   d_enc [batch][T][J], d_pred [batch][U1 = max_label_len + 1][J]; d_out: the Dense block W [J,V] row-major | b [V], the layout
+ *     nntk_rnnt_decoder_create takes; activation 0 identity, 1 tanh, 2 relu, as in nntk_rnnt_joint_device.  Cells with t >= T_b or
+ *     u > U_b influence nothing: enc / pred may hold NaN there, and none of it reaches any output.
+ *   input_lengths / labels / label_lengths: HOST memory, exactly the checks of nntk_rnnt_loss_device.
+ *   d_denc [batch][T][J], d_dpred [batch][U1][J], d_dout [J V + V] (laid out like d_out): all three NULL (loss only) or all three given;
+ *     the gradients of the PLAIN SUM of the loss rows (no averaging), overwritten, every element written; exact zeros in d_denc for
+ *     t >= T_b, in d_dpred for u > U_b, and from a row with P = 0.
+ *   d_workspace: nntk_rnnt_fused_workspace_floats(batch, T, max_label_len, J, V, want_grad) floats, 16-byte aligned.  In floats, with
+ *     cells = batch T U1: nntk_rnnt_workspace_floats(batch, T, max_label_len, want_grad) -- the per-cell scalars: 4 per cell, 6 more with a
+ *     gradient, and the host arrays -- and, with a gradient only, cells J (d z act', the one tensor of the joiner's size) +
+ *     J V (W transposed) + 32 (J + 1) V (32 partial blocks of d_dout, added in order: a constant number, whatever the batch, T and
+ *     the labels).  Every part is rounded up to 16 bytes.  Nothing of
+ *     batch T U1 V elements exists anywhere.
+ * Refused on the host before anything is enqueued (-1, nntk_last_error(), nothing written, no device needed): everything
+ * nntk_rnnt_loss_device and nntk_rnnt_joint_device refuse; J outside [1, 1024]; V above 8192; gradient pointers only partly given; a NULL
+ * tensor; a workspace that is not 16-byte aligned; an output overlapping another output, an input or the workspace.
+ * Deterministic: no atomics, the same bits on every call, the same loss bits with and without a gradient; a row's loss, d_denc and
+ * d_dpred bits do not depend on the other rows, on the row's position in the batch or on the T / max_label_len padding.  The products
+ * run on the exact-f32 MFMA (f32 inputs, one fmaf chain per element).  Runs on the calling thread's stream and reads nothing back; the
+ * host-pointer form uploads, runs the device form and downloads. */
+size_t nntk_rnnt_fused_workspace_floats(int batch, int T, int max_label_len, int J, int V, int want_grad);
+int nntk_rnnt_fused_loss_device(const float *d_enc, const float *d_pred, const float *d_out, int batch, int T, int J, int V, int activation,
+                                const int *input_lengths, const int *labels, const int *label_lengths, int max_label_len, int blank,
+                                float *d_loss_rows, float *d_denc, float *d_dpred, float *d_dout, float *d_workspace);
+int nntk_rnnt_fused_loss(const float *enc, const float *pred, const float *out, int batch, int T, int J, int V, int activation,
+                         const int *input_lengths, const int *labels, const int *label_lengths, int max_label_len, int blank,
+                         float *loss_rows, float *denc, float *dpred, float *dout);
+
 /* ---- RNN-Transducer: greedy decoding (csrc/hip/rnnt_decode.hip; INTEGRATION.md "RNN-Transducer: greedy decoding") ----
  * The model: a one-layer LSTM prediction network over a label embedding, a linear projection to the joiner width, the joiner of
  * nntk_rnnt_joint_device and a vocabulary Dense.  V classes, embedding width E, hidden width H, joiner width J; caller-owned device blocks:

@@ -466,6 +466,11 @@ SIGNATURES = {
     "nntk_rnnt_loss": (C.c_int, [fp, C.c_int, C.c_int, C.c_int, ip, ip, ip, C.c_int, C.c_int, fp, fp]),
     "nntk_rnnt_joint_device": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
     "nntk_rnnt_joint_backward_device": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),
+    "nntk_rnnt_fused_workspace_floats": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "nntk_rnnt_fused_loss_device": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, ip, ip, ip, C.c_int, C.c_int,
+                                              vp, vp, vp, vp, vp]),
+    "nntk_rnnt_fused_loss": (C.c_int, [fp, fp, fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, ip, ip, ip, C.c_int, C.c_int,
+                                       fp, fp, fp, fp]),
     # RNN-Transducer: greedy decoding, one-shot and streamed (INTEGRATION.md "RNN-Transducer: greedy decoding")
     "nntk_rnnt_decoder_create": (vp, [NntkRnntDecoderConfig, vp, vp, vp, vp]),
     "nntk_rnnt_decoder_load_weights_device": (C.c_int, [vp, vp, vp, vp, vp]),

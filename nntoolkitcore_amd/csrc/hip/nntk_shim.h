@@ -210,6 +210,16 @@ int nntk_shim_rnnt_loss(const float *d_logits, int B, int T, int V, const int *h
 int nntk_shim_rnnt_joint(const float *d_enc, const float *d_pred, int B, int T, int U1, int J, int kind, float *d_out);
 int nntk_shim_rnnt_joint_backward(const float *d_out_fwd, const float *d_dout, int B, int T, int U1, int J, int kind, float *d_denc,
                                   float *d_dpred);
+/* ---- the fused transducer training loss (rnnt_fused.hip): joiner, vocabulary projection and loss from enc [B][T][J], pred [B][U1][J] and
+ *      the Dense block W [J,V] | b [V]; the three gradient pointers all NULL = loss only.  Host int arrays as for nntk_shim_rnnt_loss,
+ *      already checked by the caller (rnnt.c).  The limits: a tile's 32 rows of z (J floats each) and a group of g columns share one
+ *      workgroup's LDS; V only bounds the partial blocks of d W. ---- */
+#define NNTK_RNNT_FUSED_MAX_J 1024
+#define NNTK_RNNT_FUSED_MAX_V 8192
+size_t nntk_shim_rnnt_fused_workspace_floats(int batch, int T, int max_label_len, int J, int V, int want_grad);
+int nntk_shim_rnnt_fused_loss(const float *d_enc, const float *d_pred, const float *d_out, int B, int T, int J, int V, int kind,
+                              const int *h_input_lengths, const int *h_labels, const int *h_label_lengths, int max_label_len, int blank,
+                              float *d_loss_rows, float *d_denc, float *d_dpred, float *d_dout, float *d_ws);
 /* ---- greedy transducer decoding (rnnt_decode.hip).  The limits, stated once for the host's checks (rnnt_decode.c) and the launcher: a
  *      row's h, c, g, joiner output and max(4H, V) logits / gate pre-activations live in one workgroup's LDS (48 KiB at the limits), and
  *      the folded input table is V x 4H floats (128 MiB at the limits).  Batches above NNTK_RNNT_DEC_GROUP_BATCH rows put

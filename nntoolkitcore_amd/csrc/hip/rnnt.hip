@@ -18,30 +18,9 @@
 //    the two outgoing flows), then V scores in and g[v] = A exp(x[v] - lse) - [v = blank] flow_blank - [v = label] flow_label out.
 //    Padding cells (t >= T_b or u > U_b) are zero-filled with 16-byte stores.
 // No atomics anywhere; every reduction is a fixed butterfly or a fixed-order loop.
-#include <stdint.h>
-#include "nntk_common.hpp"
-#include "ctc_xf.hpp"
+#include "rnnt_common.hpp"                 // the workspace layout, the emission, the cell index, the activation: shared with rnnt_fused.hip
 
-#define RNNT_EMIN (-4000)                 // floor of an emission's base-2 exponent: NNTK_RNNT_MAX_DIAGONALS * 4000 < 2^28 = -CTC_EZERO
-#define RNNT_MAX_GRID (1 << 20)
 #define RNNT_JOINT_UNROLL 4               // terms of a joiner-backward sum loaded together (added in ascending order all the same)
-
-// workspace, in 4-byte words: [ints: input lengths B | label lengths B | labels B*maxL] [P per row: 2B] [emissions: 4 per cell]
-// with a gradient: [lse: 2 per cell] [alpha: 2 per cell] [beta: 2 per cell]; every part starts on a 16-byte boundary
-struct RnntLayout { size_t hdr, em, lse, alpha, beta, total; };
-static RnntLayout rnnt_layout(int B, int T, int maxL, int want_grad) {
-    RnntLayout l;
-    const size_t b = B > 0 ? (size_t)B : 0, t = T > 0 ? (size_t)T : 0, ml = maxL > 0 ? (size_t)maxL : 0;
-    auto up = [](size_t x) { return (x + 3) & ~(size_t)3; };
-    const size_t cells = b * t * (ml + 1);
-    l.hdr = up(b * (2 + ml));
-    l.em = l.hdr + up(2 * b);
-    l.lse = l.em + 4 * cells;
-    l.alpha = l.lse + (want_grad ? up(2 * cells) : 0);
-    l.beta = l.alpha + (want_grad ? up(2 * cells) : 0);
-    l.total = l.beta + (want_grad ? up(2 * cells) : 0) + 4;
-    return l;
-}
 
 __device__ __forceinline__ float rnnt_wave_max(float v) {
     for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off));
@@ -50,26 +29,6 @@ __device__ __forceinline__ float rnnt_wave_max(float v) {
 __device__ __forceinline__ double rnnt_wave_sum(double v) {
     for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
     return v;
-}
-
-// exp(x - lse) as mantissa and exponent; -inf (and NaN) scores: zero
-__device__ __forceinline__ xf rnnt_emission(float x, double lse) {
-    if (!(x > -INFINITY)) return xf_zero();
-    double l2 = ((double)x - lse) * 1.44269504088896340736;
-    l2 = l2 < (double)RNNT_EMIN ? (double)RNNT_EMIN : l2;
-    const double fl = floor(l2);
-    return xf_norm(exp2f((float)(l2 - fl)), (int)fl);
-}
-
-// cell c = (b * T + t) * U1 + u
-struct RnntCell { int b, t, u; };
-__device__ __forceinline__ RnntCell rnnt_cell(long c, int T, int U1) {
-    RnntCell r;
-    const long bt = c / U1;
-    r.u = (int)(c - bt * U1);
-    r.b = (int)(bt / T);
-    r.t = (int)(bt - (long)r.b * T);
-    return r;
 }
 
 // VEC: V % 4 == 0 and the tensor 16-byte aligned, so every row is: 16-byte loads
@@ -274,10 +233,6 @@ __global__ __launch_bounds__(CTC_THREADS) void rnnt_grad_kernel(const float *__r
 }
 
 // ---- the joiner: out[b][t][u][:] = act(enc[b][t][:] + pred[b][u][:]); activation 0 identity, 1 tanh (tanhf), 2 relu (max(x, 0)) ----
-__device__ __forceinline__ float rnnt_act(int kind, float x) { return kind == 1 ? tanhf(x) : kind == 2 ? fmaxf(x, 0.0f) : x; }
-// d act / d x from the activation's OUTPUT
-__device__ __forceinline__ float rnnt_dact(int kind, float o) { return kind == 1 ? 1.0f - o * o : kind == 2 ? (o > 0.0f ? 1.0f : 0.0f) : 1.0f; }
-
 // W = 4: J % 4 == 0 and the three tensors 16-byte aligned; n = elements / W
 template <int W>
 __global__ __launch_bounds__(256) void rnnt_joint_kernel(const float *__restrict__ enc, const float *__restrict__ pred, int T, int U1, int JW,
@@ -324,9 +279,23 @@ __global__ __launch_bounds__(256) void rnnt_joint_reduce_kernel(const float *__r
     }
 }
 
-static unsigned rnnt_grid(long items, long per_block) {
-    long g = (items + per_block - 1) / per_block;
-    return (unsigned)(g < 1 ? 1 : g > RNNT_MAX_GRID ? RNNT_MAX_GRID : g);
+// the lattice on the emissions, for this unit and for rnnt_fused.hip; wa / wb NULL: the forward direction alone
+int nntk_rnnt_lattice_launch(int B, int T, int U1, const int *d_ints, const float4 *em, float2 *wa, float2 *wb, float *hdr,
+                             float *d_loss_rows) {
+    const size_t lds = 2 * (size_t)U1 * sizeof(float4);
+    const dim3 grid((unsigned)B, wb ? 2 : 1);
+#define RNNT_AB(NJ)                                                                                                          \
+    do {                                                                                                                     \
+        if (lds > 48 * 1024 && nntk_set_max_dynamic_lds((const void *)rnnt_lattice_kernel<NJ>, lds)) return -1;               \
+        hipLaunchKernelGGL(rnnt_lattice_kernel<NJ>, grid, dim3(CTC_THREADS), lds, nntk_stream(), B, T, U1, d_ints, em, wa, wb, \
+                           hdr, d_loss_rows);                                                                                \
+    } while (0)
+    if (U1 <= CTC_THREADS) RNNT_AB(1);
+    else if (U1 <= 2 * CTC_THREADS) RNNT_AB(2);
+    else RNNT_AB(0);
+#undef RNNT_AB
+    NNTK_LAUNCH_CHECK("rnnt_lattice_kernel");
+    return 0;
 }
 
 extern "C" {
@@ -360,19 +329,7 @@ int nntk_shim_rnnt_loss(const float *d_logits, int B, int T, int V, const int *h
     else
         hipLaunchKernelGGL(rnnt_emit_kernel<false>, cgrid, dim3(CTC_THREADS), 0, nntk_stream(), d_logits, B, T, U1, V, blank, d_ints, em, lse, cells);
     NNTK_LAUNCH_CHECK("rnnt_emit_kernel");
-    const size_t lds = 2 * (size_t)U1 * sizeof(float4);
-    const dim3 grid((unsigned)B, d_dlogits ? 2 : 1);
-#define RNNT_AB(NJ)                                                                                                          \
-    do {                                                                                                                     \
-        if (lds > 48 * 1024 && nntk_set_max_dynamic_lds((const void *)rnnt_lattice_kernel<NJ>, lds)) return -1;               \
-        hipLaunchKernelGGL(rnnt_lattice_kernel<NJ>, grid, dim3(CTC_THREADS), lds, nntk_stream(), B, T, U1, d_ints, em, wa, wb, \
-                           hdr, d_loss_rows);                                                                                \
-    } while (0)
-    if (U1 <= CTC_THREADS) RNNT_AB(1);
-    else if (U1 <= 2 * CTC_THREADS) RNNT_AB(2);
-    else RNNT_AB(0);
-#undef RNNT_AB
-    NNTK_LAUNCH_CHECK("rnnt_lattice_kernel");
+    if (nntk_rnnt_lattice_launch(B, T, U1, d_ints, em, wa, wb, hdr, d_loss_rows)) return -1;
     if (d_dlogits) {
         if (vec)
             hipLaunchKernelGGL(rnnt_grad_kernel<true>, cgrid, dim3(CTC_THREADS), 0, nntk_stream(), d_logits, B, T, U1, V, blank, d_ints, em, lse,

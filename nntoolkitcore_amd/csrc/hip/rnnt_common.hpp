@@ -1,0 +1,62 @@
+// rnnt_common.hpp -- what the two transducer-loss units share (rnnt.hip: the loss on a stored score tensor; rnnt_fused.hip: the loss
+// that makes its scores from the joiner's inputs and never stores them): the workspace layout of the per-cell scalars, the emission
+// as mantissa and exponent, the cell index, the joiner's activation, and the launchers of the kernels that rnnt.hip owns and
+// rnnt_fused.hip reuses unchanged (the lattice and the joiner's backward reduction).
+#pragma once
+#include <stdint.h>
+#include "nntk_common.hpp"
+#include "ctc_xf.hpp"
+
+#define RNNT_EMIN (-4000)                 // floor of an emission's base-2 exponent: NNTK_RNNT_MAX_DIAGONALS * 4000 < 2^28 = -CTC_EZERO
+#define RNNT_MAX_GRID (1 << 20)
+
+// workspace, in 4-byte words: [ints: input lengths B | label lengths B | labels B*maxL] [P per row: 2B] [emissions: 4 per cell]
+// with a gradient: [lse: 2 per cell] [alpha: 2 per cell] [beta: 2 per cell]; every part starts on a 16-byte boundary
+struct RnntLayout { size_t hdr, em, lse, alpha, beta, total; };
+static inline RnntLayout rnnt_layout(int B, int T, int maxL, int want_grad) {
+    RnntLayout l;
+    const size_t b = B > 0 ? (size_t)B : 0, t = T > 0 ? (size_t)T : 0, ml = maxL > 0 ? (size_t)maxL : 0;
+    auto up = [](size_t x) { return (x + 3) & ~(size_t)3; };
+    const size_t cells = b * t * (ml + 1);
+    l.hdr = up(b * (2 + ml));
+    l.em = l.hdr + up(2 * b);
+    l.lse = l.em + 4 * cells;
+    l.alpha = l.lse + (want_grad ? up(2 * cells) : 0);
+    l.beta = l.alpha + (want_grad ? up(2 * cells) : 0);
+    l.total = l.beta + (want_grad ? up(2 * cells) : 0) + 4;
+    return l;
+}
+
+// exp(x - lse) as mantissa and exponent; -inf (and NaN) scores: zero
+__device__ __forceinline__ xf rnnt_emission(float x, double lse) {
+    if (!(x > -INFINITY)) return xf_zero();
+    double l2 = ((double)x - lse) * 1.44269504088896340736;
+    l2 = l2 < (double)RNNT_EMIN ? (double)RNNT_EMIN : l2;
+    const double fl = floor(l2);
+    return xf_norm(exp2f((float)(l2 - fl)), (int)fl);
+}
+
+// cell c = (b * T + t) * U1 + u
+struct RnntCell { int b, t, u; };
+__device__ __forceinline__ RnntCell rnnt_cell(long c, int T, int U1) {
+    RnntCell r;
+    const long bt = c / U1;
+    r.u = (int)(c - bt * U1);
+    r.b = (int)(bt / T);
+    r.t = (int)(bt - (long)r.b * T);
+    return r;
+}
+
+// ---- the joiner: out[b][t][u][:] = act(enc[b][t][:] + pred[b][u][:]); activation 0 identity, 1 tanh (tanhf), 2 relu (max(x, 0)) ----
+__device__ __forceinline__ float rnnt_act(int kind, float x) { return kind == 1 ? tanhf(x) : kind == 2 ? fmaxf(x, 0.0f) : x; }
+// d act / d x from the activation's OUTPUT
+__device__ __forceinline__ float rnnt_dact(int kind, float o) { return kind == 1 ? 1.0f - o * o : kind == 2 ? (o > 0.0f ? 1.0f : 0.0f) : 1.0f; }
+
+static inline unsigned rnnt_grid(long items, long per_block) {
+    long g = (items + per_block - 1) / per_block;
+    return (unsigned)(g < 1 ? 1 : g > RNNT_MAX_GRID ? RNNT_MAX_GRID : g);
+}
+
+// rnnt.hip: rnnt_lattice_kernel on the emissions em [cells] (float4 each); wa / wb NULL = the forward direction alone (loss only)
+int nntk_rnnt_lattice_launch(int B, int T, int U1, const int *d_ints, const float4 *em, float2 *wa, float2 *wb, float *hdr,
+                             float *d_loss_rows);

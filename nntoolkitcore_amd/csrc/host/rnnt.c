@@ -129,3 +129,90 @@ int nntk_rnnt_joint_backward_device(const float *d_out_fwd, const float *d_dout,
         rnnt_check_ptr(who, "d_denc", d_denc, 4) || rnnt_check_ptr(who, "d_dpred", d_dpred, 4)) return -1;
     return nntk_shim_rnnt_joint_backward(d_out_fwd, d_dout, batch, T, U1, J, activation, d_denc, d_dpred);
 }
+
+/* ---- the fused training loss: joiner + vocabulary projection + loss, the scores never stored (csrc/hip/rnnt_fused.hip) ---- */
+static int fused_check(const char *who, int batch, int T, int J, int V, int activation, const int *input_lengths, const int *labels,
+                       const int *label_lengths, int max_label_len, int blank, const void *denc, const void *dpred, const void *ddout) {
+    if (rnnt_check(who, batch, T, V, input_lengths, labels, label_lengths, max_label_len, blank)) return -1;
+    if (joint_check(who, batch, T, max_label_len + 1, J, activation)) return -1;
+    if (J < 1 || J > NNTK_RNNT_FUSED_MAX_J) return rnnt_fail(who, "J %d is outside [1, %d]", J, NNTK_RNNT_FUSED_MAX_J, 0);
+    if (V > NNTK_RNNT_FUSED_MAX_V) return rnnt_fail(who, "V %d is more than %d", V, NNTK_RNNT_FUSED_MAX_V, 0);
+    const int given = (denc != NULL) + (dpred != NULL) + (ddout != NULL);
+    if (given != 0 && given != 3)
+        return rnnt_fail(who, "the gradient outputs d_denc, d_dpred, d_dout are all NULL or all given (%d of 3 are)", given, 0, 0);
+    return 0;
+}
+
+typedef struct { const char *name; uintptr_t at; size_t bytes; } fused_span;
+
+size_t nntk_rnnt_fused_workspace_floats(int batch, int T, int max_label_len, int J, int V, int want_grad) {
+    return nntk_shim_rnnt_fused_workspace_floats(batch, T, max_label_len, J, V, want_grad != 0);
+}
+
+int nntk_rnnt_fused_loss_device(const float *d_enc, const float *d_pred, const float *d_out, int batch, int T, int J, int V, int activation,
+                                const int *input_lengths, const int *labels, const int *label_lengths, int max_label_len, int blank,
+                                float *d_loss_rows, float *d_denc, float *d_dpred, float *d_dout, float *d_workspace) {
+    static const char who[] = "nntk_rnnt_fused_loss_device";
+    nntk_shim_clear_error();
+    if (fused_check(who, batch, T, J, V, activation, input_lengths, labels, label_lengths, max_label_len, blank, d_denc, d_dpred, d_dout))
+        return -1;
+    if (batch == 0) return 0;
+    if (rnnt_check_ptr(who, "d_enc", d_enc, 4) || rnnt_check_ptr(who, "d_pred", d_pred, 4) || rnnt_check_ptr(who, "d_out", d_out, 4) ||
+        rnnt_check_ptr(who, "d_loss_rows", d_loss_rows, 4) || rnnt_check_ptr(who, "d_workspace", d_workspace, 16) ||
+        (d_denc && (rnnt_check_ptr(who, "d_denc", d_denc, 4) || rnnt_check_ptr(who, "d_dpred", d_dpred, 4) ||
+                    rnnt_check_ptr(who, "d_dout", d_dout, 4)))) return -1;
+    const size_t U1 = (size_t)max_label_len + 1, f = sizeof(float);
+    const size_t ne = (size_t)batch * T * J, npd = (size_t)batch * U1 * J, nw = ((size_t)J + 1) * V;
+    /* outputs first: each of them against everything after it */
+    const fused_span sp[] = {{"d_loss_rows", (uintptr_t)d_loss_rows, (size_t)batch * f}, {"d_denc", (uintptr_t)d_denc, ne * f},
+                             {"d_dpred", (uintptr_t)d_dpred, npd * f}, {"d_dout", (uintptr_t)d_dout, nw * f},
+                             {"d_enc", (uintptr_t)d_enc, ne * f}, {"d_pred", (uintptr_t)d_pred, npd * f}, {"d_out", (uintptr_t)d_out, nw * f},
+                             {"d_workspace", (uintptr_t)d_workspace,
+                              nntk_shim_rnnt_fused_workspace_floats(batch, T, max_label_len, J, V, d_denc != NULL) * f}};
+    for (int o = 0; o < 4; ++o)
+        for (int k = o + 1; k < 8; ++k)
+            if (sp[o].at && sp[k].at && sp[o].at < sp[k].at + sp[k].bytes && sp[k].at < sp[o].at + sp[o].bytes) {
+                char msg[200];
+                snprintf(msg, sizeof msg, "%s: %s overlaps %s", who, sp[o].name, sp[k].name);
+                nntk_set_error(msg);
+                return -1;
+            }
+    int *len = (int *)malloc((size_t)batch * sizeof(int));
+    if (!len) NNTK_FAIL("out of host memory");
+    for (int b = 0; b < batch; ++b) len[b] = input_lengths ? input_lengths[b] : T;
+    int rc = nntk_shim_rnnt_fused_loss(d_enc, d_pred, d_out, batch, T, J, V, activation, len, labels, label_lengths, max_label_len, blank,
+                                       d_loss_rows, d_denc, d_dpred, d_dout, d_workspace);
+    free(len);
+    return rc;
+}
+
+int nntk_rnnt_fused_loss(const float *enc, const float *pred, const float *out, int batch, int T, int J, int V, int activation,
+                         const int *input_lengths, const int *labels, const int *label_lengths, int max_label_len, int blank,
+                         float *loss_rows, float *denc, float *dpred, float *dout) {
+    static const char who[] = "nntk_rnnt_fused_loss";
+    nntk_shim_clear_error();
+    if (fused_check(who, batch, T, J, V, activation, input_lengths, labels, label_lengths, max_label_len, blank, denc, dpred, dout)) return -1;
+    if (batch == 0) return 0;
+    if (rnnt_check_ptr(who, "enc", enc, 4) || rnnt_check_ptr(who, "pred", pred, 4) || rnnt_check_ptr(who, "out", out, 4) ||
+        rnnt_check_ptr(who, "loss_rows", loss_rows, 4) ||
+        (denc && (rnnt_check_ptr(who, "denc", denc, 4) || rnnt_check_ptr(who, "dpred", dpred, 4) || rnnt_check_ptr(who, "dout", dout, 4))))
+        return -1;
+    const size_t up = 3, U1 = (size_t)max_label_len + 1;
+    const size_t ne = ((size_t)batch * T * J + up) & ~up, npd = ((size_t)batch * U1 * J + up) & ~up, nw = (((size_t)J + 1) * V + up) & ~up;
+    const size_t nl = ((size_t)batch + up) & ~up;
+    /* inputs | loss rows in one block, the gradients in a second, the workspace in a third */
+    float *d_in = nntk_devbuf_reserve(&t_a, ne + npd + nw + nl + 4);
+    float *d_g = denc ? nntk_devbuf_reserve(&t_b, ne + npd + nw + 4) : NULL;
+    float *d_ws = nntk_devbuf_reserve(&t_c, nntk_shim_rnnt_fused_workspace_floats(batch, T, max_label_len, J, V, denc != NULL));
+    if (!d_in || (denc && !d_g) || !d_ws) return -1;
+    float *d_enc = d_in, *d_pred = d_in + ne, *d_out = d_pred + npd, *d_loss = d_out + nw;
+    if (nntk_shim_upload(d_enc, enc, (size_t)batch * T * J * sizeof(float)) || nntk_shim_upload(d_pred, pred, (size_t)batch * U1 * J * sizeof(float)) ||
+        nntk_shim_upload(d_out, out, ((size_t)J + 1) * V * sizeof(float))) return -1;
+    if (nntk_rnnt_fused_loss_device(d_enc, d_pred, d_out, batch, T, J, V, activation, input_lengths, labels, label_lengths, max_label_len, blank,
+                                    d_loss, d_g, d_g ? d_g + ne : NULL, d_g ? d_g + ne + npd : NULL, d_ws)) return -1;
+    if (nntk_shim_download(loss_rows, d_loss, (size_t)batch * sizeof(float))) return -1;
+    if (!denc) return 0;
+    if (nntk_shim_download(denc, d_g, (size_t)batch * T * J * sizeof(float)) ||
+        nntk_shim_download(dpred, d_g + ne, (size_t)batch * U1 * J * sizeof(float))) return -1;
+    return nntk_shim_download(dout, d_g + ne + npd, ((size_t)J + 1) * V * sizeof(float));
+}

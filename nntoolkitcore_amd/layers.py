@@ -1019,6 +1019,53 @@ def rnnt_joint_backward_device(out, dout, activation=ACT_TANH, denc=None, dpred=
     return denc, dpred
 
 
+def rnnt_fused_loss_device(enc, pred, out_block, labels, label_lengths=None, input_lengths=None, blank=0, activation=ACT_TANH, want_grad=True,
+                           loss=None, denc=None, dpred=None, dout=None, workspace=None):
+    """``nntk_rnnt_fused_loss_device``: enc [B,T,J], pred [B,U1,J] and the Dense block W [J,V] | b [V] (J V + V floats) as device tensors;
+    labels as for ``rnnt_loss_device``.  Returns (loss rows [B], d enc, d pred, d out_block), the gradients of the plain sum of the loss
+    rows (None without want_grad).  The [B,T,U1,V] logits are never stored."""
+    import torch
+    B, T, J = enc.shape
+    U1 = pred.shape[1]
+    assert tuple(pred.shape) == (B, U1, J), "pred: [B, U1, J] with enc's B and J"
+    assert out_block.numel() % (J + 1) == 0, "out_block: W [J, V] | b [V]"
+    V = out_block.numel() // (J + 1)
+    lab, ll = _rnnt_labels(labels, label_lengths, B, U1 - 1)
+    il, ilp = _ctc_lengths(input_lengths, B)
+    L = capi.load()
+    need = L.nntk_rnnt_fused_workspace_floats(B, T, U1 - 1, J, V, int(want_grad))
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.float32, device=enc.device)
+    assert workspace.numel() >= need, "workspace: nntk_rnnt_fused_workspace_floats(B, T, max_label_len, J, V, want_grad) floats"
+    if loss is None:
+        loss = torch.empty(B, dtype=torch.float32, device=enc.device)
+    if want_grad:
+        denc = torch.empty_like(enc) if denc is None else denc
+        dpred = torch.empty_like(pred) if dpred is None else dpred
+        dout = torch.empty_like(out_block) if dout is None else dout
+    check(L.nntk_rnnt_fused_loss_device(_dp(enc), _dp(pred), _dp(out_block), B, T, J, V, RNNT_ACTIVATIONS[activation], ilp,
+                                        lab.ctypes.data_as(capi.ip), ll.ctypes.data_as(capi.ip), U1 - 1, blank, _dp(loss),
+                                        _dp(denc) if want_grad else None, _dp(dpred) if want_grad else None,
+                                        _dp(dout) if want_grad else None, _dp(workspace)), "nntk_rnnt_fused_loss_device")
+    return (loss, denc, dpred, dout) if want_grad else (loss, None, None, None)
+
+
+def rnnt_fused_loss(enc, pred, out_block, labels, label_lengths=None, input_lengths=None, blank=0, activation=ACT_TANH, want_grad=True):
+    """The host-memory form (``nntk_rnnt_fused_loss``) on numpy arrays."""
+    enc, pred, out_block = _f32(enc), _f32(pred), _f32(out_block)
+    B, T, J = enc.shape
+    U1 = pred.shape[1]
+    V = out_block.size // (J + 1)
+    lab, ll = _rnnt_labels(labels, label_lengths, B, U1 - 1)
+    il, ilp = _ctc_lengths(input_lengths, B)
+    loss = np.empty(B, np.float32)
+    g = (np.empty_like(enc), np.empty_like(pred), np.empty_like(out_block)) if want_grad else (None, None, None)
+    check(capi.load().nntk_rnnt_fused_loss(_p(enc), _p(pred), _p(out_block), B, T, J, V, RNNT_ACTIVATIONS[activation], ilp,
+                                           lab.ctypes.data_as(capi.ip), ll.ctypes.data_as(capi.ip), U1 - 1, blank, _p(loss),
+                                           *[_p(a) if want_grad else None for a in g]), "nntk_rnnt_fused_loss")
+    return (loss,) + g
+
+
 def _ipv(t):
     """device pointer of a contiguous int32 torch tensor"""
     import torch
