@@ -33,7 +33,8 @@ def beam_decode(embed, lstm_block, pred_proj, out, enc, n_frames=None, blank=0, 
     final hypothesis as (labels, score); cut_gap [B]: the smallest difference, over every top-W cut of C and of B, between the last kept
     and the best dropped score (inf where nothing was dropped); order_gap [B]: the smallest difference between consecutive scores among
     the first nbest + 1 final hypotheses (inf for fewer than two); merges [B]: candidates that met their label sequence in B; cuts [B]:
-    cuts that dropped something; at_max [B]: hypotheses that could not be extended because they held max_labels labels).
+    cuts that dropped something; at_max [B]: hypotheses that could not be extended because they held max_labels labels; max_b [B]: the
+    largest number of entries B held at the end of any frame, before its cut).
     dtype float32: the sequential restatement."""
     seq = dtype == np.float32
     f = lambda a: np.asarray(a, dtype=dtype)
@@ -63,7 +64,7 @@ def beam_decode(embed, lstm_block, pred_proj, out, enc, n_frames=None, blank=0, 
         return (logits - m) - np.log(_sum(np.exp(logits - m), seq))
 
     res = dict(labels=[], scores=[], final=[], cut_gap=np.full(B, np.inf), order_gap=np.full(B, np.inf), merges=np.zeros(B, int),
-               cuts=np.zeros(B, int), at_max=np.zeros(B, int))
+               cuts=np.zeros(B, int), at_max=np.zeros(B, int), max_b=np.zeros(B, int))
 
     def cut(b, scores):
         """scores: descending; the gap between the last kept and the best dropped"""
@@ -110,6 +111,7 @@ def beam_decode(embed, lstm_block, pred_proj, out, enc, n_frames=None, blank=0, 
                 C = nxt
                 if not C:
                     break
+            res["max_b"][b] = max(res["max_b"][b], len(Bl))
             order = np.argsort(-np.array([e[1] for e in Bl], dtype=dtype), kind="stable") if Bl else []
             cut(b, [Bl[j][1] for j in order])
             A = [tuple(Bl[j]) for j in order[:BW]]
