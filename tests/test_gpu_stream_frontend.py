@@ -86,8 +86,7 @@ def test_spectrogram_stream_equals_one_shot(case):
     spec.destroy()
 
 
-@pytest.mark.parametrize("nfft,win,nov,fused", [(512, 400, 240, True), (512, 400, 240, False), (1024, 800, 480, False)])
-def test_logmel_stream_equals_one_shot(nfft, win, nov, fused):
+def _logmel_stream_equals_one_shot(nfft, win, nov, fused, **spec_kw):
     rng = np.random.default_rng(5 + nfft + fused)
     step = win - nov
     B, cap = 6, 2 * step + 5
@@ -96,19 +95,32 @@ def test_logmel_stream_equals_one_shot(nfft, win, nov, fused):
     if not fused:
         capi.set_option("spec_variant", 1)
     try:
-        spec = NL.Spectrogram(nfft, win, nov, cap)
+        spec = NL.Spectrogram(nfft, win, nov, cap, **spec_kw)
         lm = NL.LogMelSpectrogram(spec, 40)
         state = lm.new_stream_state(B)
         got = _stream(lambda x, n, st, f: lm.apply_device_stream(x, n, st, final=f), streams, _schedules(rng, totals, cap), cap, state, ())
         for b in range(B):
-            s1 = NL.Spectrogram(nfft, win, nov, totals[b])
+            s1 = NL.Spectrogram(nfft, win, nov, totals[b], **spec_kw)
             l1 = NL.LogMelSpectrogram(s1, 40)
             ref = l1.apply_device(torch.from_numpy(streams[b][None]).cuda()).cpu().numpy()[0]
+            assert got[b].shape == ref.shape, (b, got[b].shape, ref.shape)
             assert np.array_equal(got[b], ref), "row %d differs from the one-shot call" % b
             l1.destroy(); s1.destroy()
         lm.destroy(); spec.destroy()
     finally:
         capi.set_option("spec_variant", "auto")
+
+
+@pytest.mark.parametrize("nfft,win,nov,fused", [(512, 400, 240, True), (512, 400, 240, False), (1024, 800, 480, False)])
+def test_logmel_stream_equals_one_shot(nfft, win, nov, fused):
+    _logmel_stream_equals_one_shot(nfft, win, nov, fused)
+
+
+@pytest.mark.parametrize("nfft,win,nov", [(512, 512, 128), (512, 320, 160)])
+def test_fused_logmel_stream_equals_one_shot_psd_norm_unmasked_rows(nfft, win, nov):
+    """the fused stream form beyond window 400: all eight register rows masked, four loads per lane (512, 128) and three (320, 160),
+    fft_norm 0.5, PSD"""
+    _logmel_stream_equals_one_shot(nfft, win, nov, True, mode="psd", fs=16000, fft_norm=0.5)
 
 
 CONV_CASES = [(257, 128, 5, 1), (40, 128, 5, 1), (64, 64, 5, 2)]   # cfg-5 shape, flat-K shape, stride 2
