@@ -1184,8 +1184,8 @@ int nntk_rnnt_greedy_decode(NntkRnntDecoder d, NntkRnntDecodeState state, const 
  * not 16-byte aligned; outputs overlapping one another, d_enc or the workspace; a model beyond the kernel's LDS.
  * Deterministic: no atomics, the same bits on every call; a row's bits do not depend on the other rows, its position in the batch,
  * the T padding, or how many hypotheses share a pass over a matrix.  One launch on the calling thread's stream.  The host-pointer
- * form uploads, runs the device form on a workspace of its own and downloads.  Not part of the call: label timestamps,
- * language-model fusion, length normalisation. */
+ * form uploads, runs the device form on a workspace of its own and downloads.  Not part of the call: label timestamps, length
+ * normalisation.  Language-model fusion: below. */
 typedef struct NntkRnntBeamStateStruct *NntkRnntBeamState;
 size_t nntk_rnnt_beam_workspace_floats(NntkRnntDecoder d, int batch, int beam_width, int max_labels);
 int nntk_rnnt_beam_decode_device(NntkRnntDecoder d, NntkRnntBeamState state, const float *d_enc, int batch, int T, const int *n_frames,
@@ -1197,6 +1197,45 @@ NntkRnntBeamState nntk_rnnt_beam_state_create(NntkRnntDecoder d, int batch, int 
 size_t nntk_rnnt_beam_state_bytes(NntkRnntDecoder d, int batch, int beam_width, int max_labels);
 int nntk_rnnt_beam_state_reset(NntkRnntBeamState s, const int *rows, int n_rows);
 void nntk_rnnt_beam_state_destroy(NntkRnntBeamState s);
+/* ---- language-model fusion (INTEGRATION.md "RNN-Transducer: beam search", Language-model fusion) ----
+ * nntk_rnnt_beam_decode_lm_device: nntk_rnnt_beam_decode_device with an n-gram handle (NntkNgramLm, above) fused into the search, in
+ * the same single launch.  Every hypothesis carries a state q of the automaton; the initial hypothesis has q = start_state.  In the
+ * pseudo-code above:
+ *   blank: cand = hyp.score + logp(t, hyp)[blank], q kept -- unchanged.  The automaton is deterministic, so hypotheses with the same
+ *     labels have the same q and a merge in B needs no rule for it.
+ *   label cell (i, v): score = (C[i].score + logp(t, C[i])[v]) + lnF(q_i, v), in double; the parenthesised part is the acoustic
+ *     call's expression.  The new hypothesis takes q = next(q_i, v).  A cell whose score is -inf (an arc of log-probability -inf) is
+ *     not a candidate.  The W best cells and the W best of B are chosen on these fused scores, with the tie rules above.
+ *   lnF(s, v) is the walk of nntk_ngram_lm_score: from s, add ln B(s) and move to backoff_state[s] until a state has an arc labelled
+ *     v, then add ln G(arc), next = arc_next; when state 0 has none, add ln U, next = 0.  lnF = ((0 + b_0) + b_1 ...) + g, from left to
+ *     right in double, on the unrounded doubles nntk_ngram_lm_score sums (ln G = alpha arc_logp + beta, ln B = alpha backoff_logw,
+ *     ln U = alpha unk_logp + beta, ln E = alpha final_logp; alpha == 0: beta, 0, beta, 0).  The device only adds them.
+ *   report: every entry of the final A gets + ln E(q) (0 without final_logp); entries at -inf are dropped, the rest are ordered
+ *     descending, exact ties to the lower rank in A, and the first nbest are written.  A row without frames (and without a carried
+ *     beam) reports the empty hypothesis with score ln E(start_state).  With a state, the ln E term applies to what is reported after
+ *     each push, never to the carried beam: any split of a row's frames into pushes gives the one-shot call's bits after every push.
+ *   lm == NULL: the acoustic call, bit for bit.  alpha == 0, beta == 0 and no final_logp: every term is +0.0 and the bits are again the
+ *     acoustic call's.  score - nntk_ngram_lm_score(lm, y, n, 1) is the acoustic log mass of y.
+ * d_workspace: nntk_rnnt_beam_lm_workspace_floats floats with a model (the acoustic workspace, then per row 4 bytes per hypothesis
+ * slot and 8 beam_width V bytes), nntk_rnnt_beam_workspace_floats without.  nntk_rnnt_beam_state_create_lm: a state for streams
+ * decoded with lm (NULL: nntk_rnnt_beam_state_create), nntk_rnnt_beam_state_bytes_lm bytes: 4 more per row and beam entry, the
+ * state q.  The lm must outlive the state; reset, destroy and the decode calls take the state as before.  The search reads the
+ * lookup records of nntk_ngram_lm_device_bytes and doubles of its own -- nntk_ngram_lm_rnnt_device_bytes: 8 bytes per arc, 16 per
+ * state -- which the first transducer decode that uses the handle uploads.
+ * Refused on the host before anything is enqueued (-1 / NULL, nntk_last_error(), nothing written): everything the acoustic call
+ * refuses; an lm built for another class count than V or another blank than the decoder's; a state created without an lm in a call
+ * with one, a state created with an lm in a call without (nntk_rnnt_beam_decode_device included), a state created with another lm.
+ * The guarantees of the acoustic call hold: no atomics, the same bits on every call, a row's bits independent of the other rows, its
+ * batch position, the T padding (NaN there included) and how many hypotheses share a pass over a matrix. */
+size_t nntk_ngram_lm_rnnt_device_bytes(NntkNgramLm lm);
+size_t nntk_rnnt_beam_lm_workspace_floats(NntkRnntDecoder d, int batch, int beam_width, int max_labels);
+int nntk_rnnt_beam_decode_lm_device(NntkRnntDecoder d, NntkRnntBeamState state, const float *d_enc, int batch, int T, const int *n_frames,
+                                    int beam_width, int nbest, int max_labels, NntkNgramLm lm, int *d_labels_out, int *d_out_lengths,
+                                    float *d_scores, float *d_workspace);
+int nntk_rnnt_beam_decode_lm(NntkRnntDecoder d, NntkRnntBeamState state, const float *enc, int batch, int T, const int *n_frames,
+                             int beam_width, int nbest, int max_labels, NntkNgramLm lm, int *labels_out, int *out_lengths, float *scores);
+NntkRnntBeamState nntk_rnnt_beam_state_create_lm(NntkRnntDecoder d, int batch, int beam_width, int max_labels, NntkNgramLm lm);
+size_t nntk_rnnt_beam_state_bytes_lm(NntkRnntDecoder d, int batch, int beam_width, int max_labels);
 
 #ifdef __cplusplus
 }

@@ -488,6 +488,12 @@ SIGNATURES = {
     "nntk_rnnt_beam_state_bytes": (C.c_size_t, [vp, C.c_int, C.c_int, C.c_int]),
     "nntk_rnnt_beam_state_reset": (C.c_int, [vp, ip, C.c_int]),
     "nntk_rnnt_beam_state_destroy": (None, [vp]),
+    "nntk_ngram_lm_rnnt_device_bytes": (C.c_size_t, [vp]),
+    "nntk_rnnt_beam_lm_workspace_floats": (C.c_size_t, [vp, C.c_int, C.c_int, C.c_int]),
+    "nntk_rnnt_beam_decode_lm_device": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, ip, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp]),
+    "nntk_rnnt_beam_decode_lm": (C.c_int, [vp, vp, fp, C.c_int, C.c_int, ip, C.c_int, C.c_int, C.c_int, vp, ip, ip, fp]),
+    "nntk_rnnt_beam_state_create_lm": (vp, [vp, C.c_int, C.c_int, C.c_int, vp]),
+    "nntk_rnnt_beam_state_bytes_lm": (C.c_size_t, [vp, C.c_int, C.c_int, C.c_int]),
     # weights from device memory into a handle; the multi-tensor optimizer (INTEGRATION.md "Optimizers")
     "Conv1dLoadWeightsDevice": (C.c_int, [vp, vp]),
     "BatchNormLoadWeightsDevice": (C.c_int, [vp, vp]),

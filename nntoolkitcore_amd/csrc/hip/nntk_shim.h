@@ -262,6 +262,21 @@ void nntk_shim_rnnt_beam_set_group(int group);
 /* h_n_frames HOST [batch], checked by the caller, copied in stream order into the workspace; d_ws 16-byte aligned */
 int nntk_shim_rnnt_beam(const nntk_shim_rnnt_dec *m, const float *d_enc, int batch, int T, const int *h_n_frames, int beam_width, int nbest,
                         int max_labels, const nntk_shim_rnnt_beam_state *st, int *d_labels, int *d_lengths, float *d_scores, float *d_ws);
+/* Language-model fusion (INTEGRATION.md "RNN-Transducer: beam search", Language-model fusion).  The search adds natural logs in double, so
+ * next to the lookup records of nntk_shim_lm (d_arcs {label, next state, -, -}, d_states {first arc, arcs, backoff state, 0}) it reads
+ * tables of its own: d_arc_ln [arcs] = ln G, d_state_ln [states][2] = ln B | ln E, and ln U.  lm NULL: nntk_shim_rnnt_beam.  With a
+ * model the workspace is nntk_shim_rnnt_beam_lm_workspace_floats words -- the acoustic layout, then per row an int per hypothesis slot
+ * and beam_width V doubles -- and a stream's rows carry d_st_q [batch][W], the LM state of each hypothesis. */
+typedef struct {
+    const int *d_arcs, *d_states;
+    const double *d_arc_ln, *d_state_ln;
+    double unk_ln;
+    int start_state;
+} nntk_shim_rnnt_lm;
+size_t nntk_shim_rnnt_beam_lm_workspace_floats(int batch, int H, int J, int V, int max_sym, int beam_width, int max_labels);
+int nntk_shim_rnnt_beam_lm(const nntk_shim_rnnt_dec *m, const float *d_enc, int batch, int T, const int *h_n_frames, int beam_width, int nbest,
+                           int max_labels, const nntk_shim_rnnt_beam_state *st, const nntk_shim_rnnt_lm *lm, int *d_st_q, int *d_labels,
+                           int *d_lengths, float *d_scores, float *d_ws);
 /* BatchNorm training (batch_norm.c:191-386): x, d_out [N, F]; d_block = gamma | beta | ...; d_stats [8][F] = mean | variance |
  * var_eps | sqrt_var | d_beta | d_gamma | d_var | d_mu; d_partial [slices][3][F] with slices from nntk_shim_bn_train_slices */
 /* Ragged batches and carried state for the recurrent training launchers below (the *VarLen training calls; a NULL pointer to it = the

@@ -21,6 +21,18 @@
 // Selection.  The W best of the depth's cells (and of B at the end of a frame) are found by W rounds of a workgroup arg-max over
 // (score descending, index ascending), each round restricted to what ranks behind the round before: exact and order-stable.  Scores,
 // compares and logaddexp are in double.  The LSTM step of a selected cell runs after the selection: W steps a depth.
+//
+// Language-model fusion (the LM = true instantiations; include/nntoolkitcore_hip.h, "Language-model fusion" under the beam search).  Every
+// slot carries the state q of a backoff automaton (lmq, behind the acoustic workspace, which does not move), and the row owns
+// lmterm [W][V] doubles.  Once per depth the rows of lmterm are filled by scattering the backoff chains instead of V binary searches:
+// every element is marked unset; level by level (q_i, backoff(q_i), ... 0, a workgroup barrier between levels) the lanes stride over
+// the arcs of hypothesis i's state of that level and an unset label takes acc + ln G(arc), acc = ((b_0 + b_1) + ...) the backoffs
+// taken so far; what is still unset after state 0 takes acc + ln U.  Labels within a state are distinct and rows belong to one
+// hypothesis, so nothing races, and the cost is the chain's arcs + V per hypothesis.  The same pass that fills the unknown labels adds
+// the acoustic cell, (base + logp) + lnF, so the W rounds of the selection read one double a cell; -inf (a zero-mass arc, the blank, a
+// hypothesis that cannot be extended) is no candidate.  next(q_i, v) is looked up for the W selected cells only, by binary search
+// along the chain.  The tables are global memory; no LDS is added.  At the end the entries of A take + ln E(q), the -inf ones are
+// dropped and the rest are ranked (at most 32: every entry counts the entries ahead of it); the carried A stays as it was.
 #include <limits.h>
 #include "rnnt_dec_common.hpp"
 
@@ -28,10 +40,11 @@
 
 struct RbLayout {                          // offsets in floats from the row's block, each a multiple of 4
     size_t bscore, states, labels, meta, logits, bslot, row;
+    size_t lmq, lmterm;                    // with a language model only, behind the acoustic layout: [(S' + 2) W] ints | [W][V] doubles
     int nslots, nbmax, SF;
 };
 
-static RbLayout rb_layout(int H, int J, int V, int max_sym, int W, int max_labels) {
+static RbLayout rb_layout(int H, int J, int V, int max_sym, int W, int max_labels, bool lm = false) {
     RbLayout l;
     const int depths = max_sym < max_labels ? max_sym : max_labels;
     l.nslots = (depths + 2) * W; l.nbmax = (depths + 1) * W; l.SF = 2 * H + J;
@@ -43,6 +56,11 @@ static RbLayout rb_layout(int H, int J, int V, int max_sym, int W, int max_label
     l.meta = take(2 * (size_t)l.nslots);
     l.logits = take((size_t)W * V);
     l.bslot = take((size_t)l.nbmax);
+    l.lmq = l.lmterm = at;
+    if (lm) {
+        l.lmq = take((size_t)l.nslots);
+        l.lmterm = take(2 * (size_t)W * V);
+    }
     l.row = at;
     return l;
 }
@@ -57,6 +75,8 @@ struct RnntBeamArgs {
     RbLayout lay;
     size_t ws_head;                        // floats before the first row's block: the frame counts
     int batch, T, V, blank, H, J, act, max_sym, W, nbest, max_labels;
+    nntk_shim_rnnt_lm lm;                  // the LM instantiations only
+    int *st_q;                             // [batch][W]: the LM states of a stream's rows (with st)
 };
 
 template <int R> struct RbShared {
@@ -84,7 +104,21 @@ __device__ __forceinline__ double rb_logaddexp(double x, double y) {         // 
     return m + log1p(exp(d));
 }
 
-template <int R>
+// next(q, v): the first state along q's backoff chain with an arc labelled v gives the arc's next state; none, state 0 included: 0
+__device__ static int rb_lm_next(const nntk_shim_rnnt_lm &lm, int s, int v) {
+    for (;;) {
+        int lo = lm.d_states[4 * s], hi = lo + lm.d_states[4 * s + 1] - 1;
+        while (lo <= hi) {
+            const int mid = lo + (hi - lo) / 2, c = lm.d_arcs[4 * (size_t)mid];
+            if (c == v) return lm.d_arcs[4 * (size_t)mid + 1];
+            if (c < v) lo = mid + 1; else hi = mid - 1;
+        }
+        if (s == 0) return 0;
+        s = lm.d_states[4 * s + 2];
+    }
+}
+
+template <int R, bool LM>
 __global__ __launch_bounds__(RD_THREADS) void rnnt_beam_kernel(const RnntBeamArgs a) {
     extern __shared__ __align__(16) unsigned char rb_smem[];
     RbShared<R> &sh = *(RbShared<R> *)rb_smem;
@@ -100,6 +134,8 @@ __global__ __launch_bounds__(RD_THREADS) void rnnt_beam_kernel(const RnntBeamArg
     double *bscore = (double *)(row + a.lay.bscore);
     float *states = row + a.lay.states, *lg = row + a.lay.logits;
     int *labs = (int *)(row + a.lay.labels), *meta = (int *)(row + a.lay.meta), *bslot = (int *)(row + a.lay.bslot);
+    int *lmq = (int *)(row + a.lay.lmq);                                     // LM only, as is lmterm
+    double *lmterm = (double *)(row + a.lay.lmterm);
     const int n = ((const int *)a.ws)[b];
     const bool started = a.st.i && a.st.i[4 * b] != 0;
 
@@ -247,11 +283,13 @@ __global__ __launch_bounds__(RD_THREADS) void rnnt_beam_kernel(const RnntBeamArg
         if (tid < nA) {
             meta[2 * tid] = a.st.meta[2 * (at + tid)]; meta[2 * tid + 1] = a.st.meta[2 * (at + tid) + 1];
             sh.a_score[tid] = a.st.score[at + tid];
+            if constexpr (LM) lmq[tid] = a.st_q[at + tid];
         }
         if (tid == 0) sh.nA = nA;
         __syncthreads();
     } else {
         if (tid == 0) { meta[0] = 0; meta[1] = 0; sh.a_score[0] = 0.0; sh.n_src[0] = -1; sh.n_lab[0] = a.blank; sh.nA = 1; }
+        if constexpr (LM) { if (tid == 0) lmq[0] = a.lm.start_state; }
         __syncthreads();
         step_group(0, 1, 0);                                                 // the step on embed[blank] from the zero state
     }
@@ -309,9 +347,51 @@ __global__ __launch_bounds__(RD_THREADS) void rnnt_beam_kernel(const RnntBeamArg
             // the W best label cells (i, v), v != blank
             double prev_s = INFINITY;
             int prev_i = -1, nSel = 0;
+            if constexpr (LM) {
+                // lmterm[i][v] = ln F(q_i, v) by scattering q_i's backoff chain, then the fused score of the cell in its place
+                for (int idx = tid; idx < nC * V; idx += RD_THREADS) lmterm[idx] = NAN;      // unset (no table value is a NaN)
+                __syncthreads();
+                for (int level = 0;; ++level) {
+                    bool more = false;
+                    for (int i = 0; i < nC; ++i) {
+                        int s = lmq[sh.c_slot[i]], l = 0;
+                        double acc = 0.0;
+                        for (; l < level && s != 0; ++l) { acc += a.lm.d_state_ln[2 * s]; s = a.lm.d_states[4 * s + 2]; }
+                        if (l < level) continue;                             // the chain ended at state 0, levels ago
+                        more |= s != 0;
+                        const int first = a.lm.d_states[4 * s], cnt = a.lm.d_states[4 * s + 1];
+                        for (int q = tid; q < cnt; q += RD_THREADS) {
+                            double *cell = lmterm + (size_t)i * V + a.lm.d_arcs[4 * (size_t)(first + q)];
+                            if (*cell != *cell) *cell = acc + a.lm.d_arc_ln[first + q];
+                        }
+                    }
+                    __syncthreads();
+                    if (!more) break;
+                }
+                for (int i = 0; i < nC; ++i) {
+                    const double base = sh.c_score[i], lse = sh.c_lse[i];
+                    const bool open = sh.c_len[i] < ML && base > -INFINITY;
+                    const float mx = sh.c_max[i];
+                    double acc = 0.0;
+                    for (int s = lmq[sh.c_slot[i]]; s != 0; s = a.lm.d_states[4 * s + 2]) acc += a.lm.d_state_ln[2 * s];
+                    for (int v = tid; v < V; v += RD_THREADS) {
+                        const double t = lmterm[(size_t)i * V + v];
+                        const double f = (base + ((double)(lg[(size_t)i * V + v] - mx) - lse)) + (t != t ? acc + a.lm.unk_ln : t);
+                        lmterm[(size_t)i * V + v] = open && v != a.blank ? f : -INFINITY;
+                    }
+                }
+                __syncthreads();
+            }
             for (int k = 0; k < W; ++k) {
                 double bs = -INFINITY;
                 int bi = INT_MAX;
+                if constexpr (LM) {
+                    for (int idx = tid; idx < nC * V; idx += RD_THREADS) {
+                        const double s = lmterm[idx];
+                        if (!(s > -INFINITY)) continue;                      // no candidate
+                        if ((s < prev_s || (s == prev_s && idx > prev_i)) && (bi == INT_MAX || s > bs)) { bs = s; bi = idx; }
+                    }
+                } else {
                 for (int i = 0; i < nC; ++i) {
                     const double base = sh.c_score[i], lse = sh.c_lse[i];
                     if (!(sh.c_len[i] < ML && base > -INFINITY)) continue;
@@ -322,6 +402,7 @@ __global__ __launch_bounds__(RD_THREADS) void rnnt_beam_kernel(const RnntBeamArg
                         const int idx = i * V + v;
                         if ((s < prev_s || (s == prev_s && idx > prev_i)) && (bi == INT_MAX || s > bs)) { bs = s; bi = idx; }
                     }
+                }
                 }
                 block_best(bs, bi);
                 if (sh.best_i == INT_MAX) break;
@@ -341,6 +422,7 @@ __global__ __launch_bounds__(RD_THREADS) void rnnt_beam_kernel(const RnntBeamArg
                 const unsigned nh = oh * 1000003u + (unsigned)(sh.n_lab[tid] + 1);
                 sh.n_src[tid] = ss; sh.c_slot[tid] = dst0 + tid; sh.c_score[tid] = sh.n_score[tid]; sh.c_len[tid] = ol + 1; sh.c_hash[tid] = nh;
                 meta[2 * (dst0 + tid)] = ol + 1; meta[2 * (dst0 + tid) + 1] = (int)nh;
+                if constexpr (LM) lmq[dst0 + tid] = rb_lm_next(a.lm, lmq[ss], sh.n_lab[tid]);
             }
             if (tid == 0) sh.nC = nSel;
             __syncthreads();
@@ -377,12 +459,44 @@ __global__ __launch_bounds__(RD_THREADS) void rnnt_beam_kernel(const RnntBeamArg
             for (int j = tid; j < SF; j += RD_THREADS) states[(size_t)dst * SF + j] = states[(size_t)src * SF + j];
             for (int j = tid; j < len; j += RD_THREADS) labs[(size_t)dst * ML + j] = labs[(size_t)src * ML + j];
             if (tid == 0) { meta[2 * dst] = len; meta[2 * dst + 1] = meta[2 * src + 1]; }
+            if constexpr (LM) { if (tid == 0) lmq[dst] = lmq[src]; }
         }
         if (tid == 0) sh.nA = nNew;
         __syncthreads();
     }
 
     const int nA = sh.nA;
+    if constexpr (LM) {
+        // the report: + ln E(q), the -inf entries dropped, the rest ranked descending, ties to the lower rank in A; A itself stays
+        __syncthreads();
+        if (tid < nA) sh.cand[tid] = sh.a_score[tid] + a.lm.d_state_ln[2 * lmq[cur * W + tid] + 1];
+        __syncthreads();
+        if (tid < nA) {
+            const double s = sh.cand[tid];
+            int ahead = 0;
+            for (int j = 0; j < nA; ++j) {
+                const double o = sh.cand[j];
+                ahead += o > -INFINITY && (o > s || (o == s && j < tid));
+            }
+            if (s > -INFINITY) sh.found[ahead] = tid;
+        }
+        if (tid == 0) {
+            int kept = 0;
+            for (int j = 0; j < nA; ++j) kept += sh.cand[j] > -INFINITY;
+            sh.nSel = kept;
+        }
+        __syncthreads();
+        const int kept = sh.nSel;
+        for (int k = 0; k < a.nbest; ++k) {
+            const size_t o = (size_t)b * a.nbest + k;
+            const int src = k < kept ? sh.found[k] : 0, slot = cur * W + src, len = k < kept ? meta[2 * slot] : 0;
+            for (int j = tid; j < ML; j += RD_THREADS) a.labels[o * ML + j] = j < len ? labs[(size_t)slot * ML + j] : -1;
+            if (tid == 0) {
+                a.lengths[o] = k < kept ? len : -1;
+                a.scores[o] = k < kept ? (float)sh.cand[src] : -INFINITY;
+            }
+        }
+    } else {
     for (int k = 0; k < a.nbest; ++k) {
         const size_t o = (size_t)b * a.nbest + k;
         const int slot = cur * W + k, len = k < nA ? meta[2 * slot] : 0;
@@ -391,6 +505,7 @@ __global__ __launch_bounds__(RD_THREADS) void rnnt_beam_kernel(const RnntBeamArg
             a.lengths[o] = k < nA ? len : -1;
             a.scores[o] = k < nA ? (float)sh.a_score[k] : -INFINITY;
         }
+    }
     }
     if (a.st.i) {
         const size_t at = (size_t)b * W;
@@ -403,9 +518,17 @@ __global__ __launch_bounds__(RD_THREADS) void rnnt_beam_kernel(const RnntBeamArg
             const int slot = cur * W + tid;
             a.st.meta[2 * (at + tid)] = meta[2 * slot]; a.st.meta[2 * (at + tid) + 1] = meta[2 * slot + 1];
             a.st.score[at + tid] = sh.a_score[tid];
+            if constexpr (LM) a.st_q[at + tid] = lmq[slot];
         }
         if (tid == 0) { a.st.i[4 * b] = 1; a.st.i[4 * b + 1] = nA; }
     }
+}
+
+template <int R, bool LM>
+static int rb_launch(const RnntBeamArgs &a, size_t lds) {
+    if (lds > 48 * 1024 && nntk_set_max_dynamic_lds((const void *)rnnt_beam_kernel<R, LM>, lds)) return -1;
+    hipLaunchKernelGGL((rnnt_beam_kernel<R, LM>), dim3((unsigned)a.batch), dim3(RD_THREADS), lds, nntk_stream(), a);
+    return 0;
 }
 
 static int rb_forced_group = 0;
@@ -427,8 +550,20 @@ int nntk_shim_rnnt_beam_group(int beam_width, int H, int J, int V) {
 
 void nntk_shim_rnnt_beam_set_group(int group) { rb_forced_group = group == 1 || group == NNTK_RNNT_DEC_GROUP ? group : 0; }
 
+size_t nntk_shim_rnnt_beam_lm_workspace_floats(int batch, int H, int J, int V, int max_sym, int beam_width, int max_labels) {
+    if (batch <= 0) return 0;
+    return (((size_t)batch + 3) & ~(size_t)3) + (size_t)batch * rb_layout(H, J, V, max_sym, beam_width, max_labels, true).row;
+}
+
 int nntk_shim_rnnt_beam(const nntk_shim_rnnt_dec *m, const float *d_enc, int batch, int T, const int *h_n_frames, int beam_width, int nbest,
                         int max_labels, const nntk_shim_rnnt_beam_state *st, int *d_labels, int *d_lengths, float *d_scores, float *d_ws) {
+    return nntk_shim_rnnt_beam_lm(m, d_enc, batch, T, h_n_frames, beam_width, nbest, max_labels, st, nullptr, nullptr, d_labels, d_lengths,
+                                  d_scores, d_ws);
+}
+
+int nntk_shim_rnnt_beam_lm(const nntk_shim_rnnt_dec *m, const float *d_enc, int batch, int T, const int *h_n_frames, int beam_width, int nbest,
+                           int max_labels, const nntk_shim_rnnt_beam_state *st, const nntk_shim_rnnt_lm *lm, int *d_st_q, int *d_labels,
+                           int *d_lengths, float *d_scores, float *d_ws) {
     if (batch <= 0) return 0;
     const int depths = m->max_symbols_per_frame < max_labels ? m->max_symbols_per_frame : max_labels;
     if (m->E < 1 || m->H < 1 || m->J < 1 || m->V < 2 || m->H > NNTK_RNNT_DEC_MAX_WIDTH || m->J > NNTK_RNNT_DEC_MAX_WIDTH ||
@@ -442,20 +577,16 @@ int nntk_shim_rnnt_beam(const nntk_shim_rnnt_dec *m, const float *d_enc, int bat
     if (st) a.st = *st;
     else { a.st.score = nullptr; a.st.f = nullptr; a.st.lab = nullptr; a.st.meta = nullptr; a.st.i = nullptr; }
     a.labels = d_labels; a.lengths = d_lengths; a.scores = d_scores;
-    a.lay = rb_layout(m->H, m->J, m->V, m->max_symbols_per_frame, beam_width, max_labels);
+    a.lay = rb_layout(m->H, m->J, m->V, m->max_symbols_per_frame, beam_width, max_labels, lm != nullptr);
     a.ws_head = ((size_t)batch + 3) & ~(size_t)3;
     a.batch = batch; a.T = T; a.V = m->V; a.blank = m->blank; a.H = m->H; a.J = m->J; a.act = m->activation;
     a.max_sym = m->max_symbols_per_frame; a.W = beam_width; a.nbest = nbest; a.max_labels = max_labels;
+    a.lm = lm ? *lm : nntk_shim_rnnt_lm();
+    a.st_q = st ? d_st_q : nullptr;
     const int R = nntk_shim_rnnt_beam_group(beam_width, m->H, m->J, m->V);
     const size_t lds = rb_lds_bytes(R, m->H, m->J, m->V);
-    const dim3 grid((unsigned)batch);
-    if (R == 1) {
-        if (lds > 48 * 1024 && nntk_set_max_dynamic_lds((const void *)rnnt_beam_kernel<1>, lds)) return -1;
-        hipLaunchKernelGGL(rnnt_beam_kernel<1>, grid, dim3(RD_THREADS), lds, nntk_stream(), a);
-    } else {
-        if (lds > 48 * 1024 && nntk_set_max_dynamic_lds((const void *)rnnt_beam_kernel<NNTK_RNNT_DEC_GROUP>, lds)) return -1;
-        hipLaunchKernelGGL(rnnt_beam_kernel<NNTK_RNNT_DEC_GROUP>, grid, dim3(RD_THREADS), lds, nntk_stream(), a);
-    }
+    if (R == 1 ? (lm ? rb_launch<1, true>(a, lds) : rb_launch<1, false>(a, lds))
+               : (lm ? rb_launch<NNTK_RNNT_DEC_GROUP, true>(a, lds) : rb_launch<NNTK_RNNT_DEC_GROUP, false>(a, lds))) return -1;
     NNTK_LAUNCH_CHECK("rnnt_beam_kernel");
     return 0;
 }

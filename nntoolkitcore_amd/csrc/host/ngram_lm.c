@@ -1,7 +1,8 @@
 /*
  * ngram_lm.c -- the token-level n-gram language model of the fused CTC beam search (INTEGRATION.md "CTC prefix beam search",
  * Language-model fusion): a deterministic backoff automaton, checked in full on the host, scored on the host in double, and laid out
- * as 16-byte records that the first decode using the handle uploads.  create, score and destroy never touch a device.
+ * as 16-byte records that the first decode using the handle uploads.  create, score and destroy never touch a device.  The fused
+ * transducer beam search (rnnt_decode.c) adds the unrounded logs themselves: a second table of doubles, uploaded by its first decode.
  */
 #include <math.h>
 #include <stdio.h>
@@ -22,6 +23,8 @@ struct NntkNgramLmStruct {
     int unk_m, unk_e;
     nntk_devbuf d_tab;
     int uploaded;
+    nntk_devbuf d_ln;                      /* the transducer search's doubles: ln G per arc, then ln B | ln E per state */
+    int ln_uploaded;
 };
 
 static void *lm_fail(const char *fmt, long a, long b, long c) {
@@ -150,6 +153,7 @@ NntkNgramLm nntk_ngram_lm_create(int n_classes, int blank, int n_states, const l
 void nntk_ngram_lm_destroy(NntkNgramLm lm) {
     if (!lm) return;
     if (lm->d_tab.p) nntk_devbuf_free(&lm->d_tab);
+    if (lm->d_ln.p) nntk_devbuf_free(&lm->d_ln);
     free(lm->arc_begin); free(lm->arc_label); free(lm->arc_next); free(lm->backoff_state);
     free(lm->arc_ln); free(lm->backoff_ln); free(lm->final_ln); free(lm->tab);
     free(lm);
@@ -157,6 +161,10 @@ void nntk_ngram_lm_destroy(NntkNgramLm lm) {
 
 size_t nntk_ngram_lm_device_bytes(NntkNgramLm lm) {
     return lm ? 16 * ((size_t)lm->n_arcs + 2 * (size_t)lm->n_states) : 0;
+}
+
+size_t nntk_ngram_lm_rnnt_device_bytes(NntkNgramLm lm) {
+    return lm ? 8 * (size_t)lm->n_arcs + 16 * (size_t)lm->n_states : 0;
 }
 
 double nntk_ngram_lm_score(NntkNgramLm lm, const int *labels, int n, int with_final) {
@@ -184,7 +192,7 @@ double nntk_ngram_lm_score(NntkNgramLm lm, const int *labels, int n, int with_fi
     return sum;
 }
 
-/* ---- for the decoders (ctc.c) ---- */
+/* ---- for the decoders (ctc.c, rnnt_decode.c) ---- */
 int nntk_ngram_lm_matches(NntkNgramLm lm, int C, int blank) { return lm->n_classes == C && lm->blank == blank; }
 
 int nntk_ngram_lm_device(NntkNgramLm lm, nntk_shim_lm *out) {
@@ -205,5 +213,30 @@ int nntk_ngram_lm_device(NntkNgramLm lm, nntk_shim_lm *out) {
     out->depth = lm->depth;
     out->unk_m = lm->unk_m;
     out->unk_e = lm->unk_e;
+    return 0;
+}
+
+/* the transducer beam search adds natural logs in double: the unrounded values nntk_ngram_lm_score sums, next to the lookup records */
+int nntk_ngram_lm_rnnt_device(NntkNgramLm lm, nntk_shim_rnnt_lm *out) {
+    nntk_shim_lm tab;
+    if (nntk_ngram_lm_device(lm, &tab)) return -1;
+    const size_t na = (size_t)lm->n_arcs, ns = (size_t)lm->n_states;
+    if (!lm->ln_uploaded) {
+        double *h = (double *)malloc((na + 2 * ns) * sizeof(double));
+        if (!h) NNTK_FAIL("nntk_ngram_lm: out of host memory");
+        memcpy(h, lm->arc_ln, na * sizeof(double));
+        for (size_t s = 0; s < ns; ++s) { h[na + 2 * s] = lm->backoff_ln[s]; h[na + 2 * s + 1] = lm->final_ln[s]; }
+        float *d = nntk_devbuf_reserve(&lm->d_ln, 2 * (na + 2 * ns));
+        const int rc = d ? nntk_shim_upload(d, h, (na + 2 * ns) * sizeof(double)) : -1;
+        free(h);
+        if (rc) return -1;
+        lm->ln_uploaded = 1;
+    }
+    out->d_arcs = tab.d_arcs;
+    out->d_states = tab.d_states;
+    out->d_arc_ln = (const double *)lm->d_ln.p;
+    out->d_state_ln = out->d_arc_ln + na;
+    out->unk_ln = lm->unk_ln;
+    out->start_state = lm->start_state;
     return 0;
 }

@@ -103,6 +103,8 @@ int nntk_check_lengths(const char *who, const int *lengths, int B, int T, int *m
  * tables, uploaded by the first call (-1 with the error set when that fails).  Internal to the library. */
 __attribute__((visibility("hidden"))) int nntk_ngram_lm_matches(NntkNgramLm lm, int C, int blank);
 __attribute__((visibility("hidden"))) int nntk_ngram_lm_device(NntkNgramLm lm, nntk_shim_lm *out);
+/* ... and for the transducer beam search of rnnt_decode.c: the lookup records with the double tables of natural logs */
+__attribute__((visibility("hidden"))) int nntk_ngram_lm_rnnt_device(NntkNgramLm lm, nntk_shim_rnnt_lm *out);
 
 void nntk_set_error(const char *msg);
 #define NNTK_FAIL(msg) do { nntk_set_error(msg); return -1; } while (0)

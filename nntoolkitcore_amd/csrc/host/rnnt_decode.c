@@ -243,6 +243,8 @@ struct NntkRnntBeamStateStruct {
     NntkRnntDecoder dec;
     int batch, width, max_labels;
     nntk_shim_rnnt_beam_state d;                /* d.i: [batch][4], then [batch]: the rows of a reset */
+    NntkNgramLm lm;                             /* the model the stream was created with (NULL: none), and */
+    int *d_q;                                   /* [batch][width]: each hypothesis's state in it */
 };
 
 static int beam_check_sizes(const char *who, NntkRnntDecoder d, int beam_width, int max_labels) {
@@ -264,25 +266,50 @@ size_t nntk_rnnt_beam_state_bytes(NntkRnntDecoder d, int batch, int beam_width, 
     return (size_t)batch * (beam_width * per_hyp + 5 * sizeof(int));
 }
 
-NntkRnntBeamState nntk_rnnt_beam_state_create(NntkRnntDecoder d, int batch, int beam_width, int max_labels) {
-    static const char who[] = "nntk_rnnt_beam_state_create";
+size_t nntk_rnnt_beam_lm_workspace_floats(NntkRnntDecoder d, int batch, int beam_width, int max_labels) {
+    if (!d || batch <= 0 || beam_width < 1 || beam_width > NNTK_RNNT_BEAM_MAX_W || max_labels < 1) return 0;
+    return nntk_shim_rnnt_beam_lm_workspace_floats(batch, d->cfg.H, d->cfg.J, d->cfg.V, d->cfg.max_symbols_per_frame, beam_width, max_labels);
+}
+
+size_t nntk_rnnt_beam_state_bytes_lm(NntkRnntDecoder d, int batch, int beam_width, int max_labels) {
+    const size_t acoustic = nntk_rnnt_beam_state_bytes(d, batch, beam_width, max_labels);
+    return acoustic ? acoustic + (size_t)batch * beam_width * sizeof(int) : 0;
+}
+
+static int beam_check_lm(const char *who, NntkRnntDecoder d, NntkNgramLm lm) {
+    if (lm && !nntk_ngram_lm_matches(lm, d->cfg.V, d->cfg.blank))
+        return dec_fail(who, "the language model was built for another class count or blank than V %ld, blank %ld", d->cfg.V, d->cfg.blank, 0);
+    return 0;
+}
+
+static NntkRnntBeamState beam_state_create(const char *who, NntkRnntDecoder d, int batch, int beam_width, int max_labels, NntkNgramLm lm) {
     nntk_shim_clear_error();
     if (beam_check_sizes(who, d, beam_width, max_labels)) return NULL;
     if (batch < 1) { dec_fail(who, "batch %ld < 1", batch, 0, 0); return NULL; }
+    if (beam_check_lm(who, d, lm)) return NULL;
     NntkRnntBeamState s = (NntkRnntBeamState)calloc(1, sizeof *s);
     if (!s) { nntk_set_error("nntk_rnnt_beam_state_create: out of host memory"); return NULL; }
-    s->dec = d; s->batch = batch; s->width = beam_width; s->max_labels = max_labels;
+    s->dec = d; s->batch = batch; s->width = beam_width; s->max_labels = max_labels; s->lm = lm;
     const size_t hyps = (size_t)batch * beam_width;
     s->d.score = (double *)nntk_shim_malloc(hyps * sizeof(double));
     s->d.f = s->d.score ? (float *)nntk_shim_malloc(hyps * (2 * (size_t)d->cfg.H + d->cfg.J) * sizeof(float)) : NULL;
     s->d.lab = s->d.f ? (int *)nntk_shim_malloc(hyps * max_labels * sizeof(int)) : NULL;
     s->d.meta = s->d.lab ? (int *)nntk_shim_malloc(hyps * 2 * sizeof(int)) : NULL;
     s->d.i = s->d.meta ? (int *)nntk_shim_malloc((size_t)batch * 5 * sizeof(int)) : NULL;
-    if (!s->d.i || nntk_shim_memset(s->d.i, 0, (size_t)batch * 5 * sizeof(int))) {
+    s->d_q = s->d.i && lm ? (int *)nntk_shim_malloc(hyps * sizeof(int)) : NULL;
+    if (!s->d.i || (lm && !s->d_q) || nntk_shim_memset(s->d.i, 0, (size_t)batch * 5 * sizeof(int))) {
         nntk_rnnt_beam_state_destroy(s);
         return NULL;
     }
     return s;
+}
+
+NntkRnntBeamState nntk_rnnt_beam_state_create(NntkRnntDecoder d, int batch, int beam_width, int max_labels) {
+    return beam_state_create("nntk_rnnt_beam_state_create", d, batch, beam_width, max_labels, NULL);
+}
+
+NntkRnntBeamState nntk_rnnt_beam_state_create_lm(NntkRnntDecoder d, int batch, int beam_width, int max_labels, NntkNgramLm lm) {
+    return beam_state_create("nntk_rnnt_beam_state_create_lm", d, batch, beam_width, max_labels, lm);
 }
 
 int nntk_rnnt_beam_state_reset(NntkRnntBeamState s, const int *rows, int n_rows) {
@@ -308,14 +335,19 @@ void nntk_rnnt_beam_state_destroy(NntkRnntBeamState s) {
     nntk_shim_free(s->d.lab);
     nntk_shim_free(s->d.meta);
     nntk_shim_free(s->d.i);
+    nntk_shim_free(s->d_q);
     free(s);
 }
 
-/* everything a beam call can be refused for; ws NULL: the host-pointer form, which owns its workspace */
+/* everything a beam call can be refused for; ws NULL: the host-pointer form, which owns its workspace; lm NULL: the acoustic search */
 static int beam_check_call(const char *who, NntkRnntDecoder d, NntkRnntBeamState state, const float *enc, int batch, int T,
-                           const int *n_frames, int beam_width, int nbest, int max_labels, const int *labels_out, const int *out_lengths,
-                           const float *scores, const float *ws, int device_form) {
+                           const int *n_frames, int beam_width, int nbest, int max_labels, NntkNgramLm lm, const int *labels_out,
+                           const int *out_lengths, const float *scores, const float *ws, int device_form) {
     if (!d) return dec_fail(who, "NULL decoder", 0, 0, 0);
+    if (beam_check_lm(who, d, lm)) return -1;
+    if (state && state->lm != lm)
+        return dec_fail(who, !state->lm ? "the state was created without a language model" :
+                             !lm ? "the state was created with a language model" : "the state was created with another language model", 0, 0, 0);
     if (batch < 0 || T < 0) return dec_fail(who, "batch %ld, T %ld: neither may be negative", batch, T, 0);
     if (beam_width < 1 || beam_width > NNTK_RNNT_BEAM_MAX_W)
         return dec_fail(who, "beam_width %ld is outside [1, %ld]", beam_width, NNTK_RNNT_BEAM_MAX_W, 0);
@@ -344,7 +376,8 @@ static int beam_check_call(const char *who, NntkRnntDecoder d, NntkRnntBeamState
     const size_t nh = (size_t)batch * nbest;
     const void *p[5] = { labels_out, out_lengths, scores, enc, ws };
     const size_t n[5] = { nh * max_labels * sizeof(int), nh * sizeof(int), nh * sizeof(float), (size_t)batch * T * d->cfg.J * sizeof(float),
-                          device_form ? nntk_rnnt_beam_workspace_floats(d, batch, beam_width, max_labels) * sizeof(float) : 0 };
+                          !device_form ? 0 : (lm ? nntk_rnnt_beam_lm_workspace_floats(d, batch, beam_width, max_labels)
+                                                 : nntk_rnnt_beam_workspace_floats(d, batch, beam_width, max_labels)) * sizeof(float) };
     static const char *const name[5] = { "labels_out", "out_lengths", "scores", "enc", "workspace" };
     for (int i = 0; i < 3; ++i)
         for (int j = i + 1; j < 5; ++j)
@@ -359,42 +392,72 @@ static int beam_check_call(const char *who, NntkRnntDecoder d, NntkRnntBeamState
     return 0;
 }
 
-int nntk_rnnt_beam_decode_device(NntkRnntDecoder d, NntkRnntBeamState state, const float *d_enc, int batch, int T, const int *n_frames,
-                                 int beam_width, int nbest, int max_labels, int *d_labels_out, int *d_out_lengths, float *d_scores,
-                                 float *d_workspace) {
-    static const char who[] = "nntk_rnnt_beam_decode_device";
+static int beam_decode_device(const char *who, NntkRnntDecoder d, NntkRnntBeamState state, const float *d_enc, int batch, int T,
+                              const int *n_frames, int beam_width, int nbest, int max_labels, NntkNgramLm lm, int *d_labels_out,
+                              int *d_out_lengths, float *d_scores, float *d_workspace) {
     nntk_shim_clear_error();
-    if (beam_check_call(who, d, state, d_enc, batch, T, n_frames, beam_width, nbest, max_labels, d_labels_out, d_out_lengths, d_scores,
+    if (beam_check_call(who, d, state, d_enc, batch, T, n_frames, beam_width, nbest, max_labels, lm, d_labels_out, d_out_lengths, d_scores,
                         d_workspace, 1)) return -1;
     if (batch == 0) return 0;
+    nntk_shim_rnnt_lm tab;
+    if (lm && nntk_ngram_lm_rnnt_device(lm, &tab)) return -1;
     int *len = (int *)malloc((size_t)batch * sizeof(int));
     if (!len) NNTK_FAIL("nntk_rnnt_beam_decode_device: out of host memory");
     for (int b = 0; b < batch; ++b) len[b] = n_frames ? n_frames[b] : T;
     const nntk_shim_rnnt_dec m = { d->d_table, d->d_U, d->d_proj, d->d_out, d->cfg.V, d->cfg.blank, d->cfg.E, d->cfg.H, d->cfg.J,
                                    d->cfg.joint_activation, d->cfg.max_symbols_per_frame };
-    int rc = nntk_shim_rnnt_beam(&m, d_enc, batch, T, len, beam_width, nbest, max_labels, state ? &state->d : NULL, d_labels_out,
-                                 d_out_lengths, d_scores, d_workspace);
+    int rc = lm ? nntk_shim_rnnt_beam_lm(&m, d_enc, batch, T, len, beam_width, nbest, max_labels, state ? &state->d : NULL, &tab,
+                                         state ? state->d_q : NULL, d_labels_out, d_out_lengths, d_scores, d_workspace)
+                : nntk_shim_rnnt_beam(&m, d_enc, batch, T, len, beam_width, nbest, max_labels, state ? &state->d : NULL, d_labels_out,
+                                      d_out_lengths, d_scores, d_workspace);
     free(len);
     return rc;
 }
 
-int nntk_rnnt_beam_decode(NntkRnntDecoder d, NntkRnntBeamState state, const float *enc, int batch, int T, const int *n_frames,
-                          int beam_width, int nbest, int max_labels, int *labels_out, int *out_lengths, float *scores) {
-    static const char who[] = "nntk_rnnt_beam_decode";
+int nntk_rnnt_beam_decode_device(NntkRnntDecoder d, NntkRnntBeamState state, const float *d_enc, int batch, int T, const int *n_frames,
+                                 int beam_width, int nbest, int max_labels, int *d_labels_out, int *d_out_lengths, float *d_scores,
+                                 float *d_workspace) {
+    return beam_decode_device("nntk_rnnt_beam_decode_device", d, state, d_enc, batch, T, n_frames, beam_width, nbest, max_labels, NULL,
+                              d_labels_out, d_out_lengths, d_scores, d_workspace);
+}
+
+int nntk_rnnt_beam_decode_lm_device(NntkRnntDecoder d, NntkRnntBeamState state, const float *d_enc, int batch, int T, const int *n_frames,
+                                    int beam_width, int nbest, int max_labels, NntkNgramLm lm, int *d_labels_out, int *d_out_lengths,
+                                    float *d_scores, float *d_workspace) {
+    return beam_decode_device("nntk_rnnt_beam_decode_lm_device", d, state, d_enc, batch, T, n_frames, beam_width, nbest, max_labels, lm,
+                              d_labels_out, d_out_lengths, d_scores, d_workspace);
+}
+
+static int beam_decode_host(const char *who, NntkRnntDecoder d, NntkRnntBeamState state, const float *enc, int batch, int T,
+                            const int *n_frames, int beam_width, int nbest, int max_labels, NntkNgramLm lm, int *labels_out,
+                            int *out_lengths, float *scores) {
     nntk_shim_clear_error();
-    if (beam_check_call(who, d, state, enc, batch, T, n_frames, beam_width, nbest, max_labels, labels_out, out_lengths, scores, NULL, 0))
+    if (beam_check_call(who, d, state, enc, batch, T, n_frames, beam_width, nbest, max_labels, lm, labels_out, out_lengths, scores, NULL, 0))
         return -1;
     if (batch == 0) return 0;
     const size_t ne = (size_t)batch * T * d->cfg.J, nh = (size_t)batch * nbest, nl = nh * max_labels;
     float *d_enc = nntk_devbuf_reserve(&t_a, ne + 4);
     int *d_lab = (int *)nntk_devbuf_reserve(&t_b, nl + 2 * nh + 4);
-    float *d_ws = nntk_devbuf_reserve(nntk_thread_scratch(NNTK_TS_C), nntk_rnnt_beam_workspace_floats(d, batch, beam_width, max_labels));
+    float *d_ws = nntk_devbuf_reserve(nntk_thread_scratch(NNTK_TS_C), lm ? nntk_rnnt_beam_lm_workspace_floats(d, batch, beam_width, max_labels)
+                                                                          : nntk_rnnt_beam_workspace_floats(d, batch, beam_width, max_labels));
     if (!d_enc || !d_lab || !d_ws) return -1;
     int *d_len = d_lab + nl;
     float *d_sc = (float *)(d_len + nh);
     if (ne && nntk_shim_upload(d_enc, enc, ne * sizeof(float))) return -1;
-    if (nntk_rnnt_beam_decode_device(d, state, d_enc, batch, T, n_frames, beam_width, nbest, max_labels, d_lab, d_len, d_sc, d_ws)) return -1;
+    if (beam_decode_device(who, d, state, d_enc, batch, T, n_frames, beam_width, nbest, max_labels, lm, d_lab, d_len, d_sc, d_ws)) return -1;
     if (nntk_shim_download(labels_out, d_lab, nl * sizeof(int))) return -1;
     if (nntk_shim_download(out_lengths, d_len, nh * sizeof(int))) return -1;
     return nntk_shim_download(scores, d_sc, nh * sizeof(float));
+}
+
+int nntk_rnnt_beam_decode(NntkRnntDecoder d, NntkRnntBeamState state, const float *enc, int batch, int T, const int *n_frames,
+                          int beam_width, int nbest, int max_labels, int *labels_out, int *out_lengths, float *scores) {
+    return beam_decode_host("nntk_rnnt_beam_decode", d, state, enc, batch, T, n_frames, beam_width, nbest, max_labels, NULL, labels_out,
+                            out_lengths, scores);
+}
+
+int nntk_rnnt_beam_decode_lm(NntkRnntDecoder d, NntkRnntBeamState state, const float *enc, int batch, int T, const int *n_frames,
+                             int beam_width, int nbest, int max_labels, NntkNgramLm lm, int *labels_out, int *out_lengths, float *scores) {
+    return beam_decode_host("nntk_rnnt_beam_decode_lm", d, state, enc, batch, T, n_frames, beam_width, nbest, max_labels, lm, labels_out,
+                            out_lengths, scores);
 }

@@ -697,7 +697,8 @@ def ctc_beam_decode(probs, input_lengths=None, blank=0, beam_width=16, cutoff_to
 
 class NgramLm:
     """``nntk_ngram_lm_*``: a token-level n-gram language model as a deterministic backoff automaton, for ``ctc_beam_decode_lm_device``
-    and ``CtcBeamStream(lm=...)`` (INTEGRATION.md "CTC prefix beam search", Language-model fusion).  Log-probabilities are natural."""
+    and ``CtcBeamStream(lm=...)`` (INTEGRATION.md "CTC prefix beam search", Language-model fusion) and for the transducer's
+    ``RnntDecoder.beam_decode(lm=...)`` and ``RnntBeamStream(lm=...)``.  Log-probabilities are natural."""
 
     def __init__(self, h, n_states):
         self.h, self.n_states = h, n_states
@@ -795,6 +796,10 @@ class NgramLm:
 
     def device_bytes(self):
         return capi.load().nntk_ngram_lm_device_bytes(self.h)
+
+    def rnnt_device_bytes(self):
+        """the doubles the transducer beam search reads next to the lookup records of ``device_bytes``"""
+        return capi.load().nntk_ngram_lm_rnnt_device_bytes(self.h)
 
     def close(self):
         if self.h:
@@ -1134,31 +1139,37 @@ class RnntDecoder:
         return (torch.empty((B, nbest, max_labels), dtype=torch.int32, device=device),
                 torch.empty((B, nbest), dtype=torch.int32, device=device), torch.empty((B, nbest), dtype=torch.float32, device=device))
 
-    def _beam_workspace(self, device, B, beam_width, max_labels):
+    def _beam_workspace(self, device, B, beam_width, max_labels, lm=None):
         import torch
-        need = capi.load().nntk_rnnt_beam_workspace_floats(self.h, B, int(beam_width), int(max_labels))
+        size = capi.load().nntk_rnnt_beam_workspace_floats if lm is None else capi.load().nntk_rnnt_beam_lm_workspace_floats
+        need = size(self.h, B, int(beam_width), int(max_labels))
         return torch.empty(max(int(need), 4), dtype=torch.float32, device=device)
 
-    def _beam(self, state, enc, n_frames, beam_width, nbest, max_labels, outs, workspace):
+    def _beam(self, state, enc, n_frames, beam_width, nbest, max_labels, outs, workspace, lm=None):
         B, T, J = enc.shape
         assert J == self.J, "enc: [B, T, J]"
         nf = None if n_frames is None else _host_ints(n_frames, B, "n_frames")
         labels, lengths, scores = outs
-        check(capi.load().nntk_rnnt_beam_decode_device(self.h, state, _dp(enc), B, T, nf.ctypes.data_as(capi.ip) if nf is not None else None,
-                                                       int(beam_width), int(nbest), int(max_labels), _ipv(labels), _ipv(lengths),
-                                                       _dp(scores), _dp(workspace)), "nntk_rnnt_beam_decode_device")
+        head = (self.h, state, _dp(enc), B, T, nf.ctypes.data_as(capi.ip) if nf is not None else None, int(beam_width), int(nbest),
+                int(max_labels))
+        tail = (_ipv(labels), _ipv(lengths), _dp(scores), _dp(workspace))
+        if lm is None:
+            check(capi.load().nntk_rnnt_beam_decode_device(*head, *tail), "nntk_rnnt_beam_decode_device")
+        else:
+            check(capi.load().nntk_rnnt_beam_decode_lm_device(*head, lm.h, *tail), "nntk_rnnt_beam_decode_lm_device")
         return outs
 
-    def beam_decode(self, enc, n_frames=None, beam_width=8, nbest=1, max_labels=None):
+    def beam_decode(self, enc, n_frames=None, beam_width=8, nbest=1, max_labels=None, lm=None):
         """``nntk_rnnt_beam_decode_device`` (INTEGRATION.md "RNN-Transducer: beam search"): enc [B, T, J] device tensor, n_frames host
         ints per row (None: T) -> (labels [B, nbest, max_labels] int32, -1 behind each hypothesis's labels; lengths [B, nbest] int32,
         -1 for a slot without a hypothesis; scores [B, nbest] float32, -inf there).  max_labels defaults to
-        max_symbols_per_frame * T, which never truncates."""
+        max_symbols_per_frame * T, which never truncates.  lm: an NgramLm fused into the search
+        (``nntk_rnnt_beam_decode_lm_device``; scores then hold the model's terms and its end-of-sentence term), or None."""
         B, T, _ = enc.shape
         if max_labels is None:
             max_labels = max(1, self.max_symbols * T)
         return self._beam(None, enc, n_frames, beam_width, nbest, max_labels, self._beam_outputs(enc.device, B, nbest, max_labels),
-                          self._beam_workspace(enc.device, B, beam_width, max_labels))
+                          self._beam_workspace(enc.device, B, beam_width, max_labels, lm), lm)
 
     def destroy(self):
         if self.h:
@@ -1215,12 +1226,16 @@ class RnntBeamStream:
     """``nntk_rnnt_beam_state_*``: transducer beam search pushed chunk by chunk for ``batch`` independent streams.  After every push
     row b holds what ``decoder.beam_decode`` gives on the row's frames since its last reset, bit for bit.  The stream owns the output
     buffers (labels [batch, nbest, max_labels]; lengths, scores [batch, nbest]) and the workspace, and returns the outputs from every
-    push."""
+    push.  lm: an NgramLm fused into the search (``nntk_rnnt_beam_state_create_lm``); it must stay open as long as the stream."""
 
-    def __init__(self, decoder, batch, beam_width, nbest, max_labels):
+    def __init__(self, decoder, batch, beam_width, nbest, max_labels, lm=None):
         self.dec, self.B, self.W, self.nbest, self.max_labels = decoder, int(batch), int(beam_width), int(nbest), int(max_labels)
         self.outs = self.ws = None
-        self.h = capi.load().nntk_rnnt_beam_state_create(decoder.h, self.B, self.W, self.max_labels)
+        self.lm = lm
+        if lm is None:
+            self.h = capi.load().nntk_rnnt_beam_state_create(decoder.h, self.B, self.W, self.max_labels)
+        else:
+            self.h = capi.load().nntk_rnnt_beam_state_create_lm(decoder.h, self.B, self.W, self.max_labels, lm.h)
         if not self.h:
             raise capi.NNTKError("nntk_rnnt_beam_state_create: " + capi.last_error())
 
@@ -1229,8 +1244,8 @@ class RnntBeamStream:
         assert enc_chunk.shape[0] == self.B, "enc_chunk: [batch, T, J]"
         if self.outs is None:
             self.outs = self.dec._beam_outputs(enc_chunk.device, self.B, self.nbest, self.max_labels)
-            self.ws = self.dec._beam_workspace(enc_chunk.device, self.B, self.W, self.max_labels)
-        return self.dec._beam(self.h, enc_chunk, n_frames, self.W, self.nbest, self.max_labels, self.outs, self.ws)
+            self.ws = self.dec._beam_workspace(enc_chunk.device, self.B, self.W, self.max_labels, self.lm)
+        return self.dec._beam(self.h, enc_chunk, n_frames, self.W, self.nbest, self.max_labels, self.outs, self.ws, self.lm)
 
     def reset(self, rows=None):
         """these rows (None: every row) start new streams"""
@@ -1253,9 +1268,10 @@ class RnntBeamStream:
 
 
 def rnnt_beam_decode(embed, lstm_block, pred_proj, out, enc, n_frames=None, beam_width=8, nbest=1, max_labels=None, blank=0,
-                     joint_activation=ACT_TANH, max_symbols_per_frame=10):
+                     joint_activation=ACT_TANH, max_symbols_per_frame=10, lm=None):
     """Transducer beam search on numpy arrays (the weights go to the device, ``nntk_rnnt_beam_decode`` takes enc and the results as
-    host memory): enc [B, T, J] -> (labels [B, nbest, max_labels], lengths [B, nbest], scores [B, nbest])"""
+    host memory): enc [B, T, J] -> (labels [B, nbest, max_labels], lengths [B, nbest], scores [B, nbest]).  lm: an NgramLm fused into
+    the search (``nntk_rnnt_beam_decode_lm``), or None."""
     import torch
     dev = lambda a: None if a is None else torch.from_numpy(_f32(a).reshape(-1) if a is not embed else _f32(a)).cuda()
     dec = RnntDecoder(dev(embed), dev(lstm_block), dev(pred_proj), dev(out), blank, joint_activation, max_symbols_per_frame)
@@ -1267,9 +1283,13 @@ def rnnt_beam_decode(embed, lstm_block, pred_proj, out, enc, n_frames=None, beam
     labels = np.empty((B, nbest, max_labels), np.int32)
     lengths, scores = np.empty((B, nbest), np.int32), np.empty((B, nbest), np.float32)
     try:
-        check(capi.load().nntk_rnnt_beam_decode(dec.h, None, _p(enc), B, T, nf.ctypes.data_as(capi.ip) if nf is not None else None,
-                                                int(beam_width), int(nbest), int(max_labels), labels.ctypes.data_as(capi.ip),
-                                                lengths.ctypes.data_as(capi.ip), _p(scores)), "nntk_rnnt_beam_decode")
+        head = (dec.h, None, _p(enc), B, T, nf.ctypes.data_as(capi.ip) if nf is not None else None, int(beam_width), int(nbest),
+                int(max_labels))
+        tail = (labels.ctypes.data_as(capi.ip), lengths.ctypes.data_as(capi.ip), _p(scores))
+        if lm is None:
+            check(capi.load().nntk_rnnt_beam_decode(*head, *tail), "nntk_rnnt_beam_decode")
+        else:
+            check(capi.load().nntk_rnnt_beam_decode_lm(*head, lm.h, *tail), "nntk_rnnt_beam_decode_lm")
     finally:
         dec.destroy()
     return labels, lengths, scores
