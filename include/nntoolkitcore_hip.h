@@ -1097,6 +1097,49 @@ int nntk_rnnt_fused_loss(const float *enc, const float *pred, const float *out, 
                          const int *input_lengths, const int *labels, const int *label_lengths, int max_label_len, int blank,
                          float *loss_rows, float *denc, float *dpred, float *dout);
 
+/* ---- RNN-Transducer: forced alignment (csrc/hip/rnnt_align.hip; INTEGRATION.md "RNN-Transducer: forced alignment") ----
+ * Given a row's labels, its single most probable path through the lattice (Viterbi): in which frame every label is emitted.
+ *   d_logits, input_lengths, labels, label_lengths, blank: as for nntk_rnnt_loss_device, with exactly its checks, made before anything
+ *     is enqueued: -1, nntk_last_error(), nothing written, no device needed.  The fused form takes d_enc, d_pred, d_out, J, V and
+ *     activation as nntk_rnnt_fused_loss_device does, with that call's checks and its limits J <= 1024, V <= 8192; the scores are
+ *     never stored.  Cells with t >= T_b or u > U_b influence nothing and may hold NaN.
+ *   v(0, 0) = 1; into cell (t, u) the candidates are taken in the order v(t-1, u) p_blank(t-1, u) (the blank move), then
+ *     v(t, u-1) p_{y_u}(t, u-1) (the label move), and the label move replaces the blank move only if it is strictly greater; the path's
+ *     probability is v(T_b-1, U_b) p_blank(T_b-1, U_b).  Values and emissions carry an int32 exponent of their own: no underflow at
+ *     any T + U.  As in the loss, an emission below 2^-4000 of its cell's total counts as 2^-4000.
+ *   d_label_frames [batch][max_label_len] or NULL: the frame t in which label i < U_b is emitted (the move (t, i) -> (t, i + 1)),
+ *     non-decreasing in i; -1 for i >= U_b.
+ *   d_frame_labels [batch][T] or NULL: the number of labels emitted when frame t < T_b is left by its blank (the u of that blank move);
+ *     -1 for t >= T_b.
+ *   d_label_logp [batch][max_label_len] / d_frame_logp [batch][T], or NULL: ln of the label's emission and of the frame's blank
+ *     emission on the path, from mantissa and exponent; 0 in the padding.  exp(label_logp) is a per-label confidence.
+ *   d_scores [batch]: ln of the path's probability; the sum of the row's label_logp and frame_logp up to rounding.  A row whose every
+ *     path holds a zero emission (-inf scores): -inf, label_frames and frame_labels -1, both logp arrays 0.
+ *   Every element of every non-NULL output is written.  Outputs may not overlap one another, the inputs or the workspace.
+ *   d_workspace, 16-byte aligned: nntk_rnnt_align_workspace_floats(batch, T, max_label_len) =
+ *     nntk_rnnt_workspace_floats(batch, T, max_label_len, 0) rounded up to 4 floats, plus one backpointer byte per cell of
+ *     batch (T + max_label_len) anti-diagonals, each min(T, max_label_len + 1) cells wide (rounded up to 16 bytes), plus 16 bytes;
+ *     nntk_rnnt_fused_align_workspace_floats(batch, T, max_label_len, J, V): the same on top of
+ *     nntk_rnnt_fused_workspace_floats(batch, T, max_label_len, J, V, 0).
+ * Limits: max_label_len <= 4000, T + max_label_len <= 65536.  Deterministic: no atomics, the same bits on every call; a row's bits
+ * do not depend on the other rows, on its position in the batch or on the T / max_label_len padding.  The device forms run on the
+ * calling thread's stream and read nothing back; the host-pointer forms upload, run the device form and download. */
+size_t nntk_rnnt_align_workspace_floats(int batch, int T, int max_label_len);
+int nntk_rnnt_align_device(const float *d_logits, int batch, int T, int V, const int *input_lengths, const int *labels,
+                           const int *label_lengths, int max_label_len, int blank, int *d_label_frames, int *d_frame_labels,
+                           float *d_label_logp, float *d_frame_logp, float *d_scores, float *d_workspace);
+int nntk_rnnt_align(const float *logits, int batch, int T, int V, const int *input_lengths, const int *labels, const int *label_lengths,
+                    int max_label_len, int blank, int *label_frames, int *frame_labels, float *label_logp, float *frame_logp,
+                    float *scores);
+size_t nntk_rnnt_fused_align_workspace_floats(int batch, int T, int max_label_len, int J, int V);
+int nntk_rnnt_fused_align_device(const float *d_enc, const float *d_pred, const float *d_out, int batch, int T, int J, int V, int activation,
+                                 const int *input_lengths, const int *labels, const int *label_lengths, int max_label_len, int blank,
+                                 int *d_label_frames, int *d_frame_labels, float *d_label_logp, float *d_frame_logp, float *d_scores,
+                                 float *d_workspace);
+int nntk_rnnt_fused_align(const float *enc, const float *pred, const float *out, int batch, int T, int J, int V, int activation,
+                          const int *input_lengths, const int *labels, const int *label_lengths, int max_label_len, int blank,
+                          int *label_frames, int *frame_labels, float *label_logp, float *frame_logp, float *scores);
+
 /* ---- RNN-Transducer: greedy decoding (csrc/hip/rnnt_decode.hip; INTEGRATION.md "RNN-Transducer: greedy decoding") ----
  * The model: a one-layer LSTM prediction network over a label embedding, a linear projection to the joiner width, the joiner of
  * nntk_rnnt_joint_device and a vocabulary Dense.  V classes, embedding width E, hidden width H, joiner width J; caller-owned device blocks:

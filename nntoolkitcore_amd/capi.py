@@ -471,6 +471,15 @@ SIGNATURES = {
                                               vp, vp, vp, vp, vp]),
     "nntk_rnnt_fused_loss": (C.c_int, [fp, fp, fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, ip, ip, ip, C.c_int, C.c_int,
                                        fp, fp, fp, fp]),
+    # RNN-Transducer: forced alignment on stored scores and on the joiner's inputs (INTEGRATION.md "RNN-Transducer: forced alignment")
+    "nntk_rnnt_align_workspace_floats": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "nntk_rnnt_align_device": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, ip, ip, ip, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp]),
+    "nntk_rnnt_align": (C.c_int, [fp, C.c_int, C.c_int, C.c_int, ip, ip, ip, C.c_int, C.c_int, ip, ip, fp, fp, fp]),
+    "nntk_rnnt_fused_align_workspace_floats": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "nntk_rnnt_fused_align_device": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, ip, ip, ip, C.c_int, C.c_int,
+                                               vp, vp, vp, vp, vp, vp]),
+    "nntk_rnnt_fused_align": (C.c_int, [fp, fp, fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, ip, ip, ip, C.c_int, C.c_int,
+                                        ip, ip, fp, fp, fp]),
     # RNN-Transducer: greedy decoding, one-shot and streamed (INTEGRATION.md "RNN-Transducer: greedy decoding")
     "nntk_rnnt_decoder_create": (vp, [NntkRnntDecoderConfig, vp, vp, vp, vp]),
     "nntk_rnnt_decoder_load_weights_device": (C.c_int, [vp, vp, vp, vp, vp]),

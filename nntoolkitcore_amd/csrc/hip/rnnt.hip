@@ -298,6 +298,18 @@ int nntk_rnnt_lattice_launch(int B, int T, int U1, const int *d_ints, const floa
     return 0;
 }
 
+// the emissions of the stored scores, for this unit and for rnnt_align.hip; d_logits 16-byte aligned; lse NULL: not kept
+int nntk_rnnt_emit_launch(const float *d_logits, int B, int T, int U1, int V, int blank, const int *d_ints, float4 *em, double *lse) {
+    const long cells = (long)B * T * U1;
+    const dim3 cgrid(rnnt_grid(cells, 4));
+    if ((V & 3) == 0)
+        hipLaunchKernelGGL(rnnt_emit_kernel<true>, cgrid, dim3(CTC_THREADS), 0, nntk_stream(), d_logits, B, T, U1, V, blank, d_ints, em, lse, cells);
+    else
+        hipLaunchKernelGGL(rnnt_emit_kernel<false>, cgrid, dim3(CTC_THREADS), 0, nntk_stream(), d_logits, B, T, U1, V, blank, d_ints, em, lse, cells);
+    NNTK_LAUNCH_CHECK("rnnt_emit_kernel");
+    return 0;
+}
+
 extern "C" {
 
 size_t nntk_shim_rnnt_workspace_floats(int batch, int T, int max_label_len, int want_grad) {
@@ -324,11 +336,7 @@ int nntk_shim_rnnt_loss(const float *d_logits, int B, int T, int V, const int *h
     float2 *wa = d_dlogits ? (float2 *)(d_ws + lay.alpha) : nullptr, *wb = d_dlogits ? (float2 *)(d_ws + lay.beta) : nullptr;
     const bool vec = (V & 3) == 0;
     const dim3 cgrid(rnnt_grid(cells, 4));
-    if (vec)
-        hipLaunchKernelGGL(rnnt_emit_kernel<true>, cgrid, dim3(CTC_THREADS), 0, nntk_stream(), d_logits, B, T, U1, V, blank, d_ints, em, lse, cells);
-    else
-        hipLaunchKernelGGL(rnnt_emit_kernel<false>, cgrid, dim3(CTC_THREADS), 0, nntk_stream(), d_logits, B, T, U1, V, blank, d_ints, em, lse, cells);
-    NNTK_LAUNCH_CHECK("rnnt_emit_kernel");
+    if (nntk_rnnt_emit_launch(d_logits, B, T, U1, V, blank, d_ints, em, lse)) return -1;
     if (nntk_rnnt_lattice_launch(B, T, U1, d_ints, em, wa, wb, hdr, d_loss_rows)) return -1;
     if (d_dlogits) {
         if (vec)

@@ -27,6 +27,18 @@ static inline RnntLayout rnnt_layout(int B, int T, int maxL, int want_grad) {
     return l;
 }
 
+// forced alignment (rnnt_align.hip): a loss-only workspace of `base` words (either loss call's), then one backpointer byte per cell of
+// the row's T + maxL diagonals, each min(T, maxL + 1) wide, then 16 bytes the staging loads may run into
+struct RnntAlignLayout { size_t bp, total; };
+static inline RnntAlignLayout rnnt_align_layout(size_t base, int B, int T, int maxL) {
+    RnntAlignLayout l;
+    const size_t b = B > 0 ? (size_t)B : 0, t = T > 0 ? (size_t)T : 0, ml = maxL > 0 ? (size_t)maxL : 0;
+    auto up = [](size_t x) { return (x + 3) & ~(size_t)3; };
+    l.bp = up(base);
+    l.total = l.bp + up((b * (t + ml) * (t < ml + 1 ? t : ml + 1) + 3) / 4) + 4;
+    return l;
+}
+
 // exp(x - lse) as mantissa and exponent; -inf (and NaN) scores: zero
 __device__ __forceinline__ xf rnnt_emission(float x, double lse) {
     if (!(x > -INFINITY)) return xf_zero();
@@ -60,3 +72,8 @@ static inline unsigned rnnt_grid(long items, long per_block) {
 // rnnt.hip: rnnt_lattice_kernel on the emissions em [cells] (float4 each); wa / wb NULL = the forward direction alone (loss only)
 int nntk_rnnt_lattice_launch(int B, int T, int U1, const int *d_ints, const float4 *em, float2 *wa, float2 *wb, float *hdr,
                              float *d_loss_rows);
+// rnnt.hip: rnnt_emit_kernel, the emissions of the stored scores d_logits [B][T][U1][V] into em; lse NULL = not kept (loss only)
+int nntk_rnnt_emit_launch(const float *d_logits, int B, int T, int U1, int V, int blank, const int *d_ints, float4 *em, double *lse);
+// rnnt_fused.hip: rnnt_fused_forward_kernel, the same emissions from the joiner's inputs and the Dense block d_out
+int nntk_rnnt_fused_emit_launch(const float *d_enc, const float *d_pred, const float *d_out, int B, int T, int U1, int J, int V, int kind,
+                                int blank, const int *d_ints, float4 *em, double *lse);

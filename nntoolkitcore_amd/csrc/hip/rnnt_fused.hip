@@ -392,6 +392,18 @@ __global__ __launch_bounds__(256) void rnnt_fused_transpose_kernel(const float *
         if (v0 + r < V && j0 + x < J) WT[(long)(v0 + r) * J + j0 + x] = t[x][r];
 }
 
+// the emissions from the joiner's inputs, for this unit and for rnnt_align.hip; lse NULL: not kept (the loss-only form)
+int nntk_rnnt_fused_emit_launch(const float *d_enc, const float *d_pred, const float *d_out, int B, int T, int U1, int J, int V, int kind,
+                                int blank, const int *d_ints, float4 *em, double *lse) {
+    const long cells = (long)B * T * U1, tiles = (cells + FT_M - 1) / FT_M;
+    const size_t zbytes = (size_t)J * FT_PITCH * sizeof(float);
+    if (zbytes > 48 * 1024 && nntk_set_max_dynamic_lds((const void *)rnnt_fused_forward_kernel, zbytes)) return -1;
+    hipLaunchKernelGGL(rnnt_fused_forward_kernel, dim3(rnnt_grid(tiles, 1)), dim3(FT_THREADS), zbytes, nntk_stream(), d_enc, d_pred, d_out, B,
+                       T, U1, J, V, kind, blank, d_ints, em, lse, cells, tiles);
+    NNTK_LAUNCH_CHECK("rnnt_fused_forward_kernel");
+    return 0;
+}
+
 extern "C" {
 
 size_t nntk_shim_rnnt_fused_workspace_floats(int batch, int T, int max_label_len, int J, int V, int want_grad) {
@@ -418,10 +430,7 @@ int nntk_shim_rnnt_fused_loss(const float *d_enc, const float *d_pred, const flo
     double *lse = grad ? (double *)(d_ws + lay.base.lse) : nullptr;
     float2 *wa = grad ? (float2 *)(d_ws + lay.base.alpha) : nullptr, *wb = grad ? (float2 *)(d_ws + lay.base.beta) : nullptr;
     const size_t zbytes = (size_t)J * FT_PITCH * sizeof(float);
-    if (zbytes > 48 * 1024 && nntk_set_max_dynamic_lds((const void *)rnnt_fused_forward_kernel, zbytes)) return -1;
-    hipLaunchKernelGGL(rnnt_fused_forward_kernel, dim3(rnnt_grid(tiles, 1)), dim3(FT_THREADS), zbytes, nntk_stream(), d_enc, d_pred, d_out, B,
-                       T, U1, J, V, kind, blank, d_ints, em, lse, cells, tiles);
-    NNTK_LAUNCH_CHECK("rnnt_fused_forward_kernel");
+    if (nntk_rnnt_fused_emit_launch(d_enc, d_pred, d_out, B, T, U1, J, V, kind, blank, d_ints, em, lse)) return -1;
     if (nntk_rnnt_lattice_launch(B, T, U1, d_ints, em, wa, wb, hdr, d_loss_rows)) return -1;
     if (!grad) return 0;
     float *wt = d_ws + lay.wt, *partial = d_ws + lay.partial, *dzt = d_ws + lay.dz;

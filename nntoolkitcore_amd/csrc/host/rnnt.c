@@ -216,3 +216,160 @@ int nntk_rnnt_fused_loss(const float *enc, const float *pred, const float *out, 
         nntk_shim_download(dpred, d_g + ne, (size_t)batch * U1 * J * sizeof(float))) return -1;
     return nntk_shim_download(dout, d_g + ne + npd, ((size_t)J + 1) * V * sizeof(float));
 }
+
+/* ---- forced alignment (csrc/hip/rnnt_align.hip): the best single path, on stored scores and on the joiner's inputs ---- */
+/* the first `outputs` spans each against everything after it; a span at 0 is an output not asked for */
+static int align_overlap(const char *who, const fused_span *sp, int outputs, int n) {
+    for (int o = 0; o < outputs; ++o)
+        for (int k = o + 1; k < n; ++k)
+            if (sp[o].at && sp[k].at && sp[o].at < sp[k].at + sp[k].bytes && sp[k].at < sp[o].at + sp[o].bytes) {
+                char msg[200];
+                snprintf(msg, sizeof msg, "%s: %s overlaps %s", who, sp[o].name, sp[k].name);
+                nntk_set_error(msg);
+                return -1;
+            }
+    return 0;
+}
+
+static int align_check_outputs(const char *who, const int *label_frames, const int *frame_labels, const float *label_logp,
+                               const float *frame_logp, const float *scores) {
+    return rnnt_check_ptr(who, "scores", scores, 4) || (label_frames && rnnt_check_ptr(who, "label_frames", label_frames, 4)) ||
+           (frame_labels && rnnt_check_ptr(who, "frame_labels", frame_labels, 4)) ||
+           (label_logp && rnnt_check_ptr(who, "label_logp", label_logp, 4)) || (frame_logp && rnnt_check_ptr(who, "frame_logp", frame_logp, 4));
+}
+
+size_t nntk_rnnt_align_workspace_floats(int batch, int T, int max_label_len) {
+    return nntk_shim_rnnt_align_workspace_floats(batch, T, max_label_len);
+}
+
+int nntk_rnnt_align_device(const float *d_logits, int batch, int T, int V, const int *input_lengths, const int *labels,
+                           const int *label_lengths, int max_label_len, int blank, int *d_label_frames, int *d_frame_labels,
+                           float *d_label_logp, float *d_frame_logp, float *d_scores, float *d_workspace) {
+    static const char who[] = "nntk_rnnt_align_device";
+    nntk_shim_clear_error();
+    if (rnnt_check(who, batch, T, V, input_lengths, labels, label_lengths, max_label_len, blank)) return -1;
+    if (batch == 0) return 0;
+    if (rnnt_check_ptr(who, "d_logits", d_logits, 16) || rnnt_check_ptr(who, "d_workspace", d_workspace, 16) ||
+        align_check_outputs(who, d_label_frames, d_frame_labels, d_label_logp, d_frame_logp, d_scores)) return -1;
+    const size_t f = sizeof(float), nl = (size_t)batch * max_label_len * f, nt = (size_t)batch * T * f;
+    const fused_span sp[] = {{"d_label_frames", (uintptr_t)d_label_frames, nl}, {"d_frame_labels", (uintptr_t)d_frame_labels, nt},
+                             {"d_label_logp", (uintptr_t)d_label_logp, nl}, {"d_frame_logp", (uintptr_t)d_frame_logp, nt},
+                             {"d_scores", (uintptr_t)d_scores, (size_t)batch * f},
+                             {"d_logits", (uintptr_t)d_logits, (size_t)batch * T * (max_label_len + 1) * V * f},
+                             {"d_workspace", (uintptr_t)d_workspace, nntk_shim_rnnt_align_workspace_floats(batch, T, max_label_len) * f}};
+    if (align_overlap(who, sp, 5, 7)) return -1;
+    int *len = (int *)malloc((size_t)batch * sizeof(int));
+    if (!len) NNTK_FAIL("out of host memory");
+    for (int b = 0; b < batch; ++b) len[b] = input_lengths ? input_lengths[b] : T;
+    int rc = nntk_shim_rnnt_align(d_logits, batch, T, V, len, labels, label_lengths, max_label_len, blank, d_label_frames, d_frame_labels,
+                                  d_label_logp, d_frame_logp, d_scores, d_workspace);
+    free(len);
+    return rc;
+}
+
+/* the outputs of both host-pointer forms live in one device block: label_frames | frame_labels | label_logp | frame_logp | scores,
+ * a part that is not asked for taking no room */
+typedef struct { size_t lf, fl, ll, fp, sc, total; } align_out;
+static align_out align_out_layout(int batch, int T, int max_label_len, const void *label_frames, const void *frame_labels,
+                                  const void *label_logp, const void *frame_logp) {
+    align_out o;
+    const size_t nl = (size_t)batch * max_label_len, nt = (size_t)batch * T;
+    o.lf = 0;
+    o.fl = o.lf + (label_frames ? nl : 0);
+    o.ll = o.fl + (frame_labels ? nt : 0);
+    o.fp = o.ll + (label_logp ? nl : 0);
+    o.sc = o.fp + (frame_logp ? nt : 0);
+    o.total = o.sc + (size_t)batch;
+    return o;
+}
+
+static int align_download(const align_out *o, const float *d_o, int batch, int T, int max_label_len, int *label_frames, int *frame_labels,
+                          float *label_logp, float *frame_logp, float *scores) {
+    const size_t nl = (size_t)batch * max_label_len * sizeof(float), nt = (size_t)batch * T * sizeof(float);
+    if (label_frames && nl && nntk_shim_download(label_frames, d_o + o->lf, nl)) return -1;
+    if (frame_labels && nntk_shim_download(frame_labels, d_o + o->fl, nt)) return -1;
+    if (label_logp && nl && nntk_shim_download(label_logp, d_o + o->ll, nl)) return -1;
+    if (frame_logp && nntk_shim_download(frame_logp, d_o + o->fp, nt)) return -1;
+    return nntk_shim_download(scores, d_o + o->sc, (size_t)batch * sizeof(float));
+}
+
+int nntk_rnnt_align(const float *logits, int batch, int T, int V, const int *input_lengths, const int *labels, const int *label_lengths,
+                    int max_label_len, int blank, int *label_frames, int *frame_labels, float *label_logp, float *frame_logp,
+                    float *scores) {
+    static const char who[] = "nntk_rnnt_align";
+    nntk_shim_clear_error();
+    if (rnnt_check(who, batch, T, V, input_lengths, labels, label_lengths, max_label_len, blank)) return -1;
+    if (batch == 0) return 0;
+    if (rnnt_check_ptr(who, "logits", logits, 4) || align_check_outputs(who, label_frames, frame_labels, label_logp, frame_logp, scores))
+        return -1;
+    const size_t n = (size_t)batch * T * (max_label_len + 1) * V;
+    const align_out o = align_out_layout(batch, T, max_label_len, label_frames, frame_labels, label_logp, frame_logp);
+    float *d_x = nntk_devbuf_reserve(&t_a, n + 4);
+    float *d_o = nntk_devbuf_reserve(&t_b, o.total + 4);
+    float *d_ws = nntk_devbuf_reserve(&t_c, nntk_shim_rnnt_align_workspace_floats(batch, T, max_label_len));
+    if (!d_x || !d_o || !d_ws) return -1;
+    if (nntk_shim_upload(d_x, logits, n * sizeof(float))) return -1;
+    if (nntk_rnnt_align_device(d_x, batch, T, V, input_lengths, labels, label_lengths, max_label_len, blank,
+                               label_frames ? (int *)(d_o + o.lf) : NULL, frame_labels ? (int *)(d_o + o.fl) : NULL,
+                               label_logp ? d_o + o.ll : NULL, frame_logp ? d_o + o.fp : NULL, d_o + o.sc, d_ws)) return -1;
+    return align_download(&o, d_o, batch, T, max_label_len, label_frames, frame_labels, label_logp, frame_logp, scores);
+}
+
+size_t nntk_rnnt_fused_align_workspace_floats(int batch, int T, int max_label_len, int J, int V) {
+    return nntk_shim_rnnt_fused_align_workspace_floats(batch, T, max_label_len, J, V);
+}
+
+int nntk_rnnt_fused_align_device(const float *d_enc, const float *d_pred, const float *d_out, int batch, int T, int J, int V, int activation,
+                                 const int *input_lengths, const int *labels, const int *label_lengths, int max_label_len, int blank,
+                                 int *d_label_frames, int *d_frame_labels, float *d_label_logp, float *d_frame_logp, float *d_scores,
+                                 float *d_workspace) {
+    static const char who[] = "nntk_rnnt_fused_align_device";
+    nntk_shim_clear_error();
+    if (fused_check(who, batch, T, J, V, activation, input_lengths, labels, label_lengths, max_label_len, blank, NULL, NULL, NULL)) return -1;
+    if (batch == 0) return 0;
+    if (rnnt_check_ptr(who, "d_enc", d_enc, 4) || rnnt_check_ptr(who, "d_pred", d_pred, 4) || rnnt_check_ptr(who, "d_out", d_out, 4) ||
+        rnnt_check_ptr(who, "d_workspace", d_workspace, 16) ||
+        align_check_outputs(who, d_label_frames, d_frame_labels, d_label_logp, d_frame_logp, d_scores)) return -1;
+    const size_t f = sizeof(float), nl = (size_t)batch * max_label_len * f, nt = (size_t)batch * T * f;
+    const fused_span sp[] = {{"d_label_frames", (uintptr_t)d_label_frames, nl}, {"d_frame_labels", (uintptr_t)d_frame_labels, nt},
+                             {"d_label_logp", (uintptr_t)d_label_logp, nl}, {"d_frame_logp", (uintptr_t)d_frame_logp, nt},
+                             {"d_scores", (uintptr_t)d_scores, (size_t)batch * f},
+                             {"d_enc", (uintptr_t)d_enc, (size_t)batch * T * J * f},
+                             {"d_pred", (uintptr_t)d_pred, (size_t)batch * (max_label_len + 1) * J * f},
+                             {"d_out", (uintptr_t)d_out, ((size_t)J + 1) * V * f},
+                             {"d_workspace", (uintptr_t)d_workspace,
+                              nntk_shim_rnnt_fused_align_workspace_floats(batch, T, max_label_len, J, V) * f}};
+    if (align_overlap(who, sp, 5, 9)) return -1;
+    int *len = (int *)malloc((size_t)batch * sizeof(int));
+    if (!len) NNTK_FAIL("out of host memory");
+    for (int b = 0; b < batch; ++b) len[b] = input_lengths ? input_lengths[b] : T;
+    int rc = nntk_shim_rnnt_fused_align(d_enc, d_pred, d_out, batch, T, J, V, activation, len, labels, label_lengths, max_label_len, blank,
+                                        d_label_frames, d_frame_labels, d_label_logp, d_frame_logp, d_scores, d_workspace);
+    free(len);
+    return rc;
+}
+
+int nntk_rnnt_fused_align(const float *enc, const float *pred, const float *out, int batch, int T, int J, int V, int activation,
+                          const int *input_lengths, const int *labels, const int *label_lengths, int max_label_len, int blank,
+                          int *label_frames, int *frame_labels, float *label_logp, float *frame_logp, float *scores) {
+    static const char who[] = "nntk_rnnt_fused_align";
+    nntk_shim_clear_error();
+    if (fused_check(who, batch, T, J, V, activation, input_lengths, labels, label_lengths, max_label_len, blank, NULL, NULL, NULL)) return -1;
+    if (batch == 0) return 0;
+    if (rnnt_check_ptr(who, "enc", enc, 4) || rnnt_check_ptr(who, "pred", pred, 4) || rnnt_check_ptr(who, "out", out, 4) ||
+        align_check_outputs(who, label_frames, frame_labels, label_logp, frame_logp, scores)) return -1;
+    const size_t up = 3, U1 = (size_t)max_label_len + 1;
+    const size_t ne = ((size_t)batch * T * J + up) & ~up, npd = ((size_t)batch * U1 * J + up) & ~up, nw = (((size_t)J + 1) * V + up) & ~up;
+    const align_out o = align_out_layout(batch, T, max_label_len, label_frames, frame_labels, label_logp, frame_logp);
+    float *d_in = nntk_devbuf_reserve(&t_a, ne + npd + nw + 4);
+    float *d_o = nntk_devbuf_reserve(&t_b, o.total + 4);
+    float *d_ws = nntk_devbuf_reserve(&t_c, nntk_shim_rnnt_fused_align_workspace_floats(batch, T, max_label_len, J, V));
+    if (!d_in || !d_o || !d_ws) return -1;
+    float *d_enc = d_in, *d_pred = d_in + ne, *d_out = d_pred + npd;
+    if (nntk_shim_upload(d_enc, enc, (size_t)batch * T * J * sizeof(float)) || nntk_shim_upload(d_pred, pred, (size_t)batch * U1 * J * sizeof(float)) ||
+        nntk_shim_upload(d_out, out, ((size_t)J + 1) * V * sizeof(float))) return -1;
+    if (nntk_rnnt_fused_align_device(d_enc, d_pred, d_out, batch, T, J, V, activation, input_lengths, labels, label_lengths, max_label_len, blank,
+                                     label_frames ? (int *)(d_o + o.lf) : NULL, frame_labels ? (int *)(d_o + o.fl) : NULL,
+                                     label_logp ? d_o + o.ll : NULL, frame_logp ? d_o + o.fp : NULL, d_o + o.sc, d_ws)) return -1;
+    return align_download(&o, d_o, batch, T, max_label_len, label_frames, frame_labels, label_logp, frame_logp, scores);
+}

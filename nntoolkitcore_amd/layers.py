@@ -1071,6 +1071,91 @@ def rnnt_fused_loss(enc, pred, out_block, labels, label_lengths=None, input_leng
     return (loss,) + g
 
 
+def _align_outputs(dev, B, T, maxL, given):
+    """the five outputs of the alignment calls as device tensors, those the caller passed reused"""
+    import torch
+    shapes = (((B, maxL), torch.int32), ((B, T), torch.int32), ((B, maxL), torch.float32), ((B, T), torch.float32), ((B,), torch.float32))
+    outs = [torch.empty(s, dtype=d, device=dev) if g is None else g for (s, d), g in zip(shapes, given)]
+    for o, (s, d) in zip(outs, shapes):
+        assert tuple(o.shape) == s and o.dtype == d and o.is_contiguous(), "alignment outputs: %s %s" % (s, d)
+    return outs
+
+
+def rnnt_align_device(logits, labels, label_lengths=None, input_lengths=None, blank=0, label_frames=None, frame_labels=None,
+                      label_logp=None, frame_logp=None, scores=None, workspace=None):
+    """``nntk_rnnt_align_device``: the most probable path of logits [B,T,U1,V] (as for ``rnnt_loss_device``) through each row's labels ->
+    (label_frames [B,U1-1] int32, the frame each label is emitted in, -1 behind the row's labels; frame_labels [B,T] int32, the number of
+    labels emitted when each frame is left, -1 behind the row's frames; label_logp [B,U1-1] and frame_logp [B,T] float32, ln of those
+    label and blank emissions, 0 in the padding; scores [B] float32 = ln of the path's probability, -inf where there is no path)"""
+    import torch
+    B, T, U1, V = logits.shape
+    lab, ll = _rnnt_labels(labels, label_lengths, B, U1 - 1)
+    il, ilp = _ctc_lengths(input_lengths, B)
+    L = capi.load()
+    need = L.nntk_rnnt_align_workspace_floats(B, T, U1 - 1)
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.float32, device=logits.device)
+    assert workspace.numel() >= need, "workspace: nntk_rnnt_align_workspace_floats(B, T, max_label_len) floats"
+    outs = _align_outputs(logits.device, B, T, U1 - 1, (label_frames, frame_labels, label_logp, frame_logp, scores))
+    check(L.nntk_rnnt_align_device(_dp(logits), B, T, V, ilp, lab.ctypes.data_as(capi.ip), ll.ctypes.data_as(capi.ip), U1 - 1, blank,
+                                   *[C.c_void_p(o.data_ptr()) for o in outs], _dp(workspace)), "nntk_rnnt_align_device")
+    return tuple(outs)
+
+
+def rnnt_align(logits, labels, label_lengths=None, input_lengths=None, blank=0):
+    """The host-memory form (``nntk_rnnt_align``): logits [B,T,U1,V] numpy array."""
+    logits = _f32(logits)
+    B, T, U1, V = logits.shape
+    lab, ll = _rnnt_labels(labels, label_lengths, B, U1 - 1)
+    il, ilp = _ctc_lengths(input_lengths, B)
+    lf, fl = np.empty((B, U1 - 1), np.int32), np.empty((B, T), np.int32)
+    lp, fp, sc = np.empty((B, U1 - 1), np.float32), np.empty((B, T), np.float32), np.empty(B, np.float32)
+    check(capi.load().nntk_rnnt_align(_p(logits), B, T, V, ilp, lab.ctypes.data_as(capi.ip), ll.ctypes.data_as(capi.ip), U1 - 1, blank,
+                                      lf.ctypes.data_as(capi.ip), fl.ctypes.data_as(capi.ip), _p(lp), _p(fp), _p(sc)), "nntk_rnnt_align")
+    return lf, fl, lp, fp, sc
+
+
+def rnnt_fused_align_device(enc, pred, out_block, labels, label_lengths=None, input_lengths=None, blank=0, activation=ACT_TANH,
+                            label_frames=None, frame_labels=None, label_logp=None, frame_logp=None, scores=None, workspace=None):
+    """``nntk_rnnt_fused_align_device``: the alignment of ``rnnt_align_device`` from enc [B,T,J], pred [B,U1,J] and the Dense block
+    W [J,V] | b [V], as ``rnnt_fused_loss_device`` takes them; the [B,T,U1,V] logits are never stored."""
+    import torch
+    B, T, J = enc.shape
+    U1 = pred.shape[1]
+    assert tuple(pred.shape) == (B, U1, J), "pred: [B, U1, J] with enc's B and J"
+    assert out_block.numel() % (J + 1) == 0, "out_block: W [J, V] | b [V]"
+    V = out_block.numel() // (J + 1)
+    lab, ll = _rnnt_labels(labels, label_lengths, B, U1 - 1)
+    il, ilp = _ctc_lengths(input_lengths, B)
+    L = capi.load()
+    need = L.nntk_rnnt_fused_align_workspace_floats(B, T, U1 - 1, J, V)
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.float32, device=enc.device)
+    assert workspace.numel() >= need, "workspace: nntk_rnnt_fused_align_workspace_floats(B, T, max_label_len, J, V) floats"
+    outs = _align_outputs(enc.device, B, T, U1 - 1, (label_frames, frame_labels, label_logp, frame_logp, scores))
+    check(L.nntk_rnnt_fused_align_device(_dp(enc), _dp(pred), _dp(out_block), B, T, J, V, RNNT_ACTIVATIONS[activation], ilp,
+                                         lab.ctypes.data_as(capi.ip), ll.ctypes.data_as(capi.ip), U1 - 1, blank,
+                                         *[C.c_void_p(o.data_ptr()) for o in outs], _dp(workspace)), "nntk_rnnt_fused_align_device")
+    return tuple(outs)
+
+
+def rnnt_fused_align(enc, pred, out_block, labels, label_lengths=None, input_lengths=None, blank=0, activation=ACT_TANH):
+    """The host-memory form (``nntk_rnnt_fused_align``) on numpy arrays."""
+    enc, pred, out_block = _f32(enc), _f32(pred), _f32(out_block)
+    B, T, J = enc.shape
+    U1 = pred.shape[1]
+    V = out_block.size // (J + 1)
+    lab, ll = _rnnt_labels(labels, label_lengths, B, U1 - 1)
+    il, ilp = _ctc_lengths(input_lengths, B)
+    lf, fl = np.empty((B, U1 - 1), np.int32), np.empty((B, T), np.int32)
+    lp, fp, sc = np.empty((B, U1 - 1), np.float32), np.empty((B, T), np.float32), np.empty(B, np.float32)
+    check(capi.load().nntk_rnnt_fused_align(_p(enc), _p(pred), _p(out_block), B, T, J, V, RNNT_ACTIVATIONS[activation], ilp,
+                                            lab.ctypes.data_as(capi.ip), ll.ctypes.data_as(capi.ip), U1 - 1, blank,
+                                            lf.ctypes.data_as(capi.ip), fl.ctypes.data_as(capi.ip), _p(lp), _p(fp), _p(sc)),
+          "nntk_rnnt_fused_align")
+    return lf, fl, lp, fp, sc
+
+
 def _ipv(t):
     """device pointer of a contiguous int32 torch tensor"""
     import torch
