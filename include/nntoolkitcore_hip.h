@@ -1227,8 +1227,8 @@ int nntk_rnnt_greedy_decode(NntkRnntDecoder d, NntkRnntDecodeState state, const 
  * not 16-byte aligned; outputs overlapping one another, d_enc or the workspace; a model beyond the kernel's LDS.
  * Deterministic: no atomics, the same bits on every call; a row's bits do not depend on the other rows, its position in the batch,
  * the T padding, or how many hypotheses share a pass over a matrix.  One launch on the calling thread's stream.  The host-pointer
- * form uploads, runs the device form on a workspace of its own and downloads.  Not part of the call: label timestamps, length
- * normalisation.  Language-model fusion: below. */
+ * form uploads, runs the device form on a workspace of its own and downloads.  Language-model fusion, and label timestamps,
+ * confidences and length normalisation: below. */
 typedef struct NntkRnntBeamStateStruct *NntkRnntBeamState;
 size_t nntk_rnnt_beam_workspace_floats(NntkRnntDecoder d, int batch, int beam_width, int max_labels);
 int nntk_rnnt_beam_decode_device(NntkRnntDecoder d, NntkRnntBeamState state, const float *d_enc, int batch, int T, const int *n_frames,
@@ -1279,6 +1279,58 @@ int nntk_rnnt_beam_decode_lm(NntkRnntDecoder d, NntkRnntBeamState state, const f
                              int beam_width, int nbest, int max_labels, NntkNgramLm lm, int *labels_out, int *out_lengths, float *scores);
 NntkRnntBeamState nntk_rnnt_beam_state_create_lm(NntkRnntDecoder d, int batch, int beam_width, int max_labels, NntkNgramLm lm);
 size_t nntk_rnnt_beam_state_bytes_lm(NntkRnntDecoder d, int batch, int beam_width, int max_labels);
+/* ---- label timestamps, confidences and length normalisation (INTEGRATION.md "RNN-Transducer: beam search", Label timestamps,
+ *      confidences and length normalisation) ----
+ * nntk_rnnt_beam_decode_opt_device: the beam search above with an options struct; o == NULL or a struct with everything off (lm NULL,
+ * length_norm 0, both pointers NULL) is nntk_rnnt_beam_decode_device bit for bit, lm alone nntk_rnnt_beam_decode_lm_device.  "Detail"
+ * is on when label_frames or label_logps is not NULL.  Every hypothesis then carries two arrays of length |y| next to its labels:
+ * frames[j], the frame in which label j was emitted, counted from the start of the row's stream, and lps[j], the acoustic
+ * log-probability of that emission.  In the pseudo-code above:
+ *   label cell (i, v) at frame t: the new hypothesis takes C[i].frames + [t0 + t] and C[i].lps + [(float)((double)(logits[v] - max) -
+ *     lse)]: t0 is the number of frames the row's stream consumed before this call (0 without a state or after a reset), the value is
+ *     the double the selection already forms, rounded once to f32.  With a language model lnF is NOT part of it: lps is the acoustic
+ *     confidence.
+ *   entries of B also hold lead, a double, and the arrays they report.  Insert: lead = cand.score, the candidate's arrays.  Merge: the
+ *     score is the logaddexp as before and the entry keeps its insertion index and state as before; if cand.score > lead (a double
+ *     compare) then lead = cand.score and the entry takes the candidate's arrays; on an exact tie it keeps what it has.  A merged
+ *     hypothesis so reports the alignment of its dominant contributor (not the Viterbi alignment: nntk_rnnt_align_device gives that).
+ *     Which arrays are kept never influences a score, a cut or a state.
+ *   frame end: A's entries take the arrays of their B entry.
+ *   report: length_norm == 0: the order above.  length_norm == 1: the entries to be reported (with a model: after + ln E, the -inf
+ *     entries dropped) are ranked by key = score / (double)(length + 1), the + 1 counting the initial blank, descending, exact ties to
+ *     the lower rank in A, and the first nbest are written.  d_scores holds the plain score whatever the order, so with a model score -
+ *     nntk_ngram_lm_score(...) stays the acoustic mass.  Normalisation touches only the report, never a cut and never the carried beam:
+ *     any split of a stream into pushes gives the one-shot bits after every push, for all five outputs.
+ * label_frames [batch][nbest][max_labels] int: hypothesis k's frames, then -1; label_logps, the same shape, float: the values, then
+ * 0.0f.  A slot without a hypothesis holds -1 / 0.0f throughout; every element of an output that is asked for is written.  Either may
+ * be NULL; in the _device form both are device pointers, in the host form host pointers.
+ * d_workspace: nntk_rnnt_beam_opt_workspace_floats(d, batch, beam_width, max_labels, o) floats: what the call without the struct needs,
+ * and with detail or length_norm per row 8 max_labels bytes per hypothesis slot and 12 bytes per entry of B behind it.
+ * nntk_rnnt_beam_state_create_opt(.., lm, with_detail): a stream state; with_detail 0 it is nntk_rnnt_beam_state_create(_lm)'s.  With
+ * detail it holds per row and beam entry max_labels ints and max_labels floats more (nntk_rnnt_beam_state_bytes_opt; whatever the
+ * stream's length) and the row's count of consumed frames, which a reset of the row puts back to 0.
+ * Refused on the host before anything is enqueued (-1 / NULL, nntk_last_error(), nothing written): everything the calls above refuse;
+ * length_norm outside {0, 1}; a detail output that is not 4-byte aligned or overlaps another output, d_enc or the workspace; a state
+ * created without detail in a call with detail and the reverse -- so a state created with detail is refused by
+ * nntk_rnnt_beam_decode_device and nntk_rnnt_beam_decode_lm_device.
+ * The guarantees above hold for the five outputs: no atomics, one launch, the same bits on every call, a row independent of the other
+ * rows, its batch position, the T padding (NaN there included) and how many hypotheses share a pass over a matrix. */
+typedef struct {
+    NntkNgramLm lm;          /* NULL: the acoustic search */
+    int length_norm;         /* 0 | 1 */
+    int *label_frames;       /* [batch][nbest][max_labels] or NULL; a device pointer in the _device form */
+    float *label_logps;      /* the same shape, or NULL */
+} NntkRnntBeamOptions;
+size_t nntk_rnnt_beam_opt_workspace_floats(NntkRnntDecoder d, int batch, int beam_width, int max_labels, const NntkRnntBeamOptions *o);
+int nntk_rnnt_beam_decode_opt_device(NntkRnntDecoder d, NntkRnntBeamState state, const float *d_enc, int batch, int T, const int *n_frames,
+                                     int beam_width, int nbest, int max_labels, const NntkRnntBeamOptions *o, int *d_labels_out,
+                                     int *d_out_lengths, float *d_scores, float *d_workspace);
+int nntk_rnnt_beam_decode_opt(NntkRnntDecoder d, NntkRnntBeamState state, const float *enc, int batch, int T, const int *n_frames,
+                              int beam_width, int nbest, int max_labels, const NntkRnntBeamOptions *o, int *labels_out, int *out_lengths,
+                              float *scores);
+NntkRnntBeamState nntk_rnnt_beam_state_create_opt(NntkRnntDecoder d, int batch, int beam_width, int max_labels, NntkNgramLm lm,
+                                                  int with_detail);
+size_t nntk_rnnt_beam_state_bytes_opt(NntkRnntDecoder d, int batch, int beam_width, int max_labels, int with_lm, int with_detail);
 
 #ifdef __cplusplus
 }

@@ -66,6 +66,10 @@ class NntkRnntDecoderConfig(C.Structure):
                 ("max_symbols_per_frame", C.c_int)]
 
 
+class NntkRnntBeamOptions(C.Structure):
+    _fields_ = [("lm", vp), ("length_norm", C.c_int), ("label_frames", vp), ("label_logps", vp)]
+
+
 class DefaultWeights(C.Structure):
     _fields_ = [("W", fp), ("b", fp)]
 
@@ -503,6 +507,14 @@ SIGNATURES = {
     "nntk_rnnt_beam_decode_lm": (C.c_int, [vp, vp, fp, C.c_int, C.c_int, ip, C.c_int, C.c_int, C.c_int, vp, ip, ip, fp]),
     "nntk_rnnt_beam_state_create_lm": (vp, [vp, C.c_int, C.c_int, C.c_int, vp]),
     "nntk_rnnt_beam_state_bytes_lm": (C.c_size_t, [vp, C.c_int, C.c_int, C.c_int]),
+    # ... with label timestamps, confidences and length normalisation (the options struct; NULL: the calls above)
+    "nntk_rnnt_beam_opt_workspace_floats": (C.c_size_t, [vp, C.c_int, C.c_int, C.c_int, C.POINTER(NntkRnntBeamOptions)]),
+    "nntk_rnnt_beam_decode_opt_device": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, ip, C.c_int, C.c_int, C.c_int,
+                                                   C.POINTER(NntkRnntBeamOptions), vp, vp, vp, vp]),
+    "nntk_rnnt_beam_decode_opt": (C.c_int, [vp, vp, fp, C.c_int, C.c_int, ip, C.c_int, C.c_int, C.c_int, C.POINTER(NntkRnntBeamOptions),
+                                            ip, ip, fp]),
+    "nntk_rnnt_beam_state_create_opt": (vp, [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int]),
+    "nntk_rnnt_beam_state_bytes_opt": (C.c_size_t, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     # weights from device memory into a handle; the multi-tensor optimizer (INTEGRATION.md "Optimizers")
     "Conv1dLoadWeightsDevice": (C.c_int, [vp, vp]),
     "BatchNormLoadWeightsDevice": (C.c_int, [vp, vp]),

@@ -262,7 +262,7 @@ int nntk_shim_rnnt_greedy(const nntk_shim_rnnt_dec *m, const float *d_enc, int b
  *      S' = min(max_symbols_per_frame, max_labels). ---- */
 #define NNTK_RNNT_BEAM_MAX_W 32
 /* a stream's rows: score [batch][W] doubles, f [batch][W][2H + J], lab [batch][W][max_labels], meta [batch][W][2] (length | hash),
- * i [batch][4] (started | hypotheses | - | -); all NULL: every row from the start, nothing kept */
+ * i [batch][4] (started | hypotheses | frames consumed, with detail | -); all NULL: every row from the start, nothing kept */
 typedef struct {
     double *score;
     float *f;
@@ -290,6 +290,24 @@ size_t nntk_shim_rnnt_beam_lm_workspace_floats(int batch, int H, int J, int V, i
 int nntk_shim_rnnt_beam_lm(const nntk_shim_rnnt_dec *m, const float *d_enc, int batch, int T, const int *h_n_frames, int beam_width, int nbest,
                            int max_labels, const nntk_shim_rnnt_beam_state *st, const nntk_shim_rnnt_lm *lm, int *d_st_q, int *d_labels,
                            int *d_lengths, float *d_scores, float *d_ws);
+/* Label timestamps, confidences and length normalisation (include/nntoolkitcore_hip.h, "Label timestamps" under the beam search).  dt
+ * NULL: nntk_shim_rnnt_beam_lm, the same kernels.  With dt the workspace is nntk_shim_rnnt_beam_opt_workspace_floats(.., with_detail = 1)
+ * words -- the acoustic and LM layouts, then per row two words per hypothesis slot and label and three per entry of B.  d_frames,
+ * d_logps [batch][nbest][max_labels], each may be NULL.  d_st_fr, d_st_lp [batch][W][max_labels]: the arrays of a stream's rows, both
+ * or neither (neither: the arrays are not carried); the frames a row has consumed ride in word 2 of the state's i, read only while
+ * the row's started word is set, so a reset row counts from 0 again. */
+typedef struct {
+    int *d_frames;
+    float *d_logps;
+    int *d_st_fr;
+    float *d_st_lp;
+    int length_norm;
+} nntk_shim_rnnt_beam_detail;
+size_t nntk_shim_rnnt_beam_opt_workspace_floats(int batch, int H, int J, int V, int max_sym, int beam_width, int max_labels, int with_lm,
+                                                int with_detail);
+int nntk_shim_rnnt_beam_opt(const nntk_shim_rnnt_dec *m, const float *d_enc, int batch, int T, const int *h_n_frames, int beam_width, int nbest,
+                            int max_labels, const nntk_shim_rnnt_beam_state *st, const nntk_shim_rnnt_lm *lm, int *d_st_q,
+                            const nntk_shim_rnnt_beam_detail *dt, int *d_labels, int *d_lengths, float *d_scores, float *d_ws);
 /* BatchNorm training (batch_norm.c:191-386): x, d_out [N, F]; d_block = gamma | beta | ...; d_stats [8][F] = mean | variance |
  * var_eps | sqrt_var | d_beta | d_gamma | d_var | d_mu; d_partial [slices][3][F] with slices from nntk_shim_bn_train_slices */
 /* Ragged batches and carried state for the recurrent training launchers below (the *VarLen training calls; a NULL pointer to it = the

@@ -33,6 +33,15 @@
 // hypothesis that cannot be extended) is no candidate.  next(q_i, v) is looked up for the W selected cells only, by binary search
 // along the chain.  The tables are global memory; no LDS is added.  At the end the entries of A take + ln E(q), the -inf ones are
 // dropped and the rest are ranked (at most 32: every entry counts the entries ahead of it); the carried A stays as it was.
+//
+// Label timestamps, confidences and length normalisation (the DETAIL = true instantiations; include/nntoolkitcore_hip.h, "Label
+// timestamps" under the beam search).  Behind the LM part of the row's block, so that nothing else moves: per slot frames [max_labels]
+// ints and lps [max_labels] floats, copied wherever labs is copied with the same loops, and per entry of B lead (a double: the largest
+// single contribution so far) and bfslot (the slot whose arrays the entry reports).  The lane that merges a candidate into B compares
+// it with lead and, if it is larger, points bfslot at the candidate's slot; every slot a bfslot can name (the current A buffer, the
+// depth levels) lives until the end of the frame, so nothing is moved at merge time.  At the end of a frame A's entries take the
+// state and labels of bslot[e] as before and the arrays of bfslot[e].  The report ranks the entries by score or, with length_norm,
+// by score / (length + 1), with the LM report's counting rank on sh.cand / sh.n_score / sh.found: no LDS is added.
 #include <limits.h>
 #include "rnnt_dec_common.hpp"
 
@@ -44,7 +53,11 @@ struct RbLayout {                          // offsets in floats from the row's b
     int nslots, nbmax, SF;
 };
 
-static RbLayout rb_layout(int H, int J, int V, int max_sym, int W, int max_labels, bool lm = false) {
+struct RbDetailLayout {                    // with detail only, behind both: [(S' + 2) W][max_labels] ints | the same, floats | [W (S' + 1)] doubles | ints
+    size_t fr, lp, lead, bfslot;
+};
+
+static RbLayout rb_layout(int H, int J, int V, int max_sym, int W, int max_labels, bool lm = false, RbDetailLayout *detail = nullptr) {
     RbLayout l;
     const int depths = max_sym < max_labels ? max_sym : max_labels;
     l.nslots = (depths + 2) * W; l.nbmax = (depths + 1) * W; l.SF = 2 * H + J;
@@ -60,6 +73,12 @@ static RbLayout rb_layout(int H, int J, int V, int max_sym, int W, int max_label
     if (lm) {
         l.lmq = take((size_t)l.nslots);
         l.lmterm = take(2 * (size_t)W * V);
+    }
+    if (detail) {
+        detail->fr = take((size_t)l.nslots * max_labels);
+        detail->lp = take((size_t)l.nslots * max_labels);
+        detail->lead = take(2 * (size_t)l.nbmax);
+        detail->bfslot = take((size_t)l.nbmax);
     }
     l.row = at;
     return l;
@@ -77,6 +96,8 @@ struct RnntBeamArgs {
     int batch, T, V, blank, H, J, act, max_sym, W, nbest, max_labels;
     nntk_shim_rnnt_lm lm;                  // the LM instantiations only
     int *st_q;                             // [batch][W]: the LM states of a stream's rows (with st)
+    nntk_shim_rnnt_beam_detail dt;         // the DETAIL instantiations only, as is
+    RbDetailLayout dlay;                   // their part of the row's block (lay.row counts it)
 };
 
 template <int R> struct RbShared {
@@ -118,7 +139,7 @@ __device__ static int rb_lm_next(const nntk_shim_rnnt_lm &lm, int s, int v) {
     }
 }
 
-template <int R, bool LM>
+template <int R, bool LM, bool DETAIL>
 __global__ __launch_bounds__(RD_THREADS) void rnnt_beam_kernel(const RnntBeamArgs a) {
     extern __shared__ __align__(16) unsigned char rb_smem[];
     RbShared<R> &sh = *(RbShared<R> *)rb_smem;
@@ -136,8 +157,13 @@ __global__ __launch_bounds__(RD_THREADS) void rnnt_beam_kernel(const RnntBeamArg
     int *labs = (int *)(row + a.lay.labels), *meta = (int *)(row + a.lay.meta), *bslot = (int *)(row + a.lay.bslot);
     int *lmq = (int *)(row + a.lay.lmq);                                     // LM only, as is lmterm
     double *lmterm = (double *)(row + a.lay.lmterm);
+    int *fr = (int *)(row + a.dlay.fr), *bfslot = (int *)(row + a.dlay.bfslot);   // DETAIL only, as are lp and lead
+    float *lp = row + a.dlay.lp;
+    double *lead = (double *)(row + a.dlay.lead);
     const int n = ((const int *)a.ws)[b];
     const bool started = a.st.i && a.st.i[4 * b] != 0;
+    int t0 = 0;                                                              // DETAIL: the frames the row's stream has consumed
+    if constexpr (DETAIL) { if (started) t0 = a.st.i[4 * b + 2]; }
 
     // the workgroup's best (score descending, index ascending; INT_MAX: none) -> sh.best_s, sh.best_i
     auto block_best = [&](double s, int idx) {
@@ -279,6 +305,13 @@ __global__ __launch_bounds__(RD_THREADS) void rnnt_beam_kernel(const RnntBeamArg
         for (int k = 0; k < nA; ++k) {
             const int len = a.st.meta[2 * (at + k)];
             for (int j = tid; j < len; j += RD_THREADS) labs[(size_t)k * ML + j] = a.st.lab[(at + k) * ML + j];
+            if constexpr (DETAIL) {
+                if (a.dt.d_st_fr)
+                    for (int j = tid; j < len; j += RD_THREADS) {
+                        fr[(size_t)k * ML + j] = a.dt.d_st_fr[(at + k) * ML + j];
+                        lp[(size_t)k * ML + j] = a.dt.d_st_lp[(at + k) * ML + j];
+                    }
+            }
         }
         if (tid < nA) {
             meta[2 * tid] = a.st.meta[2 * (at + tid)]; meta[2 * tid + 1] = a.st.meta[2 * (at + tid) + 1];
@@ -337,6 +370,10 @@ __global__ __launch_bounds__(RD_THREADS) void rnnt_beam_kernel(const RnntBeamArg
                     const double cs = sh.cand[i];
                     if (!(cs > -INFINITY)) continue;
                     const int f = sh.found[i];
+                    if constexpr (DETAIL) {                                  // the dominant contributor's arrays; a tie keeps what is there
+                        if (f >= 0) { if (cs > lead[f]) { lead[f] = cs; bfslot[f] = sh.c_slot[i]; } }
+                        else if (nb < a.lay.nbmax) { lead[nb] = cs; bfslot[nb] = sh.c_slot[i]; }
+                    }
                     if (f >= 0) bscore[f] = rb_logaddexp(bscore[f], cs);
                     else if (nb < a.lay.nbmax) { bslot[nb] = sh.c_slot[i]; bscore[nb] = cs; ++nb; }
                 }
@@ -416,7 +453,14 @@ __global__ __launch_bounds__(RD_THREADS) void rnnt_beam_kernel(const RnntBeamArg
             const int dst0 = (2 + depth) * W;
             int ss = 0, ol = 0;
             unsigned oh = 0;
+            float nlp = 0.0f;                                                // DETAIL: the cell's acoustic log-probability
             if (tid < nSel) { const int i = sh.n_src[tid]; ss = sh.c_slot[i]; ol = sh.c_len[i]; oh = sh.c_hash[i]; }
+            if constexpr (DETAIL) {
+                if (tid < nSel) {
+                    const int i = sh.n_src[tid];
+                    nlp = (float)((double)(lg[(size_t)i * V + sh.n_lab[tid]] - sh.c_max[i]) - sh.c_lse[i]);
+                }
+            }
             __syncthreads();
             if (tid < nSel) {
                 const unsigned nh = oh * 1000003u + (unsigned)(sh.n_lab[tid] + 1);
@@ -432,6 +476,13 @@ __global__ __launch_bounds__(RD_THREADS) void rnnt_beam_kernel(const RnntBeamArg
                 int *q = labs + (size_t)sh.c_slot[k] * ML;
                 for (int j = tid; j < L; j += RD_THREADS) q[j] = p[j];
                 if (tid == 0) q[L] = sh.n_lab[k];
+                if constexpr (DETAIL) {
+                    const size_t from = (size_t)sh.n_src[k] * ML, to = (size_t)sh.c_slot[k] * ML;
+                    for (int j = tid; j < L; j += RD_THREADS) { fr[to + j] = fr[from + j]; lp[to + j] = lp[from + j]; }
+                }
+            }
+            if constexpr (DETAIL) {
+                if (tid < nSel) { fr[(size_t)(dst0 + tid) * ML + ol] = t0 + t; lp[(size_t)(dst0 + tid) * ML + ol] = nlp; }
             }
             for (int k0 = 0; k0 < nSel; k0 += R) step_group(k0, nSel - k0 < R ? nSel - k0 : R, dst0);
         }
@@ -450,6 +501,7 @@ __global__ __launch_bounds__(RD_THREADS) void rnnt_beam_kernel(const RnntBeamArg
             if (sh.best_i == INT_MAX) break;
             prev_s = sh.best_s; prev_i = sh.best_i;
             if (tid == 0) { sh.n_src[k] = bslot[prev_i]; sh.a_score[k] = prev_s; }
+            if constexpr (DETAIL) { if (tid == 0) sh.n_lab[k] = bfslot[prev_i]; }
             ++nNew;
         }
         __syncthreads();
@@ -460,13 +512,56 @@ __global__ __launch_bounds__(RD_THREADS) void rnnt_beam_kernel(const RnntBeamArg
             for (int j = tid; j < len; j += RD_THREADS) labs[(size_t)dst * ML + j] = labs[(size_t)src * ML + j];
             if (tid == 0) { meta[2 * dst] = len; meta[2 * dst + 1] = meta[2 * src + 1]; }
             if constexpr (LM) { if (tid == 0) lmq[dst] = lmq[src]; }
+            if constexpr (DETAIL) {
+                const size_t from = (size_t)sh.n_lab[k] * ML;
+                for (int j = tid; j < len; j += RD_THREADS) { fr[(size_t)dst * ML + j] = fr[from + j]; lp[(size_t)dst * ML + j] = lp[from + j]; }
+            }
         }
         if (tid == 0) sh.nA = nNew;
         __syncthreads();
     }
 
     const int nA = sh.nA;
-    if constexpr (LM) {
+    if constexpr (DETAIL) {
+        // the report: the score (with a model: + ln E(q), the -inf entries dropped) in sh.cand, the key it is ranked by in sh.n_score
+        __syncthreads();
+        if (tid < nA) {
+            double s = sh.a_score[tid];
+            if constexpr (LM) s += a.lm.d_state_ln[2 * lmq[cur * W + tid] + 1];
+            sh.cand[tid] = s;
+            sh.n_score[tid] = a.dt.length_norm ? s / (double)(meta[2 * (cur * W + tid)] + 1) : s;
+        }
+        __syncthreads();
+        if (tid < nA) {
+            const double s = sh.n_score[tid];
+            int ahead = 0;
+            for (int j = 0; j < nA; ++j) {
+                const double o = sh.n_score[j];
+                ahead += o > -INFINITY && (o > s || (o == s && j < tid));
+            }
+            if (s > -INFINITY) sh.found[ahead] = tid;
+        }
+        if (tid == 0) {
+            int kept = 0;
+            for (int j = 0; j < nA; ++j) kept += sh.n_score[j] > -INFINITY;
+            sh.nSel = kept;
+        }
+        __syncthreads();
+        const int kept = sh.nSel;
+        for (int k = 0; k < a.nbest; ++k) {
+            const size_t o = (size_t)b * a.nbest + k;
+            const int src = k < kept ? sh.found[k] : 0, slot = cur * W + src, len = k < kept ? meta[2 * slot] : 0;
+            for (int j = tid; j < ML; j += RD_THREADS) {
+                a.labels[o * ML + j] = j < len ? labs[(size_t)slot * ML + j] : -1;
+                if (a.dt.d_frames) a.dt.d_frames[o * ML + j] = j < len ? fr[(size_t)slot * ML + j] : -1;
+                if (a.dt.d_logps) a.dt.d_logps[o * ML + j] = j < len ? lp[(size_t)slot * ML + j] : 0.0f;
+            }
+            if (tid == 0) {
+                a.lengths[o] = k < kept ? len : -1;
+                a.scores[o] = k < kept ? (float)sh.cand[src] : -INFINITY;
+            }
+        }
+    } else if constexpr (LM) {
         // the report: + ln E(q), the -inf entries dropped, the rest ranked descending, ties to the lower rank in A; A itself stays
         __syncthreads();
         if (tid < nA) sh.cand[tid] = sh.a_score[tid] + a.lm.d_state_ln[2 * lmq[cur * W + tid] + 1];
@@ -513,6 +608,13 @@ __global__ __launch_bounds__(RD_THREADS) void rnnt_beam_kernel(const RnntBeamArg
         for (int k = 0; k < nA; ++k) {
             const int slot = cur * W + k, len = meta[2 * slot];
             for (int j = tid; j < len; j += RD_THREADS) a.st.lab[(at + k) * ML + j] = labs[(size_t)slot * ML + j];
+            if constexpr (DETAIL) {
+                if (a.dt.d_st_fr)
+                    for (int j = tid; j < len; j += RD_THREADS) {
+                        a.dt.d_st_fr[(at + k) * ML + j] = fr[(size_t)slot * ML + j];
+                        a.dt.d_st_lp[(at + k) * ML + j] = lp[(size_t)slot * ML + j];
+                    }
+            }
         }
         if (tid < nA) {
             const int slot = cur * W + tid;
@@ -521,13 +623,14 @@ __global__ __launch_bounds__(RD_THREADS) void rnnt_beam_kernel(const RnntBeamArg
             if constexpr (LM) a.st_q[at + tid] = lmq[slot];
         }
         if (tid == 0) { a.st.i[4 * b] = 1; a.st.i[4 * b + 1] = nA; }
+        if constexpr (DETAIL) { if (tid == 0) a.st.i[4 * b + 2] = t0 + n; }
     }
 }
 
-template <int R, bool LM>
+template <int R, bool LM, bool DETAIL>
 static int rb_launch(const RnntBeamArgs &a, size_t lds) {
-    if (lds > 48 * 1024 && nntk_set_max_dynamic_lds((const void *)rnnt_beam_kernel<R, LM>, lds)) return -1;
-    hipLaunchKernelGGL((rnnt_beam_kernel<R, LM>), dim3((unsigned)a.batch), dim3(RD_THREADS), lds, nntk_stream(), a);
+    if (lds > 48 * 1024 && nntk_set_max_dynamic_lds((const void *)rnnt_beam_kernel<R, LM, DETAIL>, lds)) return -1;
+    hipLaunchKernelGGL((rnnt_beam_kernel<R, LM, DETAIL>), dim3((unsigned)a.batch), dim3(RD_THREADS), lds, nntk_stream(), a);
     return 0;
 }
 
@@ -557,13 +660,28 @@ size_t nntk_shim_rnnt_beam_lm_workspace_floats(int batch, int H, int J, int V, i
 
 int nntk_shim_rnnt_beam(const nntk_shim_rnnt_dec *m, const float *d_enc, int batch, int T, const int *h_n_frames, int beam_width, int nbest,
                         int max_labels, const nntk_shim_rnnt_beam_state *st, int *d_labels, int *d_lengths, float *d_scores, float *d_ws) {
-    return nntk_shim_rnnt_beam_lm(m, d_enc, batch, T, h_n_frames, beam_width, nbest, max_labels, st, nullptr, nullptr, d_labels, d_lengths,
-                                  d_scores, d_ws);
+    return nntk_shim_rnnt_beam_opt(m, d_enc, batch, T, h_n_frames, beam_width, nbest, max_labels, st, nullptr, nullptr, nullptr, d_labels,
+                                   d_lengths, d_scores, d_ws);
+}
+
+size_t nntk_shim_rnnt_beam_opt_workspace_floats(int batch, int H, int J, int V, int max_sym, int beam_width, int max_labels, int with_lm,
+                                                int with_detail) {
+    if (batch <= 0) return 0;
+    RbDetailLayout dl;
+    return (((size_t)batch + 3) & ~(size_t)3) +
+           (size_t)batch * rb_layout(H, J, V, max_sym, beam_width, max_labels, with_lm != 0, with_detail ? &dl : nullptr).row;
 }
 
 int nntk_shim_rnnt_beam_lm(const nntk_shim_rnnt_dec *m, const float *d_enc, int batch, int T, const int *h_n_frames, int beam_width, int nbest,
                            int max_labels, const nntk_shim_rnnt_beam_state *st, const nntk_shim_rnnt_lm *lm, int *d_st_q, int *d_labels,
                            int *d_lengths, float *d_scores, float *d_ws) {
+    return nntk_shim_rnnt_beam_opt(m, d_enc, batch, T, h_n_frames, beam_width, nbest, max_labels, st, lm, d_st_q, nullptr, d_labels, d_lengths,
+                                   d_scores, d_ws);
+}
+
+int nntk_shim_rnnt_beam_opt(const nntk_shim_rnnt_dec *m, const float *d_enc, int batch, int T, const int *h_n_frames, int beam_width, int nbest,
+                            int max_labels, const nntk_shim_rnnt_beam_state *st, const nntk_shim_rnnt_lm *lm, int *d_st_q,
+                            const nntk_shim_rnnt_beam_detail *dt, int *d_labels, int *d_lengths, float *d_scores, float *d_ws) {
     if (batch <= 0) return 0;
     const int depths = m->max_symbols_per_frame < max_labels ? m->max_symbols_per_frame : max_labels;
     if (m->E < 1 || m->H < 1 || m->J < 1 || m->V < 2 || m->H > NNTK_RNNT_DEC_MAX_WIDTH || m->J > NNTK_RNNT_DEC_MAX_WIDTH ||
@@ -577,16 +695,22 @@ int nntk_shim_rnnt_beam_lm(const nntk_shim_rnnt_dec *m, const float *d_enc, int 
     if (st) a.st = *st;
     else { a.st.score = nullptr; a.st.f = nullptr; a.st.lab = nullptr; a.st.meta = nullptr; a.st.i = nullptr; }
     a.labels = d_labels; a.lengths = d_lengths; a.scores = d_scores;
-    a.lay = rb_layout(m->H, m->J, m->V, m->max_symbols_per_frame, beam_width, max_labels, lm != nullptr);
+    a.dlay = RbDetailLayout();
+    a.lay = rb_layout(m->H, m->J, m->V, m->max_symbols_per_frame, beam_width, max_labels, lm != nullptr, dt ? &a.dlay : nullptr);
     a.ws_head = ((size_t)batch + 3) & ~(size_t)3;
     a.batch = batch; a.T = T; a.V = m->V; a.blank = m->blank; a.H = m->H; a.J = m->J; a.act = m->activation;
     a.max_sym = m->max_symbols_per_frame; a.W = beam_width; a.nbest = nbest; a.max_labels = max_labels;
     a.lm = lm ? *lm : nntk_shim_rnnt_lm();
     a.st_q = st ? d_st_q : nullptr;
+    a.dt = dt ? *dt : nntk_shim_rnnt_beam_detail();
+    if (!st) a.dt.d_st_fr = nullptr, a.dt.d_st_lp = nullptr;
     const int R = nntk_shim_rnnt_beam_group(beam_width, m->H, m->J, m->V);
     const size_t lds = rb_lds_bytes(R, m->H, m->J, m->V);
-    if (R == 1 ? (lm ? rb_launch<1, true>(a, lds) : rb_launch<1, false>(a, lds))
-               : (lm ? rb_launch<NNTK_RNNT_DEC_GROUP, true>(a, lds) : rb_launch<NNTK_RNNT_DEC_GROUP, false>(a, lds))) return -1;
+    constexpr int RG = NNTK_RNNT_DEC_GROUP;
+    if (dt ? (R == 1 ? (lm ? rb_launch<1, true, true>(a, lds) : rb_launch<1, false, true>(a, lds))
+                     : (lm ? rb_launch<RG, true, true>(a, lds) : rb_launch<RG, false, true>(a, lds)))
+           : (R == 1 ? (lm ? rb_launch<1, true, false>(a, lds) : rb_launch<1, false, false>(a, lds))
+                     : (lm ? rb_launch<RG, true, false>(a, lds) : rb_launch<RG, false, false>(a, lds)))) return -1;
     NNTK_LAUNCH_CHECK("rnnt_beam_kernel");
     return 0;
 }

@@ -245,6 +245,9 @@ struct NntkRnntBeamStateStruct {
     nntk_shim_rnnt_beam_state d;                /* d.i: [batch][4], then [batch]: the rows of a reset */
     NntkNgramLm lm;                             /* the model the stream was created with (NULL: none), and */
     int *d_q;                                   /* [batch][width]: each hypothesis's state in it */
+    int detail;                                 /* created with detail: the label frames and log-probabilities are carried, in */
+    int *d_fr;                                  /* [batch][width][max_labels] and */
+    float *d_lp;                                /* the same shape; the frames a row has consumed ride in d.i */
 };
 
 static int beam_check_sizes(const char *who, NntkRnntDecoder d, int beam_width, int max_labels) {
@@ -276,20 +279,38 @@ size_t nntk_rnnt_beam_state_bytes_lm(NntkRnntDecoder d, int batch, int beam_widt
     return acoustic ? acoustic + (size_t)batch * beam_width * sizeof(int) : 0;
 }
 
+static int beam_opt_detail(const NntkRnntBeamOptions *o) { return o && (o->label_frames || o->label_logps); }
+
+/* the kernels with detail also rank the report, so length normalisation alone takes them and their workspace */
+static int beam_opt_kernel(const NntkRnntBeamOptions *o) { return beam_opt_detail(o) || (o && o->length_norm); }
+
+size_t nntk_rnnt_beam_opt_workspace_floats(NntkRnntDecoder d, int batch, int beam_width, int max_labels, const NntkRnntBeamOptions *o) {
+    if (!d || batch <= 0 || beam_width < 1 || beam_width > NNTK_RNNT_BEAM_MAX_W || max_labels < 1) return 0;
+    return nntk_shim_rnnt_beam_opt_workspace_floats(batch, d->cfg.H, d->cfg.J, d->cfg.V, d->cfg.max_symbols_per_frame, beam_width, max_labels,
+                                                    o && o->lm, beam_opt_kernel(o));
+}
+
+size_t nntk_rnnt_beam_state_bytes_opt(NntkRnntDecoder d, int batch, int beam_width, int max_labels, int with_lm, int with_detail) {
+    const size_t base = with_lm ? nntk_rnnt_beam_state_bytes_lm(d, batch, beam_width, max_labels)
+                                : nntk_rnnt_beam_state_bytes(d, batch, beam_width, max_labels);
+    return base && with_detail ? base + (size_t)batch * beam_width * max_labels * (sizeof(int) + sizeof(float)) : base;
+}
+
 static int beam_check_lm(const char *who, NntkRnntDecoder d, NntkNgramLm lm) {
     if (lm && !nntk_ngram_lm_matches(lm, d->cfg.V, d->cfg.blank))
         return dec_fail(who, "the language model was built for another class count or blank than V %ld, blank %ld", d->cfg.V, d->cfg.blank, 0);
     return 0;
 }
 
-static NntkRnntBeamState beam_state_create(const char *who, NntkRnntDecoder d, int batch, int beam_width, int max_labels, NntkNgramLm lm) {
+static NntkRnntBeamState beam_state_create(const char *who, NntkRnntDecoder d, int batch, int beam_width, int max_labels, NntkNgramLm lm,
+                                           int detail) {
     nntk_shim_clear_error();
     if (beam_check_sizes(who, d, beam_width, max_labels)) return NULL;
     if (batch < 1) { dec_fail(who, "batch %ld < 1", batch, 0, 0); return NULL; }
     if (beam_check_lm(who, d, lm)) return NULL;
     NntkRnntBeamState s = (NntkRnntBeamState)calloc(1, sizeof *s);
     if (!s) { nntk_set_error("nntk_rnnt_beam_state_create: out of host memory"); return NULL; }
-    s->dec = d; s->batch = batch; s->width = beam_width; s->max_labels = max_labels; s->lm = lm;
+    s->dec = d; s->batch = batch; s->width = beam_width; s->max_labels = max_labels; s->lm = lm; s->detail = detail != 0;
     const size_t hyps = (size_t)batch * beam_width;
     s->d.score = (double *)nntk_shim_malloc(hyps * sizeof(double));
     s->d.f = s->d.score ? (float *)nntk_shim_malloc(hyps * (2 * (size_t)d->cfg.H + d->cfg.J) * sizeof(float)) : NULL;
@@ -297,7 +318,9 @@ static NntkRnntBeamState beam_state_create(const char *who, NntkRnntDecoder d, i
     s->d.meta = s->d.lab ? (int *)nntk_shim_malloc(hyps * 2 * sizeof(int)) : NULL;
     s->d.i = s->d.meta ? (int *)nntk_shim_malloc((size_t)batch * 5 * sizeof(int)) : NULL;
     s->d_q = s->d.i && lm ? (int *)nntk_shim_malloc(hyps * sizeof(int)) : NULL;
-    if (!s->d.i || (lm && !s->d_q) || nntk_shim_memset(s->d.i, 0, (size_t)batch * 5 * sizeof(int))) {
+    s->d_fr = s->d.i && detail ? (int *)nntk_shim_malloc(hyps * max_labels * sizeof(int)) : NULL;
+    s->d_lp = s->d_fr ? (float *)nntk_shim_malloc(hyps * max_labels * sizeof(float)) : NULL;
+    if (!s->d.i || (lm && !s->d_q) || (detail && !s->d_lp) || nntk_shim_memset(s->d.i, 0, (size_t)batch * 5 * sizeof(int))) {
         nntk_rnnt_beam_state_destroy(s);
         return NULL;
     }
@@ -305,11 +328,15 @@ static NntkRnntBeamState beam_state_create(const char *who, NntkRnntDecoder d, i
 }
 
 NntkRnntBeamState nntk_rnnt_beam_state_create(NntkRnntDecoder d, int batch, int beam_width, int max_labels) {
-    return beam_state_create("nntk_rnnt_beam_state_create", d, batch, beam_width, max_labels, NULL);
+    return beam_state_create("nntk_rnnt_beam_state_create", d, batch, beam_width, max_labels, NULL, 0);
 }
 
 NntkRnntBeamState nntk_rnnt_beam_state_create_lm(NntkRnntDecoder d, int batch, int beam_width, int max_labels, NntkNgramLm lm) {
-    return beam_state_create("nntk_rnnt_beam_state_create_lm", d, batch, beam_width, max_labels, lm);
+    return beam_state_create("nntk_rnnt_beam_state_create_lm", d, batch, beam_width, max_labels, lm, 0);
+}
+
+NntkRnntBeamState nntk_rnnt_beam_state_create_opt(NntkRnntDecoder d, int batch, int beam_width, int max_labels, NntkNgramLm lm, int with_detail) {
+    return beam_state_create("nntk_rnnt_beam_state_create_opt", d, batch, beam_width, max_labels, lm, with_detail);
 }
 
 int nntk_rnnt_beam_state_reset(NntkRnntBeamState s, const int *rows, int n_rows) {
@@ -336,14 +363,23 @@ void nntk_rnnt_beam_state_destroy(NntkRnntBeamState s) {
     nntk_shim_free(s->d.meta);
     nntk_shim_free(s->d.i);
     nntk_shim_free(s->d_q);
+    nntk_shim_free(s->d_fr);
+    nntk_shim_free(s->d_lp);
     free(s);
 }
 
-/* everything a beam call can be refused for; ws NULL: the host-pointer form, which owns its workspace; lm NULL: the acoustic search */
+/* everything a beam call can be refused for; ws NULL: the host-pointer form, which owns its workspace; o NULL or o->lm NULL: the
+ * acoustic search */
 static int beam_check_call(const char *who, NntkRnntDecoder d, NntkRnntBeamState state, const float *enc, int batch, int T,
-                           const int *n_frames, int beam_width, int nbest, int max_labels, NntkNgramLm lm, const int *labels_out,
+                           const int *n_frames, int beam_width, int nbest, int max_labels, const NntkRnntBeamOptions *o, const int *labels_out,
                            const int *out_lengths, const float *scores, const float *ws, int device_form) {
+    NntkNgramLm lm = o ? o->lm : NULL;
+    const int detail = beam_opt_detail(o);
     if (!d) return dec_fail(who, "NULL decoder", 0, 0, 0);
+    if (o && o->length_norm != 0 && o->length_norm != 1) return dec_fail(who, "length_norm %ld is neither 0 nor 1", o->length_norm, 0, 0);
+    if (state && state->detail != detail)
+        return dec_fail(who, state->detail ? "the state was created with detail, the call asks for none"
+                                           : "the state was created without detail, the call asks for it", 0, 0, 0);
     if (beam_check_lm(who, d, lm)) return -1;
     if (state && state->lm != lm)
         return dec_fail(who, !state->lm ? "the state was created without a language model" :
@@ -365,6 +401,8 @@ static int beam_check_call(const char *who, NntkRnntDecoder d, NntkRnntBeamState
     if (T > 0 && dec_named_ptr(who, "enc", enc)) return -1;
     if (dec_named_ptr(who, "labels_out", labels_out) || dec_named_ptr(who, "out_lengths", out_lengths) ||
         dec_named_ptr(who, "scores", scores)) return -1;
+    if (o && o->label_frames && dec_named_ptr(who, "label_frames", o->label_frames)) return -1;
+    if (o && o->label_logps && dec_named_ptr(who, "label_logps", o->label_logps)) return -1;
     if (device_form) {
         char msg[240];
         if (!ws || ((uintptr_t)ws & 15)) {
@@ -374,13 +412,13 @@ static int beam_check_call(const char *who, NntkRnntDecoder d, NntkRnntBeamState
         }
     }
     const size_t nh = (size_t)batch * nbest;
-    const void *p[5] = { labels_out, out_lengths, scores, enc, ws };
-    const size_t n[5] = { nh * max_labels * sizeof(int), nh * sizeof(int), nh * sizeof(float), (size_t)batch * T * d->cfg.J * sizeof(float),
-                          !device_form ? 0 : (lm ? nntk_rnnt_beam_lm_workspace_floats(d, batch, beam_width, max_labels)
-                                                 : nntk_rnnt_beam_workspace_floats(d, batch, beam_width, max_labels)) * sizeof(float) };
-    static const char *const name[5] = { "labels_out", "out_lengths", "scores", "enc", "workspace" };
-    for (int i = 0; i < 3; ++i)
-        for (int j = i + 1; j < 5; ++j)
+    const void *p[7] = { labels_out, out_lengths, scores, o ? o->label_frames : NULL, o ? o->label_logps : NULL, enc, ws };
+    const size_t n[7] = { nh * max_labels * sizeof(int), nh * sizeof(int), nh * sizeof(float), nh * max_labels * sizeof(int),
+                          nh * max_labels * sizeof(float), (size_t)batch * T * d->cfg.J * sizeof(float),
+                          !device_form ? 0 : nntk_rnnt_beam_opt_workspace_floats(d, batch, beam_width, max_labels, o) * sizeof(float) };
+    static const char *const name[7] = { "labels_out", "out_lengths", "scores", "label_frames", "label_logps", "enc", "workspace" };
+    for (int i = 0; i < 5; ++i)
+        for (int j = i + 1; j < 7; ++j)
             if (dec_overlap(p[i], n[i], p[j], n[j])) {
                 char msg[240];
                 snprintf(msg, sizeof msg, "%s: %s overlaps %s", who, name[i], name[j]);
@@ -393,12 +431,13 @@ static int beam_check_call(const char *who, NntkRnntDecoder d, NntkRnntBeamState
 }
 
 static int beam_decode_device(const char *who, NntkRnntDecoder d, NntkRnntBeamState state, const float *d_enc, int batch, int T,
-                              const int *n_frames, int beam_width, int nbest, int max_labels, NntkNgramLm lm, int *d_labels_out,
+                              const int *n_frames, int beam_width, int nbest, int max_labels, const NntkRnntBeamOptions *o, int *d_labels_out,
                               int *d_out_lengths, float *d_scores, float *d_workspace) {
     nntk_shim_clear_error();
-    if (beam_check_call(who, d, state, d_enc, batch, T, n_frames, beam_width, nbest, max_labels, lm, d_labels_out, d_out_lengths, d_scores,
+    if (beam_check_call(who, d, state, d_enc, batch, T, n_frames, beam_width, nbest, max_labels, o, d_labels_out, d_out_lengths, d_scores,
                         d_workspace, 1)) return -1;
     if (batch == 0) return 0;
+    NntkNgramLm lm = o ? o->lm : NULL;
     nntk_shim_rnnt_lm tab;
     if (lm && nntk_ngram_lm_rnnt_device(lm, &tab)) return -1;
     int *len = (int *)malloc((size_t)batch * sizeof(int));
@@ -406,10 +445,11 @@ static int beam_decode_device(const char *who, NntkRnntDecoder d, NntkRnntBeamSt
     for (int b = 0; b < batch; ++b) len[b] = n_frames ? n_frames[b] : T;
     const nntk_shim_rnnt_dec m = { d->d_table, d->d_U, d->d_proj, d->d_out, d->cfg.V, d->cfg.blank, d->cfg.E, d->cfg.H, d->cfg.J,
                                    d->cfg.joint_activation, d->cfg.max_symbols_per_frame };
-    int rc = lm ? nntk_shim_rnnt_beam_lm(&m, d_enc, batch, T, len, beam_width, nbest, max_labels, state ? &state->d : NULL, &tab,
-                                         state ? state->d_q : NULL, d_labels_out, d_out_lengths, d_scores, d_workspace)
-                : nntk_shim_rnnt_beam(&m, d_enc, batch, T, len, beam_width, nbest, max_labels, state ? &state->d : NULL, d_labels_out,
-                                      d_out_lengths, d_scores, d_workspace);
+    const nntk_shim_rnnt_beam_detail dt = { o ? o->label_frames : NULL, o ? o->label_logps : NULL, state ? state->d_fr : NULL,
+                                            state ? state->d_lp : NULL, o ? o->length_norm : 0 };
+    int rc = nntk_shim_rnnt_beam_opt(&m, d_enc, batch, T, len, beam_width, nbest, max_labels, state ? &state->d : NULL, lm ? &tab : NULL,
+                                     state && lm ? state->d_q : NULL, beam_opt_kernel(o) ? &dt : NULL, d_labels_out, d_out_lengths, d_scores,
+                                     d_workspace);
     free(len);
     return rc;
 }
@@ -421,33 +461,57 @@ int nntk_rnnt_beam_decode_device(NntkRnntDecoder d, NntkRnntBeamState state, con
                               d_labels_out, d_out_lengths, d_scores, d_workspace);
 }
 
+int nntk_rnnt_beam_decode_opt_device(NntkRnntDecoder d, NntkRnntBeamState state, const float *d_enc, int batch, int T, const int *n_frames,
+                                     int beam_width, int nbest, int max_labels, const NntkRnntBeamOptions *o, int *d_labels_out,
+                                     int *d_out_lengths, float *d_scores, float *d_workspace) {
+    return beam_decode_device("nntk_rnnt_beam_decode_opt_device", d, state, d_enc, batch, T, n_frames, beam_width, nbest, max_labels, o,
+                              d_labels_out, d_out_lengths, d_scores, d_workspace);
+}
+
 int nntk_rnnt_beam_decode_lm_device(NntkRnntDecoder d, NntkRnntBeamState state, const float *d_enc, int batch, int T, const int *n_frames,
                                     int beam_width, int nbest, int max_labels, NntkNgramLm lm, int *d_labels_out, int *d_out_lengths,
                                     float *d_scores, float *d_workspace) {
-    return beam_decode_device("nntk_rnnt_beam_decode_lm_device", d, state, d_enc, batch, T, n_frames, beam_width, nbest, max_labels, lm,
+    const NntkRnntBeamOptions o = { lm, 0, NULL, NULL };
+    return beam_decode_device("nntk_rnnt_beam_decode_lm_device", d, state, d_enc, batch, T, n_frames, beam_width, nbest, max_labels, &o,
                               d_labels_out, d_out_lengths, d_scores, d_workspace);
 }
 
 static int beam_decode_host(const char *who, NntkRnntDecoder d, NntkRnntBeamState state, const float *enc, int batch, int T,
-                            const int *n_frames, int beam_width, int nbest, int max_labels, NntkNgramLm lm, int *labels_out,
+                            const int *n_frames, int beam_width, int nbest, int max_labels, const NntkRnntBeamOptions *o, int *labels_out,
                             int *out_lengths, float *scores) {
     nntk_shim_clear_error();
-    if (beam_check_call(who, d, state, enc, batch, T, n_frames, beam_width, nbest, max_labels, lm, labels_out, out_lengths, scores, NULL, 0))
+    if (beam_check_call(who, d, state, enc, batch, T, n_frames, beam_width, nbest, max_labels, o, labels_out, out_lengths, scores, NULL, 0))
         return -1;
     if (batch == 0) return 0;
     const size_t ne = (size_t)batch * T * d->cfg.J, nh = (size_t)batch * nbest, nl = nh * max_labels;
+    const int detail = beam_opt_detail(o);
     float *d_enc = nntk_devbuf_reserve(&t_a, ne + 4);
-    int *d_lab = (int *)nntk_devbuf_reserve(&t_b, nl + 2 * nh + 4);
-    float *d_ws = nntk_devbuf_reserve(nntk_thread_scratch(NNTK_TS_C), lm ? nntk_rnnt_beam_lm_workspace_floats(d, batch, beam_width, max_labels)
-                                                                          : nntk_rnnt_beam_workspace_floats(d, batch, beam_width, max_labels));
+    int *d_lab = (int *)nntk_devbuf_reserve(&t_b, (detail ? 3 : 1) * nl + 2 * nh + 4);
+    float *d_ws = nntk_devbuf_reserve(nntk_thread_scratch(NNTK_TS_C), nntk_rnnt_beam_opt_workspace_floats(d, batch, beam_width, max_labels, o));
     if (!d_enc || !d_lab || !d_ws) return -1;
     int *d_len = d_lab + nl;
     float *d_sc = (float *)(d_len + nh);
+    NntkRnntBeamOptions dev = { NULL, 0, NULL, NULL };                /* o with the detail outputs in device memory, behind the scores */
+    if (o) dev = *o;
+    if (detail) {
+        dev.label_frames = o->label_frames ? (int *)(d_sc + nh) : NULL;
+        dev.label_logps = o->label_logps ? d_sc + nh + nl : NULL;
+    }
     if (ne && nntk_shim_upload(d_enc, enc, ne * sizeof(float))) return -1;
-    if (beam_decode_device(who, d, state, d_enc, batch, T, n_frames, beam_width, nbest, max_labels, lm, d_lab, d_len, d_sc, d_ws)) return -1;
+    if (beam_decode_device(who, d, state, d_enc, batch, T, n_frames, beam_width, nbest, max_labels, o ? &dev : NULL, d_lab, d_len, d_sc, d_ws))
+        return -1;
     if (nntk_shim_download(labels_out, d_lab, nl * sizeof(int))) return -1;
     if (nntk_shim_download(out_lengths, d_len, nh * sizeof(int))) return -1;
+    if (dev.label_frames && nntk_shim_download(o->label_frames, dev.label_frames, nl * sizeof(int))) return -1;
+    if (dev.label_logps && nntk_shim_download(o->label_logps, dev.label_logps, nl * sizeof(float))) return -1;
     return nntk_shim_download(scores, d_sc, nh * sizeof(float));
+}
+
+int nntk_rnnt_beam_decode_opt(NntkRnntDecoder d, NntkRnntBeamState state, const float *enc, int batch, int T, const int *n_frames,
+                              int beam_width, int nbest, int max_labels, const NntkRnntBeamOptions *o, int *labels_out, int *out_lengths,
+                              float *scores) {
+    return beam_decode_host("nntk_rnnt_beam_decode_opt", d, state, enc, batch, T, n_frames, beam_width, nbest, max_labels, o, labels_out,
+                            out_lengths, scores);
 }
 
 int nntk_rnnt_beam_decode(NntkRnntDecoder d, NntkRnntBeamState state, const float *enc, int batch, int T, const int *n_frames,
@@ -458,6 +522,7 @@ int nntk_rnnt_beam_decode(NntkRnntDecoder d, NntkRnntBeamState state, const floa
 
 int nntk_rnnt_beam_decode_lm(NntkRnntDecoder d, NntkRnntBeamState state, const float *enc, int batch, int T, const int *n_frames,
                              int beam_width, int nbest, int max_labels, NntkNgramLm lm, int *labels_out, int *out_lengths, float *scores) {
-    return beam_decode_host("nntk_rnnt_beam_decode_lm", d, state, enc, batch, T, n_frames, beam_width, nbest, max_labels, lm, labels_out,
+    const NntkRnntBeamOptions o = { lm, 0, NULL, NULL };
+    return beam_decode_host("nntk_rnnt_beam_decode_lm", d, state, enc, batch, T, n_frames, beam_width, nbest, max_labels, &o, labels_out,
                             out_lengths, scores);
 }

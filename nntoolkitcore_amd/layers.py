@@ -1224,37 +1224,57 @@ class RnntDecoder:
         return (torch.empty((B, nbest, max_labels), dtype=torch.int32, device=device),
                 torch.empty((B, nbest), dtype=torch.int32, device=device), torch.empty((B, nbest), dtype=torch.float32, device=device))
 
-    def _beam_workspace(self, device, B, beam_width, max_labels, lm=None):
+    def _beam_detail_outputs(self, device, B, nbest, max_labels):
         import torch
-        size = capi.load().nntk_rnnt_beam_workspace_floats if lm is None else capi.load().nntk_rnnt_beam_lm_workspace_floats
-        need = size(self.h, B, int(beam_width), int(max_labels))
+        return (torch.empty((B, nbest, max_labels), dtype=torch.int32, device=device),
+                torch.empty((B, nbest, max_labels), dtype=torch.float32, device=device))
+
+    def _beam_workspace(self, device, B, beam_width, max_labels, lm=None, detail=False, length_norm=False):
+        import torch
+        if detail or length_norm:                                   # the size depends on whether the pointers are set, not on where they point
+            o = capi.NntkRnntBeamOptions(lm.h if lm is not None else None, int(bool(length_norm)), 4 if detail else None, 4 if detail else None)
+            need = capi.load().nntk_rnnt_beam_opt_workspace_floats(self.h, B, int(beam_width), int(max_labels), C.byref(o))
+        else:
+            size = capi.load().nntk_rnnt_beam_workspace_floats if lm is None else capi.load().nntk_rnnt_beam_lm_workspace_floats
+            need = size(self.h, B, int(beam_width), int(max_labels))
         return torch.empty(max(int(need), 4), dtype=torch.float32, device=device)
 
-    def _beam(self, state, enc, n_frames, beam_width, nbest, max_labels, outs, workspace, lm=None):
+    def _beam(self, state, enc, n_frames, beam_width, nbest, max_labels, outs, workspace, lm=None, length_norm=False):
+        """outs: (labels, lengths, scores), or with detail (labels, lengths, scores, label_frames, label_logps)"""
         B, T, J = enc.shape
         assert J == self.J, "enc: [B, T, J]"
         nf = None if n_frames is None else _host_ints(n_frames, B, "n_frames")
-        labels, lengths, scores = outs
+        labels, lengths, scores = outs[:3]
         head = (self.h, state, _dp(enc), B, T, nf.ctypes.data_as(capi.ip) if nf is not None else None, int(beam_width), int(nbest),
                 int(max_labels))
         tail = (_ipv(labels), _ipv(lengths), _dp(scores), _dp(workspace))
-        if lm is None:
+        if len(outs) > 3 or length_norm:
+            o = capi.NntkRnntBeamOptions(lm.h if lm is not None else None, int(bool(length_norm)),
+                                         outs[3].data_ptr() if len(outs) > 3 else None, outs[4].data_ptr() if len(outs) > 3 else None)
+            check(capi.load().nntk_rnnt_beam_decode_opt_device(*head, C.byref(o), *tail), "nntk_rnnt_beam_decode_opt_device")
+        elif lm is None:
             check(capi.load().nntk_rnnt_beam_decode_device(*head, *tail), "nntk_rnnt_beam_decode_device")
         else:
             check(capi.load().nntk_rnnt_beam_decode_lm_device(*head, lm.h, *tail), "nntk_rnnt_beam_decode_lm_device")
         return outs
 
-    def beam_decode(self, enc, n_frames=None, beam_width=8, nbest=1, max_labels=None, lm=None):
+    def beam_decode(self, enc, n_frames=None, beam_width=8, nbest=1, max_labels=None, lm=None, detail=False, length_norm=False):
         """``nntk_rnnt_beam_decode_device`` (INTEGRATION.md "RNN-Transducer: beam search"): enc [B, T, J] device tensor, n_frames host
         ints per row (None: T) -> (labels [B, nbest, max_labels] int32, -1 behind each hypothesis's labels; lengths [B, nbest] int32,
         -1 for a slot without a hypothesis; scores [B, nbest] float32, -inf there).  max_labels defaults to
         max_symbols_per_frame * T, which never truncates.  lm: an NgramLm fused into the search
-        (``nntk_rnnt_beam_decode_lm_device``; scores then hold the model's terms and its end-of-sentence term), or None."""
+        (``nntk_rnnt_beam_decode_lm_device``; scores then hold the model's terms and its end-of-sentence term), or None.
+        detail: also return label_frames [B, nbest, max_labels] int32 (the frame each label was emitted in, -1 behind them) and
+        label_logps, the same shape, float32 (the acoustic log-probability of each emission, 0 behind them): five tensors
+        (``nntk_rnnt_beam_decode_opt_device``).  length_norm: the n-best is ordered by score / (length + 1); scores stay plain."""
         B, T, _ = enc.shape
         if max_labels is None:
             max_labels = max(1, self.max_symbols * T)
-        return self._beam(None, enc, n_frames, beam_width, nbest, max_labels, self._beam_outputs(enc.device, B, nbest, max_labels),
-                          self._beam_workspace(enc.device, B, beam_width, max_labels, lm), lm)
+        outs = self._beam_outputs(enc.device, B, nbest, max_labels)
+        if detail:
+            outs = outs + self._beam_detail_outputs(enc.device, B, nbest, max_labels)
+        return self._beam(None, enc, n_frames, beam_width, nbest, max_labels, outs,
+                          self._beam_workspace(enc.device, B, beam_width, max_labels, lm, detail, length_norm), lm, length_norm)
 
     def destroy(self):
         if self.h:
@@ -1311,13 +1331,17 @@ class RnntBeamStream:
     """``nntk_rnnt_beam_state_*``: transducer beam search pushed chunk by chunk for ``batch`` independent streams.  After every push
     row b holds what ``decoder.beam_decode`` gives on the row's frames since its last reset, bit for bit.  The stream owns the output
     buffers (labels [batch, nbest, max_labels]; lengths, scores [batch, nbest]) and the workspace, and returns the outputs from every
-    push.  lm: an NgramLm fused into the search (``nntk_rnnt_beam_state_create_lm``); it must stay open as long as the stream."""
+    push.  lm: an NgramLm fused into the search (``nntk_rnnt_beam_state_create_lm``); it must stay open as long as the stream.
+    detail: the stream also owns label_frames and label_logps [batch, nbest, max_labels] and every push returns five tensors, the
+    frames counted from the start of each row's stream (``nntk_rnnt_beam_state_create_opt``).  length_norm: as in ``beam_decode``."""
 
-    def __init__(self, decoder, batch, beam_width, nbest, max_labels, lm=None):
+    def __init__(self, decoder, batch, beam_width, nbest, max_labels, lm=None, detail=False, length_norm=False):
         self.dec, self.B, self.W, self.nbest, self.max_labels = decoder, int(batch), int(beam_width), int(nbest), int(max_labels)
         self.outs = self.ws = None
-        self.lm = lm
-        if lm is None:
+        self.lm, self.detail, self.length_norm = lm, bool(detail), bool(length_norm)
+        if detail:
+            self.h = capi.load().nntk_rnnt_beam_state_create_opt(decoder.h, self.B, self.W, self.max_labels, lm.h if lm is not None else None, 1)
+        elif lm is None:
             self.h = capi.load().nntk_rnnt_beam_state_create(decoder.h, self.B, self.W, self.max_labels)
         else:
             self.h = capi.load().nntk_rnnt_beam_state_create_lm(decoder.h, self.B, self.W, self.max_labels, lm.h)
@@ -1325,12 +1349,16 @@ class RnntBeamStream:
             raise capi.NNTKError("nntk_rnnt_beam_state_create: " + capi.last_error())
 
     def push(self, enc_chunk, n_frames):
-        """enc_chunk [batch, T, J] device tensor, n_frames host ints per row (0 allowed) -> (labels, lengths, scores)"""
+        """enc_chunk [batch, T, J] device tensor, n_frames host ints per row (0 allowed) -> (labels, lengths, scores), with detail
+        (labels, lengths, scores, label_frames, label_logps)"""
         assert enc_chunk.shape[0] == self.B, "enc_chunk: [batch, T, J]"
         if self.outs is None:
             self.outs = self.dec._beam_outputs(enc_chunk.device, self.B, self.nbest, self.max_labels)
-            self.ws = self.dec._beam_workspace(enc_chunk.device, self.B, self.W, self.max_labels, self.lm)
-        return self.dec._beam(self.h, enc_chunk, n_frames, self.W, self.nbest, self.max_labels, self.outs, self.ws, self.lm)
+            if self.detail:
+                self.outs = self.outs + self.dec._beam_detail_outputs(enc_chunk.device, self.B, self.nbest, self.max_labels)
+            self.ws = self.dec._beam_workspace(enc_chunk.device, self.B, self.W, self.max_labels, self.lm, self.detail, self.length_norm)
+        return self.dec._beam(self.h, enc_chunk, n_frames, self.W, self.nbest, self.max_labels, self.outs, self.ws, self.lm,
+                              self.length_norm)
 
     def reset(self, rows=None):
         """these rows (None: every row) start new streams"""
@@ -1353,10 +1381,11 @@ class RnntBeamStream:
 
 
 def rnnt_beam_decode(embed, lstm_block, pred_proj, out, enc, n_frames=None, beam_width=8, nbest=1, max_labels=None, blank=0,
-                     joint_activation=ACT_TANH, max_symbols_per_frame=10, lm=None):
+                     joint_activation=ACT_TANH, max_symbols_per_frame=10, lm=None, detail=False, length_norm=False):
     """Transducer beam search on numpy arrays (the weights go to the device, ``nntk_rnnt_beam_decode`` takes enc and the results as
     host memory): enc [B, T, J] -> (labels [B, nbest, max_labels], lengths [B, nbest], scores [B, nbest]).  lm: an NgramLm fused into
-    the search (``nntk_rnnt_beam_decode_lm``), or None."""
+    the search (``nntk_rnnt_beam_decode_lm``), or None.  detail, length_norm: as in ``RnntDecoder.beam_decode``
+    (``nntk_rnnt_beam_decode_opt``; with detail label_frames and label_logps follow the scores)."""
     import torch
     dev = lambda a: None if a is None else torch.from_numpy(_f32(a).reshape(-1) if a is not embed else _f32(a)).cuda()
     dec = RnntDecoder(dev(embed), dev(lstm_block), dev(pred_proj), dev(out), blank, joint_activation, max_symbols_per_frame)
@@ -1371,13 +1400,18 @@ def rnnt_beam_decode(embed, lstm_block, pred_proj, out, enc, n_frames=None, beam
         head = (dec.h, None, _p(enc), B, T, nf.ctypes.data_as(capi.ip) if nf is not None else None, int(beam_width), int(nbest),
                 int(max_labels))
         tail = (labels.ctypes.data_as(capi.ip), lengths.ctypes.data_as(capi.ip), _p(scores))
-        if lm is None:
+        if detail or length_norm:
+            frames, logps = np.empty((B, nbest, max_labels), np.int32), np.empty((B, nbest, max_labels), np.float32)
+            o = capi.NntkRnntBeamOptions(lm.h if lm is not None else None, int(bool(length_norm)), frames.ctypes.data if detail else None,
+                                         logps.ctypes.data if detail else None)
+            check(capi.load().nntk_rnnt_beam_decode_opt(*head, C.byref(o), *tail), "nntk_rnnt_beam_decode_opt")
+        elif lm is None:
             check(capi.load().nntk_rnnt_beam_decode(*head, *tail), "nntk_rnnt_beam_decode")
         else:
             check(capi.load().nntk_rnnt_beam_decode_lm(*head, lm.h, *tail), "nntk_rnnt_beam_decode_lm")
     finally:
         dec.destroy()
-    return labels, lengths, scores
+    return (labels, lengths, scores, frames, logps) if detail else (labels, lengths, scores)
 
 
 def rnnt_greedy_decode(embed, lstm_block, pred_proj, out, enc, n_frames=None, max_labels=None, blank=0, joint_activation=ACT_TANH,
