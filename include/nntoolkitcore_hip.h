@@ -1332,6 +1332,64 @@ NntkRnntBeamState nntk_rnnt_beam_state_create_opt(NntkRnntDecoder d, int batch, 
                                                   int with_detail);
 size_t nntk_rnnt_beam_state_bytes_opt(NntkRnntDecoder d, int batch, int beam_width, int max_labels, int with_lm, int with_detail);
 
+/* ---- RNN-Transducer: training the prediction network (csrc/hip/rnnt_pred.hip, csrc/host/rnnt_pred.c; INTEGRATION.md "RNN-Transducer:
+ *      training the prediction network") ----
+ * Label embedding.  ids: HOST int arrays, like every label array of this library, checked on the host and copied in stream order (the
+ * array is free on return).
+ *   lookup: d_out [rows][E], d_out[r][:] = d_table[ids[r]][:], bit copies; ids[r] == -1: a row of exact zeros.  A table row that no id
+ *     names is not read (it may hold NaN).  rows == 0 writes nothing.  16-byte accesses when E % 4 == 0 and both tensors are 16-byte
+ *     aligned, one float per lane otherwise; the bits do not depend on it.
+ *   gradient: d_dtable [V][E], d_dtable[v][:] = the sum over the rows r with ids[r] == v of d_dout[r][:]; EVERY element is written, exact
+ *     zeros for an id that does not occur; rows with ids[r] == -1 are never read (they may hold NaN).  rows == 0 zeroes the table.
+ *     d_workspace: nntk_embedding_workspace_floats(rows, V, E) floats, 16-byte aligned (V + 1 + rows ints of the sort, the lists of the
+ *     heavy ids, and rows / 16 + 1 partial rows of E floats).
+ *     No atomics.  The host counting-sorts the row numbers by id (nntk_embedding_sort_ids, O(rows + V)) and uploads the offsets and the
+ *     sorted rows into the workspace.  The summation shape of an id with n rows r_0 < r_1 < .. is a function of n alone: chunks of
+ *     32 consecutive list entries, each summed in ascending order in one f32 chain that starts from the chunk's first row (so one
+ *     occurrence is a bit copy), then the chunk sums added in ascending chunk order.  An id with more than 32 rows -- the start symbol
+ *     of a transducer batch -- has every chunk summed by a workgroup of its own.  Two calls return the same bits, and the bits of
+ *     d_dtable[v] depend only on the ascending list of v's rows and their values: not on V, the other ids, or the grid.
+ *   nntk_embedding_sort_ids: the stable counting sort itself, on host memory: offsets [V + 1], sorted_rows [rows]; the rows of id v
+ *     are sorted_rows[offsets[v] .. offsets[v + 1]), ascending; id -1 is in no list.  Returns offsets[V], or -1.
+ *   Refused on the host (-1, nntk_last_error(), nothing enqueued, no device needed): a NULL pointer; V < 1; E outside [1, 1024];
+ *     rows < 0; an id outside [-1, V); a tensor that is not 4-byte aligned; a workspace that is not 16-byte aligned; d_dtable
+ *     overlapping d_dout, d_out overlapping d_table, the workspace overlapping either tensor.
+ * Predictor handle: exactly the decoder's prediction network (nntk_rnnt_decoder_create above) in training, on blocks of the decoder's
+ * layouts: d_embed [V][E]; d_lstm, the LSTMGetWeights block W | U | b_i | b_h with the default activations; d_pred_proj, the Dense block
+ * W [H,J] | b [J] -- with has_proj == 0 the projection is the identity, which requires H == J, and every projection pointer is NULL.
+ * It composes the lookup above, a training-mode LSTM (batch x U1 steps, U1 = max_label_len + 1, return_sequences) through
+ * LSTMLoadWeightsDevice / LSTMApplyTrainingBatchDeviceVarLen / LSTMCalculateGradientDeviceVarLen and a training-mode
+ * TimeDistributedDense on batch U1 rows; d_pred, d_dlstm and d_dproj are the bits of that recipe with the lookup done on the host.
+ *   load_weights_device copies the blocks into the handle (the embedding into a device copy of its own) and returns after the copies
+ *     are done: the blocks may be rewritten at once, e.g. by the next optimizer step.
+ *   forward: labels HOST [batch][max_label_len], label_lengths HOST [batch] or NULL (every row max_label_len).  With U_b =
+ *     label_lengths[b], the input token of step u is blank for u == 0 and labels[b][u-1] for 1 <= u <= U_b; row b runs U_b + 1 LSTM steps
+ *     from the zero state, d_pred[b][u] = proj(h_u): the decoder's g after blank, y_1 .. y_u.  For u > U_b, h is exact zeros, so
+ *     d_pred[b][u] is the projection's bias (zeros without a projection).  labels[b][i >= U_b] are neither checked nor read.
+ *   backward: belongs to the last forward (the handle remembers its ids and lengths).  d_dpred [batch][U1][J] is the gradient of any
+ *     scalar with respect to d_pred; d_dpred[b][u > U_b] is ignored and may hold NaN (with a projection the handle copies d_dpred into
+ *     its own scratch with those rows zeroed before the Dense gradient call; without one no copy is made, the LSTM call ignores them).
+ *     d_dembed [V][E], d_dlstm (W | U | b_i | b_h) and d_dproj (W [H,J] | b [J]) are OVERWRITTEN with that scalar's gradients.
+ *   device_bytes: the handle's own device buffers (the embedding copy, x, d x, and with a projection h, d h and the masked d pred, plus
+ *     the embedding workspace); the two layer handles own theirs.
+ * Refused on the host before anything is enqueued (-1 / NULL, nntk_last_error()): a NULL handle or pointer; V outside [2, 8192]; E, H, J
+ * outside [1, 1024]; blank outside [0, V); has_proj == 0 with H != J; batch < 1; max_label_len < 0; whatever the LSTM training handle
+ * refuses; a label outside [0, V) or equal to blank; a length outside [0, max_label_len]; forward before load_weights_device; backward
+ * before a forward; a projection pointer that does not match has_proj.  Errors of the inner calls are passed through with their text.
+ * Deterministic: no atomics in the new kernels, the same bits on every call.  Runs on the calling thread's stream, reads nothing back. */
+int nntk_embedding_lookup_device(const float *d_table, int V, int E, const int *ids, int rows, float *d_out);
+int nntk_embedding_gradient_device(const float *d_dout, const int *ids, int rows, int V, int E, float *d_dtable, float *d_workspace);
+size_t nntk_embedding_workspace_floats(int rows, int V, int E);
+int nntk_embedding_sort_ids(const int *ids, int rows, int V, int *offsets, int *sorted_rows);
+typedef struct { int V, E, H, J, blank, has_proj, batch, max_label_len; } NntkRnntPredictorConfig;
+typedef struct NntkRnntPredictorStruct *NntkRnntPredictor;
+NntkRnntPredictor nntk_rnnt_predictor_create(NntkRnntPredictorConfig cfg);
+int nntk_rnnt_predictor_load_weights_device(NntkRnntPredictor p, const float *d_embed, const float *d_lstm, const float *d_pred_proj);
+int nntk_rnnt_predictor_forward_device(NntkRnntPredictor p, const int *labels, const int *label_lengths, float *d_pred);
+int nntk_rnnt_predictor_backward_device(NntkRnntPredictor p, const float *d_dpred, float *d_dembed, float *d_dlstm, float *d_dproj);
+size_t nntk_rnnt_predictor_device_bytes(NntkRnntPredictor p);
+void nntk_rnnt_predictor_destroy(NntkRnntPredictor p);
+
 #ifdef __cplusplus
 }
 #endif

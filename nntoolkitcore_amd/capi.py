@@ -66,6 +66,11 @@ class NntkRnntDecoderConfig(C.Structure):
                 ("max_symbols_per_frame", C.c_int)]
 
 
+class NntkRnntPredictorConfig(C.Structure):
+    _fields_ = [("V", C.c_int), ("E", C.c_int), ("H", C.c_int), ("J", C.c_int), ("blank", C.c_int), ("has_proj", C.c_int),
+                ("batch", C.c_int), ("max_label_len", C.c_int)]
+
+
 class NntkRnntBeamOptions(C.Structure):
     _fields_ = [("lm", vp), ("length_norm", C.c_int), ("label_frames", vp), ("label_logps", vp)]
 
@@ -515,6 +520,17 @@ SIGNATURES = {
                                             ip, ip, fp]),
     "nntk_rnnt_beam_state_create_opt": (vp, [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int]),
     "nntk_rnnt_beam_state_bytes_opt": (C.c_size_t, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    # training the prediction network: the label embedding and the predictor handle
+    "nntk_embedding_lookup_device": (C.c_int, [vp, C.c_int, C.c_int, ip, C.c_int, vp]),
+    "nntk_embedding_gradient_device": (C.c_int, [vp, ip, C.c_int, C.c_int, C.c_int, vp, vp]),
+    "nntk_embedding_workspace_floats": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "nntk_embedding_sort_ids": (C.c_int, [ip, C.c_int, C.c_int, ip, ip]),
+    "nntk_rnnt_predictor_create": (vp, [NntkRnntPredictorConfig]),
+    "nntk_rnnt_predictor_load_weights_device": (C.c_int, [vp, vp, vp, vp]),
+    "nntk_rnnt_predictor_forward_device": (C.c_int, [vp, ip, ip, vp]),
+    "nntk_rnnt_predictor_backward_device": (C.c_int, [vp, vp, vp, vp, vp]),
+    "nntk_rnnt_predictor_device_bytes": (C.c_size_t, [vp]),
+    "nntk_rnnt_predictor_destroy": (None, [vp]),
     # weights from device memory into a handle; the multi-tensor optimizer (INTEGRATION.md "Optimizers")
     "Conv1dLoadWeightsDevice": (C.c_int, [vp, vp]),
     "BatchNormLoadWeightsDevice": (C.c_int, [vp, vp]),

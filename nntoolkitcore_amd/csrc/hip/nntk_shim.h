@@ -308,6 +308,16 @@ size_t nntk_shim_rnnt_beam_opt_workspace_floats(int batch, int H, int J, int V, 
 int nntk_shim_rnnt_beam_opt(const nntk_shim_rnnt_dec *m, const float *d_enc, int batch, int T, const int *h_n_frames, int beam_width, int nbest,
                             int max_labels, const nntk_shim_rnnt_beam_state *st, const nntk_shim_rnnt_lm *lm, int *d_st_q,
                             const nntk_shim_rnnt_beam_detail *dt, int *d_labels, int *d_lengths, float *d_scores, float *d_ws);
+/* ---- the prediction network's label embedding, for training (rnnt_pred.hip).  rows_select: d_out [rows][width] = d_src[h_idx[r]][:], exact
+ *      zeros for h_idx[r] < 0; h_idx HOST memory, checked by the caller, carried in the kernel arguments.  embedding_grad: d_dtable [V][E],
+ *      every element written, from the caller's plan (rnnt_pred.c), HOST ints laid out offsets [V + 1] | sorted rows [n_sorted] | heavy
+ *      chunks [n_items][2] (id, chunk) | heavy ids [n_heavy][2] (id, first partial slot), uploaded in stream order into d_ws (16-byte
+ *      aligned, nntk_shim_embedding_workspace_floats(rows >= n_sorted, V, E) floats); an id is heavy above NNTK_EMBED_CHUNK rows ---- */
+#define NNTK_EMBED_CHUNK 32
+int nntk_shim_rows_select(const float *d_src, int width, const int *h_idx, long rows, float *d_out);
+size_t nntk_shim_embedding_workspace_floats(long rows, int V, int E);
+int nntk_shim_embedding_grad(const float *d_dout, int V, int E, const int *h_plan, long n_sorted, long n_items, long n_heavy, float *d_dtable,
+                             float *d_ws);
 /* BatchNorm training (batch_norm.c:191-386): x, d_out [N, F]; d_block = gamma | beta | ...; d_stats [8][F] = mean | variance |
  * var_eps | sqrt_var | d_beta | d_gamma | d_var | d_mu; d_partial [slices][3][F] with slices from nntk_shim_bn_train_slices */
 /* Ragged batches and carried state for the recurrent training launchers below (the *VarLen training calls; a NULL pointer to it = the

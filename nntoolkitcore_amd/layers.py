@@ -1437,6 +1437,109 @@ def rnnt_greedy_decode(embed, lstm_block, pred_proj, out, enc, n_frames=None, ma
     return labels, frames, lengths, scores
 
 
+def _host_ids(ids):
+    return np.ascontiguousarray(np.asarray(ids, dtype=np.int32).reshape(-1))
+
+
+def embedding_lookup_device(table, ids, out=None):
+    """``nntk_embedding_lookup_device``: table [V, E] device tensor, ids host ints (-1: a row of zeros) -> out [len(ids), E], bit copies of
+    the table's rows"""
+    V, E = table.shape
+    idv = _host_ids(ids)
+    rows = idv.shape[0]
+    if out is None:
+        out = table.new_empty((rows, E))
+    assert out.numel() == rows * E, "out: [rows, E]"
+    check(capi.load().nntk_embedding_lookup_device(_dp(table), V, E, idv.ctypes.data_as(capi.ip), rows, _dp(out) if rows else None),
+          "nntk_embedding_lookup_device")
+    return out
+
+
+def embedding_gradient_device(dout, ids, V, dtable=None, workspace=None):
+    """``nntk_embedding_gradient_device``: dout [rows, E] device tensor, ids host ints -> dtable [V, E], overwritten: the sum of the rows of
+    each id, exact zeros for an absent id; rows with id -1 are never read.  No atomics, the same bits on every call."""
+    import torch
+    idv = _host_ids(ids)
+    rows = idv.shape[0]
+    E = dout.shape[-1]
+    assert dout.numel() == rows * E, "dout: [rows, E]"
+    L = capi.load()
+    need = L.nntk_embedding_workspace_floats(rows, V, E)
+    if dtable is None:
+        dtable = dout.new_empty((V, E))
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.float32, device=dout.device)
+    assert dtable.numel() == V * E, "dtable: [V, E]"
+    assert workspace.numel() >= need, "workspace: nntk_embedding_workspace_floats(rows, V, E) floats"
+    check(L.nntk_embedding_gradient_device(_dp(dout) if rows else None, idv.ctypes.data_as(capi.ip), rows, V, E, _dp(dtable), _dp(workspace)),
+          "nntk_embedding_gradient_device")
+    return dtable
+
+
+class RnntPredictor:
+    """``nntk_rnnt_predictor_*``: the decoder's prediction network -- label embedding, one LSTM, a linear projection (proj=False: the
+    identity, H == J) -- in training, on the device blocks ``RnntDecoder`` takes (INTEGRATION.md "RNN-Transducer: training the prediction
+    network").  forward gives pred [batch, max_label_len + 1, J] for the loss calls, backward the gradients of the three blocks."""
+
+    def __init__(self, V, E, H, J, batch, max_label_len, blank=0, proj=True):
+        self.V, self.E, self.H, self.J, self.batch, self.max_label_len = int(V), int(E), int(H), int(J), int(batch), int(max_label_len)
+        self.has_proj = bool(proj)
+        cfg = capi.NntkRnntPredictorConfig(self.V, self.E, self.H, self.J, int(blank), int(self.has_proj), self.batch, self.max_label_len)
+        self.h = capi.load().nntk_rnnt_predictor_create(cfg)
+        if not self.h:
+            raise capi.NNTKError("nntk_rnnt_predictor_create: " + capi.last_error())
+
+    def load_weights(self, embed, lstm_block, pred_proj):
+        """``nntk_rnnt_predictor_load_weights_device``: embed [V, E], the flat LSTM block, the flat projection block (None without one);
+        the handle keeps copies, so call it again after every optimizer step"""
+        check(capi.load().nntk_rnnt_predictor_load_weights_device(self.h, _dp(embed), _dp(lstm_block),
+                                                                  _dp(pred_proj) if pred_proj is not None else None),
+              "nntk_rnnt_predictor_load_weights_device")
+
+    def forward(self, labels, label_lengths=None, pred=None):
+        """labels: a list of per-row lists, or a padded int array [batch, max_label_len] with label_lengths (as ``rnnt_loss_device``)
+        -> pred [batch, max_label_len + 1, J]; rows u > label_lengths[b] hold the projection's bias"""
+        import torch
+        lab, ll = _rnnt_labels(labels, label_lengths, self.batch, self.max_label_len)
+        if pred is None:
+            pred = torch.empty((self.batch, self.max_label_len + 1, self.J), dtype=torch.float32, device="cuda")
+        assert pred.numel() == self.batch * (self.max_label_len + 1) * self.J, "pred: [batch, max_label_len + 1, J]"
+        check(capi.load().nntk_rnnt_predictor_forward_device(self.h, lab.ctypes.data_as(capi.ip), ll.ctypes.data_as(capi.ip), _dp(pred)),
+              "nntk_rnnt_predictor_forward_device")
+        return pred
+
+    def backward(self, dpred, dembed=None, dlstm=None, dproj=None):
+        """dpred [batch, max_label_len + 1, J] (rows u > label_lengths[b] are ignored) -> (dembed [V, E], dlstm, dproj or None), all
+        overwritten; pass the gradient tensors registered with ``Optimizer`` to have them filled in place"""
+        if dembed is None:
+            dembed = dpred.new_empty((self.V, self.E))
+        if dlstm is None:
+            dlstm = dpred.new_empty(4 * self.H * (self.E + self.H + 2))
+        if dproj is None and self.has_proj:
+            dproj = dpred.new_empty((self.H + 1) * self.J)
+        assert dpred.numel() == self.batch * (self.max_label_len + 1) * self.J, "dpred: [batch, max_label_len + 1, J]"
+        assert dembed.numel() == self.V * self.E and dlstm.numel() == 4 * self.H * (self.E + self.H + 2), "dembed [V, E], dlstm: the flat block"
+        assert dproj is None or dproj.numel() == (self.H + 1) * self.J, "dproj: the flat block W [H,J] | b [J]"
+        check(capi.load().nntk_rnnt_predictor_backward_device(self.h, _dp(dpred), _dp(dembed), _dp(dlstm),
+                                                              _dp(dproj) if dproj is not None else None),
+              "nntk_rnnt_predictor_backward_device")
+        return dembed, dlstm, dproj
+
+    def device_bytes(self):
+        return int(capi.load().nntk_rnnt_predictor_device_bytes(self.h))
+
+    def destroy(self):
+        if self.h:
+            capi.load().nntk_rnnt_predictor_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.destroy()
+        except Exception:
+            pass
+
+
 class LSTM(_Recurrent):
     def __init__(self, in_features, hidden, return_sequences, timesteps, v2=True, acts=None, mini_batch=None):
         L = capi.load()
