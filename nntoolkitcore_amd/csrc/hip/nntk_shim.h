@@ -257,10 +257,18 @@ int nntk_shim_rnnt_greedy(const nntk_shim_rnnt_dec *m, const float *d_enc, int b
 /* ---- transducer beam search (rnnt_beam.hip) on the greedy decoder's blocks.  One workgroup runs a row's whole search; the hypotheses
  *      of a depth share passes over the matrices in groups of NNTK_RNNT_DEC_GROUP where the group's LDS fits, else one by one
  *      (nntk_shim_rnnt_beam_group; nntk_shim_rnnt_beam_set_group(1 or NNTK_RNNT_DEC_GROUP) pins it for tests and timing, 0 = automatic;
- *      the bits do not depend on it).  The workspace holds, after the rows' frame counts, per row (S' + 2) beam_width hypothesis slots
- *      (h | c | g, the labels, length and hash), beam_width V logits and the frame's list of beam_width (S' + 1) finished hypotheses,
- *      S' = min(max_symbols_per_frame, max_labels). ---- */
+ *      the bits do not depend on it).  The workspace, nntk_shim_rnnt_beam_workspace_floats words, holds the rows' frame counts, then per
+ *      row three parts, each behind the one before so that an absent one moves nothing, S' = min(max_symbols_per_frame, max_labels):
+ *        acoustic       (S' + 2) beam_width hypothesis slots (h | c | g, the labels, length and hash), beam_width V logits and the
+ *                       frame's list B of beam_width (S' + 1) finished hypotheses;
+ *        with_lm        an int per hypothesis slot (its LM state) and beam_width V doubles;
+ *        with_detail    two words per hypothesis slot and label (frame, log-probability) and three per entry of B. ---- */
 #define NNTK_RNNT_BEAM_MAX_W 32
+size_t nntk_shim_rnnt_beam_workspace_floats(int batch, int H, int J, int V, int max_sym, int beam_width, int max_labels, int with_lm,
+                                            int with_detail);
+int nntk_shim_rnnt_beam_fits(int H, int J, int V);                             /* the kernel's LDS at one hypothesis a pass */
+int nntk_shim_rnnt_beam_group(int beam_width, int H, int J, int V);
+void nntk_shim_rnnt_beam_set_group(int group);
 /* a stream's rows: score [batch][W] doubles, f [batch][W][2H + J], lab [batch][W][max_labels], meta [batch][W][2] (length | hash),
  * i [batch][4] (started | hypotheses | frames consumed, with detail | -); all NULL: every row from the start, nothing kept */
 typedef struct {
@@ -268,34 +276,19 @@ typedef struct {
     float *f;
     int *lab, *meta, *i;
 } nntk_shim_rnnt_beam_state;
-size_t nntk_shim_rnnt_beam_workspace_floats(int batch, int H, int J, int V, int max_sym, int beam_width, int max_labels);
-int nntk_shim_rnnt_beam_fits(int H, int J, int V);                             /* the kernel's LDS at one hypothesis a pass */
-int nntk_shim_rnnt_beam_group(int beam_width, int H, int J, int V);
-void nntk_shim_rnnt_beam_set_group(int group);
-/* h_n_frames HOST [batch], checked by the caller, copied in stream order into the workspace; d_ws 16-byte aligned */
-int nntk_shim_rnnt_beam(const nntk_shim_rnnt_dec *m, const float *d_enc, int batch, int T, const int *h_n_frames, int beam_width, int nbest,
-                        int max_labels, const nntk_shim_rnnt_beam_state *st, int *d_labels, int *d_lengths, float *d_scores, float *d_ws);
 /* Language-model fusion (INTEGRATION.md "RNN-Transducer: beam search", Language-model fusion).  The search adds natural logs in double, so
  * next to the lookup records of nntk_shim_lm (d_arcs {label, next state, -, -}, d_states {first arc, arcs, backoff state, 0}) it reads
- * tables of its own: d_arc_ln [arcs] = ln G, d_state_ln [states][2] = ln B | ln E, and ln U.  lm NULL: nntk_shim_rnnt_beam.  With a
- * model the workspace is nntk_shim_rnnt_beam_lm_workspace_floats words -- the acoustic layout, then per row an int per hypothesis slot
- * and beam_width V doubles -- and a stream's rows carry d_st_q [batch][W], the LM state of each hypothesis. */
+ * tables of its own: d_arc_ln [arcs] = ln G, d_state_ln [states][2] = ln B | ln E, and ln U. */
 typedef struct {
     const int *d_arcs, *d_states;
     const double *d_arc_ln, *d_state_ln;
     double unk_ln;
     int start_state;
 } nntk_shim_rnnt_lm;
-size_t nntk_shim_rnnt_beam_lm_workspace_floats(int batch, int H, int J, int V, int max_sym, int beam_width, int max_labels);
-int nntk_shim_rnnt_beam_lm(const nntk_shim_rnnt_dec *m, const float *d_enc, int batch, int T, const int *h_n_frames, int beam_width, int nbest,
-                           int max_labels, const nntk_shim_rnnt_beam_state *st, const nntk_shim_rnnt_lm *lm, int *d_st_q, int *d_labels,
-                           int *d_lengths, float *d_scores, float *d_ws);
-/* Label timestamps, confidences and length normalisation (include/nntoolkitcore_hip.h, "Label timestamps" under the beam search).  dt
- * NULL: nntk_shim_rnnt_beam_lm, the same kernels.  With dt the workspace is nntk_shim_rnnt_beam_opt_workspace_floats(.., with_detail = 1)
- * words -- the acoustic and LM layouts, then per row two words per hypothesis slot and label and three per entry of B.  d_frames,
- * d_logps [batch][nbest][max_labels], each may be NULL.  d_st_fr, d_st_lp [batch][W][max_labels]: the arrays of a stream's rows, both
- * or neither (neither: the arrays are not carried); the frames a row has consumed ride in word 2 of the state's i, read only while
- * the row's started word is set, so a reset row counts from 0 again. */
+/* Label timestamps, confidences and length normalisation (include/nntoolkitcore_hip.h, "Label timestamps" under the beam search).
+ * d_frames, d_logps [batch][nbest][max_labels], each may be NULL.  d_st_fr, d_st_lp [batch][W][max_labels]: the arrays of a stream's
+ * rows, both or neither (neither: the arrays are not carried); the frames a row has consumed ride in word 2 of the state's i, read only
+ * while the row's started word is set, so a reset row counts from 0 again. */
 typedef struct {
     int *d_frames;
     float *d_logps;
@@ -303,11 +296,12 @@ typedef struct {
     float *d_st_lp;
     int length_norm;
 } nntk_shim_rnnt_beam_detail;
-size_t nntk_shim_rnnt_beam_opt_workspace_floats(int batch, int H, int J, int V, int max_sym, int beam_width, int max_labels, int with_lm,
-                                                int with_detail);
-int nntk_shim_rnnt_beam_opt(const nntk_shim_rnnt_dec *m, const float *d_enc, int batch, int T, const int *h_n_frames, int beam_width, int nbest,
-                            int max_labels, const nntk_shim_rnnt_beam_state *st, const nntk_shim_rnnt_lm *lm, int *d_st_q,
-                            const nntk_shim_rnnt_beam_detail *dt, int *d_labels, int *d_lengths, float *d_scores, float *d_ws);
+/* h_n_frames HOST [batch], checked by the caller, copied in stream order into the workspace; d_ws 16-byte aligned, sized with the flags
+ * lm != NULL and dt != NULL.  st NULL: one-shot.  lm NULL: the acoustic search; with st and lm, d_st_q [batch][W] carries each
+ * hypothesis's LM state.  dt NULL: no detail, the report in the search's own order (by score + ln E with lm); the same search either way. */
+int nntk_shim_rnnt_beam(const nntk_shim_rnnt_dec *m, const float *d_enc, int batch, int T, const int *h_n_frames, int beam_width, int nbest,
+                        int max_labels, const nntk_shim_rnnt_beam_state *st, const nntk_shim_rnnt_lm *lm, int *d_st_q,
+                        const nntk_shim_rnnt_beam_detail *dt, int *d_labels, int *d_lengths, float *d_scores, float *d_ws);
 /* ---- the prediction network's label embedding, for training (rnnt_pred.hip).  rows_select: d_out [rows][width] = d_src[h_idx[r]][:], exact
  *      zeros for h_idx[r] < 0; h_idx HOST memory, checked by the caller, carried in the kernel arguments.  embedding_grad: d_dtable [V][E],
  *      every element written, from the caller's plan (rnnt_pred.c), HOST ints laid out offsets [V + 1] | sorted rows [n_sorted] | heavy

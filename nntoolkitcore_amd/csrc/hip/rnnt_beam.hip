@@ -9,7 +9,9 @@
 // LDS.  RbShared (the reductions' scratch, the depth's hypotheses C: slot, score, length, hash, max and log-sum-exp of the logits; the
 // selected cells), then per group row  h [Hp] | c [Hp] | z [Jp] | buf [max(4H, V)]  (buf: gate pre-activations or logits).
 //
-// Workspace (global, L2-resident at these sizes): the rows' frame counts, then per row
+// Workspace (global, L2-resident at these sizes; rb_layout is the layout, nntk_shim_rnnt_beam_workspace_floats its size): the rows'
+// frame counts, then per row the acoustic part, the LM part with a model and the detail part with detail, in that order, so that a part
+// that is absent moves none of the others.  The acoustic part:
 //   bscore [W (S' + 1)] doubles      the scores of B, the hypotheses that have left the frame, in insertion order
 //   states [(S' + 2) W][2H + J]      h | c | g of every hypothesis slot: A (two buffers, swapped every frame), then one level per depth
 //   labels [(S' + 2) W][max_labels]  each slot's label sequence
@@ -627,10 +629,17 @@ __global__ __launch_bounds__(RD_THREADS) void rnnt_beam_kernel(const RnntBeamArg
     }
 }
 
-template <int R, bool LM, bool DETAIL>
-static int rb_launch(const RnntBeamArgs &a, size_t lds) {
-    if (lds > 48 * 1024 && nntk_set_max_dynamic_lds((const void *)rnnt_beam_kernel<R, LM, DETAIL>, lds)) return -1;
-    hipLaunchKernelGGL((rnnt_beam_kernel<R, LM, DETAIL>), dim3((unsigned)a.batch), dim3(RD_THREADS), lds, nntk_stream(), a);
+typedef void (*RbKernel)(const RnntBeamArgs);
+
+template <int R> static RbKernel rb_kernel(bool lm, bool detail) {
+    static const RbKernel k[2][2] = { { rnnt_beam_kernel<R, false, false>, rnnt_beam_kernel<R, false, true> },
+                                      { rnnt_beam_kernel<R, true, false>, rnnt_beam_kernel<R, true, true> } };
+    return k[lm][detail];
+}
+
+static int rb_launch(RbKernel k, const RnntBeamArgs &a, size_t lds) {
+    if (lds > 48 * 1024 && nntk_set_max_dynamic_lds((const void *)k, lds)) return -1;
+    hipLaunchKernelGGL(k, dim3((unsigned)a.batch), dim3(RD_THREADS), lds, nntk_stream(), a);
     return 0;
 }
 
@@ -638,9 +647,12 @@ static int rb_forced_group = 0;
 
 extern "C" {
 
-size_t nntk_shim_rnnt_beam_workspace_floats(int batch, int H, int J, int V, int max_sym, int beam_width, int max_labels) {
+size_t nntk_shim_rnnt_beam_workspace_floats(int batch, int H, int J, int V, int max_sym, int beam_width, int max_labels, int with_lm,
+                                            int with_detail) {
     if (batch <= 0) return 0;
-    return (((size_t)batch + 3) & ~(size_t)3) + (size_t)batch * rb_layout(H, J, V, max_sym, beam_width, max_labels).row;
+    RbDetailLayout dl;
+    return (((size_t)batch + 3) & ~(size_t)3) +
+           (size_t)batch * rb_layout(H, J, V, max_sym, beam_width, max_labels, with_lm != 0, with_detail ? &dl : nullptr).row;
 }
 
 int nntk_shim_rnnt_beam_fits(int H, int J, int V) { return rb_lds_bytes(1, H, J, V) <= RD_LDS_MAX; }
@@ -653,35 +665,9 @@ int nntk_shim_rnnt_beam_group(int beam_width, int H, int J, int V) {
 
 void nntk_shim_rnnt_beam_set_group(int group) { rb_forced_group = group == 1 || group == NNTK_RNNT_DEC_GROUP ? group : 0; }
 
-size_t nntk_shim_rnnt_beam_lm_workspace_floats(int batch, int H, int J, int V, int max_sym, int beam_width, int max_labels) {
-    if (batch <= 0) return 0;
-    return (((size_t)batch + 3) & ~(size_t)3) + (size_t)batch * rb_layout(H, J, V, max_sym, beam_width, max_labels, true).row;
-}
-
 int nntk_shim_rnnt_beam(const nntk_shim_rnnt_dec *m, const float *d_enc, int batch, int T, const int *h_n_frames, int beam_width, int nbest,
-                        int max_labels, const nntk_shim_rnnt_beam_state *st, int *d_labels, int *d_lengths, float *d_scores, float *d_ws) {
-    return nntk_shim_rnnt_beam_opt(m, d_enc, batch, T, h_n_frames, beam_width, nbest, max_labels, st, nullptr, nullptr, nullptr, d_labels,
-                                   d_lengths, d_scores, d_ws);
-}
-
-size_t nntk_shim_rnnt_beam_opt_workspace_floats(int batch, int H, int J, int V, int max_sym, int beam_width, int max_labels, int with_lm,
-                                                int with_detail) {
-    if (batch <= 0) return 0;
-    RbDetailLayout dl;
-    return (((size_t)batch + 3) & ~(size_t)3) +
-           (size_t)batch * rb_layout(H, J, V, max_sym, beam_width, max_labels, with_lm != 0, with_detail ? &dl : nullptr).row;
-}
-
-int nntk_shim_rnnt_beam_lm(const nntk_shim_rnnt_dec *m, const float *d_enc, int batch, int T, const int *h_n_frames, int beam_width, int nbest,
-                           int max_labels, const nntk_shim_rnnt_beam_state *st, const nntk_shim_rnnt_lm *lm, int *d_st_q, int *d_labels,
-                           int *d_lengths, float *d_scores, float *d_ws) {
-    return nntk_shim_rnnt_beam_opt(m, d_enc, batch, T, h_n_frames, beam_width, nbest, max_labels, st, lm, d_st_q, nullptr, d_labels, d_lengths,
-                                   d_scores, d_ws);
-}
-
-int nntk_shim_rnnt_beam_opt(const nntk_shim_rnnt_dec *m, const float *d_enc, int batch, int T, const int *h_n_frames, int beam_width, int nbest,
-                            int max_labels, const nntk_shim_rnnt_beam_state *st, const nntk_shim_rnnt_lm *lm, int *d_st_q,
-                            const nntk_shim_rnnt_beam_detail *dt, int *d_labels, int *d_lengths, float *d_scores, float *d_ws) {
+                        int max_labels, const nntk_shim_rnnt_beam_state *st, const nntk_shim_rnnt_lm *lm, int *d_st_q,
+                        const nntk_shim_rnnt_beam_detail *dt, int *d_labels, int *d_lengths, float *d_scores, float *d_ws) {
     if (batch <= 0) return 0;
     const int depths = m->max_symbols_per_frame < max_labels ? m->max_symbols_per_frame : max_labels;
     if (m->E < 1 || m->H < 1 || m->J < 1 || m->V < 2 || m->H > NNTK_RNNT_DEC_MAX_WIDTH || m->J > NNTK_RNNT_DEC_MAX_WIDTH ||
@@ -692,25 +678,20 @@ int nntk_shim_rnnt_beam_opt(const nntk_shim_rnnt_dec *m, const float *d_enc, int
     RnntBeamArgs a;
     a.enc = d_enc; a.table = m->d_table; a.U = m->d_U; a.proj = m->d_proj; a.out = m->d_out;
     a.ws = d_ws;
-    if (st) a.st = *st;
-    else { a.st.score = nullptr; a.st.f = nullptr; a.st.lab = nullptr; a.st.meta = nullptr; a.st.i = nullptr; }
+    a.st = st ? *st : nntk_shim_rnnt_beam_state();
+    a.lm = lm ? *lm : nntk_shim_rnnt_lm();
+    a.dt = dt ? *dt : nntk_shim_rnnt_beam_detail();
+    a.st_q = st ? d_st_q : nullptr;            // what a stream carries besides st is dropped without one
+    if (!st) a.dt.d_st_fr = nullptr, a.dt.d_st_lp = nullptr;
     a.labels = d_labels; a.lengths = d_lengths; a.scores = d_scores;
     a.dlay = RbDetailLayout();
     a.lay = rb_layout(m->H, m->J, m->V, m->max_symbols_per_frame, beam_width, max_labels, lm != nullptr, dt ? &a.dlay : nullptr);
     a.ws_head = ((size_t)batch + 3) & ~(size_t)3;
     a.batch = batch; a.T = T; a.V = m->V; a.blank = m->blank; a.H = m->H; a.J = m->J; a.act = m->activation;
     a.max_sym = m->max_symbols_per_frame; a.W = beam_width; a.nbest = nbest; a.max_labels = max_labels;
-    a.lm = lm ? *lm : nntk_shim_rnnt_lm();
-    a.st_q = st ? d_st_q : nullptr;
-    a.dt = dt ? *dt : nntk_shim_rnnt_beam_detail();
-    if (!st) a.dt.d_st_fr = nullptr, a.dt.d_st_lp = nullptr;
     const int R = nntk_shim_rnnt_beam_group(beam_width, m->H, m->J, m->V);
-    const size_t lds = rb_lds_bytes(R, m->H, m->J, m->V);
-    constexpr int RG = NNTK_RNNT_DEC_GROUP;
-    if (dt ? (R == 1 ? (lm ? rb_launch<1, true, true>(a, lds) : rb_launch<1, false, true>(a, lds))
-                     : (lm ? rb_launch<RG, true, true>(a, lds) : rb_launch<RG, false, true>(a, lds)))
-           : (R == 1 ? (lm ? rb_launch<1, true, false>(a, lds) : rb_launch<1, false, false>(a, lds))
-                     : (lm ? rb_launch<RG, true, false>(a, lds) : rb_launch<RG, false, false>(a, lds)))) return -1;
+    const RbKernel k = R == 1 ? rb_kernel<1>(lm != nullptr, dt != nullptr) : rb_kernel<NNTK_RNNT_DEC_GROUP>(lm != nullptr, dt != nullptr);
+    if (rb_launch(k, a, rb_lds_bytes(R, m->H, m->J, m->V))) return -1;
     NNTK_LAUNCH_CHECK("rnnt_beam_kernel");
     return 0;
 }

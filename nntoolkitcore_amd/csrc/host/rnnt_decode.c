@@ -1,8 +1,9 @@
 /*
  * rnnt_decode.c -- host layer of RNN-Transducer decoding: the decoder handle with its own device copy of the weights; greedy search
  * (csrc/hip/rnnt_decode.hip) and, below it, beam search (csrc/hip/rnnt_beam.hip), each with the per-row state of a stream and the
- * decode call in its device-pointer and host-pointer forms.  Every argument is checked here, before anything is allocated, uploaded
- * or enqueued: a refusal needs no device and writes nothing.
+ * decode call in its device-pointer and host-pointer forms; the beam search's plain, _lm and _opt entries share one body a form and the
+ * workspace of nntk_shim_rnnt_beam_workspace_floats.  Every argument is checked here, before anything is allocated, uploaded or
+ * enqueued: a refusal needs no device and writes nothing.
  */
 #include <stdint.h>
 #include <stdio.h>
@@ -135,19 +136,23 @@ NntkRnntDecodeState nntk_rnnt_decode_state_create(NntkRnntDecoder d, int batch) 
     return s;
 }
 
-int nntk_rnnt_decode_state_reset(NntkRnntDecodeState s, const int *rows, int n_rows) {
-    static const char who[] = "nntk_rnnt_decode_state_reset";
+/* the reset of a greedy or a beam state, d_i its [batch][4] (word 0 of a row: started) with [batch] for the rows behind; NULL: no state */
+static int dec_state_reset(const char *who, int batch, int *d_i, const int *rows, int n_rows) {
     nntk_shim_clear_error();
-    if (!s) return dec_fail(who, "NULL state", 0, 0, 0);
-    if (n_rows < 0 || n_rows > s->batch) return dec_fail(who, "n_rows %ld is outside [0, %ld]", n_rows, s->batch, 0);
+    if (!d_i) return dec_fail(who, "NULL state", 0, 0, 0);
+    if (n_rows < 0 || n_rows > batch) return dec_fail(who, "n_rows %ld is outside [0, %ld]", n_rows, batch, 0);
     if (!rows && n_rows > 0) return dec_fail(who, "rows is NULL with n_rows %ld", n_rows, 0, 0);
-    if (!rows) return nntk_shim_memset(s->d_i, 0, (size_t)s->batch * 4 * sizeof(int));
+    if (!rows) return nntk_shim_memset(d_i, 0, (size_t)batch * 4 * sizeof(int));
     for (int i = 0; i < n_rows; ++i)
-        if (rows[i] < 0 || rows[i] >= s->batch) return dec_fail(who, "rows[%ld] = %ld is outside [0, %ld)", i, rows[i], s->batch);
+        if (rows[i] < 0 || rows[i] >= batch) return dec_fail(who, "rows[%ld] = %ld is outside [0, %ld)", i, rows[i], batch);
     if (n_rows == 0) return 0;
-    int *d_rows = s->d_i + 4 * (size_t)s->batch;
+    int *d_rows = d_i + 4 * (size_t)batch;
     if (nntk_shim_upload_ints(d_rows, rows, n_rows)) return -1;
-    return nntk_shim_rnnt_dec_reset(s->d_i, d_rows, n_rows);
+    return nntk_shim_rnnt_dec_reset(d_i, d_rows, n_rows);
+}
+
+int nntk_rnnt_decode_state_reset(NntkRnntDecodeState s, const int *rows, int n_rows) {
+    return dec_state_reset("nntk_rnnt_decode_state_reset", s ? s->batch : 0, s ? s->d_i : NULL, rows, n_rows);
 }
 
 void nntk_rnnt_decode_state_destroy(NntkRnntDecodeState s) {
@@ -161,6 +166,19 @@ void nntk_rnnt_decode_state_destroy(NntkRnntDecodeState s) {
 
 static int dec_overlap(const void *a, size_t na, const void *b, size_t nb) {
     return a && b && na && nb && (uintptr_t)a < (uintptr_t)b + nb && (uintptr_t)b < (uintptr_t)a + na;
+}
+
+/* no output (the first n_out blocks) may overlap another block of the call */
+static int dec_check_overlaps(const char *who, int n_out, int n_all, const void *const *p, const size_t *n, const char *const *name) {
+    for (int i = 0; i < n_out; ++i)
+        for (int j = i + 1; j < n_all; ++j)
+            if (dec_overlap(p[i], n[i], p[j], n[j])) {
+                char msg[240];
+                snprintf(msg, sizeof msg, "%s: %s overlaps %s", who, name[i], name[j]);
+                nntk_set_error(msg);
+                return -1;
+            }
+    return 0;
 }
 
 /* everything a decode call can be refused for; tensors = 1: the device form's pointers (alignment, overlap) */
@@ -184,15 +202,21 @@ static int dec_check_call(const char *who, NntkRnntDecoder d, NntkRnntDecodeStat
     const void *p[5] = { labels_out, label_frames, out_lengths, scores, enc };
     const size_t n[5] = { nl, nl, nb, nb, ne };
     static const char *const name[5] = { "labels_out", "label_frames", "out_lengths", "scores", "enc" };
-    for (int i = 0; i < 5; ++i)
-        for (int j = i + 1; j < 5; ++j)
-            if (dec_overlap(p[i], n[i], p[j], n[j])) {
-                char msg[240];
-                snprintf(msg, sizeof msg, "%s: %s overlaps %s", who, name[i], name[j]);
-                nntk_set_error(msg);
-                return -1;
-            }
-    return 0;
+    return dec_check_overlaps(who, 5, 5, p, n, name);
+}
+
+/* the decoder as the launchers take it */
+static nntk_shim_rnnt_dec dec_model(NntkRnntDecoder d) {
+    return (nntk_shim_rnnt_dec){ d->d_table, d->d_U, d->d_proj, d->d_out, d->cfg.V, d->cfg.blank, d->cfg.E, d->cfg.H, d->cfg.J,
+                                 d->cfg.joint_activation, d->cfg.max_symbols_per_frame };
+}
+
+/* every row's frame count, n_frames NULL: T; the caller frees it.  NULL: out of host memory, oom the error */
+static int *dec_row_frames(const char *oom, const int *n_frames, int batch, int T) {
+    int *len = (int *)malloc((size_t)batch * sizeof(int));
+    if (!len) { nntk_set_error(oom); return NULL; }
+    for (int b = 0; b < batch; ++b) len[b] = n_frames ? n_frames[b] : T;
+    return len;
 }
 
 int nntk_rnnt_greedy_decode_device(NntkRnntDecoder d, NntkRnntDecodeState state, const float *d_enc, int batch, int T, const int *n_frames,
@@ -201,11 +225,9 @@ int nntk_rnnt_greedy_decode_device(NntkRnntDecoder d, NntkRnntDecodeState state,
     nntk_shim_clear_error();
     if (dec_check_call(who, d, state, d_enc, batch, T, n_frames, max_labels, d_labels_out, d_label_frames, d_out_lengths, d_scores)) return -1;
     if (batch == 0) return 0;
-    int *len = (int *)malloc((size_t)batch * sizeof(int));
-    if (!len) NNTK_FAIL("nntk_rnnt_greedy_decode_device: out of host memory");
-    for (int b = 0; b < batch; ++b) len[b] = n_frames ? n_frames[b] : T;
-    const nntk_shim_rnnt_dec m = { d->d_table, d->d_U, d->d_proj, d->d_out, d->cfg.V, d->cfg.blank, d->cfg.E, d->cfg.H, d->cfg.J,
-                                   d->cfg.joint_activation, d->cfg.max_symbols_per_frame };
+    const nntk_shim_rnnt_dec m = dec_model(d);
+    int *len = dec_row_frames("nntk_rnnt_greedy_decode_device: out of host memory", n_frames, batch, T);
+    if (!len) return -1;
     int rc = nntk_shim_rnnt_greedy(&m, d_enc, batch, T, len, max_labels, state ? state->d_f : NULL, state ? state->d_score : NULL,
                                    state ? state->d_i : NULL, d_labels_out, d_label_frames, d_out_lengths, d_scores);
     free(len);
@@ -258,25 +280,19 @@ static int beam_check_sizes(const char *who, NntkRnntDecoder d, int beam_width, 
     return 0;
 }
 
-size_t nntk_rnnt_beam_workspace_floats(NntkRnntDecoder d, int batch, int beam_width, int max_labels) {
-    if (!d || batch <= 0 || beam_width < 1 || beam_width > NNTK_RNNT_BEAM_MAX_W || max_labels < 1) return 0;
-    return nntk_shim_rnnt_beam_workspace_floats(batch, d->cfg.H, d->cfg.J, d->cfg.V, d->cfg.max_symbols_per_frame, beam_width, max_labels);
+static int beam_sizes_ok(NntkRnntDecoder d, int batch, int beam_width, int max_labels) {
+    return d && batch > 0 && beam_width >= 1 && beam_width <= NNTK_RNNT_BEAM_MAX_W && max_labels >= 1;
 }
 
-size_t nntk_rnnt_beam_state_bytes(NntkRnntDecoder d, int batch, int beam_width, int max_labels) {
-    if (!d || batch <= 0 || beam_width < 1 || beam_width > NNTK_RNNT_BEAM_MAX_W || max_labels < 1) return 0;
-    const size_t per_hyp = sizeof(double) + (2 * (size_t)d->cfg.H + d->cfg.J) * sizeof(float) + ((size_t)max_labels + 2) * sizeof(int);
+/* the six public sizes: the bytes of a stream's state (state = 1) or the floats of a call's workspace; 0 where a call would be refused */
+static size_t beam_size(NntkRnntDecoder d, int batch, int beam_width, int max_labels, int with_lm, int with_detail, int state) {
+    if (!beam_sizes_ok(d, batch, beam_width, max_labels)) return 0;
+    if (!state)
+        return nntk_shim_rnnt_beam_workspace_floats(batch, d->cfg.H, d->cfg.J, d->cfg.V, d->cfg.max_symbols_per_frame, beam_width, max_labels,
+                                                    with_lm, with_detail);
+    const size_t per_hyp = sizeof(double) + (2 * (size_t)d->cfg.H + d->cfg.J) * sizeof(float) + ((size_t)max_labels + 2) * sizeof(int) +
+                           (with_lm ? sizeof(int) : 0) + (with_detail ? max_labels * (sizeof(int) + sizeof(float)) : 0);
     return (size_t)batch * (beam_width * per_hyp + 5 * sizeof(int));
-}
-
-size_t nntk_rnnt_beam_lm_workspace_floats(NntkRnntDecoder d, int batch, int beam_width, int max_labels) {
-    if (!d || batch <= 0 || beam_width < 1 || beam_width > NNTK_RNNT_BEAM_MAX_W || max_labels < 1) return 0;
-    return nntk_shim_rnnt_beam_lm_workspace_floats(batch, d->cfg.H, d->cfg.J, d->cfg.V, d->cfg.max_symbols_per_frame, beam_width, max_labels);
-}
-
-size_t nntk_rnnt_beam_state_bytes_lm(NntkRnntDecoder d, int batch, int beam_width, int max_labels) {
-    const size_t acoustic = nntk_rnnt_beam_state_bytes(d, batch, beam_width, max_labels);
-    return acoustic ? acoustic + (size_t)batch * beam_width * sizeof(int) : 0;
 }
 
 static int beam_opt_detail(const NntkRnntBeamOptions *o) { return o && (o->label_frames || o->label_logps); }
@@ -284,16 +300,24 @@ static int beam_opt_detail(const NntkRnntBeamOptions *o) { return o && (o->label
 /* the kernels with detail also rank the report, so length normalisation alone takes them and their workspace */
 static int beam_opt_kernel(const NntkRnntBeamOptions *o) { return beam_opt_detail(o) || (o && o->length_norm); }
 
+size_t nntk_rnnt_beam_workspace_floats(NntkRnntDecoder d, int batch, int beam_width, int max_labels) {
+    return beam_size(d, batch, beam_width, max_labels, 0, 0, 0);
+}
+size_t nntk_rnnt_beam_lm_workspace_floats(NntkRnntDecoder d, int batch, int beam_width, int max_labels) {
+    return beam_size(d, batch, beam_width, max_labels, 1, 0, 0);
+}
 size_t nntk_rnnt_beam_opt_workspace_floats(NntkRnntDecoder d, int batch, int beam_width, int max_labels, const NntkRnntBeamOptions *o) {
-    if (!d || batch <= 0 || beam_width < 1 || beam_width > NNTK_RNNT_BEAM_MAX_W || max_labels < 1) return 0;
-    return nntk_shim_rnnt_beam_opt_workspace_floats(batch, d->cfg.H, d->cfg.J, d->cfg.V, d->cfg.max_symbols_per_frame, beam_width, max_labels,
-                                                    o && o->lm, beam_opt_kernel(o));
+    return beam_size(d, batch, beam_width, max_labels, o && o->lm, beam_opt_kernel(o), 0);
 }
 
+size_t nntk_rnnt_beam_state_bytes(NntkRnntDecoder d, int batch, int beam_width, int max_labels) {
+    return beam_size(d, batch, beam_width, max_labels, 0, 0, 1);
+}
+size_t nntk_rnnt_beam_state_bytes_lm(NntkRnntDecoder d, int batch, int beam_width, int max_labels) {
+    return beam_size(d, batch, beam_width, max_labels, 1, 0, 1);
+}
 size_t nntk_rnnt_beam_state_bytes_opt(NntkRnntDecoder d, int batch, int beam_width, int max_labels, int with_lm, int with_detail) {
-    const size_t base = with_lm ? nntk_rnnt_beam_state_bytes_lm(d, batch, beam_width, max_labels)
-                                : nntk_rnnt_beam_state_bytes(d, batch, beam_width, max_labels);
-    return base && with_detail ? base + (size_t)batch * beam_width * max_labels * (sizeof(int) + sizeof(float)) : base;
+    return beam_size(d, batch, beam_width, max_labels, with_lm, with_detail, 1);
 }
 
 static int beam_check_lm(const char *who, NntkRnntDecoder d, NntkNgramLm lm) {
@@ -340,18 +364,7 @@ NntkRnntBeamState nntk_rnnt_beam_state_create_opt(NntkRnntDecoder d, int batch, 
 }
 
 int nntk_rnnt_beam_state_reset(NntkRnntBeamState s, const int *rows, int n_rows) {
-    static const char who[] = "nntk_rnnt_beam_state_reset";
-    nntk_shim_clear_error();
-    if (!s) return dec_fail(who, "NULL state", 0, 0, 0);
-    if (n_rows < 0 || n_rows > s->batch) return dec_fail(who, "n_rows %ld is outside [0, %ld]", n_rows, s->batch, 0);
-    if (!rows && n_rows > 0) return dec_fail(who, "rows is NULL with n_rows %ld", n_rows, 0, 0);
-    if (!rows) return nntk_shim_memset(s->d.i, 0, (size_t)s->batch * 4 * sizeof(int));
-    for (int i = 0; i < n_rows; ++i)
-        if (rows[i] < 0 || rows[i] >= s->batch) return dec_fail(who, "rows[%ld] = %ld is outside [0, %ld)", i, rows[i], s->batch);
-    if (n_rows == 0) return 0;
-    int *d_rows = s->d.i + 4 * (size_t)s->batch;
-    if (nntk_shim_upload_ints(d_rows, rows, n_rows)) return -1;
-    return nntk_shim_rnnt_dec_reset(s->d.i, d_rows, n_rows);      /* the started word of a row, as in the greedy state */
+    return dec_state_reset("nntk_rnnt_beam_state_reset", s ? s->batch : 0, s ? s->d.i : NULL, rows, n_rows);
 }
 
 void nntk_rnnt_beam_state_destroy(NntkRnntBeamState s) {
@@ -403,28 +416,15 @@ static int beam_check_call(const char *who, NntkRnntDecoder d, NntkRnntBeamState
         dec_named_ptr(who, "scores", scores)) return -1;
     if (o && o->label_frames && dec_named_ptr(who, "label_frames", o->label_frames)) return -1;
     if (o && o->label_logps && dec_named_ptr(who, "label_logps", o->label_logps)) return -1;
-    if (device_form) {
-        char msg[240];
-        if (!ws || ((uintptr_t)ws & 15)) {
-            snprintf(msg, sizeof msg, ws ? "%s: workspace is not 16-byte aligned" : "%s: workspace is NULL", who);
-            nntk_set_error(msg);
-            return -1;
-        }
-    }
+    if (device_form && (!ws || ((uintptr_t)ws & 15)))
+        return dec_fail(who, ws ? "workspace is not 16-byte aligned" : "workspace is NULL", 0, 0, 0);
     const size_t nh = (size_t)batch * nbest;
     const void *p[7] = { labels_out, out_lengths, scores, o ? o->label_frames : NULL, o ? o->label_logps : NULL, enc, ws };
     const size_t n[7] = { nh * max_labels * sizeof(int), nh * sizeof(int), nh * sizeof(float), nh * max_labels * sizeof(int),
                           nh * max_labels * sizeof(float), (size_t)batch * T * d->cfg.J * sizeof(float),
                           !device_form ? 0 : nntk_rnnt_beam_opt_workspace_floats(d, batch, beam_width, max_labels, o) * sizeof(float) };
     static const char *const name[7] = { "labels_out", "out_lengths", "scores", "label_frames", "label_logps", "enc", "workspace" };
-    for (int i = 0; i < 5; ++i)
-        for (int j = i + 1; j < 7; ++j)
-            if (dec_overlap(p[i], n[i], p[j], n[j])) {
-                char msg[240];
-                snprintf(msg, sizeof msg, "%s: %s overlaps %s", who, name[i], name[j]);
-                nntk_set_error(msg);
-                return -1;
-            }
+    if (dec_check_overlaps(who, 5, 7, p, n, name)) return -1;
     if (!nntk_shim_rnnt_beam_fits(d->cfg.H, d->cfg.J, d->cfg.V))
         return dec_fail(who, "the model (H %ld, J %ld, V %ld) is beyond the beam kernel's LDS", d->cfg.H, d->cfg.J, d->cfg.V);
     return 0;
@@ -440,16 +440,14 @@ static int beam_decode_device(const char *who, NntkRnntDecoder d, NntkRnntBeamSt
     NntkNgramLm lm = o ? o->lm : NULL;
     nntk_shim_rnnt_lm tab;
     if (lm && nntk_ngram_lm_rnnt_device(lm, &tab)) return -1;
-    int *len = (int *)malloc((size_t)batch * sizeof(int));
-    if (!len) NNTK_FAIL("nntk_rnnt_beam_decode_device: out of host memory");
-    for (int b = 0; b < batch; ++b) len[b] = n_frames ? n_frames[b] : T;
-    const nntk_shim_rnnt_dec m = { d->d_table, d->d_U, d->d_proj, d->d_out, d->cfg.V, d->cfg.blank, d->cfg.E, d->cfg.H, d->cfg.J,
-                                   d->cfg.joint_activation, d->cfg.max_symbols_per_frame };
+    int *len = dec_row_frames("nntk_rnnt_beam_decode_device: out of host memory", n_frames, batch, T);
+    if (!len) return -1;
+    const nntk_shim_rnnt_dec m = dec_model(d);
     const nntk_shim_rnnt_beam_detail dt = { o ? o->label_frames : NULL, o ? o->label_logps : NULL, state ? state->d_fr : NULL,
                                             state ? state->d_lp : NULL, o ? o->length_norm : 0 };
-    int rc = nntk_shim_rnnt_beam_opt(&m, d_enc, batch, T, len, beam_width, nbest, max_labels, state ? &state->d : NULL, lm ? &tab : NULL,
-                                     state && lm ? state->d_q : NULL, beam_opt_kernel(o) ? &dt : NULL, d_labels_out, d_out_lengths, d_scores,
-                                     d_workspace);
+    int rc = nntk_shim_rnnt_beam(&m, d_enc, batch, T, len, beam_width, nbest, max_labels, state ? &state->d : NULL, lm ? &tab : NULL,
+                                 state && lm ? state->d_q : NULL, beam_opt_kernel(o) ? &dt : NULL, d_labels_out, d_out_lengths, d_scores,
+                                 d_workspace);
     free(len);
     return rc;
 }

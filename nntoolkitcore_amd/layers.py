@@ -1163,6 +1163,31 @@ def _ipv(t):
     return C.c_void_p(t.data_ptr())
 
 
+def _n_frames_ptr(n_frames, B):
+    """n_frames as the decode entries take it: a host int pointer (it keeps the array alive), None for None"""
+    return None if n_frames is None else _host_ints(n_frames, B, "n_frames").ctypes.data_as(capi.ip)
+
+
+def _rnnt_beam_entry(name, lm, opt, head, lm_args, opt_args, tail=()):
+    """The one place that picks among the three C forms of a transducer beam entry -- plain, ``_lm``, ``_opt`` -- for the workspace
+    size, the state, and the device and host calls.  name has ``{}`` where the forms' names differ; opt: the call takes the ``_opt``
+    form (detail or length_norm; for the state, detail), else a model alone takes the ``_lm`` form.  -> (result, the entry's name)"""
+    form, mid = ("_opt", opt_args) if opt else ("", ()) if lm is None else ("_lm", lm_args)
+    name = name.format(form)
+    return getattr(capi.load(), name)(*head, *mid, *tail), name
+
+
+def _rnnt_beam_options(lm, length_norm, frames, logps):
+    """NntkRnntBeamOptions by reference; frames, logps: addresses or None"""
+    return C.byref(capi.NntkRnntBeamOptions(lm.h if lm is not None else None, int(bool(length_norm)), frames, logps))
+
+
+def _rnnt_state_reset(entry, h, rows):
+    """these rows (None: every row) of a greedy or beam stream start anew"""
+    rows = None if rows is None else np.ascontiguousarray(np.asarray(rows, dtype=np.int32).reshape(-1))
+    check(getattr(capi.load(), entry)(h, *((None, 0) if rows is None else (rows.ctypes.data_as(capi.ip), rows.shape[0]))), entry)
+
+
 class RnntDecoder:
     """``nntk_rnnt_decoder_*``: greedy transducer decoding with the prediction network inside the search (INTEGRATION.md
     "RNN-Transducer: greedy decoding").  Device tensors in the library's layouts: embed [V, E]; lstm_block, the flat ``LSTMGetWeights``
@@ -1203,10 +1228,9 @@ class RnntDecoder:
     def _decode(self, state, enc, n_frames, max_labels, outs):
         B, T, J = enc.shape
         assert J == self.J, "enc: [B, T, J]"
-        nf = None if n_frames is None else _host_ints(n_frames, B, "n_frames")
         labels, frames, lengths, scores = outs
-        check(capi.load().nntk_rnnt_greedy_decode_device(self.h, state, _dp(enc), B, T, nf.ctypes.data_as(capi.ip) if nf is not None else None,
-                                                         int(max_labels), _ipv(labels), _ipv(frames), _ipv(lengths), _dp(scores)),
+        check(capi.load().nntk_rnnt_greedy_decode_device(self.h, state, _dp(enc), B, T, _n_frames_ptr(n_frames, B), int(max_labels),
+                                                         _ipv(labels), _ipv(frames), _ipv(lengths), _dp(scores)),
               "nntk_rnnt_greedy_decode_device")
         return outs
 
@@ -1231,31 +1255,23 @@ class RnntDecoder:
 
     def _beam_workspace(self, device, B, beam_width, max_labels, lm=None, detail=False, length_norm=False):
         import torch
-        if detail or length_norm:                                   # the size depends on whether the pointers are set, not on where they point
-            o = capi.NntkRnntBeamOptions(lm.h if lm is not None else None, int(bool(length_norm)), 4 if detail else None, 4 if detail else None)
-            need = capi.load().nntk_rnnt_beam_opt_workspace_floats(self.h, B, int(beam_width), int(max_labels), C.byref(o))
-        else:
-            size = capi.load().nntk_rnnt_beam_workspace_floats if lm is None else capi.load().nntk_rnnt_beam_lm_workspace_floats
-            need = size(self.h, B, int(beam_width), int(max_labels))
+        given = 4 if detail else None                               # the size depends on whether the pointers are set, not on where they point
+        need, _ = _rnnt_beam_entry("nntk_rnnt_beam{}_workspace_floats", lm, detail or length_norm, (self.h, B, int(beam_width), int(max_labels)),
+                                   (), (_rnnt_beam_options(lm, length_norm, given, given),))
         return torch.empty(max(int(need), 4), dtype=torch.float32, device=device)
 
     def _beam(self, state, enc, n_frames, beam_width, nbest, max_labels, outs, workspace, lm=None, length_norm=False):
         """outs: (labels, lengths, scores), or with detail (labels, lengths, scores, label_frames, label_logps)"""
         B, T, J = enc.shape
         assert J == self.J, "enc: [B, T, J]"
-        nf = None if n_frames is None else _host_ints(n_frames, B, "n_frames")
         labels, lengths, scores = outs[:3]
-        head = (self.h, state, _dp(enc), B, T, nf.ctypes.data_as(capi.ip) if nf is not None else None, int(beam_width), int(nbest),
-                int(max_labels))
-        tail = (_ipv(labels), _ipv(lengths), _dp(scores), _dp(workspace))
-        if len(outs) > 3 or length_norm:
-            o = capi.NntkRnntBeamOptions(lm.h if lm is not None else None, int(bool(length_norm)),
-                                         outs[3].data_ptr() if len(outs) > 3 else None, outs[4].data_ptr() if len(outs) > 3 else None)
-            check(capi.load().nntk_rnnt_beam_decode_opt_device(*head, C.byref(o), *tail), "nntk_rnnt_beam_decode_opt_device")
-        elif lm is None:
-            check(capi.load().nntk_rnnt_beam_decode_device(*head, *tail), "nntk_rnnt_beam_decode_device")
-        else:
-            check(capi.load().nntk_rnnt_beam_decode_lm_device(*head, lm.h, *tail), "nntk_rnnt_beam_decode_lm_device")
+        detail = len(outs) > 3
+        check(*_rnnt_beam_entry("nntk_rnnt_beam_decode{}_device", lm, detail or length_norm,
+                                (self.h, state, _dp(enc), B, T, _n_frames_ptr(n_frames, B), int(beam_width), int(nbest), int(max_labels)),
+                                (lm.h if lm is not None else None,),
+                                (_rnnt_beam_options(lm, length_norm, outs[3].data_ptr() if detail else None,
+                                                    outs[4].data_ptr() if detail else None),),
+                                (_ipv(labels), _ipv(lengths), _dp(scores), _dp(workspace))))
         return outs
 
     def beam_decode(self, enc, n_frames=None, beam_width=8, nbest=1, max_labels=None, lm=None, detail=False, length_norm=False):
@@ -1309,11 +1325,7 @@ class RnntGreedyStream:
 
     def reset(self, rows=None):
         """these rows (None: every row) start new streams"""
-        if rows is None:
-            check(capi.load().nntk_rnnt_decode_state_reset(self.h, None, 0), "nntk_rnnt_decode_state_reset")
-            return
-        rows = np.ascontiguousarray(np.asarray(rows, dtype=np.int32).reshape(-1))
-        check(capi.load().nntk_rnnt_decode_state_reset(self.h, rows.ctypes.data_as(capi.ip), rows.shape[0]), "nntk_rnnt_decode_state_reset")
+        _rnnt_state_reset("nntk_rnnt_decode_state_reset", self.h, rows)
 
     def close(self):
         if self.h:
@@ -1339,12 +1351,8 @@ class RnntBeamStream:
         self.dec, self.B, self.W, self.nbest, self.max_labels = decoder, int(batch), int(beam_width), int(nbest), int(max_labels)
         self.outs = self.ws = None
         self.lm, self.detail, self.length_norm = lm, bool(detail), bool(length_norm)
-        if detail:
-            self.h = capi.load().nntk_rnnt_beam_state_create_opt(decoder.h, self.B, self.W, self.max_labels, lm.h if lm is not None else None, 1)
-        elif lm is None:
-            self.h = capi.load().nntk_rnnt_beam_state_create(decoder.h, self.B, self.W, self.max_labels)
-        else:
-            self.h = capi.load().nntk_rnnt_beam_state_create_lm(decoder.h, self.B, self.W, self.max_labels, lm.h)
+        lm_h = lm.h if lm is not None else None
+        self.h, _ = _rnnt_beam_entry("nntk_rnnt_beam_state_create{}", lm, detail, (decoder.h, self.B, self.W, self.max_labels), (lm_h,), (lm_h, 1))
         if not self.h:
             raise capi.NNTKError("nntk_rnnt_beam_state_create: " + capi.last_error())
 
@@ -1362,11 +1370,7 @@ class RnntBeamStream:
 
     def reset(self, rows=None):
         """these rows (None: every row) start new streams"""
-        if rows is None:
-            check(capi.load().nntk_rnnt_beam_state_reset(self.h, None, 0), "nntk_rnnt_beam_state_reset")
-            return
-        rows = np.ascontiguousarray(np.asarray(rows, dtype=np.int32).reshape(-1))
-        check(capi.load().nntk_rnnt_beam_state_reset(self.h, rows.ctypes.data_as(capi.ip), rows.shape[0]), "nntk_rnnt_beam_state_reset")
+        _rnnt_state_reset("nntk_rnnt_beam_state_reset", self.h, rows)
 
     def close(self):
         if self.h:
@@ -1380,35 +1384,35 @@ class RnntBeamStream:
             pass
 
 
+def _rnnt_host_decoder(embed, lstm_block, pred_proj, out, enc, max_labels, blank, joint_activation, max_symbols_per_frame):
+    """the preamble of the numpy decode calls: the weights uploaded into a decoder of their own -> (decoder, enc as float32, B, T,
+    max_labels with its default)"""
+    import torch
+    dev = lambda a: None if a is None else torch.from_numpy(_f32(a).reshape(-1) if a is not embed else _f32(a)).cuda()
+    dec = RnntDecoder(dev(embed), dev(lstm_block), dev(pred_proj), dev(out), blank, joint_activation, max_symbols_per_frame)
+    enc = _f32(enc)
+    B, T, _ = enc.shape
+    return dec, enc, B, T, max(1, dec.max_symbols * T) if max_labels is None else max_labels
+
+
 def rnnt_beam_decode(embed, lstm_block, pred_proj, out, enc, n_frames=None, beam_width=8, nbest=1, max_labels=None, blank=0,
                      joint_activation=ACT_TANH, max_symbols_per_frame=10, lm=None, detail=False, length_norm=False):
     """Transducer beam search on numpy arrays (the weights go to the device, ``nntk_rnnt_beam_decode`` takes enc and the results as
     host memory): enc [B, T, J] -> (labels [B, nbest, max_labels], lengths [B, nbest], scores [B, nbest]).  lm: an NgramLm fused into
     the search (``nntk_rnnt_beam_decode_lm``), or None.  detail, length_norm: as in ``RnntDecoder.beam_decode``
     (``nntk_rnnt_beam_decode_opt``; with detail label_frames and label_logps follow the scores)."""
-    import torch
-    dev = lambda a: None if a is None else torch.from_numpy(_f32(a).reshape(-1) if a is not embed else _f32(a)).cuda()
-    dec = RnntDecoder(dev(embed), dev(lstm_block), dev(pred_proj), dev(out), blank, joint_activation, max_symbols_per_frame)
-    enc = _f32(enc)
-    B, T, _ = enc.shape
-    if max_labels is None:
-        max_labels = max(1, dec.max_symbols * T)
-    nf = None if n_frames is None else _host_ints(n_frames, B, "n_frames")
+    dec, enc, B, T, max_labels = _rnnt_host_decoder(embed, lstm_block, pred_proj, out, enc, max_labels, blank, joint_activation,
+                                                    max_symbols_per_frame)
     labels = np.empty((B, nbest, max_labels), np.int32)
     lengths, scores = np.empty((B, nbest), np.int32), np.empty((B, nbest), np.float32)
+    frames, logps = (np.empty(labels.shape, np.int32), np.empty(labels.shape, np.float32)) if detail else (None, None)
     try:
-        head = (dec.h, None, _p(enc), B, T, nf.ctypes.data_as(capi.ip) if nf is not None else None, int(beam_width), int(nbest),
-                int(max_labels))
-        tail = (labels.ctypes.data_as(capi.ip), lengths.ctypes.data_as(capi.ip), _p(scores))
-        if detail or length_norm:
-            frames, logps = np.empty((B, nbest, max_labels), np.int32), np.empty((B, nbest, max_labels), np.float32)
-            o = capi.NntkRnntBeamOptions(lm.h if lm is not None else None, int(bool(length_norm)), frames.ctypes.data if detail else None,
-                                         logps.ctypes.data if detail else None)
-            check(capi.load().nntk_rnnt_beam_decode_opt(*head, C.byref(o), *tail), "nntk_rnnt_beam_decode_opt")
-        elif lm is None:
-            check(capi.load().nntk_rnnt_beam_decode(*head, *tail), "nntk_rnnt_beam_decode")
-        else:
-            check(capi.load().nntk_rnnt_beam_decode_lm(*head, lm.h, *tail), "nntk_rnnt_beam_decode_lm")
+        check(*_rnnt_beam_entry("nntk_rnnt_beam_decode{}", lm, detail or length_norm,
+                                (dec.h, None, _p(enc), B, T, _n_frames_ptr(n_frames, B), int(beam_width), int(nbest), int(max_labels)),
+                                (lm.h if lm is not None else None,),
+                                (_rnnt_beam_options(lm, length_norm, frames.ctypes.data if detail else None,
+                                                    logps.ctypes.data if detail else None),),
+                                (labels.ctypes.data_as(capi.ip), lengths.ctypes.data_as(capi.ip), _p(scores))))
     finally:
         dec.destroy()
     return (labels, lengths, scores, frames, logps) if detail else (labels, lengths, scores)
@@ -1418,19 +1422,13 @@ def rnnt_greedy_decode(embed, lstm_block, pred_proj, out, enc, n_frames=None, ma
                        max_symbols_per_frame=10):
     """Greedy transducer decoding on numpy arrays (the weights go to the device, ``nntk_rnnt_greedy_decode`` takes enc and the results
     as host memory): enc [B, T, J] -> (labels [B, max_labels], label_frames, lengths [B], scores [B])"""
-    import torch
-    dev = lambda a: None if a is None else torch.from_numpy(_f32(a).reshape(-1) if a is not embed else _f32(a)).cuda()
-    dec = RnntDecoder(dev(embed), dev(lstm_block), dev(pred_proj), dev(out), blank, joint_activation, max_symbols_per_frame)
-    enc = _f32(enc)
-    B, T, _ = enc.shape
-    if max_labels is None:
-        max_labels = max(1, dec.max_symbols * T)
-    nf = None if n_frames is None else _host_ints(n_frames, B, "n_frames")
+    dec, enc, B, T, max_labels = _rnnt_host_decoder(embed, lstm_block, pred_proj, out, enc, max_labels, blank, joint_activation,
+                                                    max_symbols_per_frame)
     labels, frames = np.empty((B, max_labels), np.int32), np.empty((B, max_labels), np.int32)
     lengths, scores = np.empty(B, np.int32), np.empty(B, np.float32)
     try:
-        check(capi.load().nntk_rnnt_greedy_decode(dec.h, None, _p(enc), B, T, nf.ctypes.data_as(capi.ip) if nf is not None else None,
-                                                  int(max_labels), labels.ctypes.data_as(capi.ip), frames.ctypes.data_as(capi.ip),
+        check(capi.load().nntk_rnnt_greedy_decode(dec.h, None, _p(enc), B, T, _n_frames_ptr(n_frames, B), int(max_labels),
+                                                  labels.ctypes.data_as(capi.ip), frames.ctypes.data_as(capi.ip),
                                                   lengths.ctypes.data_as(capi.ip), _p(scores)), "nntk_rnnt_greedy_decode")
     finally:
         dec.destroy()

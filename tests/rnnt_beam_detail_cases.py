@@ -1,7 +1,7 @@
 """The cases of the transducer beam search's label timestamps, confidences and length normalisation (tests/test_gpu_rnnt_beam_detail.py)
-and their premises, which tests/test_rnnt_beam_detail_host.py checks without a device: the geometries of tests/test_gpu_rnnt_beam.py,
-tests/rnnt_wide_cases.py (b4) and tests/rnnt_beam_lm_cases.py, the float64 reference (tests/rnnt_beam_detail_reference.py) and its
-float32 restatement.  A helper, no test.
+and their premises, which tests/test_rnnt_beam_detail_host.py checks without a device: the geometries of tests/rnnt_beam_cases.py,
+tests/rnnt_wide_cases.py (b4) and tests/rnnt_beam_lm_cases.py, the float64 reference (tests/rnnt_beam_reference.py) and its float32
+restatement.  A helper, no test.
 
 Where a geometry's existing seed does not give the premises (a gap below GAP at a merge's lead or between the keys, no switch, no
 reordering), the case takes the same geometry with another seed, searched on the CPU alone; nothing about a seed comes from a device."""
@@ -9,12 +9,10 @@ import functools
 
 import numpy as np
 
-import rnnt_beam_detail_reference as RD
 import rnnt_beam_lm_cases as LC
-import rnnt_beam_lm_reference as RL
 import rnnt_beam_reference as RB
 import rnnt_wide_cases as WC
-from test_gpu_rnnt_beam import _case as acoustic_case, _ml, _model
+from rnnt_beam_cases import case as acoustic_case, model as _model, search_kw
 
 GAP = 1e-3
 
@@ -38,7 +36,7 @@ GAP_CASES = tuple(nm for nm in CASES if nm != "tie")
 ALL_CASES = tuple(CASES)
 NORM_CASES = tuple(nm for nm, v in CASES.items() if v[3])
 STREAM_CASES = ("stream", "lm_stream", "norm", "lm_norm")
-SEEDS = {"norm": 2, "lm_norm": 0}       # norm: the stream case of test_gpu_rnnt_beam.py itself
+SEEDS = {"norm": 2, "lm_norm": 0}       # norm: the stream case of rnnt_beam_cases.py itself
 
 
 def case(name):
@@ -72,19 +70,13 @@ def length_norm(name):
     return CASES[name][3]
 
 
-def search_kw(c):
-    m = c["m"]
-    return dict(n_frames=c["n"], blank=m["blank"], activation=c["act"], max_symbols_per_frame=c["ms"], beam_width=c["W"], nbest=c["nbest"],
-                max_labels=_ml(c))
-
-
 def run(name, dtype=np.float64, **over):
     c = case(name)
     m = c["m"]
     t = lm_table(name)
     kw = dict(search_kw(c), length_norm=length_norm(name), dtype=dtype)
     kw.update(over)
-    return RD.beam_decode(m["embed"], m["lstm"], m["proj"], m["out"], c["enc"], RD.Lm(*t) if t else None, **kw)
+    return RB.beam_decode(m["embed"], m["lstm"], m["proj"], m["out"], c["enc"], lm=RB.Lm(*t) if t else None, **kw)
 
 
 @functools.lru_cache(maxsize=None)
@@ -94,14 +86,8 @@ def reference(name):
 
 
 @functools.lru_cache(maxsize=None)
-def plain_reference(name):
-    """the search without the additions, from the modules the reference is built on"""
-    c = case(name)
-    m = c["m"]
-    t = lm_table(name)
-    if t:
-        return RL.beam_decode(m["embed"], m["lstm"], m["proj"], m["out"], c["enc"], RL.Lm(*t), **search_kw(c))
-    return RB.beam_decode(m["embed"], m["lstm"], m["proj"], m["out"], c["enc"], **search_kw(c))
+def unranked_labels(name):
+    return run(name, length_norm=False)["labels"]
 
 
 def lps_f32_error(name):
@@ -145,12 +131,8 @@ def assert_premise(name):
     print("%s: cut gap %.3e, order gap %.3e, lead gap %.3e, key gap %.3e; merges %s, switches %s, reordered %s; labels %s frames %s" % (
         name, mn("cut_gap"), mn("order_gap"), mn("lead_gap"), mn("key_gap"), r64["merges"], r64["lead_switches"], r64["reordered"],
         r64["labels"], r64["frames"]))
-    plain = plain_reference(name)
-    if not length_norm(name):                       # the additions change nothing: the modules underneath report the same
-        assert r64["labels"] == plain["labels"], name
-        assert all(float(x) == float(y) for a, b in zip(r64["scores"], plain["scores"]) for x, y in zip(a, b)), name
-    else:
-        assert r64["plain_labels"] == plain["labels"], name
+    if length_norm(name):                           # the ranking alone differs: the same search without it reports plain_labels
+        assert r64["plain_labels"] == unranked_labels(name), name
     if name == "tie":                               # exact ties by construction; whatever is no exact tie keeps its distance
         assert r64["lead_ties"].sum() > 0 and mn("lead_gap_nonzero") >= GAP, (name, r64["lead_ties"], mn("lead_gap_nonzero"))
     else:

@@ -1,6 +1,6 @@
 """The cases of the fused transducer beam search tests (tests/test_gpu_rnnt_beam_lm.py) and their premises, which
-tests/test_rnnt_beam_lm_host.py checks without a device: the acoustic models and frames of tests/test_gpu_rnnt_beam.py, the n-gram tables
-of tests/test_gpu_ctc_beam_lm.py's recipe, the float64 reference (tests/rnnt_beam_lm_reference.py) and its float32 restatement.
+tests/test_rnnt_beam_lm_host.py checks without a device: the acoustic models and frames of tests/rnnt_beam_cases.py, the n-gram tables of
+tests/test_gpu_ctc_beam_lm.py's recipe, the float64 reference (tests/rnnt_beam_reference.py with a model) and its float32 restatement.
 A helper, no test.
 
 alpha is a power of two in every case, so that alpha * v + beta is one rounding whatever the host compiler contracts, and beta is a
@@ -10,10 +10,9 @@ import functools
 
 import numpy as np
 
-import rnnt_beam_lm_reference as RL
 import rnnt_beam_reference as RB
+from rnnt_beam_cases import case as acoustic_case, model as _model, search_kw  # noqa: F401  (search_kw: the host tests take it from here)
 from test_gpu_ctc_beam_lm import _table, dense_bigram, sparse_trigram
-from test_gpu_rnnt_beam import _case as acoustic_case, _ml, _model
 
 GAP = 1e-3
 
@@ -79,21 +78,15 @@ def case(name):
     raise KeyError(name)
 
 
-def search_kw(c):
-    m = c["m"]
-    return dict(n_frames=c["n"], blank=m["blank"], activation=c["act"], max_symbols_per_frame=c["ms"], beam_width=c["W"], nbest=c["nbest"],
-                max_labels=_ml(c))
-
-
 @functools.lru_cache(maxsize=None)
 def reference(name):
     """-> (float64 result, float32 restatement, the float64 run's Lm with its counts)"""
     c = case(name)
     m = c["m"]
     t, alpha, beta = table(name)
-    lm64, lm32 = RL.Lm(t, alpha, beta), RL.Lm(t, alpha, beta)
-    r64 = RL.beam_decode(m["embed"], m["lstm"], m["proj"], m["out"], c["enc"], lm64, **search_kw(c))
-    r32 = RL.beam_decode(m["embed"], m["lstm"], m["proj"], m["out"], c["enc"], lm32, dtype=np.float32, **search_kw(c))
+    lm64, lm32 = RB.Lm(t, alpha, beta), RB.Lm(t, alpha, beta)
+    r64 = RB.beam_decode(m["embed"], m["lstm"], m["proj"], m["out"], c["enc"], lm=lm64, **search_kw(c))
+    r32 = RB.beam_decode(m["embed"], m["lstm"], m["proj"], m["out"], c["enc"], lm=lm32, dtype=np.float32, **search_kw(c))
     return r64, r32, lm64
 
 
@@ -105,7 +98,7 @@ def acoustic_reference(name):
 
 
 def _state_after(t, labels):
-    lm = RL.Lm(t)
+    lm = RB.Lm(t)
     s = lm.start
     for v in labels:
         s = lm.walk(s, v)[1]

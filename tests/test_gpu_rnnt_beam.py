@@ -3,159 +3,32 @@
 Labels and lengths are compared for EQUALITY with the float64 reference, so every case uses inputs on which the reference itself is
 unambiguous: its smallest gap at a top-W cut of C or B (cut_gap) and between consecutive scores of the first nbest + 1 final
 hypotheses (order_gap) are asserted to be at least GAP = 1e-3, and its float32 restatement must return the same labels
-(_assert_premise; the seeds were chosen on the CPU for that, nothing about them comes from a device).  The tie case is the exception
+(rnnt_beam_cases.assert_premise; the seeds were chosen on the CPU for that, nothing about them comes from a device).  The tie case is the exception
 by construction: exact ties, decided by the lower index in the reference and on the device.
 
-Score tolerance, from the CPU alone: 4 x the largest |float32 restatement - float64| score over every case of this file (_score_tol; 4
+Score tolerance, from the CPU alone: 4 x the largest |float32 restatement - float64| score over every case of tests/rnnt_beam_cases.py (score_tol; 4
 because the device's summation order differs).  Measured: largest float32 error 3.383e-6 (the stream case: scores around -5), so the
 tolerance is 1.353e-5; the device's largest error on these cases is 7.842e-7 (the awkward case), and 4.768e-7 against the device's own
 transducer loss in the exhaustive case; both are printed by every test that compares scores."""
 import ctypes as C
-import functools
 import itertools
 
 import numpy as np
 import pytest
 import torch
 
-import rnnt_beam_reference as RB
-import rnnt_decode_reference as R
 from nntoolkitcore_amd import capi, layers as NL
+from rnnt_beam_cases import assert_premise as _assert_premise, case as _case, ml as _ml, model as _model, reference as _reference, \
+    score_tol as _score_tol
+from rnnt_beam_device import assert_equals_reference, decoder as _decoder, host as _host, lattice_losses as _lattice_losses, same as _same, \
+    to_device as _t
 
 pytestmark = pytest.mark.gpu
-
-GAP = 1e-3
-
-
-def _model(seed, V, E, H, J, proj, blank=0, scale=2.0, out_scale=3.0, label_bias=0.0):
-    rng = np.random.default_rng(seed)
-    u = lambda sc, *s: rng.uniform(-sc, sc, s).astype(np.float32)
-    G = 4 * H
-    bias = u(0.1, V)
-    bias[np.arange(V) != blank] += np.float32(label_bias)
-    return dict(V=V, E=E, H=H, J=J, blank=blank, embed=u(1.0, V, E),
-                lstm=np.concatenate([u(scale * E ** -0.5, E * G), u(scale * H ** -0.5, H * G), u(0.1, G), u(0.1, G)]),
-                proj=np.concatenate([u(scale * H ** -0.5, H * J), u(0.1, J)]) if proj else None,
-                out=np.concatenate([u(out_scale * J ** -0.5, J * V), bias]), rng=rng)
-
-
-# seeds chosen on the CPU so that _assert_premise holds
-SEEDS = {"awkward": 0, "awkward_w3": 0, "awkward_w1": 15, "big_v": 0, "wide_identity": 0, "pruned": 3, "stream": 2}
-
-
-def _case(name):
-    """dict(m = the model, enc, n, act, ms = max_symbols_per_frame, W, nbest, max_labels)"""
-    if name in ("awkward", "awkward_w3", "awkward_w1", "pruned"):
-        # E 7, H 13, J 22 (none a multiple of 4), V 5, tanh, with the projection; batch 3, T 9, one row without frames
-        W, nbest, ms, ml = {"awkward": (8, 3, 3, None), "awkward_w3": (3, 2, 1, None), "awkward_w1": (1, 1, 3, None),
-                            "pruned": (3, 3, 3, 3)}[name]
-        m = _model(SEEDS[name], 5, 7, 13, 22, True, label_bias=-1.0 if name != "pruned" else 0.5)
-        return dict(m=m, enc=m["rng"].uniform(-1.5, 1.5, (3, 9, 22)).astype(np.float32), n=[9, 4, 0], act="tanh", ms=ms, W=W, nbest=nbest,
-                    max_labels=ml)
-    if name == "big_v":                              # more classes than lanes, no projection, relu
-        m = _model(SEEDS[name], 1030, 5, 16, 16, False, blank=1029, label_bias=-1.0)
-        return dict(m=m, enc=m["rng"].uniform(-1.5, 1.5, (2, 4, 16)).astype(np.float32), n=[4, 3], act="relu", ms=1, W=3, nbest=2,
-                    max_labels=None)
-    if name == "wide_identity":                      # more classes than a wavefront, no projection, identity
-        m = _model(SEEDS[name], 70, 5, 33, 33, False, blank=69, label_bias=-1.5)
-        return dict(m=m, enc=m["rng"].uniform(-1.5, 1.5, (2, 6, 33)).astype(np.float32), n=[6, 5], act="identity", ms=3, W=8, nbest=4,
-                    max_labels=None)
-    if name == "stream":                             # T 12
-        m = _model(SEEDS[name], 6, 5, 16, 16, False, blank=2, label_bias=-1.0)
-        return dict(m=m, enc=m["rng"].uniform(-1.5, 1.5, (3, 12, 16)).astype(np.float32), n=[12, 12, 7], act="tanh", ms=3, W=5, nbest=3,
-                    max_labels=12)
-    if name == "tie":                                # W_out = 0: the logits are the bias; labels 1 and 3 share it
-        m = _model(5, 5, 7, 13, 22, True, blank=0)
-        m["out"][:22 * 5] = 0.0
-        m["out"][22 * 5:] = np.float32([0.5, 0.25, -1.0, 0.25, -2.0])
-        return dict(m=m, enc=m["rng"].uniform(-1.5, 1.5, (2, 4, 22)).astype(np.float32), n=[4, 2], act="tanh", ms=2, W=3, nbest=3,
-                    max_labels=None)
-    raise KeyError(name)
-
-
-GAP_CASES = ("awkward", "awkward_w3", "awkward_w1", "big_v", "wide_identity", "pruned", "stream")
-ALL_CASES = GAP_CASES + ("tie",)
-
-
-def _ml(c):
-    return c["max_labels"] if c["max_labels"] is not None else max(1, c["ms"] * c["enc"].shape[1])
-
-
-@functools.lru_cache(maxsize=None)
-def _reference(name):
-    c = _case(name)
-    m = c["m"]
-    kw = dict(n_frames=c["n"], blank=m["blank"], activation=c["act"], max_symbols_per_frame=c["ms"], beam_width=c["W"], nbest=c["nbest"],
-              max_labels=_ml(c))
-    r64 = RB.beam_decode(m["embed"], m["lstm"], m["proj"], m["out"], c["enc"], **kw)
-    r32 = RB.beam_decode(m["embed"], m["lstm"], m["proj"], m["out"], c["enc"], dtype=np.float32, **kw)
-    return r64, r32
-
-
-def _f32_error(name):
-    r64, r32 = _reference(name)
-    return max([abs(float(x) - float(y)) for a, b in zip(r32["scores"], r64["scores"]) for x, y in zip(a, b)] + [0.0])
-
-
-@functools.lru_cache(maxsize=None)
-def _score_tol():
-    err = max(_f32_error(nm) for nm in ALL_CASES)
-    print("largest float32-restatement score error over the cases: %.3e -> tolerance %.3e" % (err, 4 * err))
-    assert err > 0
-    return 4 * err
-
-
-def _assert_premise(name):
-    r64, r32 = _reference(name)
-    c = _case(name)
-    live = [b for b, n in enumerate(c["n"]) if n > 0]
-    print("%s: cut gap %.3e, order gap %.3e; labels %s" % (name, min(r64["cut_gap"][b] for b in live),
-                                                          min(r64["order_gap"][b] for b in live), r64["labels"]))
-    assert min(r64["cut_gap"][b] for b in live) >= GAP and min(r64["order_gap"][b] for b in live) >= GAP, name
-    assert r32["labels"] == r64["labels"], name
-    assert any(len(y) > 0 for b in live for y in r64["labels"][b]), (name, "needs a label")
-
-
-def _t(gpu, a):
-    return None if a is None else torch.from_numpy(np.ascontiguousarray(a)).to(gpu)
-
-
-def _decoder(gpu, c):
-    m = c["m"]
-    return NL.RnntDecoder(_t(gpu, m["embed"]), _t(gpu, m["lstm"]), _t(gpu, m["proj"]), _t(gpu, m["out"]), blank=m["blank"],
-                          joint_activation=c["act"], max_symbols_per_frame=c["ms"])
-
-
-def _host(outs):
-    torch.cuda.synchronize()
-    return tuple(o.cpu().numpy() for o in outs)
 
 
 def _decode(gpu, dec, c, enc=None, n=None, W=None, nbest=None):
     return _host(dec.beam_decode(_t(gpu, c["enc"] if enc is None else enc), c["n"] if n is None else n, W or c["W"], nbest or c["nbest"],
                                  _ml(c)))
-
-
-def _same(x, y):
-    return all(np.array_equal(p.view(np.int32), q.view(np.int32)) for p, q in zip(x, y))
-
-
-def _assert_equals_reference(name, got, r64, nbest):
-    labels, lengths, scores = got
-    B = labels.shape[0]
-    worst = 0.0
-    for b in range(B):
-        have = len(r64["labels"][b])
-        for k in range(nbest):
-            if k < have:
-                y = r64["labels"][b][k]
-                assert lengths[b, k] == len(y) and labels[b, k, :len(y)].tolist() == y and (labels[b, k, len(y):] == -1).all(), \
-                    (name, b, k, labels[b, k], y)
-                worst = max(worst, abs(float(scores[b, k]) - float(r64["scores"][b][k])))
-            else:
-                assert lengths[b, k] == -1 and (labels[b, k] == -1).all() and scores[b, k] == -np.inf, (name, b, k)
-    print("%s: largest device score error %.3e (tolerance %.3e)" % (name, worst, _score_tol()))
-    assert worst <= _score_tol(), (name, worst, _score_tol())
 
 
 def _check(gpu, name):
@@ -164,42 +37,8 @@ def _check(gpu, name):
     dec = _decoder(gpu, c)
     got = _decode(gpu, dec, c)
     dec.destroy()
-    _assert_equals_reference(name, got, _reference(name)[0], c["nbest"])
+    assert_equals_reference(name, got, _reference(name)[0], c["nbest"], _score_tol)
     return c, got
-
-
-def _lattice_losses(gpu, c, pairs):
-    """the transducer loss of (row, labels) pairs, the logits built through the device training path"""
-    m = c["m"]
-    B, T, J = c["enc"].shape
-    V, E, H, blank = m["V"], m["E"], m["H"], m["blank"]
-    N = len(pairs)
-    U1 = max(len(y) for _, y in pairs) + 1
-    x = np.zeros((N, U1, E), np.float32)
-    for i, (_, y) in enumerate(pairs):
-        x[i] = m["embed"][[blank] + list(y) + [blank] * (U1 - 1 - len(y))]
-    lengths = np.array([len(y) for _, y in pairs], np.int32)
-    W, U, b_i, b_h = R.split_lstm(m["lstm"], E, H)
-    lstm = NL.LSTM(E, H, True, U1)
-    lstm.set_weights(W, U, b_i, b_h)
-    h = lstm.apply_device_varlen(_t(gpu, x), lengths=lengths + 1)
-    Wp, bp = R.split_dense(m["proj"], H, J)
-    tdd = NL.TimeDistributedDense(U1, H, J)
-    tdd.set_weights(Wp, bp)
-    pred = tdd.apply_device(h)
-    enc = _t(gpu, np.stack([c["enc"][b] for b, _ in pairs]))
-    joint = NL.rnnt_joint_device(enc, pred, c["act"])
-    Wo, bo = R.split_dense(m["out"], J, V)
-    voc = NL.TimeDistributedDense(T * U1, J, V)
-    voc.set_weights(Wo, bo)
-    logits = voc.apply_device(joint.reshape(N, T * U1, J)).reshape(N, T, U1, V)
-    loss, _ = NL.rnnt_loss_device(logits, [list(y) for _, y in pairs], input_lengths=[c["n"][b] for b, _ in pairs], blank=blank,
-                                  want_grad=False)
-    torch.cuda.synchronize()
-    loss = loss.cpu().numpy()
-    for o in (lstm, tdd, voc):
-        o.destroy()
-    return loss
 
 
 @pytest.mark.parametrize("blank", [0, 2])
@@ -252,7 +91,7 @@ def test_exact_ties_go_to_the_lower_index(gpu):
     dec = _decoder(gpu, c)
     got = _decode(gpu, dec, c)
     dec.destroy()
-    _assert_equals_reference("tie", got, r64, c["nbest"])
+    assert_equals_reference("tie", got, r64, c["nbest"], _score_tol)
     assert got[2][0, 0] == got[2][0, 1]
 
 

@@ -1,5 +1,5 @@
 """Label timestamps, confidences and length normalisation of the transducer beam search on the device (csrc/hip/rnnt_beam.hip, the
-DETAIL instantiations) against tests/rnnt_beam_detail_reference.py.
+DETAIL instantiations) against tests/rnnt_beam_reference.py.
 
 Labels, lengths and FRAMES are compared for equality with the float64 reference, so every case is one on which the reference is
 unambiguous (tests/rnnt_beam_detail_cases.py, checked without a device by tests/test_rnnt_beam_detail_host.py and again here): cut,
@@ -18,9 +18,10 @@ import pytest
 import torch
 
 import rnnt_beam_detail_cases as DC
-import rnnt_beam_detail_reference as RD
+import rnnt_beam_reference as RB
 from nntoolkitcore_amd import capi, layers as NL
-from test_gpu_rnnt_beam import _decoder, _host, _ml, _same, _t
+from rnnt_beam_cases import ml as _ml
+from rnnt_beam_device import assert_equals_reference, decoder as _decoder, host as _host, same as _same, to_device as _t
 
 pytestmark = pytest.mark.gpu
 
@@ -76,30 +77,13 @@ def _assert_confidences(name, c, got):
             if L <= 0:
                 continue
             y = labels[b, k, :L].tolist()
-            lat = RD.lattice_logits(m["embed"], m["lstm"], m["proj"], m["out"], c["enc"][b], y, blank=m["blank"], activation=c["act"])
+            lat = RB.lattice_logits(m["embed"], m["lstm"], m["proj"], m["out"], c["enc"][b], y, blank=m["blank"], activation=c["act"])
             for j in range(L):
                 want = _log_softmax(lat[frames[b, k, j], j])[y[j]]
                 worst = max(worst, abs(float(logps[b, k, j]) - want))
     print("%s: largest device error of a label's log-probability %.3e (tolerance %.3e)" % (name, worst, DC.lps_tol()))
     assert worst <= DC.lps_tol(), (name, worst, DC.lps_tol())
     return worst
-
-
-def _assert_equals_reference(name, c, got, r64):
-    labels, lengths, scores, frames, logps = got
-    worst = 0.0
-    for b in range(labels.shape[0]):
-        have = len(r64["labels"][b])
-        for k in range(c["nbest"]):
-            if k < have:
-                y, fr = r64["labels"][b][k], r64["frames"][b][k]
-                assert lengths[b, k] == len(y) and labels[b, k, :len(y)].tolist() == y, (name, b, k, labels[b, k], y)
-                assert frames[b, k, :len(y)].tolist() == fr, (name, b, k, frames[b, k], fr)
-                worst = max(worst, abs(float(scores[b, k]) - float(r64["scores"][b][k])))
-            else:
-                assert lengths[b, k] == -1 and scores[b, k] == -np.inf and (frames[b, k] == -1).all(), (name, b, k)
-    print("%s: largest device score error %.3e (tolerance %.3e)" % (name, worst, DC.score_tol()))
-    assert worst <= DC.score_tol(), (name, worst)
 
 
 @pytest.mark.parametrize("group", [0, 1])
@@ -126,7 +110,7 @@ def test_equals_the_reference_and_moves_nothing(gpu, name, group):
     assert _same(off[:3], plain), name                                               # 1: detail on moves no bit
     _assert_structure(name, c, got)
     _assert_structure(name, c, off)
-    _assert_equals_reference(name, c, got, r64)
+    assert_equals_reference(name, got, r64, c["nbest"], DC.score_tol)
     _assert_confidences(name, c, got)
     if DC.length_norm(name):                                                         # 7: the same final A, the plain call's bits
         assert any(_entries(got, b) != _entries(off, b) for b in range(got[0].shape[0])), (name, "nothing was reordered")
@@ -175,7 +159,7 @@ def test_an_unpruned_path_does_not_exceed_the_mass(gpu):
             if L < 0:
                 continue
             y, fr = labels[b, k, :L].tolist(), frames[b, k, :L]
-            lat = RD.lattice_logits(m["embed"], m["lstm"], m["proj"], m["out"], c["enc"][b], y, blank=m["blank"], activation=c["act"])
+            lat = RB.lattice_logits(m["embed"], m["lstm"], m["proj"], m["out"], c["enc"][b], y, blank=m["blank"], activation=c["act"])
             blanks = sum(_log_softmax(lat[t, int((fr <= t).sum())])[m["blank"]] for t in range(n))
             path = float(logps[b, k, :L].astype(np.float64).sum()) + blanks
             assert path <= float(scores[b, k]) + DC.score_tol(), (b, k, path, scores[b, k])

@@ -1,5 +1,5 @@
 """RNN-Transducer beam search fused with an n-gram language model on the device (csrc/hip/rnnt_beam.hip, the LM instantiations;
-csrc/host/rnnt_decode.c, ngram_lm.c) against tests/rnnt_beam_lm_reference.py, against the acoustic call, the device's own transducer loss
+csrc/host/rnnt_decode.c, ngram_lm.c) against tests/rnnt_beam_reference.py, against the acoustic call, the device's own transducer loss
 with the host scorer, and the streaming form against the one-shot call.
 
 The rules are those of test_gpu_rnnt_beam.py.  Labels and lengths are compared for EQUALITY with the float64 reference, on cases whose
@@ -17,9 +17,11 @@ import pytest
 import torch
 
 import rnnt_beam_lm_cases as K
-import rnnt_beam_lm_reference as RL
+import rnnt_beam_reference as RB
 from nntoolkitcore_amd import capi, layers as NL
-from test_gpu_rnnt_beam import _decoder, _host, _lattice_losses, _ml, _same, _score_tol as _acoustic_score_tol, _t
+from rnnt_beam_cases import ml as _ml, score_tol as _acoustic_score_tol
+from rnnt_beam_device import assert_equals_reference, decoder as _decoder, host as _host, lattice_losses as _lattice_losses, same as _same, \
+    to_device as _t
 
 pytestmark = pytest.mark.gpu
 
@@ -40,29 +42,12 @@ def _decode(gpu, dec, c, lm, enc=None, n=None, W=None, nbest=None):
                                  _ml(c), lm=lm))
 
 
-def _assert_equals_reference(name, got, r64, nbest):
-    labels, lengths, scores = got
-    worst = 0.0
-    for b in range(labels.shape[0]):
-        have = len(r64["labels"][b])
-        for k in range(nbest):
-            if k < have:
-                y = r64["labels"][b][k]
-                assert lengths[b, k] == len(y) and labels[b, k, :len(y)].tolist() == y and (labels[b, k, len(y):] == -1).all(), \
-                    (name, b, k, labels[b, k], y)
-                worst = max(worst, abs(float(scores[b, k]) - float(r64["scores"][b][k])))
-            else:
-                assert lengths[b, k] == -1 and (labels[b, k] == -1).all() and scores[b, k] == -np.inf, (name, b, k)
-    print("%s: largest device score error %.3e (tolerance %.3e)" % (name, worst, K.score_tol()))
-    assert worst <= K.score_tol(), (name, worst, K.score_tol())
-
-
 def _check(gpu, name):
     c = K.case(name)
     dec, lm = _decoder(gpu, c), _lm(name)
     got = _decode(gpu, dec, c, lm)
     dec.destroy(); lm.close()
-    _assert_equals_reference(name, got, K.reference(name)[0], c["nbest"])
+    assert_equals_reference(name, got, K.reference(name)[0], c["nbest"], K.score_tol)
     return c, got
 
 
@@ -71,7 +56,7 @@ def test_equals_the_float64_reference(gpu, name):
     K.assert_premise(name)
     c, (labels, lengths, scores) = _check(gpu, name)
     if name.startswith("awkward"):                   # the row without frames: the empty hypothesis with ln E(start_state)
-        ref = RL.Lm(*K.table(name))
+        ref = RB.Lm(*K.table(name))
         assert lengths[2, 0] == 0 and scores[2, 0] == np.float32(ref.final_ln[ref.start]) and (lengths[2, 1:] == -1).all()
     if name == "big_v":                              # the scatter over state 0's arcs strides the workgroup more than once
         t = K.table(name)[0]
@@ -123,7 +108,7 @@ def test_exhaustive_search_minus_the_model_is_minus_the_loss(gpu, name):
     for b in range(len(c["n"])):
         count = len(r64["final"][b])
         got = [labels[b, k, :lengths[b, k]].tolist() for k in range(count)]
-        assert got == [y for y, _ in r64["final"][b]] and (lengths[b, count:] == -1).all(), (b, got)
+        assert got == [r[0] for r in r64["final"][b]] and (lengths[b, count:] == -1).all(), (b, got)
         pairs += [(b, y) for y in got]
         fused += [float(scores[b, k]) - lm.score(y, with_final=True) for k, y in enumerate(got)]
     lm.close()

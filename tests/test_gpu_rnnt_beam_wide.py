@@ -31,35 +31,16 @@ Which test reaches which branch (the constants are mirrored in rnnt_wide_cases.p
 """
 import numpy as np
 import pytest
-import torch
 
 import rnnt_wide_cases as K
 from nntoolkitcore_amd import capi, layers as NL
+from rnnt_beam_device import assert_equals_reference, decoder as _decoder, host as _host, same as _same, to_device as _t
 
 pytestmark = pytest.mark.gpu
 
 
-def _t(gpu, a):
-    return None if a is None else torch.from_numpy(np.ascontiguousarray(a)).to(gpu)
-
-
-def _decoder(gpu, c):
-    m = c["m"]
-    return NL.RnntDecoder(_t(gpu, m["embed"]), _t(gpu, m["lstm"]), _t(gpu, m["proj"]), _t(gpu, m["out"]), blank=m["blank"],
-                          joint_activation=c["act"], max_symbols_per_frame=c["ms"])
-
-
-def _host(outs):
-    torch.cuda.synchronize()
-    return tuple(o.cpu().numpy() for o in outs)
-
-
 def _decode(gpu, dec, c, n=None):
     return _host(dec.beam_decode(_t(gpu, c["enc"]), c["n"] if n is None else n, c["W"], c["nbest"], c["max_labels"]))
-
-
-def _same(x, y):
-    return all(np.array_equal(p.view(np.int32), q.view(np.int32)) for p, q in zip(x, y))
 
 
 def _premise(name):
@@ -72,30 +53,13 @@ def _premise(name):
     return r64
 
 
-def _assert_equals_reference(name, got, r64, nbest):
-    labels, lengths, scores = got
-    worst = 0.0
-    for b in range(labels.shape[0]):
-        have = len(r64["labels"][b])
-        for k in range(nbest):
-            if k < have:
-                y = r64["labels"][b][k]
-                assert lengths[b, k] == len(y) and labels[b, k, :len(y)].tolist() == y and (labels[b, k, len(y):] == -1).all(), \
-                    (name, b, k, labels[b, k], y)
-                worst = max(worst, abs(float(scores[b, k]) - float(r64["scores"][b][k])))
-            else:
-                assert lengths[b, k] == -1 and (labels[b, k] == -1).all() and scores[b, k] == -np.inf, (name, b, k)
-    print("%s: largest device score error %.3e (tolerance %.3e)" % (name, worst, K.beam_score_tol()))
-    assert worst <= K.beam_score_tol(), (name, worst, K.beam_score_tol())
-
-
 def _check(gpu, name):
     r64 = _premise(name)
     c = K.beam_case(name)
     dec = _decoder(gpu, c)
     got = _decode(gpu, dec, c)
     dec.destroy()
-    _assert_equals_reference(name, got, r64, c["nbest"])
+    assert_equals_reference(name, got, r64, c["nbest"], K.beam_score_tol)
     return c, r64, got
 
 
@@ -113,7 +77,7 @@ def test_passes_and_the_groups_opt_in(gpu):
     finally:
         L.nntk_shim_rnnt_beam_set_group(0)
         dec.destroy()
-    _assert_equals_reference("b1", auto, r64, c["nbest"])
+    assert_equals_reference("b1", auto, r64, c["nbest"], K.beam_score_tol)
     assert _same(auto, single)
 
 
@@ -139,9 +103,9 @@ def test_the_widest_beam(gpu):
     for b, final in enumerate(r64["final"]):
         assert len(final) == c["W"]
         have = {tuple(labels[b, k, :lengths[b, k]].tolist()): float(scores[b, k]) for k in range(c["W"])}
-        assert sorted(have) == sorted(tuple(y) for y, _ in final), b
+        assert sorted(have) == sorted(tuple(r[0]) for r in final), b
         assert all(scores[b, k] >= scores[b, k + 1] for k in range(c["W"] - 1)), b
-        worst = max([worst] + [abs(have[tuple(y)] - float(s)) for y, s in final])
+        worst = max([worst] + [abs(have[tuple(r[0])] - float(r[1])) for r in final])
     print("b4, all 32 survivors: largest device score error %.3e (tolerance %.3e)" % (worst, K.beam_score_tol()))
     assert worst <= K.beam_score_tol()
 
@@ -165,5 +129,5 @@ def test_wide_stream(gpu):
         got = _host(s.push(_t(gpu, chunk), split))
         assert _same(got, _decode(gpu, dec, c, n=seen)), seen
     assert seen == c["n"]
-    _assert_equals_reference("b1 streamed", got, K.beam_reference("b1")[0], c["nbest"])
+    assert_equals_reference("b1 streamed", got, K.beam_reference("b1")[0], c["nbest"], K.beam_score_tol)
     s.close(); dec.destroy()

@@ -1,6 +1,6 @@
 """The host side of the fused transducer beam search (csrc/host/rnnt_decode.c, the nntk_rnnt_beam_*_lm functions; csrc/host/ngram_lm.c):
 the exported symbols, the refusals and sizes that need no device, the float64 reference of the device tests
-(tests/rnnt_beam_lm_reference.py) against the acoustic reference and the lattice, and the premises of every case of
+(tests/rnnt_beam_reference.py with a model) against the acoustic reference and the lattice, and the premises of every case of
 tests/test_gpu_rnnt_beam_lm.py (tests/rnnt_beam_lm_cases.py).  The refusals that need a live decoder or state are in the GPU file.
 No GPU."""
 import ctypes as C
@@ -12,7 +12,6 @@ import numpy as np
 import pytest
 
 import rnnt_beam_lm_cases as K
-import rnnt_beam_lm_reference as RL
 import rnnt_beam_reference as RB
 import rnnt_reference as RR
 from nntoolkitcore_amd import capi, layers as NL
@@ -57,9 +56,9 @@ def test_refusals_and_sizes_that_need_no_device():
 def test_shim_workspace_appends_to_the_acoustic_layout():
     """per row one int per hypothesis slot and beam_width V doubles more, each part rounded up to 16 bytes; the acoustic size is untouched"""
     L = capi.load()
-    f, g = L.nntk_shim_rnnt_beam_workspace_floats, L.nntk_shim_rnnt_beam_lm_workspace_floats
-    for fn in (f, g):
-        fn.restype, fn.argtypes = C.c_size_t, [C.c_int] * 7
+    size = L.nntk_shim_rnnt_beam_workspace_floats
+    size.restype, size.argtypes = C.c_size_t, [C.c_int] * 9
+    f, g = lambda *a: size(*a, 0, 0), lambda *a: size(*a, 1, 0)            # without and with a model, no detail
     pad = lambda x: (x + 3) & ~3
     for batch, H, J, V, S, W, ML in [(2, 12, 20, 5, 3, 4, 6), (3, 13, 22, 1030, 1, 3, 4), (1, 16, 16, 70, 3, 8, 2), (5, 7, 9, 6, 4, 32, 3)]:
         slots = (min(S, ML) + 2) * W
@@ -70,7 +69,7 @@ def test_shim_workspace_appends_to_the_acoustic_layout():
 def test_the_model_in_python_equals_the_host_scorer():
     for name in ("awkward", "big_v", "stream", "exhaustive4"):
         t, alpha, beta = K.table(name)
-        lm, ref = NL.NgramLm.from_arrays(alpha=alpha, beta=beta, **t), RL.Lm(t, alpha, beta)
+        lm, ref = NL.NgramLm.from_arrays(alpha=alpha, beta=beta, **t), RB.Lm(t, alpha, beta)
         labels = [v for v in range(t["n_classes"]) if v != t["blank"]]
         rng = np.random.default_rng(3)
         for _ in range(20):
@@ -86,7 +85,7 @@ def test_a_unit_model_leaves_the_acoustic_reference_exactly(name):
     m = c["m"]
     t = dict(K.table("awkward" if m["V"] == 5 else name)[0], final_logp=None)
     for dtype in (np.float64, np.float32):
-        got = RL.beam_decode(m["embed"], m["lstm"], m["proj"], m["out"], c["enc"], RL.Lm(t, 0.0, 0.0), dtype=dtype, **K.search_kw(c))
+        got = RB.beam_decode(m["embed"], m["lstm"], m["proj"], m["out"], c["enc"], lm=RB.Lm(t, 0.0, 0.0), dtype=dtype, **K.search_kw(c))
         want = RB.beam_decode(m["embed"], m["lstm"], m["proj"], m["out"], c["enc"], dtype=dtype, **K.search_kw(c))
         for key in ("labels", "scores", "final"):
             assert got[key] == want[key], (name, key)
@@ -106,9 +105,9 @@ def test_exhaustive_search_minus_the_model_is_the_lattice(name):
     want = sorted([()] + [(a,) for a in lab] + list(itertools.product(lab, lab)))
     assert lm.unk > 0 and lm.backoffs > 0
     for b, n in enumerate(c["n"]):
-        assert sorted(tuple(y) for y, _ in r64["final"][b]) == want
-        for y, s in r64["final"][b]:
-            logits = RL.lattice_logits(m["embed"], m["lstm"], m["proj"], m["out"], c["enc"][b, :n], y, blank=m["blank"], activation=c["act"])
+        assert sorted(tuple(r[0]) for r in r64["final"][b]) == want
+        for y, s, _, _ in r64["final"][b]:
+            logits = RB.lattice_logits(m["embed"], m["lstm"], m["proj"], m["out"], c["enc"][b, :n], y, blank=m["blank"], activation=c["act"])
             loss, _ = RR.rnnt_loss_and_grad(logits[None], [y], [n], m["blank"])
             # float64 throughout: a few dozen additions of terms below 32 in magnitude, 2^-53 * 32 * 50 < 2e-13
             assert abs((s - lm.score(y, with_final=True)) + loss[0]) < 1e-12, (b, y, s, loss[0])
@@ -131,7 +130,7 @@ def test_premises_of_the_special_cases():
     # end of sentence at -inf: the best hypothesis of row 0 leaves the report, and stays in the carried beam
     best = K.reference("awkward")[0]["labels"][0][0]
     r = K.reference("final_drop")[0]
-    assert best not in [y for y, _ in r["final"][0]] and best in [y for y, _, _ in r["carried"][0]]
+    assert best not in [r4[0] for r4 in r["final"][0]] and best in [y for y, _, _ in r["carried"][0]]
     # end of sentence reorders, ties to the lower rank in A: [1] and [3] tie before and after, the empty hypothesis overtakes both
     r = K.reference("final_tie")[0]
     assert [y for y, _, _ in r["carried"][0]][:3] == [[1], [3], []] and r["carried"][0][0][1] == r["carried"][0][1][1]
