@@ -221,18 +221,20 @@ int nntk_shim_rnnt_fused_loss(const float *d_enc, const float *d_pred, const flo
                               const int *h_input_lengths, const int *h_labels, const int *h_label_lengths, int max_label_len, int blank,
                               float *d_loss_rows, float *d_denc, float *d_dpred, float *d_dout, float *d_ws);
 /* ---- transducer forced alignment (rnnt_align.hip): the best single path of every row through its lattice, on the emissions of
- *      rnnt.hip (stored scores) or of rnnt_fused.hip (the joiner's inputs).  Host int arrays as for nntk_shim_rnnt_loss, already checked
- *      by the caller (rnnt.c), never NULL; the four path outputs may be NULL; d_ws 16-byte aligned: the matching loss-only workspace,
- *      then one backpointer byte per cell of batch * (T + max_label_len) diagonals of min(T, max_label_len + 1) cells ---- */
-size_t nntk_shim_rnnt_align_workspace_floats(int batch, int T, int max_label_len);
-int nntk_shim_rnnt_align(const float *d_logits, int B, int T, int V, const int *h_input_lengths, const int *h_labels,
-                         const int *h_label_lengths, int max_label_len, int blank, int *d_label_frames, int *d_frame_labels,
-                         float *d_label_logp, float *d_frame_logp, float *d_scores, float *d_ws);
-size_t nntk_shim_rnnt_fused_align_workspace_floats(int batch, int T, int max_label_len, int J, int V);
-int nntk_shim_rnnt_fused_align(const float *d_enc, const float *d_pred, const float *d_out, int B, int T, int J, int V, int kind,
-                               const int *h_input_lengths, const int *h_labels, const int *h_label_lengths, int max_label_len, int blank,
-                               int *d_label_frames, int *d_frame_labels, float *d_label_logp, float *d_frame_logp, float *d_scores,
-                               float *d_ws);
+ *      either score source: stored scores (rnnt.hip's writer) or the joiner's inputs (rnnt_fused.hip's).  Host int arrays as for
+ *      nntk_shim_rnnt_loss, already checked by the caller (rnnt.c), never NULL; the four path outputs may be NULL; d_ws 16-byte
+ *      aligned: the source's loss-only workspace, then one backpointer byte per cell of batch * (T + max_label_len) diagonals of
+ *      min(T, max_label_len + 1) cells ---- */
+typedef struct {
+    int fused;                              /* 0: d_logits [B][T][max_label_len + 1][V], 16-byte aligned; 1: the joiner's inputs below */
+    const float *d_logits;
+    const float *d_enc, *d_pred, *d_out;    /* [B][T][J], [B][max_label_len + 1][J], W [J,V] | b [V] */
+    int J, kind;
+} nntk_shim_rnnt_src;
+typedef struct { int *label_frames, *frame_labels; float *label_logp, *frame_logp, *scores; } nntk_shim_rnnt_path;   /* the outputs */
+size_t nntk_shim_rnnt_align_workspace_floats(const nntk_shim_rnnt_src *src, int batch, int T, int V, int max_label_len);
+int nntk_shim_rnnt_align(const nntk_shim_rnnt_src *src, int B, int T, int V, const int *h_input_lengths, const int *h_labels,
+                         const int *h_label_lengths, int max_label_len, int blank, const nntk_shim_rnnt_path *out, float *d_ws);
 /* ---- greedy transducer decoding (rnnt_decode.hip).  The limits, stated once for the host's checks (rnnt_decode.c) and the launcher: a
  *      row's h, c, g, joiner output and max(4H, V) logits / gate pre-activations live in one workgroup's LDS (48 KiB at the limits), and
  *      the folded input table is V x 4H floats (128 MiB at the limits).  Batches above NNTK_RNNT_DEC_GROUP_BATCH rows put

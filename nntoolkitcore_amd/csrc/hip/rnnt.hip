@@ -18,7 +18,7 @@
 //    the two outgoing flows), then V scores in and g[v] = A exp(x[v] - lse) - [v = blank] flow_blank - [v = label] flow_label out.
 //    Padding cells (t >= T_b or u > U_b) are zero-filled with 16-byte stores.
 // No atomics anywhere; every reduction is a fixed butterfly or a fixed-order loop.
-#include "rnnt_common.hpp"                 // the workspace layout, the emission, the cell index, the activation: shared with rnnt_fused.hip
+#include "rnnt_common.hpp"                 // the layout and its pointers, the int upload, the emission: shared by the three units
 
 #define RNNT_JOINT_UNROLL 4               // terms of a joiner-backward sum loaded together (added in ascending order all the same)
 
@@ -319,32 +319,25 @@ size_t nntk_shim_rnnt_workspace_floats(int batch, int T, int max_label_len, int 
 int nntk_shim_rnnt_loss(const float *d_logits, int B, int T, int V, const int *h_input_lengths, const int *h_labels,
                         const int *h_label_lengths, int maxL, int blank, float *d_loss_rows, float *d_dlogits, float *d_ws) {
     if (B <= 0) return 0;
-    if (maxL > NNTK_RNNT_MAX_LABELS || (long)T + maxL > NNTK_RNNT_MAX_DIAGONALS)
+    if (!rnnt_lattice_fits(T, maxL))
         return nntk_fail_msg("nntk_rnnt_loss_device: max_label_len or T + max_label_len is beyond the lattice kernel's limits");
     if ((((uintptr_t)d_ws | (uintptr_t)d_logits | (uintptr_t)d_dlogits) & 15) != 0)
         return nntk_fail_msg("nntk_rnnt_loss_device: the tensors and the workspace must be 16-byte aligned");
     const int U1 = maxL + 1;
-    const RnntLayout lay = rnnt_layout(B, T, maxL, d_dlogits != nullptr);
     const long cells = (long)B * T * U1;
-    int *d_ints = (int *)d_ws;
-    if (nntk_shim_upload_ints(d_ints, h_input_lengths, B)) return -1;
-    if (nntk_shim_upload_ints(d_ints + B, h_label_lengths, B)) return -1;
-    if (maxL > 0 && nntk_shim_upload_ints(d_ints + 2L * B, h_labels, (long)B * maxL)) return -1;
-    float *hdr = d_ws + lay.hdr;
-    float4 *em = (float4 *)(d_ws + lay.em);
-    double *lse = d_dlogits ? (double *)(d_ws + lay.lse) : nullptr;
-    float2 *wa = d_dlogits ? (float2 *)(d_ws + lay.alpha) : nullptr, *wb = d_dlogits ? (float2 *)(d_ws + lay.beta) : nullptr;
+    const RnntParts w = rnnt_parts(d_ws, rnnt_layout(B, T, maxL, d_dlogits != nullptr), d_dlogits != nullptr);
+    if (rnnt_upload_ints(w.ints, B, maxL, h_input_lengths, h_labels, h_label_lengths)) return -1;
     const bool vec = (V & 3) == 0;
     const dim3 cgrid(rnnt_grid(cells, 4));
-    if (nntk_rnnt_emit_launch(d_logits, B, T, U1, V, blank, d_ints, em, lse)) return -1;
-    if (nntk_rnnt_lattice_launch(B, T, U1, d_ints, em, wa, wb, hdr, d_loss_rows)) return -1;
+    if (nntk_rnnt_emit_launch(d_logits, B, T, U1, V, blank, w.ints, w.em, w.lse)) return -1;
+    if (nntk_rnnt_lattice_launch(B, T, U1, w.ints, w.em, w.alpha, w.beta, w.hdr, d_loss_rows)) return -1;
     if (d_dlogits) {
         if (vec)
-            hipLaunchKernelGGL(rnnt_grad_kernel<true>, cgrid, dim3(CTC_THREADS), 0, nntk_stream(), d_logits, B, T, U1, V, blank, d_ints, em, lse,
-                               wa, wb, hdr, d_dlogits, cells);
+            hipLaunchKernelGGL(rnnt_grad_kernel<true>, cgrid, dim3(CTC_THREADS), 0, nntk_stream(), d_logits, B, T, U1, V, blank, w.ints, w.em,
+                               w.lse, w.alpha, w.beta, w.hdr, d_dlogits, cells);
         else
-            hipLaunchKernelGGL(rnnt_grad_kernel<false>, cgrid, dim3(CTC_THREADS), 0, nntk_stream(), d_logits, B, T, U1, V, blank, d_ints, em, lse,
-                               wa, wb, hdr, d_dlogits, cells);
+            hipLaunchKernelGGL(rnnt_grad_kernel<false>, cgrid, dim3(CTC_THREADS), 0, nntk_stream(), d_logits, B, T, U1, V, blank, w.ints, w.em,
+                               w.lse, w.alpha, w.beta, w.hdr, d_dlogits, cells);
         NNTK_LAUNCH_CHECK("rnnt_grad_kernel");
     }
     return 0;

@@ -20,7 +20,8 @@
 // (T_b - 1, U_b) leaves v p_blank there in the header and writes the score.  rnnt_align_backtrack_kernel: one workgroup per row walks
 // the T_b + U_b moves back from (T_b - 1, U_b), a block of diagonals at a time: the block's bytes are staged into LDS with 16-byte
 // loads, one lane walks them, then all lanes turn the block's moves into outputs, reading the emissions of the path's cells for the
-// per-move logarithms.  No atomics anywhere: every output element has exactly one writer.
+// per-move logarithms.  No atomics anywhere: every output element has exactly one writer.  One entry point serves both score sources
+// (nntk_shim_rnnt_src): it differs in the limit check and in the emission writer it calls, and in nothing else.
 #include "rnnt_common.hpp"
 
 #define RNNT_BT_BYTES (64 * 1024)         // backpointer bytes staged per block of diagonals ...
@@ -180,82 +181,59 @@ __global__ __launch_bounds__(CTC_THREADS) void rnnt_align_backtrack_kernel(int B
 
 // Viterbi and backtrace on the emissions em of a loss-only workspace whose ints and header are at their places; d_bp: the backpointers
 static int rnnt_align_launch(int B, int T, int U1, const int *d_ints, const float4 *em, float *hdr, unsigned char *d_bp,
-                             int *d_label_frames, int *d_frame_labels, float *d_label_logp, float *d_frame_logp, float *d_scores) {
+                             const nntk_shim_rnnt_path *out) {
     const size_t lds = 2 * (size_t)U1 * sizeof(float4);
 #define RNNT_VIT(NJ)                                                                                                          \
     do {                                                                                                                      \
         if (lds > 48 * 1024 && nntk_set_max_dynamic_lds((const void *)rnnt_viterbi_kernel<NJ>, lds)) return -1;                \
         hipLaunchKernelGGL(rnnt_viterbi_kernel<NJ>, dim3((unsigned)B), dim3(CTC_THREADS), lds, nntk_stream(), B, T, U1, d_ints, em, \
-                           d_bp, hdr, d_scores);                                                                              \
+                           d_bp, hdr, out->scores);                                                                            \
     } while (0)
     if (U1 <= CTC_THREADS) RNNT_VIT(1);
     else if (U1 <= 2 * CTC_THREADS) RNNT_VIT(2);
     else RNNT_VIT(0);
 #undef RNNT_VIT
     NNTK_LAUNCH_CHECK("rnnt_viterbi_kernel");
-    if (!d_label_frames && !d_frame_labels && !d_label_logp && !d_frame_logp) return 0;
+    if (!out->label_frames && !out->frame_labels && !out->label_logp && !out->frame_logp) return 0;
     const int P = T < U1 ? T : U1, DC = rnnt_bt_block_diags(P);
     const size_t blds = (((size_t)(DC + 1) * 4 + 15) & ~(size_t)15) + (size_t)DC * P + 32;
     if (blds > 48 * 1024 && nntk_set_max_dynamic_lds((const void *)rnnt_align_backtrack_kernel, blds)) return -1;
     hipLaunchKernelGGL(rnnt_align_backtrack_kernel, dim3((unsigned)B), dim3(CTC_THREADS), blds, nntk_stream(), B, T, U1, DC, d_ints, em,
-                       d_bp, hdr, d_label_frames, d_frame_labels, d_label_logp, d_frame_logp);
+                       d_bp, hdr, out->label_frames, out->frame_labels, out->label_logp, out->frame_logp);
     NNTK_LAUNCH_CHECK("rnnt_align_backtrack_kernel");
     return 0;
 }
 
-static int rnnt_align_upload(int *d_ints, int B, int maxL, const int *h_input_lengths, const int *h_labels, const int *h_label_lengths) {
-    if (nntk_shim_upload_ints(d_ints, h_input_lengths, B)) return -1;
-    if (nntk_shim_upload_ints(d_ints + B, h_label_lengths, B)) return -1;
-    if (maxL > 0 && nntk_shim_upload_ints(d_ints + 2L * B, h_labels, (long)B * maxL)) return -1;
-    return 0;
+// the loss-only workspace of the score source (either loss call's), then the backpointers
+static RnntAlignLayout rnnt_align_layout_of(const nntk_shim_rnnt_src *src, int B, int T, int V, int maxL) {
+    return rnnt_align_layout(src->fused ? nntk_shim_rnnt_fused_workspace_floats(B, T, maxL, src->J, V, 0) : rnnt_layout(B, T, maxL, 0).total,
+                             B, T, maxL);
 }
 
 extern "C" {
 
-size_t nntk_shim_rnnt_align_workspace_floats(int batch, int T, int max_label_len) {
-    return rnnt_align_layout(rnnt_layout(batch, T, max_label_len, 0).total, batch, T, max_label_len).total;
+size_t nntk_shim_rnnt_align_workspace_floats(const nntk_shim_rnnt_src *src, int batch, int T, int V, int max_label_len) {
+    return rnnt_align_layout_of(src, batch, T, V, max_label_len).total;
 }
 
-size_t nntk_shim_rnnt_fused_align_workspace_floats(int batch, int T, int max_label_len, int J, int V) {
-    return rnnt_align_layout(nntk_shim_rnnt_fused_workspace_floats(batch, T, max_label_len, J, V, 0), batch, T, max_label_len).total;
-}
-
-int nntk_shim_rnnt_align(const float *d_logits, int B, int T, int V, const int *h_input_lengths, const int *h_labels,
-                         const int *h_label_lengths, int maxL, int blank, int *d_label_frames, int *d_frame_labels, float *d_label_logp,
-                         float *d_frame_logp, float *d_scores, float *d_ws) {
+int nntk_shim_rnnt_align(const nntk_shim_rnnt_src *src, int B, int T, int V, const int *h_input_lengths, const int *h_labels,
+                         const int *h_label_lengths, int maxL, int blank, const nntk_shim_rnnt_path *out, float *d_ws) {
     if (B <= 0) return 0;
-    if (maxL > NNTK_RNNT_MAX_LABELS || (long)T + maxL > NNTK_RNNT_MAX_DIAGONALS)
-        return nntk_fail_msg("nntk_rnnt_align_device: max_label_len or T + max_label_len is beyond the lattice kernel's limits");
-    if ((((uintptr_t)d_ws | (uintptr_t)d_logits) & 15) != 0)
-        return nntk_fail_msg("nntk_rnnt_align_device: the scores and the workspace must be 16-byte aligned");
+    if (src->fused) {
+        if (!rnnt_fused_fits(T, maxL, src->J, V, d_ws))
+            return nntk_fail_msg("nntk_rnnt_fused_align_device: a shape beyond the kernels' limits or a misaligned workspace");
+    } else {
+        if (!rnnt_lattice_fits(T, maxL))
+            return nntk_fail_msg("nntk_rnnt_align_device: max_label_len or T + max_label_len is beyond the lattice kernel's limits");
+        if ((((uintptr_t)d_ws | (uintptr_t)src->d_logits) & 15) != 0)
+            return nntk_fail_msg("nntk_rnnt_align_device: the scores and the workspace must be 16-byte aligned");
+    }
     const int U1 = maxL + 1;
-    const RnntLayout lay = rnnt_layout(B, T, maxL, 0);
-    const RnntAlignLayout al = rnnt_align_layout(lay.total, B, T, maxL);
-    int *d_ints = (int *)d_ws;
-    if (rnnt_align_upload(d_ints, B, maxL, h_input_lengths, h_labels, h_label_lengths)) return -1;
-    float4 *em = (float4 *)(d_ws + lay.em);
-    if (nntk_rnnt_emit_launch(d_logits, B, T, U1, V, blank, d_ints, em, nullptr)) return -1;
-    return rnnt_align_launch(B, T, U1, d_ints, em, d_ws + lay.hdr, (unsigned char *)(d_ws + al.bp), d_label_frames,
-                             d_frame_labels, d_label_logp, d_frame_logp, d_scores);
-}
-
-int nntk_shim_rnnt_fused_align(const float *d_enc, const float *d_pred, const float *d_out, int B, int T, int J, int V, int kind,
-                               const int *h_input_lengths, const int *h_labels, const int *h_label_lengths, int maxL, int blank,
-                               int *d_label_frames, int *d_frame_labels, float *d_label_logp, float *d_frame_logp, float *d_scores,
-                               float *d_ws) {
-    if (B <= 0) return 0;
-    if (maxL > NNTK_RNNT_MAX_LABELS || (long)T + maxL > NNTK_RNNT_MAX_DIAGONALS || J < 1 || J > NNTK_RNNT_FUSED_MAX_J || V < 2 ||
-        V > NNTK_RNNT_FUSED_MAX_V || ((uintptr_t)d_ws & 15) != 0)
-        return nntk_fail_msg("nntk_rnnt_fused_align_device: a shape beyond the kernels' limits or a misaligned workspace");
-    const int U1 = maxL + 1;
-    const RnntLayout lay = rnnt_layout(B, T, maxL, 0);                      // the fused loss-only workspace starts with these parts
-    const RnntAlignLayout al = rnnt_align_layout(nntk_shim_rnnt_fused_workspace_floats(B, T, maxL, J, V, 0), B, T, maxL);
-    int *d_ints = (int *)d_ws;
-    if (rnnt_align_upload(d_ints, B, maxL, h_input_lengths, h_labels, h_label_lengths)) return -1;
-    float4 *em = (float4 *)(d_ws + lay.em);
-    if (nntk_rnnt_fused_emit_launch(d_enc, d_pred, d_out, B, T, U1, J, V, kind, blank, d_ints, em, nullptr)) return -1;
-    return rnnt_align_launch(B, T, U1, d_ints, em, d_ws + lay.hdr, (unsigned char *)(d_ws + al.bp),
-                             d_label_frames, d_frame_labels, d_label_logp, d_frame_logp, d_scores);
+    const RnntParts w = rnnt_parts(d_ws, rnnt_layout(B, T, maxL, 0), false);  // the fused loss-only workspace starts with these parts too
+    if (rnnt_upload_ints(w.ints, B, maxL, h_input_lengths, h_labels, h_label_lengths)) return -1;
+    if (src->fused ? nntk_rnnt_fused_emit_launch(src->d_enc, src->d_pred, src->d_out, B, T, U1, src->J, V, src->kind, blank, w.ints, w.em, nullptr)
+                   : nntk_rnnt_emit_launch(src->d_logits, B, T, U1, V, blank, w.ints, w.em, nullptr)) return -1;
+    return rnnt_align_launch(B, T, U1, w.ints, w.em, w.hdr, (unsigned char *)(d_ws + rnnt_align_layout_of(src, B, T, V, maxL).bp), out);
 }
 
 }  // extern "C"

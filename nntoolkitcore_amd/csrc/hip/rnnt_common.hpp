@@ -1,7 +1,8 @@
-// rnnt_common.hpp -- what the two transducer-loss units share (rnnt.hip: the loss on a stored score tensor; rnnt_fused.hip: the loss
-// that makes its scores from the joiner's inputs and never stores them): the workspace layout of the per-cell scalars, the emission
-// as mantissa and exponent, the cell index, the joiner's activation, and the launchers of the kernels that rnnt.hip owns and
-// rnnt_fused.hip reuses unchanged (the lattice and the joiner's backward reduction).
+// rnnt_common.hpp -- what the three transducer loss / alignment units share (rnnt.hip: the loss on a stored score tensor;
+// rnnt_fused.hip: the loss that makes its scores from the joiner's inputs and never stores them; rnnt_align.hip: Viterbi on either's
+// emissions): the kernels' limits, the workspace layout of the per-cell scalars and its pointers, the upload of the host ints, the
+// emission as mantissa and exponent, the cell index, the joiner's activation, and the launchers of the kernels that one unit owns and
+// another reuses unchanged.
 #pragma once
 #include <stdint.h>
 #include "nntk_common.hpp"
@@ -25,6 +26,27 @@ static inline RnntLayout rnnt_layout(int B, int T, int maxL, int want_grad) {
     l.beta = l.alpha + (want_grad ? up(2 * cells) : 0);
     l.total = l.beta + (want_grad ? up(2 * cells) : 0) + 4;
     return l;
+}
+
+// the layout as pointers into d_ws; lse / alpha / beta NULL without a gradient
+struct RnntParts { int *ints; float *hdr; float4 *em; double *lse; float2 *alpha, *beta; };
+static inline RnntParts rnnt_parts(float *d_ws, const RnntLayout &l, bool grad) {
+    return {(int *)d_ws, d_ws + l.hdr, (float4 *)(d_ws + l.em), grad ? (double *)(d_ws + l.lse) : nullptr,
+            grad ? (float2 *)(d_ws + l.alpha) : nullptr, grad ? (float2 *)(d_ws + l.beta) : nullptr};
+}
+
+// the three host int arrays (checked by rnnt.c) to the head of the workspace, in stream order
+static inline int rnnt_upload_ints(int *d_ints, int B, int maxL, const int *h_input_lengths, const int *h_labels, const int *h_label_lengths) {
+    if (nntk_shim_upload_ints(d_ints, h_input_lengths, B)) return -1;
+    if (nntk_shim_upload_ints(d_ints + B, h_label_lengths, B)) return -1;
+    if (maxL > 0 && nntk_shim_upload_ints(d_ints + 2L * B, h_labels, (long)B * maxL)) return -1;
+    return 0;
+}
+
+// the limits of nntk_shim.h, for the entry points (rnnt.c checks them first; these guard a caller that bypasses it)
+static inline bool rnnt_lattice_fits(int T, int maxL) { return maxL <= NNTK_RNNT_MAX_LABELS && (long)T + maxL <= NNTK_RNNT_MAX_DIAGONALS; }
+static inline bool rnnt_fused_fits(int T, int maxL, int J, int V, const void *d_ws) {
+    return rnnt_lattice_fits(T, maxL) && J >= 1 && J <= NNTK_RNNT_FUSED_MAX_J && V >= 2 && V <= NNTK_RNNT_FUSED_MAX_V && ((uintptr_t)d_ws & 15) == 0;
 }
 
 // forced alignment (rnnt_align.hip): a loss-only workspace of `base` words (either loss call's), then one backpointer byte per cell of

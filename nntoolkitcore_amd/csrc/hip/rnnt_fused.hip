@@ -15,7 +15,8 @@
 //    exp(x - max) kept per lane in double and rescaled (double exp) only when the cell's maximum grows.  The lane that holds the
 //    blank's / the next label's column hands that logit over.  At the end the 8 waves' (max, sum) pairs are merged in wave order, and
 //    the emissions (mantissa and exponent, rnnt_emission) and lse are the only things written: 16 + 8 bytes per cell.
-//  rnnt_lattice_kernel: rnnt.hip's, unchanged, on those emissions.
+//  rnnt_lattice_kernel: rnnt.hip's, unchanged, on those emissions; the workspace starts with rnnt.hip's layout (FtLayout::base), so the
+//    entry's prologue -- int upload, pointers into the layout -- is rnnt_common.hpp's, as in rnnt.hip and rnnt_align.hip.
 //  rnnt_fused_dz_kernel, a workgroup per tile: per group of gw (8, or 4 above J = 896: LDS) column blocks, phase A: wave w < gw
 //    recomputes a logits block and forms g = occupancy exp(x - lse) - flows (rnnt_grad_kernel's formula) into LDS, transposed; phase
 //    B: every wave owns the 32-wide blocks w, w + 8, ... of J and accumulates d z += g W^T over the group's columns (W^T: a transposed
@@ -414,24 +415,17 @@ int nntk_shim_rnnt_fused_loss(const float *d_enc, const float *d_pred, const flo
                               const int *h_input_lengths, const int *h_labels, const int *h_label_lengths, int maxL, int blank,
                               float *d_loss_rows, float *d_denc, float *d_dpred, float *d_dout, float *d_ws) {
     if (B <= 0) return 0;
-    if (maxL > NNTK_RNNT_MAX_LABELS || (long)T + maxL > NNTK_RNNT_MAX_DIAGONALS || J < 1 || J > NNTK_RNNT_FUSED_MAX_J || V < 2 ||
-        V > NNTK_RNNT_FUSED_MAX_V || ((uintptr_t)d_ws & 15) != 0)
+    if (!rnnt_fused_fits(T, maxL, J, V, d_ws))
         return nntk_fail_msg("nntk_rnnt_fused_loss_device: a shape beyond the kernels' limits or a misaligned workspace");
     const bool grad = d_dout != nullptr;
     const int U1 = maxL + 1;
     const FtLayout lay = ft_layout(B, T, maxL, J, V, grad);
     const long cells = (long)B * T * U1, tiles = (cells + FT_M - 1) / FT_M;
-    int *d_ints = (int *)d_ws;
-    if (nntk_shim_upload_ints(d_ints, h_input_lengths, B)) return -1;
-    if (nntk_shim_upload_ints(d_ints + B, h_label_lengths, B)) return -1;
-    if (maxL > 0 && nntk_shim_upload_ints(d_ints + 2L * B, h_labels, (long)B * maxL)) return -1;
-    float *hdr = d_ws + lay.base.hdr;
-    float4 *em = (float4 *)(d_ws + lay.base.em);
-    double *lse = grad ? (double *)(d_ws + lay.base.lse) : nullptr;
-    float2 *wa = grad ? (float2 *)(d_ws + lay.base.alpha) : nullptr, *wb = grad ? (float2 *)(d_ws + lay.base.beta) : nullptr;
+    const RnntParts w = rnnt_parts(d_ws, lay.base, grad);
+    if (rnnt_upload_ints(w.ints, B, maxL, h_input_lengths, h_labels, h_label_lengths)) return -1;
     const size_t zbytes = (size_t)J * FT_PITCH * sizeof(float);
-    if (nntk_rnnt_fused_emit_launch(d_enc, d_pred, d_out, B, T, U1, J, V, kind, blank, d_ints, em, lse)) return -1;
-    if (nntk_rnnt_lattice_launch(B, T, U1, d_ints, em, wa, wb, hdr, d_loss_rows)) return -1;
+    if (nntk_rnnt_fused_emit_launch(d_enc, d_pred, d_out, B, T, U1, J, V, kind, blank, w.ints, w.em, w.lse)) return -1;
+    if (nntk_rnnt_lattice_launch(B, T, U1, w.ints, w.em, w.alpha, w.beta, w.hdr, d_loss_rows)) return -1;
     if (!grad) return 0;
     float *wt = d_ws + lay.wt, *partial = d_ws + lay.partial, *dzt = d_ws + lay.dz;
     hipLaunchKernelGGL(rnnt_fused_transpose_kernel, dim3((unsigned)((V + 31) / 32), (unsigned)((J + 31) / 32)), dim3(256), 0, nntk_stream(),
@@ -441,7 +435,7 @@ int nntk_shim_rnnt_fused_loss(const float *d_enc, const float *d_pred, const flo
     const size_t dzbytes = zbytes + (size_t)gw * 32 * FT_PITCH * sizeof(float);
     if (dzbytes > 48 * 1024 && nntk_set_max_dynamic_lds((const void *)rnnt_fused_dz_kernel, dzbytes)) return -1;
     hipLaunchKernelGGL(rnnt_fused_dz_kernel, dim3(rnnt_grid(tiles, 1)), dim3(FT_THREADS), dzbytes, nntk_stream(), d_enc, d_pred, d_out, wt, B, T,
-                       U1, J, V, kind, blank, d_ints, em, lse, wa, wb, hdr, dzt, cells, tiles, gw);
+                       U1, J, V, kind, blank, w.ints, w.em, w.lse, w.alpha, w.beta, w.hdr, dzt, cells, tiles, gw);
     NNTK_LAUNCH_CHECK("rnnt_fused_dz_kernel");
     const int vtw = 32 * (4 / lay.njb);
     const dim3 wgrid((unsigned)((V + vtw - 1) / vtw), (unsigned)lay.np);
@@ -450,7 +444,7 @@ int nntk_shim_rnnt_fused_loss(const float *d_enc, const float *d_pred, const flo
     do {                                                                                                                             \
         if (dwbytes > 48 * 1024 && nntk_set_max_dynamic_lds((const void *)rnnt_fused_dw_kernel<NJB>, dwbytes)) return -1;             \
         hipLaunchKernelGGL(rnnt_fused_dw_kernel<NJB>, wgrid, dim3(FT_THREADS), dwbytes, nntk_stream(), d_enc, d_pred, d_out, B, T, U1, J, V, \
-                           kind, blank, d_ints, em, lse, wa, wb, hdr, partial, cells, tiles);                                        \
+                           kind, blank, w.ints, w.em, w.lse, w.alpha, w.beta, w.hdr, partial, cells, tiles);                         \
     } while (0)
     if (lay.njb == 1) FT_DW(1);
     else if (lay.njb == 2) FT_DW(2);

@@ -1,8 +1,9 @@
 /*
  * rnnt.c -- host layer of the RNN-Transducer calls (csrc/hip/rnnt.hip): the loss over the [batch][T][max_label_len + 1][V] lattice of
  * unnormalised scores with its gradient, and the joiner with its backward.  Every host array, shape, limit and pointer is checked
- * here, before anything is enqueued or allocated: a refusal needs no device.  The loss has a device-pointer form and a host-pointer
- * form (upload, device call, download).
+ * here, before anything is enqueued or allocated: a refusal needs no device.  Every call has a device-pointer form and a host-pointer
+ * form (upload, device call, download); the two alignment calls -- on stored scores and on the joiner's inputs -- are one device body
+ * and one host body that take the score source (nntk_shim_rnnt_src).
  */
 #include <stdint.h>
 #include <stdio.h>
@@ -57,6 +58,28 @@ static int rnnt_check_ptr(const char *who, const char *name, const void *p, unsi
     return -1;
 }
 
+/* the first `outputs` spans each against everything after it; a span at 0 is a pointer not given */
+typedef struct { const char *name; uintptr_t at; size_t bytes; } rnnt_span;
+static int rnnt_overlap(const char *who, const rnnt_span *sp, int outputs, int n) {
+    for (int o = 0; o < outputs; ++o)
+        for (int k = o + 1; k < n; ++k)
+            if (sp[o].at && sp[k].at && sp[o].at < sp[k].at + sp[k].bytes && sp[k].at < sp[o].at + sp[o].bytes) {
+                char msg[200];
+                snprintf(msg, sizeof msg, "%s: %s overlaps %s", who, sp[o].name, sp[k].name);
+                nntk_set_error(msg);
+                return -1;
+            }
+    return 0;
+}
+
+/* every row's frame count for the shim, which takes no NULL: input_lengths, or T; the caller frees it.  NULL: out of host memory */
+static int *rnnt_lengths(const int *input_lengths, int batch, int T) {
+    int *len = (int *)malloc((size_t)batch * sizeof(int));
+    if (!len) { nntk_set_error("out of host memory"); return NULL; }
+    for (int b = 0; b < batch; ++b) len[b] = input_lengths ? input_lengths[b] : T;
+    return len;
+}
+
 size_t nntk_rnnt_workspace_floats(int batch, int T, int max_label_len, int want_grad) {
     return nntk_shim_rnnt_workspace_floats(batch, T, max_label_len, want_grad != 0);
 }
@@ -71,13 +94,11 @@ int nntk_rnnt_loss_device(const float *d_logits, int batch, int T, int V, const 
     if (rnnt_check_ptr(who, "d_logits", d_logits, 16) || rnnt_check_ptr(who, "d_loss_rows", d_loss_rows, 4) ||
         rnnt_check_ptr(who, "d_workspace", d_workspace, 16) || (d_dlogits && rnnt_check_ptr(who, "d_dlogits", d_dlogits, 16))) return -1;
     const size_t bytes = (size_t)batch * T * (max_label_len + 1) * V * sizeof(float);
-    if (d_dlogits && (uintptr_t)d_dlogits < (uintptr_t)d_logits + bytes && (uintptr_t)d_logits < (uintptr_t)d_dlogits + bytes)
-        return rnnt_fail(who, "d_dlogits overlaps d_logits", 0, 0, 0);
-    int *len = (int *)malloc((size_t)batch * sizeof(int));
-    if (!len) NNTK_FAIL("out of host memory");
-    for (int b = 0; b < batch; ++b) len[b] = input_lengths ? input_lengths[b] : T;
-    int rc = nntk_shim_rnnt_loss(d_logits, batch, T, V, len, labels, label_lengths, max_label_len, blank, d_loss_rows, d_dlogits,
-                                 d_workspace);
+    const rnnt_span sp[] = {{"d_dlogits", (uintptr_t)d_dlogits, bytes}, {"d_logits", (uintptr_t)d_logits, bytes}};
+    if (rnnt_overlap(who, sp, 1, 2)) return -1;
+    int *len = rnnt_lengths(input_lengths, batch, T);
+    int rc = len ? nntk_shim_rnnt_loss(d_logits, batch, T, V, len, labels, label_lengths, max_label_len, blank, d_loss_rows, d_dlogits, d_workspace)
+                 : -1;
     free(len);
     return rc;
 }
@@ -143,7 +164,22 @@ static int fused_check(const char *who, int batch, int T, int J, int V, int acti
     return 0;
 }
 
-typedef struct { const char *name; uintptr_t at; size_t bytes; } fused_span;
+/* the joiner's inputs of both fused host forms in one device block: enc | pred | out, each part rounded up to 16 bytes, then `extra`
+ * floats for the caller */
+typedef struct { size_t ne, npd, nw; float *d_enc, *d_pred, *d_out; } fused_in;
+static int fused_stage(fused_in *s, const float *enc, const float *pred, const float *out, int batch, int T, int max_label_len, int J, int V,
+                       size_t extra) {
+    const size_t up = 3, re = (size_t)batch * T * J, rp = (size_t)batch * (max_label_len + 1) * J, rw = ((size_t)J + 1) * V;
+    s->ne = (re + up) & ~up;
+    s->npd = (rp + up) & ~up;
+    s->nw = (rw + up) & ~up;
+    s->d_enc = nntk_devbuf_reserve(&t_a, s->ne + s->npd + s->nw + extra + 4);
+    if (!s->d_enc) return -1;
+    s->d_pred = s->d_enc + s->ne;
+    s->d_out = s->d_pred + s->npd;
+    return nntk_shim_upload(s->d_enc, enc, re * sizeof(float)) || nntk_shim_upload(s->d_pred, pred, rp * sizeof(float)) ||
+           nntk_shim_upload(s->d_out, out, rw * sizeof(float)) ? -1 : 0;
+}
 
 size_t nntk_rnnt_fused_workspace_floats(int batch, int T, int max_label_len, int J, int V, int want_grad) {
     return nntk_shim_rnnt_fused_workspace_floats(batch, T, max_label_len, J, V, want_grad != 0);
@@ -163,25 +199,16 @@ int nntk_rnnt_fused_loss_device(const float *d_enc, const float *d_pred, const f
                     rnnt_check_ptr(who, "d_dout", d_dout, 4)))) return -1;
     const size_t U1 = (size_t)max_label_len + 1, f = sizeof(float);
     const size_t ne = (size_t)batch * T * J, npd = (size_t)batch * U1 * J, nw = ((size_t)J + 1) * V;
-    /* outputs first: each of them against everything after it */
-    const fused_span sp[] = {{"d_loss_rows", (uintptr_t)d_loss_rows, (size_t)batch * f}, {"d_denc", (uintptr_t)d_denc, ne * f},
-                             {"d_dpred", (uintptr_t)d_dpred, npd * f}, {"d_dout", (uintptr_t)d_dout, nw * f},
-                             {"d_enc", (uintptr_t)d_enc, ne * f}, {"d_pred", (uintptr_t)d_pred, npd * f}, {"d_out", (uintptr_t)d_out, nw * f},
-                             {"d_workspace", (uintptr_t)d_workspace,
-                              nntk_shim_rnnt_fused_workspace_floats(batch, T, max_label_len, J, V, d_denc != NULL) * f}};
-    for (int o = 0; o < 4; ++o)
-        for (int k = o + 1; k < 8; ++k)
-            if (sp[o].at && sp[k].at && sp[o].at < sp[k].at + sp[k].bytes && sp[k].at < sp[o].at + sp[o].bytes) {
-                char msg[200];
-                snprintf(msg, sizeof msg, "%s: %s overlaps %s", who, sp[o].name, sp[k].name);
-                nntk_set_error(msg);
-                return -1;
-            }
-    int *len = (int *)malloc((size_t)batch * sizeof(int));
-    if (!len) NNTK_FAIL("out of host memory");
-    for (int b = 0; b < batch; ++b) len[b] = input_lengths ? input_lengths[b] : T;
-    int rc = nntk_shim_rnnt_fused_loss(d_enc, d_pred, d_out, batch, T, J, V, activation, len, labels, label_lengths, max_label_len, blank,
-                                       d_loss_rows, d_denc, d_dpred, d_dout, d_workspace);
+    /* outputs first */
+    const rnnt_span sp[] = {{"d_loss_rows", (uintptr_t)d_loss_rows, (size_t)batch * f}, {"d_denc", (uintptr_t)d_denc, ne * f},
+                            {"d_dpred", (uintptr_t)d_dpred, npd * f}, {"d_dout", (uintptr_t)d_dout, nw * f},
+                            {"d_enc", (uintptr_t)d_enc, ne * f}, {"d_pred", (uintptr_t)d_pred, npd * f}, {"d_out", (uintptr_t)d_out, nw * f},
+                            {"d_workspace", (uintptr_t)d_workspace,
+                             nntk_shim_rnnt_fused_workspace_floats(batch, T, max_label_len, J, V, d_denc != NULL) * f}};
+    if (rnnt_overlap(who, sp, 4, 8)) return -1;
+    int *len = rnnt_lengths(input_lengths, batch, T);
+    int rc = len ? nntk_shim_rnnt_fused_loss(d_enc, d_pred, d_out, batch, T, J, V, activation, len, labels, label_lengths, max_label_len, blank,
+                                             d_loss_rows, d_denc, d_dpred, d_dout, d_workspace) : -1;
     free(len);
     return rc;
 }
@@ -197,179 +224,144 @@ int nntk_rnnt_fused_loss(const float *enc, const float *pred, const float *out, 
         rnnt_check_ptr(who, "loss_rows", loss_rows, 4) ||
         (denc && (rnnt_check_ptr(who, "denc", denc, 4) || rnnt_check_ptr(who, "dpred", dpred, 4) || rnnt_check_ptr(who, "dout", dout, 4))))
         return -1;
-    const size_t up = 3, U1 = (size_t)max_label_len + 1;
-    const size_t ne = ((size_t)batch * T * J + up) & ~up, npd = ((size_t)batch * U1 * J + up) & ~up, nw = (((size_t)J + 1) * V + up) & ~up;
-    const size_t nl = ((size_t)batch + up) & ~up;
     /* inputs | loss rows in one block, the gradients in a second, the workspace in a third */
-    float *d_in = nntk_devbuf_reserve(&t_a, ne + npd + nw + nl + 4);
-    float *d_g = denc ? nntk_devbuf_reserve(&t_b, ne + npd + nw + 4) : NULL;
+    fused_in s;
+    if (fused_stage(&s, enc, pred, out, batch, T, max_label_len, J, V, ((size_t)batch + 3) & ~(size_t)3)) return -1;
+    float *d_g = denc ? nntk_devbuf_reserve(&t_b, s.ne + s.npd + s.nw + 4) : NULL;
     float *d_ws = nntk_devbuf_reserve(&t_c, nntk_shim_rnnt_fused_workspace_floats(batch, T, max_label_len, J, V, denc != NULL));
-    if (!d_in || (denc && !d_g) || !d_ws) return -1;
-    float *d_enc = d_in, *d_pred = d_in + ne, *d_out = d_pred + npd, *d_loss = d_out + nw;
-    if (nntk_shim_upload(d_enc, enc, (size_t)batch * T * J * sizeof(float)) || nntk_shim_upload(d_pred, pred, (size_t)batch * U1 * J * sizeof(float)) ||
-        nntk_shim_upload(d_out, out, ((size_t)J + 1) * V * sizeof(float))) return -1;
-    if (nntk_rnnt_fused_loss_device(d_enc, d_pred, d_out, batch, T, J, V, activation, input_lengths, labels, label_lengths, max_label_len, blank,
-                                    d_loss, d_g, d_g ? d_g + ne : NULL, d_g ? d_g + ne + npd : NULL, d_ws)) return -1;
+    if ((denc && !d_g) || !d_ws) return -1;
+    float *d_loss = s.d_out + s.nw;
+    if (nntk_rnnt_fused_loss_device(s.d_enc, s.d_pred, s.d_out, batch, T, J, V, activation, input_lengths, labels, label_lengths, max_label_len,
+                                    blank, d_loss, d_g, d_g ? d_g + s.ne : NULL, d_g ? d_g + s.ne + s.npd : NULL, d_ws)) return -1;
     if (nntk_shim_download(loss_rows, d_loss, (size_t)batch * sizeof(float))) return -1;
     if (!denc) return 0;
     if (nntk_shim_download(denc, d_g, (size_t)batch * T * J * sizeof(float)) ||
-        nntk_shim_download(dpred, d_g + ne, (size_t)batch * U1 * J * sizeof(float))) return -1;
-    return nntk_shim_download(dout, d_g + ne + npd, ((size_t)J + 1) * V * sizeof(float));
+        nntk_shim_download(dpred, d_g + s.ne, (size_t)batch * (max_label_len + 1) * J * sizeof(float))) return -1;
+    return nntk_shim_download(dout, d_g + s.ne + s.npd, ((size_t)J + 1) * V * sizeof(float));
 }
 
-/* ---- forced alignment (csrc/hip/rnnt_align.hip): the best single path, on stored scores and on the joiner's inputs ---- */
-/* the first `outputs` spans each against everything after it; a span at 0 is an output not asked for */
-static int align_overlap(const char *who, const fused_span *sp, int outputs, int n) {
-    for (int o = 0; o < outputs; ++o)
-        for (int k = o + 1; k < n; ++k)
-            if (sp[o].at && sp[k].at && sp[o].at < sp[k].at + sp[k].bytes && sp[k].at < sp[o].at + sp[o].bytes) {
-                char msg[200];
-                snprintf(msg, sizeof msg, "%s: %s overlaps %s", who, sp[o].name, sp[k].name);
-                nntk_set_error(msg);
-                return -1;
-            }
-    return 0;
+/* ---- forced alignment (csrc/hip/rnnt_align.hip): the best single path, on stored scores and on the joiner's inputs.  One device
+ *      body and one host body take the score source; in the host body its pointers are host memory ---- */
+static int align_check(const char *who, const nntk_shim_rnnt_src *src, int batch, int T, int V, const int *input_lengths, const int *labels,
+                       const int *label_lengths, int max_label_len, int blank) {
+    if (!src->fused) return rnnt_check(who, batch, T, V, input_lengths, labels, label_lengths, max_label_len, blank);
+    return fused_check(who, batch, T, src->J, V, src->kind, input_lengths, labels, label_lengths, max_label_len, blank, NULL, NULL, NULL);
 }
 
-static int align_check_outputs(const char *who, const int *label_frames, const int *frame_labels, const float *label_logp,
-                               const float *frame_logp, const float *scores) {
-    return rnnt_check_ptr(who, "scores", scores, 4) || (label_frames && rnnt_check_ptr(who, "label_frames", label_frames, 4)) ||
-           (frame_labels && rnnt_check_ptr(who, "frame_labels", frame_labels, 4)) ||
-           (label_logp && rnnt_check_ptr(who, "label_logp", label_logp, 4)) || (frame_logp && rnnt_check_ptr(who, "frame_logp", frame_logp, 4));
+/* the source's pointers, under the names of the device form (the stored scores 16-byte aligned) or of the host form */
+static int align_check_src(const char *who, const nntk_shim_rnnt_src *src, int dev) {
+    if (!src->fused) return rnnt_check_ptr(who, dev ? "d_logits" : "logits", src->d_logits, dev ? 16 : 4);
+    return rnnt_check_ptr(who, dev ? "d_enc" : "enc", src->d_enc, 4) || rnnt_check_ptr(who, dev ? "d_pred" : "pred", src->d_pred, 4) ||
+           rnnt_check_ptr(who, dev ? "d_out" : "out", src->d_out, 4);
 }
+
+static int align_check_outputs(const char *who, const nntk_shim_rnnt_path *p) {
+    return rnnt_check_ptr(who, "scores", p->scores, 4) || (p->label_frames && rnnt_check_ptr(who, "label_frames", p->label_frames, 4)) ||
+           (p->frame_labels && rnnt_check_ptr(who, "frame_labels", p->frame_labels, 4)) ||
+           (p->label_logp && rnnt_check_ptr(who, "label_logp", p->label_logp, 4)) ||
+           (p->frame_logp && rnnt_check_ptr(who, "frame_logp", p->frame_logp, 4));
+}
+
+static int align_device(const char *who, const nntk_shim_rnnt_src *src, int batch, int T, int V, const int *input_lengths, const int *labels,
+                        const int *label_lengths, int max_label_len, int blank, const nntk_shim_rnnt_path *p, float *d_workspace) {
+    nntk_shim_clear_error();
+    if (align_check(who, src, batch, T, V, input_lengths, labels, label_lengths, max_label_len, blank)) return -1;
+    if (batch == 0) return 0;
+    if (align_check_src(who, src, 1) || rnnt_check_ptr(who, "d_workspace", d_workspace, 16) || align_check_outputs(who, p)) return -1;
+    const size_t f = sizeof(float), nl = (size_t)batch * max_label_len * f, nt = (size_t)batch * T * f, U1 = (size_t)max_label_len + 1;
+    /* outputs first; of the source's four spans those of the other source are at 0 */
+    const rnnt_span sp[] = {{"d_label_frames", (uintptr_t)p->label_frames, nl}, {"d_frame_labels", (uintptr_t)p->frame_labels, nt},
+                            {"d_label_logp", (uintptr_t)p->label_logp, nl}, {"d_frame_logp", (uintptr_t)p->frame_logp, nt},
+                            {"d_scores", (uintptr_t)p->scores, (size_t)batch * f},
+                            {"d_logits", (uintptr_t)src->d_logits, (size_t)batch * T * U1 * V * f},
+                            {"d_enc", (uintptr_t)src->d_enc, (size_t)batch * T * src->J * f},
+                            {"d_pred", (uintptr_t)src->d_pred, (size_t)batch * U1 * src->J * f},
+                            {"d_out", (uintptr_t)src->d_out, ((size_t)src->J + 1) * V * f},
+                            {"d_workspace", (uintptr_t)d_workspace,
+                             nntk_shim_rnnt_align_workspace_floats(src, batch, T, V, max_label_len) * f}};
+    if (rnnt_overlap(who, sp, 5, 10)) return -1;
+    int *len = rnnt_lengths(input_lengths, batch, T);
+    int rc = len ? nntk_shim_rnnt_align(src, batch, T, V, len, labels, label_lengths, max_label_len, blank, p, d_workspace) : -1;
+    free(len);
+    return rc;
+}
+
+/* who_dev: the device form's name, under which the device body speaks.  The outputs live in one device block: label_frames |
+ * frame_labels | label_logp | frame_logp | scores, a part that is not asked for taking no room */
+static int align_host(const char *who, const char *who_dev, const nntk_shim_rnnt_src *h, int batch, int T, int V, const int *input_lengths,
+                      const int *labels, const int *label_lengths, int max_label_len, int blank, const nntk_shim_rnnt_path *p) {
+    nntk_shim_clear_error();
+    if (align_check(who, h, batch, T, V, input_lengths, labels, label_lengths, max_label_len, blank)) return -1;
+    if (batch == 0) return 0;
+    if (align_check_src(who, h, 0) || align_check_outputs(who, p)) return -1;
+    const size_t nl = (size_t)batch * max_label_len, nt = (size_t)batch * T;
+    const size_t fl = p->label_frames ? nl : 0, ll = fl + (p->frame_labels ? nt : 0), fp = ll + (p->label_logp ? nl : 0);
+    const size_t sc = fp + (p->frame_logp ? nt : 0);
+    nntk_shim_rnnt_src d = *h;
+    if (h->fused) {
+        fused_in s;
+        if (fused_stage(&s, h->d_enc, h->d_pred, h->d_out, batch, T, max_label_len, h->J, V, 0)) return -1;
+        d.d_enc = s.d_enc; d.d_pred = s.d_pred; d.d_out = s.d_out;
+    } else {
+        const size_t n = nt * (max_label_len + 1) * V;
+        float *d_x = nntk_devbuf_reserve(&t_a, n + 4);
+        if (!d_x || nntk_shim_upload(d_x, h->d_logits, n * sizeof(float))) return -1;
+        d.d_logits = d_x;
+    }
+    float *d_o = nntk_devbuf_reserve(&t_b, sc + (size_t)batch + 4);
+    float *d_ws = nntk_devbuf_reserve(&t_c, nntk_shim_rnnt_align_workspace_floats(h, batch, T, V, max_label_len));
+    if (!d_o || !d_ws) return -1;
+    const nntk_shim_rnnt_path dp = {.label_frames = p->label_frames ? (int *)d_o : NULL, .frame_labels = p->frame_labels ? (int *)(d_o + fl) : NULL,
+                                    .label_logp = p->label_logp ? d_o + ll : NULL, .frame_logp = p->frame_logp ? d_o + fp : NULL, .scores = d_o + sc};
+    if (align_device(who_dev, &d, batch, T, V, input_lengths, labels, label_lengths, max_label_len, blank, &dp, d_ws)) return -1;
+    const size_t f = sizeof(float);
+    if (p->label_frames && nl && nntk_shim_download(p->label_frames, dp.label_frames, nl * f)) return -1;
+    if (p->frame_labels && nntk_shim_download(p->frame_labels, dp.frame_labels, nt * f)) return -1;
+    if (p->label_logp && nl && nntk_shim_download(p->label_logp, dp.label_logp, nl * f)) return -1;
+    if (p->frame_logp && nntk_shim_download(p->frame_logp, dp.frame_logp, nt * f)) return -1;
+    return nntk_shim_download(p->scores, dp.scores, (size_t)batch * f);
+}
+
+#define ALIGN_STORED(x) (&(nntk_shim_rnnt_src){.fused = 0, .d_logits = (x)})
+#define ALIGN_FUSED(e, p, o, j, k) (&(nntk_shim_rnnt_src){.fused = 1, .d_enc = (e), .d_pred = (p), .d_out = (o), .J = (j), .kind = (k)})
+#define ALIGN_PATH(lf, fl, lp, fp, sc) \
+    (&(nntk_shim_rnnt_path){.label_frames = (lf), .frame_labels = (fl), .label_logp = (lp), .frame_logp = (fp), .scores = (sc)})
 
 size_t nntk_rnnt_align_workspace_floats(int batch, int T, int max_label_len) {
-    return nntk_shim_rnnt_align_workspace_floats(batch, T, max_label_len);
+    return nntk_shim_rnnt_align_workspace_floats(ALIGN_STORED(NULL), batch, T, 0, max_label_len);
 }
 
 int nntk_rnnt_align_device(const float *d_logits, int batch, int T, int V, const int *input_lengths, const int *labels,
                            const int *label_lengths, int max_label_len, int blank, int *d_label_frames, int *d_frame_labels,
                            float *d_label_logp, float *d_frame_logp, float *d_scores, float *d_workspace) {
-    static const char who[] = "nntk_rnnt_align_device";
-    nntk_shim_clear_error();
-    if (rnnt_check(who, batch, T, V, input_lengths, labels, label_lengths, max_label_len, blank)) return -1;
-    if (batch == 0) return 0;
-    if (rnnt_check_ptr(who, "d_logits", d_logits, 16) || rnnt_check_ptr(who, "d_workspace", d_workspace, 16) ||
-        align_check_outputs(who, d_label_frames, d_frame_labels, d_label_logp, d_frame_logp, d_scores)) return -1;
-    const size_t f = sizeof(float), nl = (size_t)batch * max_label_len * f, nt = (size_t)batch * T * f;
-    const fused_span sp[] = {{"d_label_frames", (uintptr_t)d_label_frames, nl}, {"d_frame_labels", (uintptr_t)d_frame_labels, nt},
-                             {"d_label_logp", (uintptr_t)d_label_logp, nl}, {"d_frame_logp", (uintptr_t)d_frame_logp, nt},
-                             {"d_scores", (uintptr_t)d_scores, (size_t)batch * f},
-                             {"d_logits", (uintptr_t)d_logits, (size_t)batch * T * (max_label_len + 1) * V * f},
-                             {"d_workspace", (uintptr_t)d_workspace, nntk_shim_rnnt_align_workspace_floats(batch, T, max_label_len) * f}};
-    if (align_overlap(who, sp, 5, 7)) return -1;
-    int *len = (int *)malloc((size_t)batch * sizeof(int));
-    if (!len) NNTK_FAIL("out of host memory");
-    for (int b = 0; b < batch; ++b) len[b] = input_lengths ? input_lengths[b] : T;
-    int rc = nntk_shim_rnnt_align(d_logits, batch, T, V, len, labels, label_lengths, max_label_len, blank, d_label_frames, d_frame_labels,
-                                  d_label_logp, d_frame_logp, d_scores, d_workspace);
-    free(len);
-    return rc;
-}
-
-/* the outputs of both host-pointer forms live in one device block: label_frames | frame_labels | label_logp | frame_logp | scores,
- * a part that is not asked for taking no room */
-typedef struct { size_t lf, fl, ll, fp, sc, total; } align_out;
-static align_out align_out_layout(int batch, int T, int max_label_len, const void *label_frames, const void *frame_labels,
-                                  const void *label_logp, const void *frame_logp) {
-    align_out o;
-    const size_t nl = (size_t)batch * max_label_len, nt = (size_t)batch * T;
-    o.lf = 0;
-    o.fl = o.lf + (label_frames ? nl : 0);
-    o.ll = o.fl + (frame_labels ? nt : 0);
-    o.fp = o.ll + (label_logp ? nl : 0);
-    o.sc = o.fp + (frame_logp ? nt : 0);
-    o.total = o.sc + (size_t)batch;
-    return o;
-}
-
-static int align_download(const align_out *o, const float *d_o, int batch, int T, int max_label_len, int *label_frames, int *frame_labels,
-                          float *label_logp, float *frame_logp, float *scores) {
-    const size_t nl = (size_t)batch * max_label_len * sizeof(float), nt = (size_t)batch * T * sizeof(float);
-    if (label_frames && nl && nntk_shim_download(label_frames, d_o + o->lf, nl)) return -1;
-    if (frame_labels && nntk_shim_download(frame_labels, d_o + o->fl, nt)) return -1;
-    if (label_logp && nl && nntk_shim_download(label_logp, d_o + o->ll, nl)) return -1;
-    if (frame_logp && nntk_shim_download(frame_logp, d_o + o->fp, nt)) return -1;
-    return nntk_shim_download(scores, d_o + o->sc, (size_t)batch * sizeof(float));
+    return align_device("nntk_rnnt_align_device", ALIGN_STORED(d_logits), batch, T, V, input_lengths, labels, label_lengths, max_label_len,
+                        blank, ALIGN_PATH(d_label_frames, d_frame_labels, d_label_logp, d_frame_logp, d_scores), d_workspace);
 }
 
 int nntk_rnnt_align(const float *logits, int batch, int T, int V, const int *input_lengths, const int *labels, const int *label_lengths,
                     int max_label_len, int blank, int *label_frames, int *frame_labels, float *label_logp, float *frame_logp,
                     float *scores) {
-    static const char who[] = "nntk_rnnt_align";
-    nntk_shim_clear_error();
-    if (rnnt_check(who, batch, T, V, input_lengths, labels, label_lengths, max_label_len, blank)) return -1;
-    if (batch == 0) return 0;
-    if (rnnt_check_ptr(who, "logits", logits, 4) || align_check_outputs(who, label_frames, frame_labels, label_logp, frame_logp, scores))
-        return -1;
-    const size_t n = (size_t)batch * T * (max_label_len + 1) * V;
-    const align_out o = align_out_layout(batch, T, max_label_len, label_frames, frame_labels, label_logp, frame_logp);
-    float *d_x = nntk_devbuf_reserve(&t_a, n + 4);
-    float *d_o = nntk_devbuf_reserve(&t_b, o.total + 4);
-    float *d_ws = nntk_devbuf_reserve(&t_c, nntk_shim_rnnt_align_workspace_floats(batch, T, max_label_len));
-    if (!d_x || !d_o || !d_ws) return -1;
-    if (nntk_shim_upload(d_x, logits, n * sizeof(float))) return -1;
-    if (nntk_rnnt_align_device(d_x, batch, T, V, input_lengths, labels, label_lengths, max_label_len, blank,
-                               label_frames ? (int *)(d_o + o.lf) : NULL, frame_labels ? (int *)(d_o + o.fl) : NULL,
-                               label_logp ? d_o + o.ll : NULL, frame_logp ? d_o + o.fp : NULL, d_o + o.sc, d_ws)) return -1;
-    return align_download(&o, d_o, batch, T, max_label_len, label_frames, frame_labels, label_logp, frame_logp, scores);
+    return align_host("nntk_rnnt_align", "nntk_rnnt_align_device", ALIGN_STORED(logits), batch, T, V, input_lengths, labels, label_lengths,
+                      max_label_len, blank, ALIGN_PATH(label_frames, frame_labels, label_logp, frame_logp, scores));
 }
 
 size_t nntk_rnnt_fused_align_workspace_floats(int batch, int T, int max_label_len, int J, int V) {
-    return nntk_shim_rnnt_fused_align_workspace_floats(batch, T, max_label_len, J, V);
+    return nntk_shim_rnnt_align_workspace_floats(ALIGN_FUSED(NULL, NULL, NULL, J, 0), batch, T, V, max_label_len);
 }
 
 int nntk_rnnt_fused_align_device(const float *d_enc, const float *d_pred, const float *d_out, int batch, int T, int J, int V, int activation,
                                  const int *input_lengths, const int *labels, const int *label_lengths, int max_label_len, int blank,
                                  int *d_label_frames, int *d_frame_labels, float *d_label_logp, float *d_frame_logp, float *d_scores,
                                  float *d_workspace) {
-    static const char who[] = "nntk_rnnt_fused_align_device";
-    nntk_shim_clear_error();
-    if (fused_check(who, batch, T, J, V, activation, input_lengths, labels, label_lengths, max_label_len, blank, NULL, NULL, NULL)) return -1;
-    if (batch == 0) return 0;
-    if (rnnt_check_ptr(who, "d_enc", d_enc, 4) || rnnt_check_ptr(who, "d_pred", d_pred, 4) || rnnt_check_ptr(who, "d_out", d_out, 4) ||
-        rnnt_check_ptr(who, "d_workspace", d_workspace, 16) ||
-        align_check_outputs(who, d_label_frames, d_frame_labels, d_label_logp, d_frame_logp, d_scores)) return -1;
-    const size_t f = sizeof(float), nl = (size_t)batch * max_label_len * f, nt = (size_t)batch * T * f;
-    const fused_span sp[] = {{"d_label_frames", (uintptr_t)d_label_frames, nl}, {"d_frame_labels", (uintptr_t)d_frame_labels, nt},
-                             {"d_label_logp", (uintptr_t)d_label_logp, nl}, {"d_frame_logp", (uintptr_t)d_frame_logp, nt},
-                             {"d_scores", (uintptr_t)d_scores, (size_t)batch * f},
-                             {"d_enc", (uintptr_t)d_enc, (size_t)batch * T * J * f},
-                             {"d_pred", (uintptr_t)d_pred, (size_t)batch * (max_label_len + 1) * J * f},
-                             {"d_out", (uintptr_t)d_out, ((size_t)J + 1) * V * f},
-                             {"d_workspace", (uintptr_t)d_workspace,
-                              nntk_shim_rnnt_fused_align_workspace_floats(batch, T, max_label_len, J, V) * f}};
-    if (align_overlap(who, sp, 5, 9)) return -1;
-    int *len = (int *)malloc((size_t)batch * sizeof(int));
-    if (!len) NNTK_FAIL("out of host memory");
-    for (int b = 0; b < batch; ++b) len[b] = input_lengths ? input_lengths[b] : T;
-    int rc = nntk_shim_rnnt_fused_align(d_enc, d_pred, d_out, batch, T, J, V, activation, len, labels, label_lengths, max_label_len, blank,
-                                        d_label_frames, d_frame_labels, d_label_logp, d_frame_logp, d_scores, d_workspace);
-    free(len);
-    return rc;
+    return align_device("nntk_rnnt_fused_align_device", ALIGN_FUSED(d_enc, d_pred, d_out, J, activation), batch, T, V, input_lengths, labels,
+                        label_lengths, max_label_len, blank, ALIGN_PATH(d_label_frames, d_frame_labels, d_label_logp, d_frame_logp, d_scores),
+                        d_workspace);
 }
 
 int nntk_rnnt_fused_align(const float *enc, const float *pred, const float *out, int batch, int T, int J, int V, int activation,
                           const int *input_lengths, const int *labels, const int *label_lengths, int max_label_len, int blank,
                           int *label_frames, int *frame_labels, float *label_logp, float *frame_logp, float *scores) {
-    static const char who[] = "nntk_rnnt_fused_align";
-    nntk_shim_clear_error();
-    if (fused_check(who, batch, T, J, V, activation, input_lengths, labels, label_lengths, max_label_len, blank, NULL, NULL, NULL)) return -1;
-    if (batch == 0) return 0;
-    if (rnnt_check_ptr(who, "enc", enc, 4) || rnnt_check_ptr(who, "pred", pred, 4) || rnnt_check_ptr(who, "out", out, 4) ||
-        align_check_outputs(who, label_frames, frame_labels, label_logp, frame_logp, scores)) return -1;
-    const size_t up = 3, U1 = (size_t)max_label_len + 1;
-    const size_t ne = ((size_t)batch * T * J + up) & ~up, npd = ((size_t)batch * U1 * J + up) & ~up, nw = (((size_t)J + 1) * V + up) & ~up;
-    const align_out o = align_out_layout(batch, T, max_label_len, label_frames, frame_labels, label_logp, frame_logp);
-    float *d_in = nntk_devbuf_reserve(&t_a, ne + npd + nw + 4);
-    float *d_o = nntk_devbuf_reserve(&t_b, o.total + 4);
-    float *d_ws = nntk_devbuf_reserve(&t_c, nntk_shim_rnnt_fused_align_workspace_floats(batch, T, max_label_len, J, V));
-    if (!d_in || !d_o || !d_ws) return -1;
-    float *d_enc = d_in, *d_pred = d_in + ne, *d_out = d_pred + npd;
-    if (nntk_shim_upload(d_enc, enc, (size_t)batch * T * J * sizeof(float)) || nntk_shim_upload(d_pred, pred, (size_t)batch * U1 * J * sizeof(float)) ||
-        nntk_shim_upload(d_out, out, ((size_t)J + 1) * V * sizeof(float))) return -1;
-    if (nntk_rnnt_fused_align_device(d_enc, d_pred, d_out, batch, T, J, V, activation, input_lengths, labels, label_lengths, max_label_len, blank,
-                                     label_frames ? (int *)(d_o + o.lf) : NULL, frame_labels ? (int *)(d_o + o.fl) : NULL,
-                                     label_logp ? d_o + o.ll : NULL, frame_logp ? d_o + o.fp : NULL, d_o + o.sc, d_ws)) return -1;
-    return align_download(&o, d_o, batch, T, max_label_len, label_frames, frame_labels, label_logp, frame_logp, scores);
+    return align_host("nntk_rnnt_fused_align", "nntk_rnnt_fused_align_device", ALIGN_FUSED(enc, pred, out, J, activation), batch, T, V,
+                      input_lengths, labels, label_lengths, max_label_len, blank,
+                      ALIGN_PATH(label_frames, frame_labels, label_logp, frame_logp, scores));
 }

@@ -962,6 +962,26 @@ def _rnnt_labels(labels, label_lengths, B, maxL):
     return lab, _host_ints(label_lengths, B, "label_lengths")
 
 
+def _rnnt_workspace(workspace, dev, size_fn, *args):
+    """the workspace of a device call: at least ``size_fn(*args)`` floats (a size function of the C API, by name), made if not given"""
+    import torch
+    need = getattr(capi.load(), size_fn)(*args)
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.float32, device=dev)
+    assert workspace.numel() >= need, "workspace: %s%s floats" % (size_fn, args)
+    return workspace
+
+
+def _rnnt_fused_dims(enc, pred, out_block):
+    """enc [B,T,J], pred [B,U1,J] and the Dense block W [J,V] | b [V] (torch or numpy) -> (B, T, U1, J, V)"""
+    B, T, J = enc.shape
+    U1 = pred.shape[1]
+    n = int(np.prod(out_block.shape))
+    assert tuple(pred.shape) == (B, U1, J), "pred: [B, U1, J] with enc's B and J"
+    assert n % (J + 1) == 0, "out_block: W [J, V] | b [V]"
+    return B, T, U1, J, n // (J + 1)
+
+
 def rnnt_loss_device(logits, labels, label_lengths=None, input_lengths=None, blank=0, want_grad=True, loss=None, dlogits=None, workspace=None):
     """``nntk_rnnt_loss_device``: logits [B,T,U1,V] device tensor of UNNORMALISED scores (U1 = max_label_len + 1); labels: a list of
     per-row lists, or a padded int array [B, U1 - 1] with label_lengths.  Returns (loss rows [B], d loss / d logits [B,T,U1,V] or None)."""
@@ -969,17 +989,13 @@ def rnnt_loss_device(logits, labels, label_lengths=None, input_lengths=None, bla
     B, T, U1, V = logits.shape
     lab, ll = _rnnt_labels(labels, label_lengths, B, U1 - 1)
     il, ilp = _ctc_lengths(input_lengths, B)
-    L = capi.load()
-    need = L.nntk_rnnt_workspace_floats(B, T, U1 - 1, int(want_grad))
-    if workspace is None:
-        workspace = torch.empty(need, dtype=torch.float32, device=logits.device)
-    assert workspace.numel() >= need, "workspace: nntk_rnnt_workspace_floats(B, T, max_label_len, want_grad) floats"
+    workspace = _rnnt_workspace(workspace, logits.device, "nntk_rnnt_workspace_floats", B, T, U1 - 1, int(want_grad))
     if loss is None:
         loss = torch.empty(B, dtype=torch.float32, device=logits.device)
     if want_grad and dlogits is None:
         dlogits = torch.empty_like(logits)
-    check(L.nntk_rnnt_loss_device(_dp(logits), B, T, V, ilp, lab.ctypes.data_as(capi.ip), ll.ctypes.data_as(capi.ip), U1 - 1, blank,
-                                  _dp(loss), _dp(dlogits) if want_grad else None, _dp(workspace)), "nntk_rnnt_loss_device")
+    check(capi.load().nntk_rnnt_loss_device(_dp(logits), B, T, V, ilp, lab.ctypes.data_as(capi.ip), ll.ctypes.data_as(capi.ip), U1 - 1, blank,
+                                            _dp(loss), _dp(dlogits) if want_grad else None, _dp(workspace)), "nntk_rnnt_loss_device")
     return loss, (dlogits if want_grad else None)
 
 
@@ -1030,37 +1046,27 @@ def rnnt_fused_loss_device(enc, pred, out_block, labels, label_lengths=None, inp
     labels as for ``rnnt_loss_device``.  Returns (loss rows [B], d enc, d pred, d out_block), the gradients of the plain sum of the loss
     rows (None without want_grad).  The [B,T,U1,V] logits are never stored."""
     import torch
-    B, T, J = enc.shape
-    U1 = pred.shape[1]
-    assert tuple(pred.shape) == (B, U1, J), "pred: [B, U1, J] with enc's B and J"
-    assert out_block.numel() % (J + 1) == 0, "out_block: W [J, V] | b [V]"
-    V = out_block.numel() // (J + 1)
+    B, T, U1, J, V = _rnnt_fused_dims(enc, pred, out_block)
     lab, ll = _rnnt_labels(labels, label_lengths, B, U1 - 1)
     il, ilp = _ctc_lengths(input_lengths, B)
-    L = capi.load()
-    need = L.nntk_rnnt_fused_workspace_floats(B, T, U1 - 1, J, V, int(want_grad))
-    if workspace is None:
-        workspace = torch.empty(need, dtype=torch.float32, device=enc.device)
-    assert workspace.numel() >= need, "workspace: nntk_rnnt_fused_workspace_floats(B, T, max_label_len, J, V, want_grad) floats"
+    workspace = _rnnt_workspace(workspace, enc.device, "nntk_rnnt_fused_workspace_floats", B, T, U1 - 1, J, V, int(want_grad))
     if loss is None:
         loss = torch.empty(B, dtype=torch.float32, device=enc.device)
     if want_grad:
         denc = torch.empty_like(enc) if denc is None else denc
         dpred = torch.empty_like(pred) if dpred is None else dpred
         dout = torch.empty_like(out_block) if dout is None else dout
-    check(L.nntk_rnnt_fused_loss_device(_dp(enc), _dp(pred), _dp(out_block), B, T, J, V, RNNT_ACTIVATIONS[activation], ilp,
-                                        lab.ctypes.data_as(capi.ip), ll.ctypes.data_as(capi.ip), U1 - 1, blank, _dp(loss),
-                                        _dp(denc) if want_grad else None, _dp(dpred) if want_grad else None,
-                                        _dp(dout) if want_grad else None, _dp(workspace)), "nntk_rnnt_fused_loss_device")
+    check(capi.load().nntk_rnnt_fused_loss_device(_dp(enc), _dp(pred), _dp(out_block), B, T, J, V, RNNT_ACTIVATIONS[activation], ilp,
+                                                  lab.ctypes.data_as(capi.ip), ll.ctypes.data_as(capi.ip), U1 - 1, blank, _dp(loss),
+                                                  _dp(denc) if want_grad else None, _dp(dpred) if want_grad else None,
+                                                  _dp(dout) if want_grad else None, _dp(workspace)), "nntk_rnnt_fused_loss_device")
     return (loss, denc, dpred, dout) if want_grad else (loss, None, None, None)
 
 
 def rnnt_fused_loss(enc, pred, out_block, labels, label_lengths=None, input_lengths=None, blank=0, activation=ACT_TANH, want_grad=True):
     """The host-memory form (``nntk_rnnt_fused_loss``) on numpy arrays."""
     enc, pred, out_block = _f32(enc), _f32(pred), _f32(out_block)
-    B, T, J = enc.shape
-    U1 = pred.shape[1]
-    V = out_block.size // (J + 1)
+    B, T, U1, J, V = _rnnt_fused_dims(enc, pred, out_block)
     lab, ll = _rnnt_labels(labels, label_lengths, B, U1 - 1)
     il, ilp = _ctc_lengths(input_lengths, B)
     loss = np.empty(B, np.float32)
@@ -1071,14 +1077,34 @@ def rnnt_fused_loss(enc, pred, out_block, labels, label_lengths=None, input_leng
     return (loss,) + g
 
 
-def _align_outputs(dev, B, T, maxL, given):
-    """the five outputs of the alignment calls as device tensors, those the caller passed reused"""
+def _rnnt_align_device(entry, size_fn, head, dev, dims, size_args, labels, label_lengths, input_lengths, blank, given, workspace):
+    """Both device forms of the alignment: the C entry by name, its argument head (the score source: the tensors, then B, T and the
+    widths as the entry takes them), dims = (B, T, U1), the workspace size function by name with its arguments, the five outputs as
+    given (None: made here)"""
     import torch
-    shapes = (((B, maxL), torch.int32), ((B, T), torch.int32), ((B, maxL), torch.float32), ((B, T), torch.float32), ((B,), torch.float32))
+    B, T, U1 = dims
+    lab, ll = _rnnt_labels(labels, label_lengths, B, U1 - 1)
+    il, ilp = _ctc_lengths(input_lengths, B)
+    workspace = _rnnt_workspace(workspace, dev, size_fn, *size_args)
+    shapes = (((B, U1 - 1), torch.int32), ((B, T), torch.int32), ((B, U1 - 1), torch.float32), ((B, T), torch.float32), ((B,), torch.float32))
     outs = [torch.empty(s, dtype=d, device=dev) if g is None else g for (s, d), g in zip(shapes, given)]
     for o, (s, d) in zip(outs, shapes):
         assert tuple(o.shape) == s and o.dtype == d and o.is_contiguous(), "alignment outputs: %s %s" % (s, d)
-    return outs
+    check(getattr(capi.load(), entry)(*head, ilp, lab.ctypes.data_as(capi.ip), ll.ctypes.data_as(capi.ip), U1 - 1, blank,
+                                      *[C.c_void_p(o.data_ptr()) for o in outs], _dp(workspace)), entry)
+    return tuple(outs)
+
+
+def _rnnt_align_host(entry, head, dims, labels, label_lengths, input_lengths, blank):
+    """Both host forms of the alignment, as ``_rnnt_align_device``"""
+    B, T, U1 = dims
+    lab, ll = _rnnt_labels(labels, label_lengths, B, U1 - 1)
+    il, ilp = _ctc_lengths(input_lengths, B)
+    lf, fl = np.empty((B, U1 - 1), np.int32), np.empty((B, T), np.int32)
+    lp, fp, sc = np.empty((B, U1 - 1), np.float32), np.empty((B, T), np.float32), np.empty(B, np.float32)
+    check(getattr(capi.load(), entry)(*head, ilp, lab.ctypes.data_as(capi.ip), ll.ctypes.data_as(capi.ip), U1 - 1, blank,
+                                      lf.ctypes.data_as(capi.ip), fl.ctypes.data_as(capi.ip), _p(lp), _p(fp), _p(sc)), entry)
+    return lf, fl, lp, fp, sc
 
 
 def rnnt_align_device(logits, labels, label_lengths=None, input_lengths=None, blank=0, label_frames=None, frame_labels=None,
@@ -1087,73 +1113,35 @@ def rnnt_align_device(logits, labels, label_lengths=None, input_lengths=None, bl
     (label_frames [B,U1-1] int32, the frame each label is emitted in, -1 behind the row's labels; frame_labels [B,T] int32, the number of
     labels emitted when each frame is left, -1 behind the row's frames; label_logp [B,U1-1] and frame_logp [B,T] float32, ln of those
     label and blank emissions, 0 in the padding; scores [B] float32 = ln of the path's probability, -inf where there is no path)"""
-    import torch
     B, T, U1, V = logits.shape
-    lab, ll = _rnnt_labels(labels, label_lengths, B, U1 - 1)
-    il, ilp = _ctc_lengths(input_lengths, B)
-    L = capi.load()
-    need = L.nntk_rnnt_align_workspace_floats(B, T, U1 - 1)
-    if workspace is None:
-        workspace = torch.empty(need, dtype=torch.float32, device=logits.device)
-    assert workspace.numel() >= need, "workspace: nntk_rnnt_align_workspace_floats(B, T, max_label_len) floats"
-    outs = _align_outputs(logits.device, B, T, U1 - 1, (label_frames, frame_labels, label_logp, frame_logp, scores))
-    check(L.nntk_rnnt_align_device(_dp(logits), B, T, V, ilp, lab.ctypes.data_as(capi.ip), ll.ctypes.data_as(capi.ip), U1 - 1, blank,
-                                   *[C.c_void_p(o.data_ptr()) for o in outs], _dp(workspace)), "nntk_rnnt_align_device")
-    return tuple(outs)
+    return _rnnt_align_device("nntk_rnnt_align_device", "nntk_rnnt_align_workspace_floats", (_dp(logits), B, T, V), logits.device,
+                              (B, T, U1), (B, T, U1 - 1), labels, label_lengths, input_lengths, blank,
+                              (label_frames, frame_labels, label_logp, frame_logp, scores), workspace)
 
 
 def rnnt_align(logits, labels, label_lengths=None, input_lengths=None, blank=0):
     """The host-memory form (``nntk_rnnt_align``): logits [B,T,U1,V] numpy array."""
     logits = _f32(logits)
     B, T, U1, V = logits.shape
-    lab, ll = _rnnt_labels(labels, label_lengths, B, U1 - 1)
-    il, ilp = _ctc_lengths(input_lengths, B)
-    lf, fl = np.empty((B, U1 - 1), np.int32), np.empty((B, T), np.int32)
-    lp, fp, sc = np.empty((B, U1 - 1), np.float32), np.empty((B, T), np.float32), np.empty(B, np.float32)
-    check(capi.load().nntk_rnnt_align(_p(logits), B, T, V, ilp, lab.ctypes.data_as(capi.ip), ll.ctypes.data_as(capi.ip), U1 - 1, blank,
-                                      lf.ctypes.data_as(capi.ip), fl.ctypes.data_as(capi.ip), _p(lp), _p(fp), _p(sc)), "nntk_rnnt_align")
-    return lf, fl, lp, fp, sc
+    return _rnnt_align_host("nntk_rnnt_align", (_p(logits), B, T, V), (B, T, U1), labels, label_lengths, input_lengths, blank)
 
 
 def rnnt_fused_align_device(enc, pred, out_block, labels, label_lengths=None, input_lengths=None, blank=0, activation=ACT_TANH,
                             label_frames=None, frame_labels=None, label_logp=None, frame_logp=None, scores=None, workspace=None):
     """``nntk_rnnt_fused_align_device``: the alignment of ``rnnt_align_device`` from enc [B,T,J], pred [B,U1,J] and the Dense block
     W [J,V] | b [V], as ``rnnt_fused_loss_device`` takes them; the [B,T,U1,V] logits are never stored."""
-    import torch
-    B, T, J = enc.shape
-    U1 = pred.shape[1]
-    assert tuple(pred.shape) == (B, U1, J), "pred: [B, U1, J] with enc's B and J"
-    assert out_block.numel() % (J + 1) == 0, "out_block: W [J, V] | b [V]"
-    V = out_block.numel() // (J + 1)
-    lab, ll = _rnnt_labels(labels, label_lengths, B, U1 - 1)
-    il, ilp = _ctc_lengths(input_lengths, B)
-    L = capi.load()
-    need = L.nntk_rnnt_fused_align_workspace_floats(B, T, U1 - 1, J, V)
-    if workspace is None:
-        workspace = torch.empty(need, dtype=torch.float32, device=enc.device)
-    assert workspace.numel() >= need, "workspace: nntk_rnnt_fused_align_workspace_floats(B, T, max_label_len, J, V) floats"
-    outs = _align_outputs(enc.device, B, T, U1 - 1, (label_frames, frame_labels, label_logp, frame_logp, scores))
-    check(L.nntk_rnnt_fused_align_device(_dp(enc), _dp(pred), _dp(out_block), B, T, J, V, RNNT_ACTIVATIONS[activation], ilp,
-                                         lab.ctypes.data_as(capi.ip), ll.ctypes.data_as(capi.ip), U1 - 1, blank,
-                                         *[C.c_void_p(o.data_ptr()) for o in outs], _dp(workspace)), "nntk_rnnt_fused_align_device")
-    return tuple(outs)
+    B, T, U1, J, V = _rnnt_fused_dims(enc, pred, out_block)
+    return _rnnt_align_device("nntk_rnnt_fused_align_device", "nntk_rnnt_fused_align_workspace_floats",
+                              (_dp(enc), _dp(pred), _dp(out_block), B, T, J, V, RNNT_ACTIVATIONS[activation]), enc.device, (B, T, U1), (B, T, U1 - 1, J, V), labels, label_lengths, input_lengths, blank,
+                              (label_frames, frame_labels, label_logp, frame_logp, scores), workspace)
 
 
 def rnnt_fused_align(enc, pred, out_block, labels, label_lengths=None, input_lengths=None, blank=0, activation=ACT_TANH):
     """The host-memory form (``nntk_rnnt_fused_align``) on numpy arrays."""
     enc, pred, out_block = _f32(enc), _f32(pred), _f32(out_block)
-    B, T, J = enc.shape
-    U1 = pred.shape[1]
-    V = out_block.size // (J + 1)
-    lab, ll = _rnnt_labels(labels, label_lengths, B, U1 - 1)
-    il, ilp = _ctc_lengths(input_lengths, B)
-    lf, fl = np.empty((B, U1 - 1), np.int32), np.empty((B, T), np.int32)
-    lp, fp, sc = np.empty((B, U1 - 1), np.float32), np.empty((B, T), np.float32), np.empty(B, np.float32)
-    check(capi.load().nntk_rnnt_fused_align(_p(enc), _p(pred), _p(out_block), B, T, J, V, RNNT_ACTIVATIONS[activation], ilp,
-                                            lab.ctypes.data_as(capi.ip), ll.ctypes.data_as(capi.ip), U1 - 1, blank,
-                                            lf.ctypes.data_as(capi.ip), fl.ctypes.data_as(capi.ip), _p(lp), _p(fp), _p(sc)),
-          "nntk_rnnt_fused_align")
-    return lf, fl, lp, fp, sc
+    B, T, U1, J, V = _rnnt_fused_dims(enc, pred, out_block)
+    return _rnnt_align_host("nntk_rnnt_fused_align", (_p(enc), _p(pred), _p(out_block), B, T, J, V, RNNT_ACTIVATIONS[activation]),
+                            (B, T, U1), labels, label_lengths, input_lengths, blank)
 
 
 def _ipv(t):

@@ -14,6 +14,8 @@ import math
 
 import numpy as np
 
+import rnnt_cases as K
+import rnnt_fused_reference as FR
 import rnnt_reference as R
 
 
@@ -125,8 +127,7 @@ def random_case(B, T, maxL, V, scale, seed=0, lens=None, ulens=None, blank=0):
     x = (scale * rng.standard_normal((B, T, maxL + 1, V))).astype(np.float32)
     lens = [T] * B if lens is None else [int(rng.integers(lens[0], lens[1] + 1)) for _ in range(B)]
     ulens = [maxL] * B if ulens is None else [int(k) for k in ulens]
-    classes = [k for k in range(V) if k != blank]
-    labels = [[classes[int(k)] for k in rng.integers(0, len(classes), n)] for n in ulens]
+    labels = [K.labels(rng, n, V, blank) for n in ulens]
     return dict(x=x, labels=labels, lens=lens, blank=blank)
 
 
@@ -239,61 +240,12 @@ def left_out(name):
     return [b for b, r in enumerate(reference(name)[0]) if not r["gap"] > gap_threshold(c["lens"][b], len(c["labels"][b]))]
 
 
-# ---- the fused form: logits in float64 from the joiner's inputs ----
-
-def fused_logits(enc, pred, out_block, labels, lens, kind):
-    """float64 [B][T][U1][V] = act(enc + pred) W + b on the live cells, zeros in the padding (whose inputs may hold NaN)"""
-    enc, pred = np.asarray(enc, np.float64), np.asarray(pred, np.float64)
-    B, T, J = enc.shape
-    U1 = pred.shape[1]
-    out_block = np.asarray(out_block, np.float64).reshape(-1)
-    V = out_block.size // (J + 1)
-    W, bias = out_block[:J * V].reshape(J, V), out_block[J * V:]
-    x = np.zeros((B, T, U1, V))
-    for b in range(B):
-        n, u1 = int(lens[b]), len(labels[b]) + 1
-        x[b, :n, :u1] = R._act(kind, enc[b, :n, None, :] + pred[b, None, :u1, :]) @ W + bias
-    return x
-
+# ---- the fused form: the cases of tests/rnnt_cases.py, the forwards of tests/rnnt_fused_reference.py ----
 
 def torch_fused_scores(enc, pred, out_block, labels, lens, blank, kind, dtype):
     """the fused form's scores in torch at `dtype` on the CPU -> float64 numpy [B]"""
-    import torch
-    B, T, J = enc.shape
-    f = lambda a: torch.from_numpy(np.nan_to_num(np.asarray(a, np.float64), nan=0.0)).to(dtype)
-    e, p, o = f(enc), f(pred), f(np.asarray(out_block).reshape(-1))
-    V = o.shape[0] // (J + 1)
-    W, bias = o[:J * V].view(J, V), o[J * V:]
-    act = torch.tanh if kind == "tanh" else torch.relu if kind == "relu" else (lambda x: x)
-    out = np.zeros(B)
-    for b in range(B):
-        n, u1 = int(lens[b]), len(labels[b]) + 1
-        out[b] = float(torch_score_row(act(e[b, :n, None, :] + p[b, None, :u1, :]) @ W + bias, list(labels[b]), blank))
-    return out
-
-
-def _labels(rng, n, V, blank):
-    classes = [k for k in range(V) if k != blank]
-    return [classes[int(k)] for k in rng.integers(0, len(classes), n)]
-
-
-def fused_ragged(J, V, blank, seed=0):
-    """the ragged case of tests/test_gpu_rnnt_fused.py: input lengths 7 / 4 / 1 of T = 7, label lengths 3 / 0 / 5 of max_label_len 5"""
-    rng = np.random.default_rng(1000 * J + V + 7 * blank + seed)
-    a, c = _labels(rng, 1, V, blank)[0], _labels(rng, 5, V, blank)
-    c[2] = c[1]
-    if blank != V - 1:
-        c[4] = V - 1
-    sc = 1.0 / np.sqrt(J)
-    return dict(enc=rng.uniform(-1.5, 1.5, (3, 7, J)).astype(np.float32), pred=rng.uniform(-1.5, 1.5, (3, 6, J)).astype(np.float32),
-                out=np.concatenate([rng.uniform(-3 * sc, 3 * sc, J * V), rng.uniform(-1, 1, V)]).astype(np.float32),
-                labels=[[a, a, _labels(rng, 1, V, blank)[0]], [], c], lens=[7, 4, 1], blank=blank)
-
-
-def fused_single(T, U, J, V, blank, seed, scale=1.0):
-    rng = np.random.default_rng(seed)
-    return dict(enc=rng.uniform(-1, 1, (1, T, J)).astype(np.float32), pred=rng.uniform(-1, 1, (1, U + 1, J)).astype(np.float32),
-                out=rng.uniform(-scale, scale, J * V + V).astype(np.float32), labels=[_labels(rng, U, V, blank)], lens=[T], blank=blank)
+    rows = FR.torch_fused_logits(enc, pred, out_block, labels, lens, kind, dtype)[1]
+    return np.array([float(torch_score_row(x, list(labels[b]), blank)) for b, x in enumerate(rows)])
 
 
 FUSED_RAGGED = [(5, 5, 4), (5, 5, 2), (67, 257, 100), (67, 257, 256)]
@@ -308,12 +260,12 @@ FUSED_GAP = 1e-3
 def fused_case(name):
     if name.startswith("ragged"):
         J, V, blank = (int(k) for k in name.split("_")[1:])
-        return fused_ragged(J, V, blank)
+        return K.fused_ragged(J, V, blank)
     if name.startswith("cells"):
         T, U = (int(k) for k in name.split("_")[1:])
-        return fused_single(T, U, 5, 5, 1, 40 + U, scale=3.0)
+        return K.fused_single(T, U, 5, 5, 1, 40 + U, scale=3.0)
     if name == "wide":                               # U = 300: rnnt_viterbi_kernel<2> behind the fused emission writer
-        return fused_single(4, 300, 6, 4, 0, 11, scale=6.0)
+        return K.fused_single(4, 300, 6, 4, 0, 11, scale=6.0)
     raise KeyError(name)
 
 
@@ -322,7 +274,7 @@ def fused_reference(name, kind):
     """(float64 logits, the float64 rows of viterbi on them, the float32 torch scores)"""
     import torch
     c = fused_case(name)
-    x = fused_logits(c["enc"], c["pred"], c["out"], c["labels"], c["lens"], kind)
+    x = FR.fused_forward(c["enc"], c["pred"], c["out"], c["labels"], c["lens"], kind)[1]
     return x, viterbi(x, c["labels"], c["lens"], c["blank"]), torch_fused_scores(c["enc"], c["pred"], c["out"], c["labels"], c["lens"],
                                                                                  c["blank"], kind, torch.float32)
 

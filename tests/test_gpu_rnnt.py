@@ -29,27 +29,13 @@ import numpy as np
 import pytest
 import torch
 
+import rnnt_cases as K
 import rnnt_reference as R
 from nntoolkitcore_amd import capi, layers as NL
 
 pytestmark = pytest.mark.gpu
 
-FACTOR = 4.0
-FLOOR = 16 * 2.0 ** -24
-
-# the constants of rnnt.hip that decide the path, mirrored so that a moved threshold turns the premise assertions red
-CTC_THREADS, LDS_OPT_IN, RNNT_JOINT_UNROLL = 256, 48 * 1024, 4
-
-
-def _lattice_path(max_label_len):
-    """(NJ of the rnnt_lattice_kernel instantiation, its LDS request in bytes)"""
-    u1 = max_label_len + 1
-    return (1 if u1 <= CTC_THREADS else 2 if u1 <= 2 * CTC_THREADS else 0), 2 * u1 * 16
-
-
-def _labels(rng, n, V, blank):
-    classes = [k for k in range(V) if k != blank]
-    return [classes[int(k)] for k in rng.integers(0, len(classes), n)]
+RNNT_JOINT_UNROLL = 4                                # of rnnt.hip, mirrored; the constants that pick a lattice kernel: rnnt_cases.py
 
 
 RAGGED = [(2, 0), (2, 1), (5, 0), (5, 4), (5, 2), (64, 0), (64, 63), (64, 17), (257, 0), (257, 256), (257, 100), (260, 7)]
@@ -58,21 +44,17 @@ RAGGED = [(2, 0), (2, 1), (5, 0), (5, 4), (5, 2), (64, 0), (64, 63), (64, 17), (
 def _case(name):
     rng = np.random.default_rng(sum(map(ord, name)))
     if name.startswith("ragged"):                    # batch 3, T = 7 with lengths (7, 4, 1), max_label_len 5 with label lengths (3, 0, 5)
-        V, blank = (int(v) for v in name.split("_")[1:])
-        a, c = _labels(rng, 2, V, blank)[0], _labels(rng, 5, V, blank)
-        c[2] = c[1]                                   # (row 2 repeats a label where V allows a choice at all; row 0 always does)
-        return dict(x=rng.uniform(-3, 3, (3, 7, 6, V)).astype(np.float32), labels=[[a, a, _labels(rng, 1, V, blank)[0]], [], c],
-                    lens=[7, 4, 1], blank=blank)
+        return K.ragged(*(int(v) for v in name.split("_")[1:]))
     if name == "U300":                               # a second, short row inside the wide lattice
-        return dict(x=rng.uniform(-2, 2, (2, 5, 301, 3)).astype(np.float32), labels=[_labels(rng, 300, 3, 1), [0, 2]], lens=[5, 3], blank=1)
+        return dict(x=rng.uniform(-2, 2, (2, 5, 301, 3)).astype(np.float32), labels=[K.labels(rng, 300, 3, 1), [0, 2]], lens=[5, 3], blank=1)
     if name == "T300":
         return dict(x=rng.uniform(-2, 2, (1, 300, 3, 3)).astype(np.float32), labels=[[1, 1]], lens=[300], blank=0)
     if name == "flat_T400_U200":                     # binomial(599, 200) = 1e164 paths of equal mass
-        return dict(x=np.zeros((1, 400, 201, 3), np.float32), labels=[_labels(rng, 200, 3, 2)], lens=[400], blank=2)
+        return dict(x=np.zeros((1, 400, 201, 3), np.float32), labels=[K.labels(rng, 200, 3, 2)], lens=[400], blank=2)
     if name == "U600":
-        return dict(x=rng.uniform(-2, 2, (1, 3, 601, 3)).astype(np.float32), labels=[_labels(rng, 600, 3, 0)], lens=[3], blank=0)
+        return dict(x=rng.uniform(-2, 2, (1, 3, 601, 3)).astype(np.float32), labels=[K.labels(rng, 600, 3, 0)], lens=[3], blank=0)
     if name == "U1600":
-        return dict(x=rng.uniform(-2, 2, (2, 2, 1601, 3)).astype(np.float32), labels=[_labels(rng, 1600, 3, 0), [1]], lens=[2, 1], blank=0)
+        return dict(x=rng.uniform(-2, 2, (2, 2, 1601, 3)).astype(np.float32), labels=[K.labels(rng, 1600, 3, 0), [1]], lens=[2, 1], blank=0)
     if name == "underflow":
         # V = 8: blank 0, labels 1..4, class 7 takes the mass everywhere.  Off the path every needed score lies 200 below it; on the path
         # the needed score equals it, except in two cells where it lies 120 below: one likely path, e^-240 of the mass on it
@@ -100,14 +82,6 @@ def _reference(name):
     return l64, g64, l32, g32
 
 
-def _with_nan_padding(c):
-    x = c["x"].copy()
-    for b, (n, lab) in enumerate(zip(c["lens"], c["labels"])):
-        x[b, n:] = np.nan
-        x[b, :, len(lab) + 1:] = np.nan
-    return x
-
-
 def _run(gpu, x, labels, lens, blank, want_grad=True):
     """outputs prefilled with NaN: every element has to be written"""
     d = torch.from_numpy(x).to(gpu)
@@ -128,13 +102,13 @@ def _assert_close(tag, loss, grad, ref):
         gs = np.abs(g64[b]).max()
         ge, ge32 = np.abs(grad[b] - g64[b]).max() / gs, np.abs(g32[b] - g64[b]).max() / gs
         print("%s row %d grad (max |g| %.3g): err %.2e, torch f32 err %.2e, ratio %.3f" % (tag, b, gs, ge, ge32, ge / max(ge32, 1e-300)))
-        assert e <= max(FACTOR * e32, FLOOR), (tag, b, e, e32)
-        assert ge <= max(FACTOR * ge32, FLOOR), (tag, b, ge, ge32)
+        assert e <= max(K.FACTOR * e32, K.FLOOR), (tag, b, e, e32)
+        assert ge <= max(K.FACTOR * ge32, K.FLOOR), (tag, b, ge, ge32)
 
 
 def _check(gpu, name):
     c = _case(name)
-    loss, grad = _run(gpu, _with_nan_padding(c), c["labels"], c["lens"], c["blank"])
+    loss, grad = _run(gpu, K.with_nan_padding(c), c["labels"], c["lens"], c["blank"])
     assert torch.isfinite(loss).all() and not torch.isnan(grad).any()
     for b, (n, lab) in enumerate(zip(c["lens"], c["labels"])):
         assert not grad[b, n:].any() and not grad[b, :, len(lab) + 1:].any(), (name, b)      # exact zeros in the padding
@@ -145,15 +119,15 @@ def _check(gpu, name):
 @pytest.mark.parametrize("V,blank", RAGGED)
 def test_ragged_batch_matches_float64(gpu, V, blank):
     c, _, _ = _check(gpu, "ragged_%d_%d" % (V, blank))
-    assert c["labels"][0][0] == c["labels"][0][1] and [len(r) for r in c["labels"]] == [3, 0, 5] and _lattice_path(5)[0] == 1
+    assert c["labels"][0][0] == c["labels"][0][1] and [len(r) for r in c["labels"]] == [3, 0, 5] and K.lattice_path(5)[0] == 1
 
 
 @pytest.mark.parametrize("name,nj,opt_in", [("U300", 2, False), ("T300", 1, False), ("flat_T400_U200", 1, False), ("U600", 0, False),
                                             ("U1600", 0, True)])
 def test_lattices_wider_than_one_pass_of_lanes(gpu, name, nj, opt_in):
     c = _case(name)
-    got_nj, lds = _lattice_path(c["x"].shape[2] - 1)
-    assert (got_nj, lds > LDS_OPT_IN) == (nj, opt_in), (name, got_nj, lds)
+    got_nj, lds = K.lattice_path(c["x"].shape[2] - 1)
+    assert (got_nj, lds > K.LDS_OPT_IN) == (nj, opt_in), (name, got_nj, lds)
     _, loss, _ = _check(gpu, name)
     if name == "flat_T400_U200":                     # ln 3^600 - ln binomial(599, 200): the path count alone is past the f32 range
         assert 280.0 < float(loss[0]) < 283.0
@@ -174,7 +148,7 @@ def test_structure(gpu, name):
     """sums over V, padding, determinism, loss-only bits, row independence -- all with the outputs prefilled with NaN (_run) and NaN in
     every padding cell of the scores"""
     c = _case(name)
-    x = _with_nan_padding(c)
+    x = K.with_nan_padding(c)
     B, T, U1, V = x.shape
     loss, grad = _run(gpu, x, c["labels"], c["lens"], c["blank"])
     g64 = _reference(name)[1]
@@ -259,7 +233,7 @@ def test_joiner_forward_and_backward(gpu, kind, B, T, U1, J):
         o64 = R.joint(enc, pred, kind)
         err, e32 = np.abs(o.double().numpy() - o64).max(), np.abs(t32.double().numpy() - o64).max()
         print("joiner tanh J %d: err %.2e, torch f32 err %.2e" % (J, err, e32))
-        assert err <= max(FACTOR * e32, FLOOR), (err, e32)
+        assert err <= max(K.FACTOR * e32, K.FLOOR), (err, e32)
     denc = torch.full((B, T, J), float("nan"), device=gpu)
     dpred = torch.full((B, U1, J), float("nan"), device=gpu)
     NL.rnnt_joint_backward_device(out, d, kind, denc=denc, dpred=dpred)
@@ -273,7 +247,7 @@ def test_joiner_forward_and_backward(gpu, kind, B, T, U1, J):
         sc = np.abs(ref).max()
         err, e32 = np.abs(got.cpu().double().numpy() - ref).max() / sc, np.abs(f32.double().numpy() - ref).max() / sc
         print("joiner %s %s J %d: err %.2e, torch f32 err %.2e" % (kind, nm, J, err, e32))
-        assert err <= max(FACTOR * e32, FLOOR), (nm, err, e32)
+        assert err <= max(K.FACTOR * e32, K.FLOOR), (nm, err, e32)
 
 
 def test_end_to_end_one_training_step(gpu):

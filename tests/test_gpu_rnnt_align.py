@@ -27,26 +27,17 @@ import pytest
 import torch
 
 import rnnt_align_reference as A
+import rnnt_cases as K
 import rnnt_reference as R
 from nntoolkitcore_amd import capi, layers as NL
 
 pytestmark = pytest.mark.gpu
 
-FACTOR = 4.0
-FLOOR = 16 * 2.0 ** -24
 SENT_I, SENT_F = -77, 7.5                            # what the outputs are prefilled with: every element has to be written
 
 
 def _logp_tol(v):
     return 4 * 2.0 ** -23 + abs(v) * 2.0 ** -23
-
-
-def _with_nan_padding(c):
-    x = c["x"].copy()
-    for b, (n, lab) in enumerate(zip(c["lens"], c["labels"])):
-        x[b, n:] = np.nan
-        x[b, :, len(lab) + 1:] = np.nan
-    return x
 
 
 def _outputs(gpu, B, T, maxL):
@@ -108,7 +99,7 @@ def _assert_matches(tag, got, rows, s32, lens, labels, allow_left_out=0.25):
         assert np.isfinite(sc[b]), (tag, b)
         e, e32 = abs(sc[b] - r["score"]) / abs(r["score"]), abs(s32[b] - r["score"]) / abs(r["score"])
         print("%s row %d score %.9g: err %.2e, torch f32 err %.2e, gap %.2e" % (tag, b, r["score"], e, e32, r["gap"]))
-        assert e <= max(FACTOR * e32, FLOOR), (tag, b, e, e32)
+        assert e <= max(K.FACTOR * e32, K.FLOOR), (tag, b, e, e32)
         if r["gap"] > A.gap_threshold(n, U):
             assert lf[b, :U].tolist() == r["label_frames"].tolist() and fl[b, :n].tolist() == r["frame_labels"].tolist(), (tag, b)
         else:
@@ -119,7 +110,7 @@ def _assert_matches(tag, got, rows, s32, lens, labels, allow_left_out=0.25):
 def _check(gpu, name, allow_left_out=0.25, nan_padding=True):
     c = A.case(name)
     rows, s32 = A.reference(name)
-    got = _run(gpu, _with_nan_padding(c) if nan_padding else c["x"], c["labels"], c["lens"], c["blank"])
+    got = _run(gpu, K.with_nan_padding(c) if nan_padding else c["x"], c["labels"], c["lens"], c["blank"])
     lps = [R.log_softmax(c["x"][b, :n, :len(lab) + 1]) for b, (n, lab) in enumerate(zip(c["lens"], c["labels"]))]
     _assert_valid(name, got, lps, c["labels"], c["lens"], c["blank"])
     _assert_matches(name, got, rows, s32, c["lens"], c["labels"], allow_left_out)
@@ -153,16 +144,16 @@ def test_tie_break_on_flat_scores(gpu):
 
 def test_against_the_loss(gpu):
     c, (lf, _, _, _, sc) = _check(gpu, "peaked")
-    d = torch.from_numpy(_with_nan_padding(c)).to(gpu)
+    d = torch.from_numpy(K.with_nan_padding(c)).to(gpu)
     loss, _ = NL.rnnt_loss_device(d, c["labels"], input_lengths=c["lens"], blank=c["blank"], want_grad=False)
     loss = loss.cpu().numpy()
     for b, lab in enumerate(c["labels"]):
         assert lf[b, :len(lab)].tolist() == c["paths"][b]
-        assert abs(sc[b] + loss[b]) <= FLOOR * max(1.0, abs(float(loss[b]))) + 1e-9, (b, sc[b], loss[b])
+        assert abs(sc[b] + loss[b]) <= K.FLOOR * max(1.0, abs(float(loss[b]))) + 1e-9, (b, sc[b], loss[b])
     c, (_, _, _, _, sc) = _check(gpu, "random")
     loss, _ = NL.rnnt_loss_device(torch.from_numpy(c["x"]).to(gpu), c["labels"], input_lengths=c["lens"], blank=c["blank"], want_grad=False)
     loss = loss.cpu().numpy()
-    assert (sc <= -loss + FLOOR * np.abs(loss)).all()
+    assert (sc <= -loss + K.FLOOR * np.abs(loss)).all()
 
 
 def test_range(gpu):
@@ -200,10 +191,7 @@ def test_against_greedy_decoding(gpu):
 def _check_fused(gpu, name, kind):
     c = A.fused_case(name)
     x64, rows, s32 = A.fused_reference(name, kind)
-    enc, pred = c["enc"].copy(), c["pred"].copy()
-    for b, (n, lab) in enumerate(zip(c["lens"], c["labels"])):
-        enc[b, n:] = np.nan
-        pred[b, len(lab) + 1:] = np.nan
+    enc, pred = K.with_nan_padding(c)
     got = _run_fused(gpu, enc, pred, c["out"], c["labels"], c["lens"], c["blank"], kind)
     plain = _run(gpu, x64.astype(np.float32), c["labels"], c["lens"], c["blank"])
     assert np.array_equal(got[0], plain[0]) and np.array_equal(got[1], plain[1]), (name, kind)
@@ -214,7 +202,7 @@ def _check_fused(gpu, name, kind):
         assert got[0][b, :U].tolist() == r["label_frames"].tolist() and got[1][b, :n].tolist() == r["frame_labels"].tolist(), (tag, b)
         e, e32 = abs(got[4][b] - r["score"]) / abs(r["score"]), abs(s32[b] - r["score"]) / abs(r["score"])
         print("%s row %d score %.9g: err %.2e, torch f32 err %.2e" % (tag, b, r["score"], e, e32))
-        assert e <= max(FACTOR * e32, FLOOR), (tag, b, e, e32)
+        assert e <= max(K.FACTOR * e32, K.FLOOR), (tag, b, e, e32)
     # validity against the float64 logits; the fused logits are a float32 chain over J: J 2^-24 max |logit| on top of LOGP_TOL
     lf, fl, llp, flp, sc = got
     J = c["enc"].shape[2]
@@ -257,7 +245,7 @@ def test_structure(gpu):
     """every element written (the sentinels are gone), the same bits over two calls, a row's bits independent of its position in the
     batch and of the T / max_label_len padding"""
     c = A.case("ragged")
-    x = _with_nan_padding(c)
+    x = K.with_nan_padding(c)
     got = _run(gpu, x, c["labels"], c["lens"], c["blank"])
     assert not any((o == SENT_I).any() for o in got[:2]) and not any((o == SENT_F).any() for o in got[2:])
     assert _equal(got, _run(gpu, x, c["labels"], c["lens"], c["blank"]))

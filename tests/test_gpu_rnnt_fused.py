@@ -28,47 +28,14 @@ import numpy as np
 import pytest
 import torch
 
+import rnnt_cases as K
 import rnnt_fused_reference as FR
 import rnnt_reference as R
 from nntoolkitcore_amd import capi, layers as NL
 
 pytestmark = pytest.mark.gpu
 
-FACTOR = 4.0
-FLOOR = 16 * 2.0 ** -24
 NAMES = ("loss", "d_enc", "d_pred", "d_out")
-
-
-def _labels(rng, n, V, blank):
-    classes = [k for k in range(V) if k != blank]
-    return [classes[int(k)] for k in rng.integers(0, len(classes), n)]
-
-
-def _ragged(J, V, blank, seed=0):
-    """the ragged case of test_gpu_rnnt.py: input lengths 7 / 4 / 1 of T = 7, label lengths 3 / 0 / 5 of max_label_len 5"""
-    rng = np.random.default_rng(1000 * J + V + 7 * blank + seed)
-    a, c = _labels(rng, 1, V, blank)[0], _labels(rng, 5, V, blank)
-    c[2] = c[1]
-    if blank != V - 1:
-        c[4] = V - 1                                      # a label in the last (partial) block of V
-    sc = 1.0 / np.sqrt(J)
-    return dict(enc=rng.uniform(-1.5, 1.5, (3, 7, J)).astype(np.float32), pred=rng.uniform(-1.5, 1.5, (3, 6, J)).astype(np.float32),
-                out=np.concatenate([rng.uniform(-3 * sc, 3 * sc, J * V), rng.uniform(-1, 1, V)]).astype(np.float32),
-                labels=[[a, a, _labels(rng, 1, V, blank)[0]], [], c], lens=[7, 4, 1], blank=blank)
-
-
-def _single(T, U, J, V, blank, seed):
-    rng = np.random.default_rng(seed)
-    return dict(enc=rng.uniform(-1, 1, (1, T, J)).astype(np.float32), pred=rng.uniform(-1, 1, (1, U + 1, J)).astype(np.float32),
-                out=rng.uniform(-1, 1, J * V + V).astype(np.float32), labels=[_labels(rng, U, V, blank)], lens=[T], blank=blank)
-
-
-def _with_nan_padding(c):
-    enc, pred = c["enc"].copy(), c["pred"].copy()
-    for b, (n, lab) in enumerate(zip(c["lens"], c["labels"])):
-        enc[b, n:] = np.nan
-        pred[b, len(lab) + 1:] = np.nan
-    return enc, pred
 
 
 def _run(gpu, enc, pred, out, labels, lens, blank, kind, want_grad=True):
@@ -109,11 +76,11 @@ def _assert_close(tag, got, refs):
         assert np.isfinite(g).all(), (tag, nm)
         for i, (e, e32) in enumerate(zip(_errors(g, a, nm != "d_out"), _errors(b, a, nm != "d_out"))):
             print("%s %s[%d]: err %.2e, torch f32 err %.2e, ratio %.3f" % (tag, nm, i, e, e32, e / max(e32, 1e-300)))
-            assert e <= max(FACTOR * e32, FLOOR), (tag, nm, i, e, e32)
+            assert e <= max(K.FACTOR * e32, K.FLOOR), (tag, nm, i, e, e32)
 
 
 def _check(gpu, tag, c, kind):
-    enc, pred = _with_nan_padding(c)
+    enc, pred = K.with_nan_padding(c)
     got = _run(gpu, enc, pred, c["out"], c["labels"], c["lens"], c["blank"], kind)
     for b, (n, lab) in enumerate(zip(c["lens"], c["labels"])):                # exact zeros in the padding
         assert not got[1][b, n:].any() and not got[2][b, len(lab) + 1:].any(), (tag, b)
@@ -128,7 +95,7 @@ OTHER_KINDS = [(1, 2, 0), (67, 257, 100), (260, 70, 3)]
 
 @pytest.mark.parametrize("J,V,blank", RAGGED)
 def test_ragged_batch_matches_float64(gpu, J, V, blank):
-    c = _ragged(J, V, blank)
+    c = K.fused_ragged(J, V, blank)
     assert [len(r) for r in c["labels"]] == [3, 0, 5] and (blank == V - 1 or c["labels"][2][4] == V - 1)
     _check(gpu, "ragged J %d V %d blank %d tanh" % (J, V, blank), c, "tanh")
 
@@ -136,13 +103,13 @@ def test_ragged_batch_matches_float64(gpu, J, V, blank):
 @pytest.mark.parametrize("kind", ["identity", "relu"])
 @pytest.mark.parametrize("J,V,blank", OTHER_KINDS)
 def test_ragged_batch_other_activations(gpu, J, V, blank, kind):
-    _check(gpu, "ragged J %d V %d blank %d %s" % (J, V, blank, kind), _ragged(J, V, blank), kind)
+    _check(gpu, "ragged J %d V %d blank %d %s" % (J, V, blank, kind), K.fused_ragged(J, V, blank), kind)
 
 
 @pytest.mark.parametrize("T,U", [(4, 4), (4, 7), (3, 10)])
 def test_cell_counts_around_one_tile(gpu, T, U):
     assert T * (U + 1) in (20, 32, 33)
-    _check(gpu, "cells %d" % (T * (U + 1)), _single(T, U, 5, 5, 1, 40 + U), "tanh")
+    _check(gpu, "cells %d" % (T * (U + 1)), K.fused_single(T, U, 5, 5, 1, 40 + U), "tanh")
 
 
 @pytest.mark.parametrize("where", ["last", "first"])
@@ -150,7 +117,7 @@ def test_running_log_sum_exp(gpu, where):
     """the bias puts every cell's maximum into the last (first) block of V, 80 above everything before (after) it: the running sum
     is rescaled by e^-80 there (or every later block adds terms of e^-80)"""
     J, V = 8, 300
-    c = _ragged(J, V, 5, seed=3)
+    c = K.fused_ragged(J, V, 5, seed=3)
     bias = c["out"][J * V:]
     if where == "last":
         bias[V - 3] += 80.0
@@ -178,7 +145,7 @@ def test_emission_underflow(gpu):
 @pytest.mark.parametrize("U,nj", [(300, 2), (600, 0)])
 def test_wide_lattices_through_the_new_emission_writer(gpu, U, nj):
     assert (1 if U + 1 <= 256 else 2 if U + 1 <= 512 else 0) == nj
-    _check(gpu, "U %d" % U, _single(3, U, 4, 3, 0, U), "tanh")
+    _check(gpu, "U %d" % U, K.fused_single(3, U, 4, 3, 0, U), "tanh")
 
 
 def _bits_equal(a, b):
@@ -189,8 +156,8 @@ def _bits_equal(a, b):
 def test_structure(gpu, J, V, blank):
     """every element written (the outputs are prefilled with NaN), d_out finite with NaN padding, determinism, loss-only bits, row
     independence under permutation and further padding"""
-    c = _ragged(J, V, blank)
-    enc, pred = _with_nan_padding(c)
+    c = K.fused_ragged(J, V, blank)
+    enc, pred = K.with_nan_padding(c)
     args = (c["out"], c["labels"], c["lens"], c["blank"], "tanh")
     got = _run(gpu, enc, pred, *args)
     assert all(torch.isfinite(t).all() for t in got)
@@ -218,7 +185,7 @@ def test_structure(gpu, J, V, blank):
 
 
 def test_host_form_equals_the_device_form(gpu):
-    c = _ragged(5, 5, 2)
+    c = K.fused_ragged(5, 5, 2)
     got = _run(gpu, c["enc"], c["pred"], c["out"], c["labels"], c["lens"], c["blank"], "tanh")
     host = NL.rnnt_fused_loss(c["enc"], c["pred"], c["out"], c["labels"], input_lengths=c["lens"], blank=c["blank"], activation="tanh")
     assert all(np.array_equal(h.view(np.int32), g.numpy().view(np.int32)) for h, g in zip(host, got))

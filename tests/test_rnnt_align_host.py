@@ -1,7 +1,6 @@
 """CPU only: the references of the transducer forced-alignment tests (tests/rnnt_align_reference.py) against enumeration and against
 the loss reference; the premises of the device cases (tests/test_gpu_rnnt_align.py), so that a case that no longer tests what it is
 there for turns red without a device; and the host-side refusals of nntk_rnnt_align* / nntk_rnnt_fused_align*, which need no device."""
-import ctypes as C
 import math
 
 import numpy as np
@@ -9,23 +8,15 @@ import pytest
 import torch
 
 import rnnt_align_reference as A
+import rnnt_cases as K
 import rnnt_reference as R
 from nntoolkitcore_amd import capi
-
-CTC_THREADS, LDS_OPT_IN = 256, 48 * 1024             # the constants of rnnt_align.hip that decide the path, mirrored
-
-
-def _viterbi_path(max_label_len):
-    """(NJ of the rnnt_viterbi_kernel instantiation, whether its LDS request needs the opt-in)"""
-    u1 = max_label_len + 1
-    return (1 if u1 <= CTC_THREADS else 2 if u1 <= 2 * CTC_THREADS else 0), 2 * u1 * 16 > LDS_OPT_IN
-
 
 @pytest.mark.parametrize("T,U,V,seed", [(1, 0, 3, 0), (1, 3, 3, 1), (3, 0, 4, 2), (2, 2, 3, 3), (4, 3, 5, 4), (3, 3, 2, 5), (4, 2, 4, 6)])
 def test_float64_reference_equals_enumeration(T, U, V, seed):
     rng = np.random.default_rng(seed)
     blank = int(rng.integers(0, V))
-    lab = A._labels(rng, U, V, blank)
+    lab = K.labels(rng, U, V, blank)
     lp = R.log_softmax(rng.uniform(-3, 3, (T, U + 1, V)))
     r = A.viterbi_row(lp, lab, blank)
     best, frames, n_paths = A.brute_force_row(lp, lab, blank)
@@ -107,7 +98,8 @@ def test_random_and_long_premise():
 def test_instantiation_premise(T, maxL):
     c = A.case("inst_%d_%d" % (T, maxL))
     assert c["x"].shape == (3, T, maxL + 1, 3) and c["lens"] == [T, T, T - 1] and [len(r) for r in c["labels"]] == [maxL, maxL, maxL // 2]
-    assert _viterbi_path(maxL) == A.INSTANTIATIONS[(T, maxL)]
+    nj, lds = K.lattice_path(maxL)
+    assert (nj, lds > K.LDS_OPT_IN) == A.INSTANTIATIONS[(T, maxL)]
 
 
 def test_two_blocks_premise():
@@ -174,37 +166,12 @@ def test_greedy_path_is_the_viterbi_path():
 
 # ---- refusals: no device needed ----
 
-GOOD = dict(B=2, T=6, J=8, V=5, ML=3, act=1, il=[6, 4], lab=[[1, 2, 0], [3, 0, 0]], ll=[2, 1], blank=4,
-            x=0x100000, enc=0x100000, pred=0x200000, out=0x300000, lf=0x400000, fl=0x410000, lp=0x420000, fp=0x430000, sc=0x440000,
-            ws=0x800000)
-BAD = [("input length > T", dict(il=[7, 4]), "input_lengths"), ("input length 0", dict(il=[6, 0]), "input_lengths"),
-       ("label length > max", dict(ll=[4, 1]), "label_lengths"), ("label length < 0", dict(ll=[2, -1]), "label_lengths"),
-       ("label is the blank", dict(lab=[[1, 4, 0], [3, 0, 0]]), "blank"), ("label >= V", dict(lab=[[1, 5, 0], [3, 0, 0]]), "not a class"),
-       ("label < 0", dict(lab=[[-1, 2, 0], [3, 0, 0]]), "not a class"), ("blank >= V", dict(blank=5), "blank"),
-       ("blank < 0", dict(blank=-1), "blank"), ("V = 1", dict(V=1, blank=0), "V 1"), ("batch < 0", dict(B=-1), "negative"),
-       ("NULL labels", dict(lab=None), "NULL"), ("NULL label lengths", dict(ll=None), "NULL"),
-       ("max_label_len beyond the limit", dict(ML=4001, lab=np.zeros((2, 4001), np.int32), ll=[0, 0]), "max_label_len"),
-       ("T + max_label_len beyond the limit", dict(T=65536 - 2, il=None), "diagonals"),
-       ("NULL scores", dict(sc=None), "NULL"), ("NULL workspace", dict(ws=None), "NULL"), ("misaligned workspace", dict(ws=0x800004), "aligned"),
-       ("misaligned label_frames", dict(lf=0x400002), "aligned"),
-       ("label_frames overlaps frame_labels", dict(lf=0x410000 + 8), "overlaps"), ("scores overlaps label_logp", dict(sc=0x420000 + 4), "overlaps"),
-       ("frame_logp overlaps the workspace", dict(fp=0x800000 + 64), "overlaps"), ("frame_labels overlaps the input", dict(fl=0x100000 + 16), "overlaps")]
-PLAIN_ONLY = [("NULL logits", dict(x=None), "NULL"), ("misaligned logits", dict(x=0x100004), "aligned")]
-FUSED_ONLY = [("activation 3", dict(act=3), "activation"), ("J = 0", dict(J=0), "J 0"), ("J above the limit", dict(J=1025), "J 1025"),
-              ("V above the limit", dict(V=8193), "V 8193"), ("NULL enc", dict(enc=None), "NULL"), ("NULL pred", dict(pred=None), "NULL"),
-              ("NULL out", dict(out=None), "NULL"), ("misaligned pred", dict(pred=0x200002), "aligned"),
-              ("scores overlaps d_out", dict(sc=0x300000 + 4), "overlaps")]
+GOOD, _ints, _p = K.GOOD, K.ints, K.ptr
+BAD = K.BAD + K.WS_BAD + K.ALIGN_ONLY
+PLAIN_ONLY, FUSED_ONLY = K.PLAIN_ONLY, K.FUSED_ONLY + K.FUSED_ALIGN_ONLY
 
 
-def _ints(a):
-    return None if a is None else np.ascontiguousarray(a, np.int32).ctypes.data_as(capi.ip)
-
-
-def _p(v):
-    return None if v is None else C.c_void_p(v)
-
-
-@pytest.mark.parametrize("name,change,word", BAD + PLAIN_ONLY, ids=[b[0] for b in BAD + PLAIN_ONLY])
+@pytest.mark.parametrize("name,change,word", BAD + PLAIN_ONLY, ids=K.ids(BAD + PLAIN_ONLY))
 def test_device_form_rejects_before_touching_a_device(name, change, word):
     """dummy device pointers: a call that got past the checks would fault, a refusal never looks at them"""
     a = dict(GOOD, **change)
@@ -213,7 +180,7 @@ def test_device_form_rejects_before_touching_a_device(name, change, word):
     assert rc == -1 and word in capi.last_error(), (name, capi.last_error())
 
 
-@pytest.mark.parametrize("name,change,word", BAD + FUSED_ONLY, ids=[b[0] for b in BAD + FUSED_ONLY])
+@pytest.mark.parametrize("name,change,word", BAD + FUSED_ONLY, ids=K.ids(BAD + FUSED_ONLY))
 def test_fused_device_form_rejects_before_touching_a_device(name, change, word):
     a = dict(GOOD, **change)
     rc = capi.load().nntk_rnnt_fused_align_device(_p(a["enc"]), _p(a["pred"]), _p(a["out"]), a["B"], a["T"], a["J"], a["V"], a["act"],
@@ -227,7 +194,7 @@ HOST_BAD = [b for b in BAD if b[0].split()[0] not in ("misaligned", "NULL", "lab
 
 
 @pytest.mark.parametrize("fused", [False, True])
-@pytest.mark.parametrize("name,change,word", HOST_BAD, ids=[b[0] for b in HOST_BAD])
+@pytest.mark.parametrize("name,change,word", HOST_BAD, ids=K.ids(HOST_BAD))
 def test_host_forms_reject_and_write_nothing(name, change, word, fused):
     L = capi.load()
     a = dict(GOOD, **change)

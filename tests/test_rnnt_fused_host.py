@@ -1,12 +1,12 @@
 """The host side of the fused transducer training loss (csrc/host/rnnt.c, nntk_rnnt_fused_*): every refusal, made before anything is
 allocated, uploaded or enqueued; the workspace size, which is the point of the call -- nothing in it grows like batch T U1 V; and the
 float64 reference of the device tests (tests/rnnt_fused_reference.py) against autograd.  No GPU."""
-import ctypes as C
 
 import numpy as np
 import pytest
 import torch
 
+import rnnt_cases as K
 import rnnt_fused_reference as FR
 from nntoolkitcore_amd import capi
 
@@ -52,39 +52,16 @@ def test_workspace_has_no_part_of_the_size_of_the_logits():
     assert f(64, 1000, 4000, 1024, 8192, 1) > 2 ** 31                            # no 32-bit arithmetic inside
 
 
-GOOD = dict(B=2, T=6, J=8, V=5, ML=3, act=1, il=[6, 4], lab=[[1, 2, 0], [3, 0, 0]], ll=[2, 1], blank=4,
-            enc=0x100000, pred=0x200000, out=0x300000, loss=0x400000, denc=0x500000, dpred=0x600000, dout=0x700000, ws=0x800000)
-BAD = [("input length > T", dict(il=[7, 4]), "input_lengths"), ("input length 0", dict(il=[6, 0]), "input_lengths"),
-       ("label length > max", dict(ll=[4, 1]), "label_lengths"), ("label length < 0", dict(ll=[2, -1]), "label_lengths"),
-       ("label is the blank", dict(lab=[[1, 4, 0], [3, 0, 0]]), "blank"), ("label >= V", dict(lab=[[1, 5, 0], [3, 0, 0]]), "not a class"),
-       ("label < 0", dict(lab=[[-1, 2, 0], [3, 0, 0]]), "not a class"), ("blank >= V", dict(blank=5), "blank"),
-       ("blank < 0", dict(blank=-1), "blank"), ("V = 1", dict(V=1, blank=0), "V 1"), ("batch < 0", dict(B=-1), "negative"),
-       ("NULL labels", dict(lab=None), "NULL"), ("NULL label lengths", dict(ll=None), "NULL"),
-       ("max_label_len beyond the limit", dict(ML=4001, lab=np.zeros((2, 4001), np.int32), ll=[0, 0]), "max_label_len"),
-       ("T + max_label_len beyond the limit", dict(T=65536 - 2, il=None), "diagonals"),
-       ("activation 3", dict(act=3), "activation"), ("activation -1", dict(act=-1), "activation"),
-       ("J = 0", dict(J=0), "J 0"), ("J < 0", dict(J=-4), "J"), ("J above the limit", dict(J=1025), "J 1025"),
-       ("V above the limit", dict(V=8193), "V 8193"),
-       ("only d_denc", dict(dpred=None, dout=None), "all NULL or all given"), ("d_dout missing", dict(dout=None), "all NULL or all given"),
-       ("d_denc missing", dict(denc=None), "all NULL or all given"),
-       ("NULL enc", dict(enc=None), "NULL"), ("NULL pred", dict(pred=None), "NULL"), ("NULL out", dict(out=None), "NULL"),
-       ("NULL loss", dict(loss=None), "NULL"), ("NULL workspace", dict(ws=None), "NULL"),
-       ("misaligned workspace", dict(ws=0x800004), "aligned"), ("misaligned enc", dict(enc=0x100002), "aligned"),
-       ("d_denc overlaps d_enc", dict(denc=0x100000 + 16), "overlaps"), ("d_dpred overlaps d_denc", dict(dpred=0x500000 + 64), "overlaps"),
-       ("d_dout overlaps d_out", dict(dout=0x300000), "overlaps"), ("d_dout overlaps the workspace", dict(dout=0x800000 + 32), "overlaps"),
-       ("loss overlaps d_pred", dict(loss=0x200000 + 8), "overlaps"), ("d_denc overlaps the loss", dict(denc=0x400000 - 16), "overlaps")]
+GOOD, _ints = K.GOOD, K.ints
+BAD = K.BAD + K.WS_BAD + K.FUSED_ONLY + K.FUSED_LOSS_ONLY
 
 
-def _ints(a):
-    return None if a is None else np.ascontiguousarray(a, np.int32).ctypes.data_as(capi.ip)
-
-
-@pytest.mark.parametrize("name,change,word", BAD, ids=[b[0] for b in BAD])
+@pytest.mark.parametrize("name,change,word", BAD, ids=K.ids(BAD))
 def test_device_form_rejects_before_touching_a_device(name, change, word):
     """dummy device pointers: a call that got past the checks would fault, a refusal never looks at them"""
     L = capi.load()
     a = dict(GOOD, **change)
-    p = lambda v: None if v is None else C.c_void_p(v)
+    p = K.ptr
     rc = L.nntk_rnnt_fused_loss_device(p(a["enc"]), p(a["pred"]), p(a["out"]), a["B"], a["T"], a["J"], a["V"], a["act"], _ints(a["il"]),
                                        _ints(a["lab"]), _ints(a["ll"]), a["ML"], a["blank"], p(a["loss"]), p(a["denc"]), p(a["dpred"]),
                                        p(a["dout"]), p(a["ws"]))
@@ -95,7 +72,7 @@ HOST_BAD = [b for b in BAD if b[0].split()[0] not in ("misaligned", "NULL", "d_d
             or b[0] in ("NULL labels", "NULL label lengths", "d_dout missing", "d_denc missing")]
 
 
-@pytest.mark.parametrize("name,change,word", HOST_BAD, ids=[b[0] for b in HOST_BAD])
+@pytest.mark.parametrize("name,change,word", HOST_BAD, ids=K.ids(HOST_BAD))
 def test_host_form_rejects_and_writes_nothing(name, change, word):
     L = capi.load()
     a = dict(GOOD, **change)
