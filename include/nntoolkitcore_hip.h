@@ -1097,6 +1097,65 @@ int nntk_rnnt_fused_loss(const float *enc, const float *pred, const float *out, 
                          const int *input_lengths, const int *labels, const int *label_lengths, int max_label_len, int blank,
                          float *loss_rows, float *denc, float *dpred, float *dout);
 
+/* ---- RNN-Transducer: pruned training loss (csrc/hip/rnnt_pruned.hip; INTEGRATION.md "RNN-Transducer: pruned training loss") ----
+ * Kuang et al., "Pruned RNN-T for fast, memory-efficient ASR training" (2022), in three steps and a joiner that gathers the band.  The
+ * conventions are those of nntk_rnnt_loss_device: U1 = max_label_len + 1, HOST input_lengths (NULL = every row T) / labels /
+ * label_lengths with exactly its checks, padding (t >= T_b or u > U_b) never read -- NaN there is legal -- and given zero gradient.
+ *
+ * 1. Simple loss.  score(t, u, v) = d_am[b][t][v] + d_lm[b][u][v], an f32 sum rounded once; no [batch][T][U1][V] tensor exists.
+ *   d_am [batch][T][V], d_lm [batch][U1][V]: 16-byte aligned.
+ *   d_loss_rows [batch]: the bits nntk_rnnt_loss_device gives on the broadcast sum tensor.
+ *   d_dam [batch][T][V], d_dlm [batch][U1][V]: both NULL or both given; the gradient of the plain sum of the loss rows: the stored loss's
+ *     per-cell gradient g(t, u, v) summed over u (d_dam) and over t (d_dlm), the index ascending, in a double rounded once.  Every
+ *     element is written; zeros on padding and from a row with P = 0.
+ *   d_occ [batch][T][U1] or NULL: the occupancy alpha(t,u) beta(t,u) / P of every cell; 0 on padding and in rows with P = 0.
+ *   d_workspace: nntk_rnnt_simple_workspace_floats(batch, T, max_label_len, want_grad) floats, 16-byte aligned; want_grad = a gradient or
+ *     d_occ is asked: nntk_rnnt_workspace_floats of the same arguments plus, with want_grad, 4 per cell.
+ * 2. Prune ranges.  From d_occ and S, d_ranges [batch][T] int on the DEVICE; nothing is read back.  With fin = max(0, U_b + 1 - S):
+ *     w(t, s) = sum over u = s .. s + S - 1, ascending, in double, of occ(t, u), for s in [0, fin]; s0[t] = the lowest s that attains the
+ *     maximum; then one forward pass, r[-1] = 0, lo[t] = max(0, fin - (T_b - 1 - t)(S - 1)), hi[t] = min(fin, t (S - 1)),
+ *     r[t] = clamp(s0[t], max(lo[t], r[t-1]), min(hi[t], r[t-1] + S - 1)).  So r[0] = 0, r[T_b - 1] = fin, r never decreases and steps by
+ *     at most S - 1: the band holds (0, 0) and (T_b - 1, U_b) and is connected.  Frames t >= T_b get fin.
+ *   Refused: S outside [1, U1]; a row with (T_b - 1)(S - 1) < U_b + 1 - S, which has no connected band.
+ *   d_workspace: nntk_rnnt_prune_workspace_floats(batch) floats (the two length arrays), 4-byte aligned.
+ * 3. Banded joiner.  d_out [batch][T][S][J] = act(d_enc[b][t][:] + d_pred[b][r[b][t] + s][:]), activations as nntk_rnnt_joint_device.
+ *   Backward from the forward OUTPUT: d_denc[b][t] = the sum over s, ascending; d_dpred[b][u] = the sum over the frames t whose window
+ *   holds u, t ascending, gathered per (b, u): one accumulator per element, no atomics, every element written.
+ * 4. Banded loss.  d_logits [batch][T][S][V] (the vocabulary Dense on the banded joiner): cell (t, s) is lattice cell (t, u = r[t] + s),
+ *   its label emission that of label u, padding where u > U_b.  d_loss_rows[b] = -log of the mass of the paths whose cells all lie in
+ *   the band, never below the full loss; d_dlogits [batch][T][S][V] or NULL, every element written once.  A row whose band carries
+ *   no mass behaves like a row with P = 0: loss +inf, zero gradient.  With S = U1 (all ranges 0) loss and gradient are the bits of
+ *   nntk_rnnt_loss_device on the same tensor.  d_logits, d_dlogits and d_workspace -- nntk_rnnt_pruned_workspace_floats(batch, T,
+ *   max_label_len, want_grad) = nntk_rnnt_workspace_floats: the per-cell scalars of the FULL lattice -- 16-byte aligned.
+ * d_ranges is device data no host check can see: every kernel clamps each value into [0, U1 - S], so no content of it causes an access
+ * outside the tensors (with the clamp r + s never exceeds U1 - 1).
+ * Refused on the host before anything is enqueued (-1, nntk_last_error(), nothing written, no device needed): everything
+ * nntk_rnnt_loss_device (and, for the joiner, nntk_rnnt_joint_device) refuses; S out of range; the infeasible row; d_dam / d_dlm only
+ * partly given; NULL or misaligned tensors; an output overlapping another output, an input or the workspace.
+ * Deterministic: no atomics, the same bits on every call, a row's bits independent of the other rows and of its position in the batch.
+ * The host-pointer forms upload, run the device form and download.  All run on the calling thread's stream. */
+size_t nntk_rnnt_simple_workspace_floats(int batch, int T, int max_label_len, int want_grad);
+int nntk_rnnt_simple_loss_device(const float *d_am, const float *d_lm, int batch, int T, int V, const int *input_lengths, const int *labels,
+                                 const int *label_lengths, int max_label_len, int blank, float *d_loss_rows, float *d_dam, float *d_dlm,
+                                 float *d_occ, float *d_workspace);
+int nntk_rnnt_simple_loss(const float *am, const float *lm, int batch, int T, int V, const int *input_lengths, const int *labels,
+                          const int *label_lengths, int max_label_len, int blank, float *loss_rows, float *dam, float *dlm, float *occ);
+size_t nntk_rnnt_prune_workspace_floats(int batch);
+int nntk_rnnt_prune_ranges_device(const float *d_occ, int batch, int T, const int *input_lengths, const int *label_lengths,
+                                  int max_label_len, int S, int *d_ranges, float *d_workspace);
+int nntk_rnnt_prune_ranges(const float *occ, int batch, int T, const int *input_lengths, const int *label_lengths, int max_label_len, int S,
+                           int *ranges);
+int nntk_rnnt_pruned_joint_device(const float *d_enc, const float *d_pred, const int *d_ranges, int batch, int T, int U1, int S, int J,
+                                  int activation, float *d_out);
+int nntk_rnnt_pruned_joint_backward_device(const float *d_out_fwd, const float *d_dout, const int *d_ranges, int batch, int T, int U1, int S,
+                                           int J, int activation, float *d_denc, float *d_dpred);
+size_t nntk_rnnt_pruned_workspace_floats(int batch, int T, int max_label_len, int want_grad);
+int nntk_rnnt_pruned_loss_device(const float *d_logits, const int *d_ranges, int batch, int T, int S, int V, const int *input_lengths,
+                                 const int *labels, const int *label_lengths, int max_label_len, int blank, float *d_loss_rows,
+                                 float *d_dlogits, float *d_workspace);
+int nntk_rnnt_pruned_loss(const float *logits, const int *ranges, int batch, int T, int S, int V, const int *input_lengths, const int *labels,
+                          const int *label_lengths, int max_label_len, int blank, float *loss_rows, float *dlogits);
+
 /* ---- RNN-Transducer: forced alignment (csrc/hip/rnnt_align.hip; INTEGRATION.md "RNN-Transducer: forced alignment") ----
  * Given a row's labels, its single most probable path through the lattice (Viterbi): in which frame every label is emitted.
  *   d_logits, input_lengths, labels, label_lengths, blank: as for nntk_rnnt_loss_device, with exactly its checks, made before anything

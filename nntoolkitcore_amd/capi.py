@@ -481,6 +481,17 @@ SIGNATURES = {
     "nntk_rnnt_fused_loss": (C.c_int, [fp, fp, fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, ip, ip, ip, C.c_int, C.c_int,
                                        fp, fp, fp, fp]),
     # RNN-Transducer: forced alignment on stored scores and on the joiner's inputs (INTEGRATION.md "RNN-Transducer: forced alignment")
+    "nntk_rnnt_simple_workspace_floats": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "nntk_rnnt_simple_loss_device": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, ip, ip, ip, C.c_int, C.c_int, vp, vp, vp, vp, vp]),
+    "nntk_rnnt_simple_loss": (C.c_int, [fp, fp, C.c_int, C.c_int, C.c_int, ip, ip, ip, C.c_int, C.c_int, fp, fp, fp, fp]),
+    "nntk_rnnt_prune_workspace_floats": (C.c_size_t, [C.c_int]),
+    "nntk_rnnt_prune_ranges_device": (C.c_int, [vp, C.c_int, C.c_int, ip, ip, C.c_int, C.c_int, vp, vp]),
+    "nntk_rnnt_prune_ranges": (C.c_int, [fp, C.c_int, C.c_int, ip, ip, C.c_int, C.c_int, ip]),
+    "nntk_rnnt_pruned_joint_device": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
+    "nntk_rnnt_pruned_joint_backward_device": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),
+    "nntk_rnnt_pruned_workspace_floats": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "nntk_rnnt_pruned_loss_device": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, ip, ip, ip, C.c_int, C.c_int, vp, vp, vp]),
+    "nntk_rnnt_pruned_loss": (C.c_int, [fp, ip, C.c_int, C.c_int, C.c_int, C.c_int, ip, ip, ip, C.c_int, C.c_int, fp, fp]),
     "nntk_rnnt_align_workspace_floats": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "nntk_rnnt_align_device": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, ip, ip, ip, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp]),
     "nntk_rnnt_align": (C.c_int, [fp, C.c_int, C.c_int, C.c_int, ip, ip, ip, C.c_int, C.c_int, ip, ip, fp, fp, fp]),

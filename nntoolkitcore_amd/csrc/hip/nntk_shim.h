@@ -220,6 +220,26 @@ size_t nntk_shim_rnnt_fused_workspace_floats(int batch, int T, int max_label_len
 int nntk_shim_rnnt_fused_loss(const float *d_enc, const float *d_pred, const float *d_out, int B, int T, int J, int V, int kind,
                               const int *h_input_lengths, const int *h_labels, const int *h_label_lengths, int max_label_len, int blank,
                               float *d_loss_rows, float *d_denc, float *d_dpred, float *d_dout, float *d_ws);
+/* ---- the pruned transducer training loss (rnnt_pruned.hip).  Host int arrays as for nntk_shim_rnnt_loss, already checked by the caller
+ *      (rnnt.c), never NULL; d_ranges [B][T] is DEVICE memory and clamped into [0, U1 - S] by every kernel that reads it.
+ *      simple_loss: scores am [B][T][V] + lm [B][U1][V], both 16-byte aligned; d_dam and d_dlm both NULL or both given; d_occ
+ *      [B][T][U1] may be NULL; the workspace with want_grad = a gradient or the occupancies are asked.
+ *      prune_ranges: d_ws takes the two length arrays.  pruned_loss: d_logits [B][T][S][V] and d_dlogits (NULL = loss only) 16-byte
+ *      aligned; its workspace is nntk_shim_rnnt_workspace_floats ---- */
+size_t nntk_shim_rnnt_simple_workspace_floats(int batch, int T, int max_label_len, int want_grad);
+int nntk_shim_rnnt_simple_loss(const float *d_am, const float *d_lm, int B, int T, int V, const int *h_input_lengths, const int *h_labels,
+                               const int *h_label_lengths, int max_label_len, int blank, float *d_loss_rows, float *d_dam, float *d_dlm,
+                               float *d_occ, float *d_ws);
+size_t nntk_shim_rnnt_prune_workspace_floats(int batch);
+int nntk_shim_rnnt_prune_ranges(const float *d_occ, int B, int T, int U1, const int *h_input_lengths, const int *h_label_lengths, int S,
+                                int *d_ranges, float *d_ws);
+int nntk_shim_rnnt_pruned_joint(const float *d_enc, const float *d_pred, const int *d_ranges, int B, int T, int U1, int S, int J, int kind,
+                                float *d_out);
+int nntk_shim_rnnt_pruned_joint_backward(const float *d_out_fwd, const float *d_dout, const int *d_ranges, int B, int T, int U1, int S, int J,
+                                         int kind, float *d_denc, float *d_dpred);
+int nntk_shim_rnnt_pruned_loss(const float *d_logits, const int *d_ranges, int B, int T, int S, int V, const int *h_input_lengths,
+                               const int *h_labels, const int *h_label_lengths, int max_label_len, int blank, float *d_loss_rows,
+                               float *d_dlogits, float *d_ws);
 /* ---- transducer forced alignment (rnnt_align.hip): the best single path of every row through its lattice, on the emissions of
  *      either score source: stored scores (rnnt.hip's writer) or the joiner's inputs (rnnt_fused.hip's).  Host int arrays as for
  *      nntk_shim_rnnt_loss, already checked by the caller (rnnt.c), never NULL; the four path outputs may be NULL; d_ws 16-byte

@@ -18,20 +18,13 @@
 //    the two outgoing flows), then V scores in and g[v] = A exp(x[v] - lse) - [v = blank] flow_blank - [v = label] flow_label out.
 //    Padding cells (t >= T_b or u > U_b) are zero-filled with 16-byte stores.
 // No atomics anywhere; every reduction is a fixed butterfly or a fixed-order loop.
-#include "rnnt_common.hpp"                 // the layout and its pointers, the int upload, the emission: shared by the three units
+// The per-cell bodies of the emit and gradient kernels live in rnnt_common.hpp, on a score source: rnnt_pruned.hip runs them on a sum
+// of two rows and on a band of the lattice, and its bit contracts with this unit rest on that.
+#include "rnnt_common.hpp"                 // the layout and its pointers, the int upload, the emission: shared by the four units
 
 #define RNNT_JOINT_UNROLL 4               // terms of a joiner-backward sum loaded together (added in ascending order all the same)
 
-__device__ __forceinline__ float rnnt_wave_max(float v) {
-    for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off));
-    return v;
-}
-__device__ __forceinline__ double rnnt_wave_sum(double v) {
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
-
-// VEC: V % 4 == 0 and the tensor 16-byte aligned, so every row is: 16-byte loads
+// VEC: V % 4 == 0 and the tensor 16-byte aligned, so every row is: 16-byte loads.  The cell's body: rnnt_emit_row (rnnt_common.hpp)
 template <bool VEC>
 __global__ __launch_bounds__(CTC_THREADS) void rnnt_emit_kernel(const float *__restrict__ logits, int B, int T, int U1, int V, int blank,
                                                                 const int *__restrict__ ints, float4 *__restrict__ em,
@@ -41,38 +34,9 @@ __global__ __launch_bounds__(CTC_THREADS) void rnnt_emit_kernel(const float *__r
         const RnntCell q = rnnt_cell(c, T, U1);
         const int Ub = ints[B + q.b];
         if (q.t >= ints[q.b] || q.u > Ub) continue;
-        const float *row = logits + c * V;
-        const f32x4 *row4 = (const f32x4 *)row;
-        float mx = -INFINITY;
-        if (VEC) {
-            for (int i = lane; i < (V >> 2); i += 64) {
-                const f32x4 x = row4[i];
-                mx = fmaxf(mx, fmaxf(fmaxf(x[0], x[1]), fmaxf(x[2], x[3])));
-            }
-        } else {
-            for (int k = lane; k < V; k += 64) mx = fmaxf(mx, row[k]);
-        }
-        mx = rnnt_wave_max(mx);
-        double s = 0.0;
-        if (VEC) {
-            for (int i = lane; i < (V >> 2); i += 64) {
-                const f32x4 x = row4[i];
-                s += (double)expf(x[0] - mx);
-                s += (double)expf(x[1] - mx);
-                s += (double)expf(x[2] - mx);
-                s += (double)expf(x[3] - mx);
-            }
-        } else {
-            for (int k = lane; k < V; k += 64) s += (double)expf(row[k] - mx);
-        }
-        s = rnnt_wave_sum(s);
-        if (lane == 0) {
-            const double lse = (double)mx + log(s);
-            const xf pb = rnnt_emission(row[blank], lse);
-            const xf py = q.u < Ub ? rnnt_emission(row[ints[2L * B + (long)q.b * (U1 - 1) + q.u]], lse) : xf_zero();
-            em[c] = make_float4(pb.m, __int_as_float(pb.e), py.m, __int_as_float(py.e));
-            if (lse_out) lse_out[c] = lse;
-        }
+        const RnntRow<false> row = {logits + c * V, nullptr};
+        rnnt_emit_row<VEC, false>(row, V, blank, q.u < Ub ? ints + 2L * B + (long)q.b * (U1 - 1) + q.u : nullptr, lane, em + c,
+                                  lse_out ? lse_out + c : nullptr);
     }
 }
 
@@ -168,6 +132,7 @@ __global__ __launch_bounds__(CTC_THREADS) void rnnt_lattice_kernel(int B, int T,
     }
 }
 
+// the cell's bodies: rnnt_cell_flows, rnnt_grad_row, rnnt_zero_row (rnnt_common.hpp)
 template <bool VEC>
 __global__ __launch_bounds__(CTC_THREADS) void rnnt_grad_kernel(const float *__restrict__ logits, int B, int T, int U1, int V, int blank,
                                                                 const int *__restrict__ ints, const float4 *__restrict__ em,
@@ -181,54 +146,13 @@ __global__ __launch_bounds__(CTC_THREADS) void rnnt_grad_kernel(const float *__r
         float *g = dlogits + c * V;
         const float mP = hdr[2 * q.b];
         if (q.t >= Tb || q.u > Ub || !(mP > 0.0f)) {                        // padding, or a row no path reaches (P = 0): zeros
-            const int head = min(V, (int)((4 - (((uintptr_t)g >> 2) & 3)) & 3));
-            const int quads = (V - head) >> 2;
-            if (lane < head) g[lane] = 0.0f;
-            f32x4 *g4 = (f32x4 *)(g + head);
-            const f32x4 z = {0.0f, 0.0f, 0.0f, 0.0f};
-            for (int i = lane; i < quads; i += 64) g4[i] = z;
-            const int done = head + 4 * quads;
-            if (lane < V - done) g[done + lane] = 0.0f;
+            rnnt_zero_row(g, V, lane);
             continue;
         }
-        const int eP = __float_as_int(hdr[2 * q.b + 1]);
-        const xf a = xf_unpack(wa[c]);
-        const float4 e4 = em[c];
-        xf pb, py;
-        pb.m = e4.x; pb.e = __float_as_int(e4.y);
-        py.m = e4.z; py.e = __float_as_int(e4.w);
-        const float occ = xf_to_float(xf_times(a, xf_unpack(wb[c])), eP) / mP;                    // alpha beta / P
-        const xf bt = q.t + 1 < Tb ? xf_unpack(wb[c + U1]) : q.u == Ub ? xf_one() : xf_zero();
-        const float fb = xf_to_float(xf_times(xf_times(a, pb), bt), eP) / mP;                    // alpha p_blank beta(t + 1, u) / P
-        float fy = 0.0f;
-        int y = -1;
-        if (q.u < Ub) {
-            y = ints[2L * B + (long)q.b * (U1 - 1) + q.u];
-            fy = xf_to_float(xf_times(xf_times(a, py), xf_unpack(wb[c + 1])), eP) / mP;           // alpha p_label beta(t, u + 1) / P
-        }
-        const double lse = lse_in[c];
-        const float *row = logits + c * V;
-        auto grad = [&](float x, int v) {
-            float r = occ * expf((float)((double)x - lse));
-            if (v == blank) r -= fb;
-            if (v == y) r -= fy;
-            return r;
-        };
-        if (VEC) {
-            const f32x4 *row4 = (const f32x4 *)row;
-            f32x4 *g4 = (f32x4 *)g;
-            for (int i = lane; i < (V >> 2); i += 64) {
-                const f32x4 x = row4[i];
-                f32x4 r;
-                r[0] = grad(x[0], 4 * i);
-                r[1] = grad(x[1], 4 * i + 1);
-                r[2] = grad(x[2], 4 * i + 2);
-                r[3] = grad(x[3], 4 * i + 3);
-                g4[i] = r;
-            }
-        } else {
-            for (int k = lane; k < V; k += 64) g[k] = grad(row[k], k);
-        }
+        const RnntFlows f = rnnt_cell_flows(c, q.t, q.u, Tb, Ub, U1, em, wa, wb, mP, __float_as_int(hdr[2 * q.b + 1]));
+        const int y = q.u < Ub ? ints[2L * B + (long)q.b * (U1 - 1) + q.u] : -1;
+        const RnntRow<false> row = {logits + c * V, nullptr};
+        rnnt_grad_row<VEC, false>(row, g, V, blank, y, f, lse_in[c], lane);
     }
 }
 
@@ -310,6 +234,15 @@ int nntk_rnnt_emit_launch(const float *d_logits, int B, int T, int U1, int V, in
     return 0;
 }
 
+// rnnt_joint_reduce_kernel, for this unit and for rnnt_pruned.hip (the banded joiner's d_enc: the same sum, S terms wide)
+int nntk_rnnt_joint_reduce_launch(const float *d_out_fwd, const float *d_dout, long n, long M, long ostride, int R, long rstride, int kind,
+                                  float *d_dst) {
+    hipLaunchKernelGGL(rnnt_joint_reduce_kernel, dim3(rnnt_grid(n, 256)), dim3(256), 0, nntk_stream(), d_out_fwd, d_dout, n, M, ostride, R,
+                       rstride, kind, d_dst);
+    NNTK_LAUNCH_CHECK("rnnt_joint_reduce_kernel");
+    return 0;
+}
+
 extern "C" {
 
 size_t nntk_shim_rnnt_workspace_floats(int batch, int T, int max_label_len, int want_grad) {
@@ -358,13 +291,8 @@ int nntk_shim_rnnt_joint(const float *d_enc, const float *d_pred, int B, int T, 
 int nntk_shim_rnnt_joint_backward(const float *d_out_fwd, const float *d_dout, int B, int T, int U1, int J, int kind, float *d_denc,
                                   float *d_dpred) {
     if ((long)B * T * U1 * J <= 0) return 0;
-    const long ne = (long)B * T * J, np = (long)B * U1 * J;
-    hipLaunchKernelGGL(rnnt_joint_reduce_kernel, dim3(rnnt_grid(ne, 256)), dim3(256), 0, nntk_stream(), d_out_fwd, d_dout, ne, (long)J,
-                       (long)U1 * J, U1, (long)J, kind, d_denc);
-    hipLaunchKernelGGL(rnnt_joint_reduce_kernel, dim3(rnnt_grid(np, 256)), dim3(256), 0, nntk_stream(), d_out_fwd, d_dout, np, (long)U1 * J,
-                       (long)T * U1 * J, T, (long)U1 * J, kind, d_dpred);
-    NNTK_LAUNCH_CHECK("rnnt_joint_reduce_kernel");
-    return 0;
+    if (nntk_rnnt_joint_reduce_launch(d_out_fwd, d_dout, (long)B * T * J, (long)J, (long)U1 * J, U1, (long)J, kind, d_denc)) return -1;
+    return nntk_rnnt_joint_reduce_launch(d_out_fwd, d_dout, (long)B * U1 * J, (long)U1 * J, (long)T * U1 * J, T, (long)U1 * J, kind, d_dpred);
 }
 
 }  // extern "C"

@@ -3,7 +3,8 @@
  * unnormalised scores with its gradient, and the joiner with its backward.  Every host array, shape, limit and pointer is checked
  * here, before anything is enqueued or allocated: a refusal needs no device.  Every call has a device-pointer form and a host-pointer
  * form (upload, device call, download); the two alignment calls -- on stored scores and on the joiner's inputs -- are one device body
- * and one host body that take the score source (nntk_shim_rnnt_src).
+ * and one host body that take the score source (nntk_shim_rnnt_src).  The pruned training loss (csrc/hip/rnnt_pruned.hip) -- simple
+ * loss, prune ranges, banded joiner, banded loss -- is checked here too, with the same helpers.
  */
 #include <stdint.h>
 #include <stdio.h>
@@ -364,4 +365,218 @@ int nntk_rnnt_fused_align(const float *enc, const float *pred, const float *out,
     return align_host("nntk_rnnt_fused_align", "nntk_rnnt_fused_align_device", ALIGN_FUSED(enc, pred, out, J, activation), batch, T, V,
                       input_lengths, labels, label_lengths, max_label_len, blank,
                       ALIGN_PATH(label_frames, frame_labels, label_logp, frame_logp, scores));
+}
+
+/* ---- the pruned training loss (csrc/hip/rnnt_pruned.hip): simple loss, prune ranges, banded joiner, banded loss.  d_ranges is device
+ *      memory the host cannot check: the kernels clamp it ---- */
+static int pruned_check_s(const char *who, int S, int U1) {
+    if (S < 1 || S > U1) return rnnt_fail(who, "S %d is outside [1, %d]", S, U1, 0);
+    return 0;
+}
+
+/* S, and every row's band: (T_b - 1)(S - 1) >= U_b + 1 - S, or no connected band runs from (0, 0) to (T_b - 1, U_b) */
+static int prune_check(const char *who, int batch, int T, const int *input_lengths, const int *label_lengths, int max_label_len, int S) {
+    if (batch < 0 || T < 0 || max_label_len < 0)
+        return rnnt_fail(who, "batch %d, T %d, max_label_len %d: none may be negative", batch, T, max_label_len);
+    if (max_label_len > NNTK_RNNT_MAX_LABELS)
+        return rnnt_fail(who, "max_label_len %d is beyond what one workgroup's LDS holds (%d)", max_label_len, NNTK_RNNT_MAX_LABELS, 0);
+    if ((long long)T + max_label_len > NNTK_RNNT_MAX_DIAGONALS)
+        return rnnt_fail(who, "T + max_label_len = %d is more than %d lattice diagonals", T + max_label_len, NNTK_RNNT_MAX_DIAGONALS, 0);
+    if (pruned_check_s(who, S, max_label_len + 1)) return -1;
+    if (batch > 0 && !label_lengths) return rnnt_fail(who, "NULL label_lengths", 0, 0, 0);
+    if (batch > 0 && T < 1) return rnnt_fail(who, "T %d < 1", T, 0, 0);
+    for (int b = 0; b < batch; ++b) {
+        const int Tb = input_lengths ? input_lengths[b] : T, Ub = label_lengths[b];
+        if (Tb < 1 || Tb > T) return rnnt_fail(who, "input_lengths[%d] = %d is outside [1, %d]", b, Tb, T);
+        if (Ub < 0 || Ub > max_label_len) return rnnt_fail(who, "label_lengths[%d] = %d is outside [0, %d]", b, Ub, max_label_len);
+        if ((long long)(Tb - 1) * (S - 1) < (long long)Ub + 1 - S)
+            return rnnt_fail(who, "row %d: %d frames cannot carry a connected band of %d positions across its labels (infeasible)", b, Tb, S);
+    }
+    return 0;
+}
+
+size_t nntk_rnnt_simple_workspace_floats(int batch, int T, int max_label_len, int want_grad) {
+    return nntk_shim_rnnt_simple_workspace_floats(batch, T, max_label_len, want_grad != 0);
+}
+
+static int simple_check(const char *who, int batch, int T, int V, const int *input_lengths, const int *labels, const int *label_lengths,
+                        int max_label_len, int blank, const void *dam, const void *dlm) {
+    if (rnnt_check(who, batch, T, V, input_lengths, labels, label_lengths, max_label_len, blank)) return -1;
+    const int given = (dam != NULL) + (dlm != NULL);
+    if (given == 1) return rnnt_fail(who, "the gradient outputs d_dam, d_dlm are all NULL or all given (%d of 2 are)", given, 0, 0);
+    return 0;
+}
+
+int nntk_rnnt_simple_loss_device(const float *d_am, const float *d_lm, int batch, int T, int V, const int *input_lengths, const int *labels,
+                                 const int *label_lengths, int max_label_len, int blank, float *d_loss_rows, float *d_dam, float *d_dlm,
+                                 float *d_occ, float *d_workspace) {
+    static const char who[] = "nntk_rnnt_simple_loss_device";
+    nntk_shim_clear_error();
+    if (simple_check(who, batch, T, V, input_lengths, labels, label_lengths, max_label_len, blank, d_dam, d_dlm)) return -1;
+    if (batch == 0) return 0;
+    if (rnnt_check_ptr(who, "d_am", d_am, 16) || rnnt_check_ptr(who, "d_lm", d_lm, 16) || rnnt_check_ptr(who, "d_loss_rows", d_loss_rows, 4) ||
+        rnnt_check_ptr(who, "d_workspace", d_workspace, 16) ||
+        (d_dam && (rnnt_check_ptr(who, "d_dam", d_dam, 4) || rnnt_check_ptr(who, "d_dlm", d_dlm, 4))) ||
+        (d_occ && rnnt_check_ptr(who, "d_occ", d_occ, 4))) return -1;
+    const size_t U1 = (size_t)max_label_len + 1, f = sizeof(float), na = (size_t)batch * T * V * f, nl = (size_t)batch * U1 * V * f;
+    /* outputs first */
+    const rnnt_span sp[] = {{"d_loss_rows", (uintptr_t)d_loss_rows, (size_t)batch * f}, {"d_dam", (uintptr_t)d_dam, na}, {"d_dlm", (uintptr_t)d_dlm, nl},
+                            {"d_occ", (uintptr_t)d_occ, (size_t)batch * T * U1 * f}, {"d_am", (uintptr_t)d_am, na}, {"d_lm", (uintptr_t)d_lm, nl},
+                            {"d_workspace", (uintptr_t)d_workspace,
+                             nntk_shim_rnnt_simple_workspace_floats(batch, T, max_label_len, d_dam != NULL || d_occ != NULL) * f}};
+    if (rnnt_overlap(who, sp, 4, 7)) return -1;
+    int *len = rnnt_lengths(input_lengths, batch, T);
+    int rc = len ? nntk_shim_rnnt_simple_loss(d_am, d_lm, batch, T, V, len, labels, label_lengths, max_label_len, blank, d_loss_rows, d_dam,
+                                              d_dlm, d_occ, d_workspace) : -1;
+    free(len);
+    return rc;
+}
+
+int nntk_rnnt_simple_loss(const float *am, const float *lm, int batch, int T, int V, const int *input_lengths, const int *labels,
+                          const int *label_lengths, int max_label_len, int blank, float *loss_rows, float *dam, float *dlm, float *occ) {
+    static const char who[] = "nntk_rnnt_simple_loss";
+    nntk_shim_clear_error();
+    if (simple_check(who, batch, T, V, input_lengths, labels, label_lengths, max_label_len, blank, dam, dlm)) return -1;
+    if (batch == 0) return 0;
+    if (rnnt_check_ptr(who, "am", am, 4) || rnnt_check_ptr(who, "lm", lm, 4) || rnnt_check_ptr(who, "loss_rows", loss_rows, 4) ||
+        (dam && (rnnt_check_ptr(who, "dam", dam, 4) || rnnt_check_ptr(who, "dlm", dlm, 4))) || (occ && rnnt_check_ptr(who, "occ", occ, 4)))
+        return -1;
+    /* am | lm | loss rows in one block, dam | dlm | occ in a second (each part rounded up to 16 bytes), the workspace in a third */
+    const size_t up = 3, U1 = (size_t)max_label_len + 1, ra = (size_t)batch * T * V, rl = (size_t)batch * U1 * V, ro = (size_t)batch * T * U1;
+    const size_t na = (ra + up) & ~up, nl = (rl + up) & ~up, no = (ro + up) & ~up;
+    float *d_in = nntk_devbuf_reserve(&t_a, na + nl + (size_t)batch + 4);
+    float *d_g = (dam || occ) ? nntk_devbuf_reserve(&t_b, na + nl + no + 4) : NULL;
+    float *d_ws = nntk_devbuf_reserve(&t_c, nntk_shim_rnnt_simple_workspace_floats(batch, T, max_label_len, dam != NULL || occ != NULL));
+    if (!d_in || ((dam || occ) && !d_g) || !d_ws) return -1;
+    float *d_loss = d_in + na + nl;
+    if (nntk_shim_upload(d_in, am, ra * sizeof(float)) || nntk_shim_upload(d_in + na, lm, rl * sizeof(float))) return -1;
+    if (nntk_rnnt_simple_loss_device(d_in, d_in + na, batch, T, V, input_lengths, labels, label_lengths, max_label_len, blank, d_loss,
+                                     dam ? d_g : NULL, dam ? d_g + na : NULL, occ ? d_g + na + nl : NULL, d_ws)) return -1;
+    if (nntk_shim_download(loss_rows, d_loss, (size_t)batch * sizeof(float))) return -1;
+    if (dam && (nntk_shim_download(dam, d_g, ra * sizeof(float)) || nntk_shim_download(dlm, d_g + na, rl * sizeof(float)))) return -1;
+    return occ ? nntk_shim_download(occ, d_g + na + nl, ro * sizeof(float)) : 0;
+}
+
+size_t nntk_rnnt_prune_workspace_floats(int batch) { return nntk_shim_rnnt_prune_workspace_floats(batch); }
+
+int nntk_rnnt_prune_ranges_device(const float *d_occ, int batch, int T, const int *input_lengths, const int *label_lengths,
+                                  int max_label_len, int S, int *d_ranges, float *d_workspace) {
+    static const char who[] = "nntk_rnnt_prune_ranges_device";
+    nntk_shim_clear_error();
+    if (prune_check(who, batch, T, input_lengths, label_lengths, max_label_len, S)) return -1;
+    if (batch == 0) return 0;
+    if (rnnt_check_ptr(who, "d_occ", d_occ, 4) || rnnt_check_ptr(who, "d_ranges", d_ranges, 4) ||
+        rnnt_check_ptr(who, "d_workspace", d_workspace, 4)) return -1;
+    const size_t f = sizeof(float);
+    const rnnt_span sp[] = {{"d_ranges", (uintptr_t)d_ranges, (size_t)batch * T * f},
+                            {"d_occ", (uintptr_t)d_occ, (size_t)batch * T * ((size_t)max_label_len + 1) * f},
+                            {"d_workspace", (uintptr_t)d_workspace, nntk_shim_rnnt_prune_workspace_floats(batch) * f}};
+    if (rnnt_overlap(who, sp, 1, 3)) return -1;
+    int *len = rnnt_lengths(input_lengths, batch, T);
+    int rc = len ? nntk_shim_rnnt_prune_ranges(d_occ, batch, T, max_label_len + 1, len, label_lengths, S, d_ranges, d_workspace) : -1;
+    free(len);
+    return rc;
+}
+
+int nntk_rnnt_prune_ranges(const float *occ, int batch, int T, const int *input_lengths, const int *label_lengths, int max_label_len, int S,
+                           int *ranges) {
+    static const char who[] = "nntk_rnnt_prune_ranges";
+    nntk_shim_clear_error();
+    if (prune_check(who, batch, T, input_lengths, label_lengths, max_label_len, S)) return -1;
+    if (batch == 0) return 0;
+    if (rnnt_check_ptr(who, "occ", occ, 4) || rnnt_check_ptr(who, "ranges", ranges, 4)) return -1;
+    const size_t n = (size_t)batch * T * ((size_t)max_label_len + 1), nu = (n + 3) & ~(size_t)3;
+    float *d_occ = nntk_devbuf_reserve(&t_a, nu + (size_t)batch * T + 4);
+    float *d_ws = nntk_devbuf_reserve(&t_c, nntk_shim_rnnt_prune_workspace_floats(batch));
+    if (!d_occ || !d_ws || nntk_shim_upload(d_occ, occ, n * sizeof(float))) return -1;
+    if (nntk_rnnt_prune_ranges_device(d_occ, batch, T, input_lengths, label_lengths, max_label_len, S, (int *)(d_occ + nu), d_ws)) return -1;
+    return nntk_shim_download(ranges, d_occ + nu, (size_t)batch * T * sizeof(int));
+}
+
+static int pruned_joint_check(const char *who, int batch, int T, int U1, int S, int J, int activation) {
+    if (joint_check(who, batch, T, U1, J, activation)) return -1;
+    return (size_t)batch * T * U1 * J == 0 ? 0 : pruned_check_s(who, S, U1);      /* an empty tensor is not an error */
+}
+
+int nntk_rnnt_pruned_joint_device(const float *d_enc, const float *d_pred, const int *d_ranges, int batch, int T, int U1, int S, int J,
+                                  int activation, float *d_out) {
+    static const char who[] = "nntk_rnnt_pruned_joint_device";
+    nntk_shim_clear_error();
+    if (pruned_joint_check(who, batch, T, U1, S, J, activation)) return -1;
+    if ((size_t)batch * T * U1 * J == 0) return 0;
+    if (rnnt_check_ptr(who, "d_enc", d_enc, 4) || rnnt_check_ptr(who, "d_pred", d_pred, 4) || rnnt_check_ptr(who, "d_ranges", d_ranges, 4) ||
+        rnnt_check_ptr(who, "d_out", d_out, 4)) return -1;
+    const size_t f = sizeof(float);
+    const rnnt_span sp[] = {{"d_out", (uintptr_t)d_out, (size_t)batch * T * S * J * f}, {"d_enc", (uintptr_t)d_enc, (size_t)batch * T * J * f},
+                            {"d_pred", (uintptr_t)d_pred, (size_t)batch * U1 * J * f}, {"d_ranges", (uintptr_t)d_ranges, (size_t)batch * T * f}};
+    if (rnnt_overlap(who, sp, 1, 4)) return -1;
+    return nntk_shim_rnnt_pruned_joint(d_enc, d_pred, d_ranges, batch, T, U1, S, J, activation, d_out);
+}
+
+int nntk_rnnt_pruned_joint_backward_device(const float *d_out_fwd, const float *d_dout, const int *d_ranges, int batch, int T, int U1, int S,
+                                           int J, int activation, float *d_denc, float *d_dpred) {
+    static const char who[] = "nntk_rnnt_pruned_joint_backward_device";
+    nntk_shim_clear_error();
+    if (pruned_joint_check(who, batch, T, U1, S, J, activation)) return -1;
+    if ((size_t)batch * T * U1 * J == 0) return 0;
+    if ((activation != 0 && rnnt_check_ptr(who, "d_out_fwd", d_out_fwd, 4)) || rnnt_check_ptr(who, "d_dout", d_dout, 4) ||
+        rnnt_check_ptr(who, "d_ranges", d_ranges, 4) || rnnt_check_ptr(who, "d_denc", d_denc, 4) || rnnt_check_ptr(who, "d_dpred", d_dpred, 4))
+        return -1;
+    const size_t f = sizeof(float), band = (size_t)batch * T * S * J * f;
+    const rnnt_span sp[] = {{"d_denc", (uintptr_t)d_denc, (size_t)batch * T * J * f}, {"d_dpred", (uintptr_t)d_dpred, (size_t)batch * U1 * J * f},
+                            {"d_out_fwd", (uintptr_t)(activation ? d_out_fwd : NULL), band}, {"d_dout", (uintptr_t)d_dout, band},
+                            {"d_ranges", (uintptr_t)d_ranges, (size_t)batch * T * f}};
+    if (rnnt_overlap(who, sp, 2, 5)) return -1;
+    return nntk_shim_rnnt_pruned_joint_backward(d_out_fwd, d_dout, d_ranges, batch, T, U1, S, J, activation, d_denc, d_dpred);
+}
+
+size_t nntk_rnnt_pruned_workspace_floats(int batch, int T, int max_label_len, int want_grad) {
+    return nntk_shim_rnnt_workspace_floats(batch, T, max_label_len, want_grad != 0);
+}
+
+int nntk_rnnt_pruned_loss_device(const float *d_logits, const int *d_ranges, int batch, int T, int S, int V, const int *input_lengths,
+                                 const int *labels, const int *label_lengths, int max_label_len, int blank, float *d_loss_rows,
+                                 float *d_dlogits, float *d_workspace) {
+    static const char who[] = "nntk_rnnt_pruned_loss_device";
+    nntk_shim_clear_error();
+    if (rnnt_check(who, batch, T, V, input_lengths, labels, label_lengths, max_label_len, blank) ||
+        pruned_check_s(who, S, max_label_len + 1)) return -1;
+    if (batch == 0) return 0;
+    if (rnnt_check_ptr(who, "d_logits", d_logits, 16) || rnnt_check_ptr(who, "d_ranges", d_ranges, 4) ||
+        rnnt_check_ptr(who, "d_loss_rows", d_loss_rows, 4) || rnnt_check_ptr(who, "d_workspace", d_workspace, 16) ||
+        (d_dlogits && rnnt_check_ptr(who, "d_dlogits", d_dlogits, 16))) return -1;
+    const size_t f = sizeof(float), bytes = (size_t)batch * T * S * V * f;
+    const rnnt_span sp[] = {{"d_dlogits", (uintptr_t)d_dlogits, bytes}, {"d_loss_rows", (uintptr_t)d_loss_rows, (size_t)batch * f},
+                            {"d_logits", (uintptr_t)d_logits, bytes}, {"d_ranges", (uintptr_t)d_ranges, (size_t)batch * T * f},
+                            {"d_workspace", (uintptr_t)d_workspace,
+                             nntk_shim_rnnt_workspace_floats(batch, T, max_label_len, d_dlogits != NULL) * f}};
+    if (rnnt_overlap(who, sp, 2, 5)) return -1;
+    int *len = rnnt_lengths(input_lengths, batch, T);
+    int rc = len ? nntk_shim_rnnt_pruned_loss(d_logits, d_ranges, batch, T, S, V, len, labels, label_lengths, max_label_len, blank, d_loss_rows,
+                                              d_dlogits, d_workspace) : -1;
+    free(len);
+    return rc;
+}
+
+int nntk_rnnt_pruned_loss(const float *logits, const int *ranges, int batch, int T, int S, int V, const int *input_lengths, const int *labels,
+                          const int *label_lengths, int max_label_len, int blank, float *loss_rows, float *dlogits) {
+    static const char who[] = "nntk_rnnt_pruned_loss";
+    nntk_shim_clear_error();
+    if (rnnt_check(who, batch, T, V, input_lengths, labels, label_lengths, max_label_len, blank) ||
+        pruned_check_s(who, S, max_label_len + 1)) return -1;
+    if (batch == 0) return 0;
+    if (rnnt_check_ptr(who, "logits", logits, 4) || rnnt_check_ptr(who, "ranges", ranges, 4) || rnnt_check_ptr(who, "loss_rows", loss_rows, 4) ||
+        (dlogits && rnnt_check_ptr(who, "dlogits", dlogits, 4))) return -1;
+    /* logits | ranges | loss rows in one block (each part rounded up to 16 bytes), the gradient in a second, the workspace in a third */
+    const size_t up = 3, n = (size_t)batch * T * S * V, nu = (n + up) & ~up, nr = ((size_t)batch * T + up) & ~up;
+    float *d_x = nntk_devbuf_reserve(&t_a, nu + nr + (size_t)batch + 4);
+    float *d_g = dlogits ? nntk_devbuf_reserve(&t_b, n + 4) : NULL;
+    float *d_ws = nntk_devbuf_reserve(&t_c, nntk_shim_rnnt_workspace_floats(batch, T, max_label_len, dlogits != NULL));
+    if (!d_x || (dlogits && !d_g) || !d_ws) return -1;
+    float *d_loss = d_x + nu + nr;
+    if (nntk_shim_upload(d_x, logits, n * sizeof(float)) || nntk_shim_upload(d_x + nu, ranges, (size_t)batch * T * sizeof(int))) return -1;
+    if (nntk_rnnt_pruned_loss_device(d_x, (const int *)(d_x + nu), batch, T, S, V, input_lengths, labels, label_lengths, max_label_len, blank,
+                                     d_loss, d_g, d_ws)) return -1;
+    if (nntk_shim_download(loss_rows, d_loss, (size_t)batch * sizeof(float))) return -1;
+    return dlogits ? nntk_shim_download(dlogits, d_g, n * sizeof(float)) : 0;
 }

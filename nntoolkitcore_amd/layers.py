@@ -1077,6 +1077,144 @@ def rnnt_fused_loss(enc, pred, out_block, labels, label_lengths=None, input_leng
     return (loss,) + g
 
 
+def _ip(t):
+    """device pointer of a contiguous int32 torch tensor"""
+    import torch
+    assert t.is_cuda and t.is_contiguous() and t.dtype == torch.int32
+    return C.c_void_p(t.data_ptr())
+
+
+def rnnt_simple_loss_device(am, lm, labels, label_lengths=None, input_lengths=None, blank=0, want_grad=True, want_occ=True, loss=None,
+                            dam=None, dlm=None, occ=None, workspace=None):
+    """``nntk_rnnt_simple_loss_device``: am [B,T,V], lm [B,U1,V] device tensors, score(t, u, v) = am[b,t,v] + lm[b,u,v], never stored.
+    Returns (loss rows [B], d am, d lm, occupancy [B,T,U1]); the gradients / the occupancy are None where not asked."""
+    import torch
+    B, T, V = am.shape
+    U1 = lm.shape[1]
+    assert tuple(lm.shape) == (B, U1, V), "lm: [B, U1, V] with am's B and V"
+    lab, ll = _rnnt_labels(labels, label_lengths, B, U1 - 1)
+    il, ilp = _ctc_lengths(input_lengths, B)
+    workspace = _rnnt_workspace(workspace, am.device, "nntk_rnnt_simple_workspace_floats", B, T, U1 - 1, int(want_grad or want_occ))
+    if loss is None:
+        loss = torch.empty(B, dtype=torch.float32, device=am.device)
+    if want_grad:
+        dam = torch.empty_like(am) if dam is None else dam
+        dlm = torch.empty_like(lm) if dlm is None else dlm
+    if want_occ and occ is None:
+        occ = torch.empty((B, T, U1), dtype=torch.float32, device=am.device)
+    check(capi.load().nntk_rnnt_simple_loss_device(_dp(am), _dp(lm), B, T, V, ilp, lab.ctypes.data_as(capi.ip), ll.ctypes.data_as(capi.ip),
+                                                   U1 - 1, blank, _dp(loss), _dp(dam) if want_grad else None,
+                                                   _dp(dlm) if want_grad else None, _dp(occ) if want_occ else None, _dp(workspace)),
+          "nntk_rnnt_simple_loss_device")
+    return loss, (dam if want_grad else None), (dlm if want_grad else None), (occ if want_occ else None)
+
+
+def rnnt_simple_loss(am, lm, labels, label_lengths=None, input_lengths=None, blank=0, want_grad=True, want_occ=True):
+    """The host-memory form (``nntk_rnnt_simple_loss``) on numpy arrays."""
+    am, lm = _f32(am), _f32(lm)
+    B, T, V = am.shape
+    U1 = lm.shape[1]
+    lab, ll = _rnnt_labels(labels, label_lengths, B, U1 - 1)
+    il, ilp = _ctc_lengths(input_lengths, B)
+    loss = np.empty(B, np.float32)
+    dam, dlm = (np.empty_like(am), np.empty_like(lm)) if want_grad else (None, None)
+    occ = np.empty((B, T, U1), np.float32) if want_occ else None
+    check(capi.load().nntk_rnnt_simple_loss(_p(am), _p(lm), B, T, V, ilp, lab.ctypes.data_as(capi.ip), ll.ctypes.data_as(capi.ip), U1 - 1, blank,
+                                            _p(loss), *[None if a is None else _p(a) for a in (dam, dlm, occ)]), "nntk_rnnt_simple_loss")
+    return loss, dam, dlm, occ
+
+
+def rnnt_prune_ranges_device(occ, label_lengths, S, input_lengths=None, ranges=None, workspace=None):
+    """``nntk_rnnt_prune_ranges_device``: the occupancy [B,T,U1] of ``rnnt_simple_loss_device`` -> ranges [B,T] int32 on the device: per
+    frame the first of the S label positions the banded joiner and the banded loss keep"""
+    import torch
+    B, T, U1 = occ.shape
+    ll = _host_ints(label_lengths, B, "label_lengths")
+    il, ilp = _ctc_lengths(input_lengths, B)
+    workspace = _rnnt_workspace(workspace, occ.device, "nntk_rnnt_prune_workspace_floats", B)
+    if ranges is None:
+        ranges = torch.empty((B, T), dtype=torch.int32, device=occ.device)
+    check(capi.load().nntk_rnnt_prune_ranges_device(_dp(occ), B, T, ilp, ll.ctypes.data_as(capi.ip), U1 - 1, S, _ip(ranges), _dp(workspace)),
+          "nntk_rnnt_prune_ranges_device")
+    return ranges
+
+
+def rnnt_prune_ranges(occ, label_lengths, S, input_lengths=None):
+    """The host-memory form (``nntk_rnnt_prune_ranges``): occ [B,T,U1] numpy array -> ranges [B,T] int32."""
+    occ = _f32(occ)
+    B, T, U1 = occ.shape
+    ll = _host_ints(label_lengths, B, "label_lengths")
+    il, ilp = _ctc_lengths(input_lengths, B)
+    ranges = np.empty((B, T), np.int32)
+    check(capi.load().nntk_rnnt_prune_ranges(_p(occ), B, T, ilp, ll.ctypes.data_as(capi.ip), U1 - 1, S, ranges.ctypes.data_as(capi.ip)),
+          "nntk_rnnt_prune_ranges")
+    return ranges
+
+
+def rnnt_pruned_joint_device(enc, pred, ranges, S, activation=ACT_TANH, out=None):
+    """``nntk_rnnt_pruned_joint_device``: enc [B,T,J], pred [B,U1,J], ranges [B,T] int32 -> out [B,T,S,J] = act(enc[b,t] + pred[b,r[b,t]+s])"""
+    B, T, J = enc.shape
+    U1 = pred.shape[1]
+    assert tuple(pred.shape) == (B, U1, J), "pred: [B, U1, J] with enc's B and J"
+    assert tuple(ranges.shape) == (B, T)
+    if out is None:
+        out = enc.new_empty((B, T, S, J))
+    assert tuple(out.shape) == (B, T, S, J)
+    check(capi.load().nntk_rnnt_pruned_joint_device(_dp(enc), _dp(pred), _ip(ranges), B, T, U1, S, J, RNNT_ACTIVATIONS[activation], _dp(out)),
+          "nntk_rnnt_pruned_joint_device")
+    return out
+
+
+def rnnt_pruned_joint_backward_device(out, dout, ranges, U1, activation=ACT_TANH, denc=None, dpred=None):
+    """``nntk_rnnt_pruned_joint_backward_device``: the banded joiner's forward output and the gradient arriving at it, both [B,T,S,J] ->
+    (d enc [B,T,J], d pred [B,U1,J]), both overwritten"""
+    B, T, S, J = dout.shape
+    assert tuple(out.shape) == (B, T, S, J) and tuple(ranges.shape) == (B, T)
+    if denc is None:
+        denc = dout.new_empty((B, T, J))
+    if dpred is None:
+        dpred = dout.new_empty((B, U1, J))
+    assert tuple(denc.shape) == (B, T, J) and tuple(dpred.shape) == (B, U1, J)
+    check(capi.load().nntk_rnnt_pruned_joint_backward_device(_dp(out), _dp(dout), _ip(ranges), B, T, U1, S, J, RNNT_ACTIVATIONS[activation],
+                                                             _dp(denc), _dp(dpred)), "nntk_rnnt_pruned_joint_backward_device")
+    return denc, dpred
+
+
+def rnnt_pruned_loss_device(logits, ranges, labels, max_label_len, label_lengths=None, input_lengths=None, blank=0, want_grad=True, loss=None,
+                            dlogits=None, workspace=None):
+    """``nntk_rnnt_pruned_loss_device``: logits [B,T,S,V] device tensor of UNNORMALISED scores on the band ranges [B,T] (int32) of a
+    lattice with U1 = max_label_len + 1.  Returns (loss rows [B], d loss / d logits [B,T,S,V] or None)."""
+    import torch
+    B, T, S, V = logits.shape
+    assert tuple(ranges.shape) == (B, T)
+    lab, ll = _rnnt_labels(labels, label_lengths, B, max_label_len)
+    il, ilp = _ctc_lengths(input_lengths, B)
+    workspace = _rnnt_workspace(workspace, logits.device, "nntk_rnnt_pruned_workspace_floats", B, T, max_label_len, int(want_grad))
+    if loss is None:
+        loss = torch.empty(B, dtype=torch.float32, device=logits.device)
+    if want_grad and dlogits is None:
+        dlogits = torch.empty_like(logits)
+    check(capi.load().nntk_rnnt_pruned_loss_device(_dp(logits), _ip(ranges), B, T, S, V, ilp, lab.ctypes.data_as(capi.ip),
+                                                   ll.ctypes.data_as(capi.ip), max_label_len, blank, _dp(loss),
+                                                   _dp(dlogits) if want_grad else None, _dp(workspace)), "nntk_rnnt_pruned_loss_device")
+    return loss, (dlogits if want_grad else None)
+
+
+def rnnt_pruned_loss(logits, ranges, labels, max_label_len, label_lengths=None, input_lengths=None, blank=0, want_grad=True):
+    """The host-memory form (``nntk_rnnt_pruned_loss``): logits [B,T,S,V] and ranges [B,T] numpy arrays."""
+    logits = _f32(logits)
+    B, T, S, V = logits.shape
+    ranges = np.ascontiguousarray(ranges, np.int32).reshape(B, T)
+    lab, ll = _rnnt_labels(labels, label_lengths, B, max_label_len)
+    il, ilp = _ctc_lengths(input_lengths, B)
+    loss = np.empty(B, np.float32)
+    g = np.empty_like(logits) if want_grad else None
+    check(capi.load().nntk_rnnt_pruned_loss(_p(logits), ranges.ctypes.data_as(capi.ip), B, T, S, V, ilp, lab.ctypes.data_as(capi.ip),
+                                            ll.ctypes.data_as(capi.ip), max_label_len, blank, _p(loss), _p(g) if want_grad else None),
+          "nntk_rnnt_pruned_loss")
+    return loss, g
+
+
 def _rnnt_align_device(entry, size_fn, head, dev, dims, size_args, labels, label_lengths, input_lengths, blank, given, workspace):
     """Both device forms of the alignment: the C entry by name, its argument head (the score source: the tensors, then B, T and the
     widths as the entry takes them), dims = (B, T, U1), the workspace size function by name with its arguments, the five outputs as
