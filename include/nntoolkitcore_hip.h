@@ -1042,6 +1042,9 @@ int nntk_ctc_align(const float *probs, int batch, int T, int C, const int *input
  *     refusal needs no device.  Repeated labels need no special rule.
  *   d_loss_rows [batch]: -log P_b, unreduced.  Finite whenever the row's live scores are (the variables and the emissions carry an
  *     int32 exponent of their own; an emission below 2^-4000 of its cell's total counts as 2^-4000); +inf only through -inf scores.
+ *     A -inf score is a zero emission (a masked class, a -inf bias of the projection) and has the gradient 0.  A live cell whose V
+ *     scores are all -inf has two zero emissions: no path passes through it, its gradient row is exact zeros and never NaN, and the
+ *     row's loss is finite as long as a path goes round the cell.  This holds for the stored, the fused, the simple and the banded loss.
  *   d_dlogits or NULL: d loss_b / d logits; per live cell
  *       alpha(t,u) / P ( p_v beta(t,u) - [v = blank] p_blank beta(t+1,u) - [v = y_{u+1}] p_y beta(t,u+1) ),
  *     beta(T_b, U_b) standing for 1 in the blank term of the last cell.  Every element is written: exact zeros for t >= T_b or u > U_b
@@ -1115,7 +1118,9 @@ int nntk_rnnt_fused_loss(const float *enc, const float *pred, const float *out, 
  *     w(t, s) = sum over u = s .. s + S - 1, ascending, in double, of occ(t, u), for s in [0, fin]; s0[t] = the lowest s that attains the
  *     maximum; then one forward pass, r[-1] = 0, lo[t] = max(0, fin - (T_b - 1 - t)(S - 1)), hi[t] = min(fin, t (S - 1)),
  *     r[t] = clamp(s0[t], max(lo[t], r[t-1]), min(hi[t], r[t-1] + S - 1)).  So r[0] = 0, r[T_b - 1] = fin, r never decreases and steps by
- *     at most S - 1: the band holds (0, 0) and (T_b - 1, U_b) and is connected.  Frames t >= T_b get fin.
+ *     at most S - 1: the band holds (0, 0) and (T_b - 1, U_b) and is connected.  Frames t >= T_b get fin.  Frames t >= T_b of d_occ
+ *     are never read, nor is u > U_b in a row with U_b + 1 >= S.  A row with fewer positions than S (U_b + 1 < S) has the one window
+ *     s = 0, whose sum does reach into u in (U_b, S): what those cells hold (NaN included) changes nothing, r[t] is 0 either way.
  *   Refused: S outside [1, U1]; a row with (T_b - 1)(S - 1) < U_b + 1 - S, which has no connected band.
  *   d_workspace: nntk_rnnt_prune_workspace_floats(batch) floats (the two length arrays), 4-byte aligned.
  * 3. Banded joiner.  d_out [batch][T][S][J] = act(d_enc[b][t][:] + d_pred[b][r[b][t] + s][:]), activations as nntk_rnnt_joint_device.

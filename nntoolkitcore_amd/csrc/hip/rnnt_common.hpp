@@ -160,9 +160,11 @@ __device__ __forceinline__ RnntFlows rnnt_cell_flows(long c, int t, int u, int T
     return f;
 }
 
-// d loss / d score v of a cell: occ exp(x - lse) - [v = blank] fb - [v = y] fy (y = -1: no label leaves the cell)
+// d loss / d score v of a cell: occ exp(x - lse) - [v = blank] fb - [v = y] fy (y = -1: no label leaves the cell).  An occupancy of
+// exactly 0 is a first term of exactly 0, selected and not multiplied: a live cell whose V scores are all -inf has two zero emissions,
+// so beta and the occupancy are 0, and lse = NaN (-inf - -inf).  On finite scores 0 exp(x - lse) was +0 already: the same bits
 __device__ __forceinline__ float rnnt_grad_value(const RnntFlows f, double lse, int blank, int y, float x, int v) {
-    float r = f.occ * expf((float)((double)x - lse));
+    float r = f.occ == 0.0f ? 0.0f : f.occ * expf((float)((double)x - lse));
     if (v == blank) r -= f.fb;
     if (v == y) r -= f.fy;
     return r;

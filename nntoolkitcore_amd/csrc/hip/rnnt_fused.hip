@@ -233,7 +233,7 @@ __device__ __forceinline__ void ft_g_block(float *Gs, const float *Zs, const FtT
     for (int v = 0; v < 16; ++v) {
         const int row = ft_row(v, kk);
         const float x = acc[v] + bv;
-        float r = s.occ[row] * expf((float)((double)x - s.lse[row]));
+        float r = s.occ[row] == 0.0f ? 0.0f : s.occ[row] * expf((float)((double)x - s.lse[row]));      // rnnt_grad_value's selection
         if (col == blank) r -= s.fb[row];
         if (col == s.y[row]) r -= s.fy[row];
         gp[row] = colv && s.live[row] ? r : 0.0f;

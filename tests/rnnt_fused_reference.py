@@ -62,9 +62,12 @@ def torch_fused_logits(enc, pred, out_block, labels, lens, kind, dtype, grad=Fal
 
 
 def torch_fused(enc, pred, out_block, labels, lens, blank, kind, dtype):
-    """the loss in torch on the CPU at `dtype` (rnnt_reference._torch_row per row), autograd -> float64 numpy, as above"""
+    """the loss in torch on the CPU at `dtype` (rnnt_reference.torch_lattice per row), autograd -> float64 numpy, as above; a row without
+    a path has the loss inf and adds nothing to the sum that is differentiated"""
     import torch
     leaves, rows = torch_fused_logits(enc, pred, out_block, labels, lens, kind, dtype, grad=True)
-    loss = torch.stack([R._torch_row(x, list(labels[b]), blank) for b, x in enumerate(rows)])
-    grads = torch.autograd.grad(loss.sum(), leaves)
-    return tuple(a.detach().double().numpy() for a in (loss,) + tuple(grads))
+    rows = [R.torch_lattice(x, list(labels[b]), blank)[0] for b, x in enumerate(rows)]
+    loss = np.array([np.inf if l is None else float(l.detach()) for l in rows])
+    live = [l for l in rows if l is not None]
+    grads = torch.autograd.grad(torch.stack(live).sum(), leaves) if live else [torch.zeros_like(a) for a in leaves]
+    return (loss,) + tuple(a.detach().double().numpy() for a in grads)

@@ -26,72 +26,22 @@ def clamp_ranges(ranges, U1, S):
 
 def lattice64(x, lab, blank, mask):
     """x [T][U + 1][V] float64 scores of one row's live cells, mask [T][U + 1] bool -> (loss, d loss / d x, occupancy [T][U + 1]);
-    cells outside the mask are never looked at and get zeros.  No path: (inf, zeros, zeros)"""
-    T, U1, V = x.shape
-    U = U1 - 1
-    ninf = -math.inf
-    lp = np.where(mask[:, :, None], R.log_softmax(np.where(mask[:, :, None], x, 0.0)), ninf)
-    lb = lp[:, :, blank]
-    ly = np.full((T, U1), ninf)
-    for u in range(U):
-        ly[:, u] = lp[:, u, lab[u]]
-    alpha = np.full((T, U1), ninf)
-    beta = np.full((T + 1, U1 + 1), ninf)
-    for t in range(T):
-        for u in range(U1):
-            if t == 0 and u == 0:
-                alpha[0, 0] = 0.0
-                continue
-            a = alpha[t - 1, u] + lb[t - 1, u] if t > 0 else ninf
-            c = alpha[t, u - 1] + ly[t, u - 1] if u > 0 else ninf
-            alpha[t, u] = R._lae(a, c)
-    beta[T, U] = 0.0
-    for t in range(T - 1, -1, -1):
-        for u in range(U, -1, -1):
-            beta[t, u] = R._lae(lb[t, u] + beta[t + 1, u], ly[t, u] + beta[t, u + 1])
-    logp = alpha[T - 1, U] + lb[T - 1, U]
-    if logp == ninf:
-        return math.inf, np.zeros((T, U1, V)), np.zeros((T, U1))
-    assert abs(logp - beta[0, 0]) <= 1e-9 * max(1.0, abs(logp))
-    with np.errstate(invalid="ignore"):
-        w = alpha + beta[:T, :U1] - logp
-        occ = np.where(mask, np.exp(np.where(np.isnan(w), ninf, w)), 0.0)
-        g = occ[:, :, None] * np.exp(np.where(mask[:, :, None], lp, ninf))
-        fb = alpha + lb + beta[1:, :U1] - logp
-        g[:, :, blank] -= np.exp(np.where(np.isnan(fb), ninf, fb))
-        for u in range(U):
-            fy = alpha[:, u] + ly[:, u] + beta[:T, u + 1] - logp
-            g[:, u, lab[u]] -= np.exp(np.where(np.isnan(fy), ninf, fy))
-    return -logp, np.where(mask[:, :, None], g, 0.0), occ
+    cells outside the mask are never looked at and get zeros.  No path: (inf, zeros, zeros).  The lattice is rnnt_reference.lattice64:
+    a cell outside the mask has -inf for every log-probability"""
+    lp = np.where(mask[:, :, None], R.log_softmax(np.where(mask[:, :, None], x, 0.0)), -math.inf)
+    return R.lattice64(lp, lab, blank, factored=True)
 
 
 def lattice_torch(x, lab, blank, mask, dtype):
-    """the same three results from torch at `dtype`, by autograd, as float64 numpy; the occupancy of a cell is what flows out of it:
-    -(d loss / d log p_blank + d loss / d log p_label)"""
+    """the same three results from torch at `dtype` (rnnt_reference.torch_lattice), by autograd, as float64 numpy; the occupancy of a
+    cell is what flows out of it: -(d loss / d log p_blank + d loss / d log p_label)"""
     import torch
     T, U1, V = x.shape
     U = U1 - 1
     X = torch.from_numpy(np.where(mask[:, :, None], x, 0.0)).to(dtype).requires_grad_(True)
-    lp = torch.log_softmax(X, -1)
-    lp.retain_grad()
-    alpha = [[None] * U1 for _ in range(T)]
-    for t in range(T):
-        for u in range(U1):
-            if not mask[t, u]:
-                continue
-            if t == 0 and u == 0:
-                alpha[0][0] = torch.zeros((), dtype=dtype)
-                continue
-            terms = []
-            if t > 0 and alpha[t - 1][u] is not None:
-                terms.append(alpha[t - 1][u] + lp[t - 1, u, blank])
-            if u > 0 and alpha[t][u - 1] is not None:
-                terms.append(alpha[t][u - 1] + lp[t, u - 1, lab[u - 1]])
-            if terms:
-                alpha[t][u] = terms[0] if len(terms) == 1 else torch.logaddexp(terms[0], terms[1])
-    if alpha[T - 1][U] is None:
+    loss, lp = R.torch_lattice(X, lab, blank, mask)
+    if loss is None:
         return math.inf, np.zeros((T, U1, V)), np.zeros((T, U1))
-    loss = -(alpha[T - 1][U] + lp[T - 1, U, blank])
     loss.backward()
     glp = lp.grad.double().numpy()
     occ = -glp[:, :, blank].copy()

@@ -6,7 +6,11 @@ at most FACTOR x the error of a float32 torch restatement, or FLOOR where that i
 to the row's largest |value|.  Bit contracts are asserted with torch.equal / array_equal.
 
 The base case: B = 3, T = 9, input lengths (9, 5, 2), max_label_len 4, label lengths (4, 0, 2): row 2 sits on the feasibility edge for
-S = 2, row 1 has no labels.  V in {2, 5, 257, 260} covers the scalar and the 16-byte row paths of the emit and gradient bodies."""
+S = 2, row 1 has no labels.  V in {2, 5, 257, 260} covers the scalar and the 16-byte row paths of the emit and gradient bodies.
+
+Beyond the base case: rnnt_prune_kernel's second and third pass of its 256 threads over the frames, with T_b on either side of 256
+(test_prune_ranges_on_long_rows), its smallest shapes, and the simple loss's gradient on a lattice wider than 256
+(test_simple_gradient_on_one_wide_lattice).  -inf scores and rows without a path: tests/test_gpu_rnnt_masked.py."""
 import ctypes as C
 import functools
 import math
@@ -324,6 +328,76 @@ def test_one_wide_lattice(gpu):
     _close("wide banded loss", bl.numpy()[:, None], l64[:, None], l32[:, None])
     _close("wide banded gradient", bg.numpy(), g64, g32)
     assert float(bl[0]) >= float(loss[0]) * (1 - K.FLOOR)
+
+
+def test_simple_gradient_on_one_wide_lattice(gpu):
+    """the same case, with the gradient and the occupancies: rnnt_simple_reduce_kernel sums 301 terms into every d_am element and 50
+    into every d_lm element (the base case: 5 and 9), and the cell kernel runs on a lattice wider than 256"""
+    c = _wide()
+    loss, dam, dlm, occ = _simple(gpu, c["am"], c["lm"], c)
+    assert torch.equal(loss, _simple(gpu, c["am"], c["lm"], c, want_grad=False)[0])
+    r64 = P.simple_loss(c["am"], c["lm"], c["labels"], c["lens"], c["blank"])
+    r32 = P.simple_loss(c["am"], c["lm"], c["labels"], c["lens"], c["blank"], torch.float32)
+    assert not torch.isnan(dam).any() and not torch.isnan(dlm).any() and not torch.isnan(occ).any()
+    _close("wide simple loss", loss.cpu().numpy()[:, None], r64[0][:, None], r32[0][:, None])
+    _close("wide d_am", dam.cpu().numpy(), r64[1], r32[1])
+    _close("wide d_lm", dlm.cpu().numpy(), r64[2], r32[2])
+    _close("wide occ", occ.cpu().numpy(), r64[3], r32[3])
+
+
+# ---- the prune kernel beyond one pass of its 256 threads over the frames ----
+
+PRUNE_THREADS = 256                                   # of rnnt_prune_kernel, mirrored (tests/test_rnnt_masked_host.py reads the source)
+
+
+def _band_is_connected(r, lens, ll, S):
+    for b, (Tb, Ub) in enumerate(zip(lens, ll)):
+        fin = max(0, Ub + 1 - S)
+        assert r[b, 0] == 0 and r[b, Tb - 1] == fin and (r[b, Tb:] == fin).all(), b
+        assert all(0 <= r[b, t + 1] - r[b, t] <= S - 1 for t in range(Tb - 1)), b
+
+
+def test_prune_ranges_on_long_rows(gpu):
+    """T = 600: the threads go over t three times; T_b = 600, 257 (one frame into the second pass) and 256 (the first pass exactly)"""
+    B, T, ML, lens, ll, S = 3, 600, 6, [600, 257, 256], [6, 0, 4], 3
+    assert T > 2 * PRUNE_THREADS and sorted(lens)[:2] == [PRUNE_THREADS, PRUNE_THREADS + 1] and all(P.feasible(n, u, S) for n, u in zip(lens, ll))
+    # random, plus a ridge that climbs over the whole row: the ranges never go down, so on noise alone they would reach their end within
+    # a few frames and stay, whatever the later frames chose
+    occ = np.random.default_rng(600).uniform(0, 1, (B, T, ML + 1)).astype(np.float32)
+    for b, (n, u) in enumerate(zip(lens, ll)):
+        for t in range(n):
+            s = int(round(max(0, u + 1 - S) * t / (n - 1)))
+            occ[b, t, s:s + S] += 4.0
+    want = P.prune_ranges(occ, lens, ll, S)
+    r = _ranges(gpu, torch.from_numpy(occ).to(gpu), S, lens=lens, ll=ll).cpu().numpy()
+    assert np.array_equal(r, want), np.nonzero(r != want)
+    _band_is_connected(r, lens, ll, S)
+    assert len(set(want[0, PRUNE_THREADS:].tolist())) > 1             # the later passes decide something
+    # NaN in the padding (t >= T_b, u > U_b) changes nothing: no window of a row with U_b + 1 >= S holds such a cell, and a row with
+    # fewer positions than S (row 1) has the one window s = 0, whatever it weighs
+    nan = occ.copy()
+    for b, (n, u) in enumerate(zip(lens, ll)):
+        nan[b, n:] = np.nan
+        nan[b, :, u + 1:] = np.nan
+    r2 = _ranges(gpu, torch.from_numpy(nan).to(gpu), S, lens=lens, ll=ll).cpu().numpy()
+    assert np.array_equal(r2, want)
+    assert np.array_equal(NL.rnnt_prune_ranges(occ, ll, S, input_lengths=lens), want)
+
+
+def test_prune_ranges_at_the_smallest_shapes(gpu):
+    """one frame on the feasibility edge (T_b = 1, U_b = 1, S = 2); S = 1 on a batch whose labels are all empty.  fin is 0 at both
+    shapes, so 0 is the only answer a correct walk can give: what this guards is that the call is accepted at these sizes, that every
+    element of the ranges is written (they are prefilled with -77), frames past T_b included, and that a window of S = U1 positions
+    and steps of S - 1 = 0 stay inside the tensors.  It cannot tell one choice of window from another; test_prune_ranges_on_long_rows
+    and the tie test do that"""
+    assert P.feasible(1, 1, 2) and not P.feasible(1, 2, 2)
+    occ = np.array([[[0.25, 0.75]]], np.float32)
+    r = _ranges(gpu, torch.from_numpy(occ).to(gpu), 2, lens=[1], ll=[1]).cpu().numpy()
+    assert r.tolist() == P.prune_ranges(occ, [1], [1], 2).tolist() == [[0]]
+    occ = np.ones((2, 5, 1), np.float32)
+    occ[1, 3:] = np.nan
+    r = _ranges(gpu, torch.from_numpy(occ).to(gpu), 1, lens=[5, 3], ll=[0, 0]).cpu().numpy()
+    assert r.tolist() == P.prune_ranges(occ, [5, 3], [0, 0], 1).tolist() == [[0] * 5, [0] * 5]
 
 
 def test_repeat_and_batch_position(gpu):
