@@ -993,6 +993,52 @@ int nntk_ctc_beam_decode_lm(const float *probs, int batch, int T, int C, const i
 NntkCtcBeamStream nntk_ctc_beam_stream_create_lm(int batch, int max_frames, int C, int blank, int beam_width, int cutoff_top_n, int nbest,
                                                  int max_labels, NntkNgramLm lm);
 size_t nntk_ctc_beam_stream_state_bytes_lm(int batch, int max_frames, int C, int beam_width, int cutoff_top_n, int max_labels);
+/* ---- label timestamps and confidences (INTEGRATION.md "CTC prefix beam search", Label timestamps and confidences) ----
+ * The option form of the search: lm as above (NULL: acoustic), and per reported label the frame it is timed at and the log of its
+ * acoustic probability there.  o == NULL, or a struct with everything off, is nntk_ctc_beam_decode_device bit for bit; lm alone is
+ * nntk_ctc_beam_decode_lm_device bit for bit.  Detail is on when either pointer is not NULL; either may be NULL.  Labels, lengths and
+ * score bits never depend on it.
+ *   The rule.  Every beam entry carries one frame per label.  A plain stay keeps them; a plain extension at frame t appends t (counted
+ *     from the row's start; in a stream from the row's last reset).  When entry j's stay is merged into entry i's extend cell, the
+ *     extension's p_nb' (the LM factor included) is compared with j's stay p_nb' in the search's own number form: extension > stay,
+ *     strictly, replaces the LAST frame of j by t; otherwise (exact ties included) j's frames stay.  So a label's frame is the latest
+ *     frame at which entering the label outweighed continuing it -- the usual rule of open CTC decoders, NOT the Viterbi alignment
+ *     (nntk_ctc_align_device gives that).  Which frames an entry holds never influences a mass, the order, the cut or an LM state.
+ *   label_logps[k] = (float) log((double) probs[b][label_frames[k]][labels[k]]): the acoustic posterior, never the LM factor; always
+ *     finite (a zero-probability extension is dropped, and a merge takes a frame only when its extension is > 0).
+ *   label_frames / label_logps [batch][nbest][T] (the one-shot calls) or [batch][nbest][max_labels] (a push): frames are followed by
+ *     -1, log-probabilities by 0.0f; a slot without a hypothesis is -1 / 0.0f throughout; every element of an output that is asked
+ *     for is written.  In the device forms they are device pointers, in the host forms host pointers.
+ *   Refused before anything is enqueued (-1 / NULL, nntk_last_error(), nothing written): everything the plain calls refuse; a detail
+ *     output that is not 4-byte aligned or overlaps the other detail output, d_labels_out, d_out_lengths, d_scores, d_probs or
+ *     d_workspace; detail pointers pushed into a stream created without detail; a stream created with detail pushed through
+ *     nntk_ctc_beam_stream_push[_device].
+ *   Workspace: nntk_ctc_beam_opt_workspace_floats -- detail needs no words of its own.  A stream with detail carries two more
+ *     double-buffered strings per row and beam entry, the frames and the log-probabilities of its labels (earlier pushes'
+ *     probabilities are gone): nntk_ctc_beam_stream_state_bytes_opt is 16 * max_labels bytes more per row and beam entry, next to the
+ *     40 (44 with a model) and the 8 * max_labels of the label strings.  A hypothesis longer than max_labels keeps the frames and
+ *     log-probabilities of its first max_labels labels, as it keeps those labels.  After every push the five outputs have the bits
+ *     of the one-shot call on the row's frames since its reset, for every chunking. */
+typedef struct {
+    NntkNgramLm lm;        /* NULL: acoustic scores only */
+    int *label_frames;     /* [batch][nbest][T], or NULL */
+    float *label_logps;    /* the same shape, or NULL */
+} NntkCtcBeamOptions;
+size_t nntk_ctc_beam_opt_workspace_floats(int batch, int T, int C, int beam_width, int cutoff_top_n, const NntkCtcBeamOptions *o);
+int nntk_ctc_beam_decode_opt_device(const float *d_probs, int batch, int T, int C, const int *input_lengths, int blank, int beam_width,
+                                    int cutoff_top_n, int nbest, const NntkCtcBeamOptions *o, int *d_labels_out, int *d_out_lengths,
+                                    float *d_scores, float *d_workspace);
+int nntk_ctc_beam_decode_opt(const float *probs, int batch, int T, int C, const int *input_lengths, int blank, int beam_width,
+                             int cutoff_top_n, int nbest, const NntkCtcBeamOptions *o, int *labels_out, int *out_lengths, float *scores);
+NntkCtcBeamStream nntk_ctc_beam_stream_create_opt(int batch, int max_frames, int C, int blank, int beam_width, int cutoff_top_n, int nbest,
+                                                  int max_labels, NntkNgramLm lm, int with_detail);
+size_t nntk_ctc_beam_stream_state_bytes_opt(int batch, int max_frames, int C, int beam_width, int cutoff_top_n, int max_labels, int with_lm,
+                                            int with_detail);
+int nntk_ctc_beam_stream_push_opt_device(NntkCtcBeamStream s, const float *d_probs, const int *n_frames, const int *final,
+                                         int *d_labels_out, int *d_out_lengths, float *d_scores, int *d_label_frames,
+                                         float *d_label_logps);
+int nntk_ctc_beam_stream_push_opt(NntkCtcBeamStream s, const float *probs, const int *n_frames, const int *final, int *labels_out,
+                                  int *out_lengths, float *scores, int *label_frames, float *label_logps);
 /* Streaming best path: the labels THIS chunk adds.  d_probs [batch][T][C]; n_frames HOST int [batch], 0..T; d_prev [batch] device
  * int, in/out: the argmax of the row's last frame seen, -1 = a new stream (the caller resets a row by writing -1); unchanged where
  * n_frames[b] == 0.  A frame whose argmax equals the previous frame's (d_prev[b] for the chunk's first) is dropped, then blanks are.

@@ -75,6 +75,10 @@ class NntkRnntBeamOptions(C.Structure):
     _fields_ = [("lm", vp), ("length_norm", C.c_int), ("label_frames", vp), ("label_logps", vp)]
 
 
+class NntkCtcBeamOptions(C.Structure):
+    _fields_ = [("lm", vp), ("label_frames", vp), ("label_logps", vp)]
+
+
 class DefaultWeights(C.Structure):
     _fields_ = [("W", fp), ("b", fp)]
 
@@ -466,6 +470,16 @@ SIGNATURES = {
     "nntk_ctc_beam_decode_lm": (C.c_int, [fp, C.c_int, C.c_int, C.c_int, ip, C.c_int, C.c_int, C.c_int, C.c_int, vp, ip, ip, fp]),
     "nntk_ctc_beam_stream_create_lm": (vp, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
     "nntk_ctc_beam_stream_state_bytes_lm": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    # label timestamps and confidences: the option form (NntkCtcBeamOptions), one-shot and streamed
+    "nntk_ctc_beam_opt_workspace_floats": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(NntkCtcBeamOptions)]),
+    "nntk_ctc_beam_decode_opt_device": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, ip, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                  C.POINTER(NntkCtcBeamOptions), vp, vp, vp, vp]),
+    "nntk_ctc_beam_decode_opt": (C.c_int, [fp, C.c_int, C.c_int, C.c_int, ip, C.c_int, C.c_int, C.c_int, C.c_int,
+                                           C.POINTER(NntkCtcBeamOptions), ip, ip, fp]),
+    "nntk_ctc_beam_stream_create_opt": (vp, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int]),
+    "nntk_ctc_beam_stream_state_bytes_opt": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "nntk_ctc_beam_stream_push_opt_device": (C.c_int, [vp, vp, ip, ip, vp, vp, vp, vp, vp]),
+    "nntk_ctc_beam_stream_push_opt": (C.c_int, [vp, fp, ip, ip, ip, ip, fp, ip, fp]),
     "nntk_ctc_align_workspace_floats": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "nntk_ctc_align_device": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, ip, ip, ip, C.c_int, C.c_int, vp, vp, vp, vp]),
     "nntk_ctc_align": (C.c_int, [fp, C.c_int, C.c_int, C.c_int, ip, ip, ip, C.c_int, C.c_int, ip, ip, fp]),

@@ -33,6 +33,13 @@
 // as by reaching state 0.  Cells stay 8 bytes: the next state is looked up again for the at most W surviving extend cells.  After the
 // row's last frame every total is multiplied by the end-of-sentence factor of its state and the entries are ranked again; the
 // backtrack (or the commit of a stream) reports in that order, and a stream carries the beam as it was before it.
+//
+// Label timestamps (DETAIL instantiations only; INTEGRATION.md "Label timestamps and confidences").  A label's frame is the latest frame
+// at which entering the label outweighed continuing it.  The records already say where a label entered (class >= 0, at the length it
+// made).  The one new bit: when a stay is merged into an extend cell, the merging lane compares extension and stay by their keys just
+// before it sums them, and a merge with extension > stay is recorded with class -2 instead of -1.  A walker going backwards gives
+// position len - 1 the frame of the first extension-or-(-2) record it meets at length len and ignores the earlier ones; `r.y >= 0`
+// walkers never see the mark.  Confidence: ln of the acoustic probability of the label at that frame, gathered by the walker.
 #include <stdint.h>
 #include <limits.h>
 #include "nntk_common.hpp"
@@ -105,6 +112,8 @@ __device__ __forceinline__ float beam_score(float4 m) {
     const xf s = xf_add2(pb, pnb);
     return (float)((double)s.e * 0.69314718055994530942 + log((double)s.m));
 }
+// a label's confidence: ln of its acoustic probability at its reported frame, in double, rounded once.  One expression for both forms.
+__device__ __forceinline__ float beam_logp(float p) { return (float)log((double)p); }
 
 // ---- language model: F(state, c) and next(state, c) of INTEGRATION.md "Language-model fusion" ----
 __device__ __forceinline__ xf xf_mul(xf a, xf b) { return xf_norm(a.m * b.m, a.e + b.e); }
@@ -148,8 +157,8 @@ struct BeamCarry {
     const int *seen;                      // ctl + B
 };
 // buffer of a streaming handle, in 4-byte words; every part starts on a 16-byte boundary
-struct BeamStreamLayout { size_t ctl, nb, mass, h, ph, tail, str, hist, cut, lm, total; };
-static BeamStreamLayout beam_stream_layout(int B, int T, int W, int ncut, int L, bool lm = false) {
+struct BeamStreamLayout { size_t ctl, nb, mass, h, ph, tail, str, hist, cut, lm, fstr, lstr, total; };
+static BeamStreamLayout beam_stream_layout(int B, int T, int W, int ncut, int L, bool lm = false, bool detail = false) {
     BeamStreamLayout l;
     const size_t b = B > 0 ? (size_t)B : 0, t = T > 0 ? (size_t)T : 0, w = W > 0 ? (size_t)W : 0, n = ncut > 0 ? (size_t)ncut : 0;
     const size_t ml = L > 0 ? (size_t)L : 0;
@@ -164,7 +173,9 @@ static BeamStreamLayout beam_stream_layout(int B, int T, int W, int ncut, int L,
     l.hist = l.str + up(2 * b * w * ml);
     l.cut = l.hist + up(2 * b * t * w);
     l.lm = l.cut + up(2 * b * t * n);                                          // the carried LM states, behind everything else
-    l.total = l.lm + (lm ? up(b * w) : 0) + 4;
+    l.fstr = l.lm + (lm ? up(b * w) : 0);                                      // detail: both halves of the frame strings, then of the
+    l.lstr = l.fstr + (detail ? up(2 * b * w * ml) : 0);                       // log-probability strings: 16 * L bytes per row and entry
+    l.total = l.lstr + (detail ? up(2 * b * w * ml) : 0) + 4;
     return l;
 }
 
@@ -219,7 +230,9 @@ __global__ __launch_bounds__(CTC_THREADS) void ctc_beam_cut_kernel(const float *
 // a row that has seen no frame) and ends there; the masses of the frames in between are not kept.
 // LM: every extension is weighted by the language model `lm`; !STREAM: the final ranking goes to forder / fmass ([B][W] each: the entry
 // of the last beam that hypothesis k is, and its finalised total as (m, e, 0, zero's exponent)) and its size to nfin.
-template <bool CUT, bool STAGE, bool STREAM, bool LM>
+// DETAIL (label timestamps; "Label timestamps" below): a merge whose extension outweighs the stay it is summed with writes its record's
+// class as -2 instead of -1.  Nothing else changes: no mass, key, cut, hash or LM state depends on it.
+template <bool CUT, bool STAGE, bool STREAM, bool LM, bool DETAIL>
 __global__ __launch_bounds__(CTC_THREADS) void ctc_beam_kernel(const float *__restrict__ probs, int T, int C, int blank, int W, int n,
                                                                unsigned magic, const int *__restrict__ lens, int *__restrict__ nfin,
                                                                int2 *__restrict__ hist, float4 *__restrict__ mass,
@@ -378,8 +391,10 @@ __global__ __launch_bounds__(CTC_THREADS) void ctc_beam_kernel(const float *__re
         }
         CTC_LDS_BARRIER();
         // ---- merges: p_nb' = stay + extension, in that order; the cell holds the candidate's total ----
+        bool moved = false;                                                    // DETAIL: this lane's merge takes the frame (same lane below)
         if (tid < nb && s_home[o + tid] >= 0) {
             const int hc = s_home[o + tid];
+            if (DETAIL) moved = beam_key(cell[hc]) > beam_key(f_spnb[tid]);       // extension > stay, strictly, as (exponent, mantissa)
             const xf mnb = xf_add2(xf_unpack(f_spnb[tid]), xf_unpack(cell[hc]));
             f_spnb[tid] = xf_pack(mnb);
             cell[hc] = xf_pack(xf_add2(xf_unpack(f_spb[tid]), mnb));
@@ -519,7 +534,7 @@ __global__ __launch_bounds__(CTC_THREADS) void ctc_beam_kernel(const float *__re
                 s_last[on + r] = s_last[o + tid];
                 s_len[on + r] = s_len[o + tid];
                 if (LM) s_lm[on + r] = s_lm[o + tid];
-                f_rec[r] = make_int2(tid | (s_len[o + tid] << 8), -1);
+                f_rec[r] = make_int2(tid | (s_len[o + tid] << 8), DETAIL && moved ? -2 : -1);
             }
         }
         if (STAGE && t + 1 < Tb) {
@@ -592,12 +607,16 @@ __global__ __launch_bounds__(CTC_THREADS) void ctc_beam_kernel(const float *__re
 }
 
 // ---- backtrack: hypothesis k of a row is entry k of its last frame; FIN (the LM calls): entry forder[k], with the total fmass[k] ----
-template <bool FIN>
+// DETAIL: the walking lane also writes frames / logps ([B][nbest][T] each, either may be null; "Label timestamps" above).  `ft`, the frame
+// a -2 record claimed for the position the walk stands at, lives in a register of the lane and so crosses the staged blocks' edges.
+template <bool FIN, bool DETAIL>
 __global__ __launch_bounds__(CTC_THREADS) void ctc_beam_backtrack_kernel(int T, int W, int nbest, const int *__restrict__ lens,
                                                                          const int *__restrict__ nfin, const int2 *__restrict__ hist,
                                                                          const float4 *__restrict__ mass, const int *__restrict__ forder,
                                                                          const float4 *__restrict__ fmass, int *__restrict__ labels,
-                                                                         int *__restrict__ out_len, float *__restrict__ scores) {
+                                                                         int *__restrict__ out_len, float *__restrict__ scores,
+                                                                         const float *__restrict__ probs, int C, int *__restrict__ frames,
+                                                                         float *__restrict__ logps) {
     extern __shared__ __align__(16) unsigned char beam_smem[];
     __shared__ int s_hlen[BEAM_MAX_W];
     int2 *rec = (int2 *)beam_smem;
@@ -607,7 +626,10 @@ __global__ __launch_bounds__(CTC_THREADS) void ctc_beam_backtrack_kernel(int T, 
     const int2 *hrow = hist + (long)b * T * W;
     const float4 *mrow = mass + (long)b * T * W;
     int *lab = labels + (long)b * nbest * T;
-    int rank = tid, len = -1, pos = -1;
+    const float *prow = DETAIL ? probs + (long)b * T * C : nullptr;
+    int *fr = DETAIL && frames ? frames + (long)b * nbest * T : nullptr;
+    float *lp = DETAIL && logps ? logps + (long)b * nbest * T : nullptr;
+    int rank = tid, len = -1, pos = -1, ft = -1;
     if (tid < nbest) {
         float score = -INFINITY;
         if (tid < nh) {
@@ -636,7 +658,16 @@ __global__ __launch_bounds__(CTC_THREADS) void ctc_beam_backtrack_kernel(int T, 
         if (tid < nh) {
             for (int t = t1 - 1; t >= t0; --t) {
                 const int2 r = rec[(t - t0) * W + rank];
-                if (r.y >= 0 && pos >= 0) lab[(long)tid * T + pos--] = r.y;
+                if (DETAIL && r.y == -2 && ft < 0) ft = t;                     // the latest merge that took this position's frame
+                if (r.y >= 0 && pos >= 0) {
+                    if (DETAIL) {
+                        const int f = ft >= 0 ? ft : t;
+                        if (fr) fr[(long)tid * T + pos] = f;
+                        if (lp) lp[(long)tid * T + pos] = beam_logp(prow[(long)f * C + r.y]);
+                        ft = -1;
+                    }
+                    lab[(long)tid * T + pos--] = r.y;
+                }
                 rank = r.x & 0xff;
             }
         }
@@ -645,7 +676,13 @@ __global__ __launch_bounds__(CTC_THREADS) void ctc_beam_backtrack_kernel(int T, 
     const long cells = (long)nbest * T;
     for (long q = tid; q < cells; q += CTC_THREADS) {
         const int k = (int)(q / T), p = (int)(q % T);
-        if (p >= s_hlen[k]) lab[q] = -1;
+        if (p >= s_hlen[k]) {
+            lab[q] = -1;
+            if (DETAIL) {
+                if (fr) fr[q] = -1;
+                if (lp) lp[q] = 0.0f;
+            }
+        }
     }
 }
 
@@ -656,13 +693,22 @@ __global__ __launch_bounds__(CTC_THREADS) void ctc_beam_backtrack_kernel(int T, 
 // without frames in this push only rewrites its outputs from what it holds.  FIN (a stream with a language model): what is REPORTED is
 // the beam after the end-of-sentence factors -- entry tid goes to output slot `slot` (its rank among the finalised totals, or none) --
 // while the carried beam and its strings stay in entry order, unfinalised.
-template <bool FIN>
+// DETAIL: every entry also carries the frame and the log-probability of each of its labels (fstrs / lstrs, laid out and double-buffered
+// like strs): earlier pushes' probabilities are gone, so the values travel.  A label gained in this push takes `seen` + its frame and
+// this push's probability; a -2 record that no extension of this push answers moves the LAST element the ancestor held (s_mvt: the
+// push's frame, or -1), frame and log-probability, if that position is stored at all.  oframes / ologps ([B][nbest][L], either may be
+// null) report like labels.
+template <bool FIN, bool DETAIL>
 __global__ __launch_bounds__(CTC_THREADS) void ctc_beam_commit_kernel(int B, int T, int W, int nbest, int L, const int *__restrict__ ctl,
                                                                       BeamCarry cs, const int2 *__restrict__ hist, int *__restrict__ strs,
                                                                       int *__restrict__ labels, int *__restrict__ out_len,
-                                                                      float *__restrict__ scores, nntk_shim_lm lm) {
+                                                                      float *__restrict__ scores, nntk_shim_lm lm,
+                                                                      const float *__restrict__ probs, int C, int *__restrict__ fstrs,
+                                                                      float *__restrict__ lstrs, int *__restrict__ oframes,
+                                                                      float *__restrict__ ologps) {
     extern __shared__ __align__(16) unsigned char beam_smem[];
     __shared__ int s_hlen[BEAM_MAX_W], s_anc[BEAM_MAX_W], s_alen[BEAM_MAX_W];
+    __shared__ int s_mvt[DETAIL ? BEAM_MAX_W : 1];
     __shared__ int s_slot[FIN ? BEAM_MAX_W : 1], s_ord[FIN ? BEAM_MAX_W : 1];
     __shared__ u64 s_key[FIN ? BEAM_MAX_W : 1];
     int2 *rec = (int2 *)beam_smem;
@@ -675,6 +721,13 @@ __global__ __launch_bounds__(CTC_THREADS) void ctc_beam_commit_kernel(int B, int
     int *dst = strs + ((long)(par ^ 1) * B + b) * W * L;
     const int2 *hrow = hist + (long)b * T * W;
     int *lab = labels + (long)b * nbest * L;
+    const int *fsrc = DETAIL ? fstrs + ((long)par * B + b) * W * L : nullptr;
+    int *fdst = DETAIL ? fstrs + ((long)(par ^ 1) * B + b) * W * L : nullptr;
+    const float *lsrc = DETAIL ? lstrs + ((long)par * B + b) * W * L : nullptr;
+    float *ldst = DETAIL ? lstrs + ((long)(par ^ 1) * B + b) * W * L : nullptr;
+    const float *prow = DETAIL ? probs + (long)b * T * C : nullptr;
+    int *ofr = DETAIL && oframes ? oframes + (long)b * nbest * L : nullptr;
+    float *olp = DETAIL && ologps ? ologps + (long)b * nbest * L : nullptr;
     int len = -1;
     if (tid < nb) len = fresh ? 0 : cs.tail[(long)b * W + tid].y;
     int slot = tid < nh ? tid : -1;                                            // the output slot that reports entry tid
@@ -724,11 +777,16 @@ __global__ __launch_bounds__(CTC_THREADS) void ctc_beam_commit_kernel(int B, int
         for (long q = tid; q < cells_out; q += CTC_THREADS) {
             const int k = (int)(q / L), p = (int)(q % L);
             const int e = FIN ? (k < nh ? s_ord[k] : 0) : k;
-            lab[q] = (k < nh && p < min(s_hlen[e], L)) ? src[(long)e * L + p] : -1;
+            const bool held = k < nh && p < min(s_hlen[e], L);
+            lab[q] = held ? src[(long)e * L + p] : -1;
+            if (DETAIL) {
+                if (ofr) ofr[q] = held ? fsrc[(long)e * L + p] : -1;
+                if (olp) olp[q] = held ? lsrc[(long)e * L + p] : 0.0f;
+            }
         }
         return;
     }
-    int rank = tid, gained = 0;
+    int rank = tid, gained = 0, ft = -1;
     const int TC = max(1, BEAM_BT_RECORDS / W);
     for (int t1 = Tb; t1 > 0; t1 -= TC) {
         const int t0 = max(0, t1 - TC);
@@ -740,20 +798,45 @@ __global__ __launch_bounds__(CTC_THREADS) void ctc_beam_commit_kernel(int B, int
         if (tid < nb) {
             for (int t = t1 - 1; t >= t0; --t) {
                 const int2 r = rec[(t - t0) * W + rank];
+                if (DETAIL && r.y == -2 && ft < 0) ft = t;                     // the latest merge that took this position's frame
                 if (r.y >= 0) {
                     const int pos = (r.x >> 8) - 1;
                     if (pos < L) {
+                        const bool told = FIN ? slot >= 0 : tid < nbest;
+                        const long at = (long)(FIN ? slot : tid) * L + pos;
                         dst[(long)tid * L + pos] = r.y;
-                        if (FIN ? slot >= 0 : tid < nbest) lab[(long)(FIN ? slot : tid) * L + pos] = r.y;
+                        if (told) lab[at] = r.y;
+                        if (DETAIL) {
+                            const int f = ft >= 0 ? ft : t;
+                            const float v = beam_logp(prow[(long)f * C + r.y]);
+                            fdst[(long)tid * L + pos] = seen + f;
+                            ldst[(long)tid * L + pos] = v;
+                            if (told && ofr) ofr[at] = seen + f;
+                            if (told && olp) olp[at] = v;
+                        }
                     }
+                    if (DETAIL) ft = -1;
                     ++gained;
                 }
                 rank = r.x & 0xff;
             }
         }
     }
-    if (tid < nb) { s_anc[tid] = rank; s_alen[tid] = len - gained; }
+    if (tid < nb) {
+        s_anc[tid] = rank;
+        s_alen[tid] = len - gained;
+        if (DETAIL) s_mvt[tid] = ft;
+    }
     __syncthreads();
+    // DETAIL: element p of entry k's ancestor, moved when this push took the ancestor's last frame
+    auto carried = [&](int k, int p, int v, int &f, float &lg) {
+        f = fsrc[(long)s_anc[k] * L + p];
+        lg = lsrc[(long)s_anc[k] * L + p];
+        if (p == s_alen[k] - 1 && s_mvt[k] >= 0) {
+            f = seen + s_mvt[k];
+            lg = beam_logp(prow[(long)s_mvt[k] * C + min(max(v, 0), C - 1)]);
+        }
+    };
     // the ancestors' strings, and the -1 behind every reported hypothesis; the places in between were written above
     const long cells = (long)max(nb, nbest) * L;
     for (long q = tid; q < cells; q += CTC_THREADS) {
@@ -764,14 +847,38 @@ __global__ __launch_bounds__(CTC_THREADS) void ctc_beam_commit_kernel(int B, int
                 const int v = src[(long)s_anc[k] * L + p];
                 dst[(long)k * L + p] = v;
                 if (s_slot[k] >= 0) lab[(long)s_slot[k] * L + p] = v;
+                if (DETAIL) {
+                    int f;
+                    float lg;
+                    carried(k, p, v, f, lg);
+                    fdst[(long)k * L + p] = f;
+                    ldst[(long)k * L + p] = lg;
+                    if (s_slot[k] >= 0 && ofr) ofr[(long)s_slot[k] * L + p] = f;
+                    if (s_slot[k] >= 0 && olp) olp[(long)s_slot[k] * L + p] = lg;
+                }
             }
-            if (k < nbest && (k >= nh || p >= min(s_hlen[s_ord[k < nh ? k : 0]], L))) lab[(long)k * L + p] = -1;
+            if (k < nbest && (k >= nh || p >= min(s_hlen[s_ord[k < nh ? k : 0]], L))) {
+                lab[(long)k * L + p] = -1;
+                if (DETAIL && ofr) ofr[(long)k * L + p] = -1;
+                if (DETAIL && olp) olp[(long)k * L + p] = 0.0f;
+            }
         } else if (k < nb && p < min(s_alen[k], L)) {
             const int v = src[(long)s_anc[k] * L + p];
             dst[(long)k * L + p] = v;
             if (k < nbest) lab[(long)k * L + p] = v;
+            if (DETAIL) {
+                int f;
+                float lg;
+                carried(k, p, v, f, lg);
+                fdst[(long)k * L + p] = f;
+                ldst[(long)k * L + p] = lg;
+                if (k < nbest && ofr) ofr[(long)k * L + p] = f;
+                if (k < nbest && olp) olp[(long)k * L + p] = lg;
+            }
         } else if (k < nbest && (k >= nh || p >= min(s_hlen[k], L))) {
             lab[(long)k * L + p] = -1;
+            if (DETAIL && ofr) ofr[(long)k * L + p] = -1;
+            if (DETAIL && olp) olp[(long)k * L + p] = 0.0f;
         }
     }
 }
@@ -780,9 +887,10 @@ __global__ __launch_bounds__(CTC_THREADS) void ctc_beam_commit_kernel(int B, int
 
 // The class cut (when one applies) and the beam kernel.  One-shot call (STREAM false): lens = the rows' lengths, nfin / mass / forder /
 // fmass the workspace's, an empty carry.  Push (STREAM true): lens = the control block, cs = the handle's beam, those four null.
+// detail: the instantiations that mark the merges which take a label's frame.
 template <bool STREAM>
-static int beam_launch(const float *d_probs, int B, int T, int C, int blank, int W, int ncut, const nntk_shim_lm *lm, const int *d_lens,
-                       int *d_nfin, int2 *d_hist, float4 *d_mass, float2 *d_pairs, const BeamCarry &cs, int *d_forder, float4 *d_fmass) {
+static int beam_launch(const float *d_probs, int B, int T, int C, int blank, int W, int ncut, const nntk_shim_lm *lm, bool detail,
+                       const int *d_lens, int *d_nfin, int2 *d_hist, float4 *d_mass, float2 *d_pairs, const BeamCarry &cs, int *d_forder, float4 *d_fmass) {
     const int n = ncut ? ncut : C - 1;
     const long frames = (long)B * T;
     if (ncut && frames > 0) {
@@ -800,18 +908,21 @@ static int beam_launch(const float *d_probs, int B, int T, int C, int blank, int
                                     : "nntk_ctc_beam_decode_device: the beam does not fit one workgroup's LDS");
     const unsigned magic = n + 1 > 1 ? (unsigned)(0x100000000ull / (unsigned)(n + 1)) + 1u : 0u;
     const nntk_shim_lm lmv = lm ? *lm : nntk_shim_lm();
-#define BEAM_GO(CUT, STAGE, LM)                                                                                                    \
+#define BEAM_GO(CUT, STAGE, LM, DETAIL)                                                                                            \
     do {                                                                                                                           \
-        if (lds > 48 * 1024 && nntk_set_max_dynamic_lds((const void *)ctc_beam_kernel<CUT, STAGE, STREAM, LM>, lds)) return -1;    \
-        hipLaunchKernelGGL((ctc_beam_kernel<CUT, STAGE, STREAM, LM>), dim3((unsigned)B), dim3(CTC_THREADS), lds, nntk_stream(),    \
-                           d_probs, T, C, blank, W, n, magic, d_lens, d_nfin, d_hist, d_mass, d_pairs, cs, lmv, d_forder, d_fmass); \
+        if (lds > 48 * 1024 && nntk_set_max_dynamic_lds((const void *)ctc_beam_kernel<CUT, STAGE, STREAM, LM, DETAIL>, lds))       \
+            return -1;                                                                                                             \
+        hipLaunchKernelGGL((ctc_beam_kernel<CUT, STAGE, STREAM, LM, DETAIL>), dim3((unsigned)B), dim3(CTC_THREADS), lds,           \
+                           nntk_stream(), d_probs, T, C, blank, W, n, magic, d_lens, d_nfin, d_hist, d_mass, d_pairs, cs, lmv,     \
+                           d_forder, d_fmass);                                                                                     \
     } while (0)
-#define BEAM_GO2(LM)                                                                                                               \
+#define BEAM_GO2(LM, DETAIL)                                                                                                       \
     do {                                                                                                                           \
-        if (ncut) { if (stage) BEAM_GO(true, true, LM); else BEAM_GO(true, false, LM); }                                           \
-        else { if (stage) BEAM_GO(false, true, LM); else BEAM_GO(false, false, LM); }                                              \
+        if (ncut) { if (stage) BEAM_GO(true, true, LM, DETAIL); else BEAM_GO(true, false, LM, DETAIL); }                           \
+        else { if (stage) BEAM_GO(false, true, LM, DETAIL); else BEAM_GO(false, false, LM, DETAIL); }                              \
     } while (0)
-    if (lm) BEAM_GO2(true); else BEAM_GO2(false);
+    if (detail) { if (lm) BEAM_GO2(true, true); else BEAM_GO2(false, true); }
+    else { if (lm) BEAM_GO2(true, false); else BEAM_GO2(false, false); }
 #undef BEAM_GO2
 #undef BEAM_GO
     NNTK_LAUNCH_CHECK("ctc_beam_kernel");
@@ -825,8 +936,10 @@ size_t nntk_shim_ctc_beam_workspace_floats(int batch, int T, int C, int beam_wid
 }
 
 int nntk_shim_ctc_beam_decode(const float *d_probs, int B, int T, int C, const int *h_input_lengths, int blank, int W, int cutoff_top_n,
-                              int nbest, const nntk_shim_lm *lm, int *d_labels_out, int *d_out_lengths, float *d_scores, float *d_ws) {
+                              int nbest, const nntk_shim_lm *lm, int *d_labels_out, int *d_out_lengths, float *d_scores,
+                              int *d_label_frames, float *d_label_logps, float *d_ws) {
     if (B <= 0) return 0;
+    const bool detail = d_label_frames || d_label_logps;
     if (((uintptr_t)d_ws & 15) != 0) return nntk_fail_msg("nntk_ctc_beam_decode_device: the workspace must be 16-byte aligned");
     const int ncut = beam_ncut(C, cutoff_top_n), n = ncut ? ncut : C - 1;
     if (W < 1 || W > BEAM_MAX_W || nbest < 1 || nbest > W || (long)W * (n + 1) > BEAM_MAX_CELLS || T > BEAM_MAX_T)
@@ -838,24 +951,27 @@ int nntk_shim_ctc_beam_decode(const float *d_probs, int B, int T, int C, const i
     int2 *d_hist = (int2 *)(d_ws + lay.hist);
     float4 *d_mass = (float4 *)(d_ws + lay.mass);
     if (nntk_shim_upload_ints(d_lens, h_input_lengths, B)) return -1;
-    if (beam_launch<false>(d_probs, B, T, C, blank, W, ncut, lm, d_lens, d_nfin, d_hist, d_mass, (float2 *)(d_ws + lay.cut), BeamCarry(),
+    if (beam_launch<false>(d_probs, B, T, C, blank, W, ncut, lm, detail, d_lens, d_nfin, d_hist, d_mass, (float2 *)(d_ws + lay.cut), BeamCarry(),
                            d_forder, d_fmass)) return -1;
     const size_t blds = (size_t)BEAM_BT_RECORDS * sizeof(int2);
-#define BEAM_BT(FIN)                                                                                                               \
+#define BEAM_BT(FIN, DETAIL)                                                                                                       \
     do {                                                                                                                           \
-        if (nntk_set_max_dynamic_lds((const void *)ctc_beam_backtrack_kernel<FIN>, blds)) return -1;                               \
-        hipLaunchKernelGGL(ctc_beam_backtrack_kernel<FIN>, dim3((unsigned)B), dim3(CTC_THREADS), blds, nntk_stream(), T, W, nbest,   \
-                           d_lens, d_nfin, d_hist, d_mass, d_forder, d_fmass, d_labels_out, d_out_lengths, d_scores);              \
+        if (nntk_set_max_dynamic_lds((const void *)ctc_beam_backtrack_kernel<FIN, DETAIL>, blds)) return -1;                       \
+        hipLaunchKernelGGL((ctc_beam_backtrack_kernel<FIN, DETAIL>), dim3((unsigned)B), dim3(CTC_THREADS), blds, nntk_stream(), T, \
+                           W, nbest, d_lens, d_nfin, d_hist, d_mass, d_forder, d_fmass, d_labels_out, d_out_lengths, d_scores,     \
+                           d_probs, C, d_label_frames, d_label_logps);                                                             \
     } while (0)
-    if (lm) BEAM_BT(true); else BEAM_BT(false);
+    if (detail) { if (lm) BEAM_BT(true, true); else BEAM_BT(false, true); }
+    else { if (lm) BEAM_BT(true, false); else BEAM_BT(false, false); }
 #undef BEAM_BT
     NNTK_LAUNCH_CHECK("ctc_beam_backtrack_kernel");
     return 0;
 }
 
 // ---- streaming form: the handle's buffer (beam_stream_layout), one push ----
-size_t nntk_shim_ctc_beam_stream_floats(int batch, int max_frames, int C, int beam_width, int cutoff_top_n, int max_labels, int lm) {
-    return beam_stream_layout(batch, max_frames, beam_width, beam_ncut(C, cutoff_top_n), max_labels, lm != 0).total;
+size_t nntk_shim_ctc_beam_stream_floats(int batch, int max_frames, int C, int beam_width, int cutoff_top_n, int max_labels, int lm,
+                                        int detail) {
+    return beam_stream_layout(batch, max_frames, beam_width, beam_ncut(C, cutoff_top_n), max_labels, lm != 0, detail != 0).total;
 }
 
 // the limits of the kernel that only the launch knows in the one-shot call; no device is touched.  lm: with the per-entry LM state in the
@@ -870,12 +986,12 @@ int nntk_shim_ctc_beam_stream_check(int C, int W, int cutoff_top_n, int lm) {
 }
 
 int nntk_shim_ctc_beam_stream_push(const float *d_probs, int B, int T, int C, const int *h_ctl, int any_frames, int blank, int W,
-                                   int cutoff_top_n, int nbest, int L, const nntk_shim_lm *lm, int *d_labels_out, int *d_out_lengths,
-                                   float *d_scores, float *d_buf) {
+                                   int cutoff_top_n, int nbest, int L, const nntk_shim_lm *lm, int detail, int *d_labels_out,
+                                   int *d_out_lengths, float *d_scores, int *d_label_frames, float *d_label_logps, float *d_buf) {
     if (B <= 0) return 0;
     if (((uintptr_t)d_buf & 15) != 0) return nntk_fail_msg("nntk_ctc_beam_stream_push_device: the handle's buffer is not 16-byte aligned");
     const int ncut = beam_ncut(C, cutoff_top_n);
-    const BeamStreamLayout lay = beam_stream_layout(B, T, W, ncut, L, lm != nullptr);
+    const BeamStreamLayout lay = beam_stream_layout(B, T, W, ncut, L, lm != nullptr, detail != 0);
     int *d_ctl = (int *)d_buf;
     BeamCarry cs;
     cs.nb = (int *)(d_buf + lay.nb);
@@ -886,19 +1002,23 @@ int nntk_shim_ctc_beam_stream_push(const float *d_probs, int B, int T, int C, co
     cs.lm = lm ? (int *)(d_buf + lay.lm) : nullptr;
     cs.seen = d_ctl + B;
     int *d_strs = (int *)(d_buf + lay.str);
+    int *d_fstrs = (int *)(d_buf + lay.fstr);
+    float *d_lstrs = d_buf + lay.lstr;
     int2 *d_hist = (int2 *)(d_buf + lay.hist);
     const nntk_shim_lm lmv = lm ? *lm : nntk_shim_lm();
     if (nntk_shim_upload_ints(d_ctl, h_ctl, 4L * B)) return -1;
-    if (any_frames && beam_launch<true>(d_probs, B, T, C, blank, W, ncut, lm, d_ctl, nullptr, d_hist, nullptr, (float2 *)(d_buf + lay.cut),
+    if (any_frames && beam_launch<true>(d_probs, B, T, C, blank, W, ncut, lm, detail != 0, d_ctl, nullptr, d_hist, nullptr, (float2 *)(d_buf + lay.cut),
                                         cs, nullptr, nullptr)) return -1;
     const size_t blds = (size_t)BEAM_BT_RECORDS * sizeof(int2);
-#define BEAM_COMMIT(FIN)                                                                                                           \
+#define BEAM_COMMIT(FIN, DETAIL)                                                                                                   \
     do {                                                                                                                           \
-        if (nntk_set_max_dynamic_lds((const void *)ctc_beam_commit_kernel<FIN>, blds)) return -1;                                  \
-        hipLaunchKernelGGL(ctc_beam_commit_kernel<FIN>, dim3((unsigned)B), dim3(CTC_THREADS), blds, nntk_stream(), B, T, W, nbest, L, \
-                           d_ctl, cs, d_hist, d_strs, d_labels_out, d_out_lengths, d_scores, lmv);                                 \
+        if (nntk_set_max_dynamic_lds((const void *)ctc_beam_commit_kernel<FIN, DETAIL>, blds)) return -1;                          \
+        hipLaunchKernelGGL((ctc_beam_commit_kernel<FIN, DETAIL>), dim3((unsigned)B), dim3(CTC_THREADS), blds, nntk_stream(), B, T, \
+                           W, nbest, L, d_ctl, cs, d_hist, d_strs, d_labels_out, d_out_lengths, d_scores, lmv, d_probs, C,         \
+                           d_fstrs, d_lstrs, d_label_frames, d_label_logps);                                                       \
     } while (0)
-    if (lm) BEAM_COMMIT(true); else BEAM_COMMIT(false);
+    if (detail) { if (lm) BEAM_COMMIT(true, true); else BEAM_COMMIT(false, true); }
+    else { if (lm) BEAM_COMMIT(true, false); else BEAM_COMMIT(false, false); }
 #undef BEAM_COMMIT
     NNTK_LAUNCH_CHECK("ctc_beam_commit_kernel");
     return 0;

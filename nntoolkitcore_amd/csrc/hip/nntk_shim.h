@@ -177,20 +177,25 @@ typedef struct {
 } nntk_shim_lm;
 /* ---- CTC prefix beam search (ctc_beam.hip): the n-best prefixes of every row with their log-probabilities.  lm NULL (the sizes and the
  *      check: lm 0): acoustic scores only, on kernels compiled without the model.  h_input_lengths is HOST memory, checked by the caller
- *      (ctc.c), never NULL; d_ws 16-byte aligned, nntk_shim_ctc_beam_workspace_floats words ---- */
+ *      (ctc.c), never NULL; d_ws 16-byte aligned, nntk_shim_ctc_beam_workspace_floats words.  d_label_frames / d_label_logps
+ *      ([B][nbest][T], either or both NULL): the labels' frames and log-probabilities; both NULL: the kernels compiled without them ---- */
 size_t nntk_shim_ctc_beam_workspace_floats(int batch, int T, int C, int beam_width, int cutoff_top_n, int lm);
 int nntk_shim_ctc_beam_decode(const float *d_probs, int B, int T, int C, const int *h_input_lengths, int blank, int beam_width,
                               int cutoff_top_n, int nbest, const nntk_shim_lm *lm, int *d_labels_out, int *d_out_lengths,
-                              float *d_scores, float *d_ws);
+                              float *d_scores, int *d_label_frames, float *d_label_logps, float *d_ws);
 /* streaming form: d_buf = the handle's buffer, nntk_shim_ctc_beam_stream_floats words, 16-byte aligned, kept from push to push (the
  * carried beam, both halves of the label strings, the records and cut pairs of one push).  h_ctl HOST [4][B], built by ctc.c:
  * frames in this push | frames the row had seen before it | the current half of its label strings | 0.  any_frames 0: no row brings
- * a frame, only the outputs are rewritten.  _check: the launch-time limits, without a device. */
-size_t nntk_shim_ctc_beam_stream_floats(int batch, int max_frames, int C, int beam_width, int cutoff_top_n, int max_labels, int lm);
+ * a frame, only the outputs are rewritten.  _check: the launch-time limits, without a device.  detail: the handle also carries both
+ * halves of the labels' frame and log-probability strings; d_label_frames / d_label_logps ([B][nbest][max_labels], either may be NULL)
+ * report them and are NULL without it. */
+size_t nntk_shim_ctc_beam_stream_floats(int batch, int max_frames, int C, int beam_width, int cutoff_top_n, int max_labels, int lm,
+                                        int detail);
 int nntk_shim_ctc_beam_stream_check(int C, int beam_width, int cutoff_top_n, int lm);
 int nntk_shim_ctc_beam_stream_push(const float *d_probs, int B, int max_frames, int C, const int *h_ctl, int any_frames, int blank,
-                                   int beam_width, int cutoff_top_n, int nbest, int max_labels, const nntk_shim_lm *lm,
-                                   int *d_labels_out, int *d_out_lengths, float *d_scores, float *d_buf);
+                                   int beam_width, int cutoff_top_n, int nbest, int max_labels, const nntk_shim_lm *lm, int detail,
+                                   int *d_labels_out, int *d_out_lengths, float *d_scores, int *d_label_frames, float *d_label_logps,
+                                   float *d_buf);
 /* ---- CTC forced alignment (ctc_align.hip): the best single alignment of every row to its labels -- the state of every frame, the
  *      frame span of every label, ln of the path's probability.  The int arrays are HOST memory, already checked by the caller
  *      (ctc.c), never NULL; d_states / d_spans may be NULL; d_ws 16-byte aligned, nntk_shim_ctc_align_workspace_floats words ---- */

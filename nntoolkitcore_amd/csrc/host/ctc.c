@@ -5,6 +5,7 @@
  * device-pointer form and a host-pointer form (upload, device call, download).
  */
 #include <stdio.h>
+#include <stdint.h>
 #include <stdlib.h>
 #include "nntk_internal.h"
 
@@ -141,28 +142,67 @@ static int ctc_beam_lm_check(const char *who, NntkNgramLm lm, int C, int blank) 
     return 0;
 }
 
+/* the detail outputs (label frames / log-probabilities, nl elements each; INTEGRATION.md "Label timestamps and confidences") of a device
+ * call: 4-byte aligned, and apart from each other, from the other outputs and from what the kernels read while they write them */
+typedef struct { const void *p; size_t bytes; const char *name; } beam_span;
+static int beam_detail_check(const char *who, const int *d_frames, const float *d_logps, size_t nl, const beam_span *other, int n_other) {
+    const beam_span det[2] = { { d_frames, nl * sizeof(int), "d_label_frames" }, { d_logps, nl * sizeof(float), "d_label_logps" } };
+    char msg[200];
+    for (int i = 0; i < 2; ++i) {
+        if (!det[i].p) continue;
+        if ((uintptr_t)det[i].p & 3) {
+            snprintf(msg, sizeof msg, "%s: %s is not 4-byte aligned", who, det[i].name);
+            nntk_set_error(msg);
+            return -1;
+        }
+        for (int k = i + 1; k < 2 + n_other; ++k) {
+            const beam_span *q = k < 2 ? &det[k] : &other[k - 2];
+            const char *a = (const char *)det[i].p, *b = (const char *)q->p;
+            if (b && det[i].bytes && q->bytes && a < b + q->bytes && b < a + det[i].bytes) {
+                snprintf(msg, sizeof msg, "%s: %s overlaps %s", who, det[i].name, q->name);
+                nntk_set_error(msg);
+                return -1;
+            }
+        }
+    }
+    return 0;
+}
+
 size_t nntk_ctc_beam_workspace_floats(int batch, int T, int C, int beam_width, int cutoff_top_n) {
     return nntk_shim_ctc_beam_workspace_floats(batch, T, C, beam_width, cutoff_top_n, 0);
 }
 size_t nntk_ctc_beam_lm_workspace_floats(int batch, int T, int C, int beam_width, int cutoff_top_n) {
     return nntk_shim_ctc_beam_workspace_floats(batch, T, C, beam_width, cutoff_top_n, 1);
 }
+/* the detail outputs are written by the backtrack from what the search keeps anyway: no words of their own */
+size_t nntk_ctc_beam_opt_workspace_floats(int batch, int T, int C, int beam_width, int cutoff_top_n, const NntkCtcBeamOptions *o) {
+    return nntk_shim_ctc_beam_workspace_floats(batch, T, C, beam_width, cutoff_top_n, o && o->lm);
+}
 
 /* the device-pointer search under the name of the entry that was called */
 static int beam_decode_device(const char *who, const float *d_probs, int batch, int T, int C, const int *input_lengths, int blank,
                               int beam_width, int cutoff_top_n, int nbest, NntkNgramLm lm, int *d_labels_out, int *d_out_lengths,
-                              float *d_scores, float *d_workspace) {
+                              float *d_scores, int *d_label_frames, float *d_label_logps, float *d_workspace) {
     nntk_shim_clear_error();
     if (ctc_beam_check(who, batch, T, C, input_lengths, blank, beam_width, cutoff_top_n, nbest) || ctc_beam_lm_check(who, lm, C, blank))
         return -1;
     if (batch == 0) return 0;
     if (!d_out_lengths || !d_scores || !d_workspace || ((!d_probs || !d_labels_out) && T > 0)) return ctc_fail(who, "NULL tensor", 0, 0, 0);
+    if (d_label_frames || d_label_logps) {
+        const size_t nh = (size_t)batch * nbest, nl = nh * T;
+        const beam_span other[5] = {
+            { d_labels_out, nl * sizeof(int), "d_labels_out" }, { d_out_lengths, nh * sizeof(int), "d_out_lengths" },
+            { d_scores, nh * sizeof(float), "d_scores" }, { d_probs, (size_t)batch * T * C * sizeof(float), "d_probs" },
+            { d_workspace, sizeof(float) * nntk_shim_ctc_beam_workspace_floats(batch, T, C, beam_width, cutoff_top_n, lm != NULL),
+              "d_workspace" } };
+        if (beam_detail_check(who, d_label_frames, d_label_logps, nl, other, 5)) return -1;
+    }
     nntk_shim_lm tab;
     if (lm && nntk_ngram_lm_device(lm, &tab)) return -1;
     int *len = ctc_lengths(input_lengths, batch, T);
     if (!len) return -1;
     int rc = nntk_shim_ctc_beam_decode(d_probs, batch, T, C, len, blank, beam_width, cutoff_top_n, nbest, lm ? &tab : NULL, d_labels_out,
-                                       d_out_lengths, d_scores, d_workspace);
+                                       d_out_lengths, d_scores, d_label_frames, d_label_logps, d_workspace);
     free(len);
     return rc;
 }
@@ -171,26 +211,40 @@ int nntk_ctc_beam_decode_device(const float *d_probs, int batch, int T, int C, c
                                 int cutoff_top_n, int nbest, int *d_labels_out, int *d_out_lengths, float *d_scores,
                                 float *d_workspace) {
     return beam_decode_device("nntk_ctc_beam_decode_device", d_probs, batch, T, C, input_lengths, blank, beam_width, cutoff_top_n, nbest,
-                              NULL, d_labels_out, d_out_lengths, d_scores, d_workspace);
+                              NULL, d_labels_out, d_out_lengths, d_scores, NULL, NULL, d_workspace);
 }
 /* lm NULL: the call above itself, under its name */
 int nntk_ctc_beam_decode_lm_device(const float *d_probs, int batch, int T, int C, const int *input_lengths, int blank, int beam_width,
                                    int cutoff_top_n, int nbest, NntkNgramLm lm, int *d_labels_out, int *d_out_lengths, float *d_scores,
                                    float *d_workspace) {
     return beam_decode_device(lm ? "nntk_ctc_beam_decode_lm_device" : "nntk_ctc_beam_decode_device", d_probs, batch, T, C, input_lengths,
-                              blank, beam_width, cutoff_top_n, nbest, lm, d_labels_out, d_out_lengths, d_scores, d_workspace);
+                              blank, beam_width, cutoff_top_n, nbest, lm, d_labels_out, d_out_lengths, d_scores, NULL, NULL, d_workspace);
+}
+/* o NULL or all off: nntk_ctc_beam_decode_device itself; lm alone: the _lm_ call itself -- under their names */
+int nntk_ctc_beam_decode_opt_device(const float *d_probs, int batch, int T, int C, const int *input_lengths, int blank, int beam_width,
+                                    int cutoff_top_n, int nbest, const NntkCtcBeamOptions *o, int *d_labels_out, int *d_out_lengths,
+                                    float *d_scores, float *d_workspace) {
+    const char *who = o && (o->label_frames || o->label_logps) ? "nntk_ctc_beam_decode_opt_device"
+                      : o && o->lm ? "nntk_ctc_beam_decode_lm_device" : "nntk_ctc_beam_decode_device";
+    return beam_decode_device(who, d_probs, batch, T, C, input_lengths, blank, beam_width, cutoff_top_n, nbest, o ? o->lm : NULL,
+                              d_labels_out, d_out_lengths, d_scores, o ? o->label_frames : NULL, o ? o->label_logps : NULL, d_workspace);
 }
 
-/* the results of a host-pointer search or push, packed at d_o: labels [nl] | lengths [nh] | scores [nh] */
-static int beam_download(const int *d_o, size_t nl, size_t nh, int *labels_out, int *out_lengths, float *scores) {
+/* the results of a host-pointer search or push, packed at d_o: labels [nl] | lengths [nh] | scores [nh] | label frames [nl] |
+ * label log-probabilities [nl]; the last two only where the caller asked (either may be NULL) */
+static int beam_download(const int *d_o, size_t nl, size_t nh, int *labels_out, int *out_lengths, float *scores, int *label_frames,
+                         float *label_logps) {
     if (nl && nntk_shim_download(labels_out, d_o, nl * sizeof(int))) return -1;
     if (nntk_shim_download(out_lengths, d_o + nl, nh * sizeof(int))) return -1;
-    return nntk_shim_download(scores, d_o + nl + nh, nh * sizeof(float));
+    if (nntk_shim_download(scores, d_o + nl + nh, nh * sizeof(float))) return -1;
+    if (nl && label_frames && nntk_shim_download(label_frames, d_o + nl + 2 * nh, nl * sizeof(int))) return -1;
+    if (nl && label_logps && nntk_shim_download(label_logps, d_o + 2 * nl + 2 * nh, nl * sizeof(float))) return -1;
+    return 0;
 }
 
 static int beam_decode_host(const char *who, const float *probs, int batch, int T, int C, const int *input_lengths, int blank,
                             int beam_width, int cutoff_top_n, int nbest, NntkNgramLm lm, int *labels_out, int *out_lengths,
-                            float *scores) {
+                            float *scores, int *label_frames, float *label_logps) {
     nntk_shim_clear_error();
     if (ctc_beam_check(who, batch, T, C, input_lengths, blank, beam_width, cutoff_top_n, nbest) || ctc_beam_lm_check(who, lm, C, blank))
         return -1;
@@ -198,24 +252,31 @@ static int beam_decode_host(const char *who, const float *probs, int batch, int 
     if (!out_lengths || !scores || ((!probs || !labels_out) && T > 0)) return ctc_fail(who, "NULL array", 0, 0, 0);
     const size_t n = (size_t)batch * T * C, nh = (size_t)batch * nbest, nl = nh * T;
     float *d_p = nntk_devbuf_reserve(&t_a, n + 4);
-    int *d_o = (int *)nntk_devbuf_reserve(&t_b, nl + 2 * nh + 4);             /* labels | lengths | scores */
+    const int detail = label_frames || label_logps;
+    int *d_o = (int *)nntk_devbuf_reserve(&t_b, nl + 2 * nh + (detail ? 2 * nl : 0) + 4);   /* beam_download's packing */
     float *d_ws = nntk_devbuf_reserve(&t_c, nntk_shim_ctc_beam_workspace_floats(batch, T, C, beam_width, cutoff_top_n, lm != NULL));
     if (!d_p || !d_o || !d_ws) return -1;
     if (n && nntk_shim_upload(d_p, probs, n * sizeof(float))) return -1;
-    if (nntk_ctc_beam_decode_lm_device(d_p, batch, T, C, input_lengths, blank, beam_width, cutoff_top_n, nbest, lm, d_o, d_o + nl,
-                                       (float *)(d_o + nl + nh), d_ws)) return -1;
-    return beam_download(d_o, nl, nh, labels_out, out_lengths, scores);
+    const NntkCtcBeamOptions dev = { lm, label_frames ? d_o + nl + 2 * nh : NULL, label_logps ? (float *)(d_o + 2 * nl + 2 * nh) : NULL };
+    if (nntk_ctc_beam_decode_opt_device(d_p, batch, T, C, input_lengths, blank, beam_width, cutoff_top_n, nbest, &dev, d_o, d_o + nl,
+                                        (float *)(d_o + nl + nh), d_ws)) return -1;
+    return beam_download(d_o, nl, nh, labels_out, out_lengths, scores, label_frames, label_logps);
 }
 
 int nntk_ctc_beam_decode(const float *probs, int batch, int T, int C, const int *input_lengths, int blank, int beam_width,
                          int cutoff_top_n, int nbest, int *labels_out, int *out_lengths, float *scores) {
     return beam_decode_host("nntk_ctc_beam_decode", probs, batch, T, C, input_lengths, blank, beam_width, cutoff_top_n, nbest, NULL,
-                            labels_out, out_lengths, scores);
+                            labels_out, out_lengths, scores, NULL, NULL);
 }
 int nntk_ctc_beam_decode_lm(const float *probs, int batch, int T, int C, const int *input_lengths, int blank, int beam_width,
                             int cutoff_top_n, int nbest, NntkNgramLm lm, int *labels_out, int *out_lengths, float *scores) {
     return beam_decode_host("nntk_ctc_beam_decode_lm", probs, batch, T, C, input_lengths, blank, beam_width, cutoff_top_n, nbest, lm,
-                            labels_out, out_lengths, scores);
+                            labels_out, out_lengths, scores, NULL, NULL);
+}
+int nntk_ctc_beam_decode_opt(const float *probs, int batch, int T, int C, const int *input_lengths, int blank, int beam_width,
+                             int cutoff_top_n, int nbest, const NntkCtcBeamOptions *o, int *labels_out, int *out_lengths, float *scores) {
+    return beam_decode_host("nntk_ctc_beam_decode_opt", probs, batch, T, C, input_lengths, blank, beam_width, cutoff_top_n, nbest,
+                            o ? o->lm : NULL, labels_out, out_lengths, scores, o ? o->label_frames : NULL, o ? o->label_logps : NULL);
 }
 
 /* ---- streaming CTC decoding (INTEGRATION.md "CTC prefix beam search", Streaming).  The beam lives in the handle's device buffer; which
@@ -227,19 +288,25 @@ struct NntkCtcBeamStreamStruct {
     int *half;                      /* [batch] the current half of the row's label strings */
     int *ctl;                       /* [4][batch] staging of one push */
     NntkNgramLm lm;                 /* NULL: acoustic scores only.  Not owned: it outlives the stream */
+    int detail;                     /* the rows also carry their labels' frames and log-probabilities */
     nntk_devbuf d_buf;              /* nntk_shim_ctc_beam_stream_floats words, reserved by the first push */
     nntk_devbuf d_io;               /* the host-pointer push: probabilities | labels | lengths | scores */
 };
 
 size_t nntk_ctc_beam_stream_state_bytes(int batch, int max_frames, int C, int beam_width, int cutoff_top_n, int max_labels) {
-    return sizeof(float) * nntk_shim_ctc_beam_stream_floats(batch, max_frames, C, beam_width, cutoff_top_n, max_labels, 0);
+    return sizeof(float) * nntk_shim_ctc_beam_stream_floats(batch, max_frames, C, beam_width, cutoff_top_n, max_labels, 0, 0);
 }
 size_t nntk_ctc_beam_stream_state_bytes_lm(int batch, int max_frames, int C, int beam_width, int cutoff_top_n, int max_labels) {
-    return sizeof(float) * nntk_shim_ctc_beam_stream_floats(batch, max_frames, C, beam_width, cutoff_top_n, max_labels, 1);
+    return sizeof(float) * nntk_shim_ctc_beam_stream_floats(batch, max_frames, C, beam_width, cutoff_top_n, max_labels, 1, 0);
+}
+size_t nntk_ctc_beam_stream_state_bytes_opt(int batch, int max_frames, int C, int beam_width, int cutoff_top_n, int max_labels, int with_lm,
+                                            int with_detail) {
+    return sizeof(float) * nntk_shim_ctc_beam_stream_floats(batch, max_frames, C, beam_width, cutoff_top_n, max_labels, with_lm != 0,
+                                                            with_detail != 0);
 }
 
 static NntkCtcBeamStream beam_stream_create(int batch, int max_frames, int C, int blank, int beam_width, int cutoff_top_n, int nbest,
-                                            int max_labels, NntkNgramLm lm) {
+                                            int max_labels, NntkNgramLm lm, int detail) {
     static const char who[] = "nntk_ctc_beam_stream_create";
     nntk_shim_clear_error();
     if (ctc_beam_check(who, batch, 0, C, NULL, blank, beam_width, cutoff_top_n, nbest)) return NULL;
@@ -262,16 +329,21 @@ static NntkCtcBeamStream beam_stream_create(int batch, int max_frames, int C, in
     s->batch = batch; s->max_frames = max_frames; s->C = C; s->blank = blank;
     s->beam_width = beam_width; s->cutoff_top_n = cutoff_top_n; s->nbest = nbest; s->max_labels = max_labels;
     s->lm = lm;
+    s->detail = detail != 0;
     return s;
 }
 
 NntkCtcBeamStream nntk_ctc_beam_stream_create(int batch, int max_frames, int C, int blank, int beam_width, int cutoff_top_n, int nbest,
                                               int max_labels) {
-    return beam_stream_create(batch, max_frames, C, blank, beam_width, cutoff_top_n, nbest, max_labels, NULL);
+    return beam_stream_create(batch, max_frames, C, blank, beam_width, cutoff_top_n, nbest, max_labels, NULL, 0);
 }
 NntkCtcBeamStream nntk_ctc_beam_stream_create_lm(int batch, int max_frames, int C, int blank, int beam_width, int cutoff_top_n, int nbest,
                                                  int max_labels, NntkNgramLm lm) {
-    return beam_stream_create(batch, max_frames, C, blank, beam_width, cutoff_top_n, nbest, max_labels, lm);
+    return beam_stream_create(batch, max_frames, C, blank, beam_width, cutoff_top_n, nbest, max_labels, lm, 0);
+}
+NntkCtcBeamStream nntk_ctc_beam_stream_create_opt(int batch, int max_frames, int C, int blank, int beam_width, int cutoff_top_n, int nbest,
+                                                  int max_labels, NntkNgramLm lm, int with_detail) {
+    return beam_stream_create(batch, max_frames, C, blank, beam_width, cutoff_top_n, nbest, max_labels, lm, with_detail);
 }
 
 void nntk_ctc_beam_stream_destroy(NntkCtcBeamStream s) {
@@ -309,18 +381,35 @@ static int beam_stream_check_push(const char *who, NntkCtcBeamStream s, const vo
     return 0;
 }
 
-int nntk_ctc_beam_stream_push_device(NntkCtcBeamStream s, const float *d_probs, const int *n_frames, const int *final,
-                                     int *d_labels_out, int *d_out_lengths, float *d_scores) {
-    static const char who[] = "nntk_ctc_beam_stream_push_device";
+/* which push a handle takes: one created with detail only the _opt pushes (opt), one created without it no detail pointer */
+static int beam_stream_check_detail(const char *who, NntkCtcBeamStream s, int opt, const void *frames, const void *logps) {
+    if (s->detail && !opt)
+        return ctc_fail(who, "the stream was created with detail: push it through the _opt call", 0, 0, 0);
+    if (!s->detail && (frames || logps))
+        return ctc_fail(who, "the stream was created without detail: it holds no label frames or log-probabilities", 0, 0, 0);
+    return 0;
+}
+
+static int beam_stream_push_device(const char *who, int opt, NntkCtcBeamStream s, const float *d_probs, const int *n_frames,
+                                   const int *final, int *d_labels_out, int *d_out_lengths, float *d_scores, int *d_label_frames,
+                                   float *d_label_logps) {
     nntk_shim_clear_error();
-    if (!s) NNTK_FAIL("nntk_ctc_beam_stream_push_device: NULL handle");
+    if (!s) return ctc_fail(who, "NULL handle", 0, 0, 0);
     if (s->batch == 0) return 0;
-    if (beam_stream_check_push(who, s, d_probs, n_frames, d_labels_out, d_out_lengths, d_scores)) return -1;
+    if (beam_stream_check_push(who, s, d_probs, n_frames, d_labels_out, d_out_lengths, d_scores) ||
+        beam_stream_check_detail(who, s, opt, d_label_frames, d_label_logps)) return -1;
+    if (d_label_frames || d_label_logps) {
+        const size_t nh = (size_t)s->batch * s->nbest, nl = nh * s->max_labels;
+        const beam_span other[4] = {
+            { d_labels_out, nl * sizeof(int), "d_labels_out" }, { d_out_lengths, nh * sizeof(int), "d_out_lengths" },
+            { d_scores, nh * sizeof(float), "d_scores" }, { d_probs, (size_t)s->batch * s->max_frames * s->C * sizeof(float), "d_probs" } };
+        if (beam_detail_check(who, d_label_frames, d_label_logps, nl, other, 4)) return -1;
+    }
     const int B = s->batch;
     nntk_shim_lm tab;
     if (s->lm && nntk_ngram_lm_device(s->lm, &tab)) return -1;
     float *d_buf = nntk_devbuf_reserve(&s->d_buf, nntk_shim_ctc_beam_stream_floats(B, s->max_frames, s->C, s->beam_width, s->cutoff_top_n,
-                                                                                   s->max_labels, s->lm != NULL));
+                                                                                   s->max_labels, s->lm != NULL, s->detail));
     if (!d_buf) return -1;
     int any = 0;
     for (int b = 0; b < B; ++b) {
@@ -331,7 +420,8 @@ int nntk_ctc_beam_stream_push_device(NntkCtcBeamStream s, const float *d_probs, 
         any |= n_frames[b] > 0;
     }
     if (nntk_shim_ctc_beam_stream_push(d_probs, B, s->max_frames, s->C, s->ctl, any, s->blank, s->beam_width, s->cutoff_top_n, s->nbest,
-                                       s->max_labels, s->lm ? &tab : NULL, d_labels_out, d_out_lengths, d_scores, d_buf)) return -1;
+                                       s->max_labels, s->lm ? &tab : NULL, s->detail, d_labels_out, d_out_lengths, d_scores, d_label_frames,
+                                       d_label_logps, d_buf)) return -1;
     for (int b = 0; b < B; ++b) {
         if (n_frames[b] > 0) { s->frames[b] += n_frames[b]; s->half[b] ^= 1; }
         if (final && final[b]) s->frames[b] = 0;
@@ -339,20 +429,43 @@ int nntk_ctc_beam_stream_push_device(NntkCtcBeamStream s, const float *d_probs, 
     return 0;
 }
 
-int nntk_ctc_beam_stream_push(NntkCtcBeamStream s, const float *probs, const int *n_frames, const int *final, int *labels_out,
-                              int *out_lengths, float *scores) {
-    static const char who[] = "nntk_ctc_beam_stream_push";
+int nntk_ctc_beam_stream_push_device(NntkCtcBeamStream s, const float *d_probs, const int *n_frames, const int *final,
+                                     int *d_labels_out, int *d_out_lengths, float *d_scores) {
+    return beam_stream_push_device("nntk_ctc_beam_stream_push_device", 0, s, d_probs, n_frames, final, d_labels_out, d_out_lengths,
+                                   d_scores, NULL, NULL);
+}
+int nntk_ctc_beam_stream_push_opt_device(NntkCtcBeamStream s, const float *d_probs, const int *n_frames, const int *final,
+                                         int *d_labels_out, int *d_out_lengths, float *d_scores, int *d_label_frames,
+                                         float *d_label_logps) {
+    return beam_stream_push_device("nntk_ctc_beam_stream_push_opt_device", 1, s, d_probs, n_frames, final, d_labels_out, d_out_lengths,
+                                   d_scores, d_label_frames, d_label_logps);
+}
+
+static int beam_stream_push_host(const char *who, int opt, NntkCtcBeamStream s, const float *probs, const int *n_frames, const int *final,
+                                 int *labels_out, int *out_lengths, float *scores, int *label_frames, float *label_logps) {
     nntk_shim_clear_error();
-    if (!s) NNTK_FAIL("nntk_ctc_beam_stream_push: NULL handle");
+    if (!s) return ctc_fail(who, "NULL handle", 0, 0, 0);
     if (s->batch == 0) return 0;
-    if (beam_stream_check_push(who, s, probs, n_frames, labels_out, out_lengths, scores)) return -1;
+    if (beam_stream_check_push(who, s, probs, n_frames, labels_out, out_lengths, scores) ||
+        beam_stream_check_detail(who, s, opt, label_frames, label_logps)) return -1;
     const size_t n = (size_t)s->batch * s->max_frames * s->C, nh = (size_t)s->batch * s->nbest, nl = nh * s->max_labels;
-    float *d_p = nntk_devbuf_reserve(&s->d_io, n + nl + 2 * nh + 4);
+    float *d_p = nntk_devbuf_reserve(&s->d_io, n + nl + 2 * nh + (s->detail ? 2 * nl : 0) + 4);
     if (!d_p) return -1;
     int *d_o = (int *)(d_p + n);
     if (nntk_shim_upload(d_p, probs, n * sizeof(float))) return -1;
-    if (nntk_ctc_beam_stream_push_device(s, d_p, n_frames, final, d_o, d_o + nl, (float *)(d_o + nl + nh))) return -1;
-    return beam_download(d_o, nl, nh, labels_out, out_lengths, scores);
+    if (beam_stream_push_device(who, opt, s, d_p, n_frames, final, d_o, d_o + nl, (float *)(d_o + nl + nh),
+                                label_frames ? d_o + nl + 2 * nh : NULL, label_logps ? (float *)(d_o + 2 * nl + 2 * nh) : NULL)) return -1;
+    return beam_download(d_o, nl, nh, labels_out, out_lengths, scores, label_frames, label_logps);
+}
+
+int nntk_ctc_beam_stream_push(NntkCtcBeamStream s, const float *probs, const int *n_frames, const int *final, int *labels_out,
+                              int *out_lengths, float *scores) {
+    return beam_stream_push_host("nntk_ctc_beam_stream_push", 0, s, probs, n_frames, final, labels_out, out_lengths, scores, NULL, NULL);
+}
+int nntk_ctc_beam_stream_push_opt(NntkCtcBeamStream s, const float *probs, const int *n_frames, const int *final, int *labels_out,
+                                  int *out_lengths, float *scores, int *label_frames, float *label_logps) {
+    return beam_stream_push_host("nntk_ctc_beam_stream_push_opt", 1, s, probs, n_frames, final, labels_out, out_lengths, scores,
+                                 label_frames, label_logps);
 }
 
 int nntk_ctc_greedy_decode_stream_device(const float *d_probs, int batch, int T, int C, const int *n_frames, int blank, int *d_prev,

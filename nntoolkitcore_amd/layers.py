@@ -653,9 +653,21 @@ def _beam_outputs(device, B, nbest, L, labels_out, out_lengths, scores):
     return labels_out, out_lengths, scores
 
 
+def _beam_detail_outputs(device, B, nbest, L):
+    """new label_frames int32 / label_logps float32 tensors [B, nbest, L] of a search with detail"""
+    import torch
+    return (torch.empty((B, nbest, L), dtype=torch.int32, device=device), torch.empty((B, nbest, L), dtype=torch.float32, device=device))
+
+
+def _ctc_beam_opts(lm, frames=None, logps=None):
+    """NntkCtcBeamOptions by reference; frames, logps: addresses or None"""
+    return C.byref(capi.NntkCtcBeamOptions(lm.h if lm is not None else None, frames, logps))
+
+
 def _beam_decode_device(entry, ws_name, lm_arg, probs, input_lengths, blank, beam_width, cutoff_top_n, nbest, labels_out, out_lengths, scores,
-                        workspace):
-    """the one-shot search on device tensors through the C entry ``entry``; lm_arg: () for the acoustic entries, else (model handle or None,)"""
+                        workspace, detail=False):
+    """the one-shot search on device tensors through the C entry ``entry``; lm_arg: () for the acoustic entries, else (model handle or
+    None,).  detail: through ``nntk_ctc_beam_decode_opt_device`` instead, lm_arg = (the NgramLm or None,) -> the three and (frames, logps)"""
     import torch
     B, T, Cc = probs.shape
     il, ilp = _ctc_lengths(input_lengths, B)
@@ -665,33 +677,53 @@ def _beam_decode_device(entry, ws_name, lm_arg, probs, input_lengths, blank, bea
         workspace = torch.empty(need, dtype=torch.float32, device=probs.device)
     assert workspace.numel() >= need, "workspace: %s(B, T, C, beam_width, cutoff_top_n) floats" % ws_name
     labels_out, out_lengths, scores = _beam_outputs(probs.device, B, max(nbest, 0), T, labels_out, out_lengths, scores)
+    if detail:
+        frames, logps = _beam_detail_outputs(probs.device, B, max(nbest, 0), T)
+        check(L.nntk_ctc_beam_decode_opt_device(_dp(probs), B, T, Cc, ilp, blank, beam_width, cutoff_top_n, nbest,
+                                                _ctc_beam_opts(lm_arg[0], frames.data_ptr(), logps.data_ptr()),
+                                                C.c_void_p(labels_out.data_ptr()), C.c_void_p(out_lengths.data_ptr()), _dp(scores),
+                                                _dp(workspace)), "nntk_ctc_beam_decode_opt_device")
+        return labels_out, out_lengths, scores, frames, logps
     check(getattr(L, entry)(_dp(probs), B, T, Cc, ilp, blank, beam_width, cutoff_top_n, nbest, *lm_arg, C.c_void_p(labels_out.data_ptr()),
                             C.c_void_p(out_lengths.data_ptr()), _dp(scores), _dp(workspace)), entry)
     return labels_out, out_lengths, scores
 
 
-def _beam_decode_host(entry, lm_arg, probs, input_lengths, blank, beam_width, cutoff_top_n, nbest):
-    """the host-memory form of the same; lm_arg as above"""
+def _beam_decode_host(entry, lm_arg, probs, input_lengths, blank, beam_width, cutoff_top_n, nbest, detail=False):
+    """the host-memory form of the same; lm_arg and detail as above (``nntk_ctc_beam_decode_opt``)"""
     probs = _f32(probs)
     B, T, Cc = probs.shape
     il, ilp = _ctc_lengths(input_lengths, B)
     nb = max(nbest, 0)
     out, n, sc = np.empty((B, nb, T), np.int32), np.empty((B, nb), np.int32), np.empty((B, nb), np.float32)
+    if detail:
+        fr, lg = np.empty((B, nb, T), np.int32), np.empty((B, nb, T), np.float32)
+        check(capi.load().nntk_ctc_beam_decode_opt(_p(probs), B, T, Cc, ilp, blank, beam_width, cutoff_top_n, nbest,
+                                                   _ctc_beam_opts(lm_arg[0], fr.ctypes.data, lg.ctypes.data), out.ctypes.data_as(capi.ip),
+                                                   n.ctypes.data_as(capi.ip), _p(sc)), "nntk_ctc_beam_decode_opt")
+        return out, n, sc, fr, lg
     check(getattr(capi.load(), entry)(_p(probs), B, T, Cc, ilp, blank, beam_width, cutoff_top_n, nbest, *lm_arg, out.ctypes.data_as(capi.ip),
                                       n.ctypes.data_as(capi.ip), _p(sc)), entry)
     return out, n, sc
 
 
 def ctc_beam_decode_device(probs, input_lengths=None, blank=0, beam_width=16, cutoff_top_n=0, nbest=1, labels_out=None, out_lengths=None,
-                           scores=None, workspace=None):
+                           scores=None, workspace=None, detail=False):
     """``nntk_ctc_beam_decode_device``: prefix beam search over probs [B,T,C] -> (labels [B,nbest,T] int32, -1 behind each hypothesis'
-    labels; lengths [B,nbest] int32, -1 for a slot without a hypothesis; scores [B,nbest] float32 = ln of the prefix probability)"""
+    labels; lengths [B,nbest] int32, -1 for a slot without a hypothesis; scores [B,nbest] float32 = ln of the prefix probability).
+    ``detail=True`` (``nntk_ctc_beam_decode_opt_device``): the same three and (label_frames [B,nbest,T] int32, -1 behind the labels';
+    label_logps [B,nbest,T] float32, 0.0 behind them) -- INTEGRATION.md "Label timestamps and confidences"."""
+    if detail:
+        return _beam_decode_device(None, "nntk_ctc_beam_workspace_floats", (None,), probs, input_lengths, blank, beam_width, cutoff_top_n,
+                                   nbest, labels_out, out_lengths, scores, workspace, True)
     return _beam_decode_device("nntk_ctc_beam_decode_device", "nntk_ctc_beam_workspace_floats", (), probs, input_lengths, blank, beam_width,
                                cutoff_top_n, nbest, labels_out, out_lengths, scores, workspace)
 
 
-def ctc_beam_decode(probs, input_lengths=None, blank=0, beam_width=16, cutoff_top_n=0, nbest=1):
-    """The host-memory form (``nntk_ctc_beam_decode``): probs [B,T,C] numpy array."""
+def ctc_beam_decode(probs, input_lengths=None, blank=0, beam_width=16, cutoff_top_n=0, nbest=1, detail=False):
+    """The host-memory form (``nntk_ctc_beam_decode``, with detail ``nntk_ctc_beam_decode_opt``): probs [B,T,C] numpy array."""
+    if detail:
+        return _beam_decode_host(None, (None,), probs, input_lengths, blank, beam_width, cutoff_top_n, nbest, True)
     return _beam_decode_host("nntk_ctc_beam_decode", (), probs, input_lengths, blank, beam_width, cutoff_top_n, nbest)
 
 
@@ -814,15 +846,21 @@ class NgramLm:
 
 
 def ctc_beam_decode_lm_device(probs, lm, input_lengths=None, blank=0, beam_width=16, cutoff_top_n=0, nbest=1, labels_out=None,
-                              out_lengths=None, scores=None, workspace=None):
+                              out_lengths=None, scores=None, workspace=None, detail=False):
     """``nntk_ctc_beam_decode_lm_device``: ``ctc_beam_decode_device`` with the n-gram model ``lm`` (an NgramLm, or None) fused in;
-    scores = ln(acoustic prefix probability x LM factors x end-of-sentence factor)"""
+    scores = ln(acoustic prefix probability x LM factors x end-of-sentence factor).  ``detail=True``: as in ``ctc_beam_decode_device``
+    (label_logps stays the acoustic log-probability, never the model's factor)."""
+    if detail:
+        return _beam_decode_device(None, "nntk_ctc_beam_lm_workspace_floats", (lm,), probs, input_lengths, blank, beam_width, cutoff_top_n,
+                                   nbest, labels_out, out_lengths, scores, workspace, True)
     return _beam_decode_device("nntk_ctc_beam_decode_lm_device", "nntk_ctc_beam_lm_workspace_floats", (lm.h if lm else None,), probs,
                                input_lengths, blank, beam_width, cutoff_top_n, nbest, labels_out, out_lengths, scores, workspace)
 
 
-def ctc_beam_decode_lm(probs, lm, input_lengths=None, blank=0, beam_width=16, cutoff_top_n=0, nbest=1):
-    """The host-memory form (``nntk_ctc_beam_decode_lm``): probs [B,T,C] numpy array."""
+def ctc_beam_decode_lm(probs, lm, input_lengths=None, blank=0, beam_width=16, cutoff_top_n=0, nbest=1, detail=False):
+    """The host-memory form (``nntk_ctc_beam_decode_lm``, with detail ``nntk_ctc_beam_decode_opt``): probs [B,T,C] numpy array."""
+    if detail:
+        return _beam_decode_host(None, (lm,), probs, input_lengths, blank, beam_width, cutoff_top_n, nbest, True)
     return _beam_decode_host("nntk_ctc_beam_decode_lm", (lm.h if lm else None,), probs, input_lengths, blank, beam_width, cutoff_top_n, nbest)
 
 
@@ -830,13 +868,19 @@ class CtcBeamStream:
     """``nntk_ctc_beam_stream_*``: prefix beam search pushed chunk by chunk for ``batch`` independent streams.  After every push row
     b holds what ``ctc_beam_decode_device`` gives on the row's frames since its last reset, bit for bit (INTEGRATION.md "CTC prefix
     beam search", Streaming).  ``max_labels``: the capacity of the returned label strings (default: max_frames).  ``lm``: an NgramLm
-    fused in as by ``ctc_beam_decode_lm_device``; it must outlive the stream."""
+    fused in as by ``ctc_beam_decode_lm_device``; it must outlive the stream.  ``detail=True`` (``nntk_ctc_beam_stream_create_opt``):
+    the rows also carry their labels' frames (counted from the row's last reset) and log-probabilities, and ``push`` / ``push_host``
+    return (labels, lengths, scores, label_frames, label_logps), the last two [B, nbest, max_labels]."""
 
-    def __init__(self, batch, max_frames, C, blank=0, beam_width=16, cutoff_top_n=0, nbest=1, max_labels=None, lm=None):
+    def __init__(self, batch, max_frames, C, blank=0, beam_width=16, cutoff_top_n=0, nbest=1, max_labels=None, lm=None, detail=False):
         self.B, self.T, self.C, self.nbest = int(batch), int(max_frames), int(C), int(nbest)
         self.max_labels = int(max_frames if max_labels is None else max_labels)
         self.lm = lm
-        if lm is None:
+        self.detail = bool(detail)
+        if self.detail:
+            self.h = capi.load().nntk_ctc_beam_stream_create_opt(self.B, self.T, self.C, blank, beam_width, cutoff_top_n, nbest,
+                                                                 self.max_labels, lm.h if lm is not None else None, 1)
+        elif lm is None:
             self.h = capi.load().nntk_ctc_beam_stream_create(self.B, self.T, self.C, blank, beam_width, cutoff_top_n, nbest, self.max_labels)
         else:
             self.h = capi.load().nntk_ctc_beam_stream_create_lm(self.B, self.T, self.C, blank, beam_width, cutoff_top_n, nbest,
@@ -857,6 +901,13 @@ class CtcBeamStream:
         nf = _host_ints(n_frames, self.B, "n_frames")
         f, fptr = self._final(final)
         labels_out, out_lengths, scores = _beam_outputs(probs.device, self.B, self.nbest, self.max_labels, labels_out, out_lengths, scores)
+        if self.detail:
+            frames, logps = _beam_detail_outputs(probs.device, self.B, self.nbest, self.max_labels)
+            check(capi.load().nntk_ctc_beam_stream_push_opt_device(self.h, _dp(probs), nf.ctypes.data_as(capi.ip), fptr,
+                                                                   C.c_void_p(labels_out.data_ptr()), C.c_void_p(out_lengths.data_ptr()),
+                                                                   _dp(scores), C.c_void_p(frames.data_ptr()), _dp(logps)),
+                  "nntk_ctc_beam_stream_push_opt_device")
+            return labels_out, out_lengths, scores, frames, logps
         check(capi.load().nntk_ctc_beam_stream_push_device(self.h, _dp(probs), nf.ctypes.data_as(capi.ip), fptr,
                                                            C.c_void_p(labels_out.data_ptr()), C.c_void_p(out_lengths.data_ptr()),
                                                            _dp(scores)), "nntk_ctc_beam_stream_push_device")
@@ -870,6 +921,12 @@ class CtcBeamStream:
         f, fptr = self._final(final)
         out = np.empty((self.B, self.nbest, self.max_labels), np.int32)
         n, sc = np.empty((self.B, self.nbest), np.int32), np.empty((self.B, self.nbest), np.float32)
+        if self.detail:
+            fr, lg = np.empty(out.shape, np.int32), np.empty(out.shape, np.float32)
+            check(capi.load().nntk_ctc_beam_stream_push_opt(self.h, _p(probs), nf.ctypes.data_as(capi.ip), fptr, out.ctypes.data_as(capi.ip),
+                                                            n.ctypes.data_as(capi.ip), _p(sc), fr.ctypes.data_as(capi.ip), _p(lg)),
+                  "nntk_ctc_beam_stream_push_opt")
+            return out, n, sc, fr, lg
         check(capi.load().nntk_ctc_beam_stream_push(self.h, _p(probs), nf.ctypes.data_as(capi.ip), fptr, out.ctypes.data_as(capi.ip),
                                                     n.ctypes.data_as(capi.ip), _p(sc)), "nntk_ctc_beam_stream_push")
         return out, n, sc
