@@ -7,16 +7,15 @@ checks in the same run that both give identical outputs:
 Each shape runs with every length T and with ragged lengths (uniform in [T/2, T]).
 usage: python tools/bd_time.py [--rounds N] [--batches 64,256,...] cell:in:H:T ...
 default: gru:128:256:1000 gru:256:256:1000 lstm:128:512:996 at B = 64, 256, 512, 1024"""
-import os, sys
+import sys
 import numpy as np
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import torch
+from timing import open_device, timed
+from nntoolkitcore_amd import capi, layers as NL
 
 
 def main():
-    import torch
-    from nntoolkitcore_amd import capi, layers as NL
-    torch.cuda.set_device(0); L = capi.load(); NL.use_torch_stream()
+    L = open_device()
     rounds, batches = 7, [64, 256, 512, 1024]
     args = sys.argv[1:]
     while args and args[0].startswith("--"):
@@ -69,9 +68,7 @@ def main():
                 ts = {name: [] for name in variants}
                 for _ in range(rounds):
                     for name, fn in variants.items():
-                        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                        e0.record(); fn(); e1.record(); torch.cuda.synchronize()
-                        ts[name].append(e0.elapsed_time(e1))
+                        ts[name].append(timed(fn, 1, warmup=0).median)
                 a = np.median(ts["a composed"])
                 print("%s B=%d %s  identical outputs: %s" % (spec, B, "all T" if lens is None else "ragged (mean %.3f T)" % (lens.mean() / T),
                                                             same))

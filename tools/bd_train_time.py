@@ -17,9 +17,9 @@ import sys
 import tempfile
 
 import numpy as np
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import torch
+from timing import open_device, timed
+from nntoolkitcore_amd import capi, layers as NL
 
 
 NEW_KERNELS = ("bd_merge_kernel", "bd_scatter_kernel", "bd_accumulate_kernel")
@@ -61,9 +61,7 @@ def main():
         else:
             spec, args = args[0], args[1:]
     trace = kernel_trace(spec, 10) if share and not pair_only else None
-    import torch
-    from nntoolkitcore_amd import capi, layers as NL
-    torch.cuda.set_device(0); L = capi.load(); NL.use_torch_stream()
+    L = open_device()
     f = spec.split(":")
     kind, I, H, T, B = f[0], int(f[1]), int(f[2]), int(f[3]), int(f[4])
     G = {"lstm": 4, "gru": 3, "rnn": 1}[kind]
@@ -115,14 +113,6 @@ def main():
         print("ran the pair %d times" % pair_only)
         return 0
 
-    def timed(fn, n):
-        ts = []
-        for _ in range(n):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record(); fn(); e1.record(); torch.cuda.synchronize()
-            ts.append(e0.elapsed_time(e1))
-        return np.array(ts)
-
     variants = {"a composed": composed, "b one call per pass": one_call}
     for fn in variants.values():
         for _ in range(3):
@@ -132,7 +122,7 @@ def main():
     ts = {name: [] for name in variants}
     for _ in range(rounds):
         for name, fn in variants.items():
-            ts[name] += list(timed(fn, 1))
+            ts[name].append(timed(fn, 1, warmup=0).median)
     print("%s B=%d, lengths all T, forward + gradient; identical output / d_X / gradient blocks: %s" % (spec, B, same))
     base = np.median(ts["a composed"])
     for name in variants:

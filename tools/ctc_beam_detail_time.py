@@ -7,41 +7,25 @@ cutoff_top_n 40; nbest = 4.  The detail call next to the plain call of the same 
 probability per reported label, two more [B][nbest][T] outputs written in full).  Stream: the shape of tools/ctc_beam_stream_time.py
 (B 64, C 29, beam_width 16, nbest 1, max_labels 512, chunks of 10 and 50 frames), one push in the stream's later three quarters, with
 and without detail (16 * max_labels more bytes of state per row and entry, half of them copied per push).
---parent LIB: the plain one-shot calls of this library next to those of another build (the parent commit's), alternating, twice
-each, every measurement in a fresh process that binds only what both libraries have; the spread of each library's two medians is its
-run-to-run spread.  HIP events, warm-up, median of the repeats (default 7)."""
+--parent LIB: the plain one-shot calls of this library next to those of another build (the parent commit's), by the A/B protocol of
+tools/timing.py; a child binds only what both libraries have.  Timing as in tools/timing.py, repeats default 7."""
 import ctypes as C
-import json, os, subprocess, sys
+import json, os, sys
 import numpy as np
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
+from timing import ab_children, ab_figures, emit, open_device, ragged, timed, timed_marks
 
 ONE_SHOT = ((512, 250, 40, 16, 0), (512, 250, 40, 64, 0), (512, 1000, 1000, 64, 40))     # B, T, C, beam_width, cutoff_top_n
 NBEST = 4
 SB, ST, SC, SW, SNBEST, SMAX_LABELS = 64, 1000, 29, 16, 1, 512
 CHUNKS = (10, 50)
 WARMUP = 2
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def timed(fn, repeats):
-    for _ in range(WARMUP):
-        fn()
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(repeats):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record(); fn(); b.record(); b.synchronize()
-        ms.append(a.elapsed_time(b))
-    return {"median": float(np.median(ms)), "min": float(min(ms)), "max": float(max(ms))}
 
 
 def inputs(B, T, Cc):
     g = torch.Generator(device="cuda").manual_seed(B + T + Cc)
     probs = torch.softmax(4 * torch.rand((B, T, Cc), device="cuda", generator=g) - 2, -1)
-    il = np.random.default_rng(T).integers(T // 2, T + 1, B).astype(np.int32)
-    il[0] = T
-    return probs, il
+    return probs, ragged(np.random.default_rng(T), T, B)
 
 
 def plain_only(lib_path, repeats):
@@ -63,17 +47,11 @@ def plain_only(lib_path, repeats):
             rc = lib.nntk_ctc_beam_decode_device(probs.data_ptr(), B, T, Cc, il.ctypes.data, 0, W, cut, NBEST, lab.data_ptr(), n.data_ptr(),
                                                  sc.data_ptr(), ws.data_ptr())
             assert rc == 0
-        out.append(timed(call, repeats))
+        out.append(timed(call, repeats, WARMUP).dict)
         assert torch.isfinite(sc[:, 0]).all()
         del probs, ws
         torch.cuda.empty_cache()
     print(json.dumps(out))
-
-
-def child(lib_path, repeats):
-    res = subprocess.run([sys.executable, os.path.abspath(__file__), "--plain-only", lib_path, str(repeats)], stdout=subprocess.PIPE,
-                         text=True, timeout=300, check=True)
-    return json.loads(res.stdout.strip().splitlines()[-1])
 
 
 def main():
@@ -86,24 +64,13 @@ def main():
     repeats = int(args[0]) if args else 7
     out = {"tool": "ctc_beam_detail_time", "repeats": repeats, "warmup": WARMUP, "nbest": NBEST}
     if parent:
-        # children first, before this process opens the device; this, parent, this, parent
-        from nntoolkitcore_amd import capi
-        runs = {"this": [], "parent": []}
-        for _ in range(2):
-            runs["this"].append(child(capi.LIB_PATH, repeats))
-            runs["parent"].append(child(parent, repeats))
-        ab = []
-        for i, (B, T, Cc, W, cut) in enumerate(ONE_SHOT):
-            med = {k: [r[i]["median"] for r in v] for k, v in runs.items()}
-            mean = {k: float(np.mean(v)) for k, v in med.items()}
-            ab.append({"B": B, "T": T, "C": Cc, "beam_width": W, "cutoff_top_n": cut, "this_ms": med["this"], "parent_ms": med["parent"],
-                       "this_spread": abs(med["this"][0] - med["this"][1]) / mean["this"],
-                       "parent_spread": abs(med["parent"][0] - med["parent"][1]) / mean["parent"],
-                       "this_over_parent": mean["this"] / mean["parent"]})
-        out["plain_vs_parent"] = ab
-    assert torch.cuda.is_available(), "needs the GPU"
-    from nntoolkitcore_amd import capi, layers as NL
-    torch.cuda.set_device(0); L = capi.load(); NL.use_torch_stream()
+        from nntoolkitcore_amd import capi                # the children run before this process opens the device
+        runs = ab_children(__file__, "--plain-only", capi.LIB_PATH, parent, repeats)
+        out["plain_vs_parent"] = [{"B": B, "T": T, "C": Cc, "beam_width": W, "cutoff_top_n": cut,
+                                   **ab_figures(*([r[i]["median"] for r in runs[k]] for k in ("this", "parent")))}
+                                  for i, (B, T, Cc, W, cut) in enumerate(ONE_SHOT)]
+    L = open_device()
+    from nntoolkitcore_amd import layers as NL
     out["source_hash"] = L.nntk_build_source_hash().decode()
     out["one_shot"] = []
     for B, T, Cc, W, cut in ONE_SHOT:
@@ -113,10 +80,10 @@ def main():
         n = torch.empty((B, NBEST), dtype=torch.int32, device="cuda")
         sc = torch.empty((B, NBEST), device="cuda")
         plain = timed(lambda: NL.ctc_beam_decode_device(probs, il, 0, W, cut, NBEST, labels_out=lab, out_lengths=n, scores=sc, workspace=ws),
-                      repeats)
+                      repeats, WARMUP).dict
         bits = (lab.cpu().numpy().tobytes(), n.cpu().numpy().tobytes(), sc.cpu().numpy().tobytes())
         detail = timed(lambda: NL.ctc_beam_decode_device(probs, il, 0, W, cut, NBEST, labels_out=lab, out_lengths=n, scores=sc, workspace=ws,
-                                                         detail=True), repeats)
+                                                         detail=True), repeats, WARMUP).dict
         fr = NL.ctc_beam_decode_device(probs, il, 0, W, cut, NBEST, labels_out=lab, out_lengths=n, scores=sc, workspace=ws, detail=True)[3]
         assert bits == (lab.cpu().numpy().tobytes(), n.cpu().numpy().tobytes(), sc.cpu().numpy().tobytes())
         labels = int((fr >= 0).sum())
@@ -128,7 +95,7 @@ def main():
 
     probs, _ = inputs(SB, ST, SC)
     out["stream"] = {"B": SB, "T": ST, "C": SC, "beam_width": SW, "nbest": SNBEST, "max_labels": SMAX_LABELS, "chunks": []}
-    rows, ev = np.arange(SB, dtype=np.int32), lambda: torch.cuda.Event(enable_timing=True)
+    rows = np.arange(SB, dtype=np.int32)
     for mf in CHUNKS:
         blocks = [probs[:, t:t + mf].contiguous() for t in range(0, ST, mf)]
         nf = np.full(SB, mf, np.int32)
@@ -136,7 +103,7 @@ def main():
         for detail in (False, True):
             dec = NL.CtcBeamStream(SB, mf, SC, 0, SW, 0, SNBEST, max_labels=SMAX_LABELS, detail=detail)
 
-            def stream(events=None):
+            def stream(events):
                 dec.reset(rows)
                 for i, x in enumerate(blocks):
                     if events is not None:
@@ -144,27 +111,14 @@ def main():
                     dec.push(x, nf)
                     if events is not None:
                         events[i][1].record()
-            for _ in range(WARMUP):
-                stream()
-            torch.cuda.synchronize()
-            per_push = []
-            for _ in range(repeats):
-                events = [(ev(), ev()) for _ in blocks]
-                stream(events)
-                torch.cuda.synchronize()
-                per_push.extend(s.elapsed_time(e) for s, e in events[len(blocks) // 4:])
             key = "detail" if detail else "plain"
-            row[key + "_push_ms"] = {"median": float(np.median(per_push)), "min": float(min(per_push)), "max": float(max(per_push))}
+            row[key + "_push_ms"] = timed_marks(stream, len(blocks), repeats, len(blocks) // 4, WARMUP).dict
             row[key + "_state_bytes"] = int(L.nntk_ctc_beam_stream_state_bytes_opt(SB, mf, SC, SW, 0, SMAX_LABELS, 0, int(detail)))
             dec.close()
         row["detail_over_plain"] = row["detail_push_ms"]["median"] / row["plain_push_ms"]["median"]
         row["detail_string_bytes_per_push_at_most"] = 2 * 8 * SB * SW * SMAX_LABELS      # read one half, write the other
         out["stream"]["chunks"].append(row)
-    line = json.dumps(out)
-    os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
-    with open(os.path.join(ROOT, "profiles", "ctc_beam_detail_time.json"), "w") as fh:
-        fh.write(line + "\n")
-    print(line)
+    emit(out, "ctc_beam_detail_time")
 
 
 if __name__ == "__main__":

@@ -3,31 +3,18 @@
 python tools/ctc_beam_lm_time.py [repeats]      -> one JSON line, also written to profiles/ctc_beam_lm_time.json
 One decoding-sized shape, B = 64, T = 500, C = 64, beam_width 32, no class cut, nbest 4; three calls on the same posteriors:
 nntk_ctc_beam_decode_lm_device with a sparse random trigram of about 50 k arcs, the same call with the unit model (alpha = beta = 0: the
-same walks, every factor one), and nntk_ctc_beam_decode_device.  HIP events, warm-up, median of the repeats.
+same walks, every factor one), and nntk_ctc_beam_decode_device.  Timed by tools/timing.py.
 probes_per_frame: the 16-byte arc records a row's frame reads in its binary searches -- beam_width * (C - 1) extend cells plus
 beam_width re-lookups, each the mean over the table's two-label states and all classes of the probes of one walk (a binary search
 over k arcs costs floor(log2 k) + 1 probes on a miss)."""
-import json, os, sys
+import sys
 import numpy as np
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
-from nntoolkitcore_amd import capi, layers as NL
+from timing import emit, open_device, timed
+from nntoolkitcore_amd import layers as NL
 
 B, T, CC, W, NBEST, BLANK = 64, 500, 64, 32, 4, 0
 WARMUP = 2
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def timed(fn, repeats):
-    for _ in range(WARMUP):
-        fn()
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(repeats):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record(); fn(); b.record(); b.synchronize()
-        ms.append(a.elapsed_time(b))
-    return float(np.median(ms)), float(min(ms)), float(max(ms))
 
 
 def trigram(seed, per_state):
@@ -68,8 +55,7 @@ def probes_per_walk(per_state):
 
 def main():
     repeats = int(sys.argv[1]) if len(sys.argv) > 1 else 5
-    assert torch.cuda.is_available(), "needs the GPU"
-    torch.cuda.set_device(0); L = capi.load(); NL.use_torch_stream()
+    L = open_device()
     per_state = 12
     t = trigram(1, per_state)
     g = torch.Generator(device="cuda").manual_seed(B + T + CC)
@@ -82,11 +68,11 @@ def main():
     kw = dict(labels_out=lab, out_lengths=n, scores=sc, workspace=ws)
     lm = NL.NgramLm.from_arrays(alpha=0.5, beta=0.25, **t)
     unit = NL.NgramLm.from_arrays(alpha=0.0, beta=0.0, **t)
-    t_lm = timed(lambda: NL.ctc_beam_decode_lm_device(probs, lm, il, BLANK, W, 0, NBEST, **kw), repeats)
+    t_lm = timed(lambda: NL.ctc_beam_decode_lm_device(probs, lm, il, BLANK, W, 0, NBEST, **kw), repeats, WARMUP)
     assert torch.isfinite(sc[:, 0]).all()
-    t_unit = timed(lambda: NL.ctc_beam_decode_lm_device(probs, unit, il, BLANK, W, 0, NBEST, **kw), repeats)
+    t_unit = timed(lambda: NL.ctc_beam_decode_lm_device(probs, unit, il, BLANK, W, 0, NBEST, **kw), repeats, WARMUP)
     unit_sc = sc.clone()
-    t_ac = timed(lambda: NL.ctc_beam_decode_device(probs, il, BLANK, W, 0, NBEST, **kw), repeats)
+    t_ac = timed(lambda: NL.ctc_beam_decode_device(probs, il, BLANK, W, 0, NBEST, **kw), repeats, WARMUP)
     assert torch.equal(unit_sc, sc), "the unit model must give the acoustic bits"
     walk = probes_per_walk(per_state)
     out = {"tool": "ctc_beam_lm_time", "repeats": repeats, "warmup": WARMUP, "source_hash": L.nntk_build_source_hash().decode(),
@@ -95,11 +81,7 @@ def main():
            "unit_lm_ms_min_max": t_unit[1:], "acoustic_ms": t_ac[0], "acoustic_ms_min_max": t_ac[1:], "lm_over_acoustic": t_lm[0] / t_ac[0],
            "unit_over_acoustic": t_unit[0] / t_ac[0], "lm_over_unit": t_lm[0] / t_unit[0], "probes_per_walk": walk,
            "probes_per_frame": walk * (W * (CC - 1) + W), "us_per_frame": {"lm": 1e3 * t_lm[0] / T, "acoustic": 1e3 * t_ac[0] / T}}
-    line = json.dumps(out)
-    os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
-    with open(os.path.join(ROOT, "profiles", "ctc_beam_lm_time.json"), "w") as fh:
-        fh.write(line + "\n")
-    print(line)
+    emit(out, "ctc_beam_lm_time")
 
 
 if __name__ == "__main__":

@@ -5,29 +5,22 @@ B = 64 streams, C = 29, beam_width 16, nbest 1, a 1000-frame utterance per row, 
 chunk).  Three numbers per chunk size: the latency of one push in the middle of the stream (HIP events around a single push, median
 of the repeats x pushes samples); the one-shot call on the whole utterance, as time per frame; and the sum over all pushes of one
 stream (events around the whole stream, median of the repeats) against that one-shot call.  Warm-up: two whole streams / calls."""
-import json, os, sys
+import sys
 import numpy as np
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
-from nntoolkitcore_amd import capi, layers as NL
+from timing import emit, open_device, timed, timed_marks
+from nntoolkitcore_amd import layers as NL
 
 B, T, CC, W, NBEST, MAX_LABELS = 64, 1000, 29, 16, 1, 512
 CHUNKS = (10, 50)
 WARMUP = 2
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def spread(ms):
-    return {"median": float(np.median(ms)), "min": float(min(ms)), "max": float(max(ms))}
 
 
 def main():
     repeats = int(sys.argv[1]) if len(sys.argv) > 1 else 5
-    assert torch.cuda.is_available(), "needs the GPU"
-    torch.cuda.set_device(0); L = capi.load(); NL.use_torch_stream()
+    L = open_device()
     g = torch.Generator(device="cuda").manual_seed(B + T + CC)
     probs = torch.softmax(4 * torch.rand((B, T, CC), device="cuda", generator=g) - 2, -1)
-    ev = lambda: torch.cuda.Event(enable_timing=True)
     out = {"tool": "ctc_beam_stream_time", "repeats": repeats, "warmup": WARMUP, "source_hash": L.nntk_build_source_hash().decode(),
            "B": B, "T": T, "C": CC, "beam_width": W, "nbest": NBEST, "max_labels": MAX_LABELS, "chunks": []}
 
@@ -36,15 +29,7 @@ def main():
     n1 = torch.empty((B, NBEST), dtype=torch.int32, device="cuda")
     sc1 = torch.empty((B, NBEST), device="cuda")
     one = lambda: NL.ctc_beam_decode_device(probs, None, 0, W, 0, NBEST, labels_out=lab1, out_lengths=n1, scores=sc1, workspace=ws)
-    for _ in range(WARMUP):
-        one()
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(repeats):
-        a, b = ev(), ev()
-        a.record(); one(); b.record(); b.synchronize()
-        ms.append(a.elapsed_time(b))
-    out["one_shot_ms"] = spread(ms)
+    out["one_shot_ms"] = timed(one, repeats, WARMUP).dict
     out["one_shot_us_per_frame"] = 1e3 * out["one_shot_ms"]["median"] / T
     out["one_shot_workspace_bytes"] = 4 * ws.numel()
 
@@ -66,31 +51,14 @@ def main():
                 if events is not None:
                     events[i][1].record()
 
-        for _ in range(WARMUP):
-            stream()
-        torch.cuda.synchronize()
+        w = timed(stream, repeats, WARMUP).dict
         assert n.cpu().numpy().tobytes() == n1.cpu().numpy().tobytes() and sc.cpu().numpy().tobytes() == sc1.cpu().numpy().tobytes()
-        whole, per_push = [], []
-        for _ in range(repeats):
-            a, b = ev(), ev()
-            a.record(); stream(); b.record(); b.synchronize()
-            whole.append(a.elapsed_time(b))
-        for _ in range(repeats):
-            events = [(ev(), ev()) for _ in blocks]
-            stream(events)
-            torch.cuda.synchronize()
-            per_push.extend(s.elapsed_time(e) for s, e in events[len(blocks) // 4:])       # the stream's first quarter: short strings
-        w = spread(whole)
-        pp = spread(per_push)
+        pp = timed_marks(stream, len(blocks), repeats, len(blocks) // 4, 0).dict           # the stream's first quarter: short strings
         out["chunks"].append({"max_frames": mf, "pushes": len(blocks), "push_ms": pp, "push_us_per_frame": 1e3 * pp["median"] / mf,
                               "stream_ms": w, "stream_over_one_shot": w["median"] / out["one_shot_ms"]["median"],
                               "state_bytes": int(L.nntk_ctc_beam_stream_state_bytes(B, mf, CC, W, 0, MAX_LABELS))})
         dec.close()
-    line = json.dumps(out)
-    os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
-    with open(os.path.join(ROOT, "profiles", "ctc_beam_stream_time.json"), "w") as fh:
-        fh.write(line + "\n")
-    print(line)
+    emit(out, "ctc_beam_stream_time")
 
 
 if __name__ == "__main__":

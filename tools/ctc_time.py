@@ -1,35 +1,22 @@
 #!/usr/bin/env python3
 """What the CTC calls cost (csrc/hip/ctc.hip), next to torch.nn.functional.ctc_loss on the same GPU and inputs:
-python tools/ctc_time.py [repeats]      -> one JSON line (HIP events, warm-up, median of the repeats)
+python tools/ctc_time.py [repeats]      -> one JSON line (timed by tools/timing.py)
 Per shape: the loss alone, loss + gradient, the greedy decode; torch forward and forward + backward (torch is handed the
 log-probabilities ready made, [T][B][C] as it wants them); the gradient's bytes over the time the gradient adds to the call, and
 the loss-only call's time per timestep (that call is the alpha recursion and nothing else)."""
-import json, os, sys
+import sys
 import numpy as np
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
-from nntoolkitcore_amd import capi, layers as NL
+from timing import emit, open_device, ragged, timed
+from nntoolkitcore_amd import layers as NL
 
 SHAPES = ((512, 1000, 1000, 100), (512, 250, 40, 60))
 WARMUP = 2
 
 
-def timed(fn, repeats):
-    for _ in range(WARMUP):
-        fn()
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(repeats):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record(); fn(); b.record(); b.synchronize()
-        ms.append(a.elapsed_time(b))
-    return float(np.median(ms)), float(min(ms)), float(max(ms))
-
-
 def main():
     repeats = int(sys.argv[1]) if len(sys.argv) > 1 else 7
-    assert torch.cuda.is_available(), "needs the GPU"
-    torch.cuda.set_device(0); L = capi.load(); NL.use_torch_stream()
+    L = open_device()
     out = {"tool": "ctc_time", "repeats": repeats, "warmup": WARMUP, "source_hash": L.nntk_build_source_hash().decode(), "shapes": []}
     for B, T, Cc, ML in SHAPES:
         g = torch.Generator(device="cuda").manual_seed(B + T + Cc)
@@ -37,14 +24,14 @@ def main():
         rng = np.random.default_rng(T)
         lab = rng.integers(1, Cc, (B, ML)).astype(np.int32)
         lab[:, 1:] = np.where(lab[:, 1:] == lab[:, :-1], 1 + lab[:, 1:] % (Cc - 1), lab[:, 1:])     # mostly no repeats; feasible anyway: T >= 2 ML
-        ll = rng.integers(ML // 2, ML + 1, B).astype(np.int32); ll[0] = ML
+        ll = ragged(rng, ML, B)
         il = rng.integers(max(2 * ML, T // 2), T + 1, B).astype(np.int32); il[0] = T
         ws = torch.empty(L.nntk_ctc_workspace_floats(B, T, ML), device="cuda")
         loss, dprobs = torch.empty(B, device="cuda"), torch.empty_like(probs)
         dec, dn = torch.empty((B, T), dtype=torch.int32, device="cuda"), torch.empty(B, dtype=torch.int32, device="cuda")
-        t_loss = timed(lambda: NL.ctc_loss_device(probs, lab, ll, il, 0, want_grad=False, loss=loss, workspace=ws), repeats)
-        t_grad = timed(lambda: NL.ctc_loss_device(probs, lab, ll, il, 0, want_grad=True, loss=loss, dprobs=dprobs, workspace=ws), repeats)
-        t_dec = timed(lambda: NL.ctc_greedy_decode_device(probs, il, 0, labels_out=dec, out_lengths=dn), repeats)
+        t_loss = timed(lambda: NL.ctc_loss_device(probs, lab, ll, il, 0, want_grad=False, loss=loss, workspace=ws), repeats, WARMUP)
+        t_grad = timed(lambda: NL.ctc_loss_device(probs, lab, ll, il, 0, want_grad=True, loss=loss, dprobs=dprobs, workspace=ws), repeats, WARMUP)
+        t_dec = timed(lambda: NL.ctc_greedy_decode_device(probs, il, 0, labels_out=dec, out_lengths=dn), repeats, WARMUP)
         ours = loss.clone()
         assert torch.isfinite(ours).all() and torch.isfinite(dprobs).all()
         lp = torch.log(probs).transpose(0, 1).contiguous().requires_grad_(True)
@@ -58,8 +45,8 @@ def main():
             lp.grad = None
             torch.nn.functional.ctc_loss(lp, tl, til, tll, blank=0, reduction="sum").backward()
 
-        tt_f = timed(t_fwd, repeats)
-        tt_fb = timed(t_fwd_bwd, repeats)
+        tt_f = timed(t_fwd, repeats, WARMUP)
+        tt_fb = timed(t_fwd_bwd, repeats, WARMUP)
         rel = float(((keep["l"].detach() - ours).abs() / keep["l"].detach().abs()).max())
         gbytes = 4.0 * B * T * Cc
         out["shapes"].append({
@@ -75,7 +62,7 @@ def main():
             "max_rel_diff_loss_vs_torch_gpu": rel})
         del lp, probs, dprobs, ws
         torch.cuda.empty_cache()
-    print(json.dumps(out))
+    emit(out)
 
 
 if __name__ == "__main__":

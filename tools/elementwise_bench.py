@@ -5,17 +5,14 @@ bn_kernel_vec4_rows; batch_norm.c:140-163), ReLU and sigmoid (act_kernel; activa
 is the memory-bound path north_star asks a GB/s figure for.  Prints achieved GB/s from HIP events (algorithmic bytes = one
 read + one write of the tensor); run it under `rocprofv3 --kernel-trace --stats` for the per-kernel durations
 (tools/final_profile.sh does, profiles/r03_elementwise_kernel_stats.csv)."""
-import os, sys
 import numpy as np
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import torch
+from timing import open_device, timed
+from nntoolkitcore_amd import layers as NL
 
 
 def main():
-    import ctypes as C
-    import torch
-    from nntoolkitcore_amd import capi, layers as NL
-    torch.cuda.set_device(0); L = capi.load(); NL.use_torch_stream()
+    open_device()
     rows, Cc = 1024 * 996, 128
     r = np.random.default_rng(0)
     x = torch.randn(rows, Cc, device="cuda")
@@ -30,15 +27,7 @@ def main():
              ("sigmoid               (act_kernel)", lambda: sig.apply_device(x, out=y)),
              ("softmax over 128      (softmax_short_kernel<32>)", lambda: sm.apply_device(x, out=y))]
     for name, fn in cases:
-        for _ in range(3):
-            fn()
-        torch.cuda.synchronize()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(20):
-            fn()
-        e1.record(); torch.cuda.synchronize()
-        ms = e0.elapsed_time(e1) / 20
+        ms = timed(fn, 1, warmup=3, inner=20).median
         print("%-42s %8.1f us  %6.2f TB/s = %.2f of 8 TB/s   (%.0f MB read + written)" % (name, ms * 1e3, nbytes / ms / 1e9, nbytes / ms / 1e9 / 8.0, nbytes / 1e6), flush=True)
     for o in (bn, relu, sig, sm):
         o.destroy()

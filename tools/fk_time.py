@@ -3,14 +3,13 @@
 usage: python tools/fk_time.py [--reps N] cell:in:H[:B[:T]] ...      e.g.  gru:128:256 gru:256:256 lstm:128:512:512:996"""
 import os, sys
 import numpy as np
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import torch
+from timing import open_device, timed
+from nntoolkitcore_amd import capi, layers as NL
 
 
 def main():
-    import torch
-    from nntoolkitcore_amd import capi, layers as NL
-    torch.cuda.set_device(0); L = capi.load(); NL.use_torch_stream()
+    L = open_device()
     capi.set_option("rec_fk", int(os.environ.get("NNTK_REC_FK", "1")))
     reps = 7
     args = sys.argv[1:]
@@ -28,15 +27,8 @@ def main():
         lay = NL.LSTM(I, H, True, T, v2=True) if kind == "lstm" else NL.GRU(I, H, True, T)
         lay.set_weights(u(I, G * H, sc=I ** -0.5), u(H, G * H, sc=H ** -0.5), u(G * H, sc=0.1), u(G * H, sc=0.1))
         x = torch.randn(B, T, I, device="cuda"); h = torch.empty(B, T, H, device="cuda")
-        for _ in range(2):
-            lay.apply_device(x, out=h)
-        torch.cuda.synchronize()
-        ts = []
-        for _ in range(reps):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record(); lay.apply_device(x, out=h); e1.record(); torch.cuda.synchronize()
-            ts.append(e0.elapsed_time(e1))
-        out.append("%s %s med %.3f min %.3f ms" % (spec, L.nntk_hip_last_recurrent_kernel().decode(), np.median(ts), np.min(ts)))
+        t = timed(lambda: lay.apply_device(x, out=h), reps)
+        out.append("%s %s med %.3f min %.3f ms" % (spec, L.nntk_hip_last_recurrent_kernel().decode(), t.median, t.min))
         lay.destroy()
     print(" | ".join(out), flush=True)
 

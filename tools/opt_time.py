@@ -4,18 +4,17 @@ before the optimizer existed -- and (b) torch.optim.Adam(fused=True) + clip_grad
 
 Two block sets: the bench's config-5 parameters (conv 257->128 k 5 | BN 128 | LSTM 128->512 | TDD 512->1000, W and b as the gradient
 blocks hand them out) and the edge set of tests/test_gpu_optimizer.py.  Per measurement: WARMUP calls, then REPEATS timings of INNER
-back-to-back steps between two events; the median per step, the spread (min .. max) and bytes moved / time as a fraction of 8 TB/s.
+back-to-back steps between two events (tools/timing.py); the median per step, the spread (min .. max) and bytes moved / time as a
+fraction of 8 TB/s.
 Writes profiles/opt_time.json (--out)."""
 import argparse
 import ctypes as C
 import json
 import os
-import sys
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-import numpy as np
 import torch
 
+import timing
 from nntoolkitcore_amd import capi, layers as NL
 
 WARMUP, REPEATS, INNER = 20, 15, 50
@@ -25,30 +24,15 @@ SETS = {
 }
 
 
-def timed(fn):
-    for _ in range(WARMUP):
-        fn()
-    torch.cuda.synchronize()
-    out = []
-    for _ in range(REPEATS):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        for _ in range(INNER):
-            fn()
-        b.record()
-        b.synchronize()
-        out.append(a.elapsed_time(b) * 1e3 / INNER)
-    out.sort()
-    return {"median_us": out[len(out) // 2], "min_us": out[0], "max_us": out[-1]}
+def step_us(fn):
+    return {k + "_us": 1e3 * ms for k, ms in timing.timed(fn, REPEATS, WARMUP, INNER).dict.items()}
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join("profiles", "opt_time.json"))
     args = ap.parse_args()
-    torch.cuda.set_device(0)
-    NL.use_torch_stream()
-    L = capi.load()
+    L = timing.open_device()
     res = {"device": torch.cuda.get_device_name(0), "warmup": WARMUP, "repeats": REPEATS, "inner": INNER, "sets": {}}
     for name, sizes in SETS.items():
         n = sum(sizes)
@@ -60,7 +44,7 @@ def main():
                 ("adam_clip_zero", "adam", dict(learning_rate=1e-3, clip_norm=1.0, zero_gradients=1), 4 * (1 + 4 + 4)),   # pass 1 reads g; pass 2 reads g w m v, writes w m v g
                 ("sgd_zero", "sgd", dict(learning_rate=1e-3, zero_gradients=1), 4 * (1 + 2 + 2))):
             opt = NL.Optimizer(kind, blocks, **cfg)
-            t = timed(opt.step)
+            t = step_us(opt.step)
             t["bytes"] = bytes_per * n
             t["fraction_of_8TBs"] = t["bytes"] / (t["median_us"] * 1e-6) / 8e12
             r["optimizer_" + tag] = t
@@ -71,7 +55,7 @@ def main():
                 if w.numel():
                     L.nntk_sgd_optimize_device(capi.SGD(1e-3), C.c_void_p(g.data_ptr()), C.c_void_p(w.data_ptr()), w.numel())
                     g.zero_()
-        t = timed(parent)
+        t = step_us(parent)
         t["bytes"] = 4 * (2 + 1 + 1) * n
         t["fraction_of_8TBs"] = t["bytes"] / (t["median_us"] * 1e-6) / 8e12
         r["per_block_sgd_plus_memset"] = t
@@ -83,7 +67,7 @@ def main():
         def torch_step():
             torch.nn.utils.clip_grad_norm_(params, 1.0)
             topt.step()
-        t = timed(torch_step)
+        t = step_us(torch_step)
         t["bytes"] = 4 * (1 + 2 + 4 + 3) * n
         t["fraction_of_8TBs"] = t["bytes"] / (t["median_us"] * 1e-6) / 8e12
         r["torch_adam_fused_plus_clip"] = t

@@ -4,7 +4,7 @@ the plain call:
 python tools/rnnt_beam_detail_time.py [repeats] [--acoustic-json OUT] [--parent FILE]... [--same FILE]...
     -> profiles/rnnt_beam_detail_time.json and the same JSON line on stdout
 The model, frames and batch of tools/rnnt_beam_lm_time.py (E = H = J = 512, V = 1024, T = 100, tanh joiner, projection,
-max_symbols_per_frame 3, batch 16) at beam_width 4 and 8 (nbest = beam_width), HIP events, warm-up, median of the repeats.  Per width:
+max_symbols_per_frame 3, batch 16) at beam_width 4 and 8 (nbest = beam_width), timed by tools/timing.py.  Per width:
   acoustic_ms        nntk_rnnt_beam_decode_device
   detail_ms          nntk_rnnt_beam_decode_opt_device with label_frames and label_logps; its labels, lengths and score bits must be the
                      plain call's (detail_bits_equal_acoustic)
@@ -15,14 +15,13 @@ max_symbols_per_frame 3, batch 16) at beam_width 4 and 8 (nbest = beam_width), H
 parent commit's) is measured with the same code.  --parent FILE / --same FILE take such files -- of the parent's library, and of
 earlier runs of this one -- into the result: per width the parent's figures, and `spread`, the largest relative difference between
 two runs of one library in this session, which is the yardstick for `acoustic_vs_parent`.  Nothing but the bits is asserted."""
-import json, os, sys
+import json, sys
 import numpy as np
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import torch
+from timing import emit, open_device, timed
 from nntoolkitcore_amd import capi, layers as NL
-from rnnt_beam_lm_time import WIDTHS, trigram
-from rnnt_beam_time import BATCH, BLANK, E, H, J, MAX_SYMBOLS, T, V, model, timed
+from rnnt_beam_lm_time import WIDTHS, trigram, vs_parent
+from rnnt_beam_time import BATCH, BLANK, E, H, J, MAX_SYMBOLS, T, V, WARMUP, model
 
 
 def main():
@@ -31,13 +30,12 @@ def main():
     acoustic_json, parents, sames = take("--acoustic-json"), take("--parent"), take("--same")
     rest = [a for i, a in enumerate(args) if not a.startswith("--") and (i == 0 or not args[i - 1].startswith("--"))]
     repeats = int(rest[0]) if rest else 7
-    assert torch.cuda.is_available(), "needs the GPU"
     if acoustic_json:                                # an older build of the library lacks the newest entry points: bind what it exports
         import ctypes
         older = ctypes.CDLL(capi.LIB_PATH)
         for name in [n for n in capi.SIGNATURES if not hasattr(older, n)]:
             del capi.SIGNATURES[name]
-    torch.cuda.set_device(0); L = capi.load(); NL.use_torch_stream()
+    L = open_device()
     rng = np.random.default_rng(2024)
     m = model(rng)
     d = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
@@ -52,7 +50,7 @@ def main():
     def acoustic(W):
         outs, ws = dec._beam_outputs(enc.device, BATCH, W, ML), dec._beam_workspace(enc.device, BATCH, W, ML)
         ms, mm = timed(lambda: L.nntk_rnnt_beam_decode_device(dec.h, None, NL._dp(enc), BATCH, T, None, W, W, ML, NL._ipv(outs[0]),
-                                                              NL._ipv(outs[1]), NL._dp(outs[2]), NL._dp(ws)), repeats)
+                                                              NL._ipv(outs[1]), NL._dp(outs[2]), NL._dp(ws)), repeats, WARMUP).pair
         return ms, mm, [o.cpu().numpy() for o in outs]
 
     if acoustic_json:
@@ -70,7 +68,7 @@ def main():
     def run(W, model_, detail, norm):
         outs = dec._beam_outputs(enc.device, BATCH, W, ML) + (dec._beam_detail_outputs(enc.device, BATCH, W, ML) if detail else ())
         ws = dec._beam_workspace(enc.device, BATCH, W, ML, model_, detail, norm)
-        ms, mm = timed(lambda: dec._beam(None, enc, None, W, W, ML, outs, ws, model_, norm), repeats)
+        ms, mm = timed(lambda: dec._beam(None, enc, None, W, W, ML, outs, ws, model_, norm), repeats, WARMUP).pair
         return ms, mm, [o.cpu().numpy() for o in outs], ws.numel() * 4 / 2 ** 20
 
     load = lambda files: [json.load(open(f)) for f in files]
@@ -95,20 +93,9 @@ def main():
                    detail_lm_bits_equal_lm=same(got[:3], lm_plain))
         assert row["detail_lm_bits_equal_lm"], W
         if parent_runs:
-            row["parent_acoustic_ms"] = [r["widths"][i]["acoustic_ms"] for r in parent_runs]
-            row["parent_source_hash"] = parent_runs[0]["source_hash"]
-            row["acoustic_ms_earlier_runs"] = [r["widths"][i]["acoustic_ms"] for r in same_runs]
-            rel = lambda v: (max(v) - min(v)) / min(v) if len(v) > 1 else None
-            mine = row["acoustic_ms_earlier_runs"] + [ms]
-            row["spread"] = {"parent_runs": rel(row["parent_acoustic_ms"]), "this_commit_runs": rel(mine)}
-            row["acoustic_vs_parent"] = float(np.median(mine) / np.median(row["parent_acoustic_ms"]))
+            row.update(vs_parent(i, ms, parent_runs, same_runs))
         out["widths"].append(row)
-    line = json.dumps(out)
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    os.makedirs(os.path.join(root, "profiles"), exist_ok=True)
-    with open(os.path.join(root, "profiles", "rnnt_beam_detail_time.json"), "w") as fh:
-        fh.write(line + "\n")
-    print(line)
+    emit(out, "rnnt_beam_detail_time")
 
 
 if __name__ == "__main__":

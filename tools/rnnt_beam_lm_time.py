@@ -3,7 +3,7 @@
 python tools/rnnt_beam_lm_time.py [repeats] [--acoustic-json OUT] [--parent FILE]... [--same FILE]...
     -> profiles/rnnt_beam_lm_time.json and the same JSON line on stdout
 The model, frames and batch of tools/rnnt_beam_time.py (E = H = J = 512, V = 1024, T = 100, tanh joiner, projection,
-max_symbols_per_frame 3, batch 16) at beam_width 4 and 8 (nbest = beam_width), HIP events, warm-up, median of the repeats.  Per width:
+max_symbols_per_frame 3, batch 16) at beam_width 4 and 8 (nbest = beam_width), timed by tools/timing.py.  Per width:
   acoustic_ms           nntk_rnnt_beam_decode_device
   fused_no_arcs_ms      nntk_rnnt_beam_decode_lm_device with a one-state table without arcs, alpha = beta = 0, unk_logp 0: every term is
                         +0.0, so the search is the acoustic one step for step; what it costs beyond it is marking and filling lmterm
@@ -16,12 +16,12 @@ The trigram: every label in state 0, ten arcs from each one-label context, nine 
 parent commit's) is measured with the same code.  --parent FILE / --same FILE take such files -- of the parent's library, and of
 earlier runs of this one -- into the result: per width the parent's figures, and `spread`, the largest relative difference between
 two runs of one library in this session, which is the yardstick for `acoustic_vs_parent`.  Nothing is asserted."""
-import json, os, sys
+import json, sys
 import numpy as np
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
+from timing import emit, open_device, timed
 from nntoolkitcore_amd import capi, layers as NL
-from rnnt_beam_time import BATCH, BLANK, E, H, J, MAX_SYMBOLS, T, V, model, timed
+from rnnt_beam_time import BATCH, BLANK, E, H, J, MAX_SYMBOLS, T, V, WARMUP, model
 
 WIDTHS = (4, 8)
 
@@ -54,19 +54,31 @@ def trigram(rng):
     return t
 
 
+def vs_parent(i, ms, parent_runs, same_runs):
+    """width i of --parent / --same files next to this run's acoustic_ms: not the protocol of tools/timing.py, whose children this tool
+    does not start -- the files come from whole earlier runs, any number of them, so the spread is (max - min) / min over a library's
+    runs and the ratio is median over median"""
+    row = {"parent_acoustic_ms": [r["widths"][i]["acoustic_ms"] for r in parent_runs], "parent_source_hash": parent_runs[0]["source_hash"],
+           "acoustic_ms_earlier_runs": [r["widths"][i]["acoustic_ms"] for r in same_runs]}
+    rel = lambda v: (max(v) - min(v)) / min(v) if len(v) > 1 else None
+    mine = row["acoustic_ms_earlier_runs"] + [ms]
+    row["spread"] = {"parent_runs": rel(row["parent_acoustic_ms"]), "this_commit_runs": rel(mine)}
+    row["acoustic_vs_parent"] = float(np.median(mine) / np.median(row["parent_acoustic_ms"]))
+    return row
+
+
 def main():
     args = sys.argv[1:]
     take = lambda flag: [args[i + 1] for i, a in enumerate(args) if a == flag]
     acoustic_json, parents, sames = take("--acoustic-json"), take("--parent"), take("--same")
     rest = [a for i, a in enumerate(args) if not a.startswith("--") and (i == 0 or not args[i - 1].startswith("--"))]
     repeats = int(rest[0]) if rest else 5
-    assert torch.cuda.is_available(), "needs the GPU"
     if acoustic_json:                                # an older build of the library lacks the newest entry points: bind what it exports
         import ctypes
         older = ctypes.CDLL(capi.LIB_PATH)
         for name in [n for n in capi.SIGNATURES if not hasattr(older, n)]:
             del capi.SIGNATURES[name]
-    torch.cuda.set_device(0); L = capi.load(); NL.use_torch_stream()
+    L = open_device()
     rng = np.random.default_rng(2024)
     m = model(rng)
     d = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
@@ -81,7 +93,7 @@ def main():
     def acoustic(W):
         outs, ws = dec._beam_outputs(enc.device, BATCH, W, ML), dec._beam_workspace(enc.device, BATCH, W, ML)
         ms, mm = timed(lambda: L.nntk_rnnt_beam_decode_device(dec.h, None, NL._dp(enc), BATCH, T, None, W, W, ML, NL._ipv(outs[0]),
-                                                              NL._ipv(outs[1]), NL._dp(outs[2]), NL._dp(ws)), repeats)
+                                                              NL._ipv(outs[1]), NL._dp(outs[2]), NL._dp(ws)), repeats, WARMUP).pair
         return ms, mm, [o.cpu().numpy() for o in outs]
 
     if acoustic_json:
@@ -111,26 +123,15 @@ def main():
                "lmterm_bytes_per_depth_written_and_read": 8 * W * V}
         for name, lm in lms.items():
             outs, ws = dec._beam_outputs(enc.device, BATCH, W, ML), dec._beam_workspace(enc.device, BATCH, W, ML, lm)
-            fms, fmm = timed(lambda: dec._beam(None, enc, None, W, W, ML, outs, ws, lm), repeats)
+            fms, fmm = timed(lambda: dec._beam(None, enc, None, W, W, ML, outs, ws, lm), repeats, WARMUP).pair
             row[name + "_ms"], row[name + "_ms_min_max"], row[name + "_over_acoustic"] = fms, fmm, fms / ms
             if name != "fused_trigram":             # the unit models must leave the acoustic call's bits
                 got = [o.cpu().numpy() for o in outs]
                 row[name + "_bits_equal_acoustic"] = bool(all(np.array_equal(g.view(np.int32), p.view(np.int32)) for g, p in zip(got, plain)))
         if parent_runs:
-            row["parent_acoustic_ms"] = [r["widths"][i]["acoustic_ms"] for r in parent_runs]
-            row["parent_source_hash"] = parent_runs[0]["source_hash"]
-            row["acoustic_ms_earlier_runs"] = [r["widths"][i]["acoustic_ms"] for r in same_runs]
-            rel = lambda v: (max(v) - min(v)) / min(v) if len(v) > 1 else None
-            mine = row["acoustic_ms_earlier_runs"] + [ms]
-            row["spread"] = {"parent_runs": rel(row["parent_acoustic_ms"]), "this_commit_runs": rel(mine)}
-            row["acoustic_vs_parent"] = float(np.median(mine) / np.median(row["parent_acoustic_ms"]))
+            row.update(vs_parent(i, ms, parent_runs, same_runs))
         out["widths"].append(row)
-    line = json.dumps(out)
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    os.makedirs(os.path.join(root, "profiles"), exist_ok=True)
-    with open(os.path.join(root, "profiles", "rnnt_beam_lm_time.json"), "w") as fh:
-        fh.write(line + "\n")
-    print(line)
+    emit(out, "rnnt_beam_lm_time")
 
 
 if __name__ == "__main__":

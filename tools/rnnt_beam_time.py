@@ -2,14 +2,14 @@
 """What transducer beam search costs (csrc/hip/rnnt_beam.hip), next to greedy decoding of the same model and frames:
 python tools/rnnt_beam_time.py [repeats]      -> profiles/rnnt_beam_time.json and the same JSON line on stdout
 Model E = H = J = 512, V = 1024, T = 100, tanh joiner, with the projection, max_symbols_per_frame 3; batch 16.  `beam_ms`: one
-nntk_rnnt_beam_decode_device call at beam_width 1, 4 and 8 (nbest = beam_width; HIP events, warm-up, median of the repeats);
+nntk_rnnt_beam_decode_device call at beam_width 1, 4 and 8 (nbest = beam_width; timed by tools/timing.py);
 `greedy_ms`: one nntk_rnnt_greedy_decode_device call, measured the same way; `ratio_to_greedy` their quotient.  All numbers are
 reported as measured; nothing is asserted."""
-import json, os, sys
+import sys
 import numpy as np
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
-from nntoolkitcore_amd import capi, layers as NL
+from timing import emit, open_device, timed
+from nntoolkitcore_amd import layers as NL
 
 E = H = J = 512
 V, T, BLANK, MAX_SYMBOLS, BATCH = 1024, 100, 0, 3, 16
@@ -26,22 +26,9 @@ def model(rng):
                 Wp=u(2.0 * H ** -0.5, H, J), bp=u(0.1, J), Wo=u(3.0 * J ** -0.5, J, V), bo=bias)
 
 
-def timed(run, repeats):
-    for _ in range(WARMUP):
-        run()
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(repeats):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record(); run(); b.record(); b.synchronize()
-        ms.append(a.elapsed_time(b))
-    return float(np.median(ms)), [float(min(ms)), float(max(ms))]
-
-
 def main():
     repeats = int(sys.argv[1]) if len(sys.argv) > 1 else 5
-    assert torch.cuda.is_available(), "needs the GPU"
-    torch.cuda.set_device(0); L = capi.load(); NL.use_torch_stream()
+    L = open_device()
     rng = np.random.default_rng(2024)
     m = model(rng)
     d = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
@@ -51,7 +38,7 @@ def main():
     enc = d(rng.uniform(-1.5, 1.5, (BATCH, T, J)).astype(np.float32))
     ML = MAX_SYMBOLS * T
     g_outs = dec._outputs(enc.device, BATCH, ML)
-    greedy_ms, greedy_mm = timed(lambda: dec._decode(None, enc, None, ML, g_outs), repeats)
+    greedy_ms, greedy_mm = timed(lambda: dec._decode(None, enc, None, ML, g_outs), repeats, WARMUP).pair
     g_len, g_lab, g_sc = g_outs[2].cpu().numpy(), g_outs[0].cpu().numpy(), g_outs[3].cpu().numpy()
     out = {"tool": "rnnt_beam_time", "repeats": repeats, "warmup": WARMUP, "source_hash": L.nntk_build_source_hash().decode(),
            "model": {"E": E, "H": H, "J": J, "V": V, "T": T, "batch": BATCH, "max_symbols_per_frame": MAX_SYMBOLS},
@@ -59,19 +46,14 @@ def main():
     for W in WIDTHS:
         outs = dec._beam_outputs(enc.device, BATCH, W, ML)
         ws = dec._beam_workspace(enc.device, BATCH, W, ML)
-        ms, mm = timed(lambda: dec._beam(None, enc, None, W, W, ML, outs, ws), repeats)
+        ms, mm = timed(lambda: dec._beam(None, enc, None, W, W, ML, outs, ws), repeats, WARMUP).pair
         lab, ln, sc = (o.cpu().numpy() for o in outs)
         same = sum(lab[b, 0, :ln[b, 0]].tolist() == g_lab[b, :g_len[b]].tolist() for b in range(BATCH))
         out["widths"].append({"beam_width": W, "beam_ms": ms, "beam_ms_min_max": mm, "ratio_to_greedy": ms / greedy_ms,
                               "hypotheses_per_pass": int(L.nntk_shim_rnnt_beam_group(W, H, J, V)),
                               "workspace_mib": float(ws.numel() * 4 / 2 ** 20), "rows_whose_best_is_the_greedy_labels": int(same),
                               "rows_whose_best_score_is_at_least_greedy": int((sc[:, 0] >= g_sc - 1e-3).sum())})
-    line = json.dumps(out)
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    os.makedirs(os.path.join(root, "profiles"), exist_ok=True)
-    with open(os.path.join(root, "profiles", "rnnt_beam_time.json"), "w") as fh:
-        fh.write(line + "\n")
-    print(line)
+    emit(out, "rnnt_beam_time")
 
 
 if __name__ == "__main__":

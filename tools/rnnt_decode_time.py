@@ -2,15 +2,15 @@
 """What greedy transducer decoding costs (csrc/hip/rnnt_decode.hip), next to the host-driven loop it replaces:
 python tools/rnnt_decode_time.py [repeats]      -> profiles/rnnt_decode_time.json and the same JSON line on stdout
 Model E = H = J = 512, V = 1024, T = 200, tanh joiner, with the projection; batch 1, 16 and 256.  `decode_ms`: one
-nntk_rnnt_greedy_decode_device call (HIP events, warm-up, median of the repeats).  `host_loop_ms`: the same decoding driven from the
+nntk_rnnt_greedy_decode_device call (timed by tools/timing.py).  `host_loop_ms`: the same decoding driven from the
 host with the calls the library had before -- per decision, for the whole batch in lockstep: the joiner (T = U1 = 1), the vocabulary
 Dense, an argmax with its read-back, and for the rows that emitted a one-step LSTMApplyDeviceVarLen (length 0 keeps a row's state) and
 the projection Dense -- wall clock around the loop, median of the repeats.  Both numbers are reported as measured."""
-import json, os, sys, time
+import sys, time
 import numpy as np
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
-from nntoolkitcore_amd import capi, layers as NL
+from timing import emit, open_device, timed
+from nntoolkitcore_amd import layers as NL
 
 E = H = J = 512
 V, T, BLANK, MAX_SYMBOLS = 1024, 200, 0, 3
@@ -69,8 +69,7 @@ def host_loop(m, layers, enc, embed_d):
 
 def main():
     repeats = int(sys.argv[1]) if len(sys.argv) > 1 else 5
-    assert torch.cuda.is_available(), "needs the GPU"
-    torch.cuda.set_device(0); L = capi.load(); NL.use_torch_stream()
+    L = open_device()
     rng = np.random.default_rng(2024)
     m = model(rng)
     d = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
@@ -87,15 +86,7 @@ def main():
     for B in BATCHES:
         enc = d(rng.uniform(-1.5, 1.5, (B, T, J)).astype(np.float32))
         outs = dec._outputs(enc.device, B, MAX_SYMBOLS * T)
-        run = lambda: dec._decode(None, enc, None, MAX_SYMBOLS * T, outs)
-        for _ in range(WARMUP):
-            run()
-        torch.cuda.synchronize()
-        ms = []
-        for _ in range(repeats):
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record(); run(); b.record(); b.synchronize()
-            ms.append(a.elapsed_time(b))
+        ms, mm = timed(lambda: dec._decode(None, enc, None, MAX_SYMBOLS * T, outs), repeats, WARMUP).pair
         lengths = outs[2].cpu().numpy()
         labels = outs[0].cpu().numpy()
         hl = []
@@ -107,16 +98,12 @@ def main():
             hl.append(1e3 * (time.perf_counter() - t0))
         hl = hl[WARMUP:]
         same = sum(labels[b, :lengths[b]].tolist() == host_labels[b] for b in range(B))
-        out["batches"].append({"batch": B, "decode_ms": float(np.median(ms)), "decode_ms_min_max": [float(min(ms)), float(max(ms))],
+        out["batches"].append({"batch": B, "decode_ms": ms, "decode_ms_min_max": mm,
                                "host_loop_ms": float(np.median(hl)), "host_loop_ms_min_max": [float(min(hl)), float(max(hl))],
                                "labels_total": int(lengths.sum()),
                                "host_loop_iterations": int(decisions), "rows_with_identical_labels": int(same),
                                "rows_per_workgroup": int(L.nntk_shim_rnnt_dec_rows_per_group(B, H, J, V))})
-    line = json.dumps(out)
-    os.makedirs(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles"), exist_ok=True)
-    with open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "rnnt_decode_time.json"), "w") as fh:
-        fh.write(line + "\n")
-    print(line)
+    emit(out, "rnnt_decode_time")
 
 
 if __name__ == "__main__":

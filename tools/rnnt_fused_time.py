@@ -1,16 +1,16 @@
 #!/usr/bin/env python3
 """What the fused transducer training loss costs (csrc/hip/rnnt_fused.hip) against the composed five-call route it replaces:
-python tools/rnnt_fused_time.py [repeats] > profiles/rnnt_fused_time.json      (HIP events, 2 warm-up runs, median (min-max) of the repeats)
+python tools/rnnt_fused_time.py [repeats] > profiles/rnnt_fused_time.json      (timed by tools/timing.py)
 Per shape (batch, T, U = max_label_len, V, J), in one process: the fused call, loss only and with the gradients; the composed route
 (nntk_rnnt_joint_device, the training Dense, nntk_rnnt_loss_device, the Dense gradient, nntk_rnnt_joint_backward_device), forward only and
 with the gradients; the device bytes each route allocates for its intermediates; and the fraction of the exact-f32 MFMA peak the fused
 call reaches, counting 2 J V flops per live cell and product (1 product forward; 5 with the gradients: the forward's, its recomputation
 twice, d z and d W)."""
 import ctypes as C
-import json, os, sys
+import sys
 import numpy as np
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
+from timing import emit, open_device, ragged, timed
 from nntoolkitcore_amd import capi, layers as NL
 
 SHAPES = ((16, 200, 40, 512, 512), (4, 100, 20, 1024, 640), (4, 100, 20, 4096, 512))
@@ -18,22 +18,9 @@ WARMUP = 2
 PEAK_F32_MFMA = 157.3e12                                  # MI355X, dense f32 matrix
 
 
-def timed(fn, repeats):
-    for _ in range(WARMUP):
-        fn()
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(repeats):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record(); fn(); b.record(); b.synchronize()
-        ms.append(a.elapsed_time(b))
-    return float(np.median(ms)), float(min(ms)), float(max(ms))
-
-
 def main():
     repeats = int(sys.argv[1]) if len(sys.argv) > 1 else 9
-    assert torch.cuda.is_available(), "needs the GPU"
-    torch.cuda.set_device(0); L = capi.load(); NL.use_torch_stream()
+    L = open_device()
     dp = lambda t: C.c_void_p(t.data_ptr())
     out = {"tool": "rnnt_fused_time", "repeats": repeats, "warmup": WARMUP, "source_hash": L.nntk_build_source_hash().decode(),
            "peak_f32_mfma_flops": PEAK_F32_MFMA, "shapes": []}
@@ -41,8 +28,8 @@ def main():
         g = torch.Generator(device="cuda").manual_seed(B + T + V)
         rng = np.random.default_rng(T)
         lab = rng.integers(1, V, (B, U)).astype(np.int32)
-        ll = rng.integers(U // 2, U + 1, B).astype(np.int32); ll[0] = U
-        il = rng.integers(T // 2, T + 1, B).astype(np.int32); il[0] = T
+        ll = ragged(rng, U, B)
+        il = ragged(rng, T, B)
         live = int((il.astype(np.int64) * (ll + 1)).sum())
         U1, rows = U + 1, B * T * (U + 1)
         enc, pred = torch.rand((B, T, J), device="cuda", generator=g) - 0.5, torch.rand((B, U1, J), device="cuda", generator=g) - 0.5
@@ -51,9 +38,9 @@ def main():
         # ---- fused ----
         ws0 = torch.empty(L.nntk_rnnt_fused_workspace_floats(B, T, U, J, V, 0), device="cuda")
         ws1 = torch.empty(L.nntk_rnnt_fused_workspace_floats(B, T, U, J, V, 1), device="cuda")
-        t_f0 = timed(lambda: NL.rnnt_fused_loss_device(enc, pred, w, lab, ll, il, 0, "tanh", want_grad=False, loss=loss, workspace=ws0), repeats)
+        t_f0 = timed(lambda: NL.rnnt_fused_loss_device(enc, pred, w, lab, ll, il, 0, "tanh", want_grad=False, loss=loss, workspace=ws0), repeats, WARMUP)
         t_f1 = timed(lambda: NL.rnnt_fused_loss_device(enc, pred, w, lab, ll, il, 0, "tanh", loss=loss, denc=denc, dpred=dpred, dout=dw,
-                                                       workspace=ws1), repeats)
+                                                       workspace=ws1), repeats, WARMUP)
         fused_loss = loss.clone()
         assert torch.isfinite(loss).all() and torch.isfinite(denc).all() and torch.isfinite(dpred).all() and torch.isfinite(dw).all()
         fused_bytes = (4 * ws0.numel(), 4 * ws1.numel())
@@ -78,8 +65,8 @@ def main():
             assert L.DenseCalculateGradientDevice(dense, dp(dw), dp(djoint), dp(dlogits)) == 0, capi.last_error()
             NL.rnnt_joint_backward_device(joint, djoint, "tanh", denc=denc, dpred=dpred)
 
-        t_c0 = timed(lambda: forward(False), repeats)
-        t_c1 = timed(both, repeats)
+        t_c0 = timed(lambda: forward(False), repeats, WARMUP)
+        t_c1 = timed(both, repeats, WARMUP)
         rel = float(((loss - fused_loss).abs() / fused_loss.abs()).max())
         composed_bytes = (4 * (joint.numel() + logits.numel() + wsl.numel()),
                           4 * (joint.numel() + logits.numel() + dlogits.numel() + djoint.numel() + wsl.numel()))
@@ -98,7 +85,7 @@ def main():
             "loss_rows_max_relative_difference_fused_vs_composed": rel})
         del joint, logits, dlogits, djoint, wsl
         torch.cuda.empty_cache()
-    print(json.dumps(out))
+    emit(out)
 
 
 if __name__ == "__main__":

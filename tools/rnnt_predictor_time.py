@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """What training the prediction network costs (csrc/hip/rnnt_pred.hip, csrc/host/rnnt_pred.c):
-python tools/rnnt_predictor_time.py [repeats] [out.json]      -> profiles/rnnt_predictor_time.json (HIP events, warm-up, median)
+python tools/rnnt_predictor_time.py [repeats] [out.json]      -> profiles/rnnt_predictor_time.json (timed by tools/timing.py)
 Per shape (B, max_label_len, V, E = H = J): the predictor handle's forward + backward next to the recipe a caller had to write before --
 the lookup in numpy and an upload, the same device calls, a download of d_dX, np.add.at and an upload of d embed -- and the table
 gradient alone on the transducer's id distribution (the start symbol once per batch row) and on uniform ids, each against the time to
@@ -8,9 +8,8 @@ write V E floats and read rows E floats at the HBM copy rate DESIGN.md uses (6.2
 import ctypes as C
 import json, os, sys
 import numpy as np
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
 import torch
+from timing import ROOT, open_device, ragged, timed
 from nntoolkitcore_amd import capi, layers as NL
 
 SHAPES = ((64, 40, 1024, 512), (64, 40, 4096, 512))
@@ -19,23 +18,10 @@ HBM_COPY_BYTES_PER_S = 6.29e12
 DP = lambda t: C.c_void_p(t.data_ptr())
 
 
-def timed(fn, repeats):
-    for _ in range(WARMUP):
-        fn()
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(repeats):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record(); fn(); b.record(); b.synchronize()
-        ms.append(a.elapsed_time(b))
-    return float(np.median(ms)), float(min(ms)), float(max(ms))
-
-
 def main():
     repeats = int(sys.argv[1]) if len(sys.argv) > 1 else 15
     dest = sys.argv[2] if len(sys.argv) > 2 else os.path.join(ROOT, "profiles", "rnnt_predictor_time.json")
-    assert torch.cuda.is_available(), "needs the GPU"
-    torch.cuda.set_device(0); L = capi.load(); NL.use_torch_stream()
+    L = open_device()
     out = {"tool": "rnnt_predictor_time", "repeats": repeats, "warmup": WARMUP, "source_hash": L.nntk_build_source_hash().decode(),
            "hbm_copy_bytes_per_s": HBM_COPY_BYTES_PER_S, "shapes": []}
     for B, U, V, W in SHAPES:
@@ -45,7 +31,7 @@ def main():
         u = lambda sc, *s: torch.from_numpy(rng.uniform(-sc, sc, s).astype(np.float32)).cuda()
         embed, lstm, proj = u(1.0, V, E), u(H ** -0.5, 4 * H * (E + H + 2)), u(H ** -0.5, (H + 1) * J)
         lab = rng.integers(1, V, (B, U)).astype(np.int32)
-        ll = rng.integers(U // 2, U + 1, B).astype(np.int32); ll[0] = U
+        ll = ragged(rng, U, B)
         dpred = u(1.0, B, U1, J)
         p = NL.RnntPredictor(V, E, H, J, B, U)
         p.load_weights(embed, lstm, proj)
@@ -84,7 +70,7 @@ def main():
             np.add.at(g, ids.reshape(-1)[ids.reshape(-1) >= 0], dx[ids.reshape(-1) >= 0])
             r_dembed[0] = torch.from_numpy(g).cuda()
 
-        t_h, t_r = timed(handle, repeats), timed(recipe, repeats)
+        t_h, t_r = timed(handle, repeats, WARMUP), timed(recipe, repeats, WARMUP)
         torch.cuda.synchronize()
         assert torch.equal(pred, r_pred) and torch.equal(dlstm, r_dlstm) and torch.equal(dproj, r_dproj)
         assert torch.allclose(dembed, r_dembed[0], rtol=1e-4, atol=1e-5)
@@ -93,9 +79,9 @@ def main():
         ws = torch.empty(L.nntk_embedding_workspace_floats(rows, V, E), device="cuda")
         dout = u(1.0, rows, E)
         uniform = rng.integers(0, V, rows).astype(np.int32)
-        t_hot = timed(lambda: NL.embedding_gradient_device(dout, ids, V, dtable=dembed, workspace=ws), repeats)
-        t_uni = timed(lambda: NL.embedding_gradient_device(dout, uniform, V, dtable=dembed, workspace=ws), repeats)
-        t_look = timed(lambda: NL.embedding_lookup_device(embed, ids, out=dX.view(rows, E)), repeats)
+        t_hot = timed(lambda: NL.embedding_gradient_device(dout, ids, V, dtable=dembed, workspace=ws), repeats, WARMUP)
+        t_uni = timed(lambda: NL.embedding_gradient_device(dout, uniform, V, dtable=dembed, workspace=ws), repeats, WARMUP)
+        t_look = timed(lambda: NL.embedding_lookup_device(embed, ids, out=dX.view(rows, E)), repeats, WARMUP)
         bound_ms = 1e3 * 4.0 * (V * E + rows * E) / HBM_COPY_BYTES_PER_S
         out["shapes"].append({
             "B": B, "max_label_len": U, "V": V, "E": E, "H": H, "J": J, "rows": rows, "live_rows": int((ids >= 0).sum()),

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """What one training step of the pruned transducer loss costs (csrc/hip/rnnt_pruned.hip) against the two routes that make the whole lattice:
-python tools/rnnt_pruned_time.py [repeats] > profiles/rnnt_pruned_time.json    (HIP events, 2 warm-up runs, median (min-max) of the repeats)
+python tools/rnnt_pruned_time.py [repeats] > profiles/rnnt_pruned_time.json    (timed by tools/timing.py)
 Per shape (batch, T, U = max_label_len, V, J) and S, in one process:
   pruned: simple loss with its gradients and the occupancies (on given am [B][T][V] and lm [B][U1][V]), prune ranges, banded joiner, the
     training Dense forward on batch T S rows, banded loss and gradient, the Dense gradient, banded joiner backward -- the whole step and
@@ -10,10 +10,10 @@ Per shape (batch, T, U = max_label_len, V, J) and S, in one process:
   fused: nntk_rnnt_fused_loss_device with the gradients;
 and the device bytes each route allocates for its intermediates.  Lengths ragged as in tools/rnnt_fused_time.py."""
 import ctypes as C
-import json, os, sys
+import sys
 import numpy as np
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
+from timing import emit, open_device, ragged, timed
 from nntoolkitcore_amd import capi, layers as NL
 
 SHAPES = ((16, 200, 40, 512, 512), (4, 100, 20, 4096, 512))
@@ -21,22 +21,9 @@ S = 5
 WARMUP = 2
 
 
-def timed(fn, repeats):
-    for _ in range(WARMUP):
-        fn()
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(repeats):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record(); fn(); b.record(); b.synchronize()
-        ms.append(a.elapsed_time(b))
-    return float(np.median(ms)), float(min(ms)), float(max(ms))
-
-
 def main():
     repeats = int(sys.argv[1]) if len(sys.argv) > 1 else 9
-    assert torch.cuda.is_available(), "needs the GPU"
-    torch.cuda.set_device(0); L = capi.load(); NL.use_torch_stream()
+    L = open_device()
     dp = lambda t: C.c_void_p(t.data_ptr())
     out = {"tool": "rnnt_pruned_time", "repeats": repeats, "warmup": WARMUP, "S": S, "source_hash": L.nntk_build_source_hash().decode(),
            "shapes": []}
@@ -44,8 +31,8 @@ def main():
         g = torch.Generator(device="cuda").manual_seed(B + T + V)
         rng = np.random.default_rng(T)
         lab = rng.integers(1, V, (B, U)).astype(np.int32)
-        ll = rng.integers(U // 2, U + 1, B).astype(np.int32); ll[0] = U
-        il = rng.integers(T // 2, T + 1, B).astype(np.int32); il[0] = T
+        ll = ragged(rng, U, B)
+        il = ragged(rng, T, B)
         U1 = U + 1
         rnd = lambda *s: torch.rand(s, device="cuda", generator=g) - 0.5
         enc, pred, am, lm = rnd(B, T, J), rnd(B, U1, J), 4 * rnd(B, T, V), 4 * rnd(B, U1, V)
@@ -75,8 +62,8 @@ def main():
             for fn in parts.values():
                 fn()
 
-        t_step = timed(step, repeats)
-        t_parts = {k: timed(fn, repeats)[0] for k, fn in parts.items()}
+        t_step = timed(step, repeats, WARMUP)
+        t_parts = {k: timed(fn, repeats, WARMUP)[0] for k, fn in parts.items()}
         assert torch.isfinite(loss).all() and torch.isfinite(sloss).all() and torch.isfinite(denc).all() and torch.isfinite(dw).all()
         pruned_loss, simple_loss = loss.clone(), sloss.clone()
         pruned_bytes = 4 * sum(t.numel() for t in (dam, dlm, occ, ranges, joint, logits, dlogits, djoint, ws_s, ws_r, ws_p))
@@ -86,7 +73,7 @@ def main():
         # ---- fused ----
         ws1 = torch.empty(L.nntk_rnnt_fused_workspace_floats(B, T, U, J, V, 1), device="cuda")
         t_f = timed(lambda: NL.rnnt_fused_loss_device(enc, pred, w, lab, ll, il, 0, "tanh", loss=loss, denc=denc, dpred=dpred, dout=dw,
-                                                      workspace=ws1), repeats)
+                                                      workspace=ws1), repeats, WARMUP)
         fused_bytes = 4 * ws1.numel()
         full_loss = loss.clone()
         del ws1
@@ -108,7 +95,7 @@ def main():
             assert L.DenseCalculateGradientDevice(dense, dp(dw), dp(djoint), dp(dlogits)) == 0, capi.last_error()
             NL.rnnt_joint_backward_device(joint, djoint, "tanh", denc=denc, dpred=dpred)
 
-        t_c = timed(composed, repeats)
+        t_c = timed(composed, repeats, WARMUP)
         composed_bytes = 4 * (joint.numel() + logits.numel() + dlogits.numel() + djoint.numel() + wsl.numel())
         L.DenseDestroy(dense)
         out["shapes"].append({
@@ -123,7 +110,7 @@ def main():
             "pruned_loss_not_below_full_loss": bool((pruned_loss >= full_loss * (1 - 1e-5)).all())})
         del joint, logits, dlogits, djoint, wsl
         torch.cuda.empty_cache()
-    print(json.dumps(out))
+    emit(out)
 
 
 if __name__ == "__main__":

@@ -1,54 +1,41 @@
 #!/usr/bin/env python3
 """What the RNN-Transducer calls cost (csrc/hip/rnnt.hip):
-python tools/rnnt_time.py [repeats]      -> one JSON line (HIP events, warm-up, median of the repeats)
+python tools/rnnt_time.py [repeats]      -> one JSON line (timed by tools/timing.py)
 Per shape (batch, T, U = max_label_len, V, J): the loss alone, loss + gradient, the joiner and its backward, each with the bytes it
 cannot avoid moving and the bytes per second that makes of the measured time.  Minimum traffic: the loss reads the score tensor once;
 loss + gradient reads it once and writes the gradient once (the call reads it twice: 3 tensor passes against 2); the joiner writes its
 output once (its inputs are smaller by a factor U1 or T); the backward reads dout and, for tanh, out, once."""
-import json, os, sys
+import sys
 import numpy as np
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
-from nntoolkitcore_amd import capi, layers as NL
+from timing import emit, open_device, ragged, timed
+from nntoolkitcore_amd import layers as NL
 
 SHAPES = ((16, 200, 40, 512, 512), (4, 100, 20, 1024, 640))
 WARMUP = 2
 
 
-def timed(fn, repeats):
-    for _ in range(WARMUP):
-        fn()
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(repeats):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record(); fn(); b.record(); b.synchronize()
-        ms.append(a.elapsed_time(b))
-    return float(np.median(ms)), float(min(ms)), float(max(ms))
-
-
 def main():
     repeats = int(sys.argv[1]) if len(sys.argv) > 1 else 7
-    assert torch.cuda.is_available(), "needs the GPU"
-    torch.cuda.set_device(0); L = capi.load(); NL.use_torch_stream()
+    L = open_device()
     out = {"tool": "rnnt_time", "repeats": repeats, "warmup": WARMUP, "source_hash": L.nntk_build_source_hash().decode(), "shapes": []}
     for B, T, U, V, J in SHAPES:
         g = torch.Generator(device="cuda").manual_seed(B + T + V)
         logits = 4 * torch.rand((B, T, U + 1, V), device="cuda", generator=g) - 2
         rng = np.random.default_rng(T)
         lab = rng.integers(1, V, (B, U)).astype(np.int32)
-        ll = rng.integers(U // 2, U + 1, B).astype(np.int32); ll[0] = U
-        il = rng.integers(T // 2, T + 1, B).astype(np.int32); il[0] = T
+        ll = ragged(rng, U, B)
+        il = ragged(rng, T, B)
         ws = torch.empty(L.nntk_rnnt_workspace_floats(B, T, U, 1), device="cuda")
         loss, dlogits = torch.empty(B, device="cuda"), torch.empty_like(logits)
-        t_loss = timed(lambda: NL.rnnt_loss_device(logits, lab, ll, il, 0, want_grad=False, loss=loss, workspace=ws), repeats)
-        t_grad = timed(lambda: NL.rnnt_loss_device(logits, lab, ll, il, 0, want_grad=True, loss=loss, dlogits=dlogits, workspace=ws), repeats)
+        t_loss = timed(lambda: NL.rnnt_loss_device(logits, lab, ll, il, 0, want_grad=False, loss=loss, workspace=ws), repeats, WARMUP)
+        t_grad = timed(lambda: NL.rnnt_loss_device(logits, lab, ll, il, 0, want_grad=True, loss=loss, dlogits=dlogits, workspace=ws), repeats, WARMUP)
         assert torch.isfinite(loss).all() and torch.isfinite(dlogits).all()
         enc, pred = torch.rand((B, T, J), device="cuda", generator=g) - 0.5, torch.rand((B, U + 1, J), device="cuda", generator=g) - 0.5
         joint, denc, dpred = torch.empty((B, T, U + 1, J), device="cuda"), torch.empty_like(enc), torch.empty_like(pred)
         dout = torch.rand((B, T, U + 1, J), device="cuda", generator=g) - 0.5
-        t_j = timed(lambda: NL.rnnt_joint_device(enc, pred, "tanh", out=joint), repeats)
-        t_jb = timed(lambda: NL.rnnt_joint_backward_device(joint, dout, "tanh", denc=denc, dpred=dpred), repeats)
+        t_j = timed(lambda: NL.rnnt_joint_device(enc, pred, "tanh", out=joint), repeats, WARMUP)
+        t_jb = timed(lambda: NL.rnnt_joint_backward_device(joint, dout, "tanh", denc=denc, dpred=dpred), repeats, WARMUP)
         tensor = 4.0 * B * T * (U + 1) * V
         jt = 4.0 * B * T * (U + 1) * J
         out["shapes"].append({
@@ -63,7 +50,7 @@ def main():
             "joint_backward_moved_bytes_per_s": 4 * jt / (1e-3 * t_jb[0])})
         del logits, dlogits, ws, joint, dout
         torch.cuda.empty_cache()
-    print(json.dumps(out))
+    emit(out)
 
 
 if __name__ == "__main__":

@@ -1,15 +1,15 @@
 #!/usr/bin/env python3
 """Diagnostics build only (tools/build_variant.sh <lib> -DNNTK_RR_DBG; NNTK_LIB=<lib>, one library per compile-time mask: tools/rr_ablate.sh): time lstm_rr_kernel at the stack's
 LSTM shape with parts of the half-step removed (WRONG results, timing only).  usage: rr_ablate.py [B] [T]"""
-import os, sys
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import sys
+import torch
+from timing import open_device, timed
+import bench
+from nntoolkitcore_amd import layers as NL
 
 
 def main():
-    import torch, bench
-    from nntoolkitcore_amd import capi, layers as NL
-    torch.cuda.set_device(0); capi.load(); NL.use_torch_stream()
+    open_device()
     m = int(sys.argv[1]) if len(sys.argv) > 1 else 0
     B, T = 512, 996
     w = bench.make_weights("stack", 3)
@@ -17,15 +17,7 @@ def main():
     lstm.set_weights(w["lstm_W"], w["lstm_U"], w["lstm_bi"], w["lstm_bh"])
     x = torch.randn(B, T, 128, device="cuda"); h = torch.empty(B, T, 512, device="cuda")
     names = {1: "no operand loads", 2: "no finish", 4: "no arrive/poll", 8: "no x", 16: "no MFMA", 32: "no partial writes"}
-    for _ in range(3):
-        lstm.apply_device(x, out=h)
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(5):
-        lstm.apply_device(x, out=h)
-    e1.record(); torch.cuda.synchronize()
-    ms = e0.elapsed_time(e1) / 5
+    ms = timed(lambda: lstm.apply_device(x, out=h), 1, warmup=3, inner=5).median
     print("dbg %3d: %.3f ms = %.2f us/step   [%s]" % (m, ms, ms * 1e3 / T, ", ".join(v for k, v in names.items() if m & k) or "everything"), flush=True)
     lstm.destroy()
 

@@ -4,22 +4,17 @@ BASELINE GEMM shapes: conv config 3, the stack's conv / LSTM input projection / 
 rms |y - y64| against a float64 contraction of the same f32 inputs (torch, on the GPU), relative to rms(y64).
 usage: python tools/split_error.py [--rounds N]"""
 import json
-import os
 import sys
 
-import numpy as np
+import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+from timing import open_device, timed
+from nntoolkitcore_amd import capi, layers as NL
 
 
 def main():
-    import torch
-    from nntoolkitcore_amd import capi, layers as NL
     rounds = int(sys.argv[sys.argv.index("--rounds") + 1]) if "--rounds" in sys.argv else 5
-    torch.cuda.set_device(0)
-    capi.load()
-    NL.use_torch_stream()
+    open_device()
     g = torch.Generator(device="cuda").manual_seed(5)
     u = lambda *s, sc=1.0: (torch.rand(*s, generator=g, device="cuda") * 2 - 1) * sc
     cases = [  # name, B, T, Cin, Cout, k
@@ -89,18 +84,9 @@ def main():
         for mode in ("0", "1"):
             capi.set_option("gemm_split_bf16", mode)
             out = torch.empty(B, Tout, Cout, device="cuda")
-            conv.apply_device(x, out=out)
-            torch.cuda.synchronize()
-            ts = []
-            for _ in range(rounds):
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-                conv.apply_device(x, out=out)
-                e1.record()
-                torch.cuda.synchronize()
-                ts.append(e0.elapsed_time(e1))
+            ms = timed(lambda: conv.apply_device(x, out=out), rounds, warmup=1).median
             d = (out.double() - y64)
-            res[mode] = dict(ms=float(np.median(ts)), max_rel=float(d.abs().max()) / scale, rms_rel=float(d.pow(2).mean().sqrt()) / scale,
+            res[mode] = dict(ms=ms, max_rel=float(d.abs().max()) / scale, rms_rel=float(d.pow(2).mean().sqrt()) / scale,
                              max_abs=float(d.abs().max()))
             if mode == "0":
                 exact = out.clone()

@@ -10,19 +10,17 @@
 """
 import argparse
 import csv
-import os
-import sys
 
 import numpy as np
+import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+from timing import open_device, timed
+from nntoolkitcore_amd import layers as NL
 
 STREAM_ONLY = ("stream_gather_kernel", "varlen_zero_pad_kernel", "upload_ints_kernel")
 
 
 def build(B, chunk, rng, T_one=None):
-    from nntoolkitcore_amd import layers as NL
     from nntoolkitcore_amd.streaming import StreamingStack
     u = lambda *s, sc=1.0: rng.uniform(-sc, sc, s).astype(np.float32)
     spec = NL.Spectrogram(512, 400, 240, chunk)
@@ -43,17 +41,7 @@ def build(B, chunk, rng, T_one=None):
 
 
 def time_ms(fn, n, warm=3):
-    import torch
-    for _ in range(warm):
-        fn()
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(n):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / n
+    return timed(fn, 1, warmup=warm, inner=n).median
 
 
 def main():
@@ -70,10 +58,7 @@ def main():
                                                         100 * float(r["TotalDurationNs"]) / tot))
         print("stream-only passes (%s): %.2f %% of the GPU time" % (", ".join(STREAM_ONLY), 100 * so / tot))
         return
-    import torch
-    from nntoolkitcore_amd import layers as NL
-    torch.cuda.set_device(0)
-    NL.use_torch_stream()
+    open_device()
     rng = np.random.default_rng(0)
     if a.profile:
         B, chunk = 512, 2560

@@ -20,7 +20,7 @@ def main():
     r = np.random.default_rng(0)
     u = lambda *s, sc=1.0: r.uniform(-sc, sc, s).astype(np.float32)
 
-    def timed(name, fwd, bwd, work):
+    def wall(name, fwd, bwd, work):
         fwd(); bwd()
         capi.load().nntk_hip_synchronize()
         tf, tb = [], []
@@ -36,14 +36,14 @@ def main():
     h = L.Conv1dCreateForTraining(cfg, tc)
     x, y, d = u(B, T, Cin), np.empty((B, T - k + 1, Cout), np.float32), u(B, T - k + 1, Cout)
     g = L.Conv1dCreateGradient(cfg, tc)
-    timed("Conv1d(40->128,k5) B=64 T=1000", lambda: L.Conv1dApplyTrainingBatch(h, P(x), P(y)), lambda: L.Conv1dCalculateGradient(h, g, P(d)),
+    wall("Conv1d(40->128,k5) B=64 T=1000", lambda: L.Conv1dApplyTrainingBatch(h, P(x), P(y)), lambda: L.Conv1dCalculateGradient(h, g, P(d)),
           "%.1f GFLOP fwd" % (2e-9 * B * (T - k + 1) * Cin * k * Cout))
     import torch
     torch.cuda.set_device(0)
     dpc = lambda t: C.c_void_p(t.data_ptr())
     xd, dd, yd = torch.from_numpy(x).cuda(), torch.from_numpy(d).cuda(), torch.empty(B, T - k + 1, Cout, device="cuda")
     gd, gx = torch.zeros(Cout * Cin * k + Cout, device="cuda"), torch.empty(B, T, Cin, device="cuda")
-    timed("Conv1d(40->128,k5) B=64 T=1000, device pointers", lambda: (L.Conv1dApplyTrainingBatchDevice(h, dpc(xd), dpc(yd)), L.nntk_hip_synchronize()),
+    wall("Conv1d(40->128,k5) B=64 T=1000, device pointers", lambda: (L.Conv1dApplyTrainingBatchDevice(h, dpc(xd), dpc(yd)), L.nntk_hip_synchronize()),
           lambda: (L.Conv1dCalculateGradientDevice(h, dpc(gd), dpc(gx), dpc(dd)), L.nntk_hip_synchronize()), "same")
     L.ConvGradientDestroy(g); L.Conv1dDestroy(h)
     # BatchNorm over the conv output
@@ -55,7 +55,7 @@ def main():
     gam = np.ones(F, np.float32); C.memmove(w.gamma, gam.ctypes.data, gam.nbytes)
     x, y, d = u(B * count, F), np.empty((B * count, F), np.float32), u(B * count, F)
     g = L.BatchNormGradientCreate(bcfg, btc)
-    timed("BatchNorm(128) N=%d rows" % (B * count), lambda: L.BatchNormApplyTrainingBatch(h, P(x), P(y)), lambda: L.BatchNormCalculateGradient(h, g, P(d)),
+    wall("BatchNorm(128) N=%d rows" % (B * count), lambda: L.BatchNormApplyTrainingBatch(h, P(x), P(y)), lambda: L.BatchNormCalculateGradient(h, g, P(d)),
           "%.0f MB tensor" % (4e-6 * B * count * F))
     L.BatchNormGradientDestroy(g); L.BatchNormDestroy(h)
     # recurrent layers
@@ -74,7 +74,7 @@ def main():
             g = L.LSTMGradientCreate(cfg, capi.ConvTrainingConfig(B)); fw, bw, de = L.LSTMApplyTrainingBatch, L.LSTMCalculateGradient, L.LSTMDestroy
         W = u(n_in * G * H + H * G * H + 2 * G * H, sc=0.05); C.memmove(w.W, W.ctypes.data, W.nbytes)
         x, y, d = u(B, T, n_in), np.empty((B, T, H), np.float32), u(B, T, H)
-        timed("%s B=64 T=200" % name, lambda: fw(h, P(x), P(y)), lambda: bw(h, g, P(d)),
+        wall("%s B=64 T=200" % name, lambda: fw(h, P(x), P(y)), lambda: bw(h, g, P(d)),
               "%.1f GFLOP fwd" % (2e-9 * B * T * G * H * (n_in + H)))
         import torch
         torch.cuda.set_device(0)
@@ -82,7 +82,7 @@ def main():
         xd, dd, yd = torch.from_numpy(x).cuda(), torch.from_numpy(d).cuda(), torch.empty(B, T, H, device="cuda")
         gd, gx = torch.zeros(W.size, device="cuda"), torch.empty(B, T, n_in, device="cuda")
         fwd_, bwd_ = (L.GRUApplyTrainingBatchDevice, L.GRUCalculateGradientDevice) if G == 3 else (L.LSTMApplyTrainingBatchDevice, L.LSTMCalculateGradientDevice)
-        timed("%s B=64 T=200, device pointers" % name, lambda: (fwd_(h, dp_(xd), dp_(yd)), L.nntk_hip_synchronize()),
+        wall("%s B=64 T=200, device pointers" % name, lambda: (fwd_(h, dp_(xd), dp_(yd)), L.nntk_hip_synchronize()),
               lambda: (bwd_(h, dp_(gd), dp_(gx), dp_(dd)), L.nntk_hip_synchronize()), "same")
         L.RecurrentGradientDestroy(g); de(h)
     # dense head
@@ -91,7 +91,7 @@ def main():
     h = L.DenseCreateForTraining(cfg, capi.ConvTrainingConfig(B))
     x, y, d = u(B, n_in), np.empty((B, n_out), np.float32), u(B, n_out)
     g = L.DenseGradientCreateFromFilter(h)
-    timed("Dense(512->1000) rows=%d" % B, lambda: L.DenseApplyTrainingBatch(h, P(x), P(y)), lambda: L.DenseCalculateGradient(h, g, P(d)),
+    wall("Dense(512->1000) rows=%d" % B, lambda: L.DenseApplyTrainingBatch(h, P(x), P(y)), lambda: L.DenseCalculateGradient(h, g, P(d)),
           "%.1f GFLOP fwd" % (2e-9 * B * n_in * n_out))
     # the same mini-batch through the device-pointer forms (tensors stay in HBM: no PCIe in the timed region)
     import torch
@@ -100,7 +100,7 @@ def main():
     xd, dd = torch.from_numpy(x).cuda(), torch.from_numpy(d).cuda()
     yd = torch.empty(B, n_out, device="cuda"); gWd = torch.zeros(n_in * n_out + n_out, device="cuda"); gXd = torch.empty(B, n_in, device="cuda")
     sync = capi.load().nntk_hip_synchronize
-    timed("Dense(512->1000) rows=%d, device pointers" % B,
+    wall("Dense(512->1000) rows=%d, device pointers" % B,
           lambda: (L.DenseApplyTrainingBatchDevice(h, dp(xd), dp(yd)), sync()),
           lambda: (L.DenseCalculateGradientDevice(h, dp(gWd), dp(gXd), dp(dd)), sync()), "same")
     L.DenseGradientDestroy(g); L.DenseDestroy(h)
@@ -113,7 +113,7 @@ def main():
     N = Bm * count
     xd, dd, yd = torch.randn(N, F, device="cuda"), torch.randn(N, F, device="cuda"), torch.empty(N, F, device="cuda")
     dbe, dga, dxx = torch.empty(F, device="cuda"), torch.empty(F, device="cuda"), torch.empty(N, F, device="cuda")
-    timed("BatchNorm(128) N=%d rows, device pointers" % N,
+    wall("BatchNorm(128) N=%d rows, device pointers" % N,
           lambda: (L.BatchNormApplyTrainingBatchDevice(hb, dp(xd), dp(yd)), sync()),
           lambda: (L.BatchNormCalculateGradientDevice(hb, dp(dbe), dp(dga), dp(dxx), dp(dd)), sync()), "33 MB tensor")
     L.BatchNormDestroy(hb)

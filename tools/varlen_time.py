@@ -3,16 +3,15 @@
 alternate inside every round so that clock and power drift spread over all of them):
   (a) *ApplyDevice   (b) VarLen, every length T   (c) lengths uniform in [T/2, T], sorted descending   (d) the same lengths unsorted
 usage: python tools/varlen_time.py [--rounds N] cell:in:H:B:T ...   default: gru:128:256:1024:1000 gru:256:256:1024:1000 lstm:128:512:512:996"""
-import os, sys
+import sys
 import numpy as np
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import torch
+from timing import open_device, timed
+from nntoolkitcore_amd import layers as NL
 
 
 def main():
-    import torch
-    from nntoolkitcore_amd import capi, layers as NL
-    torch.cuda.set_device(0); L = capi.load(); NL.use_torch_stream()
+    L = open_device()
     rounds = 7
     args = sys.argv[1:]
     if args and args[0] == "--rounds":
@@ -42,9 +41,7 @@ def main():
         ts = {name: [] for name in variants}
         for _ in range(rounds):
             for name, fn in variants.items():
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record(); fn(); e1.record(); torch.cuda.synchronize()
-                ts[name].append(e0.elapsed_time(e1))
+                ts[name].append(timed(fn, 1, warmup=0).median)
         a = np.median(ts["a ApplyDevice"])
         print("%s  mean length of (c)/(d): %.3f T" % (spec, ragged.mean() / T))
         for name in variants:
