@@ -1500,6 +1500,54 @@ int nntk_rnnt_predictor_backward_device(NntkRnntPredictor p, const float *d_dpre
 size_t nntk_rnnt_predictor_device_bytes(NntkRnntPredictor p);
 void nntk_rnnt_predictor_destroy(NntkRnntPredictor p);
 
+/* ---- Error counts and MWER training (csrc/hip/edit_distance.hip; INTEGRATION.md "Error rates and MWER training") ----
+ * Edit distance: how wrong every hypothesis of an n-best list is, split into substitutions, deletions and insertions.
+ *   d_hyp [batch][n_hyp][max_hyp_len], d_hyp_lengths [batch][n_hyp]: DEVICE int, exactly as nntk_ctc_beam_decode_device /
+ *     nntk_rnnt_beam_decode_device (max_hyp_len = T / max_labels) or the greedy decoders (n_hyp = 1) leave them.  What stands behind
+ *     a hypothesis's length (the decoders write -1) is never read into the result.  A length < 0 is the decoders' "no hypothesis"
+ *     slot and gives {-1, -1, -1, -1}; a length above max_hyp_len is read as max_hyp_len.
+ *   refs [batch][max_ref_len], ref_lengths [batch]: HOST int, like the labels / label_lengths of the loss calls (the same arrays
+ *     serve both), checked before anything is enqueued, then copied in stream order.
+ *   sep < 0, unit mode: tokens are compared as ints, any value.  sep >= 0, word mode: both sequences are cut at tokens equal to sep
+ *     (leading, trailing and repeated separators make no empty words) and the same dynamic program runs over words; two words are
+ *     equal iff they have the same length and the same tokens (a hash pre-filters, the decision is exact).
+ *   Definition, h_1..h_m the hypothesis's units and r_1..r_n the reference's: D[0][j] = j (all deletions), D[i][0] = i (all
+ *     insertions); for i, j >= 1 a cell takes the smallest of (1) D[i-1][j-1] + (h_i != r_j), a hit or substitution, (2) D[i][j-1] + 1,
+ *     a deletion (r_j has no counterpart), (3) D[i-1][j] + 1, an insertion; on an equal distance the earlier candidate in that order
+ *     wins.  A cell's three counts are its chosen predecessor's counts plus the chosen operation; the result is cell (m, n) -- the
+ *     counts of a backtrace from (m, n) that takes the first minimal predecessor in the same order.  Hits = n - S - D.
+ *   d_counts [batch][n_hyp][4]: {distance = S + D + I, substitutions, deletions, insertions} of every pair.
+ *   d_ref_units [batch] or NULL: the reference's units -- ref_lengths[b], in word mode its word count.
+ *     Every element of both outputs is written.
+ *   d_workspace: nntk_edit_distance_workspace_floats(batch, n_hyp, max_hyp_len, max_ref_len) floats, 16-byte aligned: the copy of
+ *     the references and, for word mode, 8 bytes per possible word (every second token) of every sequence.
+ * Refused on the host before anything is enqueued, without a device (-1, nntk_last_error(), nothing written): batch < 0, n_hyp < 1,
+ * max_hyp_len outside [0, 32767] (every count fits 16 bits), max_ref_len outside [0, 4000] (the loss calls' limit: a pair's diagonals
+ * live in one workgroup's LDS), a reference length outside [0, max_ref_len], a NULL pointer (d_ref_units apart), a workspace that is
+ * not 16-byte aligned.  Deterministic: integer arithmetic, no atomics, the same bits on every call; a pair's counts depend on
+ * nothing but the pair -- not on the other rows, the padding, max_hyp_len or max_ref_len.  The device form runs on the calling
+ * thread's stream and reads nothing back; nntk_edit_distance takes every pointer in host memory: upload, device form, download.
+ *
+ * MWER (Prabhavalkar et al., 2018): the expected error over the renormalised n-best list and its gradient.  d_logp [batch][n_hyp]:
+ * the hypotheses' log-probabilities, finite or -inf (minus the loss rows of a loss call run with the hypotheses as labels);
+ * d_err: int, hypothesis k of row b at d_err[(b n_hyp + k) err_stride] -- err_stride 4 reads the distance column of d_counts in place.
+ * A hypothesis is valid iff err >= 0.  Over the valid ones P_k = exp(logp_k - logsumexp(logp)), e = the plain mean of err;
+ *   d_risk_rows [batch] = sum_k P_k (err_k - e),    d_dlogp [batch][n_hyp] = d risk / d logp_k = P_k ((err_k - e) - risk);
+ * either output may be NULL.  Invalid slots get exact zeros; a row with no valid hypothesis, or whose valid logp are all -inf, gets
+ * risk 0 and gradient 0: no NaN is ever written.  Accumulated in double in index order, rounded to f32 once; no atomics.
+ *
+ * Row scale: d_out[r][:] = d_x[r][:] d_scale[r] over [rows][row_floats], one f32 multiply per element; d_out may be d_x.  A
+ * d_scale[r] of exactly 0 gives exact zeros whatever the row holds, inf and NaN included.  With d_scale = -d_dlogp it turns the
+ * unreduced gradient of nntk_rnnt_loss_device / nntk_ctc_loss_device, run with the hypotheses as labels on batch n_hyp rows, into the
+ * gradient of the risk; the rows of invalid hypotheses may hold anything. */
+size_t nntk_edit_distance_workspace_floats(int batch, int n_hyp, int max_hyp_len, int max_ref_len);
+int nntk_edit_distance_device(const int *d_hyp, const int *d_hyp_lengths, int batch, int n_hyp, int max_hyp_len, const int *refs,
+                              const int *ref_lengths, int max_ref_len, int sep, int *d_counts, int *d_ref_units, float *d_workspace);
+int nntk_edit_distance(const int *hyp, const int *hyp_lengths, int batch, int n_hyp, int max_hyp_len, const int *refs,
+                       const int *ref_lengths, int max_ref_len, int sep, int *counts, int *ref_units);
+int nntk_mwer_device(const float *d_logp, const int *d_err, int err_stride, int batch, int n_hyp, float *d_risk_rows, float *d_dlogp);
+int nntk_row_scale_device(const float *d_x, const float *d_scale, long rows, long row_floats, float *d_out);
+
 #ifdef __cplusplus
 }
 #endif

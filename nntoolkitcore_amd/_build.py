@@ -13,8 +13,8 @@ CSRC = os.path.join(PKG, "csrc")
 OBJ = os.path.join(PKG, "lib", "obj")
 LIB = os.path.join(PKG, "lib", "libnntoolkitcore_hip.so")
 
-HOST_SRC = ["runtime.c", "activation.c", "conv_1d.c", "recurrent.c", "dense.c", "spectrogram.c", "mel.c", "train.c", "ctc.c", "ngram_lm.c", "rnnt.c", "rnnt_decode.c", "rnnt_pred.c"]
-HIP_SRC = ["runtime.hip", "conv1d.hip", "conv1d_s2.hip", "conv1d_flatk.hip", "recurrent.hip", "recurrent_rr.hip", "recurrent_fk.hip", "frag3.hip", "spectrogram.hip", "dist.hip", "conv1d_grad.hip", "train.hip", "ctc.hip", "ctc_beam.hip", "ctc_align.hip", "optim.hip", "bd_train.hip", "rnnt.hip", "rnnt_decode.hip", "rnnt_beam.hip", "rnnt_fused.hip", "rnnt_align.hip", "rnnt_pred.hip", "rnnt_pruned.hip"]
+HOST_SRC = ["runtime.c", "activation.c", "conv_1d.c", "recurrent.c", "dense.c", "spectrogram.c", "mel.c", "train.c", "ctc.c", "ngram_lm.c", "rnnt.c", "rnnt_decode.c", "rnnt_pred.c", "metrics.c"]
+HIP_SRC = ["runtime.hip", "conv1d.hip", "conv1d_s2.hip", "conv1d_flatk.hip", "recurrent.hip", "recurrent_rr.hip", "recurrent_fk.hip", "frag3.hip", "spectrogram.hip", "dist.hip", "conv1d_grad.hip", "train.hip", "ctc.hip", "ctc_beam.hip", "ctc_align.hip", "optim.hip", "bd_train.hip", "rnnt.hip", "rnnt_decode.hip", "rnnt_beam.hip", "rnnt_fused.hip", "rnnt_align.hip", "rnnt_pred.hip", "rnnt_pruned.hip", "edit_distance.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = "gfx950"
 

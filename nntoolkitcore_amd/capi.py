@@ -483,6 +483,12 @@ SIGNATURES = {
     "nntk_ctc_align_workspace_floats": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "nntk_ctc_align_device": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, ip, ip, ip, C.c_int, C.c_int, vp, vp, vp, vp]),
     "nntk_ctc_align": (C.c_int, [fp, C.c_int, C.c_int, C.c_int, ip, ip, ip, C.c_int, C.c_int, ip, ip, fp]),
+    # error counts, the MWER risk and the row scale (INTEGRATION.md "Error rates and MWER training")
+    "nntk_edit_distance_workspace_floats": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "nntk_edit_distance_device": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, ip, ip, C.c_int, C.c_int, vp, vp, vp]),
+    "nntk_edit_distance": (C.c_int, [ip, ip, C.c_int, C.c_int, C.c_int, ip, ip, C.c_int, C.c_int, ip, ip]),
+    "nntk_mwer_device": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp]),
+    "nntk_row_scale_device": (C.c_int, [vp, vp, C.c_long, C.c_long, vp]),
     # RNN-Transducer: loss, gradient with respect to the scores, the joiner (INTEGRATION.md "RNN-Transducer: loss and joiner")
     "nntk_rnnt_workspace_floats": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "nntk_rnnt_loss_device": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, ip, ip, ip, C.c_int, C.c_int, vp, vp, vp]),

@@ -203,6 +203,18 @@ size_t nntk_shim_ctc_align_workspace_floats(int batch, int T, int max_label_len)
 int nntk_shim_ctc_align(const float *d_probs, int B, int T, int C, const int *h_input_lengths, const int *h_labels,
                         const int *h_label_lengths, int max_label_len, int blank, int *d_states, int *d_spans, float *d_scores,
                         float *d_ws);
+/* ---- Error counts and the MWER risk (edit_distance.hip).  d_hyp [B][n_hyp][max_hyp_len] / d_hyp_len [B][n_hyp] device, as the decoders
+ *      write them; h_refs [B][max_ref_len] / h_ref_len [B] HOST memory, already checked by the caller (metrics.c), never NULL, copied in
+ *      stream order; sep < 0 units, sep >= 0 words; d_counts [B][n_hyp][4]; d_ref_units [B] or NULL; d_ws 16-byte aligned,
+ *      nntk_shim_edit_distance_workspace_floats words ---- */
+#define NNTK_EDIT_MAX_HYP_LEN 32767             /* every count of a cell fits 16 bits */
+#define NNTK_EDIT_MAX_REF_LEN NNTK_CTC_ALIGN_MAX_LABELS   /* the loss calls' limit: three diagonals of max_ref_len + 1 cells, 8 bytes each, live in LDS */
+size_t nntk_shim_edit_distance_workspace_floats(int batch, int n_hyp, int max_hyp_len, int max_ref_len);
+int nntk_shim_edit_distance(const int *d_hyp, const int *d_hyp_len, int B, int n_hyp, int max_hyp_len, const int *h_refs,
+                            const int *h_ref_len, int max_ref_len, int sep, int *d_counts, int *d_ref_units, float *d_ws);
+/* d_err read at d_err[(b * n_hyp + k) * err_stride]; d_risk_rows [B] / d_dlogp [B][n_hyp], either may be NULL */
+int nntk_shim_mwer(const float *d_logp, const int *d_err, int err_stride, int B, int n_hyp, float *d_risk_rows, float *d_dlogp);
+int nntk_shim_row_scale(const float *d_x, const float *d_scale, long rows, long row_floats, float *d_out);      /* d_out may be d_x */
 /* the transducer kernels' limits, stated here once for the host's checks (rnnt.c) and the launcher */
 #define NNTK_RNNT_MAX_LABELS 4000               /* max_label_len: two diagonals of max_label_len + 1 cells, 16 bytes each, live in LDS */
 #define NNTK_RNNT_MAX_DIAGONALS 65536           /* T + max_label_len: the exponents of that many emissions (each >= -4000) sum inside 2^28 */

@@ -1002,6 +1002,94 @@ def ctc_align(probs, labels, label_lengths=None, input_lengths=None, blank=0):
     return st, sp, sc
 
 
+def _edit_refs(refs, ref_lengths, B):
+    """references as the labels of ``ctc_loss_device`` (a list of per-row lists, or a padded int array with ref_lengths) ->
+    (int32 [B, max_ref_len], int32 [B])"""
+    lab, ll = _ctc_labels(refs, ref_lengths, B)
+    return np.ascontiguousarray(lab), ll
+
+
+def edit_distance_device(hyp, hyp_lengths, refs, ref_lengths=None, sep=-1, counts=None, ref_units=None, workspace=None):
+    """``nntk_edit_distance_device``: hyp [B,n_hyp,L] int32 device tensor with hyp_lengths [B,n_hyp], as the beam searches leave them
+    (or [B,L] with [B], the greedy decoders: n_hyp = 1); refs as the labels of the loss calls, HOST memory.  sep < 0 compares tokens,
+    sep >= 0 the words between separators.  Returns (counts [B,n_hyp,4] int32 = {distance, substitutions, deletions, insertions},
+    -1 for a slot without a hypothesis; ref_units [B] int32, the references' tokens or words)."""
+    import torch
+    if hyp.dim() == 2:
+        hyp = hyp.unsqueeze(1)
+    B, n_hyp, Lh = hyp.shape
+    assert hyp_lengths.numel() == B * n_hyp, "hyp_lengths: one per hypothesis"
+    ref, rl = _edit_refs(refs, ref_lengths, B)
+    L = capi.load()
+    need = L.nntk_edit_distance_workspace_floats(B, n_hyp, Lh, ref.shape[1])
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.float32, device=hyp.device)
+    assert workspace.numel() >= need, "workspace: nntk_edit_distance_workspace_floats(B, n_hyp, max_hyp_len, max_ref_len) floats"
+    if counts is None:
+        counts = torch.empty((B, n_hyp, 4), dtype=torch.int32, device=hyp.device)
+    if ref_units is None:
+        ref_units = torch.empty(B, dtype=torch.int32, device=hyp.device)
+    check(L.nntk_edit_distance_device(_ip(hyp), _ip(hyp_lengths), B, n_hyp, Lh, ref.ctypes.data_as(capi.ip), rl.ctypes.data_as(capi.ip),
+                                      ref.shape[1], sep, _ip(counts), _ip(ref_units), _dp(workspace)), "nntk_edit_distance_device")
+    return counts, ref_units
+
+
+def edit_distance(hyp, hyp_lengths, refs, ref_lengths=None, sep=-1):
+    """The host-memory form (``nntk_edit_distance``): hyp [B,n_hyp,L] (or [B,L]) and hyp_lengths numpy int arrays."""
+    hyp = np.ascontiguousarray(np.asarray(hyp, dtype=np.int32))
+    if hyp.ndim == 2:
+        hyp = hyp[:, None, :]
+    B, n_hyp, Lh = hyp.shape
+    hl = np.ascontiguousarray(np.asarray(hyp_lengths, dtype=np.int32).reshape(-1))
+    assert hl.shape[0] == B * n_hyp, "hyp_lengths: one per hypothesis"
+    ref, rl = _edit_refs(refs, ref_lengths, B)
+    counts, units = np.empty((B, n_hyp, 4), np.int32), np.empty(B, np.int32)
+    check(capi.load().nntk_edit_distance(hyp.ctypes.data_as(capi.ip), hl.ctypes.data_as(capi.ip), B, n_hyp, Lh, ref.ctypes.data_as(capi.ip),
+                                         rl.ctypes.data_as(capi.ip), ref.shape[1], sep, counts.ctypes.data_as(capi.ip),
+                                         units.ctypes.data_as(capi.ip)), "nntk_edit_distance")
+    return counts, units
+
+
+def error_rate(counts, ref_units):
+    """The corpus error rate of the first hypothesis of every row: sum of counts[b, 0, 0] over sum of ref_units[b] (the token error
+    rate in unit mode, the word error rate in word mode).  counts / ref_units: what ``edit_distance`` or ``edit_distance_device``
+    returned (device tensors are downloaded).  A row whose slot 0 holds no hypothesis counts as all deletions."""
+    c = counts.cpu().numpy() if hasattr(counts, "cpu") else np.asarray(counts)
+    u = ref_units.cpu().numpy() if hasattr(ref_units, "cpu") else np.asarray(ref_units)
+    d = c.reshape(u.shape[0], -1, 4)[:, 0, 0].astype(np.int64)
+    d = np.where(d < 0, u.astype(np.int64), d)
+    total = int(u.astype(np.int64).sum())
+    return float(d.sum()) / total if total else float("nan")
+
+
+def mwer_device(logp, counts, risk=None, dlogp=None):
+    """``nntk_mwer_device``: logp [B,n_hyp] float32 device tensor, the hypotheses' log-probabilities; counts: the [B,n_hyp,4] int32
+    tensor of ``edit_distance_device`` (its distance column is read in place) or a [B,n_hyp] int32 tensor of error counts; a negative
+    count marks a slot without a hypothesis.  Returns (risk [B], d risk / d logp [B,n_hyp])."""
+    import torch
+    B, n_hyp = logp.shape
+    stride = 4 if counts.dim() == 3 else 1
+    assert counts.numel() == B * n_hyp * stride, "counts: [B, n_hyp, 4] or [B, n_hyp]"
+    if risk is None:
+        risk = torch.empty(B, dtype=torch.float32, device=logp.device)
+    if dlogp is None:
+        dlogp = torch.empty_like(logp)
+    check(capi.load().nntk_mwer_device(_dp(logp), _ip(counts), stride, B, n_hyp, _dp(risk), _dp(dlogp)), "nntk_mwer_device")
+    return risk, dlogp
+
+
+def row_scale_device(x, scale, out=None):
+    """``nntk_row_scale_device``: x [rows, ...] float32 device tensor, scale [rows] -> out[r] = x[r] * scale[r] (``out`` may be ``x``);
+    a scale of exactly 0 gives zeros whatever the row holds."""
+    import torch
+    rows = scale.numel()
+    assert rows > 0 and x.shape[0] == rows or x.numel() == 0, "scale: one per row of x"
+    if out is None:
+        out = torch.empty_like(x)
+    check(capi.load().nntk_row_scale_device(_dp(x), _dp(scale), rows, x.numel() // max(rows, 1), _dp(out)), "nntk_row_scale_device")
+    return out
+
+
 RNNT_ACTIVATIONS = {ACT_IDENTITY: 0, ACT_TANH: 1, ACT_RELU: 2}
 
 
