@@ -17,7 +17,13 @@
 // barrier (the barriers wait for LDS only) and land in the other half of a double buffer at its end.  Per entry and frame one
 // (parent rank | prefix length, class or -1) record and the (p_b, p_nb) pair go to the workspace: the only global stores of the loop.
 // ctc_beam_backtrack_kernel: a workgroup per row stages the records of a block of frames in LDS and a lane per hypothesis walks them
-// from the last frame, writing labels in forward order, then the -1 padding, the lengths and the scores.
+// from the last frame, writing labels in forward order, then the -1 padding, the lengths and the scores.  ctc_beam_commit_kernel (a
+// stream's push) does the same per surviving entry for the frames of the push and appends to the strings the handle carries.
+//
+// Shared pieces, each written once.  beam_walk_records: the staged walk of the records, with a visitor per label (backtrack: write at
+// the position counted down; commit: write at the position the record names).  beam_final_rank: the end-of-sentence ranking, for the
+// one-shot call's tail and the commit.  The commit's `put` / slot_of / entry_of: one body for "entry k is hypothesis k" and for the
+// ranking's order.  beam_pad: what stands behind a hypothesis.  beam_dispatch: the host's runtime bools as template arguments.
 //
 // Prefix identity.  No label string is compared in the frame loop.  A prefix is known by a 64-bit hash chained over its labels
 // (splitmix64 finaliser), its length and its last class; an entry also carries its parent prefix's hash.  Entry j merges into the
@@ -42,6 +48,7 @@
 // walkers never see the mark.  Confidence: ln of the acoustic probability of the label at that frame, gathered by the walker.
 #include <stdint.h>
 #include <limits.h>
+#include <type_traits>
 #include "nntk_common.hpp"
 #include "ctc_xf.hpp"
 
@@ -114,6 +121,20 @@ __device__ __forceinline__ float beam_score(float4 m) {
 }
 // a label's confidence: ln of its acoustic probability at its reported frame, in double, rounded once.  One expression for both forms.
 __device__ __forceinline__ float beam_logp(float p) { return (float)log((double)p); }
+// The end-of-sentence ranking over the nb finalised keys in LDS (the caller stored them and passed a barrier): rank = the place of entry
+// tid in descending order, ties to the lower entry, or -1 for an exact zero or no entry; alive = the entries that are not zero.  One
+// expression for the one-shot call's tail and the stream's commit.
+struct BeamFinalRank { int rank, alive; };
+__device__ __forceinline__ BeamFinalRank beam_final_rank(const u64 *keys, int nb, int tid) {
+    const u64 k = tid < nb ? keys[tid] : 0ull;
+    int rank = 0, alive = 0;
+    for (int u = 0; u < nb; ++u) {
+        const u64 ku = keys[u];
+        rank += (ku > k || (ku == k && u < tid)) ? 1 : 0;
+        alive += ku != 0ull ? 1 : 0;
+    }
+    return {k != 0ull ? rank : -1, alive};
+}
 
 // ---- language model: F(state, c) and next(state, c) of INTEGRATION.md "Language-model fusion" ----
 __device__ __forceinline__ xf xf_mul(xf a, xf b) { return xf_norm(a.m * b.m, a.e + b.e); }
@@ -586,29 +607,62 @@ __global__ __launch_bounds__(CTC_THREADS) void ctc_beam_kernel(const float *__re
             lkey[tid] = beam_key(xf_pack(v));
         }
         __syncthreads();
-        if (tid < nb) {
-            const u64 k = lkey[tid];
-            int rank = 0, alive = 0;
-            for (int u = 0; u < nb; ++u) {
-                const u64 ku = lkey[u];
-                rank += (ku > k || (ku == k && u < tid)) ? 1 : 0;
-                alive += ku != 0ull ? 1 : 0;
-            }
-            if (k != 0ull) {
-                forder[(long)b * W + rank] = tid;
-                fmass[(long)b * W + rank] = make_float4(v.m, __int_as_float(v.e), 0.0f, __int_as_float(CTC_EZERO));
-            }
-            if (tid == 0) nfin[b] = alive;
+        const BeamFinalRank fin = beam_final_rank(lkey, nb, tid);
+        if (fin.rank >= 0) {
+            forder[(long)b * W + fin.rank] = tid;
+            fmass[(long)b * W + fin.rank] = make_float4(v.m, __int_as_float(v.e), 0.0f, __int_as_float(CTC_EZERO));
         }
-        if (nb == 0 && tid == 0) nfin[b] = 0;
+        if (tid == 0) nfin[b] = fin.alive;
     } else if (tid == 0) {
         nfin[b] = nb;
     }
 }
 
+// ---- what the backtrack and the stream's commit share ----
+
+// The record walk: the row's Tb frames of records are staged in LDS in blocks of BEAM_BT_RECORDS / W frames, the last block first, and
+// an `active` lane walks its entry's line of descent from `rank` in the last frame to the first frame.  Every record that made a label
+// (class >= 0) goes to visit(t, f, record): t its frame, f the frame the label reports -- under DETAIL the latest -2 record met since
+// the previous label (`ft`: a register of the lane, so it crosses the blocks' edges), else t.  Every lane of the workgroup must call:
+// the two barriers of a block are the workgroup's.  Returns the rank the line has before the first frame, and a pending `ft`.
+struct BeamWalkEnd { int rank, ft; };
+template <bool DETAIL, class Visit>
+__device__ __forceinline__ BeamWalkEnd beam_walk_records(int2 *rec, const int2 *__restrict__ hrow, int Tb, int W, int tid, bool active,
+                                                         int rank, Visit visit) {
+    int ft = -1;
+    const int TC = max(1, BEAM_BT_RECORDS / W);
+    for (int t1 = Tb; t1 > 0; t1 -= TC) {
+        const int t0 = max(0, t1 - TC);
+        const long base = (long)t0 * W;
+        const int cnt = (t1 - t0) * W;
+        __syncthreads();
+        for (int q = tid; q < cnt; q += CTC_THREADS) rec[q] = hrow[base + q];
+        __syncthreads();
+        if (active) {
+            for (int t = t1 - 1; t >= t0; --t) {
+                const int2 r = rec[(t - t0) * W + rank];
+                if (DETAIL && r.y == -2 && ft < 0) ft = t;                     // the latest merge that took this position's frame
+                if (r.y >= 0) {
+                    visit(t, ft >= 0 ? ft : t, r);
+                    ft = -1;
+                }
+                rank = r.x & 0xff;
+            }
+        }
+    }
+    return {rank, ft};
+}
+
+// behind a hypothesis: label -1, frame -1, log-probability 0.0 (fr, lp: null where that output is not asked for)
+template <bool DETAIL>
+__device__ __forceinline__ void beam_pad(long q, int *lab, int *fr, float *lp) {
+    lab[q] = -1;
+    if (DETAIL && fr) fr[q] = -1;
+    if (DETAIL && lp) lp[q] = 0.0f;
+}
+
 // ---- backtrack: hypothesis k of a row is entry k of its last frame; FIN (the LM calls): entry forder[k], with the total fmass[k] ----
-// DETAIL: the walking lane also writes frames / logps ([B][nbest][T] each, either may be null; "Label timestamps" above).  `ft`, the frame
-// a -2 record claimed for the position the walk stands at, lives in a register of the lane and so crosses the staged blocks' edges.
+// DETAIL: the walking lane also writes frames / logps ([B][nbest][T] each, either may be null; "Label timestamps" above).
 template <bool FIN, bool DETAIL>
 __global__ __launch_bounds__(CTC_THREADS) void ctc_beam_backtrack_kernel(int T, int W, int nbest, const int *__restrict__ lens,
                                                                          const int *__restrict__ nfin, const int2 *__restrict__ hist,
@@ -629,7 +683,7 @@ __global__ __launch_bounds__(CTC_THREADS) void ctc_beam_backtrack_kernel(int T, 
     const float *prow = DETAIL ? probs + (long)b * T * C : nullptr;
     int *fr = DETAIL && frames ? frames + (long)b * nbest * T : nullptr;
     float *lp = DETAIL && logps ? logps + (long)b * nbest * T : nullptr;
-    int rank = tid, len = -1, pos = -1, ft = -1;
+    int rank = tid, len = -1, pos = -1;
     if (tid < nbest) {
         float score = -INFINITY;
         if (tid < nh) {
@@ -647,43 +701,19 @@ __global__ __launch_bounds__(CTC_THREADS) void ctc_beam_backtrack_kernel(int T, 
         out_len[(long)b * nbest + tid] = len;
         scores[(long)b * nbest + tid] = score;
     }
-    const int TC = max(1, BEAM_BT_RECORDS / W);
-    for (int t1 = Tb; t1 > 0; t1 -= TC) {
-        const int t0 = max(0, t1 - TC);
-        const long base = (long)t0 * W;
-        const int cnt = (t1 - t0) * W;
-        __syncthreads();
-        for (int q = tid; q < cnt; q += CTC_THREADS) rec[q] = hrow[base + q];
-        __syncthreads();
-        if (tid < nh) {
-            for (int t = t1 - 1; t >= t0; --t) {
-                const int2 r = rec[(t - t0) * W + rank];
-                if (DETAIL && r.y == -2 && ft < 0) ft = t;                     // the latest merge that took this position's frame
-                if (r.y >= 0 && pos >= 0) {
-                    if (DETAIL) {
-                        const int f = ft >= 0 ? ft : t;
-                        if (fr) fr[(long)tid * T + pos] = f;
-                        if (lp) lp[(long)tid * T + pos] = beam_logp(prow[(long)f * C + r.y]);
-                        ft = -1;
-                    }
-                    lab[(long)tid * T + pos--] = r.y;
-                }
-                rank = r.x & 0xff;
-            }
+    // the labels in forward order: the walk meets the last one first
+    beam_walk_records<DETAIL>(rec, hrow, Tb, W, tid, tid < nh, rank, [&](int, int f, int2 r) {
+        if (pos < 0) return;
+        if (DETAIL) {
+            if (fr) fr[(long)tid * T + pos] = f;
+            if (lp) lp[(long)tid * T + pos] = beam_logp(prow[(long)f * C + r.y]);
         }
-    }
+        lab[(long)tid * T + pos--] = r.y;
+    });
     __syncthreads();
     const long cells = (long)nbest * T;
-    for (long q = tid; q < cells; q += CTC_THREADS) {
-        const int k = (int)(q / T), p = (int)(q % T);
-        if (p >= s_hlen[k]) {
-            lab[q] = -1;
-            if (DETAIL) {
-                if (fr) fr[q] = -1;
-                if (lp) lp[q] = 0.0f;
-            }
-        }
-    }
+    for (long q = tid; q < cells; q += CTC_THREADS)
+        if ((int)(q % T) >= s_hlen[(int)(q / T)]) beam_pad<DETAIL>(q, lab, fr, lp);
 }
 
 // ---- streaming commit: a workgroup per row, a lane per surviving entry.  The lane walks the push's records from its last frame to its
@@ -745,15 +775,9 @@ __global__ __launch_bounds__(CTC_THREADS) void ctc_beam_commit_kernel(int B, int
             s_key[tid] = beam_key(xf_pack(v));
         }
         __syncthreads();
-        const u64 k = tid < nb ? s_key[tid] : 0ull;
-        int rank = 0, alive = 0;
-        for (int u = 0; u < nb; ++u) {
-            const u64 ku = s_key[u];
-            rank += (ku > k || (ku == k && u < tid)) ? 1 : 0;
-            alive += ku != 0ull ? 1 : 0;
-        }
-        nh = min(nbest, alive);
-        slot = (k != 0ull && rank < nbest) ? rank : -1;
+        const BeamFinalRank fin = beam_final_rank(s_key, nb, tid);
+        nh = min(nbest, fin.alive);
+        slot = fin.rank < nbest ? fin.rank : -1;
         if (tid < W) s_slot[tid] = slot;
         if (slot >= 0) {
             s_ord[slot] = tid;
@@ -771,119 +795,84 @@ __global__ __launch_bounds__(CTC_THREADS) void ctc_beam_commit_kernel(int B, int
         scores[(long)b * nbest + tid] = score;
     }
     if (tid < W) s_hlen[tid] = len;
+    // who reports whom.  FIN: by the ranking above; else entry k is hypothesis k
+    auto slot_of = [&](int k) { return FIN ? s_slot[k] : (k < nbest ? k : -1); };     // the output slot of entry k (< nb), or -1
+    auto entry_of = [&](int k) { return FIN ? s_ord[k] : k; };                       // the entry that output slot k (< nh) reports
+    // element p of entry k: stored, and told if an output slot s >= 0 reports the entry
+    auto put = [&](int k, int s, int p, int v, int f, float lg) {
+        const long at = (long)k * L + p, to = FIN ? (long)s * L + p : at;             // !FIN: a reported entry's slot is its own index
+        dst[at] = v;
+        if (s >= 0) lab[to] = v;
+        if (DETAIL) {
+            fdst[at] = f;
+            ldst[at] = lg;
+            if (s >= 0 && ofr) ofr[to] = f;
+            if (s >= 0 && olp) olp[to] = lg;
+        }
+    };
     const long cells_out = (long)nbest * L;
     if (Tb == 0 || nb == 0) {
         __syncthreads();
         for (long q = tid; q < cells_out; q += CTC_THREADS) {
             const int k = (int)(q / L), p = (int)(q % L);
-            const int e = FIN ? (k < nh ? s_ord[k] : 0) : k;
-            const bool held = k < nh && p < min(s_hlen[e], L);
-            lab[q] = held ? src[(long)e * L + p] : -1;
-            if (DETAIL) {
-                if (ofr) ofr[q] = held ? fsrc[(long)e * L + p] : -1;
-                if (olp) olp[q] = held ? lsrc[(long)e * L + p] : 0.0f;
+            const int e = k < nh ? entry_of(k) : 0;
+            if (k < nh && p < min(s_hlen[e], L)) {
+                lab[q] = src[(long)e * L + p];
+                if (DETAIL && ofr) ofr[q] = fsrc[(long)e * L + p];
+                if (DETAIL && olp) olp[q] = lsrc[(long)e * L + p];
+            } else {
+                beam_pad<DETAIL>(q, lab, ofr, olp);
             }
         }
         return;
     }
-    int rank = tid, gained = 0, ft = -1;
-    const int TC = max(1, BEAM_BT_RECORDS / W);
-    for (int t1 = Tb; t1 > 0; t1 -= TC) {
-        const int t0 = max(0, t1 - TC);
-        const long base = (long)t0 * W;
-        const int cnt = (t1 - t0) * W;
-        __syncthreads();
-        for (int q = tid; q < cnt; q += CTC_THREADS) rec[q] = hrow[base + q];
-        __syncthreads();
-        if (tid < nb) {
-            for (int t = t1 - 1; t >= t0; --t) {
-                const int2 r = rec[(t - t0) * W + rank];
-                if (DETAIL && r.y == -2 && ft < 0) ft = t;                     // the latest merge that took this position's frame
-                if (r.y >= 0) {
-                    const int pos = (r.x >> 8) - 1;
-                    if (pos < L) {
-                        const bool told = FIN ? slot >= 0 : tid < nbest;
-                        const long at = (long)(FIN ? slot : tid) * L + pos;
-                        dst[(long)tid * L + pos] = r.y;
-                        if (told) lab[at] = r.y;
-                        if (DETAIL) {
-                            const int f = ft >= 0 ? ft : t;
-                            const float v = beam_logp(prow[(long)f * C + r.y]);
-                            fdst[(long)tid * L + pos] = seen + f;
-                            ldst[(long)tid * L + pos] = v;
-                            if (told && ofr) ofr[at] = seen + f;
-                            if (told && olp) olp[at] = v;
-                        }
-                    }
-                    if (DETAIL) ft = -1;
-                    ++gained;
-                }
-                rank = r.x & 0xff;
-            }
-        }
-    }
+    int gained = 0;
+    const BeamWalkEnd end = beam_walk_records<DETAIL>(rec, hrow, Tb, W, tid, tid < nb, tid, [&](int, int f, int2 r) {
+        const int pos = (r.x >> 8) - 1;
+        if (pos < L) put(tid, slot, pos, r.y, seen + f, DETAIL ? beam_logp(prow[(long)f * C + r.y]) : 0.0f);
+        ++gained;
+    });
     if (tid < nb) {
-        s_anc[tid] = rank;
+        s_anc[tid] = end.rank;
         s_alen[tid] = len - gained;
-        if (DETAIL) s_mvt[tid] = ft;
+        if (DETAIL) s_mvt[tid] = end.ft;
     }
     __syncthreads();
-    // DETAIL: element p of entry k's ancestor, moved when this push took the ancestor's last frame
-    auto carried = [&](int k, int p, int v, int &f, float &lg) {
-        f = fsrc[(long)s_anc[k] * L + p];
-        lg = lsrc[(long)s_anc[k] * L + p];
-        if (p == s_alen[k] - 1 && s_mvt[k] >= 0) {
-            f = seen + s_mvt[k];
-            lg = beam_logp(prow[(long)s_mvt[k] * C + min(max(v, 0), C - 1)]);
-        }
-    };
-    // the ancestors' strings, and the -1 behind every reported hypothesis; the places in between were written above
+    // the ancestors' strings, and the padding behind every reported hypothesis; the places in between were written above.  A k is looked
+    // at twice: as an entry, and as an output slot.  The places are disjoint whoever reports whom: a copy ends below s_alen <= s_hlen of
+    // the entry, the padding of the slot that reports it starts at s_hlen; and `k >= nh ||` keeps entry_of from an unreported slot
     const long cells = (long)max(nb, nbest) * L;
     for (long q = tid; q < cells; q += CTC_THREADS) {
         const int k = (int)(q / L), p = (int)(q % L);
-        if (FIN) {
-            // k as an entry: its ancestor's string; k as an output slot: the -1 behind the hypothesis it reports (disjoint places)
-            if (k < nb && p < min(s_alen[k], L)) {
-                const int v = src[(long)s_anc[k] * L + p];
-                dst[(long)k * L + p] = v;
-                if (s_slot[k] >= 0) lab[(long)s_slot[k] * L + p] = v;
-                if (DETAIL) {
-                    int f;
-                    float lg;
-                    carried(k, p, v, f, lg);
-                    fdst[(long)k * L + p] = f;
-                    ldst[(long)k * L + p] = lg;
-                    if (s_slot[k] >= 0 && ofr) ofr[(long)s_slot[k] * L + p] = f;
-                    if (s_slot[k] >= 0 && olp) olp[(long)s_slot[k] * L + p] = lg;
+        if (k < nb && p < min(s_alen[k], L)) {
+            const int a = s_anc[k], v = src[(long)a * L + p];
+            int f = 0;
+            float lg = 0.0f;
+            if (DETAIL) {
+                // the ancestor's element, moved when this push took the ancestor's last frame
+                f = fsrc[(long)a * L + p];
+                lg = lsrc[(long)a * L + p];
+                if (p == s_alen[k] - 1 && s_mvt[k] >= 0) {
+                    f = seen + s_mvt[k];
+                    lg = beam_logp(prow[(long)s_mvt[k] * C + min(max(v, 0), C - 1)]);
                 }
             }
-            if (k < nbest && (k >= nh || p >= min(s_hlen[s_ord[k < nh ? k : 0]], L))) {
-                lab[(long)k * L + p] = -1;
-                if (DETAIL && ofr) ofr[(long)k * L + p] = -1;
-                if (DETAIL && olp) olp[(long)k * L + p] = 0.0f;
-            }
-        } else if (k < nb && p < min(s_alen[k], L)) {
-            const int v = src[(long)s_anc[k] * L + p];
-            dst[(long)k * L + p] = v;
-            if (k < nbest) lab[(long)k * L + p] = v;
-            if (DETAIL) {
-                int f;
-                float lg;
-                carried(k, p, v, f, lg);
-                fdst[(long)k * L + p] = f;
-                ldst[(long)k * L + p] = lg;
-                if (k < nbest && ofr) ofr[(long)k * L + p] = f;
-                if (k < nbest && olp) olp[(long)k * L + p] = lg;
-            }
-        } else if (k < nbest && (k >= nh || p >= min(s_hlen[k], L))) {
-            lab[(long)k * L + p] = -1;
-            if (DETAIL && ofr) ofr[(long)k * L + p] = -1;
-            if (DETAIL && olp) olp[(long)k * L + p] = 0.0f;
+            put(k, slot_of(k), p, v, f, lg);
         }
+        if (k < nbest && (k >= nh || p >= min(s_hlen[entry_of(k)], L))) beam_pad<DETAIL>(q, lab, ofr, olp);
     }
 }
 
 // ---- host section.  lm NULL: the acoustic-only kernels, exactly ----
+
+// runtime bools -> template arguments: beam_dispatch(f, b0, b1, ...) calls the generic lambda f with one std::bool_constant per bool
+template <class F>
+static int beam_dispatch(F f) { return f(); }
+template <class F, class... Bools>
+static int beam_dispatch(F f, bool b, Bools... rest) {
+    return b ? beam_dispatch([&](auto... c) { return f(std::true_type(), c...); }, rest...)
+             : beam_dispatch([&](auto... c) { return f(std::false_type(), c...); }, rest...);
+}
 
 // The class cut (when one applies) and the beam kernel.  One-shot call (STREAM false): lens = the rows' lengths, nfin / mass / forder /
 // fmass the workspace's, an empty carry.  Push (STREAM true): lens = the control block, cs = the handle's beam, those four null.
@@ -908,23 +897,13 @@ static int beam_launch(const float *d_probs, int B, int T, int C, int blank, int
                                     : "nntk_ctc_beam_decode_device: the beam does not fit one workgroup's LDS");
     const unsigned magic = n + 1 > 1 ? (unsigned)(0x100000000ull / (unsigned)(n + 1)) + 1u : 0u;
     const nntk_shim_lm lmv = lm ? *lm : nntk_shim_lm();
-#define BEAM_GO(CUT, STAGE, LM, DETAIL)                                                                                            \
-    do {                                                                                                                           \
-        if (lds > 48 * 1024 && nntk_set_max_dynamic_lds((const void *)ctc_beam_kernel<CUT, STAGE, STREAM, LM, DETAIL>, lds))       \
-            return -1;                                                                                                             \
-        hipLaunchKernelGGL((ctc_beam_kernel<CUT, STAGE, STREAM, LM, DETAIL>), dim3((unsigned)B), dim3(CTC_THREADS), lds,           \
-                           nntk_stream(), d_probs, T, C, blank, W, n, magic, d_lens, d_nfin, d_hist, d_mass, d_pairs, cs, lmv,     \
-                           d_forder, d_fmass);                                                                                     \
-    } while (0)
-#define BEAM_GO2(LM, DETAIL)                                                                                                       \
-    do {                                                                                                                           \
-        if (ncut) { if (stage) BEAM_GO(true, true, LM, DETAIL); else BEAM_GO(true, false, LM, DETAIL); }                           \
-        else { if (stage) BEAM_GO(false, true, LM, DETAIL); else BEAM_GO(false, false, LM, DETAIL); }                              \
-    } while (0)
-    if (detail) { if (lm) BEAM_GO2(true, true); else BEAM_GO2(false, true); }
-    else { if (lm) BEAM_GO2(true, false); else BEAM_GO2(false, false); }
-#undef BEAM_GO2
-#undef BEAM_GO
+    if (beam_dispatch([&](auto cut, auto stg, auto lmc, auto det) {
+            const auto kern = ctc_beam_kernel<cut.value, stg.value, STREAM, lmc.value, det.value>;
+            if (lds > 48 * 1024 && nntk_set_max_dynamic_lds((const void *)kern, lds)) return -1;
+            hipLaunchKernelGGL(kern, dim3((unsigned)B), dim3(CTC_THREADS), lds, nntk_stream(), d_probs, T, C, blank, W, n, magic, d_lens,
+                               d_nfin, d_hist, d_mass, d_pairs, cs, lmv, d_forder, d_fmass);
+            return 0;
+        }, ncut != 0, stage, lm != nullptr, detail)) return -1;
     NNTK_LAUNCH_CHECK("ctc_beam_kernel");
     return 0;
 }
@@ -954,16 +933,13 @@ int nntk_shim_ctc_beam_decode(const float *d_probs, int B, int T, int C, const i
     if (beam_launch<false>(d_probs, B, T, C, blank, W, ncut, lm, detail, d_lens, d_nfin, d_hist, d_mass, (float2 *)(d_ws + lay.cut), BeamCarry(),
                            d_forder, d_fmass)) return -1;
     const size_t blds = (size_t)BEAM_BT_RECORDS * sizeof(int2);
-#define BEAM_BT(FIN, DETAIL)                                                                                                       \
-    do {                                                                                                                           \
-        if (nntk_set_max_dynamic_lds((const void *)ctc_beam_backtrack_kernel<FIN, DETAIL>, blds)) return -1;                       \
-        hipLaunchKernelGGL((ctc_beam_backtrack_kernel<FIN, DETAIL>), dim3((unsigned)B), dim3(CTC_THREADS), blds, nntk_stream(), T, \
-                           W, nbest, d_lens, d_nfin, d_hist, d_mass, d_forder, d_fmass, d_labels_out, d_out_lengths, d_scores,     \
-                           d_probs, C, d_label_frames, d_label_logps);                                                             \
-    } while (0)
-    if (detail) { if (lm) BEAM_BT(true, true); else BEAM_BT(false, true); }
-    else { if (lm) BEAM_BT(true, false); else BEAM_BT(false, false); }
-#undef BEAM_BT
+    if (beam_dispatch([&](auto fin, auto det) {
+            const auto kern = ctc_beam_backtrack_kernel<fin.value, det.value>;
+            if (nntk_set_max_dynamic_lds((const void *)kern, blds)) return -1;
+            hipLaunchKernelGGL(kern, dim3((unsigned)B), dim3(CTC_THREADS), blds, nntk_stream(), T, W, nbest, d_lens, d_nfin, d_hist, d_mass,
+                               d_forder, d_fmass, d_labels_out, d_out_lengths, d_scores, d_probs, C, d_label_frames, d_label_logps);
+            return 0;
+        }, lm != nullptr, detail)) return -1;
     NNTK_LAUNCH_CHECK("ctc_beam_backtrack_kernel");
     return 0;
 }
@@ -1010,16 +986,13 @@ int nntk_shim_ctc_beam_stream_push(const float *d_probs, int B, int T, int C, co
     if (any_frames && beam_launch<true>(d_probs, B, T, C, blank, W, ncut, lm, detail != 0, d_ctl, nullptr, d_hist, nullptr, (float2 *)(d_buf + lay.cut),
                                         cs, nullptr, nullptr)) return -1;
     const size_t blds = (size_t)BEAM_BT_RECORDS * sizeof(int2);
-#define BEAM_COMMIT(FIN, DETAIL)                                                                                                   \
-    do {                                                                                                                           \
-        if (nntk_set_max_dynamic_lds((const void *)ctc_beam_commit_kernel<FIN, DETAIL>, blds)) return -1;                          \
-        hipLaunchKernelGGL((ctc_beam_commit_kernel<FIN, DETAIL>), dim3((unsigned)B), dim3(CTC_THREADS), blds, nntk_stream(), B, T, \
-                           W, nbest, L, d_ctl, cs, d_hist, d_strs, d_labels_out, d_out_lengths, d_scores, lmv, d_probs, C,         \
-                           d_fstrs, d_lstrs, d_label_frames, d_label_logps);                                                       \
-    } while (0)
-    if (detail) { if (lm) BEAM_COMMIT(true, true); else BEAM_COMMIT(false, true); }
-    else { if (lm) BEAM_COMMIT(true, false); else BEAM_COMMIT(false, false); }
-#undef BEAM_COMMIT
+    if (beam_dispatch([&](auto fin, auto det) {
+            const auto kern = ctc_beam_commit_kernel<fin.value, det.value>;
+            if (nntk_set_max_dynamic_lds((const void *)kern, blds)) return -1;
+            hipLaunchKernelGGL(kern, dim3((unsigned)B), dim3(CTC_THREADS), blds, nntk_stream(), B, T, W, nbest, L, d_ctl, cs, d_hist, d_strs,
+                               d_labels_out, d_out_lengths, d_scores, lmv, d_probs, C, d_fstrs, d_lstrs, d_label_frames, d_label_logps);
+            return 0;
+        }, lm != nullptr, detail != 0)) return -1;
     NNTK_LAUNCH_CHECK("ctc_beam_commit_kernel");
     return 0;
 }

@@ -641,70 +641,55 @@ def ctc_greedy_decode(probs, input_lengths=None, blank=0):
     return out, n
 
 
-def _beam_outputs(device, B, nbest, L, labels_out, out_lengths, scores):
-    """the caller's output tensors of a beam search, or new ones: labels [B, nbest, L] int32, lengths [B, nbest] int32, scores float32"""
+def _ctc_beam_arrays(device, B, nbest, L, detail, given=(None, None, None)):
+    """The outputs of a CTC beam search: labels [B, nbest, L] int32, lengths [B, nbest] int32, scores [B, nbest] float32 and, with
+    detail, label_frames int32 and label_logps float32 [B, nbest, L].  Tensors on ``device`` -- the caller's (``given``: labels_out,
+    out_lengths, scores) where it passed some -- or, device None, numpy arrays.  -> (the arrays, their addresses as the C entries
+    take them: untyped for device tensors, typed for numpy arrays)"""
+    shapes = [((B, nbest, L), "int32"), ((B, nbest), "int32"), ((B, nbest), "float32")]
+    shapes += [((B, nbest, L), "int32"), ((B, nbest, L), "float32")] if detail else []
+    if device is None:
+        outs = tuple(np.empty(s, d) for s, d in shapes)
+        return outs, [a.ctypes.data_as(fp if a.dtype == np.float32 else capi.ip) for a in outs]
     import torch
-    if labels_out is None:
-        labels_out = torch.empty((B, nbest, L), dtype=torch.int32, device=device)
-    if out_lengths is None:
-        out_lengths = torch.empty((B, nbest), dtype=torch.int32, device=device)
-    if scores is None:
-        scores = torch.empty((B, nbest), dtype=torch.float32, device=device)
-    return labels_out, out_lengths, scores
+    outs = tuple(torch.empty(s, dtype=getattr(torch, d), device=device) if g is None else g
+                 for (s, d), g in zip(shapes, tuple(given) + (None, None)))
+    for a, (_, d) in zip(outs, shapes):
+        assert a.is_cuda and a.is_contiguous() and a.dtype == getattr(torch, d), "outputs: contiguous device tensors, int32 / float32"
+    return outs, [C.c_void_p(a.data_ptr()) for a in outs]
 
 
-def _beam_detail_outputs(device, B, nbest, L):
-    """new label_frames int32 / label_logps float32 tensors [B, nbest, L] of a search with detail"""
-    import torch
-    return (torch.empty((B, nbest, L), dtype=torch.int32, device=device), torch.empty((B, nbest, L), dtype=torch.float32, device=device))
-
-
-def _ctc_beam_opts(lm, frames=None, logps=None):
-    """NntkCtcBeamOptions by reference; frames, logps: addresses or None"""
-    return C.byref(capi.NntkCtcBeamOptions(lm.h if lm is not None else None, frames, logps))
-
-
-def _beam_decode_device(entry, ws_name, lm_arg, probs, input_lengths, blank, beam_width, cutoff_top_n, nbest, labels_out, out_lengths, scores,
-                        workspace, detail=False):
-    """the one-shot search on device tensors through the C entry ``entry``; lm_arg: () for the acoustic entries, else (model handle or
-    None,).  detail: through ``nntk_ctc_beam_decode_opt_device`` instead, lm_arg = (the NgramLm or None,) -> the three and (frames, logps)"""
-    import torch
+def _ctc_beam_decode(on_device, lm_entry, lm, probs, input_lengths, blank, beam_width, cutoff_top_n, nbest, detail,
+                     given=(None, None, None), workspace=None):
+    """The one-shot search in all its forms.  on_device: probs and the outputs are device tensors, else numpy arrays; lm_entry: the
+    caller is one of the ``_lm`` functions, whose model ``lm`` may still be None.  The C entry is the calling function's own:
+    ``nntk_ctc_beam_decode`` + ``_opt`` (NntkCtcBeamOptions) with detail, else ``_lm`` for an ``_lm`` function, + ``_device``."""
+    if not on_device:
+        probs = _f32(probs)
     B, T, Cc = probs.shape
     il, ilp = _ctc_lengths(input_lengths, B)
     L = capi.load()
-    need = getattr(L, ws_name)(B, T, Cc, beam_width, cutoff_top_n)
-    if workspace is None:
-        workspace = torch.empty(need, dtype=torch.float32, device=probs.device)
-    assert workspace.numel() >= need, "workspace: %s(B, T, C, beam_width, cutoff_top_n) floats" % ws_name
-    labels_out, out_lengths, scores = _beam_outputs(probs.device, B, max(nbest, 0), T, labels_out, out_lengths, scores)
+    outs, ptrs = _ctc_beam_arrays(probs.device if on_device else None, B, max(nbest, 0), T, detail, given)
+    lm_h = lm.h if lm is not None else None
     if detail:
-        frames, logps = _beam_detail_outputs(probs.device, B, max(nbest, 0), T)
-        check(L.nntk_ctc_beam_decode_opt_device(_dp(probs), B, T, Cc, ilp, blank, beam_width, cutoff_top_n, nbest,
-                                                _ctc_beam_opts(lm_arg[0], frames.data_ptr(), logps.data_ptr()),
-                                                C.c_void_p(labels_out.data_ptr()), C.c_void_p(out_lengths.data_ptr()), _dp(scores),
-                                                _dp(workspace)), "nntk_ctc_beam_decode_opt_device")
-        return labels_out, out_lengths, scores, frames, logps
-    check(getattr(L, entry)(_dp(probs), B, T, Cc, ilp, blank, beam_width, cutoff_top_n, nbest, *lm_arg, C.c_void_p(labels_out.data_ptr()),
-                            C.c_void_p(out_lengths.data_ptr()), _dp(scores), _dp(workspace)), entry)
-    return labels_out, out_lengths, scores
-
-
-def _beam_decode_host(entry, lm_arg, probs, input_lengths, blank, beam_width, cutoff_top_n, nbest, detail=False):
-    """the host-memory form of the same; lm_arg and detail as above (``nntk_ctc_beam_decode_opt``)"""
-    probs = _f32(probs)
-    B, T, Cc = probs.shape
-    il, ilp = _ctc_lengths(input_lengths, B)
-    nb = max(nbest, 0)
-    out, n, sc = np.empty((B, nb, T), np.int32), np.empty((B, nb), np.int32), np.empty((B, nb), np.float32)
-    if detail:
-        fr, lg = np.empty((B, nb, T), np.int32), np.empty((B, nb, T), np.float32)
-        check(capi.load().nntk_ctc_beam_decode_opt(_p(probs), B, T, Cc, ilp, blank, beam_width, cutoff_top_n, nbest,
-                                                   _ctc_beam_opts(lm_arg[0], fr.ctypes.data, lg.ctypes.data), out.ctypes.data_as(capi.ip),
-                                                   n.ctypes.data_as(capi.ip), _p(sc)), "nntk_ctc_beam_decode_opt")
-        return out, n, sc, fr, lg
-    check(getattr(capi.load(), entry)(_p(probs), B, T, Cc, ilp, blank, beam_width, cutoff_top_n, nbest, *lm_arg, out.ctypes.data_as(capi.ip),
-                                      n.ctypes.data_as(capi.ip), _p(sc)), entry)
-    return out, n, sc
+        form, mid = "_opt", (C.byref(capi.NntkCtcBeamOptions(lm_h, *(C.cast(q, C.c_void_p) for q in ptrs[3:]))),)
+    elif lm_entry:
+        form, mid = "_lm", (lm_h,)
+    else:
+        form, mid = "", ()
+    tail = ()
+    if on_device:
+        import torch
+        ws_name = "nntk_ctc_beam_lm_workspace_floats" if lm_entry else "nntk_ctc_beam_workspace_floats"
+        need = getattr(L, ws_name)(B, T, Cc, beam_width, cutoff_top_n)
+        if workspace is None:
+            workspace = torch.empty(need, dtype=torch.float32, device=probs.device)
+        assert workspace.numel() >= need, "workspace: %s(B, T, C, beam_width, cutoff_top_n) floats" % ws_name
+        tail = (_dp(workspace),)
+    name = "nntk_ctc_beam_decode" + form + ("_device" if on_device else "")
+    check(getattr(L, name)((_dp if on_device else _p)(probs), B, T, Cc, ilp, blank, beam_width, cutoff_top_n, nbest, *mid, *ptrs[:3],
+                           *tail), name)
+    return outs
 
 
 def ctc_beam_decode_device(probs, input_lengths=None, blank=0, beam_width=16, cutoff_top_n=0, nbest=1, labels_out=None, out_lengths=None,
@@ -713,18 +698,13 @@ def ctc_beam_decode_device(probs, input_lengths=None, blank=0, beam_width=16, cu
     labels; lengths [B,nbest] int32, -1 for a slot without a hypothesis; scores [B,nbest] float32 = ln of the prefix probability).
     ``detail=True`` (``nntk_ctc_beam_decode_opt_device``): the same three and (label_frames [B,nbest,T] int32, -1 behind the labels';
     label_logps [B,nbest,T] float32, 0.0 behind them) -- INTEGRATION.md "Label timestamps and confidences"."""
-    if detail:
-        return _beam_decode_device(None, "nntk_ctc_beam_workspace_floats", (None,), probs, input_lengths, blank, beam_width, cutoff_top_n,
-                                   nbest, labels_out, out_lengths, scores, workspace, True)
-    return _beam_decode_device("nntk_ctc_beam_decode_device", "nntk_ctc_beam_workspace_floats", (), probs, input_lengths, blank, beam_width,
-                               cutoff_top_n, nbest, labels_out, out_lengths, scores, workspace)
+    return _ctc_beam_decode(True, False, None, probs, input_lengths, blank, beam_width, cutoff_top_n, nbest, detail, (labels_out, out_lengths, scores),
+                            workspace)
 
 
 def ctc_beam_decode(probs, input_lengths=None, blank=0, beam_width=16, cutoff_top_n=0, nbest=1, detail=False):
     """The host-memory form (``nntk_ctc_beam_decode``, with detail ``nntk_ctc_beam_decode_opt``): probs [B,T,C] numpy array."""
-    if detail:
-        return _beam_decode_host(None, (None,), probs, input_lengths, blank, beam_width, cutoff_top_n, nbest, True)
-    return _beam_decode_host("nntk_ctc_beam_decode", (), probs, input_lengths, blank, beam_width, cutoff_top_n, nbest)
+    return _ctc_beam_decode(False, False, None, probs, input_lengths, blank, beam_width, cutoff_top_n, nbest, detail)
 
 
 class NgramLm:
@@ -850,18 +830,13 @@ def ctc_beam_decode_lm_device(probs, lm, input_lengths=None, blank=0, beam_width
     """``nntk_ctc_beam_decode_lm_device``: ``ctc_beam_decode_device`` with the n-gram model ``lm`` (an NgramLm, or None) fused in;
     scores = ln(acoustic prefix probability x LM factors x end-of-sentence factor).  ``detail=True``: as in ``ctc_beam_decode_device``
     (label_logps stays the acoustic log-probability, never the model's factor)."""
-    if detail:
-        return _beam_decode_device(None, "nntk_ctc_beam_lm_workspace_floats", (lm,), probs, input_lengths, blank, beam_width, cutoff_top_n,
-                                   nbest, labels_out, out_lengths, scores, workspace, True)
-    return _beam_decode_device("nntk_ctc_beam_decode_lm_device", "nntk_ctc_beam_lm_workspace_floats", (lm.h if lm else None,), probs,
-                               input_lengths, blank, beam_width, cutoff_top_n, nbest, labels_out, out_lengths, scores, workspace)
+    return _ctc_beam_decode(True, True, lm, probs, input_lengths, blank, beam_width, cutoff_top_n, nbest, detail,
+                            (labels_out, out_lengths, scores), workspace)
 
 
 def ctc_beam_decode_lm(probs, lm, input_lengths=None, blank=0, beam_width=16, cutoff_top_n=0, nbest=1, detail=False):
     """The host-memory form (``nntk_ctc_beam_decode_lm``, with detail ``nntk_ctc_beam_decode_opt``): probs [B,T,C] numpy array."""
-    if detail:
-        return _beam_decode_host(None, (lm,), probs, input_lengths, blank, beam_width, cutoff_top_n, nbest, True)
-    return _beam_decode_host("nntk_ctc_beam_decode_lm", (lm.h if lm else None,), probs, input_lengths, blank, beam_width, cutoff_top_n, nbest)
+    return _ctc_beam_decode(False, True, lm, probs, input_lengths, blank, beam_width, cutoff_top_n, nbest, detail)
 
 
 class CtcBeamStream:
@@ -878,13 +853,13 @@ class CtcBeamStream:
         self.lm = lm
         self.detail = bool(detail)
         if self.detail:
-            self.h = capi.load().nntk_ctc_beam_stream_create_opt(self.B, self.T, self.C, blank, beam_width, cutoff_top_n, nbest,
-                                                                 self.max_labels, lm.h if lm is not None else None, 1)
-        elif lm is None:
-            self.h = capi.load().nntk_ctc_beam_stream_create(self.B, self.T, self.C, blank, beam_width, cutoff_top_n, nbest, self.max_labels)
+            form, mid = "_opt", (lm.h if lm is not None else None, 1)
+        elif lm is not None:
+            form, mid = "_lm", (lm.h,)
         else:
-            self.h = capi.load().nntk_ctc_beam_stream_create_lm(self.B, self.T, self.C, blank, beam_width, cutoff_top_n, nbest,
-                                                                self.max_labels, lm.h)
+            form, mid = "", ()
+        self.h = getattr(capi.load(), "nntk_ctc_beam_stream_create" + form)(self.B, self.T, self.C, blank, beam_width, cutoff_top_n, nbest,
+                                                                            self.max_labels, *mid)
         if not self.h:
             raise capi.NNTKError("nntk_ctc_beam_stream_create: " + capi.last_error())
 
@@ -897,39 +872,21 @@ class CtcBeamStream:
     def push(self, probs, n_frames, final=None, labels_out=None, out_lengths=None, scores=None):
         """probs [B, max_frames, C] device tensor, n_frames / final host ints per row (a streaming stack's out, cnt, final) ->
         (labels [B, nbest, max_labels] int32, lengths [B, nbest] int32, scores [B, nbest] float32), the rows' current n-best"""
-        assert tuple(probs.shape) == (self.B, self.T, self.C), "probs: [batch, max_frames, C]"
-        nf = _host_ints(n_frames, self.B, "n_frames")
-        f, fptr = self._final(final)
-        labels_out, out_lengths, scores = _beam_outputs(probs.device, self.B, self.nbest, self.max_labels, labels_out, out_lengths, scores)
-        if self.detail:
-            frames, logps = _beam_detail_outputs(probs.device, self.B, self.nbest, self.max_labels)
-            check(capi.load().nntk_ctc_beam_stream_push_opt_device(self.h, _dp(probs), nf.ctypes.data_as(capi.ip), fptr,
-                                                                   C.c_void_p(labels_out.data_ptr()), C.c_void_p(out_lengths.data_ptr()),
-                                                                   _dp(scores), C.c_void_p(frames.data_ptr()), _dp(logps)),
-                  "nntk_ctc_beam_stream_push_opt_device")
-            return labels_out, out_lengths, scores, frames, logps
-        check(capi.load().nntk_ctc_beam_stream_push_device(self.h, _dp(probs), nf.ctypes.data_as(capi.ip), fptr,
-                                                           C.c_void_p(labels_out.data_ptr()), C.c_void_p(out_lengths.data_ptr()),
-                                                           _dp(scores)), "nntk_ctc_beam_stream_push_device")
-        return labels_out, out_lengths, scores
+        return self._push(True, probs, n_frames, final, (labels_out, out_lengths, scores))
 
     def push_host(self, probs, n_frames, final=None):
         """The host-memory form (``nntk_ctc_beam_stream_push``): probs [B, max_frames, C] numpy array."""
-        probs = _f32(probs)
-        assert probs.shape == (self.B, self.T, self.C), "probs: [batch, max_frames, C]"
+        return self._push(False, _f32(probs), n_frames, final)
+
+    def _push(self, on_device, probs, n_frames, final, given=(None, None, None)):
+        """both forms of a push, through ``nntk_ctc_beam_stream_push`` + ``_opt`` on a handle with detail + ``_device``"""
+        assert tuple(probs.shape) == (self.B, self.T, self.C), "probs: [batch, max_frames, C]"
         nf = _host_ints(n_frames, self.B, "n_frames")
         f, fptr = self._final(final)
-        out = np.empty((self.B, self.nbest, self.max_labels), np.int32)
-        n, sc = np.empty((self.B, self.nbest), np.int32), np.empty((self.B, self.nbest), np.float32)
-        if self.detail:
-            fr, lg = np.empty(out.shape, np.int32), np.empty(out.shape, np.float32)
-            check(capi.load().nntk_ctc_beam_stream_push_opt(self.h, _p(probs), nf.ctypes.data_as(capi.ip), fptr, out.ctypes.data_as(capi.ip),
-                                                            n.ctypes.data_as(capi.ip), _p(sc), fr.ctypes.data_as(capi.ip), _p(lg)),
-                  "nntk_ctc_beam_stream_push_opt")
-            return out, n, sc, fr, lg
-        check(capi.load().nntk_ctc_beam_stream_push(self.h, _p(probs), nf.ctypes.data_as(capi.ip), fptr, out.ctypes.data_as(capi.ip),
-                                                    n.ctypes.data_as(capi.ip), _p(sc)), "nntk_ctc_beam_stream_push")
-        return out, n, sc
+        outs, ptrs = _ctc_beam_arrays(probs.device if on_device else None, self.B, self.nbest, self.max_labels, self.detail, given)
+        name = "nntk_ctc_beam_stream_push" + ("_opt" if self.detail else "") + ("_device" if on_device else "")
+        check(getattr(capi.load(), name)(self.h, (_dp if on_device else _p)(probs), nf.ctypes.data_as(capi.ip), fptr, *ptrs), name)
+        return outs
 
     def reset(self, rows):
         """these rows start new streams"""

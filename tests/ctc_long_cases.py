@@ -15,6 +15,7 @@ import functools
 import numpy as np
 
 from ctc_reference import reference, ref_row_scaled, softmax
+from ngram_cases import sparse_trigram
 
 # mirrored from csrc/hip/ctc_beam.hip and csrc/hip/nntk_shim.h; test_ctc_long_premises.py reads them from the source text
 BT_RECORDS = 8192                                   # BEAM_BT_RECORDS
@@ -85,7 +86,6 @@ LM = dict(seed=2, n_bi=8, n_tri=20, arcs0=12, final=True, alpha=0.75, beta=0.25,
 
 
 def lm_table(Cc, blank):
-    from test_gpu_ctc_beam_lm import sparse_trigram
     return sparse_trigram(LM["seed"], Cc, blank, n_bi=LM["n_bi"], n_tri=LM["n_tri"], arcs0=LM["arcs0"], final=LM["final"])
 
 

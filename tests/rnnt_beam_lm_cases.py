@@ -1,6 +1,6 @@
 """The cases of the fused transducer beam search tests (tests/test_gpu_rnnt_beam_lm.py) and their premises, which
 tests/test_rnnt_beam_lm_host.py checks without a device: the acoustic models and frames of tests/rnnt_beam_cases.py, the n-gram tables of
-tests/test_gpu_ctc_beam_lm.py's recipe, the float64 reference (tests/rnnt_beam_reference.py with a model) and its float32 restatement.
+tests/ngram_cases.py's recipe, the float64 reference (tests/rnnt_beam_reference.py with a model) and its float32 restatement.
 A helper, no test.
 
 alpha is a power of two in every case, so that alpha * v + beta is one rounding whatever the host compiler contracts, and beta is a
@@ -12,7 +12,7 @@ import numpy as np
 
 import rnnt_beam_reference as RB
 from rnnt_beam_cases import case as acoustic_case, model as _model, search_kw  # noqa: F401  (search_kw: the host tests take it from here)
-from test_gpu_ctc_beam_lm import _table, dense_bigram, sparse_trigram
+from ngram_cases import table as _table, dense_bigram, sparse_trigram
 
 GAP = 1e-3
 

@@ -33,11 +33,12 @@ def test_the_mirrored_constants_are_the_source_texts():
     assert _define(hip, "BEAM_BT_RECORDS") == K.BT_RECORDS == 8192
     assert _define(shim, "NNTK_CTC_BEAM_MAX_W") == K.MAX_W == 128
     assert _define(shim, "NNTK_CTC_BEAM_MAX_CELLS") == K.MAX_CELLS == 16384
-    # backtrack and commit: the same block of frames, walked from the last one
-    assert hip.count("const int TC = max(1, BEAM_BT_RECORDS / W);") == 2
-    assert hip.count("for (int t1 = Tb; t1 > 0; t1 -= TC) {") == 2
+    # backtrack and commit: the same block of frames, walked from the last one -- one walk, which both kernels call
+    assert hip.count("const int TC = max(1, BEAM_BT_RECORDS / W);") == 1
+    assert hip.count("for (int t1 = Tb; t1 > 0; t1 -= TC) {") == 1
+    assert hip.count("beam_walk_records<DETAIL>(rec, hrow, Tb, W, tid, ") == 2
     # the record: length << 8 | parent rank
-    assert hip.count("rank = r.x & 0xff;") == 2 and "len = hrow[(long)(Tb - 1) * W + rank].x >> 8;" in hip and "const int pos = (r.x >> 8) - 1;" in hip
+    assert hip.count("rank = r.x & 0xff;") == 1 and "len = hrow[(long)(Tb - 1) * W + rank].x >> 8;" in hip and "const int pos = (r.x >> 8) - 1;" in hip
     # the cut kernel: a wavefront per frame, four a workgroup, the grid capped, the rest by stride
     m = re.search(r"long g = \(frames \+ 3\) / 4;\s*if \(g > (\d+)\) g = (\d+);", hip)
     assert m and int(m.group(1)) == int(m.group(2)) == K.CUT_GRID_CAP == 16384

@@ -16,7 +16,8 @@ import numpy as np
 import pytest
 import torch
 
-from ctc_reference import decode as _run, ref_row as _ref_row, reference, softmax as _softmax, tol as _tol
+from ctc_reference import (assert_scores as _assert_scores, ctc_loss64 as _ctc_loss64, decode as _run, ref_row as _ref_row, reference,
+                           softmax as _softmax, tol as _tol)
 from nntoolkitcore_amd import capi, layers as NL
 
 pytestmark = pytest.mark.gpu
@@ -25,14 +26,6 @@ pytestmark = pytest.mark.gpu
 def _reference(p, lens, blank, W, cutoff, nbest):
     """the acoustic search: without the flag of the fused search's end-of-sentence step"""
     return reference(p, lens, blank, W, cutoff, nbest)[:4]
-
-
-def _assert_scores(tag, T, got, ref):
-    fin = np.isfinite(ref)
-    np.testing.assert_array_equal(np.isneginf(got), ~fin, err_msg=tag)
-    err = np.abs(got[fin].astype(np.float64) - ref[fin])
-    print("%s: largest score error %.3g of %.3g allowed" % (tag, err.max(initial=0.0), _tol(T, ref[fin]).min(initial=np.inf)))
-    assert (err <= _tol(T, ref[fin])).all(), tag
 
 
 # name: (seed, B, T, C, W, cutoff, nbest, blank, lengths)
@@ -71,14 +64,6 @@ def test_parity_with_the_float64_reference(gpu, name):
     np.testing.assert_array_equal(got_n, n)
     np.testing.assert_array_equal(got_lab, lab)
     _assert_scores(name, T, got_sc, sc)
-
-
-def _ctc_loss64(p, labels, blank):
-    """float64 CTC loss of one labelling on the row p [T][C], torch on the CPU"""
-    lp = torch.log(torch.from_numpy(p.astype(np.float64)))[:, None, :]
-    tgt = torch.tensor([list(labels) or [0]], dtype=torch.long)
-    loss = torch.nn.functional.ctc_loss(lp, tgt, torch.tensor([p.shape[0]]), torch.tensor([len(labels)]), blank=blank, reduction="none")
-    return float(loss[0])
 
 
 def test_exhaustive_beam_equals_the_ctc_loss(gpu):

@@ -218,16 +218,22 @@ def test_stream_has_the_one_shot_bits_after_every_push(gpu, name, how):
     _against_reference(name + " streamed", got, R.one_shot_case(name)[3], R.one_shot_case(name)[0])
 
 
-def test_stream_cut_at_two_labels(gpu):
+@pytest.mark.parametrize("name", [R.STREAM_CASE, "lm"])
+def test_stream_cut_at_two_labels(gpu, name):
     """max_labels = 2 on rows that grow past it: labels, frames and log-probabilities are cut alike, the length stays true, a move at
-    position 1 applies and one at position 2 is dropped -- in later pushes than the ones that made the labels"""
-    name = R.STREAM_CASE
-    got = _stream_against_one_shot(gpu, name, _frame_by_frame(R.ONE_SHOT[name][8]), 4, max_labels=2)
-    ref = R.one_shot_case(name)[3]
+    position 1 applies and one at position 2 is dropped -- in later pushes than the ones that made the labels.  "lm": the same through
+    the commit's report by slot, on a beam that the end-of-sentence step reorders"""
+    _, B, T, Cc, W, cutoff, nbest, blank, lens, lm_seed, _ = R.ONE_SHOT[name]
+    got = _stream_against_one_shot(gpu, name, _frame_by_frame(lens), 4, max_labels=2)
+    p, _, _, ref = R.one_shot_case(name)
     assert got[0].shape[-1] == 2 and (got[1] > 2).any()
     np.testing.assert_array_equal(got[1], ref["lengths"])
     np.testing.assert_array_equal(got[3], ref["frames"][..., :2])
     np.testing.assert_array_equal(got[0], ref["labels"][..., :2])
+    walk = R.table_and_walk(Cc, blank, lm_seed)[1] if lm_seed is not None else None
+    cut = R.reference(p, lens, blank, W, cutoff, nbest, walk, cap=2)
+    assert cut["reordered"] == (name == "lm") and min(cut["gap"], cut["merge_gap"]) >= R.GAP
+    _against_reference(name + " cut at 2", got, cut, p)
 
 
 def test_final_and_reset_restart_the_frame_count(gpu):

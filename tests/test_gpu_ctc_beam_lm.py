@@ -3,7 +3,7 @@ against a float64 restatement of its semantics, against the acoustic-only call, 
 form against the one-shot call.
 
 Reference: ``ref_row`` of ctc_reference.py -- the float64 prefix beam search (dicts of label tuples, linear space, the same candidate
-cells, merge order and canonical-index tie rule) given the model (``Walk`` below): every entry carries an LM state, an extension is
+cells, merge order and canonical-index tie rule) given the model (``Walk`` of ngram_cases.py): every entry carries an LM state, an extension is
 multiplied by F(state, c) = exp(sum of alpha * backoff_logw along the walk + alpha * arc_logp + beta) (or the unknown-label factor),
 and after the last frame every total is multiplied by E(state), zeros are dropped and the rest are ordered again, ties to the lower
 rank.  The table's float32 inputs are taken as they are; everything else is float64.
@@ -25,114 +25,18 @@ import numpy as np
 import pytest
 import torch
 
-from ctc_reference import (decode as _run_acoustic, drive as _drive, eq as _eq, ref_row as _ref_row, reference as _reference,
-                           softmax as _softmax, tol_lm as _tol)
+from ctc_reference import (assert_scores, ctc_loss64 as _ctc_loss64, decode as _run_acoustic, drive as _drive, eq as _eq,
+                           ref_row as _ref_row, reference as _reference, rounds as _rounds, softmax as _softmax, tol_lm as _tol)
+from ngram_cases import Walk, dense_bigram, sparse_trigram
 from nntoolkitcore_amd import capi, layers as NL
 
 pytestmark = pytest.mark.gpu
 INF = float("inf")
-
-
-# ---- tables ----
-def _table(n_classes, blank, arcs, rng, unk, final):
-    """arcs: {context tuple: sorted labels}, closed under dropping the oldest label -> NgramLm.from_arrays' keyword arguments"""
-    ctx = sorted(arcs, key=lambda c: (len(c), c))
-    sid = {c: i for i, c in enumerate(ctx)}
-    depth = max(len(c) for c in ctx)
-
-    def state_of(hist):
-        hist = hist[len(hist) - depth:] if len(hist) > depth else hist
-        while hist not in sid:
-            hist = hist[1:]
-        return sid[hist]
-    t = dict(n_classes=n_classes, blank=blank, arc_begin=[0], arc_label=[], arc_logp=[], arc_next=[], backoff_state=[], backoff_logw=[],
-             start_state=0, unk_logp=unk)
-    for c in ctx:
-        for a in arcs[c]:
-            t["arc_label"].append(a); t["arc_logp"].append(float(np.log(rng.uniform(0.02, 0.9)))); t["arc_next"].append(state_of(c + (a,)))
-        t["arc_begin"].append(len(t["arc_label"]))
-        t["backoff_state"].append(-1 if not c else state_of(c[1:]))
-        t["backoff_logw"].append(0.0 if not c else float(np.log(rng.uniform(0.2, 0.9))))
-    t["final_logp"] = np.log(rng.uniform(0.05, 0.9, len(ctx))).tolist() if final else None
-    return t
-
-
-def dense_bigram(seed, n_classes, blank, final=False):
-    rng = np.random.default_rng(seed)
-    labels = [c for c in range(n_classes) if c != blank]
-    return _table(n_classes, blank, {c: labels for c in [()] + [(a,) for a in labels]}, rng, float(np.log(0.01)), final)
-
-
-def sparse_trigram(seed, n_classes, blank, n_bi, n_tri, arcs0, unk=float(np.log(0.01)), final=False):
-    """state 0 with arcs0 arcs (those to the n_bi one-label contexts among them), up to n_tri two-label contexts (x, a) that the state
-    (x) reaches, each backing off to (a) where that is a state, else to state 0"""
-    rng = np.random.default_rng(seed)
-    labels = [c for c in range(n_classes) if c != blank]
-    uni = sorted(rng.choice(labels, n_bi, replace=False).tolist())
-    pick = lambda k, must=(): sorted(set(must) | set(rng.choice(labels, k, replace=False).tolist()))
-    arcs = {(): pick(arcs0, uni)}
-    for x in uni:
-        arcs[(x,)] = pick(int(rng.integers(2, max(3, min(len(labels), 40) // 3))))
-    pairs = [(x, a) for x in uni for a in arcs[(x,)]]
-    for q in sorted(rng.choice(len(pairs), min(n_tri, len(pairs)), replace=False).tolist()):
-        arcs[pairs[q]] = pick(int(rng.integers(1, max(2, min(len(labels), 40) // 3))))
-    return _table(n_classes, blank, arcs, rng, unk, final)
-
-
-class Walk:
-    """float64 F, next state, backoffs taken and the unknown-label flag of (state, class), cached; counts what the search met"""
-
-    def __init__(self, t, alpha, beta):
-        self.t, self.a, self.b, self.cache = t, float(np.float32(alpha)), float(np.float32(beta)), {}
-        self.depths, self.unk, self.dead = set(), False, 0
-        f32 = lambda v: np.asarray(v, np.float32).astype(np.float64)
-        self.logp, self.bow, self.unk_logp = f32(t["arc_logp"]), f32(t["backoff_logw"]), float(np.float32(t["unk_logp"]))
-        self.fin = None if t["final_logp"] is None else f32(t["final_logp"])
-        self.lab = np.asarray(t["arc_label"], np.int64)
-
-    def _ln(self, v, beta):
-        return beta if self.a == 0.0 else self.a * v + beta
-
-    def __call__(self, s, c):
-        key = (s, c)
-        if key not in self.cache:
-            t, ln, d, st = self.t, 0.0, 0, s
-            while True:
-                lo, hi = t["arc_begin"][st], t["arc_begin"][st + 1]
-                q = lo + int(np.searchsorted(self.lab[lo:hi], c))
-                if q < hi and self.lab[q] == c:
-                    self.cache[key] = (float(np.exp(ln + self._ln(self.logp[q], self.b))), t["arc_next"][q], d, False)
-                    break
-                if st == 0:
-                    self.cache[key] = (float(np.exp(ln + self._ln(self.unk_logp, self.b))), 0, d, True)
-                    break
-                ln += self._ln(self.bow[st], 0.0)
-                st = t["backoff_state"][st]
-                d += 1
-        f, nx, d, u = self.cache[key]
-        self.depths.add(d)
-        self.unk |= u
-        self.dead += f == 0.0
-        return f, nx
-
-    def final(self, s):
-        return 1.0 if self.fin is None else float(np.exp(self._ln(self.fin[s], 0.0)))
-
-
-def _rounds(T, D):
-    return (4 + 2 * D + 2) * T + 2
+_assert_scores = functools.partial(assert_scores, allow=_tol)                  # (tag, rounds, got, ref)
 
 
 def _run(gpu, p, lm, lens, blank, W, cutoff, nbest):
     return _run_acoustic(gpu, p, lens, blank, W, cutoff, nbest, lm)
-
-
-def _assert_scores(tag, rounds, got, ref):
-    fin = np.isfinite(ref)
-    np.testing.assert_array_equal(np.isneginf(got), ~fin, err_msg=tag)
-    err = np.abs(got[fin].astype(np.float64) - ref[fin])
-    print("%s: largest score error %.3g of %.3g allowed" % (tag, err.max(initial=0.0), _tol(rounds, ref[fin]).min(initial=np.inf)))
-    assert (err <= _tol(rounds, ref[fin])).all(), tag
 
 
 # name: (posterior seed, B, T, C, W, cutoff, nbest, blank, lengths, table, alpha, beta, D)
@@ -222,13 +126,6 @@ def test_the_model_decides(gpu):
     np.testing.assert_array_equal(got[0], a_lab)
     _assert_scores("acoustic", _rounds(T, 1), got[2], a_sc)
     lm.close()
-
-
-def _ctc_loss64(p, labels, blank):
-    lp = torch.log(torch.from_numpy(p.astype(np.float64)))[:, None, :]
-    tgt = torch.tensor([list(labels) or [0]], dtype=torch.long)
-    loss = torch.nn.functional.ctc_loss(lp, tgt, torch.tensor([p.shape[0]]), torch.tensor([len(labels)]), blank=blank, reduction="none")
-    return float(loss[0])
 
 
 def test_exhaustive_beam_equals_the_ctc_loss_plus_the_model_score(gpu):

@@ -41,10 +41,8 @@ import numpy as np
 import pytest
 
 import ctc_long_cases as K
-from ctc_reference import decode, drive, eq, tol, tol_lm
+from ctc_reference import assert_scores as _assert_scores, ctc_loss64 as _ctc_loss64, decode, drive, eq, rounds as _rounds, tol, tol_lm
 from nntoolkitcore_amd import layers as NL
-from test_gpu_ctc_beam import _assert_scores, _ctc_loss64
-from test_gpu_ctc_beam_lm import _rounds
 
 pytestmark = pytest.mark.gpu
 
