@@ -1115,6 +1115,46 @@ int nntk_rnnt_joint_device(const float *d_enc, const float *d_pred, int batch, i
 int nntk_rnnt_joint_backward_device(const float *d_out_fwd, const float *d_dout, int batch, int T, int U1, int J, int activation,
                                     float *d_denc, float *d_dpred);
 
+/* ---- RNN-Transducer: token-and-duration loss (Xu et al., 2023; csrc/hip/rnnt_tdt.hip; INTEGRATION.md "RNN-Transducer: token-and-duration
+ *      loss") ----
+ *   d_logits [batch][T][max_label_len + 1][V + n_durations]: UNNORMALISED scores; columns 0 .. V-1 the token head (blank one of them),
+ *     columns V .. V+n_durations-1 the duration head, column V + i the score of durations[i].  Each head has its own softmax, both fused
+ *     into the call: p_tok(v) = exp(x_v - lse_tok - sigma), p_dur(i) = exp(x_{V+i} - lse_dur).  sigma >= 0 is the paper's logit
+ *     under-normalisation; 0 is a no-op.
+ *   durations [n_durations]: HOST memory, strictly ascending, none negative, at least one positive.  With d_i = durations[i],
+ *     alpha(0, 0) = 1 and
+ *       alpha(t, u) = sum over d_i > 0, t - d_i >= 0 of alpha(t - d_i, u)     p_tok(blank | t - d_i, u)     p_dur(i | t - d_i, u)
+ *                   + sum over t - d_i >= 0, u >= 1  of alpha(t - d_i, u - 1) p_tok(y_u   | t - d_i, u - 1) p_dur(i | t - d_i, u - 1)
+ *       P_b = sum over 0 < d_i <= T_b of alpha(T_b - d_i, U_b) p_tok(blank | T_b - d_i, U_b) p_dur(i | T_b - d_i, U_b)
+ *     A blank never takes duration 0; a path ends with a blank that lands exactly on T_b; a jump past T_b, or a label that lands on
+ *     T_b, carries no mass.  beta is the mirror image, beta(T_b, U_b) = 1.  With durations = {1} a label advances a frame: that is not
+ *     the loss of nntk_rnnt_loss_device.
+ *   input_lengths / labels / label_lengths, the shape and the pointers: exactly the checks of nntk_rnnt_loss_device, made before anything
+ *     is enqueued.  Refused as well: n_durations outside [1, 8]; durations not strictly ascending, negative, none positive, or above 16;
+ *     sigma negative or not finite; d_dlogits overlapping d_logits; the two limits below.
+ *   d_loss_rows [batch]: -log P_b.  +inf where no path exists, which happens on finite scores: durations {0, 2} cannot reach an odd
+ *     T_b, {1, 2} cannot emit more labels than there are frames.  The duration probabilities carry an exponent of their own like the
+ *     emissions: a duration head hundreds of nats apart does not become a zero.
+ *   d_dlogits or NULL: the gradient of sum_b loss_b with respect to all V + n_durations scores of a cell; with occ = alpha beta / P,
+ *       g[v]     = occ exp(x_v - lse_tok)     - [v = blank] F_blank - [v = y_{u+1}] F_label
+ *       g[V + i] = occ exp(x_{V+i} - lse_dur) - F_dur(i)
+ *     F_blank / F_label the cell's outgoing flow through blank / label moves, F_dur(i) through duration i (blank and label together), all
+ *     over P, the terminal move included.  Every element is written: exact zeros for t >= T_b or u > U_b and for a row with P = 0.
+ *   d_workspace: nntk_rnnt_tdt_workspace_floats(batch, T, max_label_len, n_durations, want_grad) floats, 16-byte aligned: 16 + 8
+ *     n_durations bytes per cell, 32 more with a gradient, plus 4 (4 + max_label_len) bytes per row and 16.
+ * Limits: (Dmax + 2) (max_label_len + 1) 16 bytes <= 160 KiB, Dmax the largest duration -- the lattice's ring of diagonals in one
+ * workgroup's LDS: max_label_len <= 1705 at Dmax = 4, 567 at Dmax = 16; T + max_label_len <= 32768, half of the classic loss's bound
+ * because a move multiplies two emissions.  Deterministic: no atomics, a cell's terms summed in one order (ascending i, blank before
+ * label), the same bits on every call, the same loss bits with and without a gradient.  The joiner serves unchanged; the projection on
+ * top is a Dense of width V + n_durations.  Decoding with durations is not in the library yet. */
+size_t nntk_rnnt_tdt_workspace_floats(int batch, int T, int max_label_len, int n_durations, int want_grad);
+int nntk_rnnt_tdt_loss_device(const float *d_logits, int batch, int T, int V, const int *durations, int n_durations,
+                              const int *input_lengths, const int *labels, const int *label_lengths, int max_label_len, int blank,
+                              float sigma, float *d_loss_rows, float *d_dlogits, float *d_workspace);
+int nntk_rnnt_tdt_loss(const float *logits, int batch, int T, int V, const int *durations, int n_durations, const int *input_lengths,
+                       const int *labels, const int *label_lengths, int max_label_len, int blank, float sigma, float *loss_rows,
+                       float *dlogits);
+
 /* ---- RNN-Transducer: fused training loss (csrc/hip/rnnt_fused.hip; INTEGRATION.md "RNN-Transducer: fused training loss") ----
  * Joiner, vocabulary projection and loss in one call: with logits[b][t][u] = act(d_enc[b][t] + d_pred[b][u]) W + b, d_loss_rows[b] is
  * what nntk_rnnt_loss_device defines on those logits -- which are never stored, and neither is their gradient.

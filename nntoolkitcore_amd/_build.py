@@ -14,7 +14,9 @@ OBJ = os.path.join(PKG, "lib", "obj")
 LIB = os.path.join(PKG, "lib", "libnntoolkitcore_hip.so")
 
 HOST_SRC = ["runtime.c", "activation.c", "conv_1d.c", "recurrent.c", "dense.c", "spectrogram.c", "mel.c", "train.c", "ctc.c", "ngram_lm.c", "rnnt.c", "rnnt_decode.c", "rnnt_pred.c", "metrics.c"]
-HIP_SRC = ["runtime.hip", "conv1d.hip", "conv1d_s2.hip", "conv1d_flatk.hip", "recurrent.hip", "recurrent_rr.hip", "recurrent_fk.hip", "frag3.hip", "spectrogram.hip", "dist.hip", "conv1d_grad.hip", "train.hip", "ctc.hip", "ctc_beam.hip", "ctc_align.hip", "optim.hip", "bd_train.hip", "rnnt.hip", "rnnt_decode.hip", "rnnt_beam.hip", "rnnt_fused.hip", "rnnt_align.hip", "rnnt_pred.hip", "rnnt_pruned.hip", "edit_distance.hip"]
+HIP_SRC = ["runtime.hip", "conv1d.hip", "conv1d_s2.hip", "conv1d_flatk.hip", "recurrent.hip", "recurrent_rr.hip", "recurrent_fk.hip", "frag3.hip", "spectrogram.hip", "dist.hip", "conv1d_grad.hip", "train.hip", "ctc.hip", "ctc_beam.hip", "ctc_align.hip", "optim.hip", "bd_train.hip", "rnnt.hip", "rnnt_decode.hip", "rnnt_beam.hip", "rnnt_fused.hip", "rnnt_align.hip", "rnnt_pred.hip", "rnnt_pruned.hip", "edit_distance.hip", "rnnt_tdt.hip"]
+# flags of single units, after the common ones: the units written since keep the compiler from forming packed f32 operations
+HIP_UNIT_FLAGS = {"rnnt_tdt.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = "gfx950"
 
@@ -76,7 +78,7 @@ def build(force=False, verbose=False):
         if force or _newer([src] + headers, obj):
             jobs.append([HIPCC, "-O3", "--offload-arch=" + ARCH, "-fPIC", "-std=c++17", "-Wall",
                          "-Wno-unused-function"] + os.environ.get("NNTK_EXTRA_HIPFLAGS", "").split() +
-                        ["-c", src, "-o", obj])
+                        HIP_UNIT_FLAGS.get(f, []) + ["-c", src, "-o", obj])
     # the identity of the sources this library is built from, embedded so that a consumer (bench.py's roofline.traffic gate) asks the
     # LOADED binary, not the source tree: a stale .so next to edited sources must not borrow the new sources' profile
     bid_src = os.path.join(OBJ, "build_id.c")

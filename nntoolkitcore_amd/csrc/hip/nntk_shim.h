@@ -227,6 +227,24 @@ int nntk_shim_rnnt_loss(const float *d_logits, int B, int T, int V, const int *h
 int nntk_shim_rnnt_joint(const float *d_enc, const float *d_pred, int B, int T, int U1, int J, int kind, float *d_out);
 int nntk_shim_rnnt_joint_backward(const float *d_out_fwd, const float *d_dout, int B, int T, int U1, int J, int kind, float *d_denc,
                                   float *d_dpred);
+/* ---- the token-and-duration transducer (rnnt_tdt.hip): loss rows and the gradient with respect to the unnormalised scores
+ *      [B][T][max_label_len + 1][V + D], D duration columns after the V token columns.  h_durations [D] and the int arrays are HOST
+ *      memory, already checked by the caller (rnnt.c), never NULL; d_dlogits NULL = loss only; the tensors and d_ws 16-byte aligned,
+ *      nntk_shim_rnnt_tdt_workspace_floats words.  The limits, each derived:
+ *      - a wavefront's first 8 lanes hold the duration head, and a cell's up to 2 D terms live in registers: D <= 8;
+ *      - the lattice keeps the last Dmax + 1 diagonals in a ring of Dmax + 2 slots of max_label_len + 1 cells, 16 bytes each, in one
+ *        workgroup's LDS (160 KiB on gfx950): (Dmax + 2) (max_label_len + 1) 16 <= NNTK_RNNT_TDT_LDS_BYTES.  Dmax <= 16 leaves
+ *        max_label_len <= 567 at the largest duration and 1705 at Dmax = 4;
+ *      - a move multiplies two emissions, each >= 2^-4000, and a path has at most T + max_label_len moves: their exponents sum inside
+ *        2^28 for T + max_label_len <= 32768 (8002 * 32768 < 2^28, the 2 for the products' normalisation) ---- */
+#define NNTK_RNNT_TDT_MAX_DURATIONS 8
+#define NNTK_RNNT_TDT_MAX_DURATION 16
+#define NNTK_RNNT_TDT_LDS_BYTES (160 * 1024)
+#define NNTK_RNNT_TDT_MAX_DIAGONALS 32768
+size_t nntk_shim_rnnt_tdt_workspace_floats(int batch, int T, int max_label_len, int n_durations, int want_grad);
+int nntk_shim_rnnt_tdt_loss(const float *d_logits, int B, int T, int V, const int *h_durations, int n_durations, const int *h_input_lengths,
+                            const int *h_labels, const int *h_label_lengths, int max_label_len, int blank, float sigma, float *d_loss_rows,
+                            float *d_dlogits, float *d_ws);
 /* ---- the fused transducer training loss (rnnt_fused.hip): joiner, vocabulary projection and loss from enc [B][T][J], pred [B][U1][J] and
  *      the Dense block W [J,V] | b [V]; the three gradient pointers all NULL = loss only.  Host int arrays as for nntk_shim_rnnt_loss,
  *      already checked by the caller (rnnt.c).  The limits: a tile's 32 rows of z (J floats each) and a group of g columns share one

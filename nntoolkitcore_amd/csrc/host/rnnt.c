@@ -124,6 +124,77 @@ int nntk_rnnt_loss(const float *logits, int batch, int T, int V, const int *inpu
     return dlogits ? nntk_shim_download(dlogits, d_g, n * sizeof(float)) : 0;
 }
 
+/* ---- the token-and-duration transducer (csrc/hip/rnnt_tdt.hip): the checks of the classic loss, then the durations, sigma and the
+ *      limits of the ring lattice (nntk_shim.h derives them) ---- */
+static int tdt_check(const char *who, int batch, int T, int V, const int *durations, int n_durations, const int *input_lengths,
+                     const int *labels, const int *label_lengths, int max_label_len, int blank, float sigma) {
+    if (rnnt_check(who, batch, T, V, input_lengths, labels, label_lengths, max_label_len, blank)) return -1;
+    if (n_durations < 1 || n_durations > NNTK_RNNT_TDT_MAX_DURATIONS)
+        return rnnt_fail(who, "n_durations %d is outside [1, %d]", n_durations, NNTK_RNNT_TDT_MAX_DURATIONS, 0);
+    if (!durations) return rnnt_fail(who, "NULL durations", 0, 0, 0);
+    for (int i = 0; i < n_durations; ++i) {
+        if (durations[i] < 0) return rnnt_fail(who, "durations[%d] = %d is negative", i, durations[i], 0);
+        if (i > 0 && durations[i] <= durations[i - 1])
+            return rnnt_fail(who, "durations[%d] = %d after %d: the durations are strictly ascending", i, durations[i], durations[i - 1]);
+    }
+    const int dmax = durations[n_durations - 1];
+    if (dmax < 1) return rnnt_fail(who, "no positive duration: a blank never takes duration 0, so no path would end", 0, 0, 0);
+    if (dmax > NNTK_RNNT_TDT_MAX_DURATION) return rnnt_fail(who, "the largest duration %d is more than %d", dmax, NNTK_RNNT_TDT_MAX_DURATION, 0);
+    if (!(sigma >= 0.0f && sigma <= 3.0e38f)) return rnnt_fail(who, "sigma is negative or not finite", 0, 0, 0);
+    if (((size_t)dmax + 2) * ((size_t)max_label_len + 1) * 16 > NNTK_RNNT_TDT_LDS_BYTES)
+        return rnnt_fail(who, "max_label_len %d with the largest duration %d: %d diagonals of the lattice are beyond one workgroup's LDS",
+                         max_label_len, dmax, dmax + 2);
+    if ((long long)T + max_label_len > NNTK_RNNT_TDT_MAX_DIAGONALS)
+        return rnnt_fail(who, "T + max_label_len = %d is more than %d lattice diagonals of two emissions a move", T + max_label_len,
+                         NNTK_RNNT_TDT_MAX_DIAGONALS, 0);
+    return 0;
+}
+
+size_t nntk_rnnt_tdt_workspace_floats(int batch, int T, int max_label_len, int n_durations, int want_grad) {
+    return nntk_shim_rnnt_tdt_workspace_floats(batch, T, max_label_len, n_durations, want_grad != 0);
+}
+
+int nntk_rnnt_tdt_loss_device(const float *d_logits, int batch, int T, int V, const int *durations, int n_durations,
+                              const int *input_lengths, const int *labels, const int *label_lengths, int max_label_len, int blank,
+                              float sigma, float *d_loss_rows, float *d_dlogits, float *d_workspace) {
+    static const char who[] = "nntk_rnnt_tdt_loss_device";
+    nntk_shim_clear_error();
+    if (tdt_check(who, batch, T, V, durations, n_durations, input_lengths, labels, label_lengths, max_label_len, blank, sigma)) return -1;
+    if (batch == 0) return 0;
+    if (rnnt_check_ptr(who, "d_logits", d_logits, 16) || rnnt_check_ptr(who, "d_loss_rows", d_loss_rows, 4) ||
+        rnnt_check_ptr(who, "d_workspace", d_workspace, 16) || (d_dlogits && rnnt_check_ptr(who, "d_dlogits", d_dlogits, 16))) return -1;
+    const size_t bytes = (size_t)batch * T * (max_label_len + 1) * ((size_t)V + n_durations) * sizeof(float);
+    const rnnt_span sp[] = {{"d_dlogits", (uintptr_t)d_dlogits, bytes}, {"d_logits", (uintptr_t)d_logits, bytes}};
+    if (rnnt_overlap(who, sp, 1, 2)) return -1;
+    int *len = rnnt_lengths(input_lengths, batch, T);
+    int rc = len ? nntk_shim_rnnt_tdt_loss(d_logits, batch, T, V, durations, n_durations, len, labels, label_lengths, max_label_len, blank,
+                                           sigma, d_loss_rows, d_dlogits, d_workspace) : -1;
+    free(len);
+    return rc;
+}
+
+int nntk_rnnt_tdt_loss(const float *logits, int batch, int T, int V, const int *durations, int n_durations, const int *input_lengths,
+                       const int *labels, const int *label_lengths, int max_label_len, int blank, float sigma, float *loss_rows,
+                       float *dlogits) {
+    static const char who[] = "nntk_rnnt_tdt_loss";
+    nntk_shim_clear_error();
+    if (tdt_check(who, batch, T, V, durations, n_durations, input_lengths, labels, label_lengths, max_label_len, blank, sigma)) return -1;
+    if (batch == 0) return 0;
+    if (rnnt_check_ptr(who, "logits", logits, 4) || rnnt_check_ptr(who, "loss_rows", loss_rows, 4) ||
+        (dlogits && rnnt_check_ptr(who, "dlogits", dlogits, 4))) return -1;
+    const size_t n = (size_t)batch * T * (max_label_len + 1) * ((size_t)V + n_durations), nu = (n + 3) & ~(size_t)3;
+    float *d_x = nntk_devbuf_reserve(&t_a, nu + (size_t)batch + 4);
+    float *d_g = dlogits ? nntk_devbuf_reserve(&t_b, n + 4) : NULL;
+    float *d_ws = nntk_devbuf_reserve(&t_c, nntk_shim_rnnt_tdt_workspace_floats(batch, T, max_label_len, n_durations, dlogits != NULL));
+    if (!d_x || (dlogits && !d_g) || !d_ws) return -1;
+    float *d_loss = d_x + nu;
+    if (nntk_shim_upload(d_x, logits, n * sizeof(float))) return -1;
+    if (nntk_rnnt_tdt_loss_device(d_x, batch, T, V, durations, n_durations, input_lengths, labels, label_lengths, max_label_len, blank, sigma,
+                                  d_loss, d_g, d_ws)) return -1;
+    if (nntk_shim_download(loss_rows, d_loss, (size_t)batch * sizeof(float))) return -1;
+    return dlogits ? nntk_shim_download(dlogits, d_g, n * sizeof(float)) : 0;
+}
+
 /* ---- the joiner ---- */
 static int joint_check(const char *who, int batch, int T, int U1, int J, int activation) {
     if (batch < 0 || T < 0 || U1 < 0) return rnnt_fail(who, "batch %d, T %d, U1 %d: none may be negative", batch, T, U1);

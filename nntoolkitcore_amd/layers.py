@@ -1114,6 +1114,44 @@ def rnnt_loss(logits, labels, label_lengths=None, input_lengths=None, blank=0, w
     return loss, g
 
 
+def rnnt_tdt_loss_device(logits, labels, durations, label_lengths=None, input_lengths=None, blank=0, sigma=0.0, want_grad=True, loss=None,
+                         dlogits=None, workspace=None):
+    """``nntk_rnnt_tdt_loss_device``, the token-and-duration transducer: logits [B,T,U1,V + D] device tensor of UNNORMALISED scores, the
+    D = len(durations) duration scores after the V token scores; durations: ascending host ints, e.g. [0, 1, 2, 3, 4]; sigma: the logit
+    under-normalisation of the token head.  labels as for ``rnnt_loss_device``.  Returns (loss rows [B], d loss / d logits or None)."""
+    import torch
+    dur = np.ascontiguousarray(np.asarray(durations, dtype=np.int32)).reshape(-1)
+    B, T, U1, W = logits.shape
+    V, D = W - dur.shape[0], dur.shape[0]
+    lab, ll = _rnnt_labels(labels, label_lengths, B, U1 - 1)
+    il, ilp = _ctc_lengths(input_lengths, B)
+    workspace = _rnnt_workspace(workspace, logits.device, "nntk_rnnt_tdt_workspace_floats", B, T, U1 - 1, D, int(want_grad))
+    if loss is None:
+        loss = torch.empty(B, dtype=torch.float32, device=logits.device)
+    if want_grad and dlogits is None:
+        dlogits = torch.empty_like(logits)
+    check(capi.load().nntk_rnnt_tdt_loss_device(_dp(logits), B, T, V, dur.ctypes.data_as(capi.ip), D, ilp, lab.ctypes.data_as(capi.ip),
+                                                ll.ctypes.data_as(capi.ip), U1 - 1, blank, float(sigma), _dp(loss),
+                                                _dp(dlogits) if want_grad else None, _dp(workspace)), "nntk_rnnt_tdt_loss_device")
+    return loss, (dlogits if want_grad else None)
+
+
+def rnnt_tdt_loss(logits, labels, durations, label_lengths=None, input_lengths=None, blank=0, sigma=0.0, want_grad=True):
+    """The host-memory form (``nntk_rnnt_tdt_loss``): logits [B,T,U1,V + D] numpy array."""
+    logits = _f32(logits)
+    dur = np.ascontiguousarray(np.asarray(durations, dtype=np.int32)).reshape(-1)
+    B, T, U1, W = logits.shape
+    V, D = W - dur.shape[0], dur.shape[0]
+    lab, ll = _rnnt_labels(labels, label_lengths, B, U1 - 1)
+    il, ilp = _ctc_lengths(input_lengths, B)
+    loss = np.empty(B, np.float32)
+    g = np.empty_like(logits) if want_grad else None
+    check(capi.load().nntk_rnnt_tdt_loss(_p(logits), B, T, V, dur.ctypes.data_as(capi.ip), D, ilp, lab.ctypes.data_as(capi.ip),
+                                         ll.ctypes.data_as(capi.ip), U1 - 1, blank, float(sigma), _p(loss), _p(g) if want_grad else None),
+          "nntk_rnnt_tdt_loss")
+    return loss, g
+
+
 def rnnt_joint_device(enc, pred, activation=ACT_TANH, out=None):
     """``nntk_rnnt_joint_device``: enc [B,T,J], pred [B,U1,J] device tensors -> out [B,T,U1,J] = act(enc[b,t] + pred[b,u])"""
     B, T, J = enc.shape
