@@ -1146,7 +1146,8 @@ int nntk_rnnt_joint_backward_device(const float *d_out_fwd, const float *d_dout,
  * workgroup's LDS: max_label_len <= 1705 at Dmax = 4, 567 at Dmax = 16; T + max_label_len <= 32768, half of the classic loss's bound
  * because a move multiplies two emissions.  Deterministic: no atomics, a cell's terms summed in one order (ascending i, blank before
  * label), the same bits on every call, the same loss bits with and without a gradient.  The joiner serves unchanged; the projection on
- * top is a Dense of width V + n_durations.  Decoding with durations is not in the library yet. */
+ * top is a Dense of width V + n_durations.  Decoding such a model: nntk_rnnt_tdt_greedy_decode_device below (greedy, one-shot and
+ * streamed); beam search with durations is not in the library. */
 size_t nntk_rnnt_tdt_workspace_floats(int batch, int T, int max_label_len, int n_durations, int want_grad);
 int nntk_rnnt_tdt_loss_device(const float *d_logits, int batch, int T, int V, const int *durations, int n_durations,
                               const int *input_lengths, const int *labels, const int *label_lengths, int max_label_len, int blank,
@@ -1334,6 +1335,40 @@ int nntk_rnnt_greedy_decode_device(NntkRnntDecoder d, NntkRnntDecodeState state,
                                    int max_labels, int *d_labels_out, int *d_label_frames, int *d_out_lengths, float *d_scores);
 int nntk_rnnt_greedy_decode(NntkRnntDecoder d, NntkRnntDecodeState state, const float *enc, int batch, int T, const int *n_frames,
                             int max_labels, int *labels_out, int *label_frames, int *out_lengths, float *scores);
+
+/* ---- RNN-Transducer: token-and-duration greedy decoding (csrc/hip/rnnt_tdt_decode.hip; INTEGRATION.md "RNN-Transducer:
+ *      token-and-duration greedy decoding") ----
+ * Greedy search for a model trained against nntk_rnnt_tdt_loss_device: the greedy decoder's model with a vocabulary Dense of width
+ * V + D, d_out = W [J, V + D] | b [V + D], columns V .. V+D-1 the duration head; cfg.V stays the token count.  durations [n_durations]
+ * is HOST memory under the loss's rules (n_durations in [1, 8], strictly ascending, none negative, at least one positive, none above
+ * 16), checked before anything is allocated.  The handle is an NntkRnntDecoder: load_weights_device, destroy and
+ * nntk_rnnt_decode_state_create / _reset / _destroy work on it (its state is one int per row wider: the frames still owed).
+ * Per row b with n = n_frames[b]: (h, c) = 0, one LSTM step on embed[blank], g = proj(h); t = 0, s = 0; while t < n and the row holds
+ * fewer than max_labels labels: x = act(enc[b][t] + g) W_out + b_out;
+ *   k = argmax x[0..V) (ties: the lowest index), lp_tok = x[k] - logsumexp(x[0..V));
+ *   i = argmax x[V..V+D) (ties: the lowest index), for k == blank over the i with durations[i] > 0 only (a blank never takes duration
+ *   0, as in the loss); lp_dur = x[V + i] - logsumexp(x[V..V+D)), the normaliser over all D either way; score += lp_tok + lp_dur
+ *   (the loss at sigma = 0: the greedy path is a path of the loss's lattice);
+ *   k == blank: t += durations[i], s = 0;
+ *   else label k is appended with frame t and duration durations[i], an LSTM step on embed[k], g = proj(h); durations[i] > 0:
+ *   t += durations[i], s = 0; else s += 1, and when s == max_symbols_per_frame: t += 1, s = 0 (unscored, the recorded duration stays 0).
+ * A jump past n ends the row; with a state the frames beyond the chunk are owed: the next pushes skip them (a push with n_frames[b] <=
+ * owed only pays and decides nothing).  Frames at or beyond n and frames jumped over are never read and may hold NaN.
+ *   d_labels_out, d_label_frames (or NULL), d_label_durations (or NULL) [batch][max_labels]: then -1; d_out_lengths [batch];
+ *   d_scores [batch] or NULL, the score carried in double and rounded on output.  n_frames 0: length 0, score 0.
+ * Any split of a row's frames into pushes gives the one-shot call's labels, frames, durations, lengths and score bits.  The checks
+ * are those of nntk_rnnt_greedy_decode_device, with d_label_durations among the outputs that may not overlap, and V + D must fit
+ * the kernel's LDS with max(4H, V + D) in V's place.  Refused on the host, nothing written: this call on a handle of
+ * nntk_rnnt_decoder_create; nntk_rnnt_greedy_decode*, and every nntk_rnnt_beam_* decode, state create and size query (0), on a
+ * handle of nntk_rnnt_tdt_decoder_create.  Deterministic as the greedy call: a row's bits do not depend on the batch, its position,
+ * the T padding or how many rows share a workgroup. */
+NntkRnntDecoder nntk_rnnt_tdt_decoder_create(NntkRnntDecoderConfig cfg, const int *durations, int n_durations, const float *d_embed,
+                                             const float *d_lstm, const float *d_pred_proj, const float *d_out);
+int nntk_rnnt_tdt_greedy_decode_device(NntkRnntDecoder d, NntkRnntDecodeState state, const float *d_enc, int batch, int T,
+                                       const int *n_frames, int max_labels, int *d_labels_out, int *d_label_frames, int *d_label_durations,
+                                       int *d_out_lengths, float *d_scores);
+int nntk_rnnt_tdt_greedy_decode(NntkRnntDecoder d, NntkRnntDecodeState state, const float *enc, int batch, int T, const int *n_frames,
+                                int max_labels, int *labels_out, int *label_frames, int *label_durations, int *out_lengths, float *scores);
 
 /* ---- RNN-Transducer: beam search (csrc/hip/rnnt_beam.hip; INTEGRATION.md "RNN-Transducer: beam search") ----
  * The model, the weight blocks, the decoder handle and max_symbols_per_frame (S below) are those of greedy decoding; W = beam_width.

@@ -311,6 +311,21 @@ int nntk_shim_rnnt_dec_reset(int *d_st_i, const int *d_rows, int n_rows);      /
  * row from the start.  d_frames, d_scores may be NULL. */
 int nntk_shim_rnnt_greedy(const nntk_shim_rnnt_dec *m, const float *d_enc, int batch, int T, const int *h_n_frames, int max_labels,
                           float *d_st_f, double *d_st_score, int *d_st_i, int *d_labels, int *d_frames, int *d_lengths, float *d_scores);
+/* ---- token-and-duration greedy decoding (rnnt_tdt_decode.hip) on the greedy decoder's blocks, d_out [J][V + D] | b [V + D].  The
+ *      limits are the classic ones with V + D in V's place in the LDS: V <= NNTK_RNNT_DEC_MAX_V tokens, D <= NNTK_RNNT_TDT_MAX_DURATIONS
+ *      (the duration head is reduced serially by one lane per row, and the table travels by value), so a row's max(4H, V + D) buffer is
+ *      at most 8200 floats and the R = 1 LDS 49 KiB at the limits, inside the 152 KiB the kernels allow themselves; the launcher checks
+ *      it all the same.  The durations (checked by the caller: rnnt_decode.c) and the mask of the positive ones ride in the kernel
+ *      arguments.  The state is the classic one plus d_st_owed [batch]: the frames a row's last jump went past its chunk's end, read
+ *      only where the row has started. ---- */
+typedef struct {
+    int n, pos_mask;                            /* bit i of pos_mask: dur[i] > 0 */
+    int dur[NNTK_RNNT_TDT_MAX_DURATIONS];
+} nntk_shim_rnnt_tdt_durs;
+int nntk_shim_rnnt_tdt_dec_rows_per_group(int batch, int H, int J, int V, int D);
+int nntk_shim_rnnt_tdt_greedy(const nntk_shim_rnnt_dec *m, const nntk_shim_rnnt_tdt_durs *du, const float *d_enc, int batch, int T,
+                              const int *h_n_frames, int max_labels, float *d_st_f, double *d_st_score, int *d_st_i, int *d_st_owed,
+                              int *d_labels, int *d_frames, int *d_durations, int *d_lengths, float *d_scores);
 /* ---- transducer beam search (rnnt_beam.hip) on the greedy decoder's blocks.  One workgroup runs a row's whole search; the hypotheses
  *      of a depth share passes over the matrices in groups of NNTK_RNNT_DEC_GROUP where the group's LDS fits, else one by one
  *      (nntk_shim_rnnt_beam_group; nntk_shim_rnnt_beam_set_group(1 or NNTK_RNNT_DEC_GROUP) pins it for tests and timing, 0 = automatic;

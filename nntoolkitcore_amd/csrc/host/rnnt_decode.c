@@ -1,6 +1,7 @@
 /*
  * rnnt_decode.c -- host layer of RNN-Transducer decoding: the decoder handle with its own device copy of the weights; greedy search
- * (csrc/hip/rnnt_decode.hip) and, below it, beam search (csrc/hip/rnnt_beam.hip), each with the per-row state of a stream and the
+ * (csrc/hip/rnnt_decode.hip), its token-and-duration form (csrc/hip/rnnt_tdt_decode.hip: the same handle and state, created with a
+ * duration table; each decode call refuses the other kind's handle) and, below them, beam search (csrc/hip/rnnt_beam.hip), each with the per-row state of a stream and the
  * decode call in its device-pointer and host-pointer forms; the beam search's plain, _lm and _opt entries share one body a form and the
  * workspace of nntk_shim_rnnt_beam_workspace_floats.  Every argument is checked here, before anything is allocated, uploaded or
  * enqueued: a refusal needs no device and writes nothing.
@@ -18,6 +19,7 @@
 struct NntkRnntDecoderStruct {
     NntkRnntDecoderConfig cfg;
     float *d_table, *d_U, *d_proj, *d_out;      /* the decoder's own blocks (d_proj NULL: identity) */
+    nntk_shim_rnnt_tdt_durs du;                 /* du.n > 0: a token-and-duration decoder, d_out [J][V + du.n] | b [V + du.n] */
 };
 
 struct NntkRnntDecodeStateStruct {
@@ -25,7 +27,7 @@ struct NntkRnntDecodeStateStruct {
     int batch;
     float *d_f;                                 /* [batch][2H + J] */
     double *d_score;                            /* [batch] */
-    int *d_i;                                   /* [batch][4], then [batch]: the rows of a reset */
+    int *d_i;                                   /* [batch][4], then [batch]: the rows of a reset; a TDT decoder's: then [batch] frames owed */
 };
 
 static int dec_fail(const char *who, const char *fmt, long a, long b, long c) {
@@ -73,28 +75,62 @@ static int dec_load(NntkRnntDecoder d, const float *d_embed, const float *d_lstm
     if (nntk_shim_rnnt_dec_table(d_embed, d_lstm, c->V, c->E, c->H, d->d_table)) return -1;
     if (nntk_shim_copy_d2d(d->d_U, d_lstm + (size_t)c->E * G, (size_t)c->H * G * sizeof(float))) return -1;
     if (d_pred_proj && nntk_shim_copy_d2d(d->d_proj, d_pred_proj, ((size_t)c->H + 1) * c->J * sizeof(float))) return -1;
-    if (nntk_shim_copy_d2d(d->d_out, d_out, ((size_t)c->J + 1) * c->V * sizeof(float))) return -1;
+    if (nntk_shim_copy_d2d(d->d_out, d_out, ((size_t)c->J + 1) * (c->V + d->du.n) * sizeof(float))) return -1;
     return nntk_shim_synchronize();             /* the caller's blocks are free for reuse on return */
 }
 
-NntkRnntDecoder nntk_rnnt_decoder_create(NntkRnntDecoderConfig cfg, const float *d_embed, const float *d_lstm, const float *d_pred_proj,
-                                         const float *d_out) {
-    static const char who[] = "nntk_rnnt_decoder_create";
-    nntk_shim_clear_error();
+/* the loss's rules (rnnt.c: tdt_check), so that whatever was trained can be decoded and nothing else */
+static int dec_check_durations(const char *who, const int *durations, int n_durations) {
+    if (n_durations < 1 || n_durations > NNTK_RNNT_TDT_MAX_DURATIONS)
+        return dec_fail(who, "n_durations %ld is outside [1, %ld]", n_durations, NNTK_RNNT_TDT_MAX_DURATIONS, 0);
+    if (!durations) return dec_fail(who, "NULL durations", 0, 0, 0);
+    for (int i = 0; i < n_durations; ++i) {
+        if (durations[i] < 0) return dec_fail(who, "durations[%ld] = %ld is negative", i, durations[i], 0);
+        if (i > 0 && durations[i] <= durations[i - 1])
+            return dec_fail(who, "durations[%ld] = %ld after %ld: the durations are strictly ascending", i, durations[i], durations[i - 1]);
+    }
+    const int dmax = durations[n_durations - 1];
+    if (dmax < 1) return dec_fail(who, "no positive duration: a blank never takes duration 0, so no row would end", 0, 0, 0);
+    if (dmax > NNTK_RNNT_TDT_MAX_DURATION) return dec_fail(who, "the largest duration %ld is more than %ld", dmax, NNTK_RNNT_TDT_MAX_DURATION, 0);
+    return 0;
+}
+
+/* durations NULL: the classic decoder */
+static NntkRnntDecoder dec_create(const char *who, NntkRnntDecoderConfig cfg, const int *durations, int n_durations, const float *d_embed,
+                                  const float *d_lstm, const float *d_pred_proj, const float *d_out) {
     if (dec_check_config(who, &cfg) || dec_check_blocks(who, &cfg, d_embed, d_lstm, d_pred_proj, d_out)) return NULL;
     NntkRnntDecoder d = (NntkRnntDecoder)calloc(1, sizeof *d);
-    if (!d) { nntk_set_error("nntk_rnnt_decoder_create: out of host memory"); return NULL; }
+    if (!d) { dec_fail(who, "out of host memory", 0, 0, 0); return NULL; }
     d->cfg = cfg;
+    for (int i = 0; durations && i < n_durations; ++i) {
+        d->du.dur[i] = durations[i];
+        d->du.pos_mask |= (durations[i] > 0) << i;
+    }
+    d->du.n = durations ? n_durations : 0;
     const size_t G = 4 * (size_t)cfg.H;
     d->d_table = (float *)nntk_shim_malloc((size_t)cfg.V * G * sizeof(float));
     d->d_U = d->d_table ? (float *)nntk_shim_malloc((size_t)cfg.H * G * sizeof(float)) : NULL;
-    d->d_out = d->d_U ? (float *)nntk_shim_malloc(((size_t)cfg.J + 1) * cfg.V * sizeof(float)) : NULL;
+    d->d_out = d->d_U ? (float *)nntk_shim_malloc(((size_t)cfg.J + 1) * (cfg.V + d->du.n) * sizeof(float)) : NULL;
     if (d->d_out && d_pred_proj) d->d_proj = (float *)nntk_shim_malloc(((size_t)cfg.H + 1) * cfg.J * sizeof(float));
     if (!d->d_table || !d->d_U || !d->d_out || (d_pred_proj && !d->d_proj) || dec_load(d, d_embed, d_lstm, d_pred_proj, d_out)) {
         nntk_rnnt_decoder_destroy(d);
         return NULL;
     }
     return d;
+}
+
+NntkRnntDecoder nntk_rnnt_decoder_create(NntkRnntDecoderConfig cfg, const float *d_embed, const float *d_lstm, const float *d_pred_proj,
+                                         const float *d_out) {
+    nntk_shim_clear_error();
+    return dec_create("nntk_rnnt_decoder_create", cfg, NULL, 0, d_embed, d_lstm, d_pred_proj, d_out);
+}
+
+NntkRnntDecoder nntk_rnnt_tdt_decoder_create(NntkRnntDecoderConfig cfg, const int *durations, int n_durations, const float *d_embed,
+                                             const float *d_lstm, const float *d_pred_proj, const float *d_out) {
+    static const char who[] = "nntk_rnnt_tdt_decoder_create";
+    nntk_shim_clear_error();
+    if (dec_check_durations(who, durations, n_durations)) return NULL;
+    return dec_create(who, cfg, durations, n_durations, d_embed, d_lstm, d_pred_proj, d_out);
 }
 
 int nntk_rnnt_decoder_load_weights_device(NntkRnntDecoder d, const float *d_embed, const float *d_lstm, const float *d_pred_proj,
@@ -128,8 +164,9 @@ NntkRnntDecodeState nntk_rnnt_decode_state_create(NntkRnntDecoder d, int batch) 
     s->batch = batch;
     s->d_f = (float *)nntk_shim_malloc((size_t)batch * (2 * (size_t)d->cfg.H + d->cfg.J) * sizeof(float));
     s->d_score = s->d_f ? (double *)nntk_shim_malloc((size_t)batch * sizeof(double)) : NULL;
-    s->d_i = s->d_score ? (int *)nntk_shim_malloc((size_t)batch * 5 * sizeof(int)) : NULL;
-    if (!s->d_i || nntk_shim_memset(s->d_i, 0, (size_t)batch * 5 * sizeof(int))) {
+    const size_t words = (size_t)batch * (d->du.n ? 6 : 5);
+    s->d_i = s->d_score ? (int *)nntk_shim_malloc(words * sizeof(int)) : NULL;
+    if (!s->d_i || nntk_shim_memset(s->d_i, 0, words * sizeof(int))) {
         nntk_rnnt_decode_state_destroy(s);
         return NULL;
     }
@@ -181,11 +218,20 @@ static int dec_check_overlaps(const char *who, int n_out, int n_all, const void 
     return 0;
 }
 
-/* everything a decode call can be refused for; tensors = 1: the device form's pointers (alignment, overlap) */
-static int dec_check_call(const char *who, NntkRnntDecoder d, NntkRnntDecodeState state, const float *enc, int batch, int T,
-                          const int *n_frames, int max_labels, const int *labels_out, const int *label_frames, const int *out_lengths,
-                          const float *scores) {
+/* a decoder of the other kind: tdt = what the entry serves */
+static int dec_check_kind(const char *who, NntkRnntDecoder d, int tdt) {
+    if ((d->du.n != 0) == tdt) return 0;
+    return dec_fail(who, tdt ? "the decoder has no durations (nntk_rnnt_decoder_create): nntk_rnnt_greedy_decode_device serves it"
+                             : "the decoder has durations (nntk_rnnt_tdt_decoder_create): only nntk_rnnt_tdt_greedy_decode_device serves it",
+                    0, 0, 0);
+}
+
+/* everything a decode call can be refused for; tdt = 1: the token-and-duration call, label_durs its extra output (or NULL) */
+static int dec_check_call(const char *who, int tdt, NntkRnntDecoder d, NntkRnntDecodeState state, const float *enc, int batch, int T,
+                          const int *n_frames, int max_labels, const int *labels_out, const int *label_frames, const int *label_durs,
+                          const int *out_lengths, const float *scores) {
     if (!d) return dec_fail(who, "NULL decoder", 0, 0, 0);
+    if (dec_check_kind(who, d, tdt)) return -1;
     if (batch < 0 || T < 0) return dec_fail(who, "batch %ld, T %ld: neither may be negative", batch, T, 0);
     if (max_labels < 1) return dec_fail(who, "max_labels %ld < 1", max_labels, 0, 0);
     if (state && state->dec != d) return dec_fail(who, "the state belongs to another decoder", 0, 0, 0);
@@ -196,13 +242,14 @@ static int dec_check_call(const char *who, NntkRnntDecoder d, NntkRnntDecodeStat
     if (T > 0 && dec_named_ptr(who, "enc", enc)) return -1;
     if (dec_named_ptr(who, "labels_out", labels_out) || dec_named_ptr(who, "out_lengths", out_lengths)) return -1;
     if (label_frames && dec_named_ptr(who, "label_frames", label_frames)) return -1;
+    if (label_durs && dec_named_ptr(who, "label_durations", label_durs)) return -1;
     if (scores && dec_named_ptr(who, "scores", scores)) return -1;
     const size_t nl = (size_t)batch * max_labels * sizeof(int), nb = (size_t)batch * sizeof(int);
     const size_t ne = (size_t)batch * T * d->cfg.J * sizeof(float);
-    const void *p[5] = { labels_out, label_frames, out_lengths, scores, enc };
-    const size_t n[5] = { nl, nl, nb, nb, ne };
-    static const char *const name[5] = { "labels_out", "label_frames", "out_lengths", "scores", "enc" };
-    return dec_check_overlaps(who, 5, 5, p, n, name);
+    const void *p[6] = { labels_out, label_frames, label_durs, out_lengths, scores, enc };
+    const size_t n[6] = { nl, nl, nl, nb, nb, ne };
+    static const char *const name[6] = { "labels_out", "label_frames", "label_durations", "out_lengths", "scores", "enc" };
+    return dec_check_overlaps(who, 5, 6, p, n, name);
 }
 
 /* the decoder as the launchers take it */
@@ -223,7 +270,8 @@ int nntk_rnnt_greedy_decode_device(NntkRnntDecoder d, NntkRnntDecodeState state,
                                    int max_labels, int *d_labels_out, int *d_label_frames, int *d_out_lengths, float *d_scores) {
     static const char who[] = "nntk_rnnt_greedy_decode_device";
     nntk_shim_clear_error();
-    if (dec_check_call(who, d, state, d_enc, batch, T, n_frames, max_labels, d_labels_out, d_label_frames, d_out_lengths, d_scores)) return -1;
+    if (dec_check_call(who, 0, d, state, d_enc, batch, T, n_frames, max_labels, d_labels_out, d_label_frames, NULL, d_out_lengths, d_scores))
+        return -1;
     if (batch == 0) return 0;
     const nntk_shim_rnnt_dec m = dec_model(d);
     int *len = dec_row_frames("nntk_rnnt_greedy_decode_device: out of host memory", n_frames, batch, T);
@@ -238,7 +286,7 @@ int nntk_rnnt_greedy_decode(NntkRnntDecoder d, NntkRnntDecodeState state, const 
                             int max_labels, int *labels_out, int *label_frames, int *out_lengths, float *scores) {
     static const char who[] = "nntk_rnnt_greedy_decode";
     nntk_shim_clear_error();
-    if (dec_check_call(who, d, state, enc, batch, T, n_frames, max_labels, labels_out, label_frames, out_lengths, scores)) return -1;
+    if (dec_check_call(who, 0, d, state, enc, batch, T, n_frames, max_labels, labels_out, label_frames, NULL, out_lengths, scores)) return -1;
     if (batch == 0) return 0;
     const size_t ne = (size_t)batch * T * d->cfg.J, nl = (size_t)batch * max_labels;
     float *d_enc = nntk_devbuf_reserve(&t_a, ne + 4);
@@ -259,7 +307,56 @@ int nntk_rnnt_greedy_decode(NntkRnntDecoder d, NntkRnntDecodeState state, const 
     return scores ? nntk_shim_download(scores, d_sc, (size_t)batch * sizeof(float)) : 0;
 }
 
-/* ---- beam search (csrc/hip/rnnt_beam.hip) on the same decoder handle ---- */
+/* ---- token-and-duration greedy decoding (csrc/hip/rnnt_tdt_decode.hip) on a handle of nntk_rnnt_tdt_decoder_create ---- */
+
+int nntk_rnnt_tdt_greedy_decode_device(NntkRnntDecoder d, NntkRnntDecodeState state, const float *d_enc, int batch, int T,
+                                       const int *n_frames, int max_labels, int *d_labels_out, int *d_label_frames, int *d_label_durations,
+                                       int *d_out_lengths, float *d_scores) {
+    static const char who[] = "nntk_rnnt_tdt_greedy_decode_device";
+    nntk_shim_clear_error();
+    if (dec_check_call(who, 1, d, state, d_enc, batch, T, n_frames, max_labels, d_labels_out, d_label_frames, d_label_durations, d_out_lengths,
+                       d_scores)) return -1;
+    if (batch == 0) return 0;
+    const nntk_shim_rnnt_dec m = dec_model(d);
+    int *len = dec_row_frames("nntk_rnnt_tdt_greedy_decode_device: out of host memory", n_frames, batch, T);
+    if (!len) return -1;
+    int rc = nntk_shim_rnnt_tdt_greedy(&m, &d->du, d_enc, batch, T, len, max_labels, state ? state->d_f : NULL, state ? state->d_score : NULL,
+                                       state ? state->d_i : NULL, state ? state->d_i + 5 * (size_t)batch : NULL, d_labels_out, d_label_frames,
+                                       d_label_durations, d_out_lengths, d_scores);
+    free(len);
+    return rc;
+}
+
+int nntk_rnnt_tdt_greedy_decode(NntkRnntDecoder d, NntkRnntDecodeState state, const float *enc, int batch, int T, const int *n_frames,
+                                int max_labels, int *labels_out, int *label_frames, int *label_durations, int *out_lengths, float *scores) {
+    static const char who[] = "nntk_rnnt_tdt_greedy_decode";
+    nntk_shim_clear_error();
+    if (dec_check_call(who, 1, d, state, enc, batch, T, n_frames, max_labels, labels_out, label_frames, label_durations, out_lengths, scores))
+        return -1;
+    if (batch == 0) return 0;
+    const size_t ne = (size_t)batch * T * d->cfg.J, nl = (size_t)batch * max_labels;
+    float *d_enc = nntk_devbuf_reserve(&t_a, ne + 4);
+    int *d_lab = (int *)nntk_devbuf_reserve(&t_b, 3 * nl + 2 * (size_t)batch + 4);
+    if (!d_enc || !d_lab) return -1;
+    int *d_fr = d_lab + nl, *d_du = d_fr + nl, *d_len = d_du + nl;
+    float *d_sc = (float *)(d_len + batch);
+    if (ne && nntk_shim_upload(d_enc, enc, ne * sizeof(float))) return -1;
+    if (state) {                                /* a push appends to what the caller's buffers hold */
+        if (nntk_shim_upload(d_lab, labels_out, nl * sizeof(int))) return -1;
+        if (label_frames && nntk_shim_upload(d_fr, label_frames, nl * sizeof(int))) return -1;
+        if (label_durations && nntk_shim_upload(d_du, label_durations, nl * sizeof(int))) return -1;
+    }
+    if (nntk_rnnt_tdt_greedy_decode_device(d, state, d_enc, batch, T, n_frames, max_labels, d_lab, label_frames ? d_fr : NULL,
+                                           label_durations ? d_du : NULL, d_len, scores ? d_sc : NULL)) return -1;
+    if (nntk_shim_download(labels_out, d_lab, nl * sizeof(int))) return -1;
+    if (label_frames && nntk_shim_download(label_frames, d_fr, nl * sizeof(int))) return -1;
+    if (label_durations && nntk_shim_download(label_durations, d_du, nl * sizeof(int))) return -1;
+    if (nntk_shim_download(out_lengths, d_len, (size_t)batch * sizeof(int))) return -1;
+    return scores ? nntk_shim_download(scores, d_sc, (size_t)batch * sizeof(float)) : 0;
+}
+
+/* ---- beam search (csrc/hip/rnnt_beam.hip) on the same decoder handle; beam search with durations is not built: a handle with
+ *      durations is refused by every entry, and its sizes are 0 ---- */
 
 struct NntkRnntBeamStateStruct {
     NntkRnntDecoder dec;
@@ -274,6 +371,7 @@ struct NntkRnntBeamStateStruct {
 
 static int beam_check_sizes(const char *who, NntkRnntDecoder d, int beam_width, int max_labels) {
     if (!d) return dec_fail(who, "NULL decoder", 0, 0, 0);
+    if (dec_check_kind(who, d, 0)) return -1;
     if (beam_width < 1 || beam_width > NNTK_RNNT_BEAM_MAX_W)
         return dec_fail(who, "beam_width %ld is outside [1, %ld]", beam_width, NNTK_RNNT_BEAM_MAX_W, 0);
     if (max_labels < 1) return dec_fail(who, "max_labels %ld < 1", max_labels, 0, 0);
@@ -281,7 +379,7 @@ static int beam_check_sizes(const char *who, NntkRnntDecoder d, int beam_width, 
 }
 
 static int beam_sizes_ok(NntkRnntDecoder d, int batch, int beam_width, int max_labels) {
-    return d && batch > 0 && beam_width >= 1 && beam_width <= NNTK_RNNT_BEAM_MAX_W && max_labels >= 1;
+    return d && !d->du.n && batch > 0 && beam_width >= 1 && beam_width <= NNTK_RNNT_BEAM_MAX_W && max_labels >= 1;
 }
 
 /* the six public sizes: the bytes of a stream's state (state = 1) or the floats of a call's workspace; 0 where a call would be refused */
@@ -389,6 +487,7 @@ static int beam_check_call(const char *who, NntkRnntDecoder d, NntkRnntBeamState
     NntkNgramLm lm = o ? o->lm : NULL;
     const int detail = beam_opt_detail(o);
     if (!d) return dec_fail(who, "NULL decoder", 0, 0, 0);
+    if (dec_check_kind(who, d, 0)) return -1;
     if (o && o->length_norm != 0 && o->length_norm != 1) return dec_fail(who, "length_norm %ld is neither 0 nor 1", o->length_norm, 0, 0);
     if (state && state->detail != detail)
         return dec_fail(who, state->detail ? "the state was created with detail, the call asks for none"

@@ -1458,20 +1458,26 @@ class RnntDecoder:
     """``nntk_rnnt_decoder_*``: greedy transducer decoding with the prediction network inside the search (INTEGRATION.md
     "RNN-Transducer: greedy decoding").  Device tensors in the library's layouts: embed [V, E]; lstm_block, the flat ``LSTMGetWeights``
     block W [E,4H] | U [H,4H] | b_i | b_h; pred_proj, the flat Dense block W [H,J] | b [J], or None (identity, H == J); out, the flat
-    Dense block W [J,V] | b [V].  The decoder keeps its own copy: the tensors may be freed or updated afterwards (``load_weights``)."""
+    Dense block W [J,V] | b [V].  The decoder keeps its own copy: the tensors may be freed or updated afterwards (``load_weights``).
+    durations: host ints, the duration table of a token-and-duration model (``nntk_rnnt_tdt_decoder_create``, INTEGRATION.md
+    "RNN-Transducer: token-and-duration greedy decoding"); out is then W [J, V + D] | b [V + D], ``decode`` and ``RnntGreedyStream.push``
+    return five tensors (label_durations third) and ``beam_decode`` raises."""
 
-    def __init__(self, embed, lstm_block, pred_proj, out, blank=0, joint_activation=ACT_TANH, max_symbols_per_frame=10):
+    def __init__(self, embed, lstm_block, pred_proj, out, blank=0, joint_activation=ACT_TANH, max_symbols_per_frame=10, durations=None):
         V, E = embed.shape
         H = self._hidden(lstm_block.numel(), E)
         J = H if pred_proj is None else pred_proj.numel() // (H + 1)
+        self.durations = None if durations is None else np.ascontiguousarray(np.asarray(durations, dtype=np.int32).reshape(-1))
+        D = 0 if durations is None else self.durations.shape[0]
         assert pred_proj is None or pred_proj.numel() == (H + 1) * J, "pred_proj: the flat block W [H,J] | b [J]"
-        assert out.numel() == (J + 1) * V, "out: the flat block W [J,V] | b [V]"
+        assert out.numel() == (J + 1) * (V + D), "out: the flat block W [J,V] | b [V], with durations W [J,V + D] | b [V + D]"
         self.V, self.E, self.H, self.J, self.max_symbols = int(V), int(E), int(H), int(J), int(max_symbols_per_frame)
         cfg = capi.NntkRnntDecoderConfig(self.V, int(blank), self.E, self.H, self.J, RNNT_ACTIVATIONS[joint_activation], self.max_symbols)
-        self.h = capi.load().nntk_rnnt_decoder_create(cfg, _dp(embed), _dp(lstm_block), _dp(pred_proj) if pred_proj is not None else None,
-                                                      _dp(out))
+        blocks = (_dp(embed), _dp(lstm_block), _dp(pred_proj) if pred_proj is not None else None, _dp(out))
+        entry = "nntk_rnnt_decoder_create" if durations is None else "nntk_rnnt_tdt_decoder_create"
+        self.h = getattr(capi.load(), entry)(cfg, *(() if durations is None else (self.durations.ctypes.data_as(capi.ip), D)), *blocks)
         if not self.h:
-            raise capi.NNTKError("nntk_rnnt_decoder_create: " + capi.last_error())
+            raise capi.NNTKError(entry + ": " + capi.last_error())
 
     @staticmethod
     def _hidden(n, E):
@@ -1488,22 +1494,21 @@ class RnntDecoder:
 
     def _outputs(self, device, B, max_labels):
         import torch
-        return (torch.empty((B, max_labels), dtype=torch.int32, device=device), torch.empty((B, max_labels), dtype=torch.int32, device=device),
-                torch.empty(B, dtype=torch.int32, device=device), torch.empty(B, dtype=torch.float32, device=device))
+        per_label = tuple(torch.empty((B, max_labels), dtype=torch.int32, device=device) for _ in range(2 if self.durations is None else 3))
+        return per_label + (torch.empty(B, dtype=torch.int32, device=device), torch.empty(B, dtype=torch.float32, device=device))
 
     def _decode(self, state, enc, n_frames, max_labels, outs):
         B, T, J = enc.shape
         assert J == self.J, "enc: [B, T, J]"
-        labels, frames, lengths, scores = outs
-        check(capi.load().nntk_rnnt_greedy_decode_device(self.h, state, _dp(enc), B, T, _n_frames_ptr(n_frames, B), int(max_labels),
-                                                         _ipv(labels), _ipv(frames), _ipv(lengths), _dp(scores)),
-              "nntk_rnnt_greedy_decode_device")
+        entry = "nntk_rnnt_greedy_decode_device" if self.durations is None else "nntk_rnnt_tdt_greedy_decode_device"
+        check(getattr(capi.load(), entry)(self.h, state, _dp(enc), B, T, _n_frames_ptr(n_frames, B), int(max_labels),
+                                          *(_ipv(o) for o in outs[:-1]), _dp(outs[-1])), entry)
         return outs
 
     def decode(self, enc, n_frames=None, max_labels=None):
         """enc [B, T, J] device tensor, n_frames host ints per row (None: T) -> (labels [B, max_labels] int32, -1 behind each row's
-        labels; label_frames, the same shape; lengths [B] int32; scores [B] float32).  max_labels defaults to
-        max_symbols_per_frame * T, which never truncates."""
+        labels; label_frames, the same shape; lengths [B] int32; scores [B] float32); with durations (labels, label_frames,
+        label_durations, lengths, scores).  max_labels defaults to max_symbols_per_frame * T, which never truncates."""
         B, T, _ = enc.shape
         if max_labels is None:
             max_labels = max(1, self.max_symbols * T)
@@ -1583,7 +1588,8 @@ class RnntGreedyStream:
             raise capi.NNTKError("nntk_rnnt_decode_state_create: " + capi.last_error())
 
     def push(self, enc_chunk, n_frames):
-        """enc_chunk [batch, T, J] device tensor, n_frames host ints per row (0 allowed) -> (labels, label_frames, lengths, scores)"""
+        """enc_chunk [batch, T, J] device tensor, n_frames host ints per row (0 allowed) -> (labels, label_frames, lengths, scores);
+        on a decoder with durations (labels, label_frames, label_durations, lengths, scores)"""
         assert enc_chunk.shape[0] == self.B, "enc_chunk: [batch, T, J]"
         if self.outs is None:
             self.outs = self.dec._outputs(enc_chunk.device, self.B, self.max_labels)
@@ -1650,12 +1656,12 @@ class RnntBeamStream:
             pass
 
 
-def _rnnt_host_decoder(embed, lstm_block, pred_proj, out, enc, max_labels, blank, joint_activation, max_symbols_per_frame):
+def _rnnt_host_decoder(embed, lstm_block, pred_proj, out, enc, max_labels, blank, joint_activation, max_symbols_per_frame, durations=None):
     """the preamble of the numpy decode calls: the weights uploaded into a decoder of their own -> (decoder, enc as float32, B, T,
     max_labels with its default)"""
     import torch
     dev = lambda a: None if a is None else torch.from_numpy(_f32(a).reshape(-1) if a is not embed else _f32(a)).cuda()
-    dec = RnntDecoder(dev(embed), dev(lstm_block), dev(pred_proj), dev(out), blank, joint_activation, max_symbols_per_frame)
+    dec = RnntDecoder(dev(embed), dev(lstm_block), dev(pred_proj), dev(out), blank, joint_activation, max_symbols_per_frame, durations)
     enc = _f32(enc)
     B, T, _ = enc.shape
     return dec, enc, B, T, max(1, dec.max_symbols * T) if max_labels is None else max_labels
@@ -1699,6 +1705,24 @@ def rnnt_greedy_decode(embed, lstm_block, pred_proj, out, enc, n_frames=None, ma
     finally:
         dec.destroy()
     return labels, frames, lengths, scores
+
+
+def rnnt_tdt_greedy_decode(embed, lstm_block, pred_proj, out, enc, durations, n_frames=None, max_labels=None, blank=0,
+                           joint_activation=ACT_TANH, max_symbols_per_frame=10):
+    """Token-and-duration greedy decoding on numpy arrays (``nntk_rnnt_tdt_greedy_decode``): out W [J, V + D] | b [V + D], enc [B, T, J]
+    -> (labels [B, max_labels], label_frames, label_durations, lengths [B], scores [B])"""
+    dec, enc, B, T, max_labels = _rnnt_host_decoder(embed, lstm_block, pred_proj, out, enc, max_labels, blank, joint_activation,
+                                                    max_symbols_per_frame, durations)
+    labels, frames, durs = (np.empty((B, max_labels), np.int32) for _ in range(3))
+    lengths, scores = np.empty(B, np.int32), np.empty(B, np.float32)
+    try:
+        check(capi.load().nntk_rnnt_tdt_greedy_decode(dec.h, None, _p(enc), B, T, _n_frames_ptr(n_frames, B), int(max_labels),
+                                                      labels.ctypes.data_as(capi.ip), frames.ctypes.data_as(capi.ip),
+                                                      durs.ctypes.data_as(capi.ip), lengths.ctypes.data_as(capi.ip), _p(scores)),
+              "nntk_rnnt_tdt_greedy_decode")
+    finally:
+        dec.destroy()
+    return labels, frames, durs, lengths, scores
 
 
 def _host_ids(ids):
