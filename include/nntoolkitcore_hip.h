@@ -1147,7 +1147,7 @@ int nntk_rnnt_joint_backward_device(const float *d_out_fwd, const float *d_dout,
  * because a move multiplies two emissions.  Deterministic: no atomics, a cell's terms summed in one order (ascending i, blank before
  * label), the same bits on every call, the same loss bits with and without a gradient.  The joiner serves unchanged; the projection on
  * top is a Dense of width V + n_durations.  Decoding such a model: nntk_rnnt_tdt_greedy_decode_device below (greedy, one-shot and
- * streamed); beam search with durations is not in the library. */
+ * streamed); forced alignment: nntk_rnnt_tdt_align_device below; beam search with durations is not in the library. */
 size_t nntk_rnnt_tdt_workspace_floats(int batch, int T, int max_label_len, int n_durations, int want_grad);
 int nntk_rnnt_tdt_loss_device(const float *d_logits, int batch, int T, int V, const int *durations, int n_durations,
                               const int *input_lengths, const int *labels, const int *label_lengths, int max_label_len, int blank,
@@ -1155,6 +1155,47 @@ int nntk_rnnt_tdt_loss_device(const float *d_logits, int batch, int T, int V, co
 int nntk_rnnt_tdt_loss(const float *logits, int batch, int T, int V, const int *durations, int n_durations, const int *input_lengths,
                        const int *labels, const int *label_lengths, int max_label_len, int blank, float sigma, float *loss_rows,
                        float *dlogits);
+
+/* ---- RNN-Transducer: token-and-duration forced alignment (csrc/hip/rnnt_tdt_align.hip; INTEGRATION.md "RNN-Transducer: TDT forced
+ *      alignment") ----
+ * Given a row's labels, its single most probable path through the token-and-duration lattice (Viterbi): out of which frame every label
+ * is emitted, and with which duration the model jumped at every move.
+ *   d_logits, durations, input_lengths, labels, label_lengths, blank, sigma: as for nntk_rnnt_tdt_loss_device, with exactly its checks,
+ *     made before anything is enqueued: -1, nntk_last_error(), nothing written, no device needed.  Its emissions too: p_tok =
+ *     exp(x - lse_tok - sigma), p_dur = exp(x - lse_dur), each with an int32 exponent of its own, floored at 2^-4000.  Cells with
+ *     t >= T_b or u > U_b are never read and may hold NaN.
+ *   v(0, 0) = 1; v(t, u) is the maximum over exactly the terms whose sum is alpha(t, u) above, each term one product v p_tok p_dur; the
+ *     path's probability is the maximum over 0 < d_i <= T_b of v(T_b - d_i, U_b) p_tok(blank) p_dur(i).  Tie-break: the candidates are
+ *     taken in the loss's one order -- ascending i, for each i the blank term before the label term -- and a later candidate replaces
+ *     the current one only if it is strictly greater; a cell that no candidate of non-zero mass reaches has value zero and no
+ *     backpointer.
+ *   d_label_frames [batch][max_label_len] or NULL: the frame t out of which label i < U_b is emitted (the move (t, i) ->
+ *     (t + d, i + 1)), non-decreasing in i; -1 for i >= U_b.  d_label_durations, same shape, or NULL: that move's duration d in frames
+ *     (the value, not the index); -1 for i >= U_b.
+ *   d_frame_labels [batch][T] or NULL: the u of the blank move that leaves frame t on the path; -1 in every frame the path leaves by no
+ *     blank (jumped over, or left by a label with a positive duration) and for t >= T_b.  d_frame_durations, same shape, or NULL: that
+ *     blank's duration; -1 in the same frames.
+ *   d_label_logp [batch][max_label_len] / d_frame_logp [batch][T], or NULL: ln(p_tok p_dur) of the label's move and of the frame's blank
+ *     move, from mantissa and exponent in double; 0 in the padding and where there is no blank move.
+ *   d_scores [batch]: ln of the path's probability: the sum of the row's two logp arrays up to rounding, and never above -loss of the
+ *     same row.  -inf for a row without a path -- the finite-score ways above ({0, 2} on an odd T_b, {1, 2} with more labels than
+ *     frames) and -inf scores; for such a row all four int arrays are -1 and both logp arrays 0.
+ *   Every element of every non-NULL output is written.  Outputs may not overlap one another, the inputs or the workspace.
+ *   d_workspace, 16-byte aligned: nntk_rnnt_tdt_align_workspace_floats(batch, T, max_label_len, n_durations) =
+ *     nntk_rnnt_tdt_workspace_floats(batch, T, max_label_len, n_durations, 0) rounded up to 4 floats, plus one word per row (the
+ *     terminal move's choice; rounded up to 16 bytes), plus one backpointer byte per cell of batch (T + max_label_len) anti-diagonals,
+ *     each min(T, max_label_len + 1) cells wide (rounded up to 16 bytes), plus 16 bytes.
+ * Limits: those of nntk_rnnt_tdt_loss_device.  Deterministic: no atomics, the same bits on every call; a row's bits do not depend on
+ * the other rows, on its position in the batch or on the T / max_label_len padding.  The device form runs on the calling thread's
+ * stream and reads nothing back; the host-pointer form uploads, runs the device form and downloads. */
+size_t nntk_rnnt_tdt_align_workspace_floats(int batch, int T, int max_label_len, int n_durations);
+int nntk_rnnt_tdt_align_device(const float *d_logits, int batch, int T, int V, const int *durations, int n_durations,
+                               const int *input_lengths, const int *labels, const int *label_lengths, int max_label_len, int blank,
+                               float sigma, int *d_label_frames, int *d_label_durations, int *d_frame_labels, int *d_frame_durations,
+                               float *d_label_logp, float *d_frame_logp, float *d_scores, float *d_workspace);
+int nntk_rnnt_tdt_align(const float *logits, int batch, int T, int V, const int *durations, int n_durations, const int *input_lengths,
+                        const int *labels, const int *label_lengths, int max_label_len, int blank, float sigma, int *label_frames,
+                        int *label_durations, int *frame_labels, int *frame_durations, float *label_logp, float *frame_logp, float *scores);
 
 /* ---- RNN-Transducer: fused training loss (csrc/hip/rnnt_fused.hip; INTEGRATION.md "RNN-Transducer: fused training loss") ----
  * Joiner, vocabulary projection and loss in one call: with logits[b][t][u] = act(d_enc[b][t] + d_pred[b][u]) W + b, d_loss_rows[b] is

@@ -496,6 +496,12 @@ SIGNATURES = {
     "nntk_rnnt_tdt_workspace_floats": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "nntk_rnnt_tdt_loss_device": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, ip, C.c_int, ip, ip, ip, C.c_int, C.c_int, C.c_float, vp, vp, vp]),
     "nntk_rnnt_tdt_loss": (C.c_int, [fp, C.c_int, C.c_int, C.c_int, ip, C.c_int, ip, ip, ip, C.c_int, C.c_int, C.c_float, fp, fp]),
+    # token-and-duration forced alignment (INTEGRATION.md "RNN-Transducer: TDT forced alignment")
+    "nntk_rnnt_tdt_align_workspace_floats": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "nntk_rnnt_tdt_align_device": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, ip, C.c_int, ip, ip, ip, C.c_int, C.c_int, C.c_float,
+                                             vp, vp, vp, vp, vp, vp, vp, vp]),
+    "nntk_rnnt_tdt_align": (C.c_int, [fp, C.c_int, C.c_int, C.c_int, ip, C.c_int, ip, ip, ip, C.c_int, C.c_int, C.c_float,
+                                      ip, ip, ip, ip, fp, fp, fp]),
     "nntk_rnnt_joint_device": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
     "nntk_rnnt_joint_backward_device": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),
     "nntk_rnnt_fused_workspace_floats": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),

@@ -245,6 +245,18 @@ size_t nntk_shim_rnnt_tdt_workspace_floats(int batch, int T, int max_label_len, 
 int nntk_shim_rnnt_tdt_loss(const float *d_logits, int B, int T, int V, const int *h_durations, int n_durations, const int *h_input_lengths,
                             const int *h_labels, const int *h_label_lengths, int max_label_len, int blank, float sigma, float *d_loss_rows,
                             float *d_dlogits, float *d_ws);
+/* ---- token-and-duration forced alignment (rnnt_tdt_align.hip): the best single path of every row, on the scores, durations and host
+ *      arrays of nntk_shim_rnnt_tdt_loss with its limits; every output but scores may be NULL; d_ws 16-byte aligned,
+ *      nntk_shim_rnnt_tdt_align_workspace_floats words: the loss-only workspace, one word per row for the terminal move, one
+ *      backpointer byte per cell of batch (T + max_label_len) diagonals of min(T, max_label_len + 1) cells, and 16 bytes ---- */
+typedef struct {
+    int *label_frames, *label_durations, *frame_labels, *frame_durations;
+    float *label_logp, *frame_logp, *scores;
+} nntk_shim_rnnt_tdt_path;
+size_t nntk_shim_rnnt_tdt_align_workspace_floats(int batch, int T, int max_label_len, int n_durations);
+int nntk_shim_rnnt_tdt_align(const float *d_logits, int B, int T, int V, const int *h_durations, int n_durations, const int *h_input_lengths,
+                             const int *h_labels, const int *h_label_lengths, int max_label_len, int blank, float sigma,
+                             const nntk_shim_rnnt_tdt_path *out, float *d_ws);
 /* ---- the fused transducer training loss (rnnt_fused.hip): joiner, vocabulary projection and loss from enc [B][T][J], pred [B][U1][J] and
  *      the Dense block W [J,V] | b [V]; the three gradient pointers all NULL = loss only.  Host int arrays as for nntk_shim_rnnt_loss,
  *      already checked by the caller (rnnt.c).  The limits: a tile's 32 rows of z (J floats each) and a group of g columns share one

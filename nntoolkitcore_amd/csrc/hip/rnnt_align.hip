@@ -24,13 +24,6 @@
 // (nntk_shim_rnnt_src): it differs in the limit check and in the emission writer it calls, and in nothing else.
 #include "rnnt_common.hpp"
 
-#define RNNT_BT_BYTES (64 * 1024)         // backpointer bytes staged per block of diagonals ...
-#define RNNT_BT_DIAGS 2048                // ... and the diagonals of a block at most (their u sit in LDS too)
-static int rnnt_bt_block_diags(int P) {
-    const int dc = RNNT_BT_BYTES / P;
-    return dc < 1 ? 1 : dc > RNNT_BT_DIAGS ? RNNT_BT_DIAGS : dc;
-}
-
 // NJ as in rnnt_lattice_kernel.  LDS per u: v p_blank | v p_label of the lane's cell -- what moves on to (t + 1, u) and to (t, u + 1)
 template <int NJ>
 __global__ __launch_bounds__(CTC_THREADS) void rnnt_viterbi_kernel(int B, int T, int U1, const int *__restrict__ ints,

@@ -62,6 +62,14 @@ static inline RnntAlignLayout rnnt_align_layout(size_t base, int B, int T, int m
     return l;
 }
 
+// the backtrack of both aligners (rnnt_align.hip, rnnt_tdt_align.hip) stages the backpointers into LDS a block of diagonals at a time
+#define RNNT_BT_BYTES (64 * 1024)         // backpointer bytes staged per block of diagonals ...
+#define RNNT_BT_DIAGS 2048                // ... and the diagonals of a block at most (their path entries sit in LDS too)
+static inline int rnnt_bt_block_diags(int P) {
+    const int dc = RNNT_BT_BYTES / P;
+    return dc < 1 ? 1 : dc > RNNT_BT_DIAGS ? RNNT_BT_DIAGS : dc;
+}
+
 // exp(x - lse) as mantissa and exponent; -inf (and NaN) scores: zero
 __device__ __forceinline__ xf rnnt_emission(float x, double lse) {
     if (!(x > -INFINITY)) return xf_zero();

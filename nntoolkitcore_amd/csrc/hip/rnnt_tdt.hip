@@ -36,35 +36,7 @@
 //    g[v] = occ exp(x_v - lse_tok) - [v = blank] F_blank - [v = label] F_label, g[V + i] = occ exp(x_{V+i} - lse_dur) - F_dur(i) out,
 //    16 bytes at a time where (V + D) % 4 == 0.  Padding cells and the rows with P = 0 are zero-filled.
 // No atomics anywhere; every reduction is a fixed butterfly or a fixed-order loop.
-#include "rnnt_common.hpp"
-
-#define TDT_MAXD NNTK_RNNT_TDT_MAX_DURATIONS
-
-struct TdtDur { int n, dmax; int d[TDT_MAXD]; };                             // the durations, by value: strictly ascending, d[0] >= 0
-
-// workspace, in 4-byte words: [ints: input lengths B | label lengths B | labels B*maxL] [P per row: 2B] [token emissions: 4 per cell]
-// [duration probabilities: 2 D per cell]; with a gradient: [lse_tok, lse_dur: 4 per cell] [alpha: 2 per cell] [beta: 2 per cell]; every
-// part starts on a 16-byte boundary
-struct TdtLayout { size_t hdr, em, dur, lse, alpha, beta, total; };
-static inline TdtLayout tdt_layout(int B, int T, int maxL, int D, int want_grad) {
-    TdtLayout l;
-    const size_t b = B > 0 ? (size_t)B : 0, t = T > 0 ? (size_t)T : 0, ml = maxL > 0 ? (size_t)maxL : 0, nd = D > 0 ? (size_t)D : 0;
-    auto up = [](size_t x) { return (x + 3) & ~(size_t)3; };
-    const size_t cells = b * t * (ml + 1);
-    l.hdr = up(b * (2 + ml));
-    l.em = l.hdr + up(2 * b);
-    l.dur = l.em + 4 * cells;
-    l.lse = l.dur + up(2 * nd * cells);
-    l.alpha = l.lse + (want_grad ? 4 * cells : 0);
-    l.beta = l.alpha + (want_grad ? up(2 * cells) : 0);
-    l.total = l.beta + (want_grad ? up(2 * cells) : 0) + 4;
-    return l;
-}
-
-static inline size_t tdt_ring_bytes(int U1, int dmax) { return (size_t)(dmax + 2) * (size_t)U1 * sizeof(float4); }
-
-__device__ __forceinline__ xf tdt_xf(float2 w) { return xf_unpack(w); }
-__device__ __forceinline__ float2 tdt_zero2() { return make_float2(0.0f, __int_as_float(CTC_EZERO)); }
+#include "rnnt_tdt_common.hpp"
 
 // the up to 2 D terms of a cell, in their one order: aligned to the largest exponent, added left to right, normalised once
 __device__ __forceinline__ xf tdt_sum(const xf (&tm)[2 * TDT_MAXD]) {
@@ -136,11 +108,6 @@ __global__ __launch_bounds__(CTC_THREADS) void tdt_emit_kernel(const float *__re
         }
     }
 }
-
-// what a cell of the lattice takes from global memory: its own token emissions and, forwards, the duration probabilities of its
-// sources -- a[i] of (t - d_i, u), the blank's; b[i] of (t - d_i, u - 1), the label's -- backwards its own, in a[i].  A term that does
-// not exist has a zero there
-struct TdtRec { float4 e; float2 a[TDT_MAXD], b[TDT_MAXD]; };
 
 // REG: U1 <= 256, a lane owns the cell u = tid of a diagonal and takes its record from registers, loaded one diagonal ahead; else any U1
 // whose ring fits the LDS, lanes stride over u and the record is fetched inside the step
@@ -344,12 +311,18 @@ __global__ __launch_bounds__(CTC_THREADS) void tdt_grad_kernel(const float *__re
     }
 }
 
-// the limits of nntk_shim.h, for a caller that bypasses rnnt.c
-static bool tdt_fits(int T, int maxL, const int *dur, int D) {
-    if (D < 1 || D > TDT_MAXD || dur[0] < 0 || dur[D - 1] < 1 || dur[D - 1] > NNTK_RNNT_TDT_MAX_DURATION) return false;
-    for (int i = 1; i < D; ++i)
-        if (dur[i] <= dur[i - 1]) return false;
-    return maxL >= 0 && tdt_ring_bytes(maxL + 1, dur[D - 1]) <= NNTK_RNNT_TDT_LDS_BYTES && (long)T + maxL <= NNTK_RNNT_TDT_MAX_DIAGONALS;
+int nntk_rnnt_tdt_emit_launch(const float *d_logits, int B, int T, int U1, int V, int D, int blank, float sigma, const int *d_ints,
+                              float4 *em, float2 *pdur, double *lse) {
+    const long cells = (long)B * T * U1;
+    const dim3 cgrid(rnnt_grid(cells, 4));
+    if (((V + D) & 3) == 0)
+        hipLaunchKernelGGL(tdt_emit_kernel<true>, cgrid, dim3(CTC_THREADS), 0, nntk_stream(), d_logits, B, T, U1, V, D, blank, sigma, d_ints, em,
+                           pdur, lse, cells);
+    else
+        hipLaunchKernelGGL(tdt_emit_kernel<false>, cgrid, dim3(CTC_THREADS), 0, nntk_stream(), d_logits, B, T, U1, V, D, blank, sigma, d_ints, em,
+                           pdur, lse, cells);
+    NNTK_LAUNCH_CHECK("tdt_emit_kernel");
+    return 0;
 }
 
 extern "C" {
@@ -377,19 +350,10 @@ int nntk_shim_rnnt_tdt_loss(const float *d_logits, int B, int T, int V, const in
     float2 *pdur = (float2 *)(d_ws + l.dur);
     double *lse = grad ? (double *)(d_ws + l.lse) : nullptr;
     float2 *wa = grad ? (float2 *)(d_ws + l.alpha) : nullptr, *wb = grad ? (float2 *)(d_ws + l.beta) : nullptr;
-    TdtDur dur;
-    dur.n = D;
-    dur.dmax = h_durations[D - 1];
-    for (int i = 0; i < TDT_MAXD; ++i) dur.d[i] = i < D ? h_durations[i] : 0;
+    const TdtDur dur = tdt_dur(h_durations, D);
     if (rnnt_upload_ints(ints, B, maxL, h_input_lengths, h_labels, h_label_lengths)) return -1;
     const dim3 cgrid(rnnt_grid(cells, 4));
-    if (vec)
-        hipLaunchKernelGGL(tdt_emit_kernel<true>, cgrid, dim3(CTC_THREADS), 0, nntk_stream(), d_logits, B, T, U1, V, D, blank, sigma, ints, em,
-                           pdur, lse, cells);
-    else
-        hipLaunchKernelGGL(tdt_emit_kernel<false>, cgrid, dim3(CTC_THREADS), 0, nntk_stream(), d_logits, B, T, U1, V, D, blank, sigma, ints, em,
-                           pdur, lse, cells);
-    NNTK_LAUNCH_CHECK("tdt_emit_kernel");
+    if (nntk_rnnt_tdt_emit_launch(d_logits, B, T, U1, V, D, blank, sigma, ints, em, pdur, lse)) return -1;
     const size_t lds = tdt_ring_bytes(U1, dur.dmax);
     const dim3 lgrid((unsigned)B, grad ? 2 : 1);
 #define TDT_AB(REG)                                                                                                             \

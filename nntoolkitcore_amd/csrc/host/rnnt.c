@@ -195,6 +195,98 @@ int nntk_rnnt_tdt_loss(const float *logits, int batch, int T, int V, const int *
     return dlogits ? nntk_shim_download(dlogits, d_g, n * sizeof(float)) : 0;
 }
 
+/* ---- token-and-duration forced alignment (csrc/hip/rnnt_tdt_align.hip): tdt_check, the loss's own, then the outputs.  The seven
+ *      outputs in the entries' order as one table: per row max_label_len or T elements, scores one ---- */
+enum { TDT_OUTS = 7 };
+typedef struct { const char *name; void *p; size_t n; } tdt_out;
+static void tdt_outs(tdt_out *o, const nntk_shim_rnnt_tdt_path *p, int dev, int batch, int T, int max_label_len) {
+    const size_t nl = (size_t)batch * max_label_len, nt = (size_t)batch * T;
+    const tdt_out all[TDT_OUTS] = {{"d_label_frames", p->label_frames, nl}, {"d_label_durations", p->label_durations, nl},
+                                   {"d_frame_labels", p->frame_labels, nt}, {"d_frame_durations", p->frame_durations, nt},
+                                   {"d_label_logp", p->label_logp, nl}, {"d_frame_logp", p->frame_logp, nt}, {"d_scores", p->scores, (size_t)batch}};
+    for (int k = 0; k < TDT_OUTS; ++k) {
+        o[k] = all[k];
+        if (!dev) o[k].name += 2;                                           /* the host form's names: without the d_ */
+    }
+}
+
+static int tdt_check_outs(const char *who, const tdt_out *o) {
+    for (int k = 0; k < TDT_OUTS; ++k)
+        if ((o[k].p || k == TDT_OUTS - 1) && rnnt_check_ptr(who, o[k].name, o[k].p, 4)) return -1;
+    return 0;
+}
+
+size_t nntk_rnnt_tdt_align_workspace_floats(int batch, int T, int max_label_len, int n_durations) {
+    return nntk_shim_rnnt_tdt_align_workspace_floats(batch, T, max_label_len, n_durations);
+}
+
+static int tdt_align_device(const char *who, const float *d_logits, int batch, int T, int V, const int *durations, int n_durations,
+                            const int *input_lengths, const int *labels, const int *label_lengths, int max_label_len, int blank, float sigma,
+                            const nntk_shim_rnnt_tdt_path *p, float *d_workspace) {
+    nntk_shim_clear_error();
+    if (tdt_check(who, batch, T, V, durations, n_durations, input_lengths, labels, label_lengths, max_label_len, blank, sigma)) return -1;
+    if (batch == 0) return 0;
+    tdt_out o[TDT_OUTS];
+    tdt_outs(o, p, 1, batch, T, max_label_len);
+    if (rnnt_check_ptr(who, "d_logits", d_logits, 16) || rnnt_check_ptr(who, "d_workspace", d_workspace, 16) || tdt_check_outs(who, o)) return -1;
+    const size_t f = sizeof(float);
+    rnnt_span sp[TDT_OUTS + 2];                                             /* outputs first */
+    for (int k = 0; k < TDT_OUTS; ++k) sp[k] = (rnnt_span){o[k].name, (uintptr_t)o[k].p, o[k].n * f};
+    sp[TDT_OUTS] = (rnnt_span){"d_logits", (uintptr_t)d_logits, (size_t)batch * T * (max_label_len + 1) * ((size_t)V + n_durations) * f};
+    sp[TDT_OUTS + 1] = (rnnt_span){"d_workspace", (uintptr_t)d_workspace,
+                                   nntk_shim_rnnt_tdt_align_workspace_floats(batch, T, max_label_len, n_durations) * f};
+    if (rnnt_overlap(who, sp, TDT_OUTS, TDT_OUTS + 2)) return -1;
+    int *len = rnnt_lengths(input_lengths, batch, T);
+    int rc = len ? nntk_shim_rnnt_tdt_align(d_logits, batch, T, V, durations, n_durations, len, labels, label_lengths, max_label_len, blank,
+                                            sigma, p, d_workspace) : -1;
+    free(len);
+    return rc;
+}
+
+#define TDT_PATH(lf, ld, fl, fd, lp, fp, sc)                                                                                              \
+    (&(nntk_shim_rnnt_tdt_path){.label_frames = (lf), .label_durations = (ld), .frame_labels = (fl), .frame_durations = (fd), .label_logp = (lp), \
+                                .frame_logp = (fp), .scores = (sc)})
+
+int nntk_rnnt_tdt_align_device(const float *d_logits, int batch, int T, int V, const int *durations, int n_durations,
+                               const int *input_lengths, const int *labels, const int *label_lengths, int max_label_len, int blank,
+                               float sigma, int *d_label_frames, int *d_label_durations, int *d_frame_labels, int *d_frame_durations,
+                               float *d_label_logp, float *d_frame_logp, float *d_scores, float *d_workspace) {
+    return tdt_align_device("nntk_rnnt_tdt_align_device", d_logits, batch, T, V, durations, n_durations, input_lengths, labels, label_lengths,
+                            max_label_len, blank, sigma,
+                            TDT_PATH(d_label_frames, d_label_durations, d_frame_labels, d_frame_durations, d_label_logp, d_frame_logp, d_scores),
+                            d_workspace);
+}
+
+/* the outputs live in one device block, in the entry's order, a part that is not asked for taking no room */
+int nntk_rnnt_tdt_align(const float *logits, int batch, int T, int V, const int *durations, int n_durations, const int *input_lengths,
+                        const int *labels, const int *label_lengths, int max_label_len, int blank, float sigma, int *label_frames,
+                        int *label_durations, int *frame_labels, int *frame_durations, float *label_logp, float *frame_logp, float *scores) {
+    static const char who[] = "nntk_rnnt_tdt_align";
+    nntk_shim_clear_error();
+    if (tdt_check(who, batch, T, V, durations, n_durations, input_lengths, labels, label_lengths, max_label_len, blank, sigma)) return -1;
+    if (batch == 0) return 0;
+    tdt_out o[TDT_OUTS];
+    tdt_outs(o, TDT_PATH(label_frames, label_durations, frame_labels, frame_durations, label_logp, frame_logp, scores), 0, batch, T, max_label_len);
+    if (rnnt_check_ptr(who, "logits", logits, 4) || tdt_check_outs(who, o)) return -1;
+    const size_t n = (size_t)batch * T * (max_label_len + 1) * ((size_t)V + n_durations);
+    size_t at[TDT_OUTS], total = 0;
+    for (int k = 0; k < TDT_OUTS; ++k) {
+        at[k] = total;
+        total += o[k].p ? o[k].n : 0;
+    }
+    float *d_x = nntk_devbuf_reserve(&t_a, n + 4);
+    float *d_o = nntk_devbuf_reserve(&t_b, total + 4);
+    float *d_ws = nntk_devbuf_reserve(&t_c, nntk_shim_rnnt_tdt_align_workspace_floats(batch, T, max_label_len, n_durations));
+    if (!d_x || !d_o || !d_ws || nntk_shim_upload(d_x, logits, n * sizeof(float))) return -1;
+    void *d[TDT_OUTS];
+    for (int k = 0; k < TDT_OUTS; ++k) d[k] = o[k].p ? (void *)(d_o + at[k]) : NULL;
+    if (tdt_align_device("nntk_rnnt_tdt_align_device", d_x, batch, T, V, durations, n_durations, input_lengths, labels, label_lengths,
+                         max_label_len, blank, sigma, TDT_PATH(d[0], d[1], d[2], d[3], d[4], d[5], d[6]), d_ws)) return -1;
+    for (int k = 0; k < TDT_OUTS; ++k)
+        if (o[k].p && o[k].n && nntk_shim_download(o[k].p, d[k], o[k].n * sizeof(float))) return -1;
+    return 0;
+}
+
 /* ---- the joiner ---- */
 static int joint_check(const char *who, int batch, int T, int U1, int J, int activation) {
     if (batch < 0 || T < 0 || U1 < 0) return rnnt_fail(who, "batch %d, T %d, U1 %d: none may be negative", batch, T, U1);

@@ -1355,34 +1355,41 @@ def rnnt_pruned_loss(logits, ranges, labels, max_label_len, label_lengths=None, 
     return loss, g
 
 
-def _rnnt_align_device(entry, size_fn, head, dev, dims, size_args, labels, label_lengths, input_lengths, blank, given, workspace):
-    """Both device forms of the alignment: the C entry by name, its argument head (the score source: the tensors, then B, T and the
-    widths as the entry takes them), dims = (B, T, U1), the workspace size function by name with its arguments, the five outputs as
-    given (None: made here)"""
+def _rnnt_align_outputs(B, T, U1, tdt):
+    """The alignment's outputs in the entries' order as (shape, is an int array): label_frames, frame_labels, label_logp, frame_logp,
+    scores; tdt: label_durations after label_frames and frame_durations after frame_labels"""
+    lab, frm = (B, U1 - 1), (B, T)
+    return [(s, True) for s in ((lab, lab, frm, frm) if tdt else (lab, frm))] + [(lab, False), (frm, False), ((B,), False)]
+
+
+def _rnnt_align_device(entry, size_fn, head, dev, dims, size_args, labels, label_lengths, input_lengths, blank, given, workspace, tail=()):
+    """The device forms of the alignment: the C entry by name, its argument head (the score source: the tensors, then B, T and the
+    widths as the entry takes them), dims = (B, T, U1), the workspace size function by name with its arguments, the outputs as
+    given (None: made here; False: not asked for, NULL to the entry and None in the result; seven of them: the token-and-duration
+    entry), tail: what the entry takes between blank and the outputs"""
     import torch
     B, T, U1 = dims
     lab, ll = _rnnt_labels(labels, label_lengths, B, U1 - 1)
     il, ilp = _ctc_lengths(input_lengths, B)
     workspace = _rnnt_workspace(workspace, dev, size_fn, *size_args)
-    shapes = (((B, U1 - 1), torch.int32), ((B, T), torch.int32), ((B, U1 - 1), torch.float32), ((B, T), torch.float32), ((B,), torch.float32))
-    outs = [torch.empty(s, dtype=d, device=dev) if g is None else g for (s, d), g in zip(shapes, given)]
+    shapes = [(s, torch.int32 if i else torch.float32) for s, i in _rnnt_align_outputs(B, T, U1, len(given) == 7)]
+    outs = [None if g is False else torch.empty(s, dtype=d, device=dev) if g is None else g for (s, d), g in zip(shapes, given)]
     for o, (s, d) in zip(outs, shapes):
-        assert tuple(o.shape) == s and o.dtype == d and o.is_contiguous(), "alignment outputs: %s %s" % (s, d)
-    check(getattr(capi.load(), entry)(*head, ilp, lab.ctypes.data_as(capi.ip), ll.ctypes.data_as(capi.ip), U1 - 1, blank,
-                                      *[C.c_void_p(o.data_ptr()) for o in outs], _dp(workspace)), entry)
+        assert o is None or (tuple(o.shape) == s and o.dtype == d and o.is_contiguous()), "alignment outputs: %s %s" % (s, d)
+    check(getattr(capi.load(), entry)(*head, ilp, lab.ctypes.data_as(capi.ip), ll.ctypes.data_as(capi.ip), U1 - 1, blank, *tail,
+                                      *[None if o is None else C.c_void_p(o.data_ptr()) for o in outs], _dp(workspace)), entry)
     return tuple(outs)
 
 
-def _rnnt_align_host(entry, head, dims, labels, label_lengths, input_lengths, blank):
-    """Both host forms of the alignment, as ``_rnnt_align_device``"""
+def _rnnt_align_host(entry, head, dims, labels, label_lengths, input_lengths, blank, tail=(), tdt=False):
+    """The host forms of the alignment, as ``_rnnt_align_device``"""
     B, T, U1 = dims
     lab, ll = _rnnt_labels(labels, label_lengths, B, U1 - 1)
     il, ilp = _ctc_lengths(input_lengths, B)
-    lf, fl = np.empty((B, U1 - 1), np.int32), np.empty((B, T), np.int32)
-    lp, fp, sc = np.empty((B, U1 - 1), np.float32), np.empty((B, T), np.float32), np.empty(B, np.float32)
-    check(getattr(capi.load(), entry)(*head, ilp, lab.ctypes.data_as(capi.ip), ll.ctypes.data_as(capi.ip), U1 - 1, blank,
-                                      lf.ctypes.data_as(capi.ip), fl.ctypes.data_as(capi.ip), _p(lp), _p(fp), _p(sc)), entry)
-    return lf, fl, lp, fp, sc
+    outs = [np.empty(s, np.int32 if i else np.float32) for s, i in _rnnt_align_outputs(B, T, U1, tdt)]
+    check(getattr(capi.load(), entry)(*head, ilp, lab.ctypes.data_as(capi.ip), ll.ctypes.data_as(capi.ip), U1 - 1, blank, *tail,
+                                      *[o.ctypes.data_as(capi.ip) if o.dtype == np.int32 else _p(o) for o in outs]), entry)
+    return tuple(outs)
 
 
 def rnnt_align_device(logits, labels, label_lengths=None, input_lengths=None, blank=0, label_frames=None, frame_labels=None,
@@ -1420,6 +1427,37 @@ def rnnt_fused_align(enc, pred, out_block, labels, label_lengths=None, input_len
     B, T, U1, J, V = _rnnt_fused_dims(enc, pred, out_block)
     return _rnnt_align_host("nntk_rnnt_fused_align", (_p(enc), _p(pred), _p(out_block), B, T, J, V, RNNT_ACTIVATIONS[activation]),
                             (B, T, U1), labels, label_lengths, input_lengths, blank)
+
+
+def _rnnt_tdt_head(ptr, shape, durations):
+    """the score source of the token-and-duration entries: the tensor, B, T, V, the durations and D -> (head, dims, D)"""
+    dur = np.ascontiguousarray(np.asarray(durations, dtype=np.int32)).reshape(-1)
+    B, T, U1, W = shape
+    return (ptr, B, T, W - dur.shape[0], dur.ctypes.data_as(capi.ip), dur.shape[0]), (B, T, U1), dur
+
+
+def rnnt_tdt_align_device(logits, labels, durations, label_lengths=None, input_lengths=None, blank=0, sigma=0.0, label_frames=None,
+                          label_durations=None, frame_labels=None, frame_durations=None, label_logp=None, frame_logp=None, scores=None,
+                          workspace=None):
+    """``nntk_rnnt_tdt_align_device``: the most probable path of logits [B,T,U1,V + D] (as for ``rnnt_tdt_loss_device``) through each
+    row's labels -> (label_frames [B,U1-1] int32, the frame out of which each label is emitted, and label_durations, the duration of that
+    move in frames, both -1 behind the row's labels; frame_labels [B,T] int32, the label count of the blank that leaves each frame, and
+    frame_durations, that blank's duration, both -1 where no blank of the path leaves the frame; label_logp [B,U1-1] and frame_logp
+    [B,T] float32, ln(p_tok p_dur) of those moves, 0 elsewhere; scores [B] float32 = ln of the path's probability, -inf without a path).
+    An output given as False is not computed; with all six but scores False the backtrack is not launched."""
+    head, dims, dur = _rnnt_tdt_head(_dp(logits), logits.shape, durations)
+    B, T, U1 = dims
+    return _rnnt_align_device("nntk_rnnt_tdt_align_device", "nntk_rnnt_tdt_align_workspace_floats", head, logits.device, dims,
+                              (B, T, U1 - 1, dur.shape[0]), labels, label_lengths, input_lengths, blank,
+                              (label_frames, label_durations, frame_labels, frame_durations, label_logp, frame_logp, scores), workspace,
+                              tail=(float(sigma),))
+
+
+def rnnt_tdt_align(logits, labels, durations, label_lengths=None, input_lengths=None, blank=0, sigma=0.0):
+    """The host-memory form (``nntk_rnnt_tdt_align``): logits [B,T,U1,V + D] numpy array."""
+    logits = _f32(logits)
+    head, dims, dur = _rnnt_tdt_head(_p(logits), logits.shape, durations)
+    return _rnnt_align_host("nntk_rnnt_tdt_align", head, dims, labels, label_lengths, input_lengths, blank, tail=(float(sigma),), tdt=True)
 
 
 def _ipv(t):
