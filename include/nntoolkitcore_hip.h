@@ -1147,7 +1147,7 @@ int nntk_rnnt_joint_backward_device(const float *d_out_fwd, const float *d_dout,
  * because a move multiplies two emissions.  Deterministic: no atomics, a cell's terms summed in one order (ascending i, blank before
  * label), the same bits on every call, the same loss bits with and without a gradient.  The joiner serves unchanged; the projection on
  * top is a Dense of width V + n_durations.  Decoding such a model: nntk_rnnt_tdt_greedy_decode_device below (greedy, one-shot and
- * streamed); forced alignment: nntk_rnnt_tdt_align_device below; beam search with durations is not in the library. */
+ * streamed); forced alignment: nntk_rnnt_tdt_align_device below; beam search with durations: nntk_rnnt_tdt_beam_decode_device below. */
 size_t nntk_rnnt_tdt_workspace_floats(int batch, int T, int max_label_len, int n_durations, int want_grad);
 int nntk_rnnt_tdt_loss_device(const float *d_logits, int batch, int T, int V, const int *durations, int n_durations,
                               const int *input_lengths, const int *labels, const int *label_lengths, int max_label_len, int blank,
@@ -1401,7 +1401,7 @@ int nntk_rnnt_greedy_decode(NntkRnntDecoder d, NntkRnntDecodeState state, const 
  * are those of nntk_rnnt_greedy_decode_device, with d_label_durations among the outputs that may not overlap, and V + D must fit
  * the kernel's LDS with max(4H, V + D) in V's place.  Refused on the host, nothing written: this call on a handle of
  * nntk_rnnt_decoder_create; nntk_rnnt_greedy_decode*, and every nntk_rnnt_beam_* decode, state create and size query (0), on a
- * handle of nntk_rnnt_tdt_decoder_create.  Deterministic as the greedy call: a row's bits do not depend on the batch, its position,
+ * handle of nntk_rnnt_tdt_decoder_create (nntk_rnnt_tdt_beam_decode_device serves it).  Deterministic as the greedy call: a row's bits do not depend on the batch, its position,
  * the T padding or how many rows share a workgroup. */
 NntkRnntDecoder nntk_rnnt_tdt_decoder_create(NntkRnntDecoderConfig cfg, const int *durations, int n_durations, const float *d_embed,
                                              const float *d_lstm, const float *d_pred_proj, const float *d_out);
@@ -1410,6 +1410,58 @@ int nntk_rnnt_tdt_greedy_decode_device(NntkRnntDecoder d, NntkRnntDecodeState st
                                        int *d_out_lengths, float *d_scores);
 int nntk_rnnt_tdt_greedy_decode(NntkRnntDecoder d, NntkRnntDecodeState state, const float *enc, int batch, int T, const int *n_frames,
                                 int max_labels, int *labels_out, int *label_frames, int *label_durations, int *out_lengths, float *scores);
+
+/* ---- RNN-Transducer: token-and-duration beam search (csrc/hip/rnnt_tdt_beam.hip; INTEGRATION.md "RNN-Transducer: token-and-duration
+ *      beam search") ----
+ * The model, the blocks, S = max_symbols_per_frame and the duration table d_0 < .. < d_{D-1} are those of the handle of
+ * nntk_rnnt_tdt_decoder_create; Dmax = d_{D-1}, W = beam_width.  A hypothesis is a label sequence y, a score (natural log of mass, in
+ * double) and the prediction-network state after blank, y_1 .. y_|y|.  One pass over [J][V + D] for a hypothesis at frame t gives x;
+ * lp_tok[v] = (x[v] - max) - log(sum exp(x[0..V) - max)) as the classic beam search forms logp (the difference in float, the rest in
+ * double); lp_dur[k] = (x[V + k] - max') - log(sum exp(x[V..V+D) - max')) as the TDT greedy kernel forms it (the maximum exact, expf
+ * per element, the sum in double with k ascending).  A move's score is score + (lp_tok + lp_dur[k]) in double.  Per row b, n = n_frames[b]:
+ *   bucket[0 .. n]: ordered lists of (y, score, state), in insertion order
+ *   bucket[0] = [ ((), 0, LSTM step on embed[blank] from zero) ]
+ *   for t in 0 .. n-1:
+ *       if bucket[t] is empty: continue            never joined, never projected, never read (the frame may hold NaN)
+ *       C = the W best of bucket[t]                score descending, exact ties to the lower insertion index
+ *       for depth in 0 .. S:                       depth = labels emitted in frame t with duration 0
+ *           for i, hyp in enumerate(C):            position order
+ *               for k ascending with d_k > 0:      a blank never takes duration 0
+ *                   cand = (hyp.y, hyp.score + (lp_tok[blank] + lp_dur[k])); f = min(t + d_k, n)
+ *                   -inf: drop; the same label sequence already in bucket[f]: entry.score = logaddexp(entry.score, cand.score)
+ *                   (the entry keeps its index and state); else append to bucket[f]
+ *           cells = { (i, v, k): C[i].score + (lp_tok[v] + lp_dur[k]) : v != blank, C[i] has fewer than max_labels labels,
+ *                     the cell's score > -inf, and d_k > 0 when depth == S }
+ *           sel = the W best cells, score descending, exact ties to the lower (i*V + v)*D + k
+ *           for each of sel, in that order: hyp' = (C[i].y + v, score, LSTM step on embed[v] from C[i]'s state)
+ *               d_k == 0: hyp' joins the next C;  else merged into / appended to bucket[min(t + d_k, n)] as above
+ *           if depth == S or the next C is empty: break
+ *   result: the W best of bucket[n], the first nbest of them
+ * A move that lands at or beyond n ends in bucket[n]: the greedy decoder's end rule, "a jump past n ends the row" (the loss's rule,
+ * a blank landing exactly on n, would let most of a beam die on the last frames).  Merging happens only in buckets.  Both heads
+ * depend on (t, y) only, so the search is the lattice sum: with nothing pruned and S and max_labels at least the label count, a
+ * hypothesis's score is the log of the total mass of its paths under that end rule -- not minus nntk_rnnt_tdt_loss_device, whose
+ * paths end with a blank landing exactly on T_b.  "Same label sequence" is decided on the labels (a hash only pre-filters).
+ *   d_labels_out [batch][nbest][max_labels]: hypothesis k's labels, then -1; d_out_lengths [batch][nbest]; d_scores [batch][nbest]: the
+ *   double score rounded to f32.  A slot without a hypothesis holds -1, -1 and -inf; n_frames[b] == 0 gives the empty hypothesis with
+ *   score 0 in slot 0.  Every element of the three outputs is written.  Frames at or beyond n and frames nobody lands on are not read.
+ *   d_workspace: nntk_rnnt_tdt_beam_workspace_floats(d, batch, beam_width, max_labels) floats, 16-byte aligned.  With
+ *   S' = min(S, max_labels), per row: a ring of Dmax + 1 frames of (S' + 2) W hypothesis slots of 2H + J + max_labels + 2 words, a
+ *   ring of Dmax + 1 buckets of 2 W (S' + 1) Dmax entries of 3 words (a source frame gives a bucket at most W (S' + 1) blank entries
+ *   and W (S' + 1) selected cells, and Dmax source frames reach it) and W V logits; plus 3 words a row; each array padded to 4 words.
+ * Checks, all on the host before anything is enqueued (-1, nntk_last_error(), nothing written): those of
+ * nntk_rnnt_beam_decode_device without a state, plus: the handle has durations (a handle of nntk_rnnt_decoder_create is refused with
+ * a message that names nntk_rnnt_beam_decode_device, and its size query is 0; the nntk_rnnt_beam_* entries keep refusing a handle
+ * with durations); max(4H, V + D) floats a hypothesis fit the kernel's LDS; the rings stay inside 2^29 slots and entries.
+ * Deterministic: no atomics, the same bits on every call; a row's bits do not depend on the other rows, its position in the batch,
+ * the T padding, or how many hypotheses share a pass over a matrix.  One launch on the calling thread's stream.  The host-pointer
+ * form uploads, runs the device form on a workspace of its own and downloads.  Not in this call, each a follow-up on its kernel:
+ * streaming with a carried ring, language-model fusion, per-label frames, durations and confidences, length normalisation. */
+size_t nntk_rnnt_tdt_beam_workspace_floats(NntkRnntDecoder d, int batch, int beam_width, int max_labels);
+int nntk_rnnt_tdt_beam_decode_device(NntkRnntDecoder d, const float *d_enc, int batch, int T, const int *n_frames, int beam_width, int nbest,
+                                     int max_labels, int *d_labels_out, int *d_out_lengths, float *d_scores, float *d_workspace);
+int nntk_rnnt_tdt_beam_decode(NntkRnntDecoder d, const float *enc, int batch, int T, const int *n_frames, int beam_width, int nbest,
+                              int max_labels, int *labels_out, int *out_lengths, float *scores);
 
 /* ---- RNN-Transducer: beam search (csrc/hip/rnnt_beam.hip; INTEGRATION.md "RNN-Transducer: beam search") ----
  * The model, the weight blocks, the decoder handle and max_symbols_per_frame (S below) are those of greedy decoding; W = beam_width.

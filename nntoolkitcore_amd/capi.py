@@ -542,6 +542,9 @@ SIGNATURES = {
     "nntk_rnnt_tdt_greedy_decode_device": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, ip, C.c_int, vp, vp, vp, vp, vp]),
     "nntk_rnnt_tdt_greedy_decode": (C.c_int, [vp, vp, fp, C.c_int, C.c_int, ip, C.c_int, ip, ip, ip, ip, fp]),
     # RNN-Transducer: beam search with n-best, one-shot and streamed (INTEGRATION.md "RNN-Transducer: beam search")
+    "nntk_rnnt_tdt_beam_workspace_floats": (C.c_size_t, [vp, C.c_int, C.c_int, C.c_int]),
+    "nntk_rnnt_tdt_beam_decode_device": (C.c_int, [vp, vp, C.c_int, C.c_int, ip, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]),
+    "nntk_rnnt_tdt_beam_decode": (C.c_int, [vp, fp, C.c_int, C.c_int, ip, C.c_int, C.c_int, C.c_int, ip, ip, fp]),
     "nntk_rnnt_beam_workspace_floats": (C.c_size_t, [vp, C.c_int, C.c_int, C.c_int]),
     "nntk_rnnt_beam_decode_device": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, ip, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]),
     "nntk_rnnt_beam_decode": (C.c_int, [vp, vp, fp, C.c_int, C.c_int, ip, C.c_int, C.c_int, C.c_int, ip, ip, fp]),

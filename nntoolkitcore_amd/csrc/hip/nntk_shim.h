@@ -338,6 +338,22 @@ int nntk_shim_rnnt_tdt_dec_rows_per_group(int batch, int H, int J, int V, int D)
 int nntk_shim_rnnt_tdt_greedy(const nntk_shim_rnnt_dec *m, const nntk_shim_rnnt_tdt_durs *du, const float *d_enc, int batch, int T,
                               const int *h_n_frames, int max_labels, float *d_st_f, double *d_st_score, int *d_st_i, int *d_st_owed,
                               int *d_labels, int *d_frames, int *d_durations, int *d_lengths, float *d_scores);
+/* ---- token-and-duration beam search (rnnt_tdt_beam.hip) on the same blocks and durations, one-shot.  One workgroup runs a row's whole
+ *      search; the hypotheses of a depth share passes over the matrices in groups of NNTK_RNNT_DEC_GROUP where the group's LDS fits
+ *      (max(4H, V + D) floats a hypothesis), else one by one (nntk_shim_rnnt_tdt_beam_group; _set_group(1 or NNTK_RNNT_DEC_GROUP) pins it
+ *      for tests and timing, 0 = automatic; the bits do not depend on it).  The workspace, with S' = min(max_symbols_per_frame,
+ *      max_labels), Dmax the largest duration and W = beam_width: the rows' frame counts [batch], two counters per row that the kernel
+ *      leaves for timing tools (frames joined | LSTM steps), then per row a ring of Dmax + 1 frames of (S' + 2) W hypothesis slots
+ *      (h | c | g, max_labels labels, length and hash), a ring of Dmax + 1 buckets of 2 W (S' + 1) Dmax entries (a double and a slot
+ *      each) and W V logits; every array padded to 4 words.  0: batch <= 0 or sizes beyond 2^29 slots or entries.  h_n_frames HOST
+ *      [batch], checked by the caller, copied in stream order into the workspace; d_ws 16-byte aligned. ---- */
+size_t nntk_shim_rnnt_tdt_beam_workspace_floats(int batch, int H, int J, int V, int max_sym, int dmax, int beam_width, int max_labels);
+int nntk_shim_rnnt_tdt_beam_fits(int H, int J, int V, int D);                  /* the kernel's LDS at one hypothesis a pass */
+int nntk_shim_rnnt_tdt_beam_group(int beam_width, int H, int J, int V, int D);
+void nntk_shim_rnnt_tdt_beam_set_group(int group);
+int nntk_shim_rnnt_tdt_beam(const nntk_shim_rnnt_dec *m, const nntk_shim_rnnt_tdt_durs *du, const float *d_enc, int batch, int T,
+                            const int *h_n_frames, int beam_width, int nbest, int max_labels, int *d_labels, int *d_lengths, float *d_scores,
+                            float *d_ws);
 /* ---- transducer beam search (rnnt_beam.hip) on the greedy decoder's blocks.  One workgroup runs a row's whole search; the hypotheses
  *      of a depth share passes over the matrices in groups of NNTK_RNNT_DEC_GROUP where the group's LDS fits, else one by one
  *      (nntk_shim_rnnt_beam_group; nntk_shim_rnnt_beam_set_group(1 or NNTK_RNNT_DEC_GROUP) pins it for tests and timing, 0 = automatic;

@@ -1,0 +1,550 @@
+// rnnt_tdt_beam.hip -- beam search for a token-and-duration transducer (TDT) with the network inside the search (the contract:
+// include/nntoolkitcore_hip.h, "RNN-Transducer: token-and-duration beam search").  One launch runs every row's whole search.
+//
+// Why not rnnt_beam.hip on a [J][V + D] block.  The classic search is frame-synchronous: one set A enters frame t, one set B leaves it.
+// Here a move carries a duration, so the hypotheses that leave frame t land on t + 1 .. t + Dmax, and a frame nobody lands on is never
+// joined.  The search therefore keeps BUCKETS, one list of (score, slot) per future frame, instead of A and B.
+//
+// Work split.  One workgroup of RD_THREADS lanes owns a row and runs its frames, depths and hypotheses; rows never talk to each other:
+// no flags, no spins, no atomics.  The hypotheses of a depth go through the joiner, the [J][V + D] block and h U in groups of R
+// (NNTK_RNNT_DEC_GROUP where the group's LDS fits, else 1) with rd_matvec's bits whatever R.  A lane owns column n of [0, V + D), so both
+// heads land in LDS in one pass; the token head's max and sum-exp cover [0, V) with the reductions of rnnt_dec_common.hpp, the duration
+// head (at most 8 values) is reduced serially by one lane per hypothesis -- lane RD_THREADS - 1 - r, while the others sum the token
+// head -- exactly as rnnt_tdt_decode.hip does, and leaves lp_dur [D] doubles in LDS.  These products are matrix-vector products for at
+// most 4 hypotheses, bound to the greedy kernel's four fmaf chains: no matrix instructions.
+//
+// The ring.  A slot (h | c | g, labels, length, hash) written in frame t is referenced by buckets up to t + Dmax, so the slots form a
+// ring of Dmax + 1 frames of (S' + 2) W slots, S' = min(max_symbols_per_frame, max_labels): level 0 the frame's C, one level per depth
+// for the selected cells.  The buckets form a ring of Dmax + 1 lists; frame t uses position t mod (Dmax + 1) of both.  bucket[n] sits
+// where n would: the clamp min(t + d, n) only redirects moves into it.  At the start of frame t the W best of bucket[t] are copied into
+// frame t's level 0 from frames t - Dmax .. t - 1, which are other ring positions; the bucket is then empty for frame t + Dmax + 1.  An
+// empty bucket[t] skips the frame before any barrier.  A bucket holds at most 2 W (S' + 1) Dmax entries: a source frame contributes at
+// most W (S' + 1) blank entries (equal label sequences merge) and W (S' + 1) selected cells, and Dmax source frames reach one bucket.
+// The initial hypothesis lives in the ring position of frame -1.
+//
+// Selection.  The W best of the W V D cells are found by W rounds of a workgroup arg-max over (score descending, index (i V + v) D + k
+// ascending), each round restricted to what ranks behind the round before.  The score separates, base_i + (lp_tok[i][v] + lp_dur[i][k]):
+// a lane reads its columns' logits from the workspace and the hypothesis's D values of lp_dur from LDS; no [W][V][D] array exists.  Two
+// selected cells (i, v, k) and (i, v, k') are the same hypothesis up to score and landing frame: they share ONE slot and one LSTM step.
+//
+// Merging.  A move into a bucket looks for its label sequence there: one wavefront per candidate scans the bucket (length and hash
+// pre-filter, equality on the labels), then lane 0 of the workgroup applies the candidates in order -- logaddexp into the entry found, or
+// append.  Two candidates of one phase can only share a label sequence by sharing a slot (one hypothesis, two durations, both clamped to
+// n); the applying lane finds that twin among the entries the phase appended to bucket[n].
+//
+// Barriers per depth, nC hypotheses in C, W' cells selected, U of them distinct steps: 4 ceil(nC / R) (z | max parts | sum parts and the
+// duration head | lp ready) + 1 + 2 (blank moves: built | found | applied) + 2 a round, W' + 1 rounds at most, + 1 + 3 (twins | slots | lists) +
+// 4 ceil(U / R) (the classic step) + 2 (label moves).  A joined frame adds 2 W + 3 for its C and its end; a skipped frame adds none.
+//
+// LDS.  TbShared (the reductions' scratch; C: slot, score, length, hash, max, log-sum-exp, lp_blank, lp_dur [W][8] doubles; the selected
+// cells; the candidates of a phase, W * 8 of them; the buckets' counts), 10.8 KiB at R = 4, then per group row
+// h [Hp] | c [Hp] | z [Jp] | buf [max(4H, V + D)]: the classic beam's layout with V + D in V's place.  H = J = 640, V = 1024, D = 5,
+// R = 4: 10.8 + 4 * 17.5 = 80.8 KiB.
+//
+// Workspace (tb_layout; nntk_shim_rnnt_tdt_beam_workspace_floats): the rows' frame counts, two counters per row (frames joined | LSTM
+// steps, for the timing tool), then per row  bscore [Dmax + 1][cap] doubles | bslot [Dmax + 1][cap] | states [slots][2H + J] |
+// labels [slots][max_labels] | meta [slots][2] | logits [W][V],  cap = 2 W (S' + 1) Dmax, slots = (Dmax + 1)(S' + 2) W.
+#include <limits.h>
+#include "rnnt_dec_common.hpp"
+
+#define TB_MAX_W NNTK_RNNT_BEAM_MAX_W
+#define TB_MAX_D NNTK_RNNT_TDT_MAX_DURATIONS
+#define TB_MAX_RING (NNTK_RNNT_TDT_MAX_DURATION + 1)
+
+struct TbLayout {                          // offsets in floats from the row's block, each a multiple of 4
+    size_t bscore, bslot, states, labels, meta, logits, row;
+    int frame_slots, cap, SF, depths;      // slots a frame, entries a bucket, floats of a state, S'
+};
+
+static TbLayout tb_layout(int H, int J, int V, int max_sym, int dmax, int W, int max_labels) {
+    TbLayout l;
+    l.depths = max_sym < max_labels ? max_sym : max_labels;
+    l.frame_slots = (l.depths + 2) * W; l.cap = 2 * W * (l.depths + 1) * dmax; l.SF = 2 * H + J;
+    const size_t ring = (size_t)dmax + 1, slots = ring * l.frame_slots;
+    size_t at = 0;
+    auto take = [&at](size_t n) { const size_t a = at; at += (n + 3) & ~(size_t)3; return a; };
+    l.bscore = take(2 * ring * l.cap);
+    l.bslot = take(ring * l.cap);
+    l.states = take(slots * l.SF);
+    l.labels = take(slots * max_labels);
+    l.meta = take(2 * slots);
+    l.logits = take((size_t)W * V);
+    l.row = at;
+    return l;
+}
+
+// the ring's slots and entries stay inside 2^29, so that every index is an int
+static bool tb_sizes_ok(int max_sym, int dmax, int W, int max_labels) {
+    const size_t depths = (size_t)(max_sym < max_labels ? max_sym : max_labels);
+    return max_sym >= 1 && max_labels >= 1 && dmax >= 1 && W >= 1 && 2 * ((size_t)dmax + 1) * (depths + 2) * W * dmax <= (size_t)INT_MAX / 4;
+}
+
+static size_t tb_head(int batch) { return (((size_t)batch + 3) & ~(size_t)3) + ((2 * (size_t)batch + 3) & ~(size_t)3); }
+
+struct TbArgs {
+    const float *enc;                      // [batch][T][J]
+    const float *table, *U, *proj, *out;   // as in rnnt_tdt_decode.hip: out [J][V + D] b[V + D]
+    float *ws;
+    int *labels, *lengths;                 // [batch][nbest][max_labels] | [batch][nbest]
+    float *scores;
+    TbLayout lay;
+    size_t ws_head;
+    int batch, T, V, blank, H, J, act, max_sym, W, nbest, max_labels;
+    nntk_shim_rnnt_tdt_durs du;
+};
+
+template <int R> struct TbShared {
+    double red_sum[R][RD_WAVES];
+    double red_s[RD_WAVES];
+    double c_score[TB_MAX_W], c_lse[TB_MAX_W], c_lpb[TB_MAX_W], n_score[TB_MAX_W];
+    double lp_dur[TB_MAX_W][TB_MAX_D];
+    double cd_s[TB_MAX_W * TB_MAX_D];
+    double best_s;
+    float red_max[R][RD_WAVES];
+    float c_max[TB_MAX_W];
+    int red_i[RD_WAVES];
+    int c_slot[TB_MAX_W], c_len[TB_MAX_W], n_i[TB_MAX_W], n_v[TB_MAX_W], n_k[TB_MAX_W], n_slot[TB_MAX_W], n_par[TB_MAX_W], n_len[TB_MAX_W];
+    int st_src[TB_MAX_W], st_lab[TB_MAX_W], st_dst[TB_MAX_W];
+    unsigned c_hash[TB_MAX_W], n_hash[TB_MAX_W];
+    int cd_slot[TB_MAX_W * TB_MAX_D], cd_f[TB_MAX_W * TB_MAX_D], cd_found[TB_MAX_W * TB_MAX_D];
+    int nb[TB_MAX_RING];
+    int best_i, nC, nStep, nCand;
+};
+
+static size_t tb_lds_bytes(int R, int H, int J, int VD) {
+    const size_t Hp = (size_t)(H + 3) & ~(size_t)3, Jp = (size_t)(J + 3) & ~(size_t)3;
+    const size_t W = 4 * (size_t)H > (size_t)VD ? 4 * (size_t)H : (size_t)VD, Wp = (W + 3) & ~(size_t)3;
+    const size_t fixed = R == 1 ? sizeof(TbShared<1>) : sizeof(TbShared<NNTK_RNNT_DEC_GROUP>);
+    return ((fixed + 15) & ~(size_t)15) + (size_t)R * (2 * Hp + Jp + Wp) * sizeof(float);
+}
+
+__device__ __forceinline__ double tb_logaddexp(double x, double y) {         // both finite
+    const double m = x > y ? x : y, d = x > y ? y - x : x - y;
+    return m + log1p(exp(d));
+}
+
+// durations[i] out of the kernel arguments: a select chain, so that the table stays in scalar registers
+__device__ __forceinline__ int tb_duration(const nntk_shim_rnnt_tdt_durs &du, int i) {
+    int d = du.dur[0];
+#pragma unroll
+    for (int j = 1; j < TB_MAX_D; ++j) d = i == j ? du.dur[j] : d;
+    return d;
+}
+
+template <int R>
+__global__ __launch_bounds__(RD_THREADS) void rnnt_tdt_beam_kernel(const TbArgs a) {
+    extern __shared__ __align__(16) unsigned char tb_smem[];
+    TbShared<R> &sh = *(TbShared<R> *)tb_smem;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int H = a.H, J = a.J, V = a.V, D = a.du.n, VD = V + D, G = 4 * H, W = a.W, ML = a.max_labels, SF = a.lay.SF;
+    const int Hp = (H + 3) & ~3, Jp = (J + 3) & ~3, Wp = ((G > VD ? G : VD) + 3) & ~3;
+    const int RING = tb_duration(a.du, D - 1) + 1, cap = a.lay.cap, Dp = __popc(a.du.pos_mask);
+    float *sh_h = (float *)(tb_smem + ((sizeof(TbShared<R>) + 15) & ~(size_t)15));
+    float *sh_c = sh_h + R * Hp, *sh_z = sh_c + R * Hp, *sh_buf = sh_z + R * Jp;
+    const float *pbias = a.proj ? a.proj + (size_t)H * J : nullptr;
+    const float *obias = a.out + (size_t)J * VD;
+    const int b = blockIdx.x;
+    float *row = a.ws + a.ws_head + (size_t)b * a.lay.row;
+    double *bscore = (double *)(row + a.lay.bscore);
+    float *states = row + a.lay.states, *lg = row + a.lay.logits;
+    int *bslot = (int *)(row + a.lay.bslot), *labs = (int *)(row + a.lay.labels), *meta = (int *)(row + a.lay.meta);
+    const int n = ((const int *)a.ws)[b];
+    int joined = 0, steps = 0;                                               // lane 0's counters, for the timing tool
+
+    // the workgroup's best (score descending, index ascending; INT_MAX: none) -> sh.best_s, sh.best_i
+    auto block_best = [&](double s, int idx) {
+        for (int off = 32; off > 0; off >>= 1) {
+            const double os = __shfl_xor(s, off);
+            const int oi = __shfl_xor(idx, off);
+            if (oi != INT_MAX && (idx == INT_MAX || os > s || (os == s && oi < idx))) { s = os; idx = oi; }
+        }
+        if (lane == 0) { sh.red_s[wave] = s; sh.red_i[wave] = idx; }
+        __syncthreads();
+        if (tid == 0) {
+            s = sh.red_s[0]; idx = sh.red_i[0];
+            for (int w = 1; w < RD_WAVES; ++w) {
+                const double os = sh.red_s[w];
+                const int oi = sh.red_i[w];
+                if (oi != INT_MAX && (idx == INT_MAX || os > s || (os == s && oi < idx))) { s = os; idx = oi; }
+            }
+            sh.best_s = s; sh.best_i = idx;
+        }
+        __syncthreads();
+    };
+
+    // the `count` best entries of ring position p's bucket (score descending, insertion index ascending) -> sh.n_slot, sh.n_score
+    auto bucket_best = [&](int p, int count) {
+        const int nB = sh.nb[p];
+        double prev_s = INFINITY;
+        int prev_i = -1, got = 0;
+        for (int k = 0; k < count; ++k) {
+            double bs = -INFINITY;
+            int bi = INT_MAX;
+            for (int e = tid; e < nB; e += RD_THREADS) {
+                const double s = bscore[(size_t)p * cap + e];
+                if ((s < prev_s || (s == prev_s && e > prev_i)) && (bi == INT_MAX || s > bs)) { bs = s; bi = e; }
+            }
+            block_best(bs, bi);
+            if (sh.best_i == INT_MAX) break;
+            prev_s = sh.best_s; prev_i = sh.best_i;
+            if (tid == 0) { sh.n_slot[k] = bslot[(size_t)p * cap + prev_i]; sh.n_score[k] = prev_s; }
+            ++got;
+        }
+        __syncthreads();
+        return got;
+    };
+
+    // the prediction network for the steps k0 .. k0 + cnt - 1 of the list: from slot st_src (-1: the zero state) on label st_lab into st_dst
+    auto step_group = [&](int k0, int cnt) {
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            const int src = r < cnt ? sh.st_src[k0 + r] : -1;
+            const float *st = states + (size_t)(src < 0 ? 0 : src) * SF;
+            for (int j = tid; j < H; j += RD_THREADS) {
+                sh_h[r * Hp + j] = src >= 0 ? st[j] : 0.0f;
+                sh_c[r * Hp + j] = src >= 0 ? st[H + j] : 0.0f;
+            }
+        }
+        __syncthreads();
+        for (int nn = tid; nn < G; nn += RD_THREADS) {
+            float hu[R];
+            rd_matvec<R>(a.U, H, G, nn, sh_h, Hp, hu);
+#pragma unroll
+            for (int r = 0; r < R; ++r)
+                if (r < cnt) sh_buf[r * Wp + nn] = a.table[(size_t)sh.st_lab[k0 + r] * G + nn] + hu[r];
+        }
+        __syncthreads();
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            if (r >= cnt) continue;
+            const float *zg = sh_buf + r * Wp;
+            float *st = states + (size_t)sh.st_dst[k0 + r] * SF;
+            for (int j = tid; j < H; j += RD_THREADS) {
+                const float gi = rd_sigmoid(zg[j]), gf = rd_sigmoid(zg[H + j]), gg = tanhf(zg[2 * H + j]), go = rd_sigmoid(zg[3 * H + j]);
+                const float c = gf * sh_c[r * Hp + j] + gi * gg;
+                const float h = go * tanhf(c);
+                sh_h[r * Hp + j] = h;
+                st[j] = h; st[H + j] = c;
+            }
+        }
+        __syncthreads();
+        for (int j = tid; j < J; j += RD_THREADS) {
+            if (a.proj) {
+                float ph[R];
+                rd_matvec<R>(a.proj, H, J, j, sh_h, Hp, ph);
+#pragma unroll
+                for (int r = 0; r < R; ++r)
+                    if (r < cnt) states[(size_t)sh.st_dst[k0 + r] * SF + 2 * H + j] = ph[r] + pbias[j];
+            } else {
+#pragma unroll
+                for (int r = 0; r < R; ++r)
+                    if (r < cnt) states[(size_t)sh.st_dst[k0 + r] * SF + 2 * H + j] = sh_h[r * Hp + j];
+            }
+        }
+        __syncthreads();
+    };
+
+    // frame t for the hypotheses i0 .. i0 + cnt - 1 of C, one pass over [J][V + D]: the token logits into the workspace, their max and
+    // log-sum-exp, lp_tok[blank] and the duration head's lp_dur [D]
+    auto heads_group = [&](int i0, int cnt, int t) {
+        const float *e = a.enc + ((size_t)b * a.T + t) * J;
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            if (r < cnt) {
+                const float *g = states + (size_t)sh.c_slot[i0 + r] * SF + 2 * H;
+                for (int j = tid; j < J; j += RD_THREADS) sh_z[r * Jp + j] = rd_act(a.act, e[j] + g[j]);
+            } else {
+                for (int j = tid; j < J; j += RD_THREADS) sh_z[r * Jp + j] = 0.0f;
+            }
+        }
+        __syncthreads();
+        float m[R];
+#pragma unroll
+        for (int r = 0; r < R; ++r) m[r] = -INFINITY;
+        for (int nn = tid; nn < VD; nn += RD_THREADS) {
+            float x[R];
+            rd_matvec<R>(a.out, J, VD, nn, sh_z, Jp, x);
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                x[r] += obias[nn];
+                sh_buf[r * Wp + nn] = x[r];
+                if (nn < V) {
+                    if (x[r] > m[r]) m[r] = x[r];
+                    if (r < cnt) lg[(size_t)(i0 + r) * V + nn] = x[r];
+                }
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            for (int off = 32; off > 0; off >>= 1) {
+                const float om = __shfl_xor(m[r], off);
+                if (om > m[r]) m[r] = om;
+            }
+            if (lane == 0) sh.red_max[r][wave] = m[r];
+        }
+        __syncthreads();
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            m[r] = sh.red_max[r][0];
+            for (int w = 1; w < RD_WAVES; ++w) {
+                const float om = sh.red_max[r][w];
+                if (om > m[r]) m[r] = om;
+            }
+            const double sum = rd_wave_sum_exp(sh_buf + r * Wp, V, tid, m[r]);
+            if (lane == 0) sh.red_sum[r][wave] = sum;
+            if (tid == 0 && r < cnt) sh.c_max[i0 + r] = m[r];
+            if (tid == RD_THREADS - 1 - r && r < cnt) {                      // the duration head, serially, i ascending
+                const float *xd = sh_buf + r * Wp + V;
+                float bm = xd[0];
+                for (int i = 1; i < D; ++i)
+                    if (xd[i] > bm) bm = xd[i];
+                double ds = 0.0;
+                for (int i = 0; i < D; ++i) ds += (double)expf(xd[i] - bm);
+                const double ld = log(ds);
+                for (int i = 0; i < D; ++i) sh.lp_dur[i0 + r][i] = ((double)xd[i] - (double)bm) - ld;
+            }
+        }
+        __syncthreads();
+        if (tid < cnt) {
+            const int r = tid, i = i0 + r;
+            double sum = 0.0;
+            for (int w = 0; w < RD_WAVES; ++w) sum += sh.red_sum[r][w];
+            const double lse = log(sum);
+            sh.c_lse[i] = lse;
+            sh.c_lpb[i] = (double)(sh_buf[r * Wp + a.blank] - sh.c_max[i]) - lse;
+        }
+        __syncthreads();
+    };
+
+    // the phase's candidates cd_s | cd_slot | cd_f (the landing frame, -1: dropped) move into their buckets, in order
+    auto merge_phase = [&](int nCand) {
+        for (int c = wave; c < nCand; c += RD_WAVES) {
+            int f = -1;
+            const int fr = sh.cd_f[c];
+            if (fr >= 0) {
+                const int p = fr % RING, cnt = sh.nb[p], slot = sh.cd_slot[c], len = meta[2 * slot], hs = meta[2 * slot + 1];
+                const int *q = labs + (size_t)slot * ML;
+                for (int e = lane; e < cnt; e += 64) {
+                    const int s = bslot[(size_t)p * cap + e];
+                    if (meta[2 * s] != len || meta[2 * s + 1] != hs) continue;
+                    const int *pl = labs + (size_t)s * ML;
+                    bool eq = true;
+                    for (int j = 0; j < len; ++j)
+                        if (pl[j] != q[j]) { eq = false; break; }
+                    if (eq) f = e;
+                }
+                for (int off = 32; off > 0; off >>= 1) {
+                    const int of = __shfl_xor(f, off);
+                    if (of > f) f = of;
+                }
+            }
+            if (lane == 0) sh.cd_found[c] = f;
+        }
+        __syncthreads();
+        if (tid == 0) {
+            const int pn = n % RING, start_n = sh.nb[pn];
+            for (int c = 0; c < nCand; ++c) {
+                const int fr = sh.cd_f[c];
+                if (fr < 0) continue;
+                const int p = fr % RING, nbp = sh.nb[p], slot = sh.cd_slot[c];
+                const double s = sh.cd_s[c];
+                int e = sh.cd_found[c];
+                if (e < 0 && fr == n)                                        // its twin of this phase: the same slot, clamped as well
+                    for (int e2 = start_n; e2 < nbp; ++e2)
+                        if (bslot[(size_t)pn * cap + e2] == slot) { e = e2; break; }
+                double *at = bscore + (size_t)p * cap;
+                if (e >= 0) at[e] = tb_logaddexp(at[e], s);
+                else if (nbp < cap) { bslot[(size_t)p * cap + nbp] = slot; at[nbp] = s; sh.nb[p] = nbp + 1; }
+            }
+        }
+        __syncthreads();
+    };
+
+    for (int i = tid; i < R * (2 * Hp + Jp); i += RD_THREADS) sh_h[i] = 0.0f;
+    const int slot0 = (RING - 1) * a.lay.frame_slots;                        // frame -1's ring position
+    if (tid < RING) sh.nb[tid] = tid == 0;
+    if (tid == 0) {
+        meta[2 * slot0] = 0; meta[2 * slot0 + 1] = 0; bslot[0] = slot0; bscore[0] = 0.0;
+        sh.st_src[0] = -1; sh.st_lab[0] = a.blank; sh.st_dst[0] = slot0;
+    }
+    __syncthreads();
+    step_group(0, 1);                                                        // the step on embed[blank] from the zero state
+
+    for (int t = 0; t < n; ++t) {
+        const int p = t % RING;
+        if (sh.nb[p] == 0) continue;                                         // nobody landed here: no barrier, no read of the frame
+        const int nA = bucket_best(p, W), fb = p * a.lay.frame_slots;
+        for (int k = 0; k < nA; ++k) {                                       // C = the W best, into the frame's level 0
+            const int src = sh.n_slot[k], dst = fb + k, len = meta[2 * src];
+            for (int j = tid; j < SF; j += RD_THREADS) states[(size_t)dst * SF + j] = states[(size_t)src * SF + j];
+            for (int j = tid; j < len; j += RD_THREADS) labs[(size_t)dst * ML + j] = labs[(size_t)src * ML + j];
+            if (tid == 0) { meta[2 * dst] = len; meta[2 * dst + 1] = meta[2 * src + 1]; }
+        }
+        if (tid < nA) {
+            const int src = sh.n_slot[tid];
+            sh.c_slot[tid] = fb + tid; sh.c_score[tid] = sh.n_score[tid]; sh.c_len[tid] = meta[2 * src]; sh.c_hash[tid] = (unsigned)meta[2 * src + 1];
+        }
+        if (tid == 0) { sh.nC = nA; sh.nb[p] = 0; ++joined; }
+        __syncthreads();
+        for (int depth = 0;; ++depth) {
+            const int nC = sh.nC;
+            const bool last = depth == a.max_sym;
+            for (int i0 = 0; i0 < nC; i0 += R) heads_group(i0, nC - i0 < R ? nC - i0 : R, t);
+            // the blanks: every hypothesis leaves the frame with every positive duration
+            for (int idx = tid; idx < nC * D; idx += RD_THREADS) {
+                const int i = idx / D, k = idx % D;
+                if (!((a.du.pos_mask >> k) & 1)) continue;
+                const int c = i * Dp + __popc(a.du.pos_mask & ((1u << k) - 1)), f = t + tb_duration(a.du, k);
+                const double s = sh.c_score[i] + (sh.c_lpb[i] + sh.lp_dur[i][k]);
+                sh.cd_s[c] = s; sh.cd_slot[c] = sh.c_slot[i]; sh.cd_f[c] = s > -INFINITY ? (f < n ? f : n) : -1;
+            }
+            __syncthreads();
+            merge_phase(nC * Dp);
+            // the W best label cells (i, v, k), v != blank; the last depth takes no duration 0
+            const unsigned kmask = depth > a.lay.depths ? 0u : last ? a.du.pos_mask : (1u << D) - 1;
+            double prev_s = INFINITY;
+            int prev_i = -1, nSel = 0;
+            for (int k = 0; k < W; ++k) {
+                double bs = -INFINITY;
+                int bi = INT_MAX;
+                for (int i = 0; i < nC; ++i) {
+                    if (sh.c_len[i] >= ML) continue;
+                    const double base = sh.c_score[i], lse = sh.c_lse[i];
+                    const float mx = sh.c_max[i];
+                    for (int v = tid; v < V; v += RD_THREADS) {
+                        if (v == a.blank) continue;
+                        const double lt = (double)(lg[(size_t)i * V + v] - mx) - lse;
+                        for (int kk = 0; kk < D; ++kk) {
+                            if (!((kmask >> kk) & 1)) continue;
+                            const double s = base + (lt + sh.lp_dur[i][kk]);
+                            const int idx = (i * V + v) * D + kk;
+                            if (s > -INFINITY && (s < prev_s || (s == prev_s && idx > prev_i)) && (bi == INT_MAX || s > bs)) { bs = s; bi = idx; }
+                        }
+                    }
+                }
+                block_best(bs, bi);
+                if (sh.best_i == INT_MAX) break;
+                prev_s = sh.best_s; prev_i = sh.best_i;
+                if (tid == 0) { sh.n_i[k] = prev_i / D / V; sh.n_v[k] = prev_i / D % V; sh.n_k[k] = prev_i % D; sh.n_score[k] = prev_s; }
+                ++nSel;
+            }
+            if (nSel == 0) break;
+            __syncthreads();
+            // a cell's slot is that of the first selected cell with its (i, v): one hypothesis, one LSTM step
+            const int dst0 = fb + (depth + 1) * W;
+            int first = tid, ps = 0, ol = 0;
+            unsigned oh = 0;
+            if (tid < nSel) {
+                const int i = sh.n_i[tid], v = sh.n_v[tid];
+                for (int j = 0; j < tid; ++j)
+                    if (sh.n_i[j] == i && sh.n_v[j] == v) { first = j; break; }
+                ps = sh.c_slot[i]; ol = sh.c_len[i]; oh = sh.c_hash[i];
+            }
+            __syncthreads();
+            if (tid < nSel) {
+                const unsigned nh = oh * 1000003u + (unsigned)(sh.n_v[tid] + 1);
+                sh.n_slot[tid] = dst0 + first; sh.n_par[tid] = ps; sh.n_len[tid] = ol + 1; sh.n_hash[tid] = nh;
+                if (first == tid) { meta[2 * (dst0 + tid)] = ol + 1; meta[2 * (dst0 + tid) + 1] = (int)nh; }
+            }
+            __syncthreads();
+            if (tid == 0) {                                                  // the steps to run, the next C (duration 0), the moves (the rest)
+                int nStep = 0, nNext = 0, nCand = 0;
+                for (int k = 0; k < nSel; ++k) {
+                    const int slot = sh.n_slot[k], d = tb_duration(a.du, sh.n_k[k]);
+                    if (slot == dst0 + k) { sh.st_src[nStep] = sh.n_par[k]; sh.st_lab[nStep] = sh.n_v[k]; sh.st_dst[nStep] = slot; ++nStep; }
+                    if (d == 0) {
+                        sh.c_slot[nNext] = slot; sh.c_score[nNext] = sh.n_score[k]; sh.c_len[nNext] = sh.n_len[k]; sh.c_hash[nNext] = sh.n_hash[k];
+                        ++nNext;
+                    } else {
+                        sh.cd_s[nCand] = sh.n_score[k]; sh.cd_slot[nCand] = slot; sh.cd_f[nCand] = t + d < n ? t + d : n;
+                        ++nCand;
+                    }
+                }
+                sh.nStep = nStep; sh.nC = nNext; sh.nCand = nCand;
+                steps += nStep;
+            }
+            __syncthreads();
+            const int nStep = sh.nStep;
+            for (int k = 0; k < nStep; ++k) {
+                const int L = meta[2 * sh.st_dst[k]] - 1;
+                const int *pl = labs + (size_t)sh.st_src[k] * ML;
+                int *q = labs + (size_t)sh.st_dst[k] * ML;
+                for (int j = tid; j < L; j += RD_THREADS) q[j] = pl[j];
+                if (tid == 0) q[L] = sh.st_lab[k];
+            }
+            for (int k0 = 0; k0 < nStep; k0 += R) step_group(k0, nStep - k0 < R ? nStep - k0 : R);
+            merge_phase(sh.nCand);
+            if (last || sh.nC == 0) break;
+        }
+        __syncthreads();
+    }
+
+    const int nOut = bucket_best(n % RING, a.nbest);
+    for (int k = 0; k < a.nbest; ++k) {
+        const size_t o = (size_t)b * a.nbest + k;
+        const int slot = k < nOut ? sh.n_slot[k] : 0, len = k < nOut ? meta[2 * slot] : 0;
+        for (int j = tid; j < ML; j += RD_THREADS) a.labels[o * ML + j] = j < len ? labs[(size_t)slot * ML + j] : -1;
+        if (tid == 0) {
+            a.lengths[o] = k < nOut ? len : -1;
+            a.scores[o] = k < nOut ? (float)sh.n_score[k] : -INFINITY;
+        }
+    }
+    if (tid == 0) {
+        int *stat = (int *)a.ws + (((size_t)a.batch + 3) & ~(size_t)3) + 2 * (size_t)b;
+        stat[0] = joined; stat[1] = steps;
+    }
+}
+
+static int tb_forced_group = 0;
+
+extern "C" {
+
+size_t nntk_shim_rnnt_tdt_beam_workspace_floats(int batch, int H, int J, int V, int max_sym, int dmax, int beam_width, int max_labels) {
+    if (batch <= 0 || !tb_sizes_ok(max_sym, dmax, beam_width, max_labels)) return 0;
+    return tb_head(batch) + (size_t)batch * tb_layout(H, J, V, max_sym, dmax, beam_width, max_labels).row;
+}
+
+int nntk_shim_rnnt_tdt_beam_fits(int H, int J, int V, int D) { return tb_lds_bytes(1, H, J, V + D) <= RD_LDS_MAX; }
+
+int nntk_shim_rnnt_tdt_beam_group(int beam_width, int H, int J, int V, int D) {
+    const bool fits = tb_lds_bytes(NNTK_RNNT_DEC_GROUP, H, J, V + D) <= RD_LDS_MAX;
+    if (tb_forced_group) return tb_forced_group == NNTK_RNNT_DEC_GROUP && fits ? NNTK_RNNT_DEC_GROUP : 1;
+    return beam_width > 1 && fits ? NNTK_RNNT_DEC_GROUP : 1;
+}
+
+void nntk_shim_rnnt_tdt_beam_set_group(int group) { tb_forced_group = group == 1 || group == NNTK_RNNT_DEC_GROUP ? group : 0; }
+
+int nntk_shim_rnnt_tdt_beam(const nntk_shim_rnnt_dec *m, const nntk_shim_rnnt_tdt_durs *du, const float *d_enc, int batch, int T,
+                            const int *h_n_frames, int beam_width, int nbest, int max_labels, int *d_labels, int *d_lengths, float *d_scores,
+                            float *d_ws) {
+    if (batch <= 0) return 0;
+    const int dmax = du->n >= 1 && du->n <= TB_MAX_D ? du->dur[du->n - 1] : 0;
+    if (m->E < 1 || m->H < 1 || m->J < 1 || m->V < 2 || m->H > NNTK_RNNT_DEC_MAX_WIDTH || m->J > NNTK_RNNT_DEC_MAX_WIDTH ||
+        m->V > NNTK_RNNT_DEC_MAX_V || dmax < 1 || dmax > NNTK_RNNT_TDT_MAX_DURATION || du->pos_mask == 0 ||
+        !nntk_shim_rnnt_tdt_beam_fits(m->H, m->J, m->V, du->n) || beam_width < 1 || beam_width > TB_MAX_W || nbest < 1 || nbest > beam_width ||
+        !tb_sizes_ok(m->max_symbols_per_frame, dmax, beam_width, max_labels))
+        return nntk_fail_msg("nntk_rnnt_tdt_beam_decode_device: the model is beyond the decoding kernel's limits");
+    if (nntk_shim_upload_ints((int *)d_ws, h_n_frames, batch)) return -1;
+    TbArgs a;
+    a.enc = d_enc; a.table = m->d_table; a.U = m->d_U; a.proj = m->d_proj; a.out = m->d_out;
+    a.ws = d_ws;
+    a.labels = d_labels; a.lengths = d_lengths; a.scores = d_scores;
+    a.lay = tb_layout(m->H, m->J, m->V, m->max_symbols_per_frame, dmax, beam_width, max_labels);
+    a.ws_head = tb_head(batch);
+    a.batch = batch; a.T = T; a.V = m->V; a.blank = m->blank; a.H = m->H; a.J = m->J; a.act = m->activation;
+    a.max_sym = m->max_symbols_per_frame; a.W = beam_width; a.nbest = nbest; a.max_labels = max_labels;
+    a.du = *du;
+    const int R = nntk_shim_rnnt_tdt_beam_group(beam_width, m->H, m->J, m->V, du->n);
+    const size_t lds = tb_lds_bytes(R, m->H, m->J, m->V + du->n);
+    if (R == 1) {
+        if (lds > 48 * 1024 && nntk_set_max_dynamic_lds((const void *)rnnt_tdt_beam_kernel<1>, lds)) return -1;
+        hipLaunchKernelGGL(rnnt_tdt_beam_kernel<1>, dim3((unsigned)batch), dim3(RD_THREADS), lds, nntk_stream(), a);
+    } else {
+        if (lds > 48 * 1024 && nntk_set_max_dynamic_lds((const void *)rnnt_tdt_beam_kernel<NNTK_RNNT_DEC_GROUP>, lds)) return -1;
+        hipLaunchKernelGGL(rnnt_tdt_beam_kernel<NNTK_RNNT_DEC_GROUP>, dim3((unsigned)batch), dim3(RD_THREADS), lds, nntk_stream(), a);
+    }
+    NNTK_LAUNCH_CHECK("rnnt_tdt_beam_kernel");
+    return 0;
+}
+
+}  // extern "C"

@@ -3,7 +3,8 @@
  * (csrc/hip/rnnt_decode.hip), its token-and-duration form (csrc/hip/rnnt_tdt_decode.hip: the same handle and state, created with a
  * duration table; each decode call refuses the other kind's handle) and, below them, beam search (csrc/hip/rnnt_beam.hip), each with the per-row state of a stream and the
  * decode call in its device-pointer and host-pointer forms; the beam search's plain, _lm and _opt entries share one body a form and the
- * workspace of nntk_shim_rnnt_beam_workspace_floats.  Every argument is checked here, before anything is allocated, uploaded or
+ * workspace of nntk_shim_rnnt_beam_workspace_floats; last, the one-shot beam search of a handle with durations
+ * (csrc/hip/rnnt_tdt_beam.hip).  Every argument is checked here, before anything is allocated, uploaded or
  * enqueued: a refusal needs no device and writes nothing.
  */
 #include <stdint.h>
@@ -355,8 +356,8 @@ int nntk_rnnt_tdt_greedy_decode(NntkRnntDecoder d, NntkRnntDecodeState state, co
     return scores ? nntk_shim_download(scores, d_sc, (size_t)batch * sizeof(float)) : 0;
 }
 
-/* ---- beam search (csrc/hip/rnnt_beam.hip) on the same decoder handle; beam search with durations is not built: a handle with
- *      durations is refused by every entry, and its sizes are 0 ---- */
+/* ---- beam search (csrc/hip/rnnt_beam.hip) on the same decoder handle; a handle with durations is refused by every entry, and its
+ *      sizes are 0: the nntk_rnnt_tdt_beam_* entries at the end of this file serve it ---- */
 
 struct NntkRnntBeamStateStruct {
     NntkRnntDecoder dec;
@@ -622,4 +623,86 @@ int nntk_rnnt_beam_decode_lm(NntkRnntDecoder d, NntkRnntBeamState state, const f
     const NntkRnntBeamOptions o = { lm, 0, NULL, NULL };
     return beam_decode_host("nntk_rnnt_beam_decode_lm", d, state, enc, batch, T, n_frames, beam_width, nbest, max_labels, &o, labels_out,
                             out_lengths, scores);
+}
+
+/* ---- token-and-duration beam search (csrc/hip/rnnt_tdt_beam.hip) on a handle of nntk_rnnt_tdt_decoder_create, one-shot ---- */
+
+size_t nntk_rnnt_tdt_beam_workspace_floats(NntkRnntDecoder d, int batch, int beam_width, int max_labels) {
+    if (!d || !d->du.n || batch <= 0 || beam_width < 1 || beam_width > NNTK_RNNT_BEAM_MAX_W || max_labels < 1) return 0;
+    return nntk_shim_rnnt_tdt_beam_workspace_floats(batch, d->cfg.H, d->cfg.J, d->cfg.V, d->cfg.max_symbols_per_frame, d->du.dur[d->du.n - 1],
+                                                    beam_width, max_labels);
+}
+
+/* everything the call can be refused for; device_form 0: the host-pointer form, which owns its workspace */
+static int tdt_beam_check_call(const char *who, NntkRnntDecoder d, const float *enc, int batch, int T, const int *n_frames, int beam_width,
+                               int nbest, int max_labels, const int *labels_out, const int *out_lengths, const float *scores, const float *ws,
+                               int device_form) {
+    if (!d) return dec_fail(who, "NULL decoder", 0, 0, 0);
+    if (!d->du.n) return dec_fail(who, "the decoder has no durations (nntk_rnnt_decoder_create): nntk_rnnt_beam_decode_device serves it", 0, 0, 0);
+    if (batch < 0 || T < 0) return dec_fail(who, "batch %ld, T %ld: neither may be negative", batch, T, 0);
+    if (beam_width < 1 || beam_width > NNTK_RNNT_BEAM_MAX_W)
+        return dec_fail(who, "beam_width %ld is outside [1, %ld]", beam_width, NNTK_RNNT_BEAM_MAX_W, 0);
+    if (nbest < 1 || nbest > beam_width) return dec_fail(who, "nbest %ld is outside [1, beam_width %ld]", nbest, beam_width, 0);
+    if (max_labels < 1) return dec_fail(who, "max_labels %ld < 1", max_labels, 0, 0);
+    if (batch == 0) return 0;
+    for (int b = 0; n_frames && b < batch; ++b)
+        if (n_frames[b] < 0 || n_frames[b] > T) return dec_fail(who, "n_frames[%ld] = %ld is outside [0, %ld]", b, n_frames[b], T);
+    if (T > 0 && dec_named_ptr(who, "enc", enc)) return -1;
+    if (dec_named_ptr(who, "labels_out", labels_out) || dec_named_ptr(who, "out_lengths", out_lengths) ||
+        dec_named_ptr(who, "scores", scores)) return -1;
+    if (device_form && (!ws || ((uintptr_t)ws & 15)))
+        return dec_fail(who, ws ? "workspace is not 16-byte aligned" : "workspace is NULL", 0, 0, 0);
+    if (!nntk_shim_rnnt_tdt_beam_fits(d->cfg.H, d->cfg.J, d->cfg.V, d->du.n))
+        return dec_fail(who, "the model (H %ld, max(4H, V + D) %ld floats a hypothesis) is beyond the beam kernel's LDS", d->cfg.H,
+                        4 * d->cfg.H > d->cfg.V + d->du.n ? 4 * d->cfg.H : d->cfg.V + d->du.n, 0);
+    const size_t need = nntk_rnnt_tdt_beam_workspace_floats(d, batch, beam_width, max_labels);
+    if (!need) return dec_fail(who, "max_symbols_per_frame %ld, max_labels %ld and the largest duration %ld ask for more than 2^29 slots",
+                               d->cfg.max_symbols_per_frame, max_labels, d->du.dur[d->du.n - 1]);
+    const size_t nh = (size_t)batch * nbest;
+    const void *p[5] = { labels_out, out_lengths, scores, enc, ws };
+    const size_t n[5] = { nh * max_labels * sizeof(int), nh * sizeof(int), nh * sizeof(float), (size_t)batch * T * d->cfg.J * sizeof(float),
+                          device_form ? need * sizeof(float) : 0 };
+    static const char *const name[5] = { "labels_out", "out_lengths", "scores", "enc", "workspace" };
+    return dec_check_overlaps(who, 3, 5, p, n, name);
+}
+
+static int tdt_beam_device(const char *who, NntkRnntDecoder d, const float *d_enc, int batch, int T, const int *n_frames, int beam_width,
+                           int nbest, int max_labels, int *d_labels_out, int *d_out_lengths, float *d_scores, float *d_workspace) {
+    nntk_shim_clear_error();
+    if (tdt_beam_check_call(who, d, d_enc, batch, T, n_frames, beam_width, nbest, max_labels, d_labels_out, d_out_lengths, d_scores,
+                            d_workspace, 1)) return -1;
+    if (batch == 0) return 0;
+    int *len = dec_row_frames("nntk_rnnt_tdt_beam_decode_device: out of host memory", n_frames, batch, T);
+    if (!len) return -1;
+    const nntk_shim_rnnt_dec m = dec_model(d);
+    int rc = nntk_shim_rnnt_tdt_beam(&m, &d->du, d_enc, batch, T, len, beam_width, nbest, max_labels, d_labels_out, d_out_lengths, d_scores,
+                                     d_workspace);
+    free(len);
+    return rc;
+}
+
+int nntk_rnnt_tdt_beam_decode_device(NntkRnntDecoder d, const float *d_enc, int batch, int T, const int *n_frames, int beam_width, int nbest,
+                                     int max_labels, int *d_labels_out, int *d_out_lengths, float *d_scores, float *d_workspace) {
+    return tdt_beam_device("nntk_rnnt_tdt_beam_decode_device", d, d_enc, batch, T, n_frames, beam_width, nbest, max_labels, d_labels_out,
+                           d_out_lengths, d_scores, d_workspace);
+}
+
+int nntk_rnnt_tdt_beam_decode(NntkRnntDecoder d, const float *enc, int batch, int T, const int *n_frames, int beam_width, int nbest,
+                              int max_labels, int *labels_out, int *out_lengths, float *scores) {
+    static const char who[] = "nntk_rnnt_tdt_beam_decode";
+    nntk_shim_clear_error();
+    if (tdt_beam_check_call(who, d, enc, batch, T, n_frames, beam_width, nbest, max_labels, labels_out, out_lengths, scores, NULL, 0)) return -1;
+    if (batch == 0) return 0;
+    const size_t ne = (size_t)batch * T * d->cfg.J, nh = (size_t)batch * nbest, nl = nh * max_labels;
+    float *d_enc = nntk_devbuf_reserve(&t_a, ne + 4);
+    int *d_lab = (int *)nntk_devbuf_reserve(&t_b, nl + 2 * nh + 4);
+    float *d_ws = nntk_devbuf_reserve(nntk_thread_scratch(NNTK_TS_C), nntk_rnnt_tdt_beam_workspace_floats(d, batch, beam_width, max_labels));
+    if (!d_enc || !d_lab || !d_ws) return -1;
+    int *d_len = d_lab + nl;
+    float *d_sc = (float *)(d_len + nh);
+    if (ne && nntk_shim_upload(d_enc, enc, ne * sizeof(float))) return -1;
+    if (tdt_beam_device(who, d, d_enc, batch, T, n_frames, beam_width, nbest, max_labels, d_lab, d_len, d_sc, d_ws)) return -1;
+    if (nntk_shim_download(labels_out, d_lab, nl * sizeof(int))) return -1;
+    if (nntk_shim_download(out_lengths, d_len, nh * sizeof(int))) return -1;
+    return nntk_shim_download(scores, d_sc, nh * sizeof(float));
 }

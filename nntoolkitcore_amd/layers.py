@@ -1499,7 +1499,7 @@ class RnntDecoder:
     Dense block W [J,V] | b [V].  The decoder keeps its own copy: the tensors may be freed or updated afterwards (``load_weights``).
     durations: host ints, the duration table of a token-and-duration model (``nntk_rnnt_tdt_decoder_create``, INTEGRATION.md
     "RNN-Transducer: token-and-duration greedy decoding"); out is then W [J, V + D] | b [V + D], ``decode`` and ``RnntGreedyStream.push``
-    return five tensors (label_durations third) and ``beam_decode`` raises."""
+    return five tensors (label_durations third), ``beam_decode`` raises and ``tdt_beam_decode`` is the beam search."""
 
     def __init__(self, embed, lstm_block, pred_proj, out, blank=0, joint_activation=ACT_TANH, max_symbols_per_frame=10, durations=None):
         V, E = embed.shape
@@ -1600,6 +1600,30 @@ class RnntDecoder:
             outs = outs + self._beam_detail_outputs(enc.device, B, nbest, max_labels)
         return self._beam(None, enc, n_frames, beam_width, nbest, max_labels, outs,
                           self._beam_workspace(enc.device, B, beam_width, max_labels, lm, detail, length_norm), lm, length_norm)
+
+    def _tdt_beam(self, enc, n_frames, beam_width, nbest, max_labels, workspace=None):
+        """the device call on given or own workspace -> (labels, lengths, scores), the workspace"""
+        import torch
+        B, T, J = enc.shape
+        assert J == self.J, "enc: [B, T, J]"
+        L = capi.load()
+        if workspace is None:
+            need = L.nntk_rnnt_tdt_beam_workspace_floats(self.h, B, int(beam_width), int(max_labels))
+            workspace = torch.empty(max(int(need), 4), dtype=torch.float32, device=enc.device)
+        outs = self._beam_outputs(enc.device, B, max(int(nbest), 1), max_labels)
+        check(L.nntk_rnnt_tdt_beam_decode_device(self.h, _dp(enc), B, T, _n_frames_ptr(n_frames, B), int(beam_width), int(nbest),
+                                                 int(max_labels), _ipv(outs[0]), _ipv(outs[1]), _dp(outs[2]), _dp(workspace)),
+              "nntk_rnnt_tdt_beam_decode_device")
+        return outs, workspace
+
+    def tdt_beam_decode(self, enc, n_frames=None, beam_width=8, nbest=1, max_labels=None):
+        """``nntk_rnnt_tdt_beam_decode_device`` (INTEGRATION.md "RNN-Transducer: token-and-duration beam search"), on a decoder with
+        durations: enc [B, T, J] device tensor, n_frames host ints per row (None: T) -> (labels [B, nbest, max_labels] int32, -1 behind
+        each hypothesis's labels; lengths [B, nbest] int32, -1 for a slot without a hypothesis; scores [B, nbest] float32, -inf there).
+        max_labels defaults to max_symbols_per_frame * T."""
+        if max_labels is None:
+            max_labels = max(1, self.max_symbols * enc.shape[1])
+        return self._tdt_beam(enc, n_frames, beam_width, nbest, max_labels)[0]
 
     def destroy(self):
         if self.h:
@@ -1761,6 +1785,23 @@ def rnnt_tdt_greedy_decode(embed, lstm_block, pred_proj, out, enc, durations, n_
     finally:
         dec.destroy()
     return labels, frames, durs, lengths, scores
+
+
+def rnnt_tdt_beam_decode(embed, lstm_block, pred_proj, out, enc, durations, n_frames=None, beam_width=8, nbest=1, max_labels=None, blank=0,
+                         joint_activation=ACT_TANH, max_symbols_per_frame=10):
+    """Token-and-duration beam search on numpy arrays (``nntk_rnnt_tdt_beam_decode``): out W [J, V + D] | b [V + D], enc [B, T, J]
+    -> (labels [B, nbest, max_labels], lengths [B, nbest], scores [B, nbest])"""
+    dec, enc, B, T, max_labels = _rnnt_host_decoder(embed, lstm_block, pred_proj, out, enc, max_labels, blank, joint_activation,
+                                                    max_symbols_per_frame, durations)
+    labels = np.empty((B, nbest, max_labels), np.int32)
+    lengths, scores = np.empty((B, nbest), np.int32), np.empty((B, nbest), np.float32)
+    try:
+        check(capi.load().nntk_rnnt_tdt_beam_decode(dec.h, _p(enc), B, T, _n_frames_ptr(n_frames, B), int(beam_width), int(nbest),
+                                                    int(max_labels), labels.ctypes.data_as(capi.ip), lengths.ctypes.data_as(capi.ip),
+                                                    _p(scores)), "nntk_rnnt_tdt_beam_decode")
+    finally:
+        dec.destroy()
+    return labels, lengths, scores
 
 
 def _host_ids(ids):
