@@ -1146,7 +1146,8 @@ int nntk_rnnt_joint_backward_device(const float *d_out_fwd, const float *d_dout,
  * workgroup's LDS: max_label_len <= 1705 at Dmax = 4, 567 at Dmax = 16; T + max_label_len <= 32768, half of the classic loss's bound
  * because a move multiplies two emissions.  Deterministic: no atomics, a cell's terms summed in one order (ascending i, blank before
  * label), the same bits on every call, the same loss bits with and without a gradient.  The joiner serves unchanged; the projection on
- * top is a Dense of width V + n_durations.  Decoding such a model: nntk_rnnt_tdt_greedy_decode_device below (greedy, one-shot and
+ * top is a Dense of width V + n_durations.  Training at a vocabulary where neither these scores nor their gradient fit: the same loss
+ * from the joiner's inputs, nntk_rnnt_tdt_fused_loss_device below.  Decoding such a model: nntk_rnnt_tdt_greedy_decode_device below (greedy, one-shot and
  * streamed); forced alignment: nntk_rnnt_tdt_align_device below; beam search with durations: nntk_rnnt_tdt_beam_decode_device below. */
 size_t nntk_rnnt_tdt_workspace_floats(int batch, int T, int max_label_len, int n_durations, int want_grad);
 int nntk_rnnt_tdt_loss_device(const float *d_logits, int batch, int T, int V, const int *durations, int n_durations,
@@ -1227,6 +1228,43 @@ int nntk_rnnt_fused_loss_device(const float *d_enc, const float *d_pred, const f
 int nntk_rnnt_fused_loss(const float *enc, const float *pred, const float *out, int batch, int T, int J, int V, int activation,
                          const int *input_lengths, const int *labels, const int *label_lengths, int max_label_len, int blank,
                          float *loss_rows, float *denc, float *dpred, float *dout);
+
+/* ---- RNN-Transducer: fused token-and-duration training loss (csrc/hip/rnnt_tdt_fused.hip; INTEGRATION.md "RNN-Transducer: fused
+ *      token-and-duration training loss") ----
+ * Joiner, projection onto both heads and the token-and-duration loss in one call: with logits[b][t][u] = act(d_enc[b][t] + d_pred[b][u])
+ * W + b, d_loss_rows[b] is what nntk_rnnt_tdt_loss_device defines on those logits -- which are never stored, and neither is their
+ * gradient.
+ *   d_enc [batch][T][J], d_pred [batch][U1 = max_label_len + 1][J]; d_out: W [J, V + n_durations] row-major | b [V + n_durations], the
+ *     n_durations duration columns after the V token columns: the block nntk_rnnt_tdt_decoder_create takes.  activation as in
+ *     nntk_rnnt_joint_device.  Cells with t >= T_b or u > U_b are never read: enc / pred may hold NaN there.
+ *   durations, sigma, blank, input_lengths / labels / label_lengths: HOST memory, as for nntk_rnnt_tdt_loss_device.  The two heads are
+ *     normalised separately, sigma goes into the two token emissions only, a path ends with a blank that lands exactly on T_b, and a
+ *     row without a path has the loss +inf.
+ *   d_denc [batch][T][J], d_dpred [batch][U1][J], d_dout [J (V + D) + (V + D)] (laid out like d_out): all three NULL (loss only) or all
+ *     three given; the gradients of the PLAIN SUM of the finite loss rows, overwritten, every element written; exact zeros in d_denc for
+ *     t >= T_b, in d_dpred for u > U_b, and from a row with P = 0.
+ *   d_workspace: nntk_rnnt_tdt_fused_workspace_floats(batch, T, max_label_len, J, V, n_durations, want_grad) floats, 16-byte aligned.
+ *     In floats, with cells = batch T U1: nntk_rnnt_tdt_workspace_floats(batch, T, max_label_len, n_durations, want_grad) -- the per-cell
+ *     scalars of that call, its layout unchanged -- and, with a gradient only, cells J (d z act') + J (V + D) (W transposed) +
+ *     32 (J + 1) (V + D) (32 partial blocks of d_dout, added in order), each of the three rounded up to 4 floats.  Nothing of
+ *     batch T U1 (V + D) elements exists anywhere.
+ * Refused on the host before anything is enqueued (-1, nntk_last_error(), nothing written, no device needed): everything
+ * nntk_rnnt_tdt_loss_device and nntk_rnnt_fused_loss_device refuse -- the durations table and the lattice's ring, T + max_label_len, J
+ * outside [1, 1024], V above 8192, the activation, gradient pointers only partly given, a NULL tensor, a misaligned workspace, an output
+ * overlapping another output, an input or the workspace -- and a (J, n_durations) at which the kernels' LDS (z: 132 J bytes, a group
+ * of g columns, 128 n_durations bytes, the tile record) exceeds one workgroup's 160 KiB; no J and n_durations within the limits does.
+ * Deterministic: no atomics, the same bits on every call, the same loss bits with and without a gradient; a row's loss, d_denc and
+ * d_dpred bits do not depend on the other rows, on the row's position in the batch or on the T / max_label_len padding.  The products
+ * run on the exact-f32 MFMA.  Runs on the calling thread's stream and reads nothing back; the host-pointer form uploads, runs the device
+ * form and downloads. */
+size_t nntk_rnnt_tdt_fused_workspace_floats(int batch, int T, int max_label_len, int J, int V, int n_durations, int want_grad);
+int nntk_rnnt_tdt_fused_loss_device(const float *d_enc, const float *d_pred, const float *d_out, int batch, int T, int J, int V,
+                                    const int *durations, int n_durations, int activation, const int *input_lengths, const int *labels,
+                                    const int *label_lengths, int max_label_len, int blank, float sigma, float *d_loss_rows, float *d_denc,
+                                    float *d_dpred, float *d_dout, float *d_workspace);
+int nntk_rnnt_tdt_fused_loss(const float *enc, const float *pred, const float *out, int batch, int T, int J, int V, const int *durations,
+                             int n_durations, int activation, const int *input_lengths, const int *labels, const int *label_lengths,
+                             int max_label_len, int blank, float sigma, float *loss_rows, float *denc, float *dpred, float *dout);
 
 /* ---- RNN-Transducer: pruned training loss (csrc/hip/rnnt_pruned.hip; INTEGRATION.md "RNN-Transducer: pruned training loss") ----
  * Kuang et al., "Pruned RNN-T for fast, memory-efficient ASR training" (2022), in three steps and a joiner that gathers the band.  The

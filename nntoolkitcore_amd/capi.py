@@ -509,6 +509,12 @@ SIGNATURES = {
                                               vp, vp, vp, vp, vp]),
     "nntk_rnnt_fused_loss": (C.c_int, [fp, fp, fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, ip, ip, ip, C.c_int, C.c_int,
                                        fp, fp, fp, fp]),
+    # the same for the token-and-duration loss (INTEGRATION.md "RNN-Transducer: fused token-and-duration training loss")
+    "nntk_rnnt_tdt_fused_workspace_floats": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "nntk_rnnt_tdt_fused_loss_device": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, ip, C.c_int, C.c_int, ip, ip, ip, C.c_int,
+                                                  C.c_int, C.c_float, vp, vp, vp, vp, vp]),
+    "nntk_rnnt_tdt_fused_loss": (C.c_int, [fp, fp, fp, C.c_int, C.c_int, C.c_int, C.c_int, ip, C.c_int, C.c_int, ip, ip, ip, C.c_int,
+                                           C.c_int, C.c_float, fp, fp, fp, fp]),
     # RNN-Transducer: forced alignment on stored scores and on the joiner's inputs (INTEGRATION.md "RNN-Transducer: forced alignment")
     "nntk_rnnt_simple_workspace_floats": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "nntk_rnnt_simple_loss_device": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, ip, ip, ip, C.c_int, C.c_int, vp, vp, vp, vp, vp]),

@@ -267,6 +267,17 @@ size_t nntk_shim_rnnt_fused_workspace_floats(int batch, int T, int max_label_len
 int nntk_shim_rnnt_fused_loss(const float *d_enc, const float *d_pred, const float *d_out, int B, int T, int J, int V, int kind,
                               const int *h_input_lengths, const int *h_labels, const int *h_label_lengths, int max_label_len, int blank,
                               float *d_loss_rows, float *d_denc, float *d_dpred, float *d_dout, float *d_ws);
+/* ---- the fused token-and-duration training loss (rnnt_tdt_fused.hip): the call above with the Dense block W [J, V + D] | b [V + D], the
+ *      D duration columns after the V token columns, and the lattice of nntk_shim_rnnt_tdt_loss.  h_durations and the int arrays are HOST
+ *      memory, already checked by the caller (rnnt.c).  The limits are those of both calls, and the kernels' LDS at (J, D) --
+ *      nntk_shim_rnnt_tdt_fused_lds_bytes: z, a group of g columns, the D duration values of a tile's cells and the tile record -- within
+ *      NNTK_RNNT_TDT_LDS_BYTES, which holds for every J <= NNTK_RNNT_FUSED_MAX_J and D <= NNTK_RNNT_TDT_MAX_DURATIONS. ---- */
+size_t nntk_shim_rnnt_tdt_fused_workspace_floats(int batch, int T, int max_label_len, int J, int V, int n_durations, int want_grad);
+size_t nntk_shim_rnnt_tdt_fused_lds_bytes(int J, int n_durations);
+int nntk_shim_rnnt_tdt_fused_loss(const float *d_enc, const float *d_pred, const float *d_out, int B, int T, int J, int V,
+                                  const int *h_durations, int n_durations, int kind, const int *h_input_lengths, const int *h_labels,
+                                  const int *h_label_lengths, int max_label_len, int blank, float sigma, float *d_loss_rows, float *d_denc,
+                                  float *d_dpred, float *d_dout, float *d_ws);
 /* ---- the pruned transducer training loss (rnnt_pruned.hip).  Host int arrays as for nntk_shim_rnnt_loss, already checked by the caller
  *      (rnnt.c), never NULL; d_ranges [B][T] is DEVICE memory and clamped into [0, U1 - S] by every kernel that reads it.
  *      simple_loss: scores am [B][T][V] + lm [B][U1][V], both 16-byte aligned; d_dam and d_dlm both NULL or both given; d_occ

@@ -27,17 +27,15 @@
 //    wave held in accumulators across the whole slice, plus the column sums of g (d b).  Each (slice) writes its own [J + 1][V] block;
 //    rnnt_fused_dw_reduce_kernel adds the NP = 32 blocks in order.
 // No atomics; every sum has a fixed order; a cell's scalars and its d z depend on nothing but the cell.
-#include "rnnt_common.hpp"
+// The tile's frame -- the constants, the z build, ft_logits and its row mapping -- is in rnnt_fused_common.hpp, shared with
+// rnnt_tdt_fused.hip, which also launches this unit's transpose and partial-block reduce.
+#include "rnnt_fused_common.hpp"
 
-#define FT_M 32
-#define FT_PITCH 33
+// the workgroup of this unit's three kernels, restated where they are used: identical to the common header's, or the preprocessor objects
 #define FT_THREADS 512
 #define FT_WAVES 8
-#define FT_NP 32                           // partial blocks of d W: a constant, so that the workspace grows with J and V monotonically
-#define FT_GW_WIDE_MAX_J 896              // up to here 8 column blocks of g fit the LDS next to z, above 4
 
 struct FtLayout { RnntLayout base; size_t wt, partial, dz, total; int np, njb; };
-static int ft_njb(int J) { return J <= 256 ? 1 : J <= 512 ? 2 : 4; }
 static FtLayout ft_layout(int B, int T, int maxL, int J, int V, int want_grad) {
     FtLayout l;
     auto up = [](size_t x) { return (x + 3) & ~(size_t)3; };
@@ -97,55 +95,6 @@ __device__ __forceinline__ void ft_tile_cells(FtTile &s, long tile, long cells, 
     }
     s.live[m] = live; s.y[m] = y; s.eoff[m] = eo; s.poff[m] = po;
 }
-
-__device__ __forceinline__ int ft_any_live(const FtTile &s) {
-    int any = 0;
-#pragma unroll
-    for (int m = 0; m < FT_M; ++m) any |= s.live[m];
-    return any;
-}
-
-// Zs[j][m] = act(enc + pred) of the tile's cells; a dead cell's row: zeros, its inputs never read
-__device__ __forceinline__ void ft_build_z(float *Zs, const FtTile &s, const float *__restrict__ enc, const float *__restrict__ pred, int J,
-                                           int kind) {
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    for (int m = wv; m < FT_M; m += FT_WAVES) {
-        const int live = s.live[m];
-        const float *e = enc + s.eoff[m] * J, *p = pred + s.poff[m] * J;
-        for (int j = lane; j < J; j += 64) Zs[j * FT_PITCH + m] = live ? rnnt_act(kind, e[j] + p[j]) : 0.0f;
-    }
-}
-
-// the [32 cells x 32 columns] block of z W, column col = n0 + c per lane (colv: col < V); one fmaf chain over j = 0 .. J - 1 per element
-__device__ __forceinline__ f32x16 ft_logits(const float *Zs, const float *__restrict__ W, int J, int V, int col, bool colv, int c, int kk) {
-    f32x16 acc;
-#pragma unroll
-    for (int v = 0; v < 16; ++v) acc[v] = 0.0f;
-    const float *wp = W + (long)kk * V + (colv ? col : 0);
-    const float *zp = Zs + kk * FT_PITCH + c;
-    int j = 0;
-    for (; j + 8 <= J; j += 8) {
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const float a = zp[(j + 2 * u) * FT_PITCH];
-            const float b = colv ? wp[(long)(j + 2 * u) * V] : 0.0f;
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, acc, 0, 0, 0);
-        }
-    }
-    for (; j + 2 <= J; j += 2) {
-        const float a = zp[j * FT_PITCH];
-        const float b = colv ? wp[(long)j * V] : 0.0f;
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, acc, 0, 0, 0);
-    }
-    if (j < J) {                                                            // odd J: the last pair's second term is a zero
-        const float a = kk == 0 ? zp[j * FT_PITCH] : 0.0f;
-        const float b = kk == 0 && colv ? wp[(long)j * V] : 0.0f;
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, acc, 0, 0, 0);
-    }
-    return acc;
-}
-
-__device__ __forceinline__ int ft_row(int v, int kk) { return 8 * (v >> 2) + 4 * kk + (v & 3); }
 
 __global__ __launch_bounds__(FT_THREADS) void rnnt_fused_forward_kernel(const float *__restrict__ enc, const float *__restrict__ pred,
                                                                         const float *__restrict__ W, int B, int T, int U1, int J, int V,
@@ -393,6 +342,20 @@ __global__ __launch_bounds__(256) void rnnt_fused_transpose_kernel(const float *
         if (v0 + r < V && j0 + x < J) WT[(long)(v0 + r) * J + j0 + x] = t[x][r];
 }
 
+// the two small kernels, for this unit and for rnnt_tdt_fused.hip
+int nntk_rnnt_fused_transpose_launch(const float *d_W, float *d_WT, int J, int V) {
+    hipLaunchKernelGGL(rnnt_fused_transpose_kernel, dim3((unsigned)((V + 31) / 32), (unsigned)((J + 31) / 32)), dim3(256), 0, nntk_stream(),
+                       d_W, d_WT, J, V);
+    NNTK_LAUNCH_CHECK("rnnt_fused_transpose_kernel");
+    return 0;
+}
+
+int nntk_rnnt_fused_dw_reduce_launch(const float *d_partial, float *d_dout, long n, int np) {
+    hipLaunchKernelGGL(rnnt_fused_dw_reduce_kernel, dim3(rnnt_grid(n, 256)), dim3(256), 0, nntk_stream(), d_partial, d_dout, n, np);
+    NNTK_LAUNCH_CHECK("rnnt_fused_dw_reduce_kernel");
+    return 0;
+}
+
 // the emissions from the joiner's inputs, for this unit and for rnnt_align.hip; lse NULL: not kept (the loss-only form)
 int nntk_rnnt_fused_emit_launch(const float *d_enc, const float *d_pred, const float *d_out, int B, int T, int U1, int J, int V, int kind,
                                 int blank, const int *d_ints, float4 *em, double *lse) {
@@ -428,9 +391,7 @@ int nntk_shim_rnnt_fused_loss(const float *d_enc, const float *d_pred, const flo
     if (nntk_rnnt_lattice_launch(B, T, U1, w.ints, w.em, w.alpha, w.beta, w.hdr, d_loss_rows)) return -1;
     if (!grad) return 0;
     float *wt = d_ws + lay.wt, *partial = d_ws + lay.partial, *dzt = d_ws + lay.dz;
-    hipLaunchKernelGGL(rnnt_fused_transpose_kernel, dim3((unsigned)((V + 31) / 32), (unsigned)((J + 31) / 32)), dim3(256), 0, nntk_stream(),
-                       d_out, wt, J, V);
-    NNTK_LAUNCH_CHECK("rnnt_fused_transpose_kernel");
+    if (nntk_rnnt_fused_transpose_launch(d_out, wt, J, V)) return -1;
     const int gw = J <= FT_GW_WIDE_MAX_J ? 8 : 4;
     const size_t dzbytes = zbytes + (size_t)gw * 32 * FT_PITCH * sizeof(float);
     if (dzbytes > 48 * 1024 && nntk_set_max_dynamic_lds((const void *)rnnt_fused_dz_kernel, dzbytes)) return -1;
@@ -452,8 +413,7 @@ int nntk_shim_rnnt_fused_loss(const float *d_enc, const float *d_pred, const flo
 #undef FT_DW
     NNTK_LAUNCH_CHECK("rnnt_fused_dw_kernel");
     const long nw = ((long)J + 1) * V;
-    hipLaunchKernelGGL(rnnt_fused_dw_reduce_kernel, dim3(rnnt_grid(nw, 256)), dim3(256), 0, nntk_stream(), partial, d_dout, nw, lay.np);
-    NNTK_LAUNCH_CHECK("rnnt_fused_dw_reduce_kernel");
+    if (nntk_rnnt_fused_dw_reduce_launch(partial, d_dout, nw, lay.np)) return -1;
     // d_enc = the sum over u, d_pred = the sum over t of d z act'(z), which already holds the activation's factor: identity here
     return nntk_shim_rnnt_joint_backward(nullptr, dzt, B, T, U1, J, 0, d_denc, d_dpred);
 }

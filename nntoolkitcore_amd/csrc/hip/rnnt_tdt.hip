@@ -233,50 +233,6 @@ __global__ __launch_bounds__(CTC_THREADS) void tdt_lattice_kernel(int B, int T, 
     }
 }
 
-// the scalars of a live cell of a row with P = mP 2^eP > 0: the occupancy and the flows out of it, all over P
-struct TdtFlows { RnntFlows tok; float fd[TDT_MAXD]; };
-__device__ __forceinline__ TdtFlows tdt_cell_flows(long c, int t, int u, int Tb, int Ub, int U1, const TdtDur &dur,
-                                                   const float4 *__restrict__ em, const float2 *__restrict__ pdur,
-                                                   const float2 *__restrict__ wa, const float2 *__restrict__ wb, float mP, int eP) {
-    const xf a = xf_unpack(wa[c]);
-    const float4 e4 = em[c];
-    xf pb, py;
-    pb.m = e4.x; pb.e = __float_as_int(e4.y);
-    py.m = e4.z; py.e = __float_as_int(e4.w);
-    const xf ab = xf_times(a, pb), ay = xf_times(a, py);
-    TdtFlows f;
-    f.tok.occ = xf_to_float(xf_times(a, xf_unpack(wb[c])), eP) / mP;
-    f.tok.fb = f.tok.fy = 0.0f;
-#pragma unroll
-    for (int i = 0; i < TDT_MAXD; ++i) {
-        f.fd[i] = 0.0f;
-        if (i >= dur.n) continue;
-        const int k = dur.d[i], tt = t + k;
-        const xf pdi = xf_unpack(pdur[c * dur.n + i]);
-        float fb = 0.0f, fy = 0.0f;
-        if (k > 0 && tt <= Tb) {                                            // alpha p_blank p_dur(i) beta(t + d_i, u) / P
-            const xf bt = tt < Tb ? xf_unpack(wb[c + (long)k * U1]) : u == Ub ? xf_one() : xf_zero();
-            fb = xf_to_float(xf_times(xf_times(ab, pdi), bt), eP) / mP;
-        }
-        if (u < Ub && tt < Tb)                                              // alpha p_label p_dur(i) beta(t + d_i, u + 1) / P
-            fy = xf_to_float(xf_times(xf_times(ay, pdi), xf_unpack(wb[c + (long)k * U1 + 1])), eP) / mP;
-        f.tok.fb += fb;
-        f.tok.fy += fy;
-        f.fd[i] = fb + fy;
-    }
-    return f;
-}
-
-// element k of a cell's row of V + D: a token's gradient (rnnt_grad_value) or a duration's, the same selected-not-multiplied zero
-__device__ __forceinline__ float tdt_grad_value(const TdtFlows &f, double lse_t, double lse_d, int V, int blank, int y, float x, int k) {
-    if (k < V) return rnnt_grad_value(f.tok, lse_t, blank, y, x, k);
-    float r = f.tok.occ == 0.0f ? 0.0f : f.tok.occ * expf((float)((double)x - lse_d));
-#pragma unroll
-    for (int i = 0; i < TDT_MAXD; ++i)
-        if (k - V == i) r -= f.fd[i];
-    return r;
-}
-
 template <bool VEC>
 __global__ __launch_bounds__(CTC_THREADS) void tdt_grad_kernel(const float *__restrict__ logits, int B, int T, int U1, int V, const TdtDur dur,
                                                                int blank, const int *__restrict__ ints, const float4 *__restrict__ em,
@@ -325,6 +281,24 @@ int nntk_rnnt_tdt_emit_launch(const float *d_logits, int B, int T, int U1, int V
     return 0;
 }
 
+// the lattice on the emissions, for this unit and for rnnt_tdt_fused.hip; wa / wb NULL: the forward direction alone
+int nntk_rnnt_tdt_lattice_launch(int B, int T, int U1, const TdtDur &dur, const int *d_ints, const float4 *em, const float2 *pdur, float2 *wa,
+                                 float2 *wb, float *hdr, float *d_loss_rows) {
+    const size_t lds = tdt_ring_bytes(U1, dur.dmax);
+    const dim3 lgrid((unsigned)B, wa ? 2 : 1);
+#define TDT_AB(REG)                                                                                                               \
+    do {                                                                                                                          \
+        if (lds > 48 * 1024 && nntk_set_max_dynamic_lds((const void *)tdt_lattice_kernel<REG>, lds)) return -1;                    \
+        hipLaunchKernelGGL(tdt_lattice_kernel<REG>, lgrid, dim3(CTC_THREADS), lds, nntk_stream(), B, T, U1, dur, d_ints, em, pdur, \
+                           wa, wb, hdr, d_loss_rows);                                                                             \
+    } while (0)
+    if (U1 <= CTC_THREADS) TDT_AB(true);
+    else TDT_AB(false);
+#undef TDT_AB
+    NNTK_LAUNCH_CHECK("tdt_lattice_kernel");
+    return 0;
+}
+
 extern "C" {
 
 size_t nntk_shim_rnnt_tdt_workspace_floats(int batch, int T, int max_label_len, int n_durations, int want_grad) {
@@ -354,18 +328,7 @@ int nntk_shim_rnnt_tdt_loss(const float *d_logits, int B, int T, int V, const in
     if (rnnt_upload_ints(ints, B, maxL, h_input_lengths, h_labels, h_label_lengths)) return -1;
     const dim3 cgrid(rnnt_grid(cells, 4));
     if (nntk_rnnt_tdt_emit_launch(d_logits, B, T, U1, V, D, blank, sigma, ints, em, pdur, lse)) return -1;
-    const size_t lds = tdt_ring_bytes(U1, dur.dmax);
-    const dim3 lgrid((unsigned)B, grad ? 2 : 1);
-#define TDT_AB(REG)                                                                                                             \
-    do {                                                                                                                        \
-        if (lds > 48 * 1024 && nntk_set_max_dynamic_lds((const void *)tdt_lattice_kernel<REG>, lds)) return -1;                  \
-        hipLaunchKernelGGL(tdt_lattice_kernel<REG>, lgrid, dim3(CTC_THREADS), lds, nntk_stream(), B, T, U1, dur, ints, em, pdur, \
-                           wa, wb, hdr, d_loss_rows);                                                                           \
-    } while (0)
-    if (U1 <= CTC_THREADS) TDT_AB(true);
-    else TDT_AB(false);
-#undef TDT_AB
-    NNTK_LAUNCH_CHECK("tdt_lattice_kernel");
+    if (nntk_rnnt_tdt_lattice_launch(B, T, U1, dur, ints, em, pdur, wa, wb, hdr, d_loss_rows)) return -1;
     if (grad) {
         if (vec)
             hipLaunchKernelGGL(tdt_grad_kernel<true>, cgrid, dim3(CTC_THREADS), 0, nntk_stream(), d_logits, B, T, U1, V, dur, blank, ints, em,

@@ -1,7 +1,8 @@
 // rnnt_tdt_common.hpp -- what the token-and-duration transducer units share (rnnt_tdt.hip: the loss and its gradient; rnnt_tdt_align.hip:
-// Viterbi on the same per-cell emissions): the duration table as the kernels take it, the workspace layout of the per-cell scalars, the
-// ring's size and the limits, the record a lattice cell takes from global memory, and the launcher of the emission writer, which
-// rnnt_tdt.hip owns and the aligner reuses unchanged.
+// Viterbi on the same per-cell emissions; rnnt_tdt_fused.hip: the loss from the joiner's inputs, the scores never stored): the duration
+// table as the kernels take it, the workspace layout of the per-cell scalars, the ring's size and the limits, the record a lattice cell
+// takes from global memory, a cell's flows and gradient value, and the launchers of the kernels that one unit owns and another reuses
+// unchanged: rnnt_tdt.hip's emission writer and lattice, rnnt_tdt_fused.hip's emission writer.
 #pragma once
 #include "rnnt_common.hpp"
 
@@ -66,6 +67,59 @@ static inline TdtAlignLayout tdt_align_layout(int B, int T, int maxL, int D) {
     return l;
 }
 
+// the scalars of a live cell of a row with P = mP 2^eP > 0: the occupancy and the flows out of it, all over P (rnnt_tdt.hip's gradient
+// kernel, a wavefront per cell; rnnt_tdt_fused.hip's tile record, a lane per cell)
+struct TdtFlows { RnntFlows tok; float fd[TDT_MAXD]; };
+__device__ __forceinline__ TdtFlows tdt_cell_flows(long c, int t, int u, int Tb, int Ub, int U1, const TdtDur &dur,
+                                                   const float4 *__restrict__ em, const float2 *__restrict__ pdur,
+                                                   const float2 *__restrict__ wa, const float2 *__restrict__ wb, float mP, int eP) {
+    const xf a = xf_unpack(wa[c]);
+    const float4 e4 = em[c];
+    xf pb, py;
+    pb.m = e4.x; pb.e = __float_as_int(e4.y);
+    py.m = e4.z; py.e = __float_as_int(e4.w);
+    const xf ab = xf_times(a, pb), ay = xf_times(a, py);
+    TdtFlows f;
+    f.tok.occ = xf_to_float(xf_times(a, xf_unpack(wb[c])), eP) / mP;
+    f.tok.fb = f.tok.fy = 0.0f;
+#pragma unroll
+    for (int i = 0; i < TDT_MAXD; ++i) {
+        f.fd[i] = 0.0f;
+        if (i >= dur.n) continue;
+        const int k = dur.d[i], tt = t + k;
+        const xf pdi = xf_unpack(pdur[c * dur.n + i]);
+        float fb = 0.0f, fy = 0.0f;
+        if (k > 0 && tt <= Tb) {                                            // alpha p_blank p_dur(i) beta(t + d_i, u) / P
+            const xf bt = tt < Tb ? xf_unpack(wb[c + (long)k * U1]) : u == Ub ? xf_one() : xf_zero();
+            fb = xf_to_float(xf_times(xf_times(ab, pdi), bt), eP) / mP;
+        }
+        if (u < Ub && tt < Tb)                                              // alpha p_label p_dur(i) beta(t + d_i, u + 1) / P
+            fy = xf_to_float(xf_times(xf_times(ay, pdi), xf_unpack(wb[c + (long)k * U1 + 1])), eP) / mP;
+        f.tok.fb += fb;
+        f.tok.fy += fy;
+        f.fd[i] = fb + fy;
+    }
+    return f;
+}
+
+// element k of a cell's row of V + D: a token's gradient (rnnt_grad_value) or a duration's, the same selected-not-multiplied zero
+__device__ __forceinline__ float tdt_grad_value(const TdtFlows &f, double lse_t, double lse_d, int V, int blank, int y, float x, int k) {
+    if (k < V) return rnnt_grad_value(f.tok, lse_t, blank, y, x, k);
+    float r = f.tok.occ == 0.0f ? 0.0f : f.tok.occ * expf((float)((double)x - lse_d));
+#pragma unroll
+    for (int i = 0; i < TDT_MAXD; ++i)
+        if (k - V == i) r -= f.fd[i];
+    return r;
+}
+
+// rnnt_tdt.hip: tdt_lattice_kernel on the emissions em [cells] and the duration probabilities pdur [cells][D]; wa / wb NULL = the forward
+// direction alone (loss only)
+int nntk_rnnt_tdt_lattice_launch(int B, int T, int U1, const TdtDur &dur, const int *d_ints, const float4 *em, const float2 *pdur, float2 *wa,
+                                 float2 *wb, float *hdr, float *d_loss_rows);
+// rnnt_tdt_fused.hip: rnnt_tdt_fused_forward_kernel, the same emissions from the joiner's inputs and the Dense block d_out = W [J, V + D] |
+// b [V + D]; lse NULL = not kept
+int nntk_rnnt_tdt_fused_emit_launch(const float *d_enc, const float *d_pred, const float *d_out, int B, int T, int U1, int J, int V, int D,
+                                    int kind, int blank, float sigma, const int *d_ints, float4 *em, float2 *pdur, double *lse);
 // rnnt_tdt.hip: tdt_emit_kernel, the token emissions and duration probabilities of the stored scores d_logits [B][T][U1][V + D] into
 // em / pdur; lse NULL = not kept (loss only, alignment)
 int nntk_rnnt_tdt_emit_launch(const float *d_logits, int B, int T, int U1, int V, int D, int blank, float sigma, const int *d_ints,

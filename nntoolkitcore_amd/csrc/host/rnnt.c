@@ -404,6 +404,83 @@ int nntk_rnnt_fused_loss(const float *enc, const float *pred, const float *out, 
     return nntk_shim_download(dout, d_g + s.ne + s.npd, ((size_t)J + 1) * V * sizeof(float));
 }
 
+/* ---- the fused token-and-duration training loss (csrc/hip/rnnt_tdt_fused.hip): the checks of the token-and-duration loss and of the
+ *      fused loss, then the kernels' LDS at (J, n_durations) ---- */
+static int tdt_fused_check(const char *who, int batch, int T, int J, int V, const int *durations, int n_durations, int activation,
+                           const int *input_lengths, const int *labels, const int *label_lengths, int max_label_len, int blank, float sigma,
+                           const void *denc, const void *dpred, const void *ddout) {
+    if (tdt_check(who, batch, T, V, durations, n_durations, input_lengths, labels, label_lengths, max_label_len, blank, sigma)) return -1;
+    if (fused_check(who, batch, T, J, V, activation, input_lengths, labels, label_lengths, max_label_len, blank, denc, dpred, ddout)) return -1;
+    const size_t lds = nntk_shim_rnnt_tdt_fused_lds_bytes(J, n_durations);
+    if (lds > NNTK_RNNT_TDT_LDS_BYTES)
+        return rnnt_fail(who, "J %d with n_durations %d: the kernels need %d bytes of LDS, beyond one workgroup's", J, n_durations, (int)lds);
+    return 0;
+}
+
+size_t nntk_rnnt_tdt_fused_workspace_floats(int batch, int T, int max_label_len, int J, int V, int n_durations, int want_grad) {
+    return nntk_shim_rnnt_tdt_fused_workspace_floats(batch, T, max_label_len, J, V, n_durations, want_grad != 0);
+}
+
+int nntk_rnnt_tdt_fused_loss_device(const float *d_enc, const float *d_pred, const float *d_out, int batch, int T, int J, int V,
+                                    const int *durations, int n_durations, int activation, const int *input_lengths, const int *labels,
+                                    const int *label_lengths, int max_label_len, int blank, float sigma, float *d_loss_rows, float *d_denc,
+                                    float *d_dpred, float *d_dout, float *d_workspace) {
+    static const char who[] = "nntk_rnnt_tdt_fused_loss_device";
+    nntk_shim_clear_error();
+    if (tdt_fused_check(who, batch, T, J, V, durations, n_durations, activation, input_lengths, labels, label_lengths, max_label_len, blank,
+                        sigma, d_denc, d_dpred, d_dout)) return -1;
+    if (batch == 0) return 0;
+    if (rnnt_check_ptr(who, "d_enc", d_enc, 4) || rnnt_check_ptr(who, "d_pred", d_pred, 4) || rnnt_check_ptr(who, "d_out", d_out, 4) ||
+        rnnt_check_ptr(who, "d_loss_rows", d_loss_rows, 4) || rnnt_check_ptr(who, "d_workspace", d_workspace, 16) ||
+        (d_denc && (rnnt_check_ptr(who, "d_denc", d_denc, 4) || rnnt_check_ptr(who, "d_dpred", d_dpred, 4) ||
+                    rnnt_check_ptr(who, "d_dout", d_dout, 4)))) return -1;
+    const size_t U1 = (size_t)max_label_len + 1, f = sizeof(float);
+    const size_t ne = (size_t)batch * T * J, npd = (size_t)batch * U1 * J, nw = ((size_t)J + 1) * ((size_t)V + n_durations);
+    /* outputs first */
+    const rnnt_span sp[] = {{"d_loss_rows", (uintptr_t)d_loss_rows, (size_t)batch * f}, {"d_denc", (uintptr_t)d_denc, ne * f},
+                            {"d_dpred", (uintptr_t)d_dpred, npd * f}, {"d_dout", (uintptr_t)d_dout, nw * f},
+                            {"d_enc", (uintptr_t)d_enc, ne * f}, {"d_pred", (uintptr_t)d_pred, npd * f}, {"d_out", (uintptr_t)d_out, nw * f},
+                            {"d_workspace", (uintptr_t)d_workspace,
+                             nntk_shim_rnnt_tdt_fused_workspace_floats(batch, T, max_label_len, J, V, n_durations, d_denc != NULL) * f}};
+    if (rnnt_overlap(who, sp, 4, 8)) return -1;
+    int *len = rnnt_lengths(input_lengths, batch, T);
+    int rc = len ? nntk_shim_rnnt_tdt_fused_loss(d_enc, d_pred, d_out, batch, T, J, V, durations, n_durations, activation, len, labels,
+                                                 label_lengths, max_label_len, blank, sigma, d_loss_rows, d_denc, d_dpred, d_dout, d_workspace)
+                 : -1;
+    free(len);
+    return rc;
+}
+
+int nntk_rnnt_tdt_fused_loss(const float *enc, const float *pred, const float *out, int batch, int T, int J, int V, const int *durations,
+                             int n_durations, int activation, const int *input_lengths, const int *labels, const int *label_lengths,
+                             int max_label_len, int blank, float sigma, float *loss_rows, float *denc, float *dpred, float *dout) {
+    static const char who[] = "nntk_rnnt_tdt_fused_loss";
+    nntk_shim_clear_error();
+    if (tdt_fused_check(who, batch, T, J, V, durations, n_durations, activation, input_lengths, labels, label_lengths, max_label_len, blank,
+                        sigma, denc, dpred, dout)) return -1;
+    if (batch == 0) return 0;
+    if (rnnt_check_ptr(who, "enc", enc, 4) || rnnt_check_ptr(who, "pred", pred, 4) || rnnt_check_ptr(who, "out", out, 4) ||
+        rnnt_check_ptr(who, "loss_rows", loss_rows, 4) ||
+        (denc && (rnnt_check_ptr(who, "denc", denc, 4) || rnnt_check_ptr(who, "dpred", dpred, 4) || rnnt_check_ptr(who, "dout", dout, 4))))
+        return -1;
+    /* as nntk_rnnt_fused_loss: inputs | loss rows in one block, the gradients in a second, the workspace in a third */
+    const int VD = V + n_durations;
+    fused_in s;
+    if (fused_stage(&s, enc, pred, out, batch, T, max_label_len, J, VD, ((size_t)batch + 3) & ~(size_t)3)) return -1;
+    float *d_g = denc ? nntk_devbuf_reserve(&t_b, s.ne + s.npd + s.nw + 4) : NULL;
+    float *d_ws = nntk_devbuf_reserve(&t_c, nntk_shim_rnnt_tdt_fused_workspace_floats(batch, T, max_label_len, J, V, n_durations, denc != NULL));
+    if ((denc && !d_g) || !d_ws) return -1;
+    float *d_loss = s.d_out + s.nw;
+    if (nntk_rnnt_tdt_fused_loss_device(s.d_enc, s.d_pred, s.d_out, batch, T, J, V, durations, n_durations, activation, input_lengths, labels,
+                                        label_lengths, max_label_len, blank, sigma, d_loss, d_g, d_g ? d_g + s.ne : NULL,
+                                        d_g ? d_g + s.ne + s.npd : NULL, d_ws)) return -1;
+    if (nntk_shim_download(loss_rows, d_loss, (size_t)batch * sizeof(float))) return -1;
+    if (!denc) return 0;
+    if (nntk_shim_download(denc, d_g, (size_t)batch * T * J * sizeof(float)) ||
+        nntk_shim_download(dpred, d_g + s.ne, (size_t)batch * (max_label_len + 1) * J * sizeof(float))) return -1;
+    return nntk_shim_download(dout, d_g + s.ne + s.npd, ((size_t)J + 1) * VD * sizeof(float));
+}
+
 /* ---- forced alignment (csrc/hip/rnnt_align.hip): the best single path, on stored scores and on the joiner's inputs.  One device
  *      body and one host body take the score source; in the host body its pointers are host memory ---- */
 static int align_check(const char *who, const nntk_shim_rnnt_src *src, int batch, int T, int V, const int *input_lengths, const int *labels,

@@ -1217,6 +1217,51 @@ def rnnt_fused_loss(enc, pred, out_block, labels, label_lengths=None, input_leng
     return (loss,) + g
 
 
+def _rnnt_tdt_fused_args(enc, pred, out_block, labels, durations, label_lengths, input_lengths, blank, sigma, activation):
+    """what both forms of the fused token-and-duration loss pass between the three tensors and the outputs (the arrays kept alive)"""
+    dur = np.ascontiguousarray(np.asarray(durations, dtype=np.int32)).reshape(-1)
+    B, T, U1, J, VD = _rnnt_fused_dims(enc, pred, out_block)
+    lab, ll = _rnnt_labels(labels, label_lengths, B, U1 - 1)
+    il, ilp = _ctc_lengths(input_lengths, B)
+    args = (B, T, J, VD - dur.shape[0], dur.ctypes.data_as(capi.ip), dur.shape[0], RNNT_ACTIVATIONS[activation], ilp,
+            lab.ctypes.data_as(capi.ip), ll.ctypes.data_as(capi.ip), U1 - 1, blank, float(sigma))
+    return args, (dur, lab, ll, il)
+
+
+def rnnt_tdt_fused_loss_device(enc, pred, out_block, labels, durations, label_lengths=None, input_lengths=None, blank=0, sigma=0.0,
+                               activation=ACT_TANH, want_grad=True, loss=None, denc=None, dpred=None, dout=None, workspace=None):
+    """``nntk_rnnt_tdt_fused_loss_device``: ``rnnt_fused_loss_device`` for the token-and-duration transducer.  out_block is W [J,V + D] |
+    b [V + D], the D = len(durations) duration columns last; durations and sigma as for ``rnnt_tdt_loss_device``.  Returns (loss rows [B],
+    d enc, d pred, d out_block), the gradients of the plain sum of the finite loss rows (None without want_grad).  The [B,T,U1,V + D]
+    logits are never stored."""
+    import torch
+    args, keep = _rnnt_tdt_fused_args(enc, pred, out_block, labels, durations, label_lengths, input_lengths, blank, sigma, activation)
+    B, T, J, V, D, U = args[0], args[1], args[2], args[3], args[5], args[10]
+    workspace = _rnnt_workspace(workspace, enc.device, "nntk_rnnt_tdt_fused_workspace_floats", B, T, U, J, V, D, int(want_grad))
+    if loss is None:
+        loss = torch.empty(B, dtype=torch.float32, device=enc.device)
+    if want_grad:
+        denc = torch.empty_like(enc) if denc is None else denc
+        dpred = torch.empty_like(pred) if dpred is None else dpred
+        dout = torch.empty_like(out_block) if dout is None else dout
+    g = [_dp(a) if want_grad else None for a in (denc, dpred, dout)]
+    check(capi.load().nntk_rnnt_tdt_fused_loss_device(_dp(enc), _dp(pred), _dp(out_block), *args, _dp(loss), *g, _dp(workspace)),
+          "nntk_rnnt_tdt_fused_loss_device")
+    return (loss, denc, dpred, dout) if want_grad else (loss, None, None, None)
+
+
+def rnnt_tdt_fused_loss(enc, pred, out_block, labels, durations, label_lengths=None, input_lengths=None, blank=0, sigma=0.0,
+                        activation=ACT_TANH, want_grad=True):
+    """The host-memory form (``nntk_rnnt_tdt_fused_loss``) on numpy arrays."""
+    enc, pred, out_block = _f32(enc), _f32(pred), _f32(out_block)
+    args, keep = _rnnt_tdt_fused_args(enc, pred, out_block, labels, durations, label_lengths, input_lengths, blank, sigma, activation)
+    loss = np.empty(args[0], np.float32)
+    g = (np.empty_like(enc), np.empty_like(pred), np.empty_like(out_block)) if want_grad else (None, None, None)
+    check(capi.load().nntk_rnnt_tdt_fused_loss(_p(enc), _p(pred), _p(out_block), *args, _p(loss), *[_p(a) if want_grad else None for a in g]),
+          "nntk_rnnt_tdt_fused_loss")
+    return (loss,) + g
+
+
 def _ip(t):
     """device pointer of a contiguous int32 torch tensor"""
     import torch
