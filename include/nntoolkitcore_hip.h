@@ -1493,13 +1493,63 @@ int nntk_rnnt_tdt_greedy_decode(NntkRnntDecoder d, NntkRnntDecodeState state, co
  * with durations); max(4H, V + D) floats a hypothesis fit the kernel's LDS; the rings stay inside 2^29 slots and entries.
  * Deterministic: no atomics, the same bits on every call; a row's bits do not depend on the other rows, its position in the batch,
  * the T padding, or how many hypotheses share a pass over a matrix.  One launch on the calling thread's stream.  The host-pointer
- * form uploads, runs the device form on a workspace of its own and downloads.  Not in this call, each a follow-up on its kernel:
- * streaming with a carried ring, language-model fusion, per-label frames, durations and confidences, length normalisation. */
+ * form uploads, runs the device form on a workspace of its own and downloads.  Language-model fusion, label frames, durations and
+ * confidences, and length normalisation: nntk_rnnt_tdt_beam_decode_opt_device below.  Not in these calls, a follow-up on the kernel:
+ * streaming with a carried ring. */
 size_t nntk_rnnt_tdt_beam_workspace_floats(NntkRnntDecoder d, int batch, int beam_width, int max_labels);
 int nntk_rnnt_tdt_beam_decode_device(NntkRnntDecoder d, const float *d_enc, int batch, int T, const int *n_frames, int beam_width, int nbest,
                                      int max_labels, int *d_labels_out, int *d_out_lengths, float *d_scores, float *d_workspace);
 int nntk_rnnt_tdt_beam_decode(NntkRnntDecoder d, const float *enc, int batch, int T, const int *n_frames, int beam_width, int nbest,
                               int max_labels, int *labels_out, int *out_lengths, float *scores);
+/* ---- language-model fusion, label frames, durations and confidences, length normalisation (INTEGRATION.md "RNN-Transducer:
+ *      token-and-duration beam search", The options) ----
+ * nntk_rnnt_tdt_beam_decode_opt_device: the search above with an options struct, in the same single launch; o == NULL or a struct with
+ * everything off (lm NULL, length_norm 0, the three pointers NULL) is nntk_rnnt_tdt_beam_decode_device bit for bit, and the workspace
+ * query is then nntk_rnnt_tdt_beam_workspace_floats.  In the pseudo-code above, everything not mentioned unchanged:
+ *   Language model (an NntkNgramLm, as in nntk_rnnt_beam_decode_lm_device below; lnF, next, ln E and their doubles are those stated
+ *   there).  Every hypothesis carries a state q; the initial one has q = start_state.  A blank move keeps q and adds nothing.  A label
+ *   cell (i, v, k) scores (C[i].score + (lp_tok[v] + lp_dur[k])) + lnF(q_i, v) in double, the parenthesised part the acoustic
+ *   expression bit for bit; lnF does not depend on k.  A cell at -inf is no candidate.  The new hypothesis takes next(q_i, v); equal
+ *   label sequences have equal q, so a merge needs no rule.  Cuts of cells and of buckets are made on the fused scores with the tie
+ *   rules above.  Report: every one of the W best of bucket[n] gets + ln E(q), entries at -inf are dropped, the rest are ordered
+ *   descending, exact ties to the lower rank, and the first nbest are written.  A row without frames reports the empty hypothesis with
+ *   score ln E(start_state).  lm == NULL, or a unit model (alpha == 0, beta == 0, no final_logp), gives the acoustic call's bits;
+ *   score - nntk_ngram_lm_score(lm, y, n, 1) is the acoustic log mass of y.
+ *   Detail, on when any of label_frames, label_durations, label_logps is not NULL.  A hypothesis carries frames[j], durs[j], lps[j]
+ *   for its labels.  A label cell (i, v, k) at frame t appends t, the table value d_k (also when t + d_k > n and the move is clamped)
+ *   and (float)lp_tok[v], the double the selection already forms, rounded once: neither the duration head nor lnF is part of it, it
+ *   is the quantity nntk_rnnt_beam_decode_opt_device reports.  Bucket entries also hold lead: an insert sets lead = cand.score and
+ *   stores the candidate's arrays; a merge with cand.score > lead (a double compare) takes the candidate's arrays and lead, an exact
+ *   tie keeps what is there; the entry's score, index and state behave as above.  So a merged hypothesis reports the alignment of its
+ *   dominant contributor (not the Viterbi alignment: nntk_rnnt_tdt_align_device gives that).  Which arrays are kept never influences a
+ *   score, a cut or a state: with detail on, labels, lengths and scores are the bits of the call without it.
+ *   length_norm == 1: what is to be reported (with a model: after + ln E, the -inf entries dropped) is ranked by
+ *   score / (double)(length + 1), descending, exact ties to the lower rank among the W best of bucket[n].  d_scores stays the plain
+ *   score.  It touches only the report.
+ * label_frames, label_durations [batch][nbest][max_labels] int: hypothesis k's values, then -1; label_logps, the same shape, float: the
+ * values, then 0.0f.  A slot without a hypothesis holds those throughout; every element of an output that is asked for is written.
+ * Each may be NULL; device pointers in the _device form, host pointers in the host form.
+ * d_workspace: nntk_rnnt_tdt_beam_opt_workspace_floats(d, batch, beam_width, max_labels, o) floats, 16-byte aligned: what the plain
+ * call needs; with lm, behind it per row 4 bytes a hypothesis slot and 8 beam_width V bytes; with detail or length_norm, behind both
+ * per row 12 max_labels bytes a slot, 16 bytes a bucket entry and 32 beam_width bytes.  The kernel's LDS is the plain call's.
+ * Refused on the host before anything is enqueued (-1, nntk_last_error(), nothing written): everything the plain call refuses, a
+ * handle of nntk_rnnt_decoder_create included; an lm built for another class count than V or another blank than the decoder's;
+ * length_norm outside {0, 1}; a detail output that is not 4-byte aligned or overlaps another output, d_enc or the workspace.
+ * The guarantees above hold for the six outputs: no atomics, one launch, the same bits on every call, a row independent of the other
+ * rows, its batch position, the T padding and unjoined frames (NaN there included) and how many hypotheses share a pass over a matrix. */
+typedef struct {
+    NntkNgramLm lm;           /* NULL: the acoustic search */
+    int length_norm;          /* 0 | 1 */
+    int *label_frames;        /* [batch][nbest][max_labels] or NULL; a device pointer in the _device form */
+    int *label_durations;     /* the same shape, or NULL */
+    float *label_logps;       /* the same shape, or NULL */
+} NntkRnntTdtBeamOptions;
+size_t nntk_rnnt_tdt_beam_opt_workspace_floats(NntkRnntDecoder d, int batch, int beam_width, int max_labels, const NntkRnntTdtBeamOptions *o);
+int nntk_rnnt_tdt_beam_decode_opt_device(NntkRnntDecoder d, const float *d_enc, int batch, int T, const int *n_frames, int beam_width,
+                                         int nbest, int max_labels, const NntkRnntTdtBeamOptions *o, int *d_labels_out,
+                                         int *d_out_lengths, float *d_scores, float *d_workspace);
+int nntk_rnnt_tdt_beam_decode_opt(NntkRnntDecoder d, const float *enc, int batch, int T, const int *n_frames, int beam_width, int nbest,
+                                  int max_labels, const NntkRnntTdtBeamOptions *o, int *labels_out, int *out_lengths, float *scores);
 
 /* ---- RNN-Transducer: beam search (csrc/hip/rnnt_beam.hip; INTEGRATION.md "RNN-Transducer: beam search") ----
  * The model, the weight blocks, the decoder handle and max_symbols_per_frame (S below) are those of greedy decoding; W = beam_width.

@@ -75,6 +75,10 @@ class NntkRnntBeamOptions(C.Structure):
     _fields_ = [("lm", vp), ("length_norm", C.c_int), ("label_frames", vp), ("label_logps", vp)]
 
 
+class NntkRnntTdtBeamOptions(C.Structure):
+    _fields_ = [("lm", vp), ("length_norm", C.c_int), ("label_frames", vp), ("label_durations", vp), ("label_logps", vp)]
+
+
 class NntkCtcBeamOptions(C.Structure):
     _fields_ = [("lm", vp), ("label_frames", vp), ("label_logps", vp)]
 
@@ -551,6 +555,11 @@ SIGNATURES = {
     "nntk_rnnt_tdt_beam_workspace_floats": (C.c_size_t, [vp, C.c_int, C.c_int, C.c_int]),
     "nntk_rnnt_tdt_beam_decode_device": (C.c_int, [vp, vp, C.c_int, C.c_int, ip, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]),
     "nntk_rnnt_tdt_beam_decode": (C.c_int, [vp, fp, C.c_int, C.c_int, ip, C.c_int, C.c_int, C.c_int, ip, ip, fp]),
+    "nntk_rnnt_tdt_beam_opt_workspace_floats": (C.c_size_t, [vp, C.c_int, C.c_int, C.c_int, C.POINTER(NntkRnntTdtBeamOptions)]),
+    "nntk_rnnt_tdt_beam_decode_opt_device": (C.c_int, [vp, vp, C.c_int, C.c_int, ip, C.c_int, C.c_int, C.c_int,
+                                                       C.POINTER(NntkRnntTdtBeamOptions), vp, vp, vp, vp]),
+    "nntk_rnnt_tdt_beam_decode_opt": (C.c_int, [vp, fp, C.c_int, C.c_int, ip, C.c_int, C.c_int, C.c_int,
+                                                C.POINTER(NntkRnntTdtBeamOptions), ip, ip, fp]),
     "nntk_rnnt_beam_workspace_floats": (C.c_size_t, [vp, C.c_int, C.c_int, C.c_int]),
     "nntk_rnnt_beam_decode_device": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, ip, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]),
     "nntk_rnnt_beam_decode": (C.c_int, [vp, vp, fp, C.c_int, C.c_int, ip, C.c_int, C.c_int, C.c_int, ip, ip, fp]),

@@ -358,13 +358,9 @@ int nntk_shim_rnnt_tdt_greedy(const nntk_shim_rnnt_dec *m, const nntk_shim_rnnt_
  *      (h | c | g, max_labels labels, length and hash), a ring of Dmax + 1 buckets of 2 W (S' + 1) Dmax entries (a double and a slot
  *      each) and W V logits; every array padded to 4 words.  0: batch <= 0 or sizes beyond 2^29 slots or entries.  h_n_frames HOST
  *      [batch], checked by the caller, copied in stream order into the workspace; d_ws 16-byte aligned. ---- */
-size_t nntk_shim_rnnt_tdt_beam_workspace_floats(int batch, int H, int J, int V, int max_sym, int dmax, int beam_width, int max_labels);
 int nntk_shim_rnnt_tdt_beam_fits(int H, int J, int V, int D);                  /* the kernel's LDS at one hypothesis a pass */
 int nntk_shim_rnnt_tdt_beam_group(int beam_width, int H, int J, int V, int D);
 void nntk_shim_rnnt_tdt_beam_set_group(int group);
-int nntk_shim_rnnt_tdt_beam(const nntk_shim_rnnt_dec *m, const nntk_shim_rnnt_tdt_durs *du, const float *d_enc, int batch, int T,
-                            const int *h_n_frames, int beam_width, int nbest, int max_labels, int *d_labels, int *d_lengths, float *d_scores,
-                            float *d_ws);
 /* ---- transducer beam search (rnnt_beam.hip) on the greedy decoder's blocks.  One workgroup runs a row's whole search; the hypotheses
  *      of a depth share passes over the matrices in groups of NNTK_RNNT_DEC_GROUP where the group's LDS fits, else one by one
  *      (nntk_shim_rnnt_beam_group; nntk_shim_rnnt_beam_set_group(1 or NNTK_RNNT_DEC_GROUP) pins it for tests and timing, 0 = automatic;
@@ -413,6 +409,22 @@ typedef struct {
 int nntk_shim_rnnt_beam(const nntk_shim_rnnt_dec *m, const float *d_enc, int batch, int T, const int *h_n_frames, int beam_width, int nbest,
                         int max_labels, const nntk_shim_rnnt_beam_state *st, const nntk_shim_rnnt_lm *lm, int *d_st_q,
                         const nntk_shim_rnnt_beam_detail *dt, int *d_labels, int *d_lengths, float *d_scores, float *d_ws);
+/* The token-and-duration beam search's entry, behind nntk_shim_rnnt_lm which it shares with the classic one.  lm NULL: the acoustic
+ * search; with it every slot of the ring carries its state (4 bytes) and the row W V doubles of ln F, behind the acoustic workspace,
+ * which does not move.  dt NULL: no detail, the report in the search's own order (by score + ln E with lm).  dt (label frames,
+ * durations, confidences, length normalisation; each output [batch][nbest][max_labels] or NULL): behind both, 12 max_labels bytes a
+ * slot, 16 bytes a bucket entry (lead, the slot whose arrays it reports, its last label's duration) and 32 W bytes; the report is
+ * ranked by score or score / (length + 1).  The same search and the same LDS whatever lm and dt; the sizes take both as flags. */
+typedef struct {
+    int *d_frames, *d_durations;
+    float *d_logps;
+    int length_norm;
+} nntk_shim_rnnt_tdt_beam_detail;
+size_t nntk_shim_rnnt_tdt_beam_workspace_floats(int batch, int H, int J, int V, int max_sym, int dmax, int beam_width, int max_labels,
+                                                int with_lm, int with_detail);
+int nntk_shim_rnnt_tdt_beam(const nntk_shim_rnnt_dec *m, const nntk_shim_rnnt_tdt_durs *du, const float *d_enc, int batch, int T,
+                            const int *h_n_frames, int beam_width, int nbest, int max_labels, const nntk_shim_rnnt_lm *lm,
+                            const nntk_shim_rnnt_tdt_beam_detail *dt, int *d_labels, int *d_lengths, float *d_scores, float *d_ws);
 /* ---- the prediction network's label embedding, for training (rnnt_pred.hip).  rows_select: d_out [rows][width] = d_src[h_idx[r]][:], exact
  *      zeros for h_idx[r] < 0; h_idx HOST memory, checked by the caller, carried in the kernel arguments.  embedding_grad: d_dtable [V][E],
  *      every element written, from the caller's plan (rnnt_pred.c), HOST ints laid out offsets [V + 1] | sorted rows [n_sorted] | heavy

@@ -127,20 +127,6 @@ __device__ __forceinline__ double rb_logaddexp(double x, double y) {         // 
     return m + log1p(exp(d));
 }
 
-// next(q, v): the first state along q's backoff chain with an arc labelled v gives the arc's next state; none, state 0 included: 0
-__device__ static int rb_lm_next(const nntk_shim_rnnt_lm &lm, int s, int v) {
-    for (;;) {
-        int lo = lm.d_states[4 * s], hi = lo + lm.d_states[4 * s + 1] - 1;
-        while (lo <= hi) {
-            const int mid = lo + (hi - lo) / 2, c = lm.d_arcs[4 * (size_t)mid];
-            if (c == v) return lm.d_arcs[4 * (size_t)mid + 1];
-            if (c < v) lo = mid + 1; else hi = mid - 1;
-        }
-        if (s == 0) return 0;
-        s = lm.d_states[4 * s + 2];
-    }
-}
-
 template <int R, bool LM, bool DETAIL>
 __global__ __launch_bounds__(RD_THREADS) void rnnt_beam_kernel(const RnntBeamArgs a) {
     extern __shared__ __align__(16) unsigned char rb_smem[];
@@ -468,7 +454,7 @@ __global__ __launch_bounds__(RD_THREADS) void rnnt_beam_kernel(const RnntBeamArg
                 const unsigned nh = oh * 1000003u + (unsigned)(sh.n_lab[tid] + 1);
                 sh.n_src[tid] = ss; sh.c_slot[tid] = dst0 + tid; sh.c_score[tid] = sh.n_score[tid]; sh.c_len[tid] = ol + 1; sh.c_hash[tid] = nh;
                 meta[2 * (dst0 + tid)] = ol + 1; meta[2 * (dst0 + tid) + 1] = (int)nh;
-                if constexpr (LM) lmq[dst0 + tid] = rb_lm_next(a.lm, lmq[ss], sh.n_lab[tid]);
+                if constexpr (LM) lmq[dst0 + tid] = rd_lm_next(a.lm, lmq[ss], sh.n_lab[tid]);
             }
             if (tid == 0) sh.nC = nSel;
             __syncthreads();

@@ -67,3 +67,18 @@ __device__ __forceinline__ double rd_wave_sum_exp(const float *x, int V, int tid
     for (int off = 32; off > 0; off >>= 1) sum += __shfl_xor(sum, off);
     return sum;
 }
+
+// the n-gram automaton of the fused beam searches (rnnt_beam.hip, rnnt_tdt_beam.hip).  next(q, v): the first state along q's backoff
+// chain with an arc labelled v gives the arc's next state; none, state 0 included: 0
+__device__ static inline int rd_lm_next(const nntk_shim_rnnt_lm &lm, int s, int v) {
+    for (;;) {
+        int lo = lm.d_states[4 * s], hi = lo + lm.d_states[4 * s + 1] - 1;
+        while (lo <= hi) {
+            const int mid = lo + (hi - lo) / 2, c = lm.d_arcs[4 * (size_t)mid];
+            if (c == v) return lm.d_arcs[4 * (size_t)mid + 1];
+            if (c < v) lo = mid + 1; else hi = mid - 1;
+        }
+        if (s == 0) return 0;
+        s = lm.d_states[4 * s + 2];
+    }
+}

@@ -44,6 +44,27 @@
 // Workspace (tb_layout; nntk_shim_rnnt_tdt_beam_workspace_floats): the rows' frame counts, two counters per row (frames joined | LSTM
 // steps, for the timing tool), then per row  bscore [Dmax + 1][cap] doubles | bslot [Dmax + 1][cap] | states [slots][2H + J] |
 // labels [slots][max_labels] | meta [slots][2] | logits [W][V],  cap = 2 W (S' + 1) Dmax, slots = (Dmax + 1)(S' + 2) W.
+//
+// Language-model fusion (the LM = true instantiations; include/nntoolkitcore_hip.h, the options under the TDT beam search).  The state q
+// of the backoff automaton is one word per slot of the ring (lmq, behind the acoustic workspace, which does not move): a bucket entry's
+// q is its slot's, and equal label sequences have equal q, so merging needs no rule.  The selection's score still separates,
+// (base_i + (lp_tok[i][v] + lp_dur[i][k])) + lnF[i][v], and lnF does not depend on k: before the W rounds of a depth the row's
+// lmterm [W][V] doubles are filled, one walk per (i, v) whatever D, by scattering q_i's backoff chain as rnnt_beam.hip does (every
+// element marked unset; level by level, a barrier between levels, the lanes stride over the arcs of hypothesis i's state of that level
+// and an unset label takes acc + ln G(arc); what is still unset after state 0 takes acc + ln U).  A round reads one more double per
+// (i, v) and adds it last, in the header's order; a cell at -inf is no candidate, as before.  next(q_i, v) is looked up for the first
+// selected cell of each (i, v) only, with its slot.  No LDS is added.
+//
+// Label frames, durations, confidences and length normalisation (the DETAIL = true instantiations).  Behind the LM part: per slot
+// fr | du | lp [max_labels], copied wherever labs is copied; per bucket entry lead (the largest single contribution), bfslot (the slot
+// whose arrays it reports: a reference, not a copy -- that slot was written at most Dmax frames before the bucket is consumed, so it is
+// still on the ring) and bdur; per candidate of a phase cld.  Twins -- two selected cells (i, v, k), (i, v, k') -- share a slot and so
+// fr and lp, but not the last label's duration: that one value rides with the candidate (cld) and the bucket entry (bdur), and reaches
+// a slot's du only when the entry is copied into a frame's level 0 or reported.  A new slot's own last du is 0: what its hypothesis
+// took if it joins the next C, which only a duration-0 cell does.  The lane that applies a candidate compares it with lead and, if
+// it is larger, points bfslot and bdur at the candidate; the twin found in bucket[n] comes by the same lines.  The report (also the LM
+// one) takes the W best of bucket[n] and ranks them by score or score / (length + 1), every entry counting the entries ahead of it, on
+// arrays of TbShared that the frames have left free: no LDS is added, so tb_lds_bytes, fits and group hold for every instantiation.
 #include <limits.h>
 #include "rnnt_dec_common.hpp"
 
@@ -56,8 +77,17 @@ struct TbLayout {                          // offsets in floats from the row's b
     int frame_slots, cap, SF, depths;      // slots a frame, entries a bucket, floats of a state, S'
 };
 
-static TbLayout tb_layout(int H, int J, int V, int max_sym, int dmax, int W, int max_labels) {
+struct TbOptLayout {                       // behind the acoustic layout, which does not move; a part that is absent takes no room
+    size_t lmq, lmterm;                    // with a language model: [slots] ints | [W][V] doubles
+    size_t fr, du, lp;                     // with detail, per slot: [max_labels] ints | ints | floats
+    size_t lead, bfslot, bdur;             // ... per bucket entry: [Dmax + 1][cap] doubles | ints | ints
+    size_t cld;                            // ... per candidate of a phase: [W * 8] ints, its last label's duration
+};
+
+static TbLayout tb_layout(int H, int J, int V, int max_sym, int dmax, int W, int max_labels, bool lm = false, bool detail = false,
+                          TbOptLayout *opt = nullptr) {
     TbLayout l;
+    TbOptLayout o = TbOptLayout();
     l.depths = max_sym < max_labels ? max_sym : max_labels;
     l.frame_slots = (l.depths + 2) * W; l.cap = 2 * W * (l.depths + 1) * dmax; l.SF = 2 * H + J;
     const size_t ring = (size_t)dmax + 1, slots = ring * l.frame_slots;
@@ -69,7 +99,21 @@ static TbLayout tb_layout(int H, int J, int V, int max_sym, int dmax, int W, int
     l.labels = take(slots * max_labels);
     l.meta = take(2 * slots);
     l.logits = take((size_t)W * V);
+    if (lm) {
+        o.lmq = take(slots);
+        o.lmterm = take(2 * (size_t)W * V);
+    }
+    if (detail) {
+        o.fr = take(slots * max_labels);
+        o.du = take(slots * max_labels);
+        o.lp = take(slots * max_labels);
+        o.lead = take(2 * ring * l.cap);
+        o.bfslot = take(ring * l.cap);
+        o.bdur = take(ring * l.cap);
+        o.cld = take((size_t)W * TB_MAX_D);
+    }
     l.row = at;
+    if (opt) *opt = o;
     return l;
 }
 
@@ -91,6 +135,9 @@ struct TbArgs {
     size_t ws_head;
     int batch, T, V, blank, H, J, act, max_sym, W, nbest, max_labels;
     nntk_shim_rnnt_tdt_durs du;
+    TbOptLayout opt;                       // the LM and DETAIL instantiations only, as is what follows (lay.row counts both parts)
+    nntk_shim_rnnt_lm lm;
+    nntk_shim_rnnt_tdt_beam_detail dt;
 };
 
 template <int R> struct TbShared {
@@ -131,7 +178,7 @@ __device__ __forceinline__ int tb_duration(const nntk_shim_rnnt_tdt_durs &du, in
     return d;
 }
 
-template <int R>
+template <int R, bool LM, bool DETAIL>
 __global__ __launch_bounds__(RD_THREADS) void rnnt_tdt_beam_kernel(const TbArgs a) {
     extern __shared__ __align__(16) unsigned char tb_smem[];
     TbShared<R> &sh = *(TbShared<R> *)tb_smem;
@@ -148,6 +195,12 @@ __global__ __launch_bounds__(RD_THREADS) void rnnt_tdt_beam_kernel(const TbArgs 
     double *bscore = (double *)(row + a.lay.bscore);
     float *states = row + a.lay.states, *lg = row + a.lay.logits;
     int *bslot = (int *)(row + a.lay.bslot), *labs = (int *)(row + a.lay.labels), *meta = (int *)(row + a.lay.meta);
+    int *lmq = (int *)(row + a.opt.lmq);                                     // LM only, as is lmterm
+    double *lmterm = (double *)(row + a.opt.lmterm);
+    int *fr = (int *)(row + a.opt.fr), *du = (int *)(row + a.opt.du);        // DETAIL only, as are lp .. cld
+    float *lp = row + a.opt.lp;
+    double *lead = (double *)(row + a.opt.lead);
+    int *bfslot = (int *)(row + a.opt.bfslot), *bdur = (int *)(row + a.opt.bdur), *cld = (int *)(row + a.opt.cld);
     const int n = ((const int *)a.ws)[b];
     int joined = 0, steps = 0;                                               // lane 0's counters, for the timing tool
 
@@ -173,6 +226,7 @@ __global__ __launch_bounds__(RD_THREADS) void rnnt_tdt_beam_kernel(const TbArgs 
     };
 
     // the `count` best entries of ring position p's bucket (score descending, insertion index ascending) -> sh.n_slot, sh.n_score
+    // (DETAIL: and the entry's index -> sh.n_par, for its lead's arrays)
     auto bucket_best = [&](int p, int count) {
         const int nB = sh.nb[p];
         double prev_s = INFINITY;
@@ -188,6 +242,7 @@ __global__ __launch_bounds__(RD_THREADS) void rnnt_tdt_beam_kernel(const TbArgs 
             if (sh.best_i == INT_MAX) break;
             prev_s = sh.best_s; prev_i = sh.best_i;
             if (tid == 0) { sh.n_slot[k] = bslot[(size_t)p * cap + prev_i]; sh.n_score[k] = prev_s; }
+            if constexpr (DETAIL) { if (tid == 0) sh.n_par[k] = prev_i; }
             ++got;
         }
         __syncthreads();
@@ -353,6 +408,10 @@ __global__ __launch_bounds__(RD_THREADS) void rnnt_tdt_beam_kernel(const TbArgs 
                     for (int e2 = start_n; e2 < nbp; ++e2)
                         if (bslot[(size_t)pn * cap + e2] == slot) { e = e2; break; }
                 double *at = bscore + (size_t)p * cap;
+                if constexpr (DETAIL) {                                      // the dominant contributor's arrays and last duration; a tie
+                    const size_t en = (size_t)p * cap + (e >= 0 ? e : nbp);  // keeps what is there.  The twin of bucket[n] comes by here too
+                    if (e >= 0 ? s > lead[en] : nbp < cap) { lead[en] = s; bfslot[en] = slot; bdur[en] = cld[c]; }
+                }
                 if (e >= 0) at[e] = tb_logaddexp(at[e], s);
                 else if (nbp < cap) { bslot[(size_t)p * cap + nbp] = slot; at[nbp] = s; sh.nb[p] = nbp + 1; }
             }
@@ -365,6 +424,8 @@ __global__ __launch_bounds__(RD_THREADS) void rnnt_tdt_beam_kernel(const TbArgs 
     if (tid < RING) sh.nb[tid] = tid == 0;
     if (tid == 0) {
         meta[2 * slot0] = 0; meta[2 * slot0 + 1] = 0; bslot[0] = slot0; bscore[0] = 0.0;
+        if constexpr (LM) lmq[slot0] = a.lm.start_state;
+        if constexpr (DETAIL) { lead[0] = 0.0; bfslot[0] = slot0; bdur[0] = 0; }
         sh.st_src[0] = -1; sh.st_lab[0] = a.blank; sh.st_dst[0] = slot0;
     }
     __syncthreads();
@@ -379,6 +440,13 @@ __global__ __launch_bounds__(RD_THREADS) void rnnt_tdt_beam_kernel(const TbArgs 
             for (int j = tid; j < SF; j += RD_THREADS) states[(size_t)dst * SF + j] = states[(size_t)src * SF + j];
             for (int j = tid; j < len; j += RD_THREADS) labs[(size_t)dst * ML + j] = labs[(size_t)src * ML + j];
             if (tid == 0) { meta[2 * dst] = len; meta[2 * dst + 1] = meta[2 * src + 1]; }
+            if constexpr (LM) { if (tid == 0) lmq[dst] = lmq[src]; }
+            if constexpr (DETAIL) {                                          // the lead's arrays; the last duration is the entry's own
+                const size_t en = (size_t)p * cap + sh.n_par[k], from = (size_t)bfslot[en] * ML, to = (size_t)dst * ML;
+                for (int j = tid; j < len; j += RD_THREADS) {
+                    fr[to + j] = fr[from + j]; lp[to + j] = lp[from + j]; du[to + j] = j == len - 1 ? bdur[en] : du[from + j];
+                }
+            }
         }
         if (tid < nA) {
             const int src = sh.n_slot[tid];
@@ -397,6 +465,7 @@ __global__ __launch_bounds__(RD_THREADS) void rnnt_tdt_beam_kernel(const TbArgs 
                 const int c = i * Dp + __popc(a.du.pos_mask & ((1u << k) - 1)), f = t + tb_duration(a.du, k);
                 const double s = sh.c_score[i] + (sh.c_lpb[i] + sh.lp_dur[i][k]);
                 sh.cd_s[c] = s; sh.cd_slot[c] = sh.c_slot[i]; sh.cd_f[c] = s > -INFINITY ? (f < n ? f : n) : -1;
+                if constexpr (DETAIL) cld[c] = sh.c_len[i] ? du[(size_t)sh.c_slot[i] * ML + sh.c_len[i] - 1] : 0;
             }
             __syncthreads();
             merge_phase(nC * Dp);
@@ -404,6 +473,38 @@ __global__ __launch_bounds__(RD_THREADS) void rnnt_tdt_beam_kernel(const TbArgs 
             const unsigned kmask = depth > a.lay.depths ? 0u : last ? a.du.pos_mask : (1u << D) - 1;
             double prev_s = INFINITY;
             int prev_i = -1, nSel = 0;
+            if constexpr (LM) {
+                // lmterm[i][v] = ln F(q_i, v), one walk per (i, v) whatever the durations: q_i's backoff chain is scattered level by level
+                // (the arcs of the level's state over the lanes, an unset label takes acc + ln G), what no level set takes acc + ln U
+                for (int idx = tid; idx < nC * V; idx += RD_THREADS) lmterm[idx] = NAN;      // unset (no table value is a NaN)
+                __syncthreads();
+                for (int level = 0;; ++level) {
+                    bool more = false;
+                    for (int i = 0; i < nC; ++i) {
+                        int s = lmq[sh.c_slot[i]], l = 0;
+                        double acc = 0.0;
+                        for (; l < level && s != 0; ++l) { acc += a.lm.d_state_ln[2 * s]; s = a.lm.d_states[4 * s + 2]; }
+                        if (l < level) continue;                             // the chain ended at state 0, levels ago
+                        more |= s != 0;
+                        const int first = a.lm.d_states[4 * s], cnt = a.lm.d_states[4 * s + 1];
+                        for (int q = tid; q < cnt; q += RD_THREADS) {
+                            double *cell = lmterm + (size_t)i * V + a.lm.d_arcs[4 * (size_t)(first + q)];
+                            if (*cell != *cell) *cell = acc + a.lm.d_arc_ln[first + q];
+                        }
+                    }
+                    __syncthreads();
+                    if (!more) break;
+                }
+                for (int i = 0; i < nC; ++i) {
+                    double acc = 0.0;
+                    for (int s = lmq[sh.c_slot[i]]; s != 0; s = a.lm.d_states[4 * s + 2]) acc += a.lm.d_state_ln[2 * s];
+                    for (int v = tid; v < V; v += RD_THREADS) {
+                        const double x = lmterm[(size_t)i * V + v];
+                        if (x != x) lmterm[(size_t)i * V + v] = acc + a.lm.unk_ln;
+                    }
+                }
+                __syncthreads();
+            }
             for (int k = 0; k < W; ++k) {
                 double bs = -INFINITY;
                 int bi = INT_MAX;
@@ -414,9 +515,10 @@ __global__ __launch_bounds__(RD_THREADS) void rnnt_tdt_beam_kernel(const TbArgs 
                     for (int v = tid; v < V; v += RD_THREADS) {
                         if (v == a.blank) continue;
                         const double lt = (double)(lg[(size_t)i * V + v] - mx) - lse;
+                        const double lf = LM ? lmterm[(size_t)i * V + v] : 0.0;
                         for (int kk = 0; kk < D; ++kk) {
                             if (!((kmask >> kk) & 1)) continue;
-                            const double s = base + (lt + sh.lp_dur[i][kk]);
+                            const double s = LM ? (base + (lt + sh.lp_dur[i][kk])) + lf : base + (lt + sh.lp_dur[i][kk]);
                             const int idx = (i * V + v) * D + kk;
                             if (s > -INFINITY && (s < prev_s || (s == prev_s && idx > prev_i)) && (bi == INT_MAX || s > bs)) { bs = s; bi = idx; }
                         }
@@ -434,17 +536,24 @@ __global__ __launch_bounds__(RD_THREADS) void rnnt_tdt_beam_kernel(const TbArgs 
             const int dst0 = fb + (depth + 1) * W;
             int first = tid, ps = 0, ol = 0;
             unsigned oh = 0;
+            float nlp = 0.0f;                                                // DETAIL: the token head's lp_tok[v], as the selection formed it
             if (tid < nSel) {
                 const int i = sh.n_i[tid], v = sh.n_v[tid];
                 for (int j = 0; j < tid; ++j)
                     if (sh.n_i[j] == i && sh.n_v[j] == v) { first = j; break; }
                 ps = sh.c_slot[i]; ol = sh.c_len[i]; oh = sh.c_hash[i];
+                if constexpr (DETAIL) nlp = (float)((double)(lg[(size_t)i * V + v] - sh.c_max[i]) - sh.c_lse[i]);
             }
             __syncthreads();
             if (tid < nSel) {
                 const unsigned nh = oh * 1000003u + (unsigned)(sh.n_v[tid] + 1);
                 sh.n_slot[tid] = dst0 + first; sh.n_par[tid] = ps; sh.n_len[tid] = ol + 1; sh.n_hash[tid] = nh;
                 if (first == tid) { meta[2 * (dst0 + tid)] = ol + 1; meta[2 * (dst0 + tid) + 1] = (int)nh; }
+                if constexpr (LM) { if (first == tid) lmq[dst0 + tid] = rd_lm_next(a.lm, lmq[ps], sh.n_v[tid]); }
+                if constexpr (DETAIL) {                                      // duration 0: what the slot's own hypothesis (the next C) took;
+                    const size_t at = (size_t)(dst0 + tid) * ML + ol;        // a twin's positive one rides with its candidate and entry
+                    if (first == tid) { fr[at] = t; lp[at] = nlp; du[at] = 0; }
+                }
             }
             __syncthreads();
             if (tid == 0) {                                                  // the steps to run, the next C (duration 0), the moves (the rest)
@@ -457,6 +566,7 @@ __global__ __launch_bounds__(RD_THREADS) void rnnt_tdt_beam_kernel(const TbArgs 
                         ++nNext;
                     } else {
                         sh.cd_s[nCand] = sh.n_score[k]; sh.cd_slot[nCand] = slot; sh.cd_f[nCand] = t + d < n ? t + d : n;
+                        if constexpr (DETAIL) cld[nCand] = d;
                         ++nCand;
                     }
                 }
@@ -471,6 +581,10 @@ __global__ __launch_bounds__(RD_THREADS) void rnnt_tdt_beam_kernel(const TbArgs 
                 int *q = labs + (size_t)sh.st_dst[k] * ML;
                 for (int j = tid; j < L; j += RD_THREADS) q[j] = pl[j];
                 if (tid == 0) q[L] = sh.st_lab[k];
+                if constexpr (DETAIL) {
+                    const size_t from = (size_t)sh.st_src[k] * ML, to = (size_t)sh.st_dst[k] * ML;
+                    for (int j = tid; j < L; j += RD_THREADS) { fr[to + j] = fr[from + j]; lp[to + j] = lp[from + j]; du[to + j] = du[from + j]; }
+                }
             }
             for (int k0 = 0; k0 < nStep; k0 += R) step_group(k0, nStep - k0 < R ? nStep - k0 : R);
             merge_phase(sh.nCand);
@@ -479,6 +593,56 @@ __global__ __launch_bounds__(RD_THREADS) void rnnt_tdt_beam_kernel(const TbArgs 
         __syncthreads();
     }
 
+    if constexpr (LM || DETAIL) {
+        // the report: the W best of bucket[n], + ln E(q) with a model, the -inf ones dropped, ranked by score or score / (length + 1)
+        // (every entry counts the entries ahead of it; ties to the lower rank).  On what the frames have left free: the score in
+        // sh.c_score, the key in sh.c_lse, the order in sh.n_i, the kept count in sh.nCand
+        const int pn = n % RING, nW = bucket_best(pn, W);
+        if (tid < nW) {
+            double s = sh.n_score[tid];
+            if constexpr (LM) s += a.lm.d_state_ln[2 * lmq[sh.n_slot[tid]] + 1];
+            sh.c_score[tid] = s;
+            sh.c_lse[tid] = a.dt.length_norm ? s / (double)(meta[2 * sh.n_slot[tid]] + 1) : s;
+        }
+        __syncthreads();
+        if (tid < nW) {
+            const double s = sh.c_lse[tid];
+            int ahead = 0;
+            for (int j = 0; j < nW; ++j) {
+                const double o = sh.c_lse[j];
+                ahead += o > -INFINITY && (o > s || (o == s && j < tid));
+            }
+            if (s > -INFINITY) sh.n_i[ahead] = tid;
+        }
+        if (tid == 0) {
+            int kept = 0;
+            for (int j = 0; j < nW; ++j) kept += sh.c_lse[j] > -INFINITY;
+            sh.nCand = kept;
+        }
+        __syncthreads();
+        const int kept = sh.nCand;
+        for (int k = 0; k < a.nbest; ++k) {
+            const size_t o = (size_t)b * a.nbest + k;
+            const int src = k < kept ? sh.n_i[k] : 0, slot = sh.n_slot[src], len = k < kept ? meta[2 * slot] : 0;
+            size_t from = 0;
+            int ld = 0;
+            if constexpr (DETAIL) {
+                if (k < kept) { const size_t en = (size_t)pn * cap + sh.n_par[src]; from = (size_t)bfslot[en] * ML; ld = bdur[en]; }
+            }
+            for (int j = tid; j < ML; j += RD_THREADS) {
+                a.labels[o * ML + j] = j < len ? labs[(size_t)slot * ML + j] : -1;
+                if constexpr (DETAIL) {
+                    if (a.dt.d_frames) a.dt.d_frames[o * ML + j] = j < len ? fr[from + j] : -1;
+                    if (a.dt.d_durations) a.dt.d_durations[o * ML + j] = j < len ? (j == len - 1 ? ld : du[from + j]) : -1;
+                    if (a.dt.d_logps) a.dt.d_logps[o * ML + j] = j < len ? lp[from + j] : 0.0f;
+                }
+            }
+            if (tid == 0) {
+                a.lengths[o] = k < kept ? len : -1;
+                a.scores[o] = k < kept ? (float)sh.c_score[src] : -INFINITY;
+            }
+        }
+    } else {
     const int nOut = bucket_best(n % RING, a.nbest);
     for (int k = 0; k < a.nbest; ++k) {
         const size_t o = (size_t)b * a.nbest + k;
@@ -489,19 +653,29 @@ __global__ __launch_bounds__(RD_THREADS) void rnnt_tdt_beam_kernel(const TbArgs 
             a.scores[o] = k < nOut ? (float)sh.n_score[k] : -INFINITY;
         }
     }
+    }
     if (tid == 0) {
         int *stat = (int *)a.ws + (((size_t)a.batch + 3) & ~(size_t)3) + 2 * (size_t)b;
         stat[0] = joined; stat[1] = steps;
     }
 }
 
+typedef void (*TbKernel)(const TbArgs);
+
+template <int R> static TbKernel tb_kernel(bool lm, bool detail) {
+    static const TbKernel k[2][2] = { { rnnt_tdt_beam_kernel<R, false, false>, rnnt_tdt_beam_kernel<R, false, true> },
+                                      { rnnt_tdt_beam_kernel<R, true, false>, rnnt_tdt_beam_kernel<R, true, true> } };
+    return k[lm][detail];
+}
+
 static int tb_forced_group = 0;
 
 extern "C" {
 
-size_t nntk_shim_rnnt_tdt_beam_workspace_floats(int batch, int H, int J, int V, int max_sym, int dmax, int beam_width, int max_labels) {
+size_t nntk_shim_rnnt_tdt_beam_workspace_floats(int batch, int H, int J, int V, int max_sym, int dmax, int beam_width, int max_labels,
+                                                int with_lm, int with_detail) {
     if (batch <= 0 || !tb_sizes_ok(max_sym, dmax, beam_width, max_labels)) return 0;
-    return tb_head(batch) + (size_t)batch * tb_layout(H, J, V, max_sym, dmax, beam_width, max_labels).row;
+    return tb_head(batch) + (size_t)batch * tb_layout(H, J, V, max_sym, dmax, beam_width, max_labels, with_lm != 0, with_detail != 0).row;
 }
 
 int nntk_shim_rnnt_tdt_beam_fits(int H, int J, int V, int D) { return tb_lds_bytes(1, H, J, V + D) <= RD_LDS_MAX; }
@@ -515,8 +689,8 @@ int nntk_shim_rnnt_tdt_beam_group(int beam_width, int H, int J, int V, int D) {
 void nntk_shim_rnnt_tdt_beam_set_group(int group) { tb_forced_group = group == 1 || group == NNTK_RNNT_DEC_GROUP ? group : 0; }
 
 int nntk_shim_rnnt_tdt_beam(const nntk_shim_rnnt_dec *m, const nntk_shim_rnnt_tdt_durs *du, const float *d_enc, int batch, int T,
-                            const int *h_n_frames, int beam_width, int nbest, int max_labels, int *d_labels, int *d_lengths, float *d_scores,
-                            float *d_ws) {
+                            const int *h_n_frames, int beam_width, int nbest, int max_labels, const nntk_shim_rnnt_lm *lm,
+                            const nntk_shim_rnnt_tdt_beam_detail *dt, int *d_labels, int *d_lengths, float *d_scores, float *d_ws) {
     if (batch <= 0) return 0;
     const int dmax = du->n >= 1 && du->n <= TB_MAX_D ? du->dur[du->n - 1] : 0;
     if (m->E < 1 || m->H < 1 || m->J < 1 || m->V < 2 || m->H > NNTK_RNNT_DEC_MAX_WIDTH || m->J > NNTK_RNNT_DEC_MAX_WIDTH ||
@@ -529,20 +703,18 @@ int nntk_shim_rnnt_tdt_beam(const nntk_shim_rnnt_dec *m, const nntk_shim_rnnt_td
     a.enc = d_enc; a.table = m->d_table; a.U = m->d_U; a.proj = m->d_proj; a.out = m->d_out;
     a.ws = d_ws;
     a.labels = d_labels; a.lengths = d_lengths; a.scores = d_scores;
-    a.lay = tb_layout(m->H, m->J, m->V, m->max_symbols_per_frame, dmax, beam_width, max_labels);
+    a.lm = lm ? *lm : nntk_shim_rnnt_lm();
+    a.dt = dt ? *dt : nntk_shim_rnnt_tdt_beam_detail();
+    a.lay = tb_layout(m->H, m->J, m->V, m->max_symbols_per_frame, dmax, beam_width, max_labels, lm != nullptr, dt != nullptr, &a.opt);
     a.ws_head = tb_head(batch);
     a.batch = batch; a.T = T; a.V = m->V; a.blank = m->blank; a.H = m->H; a.J = m->J; a.act = m->activation;
     a.max_sym = m->max_symbols_per_frame; a.W = beam_width; a.nbest = nbest; a.max_labels = max_labels;
     a.du = *du;
     const int R = nntk_shim_rnnt_tdt_beam_group(beam_width, m->H, m->J, m->V, du->n);
     const size_t lds = tb_lds_bytes(R, m->H, m->J, m->V + du->n);
-    if (R == 1) {
-        if (lds > 48 * 1024 && nntk_set_max_dynamic_lds((const void *)rnnt_tdt_beam_kernel<1>, lds)) return -1;
-        hipLaunchKernelGGL(rnnt_tdt_beam_kernel<1>, dim3((unsigned)batch), dim3(RD_THREADS), lds, nntk_stream(), a);
-    } else {
-        if (lds > 48 * 1024 && nntk_set_max_dynamic_lds((const void *)rnnt_tdt_beam_kernel<NNTK_RNNT_DEC_GROUP>, lds)) return -1;
-        hipLaunchKernelGGL(rnnt_tdt_beam_kernel<NNTK_RNNT_DEC_GROUP>, dim3((unsigned)batch), dim3(RD_THREADS), lds, nntk_stream(), a);
-    }
+    const TbKernel k = R == 1 ? tb_kernel<1>(lm != nullptr, dt != nullptr) : tb_kernel<NNTK_RNNT_DEC_GROUP>(lm != nullptr, dt != nullptr);
+    if (lds > 48 * 1024 && nntk_set_max_dynamic_lds((const void *)k, lds)) return -1;
+    hipLaunchKernelGGL(k, dim3((unsigned)batch), dim3(RD_THREADS), lds, nntk_stream(), a);
     NNTK_LAUNCH_CHECK("rnnt_tdt_beam_kernel");
     return 0;
 }

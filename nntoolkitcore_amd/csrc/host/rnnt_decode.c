@@ -625,20 +625,32 @@ int nntk_rnnt_beam_decode_lm(NntkRnntDecoder d, NntkRnntBeamState state, const f
                             out_lengths, scores);
 }
 
-/* ---- token-and-duration beam search (csrc/hip/rnnt_tdt_beam.hip) on a handle of nntk_rnnt_tdt_decoder_create, one-shot ---- */
+/* ---- token-and-duration beam search (csrc/hip/rnnt_tdt_beam.hip) on a handle of nntk_rnnt_tdt_decoder_create, one-shot; o NULL or
+ *      everything off: the plain call ---- */
 
-size_t nntk_rnnt_tdt_beam_workspace_floats(NntkRnntDecoder d, int batch, int beam_width, int max_labels) {
+static int tdt_beam_opt_detail(const NntkRnntTdtBeamOptions *o) { return o && (o->label_frames || o->label_durations || o->label_logps); }
+
+/* the kernels with detail also rank the report, so length normalisation alone takes them and their workspace */
+static int tdt_beam_opt_kernel(const NntkRnntTdtBeamOptions *o) { return tdt_beam_opt_detail(o) || (o && o->length_norm); }
+
+size_t nntk_rnnt_tdt_beam_opt_workspace_floats(NntkRnntDecoder d, int batch, int beam_width, int max_labels, const NntkRnntTdtBeamOptions *o) {
     if (!d || !d->du.n || batch <= 0 || beam_width < 1 || beam_width > NNTK_RNNT_BEAM_MAX_W || max_labels < 1) return 0;
     return nntk_shim_rnnt_tdt_beam_workspace_floats(batch, d->cfg.H, d->cfg.J, d->cfg.V, d->cfg.max_symbols_per_frame, d->du.dur[d->du.n - 1],
-                                                    beam_width, max_labels);
+                                                    beam_width, max_labels, o && o->lm, tdt_beam_opt_kernel(o));
+}
+
+size_t nntk_rnnt_tdt_beam_workspace_floats(NntkRnntDecoder d, int batch, int beam_width, int max_labels) {
+    return nntk_rnnt_tdt_beam_opt_workspace_floats(d, batch, beam_width, max_labels, NULL);
 }
 
 /* everything the call can be refused for; device_form 0: the host-pointer form, which owns its workspace */
 static int tdt_beam_check_call(const char *who, NntkRnntDecoder d, const float *enc, int batch, int T, const int *n_frames, int beam_width,
-                               int nbest, int max_labels, const int *labels_out, const int *out_lengths, const float *scores, const float *ws,
-                               int device_form) {
+                               int nbest, int max_labels, const NntkRnntTdtBeamOptions *o, const int *labels_out, const int *out_lengths,
+                               const float *scores, const float *ws, int device_form) {
     if (!d) return dec_fail(who, "NULL decoder", 0, 0, 0);
     if (!d->du.n) return dec_fail(who, "the decoder has no durations (nntk_rnnt_decoder_create): nntk_rnnt_beam_decode_device serves it", 0, 0, 0);
+    if (o && o->length_norm != 0 && o->length_norm != 1) return dec_fail(who, "length_norm %ld is neither 0 nor 1", o->length_norm, 0, 0);
+    if (beam_check_lm(who, d, o ? o->lm : NULL)) return -1;
     if (batch < 0 || T < 0) return dec_fail(who, "batch %ld, T %ld: neither may be negative", batch, T, 0);
     if (beam_width < 1 || beam_width > NNTK_RNNT_BEAM_MAX_W)
         return dec_fail(who, "beam_width %ld is outside [1, %ld]", beam_width, NNTK_RNNT_BEAM_MAX_W, 0);
@@ -650,59 +662,100 @@ static int tdt_beam_check_call(const char *who, NntkRnntDecoder d, const float *
     if (T > 0 && dec_named_ptr(who, "enc", enc)) return -1;
     if (dec_named_ptr(who, "labels_out", labels_out) || dec_named_ptr(who, "out_lengths", out_lengths) ||
         dec_named_ptr(who, "scores", scores)) return -1;
+    if (o && o->label_frames && dec_named_ptr(who, "label_frames", o->label_frames)) return -1;
+    if (o && o->label_durations && dec_named_ptr(who, "label_durations", o->label_durations)) return -1;
+    if (o && o->label_logps && dec_named_ptr(who, "label_logps", o->label_logps)) return -1;
     if (device_form && (!ws || ((uintptr_t)ws & 15)))
         return dec_fail(who, ws ? "workspace is not 16-byte aligned" : "workspace is NULL", 0, 0, 0);
     if (!nntk_shim_rnnt_tdt_beam_fits(d->cfg.H, d->cfg.J, d->cfg.V, d->du.n))
         return dec_fail(who, "the model (H %ld, max(4H, V + D) %ld floats a hypothesis) is beyond the beam kernel's LDS", d->cfg.H,
                         4 * d->cfg.H > d->cfg.V + d->du.n ? 4 * d->cfg.H : d->cfg.V + d->du.n, 0);
-    const size_t need = nntk_rnnt_tdt_beam_workspace_floats(d, batch, beam_width, max_labels);
+    const size_t need = nntk_rnnt_tdt_beam_opt_workspace_floats(d, batch, beam_width, max_labels, o);
     if (!need) return dec_fail(who, "max_symbols_per_frame %ld, max_labels %ld and the largest duration %ld ask for more than 2^29 slots",
                                d->cfg.max_symbols_per_frame, max_labels, d->du.dur[d->du.n - 1]);
-    const size_t nh = (size_t)batch * nbest;
-    const void *p[5] = { labels_out, out_lengths, scores, enc, ws };
-    const size_t n[5] = { nh * max_labels * sizeof(int), nh * sizeof(int), nh * sizeof(float), (size_t)batch * T * d->cfg.J * sizeof(float),
+    const size_t nh = (size_t)batch * nbest, nl = nh * max_labels * sizeof(int);
+    const void *p[8] = { labels_out, out_lengths, scores, o ? o->label_frames : NULL, o ? o->label_durations : NULL,
+                         o ? o->label_logps : NULL, enc, ws };
+    const size_t n[8] = { nl, nh * sizeof(int), nh * sizeof(float), nl, nl, nl, (size_t)batch * T * d->cfg.J * sizeof(float),
                           device_form ? need * sizeof(float) : 0 };
-    static const char *const name[5] = { "labels_out", "out_lengths", "scores", "enc", "workspace" };
-    return dec_check_overlaps(who, 3, 5, p, n, name);
+    static const char *const name[8] = { "labels_out", "out_lengths", "scores", "label_frames", "label_durations", "label_logps", "enc",
+                                         "workspace" };
+    return dec_check_overlaps(who, 6, 8, p, n, name);
 }
 
 static int tdt_beam_device(const char *who, NntkRnntDecoder d, const float *d_enc, int batch, int T, const int *n_frames, int beam_width,
-                           int nbest, int max_labels, int *d_labels_out, int *d_out_lengths, float *d_scores, float *d_workspace) {
+                           int nbest, int max_labels, const NntkRnntTdtBeamOptions *o, int *d_labels_out, int *d_out_lengths,
+                           float *d_scores, float *d_workspace) {
     nntk_shim_clear_error();
-    if (tdt_beam_check_call(who, d, d_enc, batch, T, n_frames, beam_width, nbest, max_labels, d_labels_out, d_out_lengths, d_scores,
+    if (tdt_beam_check_call(who, d, d_enc, batch, T, n_frames, beam_width, nbest, max_labels, o, d_labels_out, d_out_lengths, d_scores,
                             d_workspace, 1)) return -1;
     if (batch == 0) return 0;
+    NntkNgramLm lm = o ? o->lm : NULL;
+    nntk_shim_rnnt_lm tab;
+    if (lm && nntk_ngram_lm_rnnt_device(lm, &tab)) return -1;
     int *len = dec_row_frames("nntk_rnnt_tdt_beam_decode_device: out of host memory", n_frames, batch, T);
     if (!len) return -1;
     const nntk_shim_rnnt_dec m = dec_model(d);
-    int rc = nntk_shim_rnnt_tdt_beam(&m, &d->du, d_enc, batch, T, len, beam_width, nbest, max_labels, d_labels_out, d_out_lengths, d_scores,
-                                     d_workspace);
+    const nntk_shim_rnnt_tdt_beam_detail dt = { o ? o->label_frames : NULL, o ? o->label_durations : NULL, o ? o->label_logps : NULL,
+                                                o ? o->length_norm : 0 };
+    int rc = nntk_shim_rnnt_tdt_beam(&m, &d->du, d_enc, batch, T, len, beam_width, nbest, max_labels, lm ? &tab : NULL,
+                                     tdt_beam_opt_kernel(o) ? &dt : NULL, d_labels_out, d_out_lengths, d_scores, d_workspace);
     free(len);
     return rc;
 }
 
 int nntk_rnnt_tdt_beam_decode_device(NntkRnntDecoder d, const float *d_enc, int batch, int T, const int *n_frames, int beam_width, int nbest,
                                      int max_labels, int *d_labels_out, int *d_out_lengths, float *d_scores, float *d_workspace) {
-    return tdt_beam_device("nntk_rnnt_tdt_beam_decode_device", d, d_enc, batch, T, n_frames, beam_width, nbest, max_labels, d_labels_out,
+    return tdt_beam_device("nntk_rnnt_tdt_beam_decode_device", d, d_enc, batch, T, n_frames, beam_width, nbest, max_labels, NULL, d_labels_out,
                            d_out_lengths, d_scores, d_workspace);
+}
+
+int nntk_rnnt_tdt_beam_decode_opt_device(NntkRnntDecoder d, const float *d_enc, int batch, int T, const int *n_frames, int beam_width,
+                                         int nbest, int max_labels, const NntkRnntTdtBeamOptions *o, int *d_labels_out,
+                                         int *d_out_lengths, float *d_scores, float *d_workspace) {
+    return tdt_beam_device("nntk_rnnt_tdt_beam_decode_opt_device", d, d_enc, batch, T, n_frames, beam_width, nbest, max_labels, o,
+                           d_labels_out, d_out_lengths, d_scores, d_workspace);
+}
+
+static int tdt_beam_host(const char *who, NntkRnntDecoder d, const float *enc, int batch, int T, const int *n_frames, int beam_width,
+                         int nbest, int max_labels, const NntkRnntTdtBeamOptions *o, int *labels_out, int *out_lengths, float *scores) {
+    nntk_shim_clear_error();
+    if (tdt_beam_check_call(who, d, enc, batch, T, n_frames, beam_width, nbest, max_labels, o, labels_out, out_lengths, scores, NULL, 0))
+        return -1;
+    if (batch == 0) return 0;
+    const size_t ne = (size_t)batch * T * d->cfg.J, nh = (size_t)batch * nbest, nl = nh * max_labels;
+    const int detail = tdt_beam_opt_detail(o);
+    float *d_enc = nntk_devbuf_reserve(&t_a, ne + 4);
+    int *d_lab = (int *)nntk_devbuf_reserve(&t_b, (detail ? 4 : 1) * nl + 2 * nh + 4);
+    float *d_ws = nntk_devbuf_reserve(nntk_thread_scratch(NNTK_TS_C), nntk_rnnt_tdt_beam_opt_workspace_floats(d, batch, beam_width, max_labels, o));
+    if (!d_enc || !d_lab || !d_ws) return -1;
+    int *d_len = d_lab + nl;
+    float *d_sc = (float *)(d_len + nh);
+    NntkRnntTdtBeamOptions dev = { NULL, 0, NULL, NULL, NULL };       /* o with the detail outputs in device memory, behind the scores */
+    if (o) dev = *o;
+    if (detail) {
+        dev.label_frames = o->label_frames ? (int *)(d_sc + nh) : NULL;
+        dev.label_durations = o->label_durations ? (int *)(d_sc + nh) + nl : NULL;
+        dev.label_logps = o->label_logps ? d_sc + nh + 2 * nl : NULL;
+    }
+    if (ne && nntk_shim_upload(d_enc, enc, ne * sizeof(float))) return -1;
+    if (tdt_beam_device(who, d, d_enc, batch, T, n_frames, beam_width, nbest, max_labels, o ? &dev : NULL, d_lab, d_len, d_sc, d_ws)) return -1;
+    if (nntk_shim_download(labels_out, d_lab, nl * sizeof(int))) return -1;
+    if (nntk_shim_download(out_lengths, d_len, nh * sizeof(int))) return -1;
+    if (dev.label_frames && nntk_shim_download(o->label_frames, dev.label_frames, nl * sizeof(int))) return -1;
+    if (dev.label_durations && nntk_shim_download(o->label_durations, dev.label_durations, nl * sizeof(int))) return -1;
+    if (dev.label_logps && nntk_shim_download(o->label_logps, dev.label_logps, nl * sizeof(float))) return -1;
+    return nntk_shim_download(scores, d_sc, nh * sizeof(float));
 }
 
 int nntk_rnnt_tdt_beam_decode(NntkRnntDecoder d, const float *enc, int batch, int T, const int *n_frames, int beam_width, int nbest,
                               int max_labels, int *labels_out, int *out_lengths, float *scores) {
-    static const char who[] = "nntk_rnnt_tdt_beam_decode";
-    nntk_shim_clear_error();
-    if (tdt_beam_check_call(who, d, enc, batch, T, n_frames, beam_width, nbest, max_labels, labels_out, out_lengths, scores, NULL, 0)) return -1;
-    if (batch == 0) return 0;
-    const size_t ne = (size_t)batch * T * d->cfg.J, nh = (size_t)batch * nbest, nl = nh * max_labels;
-    float *d_enc = nntk_devbuf_reserve(&t_a, ne + 4);
-    int *d_lab = (int *)nntk_devbuf_reserve(&t_b, nl + 2 * nh + 4);
-    float *d_ws = nntk_devbuf_reserve(nntk_thread_scratch(NNTK_TS_C), nntk_rnnt_tdt_beam_workspace_floats(d, batch, beam_width, max_labels));
-    if (!d_enc || !d_lab || !d_ws) return -1;
-    int *d_len = d_lab + nl;
-    float *d_sc = (float *)(d_len + nh);
-    if (ne && nntk_shim_upload(d_enc, enc, ne * sizeof(float))) return -1;
-    if (tdt_beam_device(who, d, d_enc, batch, T, n_frames, beam_width, nbest, max_labels, d_lab, d_len, d_sc, d_ws)) return -1;
-    if (nntk_shim_download(labels_out, d_lab, nl * sizeof(int))) return -1;
-    if (nntk_shim_download(out_lengths, d_len, nh * sizeof(int))) return -1;
-    return nntk_shim_download(scores, d_sc, nh * sizeof(float));
+    return tdt_beam_host("nntk_rnnt_tdt_beam_decode", d, enc, batch, T, n_frames, beam_width, nbest, max_labels, NULL, labels_out,
+                         out_lengths, scores);
+}
+
+int nntk_rnnt_tdt_beam_decode_opt(NntkRnntDecoder d, const float *enc, int batch, int T, const int *n_frames, int beam_width, int nbest,
+                                  int max_labels, const NntkRnntTdtBeamOptions *o, int *labels_out, int *out_lengths, float *scores) {
+    return tdt_beam_host("nntk_rnnt_tdt_beam_decode_opt", d, enc, batch, T, n_frames, beam_width, nbest, max_labels, o, labels_out,
+                         out_lengths, scores);
 }

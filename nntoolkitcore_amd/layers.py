@@ -1646,29 +1646,39 @@ class RnntDecoder:
         return self._beam(None, enc, n_frames, beam_width, nbest, max_labels, outs,
                           self._beam_workspace(enc.device, B, beam_width, max_labels, lm, detail, length_norm), lm, length_norm)
 
-    def _tdt_beam(self, enc, n_frames, beam_width, nbest, max_labels, workspace=None):
-        """the device call on given or own workspace -> (labels, lengths, scores), the workspace"""
+    def _tdt_beam(self, enc, n_frames, beam_width, nbest, max_labels, workspace=None, lm=None, detail=False, length_norm=False):
+        """the device call on given or own workspace -> (labels, lengths, scores[, label_frames, label_durations, label_logps]), the
+        workspace; with nothing on it is the plain entry, else ``nntk_rnnt_tdt_beam_decode_opt_device``"""
         import torch
         B, T, J = enc.shape
         assert J == self.J, "enc: [B, T, J]"
         L = capi.load()
-        if workspace is None:
-            need = L.nntk_rnnt_tdt_beam_workspace_floats(self.h, B, int(beam_width), int(max_labels))
-            workspace = torch.empty(max(int(need), 4), dtype=torch.float32, device=enc.device)
+        opt = lm is not None or detail or length_norm
         outs = self._beam_outputs(enc.device, B, max(int(nbest), 1), max_labels)
-        check(L.nntk_rnnt_tdt_beam_decode_device(self.h, _dp(enc), B, T, _n_frames_ptr(n_frames, B), int(beam_width), int(nbest),
-                                                 int(max_labels), _ipv(outs[0]), _ipv(outs[1]), _dp(outs[2]), _dp(workspace)),
-              "nntk_rnnt_tdt_beam_decode_device")
+        if detail:
+            shape = outs[0].shape
+            outs = outs + (torch.empty(shape, dtype=torch.int32, device=enc.device), torch.empty(shape, dtype=torch.int32, device=enc.device),
+                           torch.empty(shape, dtype=torch.float32, device=enc.device))
+        o = capi.NntkRnntTdtBeamOptions(lm.h if lm is not None else None, int(bool(length_norm)), *(t.data_ptr() for t in outs[3:]))
+        if workspace is None:
+            need = L.nntk_rnnt_tdt_beam_opt_workspace_floats(self.h, B, int(beam_width), int(max_labels), C.byref(o) if opt else None)
+            workspace = torch.empty(max(int(need), 4), dtype=torch.float32, device=enc.device)
+        entry = "nntk_rnnt_tdt_beam_decode_opt_device" if opt else "nntk_rnnt_tdt_beam_decode_device"
+        check(getattr(L, entry)(self.h, _dp(enc), B, T, _n_frames_ptr(n_frames, B), int(beam_width), int(nbest), int(max_labels),
+                                *((C.byref(o),) if opt else ()), _ipv(outs[0]), _ipv(outs[1]), _dp(outs[2]), _dp(workspace)), entry)
         return outs, workspace
 
-    def tdt_beam_decode(self, enc, n_frames=None, beam_width=8, nbest=1, max_labels=None):
+    def tdt_beam_decode(self, enc, n_frames=None, beam_width=8, nbest=1, max_labels=None, lm=None, detail=False, length_norm=False):
         """``nntk_rnnt_tdt_beam_decode_device`` (INTEGRATION.md "RNN-Transducer: token-and-duration beam search"), on a decoder with
         durations: enc [B, T, J] device tensor, n_frames host ints per row (None: T) -> (labels [B, nbest, max_labels] int32, -1 behind
         each hypothesis's labels; lengths [B, nbest] int32, -1 for a slot without a hypothesis; scores [B, nbest] float32, -inf there).
-        max_labels defaults to max_symbols_per_frame * T."""
+        max_labels defaults to max_symbols_per_frame * T.  lm: an NgramLm fused into the search, or None; detail: also return
+        label_frames and label_durations, int32 in the shape of labels, -1 behind the labels' (the frame each label was emitted in and
+        the duration it took) and label_logps, float32, 0 there (the token head's log-probability): six tensors; length_norm: the n-best
+        is ordered by score / (length + 1), scores stay plain (``nntk_rnnt_tdt_beam_decode_opt_device``)."""
         if max_labels is None:
             max_labels = max(1, self.max_symbols * enc.shape[1])
-        return self._tdt_beam(enc, n_frames, beam_width, nbest, max_labels)[0]
+        return self._tdt_beam(enc, n_frames, beam_width, nbest, max_labels, None, lm, detail, length_norm)[0]
 
     def destroy(self):
         if self.h:
@@ -1833,20 +1843,26 @@ def rnnt_tdt_greedy_decode(embed, lstm_block, pred_proj, out, enc, durations, n_
 
 
 def rnnt_tdt_beam_decode(embed, lstm_block, pred_proj, out, enc, durations, n_frames=None, beam_width=8, nbest=1, max_labels=None, blank=0,
-                         joint_activation=ACT_TANH, max_symbols_per_frame=10):
+                         joint_activation=ACT_TANH, max_symbols_per_frame=10, lm=None, detail=False, length_norm=False):
     """Token-and-duration beam search on numpy arrays (``nntk_rnnt_tdt_beam_decode``): out W [J, V + D] | b [V + D], enc [B, T, J]
-    -> (labels [B, nbest, max_labels], lengths [B, nbest], scores [B, nbest])"""
+    -> (labels [B, nbest, max_labels], lengths [B, nbest], scores [B, nbest]).  lm, detail, length_norm: as in
+    ``RnntDecoder.tdt_beam_decode`` (``nntk_rnnt_tdt_beam_decode_opt``; with detail label_frames, label_durations and label_logps follow
+    the scores)."""
     dec, enc, B, T, max_labels = _rnnt_host_decoder(embed, lstm_block, pred_proj, out, enc, max_labels, blank, joint_activation,
                                                     max_symbols_per_frame, durations)
     labels = np.empty((B, nbest, max_labels), np.int32)
     lengths, scores = np.empty((B, nbest), np.int32), np.empty((B, nbest), np.float32)
+    extra = (np.empty(labels.shape, np.int32), np.empty(labels.shape, np.int32), np.empty(labels.shape, np.float32)) if detail else ()
+    opt = lm is not None or detail or length_norm
+    o = capi.NntkRnntTdtBeamOptions(lm.h if lm is not None else None, int(bool(length_norm)), *(x.ctypes.data for x in extra))
+    entry = "nntk_rnnt_tdt_beam_decode_opt" if opt else "nntk_rnnt_tdt_beam_decode"
     try:
-        check(capi.load().nntk_rnnt_tdt_beam_decode(dec.h, _p(enc), B, T, _n_frames_ptr(n_frames, B), int(beam_width), int(nbest),
-                                                    int(max_labels), labels.ctypes.data_as(capi.ip), lengths.ctypes.data_as(capi.ip),
-                                                    _p(scores)), "nntk_rnnt_tdt_beam_decode")
+        check(getattr(capi.load(), entry)(dec.h, _p(enc), B, T, _n_frames_ptr(n_frames, B), int(beam_width), int(nbest), int(max_labels),
+                                          *((C.byref(o),) if opt else ()), labels.ctypes.data_as(capi.ip),
+                                          lengths.ctypes.data_as(capi.ip), _p(scores)), entry)
     finally:
         dec.destroy()
-    return labels, lengths, scores
+    return (labels, lengths, scores) + extra
 
 
 def _host_ids(ids):
