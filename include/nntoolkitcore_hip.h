@@ -1494,8 +1494,8 @@ int nntk_rnnt_tdt_greedy_decode(NntkRnntDecoder d, NntkRnntDecodeState state, co
  * Deterministic: no atomics, the same bits on every call; a row's bits do not depend on the other rows, its position in the batch,
  * the T padding, or how many hypotheses share a pass over a matrix.  One launch on the calling thread's stream.  The host-pointer
  * form uploads, runs the device form on a workspace of its own and downloads.  Language-model fusion, label frames, durations and
- * confidences, and length normalisation: nntk_rnnt_tdt_beam_decode_opt_device below.  Not in these calls, a follow-up on the kernel:
- * streaming with a carried ring. */
+ * confidences, and length normalisation: nntk_rnnt_tdt_beam_decode_opt_device below; streamed: nntk_rnnt_tdt_beam_stream_push_device
+ * below that. */
 size_t nntk_rnnt_tdt_beam_workspace_floats(NntkRnntDecoder d, int batch, int beam_width, int max_labels);
 int nntk_rnnt_tdt_beam_decode_device(NntkRnntDecoder d, const float *d_enc, int batch, int T, const int *n_frames, int beam_width, int nbest,
                                      int max_labels, int *d_labels_out, int *d_out_lengths, float *d_scores, float *d_workspace);
@@ -1550,6 +1550,46 @@ int nntk_rnnt_tdt_beam_decode_opt_device(NntkRnntDecoder d, const float *d_enc, 
                                          int *d_out_lengths, float *d_scores, float *d_workspace);
 int nntk_rnnt_tdt_beam_decode_opt(NntkRnntDecoder d, const float *enc, int batch, int T, const int *n_frames, int beam_width, int nbest,
                                   int max_labels, const NntkRnntTdtBeamOptions *o, int *labels_out, int *out_lengths, float *scores);
+/* ---- streamed (INTEGRATION.md "RNN-Transducer: token-and-duration beam search", Streaming) ----
+ * nntk_rnnt_tdt_beam_stream_push_device: the search above pushed chunk by chunk for batch independent streams.  d_enc [batch][T][J] holds
+ * the next n_frames[b] frames of row b (0 allowed; NULL = every row T).  After every push, every output that is asked for holds, bit
+ * for bit, what nntk_rnnt_tdt_beam_decode_opt_device with the same options, beam_width and max_labels (the state's) returns on the
+ * frames the row has been pushed since its create or last reset, for any split of them into pushes: labels, lengths and scores, and
+ * with detail frames (counted from the start of the row's stream), durations and log-probabilities.  A row that has had no frames
+ * reports the empty hypothesis, score 0 or ln E(start_state); a push with n_frames[b] == 0 rewrites the row's outputs.
+ *   How.  With N frames seen, a frame t with t + Dmax <= N makes the same moves whatever the row's end will be: min(t + d, n) is t + d.
+ *   Those frames, [c_old, c_new) with c = max(0, N - Dmax + 1), are committed: they run once, on the state's copy of the row's
+ *   workspace block, with the bucket counts carried next to it.  The at most Dmax - 1 frames behind them run with the clamp n = N,
+ *   and the report with them, on a copy of that block in d_workspace; the state is not touched by them, and the next push runs them
+ *   again.  Their encoder frames are held in the state, so a chunk may be freed or overwritten after its push.  ln E and length
+ *   normalisation touch only what is reported.  Frames nobody lands on, and a chunk's frames at or beyond n_frames[b], are never
+ *   used (they may hold NaN; the held frames are bit copies).
+ * The state: nntk_rnnt_tdt_beam_state_create(d, batch, beam_width, max_labels, lm, with_detail); with_detail as the workspace rule: 1
+ * for a stream that is pushed with a detail output or length_norm.  lm (or NULL) must stay open as long as the state and is the lm of
+ * every push.  nntk_rnnt_tdt_beam_state_bytes: per row the row block of the workspace with those flags (nntk_rnnt_tdt_beam_opt_workspace_floats
+ * less its 3 words a row), Dmax + 1 bucket counts and (Dmax - 1) J floats of held frames, each padded to 4 words, and 2 ints on the
+ * host; it does not grow with the stream.  0 where create returns NULL.  _reset(s, rows, n_rows): these rows (NULL, 0: every row)
+ * start new streams with their next push; it costs no device work.  _destroy synchronises and frees.
+ *   d_workspace: nntk_rnnt_tdt_beam_opt_workspace_floats(d, batch, beam_width, max_labels, o) floats, 16-byte aligned.
+ * Checks, all on the host before anything is enqueued (-1 / NULL, nntk_last_error(), nothing written, the state unchanged):
+ * everything nntk_rnnt_tdt_beam_decode_opt_device refuses; a NULL state; a state of another decoder or batch; a state created without
+ * or with an lm, or with another lm, than the call's; a state created without detail in a call with a detail output or length_norm,
+ * and the reverse; a row whose frame count would pass INT_MAX - 16.  The state functions refuse a handle of nntk_rnnt_decoder_create
+ * (NULL, or 0 bytes) with a message that names nntk_rnnt_beam_state_create, as the nntk_rnnt_beam_state_* functions keep refusing a
+ * handle with durations.  The guarantees of the one-shot call hold: no atomics, one launch a push, the kernel's LDS, a row's bits
+ * independent of the other rows, its batch position, the T padding and how many hypotheses share a pass over a matrix.  The
+ * host-pointer form uploads the chunk, runs the device form on a workspace of its own and downloads. */
+typedef struct NntkRnntTdtBeamStateStruct *NntkRnntTdtBeamState;
+NntkRnntTdtBeamState nntk_rnnt_tdt_beam_state_create(NntkRnntDecoder d, int batch, int beam_width, int max_labels, NntkNgramLm lm,
+                                                     int with_detail);
+size_t nntk_rnnt_tdt_beam_state_bytes(NntkRnntDecoder d, int batch, int beam_width, int max_labels, int with_lm, int with_detail);
+int nntk_rnnt_tdt_beam_state_reset(NntkRnntTdtBeamState s, const int *rows, int n_rows);
+void nntk_rnnt_tdt_beam_state_destroy(NntkRnntTdtBeamState s);
+int nntk_rnnt_tdt_beam_stream_push_device(NntkRnntDecoder d, NntkRnntTdtBeamState s, const float *d_enc, int batch, int T,
+                                          const int *n_frames, int nbest, const NntkRnntTdtBeamOptions *o, int *d_labels_out,
+                                          int *d_out_lengths, float *d_scores, float *d_workspace);
+int nntk_rnnt_tdt_beam_stream_push(NntkRnntDecoder d, NntkRnntTdtBeamState s, const float *enc, int batch, int T, const int *n_frames,
+                                   int nbest, const NntkRnntTdtBeamOptions *o, int *labels_out, int *out_lengths, float *scores);
 
 /* ---- RNN-Transducer: beam search (csrc/hip/rnnt_beam.hip; INTEGRATION.md "RNN-Transducer: beam search") ----
  * The model, the weight blocks, the decoder handle and max_symbols_per_frame (S below) are those of greedy decoding; W = beam_width.

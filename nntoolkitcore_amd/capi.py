@@ -560,6 +560,13 @@ SIGNATURES = {
                                                        C.POINTER(NntkRnntTdtBeamOptions), vp, vp, vp, vp]),
     "nntk_rnnt_tdt_beam_decode_opt": (C.c_int, [vp, fp, C.c_int, C.c_int, ip, C.c_int, C.c_int, C.c_int,
                                                 C.POINTER(NntkRnntTdtBeamOptions), ip, ip, fp]),
+    "nntk_rnnt_tdt_beam_state_create": (vp, [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int]),
+    "nntk_rnnt_tdt_beam_state_bytes": (C.c_size_t, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "nntk_rnnt_tdt_beam_state_reset": (C.c_int, [vp, ip, C.c_int]),
+    "nntk_rnnt_tdt_beam_state_destroy": (None, [vp]),
+    "nntk_rnnt_tdt_beam_stream_push_device": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, ip, C.c_int, C.POINTER(NntkRnntTdtBeamOptions),
+                                                        vp, vp, vp, vp]),
+    "nntk_rnnt_tdt_beam_stream_push": (C.c_int, [vp, vp, fp, C.c_int, C.c_int, ip, C.c_int, C.POINTER(NntkRnntTdtBeamOptions), ip, ip, fp]),
     "nntk_rnnt_beam_workspace_floats": (C.c_size_t, [vp, C.c_int, C.c_int, C.c_int]),
     "nntk_rnnt_beam_decode_device": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, ip, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]),
     "nntk_rnnt_beam_decode": (C.c_int, [vp, vp, fp, C.c_int, C.c_int, ip, C.c_int, C.c_int, C.c_int, ip, ip, fp]),

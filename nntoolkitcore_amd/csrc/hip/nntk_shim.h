@@ -425,6 +425,18 @@ size_t nntk_shim_rnnt_tdt_beam_workspace_floats(int batch, int H, int J, int V, 
 int nntk_shim_rnnt_tdt_beam(const nntk_shim_rnnt_dec *m, const nntk_shim_rnnt_tdt_durs *du, const float *d_enc, int batch, int T,
                             const int *h_n_frames, int beam_width, int nbest, int max_labels, const nntk_shim_rnnt_lm *lm,
                             const nntk_shim_rnnt_tdt_beam_detail *dt, int *d_labels, int *d_lengths, float *d_scores, float *d_ws);
+/* The streamed form: one push of a stream whose rows keep d_state, nntk_shim_rnnt_tdt_beam_state_floats words (per row the row block of
+ * the workspace, Dmax + 1 bucket counts and Dmax - 1 held encoder frames of J floats, each padded to 4 words; 0 where the workspace
+ * query is 0).  HOST arrays, checked by the caller and copied in stream order into the workspace's head: h_seen_now [batch] the frames
+ * a row has seen with this push, h_seen those before it (d_enc [batch][T][J] holds the h_seen_now - h_seen new ones), h_first 1 for a
+ * row's first push since create or reset.  The frames below max(0, seen_now - Dmax + 1) run on d_state, the rest and the report on a
+ * copy of the row's block in d_ws, sized by nntk_shim_rnnt_tdt_beam_workspace_floats with the same flags; the same LDS, one launch. */
+size_t nntk_shim_rnnt_tdt_beam_state_floats(int batch, int H, int J, int V, int max_sym, int dmax, int beam_width, int max_labels,
+                                            int with_lm, int with_detail);
+int nntk_shim_rnnt_tdt_beam_stream(const nntk_shim_rnnt_dec *m, const nntk_shim_rnnt_tdt_durs *du, const float *d_enc, int batch, int T,
+                                   const int *h_seen_now, const int *h_seen, const int *h_first, float *d_state, int beam_width, int nbest,
+                                   int max_labels, const nntk_shim_rnnt_lm *lm, const nntk_shim_rnnt_tdt_beam_detail *dt, int *d_labels,
+                                   int *d_lengths, float *d_scores, float *d_ws);
 /* ---- the prediction network's label embedding, for training (rnnt_pred.hip).  rows_select: d_out [rows][width] = d_src[h_idx[r]][:], exact
  *      zeros for h_idx[r] < 0; h_idx HOST memory, checked by the caller, carried in the kernel arguments.  embedding_grad: d_dtable [V][E],
  *      every element written, from the caller's plan (rnnt_pred.c), HOST ints laid out offsets [V + 1] | sorted rows [n_sorted] | heavy

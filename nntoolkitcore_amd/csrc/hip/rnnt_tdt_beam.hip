@@ -65,7 +65,23 @@
 // it is larger, points bfslot and bdur at the candidate; the twin found in bucket[n] comes by the same lines.  The report (also the LM
 // one) takes the W best of bucket[n] and ranks them by score or score / (length + 1), every entry counting the entries ahead of it, on
 // arrays of TbShared that the frames have left free: no LDS is added, so tb_lds_bytes, fits and group hold for every instantiation.
+//
+// Streaming (the STREAM = true instantiations; include/nntoolkitcore_hip.h, "streamed" under the TDT beam search).  A push has seen N
+// frames of its row and does not know the row's end, and a frame t with t + Dmax > N makes clamped moves into bucket[N], whose
+// insertion order interleaves several source frames: carrying the ring alone cannot give the one-shot bits.  So the same frame loop runs
+// twice.  The committed frames [c_old, c_new), c = max(0, N - Dmax + 1), have t + Dmax <= N: min(t + d, n) is t + d for every end
+// n >= N, and what they write is what every longer one-shot call writes.  They run on the CARRIED block of the row (tb_layout's row
+// block in the stream's state, ring positions t mod (Dmax + 1) on the absolute frame) between a restore and a save of sh.nb.  Then
+// the workgroup copies the block into the call's workspace -- everything but logits and lmterm, which a depth fills before it reads
+// them -- re-points its row pointers at the copy, and runs the at most Dmax - 1 tail frames [c_new, N) with the clamp n = N and the
+// report there.  Every index in a block (slot, entry) is relative to it, so the copy is a search of its own; the carried block never
+// sees a clamped move, and the next push runs the tail's frames again, committed or as its own tail.  Those frames' encoder vectors
+// are held in the state, frame t at position t mod (Dmax - 1): a frame seen by an earlier push is read from there, a later one from
+// the chunk, and the tail's new frames are copied in (as bits) between the two phases, when the committed phase has read what they
+// replace.  The first push after create or reset sets up frame -1 and the blank step; the host sends that flag and the frames seen
+// before in the two counter words of the row, which the kernel reads before it writes them.  No LDS is added, no atomics, one launch.
 #include <limits.h>
+#include <stdlib.h>
 #include "rnnt_dec_common.hpp"
 
 #define TB_MAX_W NNTK_RNNT_BEAM_MAX_W
@@ -138,6 +154,8 @@ struct TbArgs {
     TbOptLayout opt;                       // the LM and DETAIL instantiations only, as is what follows (lay.row counts both parts)
     nntk_shim_rnnt_lm lm;
     nntk_shim_rnnt_tdt_beam_detail dt;
+    float *st;                             // the STREAM instantiations only: the rows' carried state, st_row floats a row, each
+    size_t st_row, st_nb, st_held;         // the row block | nb [Dmax + 1] ints | held [Dmax - 1][J] (offsets in floats)
 };
 
 template <int R> struct TbShared {
@@ -178,7 +196,7 @@ __device__ __forceinline__ int tb_duration(const nntk_shim_rnnt_tdt_durs &du, in
     return d;
 }
 
-template <int R, bool LM, bool DETAIL>
+template <int R, bool LM, bool DETAIL, bool STREAM>
 __global__ __launch_bounds__(RD_THREADS) void rnnt_tdt_beam_kernel(const TbArgs a) {
     extern __shared__ __align__(16) unsigned char tb_smem[];
     TbShared<R> &sh = *(TbShared<R> *)tb_smem;
@@ -191,7 +209,8 @@ __global__ __launch_bounds__(RD_THREADS) void rnnt_tdt_beam_kernel(const TbArgs 
     const float *pbias = a.proj ? a.proj + (size_t)H * J : nullptr;
     const float *obias = a.out + (size_t)J * VD;
     const int b = blockIdx.x;
-    float *row = a.ws + a.ws_head + (size_t)b * a.lay.row;
+    float *const ws_row = a.ws + a.ws_head + (size_t)b * a.lay.row;
+    float *row = STREAM ? a.st + (size_t)b * a.st_row : ws_row;              // a stream's committed frames run on the carried block
     double *bscore = (double *)(row + a.lay.bscore);
     float *states = row + a.lay.states, *lg = row + a.lay.logits;
     int *bslot = (int *)(row + a.lay.bslot), *labs = (int *)(row + a.lay.labels), *meta = (int *)(row + a.lay.meta);
@@ -201,7 +220,14 @@ __global__ __launch_bounds__(RD_THREADS) void rnnt_tdt_beam_kernel(const TbArgs 
     float *lp = row + a.opt.lp;
     double *lead = (double *)(row + a.opt.lead);
     int *bfslot = (int *)(row + a.opt.bfslot), *bdur = (int *)(row + a.opt.bdur), *cld = (int *)(row + a.opt.cld);
-    const int n = ((const int *)a.ws)[b];
+    const int n = ((const int *)a.ws)[b];                                    // STREAM: the frames seen with this push
+    int *const stat = (int *)a.ws + (((size_t)a.batch + 3) & ~(size_t)3) + 2 * (size_t)b;
+    // STREAM: the frames seen before (the host put them and the first-push flag where the counters go), what is committed before and
+    // after this push, c = max(0, N - Dmax + 1), and the held encoder frames, frame t at t mod (Dmax - 1)
+    const int n_old = STREAM ? stat[0] : 0, first = STREAM ? stat[1] : 1, HR = RING > 2 ? RING - 2 : 1;
+    const int c_old = n_old - RING + 2 > 0 ? n_old - RING + 2 : 0, c_new = n - RING + 2 > c_old ? n - RING + 2 : c_old;
+    float *const held = STREAM ? a.st + (size_t)b * a.st_row + a.st_held : nullptr;
+    int *const st_nb = STREAM ? (int *)(a.st + (size_t)b * a.st_row + a.st_nb) : nullptr;
     int joined = 0, steps = 0;                                               // lane 0's counters, for the timing tool
 
     // the workgroup's best (score descending, index ascending; INT_MAX: none) -> sh.best_s, sh.best_i
@@ -302,7 +328,8 @@ __global__ __launch_bounds__(RD_THREADS) void rnnt_tdt_beam_kernel(const TbArgs 
     // frame t for the hypotheses i0 .. i0 + cnt - 1 of C, one pass over [J][V + D]: the token logits into the workspace, their max and
     // log-sum-exp, lp_tok[blank] and the duration head's lp_dur [D]
     auto heads_group = [&](int i0, int cnt, int t) {
-        const float *e = a.enc + ((size_t)b * a.T + t) * J;
+        const float *e = STREAM ? (t < n_old ? held + (size_t)(t % HR) * J : a.enc + ((size_t)b * a.T + (t - n_old)) * J)
+                                : a.enc + ((size_t)b * a.T + t) * J;
 #pragma unroll
         for (int r = 0; r < R; ++r) {
             if (r < cnt) {
@@ -421,7 +448,9 @@ __global__ __launch_bounds__(RD_THREADS) void rnnt_tdt_beam_kernel(const TbArgs 
 
     for (int i = tid; i < R * (2 * Hp + Jp); i += RD_THREADS) sh_h[i] = 0.0f;
     const int slot0 = (RING - 1) * a.lay.frame_slots;                        // frame -1's ring position
-    if (tid < RING) sh.nb[tid] = tid == 0;
+    if (tid < RING) sh.nb[tid] = first ? tid == 0 : st_nb[tid];
+    if (STREAM && !first) __syncthreads();                                   // a later push: the carried block is as the last one left it
+    else {
     if (tid == 0) {
         meta[2 * slot0] = 0; meta[2 * slot0 + 1] = 0; bslot[0] = slot0; bscore[0] = 0.0;
         if constexpr (LM) lmq[slot0] = a.lm.start_state;
@@ -430,8 +459,12 @@ __global__ __launch_bounds__(RD_THREADS) void rnnt_tdt_beam_kernel(const TbArgs 
     }
     __syncthreads();
     step_group(0, 1);                                                        // the step on embed[blank] from the zero state
+    }
 
-    for (int t = 0; t < n; ++t) {
+    // STREAM: phase 0 the committed frames [c_old, c_new), where min(t + d, n) is t + d for every later end, on the carried block;
+    // phase 1 the tail [c_new, n) and the report on a copy of it in the workspace, which the next push runs again
+    for (int phase = 0, t0 = STREAM ? c_old : 0, t1 = STREAM ? c_new : n;; ++phase) {
+    for (int t = t0; t < t1; ++t) {
         const int p = t % RING;
         if (sh.nb[p] == 0) continue;                                         // nobody landed here: no barrier, no read of the frame
         const int nA = bucket_best(p, W), fb = p * a.lay.frame_slots;
@@ -592,6 +625,34 @@ __global__ __launch_bounds__(RD_THREADS) void rnnt_tdt_beam_kernel(const TbArgs 
         }
         __syncthreads();
     }
+    if constexpr (STREAM) {
+        if (phase == 1) break;
+        if (tid < RING) st_nb[tid] = sh.nb[tid];
+        if (c_new >= n) break;                                               // no tail: the report reads the carried block, and writes none of it
+        for (int t = c_new > n_old ? c_new : n_old; t < n; ++t) {            // the tail's new frames are held for the next push: bit copies
+            const unsigned *src = (const unsigned *)(a.enc + ((size_t)b * a.T + (t - n_old)) * J);
+            unsigned *dst = (unsigned *)(held + (size_t)(t % HR) * J);
+            for (int j = tid; j < J; j += RD_THREADS) dst[j] = src[j];
+        }
+        // the block without what a depth fills before it reads it (logits, lmterm); every part is a multiple of 4 floats
+        const size_t end0 = a.lay.logits, beg1 = LM ? a.opt.lmq : DETAIL ? a.opt.fr : a.lay.row, end1 = LM ? a.opt.lmterm : a.lay.row;
+        const size_t beg2 = LM && DETAIL ? a.opt.fr : a.lay.row;
+        const float4 *src4 = (const float4 *)row;
+        float4 *dst4 = (float4 *)ws_row;
+        for (size_t i = tid; i < end0 / 4; i += RD_THREADS) dst4[i] = src4[i];
+        for (size_t i = beg1 / 4 + tid; i < end1 / 4; i += RD_THREADS) dst4[i] = src4[i];
+        for (size_t i = beg2 / 4 + tid; i < a.lay.row / 4; i += RD_THREADS) dst4[i] = src4[i];
+        row = ws_row;
+        bscore = (double *)(row + a.lay.bscore); states = row + a.lay.states; lg = row + a.lay.logits;
+        bslot = (int *)(row + a.lay.bslot); labs = (int *)(row + a.lay.labels); meta = (int *)(row + a.lay.meta);
+        lmq = (int *)(row + a.opt.lmq); lmterm = (double *)(row + a.opt.lmterm);
+        fr = (int *)(row + a.opt.fr); du = (int *)(row + a.opt.du); lp = row + a.opt.lp;
+        lead = (double *)(row + a.opt.lead);
+        bfslot = (int *)(row + a.opt.bfslot); bdur = (int *)(row + a.opt.bdur); cld = (int *)(row + a.opt.cld);
+        __syncthreads();
+        t0 = c_new; t1 = n;
+    } else break;
+    }
 
     if constexpr (LM || DETAIL) {
         // the report: the W best of bucket[n], + ln E(q) with a model, the -inf ones dropped, ranked by score or score / (length + 1)
@@ -654,21 +715,29 @@ __global__ __launch_bounds__(RD_THREADS) void rnnt_tdt_beam_kernel(const TbArgs 
         }
     }
     }
-    if (tid == 0) {
-        int *stat = (int *)a.ws + (((size_t)a.batch + 3) & ~(size_t)3) + 2 * (size_t)b;
-        stat[0] = joined; stat[1] = steps;
-    }
+    if (tid == 0) { stat[0] = joined; stat[1] = steps; }
 }
 
 typedef void (*TbKernel)(const TbArgs);
 
-template <int R> static TbKernel tb_kernel(bool lm, bool detail) {
-    static const TbKernel k[2][2] = { { rnnt_tdt_beam_kernel<R, false, false>, rnnt_tdt_beam_kernel<R, false, true> },
-                                      { rnnt_tdt_beam_kernel<R, true, false>, rnnt_tdt_beam_kernel<R, true, true> } };
-    return k[lm][detail];
+template <int R> static TbKernel tb_kernel(bool lm, bool detail, bool stream) {
+    static const TbKernel k[2][2][2] = {
+        { { rnnt_tdt_beam_kernel<R, false, false, false>, rnnt_tdt_beam_kernel<R, false, false, true> },
+          { rnnt_tdt_beam_kernel<R, false, true, false>, rnnt_tdt_beam_kernel<R, false, true, true> } },
+        { { rnnt_tdt_beam_kernel<R, true, false, false>, rnnt_tdt_beam_kernel<R, true, false, true> },
+          { rnnt_tdt_beam_kernel<R, true, true, false>, rnnt_tdt_beam_kernel<R, true, true, true> } } };
+    return k[lm][detail][stream];
 }
 
 static int tb_forced_group = 0;
+
+// a stream's carried state, per row: the row block of tb_layout | nb [Dmax + 1] | held [Dmax - 1][J], each padded to 4 floats
+static size_t tb_state_row(const TbLayout &l, int dmax, int J, size_t *nb = nullptr, size_t *held = nullptr) {
+    const size_t at_nb = l.row, at_held = at_nb + (((size_t)dmax + 1 + 3) & ~(size_t)3);
+    if (nb) *nb = at_nb;
+    if (held) *held = at_held;
+    return at_held + (((size_t)(dmax - 1) * J + 3) & ~(size_t)3);
+}
 
 extern "C" {
 
@@ -688,9 +757,17 @@ int nntk_shim_rnnt_tdt_beam_group(int beam_width, int H, int J, int V, int D) {
 
 void nntk_shim_rnnt_tdt_beam_set_group(int group) { tb_forced_group = group == 1 || group == NNTK_RNNT_DEC_GROUP ? group : 0; }
 
-int nntk_shim_rnnt_tdt_beam(const nntk_shim_rnnt_dec *m, const nntk_shim_rnnt_tdt_durs *du, const float *d_enc, int batch, int T,
-                            const int *h_n_frames, int beam_width, int nbest, int max_labels, const nntk_shim_rnnt_lm *lm,
-                            const nntk_shim_rnnt_tdt_beam_detail *dt, int *d_labels, int *d_lengths, float *d_scores, float *d_ws) {
+size_t nntk_shim_rnnt_tdt_beam_state_floats(int batch, int H, int J, int V, int max_sym, int dmax, int beam_width, int max_labels,
+                                            int with_lm, int with_detail) {
+    if (batch <= 0 || !tb_sizes_ok(max_sym, dmax, beam_width, max_labels)) return 0;
+    return (size_t)batch * tb_state_row(tb_layout(H, J, V, max_sym, dmax, beam_width, max_labels, with_lm != 0, with_detail != 0), dmax, J);
+}
+
+// d_state NULL: one-shot, h_n_frames the rows' lengths.  Else a push: h_n_frames the frames seen with it, h_seen those seen before
+static int tb_run(const nntk_shim_rnnt_dec *m, const nntk_shim_rnnt_tdt_durs *du, const float *d_enc, int batch, int T,
+                  const int *h_n_frames, const int *h_seen, const int *h_first, float *d_state, int beam_width, int nbest, int max_labels,
+                  const nntk_shim_rnnt_lm *lm, const nntk_shim_rnnt_tdt_beam_detail *dt, int *d_labels, int *d_lengths, float *d_scores,
+                  float *d_ws) {
     if (batch <= 0) return 0;
     const int dmax = du->n >= 1 && du->n <= TB_MAX_D ? du->dur[du->n - 1] : 0;
     if (m->E < 1 || m->H < 1 || m->J < 1 || m->V < 2 || m->H > NNTK_RNNT_DEC_MAX_WIDTH || m->J > NNTK_RNNT_DEC_MAX_WIDTH ||
@@ -698,7 +775,17 @@ int nntk_shim_rnnt_tdt_beam(const nntk_shim_rnnt_dec *m, const nntk_shim_rnnt_td
         !nntk_shim_rnnt_tdt_beam_fits(m->H, m->J, m->V, du->n) || beam_width < 1 || beam_width > TB_MAX_W || nbest < 1 || nbest > beam_width ||
         !tb_sizes_ok(m->max_symbols_per_frame, dmax, beam_width, max_labels))
         return nntk_fail_msg("nntk_rnnt_tdt_beam_decode_device: the model is beyond the decoding kernel's limits");
-    if (nntk_shim_upload_ints((int *)d_ws, h_n_frames, batch)) return -1;
+    if (!d_state) {
+        if (nntk_shim_upload_ints((int *)d_ws, h_n_frames, batch)) return -1;
+    } else {                                                                 // the head as the kernel reads it: n [batch] | (seen, first) a row
+        const size_t at = ((size_t)batch + 3) & ~(size_t)3, words = at + 2 * (size_t)batch;
+        int *head = (int *)calloc(words, sizeof(int));
+        if (!head) return nntk_fail_msg("nntk_rnnt_tdt_beam_stream_push_device: out of host memory");
+        for (int b = 0; b < batch; ++b) { head[b] = h_n_frames[b]; head[at + 2 * b] = h_seen[b]; head[at + 2 * b + 1] = h_first[b]; }
+        const int rc = nntk_shim_upload_ints((int *)d_ws, head, (long)words);
+        free(head);
+        if (rc) return -1;
+    }
     TbArgs a;
     a.enc = d_enc; a.table = m->d_table; a.U = m->d_U; a.proj = m->d_proj; a.out = m->d_out;
     a.ws = d_ws;
@@ -707,16 +794,34 @@ int nntk_shim_rnnt_tdt_beam(const nntk_shim_rnnt_dec *m, const nntk_shim_rnnt_td
     a.dt = dt ? *dt : nntk_shim_rnnt_tdt_beam_detail();
     a.lay = tb_layout(m->H, m->J, m->V, m->max_symbols_per_frame, dmax, beam_width, max_labels, lm != nullptr, dt != nullptr, &a.opt);
     a.ws_head = tb_head(batch);
+    a.st = d_state;
+    a.st_row = tb_state_row(a.lay, dmax, m->J, &a.st_nb, &a.st_held);
     a.batch = batch; a.T = T; a.V = m->V; a.blank = m->blank; a.H = m->H; a.J = m->J; a.act = m->activation;
     a.max_sym = m->max_symbols_per_frame; a.W = beam_width; a.nbest = nbest; a.max_labels = max_labels;
     a.du = *du;
     const int R = nntk_shim_rnnt_tdt_beam_group(beam_width, m->H, m->J, m->V, du->n);
     const size_t lds = tb_lds_bytes(R, m->H, m->J, m->V + du->n);
-    const TbKernel k = R == 1 ? tb_kernel<1>(lm != nullptr, dt != nullptr) : tb_kernel<NNTK_RNNT_DEC_GROUP>(lm != nullptr, dt != nullptr);
+    const bool st = d_state != nullptr;
+    const TbKernel k = R == 1 ? tb_kernel<1>(lm != nullptr, dt != nullptr, st) : tb_kernel<NNTK_RNNT_DEC_GROUP>(lm != nullptr, dt != nullptr, st);
     if (lds > 48 * 1024 && nntk_set_max_dynamic_lds((const void *)k, lds)) return -1;
     hipLaunchKernelGGL(k, dim3((unsigned)batch), dim3(RD_THREADS), lds, nntk_stream(), a);
     NNTK_LAUNCH_CHECK("rnnt_tdt_beam_kernel");
     return 0;
+}
+
+int nntk_shim_rnnt_tdt_beam(const nntk_shim_rnnt_dec *m, const nntk_shim_rnnt_tdt_durs *du, const float *d_enc, int batch, int T,
+                            const int *h_n_frames, int beam_width, int nbest, int max_labels, const nntk_shim_rnnt_lm *lm,
+                            const nntk_shim_rnnt_tdt_beam_detail *dt, int *d_labels, int *d_lengths, float *d_scores, float *d_ws) {
+    return tb_run(m, du, d_enc, batch, T, h_n_frames, nullptr, nullptr, nullptr, beam_width, nbest, max_labels, lm, dt, d_labels, d_lengths,
+                  d_scores, d_ws);
+}
+
+int nntk_shim_rnnt_tdt_beam_stream(const nntk_shim_rnnt_dec *m, const nntk_shim_rnnt_tdt_durs *du, const float *d_enc, int batch, int T,
+                                   const int *h_seen_now, const int *h_seen, const int *h_first, float *d_state, int beam_width, int nbest,
+                                   int max_labels, const nntk_shim_rnnt_lm *lm, const nntk_shim_rnnt_tdt_beam_detail *dt, int *d_labels,
+                                   int *d_lengths, float *d_scores, float *d_ws) {
+    return tb_run(m, du, d_enc, batch, T, h_seen_now, h_seen, h_first, d_state, beam_width, nbest, max_labels, lm, dt, d_labels, d_lengths,
+                  d_scores, d_ws);
 }
 
 }  // extern "C"

@@ -3,10 +3,11 @@
  * (csrc/hip/rnnt_decode.hip), its token-and-duration form (csrc/hip/rnnt_tdt_decode.hip: the same handle and state, created with a
  * duration table; each decode call refuses the other kind's handle) and, below them, beam search (csrc/hip/rnnt_beam.hip), each with the per-row state of a stream and the
  * decode call in its device-pointer and host-pointer forms; the beam search's plain, _lm and _opt entries share one body a form and the
- * workspace of nntk_shim_rnnt_beam_workspace_floats; last, the one-shot beam search of a handle with durations
- * (csrc/hip/rnnt_tdt_beam.hip).  Every argument is checked here, before anything is allocated, uploaded or
+ * workspace of nntk_shim_rnnt_beam_workspace_floats; last, the beam search of a handle with durations
+ * (csrc/hip/rnnt_tdt_beam.hip), one-shot and streamed, one body a form.  Every argument is checked here, before anything is allocated, uploaded or
  * enqueued: a refusal needs no device and writes nothing.
  */
+#include <limits.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -625,8 +626,16 @@ int nntk_rnnt_beam_decode_lm(NntkRnntDecoder d, NntkRnntBeamState state, const f
                             out_lengths, scores);
 }
 
-/* ---- token-and-duration beam search (csrc/hip/rnnt_tdt_beam.hip) on a handle of nntk_rnnt_tdt_decoder_create, one-shot; o NULL or
- *      everything off: the plain call ---- */
+/* ---- token-and-duration beam search (csrc/hip/rnnt_tdt_beam.hip) on a handle of nntk_rnnt_tdt_decoder_create; o NULL or everything
+ *      off: the plain call; s NULL: one-shot, else a push of that stream ---- */
+
+struct NntkRnntTdtBeamStateStruct {
+    NntkRnntDecoder dec;
+    int batch, width, max_labels, detail;
+    NntkNgramLm lm;                             /* the model the stream was created with (NULL: none) */
+    float *d_state;                             /* nntk_shim_rnnt_tdt_beam_state_floats words: the rows' carried blocks */
+    int *seen;                                  /* HOST [batch][2]: the frames a row has seen | pushed since create or reset */
+};
 
 static int tdt_beam_opt_detail(const NntkRnntTdtBeamOptions *o) { return o && (o->label_frames || o->label_durations || o->label_logps); }
 
@@ -644,11 +653,26 @@ size_t nntk_rnnt_tdt_beam_workspace_floats(NntkRnntDecoder d, int batch, int bea
 }
 
 /* everything the call can be refused for; device_form 0: the host-pointer form, which owns its workspace */
-static int tdt_beam_check_call(const char *who, NntkRnntDecoder d, const float *enc, int batch, int T, const int *n_frames, int beam_width,
-                               int nbest, int max_labels, const NntkRnntTdtBeamOptions *o, const int *labels_out, const int *out_lengths,
-                               const float *scores, const float *ws, int device_form) {
+static int tdt_beam_check_call(const char *who, NntkRnntDecoder d, NntkRnntTdtBeamState s, int stream, const float *enc, int batch, int T,
+                               const int *n_frames, int beam_width, int nbest, int max_labels, const NntkRnntTdtBeamOptions *o,
+                               const int *labels_out, const int *out_lengths, const float *scores, const float *ws, int device_form) {
     if (!d) return dec_fail(who, "NULL decoder", 0, 0, 0);
     if (!d->du.n) return dec_fail(who, "the decoder has no durations (nntk_rnnt_decoder_create): nntk_rnnt_beam_decode_device serves it", 0, 0, 0);
+    if (stream) {
+        NntkNgramLm lm = o ? o->lm : NULL;
+        if (!s) return dec_fail(who, "NULL state", 0, 0, 0);
+        if (s->dec != d) return dec_fail(who, "the state belongs to another decoder", 0, 0, 0);
+        if (s->batch != batch) return dec_fail(who, "batch %ld differs from the state's %ld", batch, s->batch, 0);
+        if (s->lm != lm)                        /* beam_width and max_labels are the state's: a push takes neither */
+            return dec_fail(who, !s->lm ? "the state was created without a language model" :
+                                 !lm ? "the state was created with a language model" : "the state was created with another language model", 0, 0, 0);
+        if (s->detail != tdt_beam_opt_kernel(o))
+            return dec_fail(who, s->detail ? "the state was created with detail, the call asks for neither detail nor length_norm"
+                                           : "the state was created without detail, the call asks for detail or length_norm", 0, 0, 0);
+        for (int b = 0; b < batch; ++b)
+            if (s->seen[2 * b] > INT_MAX - 16 - (n_frames ? (n_frames[b] > 0 ? n_frames[b] : 0) : T > 0 ? T : 0))
+                return dec_fail(who, "row %ld has seen %ld frames: this push would pass INT_MAX - 16", b, s->seen[2 * b], 0);
+    }
     if (o && o->length_norm != 0 && o->length_norm != 1) return dec_fail(who, "length_norm %ld is neither 0 nor 1", o->length_norm, 0, 0);
     if (beam_check_lm(who, d, o ? o->lm : NULL)) return -1;
     if (batch < 0 || T < 0) return dec_fail(who, "batch %ld, T %ld: neither may be negative", batch, T, 0);
@@ -683,12 +707,12 @@ static int tdt_beam_check_call(const char *who, NntkRnntDecoder d, const float *
     return dec_check_overlaps(who, 6, 8, p, n, name);
 }
 
-static int tdt_beam_device(const char *who, NntkRnntDecoder d, const float *d_enc, int batch, int T, const int *n_frames, int beam_width,
-                           int nbest, int max_labels, const NntkRnntTdtBeamOptions *o, int *d_labels_out, int *d_out_lengths,
-                           float *d_scores, float *d_workspace) {
+static int tdt_beam_device(const char *who, NntkRnntDecoder d, NntkRnntTdtBeamState s, int stream, const float *d_enc, int batch, int T,
+                           const int *n_frames, int beam_width, int nbest, int max_labels, const NntkRnntTdtBeamOptions *o, int *d_labels_out,
+                           int *d_out_lengths, float *d_scores, float *d_workspace) {
     nntk_shim_clear_error();
-    if (tdt_beam_check_call(who, d, d_enc, batch, T, n_frames, beam_width, nbest, max_labels, o, d_labels_out, d_out_lengths, d_scores,
-                            d_workspace, 1)) return -1;
+    if (tdt_beam_check_call(who, d, s, stream, d_enc, batch, T, n_frames, beam_width, nbest, max_labels, o, d_labels_out, d_out_lengths,
+                            d_scores, d_workspace, 1)) return -1;
     if (batch == 0) return 0;
     NntkNgramLm lm = o ? o->lm : NULL;
     nntk_shim_rnnt_lm tab;
@@ -698,30 +722,43 @@ static int tdt_beam_device(const char *who, NntkRnntDecoder d, const float *d_en
     const nntk_shim_rnnt_dec m = dec_model(d);
     const nntk_shim_rnnt_tdt_beam_detail dt = { o ? o->label_frames : NULL, o ? o->label_durations : NULL, o ? o->label_logps : NULL,
                                                 o ? o->length_norm : 0 };
-    int rc = nntk_shim_rnnt_tdt_beam(&m, &d->du, d_enc, batch, T, len, beam_width, nbest, max_labels, lm ? &tab : NULL,
+    int rc;
+    if (!stream) {
+        rc = nntk_shim_rnnt_tdt_beam(&m, &d->du, d_enc, batch, T, len, beam_width, nbest, max_labels, lm ? &tab : NULL,
                                      tdt_beam_opt_kernel(o) ? &dt : NULL, d_labels_out, d_out_lengths, d_scores, d_workspace);
+    } else {                                    /* the kernel takes what the host can derive: seen with this push | before it | first push */
+        int *was = (int *)malloc(2 * (size_t)batch * sizeof(int));
+        if (!was) { free(len); return dec_fail(who, "out of host memory", 0, 0, 0); }
+        for (int b = 0; b < batch; ++b) { was[b] = s->seen[2 * b]; was[batch + b] = !s->seen[2 * b + 1]; len[b] += was[b]; }
+        rc = nntk_shim_rnnt_tdt_beam_stream(&m, &d->du, d_enc, batch, T, len, was, was + batch, s->d_state, beam_width, nbest, max_labels,
+                                            lm ? &tab : NULL, tdt_beam_opt_kernel(o) ? &dt : NULL, d_labels_out, d_out_lengths, d_scores,
+                                            d_workspace);
+        for (int b = 0; !rc && b < batch; ++b) { s->seen[2 * b] = len[b]; s->seen[2 * b + 1] = 1; }
+        free(was);
+    }
     free(len);
     return rc;
 }
 
 int nntk_rnnt_tdt_beam_decode_device(NntkRnntDecoder d, const float *d_enc, int batch, int T, const int *n_frames, int beam_width, int nbest,
                                      int max_labels, int *d_labels_out, int *d_out_lengths, float *d_scores, float *d_workspace) {
-    return tdt_beam_device("nntk_rnnt_tdt_beam_decode_device", d, d_enc, batch, T, n_frames, beam_width, nbest, max_labels, NULL, d_labels_out,
+    return tdt_beam_device("nntk_rnnt_tdt_beam_decode_device", d, NULL, 0, d_enc, batch, T, n_frames, beam_width, nbest, max_labels, NULL, d_labels_out,
                            d_out_lengths, d_scores, d_workspace);
 }
 
 int nntk_rnnt_tdt_beam_decode_opt_device(NntkRnntDecoder d, const float *d_enc, int batch, int T, const int *n_frames, int beam_width,
                                          int nbest, int max_labels, const NntkRnntTdtBeamOptions *o, int *d_labels_out,
                                          int *d_out_lengths, float *d_scores, float *d_workspace) {
-    return tdt_beam_device("nntk_rnnt_tdt_beam_decode_opt_device", d, d_enc, batch, T, n_frames, beam_width, nbest, max_labels, o,
+    return tdt_beam_device("nntk_rnnt_tdt_beam_decode_opt_device", d, NULL, 0, d_enc, batch, T, n_frames, beam_width, nbest, max_labels, o,
                            d_labels_out, d_out_lengths, d_scores, d_workspace);
 }
 
-static int tdt_beam_host(const char *who, NntkRnntDecoder d, const float *enc, int batch, int T, const int *n_frames, int beam_width,
-                         int nbest, int max_labels, const NntkRnntTdtBeamOptions *o, int *labels_out, int *out_lengths, float *scores) {
+static int tdt_beam_host(const char *who, NntkRnntDecoder d, NntkRnntTdtBeamState s, int stream, const float *enc, int batch, int T,
+                         const int *n_frames, int beam_width, int nbest, int max_labels, const NntkRnntTdtBeamOptions *o, int *labels_out,
+                         int *out_lengths, float *scores) {
     nntk_shim_clear_error();
-    if (tdt_beam_check_call(who, d, enc, batch, T, n_frames, beam_width, nbest, max_labels, o, labels_out, out_lengths, scores, NULL, 0))
-        return -1;
+    if (tdt_beam_check_call(who, d, s, stream, enc, batch, T, n_frames, beam_width, nbest, max_labels, o, labels_out, out_lengths, scores,
+                            NULL, 0)) return -1;
     if (batch == 0) return 0;
     const size_t ne = (size_t)batch * T * d->cfg.J, nh = (size_t)batch * nbest, nl = nh * max_labels;
     const int detail = tdt_beam_opt_detail(o);
@@ -739,7 +776,8 @@ static int tdt_beam_host(const char *who, NntkRnntDecoder d, const float *enc, i
         dev.label_logps = o->label_logps ? d_sc + nh + 2 * nl : NULL;
     }
     if (ne && nntk_shim_upload(d_enc, enc, ne * sizeof(float))) return -1;
-    if (tdt_beam_device(who, d, d_enc, batch, T, n_frames, beam_width, nbest, max_labels, o ? &dev : NULL, d_lab, d_len, d_sc, d_ws)) return -1;
+    if (tdt_beam_device(who, d, s, stream, d_enc, batch, T, n_frames, beam_width, nbest, max_labels, o ? &dev : NULL, d_lab, d_len, d_sc, d_ws))
+        return -1;
     if (nntk_shim_download(labels_out, d_lab, nl * sizeof(int))) return -1;
     if (nntk_shim_download(out_lengths, d_len, nh * sizeof(int))) return -1;
     if (dev.label_frames && nntk_shim_download(o->label_frames, dev.label_frames, nl * sizeof(int))) return -1;
@@ -750,12 +788,96 @@ static int tdt_beam_host(const char *who, NntkRnntDecoder d, const float *enc, i
 
 int nntk_rnnt_tdt_beam_decode(NntkRnntDecoder d, const float *enc, int batch, int T, const int *n_frames, int beam_width, int nbest,
                               int max_labels, int *labels_out, int *out_lengths, float *scores) {
-    return tdt_beam_host("nntk_rnnt_tdt_beam_decode", d, enc, batch, T, n_frames, beam_width, nbest, max_labels, NULL, labels_out,
+    return tdt_beam_host("nntk_rnnt_tdt_beam_decode", d, NULL, 0, enc, batch, T, n_frames, beam_width, nbest, max_labels, NULL, labels_out,
                          out_lengths, scores);
 }
 
 int nntk_rnnt_tdt_beam_decode_opt(NntkRnntDecoder d, const float *enc, int batch, int T, const int *n_frames, int beam_width, int nbest,
                                   int max_labels, const NntkRnntTdtBeamOptions *o, int *labels_out, int *out_lengths, float *scores) {
-    return tdt_beam_host("nntk_rnnt_tdt_beam_decode_opt", d, enc, batch, T, n_frames, beam_width, nbest, max_labels, o, labels_out,
+    return tdt_beam_host("nntk_rnnt_tdt_beam_decode_opt", d, NULL, 0, enc, batch, T, n_frames, beam_width, nbest, max_labels, o, labels_out,
                          out_lengths, scores);
+}
+
+/* ---- the streamed form: the state of batch rows, and a push ---- */
+
+static const char tdt_state_kind[] = "the decoder has no durations (nntk_rnnt_decoder_create): nntk_rnnt_beam_state_create serves it";
+
+static size_t tdt_beam_state_floats(NntkRnntDecoder d, int batch, int beam_width, int max_labels, int with_lm, int with_detail) {
+    if (!d || !d->du.n || batch <= 0 || beam_width < 1 || beam_width > NNTK_RNNT_BEAM_MAX_W || max_labels < 1) return 0;
+    return nntk_shim_rnnt_tdt_beam_state_floats(batch, d->cfg.H, d->cfg.J, d->cfg.V, d->cfg.max_symbols_per_frame, d->du.dur[d->du.n - 1],
+                                                beam_width, max_labels, with_lm != 0, with_detail != 0);
+}
+
+size_t nntk_rnnt_tdt_beam_state_bytes(NntkRnntDecoder d, int batch, int beam_width, int max_labels, int with_lm, int with_detail) {
+    const size_t floats = tdt_beam_state_floats(d, batch, beam_width, max_labels, with_lm, with_detail);
+    return floats ? floats * sizeof(float) + 2 * (size_t)batch * sizeof(int) : 0;
+}
+
+NntkRnntTdtBeamState nntk_rnnt_tdt_beam_state_create(NntkRnntDecoder d, int batch, int beam_width, int max_labels, NntkNgramLm lm,
+                                                     int with_detail) {
+    static const char who[] = "nntk_rnnt_tdt_beam_state_create";
+    nntk_shim_clear_error();
+    if (!d) { dec_fail(who, "NULL decoder", 0, 0, 0); return NULL; }
+    if (!d->du.n) { dec_fail(who, tdt_state_kind, 0, 0, 0); return NULL; }
+    if (beam_width < 1 || beam_width > NNTK_RNNT_BEAM_MAX_W) {
+        dec_fail(who, "beam_width %ld is outside [1, %ld]", beam_width, NNTK_RNNT_BEAM_MAX_W, 0);
+        return NULL;
+    }
+    if (max_labels < 1) { dec_fail(who, "max_labels %ld < 1", max_labels, 0, 0); return NULL; }
+    if (batch < 1) { dec_fail(who, "batch %ld < 1", batch, 0, 0); return NULL; }
+    if (beam_check_lm(who, d, lm)) return NULL;
+    const size_t floats = tdt_beam_state_floats(d, batch, beam_width, max_labels, lm != NULL, with_detail);
+    if (!floats) {
+        dec_fail(who, "max_symbols_per_frame %ld, max_labels %ld and the largest duration %ld ask for more than 2^29 slots",
+                 d->cfg.max_symbols_per_frame, max_labels, d->du.dur[d->du.n - 1]);
+        return NULL;
+    }
+    NntkRnntTdtBeamState s = (NntkRnntTdtBeamState)calloc(1, sizeof *s);
+    if (!s) { dec_fail(who, "out of host memory", 0, 0, 0); return NULL; }
+    s->dec = d; s->batch = batch; s->width = beam_width; s->max_labels = max_labels; s->lm = lm; s->detail = with_detail != 0;
+    s->seen = (int *)calloc(2 * (size_t)batch, sizeof(int));
+    if (!s->seen) { dec_fail(who, "out of host memory", 0, 0, 0); free(s); return NULL; }
+    s->d_state = (float *)nntk_shim_malloc(floats * sizeof(float));
+    if (!s->d_state || nntk_shim_memset(s->d_state, 0, floats * sizeof(float))) {
+        nntk_rnnt_tdt_beam_state_destroy(s);
+        return NULL;
+    }
+    return s;
+}
+
+/* a row's first push sets up its block anew, so a reset is the host's two words: no device work, in stream order by construction */
+int nntk_rnnt_tdt_beam_state_reset(NntkRnntTdtBeamState s, const int *rows, int n_rows) {
+    static const char who[] = "nntk_rnnt_tdt_beam_state_reset";
+    nntk_shim_clear_error();
+    if (!s) return dec_fail(who, "NULL state", 0, 0, 0);
+    if (n_rows < 0 || n_rows > s->batch) return dec_fail(who, "n_rows %ld is outside [0, %ld]", n_rows, s->batch, 0);
+    if (!rows && n_rows > 0) return dec_fail(who, "rows is NULL with n_rows %ld", n_rows, 0, 0);
+    for (int i = 0; rows && i < n_rows; ++i)
+        if (rows[i] < 0 || rows[i] >= s->batch) return dec_fail(who, "rows[%ld] = %ld is outside [0, %ld)", i, rows[i], s->batch);
+    for (int i = 0; i < (rows ? n_rows : s->batch); ++i) {
+        const int b = rows ? rows[i] : i;
+        s->seen[2 * b] = s->seen[2 * b + 1] = 0;
+    }
+    return 0;
+}
+
+void nntk_rnnt_tdt_beam_state_destroy(NntkRnntTdtBeamState s) {
+    if (!s) return;
+    if (s->d_state) nntk_shim_synchronize();
+    nntk_shim_free(s->d_state);
+    free(s->seen);
+    free(s);
+}
+
+int nntk_rnnt_tdt_beam_stream_push_device(NntkRnntDecoder d, NntkRnntTdtBeamState s, const float *d_enc, int batch, int T,
+                                          const int *n_frames, int nbest, const NntkRnntTdtBeamOptions *o, int *d_labels_out,
+                                          int *d_out_lengths, float *d_scores, float *d_workspace) {
+    return tdt_beam_device("nntk_rnnt_tdt_beam_stream_push_device", d, s, 1, d_enc, batch, T, n_frames, s ? s->width : 1, nbest,
+                           s ? s->max_labels : 1, o, d_labels_out, d_out_lengths, d_scores, d_workspace);
+}
+
+int nntk_rnnt_tdt_beam_stream_push(NntkRnntDecoder d, NntkRnntTdtBeamState s, const float *enc, int batch, int T, const int *n_frames,
+                                   int nbest, const NntkRnntTdtBeamOptions *o, int *labels_out, int *out_lengths, float *scores) {
+    return tdt_beam_host("nntk_rnnt_tdt_beam_stream_push", d, s, 1, enc, batch, T, n_frames, s ? s->width : 1, nbest, s ? s->max_labels : 1, o,
+                         labels_out, out_lengths, scores);
 }

@@ -1773,6 +1773,61 @@ class RnntBeamStream:
             pass
 
 
+class RnntTdtBeamStream:
+    """``nntk_rnnt_tdt_beam_state_*``: token-and-duration beam search pushed chunk by chunk for ``batch`` independent streams, on a
+    decoder with durations.  After every push row b holds what ``decoder.tdt_beam_decode`` with the same options gives on the row's
+    frames since its last reset, bit for bit (INTEGRATION.md "RNN-Transducer: token-and-duration beam search", Streaming).  The stream
+    owns the workspace and the output buffers of an nbest and returns the outputs from every push.  lm: an NgramLm fused into the
+    search; it must stay open as long as the stream.  detail: every push returns six tensors, the frames counted from the start of
+    each row's stream.  length_norm: as in ``tdt_beam_decode``."""
+
+    def __init__(self, decoder, batch, beam_width, max_labels, lm=None, detail=False, length_norm=False):
+        self.dec, self.B, self.W, self.max_labels = decoder, int(batch), int(beam_width), int(max_labels)
+        self.lm, self.detail, self.length_norm = lm, bool(detail), bool(length_norm)
+        self.outs, self.ws = {}, None
+        self.h = capi.load().nntk_rnnt_tdt_beam_state_create(decoder.h, self.B, self.W, self.max_labels, lm.h if lm is not None else None,
+                                                             int(self.detail or self.length_norm))
+        if not self.h:
+            raise capi.NNTKError("nntk_rnnt_tdt_beam_state_create: " + capi.last_error())
+
+    def push(self, enc, n_frames=None, nbest=1):
+        """enc [batch, T, J] device tensor, n_frames host ints per row (0 allowed; None: T) -> (labels, lengths, scores), with detail
+        (labels, lengths, scores, label_frames, label_durations, label_logps), each [batch, nbest, ...]"""
+        import torch
+        B, T, J = enc.shape
+        assert B == self.B and J == self.dec.J, "enc: [batch, T, J]"
+        L, nbest = capi.load(), int(nbest)
+        if nbest not in self.outs:
+            outs = self.dec._beam_outputs(enc.device, B, max(nbest, 1), self.max_labels)
+            if self.detail:
+                outs = outs + tuple(torch.empty(outs[0].shape, dtype=t, device=enc.device) for t in (torch.int32, torch.int32, torch.float32))
+            self.outs[nbest] = outs
+        outs = self.outs[nbest]
+        o = capi.NntkRnntTdtBeamOptions(self.lm.h if self.lm is not None else None, int(self.length_norm), *(t.data_ptr() for t in outs[3:]))
+        if self.ws is None:
+            need = L.nntk_rnnt_tdt_beam_opt_workspace_floats(self.dec.h, B, self.W, self.max_labels, C.byref(o))
+            self.ws = torch.empty(max(int(need), 4), dtype=torch.float32, device=enc.device)
+        check(L.nntk_rnnt_tdt_beam_stream_push_device(self.dec.h, self.h, _dp(enc), B, T, _n_frames_ptr(n_frames, B), nbest, C.byref(o),
+                                                      _ipv(outs[0]), _ipv(outs[1]), _dp(outs[2]), _dp(self.ws)),
+              "nntk_rnnt_tdt_beam_stream_push_device")
+        return outs
+
+    def reset(self, rows=None):
+        """these rows (None: every row) start new streams"""
+        _rnnt_state_reset("nntk_rnnt_tdt_beam_state_reset", self.h, rows)
+
+    def close(self):
+        if self.h:
+            capi.load().nntk_rnnt_tdt_beam_state_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def _rnnt_host_decoder(embed, lstm_block, pred_proj, out, enc, max_labels, blank, joint_activation, max_symbols_per_frame, durations=None):
     """the preamble of the numpy decode calls: the weights uploaded into a decoder of their own -> (decoder, enc as float32, B, T,
     max_labels with its default)"""
