@@ -1844,6 +1844,49 @@ int nntk_edit_distance(const int *hyp, const int *hyp_lengths, int batch, int n_
 int nntk_mwer_device(const float *d_logp, const int *d_err, int err_stride, int batch, int n_hyp, float *d_risk_rows, float *d_dlogp);
 int nntk_row_scale_device(const float *d_x, const float *d_scale, long rows, long row_floats, float *d_out);
 
+/* ---- Multi-head self-attention, with the masks of a streaming encoder (csrc/hip/attention.hip; INTEGRATION.md "Self-attention") ----
+ * The attention core for inference, everything f32: for every row b, head h and query frame i
+ *     out[b][i][h] = softmax_j(scale q[b][i][h] . k[b][j][h]) v[b][j][h]    over the keys j that are valid and visible to the query.
+ * The projections around it are TimeDistributedDense's.  One launch (per 128 rows); the scores never exist in memory.
+ *
+ * Layout: frame-major, heads as contiguous d_head slices of a frame, [batch][T][heads d_head], what TimeDistributedDenseApplyDevice
+ * writes.  d_q [batch][Tq], d_k / d_v [batch][Tk], each with a frame stride (>= heads d_head) and a batch stride (>= 0) in floats, so a
+ * fused [B][T][3 heads d_head] projection output or a window into a larger K/V buffer is passed by pointer arithmetic.  d_out is dense
+ * [batch][Tq][heads d_head]; d_lse [batch][heads][Tq] (or NULL) gets max + ln(sum) of each query's scaled scores.
+ *
+ * Positions: key index j has absolute stream position pos0 + j; query i sits at key index p = q_offset + i (q_offset + Tq <= Tk).
+ * kv_lengths [batch] (HOST memory; NULL: every row Tk) is the number of valid keys of a row.  A query with p >= kv_lengths[b] is
+ * invalid: zeros in d_out, -inf in d_lse, its Q row never read.
+ * Visibility: with g(x) = (pos0 + x) / chunk, key j is visible to query p iff g(p) - left <= g(j) <= g(p) + right; left / right = -1
+ * mean unlimited.  Full attention: chunk 1, left -1, right -1.  Causal: 1, -1, 0.  Sliding window: 1, L, R.  Chunked with limited
+ * left context (cache-aware streaming encoders): C, Lc, 0.  A valid query always sees itself.
+ *
+ * Limits: d_head in [1, 128], heads in [1, 64], Tq and Tk in [1, 32768], any value inside.  Refused before anything is enqueued (-1,
+ * nntk_last_error(), nothing written): a NULL tensor (d_lse may be NULL), a limit outside its range, batch < 0, q_offset < 0 or
+ * q_offset + Tq > Tk, chunk < 1, left or right below -1, pos0 < 0 or pos0 + Tk > 2^30, a kv_lengths[b] outside [0, Tk], a frame stride
+ * below heads d_head, a negative batch stride, a tensor that is not 4-byte aligned, a non-finite scale, d_out or d_lse overlapping an
+ * input or each other.
+ *
+ * The guarantee: the d_out and d_lse values of the query at absolute position pos0 + q_offset + i depend only on its Q row, on scale and
+ * d_head, and on the absolute position, the K row and the V row of its visible valid keys.  They do not depend on Tq, Tk, q_offset or
+ * pos0 individually, on the strides, on the row's place in the batch, on the other rows or heads, or on what the invisible keys hold.
+ * So pushing a stream through a sliding K/V window, split into pushes in any way, gives the one-shot call's values
+ * (np.array_equal).  What makes it so: each score is a dot product of its own; key blocks are aligned on absolute positions and their
+ * size depends on nothing but the kernel's d_head class (<= 32, <= 64, <= 128); masked scores are removed by selection, contribute
+ * exact zeros and never enter the max; a block in which a query sees nothing leaves its state as it is.  No atomics: every call
+ * returns the same bits.  Key rows that no query of the call sees, or beyond kv_lengths[b], are never read, whatever they hold, NaN
+ * included.  One limit: the K row of a key that the query does not see may hold anything, but a V row holding inf or NaN reaches every
+ * query of the 32 queries that share a wavefront with one that does see it (0 x inf in the matrix product).
+ *
+ * nntk_attention is the host-pointer form: q, k, v, out, lse in host memory (the strided spans are uploaded as they are). */
+int nntk_attention_device(const float *d_q, const float *d_k, const float *d_v, int batch, int heads, int d_head, int Tq, int Tk,
+                          long q_frame_stride, long q_batch_stride, long k_frame_stride, long k_batch_stride, long v_frame_stride,
+                          long v_batch_stride, const int *kv_lengths, int q_offset, int pos0, int chunk, int left, int right, float scale,
+                          float *d_out, float *d_lse);
+int nntk_attention(const float *q, const float *k, const float *v, int batch, int heads, int d_head, int Tq, int Tk, long q_frame_stride,
+                   long q_batch_stride, long k_frame_stride, long k_batch_stride, long v_frame_stride, long v_batch_stride,
+                   const int *kv_lengths, int q_offset, int pos0, int chunk, int left, int right, float scale, float *out, float *lse);
+
 #ifdef __cplusplus
 }
 #endif

@@ -493,6 +493,11 @@ SIGNATURES = {
     "nntk_edit_distance": (C.c_int, [ip, ip, C.c_int, C.c_int, C.c_int, ip, ip, C.c_int, C.c_int, ip, ip]),
     "nntk_mwer_device": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp]),
     "nntk_row_scale_device": (C.c_int, [vp, vp, C.c_long, C.c_long, vp]),
+    # multi-head self-attention with streaming masks (INTEGRATION.md "Self-attention")
+    "nntk_attention_device": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int] + [C.c_long] * 6 +
+                              [ip, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, vp, vp]),
+    "nntk_attention": (C.c_int, [fp, fp, fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int] + [C.c_long] * 6 +
+                       [ip, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, fp, fp]),
     # RNN-Transducer: loss, gradient with respect to the scores, the joiner (INTEGRATION.md "RNN-Transducer: loss and joiner")
     "nntk_rnnt_workspace_floats": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "nntk_rnnt_loss_device": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, ip, ip, ip, C.c_int, C.c_int, vp, vp, vp]),

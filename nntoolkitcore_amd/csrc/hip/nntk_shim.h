@@ -215,6 +215,17 @@ int nntk_shim_edit_distance(const int *d_hyp, const int *d_hyp_len, int B, int n
 /* d_err read at d_err[(b * n_hyp + k) * err_stride]; d_risk_rows [B] / d_dlogp [B][n_hyp], either may be NULL */
 int nntk_shim_mwer(const float *d_logp, const int *d_err, int err_stride, int B, int n_hyp, float *d_risk_rows, float *d_dlogp);
 int nntk_shim_row_scale(const float *d_x, const float *d_scale, long rows, long row_floats, float *d_out);      /* d_out may be d_x */
+/* ---- multi-head self-attention (attention.hip): q / k / v frame-major with heads as contiguous d_head slices, strides in floats;
+ *      h_kv_lengths [batch] HOST memory or NULL (every row Tk), already checked by the caller (attention.c), passed in the launch's
+ *      arguments; d_out [batch][Tq][heads d_head]; d_lse [batch][heads][Tq] or NULL.  One launch per 128 rows. ---- */
+#define NNTK_ATTENTION_MAX_D_HEAD 128           /* the Q strip and the O tile of a wavefront live in registers */
+#define NNTK_ATTENTION_MAX_HEADS 64
+#define NNTK_ATTENTION_MAX_FRAMES 32768
+#define NNTK_ATTENTION_MAX_POSITION (1 << 30)   /* pos0 + Tk: block and chunk arithmetic on positions stays inside an int */
+int nntk_shim_attention(const float *d_q, const float *d_k, const float *d_v, int batch, int heads, int d_head, int Tq, int Tk,
+                        long q_frame_stride, long q_batch_stride, long k_frame_stride, long k_batch_stride, long v_frame_stride,
+                        long v_batch_stride, const int *h_kv_lengths, int q_offset, int pos0, int chunk, int left, int right, float scale,
+                        float *d_out, float *d_lse);
 /* the transducer kernels' limits, stated here once for the host's checks (rnnt.c) and the launcher */
 #define NNTK_RNNT_MAX_LABELS 4000               /* max_label_len: two diagonals of max_label_len + 1 cells, 16 bytes each, live in LDS */
 #define NNTK_RNNT_MAX_DIAGONALS 65536           /* T + max_label_len: the exponents of that many emissions (each >= -4000) sum inside 2^28 */

@@ -1047,6 +1047,53 @@ def row_scale_device(x, scale, out=None):
     return out
 
 
+def _attention_args(q, k, v, heads, kv_lengths, scale):
+    """shapes, strides (in floats) and the host key counts of an attention call; q / k / v: [B, T, heads * d_head], unit stride in
+    the last dimension, anything in the other two"""
+    assert q.ndim == 3 and k.ndim == 3 and v.ndim == 3 and k.shape == v.shape and k.shape[0] == q.shape[0] and k.shape[2] == q.shape[2], \
+        "q [B, Tq, heads * d_head], k and v [B, Tk, heads * d_head]"
+    B, Tq, HD = q.shape
+    assert heads >= 1 and HD % heads == 0, "the last dimension is heads * d_head"
+    kl = None if kv_lengths is None else _host_ints(kv_lengths, B, "kv_lengths")
+    return (B, heads, HD // heads, Tq, k.shape[1]), kl, (HD // heads) ** -0.5 if scale is None else scale
+
+
+def attention_device(q, k, v, heads, kv_lengths=None, q_offset=0, pos0=0, chunk=1, left=-1, right=-1, scale=None, out=None, lse=None):
+    """``nntk_attention_device``: q [B, Tq, heads * d_head], k / v [B, Tk, heads * d_head] float32 device tensors, frame-major with the
+    heads as contiguous slices; they may be strided views of one fused projection output or of a K/V buffer (unit stride in the last
+    dimension).  kv_lengths: HOST ints, the valid keys of each row.  Key j has stream position pos0 + j, query i sits at key
+    q_offset + i; key j is visible to query p iff g(p) - left <= g(j) <= g(p) + right, g(x) = (pos0 + x) // chunk, -1 = unlimited.
+    Returns (out [B, Tq, heads * d_head], lse [B, heads, Tq])."""
+    import torch
+    dims, kl, scale = _attention_args(q, k, v, heads, kv_lengths, scale)
+    B, _, _, Tq, _ = dims
+    strides = []
+    for t in (q, k, v):
+        assert t.is_cuda and t.dtype == torch.float32 and (t.stride(2) == 1 or t.shape[2] == 1), "float32 device tensors, unit stride in the last dimension"
+        strides += [t.stride(1) if t.shape[1] > 1 else max(t.stride(1), t.shape[2]), t.stride(0)]      # a one-frame view: torch's stride is arbitrary
+    if out is None:
+        out = torch.empty((B, Tq, q.shape[2]), dtype=torch.float32, device=q.device)
+    if lse is None:
+        lse = torch.empty((B, heads, Tq), dtype=torch.float32, device=q.device)
+    check(capi.load().nntk_attention_device(C.c_void_p(q.data_ptr()), C.c_void_p(k.data_ptr()), C.c_void_p(v.data_ptr()), *dims, *strides,
+                                            kl.ctypes.data_as(capi.ip) if kl is not None else None, q_offset, pos0, chunk, left, right,
+                                            C.c_float(scale), _dp(out), _dp(lse)), "nntk_attention_device")
+    return out, lse
+
+
+def attention(q, k, v, heads, kv_lengths=None, q_offset=0, pos0=0, chunk=1, left=-1, right=-1, scale=None):
+    """The host-memory form (``nntk_attention``): q, k, v numpy arrays [B, T, heads * d_head]; returns (out, lse)."""
+    q, k, v = _f32(q), _f32(k), _f32(v)
+    dims, kl, scale = _attention_args(q, k, v, heads, kv_lengths, scale)
+    B, _, _, Tq, Tk = dims
+    HD = q.shape[2]
+    out, lse = np.empty((B, Tq, HD), np.float32), np.empty((B, heads, Tq), np.float32)
+    check(capi.load().nntk_attention(_p(q), _p(k), _p(v), *dims, HD, Tq * HD, HD, Tk * HD, HD, Tk * HD,
+                                     kl.ctypes.data_as(capi.ip) if kl is not None else None, q_offset, pos0, chunk, left, right,
+                                     C.c_float(scale), _p(out), _p(lse)), "nntk_attention")
+    return out, lse
+
+
 RNNT_ACTIVATIONS = {ACT_IDENTITY: 0, ACT_TANH: 1, ACT_RELU: 2}
 
 
