@@ -1887,6 +1887,47 @@ int nntk_attention(const float *q, const float *k, const float *v, int batch, in
                    long q_batch_stride, long k_frame_stride, long k_batch_stride, long v_frame_stride, long v_batch_stride,
                    const int *kv_lengths, int q_offset, int pos0, int chunk, int left, int right, float scale, float *out, float *lse);
 
+/* ---- Training self-attention: the backward of the attention core (csrc/hip/attention_bwd.hip; INTEGRATION.md "Self-attention") ----
+ * The gradient of out = softmax_j(scale q . k) v with respect to q, k and v, everything f32, for the same layout, visibility rule
+ * (kv_lengths, q_offset, pos0, chunk, left, right) and limits as nntk_attention_device.  With i over the valid queries and j over the
+ * keys valid and visible to i:
+ *     P_ij = exp(scale q_i . k_j - lse_i)      delta_i = dout_i . out_i      dS_ij = P_ij (dout_i . v_j - delta_i)
+ *     dq_i = scale sum_j dS_ij k_j             dk_j = scale sum_i dS_ij q_i  dv_j = sum_i P_ij dout_i
+ * The probabilities are recomputed from the forward call's lse; no [Tq][Tk] array exists in memory.  lse is a by-product of the
+ * forward call: no gradient flows into it, and the call takes no dlse.
+ *
+ * Layout: d_q, d_k, d_v and their strides as in the forward call.  d_out and d_lse are what the forward call wrote (dense
+ * [batch][Tq][heads d_head] and [batch][heads][Tq]); d_dout is dense like d_out.  d_dq is [batch][Tq] rows of heads d_head floats with
+ * the frame stride grad_frame_stride (>= heads d_head) and the batch stride Tq grad_frame_stride; d_dk and d_dv likewise with Tk.  With
+ * Tq == Tk and grad_frame_stride = 3 heads d_head the three pointers address one fused [B][T][3 heads d_head] gradient buffer, which
+ * TimeDistributedDense's backward takes as it is.  The floats between the slices are not touched.  d_workspace:
+ * nntk_attention_backward_workspace_floats(batch, heads, Tq) = batch heads Tq floats (0 on a bad argument); it carries one float per
+ * query from the first launch to the second: 1 / sum_j exp(scale q_i . k_j - lse_i), which takes the rounding of the f32 lse out of P
+ * again (it matters at scaled scores of 1e4, where an ulp of lse is 1e-3).
+ *
+ * Refused before anything is enqueued (-1, nntk_last_error(), nothing written): everything the forward call refuses; a NULL d_out,
+ * d_lse, d_dout, gradient or workspace pointer; a grad_frame_stride below heads d_head; a tensor that is not 4-byte aligned; a gradient
+ * tensor or the workspace whose span overlaps an input's span, the workspace overlapping a gradient tensor, two gradient tensors whose
+ * slices share a float.  batch == 0 returns 0 without a device.
+ *
+ * Every element of d_dq, d_dk and d_dv is written by every call: the gradients of invalid queries, of keys beyond kv_lengths[b] and of
+ * keys that no valid query sees are exact zeros.  The rows that nothing sees are never read, whatever they hold, NaN included: those K
+ * and V rows, and the Q, out, lse and dout rows of invalid queries.  Two launches (per 128 rows), no atomics: every call returns the
+ * same bits.  One limit, as in the forward call: inf or NaN in a row that is seen reaches the gradients of the up to 32 queries or keys
+ * that share a wavefront with one that sees it.
+ *
+ * nntk_attention_backward is the host-pointer form: every tensor in host memory, no workspace argument. */
+size_t nntk_attention_backward_workspace_floats(int batch, int heads, int Tq);
+int nntk_attention_backward_device(const float *d_q, const float *d_k, const float *d_v, const float *d_out, const float *d_lse,
+                                   const float *d_dout, int batch, int heads, int d_head, int Tq, int Tk, long q_frame_stride,
+                                   long q_batch_stride, long k_frame_stride, long k_batch_stride, long v_frame_stride, long v_batch_stride,
+                                   const int *kv_lengths, int q_offset, int pos0, int chunk, int left, int right, float scale,
+                                   long grad_frame_stride, float *d_dq, float *d_dk, float *d_dv, float *d_workspace);
+int nntk_attention_backward(const float *q, const float *k, const float *v, const float *out, const float *lse, const float *dout, int batch,
+                            int heads, int d_head, int Tq, int Tk, long q_frame_stride, long q_batch_stride, long k_frame_stride,
+                            long k_batch_stride, long v_frame_stride, long v_batch_stride, const int *kv_lengths, int q_offset, int pos0,
+                            int chunk, int left, int right, float scale, long grad_frame_stride, float *dq, float *dk, float *dv);
+
 #ifdef __cplusplus
 }
 #endif

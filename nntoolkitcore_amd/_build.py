@@ -14,11 +14,12 @@ OBJ = os.path.join(PKG, "lib", "obj")
 LIB = os.path.join(PKG, "lib", "libnntoolkitcore_hip.so")
 
 HOST_SRC = ["runtime.c", "activation.c", "conv_1d.c", "recurrent.c", "dense.c", "spectrogram.c", "mel.c", "train.c", "ctc.c", "ngram_lm.c", "rnnt.c", "rnnt_decode.c", "rnnt_pred.c", "metrics.c", "attention.c"]
-HIP_SRC = ["runtime.hip", "conv1d.hip", "conv1d_s2.hip", "conv1d_flatk.hip", "recurrent.hip", "recurrent_rr.hip", "recurrent_fk.hip", "frag3.hip", "spectrogram.hip", "dist.hip", "conv1d_grad.hip", "train.hip", "ctc.hip", "ctc_beam.hip", "ctc_align.hip", "optim.hip", "bd_train.hip", "rnnt.hip", "rnnt_decode.hip", "rnnt_beam.hip", "rnnt_fused.hip", "rnnt_align.hip", "rnnt_pred.hip", "rnnt_pruned.hip", "edit_distance.hip", "rnnt_tdt.hip", "rnnt_tdt_decode.hip", "rnnt_tdt_align.hip", "rnnt_tdt_beam.hip", "rnnt_tdt_fused.hip", "attention.hip"]
+HIP_SRC = ["runtime.hip", "conv1d.hip", "conv1d_s2.hip", "conv1d_flatk.hip", "recurrent.hip", "recurrent_rr.hip", "recurrent_fk.hip", "frag3.hip", "spectrogram.hip", "dist.hip", "conv1d_grad.hip", "train.hip", "ctc.hip", "ctc_beam.hip", "ctc_align.hip", "optim.hip", "bd_train.hip", "rnnt.hip", "rnnt_decode.hip", "rnnt_beam.hip", "rnnt_fused.hip", "rnnt_align.hip", "rnnt_pred.hip", "rnnt_pruned.hip", "edit_distance.hip", "rnnt_tdt.hip", "rnnt_tdt_decode.hip", "rnnt_tdt_align.hip", "rnnt_tdt_beam.hip", "rnnt_tdt_fused.hip", "attention.hip", "attention_bwd.hip"]
 # flags of single units, after the common ones: the units written since keep the compiler from forming packed f32 operations
 _NO_PACKED_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 HIP_UNIT_FLAGS = {"rnnt_tdt.hip": _NO_PACKED_F32, "rnnt_tdt_decode.hip": _NO_PACKED_F32, "rnnt_tdt_align.hip": _NO_PACKED_F32,
-                  "rnnt_tdt_beam.hip": _NO_PACKED_F32, "rnnt_tdt_fused.hip": _NO_PACKED_F32, "attention.hip": _NO_PACKED_F32}
+                  "rnnt_tdt_beam.hip": _NO_PACKED_F32, "rnnt_tdt_fused.hip": _NO_PACKED_F32, "attention.hip": _NO_PACKED_F32,
+                  "attention_bwd.hip": _NO_PACKED_F32}
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = "gfx950"
 

@@ -498,6 +498,11 @@ SIGNATURES = {
                               [ip, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, vp, vp]),
     "nntk_attention": (C.c_int, [fp, fp, fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int] + [C.c_long] * 6 +
                        [ip, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, fp, fp]),
+    "nntk_attention_backward_workspace_floats": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "nntk_attention_backward_device": (C.c_int, [vp] * 6 + [C.c_int] * 5 + [C.c_long] * 6 +
+                                       [ip, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_long, vp, vp, vp, vp]),
+    "nntk_attention_backward": (C.c_int, [fp] * 6 + [C.c_int] * 5 + [C.c_long] * 6 +
+                                [ip, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_long, fp, fp, fp]),
     # RNN-Transducer: loss, gradient with respect to the scores, the joiner (INTEGRATION.md "RNN-Transducer: loss and joiner")
     "nntk_rnnt_workspace_floats": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "nntk_rnnt_loss_device": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, ip, ip, ip, C.c_int, C.c_int, vp, vp, vp]),

@@ -226,6 +226,14 @@ int nntk_shim_attention(const float *d_q, const float *d_k, const float *d_v, in
                         long q_frame_stride, long q_batch_stride, long k_frame_stride, long k_batch_stride, long v_frame_stride,
                         long v_batch_stride, const int *h_kv_lengths, int q_offset, int pos0, int chunk, int left, int right, float scale,
                         float *d_out, float *d_lse);
+/* its gradient (attention_bwd.hip): d_out / d_dout dense [batch][Tq][heads d_head], d_lse [batch][heads][Tq] as the forward wrote it;
+ * d_dq [batch][Tq] and d_dk / d_dv [batch][Tk] rows of heads d_head floats at grad_frame_stride; d_ws batch heads Tq floats (the inverse
+ * row sums of the recomputed P).  Two launches per 128 rows, the dq kernel (which writes d_ws) first. */
+int nntk_shim_attention_backward(const float *d_q, const float *d_k, const float *d_v, const float *d_out, const float *d_lse,
+                                 const float *d_dout, int batch, int heads, int d_head, int Tq, int Tk, long q_frame_stride,
+                                 long q_batch_stride, long k_frame_stride, long k_batch_stride, long v_frame_stride, long v_batch_stride,
+                                 const int *h_kv_lengths, int q_offset, int pos0, int chunk, int left, int right, float scale,
+                                 long grad_frame_stride, float *d_dq, float *d_dk, float *d_dv, float *d_ws);
 /* the transducer kernels' limits, stated here once for the host's checks (rnnt.c) and the launcher */
 #define NNTK_RNNT_MAX_LABELS 4000               /* max_label_len: two diagonals of max_label_len + 1 cells, 16 bytes each, live in LDS */
 #define NNTK_RNNT_MAX_DIAGONALS 65536           /* T + max_label_len: the exponents of that many emissions (each >= -4000) sum inside 2^28 */

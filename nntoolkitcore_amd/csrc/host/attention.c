@@ -5,6 +5,8 @@
 #include <math.h>
 #include <stdio.h>
 #include <stdint.h>
+#include <stdlib.h>
+#include <string.h>
 #include "nntk_internal.h"
 
 /* scratch for the host-pointer form: per thread and device, freed at thread exit (nntk_thread_scratch, runtime.c) */
@@ -113,4 +115,111 @@ int nntk_attention(const float *q, const float *k, const float *v, int batch, in
         return -1;
     if (nntk_shim_download(out, d_o, n_out * 4)) return -1;
     return lse ? nntk_shim_download(lse, d_o + n_out, n_lse * 4) : 0;
+}
+
+/* ---- the backward of the attention core (csrc/hip/attention_bwd.hip) ---- */
+
+size_t nntk_attention_backward_workspace_floats(int batch, int heads, int Tq) {
+    if (batch < 1 || heads < 1 || heads > NNTK_ATTENTION_MAX_HEADS || Tq < 1 || Tq > NNTK_ATTENTION_MAX_FRAMES) return 0;
+    return (size_t)batch * (size_t)heads * (size_t)Tq;
+}
+
+/* two tensors of hd-float slices on the same frame stride gfs (a fused gradient buffer): their slices share a float */
+static int att_slices_overlap(const float *a, size_t na, const float *b, size_t nb, long gfs, int hd) {
+    if (!att_overlap(a, na, b, nb)) return 0;
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+    const uintptr_t m = ((x > y ? x - y : y - x) / 4) % (uintptr_t)gfs;            /* the phase of one against the other's frames */
+    return m < (uintptr_t)hd || m > (uintptr_t)(gfs - hd);
+}
+
+/* the pointers of a backward call (ws == NULL with need_ws == 0: the host form), after att_check */
+static int att_bwd_check(const char *who, const float *q, const float *k, const float *v, const float *out, const float *lse,
+                         const float *dout, int batch, int heads, int d_head, int Tq, int Tk, long qfs, long qbs, long kfs, long kbs,
+                         long vfs, long vbs, long gfs, const float *dq, const float *dk, const float *dv, const float *ws, int need_ws) {
+    const int hd = heads * d_head;
+    if (!q || !k || !v || !out || !lse || !dout) return att_fail(who, "NULL input tensor (q, k, v, out, lse and dout are all needed)", 0, 0, 0);
+    if (!dq || !dk || !dv) return att_fail(who, "NULL gradient tensor", 0, 0, 0);
+    if (need_ws && !ws) return att_fail(who, "NULL workspace", 0, 0, 0);
+    if (gfs < hd || gfs > ATT_MAX_STRIDE) return att_fail(who, "grad_frame_stride %ld: at least heads * d_head = %ld floats, at most 2^40", gfs, hd, 0);
+    if (((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)out | (uintptr_t)lse | (uintptr_t)dout | (uintptr_t)dq | (uintptr_t)dk |
+         (uintptr_t)dv | (uintptr_t)ws) & 3)
+        return att_fail(who, "a tensor is not 4-byte aligned", 0, 0, 0);
+    const size_t n_out = (size_t)batch * Tq * hd, n_lse = (size_t)batch * heads * Tq;
+    const void *in[6] = {q, k, v, out, lse, dout};
+    const size_t n_in[6] = {att_span(batch, Tq, qfs, qbs, hd), att_span(batch, Tk, kfs, kbs, hd), att_span(batch, Tk, vfs, vbs, hd), n_out, n_lse, n_out};
+    const float *g[4] = {dq, dk, dv, ws};
+    const size_t n_g[4] = {att_span(batch, Tq, gfs, Tq * gfs, hd), att_span(batch, Tk, gfs, Tk * gfs, hd), att_span(batch, Tk, gfs, Tk * gfs, hd), n_lse};
+    for (int t = 0; t < 4; ++t)
+        for (int u = 0; u < 6; ++u)
+            if (att_overlap(g[t], n_g[t], in[u], n_in[u])) return att_fail(who, "a gradient tensor or the workspace overlaps an input", 0, 0, 0);
+    for (int t = 0; t < 3; ++t) {
+        if (att_overlap(g[t], n_g[t], ws, n_lse)) return att_fail(who, "a gradient tensor and the workspace overlap", 0, 0, 0);
+        for (int u = t + 1; u < 3; ++u)
+            if (att_slices_overlap(g[t], n_g[t], g[u], n_g[u], gfs, hd)) return att_fail(who, "two gradient tensors overlap", 0, 0, 0);
+    }
+    return 0;
+}
+
+int nntk_attention_backward_device(const float *d_q, const float *d_k, const float *d_v, const float *d_out, const float *d_lse,
+                                   const float *d_dout, int batch, int heads, int d_head, int Tq, int Tk, long q_frame_stride,
+                                   long q_batch_stride, long k_frame_stride, long k_batch_stride, long v_frame_stride, long v_batch_stride,
+                                   const int *kv_lengths, int q_offset, int pos0, int chunk, int left, int right, float scale,
+                                   long grad_frame_stride, float *d_dq, float *d_dk, float *d_dv, float *d_workspace) {
+    static const char who[] = "nntk_attention_backward_device";
+    nntk_shim_clear_error();
+    if (att_check(who, batch, heads, d_head, Tq, Tk, q_frame_stride, q_batch_stride, k_frame_stride, k_batch_stride, v_frame_stride,
+                  v_batch_stride, kv_lengths, q_offset, pos0, chunk, left, right, scale))
+        return -1;
+    if (batch == 0) return 0;
+    if (att_bwd_check(who, d_q, d_k, d_v, d_out, d_lse, d_dout, batch, heads, d_head, Tq, Tk, q_frame_stride, q_batch_stride, k_frame_stride,
+                      k_batch_stride, v_frame_stride, v_batch_stride, grad_frame_stride, d_dq, d_dk, d_dv, d_workspace, 1))
+        return -1;
+    return nntk_shim_attention_backward(d_q, d_k, d_v, d_out, d_lse, d_dout, batch, heads, d_head, Tq, Tk, q_frame_stride, q_batch_stride,
+                                        k_frame_stride, k_batch_stride, v_frame_stride, v_batch_stride, kv_lengths, q_offset, pos0, chunk,
+                                        left, right, scale, grad_frame_stride, d_dq, d_dk, d_dv, d_workspace);
+}
+
+/* rows of hd floats, packed at src, to a host tensor with frame stride gfs: the floats between the slices are not touched */
+static void att_scatter_rows(float *dst, const float *src, size_t rows, long gfs, int hd) {
+    for (size_t r = 0; r < rows; ++r) memcpy(dst + r * (size_t)gfs, src + r * (size_t)hd, (size_t)hd * 4);
+}
+
+int nntk_attention_backward(const float *q, const float *k, const float *v, const float *out, const float *lse, const float *dout, int batch,
+                            int heads, int d_head, int Tq, int Tk, long q_frame_stride, long q_batch_stride, long k_frame_stride,
+                            long k_batch_stride, long v_frame_stride, long v_batch_stride, const int *kv_lengths, int q_offset, int pos0,
+                            int chunk, int left, int right, float scale, long grad_frame_stride, float *dq, float *dk, float *dv) {
+    static const char who[] = "nntk_attention_backward";
+    nntk_shim_clear_error();
+    if (att_check(who, batch, heads, d_head, Tq, Tk, q_frame_stride, q_batch_stride, k_frame_stride, k_batch_stride, v_frame_stride,
+                  v_batch_stride, kv_lengths, q_offset, pos0, chunk, left, right, scale))
+        return -1;
+    if (batch == 0) return 0;
+    if (att_bwd_check(who, q, k, v, out, lse, dout, batch, heads, d_head, Tq, Tk, q_frame_stride, q_batch_stride, k_frame_stride,
+                      k_batch_stride, v_frame_stride, v_batch_stride, grad_frame_stride, dq, dk, dv, NULL, 0))
+        return -1;
+    const int hd = heads * d_head;
+    const size_t n_out = (size_t)batch * Tq * hd, n_kv = (size_t)batch * Tk * hd, n_lse = (size_t)batch * heads * Tq;
+    const size_t nq = att_span(batch, Tq, q_frame_stride, q_batch_stride, hd), nk = att_span(batch, Tk, k_frame_stride, k_batch_stride, hd),
+                 nv = att_span(batch, Tk, v_frame_stride, v_batch_stride, hd);
+    float *d_in = nntk_devbuf_reserve(&t_a, nq + nk + nv + 2 * n_out + n_lse);         /* q | k | v | out | dout | lse */
+    float *d_g = nntk_devbuf_reserve(&t_b, n_out + 2 * n_kv + n_lse);                  /* dq | dk | dv, dense, | workspace */
+    if (!d_in || !d_g) return -1;
+    float *d_k = d_in + nq, *d_v = d_k + nk, *d_o = d_v + nv, *d_do = d_o + n_out, *d_l = d_do + n_out;
+    if (nntk_shim_upload(d_in, q, nq * 4) || nntk_shim_upload(d_k, k, nk * 4) || nntk_shim_upload(d_v, v, nv * 4) ||
+        nntk_shim_upload(d_o, out, n_out * 4) || nntk_shim_upload(d_do, dout, n_out * 4) || nntk_shim_upload(d_l, lse, n_lse * 4))
+        return -1;
+    if (nntk_attention_backward_device(d_in, d_k, d_v, d_o, d_l, d_do, batch, heads, d_head, Tq, Tk, q_frame_stride, q_batch_stride,
+                                       k_frame_stride, k_batch_stride, v_frame_stride, v_batch_stride, kv_lengths, q_offset, pos0, chunk, left,
+                                       right, scale, hd, d_g, d_g + n_out, d_g + n_out + n_kv, d_g + n_out + 2 * n_kv))
+        return -1;
+    float *stage = malloc((n_out + 2 * n_kv) * 4);
+    if (!stage) return att_fail(who, "out of host memory", 0, 0, 0);
+    const int rc = nntk_shim_download(stage, d_g, (n_out + 2 * n_kv) * 4);
+    if (!rc) {
+        att_scatter_rows(dq, stage, (size_t)batch * Tq, grad_frame_stride, hd);
+        att_scatter_rows(dk, stage + n_out, (size_t)batch * Tk, grad_frame_stride, hd);
+        att_scatter_rows(dv, stage + n_out + n_kv, (size_t)batch * Tk, grad_frame_stride, hd);
+    }
+    free(stage);
+    return rc;
 }

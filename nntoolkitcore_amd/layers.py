@@ -1094,7 +1094,55 @@ def attention(q, k, v, heads, kv_lengths=None, q_offset=0, pos0=0, chunk=1, left
     return out, lse
 
 
-RNNT_ACTIVATIONS = {ACT_IDENTITY: 0, ACT_TANH: 1, ACT_RELU: 2}
+def attention_backward_device(q, k, v, out, lse, dout, heads, kv_lengths=None, q_offset=0, pos0=0, chunk=1, left=-1, right=-1, scale=None,
+                              dq=None, dk=None, dv=None, workspace=None):
+    """``nntk_attention_backward_device``: the gradients of ``attention_device`` with respect to q, k and v.  q, k, v and the mask
+    arguments as in the forward call; out [B, Tq, heads * d_head] and lse [B, heads, Tq] are what it returned, dout is the gradient
+    with respect to out (all three contiguous).  dq [B, Tq, heads * d_head] and dk / dv [B, Tk, heads * d_head] may be strided views
+    of one buffer that share their frame stride (a fused [B, T, 3 * heads * d_head] gradient); what lies between them is not touched.
+    No gradient flows into lse.  workspace: B * heads * Tq floats.  Returns (dq, dk, dv)."""
+    import torch
+    dims, kl, scale = _attention_args(q, k, v, heads, kv_lengths, scale)
+    B, _, _, Tq, Tk = dims
+    HD = q.shape[2]
+    strides = []
+    for t in (q, k, v):
+        assert t.is_cuda and t.dtype == torch.float32 and (t.stride(2) == 1 or t.shape[2] == 1), "float32 device tensors, unit stride in the last dimension"
+        strides += [t.stride(1) if t.shape[1] > 1 else max(t.stride(1), t.shape[2]), t.stride(0)]
+    for t, shape in ((out, (B, Tq, HD)), (dout, (B, Tq, HD)), (lse, (B, heads, Tq))):
+        assert t.is_cuda and t.dtype == torch.float32 and tuple(t.shape) == shape and t.is_contiguous(), "out, dout [B, Tq, heads * d_head] and lse [B, heads, Tq]: contiguous float32 device tensors"
+    grads = [torch.empty((B, T, HD), dtype=torch.float32, device=q.device) if g is None else g for g, T in ((dq, Tq), (dk, Tk), (dv, Tk))]
+    # a one-frame view: torch's frame stride is arbitrary, the batch stride is the frame stride
+    gfs = max([HD] + [g.stride(1) if g.shape[1] > 1 else g.stride(0) for g in grads if g.shape[1] > 1 or B > 1])
+    for g, T in zip(grads, (Tq, Tk, Tk)):
+        assert g.is_cuda and g.dtype == torch.float32 and tuple(g.shape) == (B, T, HD) and (g.stride(2) == 1 or HD == 1) and \
+            (T == 1 or g.stride(1) == gfs) and (B == 1 or g.stride(0) == T * gfs), \
+            "dq [B, Tq, heads * d_head], dk / dv [B, Tk, heads * d_head]: one frame stride for all three, batch stride T * frame stride"
+    if workspace is None:
+        workspace = torch.empty(B * heads * Tq, dtype=torch.float32, device=q.device)
+    assert workspace.numel() >= B * heads * Tq, "workspace: B * heads * Tq floats"
+    check(capi.load().nntk_attention_backward_device(*(C.c_void_p(t.data_ptr()) for t in (q, k, v, out, lse, dout)), *dims, *strides,
+                                                     kl.ctypes.data_as(capi.ip) if kl is not None else None, q_offset, pos0, chunk, left,
+                                                     right, C.c_float(scale), gfs, *(C.c_void_p(g.data_ptr()) for g in grads), _dp(workspace)),
+          "nntk_attention_backward_device")
+    return tuple(grads)
+
+
+def attention_backward(q, k, v, out, lse, dout, heads, kv_lengths=None, q_offset=0, pos0=0, chunk=1, left=-1, right=-1, scale=None):
+    """The host-memory form (``nntk_attention_backward``) on numpy arrays; returns (dq, dk, dv)."""
+    q, k, v, out, lse, dout = (_f32(x) for x in (q, k, v, out, lse, dout))
+    dims, kl, scale = _attention_args(q, k, v, heads, kv_lengths, scale)
+    B, _, _, Tq, Tk = dims
+    HD = q.shape[2]
+    assert out.shape == (B, Tq, HD) and dout.shape == (B, Tq, HD) and lse.shape == (B, heads, Tq), "out, dout [B, Tq, heads * d_head], lse [B, heads, Tq]"
+    dq, dk, dv = (np.empty((B, T, HD), np.float32) for T in (Tq, Tk, Tk))
+    check(capi.load().nntk_attention_backward(_p(q), _p(k), _p(v), _p(out), _p(lse), _p(dout), *dims, HD, Tq * HD, HD, Tk * HD, HD, Tk * HD,
+                                              kl.ctypes.data_as(capi.ip) if kl is not None else None, q_offset, pos0, chunk, left, right,
+                                              C.c_float(scale), HD, _p(dq), _p(dk), _p(dv)), "nntk_attention_backward")
+    return dq, dk, dv
+
+
+RNNT_ACTIVATIONS ={ACT_IDENTITY: 0, ACT_TANH: 1, ACT_RELU: 2}
 
 
 def _rnnt_labels(labels, label_lengths, B, maxL):
